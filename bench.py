@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the I_ea predict hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one resident batch of synthetic clips: raw 16 kHz + 22.05 kHz waveforms ->
 masked log-mel front-end; masked 16 kHz waveform -> HuBERT-base encoder -> LN+Linear head -> codeword arg-max + mel
@@ -19,8 +19,15 @@ the same JSON line: "bf16x3_vocoder" (every fp32 operand split into bf16 hi + lo
 RMS, fp32-equivalent) and "fp32_vocoder" (exact fp32 MFMA), and `vocoder_check` holds the live RMS difference between
 the headline waveform and the fp32 leg's.
 
-Prints ONE JSON line on rank 0 (metric/value/... plus `roofline` for the dominant kernel family, measured with HIP
-events inside the timed region, and `cpu_baseline`: the CPU oracle timed on this host's cores on a bounded sample).
+A plain run sets up, warms up, times the K steps of the headline leg and prints ONE JSON line on rank 0 (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...).  Everything else is measured only with --full: the per-kernel-family
+table and `roofline` for the dominant kernel family (HIP events in the warm-up and the timed region), the bf16x3 / fp32
+vocoder legs, the configs[3] / configs[4] / end-to-end legs and `cpu_baseline` (the CPU oracle timed on this host's
+cores on a bounded sample).
+
+--dump-outputs DIR writes what the headline step returned in its last timed step (predict_batch's `feats`, `labels`,
+`mel`, `wave`; rank 0's clips) as DIR/<name>.npy in float32 / float64.  Inputs and weights are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -46,6 +53,7 @@ MFMA_PER_PRODUCT = {"f32": 1, "bf16": 1, "bf16x3": 3, "f16": 1}
 # nominal peak, never instead of it.
 SUSTAINED_MFMA_TFLOPS = {"bf16": 1820.0, "f16": 1820.0, "bf16x3": 1820.0}
 PEAK_HBM_GBS = 8000.0                                             # MI355X_MICROARCH.md: HBM3E ~8 TB/s
+DUMP_BUDGET_BYTES = 64 << 20                                      # --dump-outputs: at most this much in all
 
 
 def log(*a):
@@ -185,6 +193,35 @@ def roofline_of(prof, steps, table=None, table_steps=0):
     roof["events"] = ("timed steps: this family only; per-family table: warm-up steps, every launch bracketed" if table
                       else "timed steps: every launch bracketed")
     return roof, fams, tot
+
+
+def host_outputs(out):
+    """The step's output dict -> {name: host numpy array}: floating tensors as float32, integer ones as float64 (exact)."""
+    arrs = {}
+    for name in sorted(out):
+        v = out[name]
+        if not torch.is_tensor(v):
+            continue
+        v = v.detach().cpu()
+        arrs[name] = (v.float() if v.is_floating_point() else v.double()).numpy()
+    return arrs
+
+
+def dump_outputs(arrs, path):
+    """Write `arrs` as path/<name>.npy.  Over DUMP_BUDGET_BYTES, a fixed seeded sample of clips (the leading axis, shared
+    by every output) is written instead, and its indices as path/clip_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BUDGET_BYTES:
+        n = min(a.shape[0] for a in arrs.values())
+        keep = max(1, int(n * DUMP_BUDGET_BYTES / total))
+        idx = np.sort(np.random.default_rng(1234).choice(n, keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["clip_index"] = idx.astype(np.float64)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    log(f"[bench] outputs of the last timed step written to {path}: " + ", ".join(f"{k} {tuple(a.shape)}" for k, a in arrs.items()))
 
 
 def spawn_ranks(n: int) -> int:
@@ -415,13 +452,20 @@ def main():
     ap.add_argument("--encoder-dtype", default="bf16", choices=["fp32", "bf16", "bf16x3"])
     ap.add_argument("--vocoder-dtype", default="fp16", choices=["fp32", "bf16", "bf16x3", "fp16"])
     ap.add_argument("--vocoder-chunk", type=int, default=0)
-    ap.add_argument("--cpu-clips", type=int, default=8, help="clips timed on the CPU oracle (0 = skip)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket launches with HIP events")
-    ap.add_argument("--no-fp32-leg", action="store_true", help="skip the secondary exact-fp32-vocoder leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel HIP-event table and roofline, the bf16x3 / fp32 "
+                         "vocoder legs, the configs[3] / configs[4] / end-to-end legs, the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-clips", type=int, default=8, help="with --full: clips timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: do not bracket launches with HIP events")
+    ap.add_argument("--no-fp32-leg", action="store_true", help="with --full: skip the bf16x3 / exact-fp32 vocoder legs")
     ap.add_argument("--graph-leg", action="store_true", help="also replay the step as one hipGraph (informational)")
-    ap.add_argument("--no-config-legs", action="store_true", help="skip the configs[3] / configs[4] legs (extra keys of the JSON line)")
+    ap.add_argument("--no-config-legs", action="store_true", help="with --full: skip the configs[3] / configs[4] legs (extra keys of the JSON line)")
     ap.add_argument("--only-config-legs", action="store_true", help="diagnostic: run ONLY the configs[3] / configs[4] legs and print them")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks as FRESH child processes and relay rank 0's JSON
@@ -472,7 +516,7 @@ def main():
     s22 = (pos * 320 * 22050 // 16000).to(torch.int32)                       # I_ea/predict.py:99-100
     e22 = ((pos + MASK_FRAMES) * 320 * 22050 // 16000).to(torch.int32)
 
-    def run_mode(enc, voc, steps, warmup, events, graph_leg=False):
+    def run_mode(enc, voc, steps, warmup, events, graph_leg=False, keep_outputs=False):
         t_load = time.perf_counter()
         eng = parallel.setup_engine(lambda: InpaintingEngine(harch, varch, K, dev, enc, voc, a.vocoder_chunk), checkpoint, rank)
         torch.cuda.synchronize()
@@ -512,6 +556,7 @@ def main():
         parallel.barrier()
         elapsed = time.perf_counter() - t0
         prof = eng.ctx.profile_stop() if events else []
+        outputs = host_outputs(out) if keep_outputs and rank == 0 else None       # the last timed step's, before anything else runs
         # extra, informational: the same step replayed as ONE hipGraph (no per-launch host work, no HIP events) -- what the
         # ~230 dependent launches of a step cost in gaps.  Never `value`: the contract's roofline needs events in the timed region.
         graph_ms = None
@@ -548,14 +593,17 @@ def main():
         if not bool(stats[:, 3].min()):
             raise SystemExit("non-finite samples in the output waveform")
         return dict(elapsed=elapsed_max, clips=clips, clips_slowest_rank=clips_slowest, rms=float(stats[0, 2]), prof=prof, steps=steps, prof_warm=prof_warm, graph_ms=graph_ms,
-                    warm_steps=warm_steps,
+                    warm_steps=warm_steps, outputs=outputs,
                     wave=wav if rank == 0 else None, labels=out["labels"] if rank == 0 else None)
 
-    events = not a.no_kernel_events
-    main_run = run_mode(a.encoder_dtype, a.vocoder_dtype, a.steps, a.warmup, events, graph_leg=a.graph_leg)
+    events = a.full and not a.no_kernel_events
+    main_run = run_mode(a.encoder_dtype, a.vocoder_dtype, a.steps, a.warmup, events, graph_leg=a.graph_leg,
+                        keep_outputs=a.dump_outputs is not None)
+    if main_run["outputs"] is not None:
+        dump_outputs(main_run["outputs"], a.dump_outputs)
     # reference legs on the same inputs: the fp32-equivalent split mode and exact fp32 (fewer steps; reported, not `value`)
     legs = {}
-    if not a.no_fp32_leg:
+    if a.full and not a.no_fp32_leg:
         for voc in ("bf16x3", "fp32"):
             if voc != a.vocoder_dtype:
                 legs[voc] = run_mode(a.encoder_dtype, voc, max(2, a.steps // 3), 2, events)
@@ -625,7 +673,7 @@ def main():
             "fp32_leg_waveform_rms": float(ref.pow(2).mean().sqrt()),
             "labels_identical": bool(torch.equal(main_run["labels"], legs["fp32"]["labels"])),
             "gate": "north star: waveform RMS error <= 1e-3 (fp32 waveform)"}
-    if world == 1 and not a.no_config_legs:
+    if a.full and world == 1 and not a.no_config_legs:
         # the other single-GPU configurations of BASELINE.json, each with its own roofline object; `value` above stays configs[1]
         try:
             res["configs4"] = leg_configs4(dev, a.encoder_dtype, a.vocoder_dtype, max(3, a.steps // 2))
@@ -640,7 +688,7 @@ def main():
         except Exception as ex:
             res["config_legs_error"] = repr(ex)
             log(f"[bench] configs[3] / configs[4] legs failed: {ex!r}")
-    if world == 1 and a.cpu_clips > 0:
+    if a.full and world == 1 and a.cpu_clips > 0:
         try:
             res["cpu_baseline"] = cpu_baseline(a.cpu_clips)
         except Exception as ex:     # the oracle is a checker; its absence must not void the GPU number

@@ -72,7 +72,7 @@ def test_bench_two_rank_rehearsal_prints_the_contract_line():
     os.environ["SI_DIST_BACKEND"] = "gloo"
     try:
         p = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--no-fp32-leg", "--cpu-clips", "0"])
+                        "--full", "--no-fp32-leg", "--cpu-clips", "0"])
     finally:
         if env_backend is None:
             os.environ.pop("SI_DIST_BACKEND", None)

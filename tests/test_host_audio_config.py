@@ -9,7 +9,7 @@ from oracle import ref_cpu as R
 from speech_inpainting_amd import audio, config
 from speech_inpainting_amd.arch import mel_frames
 
-REF_YAML = "/root/reference/I_ea/predict.yaml"
+REF_YAML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "iea_predict.yaml")   # the reference's I_ea/predict.yaml
 
 
 def _yaml_text():
@@ -36,7 +36,6 @@ def test_predict_yaml_schema(tmp_path):
     assert c.hubert_type == "base" and c.device_index == 0
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference tree not present")
 def test_reference_predict_yaml_loads():
     c = config.load_predict_config(REF_YAML)
     assert c.hubert_type == "large" and c.n_clusters == 100 and c.mask_frames == 20

@@ -5,7 +5,7 @@ grep "B=\|saturated\|passed" gpurun_out/chain_t.log
 out=gpurun_out/chain_ab.txt; : > $out
 for rep in 1 2; do for v in 0 1; do
   echo "== SI_VOC_CHAIN=$v" >> $out
-  SI_VOC_CHAIN=$v python3 bench.py --steps 10 --warmup 3 --cpu-clips 0 --no-fp32-leg > /tmp/b.json 2> /tmp/b.err || { tail -5 /tmp/b.err; exit 1; }
+  SI_VOC_CHAIN=$v python3 bench.py --full --steps 10 --warmup 3 --cpu-clips 0 --no-fp32-leg > /tmp/b.json 2> /tmp/b.err || { tail -5 /tmp/b.err; exit 1; }
   grep -o '"ms_per_step": [0-9.]*' /tmp/b.json | sed -n 1p >> $out
   grep -i "respair_f16_c32\|reschain\|respair_f16_c64" /tmp/b.err >> $out
 done; done

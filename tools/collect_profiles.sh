@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/ps /tmp/pf /tmp/pw /tmp/pc
 # (--no-config-legs: the configs[3] / configs[4] legs launch the same kernel instantiations on other shapes and would dilute the
 #  per-kernel averages that roofline.avg_launch_ms is checked against; they get their own pass below)
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps -- python3 $root/bench.py --steps 5 --warmup 2 --cpu-clips 0 --no-config-legs > $out/${tag}_bench.json 2> $out/${tag}_bench_stderr.txt || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps -- python3 $root/bench.py --full --steps 5 --warmup 2 --cpu-clips 0 --no-config-legs > $out/${tag}_bench.json 2> $out/${tag}_bench_stderr.txt || exit 1
 cp /tmp/ps/*/*_kernel_stats.csv $out/${tag}_kernel_stats.csv
 cp /tmp/ps/*/*_agent_info.csv $out/${tag}_agent_info.csv
 rm -rf /tmp/pl
