@@ -87,7 +87,6 @@ struct si_ctx {
     int opt_ffn_pad = 64;                    // elements of padding behind each row of the bf16 FFN intermediate (SI_ENC_FFNPAD; multiple of 8, <= 128):
                                              // rows 6144 bytes apart are 6272 apart instead -- FFN2 -1.5 % (profiles/r04_ffnpad_ab.txt), same values
     int opt_gemmcu = 1;                      // encoder GEMMs as one tile per CU (gemmcu.hip): 0 never, 1 by the shape rule, 2 whenever the shape allows, 10 + c (A/B)
-    int opt_gemm256 = 1;                     // encoder GEMMs on 256 x 256 tiles: 0 never, 1 by the shape rule, 2 whenever the shape allows (tests)
     int opt_voc_chain = 1;                   // whole-resblock kernel on the C = 32 stage (SI_VOC_CHAIN=0: one launch per conv pair)
     int opt_voc_fuse = 1;                    // 0: never, 1: every covered width, otherwise a mask of the channel counts to fuse (32 | 64 | 128 | 256)
     // constant tables of the mel front-end (built on first use): DFT matrix [Npad][n_fft] = rows cos | -sin, periodic
@@ -161,7 +160,6 @@ int si_ensure_dyn_lds(si_ctx* ctx, const void* kern, size_t bytes) {
     }
     return SI_OK;
 }
-int si_opt_gemm256(const si_ctx* ctx) { return ctx->opt_gemm256; }
 int si_opt_gemmcu(const si_ctx* ctx) { return ctx->opt_gemmcu; }
 int si_num_cus(si_ctx* ctx) {
     if (ctx->num_cus <= 0) {
@@ -694,7 +692,6 @@ int si_create(si_ctx** out, int device_id, const si_model_desc* desc) {
     ctx->opt_att_bf16 = env_flag("SI_ATT_BF16");
     ctx->opt_enc_lingemm = env_flag("SI_ENC_LINGEMM");
     ctx->opt_enc_posconv = env_flag("SI_ENC_POSCONV");
-    ctx->opt_gemm256 = getenv("SI_ENC_GEMM256") ? atoi(getenv("SI_ENC_GEMM256")) : 1;
     ctx->opt_gemmcu = getenv("SI_ENC_GEMMCU") ? atoi(getenv("SI_ENC_GEMMCU")) : 1;
     ctx->opt_ln_fuse = getenv("SI_ENC_LNFUSE") ? atoi(getenv("SI_ENC_LNFUSE")) : 1;
     ctx->opt_voc_upsgemm = getenv("SI_VOC_UPSGEMM") ? atoi(getenv("SI_VOC_UPSGEMM")) : 1;
@@ -930,7 +927,7 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     // layer-norm flavour (HuBERT-large) in bf16 mode: every conv is followed by LayerNorm + GELU over its 512 channels; the
     // LayerNorm writes ONLY the bf16 operand of the next conv (the rounding that conv would apply while staging), into the
     // other buffer (its bf16 rows would overlap unread fp32 rows of its own input), so that the convolutions run on the
-    // dedicated bf16 GEMM kernels (lingemm / gemm256) like the group-norm flavour's; the last one writes the fp32 features.
+    // dedicated bf16 GEMM kernels (gemmcu / lingemm) like the group-norm flavour's; the last one writes the fp32 features.
     const bool l16 = ctx->opt_enc_opready && d.encoder_math == SI_MATH_BF16 && d.feat_norm_layer && d.num_conv >= 2;
     if (!d.feat_norm_layer) {
         // group-norm flavour in bf16 mode: the conv chain runs on operand-ready bf16 activations (conv0 and convs 1..n-2

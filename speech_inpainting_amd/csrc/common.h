@@ -146,7 +146,6 @@ struct LinGemmParams {
     int ldo; long o_seg_stride;
     int act;
     int xcd_rows;                               // set by the launcher: > 0 = XCD-aware tile order over this many row blocks
-    int persistent;                             // set by the launcher (gemm256): workgroups walk tiles slot, slot + grid / 8, ... of their XCD's list
     // ragged batches: segment s holds seg_m[s] output rows (device int32 (nseg); NULL: M for all); seg_m_host = the same on the host
     const int32_t* seg_m;
     const int32_t* seg_m_host;
@@ -157,12 +156,8 @@ struct LinGemmParams {
     const int32_t* tc_seg_lin; const int32_t* tc_seg_orows; int tc_olim_mul;   // ragged batches: segment s reads tc_seg_lin[s] rows, keeps [0, tc_seg_orows[s] * tc_olim_mul)
 };
 int si_launch_lingemm(si_ctx* ctx, const LinGemmParams& p, hipStream_t st);
-// The same contract on 256 x 256 tiles with LDS-DMA staging (gemm256.hip), for the shapes whose tiles fill the chip; returns 1 otherwise.
-int si_launch_gemm256(si_ctx* ctx, const LinGemmParams& p, hipStream_t st);
-int si_opt_gemm256(const si_ctx* ctx);      // SI_ENC_GEMM256: 0 never, 1 by the shape rule (default), 2 whenever the shape allows
-
-// The same contract as ONE tile per CU (gemmcu.hip: 16 waves, tile shape per instantiation), for the flat M = B * T GEMMs of the
-// transformer whose tiles then number at most the CUs; returns 1 otherwise.  Bit-identical to the other two.
+// The same contract as ONE tile per CU and round (gemmcu.hip: 8 or 16 waves, tile shape per instantiation), for the shapes whose
+// tiles fill whole rounds of the CUs; returns 1 otherwise.  Bit-identical to lingemm.hip.
 int si_launch_gemmcu(si_ctx* ctx, const LinGemmParams& p, hipStream_t st);
 // The generator's early upsamplers on the fp16 stream as the same kernel (TapGemmParams of a ConvTranspose1d in its two-tap form);
 // SI_OK when launched, negative on error, 1 when the shape is not covered (the caller uses the tap-GEMM).
@@ -286,7 +281,7 @@ int si_launch_resample_sinc(si_ctx* ctx, const float* x, const int32_t* n_len, i
 // `audio * 32768` + truncating int16 cast (I_ea/predict.py:204-206)
 int si_launch_pcm16(si_ctx* ctx, const float* wav, long n, int16_t* out, hipStream_t st);
 
-// erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemm256.hip: the SAME function, their results are bit-identical).
+// erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16
 // rounding every consumer of these outputs applies; 15 VALU operations instead of libm erff's ~31 with two divergent branches.
 __device__ __forceinline__ float si_gelu_fast(float x) {

@@ -2,28 +2,28 @@
 //
 //     out[seg][m][n] = epi( sum_k A[seg][m][k] * W[n][k] + bias[n] )        (the contract of lingemm.hip: LinGemmParams)
 //
-// Why a third kernel.  The transformer's GEMMs at the bench shape have M = B * T = 6368 rows (modeling_hubert.py:347-404: q|k|v,
+// Why a second kernel.  The transformer's GEMMs at the bench shape have M = B * T = 6368 rows (modeling_hubert.py:347-404: q|k|v,
 // out-proj, FFN1, FFN2): a launch is ONE round of the chip whatever the tile, and what a CU then pays is the operand bytes its
 // tiles draw through its L1 -- lingemm's two resident 96 x 128 tiles per CU draw 2 x (96 + 128) rows x K x 2 bytes: FFN2 (K = 3072)
 // 2.75 MB per CU in 54 us = 50 GB/s, the rate of the vector-memory path measured in profiles/r03_lingemm_pmc.txt.  The bytes per CU
 // are smallest when a CU's whole share of the output is ONE near-square tile: M * N / 256 outputs per CU is 276 x 276 for FFN1 and
-// 138 x 138 for FFN2 / out-proj.  256 x 256 tiles (gemm256.hip) leave those shapes at 300 (1.17 rounds) and 75 tiles; this kernel
+// 138 x 138 for FFN2 / out-proj.  Fixed 256 x 256 tiles would leave those shapes at 300 (1.17 rounds) and 75 tiles; this kernel
 // takes the tile shape as a template parameter and the launcher picks, per shape, among the instantiations whose tiles fill whole
 // rounds of the CUs, the one that draws the fewest bytes: 320 x 256 (FFN1: 20 x 12 = 240 tiles; conv1 as per-clip segments: 1280 =
 // 5.0 rounds), 256 x 256 (QKV: 225), 160 x 128 (N = 768: 40 x 6 = 240), 208 x 256 / 224 x 128 / 128 x 128 (conv3-6, HuBERT-large).
 //
 // Structure.  NW waves (16 for the 320- and 256-row tiles, 8 for the others) as WM (M) x WN (N); a wave owns (16 MT) x (16 NT)
 // outputs; one workgroup per CU.  Four waves per SIMD (<= 128 registers each) let the hardware interleave one wave's fragment reads
-// with its neighbours' MFMAs -- no hand-made partner schedule as in gemm256.hip, whose 8 waves hold a whole K-tile's fragments.
+// with its neighbours' MFMAs -- no hand-made partner schedule between wave groups is needed.
 // K-tiles of 64 (whole 128-byte lines of every operand row) arrive by LDS-DMA (buffer_load_dwordx4 ... lds, the XOR swizzle of
 // lingemm.hip applied on the source side) into a ring of NS stages of (BM + BN) x 128 bytes; iteration t = [counted vmcnt: own
 // pieces of K-tile t landed | barrier: everyone's landed, everyone done reading K-tile t - 1 | request K-tile t + NS - 1 into the
 // stage K-tile t - 1 occupied | 2 k-steps of MT x NT MFMAs, one A fragment at a time with the next one's read issued under the
-// current one's MFMAs].  One barrier per K-tile.  Epilogue from the accumulators (bias, fast erf-GELU, residual; bf16 through the
-// half trade of gemm256.hip).  What bounds it -- the CU's own load path at ~47 GB/s, whatever the tile, wave count or ring depth --
+// current one's MFMAs].  One barrier per K-tile.  Epilogue from the accumulators (bias, fast erf-GELU, residual; bf16 through a
+// half trade between lanes l and l + 16).  What bounds it -- the CU's own load path at ~47 GB/s, whatever the tile, wave count or ring depth --
 // and everything that was tried against that: DESIGN.md 4.1e, profiles/r04_gemmcu_ab.txt.
 //
-// BIT-IDENTICAL to lingemm.hip and gemm256.hip: every output's sum runs over K in steps of 32 through the same MFMA with the same
+// BIT-IDENTICAL to lingemm.hip: every output's sum runs over K in steps of 32 through the same MFMA with the same
 // operand roles (D^T = W A^T) and the same epilogue arithmetic, so the launcher may choose by shape and batch size without a clip's
 // result depending on it (tests/test_gpu_respair.py::test_gemmcu_*).
 #include <algorithm>
@@ -102,7 +102,8 @@ __global__ __launch_bounds__(NW * 64) void gemmcu_kernel(const LinGemmParams p) 
     const int wr = wave / WN, wc = wave % WN;
     const int r16 = lane & 15, kg = lane >> 4;
 
-    // tile walk: row-block-major order cut into 8 contiguous runs, one per XCD (workgroup ids b and b + 8 share an L2), as gemm256.hip
+    // tile walk: row-block-major order cut into 8 contiguous, equally long runs, one per XCD (workgroup ids b and b + 8 share an L2):
+    // a row block's A rows are fetched into one L2 (two at a seam), and no XCD gets more tiles than another
     const int ntn = p.N / BN;
     const int mtiles = (p.M + BM - 1) / BM;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -345,9 +346,9 @@ static int gemmcu_launch(si_ctx* ctx, const LinGemmParams& p, hipStream_t st, do
     return SI_OK;
 }
 
-// SI_OK when launched, negative on error, 1 when the shape is not covered or the rule leaves it to the other kernels.
+// SI_OK when launched, negative on error, 1 when the shape is not covered or the rule leaves it to lingemm.hip.
 // SI_ENC_GEMMCU: 0 never; 1 (default) by the rule below; 2 every shape an instantiation covers (the bit-identity tests);
-// 10 + c: instantiation c wherever it covers the shape (A/B runs).
+// 10 + c: instantiation c wherever it covers the shape (A/B runs; no instantiation c is an error).
 int si_launch_gemmcu(si_ctx* ctx, const LinGemmParams& p, hipStream_t st) {
     const int opt = si_opt_gemmcu(ctx);
     if (opt == 0) return 1;
@@ -362,7 +363,8 @@ int si_launch_gemmcu(si_ctx* ctx, const LinGemmParams& p, hipStream_t st) {
     int pick = -1;
     if (opt >= 10) {
         pick = opt - 10;
-        if (pick >= k_ncfg || p.N % k_cfgs[pick].bn) return 1;
+        if (pick >= k_ncfg) return si_fail(ctx, SI_EINVAL, "gemmcu: SI_ENC_GEMMCU=%d names no instantiation (10 ... %d)", opt, 10 + k_ncfg - 1);
+        if (p.N % k_cfgs[pick].bn) return 1;
     } else {
         // Whole rounds of the chip: among the instantiations whose tiles fill their rounds -- tiles / (rounds x CUs) >= 0.6 for one
         // round (below that the 128-row kernels' two workgroups per CU spread the same bytes over more L1s: HuBERT-large's N = 1024
@@ -371,6 +373,7 @@ int si_launch_gemmcu(si_ctx* ctx, const LinGemmParams& p, hipStream_t st) {
         // convolutions are several rounds (conv1: 1280 tiles of 320 x 256 = 5.0 rounds, against 6.25 of 256 x 256); the
         // transformer's GEMMs one.  opt == 2 drops the conditions.
         double best = 1e30;
+        bool fills_256 = false;                                        // (the fallback below)
         for (int c = 0; c < k_nrule; ++c) {
             if (p.N % k_cfgs[c].bn) continue;
             const long rb = p.seg_m_host ? si_vl_tiles(p.seg_m_host, p.nseg, k_cfgs[c].bm) : (long)p.nseg * ((p.M + k_cfgs[c].bm - 1) / k_cfgs[c].bm);
@@ -378,10 +381,16 @@ int si_launch_gemmcu(si_ctx* ctx, const LinGemmParams& p, hipStream_t st) {
             const long tiles = rb * (p.N / k_cfgs[c].bn);
             const long rounds = (tiles + cus - 1) / cus;
             const double fill = (double)tiles / (double)(rounds * cus);
+            if (c == 1) fills_256 = p.K >= 128 && fill * rows_real / ((double)rb * k_cfgs[c].bm) >= 0.72;
             if (opt == 1 && (fill < (rounds == 1 ? 0.6 : 0.75) || rows_real < 0.75 * (double)rb * k_cfgs[c].bm)) continue;
             const double cost = (double)rounds * (k_cfgs[c].bm + k_cfgs[c].bn);
             if (cost < best) { best = cost; pick = c; }
         }
+        // Last resort: a shape the conditions leave whose 256 x 256 tiles still fill >= 0.72 of their rounds with real rows (fill x
+        // rows; a sliver with fill or rows in [0.72, 0.75)) takes that instantiation, not the 128-row kernel -- the rule of the
+        // persistent 256 x 256 kernel it replaced after beating it on every shape both covered (QKV 37.1 -> 30.2 us, conv3
+        // 105 -> 99, conv4 58.7 -> 53.2: profiles/r04_gemmcu_ab.txt).
+        if (pick < 0 && opt == 1 && fills_256) pick = 1;
         if (pick < 0) return 1;
     }
     switch (pick) {

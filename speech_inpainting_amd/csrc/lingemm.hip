@@ -32,10 +32,10 @@
 // Two experiments confirmed it: a form with the A operand fetched straight into registers in the MFMA layout (half the LDS
 // staging, a three-deep W ring, the fragments of the next chunk requested before the barrier, the epilogue from the
 // accumulators) and a 13-operation erf instead of libm's erff in the epilogue both left every shape's time unchanged
-// within 2 %.  The lever is bytes per flop: gemm256.hip (256 x 256 tiles, 7.8 KB per MFLOP) takes the shapes whose tiles fill
-// the chip; this kernel keeps the rest.  Both order every output's sum identically (K in steps of 32, the same MFMA with the
-// same operand roles, the same epilogue arithmetic), so their results are BIT-IDENTICAL and the choice between them may
-// depend on the batch size without a clip's result depending on it.
+// within 2 %.  The lever is bytes per flop: gemmcu.hip (one tile per CU and round, up to 320 x 256) takes the shapes whose
+// tiles fill whole rounds of the chip; this kernel keeps the rest.  Both order every output's sum identically (K in steps of
+// 32, the same MFMA with the same operand roles, the same epilogue arithmetic), so their results are BIT-IDENTICAL and the
+// choice between them may depend on the batch size without a clip's result depending on it.
 //
 // Structure (as respair_wide.hip): one 4-wave workgroup per BM x 128 tile (BM = 128 below), two workgroups per CU.  K chunks of 64
 // stream global -> registers -> LDS through a double buffer with the stores spread behind the MFMA blocks; one barrier
@@ -286,12 +286,7 @@ int si_launch_lingemm(si_ctx* ctx, const LinGemmParams& p, hipStream_t st) {
     if (p.x_bytes <= 0 || p.w_bytes <= 0 || (long)p.nseg * p.x_seg_stride * 2 + (long)(p.M + 128) * p.lda * 2 >= (1L << 31)) return 1;
     if (!p.out && !p.out16) return si_fail(ctx, SI_EINVAL, "lingemm: no output");
     if (p.res_stats && (!p.res || !p.res_gamma || !p.res_beta || p.nseg != 1)) return si_fail(ctx, SI_EINVAL, "lingemm: a LayerNorm residual needs res, gamma, beta and one flat segment");
-    {
-        int rc = si_launch_gemmcu(ctx, p, st);                         // one tile per CU where that is one round of the chip (bit-identical results)
-        if (rc <= 0) return rc;
-        rc = si_launch_gemm256(ctx, p, st);                            // 256 x 256 tiles where they fill the chip (bit-identical results)
-        if (rc <= 0) return rc;
-    }
+    if (int rc = si_launch_gemmcu(ctx, p, st); rc <= 0) return rc;     // one tile per CU where the tiles fill whole rounds of the chip (bit-identical results)
     // Tile height: the workgroup slots are 2 per CU; a launch takes ceil(tiles / slots) rounds of a tile's time, which
     // grows with BM (plus a fixed part: prologue, epilogue).  Pick the BM with the smallest rounds x (BM + fixed).
     int bm = 128;

@@ -210,77 +210,6 @@ def test_lingemm_matches_tapgemm_in_the_bf16_encoder(arch):
     assert d <= 1.2e-2 and e1 <= 2e-2 and e0 <= 2e-2
 
 
-@pytest.mark.parametrize("arch,B,N", [("base", 3, 24000), ("large", 2, 16000), ("base", 1, 64000)])
-def test_gemm256_matches_lingemm_in_the_bf16_encoder(arch, B, N):
-    """The 256 x 256-tile GEMM (gemm256.hip: LDS-DMA staging, two wave groups one barrier apart, persistent tile walk) against the
-    128-row kernels on the same bf16 operands: SI_ENC_GEMM256=2 sends EVERY shape it covers through it (feature-extractor
-    convolutions with ragged last tiles, both projections, all four Linears of a layer, fp32 + residual and bf16 outputs, GELU
-    epilogues), =0 none.  Both kernels order every output's sum identically (K in steps of 32 through the same MFMA with the same
-    operand roles, the same epilogue), so the encoder outputs must be EQUAL -- which is what lets the launcher choose between them
-    by batch size.  Repeated runs are bit-identical (a race in the DMA / barrier schedule would show as run-to-run noise), and a
-    clip does not depend on its batch neighbours."""
-    from speech_inpainting_amd import synth
-    from speech_inpainting_amd.arch import HubertArch, VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
-    harch = HubertArch.base() if arch == "base" else HubertArch.large()
-    varch = VocoderArch.tiny()
-    hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(50)
-    wave = synth.synth_wave(B, N, 93).cuda()
-    outs, engs = {}, {}
-    for flag in ("2", "0"):
-        os.environ["SI_ENC_GEMM256"] = flag
-        os.environ["SI_ENC_GEMMCU"] = "0"                                   # (the one-tile-per-CU kernel has its own tests below)
-        try:
-            eng = InpaintingEngine(harch, varch, 50, "cuda:0", "bf16", "fp32").load_state(hsd, gsd, cb)
-        finally:
-            os.environ.pop("SI_ENC_GEMM256", None)
-            os.environ.pop("SI_ENC_GEMMCU", None)
-        eng.ctx.profile_start(4000)
-        outs[flag] = eng.encode(wave).cpu()
-        names = {e["name"] for e in eng.ctx.profile_stop()}
-        assert any(n.startswith("gemm256_bf16") for n in names) == (flag == "2"), names
-        engs[flag] = eng
-    again = [engs["2"].encode(wave).cpu() for _ in range(3)]
-    assert all(torch.equal(a, outs["2"]) for a in again)
-    if B > 1:
-        assert torch.equal(engs["2"].encode(wave[1:2].contiguous()).cpu(), outs["2"][1:2])
-    ref = InpaintingEngine(harch, varch, 50, "cuda:0", "fp32", "fp32").load_state(hsd, gsd, cb).encode(wave).cpu()
-    e2 = rms(outs["2"], ref) / rms(ref)
-    print(f"{arch} B={B} N={N}: gemm256 == 128-row kernels: {torch.equal(outs['2'], outs['0'])}; vs the fp32 encoder {e2:.3e} relative")
-    assert bool(torch.isfinite(outs["2"]).all()) and e2 <= 2e-2
-    assert torch.equal(outs["2"], outs["0"])
-
-
-def test_gemm256_persistent_walk_at_the_bench_shape():
-    """B = 32 x 4 s (the bench's encoder): the launcher's own rule puts the first four strided convolutions (1600 / 832 / 448 / 256
-    tiles: persistent workgroups that request the next tile's first K-tiles under the current tile's last two) and the QKV
-    projection on 256 x 256 tiles; the features must equal the all-128-row run bit for bit, twice."""
-    from speech_inpainting_amd import synth
-    from speech_inpainting_amd.arch import HubertArch, VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
-    harch, varch = HubertArch.base(), VocoderArch.tiny()
-    hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(50)
-    wave = synth.synth_wave(32, 64000, 95).cuda()
-    outs = {}
-    for flag in ("1", "0"):
-        os.environ["SI_ENC_GEMM256"] = flag
-        os.environ["SI_ENC_GEMMCU"] = "0"                                   # (gemmcu.hip would take conv4 and the QKV projection first)
-        try:
-            eng = InpaintingEngine(harch, varch, 50, "cuda:0", "bf16", "fp32").load_state(hsd, gsd, cb)
-        finally:
-            os.environ.pop("SI_ENC_GEMM256", None)
-            os.environ.pop("SI_ENC_GEMMCU", None)
-        eng.ctx.profile_start(4000)
-        outs[flag] = eng.encode(wave).cpu()
-        prof = {e["name"]: e["launches"] for e in eng.ctx.profile_stop()}
-        if flag == "1":
-            assert prof.get("gemm256_bf16", 0) == 4 + 12, prof                   # conv1-4 + QKV x 12 layers
-            assert torch.equal(eng.encode(wave).cpu(), outs["1"])
-        else:
-            assert "gemm256_bf16" not in prof
-    assert torch.equal(outs["1"], outs["0"])
-
-
 @pytest.mark.parametrize("arch,B,N,flag", [("base", 3, 24000, "10"), ("base", 3, 24000, "11"), ("base", 3, 24000, "12"), ("base", 3, 24000, "13"), ("large", 2, 16000, "14"), ("large", 2, 16000, "15"),
                                            ("large", 2, 16000, "2"), ("base", 1, 64000, "2")])
 def test_gemmcu_matches_lingemm_in_the_bf16_encoder(arch, B, N, flag):
@@ -299,12 +228,10 @@ def test_gemmcu_matches_lingemm_in_the_bf16_encoder(arch, B, N, flag):
     outs, engs = {}, {}
     for f in (flag, "0"):
         os.environ["SI_ENC_GEMMCU"] = f
-        os.environ["SI_ENC_GEMM256"] = "0"
         try:
             eng = InpaintingEngine(harch, varch, 50, "cuda:0", "bf16", "fp32").load_state(hsd, gsd, cb)
         finally:
             os.environ.pop("SI_ENC_GEMMCU", None)
-            os.environ.pop("SI_ENC_GEMM256", None)
         eng.ctx.profile_start(4000)
         outs[f] = eng.encode(wave).cpu()
         names = {e["name"] for e in eng.ctx.profile_stop()}
@@ -319,13 +246,14 @@ def test_gemmcu_matches_lingemm_in_the_bf16_encoder(arch, B, N, flag):
     assert torch.equal(outs[flag], outs["0"])
 
 
-@pytest.mark.parametrize("env", [{"SI_ENC_GEMMCU": "0", "SI_ENC_GEMM256": "0"}, {"SI_ENC_GEMMCU": "0", "SI_ENC_GEMM256": "2"}, {"SI_ENC_GEMMCU": "2"}, {}])
+@pytest.mark.parametrize("env", [{"SI_ENC_GEMMCU": "0"}, {"SI_ENC_GEMMCU": "11"}, {"SI_ENC_GEMMCU": "2"}, {}])
 def test_layernorm_residual_fusion_changes_no_value(env):
     """Post-LN layers in bf16 mode (SI_ENC_LNFUSE, default 1): a LayerNorm writes its bf16 GEMM operand and (mean, rstd) per row but
-    not its fp32 rows; the epilogue of the GEMM that adds them as its residual (out-proj, FFN2 -- in lingemm.hip, gemm256.hip and
-    gemmcu.hip) recomputes each element from the row it was normalised from with the LayerNorm kernel's own expression
-    (si_ln_apply), and updates the pre-LN sums in place.  The features must be EQUAL to the run in which every LayerNorm writes
-    its rows (SI_ENC_LNFUSE=0), with each of the three GEMM kernels forced, and with the launcher's own choice at B = 32."""
+    not its fp32 rows; the epilogue of the GEMM that adds them as its residual (out-proj, FFN2 -- in lingemm.hip and gemmcu.hip)
+    recomputes each element from the row it was normalised from with the LayerNorm kernel's own expression (si_ln_apply), and
+    updates the pre-LN sums in place.  The features must be EQUAL to the run in which every LayerNorm writes its rows
+    (SI_ENC_LNFUSE=0), with each of the two GEMM kernels forced (SI_ENC_GEMMCU=0: lingemm alone; =11: gemmcu's 256 x 256 tiles
+    wherever they cover the shape; =2: gemmcu wherever an instantiation does), and with the launcher's own choice at B = 32."""
     from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
     from speech_inpainting_amd.engine import InpaintingEngine
@@ -371,9 +299,10 @@ def test_ffn_row_padding_changes_no_value():
 
 
 def test_gemmcu_rule_at_the_bench_shape():
-    """B = 32 x 4 s (the bench's encoder, M = 6368 flat rows): the launcher's own rule puts the transformer's Linears and the feature
-    projection on one tile per CU (FFN1 on 320 x 256, the N = 768 GEMMs on 160 x 128); the features equal the run without
-    the kernel bit for bit, twice."""
+    """B = 32 x 4 s (the bench's encoder, M = 6368 flat rows): the launcher's own rule puts every encoder GEMM on one tile per CU --
+    the six strided convolutions (conv1 / conv2 on 320 x 256, conv3 / conv4 on 208 x 256, conv5 / conv6 on 224 x 128 / 128 x 128),
+    the feature projection and the four Linears of each of the 12 layers (FFN1 on 320 x 256, QKV on 256 x 256, the N = 768 GEMMs
+    on 160 x 128) -- and none on the 128-row kernel; the features equal the run without the kernel bit for bit, twice."""
     from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
     from speech_inpainting_amd.engine import InpaintingEngine
@@ -392,7 +321,8 @@ def test_gemmcu_rule_at_the_bench_shape():
         prof = {e["name"]: e["launches"] for e in eng.ctx.profile_stop()}
         cu = sum(v for k, v in prof.items() if k.startswith("gemmcu_bf16"))
         if flag == "1":
-            assert cu >= 12 * 3, prof                                           # at least out-proj, FFN1, FFN2 of every layer
+            assert cu == 6 + 1 + 12 * 4, prof                                   # conv1-6, the feature projection, 4 Linears x 12 layers
+            assert not any(k.startswith("lingemm_bf16_") for k in prof), prof
             assert torch.equal(eng.encode(wave).cpu(), outs["1"])
         else:
             assert cu == 0, prof
