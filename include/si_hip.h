@@ -375,7 +375,24 @@ int si_profile_stop(si_ctx* ctx, si_profile_entry* out, int capacity, int* count
 /* Test hook.  Intermediates are named "features", "projected", "encoder_in", "last_hidden" (encoder) and
  * "ups<i>", "stage<i>" (vocoder; of the last chunk of clips).  si_debug_capture registers a device buffer that
  * the NEXT forwards copy the named tensor into at the moment it is produced (workspace buffers are recycled
- * within a forward); dst = NULL unregisters.  si_debug_size returns the tensor's float count in the last forward. */
+ * within a forward); dst = NULL unregisters.  si_debug_size returns the tensor's element count in the last forward.
+ * Per-op taps of the encoder, each the tensor exactly as stored (a name ending in ".bf16" holds raw bf16 values,
+ * 2 bytes each, and its capacity counts bf16 elements; every other capacity counts floats):
+ *   conv0 / conv0.bf16        conv0 (+ GroupNorm + GELU in the group flavour), (B, L1, C0)
+ *   conv0.ln / conv0.ln.bf16  layer flavour: LayerNorm + GELU behind conv0
+ *   conv<i> / conv<i>.bf16    strided conv i (+ GELU in the group flavour), (B, L_{i+1}, C_i); ragged: rows past a clip are stale
+ *   conv<i>.ln[.bf16]         layer flavour: LayerNorm + GELU behind conv i
+ *   layer<l>.h                the fp32 hidden state entering layer l (out-proj's residual)
+ *   layer<l>.h.bf16           the QKV GEMM's bf16 operand
+ *   layer<l>.qkv[.bf16]       q | k | v, (rows, 3H)
+ *   layer<l>.att[.bf16]       attention output, (rows, H)
+ *   layer<l>.att_res          out-proj + residual
+ *   layer<l>.ln1[.bf16]       LayerNorm rows / its bf16 operand (pre-LN, bf16 mode: the operand only)
+ *   layer<l>.ffn[.bf16]       GELU(FFN1), (rows, I) (the bf16 form without its row padding)
+ *   layer<l>.ffn_res          FFN2 + residual
+ *   layer<l>.ln2[.bf16]       as ln1
+ * These are produced only while some capture is registered (they then also appear in si_debug_size); registering any
+ * capture runs the post-LN layers with every LayerNorm writing its rows (SI_ENC_LNFUSE's unfused path). */
 int si_debug_capture(si_ctx* ctx, const char* name, float* dst, long capacity);
 long si_debug_size(si_ctx* ctx, const char* name);
 

@@ -120,14 +120,31 @@ int si_fail_hip(si_ctx* ctx, hipError_t e, const char* what, const char* file, i
 }
 
 // Test hook: remember the size of a named intermediate and, when a capture is registered for it, copy it out
-// the moment it is produced (workspace buffers are recycled later in the same forward).
-static int si_tap(si_ctx* ctx, const char* name, const float* src, long n, hipStream_t st) {
+// the moment it is produced (workspace buffers are recycled later in the same forward).  n elements of esize bytes
+// (2: raw bf16, copied bit for bit); ld > 0: n / cols rows of `cols` elements stored ld elements apart (the padded
+// FFN intermediate), captured dense.  A capacity smaller than n keeps the leading whole rows.
+static int si_tap(si_ctx* ctx, const char* name, const void* src, long n, hipStream_t st, int esize = 4, long cols = 0, long ld = 0) {
     ctx->dbg_size[name] = n;
     auto it = ctx->dbg_capture.find(name);
     if (it == ctx->dbg_capture.end()) return SI_OK;
     const long m = n < it->second.second ? n : it->second.second;
-    if (m > 0) SI_HIP_CHECK(hipMemcpyAsync(it->second.first, src, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
+    if (m <= 0) return SI_OK;
+    if (ld > cols && cols > 0) {
+        if (m / cols > 0)
+            SI_HIP_CHECK(hipMemcpy2DAsync(it->second.first, (size_t)cols * esize, src, (size_t)ld * esize, (size_t)cols * esize, (size_t)(m / cols),
+                                          hipMemcpyDeviceToDevice, st));
+    } else {
+        SI_HIP_CHECK(hipMemcpyAsync(it->second.first, src, (size_t)m * esize, hipMemcpyDeviceToDevice, st));
+    }
     return SI_OK;
+}
+// The per-conv / per-layer taps of the encoder: named and looked up only while some capture is registered, so the forward
+// without captures formats no name and touches no map.  Names ending in ".bf16" hold raw bf16 values.
+static int si_tap_at(si_ctx* ctx, const char* fmt, int idx, const void* src, long n, hipStream_t st, int esize = 4, long cols = 0, long ld = 0) {
+    if (ctx->dbg_capture.empty()) return SI_OK;
+    char name[48];
+    snprintf(name, sizeof(name), fmt, idx);
+    return si_tap(ctx, name, src, n, st, esize, cols, ld);
 }
 
 // Per-launch timing with HIP events recorded on the launch stream (the same stream the kernel runs on).
@@ -929,15 +946,19 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     // other buffer (its bf16 rows would overlap unread fp32 rows of its own input), so that the convolutions run on the
     // dedicated bf16 GEMM kernels (gemmcu / lingemm) like the group-norm flavour's; the last one writes the fp32 features.
     const bool l16 = ctx->opt_enc_opready && d.encoder_math == SI_MATH_BF16 && d.feat_norm_layer && d.num_conv >= 2;
+    const long n0 = (long)B * e.L[1] * d.conv_dim[0];
     if (!d.feat_norm_layer) {
         // group-norm flavour in bf16 mode: the conv chain runs on operand-ready bf16 activations (conv0 and convs 1..n-2
         // write ONLY the bf16 operand of their single consumer; the last conv writes fp32 for the LayerNorm that follows)
         rc = si_launch_conv0_groupnorm(ctx, wp, stats, wf(ctx, L.conv0_w), wf(ctx, L.conv0_g), wf(ctx, L.conv0_b), partials, affine, cbuf[0], st,
                                        c16 ? cb16[0] : nullptr);
+        if (!rc) rc = c16 ? si_tap_at(ctx, "conv%d.bf16", 0, cb16[0], n0, st, 2) : si_tap_at(ctx, "conv%d", 0, cbuf[0], n0, st);
     } else {
         rc = si_launch_conv0_affine(ctx, wp, stats, wf(ctx, L.conv0_w), d.conv_bias ? wf(ctx, L.conv0_bias) : nullptr, affine, cbuf[0], st);
+        if (!rc) rc = si_tap_at(ctx, "conv%d", 0, cbuf[0], n0, st);
         if (!rc) rc = si_launch_layernorm(ctx, cbuf[0], nullptr, wf(ctx, L.conv0_g), wf(ctx, L.conv0_b), l16 ? nullptr : cbuf[0], (long)B * e.L[1], d.conv_dim[0],
                                           1e-5f, 1, st, l16 ? cb16[1] : nullptr);
+        if (!rc) rc = l16 ? si_tap_at(ctx, "conv%d.ln.bf16", 0, cb16[1], n0, st, 2) : si_tap_at(ctx, "conv%d.ln", 0, cbuf[0], n0, st);
     }
     if (rc) return rc;
     // A2: strided convs as tap-GEMMs
@@ -962,18 +983,23 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
             p.algo_macs = rows * d.conv_dim[i] * (double)d.conv_dim[i - 1] * d.conv_kernel[i];
         }
         if ((rc = si_launch_tapgemm(ctx, c.g.math, p, st))) return rc;
+        const long ni = (long)B * e.L[i + 1] * d.conv_dim[i];            // (B, L_{i+1}, C_i); ragged: rows past a clip's own L are stale
+        if ((rc = p.out ? si_tap_at(ctx, "conv%d", i, p.out, ni, st) : si_tap_at(ctx, "conv%d.bf16", i, p.out16, ni, st, 2))) return rc;
         if (l16) {
             const bool last = i + 1 == d.num_conv;
             if ((rc = si_launch_layernorm(ctx, cbuf[0], nullptr, wf(ctx, c.ln_g), wf(ctx, c.ln_b), last ? cbuf[1] : nullptr, (long)B * e.L[i + 1], d.conv_dim[i],
                                           1e-5f, 1, st, last ? nullptr : cb16[1])))
                 return rc;
+            if ((rc = last ? si_tap_at(ctx, "conv%d.ln", i, cbuf[1], ni, st) : si_tap_at(ctx, "conv%d.ln.bf16", i, cb16[1], ni, st, 2))) return rc;
             cur = 1;
             continue;
         }
         cur ^= 1;
-        if (d.feat_norm_layer &&
-            (rc = si_launch_layernorm(ctx, cbuf[cur], nullptr, wf(ctx, c.ln_g), wf(ctx, c.ln_b), cbuf[cur], (long)B * e.L[i + 1], d.conv_dim[i], 1e-5f, 1, st)))
-            return rc;
+        if (d.feat_norm_layer) {
+            if ((rc = si_launch_layernorm(ctx, cbuf[cur], nullptr, wf(ctx, c.ln_g), wf(ctx, c.ln_b), cbuf[cur], (long)B * e.L[i + 1], d.conv_dim[i], 1e-5f, 1, st)))
+                return rc;
+            if ((rc = si_tap_at(ctx, "conv%d.ln", i, cbuf[cur], ni, st))) return rc;
+        }
     }
     const float* feat = cbuf[cur];                                   // (B, T, CF)
     if (vl) {                                                        // -> packed rows (sum of T_b, CF): everything behind is row-wise
@@ -1026,11 +1052,23 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     // A5..A8
     for (int l = 0; l < d.num_layers; ++l) {
         const LayerW& Wl = L.layers[l];
+        const long nh = BT * H;
+        // (taps of this layer: no-ops unless a capture is registered; captures also turn ln_fuse off)
+        auto tap_attention = [&]() {
+            int r = qkv_bf16 ? si_tap_at(ctx, "layer%d.qkv.bf16", l, qkv16, 3 * nh, st, 2) : si_tap_at(ctx, "layer%d.qkv", l, qkv, 3 * nh, st);
+            if (!r) r = att16 ? si_tap_at(ctx, "layer%d.att.bf16", l, att16, nh, st, 2) : si_tap_at(ctx, "layer%d.att", l, att, nh, st);
+            return r;
+        };
+        auto tap_ffn = [&]() {
+            return e16 ? si_tap_at(ctx, "layer%d.ffn.bf16", l, ffn16, (long)BT * I, st, 2, I, ffn_ld) : si_tap_at(ctx, "layer%d.ffn", l, ffn, (long)BT * I, st);
+        };
+        if ((rc = si_tap_at(ctx, "layer%d.h", l, h, nh, st))) return rc;
         if (!d.stable_layer_norm) {       // post-LN (modeling_hubert.py:371-404); h16 = bf16(h) when e16
+            if (e16 && (rc = si_tap_at(ctx, "layer%d.h.bf16", l, h16, nh, st, 2))) return rc;
             if ((rc = linear(ctx, Wl.qkv, h, qkv_bf16 ? nullptr : qkv, BT, SI_ACT_NONE, nullptr, st, h16, qkv_bf16 ? qkv16 : nullptr))) return rc;
             if (qkv_bf16) rc = si_launch_attention_bf16in(ctx, qkv16, B, T, H, d.num_heads, st, att16, vframes, d_rowoff, sum_t2);
             else rc = si_launch_attention(ctx, qkv, att, B, T, H, d.num_heads, st, att16, ctx->opt_att_bf16, vframes, d_rowoff, sum_t2);
-            if (rc) return rc;
+            if (rc || (rc = tap_attention())) return rc;
             if (ln_fuse) {
                 // h2 holds the rows the current hidden state was normalised FROM; out-proj / FFN2 add their residual LayerNorm(h2)
                 // from it and write the next pre-LN sum over it.  The last layer's (or the asked-for layer's) output is written.
@@ -1044,22 +1082,33 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
                 cur_ln = ResLn{ln_stats, wf(ctx, Wl.ln2_g), wf(ctx, Wl.ln2_b)};
             } else {
             if ((rc = linear(ctx, Wl.out, att, h2, BT, SI_ACT_NONE, h, st, att16))) return rc;
+            if ((rc = si_tap_at(ctx, "layer%d.att_res", l, h2, nh, st))) return rc;
             if ((rc = si_launch_layernorm(ctx, h2, nullptr, wf(ctx, Wl.ln1_g), wf(ctx, Wl.ln1_b), h, BT, H, eps, 0, st, h16))) return rc;
+            if ((rc = si_tap_at(ctx, "layer%d.ln1", l, h, nh, st)) || (e16 && (rc = si_tap_at(ctx, "layer%d.ln1.bf16", l, h16, nh, st, 2)))) return rc;
             if ((rc = linear(ctx, Wl.ffn1, h, e16 ? nullptr : ffn, BT, SI_ACT_GELU, nullptr, st, h16, ffn16, 0, e16 ? ffn_ld : 0))) return rc;
+            if ((rc = tap_ffn())) return rc;
             if ((rc = linear(ctx, Wl.ffn2, ffn, h2, BT, SI_ACT_NONE, h, st, ffn16, nullptr, e16 ? ffn_ld : 0))) return rc;
+            if ((rc = si_tap_at(ctx, "layer%d.ffn_res", l, h2, nh, st))) return rc;
             if ((rc = si_launch_layernorm(ctx, h2, nullptr, wf(ctx, Wl.ln2_g), wf(ctx, Wl.ln2_b), h, BT, H, eps, 0, st, h16))) return rc;
+            if ((rc = si_tap_at(ctx, "layer%d.ln2", l, h, nh, st)) || (e16 && (rc = si_tap_at(ctx, "layer%d.ln2.bf16", l, h16, nh, st, 2)))) return rc;
             }
         } else {                          // pre-LN "stable" (modeling_hubert.py:504-547); residual adds are in place
             // (bf16 mode: the normalised rows feed GEMMs only -- their bf16 operand is all that is written)
             if ((rc = si_launch_layernorm(ctx, h, nullptr, wf(ctx, Wl.ln1_g), wf(ctx, Wl.ln1_b), e16 ? nullptr : h2, BT, H, eps, 0, st, h16))) return rc;
+            if ((rc = e16 ? si_tap_at(ctx, "layer%d.ln1.bf16", l, h16, nh, st, 2) : si_tap_at(ctx, "layer%d.ln1", l, h2, nh, st))) return rc;
+            if (e16 && (rc = si_tap_at(ctx, "layer%d.h.bf16", l, h16, nh, st, 2))) return rc;
             if ((rc = linear(ctx, Wl.qkv, h2, qkv_bf16 ? nullptr : qkv, BT, SI_ACT_NONE, nullptr, st, h16, qkv_bf16 ? qkv16 : nullptr))) return rc;
             if (qkv_bf16) rc = si_launch_attention_bf16in(ctx, qkv16, B, T, H, d.num_heads, st, att16, vframes, d_rowoff, sum_t2);
             else rc = si_launch_attention(ctx, qkv, att, B, T, H, d.num_heads, st, att16, ctx->opt_att_bf16, vframes, d_rowoff, sum_t2);
-            if (rc) return rc;
+            if (rc || (rc = tap_attention())) return rc;
             if ((rc = linear(ctx, Wl.out, att, h, BT, SI_ACT_NONE, h, st, att16))) return rc;
+            if ((rc = si_tap_at(ctx, "layer%d.att_res", l, h, nh, st))) return rc;
             if ((rc = si_launch_layernorm(ctx, h, nullptr, wf(ctx, Wl.ln2_g), wf(ctx, Wl.ln2_b), e16 ? nullptr : h2, BT, H, eps, 0, st, h16))) return rc;
+            if ((rc = e16 ? si_tap_at(ctx, "layer%d.ln2.bf16", l, h16, nh, st, 2) : si_tap_at(ctx, "layer%d.ln2", l, h2, nh, st))) return rc;
             if ((rc = linear(ctx, Wl.ffn1, h2, e16 ? nullptr : ffn, BT, SI_ACT_GELU, nullptr, st, h16, ffn16, 0, e16 ? ffn_ld : 0))) return rc;
+            if ((rc = tap_ffn())) return rc;
             if ((rc = linear(ctx, Wl.ffn2, ffn, h, BT, SI_ACT_NONE, h, st, ffn16, nullptr, e16 ? ffn_ld : 0))) return rc;
+            if ((rc = si_tap_at(ctx, "layer%d.ffn_res", l, h, nh, st))) return rc;
         }
         if (output_layer == l + 1) {
             // fairseq `extract_features(output_layer = L)` (I_da/src/hubert_feature_reader.py:60-65): the loop stops after layer

@@ -630,15 +630,17 @@ class NativeContext:
                                              _ptr(out), _ptr(ws), ws.numel(), self._stream()), "si_mel_frontend")
         return out
 
-    def capture(self, names, capacity: int = 0):
+    def capture(self, names, capacity=0):
         """Register capture buffers for the named intermediates (sizes come from the previous forward unless
-        `capacity` floats is given).  Returns {name: tensor}; the tensors are filled by the next forward."""
+        `capacity` elements is given: one count for all, or {name: count}).  Names ending in ".bf16" are raw bf16
+        tensors.  Returns {name: tensor}; the tensors are filled by the next forward."""
         out = {}
         for nm in names:
-            n = capacity or self.lib.si_debug_size(self._h, nm.encode())
+            n = capacity.get(nm, 0) if isinstance(capacity, dict) else capacity
+            n = n or self.lib.si_debug_size(self._h, nm.encode())
             if n < 0:
                 raise NativeError(self.lib.si_last_error(self._h).decode())
-            t = torch.zeros(n, dtype=torch.float32, device=self.device)
+            t = torch.zeros(n, dtype=torch.bfloat16 if nm.endswith(".bf16") else torch.float32, device=self.device)
             self._check(self.lib.si_debug_capture(self._h, nm.encode(), _ptr(t), n), "si_debug_capture")
             out[nm] = t
         self._captures = out

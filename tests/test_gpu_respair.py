@@ -274,6 +274,13 @@ def test_layernorm_residual_fusion_changes_no_value(env):
             assert torch.equal(eng.encode(wave).cpu(), outs["1"])                      # (the in-place update: run to run)
             if env:
                 assert torch.equal(eng.encode(wave[1:2].contiguous()).cpu(), outs["1"][1:2])
+                # every per-op tap registered (the debug path: LayerNorms write their rows): the same output
+                from tests.encoder_ref import tap_capacities
+                cap = tap_capacities(harch, wave.shape[0], wave.shape[1], wave.shape[0] * harch.num_frames(wave.shape[1]))
+                eng.ctx.capture(list(cap), capacity=cap)
+                tapped = eng.encode(wave).cpu()
+                eng.ctx.clear_captures()
+                assert torch.equal(tapped, outs["1"])
     assert bool(torch.isfinite(outs["1"]).all())
     assert torch.equal(outs["1"], outs["0"])
 
