@@ -373,7 +373,7 @@ int si_profile_filter(si_ctx* ctx, const char* family);
 int si_profile_stop(si_ctx* ctx, si_profile_entry* out, int capacity, int* count);
 
 /* Test hook.  Intermediates are named "features", "projected", "encoder_in", "last_hidden" (encoder) and
- * "ups<i>", "stage<i>" (vocoder; of the last chunk of clips).  si_debug_capture registers a device buffer that
+ * "ups<i>", "stage<i>" (vocoder with an fp32 residual stream; of the last chunk of clips).  si_debug_capture registers a device buffer that
  * the NEXT forwards copy the named tensor into at the moment it is produced (workspace buffers are recycled
  * within a forward); dst = NULL unregisters.  si_debug_size returns the tensor's element count in the last forward.
  * Per-op taps of the encoder, each the tensor exactly as stored (a name ending in ".bf16" holds raw bf16 values,
@@ -392,7 +392,22 @@ int si_profile_stop(si_ctx* ctx, si_profile_entry* out, int capacity, int* count
  *   layer<l>.ffn_res          FFN2 + residual
  *   layer<l>.ln2[.bf16]       as ln1
  * These are produced only while some capture is registered (they then also appear in si_debug_size); registering any
- * capture runs the post-LN layers with every LayerNorm writing its rows (SI_ENC_LNFUSE's unfused path). */
+ * capture runs the post-LN layers with every LayerNorm writing its rows (SI_ENC_LNFUSE's unfused path).
+ * Taps of the vocoder's fp16 activation stream (fp16 mode with SI_VOC_RES16, where "ups<i>" / "stage<i>" do not exist), of
+ * the last chunk of clips: names ending in ".f16" hold the raw fp16 tensor exactly as stored, 2 bytes per element, capacity
+ * counted in fp16 elements.  Ragged batches: rows past a clip's own end are stale.
+ *   pre.f16                      conv_pre's output, (B, Tout, C0)
+ *   ups<i>.f16                   upsampler i's output, (B, Lo, C_i), from upsample.hip, gemmcu.hip's TC kernels or the tap-GEMM
+ *   stage<i>.rb<j>.p<n>.f16      output of pair n of resblock j (ResBlock2: of conv n): the block's own stream for n < last, the
+ *                                running MRF sum (blocks 0 .. j, each scaled by 1 / num_kernels) for the last n.  A resblock that
+ *                                runs as one reschain.hip launch has only the last one.
+ *   stage<i>.f16                 the completed MRF mean, as the next consumer reads it
+ * Like the encoder's these are named and looked up only while some capture is registered; unlike the encoder's they are
+ * copies behind the launch that produced the tensor and change neither which kernel runs nor any value.
+ * Stored activated: the producer of an upsampler that runs in gemmcu.hip's TC kernels (profile family "gemmcu_f16_*":
+ * N = u * Cout a multiple of 256, k = 2 u, unless SI_VOC_UPSGEMM=0) stores leaky_relu(x, 0.1) of its fp32 value instead of x.
+ * That producer's tensor is "pre.f16" for upsampler 0 and "stage<i-1>.f16" (= the last "stage<i-1>.rb<j>.p<n>.f16") for upsampler i;
+ * no other tap is activated, and with SI_VOC_UPSGEMM=0 none is. */
 int si_debug_capture(si_ctx* ctx, const char* name, float* dst, long capacity);
 long si_debug_size(si_ctx* ctx, const char* name);
 

@@ -1457,6 +1457,15 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
     // the generator on clips [b0, b0 + Bc) with its own scratch, enqueued on stream `st`
     auto run = [&](int b0, int Bc, float* ext, float* const* buf, unsigned short* const* h16, hipStream_t st) -> int {
         int rc;
+        // Taps of the fp16 activation stream (names ending in ".f16": the raw fp16 tensor as stored, n elements).  Copies only, behind
+        // the launch that produced the tensor: a registered capture changes neither which kernel runs nor any value.  Named and
+        // looked up only while some capture is registered.
+        auto tap16 = [&](const void* src, long n, const char* fmt, int a, int b = 0, int c = 0) -> int {
+            if (!r16 || ctx->dbg_capture.empty()) return SI_OK;
+            char name[48];
+            snprintf(name, sizeof(name), fmt, a, b, c);
+            return si_tap(ctx, name, src, n, st, 2);
+        };
         // ragged batch: device / host rows of the chunk's clips -- dTm mel frames, dLs(s) rows at stage s (0 = stretched frames), dMt(i) GEMM rows of upsampler i
         const int32_t* dTm = vl ? d_tab + b0 : nullptr;
         auto dLs = [&](int sidx) -> const int32_t* { return vl ? d_tab + (size_t)(1 + sidx) * B + b0 : nullptr; };
@@ -1498,6 +1507,7 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
             p.pad = 3; p.ldo = d.up_initial_channel; p.o_seg_stride = Tout * d.up_initial_channel; p.olimit = p.o_seg_stride;
             seg_conv(p, 0);
             if ((rc = si_launch_tapgemm(ctx, Ly.pre.math, p, st))) return rc;
+            if ((rc = tap16(x16, (long)Bc * Tout * d.up_initial_channel, "pre.f16", 0))) return rc;
         }
         long Lc = Tout; int c = d.up_initial_channel;
         for (int i = 0; i < d.num_ups; ++i) {
@@ -1539,6 +1549,8 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
                 if (urc > 0 && (rc = si_launch_tapgemm(ctx, Ly.ups[i].math, p, st))) return rc;
             }
             if (!r16 && (rc = si_tap(ctx, upn[i], U, (long)Bc * Lo * cout, st))) return rc;
+            const long nst = (long)Bc * Lo * cout;                    // elements of every tensor of this stage
+            if ((rc = tap16(U16, nst, "ups%d.f16", i))) return rc;
             // B3: multi-receptive-field fusion: mean over the resblocks, accumulated into xs by the last conv of each
             const bool act_next = ups_on_gemmcu(i + 1, Lo, cout);   // the launch that completes the sum stores the next upsampler's activated input
             for (int j = 0; j < nk; ++j) {
@@ -1569,6 +1581,7 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
                         seg_conv(q, i + 1);
                         if (vl) q.algo_macs = rows_of(hLs(i + 1), Lo) * (double)cout * cout * rk;
                         if ((rc = si_launch_tapgemm(ctx, R.c1[n].math, q, st))) return rc;
+                        if ((rc = tap16(ynext16, nst, "stage%d.rb%d.p%d.f16", i, j, n))) return rc;
                         y = ynext;
                         y16 = ynext16;
                     }
@@ -1586,7 +1599,10 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
                     }
                     const int crc = si_launch_reschain(ctx, cout, cp, st);
                     if (crc < 0) return crc;
-                    if (crc == 0) continue;
+                    if (crc == 0) {
+                        if ((rc = tap16(xs16, nst, "stage%d.rb%d.p%d.f16", i, j, d.num_dil - 1))) return rc;
+                        continue;
+                    }
                 }
                 for (int n = 0; n < d.num_dil; ++n) {
                     const int dl = d.rb_dilations[j][n];
@@ -1599,7 +1615,11 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
                                                           last_n ? 1.0f / nk : 1.0f, last_n && j > 0, st, dLs(i + 1), hLs(i + 1),
                                                           (act_next && last_n && j == nk - 1) ? 0.1f : 1.f);
                         if (frc < 0) return frc;
-                        if (frc == 0) { y16 = yn16; continue; }
+                        if (frc == 0) {
+                            if ((rc = tap16(yn16, nst, "stage%d.rb%d.p%d.f16", i, j, n))) return rc;
+                            y16 = yn16;
+                            continue;
+                        }
                     }
                     float* t = buf[3];
                     TapGemmParams p = gemm_params(ctx, R.c1[n]);
@@ -1631,11 +1651,13 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
                     seg_conv(q, i + 1);
                     if (vl) q.algo_macs = rows_of(hLs(i + 1), Lo) * (double)cout * cout * rk;
                     if ((rc = si_launch_tapgemm(ctx, R.c2[n].math, q, st))) return rc;
+                    if ((rc = tap16(ynext16, nst, "stage%d.rb%d.p%d.f16", i, j, n))) return rc;
                     y = ynext;
                     y16 = ynext16;
                 }
             }
             if (!r16 && (rc = si_tap(ctx, stn[i], xs, (long)Bc * Lo * cout, st))) return rc;
+            if ((rc = tap16(xs16, nst, "stage%d.f16", i))) return rc;
             std::swap(x, xs);
             std::swap(x16, xs16);
             Lc = Lo; c = cout;

@@ -632,15 +632,16 @@ class NativeContext:
 
     def capture(self, names, capacity=0):
         """Register capture buffers for the named intermediates (sizes come from the previous forward unless
-        `capacity` elements is given: one count for all, or {name: count}).  Names ending in ".bf16" are raw bf16
-        tensors.  Returns {name: tensor}; the tensors are filled by the next forward."""
+        `capacity` elements is given: one count for all, or {name: count}).  Names ending in ".bf16" / ".f16" are raw
+        bf16 / fp16 tensors.  Returns {name: tensor}; the tensors are filled by the next forward."""
         out = {}
         for nm in names:
             n = capacity.get(nm, 0) if isinstance(capacity, dict) else capacity
             n = n or self.lib.si_debug_size(self._h, nm.encode())
             if n < 0:
                 raise NativeError(self.lib.si_last_error(self._h).decode())
-            t = torch.zeros(n, dtype=torch.bfloat16 if nm.endswith(".bf16") else torch.float32, device=self.device)
+            dt = torch.bfloat16 if nm.endswith(".bf16") else torch.float16 if nm.endswith(".f16") else torch.float32
+            t = torch.zeros(n, dtype=dt, device=self.device)
             self._check(self.lib.si_debug_capture(self._h, nm.encode(), _ptr(t), n), "si_debug_capture")
             out[nm] = t
         self._captures = out

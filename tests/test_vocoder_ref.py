@@ -1,0 +1,239 @@
+"""The float64 references of tests/vocoder_ref.py pinned on the CPU: with unrounded weights and the rounding steps switched
+off they reproduce the oracle's generator (ref_cpu.generator_forward run in float64, tapped at ups<i> / stage<i>) to 1e-12
+relative on the V1, v3 and a one-stage u = 1 architecture; each bound accepts ref +- E and rejects the first fp16 value past it;
+the packed leaky-ReLU emulation is checked on all 65536 bit patterns; the weight folding reproduces torch._weight_norm bit for
+bit on the synthetic checkpoint."""
+import dataclasses
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import ref_cpu as R
+from speech_inpainting_amd import synth
+from speech_inpainting_amd.arch import VocoderArch
+from tests import vocoder_ref as V
+
+
+class _F64:
+    """An entry whose `.float()` is float64: runs the oracle's functions in double precision unchanged."""
+
+    def __init__(self, t):
+        self.t = t.double()
+
+    def float(self):
+        return self.t
+
+
+def _rel(a, b):
+    return float((a - b).abs().max() / b.abs().max())
+
+
+def _one_stage(C, u=1, k=3, rk=(3, 7, 11), dil=((1, 3, 5),) * 3, resblock="1"):
+    return VocoderArch(resblock=resblock, upsample_rates=(u,), upsample_kernel_sizes=(k,), upsample_initial_channel=2 * C,
+                       resblock_kernel_sizes=rk, resblock_dilation_sizes=dil)
+
+
+ARCHS = {
+    "v1": dataclasses.replace(VocoderArch.v1(), upsample_initial_channel=128),     # V1's rates and blocks at an eighth of the width
+    "v3": dataclasses.replace(VocoderArch.v3(), upsample_initial_channel=64),
+    "u1": _one_stage(32),
+}
+
+
+def _plain(x):
+    return V.lrelu(x, 0.1)
+
+
+def _generator_by_refs(sd, arch, mel):
+    """The generator of one clip composed from the references, nothing rounded: mel (80, Tm) -> ({name: (L, C)}, wave (L,))."""
+    sd64 = {k: _F64(v) for k, v in sd.items()}
+    f = lambda n: R._conv_weight(sd64, n)                                        # noqa: E731  (the fold itself in float64, as the oracle's run)
+    taps = {}
+    x, _ = V.tapconv_ref(mel.t().double(), f("conv_pre"), sd["conv_pre.bias"])
+    nk = len(arch.resblock_kernel_sizes)
+    for i, (u, k) in enumerate(zip(arch.upsample_rates, arch.upsample_kernel_sizes)):
+        x, _ = V.upsample_ref(_plain(x), f(f"ups.{i}"), sd[f"ups.{i}.bias"], u)
+        taps[f"ups{i}"] = x
+        xs = None
+        for j, (rk, dil) in enumerate(zip(arch.resblock_kernel_sizes, arch.resblock_dilation_sizes)):
+            r = f"resblocks.{i * nk + j}."
+            if arch.resblock == "2":
+                y = x
+                for n, d in enumerate(dil):
+                    last = n == len(dil) - 1
+                    y, E = V.rb2_ref(_plain(y), y, f(f"{r}convs.{n}"), sd[f"{r}convs.{n}.bias"], d, 1.0 / nk if last else 1.0,
+                                     xs if last else None)
+                xs = y
+            else:
+                pairs = [(f(f"{r}convs1.{n}"), sd[f"{r}convs1.{n}.bias"], f(f"{r}convs2.{n}"), sd[f"{r}convs2.{n}.bias"], d)
+                         for n, d in enumerate(dil)]
+                xs, E = V.chain_ref(x, pairs, 1.0 / nk, xs, staged=_plain, round_x=False, t_slope=0.1)
+            assert bool((E > 0).all())
+        x = xs
+        taps[f"stage{i}"] = x
+    wave, E = V.conv_post_ref(x, f("conv_post"), sd["conv_post.bias"], mfma=False, slope=0.01)
+    assert bool((E > 0).all())
+    return taps, wave
+
+
+@pytest.mark.parametrize("name", list(ARCHS))
+def test_references_reproduce_the_oracle_generator(name):
+    arch = ARCHS[name]
+    sd = synth.synth_generator_state(arch)
+    B, Tm = 2, 13
+    mel = synth.synth_mel(B, Tm, 80, 5)
+    want_taps = {}
+    want = R.generator_forward({k: _F64(v) for k, v in sd.items()}, arch, _F64(mel), want_taps)
+    assert want.dtype == torch.float64 and want.shape == (B, 1, Tm * arch.hop)
+    for b in range(B):
+        taps, wave = _generator_by_refs(sd, arch, mel[b])
+        for nm, t in taps.items():
+            assert _rel(t, want_taps[nm][b].t()) <= 1e-12, (name, nm)
+        assert _rel(wave, want[b, 0]) <= 1e-12
+
+
+def test_u1_arch_is_one_stage_at_the_mel_rate():
+    arch = ARCHS["u1"]
+    sd = synth.synth_generator_state(arch)
+    for Tm in (1, 2, 255):
+        taps = {}
+        out = R.generator_forward(sd, arch, synth.synth_mel(1, Tm, 80, 6), taps)
+        assert out.shape == (1, 1, Tm) and taps["stage0"].shape == (1, 32, Tm)
+
+
+def test_packed_leaky_relu_on_every_bit_pattern():
+    """lrelu16 against max(h, h * fp16(slope)) evaluated in float64 and rounded ONCE to fp16, on all 65536 patterns (NaNs stay NaN)."""
+    bits = torch.arange(65536, dtype=torch.int32).to(torch.int16)
+    h = bits.view(torch.float16)
+    for slope in (0.1, 0.01):
+        s16 = float(torch.tensor(slope).to(torch.float16))
+        assert s16 == (0.0999755859375 if slope == 0.1 else float(np.float16(0.01)))
+        got = V.lrelu16(h, slope)
+        hd = h.double()
+        prod = V.rne_f16(hd * s16)
+        want = torch.where(hd > prod, hd, prod)
+        want = torch.where(torch.isinf(hd), hd, want)
+        nan = torch.isnan(hd)
+        assert bool(torch.isnan(got.double())[nan].all())
+        assert torch.equal(got.double()[~nan], want[~nan])
+        # and it is NOT the fp32 form rounded once: the two differ on some pattern (a kernel that staged that way would read other operands)
+        other = V.lrelu(hd, V.SLOPE32).float().to(torch.float16).double()
+        assert int((other[~nan] != want[~nan]).sum()) > 0
+
+
+def test_weight_folding_is_torch_weight_norm_bit_for_bit():
+    """fold's operation order is torch._weight_norm's: with torch's own fp32 norm it reproduces torch._weight_norm(...).half() bit
+    for bit.  With the packer's norm (squares summed in double, one rounding) the fp32 weight is within the error of torch's fp32 norm
+    and the fp16 weight is the same or, on fewer than one in 10^3, the neighbouring fp16 value."""
+    for arch in (VocoderArch.v1(), ARCHS["v3"], ARCHS["u1"]):
+        sd = synth.synth_generator_state(arch)
+        names = sorted({k[:-len(".weight_g")] for k in sd if k.endswith(".weight_g")})
+        assert names
+        for n in names:
+            want32 = torch._weight_norm(sd[n + ".weight_v"], sd[n + ".weight_g"], 0)
+            want = want32.half().double()
+            assert torch.equal(V.fold(sd, n, norm="torch"), want), n
+            assert torch.equal(V.fold(sd, n, round16=False, norm="torch"), want32.double()), n
+            got32 = V.fold(sd, n, round16=False)
+            # torch's norm sums n squares in fp32 (relative error <= n 2^-24 in any order, halved by the square root); two roundings behind it
+            n_row = want32[0].numel()
+            assert bool(((got32 - want32.double()).abs() <= (n_row * 2.0 ** -25 + 2.0 ** -22) * want32.double().abs()).all()), n
+            got = V.fold(sd, n)
+            diff = got != want
+            assert int(diff.sum()) <= max(2, diff.numel() // 1000) and bool(((got - want).abs()[diff] == V.ulp_f16(torch.minimum(got.abs(), want.abs()))[diff]).all()), n
+        folded = synth.synth_generator_state(arch, folded=True)
+        assert torch.equal(V.fold(folded, "conv_pre"), folded["conv_pre.weight"].half().double())
+
+
+def _bound_accepts_and_rejects(ref, E, f16=True):
+    """The last representable value inside ref +- E passes; the first one past it fails, on every element and both sides."""
+    check = V.check_f16 if f16 else V.check_f32
+    for sgn in (1.0, -1.0):
+        edge = ref + sgn * E
+        if f16:
+            q = V.ulp_f16(edge)
+            inside = torch.floor(edge / q) * q if sgn > 0 else torch.ceil(edge / q) * q
+            inside = torch.where((inside - ref).abs() <= E, inside, inside - sgn * q)
+            beyond = V.next_f16(inside, ref)
+        else:
+            far = torch.full_like(edge, sgn * 4.0).float()
+            inside = edge.float()
+            inside = torch.where((inside.double() - ref).abs() <= E, inside, torch.nextafter(inside, -far))
+            beyond = torch.nextafter(inside, far).double()
+            inside = inside.double()
+        assert bool(((beyond - ref).abs() > E).all()) and bool(((inside - ref).abs() <= E).all())
+        assert check(inside, ref, E)["bad"] == 0
+        r = check(beyond, ref, E)
+        assert r["bad"] == ref.numel(), (r["bad"], ref.numel())
+
+
+def _operands(C, L, k, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    y = (torch.randn(L, C, generator=g) * scale).to(torch.float16)
+    w = lambda: V.h16(torch.randn(C, C, k, generator=g) / (C * k) ** 0.5)       # noqa: E731
+    b = lambda: torch.randn(C, generator=g) * 0.05                              # noqa: E731
+    return y, w, b
+
+
+@pytest.mark.parametrize("C,k,dil", [(32, 3, 1), (64, 7, 3), (32, 11, 5)])
+def test_every_bound_accepts_its_edge_and_rejects_the_next_value(C, k, dil):
+    y, w, b = _operands(C, 40, k, 3)
+    a = V.lrelu16(y).double()
+    prev = torch.randn(40, C).to(torch.float16).double()
+    cases = {
+        "tapconv": V.tapconv_ref(a, w(), b(), dil),
+        "tapconv activated": V.tapconv_ref(a, w(), b(), dil, out_slope=V.SLOPE32),
+        "pair": V.pair_ref(a, y.double(), w(), b(), w(), b(), dil),
+        "pair alpha acc": V.pair_ref(a, y.double(), w(), b(), w(), b(), dil, V.alpha32(3), prev),
+        "pair activated": V.pair_ref(a, y.double(), w(), b(), w(), b(), dil, V.alpha32(3), prev, out_slope=V.SLOPE32),
+        "rb2": V.rb2_ref(a, y.double(), w(), b(), dil, V.alpha32(3), prev),
+        "chain": V.chain_ref(y.double(), [(w(), b(), w(), b(), d) for d in (1, 3, 5)], V.alpha32(3), prev),
+    }
+    g = torch.Generator().manual_seed(9)
+    wt = V.h16(torch.randn(C, C // 2, 4, generator=g) / (2 * C) ** 0.5)
+    cases["upsample"] = V.upsample_ref(a, wt, torch.randn(C // 2, generator=g) * 0.05, 2)
+    for name, (ref, E) in cases.items():
+        assert bool((E > 0).all()) and bool(torch.isfinite(ref).all()), name
+        assert float(E.max()) < 1e-2 * float(ref.abs().max()), name                # a bound, not a blanket
+        _bound_accepts_and_rejects(ref, E)
+    wp = torch.randn(1, C, 7, generator=g) / (7 * C) ** 0.5
+    for mfma in (True, False):
+        ref, E = V.conv_post_ref(y, wp, torch.tensor([0.01]), mfma)
+        assert ref.shape == (40,) and float(E.max()) < 2e-3
+        _bound_accepts_and_rejects(ref, E, f16=False)
+    m, _ = V.conv_post_ref(y, wp, torch.tensor([0.01]), True)
+    f, _ = V.conv_post_ref(y, wp, torch.tensor([0.01]), False)
+    assert 0 < float((m - f).abs().max()) < 2e-3                                  # fp16 weights and slope: different, and close
+
+
+def test_pair_reference_with_t_rounded_stays_inside_the_bound_of_the_unrounded_one():
+    """The bound's dt term covers the kernel's rounding of t: the reference evaluated WITH t rounded lies inside E of the one without."""
+    y, w, b = _operands(32, 64, 7, 4, scale=30.0)
+    a = V.lrelu16(y).double()
+    ws = (w(), b(), w(), b())
+    ref, E = V.pair_ref(a, y.double(), *ws, 3)
+    ref_t, _ = V.pair_ref(a, y.double(), *ws, 3, round_t=True)
+    assert float((ref_t - ref).abs().max()) > 0 and bool(((ref_t - ref).abs() <= E).all())
+    assert V.check_f16(V.rne_f16(ref_t), ref, E)["bad"] == 0
+
+
+def test_saturation_rule():
+    ref = torch.tensor([70000.0, -70000.0, 65500.0, 65500.0, 100.0, 70000.0])
+    E = torch.tensor([10.0, 10.0, 40.0, 40.0, 1.0, 10.0])
+    got = torch.tensor([65504.0, -65504.0, 65504.0, 65472.0, 100.5, 65472.0])
+    r = V.check_f16(got, ref, E)
+    assert r["ok"].tolist() == [True, True, True, True, True, False] and r["saturated"] == 4
+    assert V.check_f16(torch.tensor([65504.0]), torch.tensor([-70000.0]), torch.tensor([10.0]))["bad"] == 1
+
+
+def test_seam_distance_and_report():
+    seam, edge = V.seam_distance(10, 4)
+    assert seam.tolist() == [3, 2, 1, 0, 0, 1, 1, 0, 0, 1] and edge.tolist() == [0, 1, 2, 3, 4, 4, 3, 2, 1, 0]
+    assert V.seam_distance(4, 4)[0].tolist() == [4] * 4
+    ref = torch.zeros(10, 2, dtype=torch.float64)
+    E = torch.ones(10, 2, dtype=torch.float64)
+    got = ref.clone()
+    got[4, 1] = 3.0
+    line, near, rest = V.report("op", "kern", 1, V.check_f16(got, ref, E), 10, 4, 0)
+    assert "FAILED" in line and "row 4, channel 1, 0 rows from a tile seam, 4 from the clip edge, err/E 3.000" in line and near == 3.0 and rest == 0.0
