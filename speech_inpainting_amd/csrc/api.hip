@@ -121,30 +121,28 @@ int si_fail_hip(si_ctx* ctx, hipError_t e, const char* what, const char* file, i
 
 // Test hook: remember the size of a named intermediate and, when a capture is registered for it, copy it out
 // the moment it is produced (workspace buffers are recycled later in the same forward).  n elements of esize bytes
-// (2: raw bf16, copied bit for bit); ld > 0: n / cols rows of `cols` elements stored ld elements apart (the padded
-// FFN intermediate), captured dense.  A capacity smaller than n keeps the leading whole rows.
-static int si_tap(si_ctx* ctx, const char* name, const void* src, long n, hipStream_t st, int esize = 4, long cols = 0, long ld = 0) {
-    ctx->dbg_size[name] = n;
+// (2: raw bf16 / fp16, copied bit for bit; such names end in ".bf16" / ".f16"); ld > 0: n / cols rows of `cols` elements stored
+// ld elements apart (the padded FFN intermediate), captured dense.  A capacity smaller than n keeps the leading whole rows.
+// A name with a conversion in it ("layer%d.h": the per-conv / per-layer / per-pair taps, numbered by a, b, c) is formatted and
+// looked up only while some capture is registered, so the forward without captures formats no name and touches no map.
+struct TapSrc { const void* p; long n; int esize = 4; long cols = 0, ld = 0; };
+static int si_tap(si_ctx* ctx, hipStream_t st, TapSrc s, const char* fmt, int a = 0, int b = 0, int c = 0) {
+    if (ctx->dbg_capture.empty() && strchr(fmt, '%')) return SI_OK;
+    char name[48];
+    snprintf(name, sizeof(name), fmt, a, b, c);
+    ctx->dbg_size[name] = s.n;
     auto it = ctx->dbg_capture.find(name);
     if (it == ctx->dbg_capture.end()) return SI_OK;
-    const long m = n < it->second.second ? n : it->second.second;
+    const long m = s.n < it->second.second ? s.n : it->second.second;
     if (m <= 0) return SI_OK;
-    if (ld > cols && cols > 0) {
-        if (m / cols > 0)
-            SI_HIP_CHECK(hipMemcpy2DAsync(it->second.first, (size_t)cols * esize, src, (size_t)ld * esize, (size_t)cols * esize, (size_t)(m / cols),
-                                          hipMemcpyDeviceToDevice, st));
+    if (s.ld > s.cols && s.cols > 0) {
+        if (m / s.cols > 0)
+            SI_HIP_CHECK(hipMemcpy2DAsync(it->second.first, (size_t)s.cols * s.esize, s.p, (size_t)s.ld * s.esize, (size_t)s.cols * s.esize,
+                                          (size_t)(m / s.cols), hipMemcpyDeviceToDevice, st));
     } else {
-        SI_HIP_CHECK(hipMemcpyAsync(it->second.first, src, (size_t)m * esize, hipMemcpyDeviceToDevice, st));
+        SI_HIP_CHECK(hipMemcpyAsync(it->second.first, s.p, (size_t)m * s.esize, hipMemcpyDeviceToDevice, st));
     }
     return SI_OK;
-}
-// The per-conv / per-layer taps of the encoder: named and looked up only while some capture is registered, so the forward
-// without captures formats no name and touches no map.  Names ending in ".bf16" hold raw bf16 values.
-static int si_tap_at(si_ctx* ctx, const char* fmt, int idx, const void* src, long n, hipStream_t st, int esize = 4, long cols = 0, long ld = 0) {
-    if (ctx->dbg_capture.empty()) return SI_OK;
-    char name[48];
-    snprintf(name, sizeof(name), fmt, idx);
-    return si_tap(ctx, name, src, n, st, esize, cols, ld);
 }
 
 // Per-launch timing with HIP events recorded on the launch stream (the same stream the kernel runs on).
@@ -605,6 +603,20 @@ struct Carver {
     }
 };
 
+// Ragged batches: the per-clip length table of the call in progress.  `fill` writes its `ints` zeroed entries on the host and returns
+// an error code for a length it refuses; the table is then carved from the `what` workspace and uploaded in stream order.
+struct VlTable { const int32_t* host = nullptr; int32_t* dev = nullptr; };
+template <class Fill>
+int vl_table(si_ctx* ctx, Carver& W, size_t ints, hipStream_t st, const char* what, VlTable& t, Fill fill) {
+    ctx->vl_host.assign(ints, 0);
+    if (int rc = fill(ctx->vl_host.data())) return rc;
+    t.dev = reinterpret_cast<int32_t*>(W.bytes(ints * 4));
+    if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: %s workspace carve exceeded its own estimate", what);
+    if (int rc = vl_upload(ctx, t.dev, st)) return rc;
+    t.host = ctx->vl_host.data();
+    return SI_OK;
+}
+
 struct EncDims { int T; std::vector<int> L; };
 EncDims enc_dims(const si_model_desc& d, int N) {
     EncDims e; e.L.push_back(N);
@@ -658,18 +670,27 @@ TapGemmParams gemm_params(const si_ctx* ctx, const GemmW& G) {
     return p;
 }
 
-// y(rows x N) = x(rows x K) W^T + b [+act] [+res]
+// ConvTranspose1d(k, stride u, padding (k - u) / 2) of upsampler i over Lin rows as a GEMM: row m holds the u output rows
+// m * u - pad .. m * u - pad + u - 1 (the phases), so Lout = u * Lin output rows take M GEMM rows
+struct UpsGeom { int u, pad; long Lout; int M; };
+UpsGeom ups_geom(const si_model_desc& d, int i, long Lin) {
+    const int u = d.up_rates[i], pad = (d.up_kernels[i] - u) / 2;
+    const long Lout = Lin * u;
+    return UpsGeom{u, pad, Lout, (int)((pad + Lout - 1) / u + 1)};
+}
+
+// y(rows x N) = x(rows x K) W^T + b [+act] [+res], with the optional operands of LinearIo:
 // x16 / y16: operand-ready bf16 input (instead of x) / additional-or-only bf16 output, see TapGemmParams
 // ld_in / ld_out (elements; 0 = dense): row strides of the 16-bit input / of the output when they are padded (the FFN intermediate)
 // res_ln (stats, gamma, beta): the residual is LayerNorm(res), recomputed in the GEMM's epilogue (TapGemmParams::res_stats)
 struct ResLn { const float* stats = nullptr; const float* gamma = nullptr; const float* beta = nullptr; };
-int linear(si_ctx* ctx, const GemmW& G, const float* x, float* y, long rows, int act, const float* res, hipStream_t st,
-           const unsigned short* x16 = nullptr, unsigned short* y16 = nullptr, int ld_in = 0, int ld_out = 0, ResLn res_ln = ResLn()) {
+struct LinearIo { const unsigned short* x16 = nullptr; unsigned short* y16 = nullptr; int ld_in = 0, ld_out = 0; ResLn res_ln; };
+int linear(si_ctx* ctx, const GemmW& G, const float* x, float* y, long rows, int act, const float* res, hipStream_t st, const LinearIo& io = LinearIo()) {
     TapGemmParams p = gemm_params(ctx, G);
-    p.x = x16 ? nullptr : x; p.x16 = x16; p.out = y; p.out16 = y16; p.res = res; p.act = act;
-    p.res_stats = res_ln.stats; p.res_gamma = res_ln.gamma; p.res_beta = res_ln.beta;
-    p.nseg = 1; p.Lin = (int)rows; p.M = (int)rows; p.ldx = ld_in ? ld_in : G.Cin; p.x_seg_stride = 0;
-    p.ldo = ld_out ? ld_out : G.N; p.o_seg_stride = 0; p.ooff = 0; p.olimit = rows * p.ldo;
+    p.x = io.x16 ? nullptr : x; p.x16 = io.x16; p.out = y; p.out16 = io.y16; p.res = res; p.act = act;
+    p.res_stats = io.res_ln.stats; p.res_gamma = io.res_ln.gamma; p.res_beta = io.res_ln.beta;
+    p.nseg = 1; p.Lin = (int)rows; p.M = (int)rows; p.ldx = io.ld_in ? io.ld_in : G.Cin; p.x_seg_stride = 0;
+    p.ldo = io.ld_out ? io.ld_out : G.N; p.o_seg_stride = 0; p.ooff = 0; p.olimit = rows * p.ldo;
     p.lingemm = ctx->opt_enc_lingemm;
     return si_launch_tapgemm(ctx, G.math, p, st);
 }
@@ -868,34 +889,31 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     Carver W{static_cast<char*>(workspace), workspace_bytes};
     // ---- ragged batch: the table [samples | L_1 .. L_nconv | row offsets (B + 1)] on the host and on the device
     const bool vl = host_len != nullptr;
-    const int32_t* h_tab = nullptr;      // host
-    int32_t* d_tab = nullptr;            // device
+    VlTable tab;
     long rows_packed = 0;
     double sum_t2 = 0.0;
     if (vl) {
         if (valid_len || output_layer) return si_fail(ctx, SI_EINVAL, "ragged batches: not combined with padded batches or output_layer");
         if (d.codebook_dim % 4) return si_fail(ctx, SI_EINVAL, "ragged batches need codebook_dim %% 4 == 0");
-        std::vector<int32_t>& tab = ctx->vl_host;
-        tab.assign((size_t)(d.num_conv + 1) * B + B + 1, 0);
-        for (int b = 0; b < B; ++b) {
-            if (host_len[b] < 1 || host_len[b] > N) return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d holds %d samples, outside 1..%d", b, host_len[b], N);
-            const EncDims eb = enc_dims(d, host_len[b]);
-            if (eb.T < 1) return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d (%d samples) is shorter than the conv stack's receptive field", b, host_len[b]);
-            for (int i = 0; i <= d.num_conv; ++i) tab[(size_t)i * B + b] = eb.L[i];
-            tab[(size_t)(d.num_conv + 1) * B + b] = (int32_t)rows_packed;
-            rows_packed += eb.T;
-            sum_t2 += (double)eb.T * eb.T;
-        }
-        tab[(size_t)(d.num_conv + 1) * B + B] = (int32_t)rows_packed;
-        d_tab = reinterpret_cast<int32_t*>(W.bytes(tab.size() * 4));
-        if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: encoder workspace carve exceeded its own estimate");
-        if (int rc = vl_upload(ctx, d_tab, st)) return rc;
-        h_tab = tab.data();
-        valid_len = d_tab;                                   // the statistics and loaders of conv0 stop at each clip's own samples
+        const size_t off = (size_t)(d.num_conv + 1) * B;               // the row offsets
+        if (int trc = vl_table(ctx, W, off + B + 1, st, "encoder", tab, [&](int32_t* t) -> int {
+            for (int b = 0; b < B; ++b) {
+                if (host_len[b] < 1 || host_len[b] > N) return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d holds %d samples, outside 1..%d", b, host_len[b], N);
+                const EncDims eb = enc_dims(d, host_len[b]);
+                if (eb.T < 1) return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d (%d samples) is shorter than the conv stack's receptive field", b, host_len[b]);
+                for (int i = 0; i <= d.num_conv; ++i) t[(size_t)i * B + b] = eb.L[i];
+                t[off + b] = (int32_t)rows_packed;
+                rows_packed += eb.T;
+                sum_t2 += (double)eb.T * eb.T;
+            }
+            t[off + B] = (int32_t)rows_packed;
+            return SI_OK;
+        })) return trc;
+        valid_len = tab.dev;                                 // the statistics and loaders of conv0 stop at each clip's own samples
     }
-    auto dL = [&](int i) { return d_tab + (size_t)i * B; };            // device / host rows of conv layer i's output (0: samples)
-    auto hL = [&](int i) { return h_tab + (size_t)i * B; };
-    const int32_t* d_rowoff = vl ? d_tab + (size_t)(d.num_conv + 1) * B : nullptr;
+    auto dL = [&](int i) { return tab.dev + (size_t)i * B; };          // device / host rows of conv layer i's output (0: samples)
+    auto hL = [&](int i) { return tab.host + (size_t)i * B; };
+    const int32_t* d_rowoff = vl ? dL(d.num_conv + 1) : nullptr;
     const long BT = vl ? rows_packed : (long)B * T;          // transformer rows
     double* stats = reinterpret_cast<double*>(W.bytes((size_t)B * 16));
     int32_t* vframes = (valid_len && !vl) ? reinterpret_cast<int32_t*>(W.bytes((size_t)B * 4)) : nullptr;
@@ -936,6 +954,19 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     unsigned short* qkv16 = reinterpret_cast<unsigned short*>(qkv);
 
     int rc;
+    // A convolution of the encoder on (B, Lin, groups * Cin) -> (B, M, groups * N); ragged: clip b reads row li of the length table
+    // and writes row lo (modeling_hubert.py:664-677).  Operands, stride / padding and the epilogue are the caller's.
+    auto enc_conv = [&](const GemmW& G, int Lin, int M, int li, int lo) {
+        TapGemmParams p = gemm_params(ctx, G);
+        p.nseg = B; p.Lin = Lin; p.M = M; p.ldx = G.groups * G.Cin; p.x_seg_stride = (long)Lin * p.ldx;
+        p.ldo = G.groups * G.N; p.o_seg_stride = (long)M * p.ldo; p.olimit = p.o_seg_stride;
+        if (vl) {
+            p.seg_lin = dL(li); p.seg_m = dL(lo); p.seg_orows = dL(lo); p.olim_mul = p.ldo; p.seg_m_host = hL(lo);
+            double rows = 0; for (int b = 0; b < B; ++b) rows += hL(lo)[b];
+            p.algo_macs = rows * p.ldo * (double)G.Cin * G.ntaps;
+        }
+        return p;
+    };
     // A0 + A1: normalise fused into conv0
     WaveNormParams wp{wav, mask_start, mask_len, B, N, e.L[1], d.conv_dim[0], d.conv_kernel[0], d.conv_stride[0], normalize, valid_len, norm_eps, pre_add,
                       vl ? dL(1) : nullptr};
@@ -952,45 +983,38 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
         // write ONLY the bf16 operand of their single consumer; the last conv writes fp32 for the LayerNorm that follows)
         rc = si_launch_conv0_groupnorm(ctx, wp, stats, wf(ctx, L.conv0_w), wf(ctx, L.conv0_g), wf(ctx, L.conv0_b), partials, affine, cbuf[0], st,
                                        c16 ? cb16[0] : nullptr);
-        if (!rc) rc = c16 ? si_tap_at(ctx, "conv%d.bf16", 0, cb16[0], n0, st, 2) : si_tap_at(ctx, "conv%d", 0, cbuf[0], n0, st);
+        if (!rc) rc = c16 ? si_tap(ctx, st, {cb16[0], n0, 2}, "conv%d.bf16", 0) : si_tap(ctx, st, {cbuf[0], n0}, "conv%d", 0);
     } else {
         rc = si_launch_conv0_affine(ctx, wp, stats, wf(ctx, L.conv0_w), d.conv_bias ? wf(ctx, L.conv0_bias) : nullptr, affine, cbuf[0], st);
-        if (!rc) rc = si_tap_at(ctx, "conv%d", 0, cbuf[0], n0, st);
+        if (!rc) rc = si_tap(ctx, st, {cbuf[0], n0}, "conv%d", 0);
         if (!rc) rc = si_launch_layernorm(ctx, cbuf[0], nullptr, wf(ctx, L.conv0_g), wf(ctx, L.conv0_b), l16 ? nullptr : cbuf[0], (long)B * e.L[1], d.conv_dim[0],
                                           1e-5f, 1, st, l16 ? cb16[1] : nullptr);
-        if (!rc) rc = l16 ? si_tap_at(ctx, "conv%d.ln.bf16", 0, cb16[1], n0, st, 2) : si_tap_at(ctx, "conv%d.ln", 0, cbuf[0], n0, st);
+        if (!rc) rc = l16 ? si_tap(ctx, st, {cb16[1], n0, 2}, "conv%d.ln.bf16", 0) : si_tap(ctx, st, {cbuf[0], n0}, "conv%d.ln", 0);
     }
     if (rc) return rc;
     // A2: strided convs as tap-GEMMs
     int cur = 0;
     for (int i = 1; i < d.num_conv; ++i) {
         const ConvW& c = L.convs[i - 1];
-        TapGemmParams p = gemm_params(ctx, c.g);
+        TapGemmParams p = enc_conv(c.g, e.L[i], e.L[i + 1], i, i + 1);
         p.x = cbuf[cur]; p.out = cbuf[cur ^ 1];
         if (c16) {
             p.x = nullptr; p.x16 = cb16[cur];
             if (i + 1 < d.num_conv) { p.out = nullptr; p.out16 = cb16[cur ^ 1]; p.out16_slope = 1.f; }
         }
         if (l16) { p.x = nullptr; p.x16 = cb16[1]; p.out = cbuf[0]; }          // bf16 in from buffer 1, fp32 out to buffer 0
-        p.nseg = B; p.Lin = e.L[i]; p.M = e.L[i + 1]; p.ldx = d.conv_dim[i - 1]; p.x_seg_stride = (long)e.L[i] * d.conv_dim[i - 1];
-        p.stride = d.conv_stride[i]; p.ldo = d.conv_dim[i]; p.o_seg_stride = (long)e.L[i + 1] * d.conv_dim[i];
-        p.olimit = p.o_seg_stride;
+        p.stride = d.conv_stride[i];
         p.act = d.feat_norm_layer ? SI_ACT_NONE : SI_ACT_GELU;
         p.lingemm = ctx->opt_enc_lingemm;
-        if (vl) {                                            // each clip's own input / output rows (modeling_hubert.py:664-677)
-            p.seg_lin = dL(i); p.seg_m = dL(i + 1); p.seg_orows = dL(i + 1); p.olim_mul = p.ldo; p.seg_m_host = hL(i + 1);
-            double rows = 0; for (int b = 0; b < B; ++b) rows += hL(i + 1)[b];
-            p.algo_macs = rows * d.conv_dim[i] * (double)d.conv_dim[i - 1] * d.conv_kernel[i];
-        }
         if ((rc = si_launch_tapgemm(ctx, c.g.math, p, st))) return rc;
         const long ni = (long)B * e.L[i + 1] * d.conv_dim[i];            // (B, L_{i+1}, C_i); ragged: rows past a clip's own L are stale
-        if ((rc = p.out ? si_tap_at(ctx, "conv%d", i, p.out, ni, st) : si_tap_at(ctx, "conv%d.bf16", i, p.out16, ni, st, 2))) return rc;
+        if ((rc = p.out ? si_tap(ctx, st, {p.out, ni}, "conv%d", i) : si_tap(ctx, st, {p.out16, ni, 2}, "conv%d.bf16", i))) return rc;
         if (l16) {
             const bool last = i + 1 == d.num_conv;
             if ((rc = si_launch_layernorm(ctx, cbuf[0], nullptr, wf(ctx, c.ln_g), wf(ctx, c.ln_b), last ? cbuf[1] : nullptr, (long)B * e.L[i + 1], d.conv_dim[i],
                                           1e-5f, 1, st, last ? nullptr : cb16[1])))
                 return rc;
-            if ((rc = last ? si_tap_at(ctx, "conv%d.ln", i, cbuf[1], ni, st) : si_tap_at(ctx, "conv%d.ln.bf16", i, cb16[1], ni, st, 2))) return rc;
+            if ((rc = last ? si_tap(ctx, st, {cbuf[1], ni}, "conv%d.ln", i) : si_tap(ctx, st, {cb16[1], ni, 2}, "conv%d.ln.bf16", i))) return rc;
             cur = 1;
             continue;
         }
@@ -998,7 +1022,7 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
         if (d.feat_norm_layer) {
             if ((rc = si_launch_layernorm(ctx, cbuf[cur], nullptr, wf(ctx, c.ln_g), wf(ctx, c.ln_b), cbuf[cur], (long)B * e.L[i + 1], d.conv_dim[i], 1e-5f, 1, st)))
                 return rc;
-            if ((rc = si_tap_at(ctx, "conv%d.ln", i, cbuf[cur], ni, st))) return rc;
+            if ((rc = si_tap(ctx, st, {cbuf[cur], ni}, "conv%d.ln", i))) return rc;
         }
     }
     const float* feat = cbuf[cur];                                   // (B, T, CF)
@@ -1006,16 +1030,16 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
         if ((rc = si_launch_repack_rows(ctx, cbuf[cur], cbuf[cur ^ 1], B, T, CF, d_rowoff, false, st))) return rc;
         feat = cbuf[cur ^ 1];
     }
-    if ((rc = si_tap(ctx, "features", feat, BT * CF, st))) return rc;
+    if ((rc = si_tap(ctx, st, {feat, BT * CF}, "features"))) return rc;
     // A3: LN + projection
-    const float* pin = feat;
+    LinearIo proj_io;
     if (d.feat_proj_layer_norm) {
         // (bf16 mode: the projection reads the bf16 operand only)
         if ((rc = si_launch_layernorm(ctx, feat, nullptr, wf(ctx, L.fp_ln_g), wf(ctx, L.fp_ln_b), lnf16 ? nullptr : lnf, BT, CF, d.layer_norm_eps, 0, st, lnf16))) return rc;
-        pin = lnf;
+        proj_io.x16 = lnf16;
     }
-    if ((rc = linear(ctx, L.proj, pin, h, BT, SI_ACT_NONE, nullptr, st, d.feat_proj_layer_norm ? lnf16 : nullptr))) return rc;
-    if ((rc = si_tap(ctx, "projected", h, BT * H, st))) return rc;
+    if ((rc = linear(ctx, L.proj, d.feat_proj_layer_norm ? lnf : feat, h, BT, SI_ACT_NONE, nullptr, st, proj_io))) return rc;
+    if ((rc = si_tap(ctx, st, {h, BT * H}, "projected"))) return rc;
     // right-padded batches: padded frames of the projected states are zeroed before the positional conv and excluded
     // as attention keys (modeling_hubert.py:428-437 / 573-582)
     if (vframes && (rc = si_launch_zero_padded_rows(ctx, h, B, T, H, vframes, st))) return rc;
@@ -1029,86 +1053,89 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
         pos_done = prc == 0;
     }
     if (!pos_done) {
-        TapGemmParams p = gemm_params(ctx, L.pos);
+        TapGemmParams p = enc_conv(L.pos, T, T, d.num_conv, d.num_conv);
         p.x = h; p.out = h2; p.res = h;
-        p.nseg = B; p.Lin = T; p.M = T; p.ldx = H; p.x_seg_stride = (long)T * H;
-        p.pad = d.pos_conv_kernel / 2; p.ldo = H; p.o_seg_stride = (long)T * H; p.olimit = p.o_seg_stride;
+        p.pad = d.pos_conv_kernel / 2;
         p.act = SI_ACT_GELU;
-        if (vl) {                                            // packed rows: the conv's zero padding begins at each clip's own last frame
-            p.seg_lin = dL(d.num_conv); p.seg_m = dL(d.num_conv); p.seg_orows = dL(d.num_conv); p.olim_mul = H; p.seg_row_off = d_rowoff;
-            p.algo_macs = (double)BT * H * (double)(H / d.pos_conv_groups) * d.pos_conv_kernel;
-        }
+        if (vl) p.seg_row_off = d_rowoff;                    // packed rows: the conv's zero padding begins at each clip's own last frame
         if ((rc = si_launch_tapgemm(ctx, L.pos.math, p, st))) return rc;
     }
     const float eps = d.layer_norm_eps;
     ResLn cur_ln;                                                      // ln_fuse: the LayerNorm whose (unwritten) output is the current hidden state
+    // LayerNorm of the transformer rows: fp32 rows to y and / or their bf16 operand to y16; ln_fuse: (mean, rstd) per row for cur_ln
+    auto norm = [&](const float* x, size_t gamma, size_t beta, float* y, unsigned short* y16 = nullptr) {
+        if (ln_fuse) cur_ln = ResLn{ln_stats, wf(ctx, gamma), wf(ctx, beta)};
+        return si_launch_layernorm(ctx, x, nullptr, wf(ctx, gamma), wf(ctx, beta), y, BT, H, eps, 0, st, y16, ln_stats);
+    };
     if (!d.stable_layer_norm) {
-        if ((rc = si_launch_layernorm(ctx, h2, nullptr, wf(ctx, L.enc_ln_g), wf(ctx, L.enc_ln_b), ln_fuse ? nullptr : h, BT, H, eps, 0, st, h16, ln_stats))) return rc;
-        cur_ln = ResLn{ln_stats, wf(ctx, L.enc_ln_g), wf(ctx, L.enc_ln_b)};
+        if ((rc = norm(h2, L.enc_ln_g, L.enc_ln_b, ln_fuse ? nullptr : h, h16))) return rc;
     } else {
         std::swap(h, h2);
     }
-    if ((rc = si_tap(ctx, "encoder_in", h, BT * H, st))) return rc;
-    // A5..A8
+    if ((rc = si_tap(ctx, st, {h, BT * H}, "encoder_in"))) return rc;
+    // A5..A8.  The optional operands of a layer's four GEMMs (bf16 mode: each reads the operand-ready copy its producer wrote; the
+    // rows of the FFN intermediate are ffn_ld apart); ln_fuse adds the LayerNorm residual of the moment to out-proj's and FFN2's.
+    const long nh = BT * H;
+    LinearIo qkv_io, out_io, ffn1_io, ffn2_io;
+    qkv_io.x16 = h16; qkv_io.y16 = qkv_bf16 ? qkv16 : nullptr;
+    out_io.x16 = att16;
+    ffn1_io.x16 = h16; ffn1_io.y16 = ffn16; ffn1_io.ld_out = ffn_ld;
+    ffn2_io.x16 = ffn16; ffn2_io.ld_in = ffn_ld;
+    // (taps of a layer: no-ops unless a capture is registered; captures also turn ln_fuse off)
+    // q | k | v of layer l from x (bf16 mode: from h16 = bf16(x)), then the attention into att / att16
+    auto attention = [&](int l, const float* x) -> int {
+        int r;
+        if (e16 && (r = si_tap(ctx, st, {h16, nh, 2}, "layer%d.h.bf16", l))) return r;
+        if ((r = linear(ctx, L.layers[l].qkv, x, qkv_bf16 ? nullptr : qkv, BT, SI_ACT_NONE, nullptr, st, qkv_io))) return r;
+        if (qkv_bf16) r = si_launch_attention_bf16in(ctx, qkv16, B, T, H, d.num_heads, st, att16, vframes, d_rowoff, sum_t2);
+        else r = si_launch_attention(ctx, qkv, att, B, T, H, d.num_heads, st, att16, ctx->opt_att_bf16, vframes, d_rowoff, sum_t2);
+        if (!r) r = qkv_bf16 ? si_tap(ctx, st, {qkv16, 3 * nh, 2}, "layer%d.qkv.bf16", l) : si_tap(ctx, st, {qkv, 3 * nh}, "layer%d.qkv", l);
+        if (!r) r = att16 ? si_tap(ctx, st, {att16, nh, 2}, "layer%d.att.bf16", l) : si_tap(ctx, st, {att, nh}, "layer%d.att", l);
+        return r;
+    };
+    // the FFN's first GEMM of layer l on x (bf16 mode: on h16, writing the bf16 intermediate only)
+    auto ffn1 = [&](int l, const float* x) -> int {
+        if (int r = linear(ctx, L.layers[l].ffn1, x, e16 ? nullptr : ffn, BT, SI_ACT_GELU, nullptr, st, ffn1_io)) return r;
+        return e16 ? si_tap(ctx, st, {ffn16, BT * I, 2, I, ffn_ld}, "layer%d.ffn.bf16", l) : si_tap(ctx, st, {ffn, BT * I}, "layer%d.ffn", l);
+    };
     for (int l = 0; l < d.num_layers; ++l) {
         const LayerW& Wl = L.layers[l];
-        const long nh = BT * H;
-        // (taps of this layer: no-ops unless a capture is registered; captures also turn ln_fuse off)
-        auto tap_attention = [&]() {
-            int r = qkv_bf16 ? si_tap_at(ctx, "layer%d.qkv.bf16", l, qkv16, 3 * nh, st, 2) : si_tap_at(ctx, "layer%d.qkv", l, qkv, 3 * nh, st);
-            if (!r) r = att16 ? si_tap_at(ctx, "layer%d.att.bf16", l, att16, nh, st, 2) : si_tap_at(ctx, "layer%d.att", l, att, nh, st);
-            return r;
-        };
-        auto tap_ffn = [&]() {
-            return e16 ? si_tap_at(ctx, "layer%d.ffn.bf16", l, ffn16, (long)BT * I, st, 2, I, ffn_ld) : si_tap_at(ctx, "layer%d.ffn", l, ffn, (long)BT * I, st);
-        };
-        if ((rc = si_tap_at(ctx, "layer%d.h", l, h, nh, st))) return rc;
-        if (!d.stable_layer_norm) {       // post-LN (modeling_hubert.py:371-404); h16 = bf16(h) when e16
-            if (e16 && (rc = si_tap_at(ctx, "layer%d.h.bf16", l, h16, nh, st, 2))) return rc;
-            if ((rc = linear(ctx, Wl.qkv, h, qkv_bf16 ? nullptr : qkv, BT, SI_ACT_NONE, nullptr, st, h16, qkv_bf16 ? qkv16 : nullptr))) return rc;
-            if (qkv_bf16) rc = si_launch_attention_bf16in(ctx, qkv16, B, T, H, d.num_heads, st, att16, vframes, d_rowoff, sum_t2);
-            else rc = si_launch_attention(ctx, qkv, att, B, T, H, d.num_heads, st, att16, ctx->opt_att_bf16, vframes, d_rowoff, sum_t2);
-            if (rc || (rc = tap_attention())) return rc;
-            if (ln_fuse) {
-                // h2 holds the rows the current hidden state was normalised FROM; out-proj / FFN2 add their residual LayerNorm(h2)
-                // from it and write the next pre-LN sum over it.  The last layer's (or the asked-for layer's) output is written.
-                const bool want_rows = l + 1 == d.num_layers || output_layer == l + 1;
-                if ((rc = linear(ctx, Wl.out, att, h2, BT, SI_ACT_NONE, h2, st, att16, nullptr, 0, 0, cur_ln))) return rc;
-                if ((rc = si_launch_layernorm(ctx, h2, nullptr, wf(ctx, Wl.ln1_g), wf(ctx, Wl.ln1_b), nullptr, BT, H, eps, 0, st, h16, ln_stats))) return rc;
-                cur_ln = ResLn{ln_stats, wf(ctx, Wl.ln1_g), wf(ctx, Wl.ln1_b)};
-                if ((rc = linear(ctx, Wl.ffn1, h, nullptr, BT, SI_ACT_GELU, nullptr, st, h16, ffn16, 0, ffn_ld))) return rc;
-                if ((rc = linear(ctx, Wl.ffn2, ffn, h2, BT, SI_ACT_NONE, h2, st, ffn16, nullptr, ffn_ld, 0, cur_ln))) return rc;
-                if ((rc = si_launch_layernorm(ctx, h2, nullptr, wf(ctx, Wl.ln2_g), wf(ctx, Wl.ln2_b), want_rows ? h : nullptr, BT, H, eps, 0, st, h16, ln_stats))) return rc;
-                cur_ln = ResLn{ln_stats, wf(ctx, Wl.ln2_g), wf(ctx, Wl.ln2_b)};
-            } else {
-            if ((rc = linear(ctx, Wl.out, att, h2, BT, SI_ACT_NONE, h, st, att16))) return rc;
-            if ((rc = si_tap_at(ctx, "layer%d.att_res", l, h2, nh, st))) return rc;
-            if ((rc = si_launch_layernorm(ctx, h2, nullptr, wf(ctx, Wl.ln1_g), wf(ctx, Wl.ln1_b), h, BT, H, eps, 0, st, h16))) return rc;
-            if ((rc = si_tap_at(ctx, "layer%d.ln1", l, h, nh, st)) || (e16 && (rc = si_tap_at(ctx, "layer%d.ln1.bf16", l, h16, nh, st, 2)))) return rc;
-            if ((rc = linear(ctx, Wl.ffn1, h, e16 ? nullptr : ffn, BT, SI_ACT_GELU, nullptr, st, h16, ffn16, 0, e16 ? ffn_ld : 0))) return rc;
-            if ((rc = tap_ffn())) return rc;
-            if ((rc = linear(ctx, Wl.ffn2, ffn, h2, BT, SI_ACT_NONE, h, st, ffn16, nullptr, e16 ? ffn_ld : 0))) return rc;
-            if ((rc = si_tap_at(ctx, "layer%d.ffn_res", l, h2, nh, st))) return rc;
-            if ((rc = si_launch_layernorm(ctx, h2, nullptr, wf(ctx, Wl.ln2_g), wf(ctx, Wl.ln2_b), h, BT, H, eps, 0, st, h16))) return rc;
-            if ((rc = si_tap_at(ctx, "layer%d.ln2", l, h, nh, st)) || (e16 && (rc = si_tap_at(ctx, "layer%d.ln2.bf16", l, h16, nh, st, 2)))) return rc;
-            }
-        } else {                          // pre-LN "stable" (modeling_hubert.py:504-547); residual adds are in place
+        if ((rc = si_tap(ctx, st, {h, nh}, "layer%d.h", l))) return rc;
+        if (!d.stable_layer_norm && ln_fuse) {   // post-LN (modeling_hubert.py:371-404) with recomputed LayerNorm residuals
+            // h2 holds the rows the current hidden state was normalised FROM; out-proj / FFN2 add their residual LayerNorm(h2)
+            // from it and write the next pre-LN sum over it.  The last layer's (or the asked-for layer's) output is written.
+            const bool want_rows = l + 1 == d.num_layers || output_layer == l + 1;
+            if ((rc = attention(l, h))) return rc;
+            out_io.res_ln = cur_ln;
+            if ((rc = linear(ctx, Wl.out, att, h2, BT, SI_ACT_NONE, h2, st, out_io))) return rc;
+            if ((rc = norm(h2, Wl.ln1_g, Wl.ln1_b, nullptr, h16))) return rc;
+            if ((rc = ffn1(l, h))) return rc;
+            ffn2_io.res_ln = cur_ln;
+            if ((rc = linear(ctx, Wl.ffn2, ffn, h2, BT, SI_ACT_NONE, h2, st, ffn2_io))) return rc;
+            if ((rc = norm(h2, Wl.ln2_g, Wl.ln2_b, want_rows ? h : nullptr, h16))) return rc;
+        } else if (!d.stable_layer_norm) {       // post-LN, every LayerNorm written; h16 = bf16(h) when e16
+            if ((rc = attention(l, h))) return rc;
+            if ((rc = linear(ctx, Wl.out, att, h2, BT, SI_ACT_NONE, h, st, out_io))) return rc;
+            if ((rc = si_tap(ctx, st, {h2, nh}, "layer%d.att_res", l))) return rc;
+            if ((rc = norm(h2, Wl.ln1_g, Wl.ln1_b, h, h16))) return rc;
+            if ((rc = si_tap(ctx, st, {h, nh}, "layer%d.ln1", l)) || (e16 && (rc = si_tap(ctx, st, {h16, nh, 2}, "layer%d.ln1.bf16", l)))) return rc;
+            if ((rc = ffn1(l, h))) return rc;
+            if ((rc = linear(ctx, Wl.ffn2, ffn, h2, BT, SI_ACT_NONE, h, st, ffn2_io))) return rc;
+            if ((rc = si_tap(ctx, st, {h2, nh}, "layer%d.ffn_res", l))) return rc;
+            if ((rc = norm(h2, Wl.ln2_g, Wl.ln2_b, h, h16))) return rc;
+            if ((rc = si_tap(ctx, st, {h, nh}, "layer%d.ln2", l)) || (e16 && (rc = si_tap(ctx, st, {h16, nh, 2}, "layer%d.ln2.bf16", l)))) return rc;
+        } else {                                 // pre-LN "stable" (modeling_hubert.py:504-547); residual adds are in place
             // (bf16 mode: the normalised rows feed GEMMs only -- their bf16 operand is all that is written)
-            if ((rc = si_launch_layernorm(ctx, h, nullptr, wf(ctx, Wl.ln1_g), wf(ctx, Wl.ln1_b), e16 ? nullptr : h2, BT, H, eps, 0, st, h16))) return rc;
-            if ((rc = e16 ? si_tap_at(ctx, "layer%d.ln1.bf16", l, h16, nh, st, 2) : si_tap_at(ctx, "layer%d.ln1", l, h2, nh, st))) return rc;
-            if (e16 && (rc = si_tap_at(ctx, "layer%d.h.bf16", l, h16, nh, st, 2))) return rc;
-            if ((rc = linear(ctx, Wl.qkv, h2, qkv_bf16 ? nullptr : qkv, BT, SI_ACT_NONE, nullptr, st, h16, qkv_bf16 ? qkv16 : nullptr))) return rc;
-            if (qkv_bf16) rc = si_launch_attention_bf16in(ctx, qkv16, B, T, H, d.num_heads, st, att16, vframes, d_rowoff, sum_t2);
-            else rc = si_launch_attention(ctx, qkv, att, B, T, H, d.num_heads, st, att16, ctx->opt_att_bf16, vframes, d_rowoff, sum_t2);
-            if (rc || (rc = tap_attention())) return rc;
-            if ((rc = linear(ctx, Wl.out, att, h, BT, SI_ACT_NONE, h, st, att16))) return rc;
-            if ((rc = si_tap_at(ctx, "layer%d.att_res", l, h, nh, st))) return rc;
-            if ((rc = si_launch_layernorm(ctx, h, nullptr, wf(ctx, Wl.ln2_g), wf(ctx, Wl.ln2_b), e16 ? nullptr : h2, BT, H, eps, 0, st, h16))) return rc;
-            if ((rc = e16 ? si_tap_at(ctx, "layer%d.ln2.bf16", l, h16, nh, st, 2) : si_tap_at(ctx, "layer%d.ln2", l, h2, nh, st))) return rc;
-            if ((rc = linear(ctx, Wl.ffn1, h2, e16 ? nullptr : ffn, BT, SI_ACT_GELU, nullptr, st, h16, ffn16, 0, e16 ? ffn_ld : 0))) return rc;
-            if ((rc = tap_ffn())) return rc;
-            if ((rc = linear(ctx, Wl.ffn2, ffn, h, BT, SI_ACT_NONE, h, st, ffn16, nullptr, e16 ? ffn_ld : 0))) return rc;
-            if ((rc = si_tap_at(ctx, "layer%d.ffn_res", l, h, nh, st))) return rc;
+            if ((rc = norm(h, Wl.ln1_g, Wl.ln1_b, e16 ? nullptr : h2, h16))) return rc;
+            if ((rc = e16 ? si_tap(ctx, st, {h16, nh, 2}, "layer%d.ln1.bf16", l) : si_tap(ctx, st, {h2, nh}, "layer%d.ln1", l))) return rc;
+            if ((rc = attention(l, h2))) return rc;
+            if ((rc = linear(ctx, Wl.out, att, h, BT, SI_ACT_NONE, h, st, out_io))) return rc;
+            if ((rc = si_tap(ctx, st, {h, nh}, "layer%d.att_res", l))) return rc;
+            if ((rc = norm(h, Wl.ln2_g, Wl.ln2_b, e16 ? nullptr : h2, h16))) return rc;
+            if ((rc = e16 ? si_tap(ctx, st, {h16, nh, 2}, "layer%d.ln2.bf16", l) : si_tap(ctx, st, {h2, nh}, "layer%d.ln2", l))) return rc;
+            if ((rc = ffn1(l, h2))) return rc;
+            if ((rc = linear(ctx, Wl.ffn2, ffn, h, BT, SI_ACT_NONE, h, st, ffn2_io))) return rc;
+            if ((rc = si_tap(ctx, st, {h, nh}, "layer%d.ffn_res", l))) return rc;
         }
         if (output_layer == l + 1) {
             // fairseq `extract_features(output_layer = L)` (I_da/src/hubert_feature_reader.py:60-65): the loop stops after layer
@@ -1118,10 +1145,10 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
         }
     }
     if (d.stable_layer_norm) {
-        if ((rc = si_launch_layernorm(ctx, h, nullptr, wf(ctx, L.enc_ln_g), wf(ctx, L.enc_ln_b), h2, BT, H, eps, 0, st))) return rc;
+        if ((rc = norm(h, L.enc_ln_g, L.enc_ln_b, h2))) return rc;
         std::swap(h, h2);
     }
-    if ((rc = si_tap(ctx, "last_hidden", h, BT * H, st))) return rc;
+    if ((rc = si_tap(ctx, st, {h, BT * H}, "last_hidden"))) return rc;
     // A9: final_layers = LN -> Linear(H, codebook_dim), always fp32
     if ((rc = si_launch_layernorm(ctx, h, nullptr, wf(ctx, L.head_ln_g), wf(ctx, L.head_ln_b), h2, BT, H, 1e-5f, 0, st))) return rc;
     if (!vl) return linear(ctx, L.head, h2, out_feats, BT, SI_ACT_NONE, nullptr, st);
@@ -1408,28 +1435,24 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
     Carver W{static_cast<char*>(workspace), workspace_bytes};
     // ---- ragged batch: the table [mel frames | rows of stage 0 (stretched frames) .. stage num_ups | GEMM rows of upsampler 1 .. num_ups]
     const bool vl = host_len != nullptr;
-    const int32_t* h_tab = nullptr;
-    int32_t* d_tab = nullptr;
+    VlTable tab;
     if (vl) {
-        std::vector<int32_t>& tab = ctx->vl_host;
-        tab.assign((size_t)(2 * d.num_ups + 2) * B, 0);
-        for (int b = 0; b < B; ++b) {
-            if (host_len[b] < 1 || host_len[b] > Tm) return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d holds %d mel frames, outside 1..%d", b, host_len[b], Tm);
-            long Lb = voc_tout(host_len[b], stretch);
-            if (Lb < 1) return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d (%d mel frames) stretches to nothing", b, host_len[b]);
-            tab[b] = host_len[b];
-            tab[(size_t)B + b] = (int32_t)Lb;
-            for (int i = 0; i < d.num_ups; ++i) {
-                const int u = d.up_rates[i], pad = (d.up_kernels[i] - u) / 2;
-                Lb *= u;
-                tab[(size_t)(2 + i) * B + b] = (int32_t)Lb;
-                tab[(size_t)(2 + d.num_ups + i) * B + b] = (int32_t)((pad + Lb - 1) / u + 1);
+        if (int trc = vl_table(ctx, W, (size_t)(2 * d.num_ups + 2) * B, st, "vocoder", tab, [&](int32_t* t) -> int {
+            for (int b = 0; b < B; ++b) {
+                if (host_len[b] < 1 || host_len[b] > Tm) return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d holds %d mel frames, outside 1..%d", b, host_len[b], Tm);
+                long Lb = voc_tout(host_len[b], stretch);
+                if (Lb < 1) return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d (%d mel frames) stretches to nothing", b, host_len[b]);
+                t[b] = host_len[b];
+                t[(size_t)B + b] = (int32_t)Lb;
+                for (int i = 0; i < d.num_ups; ++i) {
+                    const UpsGeom g = ups_geom(d, i, Lb);
+                    t[(size_t)(2 + i) * B + b] = (int32_t)g.Lout;
+                    t[(size_t)(2 + d.num_ups + i) * B + b] = g.M;
+                    Lb = g.Lout;
+                }
             }
-        }
-        d_tab = reinterpret_cast<int32_t*>(W.bytes(tab.size() * 4));
-        if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: vocoder workspace carve exceeded its own estimate");
-        if (int rc = vl_upload(ctx, d_tab, st)) return rc;
-        h_tab = tab.data();
+            return SI_OK;
+        })) return trc;
         SI_HIP_CHECK(hipMemsetAsync(wav_out, 0, (size_t)B * Lwav * sizeof(float), st));   // samples past a clip's own end read as silence
     }
     float* ext_ws = W.floats((size_t)Bc_max * Tout * Ly.mel_ld);
@@ -1458,139 +1481,117 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
     auto run = [&](int b0, int Bc, float* ext, float* const* buf, unsigned short* const* h16, hipStream_t st) -> int {
         int rc;
         // Taps of the fp16 activation stream (names ending in ".f16": the raw fp16 tensor as stored, n elements).  Copies only, behind
-        // the launch that produced the tensor: a registered capture changes neither which kernel runs nor any value.  Named and
-        // looked up only while some capture is registered.
-        auto tap16 = [&](const void* src, long n, const char* fmt, int a, int b = 0, int c = 0) -> int {
-            if (!r16 || ctx->dbg_capture.empty()) return SI_OK;
-            char name[48];
-            snprintf(name, sizeof(name), fmt, a, b, c);
-            return si_tap(ctx, name, src, n, st, 2);
+        // the launch that produced the tensor: a registered capture changes neither which kernel runs nor any value; without one, none is named.
+        auto tap16 = [&](const void* src, long n, const char* fmt, int a = 0, int b = 0, int c = 0) -> int {
+            return (r16 && !ctx->dbg_capture.empty()) ? si_tap(ctx, st, {src, n, 2}, fmt, a, b, c) : SI_OK;
         };
-        // ragged batch: device / host rows of the chunk's clips -- dTm mel frames, dLs(s) rows at stage s (0 = stretched frames), dMt(i) GEMM rows of upsampler i
-        const int32_t* dTm = vl ? d_tab + b0 : nullptr;
-        auto dLs = [&](int sidx) -> const int32_t* { return vl ? d_tab + (size_t)(1 + sidx) * B + b0 : nullptr; };
-        auto hLs = [&](int sidx) -> const int32_t* { return vl ? h_tab + (size_t)(1 + sidx) * B + b0 : nullptr; };
-        auto dMt = [&](int i) -> const int32_t* { return vl ? d_tab + (size_t)(2 + d.num_ups + i) * B + b0 : nullptr; };
-        auto hMt = [&](int i) -> const int32_t* { return vl ? h_tab + (size_t)(2 + d.num_ups + i) * B + b0 : nullptr; };
+        // ragged batch: device / host rows of the chunk's clips -- dTm mel frames, dLs(s) rows at stage s (0 = stretched frames)
+        const int32_t* dTm = vl ? tab.dev + b0 : nullptr;
+        auto dLs = [&](int sidx) -> const int32_t* { return vl ? tab.dev + (size_t)(1 + sidx) * B + b0 : nullptr; };
+        auto hLs = [&](int sidx) -> const int32_t* { return vl ? tab.host + (size_t)(1 + sidx) * B + b0 : nullptr; };
         auto rows_of = [&](const int32_t* h, long uniform) { if (!h) return (double)Bc * uniform; double r = 0; for (int b = 0; b < Bc; ++b) r += h[b]; return r; };
-        // a same-length convolution at stage sidx: every clip reads and writes its own rows
-        auto seg_conv = [&](TapGemmParams& q, int sidx) { if (vl) { q.seg_lin = q.seg_m = q.seg_orows = dLs(sidx); q.olim_mul = q.ldo; q.seg_m_host = hLs(sidx); } };
+        // A same-length convolution on the L rows of stage sidx (0: the stretched frames), `cin` real input channels stored ld_in apart:
+        // every clip reads and writes its own rows.  Operands, prologue slope and epilogue are the caller's.
+        auto stage_conv = [&](const GemmW& G, int sidx, long L, int ld_in, int cin, int dil) {
+            TapGemmParams p = gemm_params(ctx, G);
+            p.nseg = Bc; p.Lin = (int)L; p.M = (int)L; p.ldx = ld_in; p.x_seg_stride = L * ld_in;
+            p.dil = dil; p.pad = dil * (G.ntaps - 1) / 2; p.ldo = G.N; p.o_seg_stride = L * G.N; p.olimit = p.o_seg_stride;
+            p.algo_macs = rows_of(hLs(sidx), L) * G.N * (double)cin * G.ntaps;
+            if (vl) { p.seg_lin = p.seg_m = p.seg_orows = dLs(sidx); p.olim_mul = p.ldo; p.seg_m_host = hLs(sidx); }
+            return p;
+        };
+        // Upsampler i on Lc input rows of c channels: leaky_relu -> ConvTranspose1d as `u` phases of a (k + u - 1) / u-tap conv (row u'
+        // reads input rows u', u'-1, ...), reading x / x16 and writing U / U16 as the arithmetic mode stores them; pro_slope is the caller's.
+        auto ups_desc = [&](int i, long Lc, int c, const float* x, const unsigned short* x16, float* U, unsigned short* U16) {
+            const UpsGeom g = ups_geom(d, i, Lc);
+            const int cout = stage_channels(ctx, i);
+            TapGemmParams p = gemm_params(ctx, Ly.ups[i]);
+            p.x = x; p.out = U;
+            if (opr) { p.x = nullptr; p.x16 = x16; p.out16 = U16; p.out16_slope = r16 ? 1.f : 0.1f; }
+            if (r16) p.out = nullptr;
+            p.nseg = Bc; p.Lin = (int)Lc; p.M = g.M; p.ldx = c; p.x_seg_stride = Lc * c;
+            p.dil = -1; p.ldo = g.u * cout; p.o_seg_stride = g.Lout * cout; p.ooff = -(long)g.pad * cout; p.olimit = g.Lout * cout;
+            p.algo_macs = rows_of(hLs(i), Lc) * (double)(d.up_initial_channel >> i) * (double)(d.up_initial_channel >> (i + 1)) * d.up_kernels[i];   // Cin*Cout*k*Lin (real widths)
+            const size_t mrow = (size_t)(2 + d.num_ups + i) * B + b0;   // the chunk's clips in the table's GEMM-row column of upsampler i
+            if (vl) { p.seg_lin = dLs(i); p.seg_m = tab.dev + mrow; p.seg_orows = dLs(i + 1); p.olim_mul = cout; p.seg_m_host = tab.host + mrow; }
+            return p;
+        };
+        // Does upsampler i take ACTIVATED input?  The early upsamplers (N = 2048 / 1024) on the fp16 stream are real GEMMs: the
+        // one-tile-per-CU kernel (gemmcu.hip, TC mode) runs them wherever it covers the layer's geometry (always = true: whatever the
+        // batch -- the two forms round differently, and a clip's samples must not depend on its batch); SI_VOC_UPSGEMM=0: the tap-GEMM.
+        // The producer of its input (conv_pre / the launch that completes the previous stage's MRF sum) then stores leaky_relu(x, 0.1)
+        // -- the upsampler's own first statement (models.py:110) applied once to the fp32 value instead of to every fragment it is read
+        // into -- and the upsampler takes its input as it is.  Asked ONCE per upsampler, the answer goes to both sides.  (The streaming
+        // kernel, which applies its own leaky-ReLU, never meets an activated input only because si_launch_upsample_stream takes
+        // N = Cin in {64, 128} and gemmcu_tc_pick N % 256 == 0: facts of upsample.hip and gemmcu.hip.)
+        auto ups_takes_activated = [&](int i, long Lc, int c) -> bool {
+            if (!r16 || !ctx->opt_voc_upsgemm || i >= d.num_ups || Ly.ups[i].math != SI_MATH_F16 || !Ly.ups[i].has_bias) return false;
+            return si_gemmcu_tc_covers(ctx, ups_desc(i, Lc, c, nullptr, h16[0], nullptr, h16[2]), true);
+        };
         // A14: stretch + transpose to channels-last
         if ((rc = si_launch_extend_mel(ctx, mel + (size_t)b0 * d.num_mels * Tm, Bc, d.num_mels, Tm, (int)Tout, stretch, ext, Ly.mel_ld, st, dTm, dLs(0)))) return rc;
-        // Will upsampler i run on gemmcu.hip's TC instantiations?  Its producer (conv_pre / the last launch of the previous stage's MRF
-        // sum) then stores leaky_relu(x, 0.1) -- the upsampler's own first statement (models.py:110) applied once to the fp32 value
-        // instead of to every fragment it is read into -- and the upsampler takes its input as it is.
-        auto ups_on_gemmcu = [&](int i, long Lc_i, int c_i) -> bool {
-            if (!r16 || !ctx->opt_voc_upsgemm || i >= d.num_ups) return false;
-            const GemmW& G = Ly.ups[i];
-            if (G.math != SI_MATH_F16 || !G.has_bias) return false;
-            const int u = d.up_rates[i], k = d.up_kernels[i], cout = stage_channels(ctx, i), pad = (k - u) / 2;
-            const long Lo_i = Lc_i * u;
-            TapGemmParams p = gemm_params(ctx, G);
-            p.x16 = h16[0]; p.out16 = h16[2]; p.out16_slope = 1.f;
-            p.nseg = Bc; p.Lin = (int)Lc_i; p.M = (int)((pad + Lo_i - 1) / u + 1); p.ldx = c_i; p.x_seg_stride = Lc_i * c_i;
-            p.dil = -1; p.ldo = u * cout; p.o_seg_stride = Lo_i * cout; p.ooff = -(long)pad * cout; p.olimit = Lo_i * cout; p.pro_slope = 0.1f;
-            if (vl) { p.seg_lin = dLs(i); p.seg_m = dMt(i); p.seg_orows = dLs(i + 1); p.olim_mul = cout; p.seg_m_host = hMt(i); }
-            return si_gemmcu_tc_covers(ctx, p, true);                 // by the layer's geometry alone: a clip's samples must not depend on its batch
-        };
         // B1: conv_pre
-        float* x = buf[0];
-        float* xs = buf[1];
+        float *x = buf[0], *xs = buf[1];
         unsigned short *x16 = h16[0], *xs16 = h16[1], *U16 = h16[2], *t16 = h16[3];
-        {
-            TapGemmParams p = gemm_params(ctx, Ly.pre);
-            p.x = ext; p.out = x;
-            if (opr) { p.out16 = x16; p.out16_slope = (r16 && !ups_on_gemmcu(0, Tout, d.up_initial_channel)) ? 1.f : 0.1f; }
-            if (r16) p.out = nullptr;
-            p.nseg = Bc; p.Lin = (int)Tout; p.M = (int)Tout; p.ldx = Ly.mel_ld; p.x_seg_stride = Tout * Ly.mel_ld;
-            p.algo_macs = rows_of(hLs(0), Tout) * d.up_initial_channel * (double)d.num_mels * 7;
-            p.pad = 3; p.ldo = d.up_initial_channel; p.o_seg_stride = Tout * d.up_initial_channel; p.olimit = p.o_seg_stride;
-            seg_conv(p, 0);
-            if ((rc = si_launch_tapgemm(ctx, Ly.pre.math, p, st))) return rc;
-            if ((rc = tap16(x16, (long)Bc * Tout * d.up_initial_channel, "pre.f16", 0))) return rc;
-        }
+        const float in_slope = (opr && !r16) ? 1.f : 0.1f;   // what a conv applies to a stage's tensor: operand-ready inputs are already activated
+        bool act_in = ups_takes_activated(0, Tout, d.up_initial_channel);   // of the upsampler that reads x16
+        TapGemmParams pre = stage_conv(Ly.pre, 0, Tout, Ly.mel_ld, d.num_mels, 1);
+        pre.x = ext; pre.out = x;
+        if (opr) { pre.out16 = x16; pre.out16_slope = (r16 && !act_in) ? 1.f : 0.1f; }
+        if (r16) pre.out = nullptr;
+        if ((rc = si_launch_tapgemm(ctx, Ly.pre.math, pre, st))) return rc;
+        if ((rc = tap16(x16, (long)Bc * Tout * d.up_initial_channel, "pre.f16"))) return rc;
         long Lc = Tout; int c = d.up_initial_channel;
         for (int i = 0; i < d.num_ups; ++i) {
-            const int u = d.up_rates[i], k = d.up_kernels[i], cout = stage_channels(ctx, i), pad = (k - u) / 2;
-            const long Lo = Lc * u;
+            const GemmW& G = Ly.ups[i];
+            const int cout = stage_channels(ctx, i);
+            const long Lo = Lc * d.up_rates[i];
             float* U = buf[2];
-            // B2: leaky_relu(0.1) -> ConvTranspose1d as `u` phases of a 2-tap conv: row u' reads input rows u', u'-1, ...
+            // B2: the upsampler
+            TapGemmParams p = ups_desc(i, Lc, c, x, x16, U, U16);
             bool ups_done = false;
-            if (r16 && (fuse_mask & 2) && u == 2 && k == 4) {          // (SI_VOC_FUSE: bit 1 = this kernel, the width bits = the ResBlock kernels)
+            if (r16 && (fuse_mask & 2) && d.up_rates[i] == 2 && d.up_kernels[i] == 4 &&   // (SI_VOC_FUSE: bit 1 = this kernel, the width bits = the ResBlock kernels)
+                G.has_bias && G.Npad == G.N && G.math == SI_MATH_F16) {
                 // the late upsamplers (128 / 64 input channels) are HBM-bound: a persistent streaming kernel (upsample.hip)
-                const GemmW& G = Ly.ups[i];
                 UpsampleParams q{};
-                q.x16 = x16; q.w = reinterpret_cast<const unsigned short*>(ctx->wdev + G.w); q.bias = reinterpret_cast<const float*>(ctx->wdev + G.bias);
-                q.out16 = U16; q.B = Bc; q.Lin = (int)Lc; q.M = (int)((pad + Lo - 1) / u + 1); q.Cin = c; q.N = u * cout; q.taps = G.ntaps;
-                q.ooff = (long)pad * cout; q.o_clip_stride = Lo * cout; q.o_clip_elems = Lo * cout;
-                q.lens_lin = dLs(i); q.lens_m = dMt(i); q.lens_m_host = hMt(i);
-                if (G.has_bias && G.Npad == G.N && G.math == SI_MATH_F16) {
-                    rc = si_launch_upsample_stream(ctx, q, st);
-                    if (rc < 0) return rc;
-                    ups_done = rc == 0;
-                }
+                q.x16 = p.x16; q.w = static_cast<const unsigned short*>(p.w); q.bias = p.bias; q.out16 = p.out16;
+                q.B = p.nseg; q.Lin = p.Lin; q.M = p.M; q.Cin = p.ldx; q.N = p.ldo; q.taps = p.ntaps;
+                q.ooff = -p.ooff; q.o_clip_stride = p.o_seg_stride; q.o_clip_elems = p.olimit;
+                q.lens_lin = p.seg_lin; q.lens_m = p.seg_m; q.lens_m_host = p.seg_m_host;
+                rc = si_launch_upsample_stream(ctx, q, st);
+                if (rc < 0) return rc;
+                ups_done = rc == 0;
             }
             if (!ups_done) {
-                TapGemmParams p = gemm_params(ctx, Ly.ups[i]);
-                p.x = x; p.out = U;
-                if (opr) { p.x = nullptr; p.x16 = x16; p.out16 = U16; p.out16_slope = r16 ? 1.f : 0.1f; }
-                if (r16) p.out = nullptr;
-                p.nseg = Bc; p.Lin = (int)Lc; p.M = (int)((pad + Lo - 1) / u + 1); p.ldx = c; p.x_seg_stride = Lc * c;
-                p.dil = -1; p.ldo = u * cout; p.o_seg_stride = Lo * cout; p.ooff = -(long)pad * cout; p.olimit = Lo * cout;
-                const bool pre_act = ups_on_gemmcu(i, Lc, c);       // (its producer stored the activated input)
-                p.pro_slope = ((opr && !r16) || pre_act) ? 1.f : 0.1f;   // operand-ready inputs are already activated
-                p.algo_macs = rows_of(hLs(i), Lc) * (double)(d.up_initial_channel >> i) * (double)(d.up_initial_channel >> (i + 1)) * k;   // Cin*Cout*k*Lin (real widths)
-                if (vl) { p.seg_lin = dLs(i); p.seg_m = dMt(i); p.seg_orows = dLs(i + 1); p.olim_mul = cout; p.seg_m_host = hMt(i); }
-                // the early upsamplers (N = 2048 / 1024) on the fp16 stream are real GEMMs: the one-tile-per-CU kernel (gemmcu.hip, TC
-                // mode) wherever it covers the layer's geometry (whatever the batch: the two forms round differently); SI_VOC_UPSGEMM=0: the tap-GEMM
-                int urc = 1;
-                if (r16 && ctx->opt_voc_upsgemm && Ly.ups[i].math == SI_MATH_F16 && Ly.ups[i].has_bias) urc = si_launch_gemmcu_tc(ctx, p, st, true);
+                p.pro_slope = act_in ? 1.f : in_slope;
+                const int urc = act_in ? si_launch_gemmcu_tc(ctx, p, st, true) : 1;
                 if (urc < 0) return urc;
-                if (urc > 0 && (rc = si_launch_tapgemm(ctx, Ly.ups[i].math, p, st))) return rc;
+                if (urc > 0 && (rc = si_launch_tapgemm(ctx, G.math, p, st))) return rc;
             }
-            if (!r16 && (rc = si_tap(ctx, upn[i], U, (long)Bc * Lo * cout, st))) return rc;
             const long nst = (long)Bc * Lo * cout;                    // elements of every tensor of this stage
+            if (!r16 && (rc = si_tap(ctx, st, {U, nst}, upn[i]))) return rc;
             if ((rc = tap16(U16, nst, "ups%d.f16", i))) return rc;
             // B3: multi-receptive-field fusion: mean over the resblocks, accumulated into xs by the last conv of each
-            const bool act_next = ups_on_gemmcu(i + 1, Lo, cout);   // the launch that completes the sum stores the next upsampler's activated input
+            const bool act_next = ups_takes_activated(i + 1, Lo, cout);
+            // What the launch that ends a step of ResBlock j stores; the block's `last` one adds its share of the MRF mean (alpha) to the
+            // earlier blocks' (accumulate).  The 16-bit copy is wanted by the block's next conv, or -- once the mean is complete -- by the next
+            // stage's upsampler (conv_post reads fp32), and carries that reader's leaky-ReLU unless the reader applies it itself (fp16 stream).
+            struct BlockOut { float alpha; int accumulate; bool copy16; float slope16; };
+            auto block_out = [&](int j, bool last) {
+                const bool completes = last && j == nk - 1;
+                return BlockOut{last ? 1.0f / nk : 1.f, last && j > 0, r16 || !last || (completes && i + 1 < d.num_ups),
+                                (r16 && !(completes && act_next)) ? 1.f : 0.1f};
+            };
             for (int j = 0; j < nk; ++j) {
                 const ResW& R = Ly.rbs[(size_t)i * nk + j];
                 const int rk = d.rb_kernels[j];
                 const float* y = U;
                 const unsigned short* y16 = U16;
-                if (d.resblock_type == 2) {
-                    // ResBlock2 (I_ea/hifi_gan/models.py:63-68): per dilation x = x + conv_d(lrelu(x)) -- ONE convolution with the
-                    // residual (and, on the block's last one, the 1 / num_kernels scale and the MRF accumulate) in its epilogue
-                    for (int n = 0; n < d.num_dil; ++n) {
-                        const int dl = d.rb_dilations[j][n];
-                        const bool last = (n == d.num_dil - 1);
-                        float* ynext = last ? xs : buf[4 + (n & 1)];
-                        unsigned short* ynext16 = last ? xs16 : h16[4 + (n & 1)];
-                        TapGemmParams q = gemm_params(ctx, R.c1[n]);
-                        q.x = y; q.out = ynext; q.res = y;
-                        if (opr) {
-                            q.x = nullptr; q.x16 = y16;
-                            if (r16) { q.res = nullptr; q.res16 = y16; q.out = nullptr; }
-                            const bool want16 = r16 || !last || (j == nk - 1 && i + 1 < d.num_ups);
-                            if (want16) { q.out16 = ynext16; q.out16_slope = (r16 && !(act_next && last && j == nk - 1)) ? 1.f : 0.1f; }
-                        }
-                        q.pro_slope = (opr && !r16) ? 1.f : 0.1f;          // operand-ready inputs are already activated
-                        q.nseg = Bc; q.Lin = (int)Lo; q.M = (int)Lo; q.ldx = cout; q.x_seg_stride = Lo * cout;
-                        q.dil = dl; q.pad = dl * (rk - 1) / 2; q.ldo = cout; q.o_seg_stride = Lo * cout; q.olimit = q.o_seg_stride;
-                        if (last) { q.alpha = 1.0f / nk; q.accumulate = (j > 0); q.acc16 = (r16 && j > 0); }
-                        seg_conv(q, i + 1);
-                        if (vl) q.algo_macs = rows_of(hLs(i + 1), Lo) * (double)cout * cout * rk;
-                        if ((rc = si_launch_tapgemm(ctx, R.c1[n].math, q, st))) return rc;
-                        if ((rc = tap16(ynext16, nst, "stage%d.rb%d.p%d.f16", i, j, n))) return rc;
-                        y = ynext;
-                        y16 = ynext16;
-                    }
-                    continue;
-                }
-                if (r16 && (fuse_mask & cout) && ctx->opt_voc_chain && d.num_dil == 3 && !(act_next && j == nk - 1)) {
-                    // full-rate stage: the whole resblock (three pairs) as one kernel, residual stream in LDS (reschain.hip)
+                const BlockOut whole = block_out(j, true);
+                if (r16 && d.resblock_type != 2 && (fuse_mask & cout) && ctx->opt_voc_chain && d.num_dil == 3 && whole.slope16 == 1.f) {
+                    // full-rate stage: the whole resblock (three pairs) as one kernel, residual stream in LDS (reschain.hip: raw fp16 out)
                     ResChainParams cp{};
-                    cp.y16 = U16; cp.out16 = xs16; cp.B = Bc; cp.L = (int)Lo; cp.k = rk; cp.alpha = 1.0f / nk; cp.accumulate = j > 0;
+                    cp.y16 = U16; cp.out16 = xs16; cp.B = Bc; cp.L = (int)Lo; cp.k = rk; cp.alpha = whole.alpha; cp.accumulate = whole.accumulate;
                     cp.lens = dLs(i + 1); cp.lens_host = hLs(i + 1);
                     for (int n = 0; n < 3; ++n) {
                         const TapGemmParams w1 = gemm_params(ctx, R.c1[n]), w2 = gemm_params(ctx, R.c2[n]);
@@ -1606,61 +1607,54 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
                 }
                 for (int n = 0; n < d.num_dil; ++n) {
                     const int dl = d.rb_dilations[j][n];
-                    const bool last_n = (n == d.num_dil - 1);
-                    if (r16 && (fuse_mask & cout)) {
-                        // narrow stages: conv pair as one kernel, the intermediate stays in LDS (respair.hip)
-                        const TapGemmParams w1 = gemm_params(ctx, R.c1[n]), w2 = gemm_params(ctx, R.c2[n]);
-                        unsigned short* yn16 = last_n ? xs16 : h16[4 + (n & 1)];
-                        const int frc = si_launch_respair(ctx, cout, y16, yn16, w1.w, w2.w, w1.bias, w2.bias, Bc, (int)Lo, rk, dl,
-                                                          last_n ? 1.0f / nk : 1.0f, last_n && j > 0, st, dLs(i + 1), hLs(i + 1),
-                                                          (act_next && last_n && j == nk - 1) ? 0.1f : 1.f);
-                        if (frc < 0) return frc;
-                        if (frc == 0) {
-                            if ((rc = tap16(yn16, nst, "stage%d.rb%d.p%d.f16", i, j, n))) return rc;
-                            y16 = yn16;
-                            continue;
-                        }
-                    }
-                    float* t = buf[3];
-                    TapGemmParams p = gemm_params(ctx, R.c1[n]);
-                    p.x = y; p.out = t;
-                    if (opr) { p.x = nullptr; p.x16 = y16; p.out = nullptr; p.out16 = t16; p.out16_slope = 0.1f; }
-                    p.pro_slope = (opr && !r16) ? 1.f : 0.1f;
-                    p.nseg = Bc; p.Lin = (int)Lo; p.M = (int)Lo; p.ldx = cout; p.x_seg_stride = Lo * cout;
-                    p.dil = dl; p.pad = dl * (rk - 1) / 2; p.ldo = cout; p.o_seg_stride = Lo * cout; p.olimit = p.o_seg_stride;
-                    seg_conv(p, i + 1);
-                    if (vl) p.algo_macs = rows_of(hLs(i + 1), Lo) * (double)cout * cout * rk;
-                    if ((rc = si_launch_tapgemm(ctx, R.c1[n].math, p, st))) return rc;
                     const bool last = (n == d.num_dil - 1);
                     float* ynext = last ? xs : buf[4 + (n & 1)];
                     unsigned short* ynext16 = last ? xs16 : h16[4 + (n & 1)];
-                    TapGemmParams q = gemm_params(ctx, R.c2[n]);
-                    q.x = t; q.out = ynext; q.res = y;
-                    if (opr) {
-                        q.x = nullptr; q.x16 = t16;
-                        if (r16) { q.res = nullptr; q.res16 = y16; q.out = nullptr; }
-                        // the 16-bit copy is wanted by the next c1 of this block, or -- once the MRF mean is complete --
-                        // by the next stage's upsampler; conv_post reads fp32
-                        const bool want16 = r16 || !last || (j == nk - 1 && i + 1 < d.num_ups);
-                        if (want16) { q.out16 = ynext16; q.out16_slope = (r16 && !(act_next && last && j == nk - 1)) ? 1.f : 0.1f; }
+                    const BlockOut o = block_out(j, last);
+                    // the convolution that ends this step: G on (in, in16) -> (ynext, ynext16) = y + conv, scaled, accumulated and copied as `o` says
+                    auto residual_conv = [&](const GemmW& G, int dil, float slope, const float* in, const unsigned short* in16) {
+                        TapGemmParams q = stage_conv(G, i + 1, Lo, cout, cout, dil);
+                        q.x = in; q.out = ynext; q.res = y; q.pro_slope = slope;
+                        if (opr) {
+                            q.x = nullptr; q.x16 = in16;
+                            if (r16) { q.res = nullptr; q.res16 = y16; q.out = nullptr; }
+                            if (o.copy16) { q.out16 = ynext16; q.out16_slope = o.slope16; }
+                        }
+                        q.alpha = o.alpha; q.accumulate = o.accumulate; q.acc16 = r16 && o.accumulate;
+                        return si_launch_tapgemm(ctx, G.math, q, st);
+                    };
+                    if (d.resblock_type == 2) {
+                        // ResBlock2 (I_ea/hifi_gan/models.py:63-68): per dilation x = x + conv_d(lrelu(x)) -- ONE convolution with the
+                        // residual (and, on the block's last one, the 1 / num_kernels scale and the MRF accumulate) in its epilogue
+                        if ((rc = residual_conv(R.c1[n], dl, in_slope, y, y16))) return rc;
+                    } else {
+                        int frc = 1;
+                        if (r16 && (fuse_mask & cout)) {
+                            // narrow stages: conv pair as one kernel, the intermediate stays in LDS (respair.hip)
+                            const TapGemmParams w1 = gemm_params(ctx, R.c1[n]), w2 = gemm_params(ctx, R.c2[n]);
+                            frc = si_launch_respair(ctx, cout, y16, ynext16, w1.w, w2.w, w1.bias, w2.bias, Bc, (int)Lo, rk, dl, o.alpha, o.accumulate, st,
+                                                    dLs(i + 1), hLs(i + 1), o.slope16);
+                            if (frc < 0) return frc;
+                        }
+                        if (frc > 0) {
+                            float* t = buf[3];
+                            TapGemmParams p = stage_conv(R.c1[n], i + 1, Lo, cout, cout, dl);
+                            p.x = y; p.out = t; p.pro_slope = in_slope;
+                            if (opr) { p.x = nullptr; p.x16 = y16; p.out = nullptr; p.out16 = t16; p.out16_slope = 0.1f; }
+                            if ((rc = si_launch_tapgemm(ctx, R.c1[n].math, p, st))) return rc;
+                            if ((rc = residual_conv(R.c2[n], 1, opr ? 1.f : 0.1f, t, t16))) return rc;   // (the intermediate is stored activated in the 16-bit modes)
+                        }
                     }
-                    q.nseg = Bc; q.Lin = (int)Lo; q.M = (int)Lo; q.ldx = cout; q.x_seg_stride = Lo * cout;
-                    q.dil = 1; q.pad = (rk - 1) / 2; q.ldo = cout; q.o_seg_stride = Lo * cout; q.olimit = q.o_seg_stride;
-                    q.pro_slope = opr ? 1.f : 0.1f;               // the intermediate is stored activated in the 16-bit modes
-                    if (last) { q.alpha = 1.0f / nk; q.accumulate = (j > 0); q.acc16 = (r16 && j > 0); }
-                    seg_conv(q, i + 1);
-                    if (vl) q.algo_macs = rows_of(hLs(i + 1), Lo) * (double)cout * cout * rk;
-                    if ((rc = si_launch_tapgemm(ctx, R.c2[n].math, q, st))) return rc;
                     if ((rc = tap16(ynext16, nst, "stage%d.rb%d.p%d.f16", i, j, n))) return rc;
                     y = ynext;
                     y16 = ynext16;
                 }
             }
-            if (!r16 && (rc = si_tap(ctx, stn[i], xs, (long)Bc * Lo * cout, st))) return rc;
+            if (!r16 && (rc = si_tap(ctx, st, {xs, nst}, stn[i]))) return rc;
             if ((rc = tap16(xs16, nst, "stage%d.f16", i))) return rc;
             std::swap(x, xs);
             std::swap(x16, xs16);
-            Lc = Lo; c = cout;
+            Lc = Lo; c = cout; act_in = act_next;
         }
         // B4: leaky_relu(0.01) -> conv_post -> tanh
         return si_launch_conv_post(ctx, x, wf(ctx, Ly.post_w), wf(ctx, Ly.post_b), Bc, (int)Lc, c, 7, wav_out + (size_t)b0 * Lwav, st,
@@ -1810,25 +1804,24 @@ static int mel_run(si_ctx* ctx, const float* wave22, const int32_t* mask_start, 
     float* spec = W.floats((size_t)B * Tm * FE_LDSPEC);
     const int32_t *d_n = nullptr, *d_tm = nullptr;
     if (host_len) {                                                    // table [samples | frames] per clip
-        std::vector<int32_t>& tab = ctx->vl_host;
-        tab.assign((size_t)2 * B, 0);
-        for (int b = 0; b < B; ++b) {
-            if (host_len[b] <= FE_PAD || host_len[b] > N22 || si_mel_frames(host_len[b]) < 1)
-                return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d holds %d samples: too short for the mel front-end or longer than its row (%d)", b, host_len[b], N22);
-            tab[b] = host_len[b];
-            tab[(size_t)B + b] = si_mel_frames(host_len[b]);
-        }
-        int32_t* d_tab = reinterpret_cast<int32_t*>(W.bytes(tab.size() * 4));
-        if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: mel workspace carve exceeded its own estimate");
-        if ((rc = vl_upload(ctx, d_tab, st))) return rc;
-        d_n = d_tab; d_tm = d_tab + B;
+        VlTable tab;
+        if ((rc = vl_table(ctx, W, (size_t)2 * B, st, "mel", tab, [&](int32_t* t) -> int {
+            for (int b = 0; b < B; ++b) {
+                if (host_len[b] <= FE_PAD || host_len[b] > N22 || si_mel_frames(host_len[b]) < 1)
+                    return si_fail(ctx, SI_EINVAL, "ragged batch: clip %d holds %d samples: too short for the mel front-end or longer than its row (%d)", b, host_len[b], N22);
+                t[b] = host_len[b];
+                t[(size_t)B + b] = si_mel_frames(host_len[b]);
+            }
+            return SI_OK;
+        }))) return rc;
+        d_n = tab.dev; d_tm = tab.dev + B;
     }
     if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: mel workspace carve exceeded its own estimate");
     const float* hann = reinterpret_cast<const float*>(ctx->fe_dev + ctx->fe_hann);
     if (normalize && (rc = si_launch_wave_peak(ctx, wave22, mask_start, mask_end, B, N22, peak, st, d_n))) return rc;
     if ((rc = si_launch_mel_frames(ctx, wave22, mask_start, mask_end, peak, hann, B, N22, Tm, FE_HOP, FE_PAD, FE_NFFT, FE_KC, normalize, frames, st, d_n, d_tm)))
         return rc;
-    if ((rc = si_tap(ctx, "mel_frames", frames, (long)B * Tm * FE_FRAME, st))) return rc;
+    if ((rc = si_tap(ctx, st, {frames, (long)B * Tm * FE_FRAME}, "mel_frames"))) return rc;
     // STFT as two exact-fp32 GEMMs on the folded frames: (B*Tm, 528) x (528, 513) -> re, (B*Tm, 512) x (512, 513) -> im
     const int npad = si_round_up(FE_NBIN, si_pick_bn(FE_NBIN));
     for (int half = 0; half < 2; ++half) {
