@@ -349,6 +349,63 @@ int si_mel_frontend(si_ctx* ctx, const float* wave22, const int32_t* mask_start,
 int si_mel_frontend_varlen(si_ctx* ctx, const float* wave22, const int32_t* mask_start, const int32_t* mask_end, const int32_t* sample_len,
                            int normalize, int B, int N22, float* mel_out, void* workspace, size_t workspace_bytes, si_stream_t stream);
 
+/* ---- Several gaps per clip -------------------------------------------------------------------------------------------------
+ * The reference's script zeroes ONE span per file (I_ea/predict.py:132-134 at 16 kHz, :99-102 at 22.05 kHz) and decides / splices the
+ * frames of that one span (:164-168,184-187).  The calls below generalise exactly those lines to 0 .. SI_MAX_SPANS spans per clip,
+ * different per clip of a batch; one span per clip reproduces the single-span entry points bit for bit.
+ *
+ * si_span_table: the zeroed sample spans of a batch as a CSR table.  Clip b owns entries [off[b], off[b + 1]) of start / len
+ * (samples of the side the call works on: 16 kHz for the encoder, 22.05 kHz for the mel front-end), sorted by start, disjoint
+ * (touching is allowed), every len >= 0 and start >= 0; the part of a span past the clip's end is ignored.  The table is given
+ * twice: host_* (HOST int32) is what the call validates -- a table it refuses is never launched -- and span_* (DEVICE int32, the
+ * same values, owned by the caller) is what the kernels read.  The library cannot see the device copy: keeping the two equal is the
+ * CALLER's duty.  A device copy that differs from the validated host copy is read unvalidated -- the kernels stay inside the clip
+ * (the span walk ends at off[b + 1], the conv0 fix-up is clamped to its window), so the result is WRONG OUTPUT, not a fault, and
+ * no error is reported.  SI_MAX_SPANS is the cap on spans per clip. */
+#define SI_MAX_SPANS 16
+typedef struct si_span_table {
+    int32_t struct_size;            /* = sizeof(si_span_table) */
+    int32_t num_clips;              /* B of the call */
+    int32_t num_spans;              /* = host_off[num_clips] */
+    int32_t reserved;
+    const int32_t* host_off;        /* HOST (num_clips + 1), host_off[0] = 0, non-decreasing */
+    const int32_t* host_start;      /* HOST (num_spans) */
+    const int32_t* host_len;        /* HOST (num_spans) */
+    const int32_t* span_off;        /* DEVICE copies of the three */
+    const int32_t* span_start;
+    const int32_t* span_len;
+} si_span_table;
+
+/* si_hubert_forward / si_hubert_forward_varlen with a span table in place of mask_start / mask_len: the zero-mask of
+ * I_ea/predict.py:132-134 for every span of the clip, then the processor's normalisation (:135-141) and CustomModel.forward
+ * (I_ea/model.py:80-89).  sample_len: HOST int32 (B) = ragged batch as si_hubert_forward_varlen, or NULL = every clip holds N samples. */
+int si_hubert_forward_spans(si_ctx* ctx, const float* wav, const si_span_table* spans, const int32_t* sample_len, int normalize,
+                            int B, int N, float* out_feats, void* workspace, size_t workspace_bytes, si_stream_t stream);
+
+/* si_mel_frontend / si_mel_frontend_varlen with a span table in place of [mask_start, mask_end): `wave_22[start:end] = 0` of
+ * I_ea/predict.py:99-102 for every span, then normalize * 0.95 and get_mel (:104-106).  sample_len as above. */
+int si_mel_frontend_spans(si_ctx* ctx, const float* wave22, const si_span_table* spans, const int32_t* sample_len, int normalize,
+                          int B, int N22, float* mel_out, void* workspace, size_t workspace_bytes, si_stream_t stream);
+
+/* si_codebook_splice over a FRAME TABLE: entry f < F names frame frame_pos[f] of clip frame_clip[f] (device int32 (F) each) -- the
+ * masked frames of all gaps of all clips, flattened; the gather + arg-max + centroid splice of I_ea/predict.py:164-168,171,184-187 per
+ * entry.  labels device int64 (F), in table order, may be NULL; an entry outside the batch or the clip's T frames gets -1.
+ * The table lives in device memory and is NOT validated: its entries must be distinct.  Two entries naming the same (clip, frame)
+ * write the same mel column concurrently -- the same values here, an unordered pair of writes in si_codebook_splice_labels_spans
+ * when their labels differ. */
+int si_codebook_splice_spans(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                             float* mel, int Tm, int64_t* labels, si_stream_t stream);
+
+/* si_codebook_splice_labels over a frame table (the `expected_inpaint` branch, I_ea/predict.py:177-189): labels device int64 (F). */
+int si_codebook_splice_labels_spans(si_ctx* ctx, const int64_t* labels, int B, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                                    float* mel, int Tm, si_stream_t stream);
+
+/* si_codebook_metrics over a frame table (I_ea/loss_fn.py:29-62, called at I_ea/predict.py:171-173): target_labels, loss_terms,
+ * pred_labels, cos_pred_target are flat (F), in table order; loss (1) = the fixed-order sum of the F terms. */
+int si_codebook_metrics_spans(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                              const int64_t* target_labels, float* loss_terms, float* loss, int64_t* pred_labels, float* cos_pred_target,
+                              si_stream_t stream);
+
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */
 int si_vocoder_samples(const si_ctx* ctx, int Tm, int stretch);   /* output samples per clip */

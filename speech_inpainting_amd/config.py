@@ -52,6 +52,7 @@ class PredictConfig:
     hubert_checkpoint: str
     asr_model_name: Optional[str] = None
     raw: Optional[dict] = None
+    masks: Optional[list] = None  # optional `masks:` list of (start_pos_in_sec, end_pos_in_sec): several gaps in the one file
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -74,6 +75,20 @@ class PredictConfig:
     def mask_pos(self) -> int:
         return self.start_sample // 320
 
+    @property
+    def gaps(self):
+        """`masks:` as (first frame, frame count) pairs, each by the single mask's arithmetic (I_ea/predict.py:85-90); None without it."""
+        if self.masks is None:
+            return None
+        return [(int(a * 16000) // 320, int((b - a) * 1000) // 20) for a, b in self.masks]
+
+    @property
+    def spans22(self):
+        """`masks:` as [start, end) sample spans of the 22.05 kHz clip (I_ea/predict.py:99-100); None without it."""
+        if self.masks is None:
+            return None
+        return [(int(a * 16000) * 22050 // 16000, int(b * 16000) * 22050 // 16000) for a, b in self.masks]
+
 
 def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
     with open(path) as f:
@@ -83,6 +98,13 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
         n = int(data["km_model"]["n_clusters"])
         ck = data["hifi_gan"]["checkpoint_file"]
         mask = data.get("mask", {})
+        masks = data.get("masks")
+        if masks is not None:
+            if "mask" in data:
+                raise ValueError(f"{path}: give either `mask:` (one gap) or `masks:` (a list of gaps), not both")
+            if not isinstance(masks, list) or not masks:
+                raise ValueError(f"{path}: `masks:` must be a non-empty list of {{start_pos_in_sec, end_pos_in_sec}} mappings")
+            masks = sorted((float(m["start_pos_in_sec"]), float(m["end_pos_in_sec"])) for m in masks)
         return PredictConfig(
             dataset=ds,
             wave_path=data["wave"][ds]["wave_path"],
@@ -98,7 +120,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_type=str(data["hubert_model"]["type"]),
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
-            raw=data)
+            raw=data, masks=masks)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

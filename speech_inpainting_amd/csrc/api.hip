@@ -701,7 +701,31 @@ const float* wf(const si_ctx* ctx, size_t off) { return reinterpret_cast<const f
 
 static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, const int32_t* mask_len, const int32_t* valid_len,
                       int normalize, float norm_eps, const double* pre_add, int output_layer, int B, int N, float* out_feats, float* out_hidden,
-                      void* workspace, size_t workspace_bytes, si_stream_t stream, const int32_t* host_len = nullptr);
+                      void* workspace, size_t workspace_bytes, si_stream_t stream, const int32_t* host_len = nullptr, const SiSpans* spans = nullptr);
+
+// A span table as the C ABI takes it: everything the kernels assume is checked here, on the host copy, before anything is launched.
+static int check_span_table(si_ctx* ctx, const char* who, const si_span_table* t, int B, SiSpans& out) {
+    if (!t || t->struct_size != (int32_t)sizeof(si_span_table)) return si_fail(ctx, SI_EINVAL, "%s: si_span_table size mismatch", who);
+    if (!t->host_off || !t->span_off) return si_fail(ctx, SI_EINVAL, "%s: span table with NULL offsets", who);
+    if (t->num_clips != B) return si_fail(ctx, SI_EINVAL, "%s: span table for %d clips, batch of %d", who, t->num_clips, B);
+    if (t->host_off[0] != 0 || t->host_off[B] != t->num_spans || t->num_spans < 0)
+        return si_fail(ctx, SI_EINVAL, "%s: span offsets run 0 .. %d but the table holds %d spans", who, t->host_off[B], t->num_spans);
+    if (t->num_spans > 0 && (!t->host_start || !t->host_len || !t->span_start || !t->span_len))
+        return si_fail(ctx, SI_EINVAL, "%s: span table with NULL start / len", who);
+    for (int b = 0; b < B; ++b) {
+        const int k0 = t->host_off[b], k1 = t->host_off[b + 1];
+        if (k1 < k0 || k1 > t->num_spans) return si_fail(ctx, SI_EINVAL, "%s: span offsets of clip %d decrease or leave the table", who, b);
+        if (k1 - k0 > SI_MAX_SPANS) return si_fail(ctx, SI_EINVAL, "%s: clip %d has %d spans, more than SI_MAX_SPANS = %d", who, b, k1 - k0, SI_MAX_SPANS);
+        for (int k = k0; k < k1; ++k) {
+            const long s = t->host_start[k], l = t->host_len[k];
+            if (s < 0 || l < 0 || s + l > 0x7fffffffL) return si_fail(ctx, SI_EINVAL, "%s: clip %d span %d = [%ld, +%ld) is not a sample range", who, b, k - k0, s, l);
+            if (k > k0 && s < (long)t->host_start[k - 1] + t->host_len[k - 1])
+                return si_fail(ctx, SI_EINVAL, "%s: clip %d span %d overlaps or precedes span %d (spans must be sorted and disjoint)", who, b, k - k0, k - k0 - 1);
+        }
+    }
+    out = SiSpans{t->span_off, t->span_start, t->span_len};
+    return SI_OK;
+}
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -853,6 +877,16 @@ int si_hubert_extract_features(si_ctx* ctx, const si_extract_desc* x, const floa
                       x->output_layer, B, N, nullptr, out_hidden, workspace, workspace_bytes, stream);
 }
 
+int si_hubert_forward_spans(si_ctx* ctx, const float* wav, const si_span_table* spans, const int32_t* sample_len, int normalize,
+                            int B, int N, float* out_feats, void* workspace, size_t workspace_bytes, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!out_feats || B <= 0) return si_fail(ctx, SI_EINVAL, "si_hubert_forward_spans: NULL / empty argument");
+    SiSpans sp;
+    if (int rc = check_span_table(ctx, "si_hubert_forward_spans", spans, B, sp)) return rc;
+    return hubert_run(ctx, wav, nullptr, nullptr, nullptr, normalize, 1e-7f, nullptr, 0, B, N, out_feats, nullptr, workspace, workspace_bytes,
+                      stream, sample_len, &sp);
+}
+
 int si_code_splice(si_ctx* ctx, const int64_t* code_clean, const int64_t* code_masked, const int32_t* first, const int32_t* last, int B, int T,
                    int64_t* out, si_stream_t stream) {
     if (!ctx) return SI_EINVAL;
@@ -870,7 +904,7 @@ int si_code_splice(si_ctx* ctx, const int64_t* code_clean, const int64_t* code_m
 // run alone (conv0 statistics over its own rows, convolutions stop at its own lengths, the transformer runs on PACKED rows).
 static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, const int32_t* mask_len, const int32_t* valid_len,
                       int normalize, float norm_eps, const double* pre_add, int output_layer, int B, int N, float* out_feats, float* out_hidden,
-                      void* workspace, size_t workspace_bytes, si_stream_t stream, const int32_t* host_len) {
+                      void* workspace, size_t workspace_bytes, si_stream_t stream, const int32_t* host_len, const SiSpans* spans) {
     if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_hubert_forward before weights were loaded");
     if (!ctx->weights_verified) if (int rcw = si_weights_check(ctx)) return rcw;      // a received blob: once, before its first use
     if (!wav || !workspace || B <= 0) return si_fail(ctx, SI_EINVAL, "si_hubert_forward: NULL / empty argument");
@@ -970,7 +1004,7 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     // A0 + A1: normalise fused into conv0
     WaveNormParams wp{wav, mask_start, mask_len, B, N, e.L[1], d.conv_dim[0], d.conv_kernel[0], d.conv_stride[0], normalize, valid_len, norm_eps, pre_add,
                       vl ? dL(1) : nullptr};
-    if ((rc = si_launch_wave_stats(ctx, wp, stats, st))) return rc;
+    if ((rc = si_launch_wave_stats(ctx, wp, stats, st, spans))) return rc;
     if (vframes && (rc = si_launch_frame_lengths(ctx, valid_len, B, d.num_conv, d.conv_kernel, d.conv_stride, e.T, vframes, st))) return rc;
     // layer-norm flavour (HuBERT-large) in bf16 mode: every conv is followed by LayerNorm + GELU over its 512 channels; the
     // LayerNorm writes ONLY the bf16 operand of the next conv (the rounding that conv would apply while staging), into the
@@ -982,10 +1016,10 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
         // group-norm flavour in bf16 mode: the conv chain runs on operand-ready bf16 activations (conv0 and convs 1..n-2
         // write ONLY the bf16 operand of their single consumer; the last conv writes fp32 for the LayerNorm that follows)
         rc = si_launch_conv0_groupnorm(ctx, wp, stats, wf(ctx, L.conv0_w), wf(ctx, L.conv0_g), wf(ctx, L.conv0_b), partials, affine, cbuf[0], st,
-                                       c16 ? cb16[0] : nullptr);
+                                       c16 ? cb16[0] : nullptr, spans);
         if (!rc) rc = c16 ? si_tap(ctx, st, {cb16[0], n0, 2}, "conv%d.bf16", 0) : si_tap(ctx, st, {cbuf[0], n0}, "conv%d", 0);
     } else {
-        rc = si_launch_conv0_affine(ctx, wp, stats, wf(ctx, L.conv0_w), d.conv_bias ? wf(ctx, L.conv0_bias) : nullptr, affine, cbuf[0], st);
+        rc = si_launch_conv0_affine(ctx, wp, stats, wf(ctx, L.conv0_w), d.conv_bias ? wf(ctx, L.conv0_bias) : nullptr, affine, cbuf[0], st, spans);
         if (!rc) rc = si_tap(ctx, st, {cbuf[0], n0}, "conv%d", 0);
         if (!rc) rc = si_launch_layernorm(ctx, cbuf[0], nullptr, wf(ctx, L.conv0_g), wf(ctx, L.conv0_b), l16 ? nullptr : cbuf[0], (long)B * e.L[1], d.conv_dim[0],
                                           1e-5f, 1, st, l16 ? cb16[1] : nullptr);
@@ -1211,6 +1245,48 @@ int si_codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, const int
     return si_launch_codebook_metrics(ctx, feats, B, T, ctx->d.codebook_dim, frame_pos, Lm, wf(ctx, L.cb_centered), wf(ctx, L.cb_rnorm),
                                       ctx->d.num_clusters, target_labels, loss_terms, loss, pred_labels, cos_pred_target,
                                       static_cast<hipStream_t>(stream));
+}
+
+int si_codebook_splice_spans(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                             float* mel, int Tm, int64_t* labels, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_splice_spans before weights were loaded");
+    if (!ctx->weights_verified) if (int rcw = si_weights_check(ctx)) return rcw;
+    if (!feats || !mel || B <= 0 || T <= 0 || Tm <= 0 || F < 0 || (F > 0 && (!frame_clip || !frame_pos)))
+        return si_fail(ctx, SI_EINVAL, "si_codebook_splice_spans: NULL / empty argument");
+    if (ctx->d.codebook_dim != ctx->d.num_mels)
+        return si_fail(ctx, SI_EINVAL, "codebook_dim %d != generator input width %d", ctx->d.codebook_dim, ctx->d.num_mels);
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    const Layout& L = ctx->lay;
+    return si_launch_codebook_splice_spans(ctx, feats, B, T, ctx->d.codebook_dim, frame_clip, frame_pos, F, wf(ctx, L.cb_centered), wf(ctx, L.cb_raw),
+                                           wf(ctx, L.cb_rnorm), ctx->d.num_clusters, mel, Tm, labels, static_cast<hipStream_t>(stream));
+}
+
+int si_codebook_splice_labels_spans(si_ctx* ctx, const int64_t* labels, int B, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                                    float* mel, int Tm, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_splice_labels_spans before weights were loaded");
+    if (!mel || B <= 0 || Tm <= 0 || F < 0 || (F > 0 && (!labels || !frame_clip || !frame_pos)))
+        return si_fail(ctx, SI_EINVAL, "si_codebook_splice_labels_spans: NULL / empty argument");
+    if (ctx->d.codebook_dim != ctx->d.num_mels)
+        return si_fail(ctx, SI_EINVAL, "codebook_dim %d != generator input width %d", ctx->d.codebook_dim, ctx->d.num_mels);
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    return si_launch_codebook_gather_spans(ctx, labels, B, ctx->d.codebook_dim, frame_clip, frame_pos, F, wf(ctx, ctx->lay.cb_raw),
+                                           ctx->d.num_clusters, mel, Tm, static_cast<hipStream_t>(stream));
+}
+
+int si_codebook_metrics_spans(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                              const int64_t* target_labels, float* loss_terms, float* loss, int64_t* pred_labels, float* cos_pred_target,
+                              si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_metrics_spans before weights were loaded");
+    if (!feats || !frame_clip || !frame_pos || !target_labels || !loss_terms || !loss || !cos_pred_target || B <= 0 || T <= 0 || F <= 0)
+        return si_fail(ctx, SI_EINVAL, "si_codebook_metrics_spans: NULL / empty argument");
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    const Layout& L = ctx->lay;
+    return si_launch_codebook_metrics_spans(ctx, feats, B, T, ctx->d.codebook_dim, frame_clip, frame_pos, F, wf(ctx, L.cb_centered), wf(ctx, L.cb_rnorm),
+                                            ctx->d.num_clusters, target_labels, loss_terms, loss, pred_labels, cos_pred_target,
+                                            static_cast<hipStream_t>(stream));
 }
 
 int si_kmeans_assign(si_ctx* ctx, const float* feats, int64_t rows, int D, const float* centroids, int K, int64_t* labels,
@@ -1769,7 +1845,17 @@ int si_mel_workspace_bytes(si_ctx* ctx, int B, int N22, size_t* out) {
 }
 
 static int mel_run(si_ctx* ctx, const float* wave22, const int32_t* mask_start, const int32_t* mask_end, int normalize, int B,
-                   int N22, float* mel_out, void* workspace, size_t workspace_bytes, si_stream_t stream, const int32_t* host_len);
+                   int N22, float* mel_out, void* workspace, size_t workspace_bytes, si_stream_t stream, const int32_t* host_len,
+                   const SiSpans* spans = nullptr);
+
+int si_mel_frontend_spans(si_ctx* ctx, const float* wave22, const si_span_table* spans, const int32_t* sample_len, int normalize,
+                          int B, int N22, float* mel_out, void* workspace, size_t workspace_bytes, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (B <= 0) return si_fail(ctx, SI_EINVAL, "si_mel_frontend_spans: NULL / empty argument");
+    SiSpans sp;
+    if (int rc = check_span_table(ctx, "si_mel_frontend_spans", spans, B, sp)) return rc;
+    return mel_run(ctx, wave22, nullptr, nullptr, normalize, B, N22, mel_out, workspace, workspace_bytes, stream, sample_len, &sp);
+}
 
 int si_mel_frontend(si_ctx* ctx, const float* wave22, const int32_t* mask_start, const int32_t* mask_end, int normalize, int B,
                     int N22, float* mel_out, void* workspace, size_t workspace_bytes, si_stream_t stream) {
@@ -1785,7 +1871,8 @@ int si_mel_frontend_varlen(si_ctx* ctx, const float* wave22, const int32_t* mask
 
 // host_len (B, HOST) or null: ragged batch -- clip b holds host_len[b] samples of its row of N22 (peak, reflection and frame count are its own)
 static int mel_run(si_ctx* ctx, const float* wave22, const int32_t* mask_start, const int32_t* mask_end, int normalize, int B,
-                   int N22, float* mel_out, void* workspace, size_t workspace_bytes, si_stream_t stream, const int32_t* host_len) {
+                   int N22, float* mel_out, void* workspace, size_t workspace_bytes, si_stream_t stream, const int32_t* host_len,
+                   const SiSpans* spans) {
     if (!ctx) return SI_EINVAL;
     if (!wave22 || !mel_out || !workspace || B <= 0) return si_fail(ctx, SI_EINVAL, "si_mel_frontend: NULL / empty argument");
     if ((mask_start == nullptr) != (mask_end == nullptr))
@@ -1818,8 +1905,8 @@ static int mel_run(si_ctx* ctx, const float* wave22, const int32_t* mask_start, 
     }
     if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: mel workspace carve exceeded its own estimate");
     const float* hann = reinterpret_cast<const float*>(ctx->fe_dev + ctx->fe_hann);
-    if (normalize && (rc = si_launch_wave_peak(ctx, wave22, mask_start, mask_end, B, N22, peak, st, d_n))) return rc;
-    if ((rc = si_launch_mel_frames(ctx, wave22, mask_start, mask_end, peak, hann, B, N22, Tm, FE_HOP, FE_PAD, FE_NFFT, FE_KC, normalize, frames, st, d_n, d_tm)))
+    if (normalize && (rc = si_launch_wave_peak(ctx, wave22, mask_start, mask_end, B, N22, peak, st, d_n, spans))) return rc;
+    if ((rc = si_launch_mel_frames(ctx, wave22, mask_start, mask_end, peak, hann, B, N22, Tm, FE_HOP, FE_PAD, FE_NFFT, FE_KC, normalize, frames, st, d_n, d_tm, spans)))
         return rc;
     if ((rc = si_tap(ctx, st, {frames, (long)B * Tm * FE_FRAME}, "mel_frames"))) return rc;
     // STFT as two exact-fp32 GEMMs on the folded frames: (B*Tm, 528) x (528, 513) -> re, (B*Tm, 512) x (512, 513) -> im

@@ -186,14 +186,42 @@ struct WaveNormParams {           // A0 + A1 (group-norm flavour)
                                   // its samples): GroupNorm statistics over those rows only, rows past them are not written
 };
 
-int si_launch_wave_stats(si_ctx* ctx, const WaveNormParams& p, double* stats /*B*2: mean, rstd*/, hipStream_t st);
+// Multi-gap masks: a clip carries 0 .. SI_MAX_SPANS zeroed sample spans instead of the one of mask_start / mask_len.  CSR table in device
+// memory: clip b owns entries [off[b], off[b + 1]) of start / len (samples), sorted by start and disjoint (si_span_table, checked on the
+// host by the C ABI).  A launcher given a table runs the `_spans` sibling of its kernel (mask_start / mask_len of the params are then
+// NULL); without one, today's kernel with today's arguments.
+struct SiSpans { const int32_t* off; const int32_t* start; const int32_t* len; };
+
+// The masked-or-not test of a thread whose sample index NEVER DECREASES between calls (the whole-clip passes wave_stats and wave_peak).
+// The thread keeps the first span that does not end at or before its index in registers: a sample that stays inside or in front of
+// that span costs the two compares of the single-span test; the table is read (two global loads) once per span the thread passes, and
+// lanes that pass a span at different samples diverge for that step.  The streaming loops ask `clear` once per 16-byte load first, so
+// outside the gaps -- nearly all of a clip -- a vector costs one compare and no walk.
+struct SiSpanWalk {
+    const int32_t* s; const int32_t* l;
+    int k, n, cs, ce;
+    __device__ __forceinline__ void load() {
+        if (k < n) { cs = s[k]; ce = cs + l[k]; } else { cs = 0x7fffffff; ce = 0x7fffffff; }
+    }
+    __device__ __forceinline__ SiSpanWalk(const SiSpans& sp, int b) : s(sp.start), l(sp.len), k(sp.off[b]), n(sp.off[b + 1]) { load(); }
+    __device__ __forceinline__ bool hit(int i) {
+        while (i >= ce) { ++k; load(); }
+        return i >= cs;
+    }
+    // true: none of the samples [i, i + cnt) is masked and the cursor needs no step (spans behind the cursor end at or before an earlier
+    // index, the cursor's span and all later ones start at cs or after) -- the one compare a 16-byte load pays outside the gaps
+    __device__ __forceinline__ bool clear(int i, int cnt) const { return i + cnt <= cs; }
+};
+
+int si_launch_wave_stats(si_ctx* ctx, const WaveNormParams& p, double* stats /*B*2: mean, rstd*/, hipStream_t st, const SiSpans* sp = nullptr);
 // conv0 -> GroupNorm(C groups) -> GELU, channels-last out (B, L1, C)
 int si_launch_conv0_groupnorm(si_ctx* ctx, const WaveNormParams& p, const double* stats, const float* w /*[C][K]*/,
                               const float* gamma, const float* beta, double* partials, float* affine, float* out,
-                              hipStream_t st, unsigned short* out16 = nullptr /* write bf16 there INSTEAD of fp32 into out */);
+                              hipStream_t st, unsigned short* out16 = nullptr /* write bf16 there INSTEAD of fp32 into out */,
+                              const SiSpans* sp = nullptr);
 // conv0 (+bias) only, channels-last out, for the layer-norm flavour (LN+GELU applied by si_launch_layernorm)
 int si_launch_conv0_affine(si_ctx* ctx, const WaveNormParams& p, const double* stats, const float* w, const float* bias,
-                           float* affine, float* out, hipStream_t st);
+                           float* affine, float* out, hipStream_t st, const SiSpans* sp = nullptr);
 size_t si_conv0_partials_bytes(int B, int N);
 
 // y = LN(x [+ add]) * gamma + beta over the last dim C (rows x C), optional GELU afterwards
@@ -240,6 +268,17 @@ int si_launch_code_splice(si_ctx* ctx, const int64_t* clean, const int64_t* mask
 int si_launch_codebook_gather(si_ctx* ctx, const int64_t* labels, int B, int D, const int32_t* frame_pos, int Lm,
                               const float* cb_raw, int K, float* mel, int Tm, hipStream_t st);
 
+// The three codebook calls over a FRAME TABLE (multi-gap masks): entry f < F = frame frame_pos[f] of clip frame_clip[f] (device int32);
+// labels / target / terms / pred / cos_pt are flat (F), in table order
+int si_launch_codebook_splice_spans(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_clip, const int32_t* frame_pos,
+                                    int F, const float* cb_centered, const float* cb_raw, const float* cb_rnorm, int K, float* mel, int Tm,
+                                    int64_t* labels, hipStream_t st);
+int si_launch_codebook_gather_spans(si_ctx* ctx, const int64_t* labels, int B, int D, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                                    const float* cb_raw, int K, float* mel, int Tm, hipStream_t st);
+int si_launch_codebook_metrics_spans(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_clip, const int32_t* frame_pos,
+                                     int F, const float* cb_centered, const float* cb_rnorm, int K, const int64_t* target, float* terms,
+                                     float* loss, int64_t* pred, float* cos_pt, hipStream_t st);
+
 // k-means unit assignment: labels[row] = argmin_k ||x_row - c_k||^2 (first minimum); dist (optional) = that squared distance
 // cnorm_scratch (K floats, device) or null: with it (and D % 32 == 0) the distance GEMM runs on the matrix pipe (exact-fp32 MFMA)
 int si_launch_kmeans_assign(si_ctx* ctx, const float* x, long rows, int D, const float* cent, int K, int64_t* labels, float* dist,
@@ -260,13 +299,13 @@ int si_launch_sisdr(si_ctx* ctx, const float* est, const float* ref, int B, int 
 // ------------------------------------------------------------------------------------------------
 // n_len / tm_len (B, device) or null: ragged batches -- clip b holds n_len[b] samples (row stride N) and tm_len[b] frames (stride Tm)
 int si_launch_wave_peak(si_ctx* ctx, const float* wav, const int32_t* ms, const int32_t* me, int B, int N, float* peak,
-                        hipStream_t st, const int32_t* n_len = nullptr);
+                        hipStream_t st, const int32_t* n_len = nullptr, const SiSpans* sp = nullptr /* multi-gap masks: instead of ms / me */);
 // mask -> normalise*0.95 -> reflect-pad -> Hann window, as the (B*Tm, kc + nfft / 2) matrix of FOLDED frames
 // [w[0], w[k] + w[nfft - k] (k = 1 .. nfft/2 - 1), w[nfft/2], zeros up to kc | 0, w[k] - w[nfft - k]]: the operands of the two
 // half-size DFT GEMMs (cosine / sine part)
 int si_launch_mel_frames(si_ctx* ctx, const float* wav, const int32_t* ms, const int32_t* me, const float* peak,
                          const float* hann, int B, int N, int Tm, int hop, int pad, int nfft, int kc, int normalize, float* frames,
-                         hipStream_t st, const int32_t* n_len = nullptr, const int32_t* tm_len = nullptr);
+                         hipStream_t st, const int32_t* n_len = nullptr, const int32_t* tm_len = nullptr, const SiSpans* sp = nullptr);
 // spec rows [re | pad | im at im_off] -> sqrt(re^2+im^2+1e-9) -> banded mel basis -> log(clamp 1e-5) -> mel (B, nmel, Tm)
 int si_launch_mel_project(si_ctx* ctx, const float* spec, int ld_spec, int nbin, int im_off, const float* basis_t, const int32_t* lo,
                           const int32_t* hi, int nmel, int B, int Tm, float* mel, hipStream_t st, const int32_t* tm_len = nullptr);

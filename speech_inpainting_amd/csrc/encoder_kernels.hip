@@ -17,6 +17,7 @@
 //    I_ea/predict.py:164-168,184-187).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 
@@ -44,9 +45,17 @@ __device__ __forceinline__ float masked_sample(float v, int i, int ms, int ml, b
     return has_add ? (float)((double)v + add) : v;
 }
 
+struct SiNoSpans {                                                   // the single-span instantiations: nothing to walk
+    __device__ __forceinline__ SiNoSpans(const SiSpans&, int) {}
+    __device__ __forceinline__ bool hit(int) { return false; }
+};
+
 // ------------------------------------------------------------------------------------------------ A0
 // stats[b] = {mean, 1/sqrt(var + eps)} of the zero-masked clip, accumulated in fp64.
-__global__ __launch_bounds__(1024) void wave_stats_kernel(WaveNormParams p, double* __restrict__ stats) {
+// SPANS: the zeroed samples are the clip's rows of the span table `sp` instead of [mask_start[b], mask_start[b] + mask_len[b]).  A zeroed
+// sample adds +0.0 to both fp64 sums, so a one-span table gives the bits of the single-span instantiation.
+template <bool SPANS>
+__device__ __forceinline__ void wave_stats_body(const WaveNormParams& p, const SiSpans& sp, double* __restrict__ stats) {
     const int b = blockIdx.x;
     if (!p.normalize) {
         if (threadIdx.x == 0) { stats[2 * b] = 0.0; stats[2 * b + 1] = 1.0; }
@@ -58,6 +67,12 @@ __global__ __launch_bounds__(1024) void wave_stats_kernel(WaveNormParams p, doub
     const int nv = p.valid_len ? min(max(p.valid_len[b], 1), p.N) : p.N;      // real samples of a right-padded clip
     const bool has_add = p.pre_add != nullptr;
     const double add = has_add ? p.pre_add[b] : 0.0;
+    std::conditional_t<SPANS, SiSpanWalk, SiNoSpans> walk(sp, b);
+    auto unmasked = [&](float v) { return has_add ? (float)((double)v + add) : v; };
+    auto sample = [&](float v, int i) {
+        if constexpr (SPANS) return walk.hit(i) ? 0.f : unmasked(v);
+        else return masked_sample(v, i, ms, ml, has_add, add);
+    };
     double s = 0.0, ss = 0.0;
     // 16 bytes per lane and four loads in flight per thread (one workgroup walks a whole clip: with 4-byte loads in a
     // dependent loop the launch was a 35 us latency chain); the tail and unaligned clips take the scalar loop
@@ -66,15 +81,19 @@ __global__ __launch_bounds__(1024) void wave_stats_kernel(WaveNormParams p, doub
 #pragma unroll 4
     for (int i = threadIdx.x * 4; i < nv4; i += blockDim.x * 4) {
         const f32x4 q = *reinterpret_cast<const f32x4*>(x + i);
+        bool clear = false;
+        if constexpr (SPANS) clear = walk.clear(i, 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float v = masked_sample(q[e], i + e, ms, ml, has_add, add);
+            float v;
+            if constexpr (SPANS) v = clear ? unmasked(q[e]) : sample(q[e], i + e);
+            else v = sample(q[e], i + e);
             s += v;
             ss += (double)v * v;
         }
     }
     for (int i = nv4 + threadIdx.x; i < nv; i += blockDim.x) {
-        const float v = masked_sample(x[i], i, ms, ml, has_add, add);
+        const float v = sample(x[i], i);
         s += v;
         ss += (double)v * v;
     }
@@ -94,16 +113,49 @@ __global__ __launch_bounds__(1024) void wave_stats_kernel(WaveNormParams p, doub
         stats[2 * b + 1] = 1.0 / sqrt(var + (double)p.norm_eps);
     }
 }
+__global__ __launch_bounds__(1024) void wave_stats_kernel(WaveNormParams p, double* __restrict__ stats) {
+    wave_stats_body<false>(p, SiSpans{}, stats);
+}
+__global__ __launch_bounds__(1024) void wave_stats_spans_kernel(WaveNormParams p, SiSpans sp, double* __restrict__ stats) {
+    wave_stats_body<true>(p, sp, stats);
+}
 
 __device__ __forceinline__ float load_norm(const float* x, int i, int ms, int ml, float mean, float rstd, int nv, bool has_add, double add) {
     if (i >= nv) return 0.f;                                         // padding value, applied after the normalisation
     return (masked_sample(x[i], i, ms, ml, has_add, add) - mean) * rstd;
 }
 
+// The conv0 loaders' window xs[0, win) = normalised samples [g0, g0 + win) of clip b.  SPANS: the window is loaded unmasked -- the
+// loop of a clip without a mask -- and then, span by span of the clip's table (a wave-uniform walk: the table comes through scalar
+// loads, once per workgroup), the part of each span inside the window is overwritten with the value a zeroed sample normalises to,
+// the expression load_norm evaluates for it.  A thread rewrites only the entries it loaded itself (i = tid mod 256), so the
+// fix-up needs no barrier of its own, and a workgroup whose window touches no span (all but a few) does no per-sample test at all.
+template <bool SPANS>
+__device__ __forceinline__ void conv0_load_window(float* xs, const float* __restrict__ x, int g0, int win, const WaveNormParams& p, const SiSpans& sp,
+                                                  int b, float mean, float rstd, int nv, bool has_add, double add) {
+    if constexpr (!SPANS) {
+        const int ms = p.mask_start ? p.mask_start[b] : 0, ml = p.mask_len ? p.mask_len[b] : 0;
+        for (int i = threadIdx.x; i < win; i += 256) xs[i] = load_norm(x, g0 + i, ms, ml, mean, rstd, nv, has_add, add);
+    } else {
+        for (int i = threadIdx.x; i < win; i += 256) xs[i] = load_norm(x, g0 + i, 0, 0, mean, rstd, nv, has_add, add);
+        const float zv = (0.f - mean) * rstd;
+        const int wend = min(g0 + win, nv);                           // samples >= nv keep the padding value
+        const int k1 = sp.off[b + 1];
+        for (int k = sp.off[b]; k < k1; ++k) {
+            const int s = sp.start[k], e = s + sp.len[k];
+            if (e <= g0) continue;
+            if (s >= wend) break;                                     // sorted: no later span reaches the window
+            const int lo = max(s, g0) - g0, hi = min(e, wend) - g0;
+            for (int i = lo + (((int)threadIdx.x - lo) & 255); i < hi; i += 256) xs[i] = zv;
+        }
+    }
+}
+
 // partials[b][chunk][NP]: NP = K + K(K+1)/2 lag sums of the normalised clip over the chunk's conv positions.
 #define SI_C0_TCH 512
-__global__ __launch_bounds__(256) void conv0_lagsums_kernel(WaveNormParams p, const double* __restrict__ stats,
-                                                            double* __restrict__ partials) {
+template <bool SPANS>
+__device__ __forceinline__ void conv0_lagsums_body(const WaveNormParams& p, const SiSpans& sp, const double* __restrict__ stats,
+                                                   double* __restrict__ partials) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* xs = reinterpret_cast<float*>(smem);                       // S*TCH + K
     const int b = blockIdx.y, chunk = blockIdx.x;
@@ -118,13 +170,12 @@ __global__ __launch_bounds__(256) void conv0_lagsums_kernel(WaveNormParams p, co
         return;
     }
     const float mean = (float)stats[2 * b], rstd = (float)stats[2 * b + 1];
-    const int ms = p.mask_start ? p.mask_start[b] : 0, ml = p.mask_len ? p.mask_len[b] : 0;
     const float* x = p.wav + (long)b * p.N;
     const int win = (nt - 1) * S + K;
     const int nv = p.valid_len ? min(max(p.valid_len[b], 1), p.N) : p.N;
     const bool has_add = p.pre_add != nullptr;
     const double add = has_add ? p.pre_add[b] : 0.0;
-    for (int i = threadIdx.x; i < win; i += 256) xs[i] = load_norm(x, t0 * S + i, ms, ml, mean, rstd, nv, has_add, add);
+    conv0_load_window<SPANS>(xs, x, t0 * S, win, p, sp, b, mean, rstd, nv, has_add, add);
     __syncthreads();
     __shared__ double part[2][160];
     const int pr = threadIdx.x & 127, half = threadIdx.x >> 7;
@@ -145,6 +196,14 @@ __global__ __launch_bounds__(256) void conv0_lagsums_kernel(WaveNormParams p, co
     }
     __syncthreads();
     if (half == 0 && pr < NP) partials[((long)b * nchunks + chunk) * NP + pr] = part[0][pr] + part[1][pr];
+}
+__global__ __launch_bounds__(256) void conv0_lagsums_kernel(WaveNormParams p, const double* __restrict__ stats,
+                                                            double* __restrict__ partials) {
+    conv0_lagsums_body<false>(p, SiSpans{}, stats, partials);
+}
+__global__ __launch_bounds__(256) void conv0_lagsums_spans_kernel(WaveNormParams p, SiSpans sp, const double* __restrict__ stats,
+                                                                  double* __restrict__ partials) {
+    conv0_lagsums_body<true>(p, sp, stats, partials);
 }
 
 // affine[b][c] = {a, sh}:  y = gelu(a * conv + sh)  with a = gamma*rstd_c, sh = beta - mean_c*a
@@ -188,10 +247,10 @@ __global__ void conv0_bias_affine_kernel(int B, int C, const float* __restrict__
 // FAST (the bf16-only output of the bf16 encoder mode): erf by the GEMM epilogues' 15-operation form (si_gelu_fast, |error| <= 1.5e-7
 // before the value is rounded to 8 bits): 152 -> 140 us for 32 clips.
 #define SI_C0_ROWS 64
-template <int K, bool GELU, bool FAST = false>
-__global__ __launch_bounds__(256) void conv0_apply_kernel(WaveNormParams p, const double* __restrict__ stats,
-                                                          const float* __restrict__ w, const float* __restrict__ affine,
-                                                          float* __restrict__ out, unsigned short* __restrict__ out16) {
+template <int K, bool GELU, bool FAST, bool SPANS>
+__device__ __forceinline__ void conv0_apply_body(const WaveNormParams& p, const SiSpans& sp, const double* __restrict__ stats,
+                                                 const float* __restrict__ w, const float* __restrict__ affine,
+                                                 float* __restrict__ out, unsigned short* __restrict__ out16) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* xs = reinterpret_cast<float*>(smem);
     const int b = blockIdx.y;
@@ -200,13 +259,12 @@ __global__ __launch_bounds__(256) void conv0_apply_kernel(WaveNormParams p, cons
     if (nt <= 0) return;                                              // ragged batches: rows past the clip's own are not written
     const int S = p.S, C = p.C;
     const float mean = (float)stats[2 * b], rstd = (float)stats[2 * b + 1];
-    const int ms = p.mask_start ? p.mask_start[b] : 0, ml = p.mask_len ? p.mask_len[b] : 0;
     const float* x = p.wav + (long)b * p.N;
     const int win = (nt - 1) * S + K;
     const int nv = p.valid_len ? min(max(p.valid_len[b], 1), p.N) : p.N;
     const bool has_add = p.pre_add != nullptr;
     const double add = has_add ? p.pre_add[b] : 0.0;
-    for (int i = threadIdx.x; i < win; i += 256) xs[i] = load_norm(x, t0 * S + i, ms, ml, mean, rstd, nv, has_add, add);
+    conv0_load_window<SPANS>(xs, x, t0 * S, win, p, sp, b, mean, rstd, nv, has_add, add);
     __syncthreads();
     const int tpr = C / 4;                       // threads per output row (float4 of channels each)
     const int rpp = 256 / tpr;                   // rows per pass
@@ -243,6 +301,18 @@ __global__ __launch_bounds__(256) void conv0_apply_kernel(WaveNormParams p, cons
         else *reinterpret_cast<f32x4*>(out + ((long)b * p.L1 + t0 + r) * C + c4) = y;
     }
 }
+template <int K, bool GELU, bool FAST = false>
+__global__ __launch_bounds__(256) void conv0_apply_kernel(WaveNormParams p, const double* __restrict__ stats,
+                                                          const float* __restrict__ w, const float* __restrict__ affine,
+                                                          float* __restrict__ out, unsigned short* __restrict__ out16) {
+    conv0_apply_body<K, GELU, FAST, false>(p, SiSpans{}, stats, w, affine, out, out16);
+}
+template <int K, bool GELU, bool FAST = false>
+__global__ __launch_bounds__(256) void conv0_apply_spans_kernel(WaveNormParams p, SiSpans sp, const double* __restrict__ stats,
+                                                                const float* __restrict__ w, const float* __restrict__ affine,
+                                                                float* __restrict__ out, unsigned short* __restrict__ out16) {
+    conv0_apply_body<K, GELU, FAST, true>(p, sp, stats, w, affine, out, out16);
+}
 
 size_t si_conv0_partials_bytes(int B, int N) {
     // upper bound on chunks: L1 <= N
@@ -258,20 +328,25 @@ static int conv0_check(si_ctx* ctx, const WaveNormParams& p) {
     return SI_OK;
 }
 
-int si_launch_wave_stats(si_ctx* ctx, const WaveNormParams& p, double* stats, hipStream_t st) {
-    si_prof_begin(ctx, "wave_stats", 3.0 * p.B * p.N, 4.0 * p.B * p.N, st);
-    hipLaunchKernelGGL(wave_stats_kernel, dim3(p.B), dim3(1024), 0, st, p, stats);
+int si_launch_wave_stats(si_ctx* ctx, const WaveNormParams& p, double* stats, hipStream_t st, const SiSpans* sp) {
+    si_prof_begin(ctx, sp ? "wave_stats_spans" : "wave_stats", 3.0 * p.B * p.N, 4.0 * p.B * p.N, st);
+    if (sp) hipLaunchKernelGGL(wave_stats_spans_kernel, dim3(p.B), dim3(1024), 0, st, p, *sp, stats);
+    else hipLaunchKernelGGL(wave_stats_kernel, dim3(p.B), dim3(1024), 0, st, p, stats);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;
 }
 
 static int conv0_apply(si_ctx* ctx, const WaveNormParams& p, const double* stats, const float* w, const float* affine,
-                       float* out, bool gelu, hipStream_t st, unsigned short* out16 = nullptr) {
+                       float* out, bool gelu, hipStream_t st, unsigned short* out16 = nullptr, const SiSpans* sp = nullptr) {
     dim3 grid((p.L1 + SI_C0_ROWS - 1) / SI_C0_ROWS, p.B);
     const size_t lds = ((size_t)(SI_C0_ROWS - 1) * p.S + p.K) * sizeof(float);
-    si_prof_begin(ctx, "conv0_apply", 2.0 * p.B * p.L1 * (double)p.C * p.K, p.B * (4.0 * p.N + (out16 ? 2.0 : 4.0) * p.L1 * p.C), st);
-    if (gelu && out16) hipLaunchKernelGGL((conv0_apply_kernel<10, true, true>), grid, dim3(256), lds, st, p, stats, w, affine, out, out16);
+    si_prof_begin(ctx, sp ? "conv0_apply_spans" : "conv0_apply", 2.0 * p.B * p.L1 * (double)p.C * p.K, p.B * (4.0 * p.N + (out16 ? 2.0 : 4.0) * p.L1 * p.C), st);
+    if (sp) {
+        if (gelu && out16) hipLaunchKernelGGL((conv0_apply_spans_kernel<10, true, true>), grid, dim3(256), lds, st, p, *sp, stats, w, affine, out, out16);
+        else if (gelu) hipLaunchKernelGGL((conv0_apply_spans_kernel<10, true>), grid, dim3(256), lds, st, p, *sp, stats, w, affine, out, out16);
+        else hipLaunchKernelGGL((conv0_apply_spans_kernel<10, false>), grid, dim3(256), lds, st, p, *sp, stats, w, affine, out, out16);
+    } else if (gelu && out16) hipLaunchKernelGGL((conv0_apply_kernel<10, true, true>), grid, dim3(256), lds, st, p, stats, w, affine, out, out16);
     else if (gelu) hipLaunchKernelGGL((conv0_apply_kernel<10, true>), grid, dim3(256), lds, st, p, stats, w, affine, out, out16);
     else hipLaunchKernelGGL((conv0_apply_kernel<10, false>), grid, dim3(256), lds, st, p, stats, w, affine, out, out16);
     si_prof_end(ctx, st);
@@ -281,31 +356,32 @@ static int conv0_apply(si_ctx* ctx, const WaveNormParams& p, const double* stats
 
 int si_launch_conv0_groupnorm(si_ctx* ctx, const WaveNormParams& p, const double* stats, const float* w, const float* gamma,
                               const float* beta, double* partials, float* affine, float* out, hipStream_t st,
-                              unsigned short* out16) {
+                              unsigned short* out16, const SiSpans* sp) {
     int rc = conv0_check(ctx, p);
     if (rc) return rc;
     const int nchunks = (p.L1 + SI_C0_TCH - 1) / SI_C0_TCH;
     const size_t lds = ((size_t)(SI_C0_TCH - 1) * p.S + p.K) * sizeof(float);
-    si_prof_begin(ctx, "conv0_lagsums", 2.0 * p.B * p.L1 * 65.0, 4.0 * p.B * p.N, st);
-    hipLaunchKernelGGL(conv0_lagsums_kernel, dim3(nchunks, p.B), dim3(256), lds, st, p, stats, partials);
+    si_prof_begin(ctx, sp ? "conv0_lagsums_spans" : "conv0_lagsums", 2.0 * p.B * p.L1 * 65.0, 4.0 * p.B * p.N, st);
+    if (sp) hipLaunchKernelGGL(conv0_lagsums_spans_kernel, dim3(nchunks, p.B), dim3(256), lds, st, p, *sp, stats, partials);
+    else hipLaunchKernelGGL(conv0_lagsums_kernel, dim3(nchunks, p.B), dim3(256), lds, st, p, stats, partials);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     si_prof_begin(ctx, "conv0_gn_affine", 2.0 * p.B * p.C * 65.0, 8.0 * p.B * p.C, st);
     hipLaunchKernelGGL(conv0_gn_affine_kernel, dim3(p.B), dim3(256), 0, st, p, partials, nchunks, w, gamma, beta, affine);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
-    return conv0_apply(ctx, p, stats, w, affine, out, true, st, out16);
+    return conv0_apply(ctx, p, stats, w, affine, out, true, st, out16, sp);
 }
 
 // plain flavour with an explicit affine scratch (used by the layer-norm feature extractor)
 int si_launch_conv0_affine(si_ctx* ctx, const WaveNormParams& p, const double* stats, const float* w, const float* bias,
-                           float* affine, float* out, hipStream_t st) {
+                           float* affine, float* out, hipStream_t st, const SiSpans* sp) {
     int rc = conv0_check(ctx, p);
     if (rc) return rc;
     const int n = p.B * p.C;
     hipLaunchKernelGGL(conv0_bias_affine_kernel, dim3((n + 255) / 256), dim3(256), 0, st, p.B, p.C, bias, affine);
     SI_HIP_CHECK(hipGetLastError());
-    return conv0_apply(ctx, p, stats, w, affine, out, false, st);
+    return conv0_apply(ctx, p, stats, w, affine, out, false, st, nullptr, sp);
 }
 
 // ------------------------------------------------------------------------------------------------ padded batches
@@ -1065,19 +1141,15 @@ __device__ __forceinline__ float block_sum_128(float x, float* scratch) {
     return scratch[0] + scratch[1];
 }
 
-__global__ __launch_bounds__(128) void codebook_metrics_kernel(const float* __restrict__ feats, int T, int D,
-                                                               const int32_t* __restrict__ frame_pos, int Lm,
-                                                               const float* __restrict__ cc, const float* __restrict__ rnorm,
-                                                               int K, const int64_t* __restrict__ target,
-                                                               float* __restrict__ terms, int64_t* __restrict__ pred,
-                                                               float* __restrict__ cos_pt) {
+// one frame of it: frame `pos` of clip b, outputs at flat index o
+__device__ __forceinline__ void codebook_metrics_frame(const float* __restrict__ feats, int T, int D, int b, int pos, long o,
+                                                       const float* __restrict__ cc, const float* __restrict__ rnorm, int K,
+                                                       const int64_t* __restrict__ target, float* __restrict__ terms,
+                                                       int64_t* __restrict__ pred, float* __restrict__ cos_pt) {
     __shared__ float v[128];
     __shared__ float red[2];
     __shared__ float bs[2];
     __shared__ int bi[2];
-    const int b = blockIdx.y, j = blockIdx.x;
-    const int pos = frame_pos[b] + j;
-    const long o = (long)b * Lm + j;
     const long y = target[o];
     const float nanv = __builtin_nanf("");
     if (pos < 0 || pos >= T || y < 0 || y >= K) {                    // uniform per block
@@ -1105,6 +1177,28 @@ __global__ __launch_bounds__(128) void codebook_metrics_kernel(const float* __re
     }
 }
 
+
+__global__ __launch_bounds__(128) void codebook_metrics_kernel(const float* __restrict__ feats, int T, int D,
+                                                               const int32_t* __restrict__ frame_pos, int Lm,
+                                                               const float* __restrict__ cc, const float* __restrict__ rnorm,
+                                                               int K, const int64_t* __restrict__ target,
+                                                               float* __restrict__ terms, int64_t* __restrict__ pred,
+                                                               float* __restrict__ cos_pt) {
+    const int b = blockIdx.y, j = blockIdx.x;
+    codebook_metrics_frame(feats, T, D, b, frame_pos[b] + j, (long)b * Lm + j, cc, rnorm, K, target, terms, pred, cos_pt);
+}
+
+// The same per entry of a FRAME TABLE (multi-gap masks): entry f = frame frame_pos[f] of clip frame_clip[f]; outputs flat (F) in table order.
+__global__ __launch_bounds__(128) void codebook_metrics_spans_kernel(const float* __restrict__ feats, int B, int T, int D,
+                                                                     const int32_t* __restrict__ frame_clip, const int32_t* __restrict__ frame_pos,
+                                                                     const float* __restrict__ cc, const float* __restrict__ rnorm, int K,
+                                                                     const int64_t* __restrict__ target, float* __restrict__ terms,
+                                                                     int64_t* __restrict__ pred, float* __restrict__ cos_pt) {
+    const int f = blockIdx.x, b = frame_clip[f];
+    const bool clip_ok = b >= 0 && b < B;
+    codebook_metrics_frame(feats, T, D, clip_ok ? b : 0, clip_ok ? frame_pos[f] : -1, f, cc, rnorm, K, target, terms, pred, cos_pt);
+}
+
 // loss = sum of the per-frame terms, in a fixed order (deterministic): double partials, tree over 256 threads
 __global__ __launch_bounds__(256) void sum_terms_kernel(const float* __restrict__ terms, long n, float* __restrict__ out) {
     __shared__ double part[256];
@@ -1128,6 +1222,20 @@ int si_launch_codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, in
     hipLaunchKernelGGL(codebook_metrics_kernel, dim3(Lm, B), dim3(128), 0, st, feats, T, D, frame_pos, Lm, cb_centered, cb_rnorm, K,
                        target, terms, pred, cos_pt);
     hipLaunchKernelGGL(sum_terms_kernel, dim3(1), dim3(256), 0, st, terms, (long)B * Lm, loss);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+int si_launch_codebook_metrics_spans(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_clip, const int32_t* frame_pos,
+                                     int F, const float* cb_centered, const float* cb_rnorm, int K, const int64_t* target, float* terms,
+                                     float* loss, int64_t* pred, float* cos_pt, hipStream_t st) {
+    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
+    if (B <= 0 || F <= 0) return SI_OK;
+    si_prof_begin(ctx, "codebook_metrics_spans", 2.0 * F * (double)K * D, 4.0 * F * 2.0 * D, st);
+    hipLaunchKernelGGL(codebook_metrics_spans_kernel, dim3(F), dim3(128), 0, st, feats, B, T, D, frame_clip, frame_pos, cb_centered, cb_rnorm, K,
+                       target, terms, pred, cos_pt);
+    hipLaunchKernelGGL(sum_terms_kernel, dim3(1), dim3(256), 0, st, terms, (long)F, loss);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;
@@ -1314,6 +1422,65 @@ __global__ __launch_bounds__(128) void codebook_gather_kernel(const int64_t* __r
     const long lab = labels[(long)b * Lm + j];
     if (pos < 0 || pos >= Tm || lab < 0 || lab >= K) return;
     if ((int)threadIdx.x < D) mel[((long)b * D + threadIdx.x) * Tm + pos] = raw[lab * D + threadIdx.x];
+}
+
+// Multi-gap masks: the two splices per entry of a FRAME TABLE -- entry f = frame frame_pos[f] of clip frame_clip[f], flattened over all
+// gaps of all clips -- with a grid over the F entries.  The arg-max and the centroid write are codebook_splice_kernel's, in its operation
+// order: a frame's label and spliced column have its bits.  labels (F) in table order; an entry outside the batch or the clip is -1.
+__global__ __launch_bounds__(128) void codebook_splice_spans_kernel(const float* __restrict__ feats, int B, int T, int D,
+                                                                    const int32_t* __restrict__ frame_clip, const int32_t* __restrict__ frame_pos,
+                                                                    const float* __restrict__ cc, const float* __restrict__ raw,
+                                                                    const float* __restrict__ rnorm, int K, float* __restrict__ mel,
+                                                                    int Tm, int64_t* __restrict__ labels) {
+    __shared__ float v[128];
+    __shared__ float bs[2];
+    __shared__ int bi[2];
+    const int f = blockIdx.x;
+    const int b = frame_clip[f], pos = frame_pos[f];
+    if (b < 0 || b >= B || pos < 0 || pos >= T) {                    // uniform per block
+        if (threadIdx.x == 0 && labels) labels[f] = -1;
+        return;
+    }
+    const float* fr = feats + ((long)b * T + pos) * D;
+    if ((int)threadIdx.x < D) v[threadIdx.x] = fr[threadIdx.x];
+    __syncthreads();
+    const int lab = codebook_argmax_128(v, D, cc, rnorm, K, bs, bi);
+    if (threadIdx.x == 0 && labels) labels[f] = lab;
+    if (pos < Tm && (int)threadIdx.x < D) mel[((long)b * D + threadIdx.x) * Tm + pos] = raw[(long)lab * D + threadIdx.x];
+}
+
+__global__ __launch_bounds__(128) void codebook_gather_spans_kernel(const int64_t* __restrict__ labels, int B, int D,
+                                                                    const int32_t* __restrict__ frame_clip, const int32_t* __restrict__ frame_pos,
+                                                                    const float* __restrict__ raw, int K, float* __restrict__ mel, int Tm) {
+    const int f = blockIdx.x;
+    const int b = frame_clip[f], pos = frame_pos[f];
+    const long lab = labels[f];
+    if (b < 0 || b >= B || pos < 0 || pos >= Tm || lab < 0 || lab >= K) return;
+    if ((int)threadIdx.x < D) mel[((long)b * D + threadIdx.x) * Tm + pos] = raw[lab * D + threadIdx.x];
+}
+
+int si_launch_codebook_splice_spans(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_clip, const int32_t* frame_pos,
+                                    int F, const float* cb_centered, const float* cb_raw, const float* cb_rnorm, int K, float* mel, int Tm,
+                                    int64_t* labels, hipStream_t st) {
+    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
+    if (B <= 0 || F <= 0) return SI_OK;
+    si_prof_begin(ctx, "codebook_splice_spans", 2.0 * F * (double)K * D, 4.0 * F * 2.0 * D, st);
+    hipLaunchKernelGGL(codebook_splice_spans_kernel, dim3(F), dim3(128), 0, st, feats, B, T, D, frame_clip, frame_pos, cb_centered, cb_raw,
+                       cb_rnorm, K, mel, Tm, labels);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+int si_launch_codebook_gather_spans(si_ctx* ctx, const int64_t* labels, int B, int D, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                                    const float* cb_raw, int K, float* mel, int Tm, hipStream_t st) {
+    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
+    if (B <= 0 || F <= 0) return SI_OK;
+    si_prof_begin(ctx, "codebook_gather_spans", 0.0, 8.0 * F * D, st);
+    hipLaunchKernelGGL(codebook_gather_spans_kernel, dim3(F), dim3(128), 0, st, labels, B, D, frame_clip, frame_pos, cb_raw, K, mel, Tm);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
 }
 
 int si_launch_codebook_gather(si_ctx* ctx, const int64_t* labels, int B, int D, const int32_t* frame_pos, int Lm,

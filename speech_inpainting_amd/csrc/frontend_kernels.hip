@@ -13,16 +13,22 @@
 //   mel_frames_kernel   mask -> normalise -> reflect-pad -> window, written as the (B*Tm, 1024) frame matrix
 //   mel_project_kernel  magnitude, banded mel projection (only the non-zero span of each triangle), log, transposed
 //                       store into the reference's (B, 80, Tm) layout
+#include <type_traits>
+
 #include "common.h"
 
+struct FeOneSpan {                                                   // the single-span instantiation: [s, e)
+    int s, e;
+    __device__ __forceinline__ bool hit(int i) const { return i >= s && i < e; }
+};
+
 // n_len (B) or null: ragged batches -- clip b holds n_len[b] samples inside its row of Ns
-__global__ __launch_bounds__(1024) void wave_peak_kernel(const float* __restrict__ wav, const int32_t* __restrict__ ms,
-                                                         const int32_t* __restrict__ me, int Ns, float* __restrict__ peak,
-                                                         const int32_t* __restrict__ n_len) {
+template <class Mask>
+__device__ __forceinline__ void wave_peak_body(const float* __restrict__ wav, Mask mask, int Ns, float* __restrict__ peak,
+                                               const int32_t* __restrict__ n_len) {
     const int b = blockIdx.x;
     const float* x = wav + (size_t)b * Ns;
     const int N = n_len ? n_len[b] : Ns;
-    const int s = ms ? ms[b] : 0, e = ms ? me[b] : 0;
     float m = 0.f;
     // 16 bytes per lane, four loads in flight (one workgroup walks a whole clip); scalar loop for the tail / unaligned clips
     const bool vec = (Ns & 3) == 0 && (reinterpret_cast<size_t>(wav) & 15) == 0;
@@ -31,11 +37,17 @@ __global__ __launch_bounds__(1024) void wave_peak_kernel(const float* __restrict
     for (int i = threadIdx.x * 4; i < n4; i += 1024 * 4) {
         const float4 q = *reinterpret_cast<const float4*>(x + i);
         const float qe[4] = {q.x, q.y, q.z, q.w};
+        if constexpr (std::is_same_v<Mask, SiSpanWalk>) {
+            if (mask.clear(i, 4)) {                             // outside the gaps: one compare per 16-byte load, no walk
+                m = fmaxf(fmaxf(m, fmaxf(fabsf(qe[0]), fabsf(qe[1]))), fmaxf(fabsf(qe[2]), fabsf(qe[3])));
+                continue;
+            }
+        }
 #pragma unroll
-        for (int t = 0; t < 4; ++t) m = fmaxf(m, (i + t >= s && i + t < e) ? 0.f : fabsf(qe[t]));
+        for (int t = 0; t < 4; ++t) m = fmaxf(m, mask.hit(i + t) ? 0.f : fabsf(qe[t]));
     }
     for (int i = n4 + threadIdx.x; i < N; i += 1024) {
-        const float v = (i >= s && i < e) ? 0.f : fabsf(x[i]);
+        const float v = mask.hit(i) ? 0.f : fabsf(x[i]);
         m = fmaxf(m, v);
     }
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
@@ -47,21 +59,52 @@ __global__ __launch_bounds__(1024) void wave_peak_kernel(const float* __restrict
         peak[b] = m;
     }
 }
+__global__ __launch_bounds__(1024) void wave_peak_kernel(const float* __restrict__ wav, const int32_t* __restrict__ ms,
+                                                         const int32_t* __restrict__ me, int Ns, float* __restrict__ peak,
+                                                         const int32_t* __restrict__ n_len) {
+    const int b = blockIdx.x;
+    wave_peak_body(wav, FeOneSpan{ms ? ms[b] : 0, ms ? me[b] : 0}, Ns, peak, n_len);
+}
+__global__ __launch_bounds__(1024) void wave_peak_spans_kernel(const float* __restrict__ wav, SiSpans sp, int Ns, float* __restrict__ peak,
+                                                               const int32_t* __restrict__ n_len) {
+    wave_peak_body(wav, SiSpanWalk(sp, blockIdx.x), Ns, peak, n_len);
+}
 
 // grid (Tm, B), 256 threads.  The windowed frame w[k] = x[.] * hann[k] is written FOLDED for the two half-size DFT GEMMs (api.hip):
 // [ s_0 .. s_{n/2} | zeros up to kc | 0, d_1 .. d_{n/2-1} ],  s_k = w[k] + w[n - k], d_k = w[k] - w[n - k]  (s_0 = w[0], s_{n/2} = w[n/2]).
 // n_len / tm_len (B) or null: ragged batches -- clip b holds n_len[b] samples (row stride Ns; the reflection is at ITS end) and
 // tm_len[b] frames (frame-matrix stride Tm); frames past them are not written
-__global__ __launch_bounds__(256) void mel_frames_kernel(const float* __restrict__ wav, const int32_t* __restrict__ ms,
-                                                         const int32_t* __restrict__ me, const float* __restrict__ peak,
-                                                         const float* __restrict__ hann, int Ns, int Tm, int hop, int pad,
-                                                         int nfft, int kc, int normalize, float* __restrict__ frames,
-                                                         const int32_t* __restrict__ n_len, const int32_t* __restrict__ tm_len) {
+// The spans of clip b that frame m's source samples can touch, found once per workgroup (wave-uniform: the table comes through scalar
+// loads): a frame reads the clip positions [a, a + nfft) reflected into [0, N), a contiguous range [jlo, jhi].  The first two such
+// spans live in registers; further ones (a frame of 1024 samples over more than two gaps) are walked.  Most frames touch none.
+struct FeFrameSpans {
+    const int32_t* st; const int32_t* ln;
+    int k0, k1, s0, e0, s1, e1;
+    __device__ __forceinline__ FeFrameSpans(const SiSpans& sp, int b, int a, int nfft, int N) : st(sp.start), ln(sp.len) {
+        const int z = a + nfft - 1;
+        int jlo = max(a, 0), jhi = min(z, N - 1);
+        if (a < 0) { jlo = 0; jhi = min(max(jhi, -a), N - 1); }
+        if (z >= N) { jlo = max(min(jlo, 2 * (N - 1) - z), 0); jhi = N - 1; }
+        k0 = sp.off[b]; k1 = sp.off[b + 1];
+        while (k0 < k1 && st[k0] + ln[k0] <= jlo) ++k0;
+        while (k1 > k0 && st[k1 - 1] > jhi) --k1;
+        s0 = e0 = s1 = e1 = 0;
+        if (k0 < k1) { s0 = st[k0]; e0 = s0 + ln[k0]; }
+        if (k0 + 1 < k1) { s1 = st[k0 + 1]; e1 = s1 + ln[k0 + 1]; }
+    }
+    __device__ __forceinline__ bool hit(int j) const {
+        if ((j >= s0 && j < e0) || (j >= s1 && j < e1)) return true;
+        for (int k = k0 + 2; k < k1; ++k) if (j >= st[k] && j < st[k] + ln[k]) return true;
+        return false;
+    }
+};
+
+template <class Mask>
+__device__ __forceinline__ void mel_frames_body(const float* __restrict__ wav, const Mask& mask, const float* __restrict__ peak,
+                                                const float* __restrict__ hann, int Ns, int Tm, int hop, int pad,
+                                                int nfft, int kc, int normalize, float* __restrict__ frames, int N) {
     const int m = blockIdx.x, b = blockIdx.y;
-    if (tm_len && m >= tm_len[b]) return;
     const float* x = wav + (size_t)b * Ns;
-    const int N = n_len ? n_len[b] : Ns;
-    const int s = ms ? ms[b] : 0, e = ms ? me[b] : 0;
     // librosa.util.normalize: divide by max |x|; a peak below the smallest normal float leaves the clip unscaled
     const float pk = normalize ? peak[b] : 1.f;
     const float div = pk < 1.17549435e-38f ? 1.f : pk;
@@ -71,7 +114,7 @@ __global__ __launch_bounds__(256) void mel_frames_kernel(const float* __restrict
         int j = m * hop + k - pad;                              // position in the un-padded clip
         if (j < 0) j = -j;                                      // reflect (no edge repeat), mel_dump.py:72
         if (j >= N) j = 2 * (N - 1) - j;
-        float v = (j >= s && j < e) ? 0.f : x[j];
+        float v = mask.hit(j) ? 0.f : x[j];
         if (normalize) v = (v / div) * 0.95f;                   // predict.py:104, in the script's operation order
         return v * hann[k];
     };
@@ -88,6 +131,24 @@ __global__ __launch_bounds__(256) void mel_frames_kernel(const float* __restrict
         }
         *reinterpret_cast<float4*>(dst + q) = o;
     }
+}
+__global__ __launch_bounds__(256) void mel_frames_kernel(const float* __restrict__ wav, const int32_t* __restrict__ ms,
+                                                         const int32_t* __restrict__ me, const float* __restrict__ peak,
+                                                         const float* __restrict__ hann, int Ns, int Tm, int hop, int pad,
+                                                         int nfft, int kc, int normalize, float* __restrict__ frames,
+                                                         const int32_t* __restrict__ n_len, const int32_t* __restrict__ tm_len) {
+    const int m = blockIdx.x, b = blockIdx.y;
+    if (tm_len && m >= tm_len[b]) return;
+    mel_frames_body(wav, FeOneSpan{ms ? ms[b] : 0, ms ? me[b] : 0}, peak, hann, Ns, Tm, hop, pad, nfft, kc, normalize, frames, n_len ? n_len[b] : Ns);
+}
+__global__ __launch_bounds__(256) void mel_frames_spans_kernel(const float* __restrict__ wav, SiSpans sp, const float* __restrict__ peak,
+                                                               const float* __restrict__ hann, int Ns, int Tm, int hop, int pad,
+                                                               int nfft, int kc, int normalize, float* __restrict__ frames,
+                                                               const int32_t* __restrict__ n_len, const int32_t* __restrict__ tm_len) {
+    const int m = blockIdx.x, b = blockIdx.y;
+    if (tm_len && m >= tm_len[b]) return;
+    const int N = n_len ? n_len[b] : Ns;
+    mel_frames_body(wav, FeFrameSpans(sp, b, m * hop - pad, nfft, N), peak, hann, Ns, Tm, hop, pad, nfft, kc, normalize, frames, N);
 }
 
 // One workgroup per frame.  spec row = [re(0..nbin-1) | pad | im(0..nbin-1) at im_off] as the two DFT GEMMs wrote it.
@@ -117,9 +178,10 @@ __global__ __launch_bounds__(128) void mel_project_kernel(const float* __restric
 }
 
 int si_launch_wave_peak(si_ctx* ctx, const float* wav, const int32_t* ms, const int32_t* me, int B, int N, float* peak,
-                        hipStream_t st, const int32_t* n_len) {
-    si_prof_begin(ctx, "wave_peak", (double)B * N, (double)B * N * 4, st);
-    wave_peak_kernel<<<B, 1024, 0, st>>>(wav, ms, me, N, peak, n_len);
+                        hipStream_t st, const int32_t* n_len, const SiSpans* sp) {
+    si_prof_begin(ctx, sp ? "wave_peak_spans" : "wave_peak", (double)B * N, (double)B * N * 4, st);
+    if (sp) wave_peak_spans_kernel<<<B, 1024, 0, st>>>(wav, *sp, N, peak, n_len);
+    else wave_peak_kernel<<<B, 1024, 0, st>>>(wav, ms, me, N, peak, n_len);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;
@@ -127,11 +189,12 @@ int si_launch_wave_peak(si_ctx* ctx, const float* wav, const int32_t* ms, const 
 
 int si_launch_mel_frames(si_ctx* ctx, const float* wav, const int32_t* ms, const int32_t* me, const float* peak,
                          const float* hann, int B, int N, int Tm, int hop, int pad, int nfft, int kc, int normalize, float* frames,
-                         hipStream_t st, const int32_t* n_len, const int32_t* tm_len) {
+                         hipStream_t st, const int32_t* n_len, const int32_t* tm_len, const SiSpans* sp) {
     if (nfft % 8 || kc % 4 || kc <= nfft / 2) return si_fail(ctx, SI_EINVAL, "mel_frames: n_fft %d / folded width %d unsupported", nfft, kc);
     if (N <= pad) return si_fail(ctx, SI_EINVAL, "mel_frames: clip of %d samples is not longer than the reflect pad %d", N, pad);
-    si_prof_begin(ctx, "mel_frames", 3.0 * B * Tm * nfft, (double)B * N * 4 + (double)B * Tm * nfft * 4, st);
-    mel_frames_kernel<<<dim3(Tm, B), 256, 0, st>>>(wav, ms, me, peak, hann, N, Tm, hop, pad, nfft, kc, normalize, frames, n_len, tm_len);
+    si_prof_begin(ctx, sp ? "mel_frames_spans" : "mel_frames", 3.0 * B * Tm * nfft, (double)B * N * 4 + (double)B * Tm * nfft * 4, st);
+    if (sp) mel_frames_spans_kernel<<<dim3(Tm, B), 256, 0, st>>>(wav, *sp, peak, hann, N, Tm, hop, pad, nfft, kc, normalize, frames, n_len, tm_len);
+    else mel_frames_kernel<<<dim3(Tm, B), 256, 0, st>>>(wav, ms, me, peak, hann, N, Tm, hop, pad, nfft, kc, normalize, frames, n_len, tm_len);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;

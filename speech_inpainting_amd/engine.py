@@ -18,7 +18,8 @@ import torch
 
 from .arch import HubertArch, VocoderArch
 from .checkpoint import flatten_checkpoint
-from .native import NativeContext, make_desc
+from . import gaps as G
+from .native import NativeContext, SpanTable, make_desc
 
 
 def mask_samples_from_frames(frame_pos: int, frame_len: int):
@@ -101,9 +102,14 @@ class InpaintingEngine:
 
     # ---- the three stages
     def encode(self, wave16: torch.Tensor, mask_start: Optional[torch.Tensor] = None, mask_len: Optional[torch.Tensor] = None,
-               normalize: bool = True, valid_len: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """valid_len (B,) int32: real samples per clip of a RIGHT-PADDED batch (the reference's attention_mask.sum(-1))."""
+               normalize: bool = True, valid_len: Optional[torch.Tensor] = None, spans: Optional[SpanTable] = None) -> torch.Tensor:
+        """valid_len (B,) int32: real samples per clip of a RIGHT-PADDED batch (the reference's attention_mask.sum(-1)).
+        spans: a SpanTable of 16 kHz sample spans -- several zeroed spans per clip -- instead of mask_start / mask_len."""
         self._need(head=True, what="encode")
+        if spans is not None:
+            if mask_start is not None or mask_len is not None or valid_len is not None:
+                raise ValueError("encode: `spans` replaces mask_start / mask_len and is not combined with valid_len")
+            return self.ctx.hubert_forward_spans(wave16, spans, normalize)
         return self.ctx.hubert_forward(wave16, mask_start, mask_len, normalize, valid_len)
 
     def extract_features(self, wave16: torch.Tensor, output_layer: int, normalize="layer_norm",
@@ -175,6 +181,24 @@ class InpaintingEngine:
         self._need(codebook=True, what="splice_labels")
         self.ctx.codebook_splice_labels(labels, frame_pos, mel)
 
+    # ---- several gaps per clip: the three codebook calls over a frame table (gaps.frame_table: clip index and frame, int32 (F) each)
+    def splice_spans(self, feats: torch.Tensor, frame_clip: torch.Tensor, frame_pos: torch.Tensor, mel: torch.Tensor) -> torch.Tensor:
+        """`splice` at the frames of a frame table, `mel` in place -> labels (F,) int64 in table order."""
+        self._need(codebook=True, what="splice_spans")
+        return self.ctx.codebook_splice_spans(feats, frame_clip, frame_pos, mel)
+
+    def splice_labels_spans(self, labels: torch.Tensor, frame_clip: torch.Tensor, frame_pos: torch.Tensor, mel: torch.Tensor) -> None:
+        """`splice_labels` at the frames of a frame table: the raw centroids of GIVEN labels (F,) into mel, in place."""
+        self._need(codebook=True, what="splice_labels_spans")
+        self.ctx.codebook_splice_labels_spans(labels, frame_clip, frame_pos, mel)
+
+    def codebook_metrics_spans(self, feats: torch.Tensor, frame_clip: torch.Tensor, frame_pos: torch.Tensor, target: torch.Tensor):
+        """`codebook_metrics` at the frames of a frame table, target (F,) int64; every per-frame output is flat (F,)."""
+        self._need(codebook=True, what="codebook_metrics_spans")
+        loss, terms, pred, cpt = self.ctx.codebook_metrics_spans(feats, frame_clip, frame_pos, target)
+        return {"loss": loss[0], "loss_terms": terms, "pred_labels": pred, "cos_pred_target": cpt,
+                "accuracy": (pred == target).float().mean()}
+
     def vocode(self, mel: torch.Tensor, stretch: bool = True) -> torch.Tensor:
         return self.ctx.hifigan_forward(mel, stretch)
 
@@ -226,10 +250,46 @@ class InpaintingEngine:
             wave[b, s0:s1] = out[b, s0 - w0 * hop:s1 - w0 * hop]
         return wave
 
+    def vocode_windows(self, wave_base: torch.Tensor, mel_var: torch.Tensor, ranges: Sequence[Sequence[Sequence[int]]],
+                       mel_len: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """The multi-window form of `vocode_window`: `mel_var` differs from the mel that produced `wave_base` only in the frame
+        ranges `ranges[b]` = (pos, len) pairs of clip b (none, one or several, any lengths).  gaps.plan_windows merges a clip's
+        windows where they overlap or touch; ALL windows of ALL clips go through the generator as one ragged stretch=False batch,
+        and each window's kept region (its output without the rf frames at an edge that is not a clip edge) is spliced into a
+        copy of `wave_base` -- the single-window rule, so the result is bit-identical to a full pass as well.
+        mel_len: per-clip mel frames of a ragged batch (the stretch and the windows stop at the clip's own end)."""
+        ext = self.ctx.extend_mel(mel_var.contiguous())
+        B, D, Tout = ext.shape
+        hop = wave_base.shape[1] // Tout
+        Rf = -(-self.receptive_radius() // hop)
+        touts = [Tout] * B if mel_len is None else [self.ctx.vocoder_samples(int(m), True) // hop for m in mel_len]
+        if mel_len is not None:
+            # the stretch of a shorter clip clamps at ITS last frame: its rows come from the clip stretched alone
+            for b in range(B):
+                if touts[b] < Tout and ranges[b]:
+                    ext[b, :, :touts[b]] = self.ctx.extend_mel(mel_var[b:b + 1, :, :int(mel_len[b])].contiguous())[0]
+        wins = [(b, w0, w1) for b in range(B) for w0, w1 in G.plan_windows(ranges[b], touts[b], Rf)]
+        wave = wave_base.clone()
+        if not wins:
+            return wave
+        W = max(w1 - w0 for _, w0, w1 in wins)
+        win = torch.zeros(len(wins), D, W, dtype=torch.float32, device=self.device)
+        for i, (b, w0, w1) in enumerate(wins):
+            win[i, :, :w1 - w0] = ext[b, :, w0:w1]
+        out = self.vocode_ragged(win, [w1 - w0 for _, w0, w1 in wins], stretch=False)
+        for i, (b, w0, w1) in enumerate(wins):
+            k0, k1 = G.kept_region(w0, w1, touts[b], Rf)
+            wave[b, k0 * hop:k1 * hop] = out[i, (k0 - w0) * hop:(k1 - w0) * hop]
+        return wave
+
     def mel(self, wave22: torch.Tensor, mask_start: Optional[torch.Tensor] = None, mask_end: Optional[torch.Tensor] = None,
-            normalize: bool = True) -> torch.Tensor:
+            normalize: bool = True, spans: Optional[SpanTable] = None) -> torch.Tensor:
         """Vocoder-side front-end (I_ea/predict.py:99-106): zero [mask_start, mask_end) of each raw 22.05 kHz clip,
-        peak-normalise * 0.95, log-mel -> (B, 80, Tm)."""
+        peak-normalise * 0.95, log-mel -> (B, 80, Tm).  spans: a SpanTable of 22.05 kHz sample spans instead of the one span."""
+        if spans is not None:
+            if mask_start is not None or mask_end is not None:
+                raise ValueError("mel: `spans` replaces mask_start / mask_end")
+            return self.ctx.mel_frontend_spans(wave22, spans, normalize)
         return self.ctx.mel_frontend(wave22, mask_start, mask_end, normalize)
 
     def resample(self, x: torch.Tensor, sr_in: int, sr_out: int, kind: str = "kaiser_best", lens=None) -> torch.Tensor:
@@ -279,15 +339,23 @@ class InpaintingEngine:
 
     # ---- ragged batches (BASELINE configs[4]): clips of different lengths in ONE set of launches
     def encode_ragged(self, wave16: torch.Tensor, len16, mask_start: Optional[torch.Tensor] = None,
-                      mask_len: Optional[torch.Tensor] = None, normalize: bool = True) -> torch.Tensor:
+                      mask_len: Optional[torch.Tensor] = None, normalize: bool = True, spans: Optional[SpanTable] = None) -> torch.Tensor:
         """wave16 (B, Nmax): clip b = the first len16[b] samples of its row -> (B, Tmax, 80); each clip's frames equal that clip
         encoded alone (the reference handles one file per run, I_ea/predict.py:76-207); rows past a clip's frames are zero."""
         self._need(head=True, what="encode_ragged")
+        if spans is not None:
+            if mask_start is not None or mask_len is not None:
+                raise ValueError("encode_ragged: `spans` replaces mask_start / mask_len")
+            return self.ctx.hubert_forward_spans(wave16, spans, normalize, sample_len=len16)
         return self.ctx.hubert_forward_varlen(wave16, len16, mask_start, mask_len, normalize)
 
     def mel_ragged(self, wave22: torch.Tensor, len22, mask_start: Optional[torch.Tensor] = None,
-                   mask_end: Optional[torch.Tensor] = None, normalize: bool = True) -> torch.Tensor:
+                   mask_end: Optional[torch.Tensor] = None, normalize: bool = True, spans: Optional[SpanTable] = None) -> torch.Tensor:
         """`mel` for clips of different lengths: (B, N22max) + per-clip sample counts -> (B, 80, Tm_max), zero frames past a clip's own."""
+        if spans is not None:
+            if mask_start is not None or mask_end is not None:
+                raise ValueError("mel_ragged: `spans` replaces mask_start / mask_end")
+            return self.ctx.mel_frontend_spans(wave22, spans, normalize, sample_len=len22)
         return self.ctx.mel_frontend_varlen(wave22, len22, mask_start, mask_end, normalize)
 
     def vocode_ragged(self, mel: torch.Tensor, mel_len, stretch: bool = True) -> torch.Tensor:
@@ -322,6 +390,90 @@ class InpaintingEngine:
         wav = self.vocode_ragged(mel2, mel_len, stretch=True)
         return {"feats": feats, "labels": labels, "mel": mel2, "wave": wav, "frames": frames, "mel_len": mel_len, "label_cnt": cnt_h,
                 "wave_len": [self.ctx.vocoder_samples(m, True) for m in mel_len]}
+
+    # ---- several gaps per clip, one pass
+    def gap_tables(self, gaps, n16: Sequence[int], n_mel: Sequence[int], mel_frames: bool = False, spans22=None, staging=None) -> Dict[str, object]:
+        """Validate `gaps` (per clip a list of (first frame, frame count)) against each clip's min(T, Tm) and build what one multi-gap
+        pass needs: gaps (sorted), tab16 (SpanTable of the 16 kHz spans), tab22 (SpanTable of the 22.05 kHz spans: the gaps' by
+        I_ea/predict.py:99-100, or `spans22[b]` = [start, end) sample pairs; None when n_mel counts mel frames), frame_clip /
+        frame_pos (device int32 (F)), label_off (B + 1, host list).
+        n16: 16 kHz samples per clip; n_mel: 22.05 kHz samples per clip, or mel frames when mel_frames=True.
+        staging = (pinned int32 tensor, device int32 tensor, stream): all tables are written into the pinned buffer and cross in ONE
+        asynchronous copy on `stream` (the request front's host-to-device stream); the caller orders that stream before the compute
+        stream and keeps both buffers untouched until the pass is done.  Default: pageable copies on the current stream."""
+        if not (len(gaps) == len(n16) == len(n_mel)):
+            raise ValueError(f"gaps for {len(gaps)} clips, batch of {len(n16)}")
+        lim = [min(self.ctx.num_frames(int(a)), int(m) if mel_frames else self.ctx.mel_frames(int(m))) for a, m in zip(n16, n_mel)]
+        g = G.normalize_gaps(gaps, lim)
+        ci, fp, off = G.frame_table(g)
+        s16 = G.spans16(g)
+        s22 = None if mel_frames else (G.spans22(g, n_mel) if spans22 is None else G.clamp_spans22(spans22, n_mel))
+        F = len(ci)
+        if staging is None:
+            tab = torch.tensor([ci, fp], dtype=torch.int32).to(self.device)
+            return {"gaps": g, "tab16": SpanTable(s16, self.device), "tab22": None if s22 is None else SpanTable(s22, self.device),
+                    "frame_clip": tab[0].contiguous(), "frame_pos": tab[1].contiguous(), "label_off": off}
+        pin, dbuf, stream = staging
+        w16, w22 = SpanTable.words(s16), 0 if s22 is None else SpanTable.words(s22)
+        total = w16 + w22 + 2 * F
+        if total > min(pin.numel(), dbuf.numel()):
+            raise ValueError(f"gap_tables: the staging buffers hold {min(pin.numel(), dbuf.numel())} words, the tables need {total}")
+        hp = pin.numpy()
+        tab16 = SpanTable(s16, self.device, staged=(hp[:w16], dbuf[:w16]))
+        tab22 = None if s22 is None else SpanTable(s22, self.device, staged=(hp[w16:w16 + w22], dbuf[w16:w16 + w22]))
+        o = w16 + w22
+        hp[o:o + F] = ci
+        hp[o + F:o + 2 * F] = fp
+        with torch.cuda.stream(stream):
+            dbuf[:total].copy_(pin[:total], non_blocking=True)
+        return {"gaps": g, "tab16": tab16, "tab22": tab22, "frame_clip": dbuf[o:o + F], "frame_pos": dbuf[o + F:o + 2 * F], "label_off": off}
+
+    def predict_multigap_batch(self, wave16: torch.Tensor, mel_or_wave22: torch.Tensor, gaps, len16: Optional[Sequence[int]] = None,
+                               len22: Optional[Sequence[int]] = None, mel_len: Optional[Sequence[int]] = None,
+                               spans22: Optional[Sequence[Sequence[Sequence[int]]]] = None, tables: Optional[Dict[str, object]] = None,
+                               vocode: bool = True) -> Dict[str, object]:
+        """`predict_batch` with 0 .. MAX_SPANS gaps per clip, different per clip, in ONE pass: all gaps are zeroed before the one
+        encoder pass, all masked frames are decided and spliced by one launch, and the vocoder runs once.
+        wave16 (B, N) raw 16 kHz clips; mel_or_wave22: the (B, 80, Tm) log-mel of the masked 22.05 kHz clips, or the RAW (B, N22)
+        22.05 kHz clips, which are then masked (the gaps' spans by I_ea/predict.py:99-100, or `spans22[b]` = [start, end) sample
+        pairs per gap) and turned into the mel here.  gaps[b] = (first 20 ms frame, frame count) pairs, any order; overlapping gaps,
+        empty ones and gaps outside the clip's min(T, Tm) frames raise a ValueError naming clip and gap.
+        len16 (+ len22 for raw clips / mel_len for a mel): host lengths of a RAGGED batch; every clip then equals itself alone.
+        tables: what `gap_tables` returned for these gaps and lengths (a caller that staged them itself); `gaps` / `spans22` are
+        then not read.  vocode=False leaves the generator pass to the caller (no `wave`).
+        -> feats (B, T, 80), labels (F,) flat over clips then gaps then frames, label_off (B + 1) (clip b's labels =
+        labels[label_off[b]:label_off[b + 1]]), mel (the spliced mel), mel_masked, wave, gaps (sorted) [+ wave_len, frames, mel_len]."""
+        self._need(head=True, codebook=True, what="predict_multigap_batch")
+        B = wave16.shape[0]
+        raw22 = mel_or_wave22.dim() == 2
+        ragged = len16 is not None
+        n16 = [int(n) for n in len16] if ragged else [wave16.shape[1]] * B
+        if raw22:
+            n22 = [int(n) for n in len22] if len22 is not None else [mel_or_wave22.shape[1]] * B
+            if ragged and len22 is None:
+                raise ValueError("predict_multigap_batch: a ragged batch of raw 22.05 kHz clips needs len22")
+            tb = tables if tables is not None else self.gap_tables(gaps, n16, n22, spans22=spans22)
+            if tb["tab22"] is None:
+                raise ValueError("predict_multigap_batch: raw 22.05 kHz clips need tables with the 22.05 kHz spans")
+            mel = self.mel_ragged(mel_or_wave22, n22, spans=tb["tab22"]) if ragged else self.mel(mel_or_wave22, spans=tb["tab22"])
+            mlen = [self.ctx.mel_frames(n) for n in n22]
+        else:
+            mel = mel_or_wave22
+            mlen = [int(m) for m in mel_len] if mel_len is not None else [mel.shape[2]] * B
+            if ragged and mel_len is None:
+                raise ValueError("predict_multigap_batch: a ragged batch with a mel needs mel_len")
+            tb = tables if tables is not None else self.gap_tables(gaps, n16, mlen, mel_frames=True)
+        feats = self.encode_ragged(wave16, n16, spans=tb["tab16"]) if ragged else self.encode(wave16, spans=tb["tab16"])
+        mel2 = mel.clone()
+        labels = self.splice_spans(feats, tb["frame_clip"], tb["frame_pos"], mel2)
+        out = {"feats": feats, "labels": labels, "label_off": tb["label_off"], "mel": mel2, "mel_masked": mel, "gaps": tb["gaps"],
+               "frame_clip": tb["frame_clip"], "frame_pos": tb["frame_pos"]}
+        if ragged:
+            out.update(frames=[self.ctx.num_frames(n) for n in n16], mel_len=mlen,
+                       wave_len=[self.ctx.vocoder_samples(m, True) for m in mlen])
+        if vocode:
+            out["wave"] = self.vocode_ragged(mel2, mlen, stretch=True) if ragged else self.vocode(mel2, stretch=True)
+        return out
 
     def predict_batch(self, wave16: torch.Tensor, mel: torch.Tensor, frame_pos: torch.Tensor, frame_len: int,
                       blind: bool = False, mask_start: Optional[torch.Tensor] = None,

@@ -1,0 +1,138 @@
+"""Several gaps per clip: the host arithmetic of the multi-gap route (pure Python, no GPU).
+
+A gap is a pair (first 20 ms frame, frame count) and means what the reference's single mask means (I_ea/predict.py:99-102,132-134,
+164-168): 16 kHz samples [p * 320 + 80, (p + l) * 320 - 1) are zeroed, 22.05 kHz samples [p * 320 * 22050 // 16000,
+(p + l) * 320 * 22050 // 16000) are zeroed, encoder frames [p, p + l) are decided and mel frames [p, p + l) replaced.  A clip carries
+0 .. MAX_SPANS gaps, sorted and disjoint; the functions here validate them, turn them into the span tables (samples) and the frame
+table (clip, frame) the library's `_spans` entry points take, and plan the generator windows of the diagnostics passes.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Sequence, Tuple
+
+MAX_SPANS = 16          # SI_MAX_SPANS of include/si_hip.h: spans per clip
+
+Gap = Tuple[int, int]
+
+
+def _is_pair(e) -> bool:
+    try:
+        p, l = e
+        int(p), int(l)
+        return True
+    except (TypeError, ValueError):
+        return False
+
+
+def normalize_gaps(gaps: Sequence[Sequence[Sequence[int]]], limits: Optional[Sequence[int]] = None) -> List[List[Gap]]:
+    """Per clip: the gaps sorted by first frame, as (pos, len) int pairs.  Raises a ValueError naming the clip and the gap for a
+    frame count <= 0, a gap outside [0, limits[clip]) (the clip's min(T, Tm): the frames that exist on the encoder AND the mel
+    side), overlapping gaps (touching ones are fine) and more than MAX_SPANS gaps in one clip."""
+    out: List[List[Gap]] = []
+    for b, clip in enumerate(gaps):
+        try:
+            g = sorted((int(p), int(l)) for p, l in clip)
+        except (TypeError, ValueError):
+            bad = next((k for k, e in enumerate(clip) if not _is_pair(e)), None)
+            raise ValueError(f"clip {b}: gap {bad} = {clip[bad] if bad is not None else clip!r} is not a (first frame, frame count) pair") from None
+        if len(g) > MAX_SPANS:
+            raise ValueError(f"clip {b}: {len(g)} gaps, more than the {MAX_SPANS} a clip may carry")
+        for k, (p, l) in enumerate(g):
+            if l <= 0:
+                raise ValueError(f"clip {b}: gap {k} = ({p}, {l}) has no frames")
+            if p < 0 or (limits is not None and p + l > int(limits[b])):
+                lim = "" if limits is None else f" ({int(limits[b])} frames on both sides)"
+                raise ValueError(f"clip {b}: gap {k} = frames [{p}, {p + l}) does not fit the clip{lim}")
+            if k and p < g[k - 1][0] + g[k - 1][1]:
+                raise ValueError(f"clip {b}: gap {k} = frames [{p}, {p + l}) overlaps gap {k - 1} = "
+                                 f"[{g[k - 1][0]}, {g[k - 1][0] + g[k - 1][1]})")
+        out.append(g)
+    return out
+
+
+def spans16(gaps: Sequence[Sequence[Gap]]) -> List[List[Gap]]:
+    """(start, len) in 16 kHz samples per gap: `mask_samples_from_frames` (I_ea/predict.py:133)."""
+    return [[(p * 320 + 80, max((p + l) * 320 - 1 - (p * 320 + 80), 0)) for p, l in clip] for clip in gaps]
+
+
+def spans22(gaps: Sequence[Sequence[Gap]], n22: Optional[Sequence[int]] = None) -> List[List[Gap]]:
+    """(start, len) in 22.05 kHz samples per gap (I_ea/predict.py:99-100: the 16 kHz positions scaled by 22050 // 16000 after the
+    product), clamped to the clip's n22[b] samples when given."""
+    out = []
+    for b, clip in enumerate(gaps):
+        row = []
+        for p, l in clip:
+            s, e = p * 320 * 22050 // 16000, (p + l) * 320 * 22050 // 16000
+            if n22 is not None:
+                s, e = min(s, int(n22[b])), min(e, int(n22[b]))
+            row.append((s, e - s))
+        out.append(row)
+    return out
+
+
+def clamp_spans22(spans22: Sequence[Sequence[Sequence[int]]], n22: Sequence[int]) -> List[List[Gap]]:
+    """Explicit 22.05 kHz spans, per clip [start, end) sample pairs (the `mask22` of predict_clips): sorted, clamped to the clip's
+    n22[b] samples, as (start, len)."""
+    out = []
+    for clip, n in zip(spans22, n22):
+        row = []
+        for a, e in sorted((int(a), int(e)) for a, e in clip):
+            a = min(max(a, 0), int(n))
+            row.append((a, max(min(e, int(n)) - a, 0)))
+        out.append(row)
+    return out
+
+
+def csr(spans: Sequence[Sequence[Gap]]) -> Tuple[List[int], List[int], List[int]]:
+    """Per-clip (start, len) lists -> the CSR arrays (off (B + 1), start, len) of si_span_table."""
+    off, st, ln = [0], [], []
+    for clip in spans:
+        for s, l in clip:
+            st.append(int(s))
+            ln.append(int(l))
+        off.append(len(st))
+    return off, st, ln
+
+
+def frame_table(gaps: Sequence[Sequence[Gap]]) -> Tuple[List[int], List[int], List[int]]:
+    """The masked frames of all gaps of all clips, flattened clip by clip, gap by gap: (clip index (F), frame (F), label_off (B + 1));
+    clip b's labels are entries [label_off[b], label_off[b + 1]) of the flat label vector."""
+    clip_idx, pos, off = [], [], [0]
+    for b, clip in enumerate(gaps):
+        for p, l in clip:
+            clip_idx += [b] * l
+            pos += list(range(p, p + l))
+        off.append(len(pos))
+    return clip_idx, pos, off
+
+
+def stretched_range(p: int, l: int, t_out: int) -> Tuple[int, int]:
+    """Frames of the x441/256 stretched mel whose two source frames touch mel frames [p, p + l) (one frame of slack each side)."""
+    r = 441.0 / 256.0
+    c0 = max(int(math.floor((p - 0.5) * r - 0.5)) - 1, 0)
+    c1 = min(int(math.ceil((p + l + 0.5) * r - 0.5)) + 1, t_out)
+    return c0, c1
+
+
+def plan_windows(ranges: Sequence[Gap], t_out: int, rf: int) -> List[Tuple[int, int]]:
+    """Generator windows [w0, w1) (stretched frames) for one clip whose mel changed in the frame ranges `ranges` = (pos, len) pairs.
+    A window is the changed stretched frames widened by 2 * rf (rf = the generator's receptive radius in frames) and clamped to the
+    clip; of its output the outer rf frames at an edge that is not a clip edge are dropped (they miss neighbours), the rest -- its
+    KEPT region, which holds every frame within rf of a changed one -- is spliced back.  Windows that overlap or touch are merged
+    (so are, a fortiori, windows whose kept regions do): the result is sorted and disjoint, and one range gives `vocode_window`'s
+    single window."""
+    wins: List[Tuple[int, int]] = []
+    for p, l in sorted((int(p), int(l)) for p, l in ranges):
+        c0, c1 = stretched_range(p, l, t_out)
+        w0, w1 = max(c0 - 2 * rf, 0), min(c1 + 2 * rf, t_out)
+        if wins and w0 <= wins[-1][1]:
+            wins[-1] = (wins[-1][0], max(wins[-1][1], w1))
+        else:
+            wins.append((w0, w1))
+    return wins
+
+
+def kept_region(w0: int, w1: int, t_out: int, rf: int) -> Tuple[int, int]:
+    """The frames of window [w0, w1) whose output is spliced back."""
+    return w0 + (rf if w0 > 0 else 0), w1 - (rf if w1 < t_out else 0)

@@ -27,7 +27,10 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_f0_encoder_weight_floats", "si_f0_encoder_frames", "si_f0_encoder_workspace_bytes", "si_f0_encoder_forward",
            "si_resample_poly", "si_resample_sinc", "si_pcm16", "si_extend_mel", "si_hifigan_forward", "si_mel_frames", "si_mel_workspace_bytes", "si_mel_frontend", "si_num_frames",
            "si_vocoder_samples", "si_profile_start", "si_profile_filter", "si_profile_stop",
-           "si_debug_capture", "si_debug_size"]
+           "si_debug_capture", "si_debug_size",
+           "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
+           "si_codebook_metrics_spans"]
+SI_MAX_SPANS = 16
 
 
 class _F0EncStruct(C.Structure):
@@ -56,6 +59,45 @@ class SincFilter(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("nwin", C.c_int32), ("num_table", C.c_int32), ("step", C.c_int32), ("n_time", C.c_int32),
                 ("reserved", C.c_int32), ("scale", C.c_double), ("ratio", C.c_double), ("win", C.c_void_p), ("dwin", C.c_void_p),
                 ("time_reg", C.c_void_p)]
+
+
+class SpanTableStruct(C.Structure):
+    """Mirror of si_span_table."""
+    _fields_ = [("struct_size", C.c_int32), ("num_clips", C.c_int32), ("num_spans", C.c_int32), ("reserved", C.c_int32),
+                ("host_off", C.c_void_p), ("host_start", C.c_void_p), ("host_len", C.c_void_p),
+                ("span_off", C.c_void_p), ("span_start", C.c_void_p), ("span_len", C.c_void_p)]
+
+
+class SpanTable:
+    """The zeroed sample spans of a batch as si_span_table takes them: `spans` = per clip a list of (start, len) in samples, sorted
+    and disjoint (gaps.spans16 / gaps.spans22 build them from frame-level gaps).  Holds the host arrays the library validates and
+    ONE device tensor [off | start | len] the kernels read (a single host-to-device copy); the library refuses a table that is
+    unsorted, overlapping or above SI_MAX_SPANS spans per clip before it launches anything.
+    staged = (host, dev): int32 views of `words(spans)` elements each -- a numpy view of a caller-owned (pinned) host buffer, which
+    is filled here, and the device tensor the CALLER copies it to (on a stream of its choice, before the table is used)."""
+
+    @staticmethod
+    def words(spans) -> int:
+        return len(spans) + 2 + 2 * sum(len(c) for c in spans)
+
+    def __init__(self, spans, device, staged=None):
+        from .gaps import csr
+        off, st, ln = csr(spans)
+        self.B, self.n = len(off) - 1, len(st)
+        vals = np.array(off + st + ln + [0], dtype=np.int32)                                  # (+ 1: never an empty array)
+        if staged is None:
+            self.host = np.ascontiguousarray(vals)
+            self.dev = torch.from_numpy(self.host).to(device, non_blocking=True)
+        else:
+            self.host, self.dev = staged
+            if self.host.size != vals.size or self.dev.numel() != vals.size:
+                raise ValueError(f"SpanTable: staged views of {self.host.size} / {self.dev.numel()} words, the table has {vals.size}")
+            np.copyto(self.host, vals)
+
+    def struct(self) -> SpanTableStruct:
+        h, d, B, n = self.host.ctypes.data, self.dev.data_ptr(), self.B, self.n
+        return SpanTableStruct(C.sizeof(SpanTableStruct), B, n, 0, h, h + 4 * (B + 1), h + 4 * (B + 1 + n),
+                               d, d + 4 * (B + 1), d + 4 * (B + 1 + n))
 
 
 class ExtractDesc(C.Structure):
@@ -192,6 +234,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_mel_frames.argtypes = [i32]
     lib.si_mel_workspace_bytes.argtypes = [vp, i32, i32, C.POINTER(sz)]
     lib.si_mel_frontend.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]
+    lib.si_hubert_forward_spans.argtypes = [vp, vp, C.POINTER(SpanTableStruct), vp, i32, i32, i32, vp, vp, sz, vp]
+    lib.si_mel_frontend_spans.argtypes = [vp, vp, C.POINTER(SpanTableStruct), vp, i32, i32, i32, vp, vp, sz, vp]
+    lib.si_codebook_splice_spans.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]
+    lib.si_codebook_splice_labels_spans.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp]
+    lib.si_codebook_metrics_spans.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.si_num_frames.argtypes = [vp, i32]
     lib.si_vocoder_samples.argtypes = [vp, i32, i32]
     lib.si_debug_capture.argtypes = [vp, C.c_char_p, vp, C.c_long]
@@ -398,6 +445,79 @@ class NativeContext:
                                                     int(normalize), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
                     "si_mel_frontend_varlen")
         return out
+
+    # ---- several gaps per clip (si_span_table / frame tables)
+    def hubert_forward_spans(self, wav: torch.Tensor, spans: "SpanTable", normalize: bool = True, sample_len=None) -> torch.Tensor:
+        """hubert_forward / hubert_forward_varlen (sample_len: host ints) with every span of `spans` (16 kHz samples) zeroed."""
+        assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
+        B, N = wav.shape
+        T = self.num_frames(N)
+        if T < 1:
+            raise ValueError(f"clip of {N} samples is too short")
+        lens = None if sample_len is None else self._host_lens(sample_len, B)
+        out = torch.empty(B, T, self.desc.codebook_dim, dtype=torch.float32, device=self.device)
+        ws = self.workspace(B, N, 0)
+        t = spans.struct()
+        self._check(self.lib.si_hubert_forward_spans(self._h, _ptr(wav), C.byref(t), None if lens is None else lens.ctypes.data_as(C.c_void_p),
+                                                     int(normalize), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
+                    "si_hubert_forward_spans")
+        return out
+
+    def mel_frontend_spans(self, wave22: torch.Tensor, spans: "SpanTable", normalize: bool = True, sample_len=None) -> torch.Tensor:
+        """mel_frontend / mel_frontend_varlen (sample_len: host ints) with every span of `spans` (22.05 kHz samples) zeroed."""
+        assert wave22.is_cuda and wave22.dtype == torch.float32 and wave22.dim() == 2 and wave22.is_contiguous()
+        B, N = wave22.shape
+        Tm = int(self.lib.si_mel_frames(N))
+        if Tm < 1:
+            raise ValueError(f"clip of {N} samples is too short for the mel front-end")
+        lens = None if sample_len is None else self._host_lens(sample_len, B)
+        ws = self._mel_workspace(B, N)
+        out = torch.empty(B, 80, Tm, dtype=torch.float32, device=self.device)
+        t = spans.struct()
+        self._check(self.lib.si_mel_frontend_spans(self._h, _ptr(wave22), C.byref(t), None if lens is None else lens.ctypes.data_as(C.c_void_p),
+                                                   int(normalize), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
+                    "si_mel_frontend_spans")
+        return out
+
+    def _frame_table(self, frame_clip: torch.Tensor, frame_pos: torch.Tensor) -> int:
+        for m in (frame_clip, frame_pos):
+            assert m.is_cuda and m.dtype == torch.int32 and m.is_contiguous() and m.dim() == 1
+        assert frame_clip.numel() == frame_pos.numel()
+        return frame_clip.numel()
+
+    def codebook_splice_spans(self, feats: torch.Tensor, frame_clip: torch.Tensor, frame_pos: torch.Tensor, mel: torch.Tensor) -> torch.Tensor:
+        """In-place splice into `mel` (B, D, Tm) of the frames of a frame table (clip, frame: int32 (F) each); labels (F,) int64."""
+        assert feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous() and feats.dim() == 3
+        assert mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.dim() == 3
+        B, T, D = feats.shape
+        assert mel.shape[0] == B and mel.shape[1] == D
+        F = self._frame_table(frame_clip, frame_pos)
+        labels = torch.empty(F, dtype=torch.int64, device=self.device)
+        self._check(self.lib.si_codebook_splice_spans(self._h, _ptr(feats), B, T, _ptr(frame_clip), _ptr(frame_pos), F, _ptr(mel), mel.shape[2],
+                                                      _ptr(labels), self._stream()), "si_codebook_splice_spans")
+        return labels
+
+    def codebook_splice_labels_spans(self, labels: torch.Tensor, frame_clip: torch.Tensor, frame_pos: torch.Tensor, mel: torch.Tensor) -> None:
+        """In-place splice of the raw centroids of GIVEN labels (F,) int64 at the frames of a frame table."""
+        assert mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.dim() == 3
+        F = self._frame_table(frame_clip, frame_pos)
+        assert labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == F
+        self._check(self.lib.si_codebook_splice_labels_spans(self._h, _ptr(labels), mel.shape[0], _ptr(frame_clip), _ptr(frame_pos), F, _ptr(mel),
+                                                             mel.shape[2], self._stream()), "si_codebook_splice_labels_spans")
+
+    def codebook_metrics_spans(self, feats: torch.Tensor, frame_clip: torch.Tensor, frame_pos: torch.Tensor, target: torch.Tensor):
+        """-> (loss (1,), loss_terms (F,), pred_labels (F,) int64, cos_pred_target (F,)) over the frames of a frame table."""
+        assert feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous() and feats.dim() == 3
+        B, T, D = feats.shape
+        F = self._frame_table(frame_clip, frame_pos)
+        assert target.is_cuda and target.dtype == torch.int64 and target.is_contiguous() and target.numel() == F
+        terms = torch.empty(F, dtype=torch.float32, device=self.device)
+        cpt = torch.empty(F, dtype=torch.float32, device=self.device)
+        pred = torch.empty(F, dtype=torch.int64, device=self.device)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        self._check(self.lib.si_codebook_metrics_spans(self._h, _ptr(feats), B, T, _ptr(frame_clip), _ptr(frame_pos), F, _ptr(target), _ptr(terms),
+                                                       _ptr(loss), _ptr(pred), _ptr(cpt), self._stream()), "si_codebook_metrics_spans")
+        return loss, terms, pred, cpt
 
     def hubert_extract_features(self, wav: torch.Tensor, output_layer: int, normalize="layer_norm",
                                 mask_start: Optional[torch.Tensor] = None, mask_len: Optional[torch.Tensor] = None,

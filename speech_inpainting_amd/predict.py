@@ -56,10 +56,17 @@ def check_mask_span(engine: InpaintingEngine, n16: int, n22: int, mask_pos: Sequ
                              f"({T} encoder frames, {Tm} mel frames)")
 
 
+def _one_of(mask_pos, mask_frames, gaps, blind: bool) -> None:
+    if gaps is not None and (mask_pos is not None or mask_frames is not None or blind):
+        raise ValueError("give either mask_pos / mask_frames (one gap per clip) or gaps= (several), not both; blind mode takes no gaps")
+    if gaps is None and (mask_pos is None or mask_frames is None):
+        raise ValueError("mask_pos and mask_frames (or gaps=) are required")
+
+
 def predict_clips(engine: InpaintingEngine, waves16: Sequence[np.ndarray], waves22: Sequence[np.ndarray],
-                  mask_pos: Sequence[int], mask_frames: int, blind: bool = False,
+                  mask_pos: Optional[Sequence[int]] = None, mask_frames: Optional[int] = None, blind: bool = False,
                   mask22: Optional[Sequence[Tuple[int, int]]] = None, diagnostics: bool = False,
-                  target_labels: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                  target_labels: Optional[torch.Tensor] = None, gaps=None) -> Dict[str, torch.Tensor]:
     """Batch form of I_ea/predict.py:97-207 for clips of EQUAL length.
     waves16 / waves22: the same clips at 16 kHz / 22.05 kHz (float32, un-normalised), mask_pos: first masked 20 ms frame.
     mask22: per-clip [start, end) of the span zeroed on the 22.05 kHz side (predict.py:99-102: the 16 kHz sample
@@ -67,7 +74,10 @@ def predict_clips(engine: InpaintingEngine, waves16: Sequence[np.ndarray], waves
     diagnostics=True adds the script's other two vocoder passes as batch outputs: `hifi_masked` (the generator on the
     masked mel alone, predict.py:123-128) and -- when `target_labels` (B, Lm) int64 ground-truth codewords are given --
     `expected_inpaint` (their centroids spliced instead of the predicted ones, predict.py:177-189,198-201) plus the
-    codeword metrics of predict.py:171-173 (`loss`, `cos_pred_target`)."""
+    codeword metrics of predict.py:171-173 (`loss`, `cos_pred_target`).
+    gaps: instead of mask_pos / mask_frames, per clip a list of (first frame, frame count) -- several gaps per clip, different per
+    clip, in one pass (engine.predict_multigap_batch).  `labels` is then flat (F,) with `label_off` (B + 1), `target_labels` flat (F,)
+    in the same order, and mask22 per clip a list of [start, end) pairs, one per gap in sorted order."""
     dev = engine.device
     n16, n22 = len(waves16[0]), len(waves22[0])
     if any(len(w) != n16 for w in waves16) or any(len(w) != n22 for w in waves22):
@@ -75,14 +85,40 @@ def predict_clips(engine: InpaintingEngine, waves16: Sequence[np.ndarray], waves
                          "different lengths)")
     wave22 = torch.from_numpy(np.stack([np.asarray(w, dtype=np.float32) for w in waves22])).to(dev)
     wave = torch.from_numpy(np.stack([np.asarray(w, dtype=np.float32) for w in waves16])).to(dev)
-    return predict_resident(engine, wave, wave22, mask_pos, mask_frames, blind, mask22, diagnostics, target_labels)
+    return predict_resident(engine, wave, wave22, mask_pos, mask_frames, blind, mask22, diagnostics, target_labels, gaps)
 
 
-def predict_resident(engine: InpaintingEngine, wave: torch.Tensor, wave22: torch.Tensor, mask_pos: Sequence[int], mask_frames: int,
-                     blind: bool = False, mask22: Optional[Sequence[Tuple[int, int]]] = None, diagnostics: bool = False,
-                     target_labels: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+def _predict_gaps(engine: InpaintingEngine, wave: torch.Tensor, wave22: torch.Tensor, gaps, mask22, diagnostics: bool,
+                  target_labels: Optional[torch.Tensor], len16=None, len22=None) -> Dict[str, object]:
+    """The multi-gap body of predict_resident / predict_clips_ragged.  diagnostics: ONE full generator pass over the masked mel
+    (`hifi_masked`); `wave` and `expected_inpaint` come from windowed passes over the merged windows around the gaps
+    (engine.vocode_windows: bit-identical to full passes)."""
+    out = engine.predict_multigap_batch(wave, wave22, gaps, len16=len16, len22=len22, spans22=mask22, vocode=not diagnostics)
+    if not diagnostics:
+        return out
+    mlen = out["mel_len"] if len16 is not None else None
+    mel = out["mel_masked"]
+    base = engine.vocode_ragged(mel, mlen, stretch=True) if mlen is not None else engine.vocode(mel, stretch=True)
+    out["hifi_masked"] = base
+    out["wave"] = engine.vocode_windows(base, out["mel"], out["gaps"], mlen)
+    if target_labels is not None:
+        tgt = target_labels.to(engine.device, torch.int64).reshape(-1).contiguous()
+        exp = mel.clone()
+        engine.splice_labels_spans(tgt, out["frame_clip"], out["frame_pos"], exp)
+        out["expected_inpaint"] = engine.vocode_windows(base, exp, out["gaps"], mlen)
+        m = engine.codebook_metrics_spans(out["feats"], out["frame_clip"], out["frame_pos"], tgt)
+        out["loss"], out["cos_pred_target"] = m["loss"], m["cos_pred_target"]
+    return out
+
+
+def predict_resident(engine: InpaintingEngine, wave: torch.Tensor, wave22: torch.Tensor, mask_pos: Optional[Sequence[int]] = None,
+                     mask_frames: Optional[int] = None, blind: bool = False, mask22: Optional[Sequence[Tuple[int, int]]] = None,
+                     diagnostics: bool = False, target_labels: Optional[torch.Tensor] = None, gaps=None) -> Dict[str, torch.Tensor]:
     """`predict_clips` on clips that are already on the GPU: wave (B, n16) / wave22 (B, n22) float32 device tensors (e.g. straight
     out of `engine.resample`); same outputs."""
+    _one_of(mask_pos, mask_frames, gaps, blind)
+    if gaps is not None:
+        return _predict_gaps(engine, wave, wave22, gaps, mask22, diagnostics, target_labels)
     dev = engine.device
     n16, n22 = wave.shape[1], wave22.shape[1]
     if not blind:
@@ -177,11 +213,20 @@ def pad_stack(waves: Sequence[np.ndarray]) -> Tuple[torch.Tensor, List[int]]:
 
 
 def predict_clips_ragged(engine: InpaintingEngine, waves16: Sequence[np.ndarray], waves22: Sequence[np.ndarray],
-                         mask_pos: Sequence[int], mask_frames: int, blind: bool = False,
-                         mask22: Optional[Sequence[Tuple[int, int]]] = None) -> Dict[str, object]:
+                         mask_pos: Optional[Sequence[int]] = None, mask_frames: Optional[int] = None, blind: bool = False,
+                         mask22: Optional[Sequence[Tuple[int, int]]] = None, gaps=None, diagnostics: bool = False,
+                         target_labels: Optional[torch.Tensor] = None) -> Dict[str, object]:
     """`predict_clips` for clips of DIFFERENT lengths in ONE set of launches (the library's ragged-batch entry points): every
-    clip's outputs equal that clip's alone.  Tensors are (B, longest ...); `wave_len`, `frames`, `mel_len` give each clip's extent."""
+    clip's outputs equal that clip's alone.  Tensors are (B, longest ...); `wave_len`, `frames`, `mel_len` give each clip's extent.
+    gaps (with diagnostics / target_labels): several gaps per clip, as predict_clips."""
     dev = engine.device
+    _one_of(mask_pos, mask_frames, gaps, blind)
+    if gaps is not None:
+        w22, len22 = pad_stack(waves22)
+        w16, len16 = pad_stack(waves16)
+        return _predict_gaps(engine, w16.to(dev), w22.to(dev), gaps, mask22, diagnostics, target_labels, len16, len22)
+    if diagnostics or target_labels is not None:
+        raise ValueError("predict_clips_ragged: diagnostics are served on the gaps= route")
     if not blind:
         for i, (a, b) in enumerate(zip(waves16, waves22)):
             check_mask_span(engine, len(a), len(b), [mask_pos[i]], mask_frames)
@@ -247,18 +292,27 @@ def main(argv=None) -> int:
     wave_22 = engine.resample(raw_dev, sr_file, 22050)                             # resampler (resampy kaiser_best); they STAY there
     wave_16 = engine.resample(raw_dev, sr_file, 16000)
     audio.write_wav(os.path.join(save_dir, "orig.wav"), wave_16[0].cpu().numpy(), 16000)
-    pos, lm = cfg.mask_pos, cfg.mask_frames
+    # one `mask:` (the reference's schema) or a `masks:` list: the same steps per gap
+    multi = cfg.gaps is not None
+    gap_list = sorted(cfg.gaps) if multi else [(cfg.mask_pos, cfg.mask_frames)]
     masked_16 = wave_16[0].clone()
-    masked_16[pos * 320 + 80:(pos + lm) * 320 + 79 - 80] = 0                       # predict.py:133
+    for pos, lm in gap_list:
+        masked_16[pos * 320 + 80:(pos + lm) * 320 + 79 - 80] = 0                   # predict.py:133
     audio.write_wav(os.path.join(save_dir, "masked.wav"), masked_16.cpu().numpy(), 16000)
 
-    span22 = (cfg.start_sample * 22050 // 16000, cfg.end_sample * 22050 // 16000)   # predict.py:99-100
     labels_path = os.path.join(cfg.path2centroids, wave_name + "_labels.pt")
     labels = None
     if os.path.exists(labels_path):                                                # predict.py:160-161
-        labels = torch.load(labels_path, map_location="cpu").t().reshape(-1)[pos:pos + lm].long()
-    out = predict_resident(engine, wave_16, wave_22, [pos], lm, mask22=[span22], diagnostics=True,
-                           target_labels=None if labels is None else labels[None])
+        all_labels = torch.load(labels_path, map_location="cpu").t().reshape(-1)
+        labels = torch.cat([all_labels[pos:pos + lm] for pos, lm in gap_list]).long()
+    if multi:
+        out = predict_resident(engine, wave_16, wave_22, gaps=[gap_list], mask22=[cfg.spans22], diagnostics=True, target_labels=labels)
+        out["labels"] = out["labels"][None]
+    else:
+        pos, lm = gap_list[0]
+        span22 = (cfg.start_sample * 22050 // 16000, cfg.end_sample * 22050 // 16000)   # predict.py:99-100
+        out = predict_resident(engine, wave_16, wave_22, [pos], lm, mask22=[span22], diagnostics=True,
+                               target_labels=None if labels is None else labels[None])
     pcm = lambda w: engine.to_int16(w[0]).cpu().numpy()                            # predict.py:204-206 on the GPU (si_pcm16)
     # hifi_masked.wav: the vocoder on the masked mel alone (predict.py:123-128)
     audio.write_wav(os.path.join(save_dir, "hifi_masked.wav"), pcm(out["hifi_masked"]), 22050)

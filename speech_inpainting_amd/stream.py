@@ -20,6 +20,7 @@ from typing import Iterable, Iterator, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import gaps as G
 from .engine import InpaintingEngine
 
 
@@ -27,17 +28,20 @@ from .engine import InpaintingEngine
 class Request:
     """One batch of clips at the FILE's sample rate (what `sf.read` / `librosa.load(sr=None)` yields: float32 in [-1, 1])."""
     clips: Sequence[np.ndarray]
-    mask_pos: Sequence[int]                 # first masked 20 ms frame per clip (ignored when blind)
+    mask_pos: Sequence[int] = ()            # first masked 20 ms frame per clip (ignored when blind or when gaps are given)
     mask_frames: int = 10
     blind: bool = False
     tag: object = None
+    gaps: Optional[Sequence[Sequence[Sequence[int]]]] = None   # per clip a list of (first frame, frame count): several gaps per clip,
+                                                               # one pass (replaces mask_pos / mask_frames; not with blind)
 
 
 @dataclass
 class Result:
     pcm: List[np.ndarray]                   # int16 at 22.05 kHz, one array per clip, cut to the clip's own length
-    labels: torch.Tensor                    # (B, Lm) predicted codewords (host)
+    labels: torch.Tensor                    # (B, Lm) predicted codewords (host); with gaps: flat (F,), clip b = [label_off[b], label_off[b + 1])
     tag: object = None
+    label_off: Optional[List[int]] = None
 
 
 @dataclass
@@ -46,6 +50,8 @@ class _Slot:
     dev_in: Optional[torch.Tensor] = None
     pin_out: Optional[torch.Tensor] = None
     pin_lab: Optional[torch.Tensor] = None
+    pin_tab: Optional[torch.Tensor] = None  # the gap tables of a Request with gaps (int32): pinned, and their device copy
+    dev_tab: Optional[torch.Tensor] = None
     ev_h2d: torch.cuda.Event = field(default_factory=torch.cuda.Event)
     ev_done: torch.cuda.Event = field(default_factory=torch.cuda.Event)
     ev_d2h: torch.cuda.Event = field(default_factory=torch.cuda.Event)
@@ -68,7 +74,7 @@ class RequestFront:
     def _len_at(self, n: int, sr: int) -> int:
         return n if sr == self.sr_in else int(math.ceil(n * float(sr) / self.sr_in))
 
-    def _ensure(self, s: _Slot, B: int, n_in: int, n_out: int, lm: int):
+    def _ensure(self, s: _Slot, B: int, n_in: int, n_out: int, lm: int, n_tab: int = 0):
         # flat, persistent buffers per slot: the device side of the H2D copy must never be a block the caching allocator could
         # hand out while kernels of the compute stream still use it (the copy stream is not ordered with that stream's frees)
         if s.pin_in is None or s.pin_in.numel() < B * n_in:
@@ -78,6 +84,9 @@ class RequestFront:
             s.pin_out = torch.empty(B * n_out, dtype=torch.int16).pin_memory()
         if s.pin_lab is None or s.pin_lab.numel() < B * max(lm, 1):
             s.pin_lab = torch.empty(B * max(lm, 1), dtype=torch.int64).pin_memory()
+        if n_tab and (s.pin_tab is None or s.pin_tab.numel() < n_tab):
+            s.pin_tab = torch.empty(n_tab, dtype=torch.int32).pin_memory()
+            s.dev_tab = torch.empty(n_tab, dtype=torch.int32, device=self.dev)
 
     def _submit(self, s: _Slot, rq: Request):
         eng, dev = self.engine, self.dev
@@ -89,9 +98,23 @@ class RequestFront:
         len16 = [self._len_at(n, 16000) for n in lens]
         mel_len = [eng.ctx.mel_frames(n) for n in len22]
         frames = [eng.ctx.num_frames(n) for n in len16]
+        if rq.gaps is not None and rq.blind:
+            raise ValueError("Request: blind mode takes no gaps")
         lm = max(min(t, m) for t, m in zip(frames, mel_len)) if rq.blind else int(rq.mask_frames)
+        n_tab = 0
+        gaps = None
+        if rq.gaps is not None:
+            # validated BEFORE any slot buffer is sized from them: a refused request (ValueError naming clip and gap) leaves the slot as it was
+            if len(rq.gaps) != B:
+                raise ValueError(f"Request: gaps for {len(rq.gaps)} clips, batch of {B}")
+            gaps = G.normalize_gaps(rq.gaps, [min(t, m) for t, m in zip(frames, mel_len)])
+            # label buffer: all masked frames of the batch, flat; table buffer: two span tables (off (B + 1), start, len, one spare
+            # word each) and the frame table (clip, frame per masked frame)
+            F = sum(l for clip in gaps for _, l in clip)
+            lm = -(-F // B)
+            n_tab = 2 * (B + 2 + 2 * sum(len(clip) for clip in gaps)) + 2 * F
         n_wave = eng.ctx.vocoder_samples(max(mel_len), True)
-        self._ensure(s, B, n_in, n_wave, lm)
+        self._ensure(s, B, n_in, n_wave, lm, n_tab)
         # host -> pinned (zero tail for shorter clips), pinned -> device on the copy stream
         # (numpy views of the pinned buffers: plain memcpy.  torch CPU ops here would each wake the intra-op thread pool, whose
         #  spinning workers burn the job's CPU quota until the cgroup is throttled -- measured: 70-280 ms stalls per request)
@@ -103,13 +126,33 @@ class RequestFront:
                 pin_np[i, lens[i]:] = 0.0
         compute = torch.cuda.current_stream(dev)
         raw = s.dev_in[:B * n_in].view(B, n_in)
+        tables = None
         with torch.cuda.stream(self.h2d):
             raw.copy_(pin, non_blocking=True)
-            s.ev_h2d.record(self.h2d)
+        if rq.gaps is not None:
+            # the span tables (16 kHz and 22.05 kHz) and the frame table are validated and built on the host, into the slot's pinned
+            # buffer, and cross on the copy stream behind the clips: no copy of this request waits on the compute stream
+            tables = eng.gap_tables(gaps, len16, len22, staging=(s.pin_tab, s.dev_tab, self.h2d))
+        s.ev_h2d.record(self.h2d)
         compute.wait_event(s.ev_h2d)
         # librosa.load x 2 (I_ea/predict.py:79-80): the file's samples at 22.05 kHz and at 16 kHz
         w22 = raw if self.sr_in == 22050 else eng.resample(raw, self.sr_in, 22050, lens=lens if ragged else None)
         w16 = raw if self.sr_in == 16000 else eng.resample(raw, self.sr_in, 16000, lens=lens if ragged else None)
+        if rq.gaps is not None:
+            out = eng.predict_multigap_batch(w16, w22, gaps, len16=len16 if ragged else None, len22=len22 if ragged else None,
+                                             tables=tables)
+            wave_len = out["wave_len"] if ragged else [out["wave"].shape[1]] * B
+            pcm = eng.to_int16(out["wave"])
+            s.ev_done.record(compute)
+            self.d2h.wait_event(s.ev_done)
+            F = out["labels"].numel()
+            with torch.cuda.stream(self.d2h):
+                s.pin_out[:pcm.numel()].view(pcm.shape).copy_(pcm, non_blocking=True)
+                s.pin_lab[:F].copy_(out["labels"], non_blocking=True)
+                s.ev_d2h.record(self.d2h)
+            s.keep = (w22, w16, out, pcm)
+            s.meta = dict(B=B, wave_len=wave_len, n_lab=F, n_wave=pcm.shape[1], tag=rq.tag, label_off=out["label_off"])
+            return
         pos = torch.tensor([int(p) for p in rq.mask_pos], dtype=torch.int32).to(dev, non_blocking=True)
         if rq.blind:
             s22 = e22 = None
@@ -140,9 +183,12 @@ class RequestFront:
         m = s.meta
         po = s.pin_out.numpy()[:m["B"] * m["n_wave"]].reshape(m["B"], m["n_wave"])
         pcm = [po[i, :m["wave_len"][i]].copy() for i in range(m["B"])]
-        lab = torch.from_numpy(s.pin_lab.numpy()[:m["B"] * m["n_lab"]].reshape(m["B"], m["n_lab"]).copy())
+        if m.get("label_off") is not None:
+            lab = torch.from_numpy(s.pin_lab.numpy()[:m["n_lab"]].copy())
+        else:
+            lab = torch.from_numpy(s.pin_lab.numpy()[:m["B"] * m["n_lab"]].reshape(m["B"], m["n_lab"]).copy())
         s.keep, s.meta = (), None
-        return Result(pcm, lab, m["tag"])
+        return Result(pcm, lab, m["tag"], m.get("label_off"))
 
     def run(self, requests: Iterable[Request]) -> Iterator[Result]:
         inflight: List[_Slot] = []

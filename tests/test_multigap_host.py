@@ -1,0 +1,170 @@
+"""Host side of the multi-gap route (several masked spans per clip in one pass): gap validation, the span and frame tables,
+the `masks:` YAML schema and the generator-window planner.  No GPU, no compute calls."""
+import os
+import random
+import re
+
+import pytest
+import yaml
+
+from oracle import ref_cpu as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ------------------------------------------------------------------------------------------------------------ validation
+def test_gaps_are_sorted_and_touching_gaps_are_accepted():
+    from speech_inpainting_amd import gaps as G
+    g = G.normalize_gaps([[(90, 10), (20, 5), (100, 12)], [], [(0, 3)]], [199, 199, 199])
+    assert g == [[(20, 5), (90, 10), (100, 12)], [], [(0, 3)]]           # (90, 10) and (100, 12) touch
+
+
+@pytest.mark.parametrize("gaps,clip,gap", [
+    ([[(20, 5)], [(60, 10), (65, 2)]], 1, 1),          # overlap
+    ([[(20, 0)]], 0, 0),                               # no frames
+    ([[], [], [(5, 3), (40, -1)]], 2, 1),              # negative count
+    ([[(190, 10)]], 0, 0),                             # past min(T, Tm) = 199
+    ([[(-1, 4)]], 0, 0),                               # before the clip
+    ([[(20, 5)], [(30, 4), (60, 10, 2)]], 1, 1),       # not a pair
+    ([[(20, 5), 40]], 0, 1),                           # not a pair
+])
+def test_bad_gaps_raise_naming_clip_and_gap(gaps, clip, gap):
+    from speech_inpainting_amd import gaps as G
+    with pytest.raises(ValueError) as e:
+        G.normalize_gaps(gaps, [199] * len(gaps))
+    assert f"clip {clip}" in str(e.value) and f"gap {gap}" in str(e.value)
+
+
+def test_more_gaps_than_the_cap_are_refused():
+    from speech_inpainting_amd import gaps as G
+    from speech_inpainting_amd import native
+    hdr = open(os.path.join(ROOT, "include", "si_hip.h")).read()
+    cap = int(re.search(r"#define\s+SI_MAX_SPANS\s+(\d+)", hdr).group(1))
+    assert G.MAX_SPANS == native.SI_MAX_SPANS == cap
+    ok = [[(4 * i, 2) for i in range(cap)]]
+    assert len(G.normalize_gaps(ok, [199])[0]) == cap
+    with pytest.raises(ValueError, match="clip 0"):
+        G.normalize_gaps([[(4 * i, 2) for i in range(cap + 1)]], [199])
+
+
+# ------------------------------------------------------------------------------------------------------------ tables
+def test_span_tables_against_the_oracles_single_mask():
+    from speech_inpainting_amd import gaps as G
+    gaps = [[(20, 5), (90, 10), (150, 20)], [(60, 10)], [], [(5, 3), (40, 8), (100, 12), (170, 15)]]
+    s16 = G.spans16(gaps)
+    for clip, spans in zip(gaps, s16):
+        assert spans == [R.mask_samples_from_frames(p, l) for p, l in clip]
+    n22 = 88200
+    s22 = G.spans22(gaps, [n22] * 4)
+    for clip, spans in zip(gaps, s22):
+        for (p, l), (s, n) in zip(clip, spans):
+            assert (s, s + n) == (p * 320 * 22050 // 16000, (p + l) * 320 * 22050 // 16000)      # I_ea/predict.py:99-100
+    off, st, ln = G.csr(s16)
+    assert off == [0, 3, 4, 4, 8] and len(st) == len(ln) == 8
+    assert all(st[k] + ln[k] <= st[k + 1] for b in range(4) for k in range(off[b], off[b + 1] - 1))
+    # the 22.05 kHz span of a gap at the end of a clip is clamped to the clip
+    assert G.spans22([[(190, 9)]], [87000])[0][0] == (83790, 87000 - 83790)            # unclamped end: 87759
+    ci, fp, loff = G.frame_table(gaps)
+    assert loff == [0, 35, 45, 45, 83] and len(ci) == len(fp) == 83
+    assert ci[:35] == [0] * 35 and fp[:5] == [20, 21, 22, 23, 24] and fp[5] == 90 and ci[45:] == [3] * 38 and fp[-1] == 184
+
+
+# ------------------------------------------------------------------------------------------------------------ YAML
+def _yaml(tmp_path, extra):
+    base = {"training_config": {"dataset": "d"}, "km_model": {"n_clusters": 100, "d": {"km_model_path": "k", "path2centroids": "c"}},
+            "hifi_gan": {"checkpoint_file": "g/gen"}, "wave": {"d": {"wave_path": "w.wav", "save_pred": "out"}},
+            "hubert_model": {"type": "base", "d": {"model_checkpoint": "m.pt"}}}
+    base.update(extra)
+    p = tmp_path / "predict.yaml"
+    p.write_text(yaml.safe_dump(base))
+    return str(p)
+
+
+def test_masks_list_in_predict_yaml(tmp_path):
+    from speech_inpainting_amd.config import load_predict_config
+    one = load_predict_config(_yaml(tmp_path, {"mask": {"start_pos_in_sec": 1.5, "end_pos_in_sec": 1.75}}))
+    assert one.gaps is None and one.masks is None and (one.mask_pos, one.mask_frames) == (75, 12)      # as before
+    many = load_predict_config(_yaml(tmp_path, {"masks": [{"start_pos_in_sec": 2.5, "end_pos_in_sec": 3.0},
+                                                          {"start_pos_in_sec": 0.5, "end_pos_in_sec": 0.75},
+                                                          {"start_pos_in_sec": 1.5, "end_pos_in_sec": 1.75}]}))
+    assert many.gaps == [(25, 12), (75, 12), (125, 25)]                    # sorted; each by the single mask's arithmetic
+    assert many.gaps[1] == (one.mask_pos, one.mask_frames)
+    assert many.spans22[1] == (one.start_sample * 22050 // 16000, one.end_sample * 22050 // 16000)
+    with pytest.raises(ValueError, match="not both"):
+        load_predict_config(_yaml(tmp_path, {"mask": {"start_pos_in_sec": 1.5, "end_pos_in_sec": 1.75},
+                                             "masks": [{"start_pos_in_sec": 0.4, "end_pos_in_sec": 0.5}]}))
+    with pytest.raises(ValueError, match="masks"):
+        load_predict_config(_yaml(tmp_path, {"masks": []}))
+
+
+# ------------------------------------------------------------------------------------------------------------ window planner
+def _todays_window(p, lm, t_out, rf):
+    """engine.vocode_window's single window, restated."""
+    import math
+    r = 441.0 / 256.0
+    c0 = max(int(math.floor((p - 0.5) * r - 0.5)) - 1, 0)
+    c1 = min(int(math.ceil((p + lm + 0.5) * r - 0.5)) + 1, t_out)
+    return max(c0 - 2 * rf, 0), min(c1 + 2 * rf, t_out)
+
+
+def test_one_gap_plans_todays_single_window():
+    from speech_inpainting_amd import gaps as G
+    for t_out, rf in ((344, 16), (344, 7), (120, 3)):
+        for p, lm in ((0, 4), (1, 10), (70, 10), (t_out * 256 // 441 - 10, 10), (30, 1)):
+            assert G.plan_windows([(p, lm)], t_out, rf) == [_todays_window(p, lm, t_out, rf)]
+
+
+def test_planner_on_random_gap_sets():
+    from speech_inpainting_amd import gaps as G
+    rng = random.Random(5)
+    merged_some = False
+    for _ in range(400):
+        tm = rng.randint(60, 600)
+        t_out, rf = tm * 441 // 256, rng.choice((2, 7, 16))
+        cuts = sorted(rng.sample(range(tm + 1), 2 * rng.randint(1, 6)))
+        gaps = [(cuts[i], cuts[i + 1] - cuts[i]) for i in range(0, len(cuts), 2) if cuts[i + 1] > cuts[i]]
+        wins = G.plan_windows(gaps, t_out, rf)
+        merged_some |= len(wins) < len(gaps)
+        assert all(0 <= w0 < w1 <= t_out for w0, w1 in wins)
+        assert all(wins[i][1] < wins[i + 1][0] for i in range(len(wins) - 1))          # sorted, disjoint, not even touching
+        kept = [G.kept_region(w0, w1, t_out, rf) for w0, w1 in wins]
+        for p, l in gaps:
+            c0, c1 = G.stretched_range(p, l, t_out)
+            # stretched frames that read a changed mel frame lie in [c0, c1): two-tap lerp of extend_mel, src = (dst + .5) 256/441 - .5
+            touched = [d for d in range(t_out) if any(p <= s < p + l for s in _sources(d, tm))]
+            assert all(c0 <= d < c1 for d in touched)
+            lo, hi = max(c0 - rf, 0), min(c1 + rf, t_out)                              # everything within reach of a changed frame
+            assert any(k0 <= lo and hi <= k1 for k0, k1 in kept), (gaps, wins, (lo, hi))
+            # and a kept frame has its whole receptive field inside its window (or at a real clip edge)
+        for (w0, w1), (k0, k1) in zip(wins, kept):
+            assert (k0 - rf >= w0 or w0 == 0) and (k1 + rf <= w1 or w1 == t_out)
+    assert merged_some
+
+
+def _sources(d, tm):
+    src = max((d + 0.5) * 256.0 / 441.0 - 0.5, 0.0)
+    i0 = min(int(src), tm - 1)
+    return (i0, min(i0 + 1, tm - 1))
+
+
+# ------------------------------------------------------------------------------------------------------------ header
+def test_header_declares_the_span_entry_points_and_native_lists_them():
+    from speech_inpainting_amd import native
+    hdr = open(os.path.join(ROOT, "include", "si_hip.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    declared = set(re.findall(r"\b(si_[a-z_0-9]+)\s*\(", code))
+    new = {"si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
+           "si_codebook_metrics_spans"}
+    assert new <= declared and new <= set(native.EXPORTS)
+    assert "typedef struct si_span_table" in code and "struct_size" in code.split("typedef struct si_span_table")[1].split("}")[0]
+    assert "#define SI_ABI_VERSION 3" in code
+    # every new declaration carries a comment citing the reference lines it generalises
+    for name in new:
+        before = hdr[:hdr.index("int " + name + "(")]
+        assert "I_ea/" in before[before.rindex("/*"):], name
+    lib = os.path.join(ROOT, "speech_inpainting_amd", "libsi_hip.so")
+    if os.path.exists(lib):
+        import ctypes
+        so = ctypes.CDLL(lib)
+        assert all(hasattr(so, n) for n in new)
+        assert ctypes.sizeof(native.SpanTableStruct) == 16 + 6 * ctypes.sizeof(ctypes.c_void_p)
