@@ -464,7 +464,15 @@ int si_profile_stop(si_ctx* ctx, si_profile_entry* out, int capacity, int* count
  * Stored activated: the producer of an upsampler that runs in gemmcu.hip's TC kernels (profile family "gemmcu_f16_*":
  * N = u * Cout a multiple of 256, k = 2 u, unless SI_VOC_UPSGEMM=0) stores leaky_relu(x, 0.1) of its fp32 value instead of x.
  * That producer's tensor is "pre.f16" for upsampler 0 and "stage<i-1>.f16" (= the last "stage<i-1>.rb<j>.p<n>.f16") for upsampler i;
- * no other tap is activated, and with SI_VOC_UPSGEMM=0 none is. */
+ * no other tap is activated, and with SI_VOC_UPSGEMM=0 none is.
+ * Taps of the vocoder's fp32 residual stream (fp32, bf16x3, bf16, and fp16 with SI_VOC_RES16=0; of the last chunk of clips), next to
+ * "ups<i>" / "stage<i>": fp32 tensors, capacities in floats, under the same rule -- copies behind the producing launch, named and
+ * looked up only while some capture is registered, changing no launch and no value.  Ragged batches: rows past a clip's own end are stale.
+ *   pre                          conv_pre's output, (B, Tout, C0)
+ *   stage<i>.rb<j>.t<n>          the intermediate of pair n of resblock j: conv 1's output before conv 2's leaky-ReLU, (B, Lo, C_i).
+ *   stage<i>.rb<j>.t<n>.bf16     The operand-ready modes store it only as conv 2's 16-bit operand, type16(leaky_relu(t, 0.1)): the raw
+ *   stage<i>.rb<j>.t<n>.f16      tensor, 2 bytes per element (bf16 mode / fp16 mode with SI_VOC_RES16=0).  ResBlock2 has no intermediate.
+ *   stage<i>.rb<j>.p<n>          as its ".f16" namesake: the block's own stream for n < last, the running MRF sum for the last n */
 int si_debug_capture(si_ctx* ctx, const char* name, float* dst, long capacity);
 long si_debug_size(si_ctx* ctx, const char* name);
 

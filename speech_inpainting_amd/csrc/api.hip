@@ -1561,6 +1561,11 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
         auto tap16 = [&](const void* src, long n, const char* fmt, int a = 0, int b = 0, int c = 0) -> int {
             return (r16 && !ctx->dbg_capture.empty()) ? si_tap(ctx, st, {src, n, 2}, fmt, a, b, c) : SI_OK;
         };
+        // Their namesakes of the fp32 residual stream ("pre", "stage<i>.rb<j>.p<n>": n floats) and the pairs' intermediate
+        // ("stage<i>.rb<j>.t<n>", or the raw 16-bit tensor where only that exists): copies under the same rule.
+        auto tap32 = [&](TapSrc s, const char* fmt, int a = 0, int b = 0, int c = 0) -> int {
+            return (!r16 && !ctx->dbg_capture.empty()) ? si_tap(ctx, st, s, fmt, a, b, c) : SI_OK;
+        };
         // ragged batch: device / host rows of the chunk's clips -- dTm mel frames, dLs(s) rows at stage s (0 = stretched frames)
         const int32_t* dTm = vl ? tab.dev + b0 : nullptr;
         auto dLs = [&](int sidx) -> const int32_t* { return vl ? tab.dev + (size_t)(1 + sidx) * B + b0 : nullptr; };
@@ -1617,6 +1622,7 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
         if (r16) pre.out = nullptr;
         if ((rc = si_launch_tapgemm(ctx, Ly.pre.math, pre, st))) return rc;
         if ((rc = tap16(x16, (long)Bc * Tout * d.up_initial_channel, "pre.f16"))) return rc;
+        if ((rc = tap32({x, (long)Bc * Tout * d.up_initial_channel}, "pre"))) return rc;
         long Lc = Tout; int c = d.up_initial_channel;
         for (int i = 0; i < d.num_ups; ++i) {
             const GemmW& G = Ly.ups[i];
@@ -1718,10 +1724,13 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
                             p.x = y; p.out = t; p.pro_slope = in_slope;
                             if (opr) { p.x = nullptr; p.x16 = y16; p.out = nullptr; p.out16 = t16; p.out16_slope = 0.1f; }
                             if ((rc = si_launch_tapgemm(ctx, R.c1[n].math, p, st))) return rc;
+                            if ((rc = !opr ? tap32({t, nst}, "stage%d.rb%d.t%d", i, j, n)
+                                           : tap32({t16, nst, 2}, d.vocoder_math == SI_MATH_F16 ? "stage%d.rb%d.t%d.f16" : "stage%d.rb%d.t%d.bf16", i, j, n))) return rc;
                             if ((rc = residual_conv(R.c2[n], 1, opr ? 1.f : 0.1f, t, t16))) return rc;   // (the intermediate is stored activated in the 16-bit modes)
                         }
                     }
                     if ((rc = tap16(ynext16, nst, "stage%d.rb%d.p%d.f16", i, j, n))) return rc;
+                    if ((rc = tap32({ynext, nst}, "stage%d.rb%d.p%d", i, j, n))) return rc;
                     y = ynext;
                     y16 = ynext16;
                 }

@@ -62,7 +62,7 @@ def gelu_fast_err(z: torch.Tensor) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------------------------------------- GEMM / conv
-def linear_ref(a, w, b=None, res=None, act=None, round_w=True):
+def linear_ref(a, w, b=None, res=None, act=None, round_w=True, fp32_products=False):
     """out = epi(a W^T + b) [+ res] in float64, and a bound E on |fp32 out - ref| (before any bf16 rounding of the store).
 
     a (M, K): the kernel's operand as stored (bf16 values, or fp32 for the tap-GEMM's fp32-input path); w (N, K) fp32, rounded
@@ -72,6 +72,10 @@ def linear_ref(a, w, b=None, res=None, act=None, round_w=True):
     z = acc + b satisfies |fl(z) - z| <= gamma(K + 1) S (K products and the bias into one sum).  A residual adds one more
     term to the same sum: |out - ref| <= gamma(K + 2) (S + |res|).  With act = "gelu" the output is GELU(z): |GELU'| <= GELU_LIP
     carries the sum error, and the epilogue's own erf adds gelu_fast_err(z), so E = GELU_LIP gamma(K + 1) S + gelu_fast_err(z).
+
+    fp32_products (the tap-GEMM's exact-fp32 path, round_w=False: operands and weights are the fp32 values themselves): a
+    product of two fp32 values is not exact in fp32.  v_mfma_f32_32x32x2_f32 either rounds it before adding it (relative U) or
+    fuses it; the bound holds for both: U (1 + gamma) sum |a||w| on top of gamma on S, i.e. gamma -> gamma + U (1 + gamma).
     """
     a = a.double()
     wd = bf16(w) if round_w else w.double()
@@ -81,11 +85,31 @@ def linear_ref(a, w, b=None, res=None, act=None, round_w=True):
     if b is not None:
         z = z + b.double()
         S = S + b.double().abs()
+    g1, g2 = gamma(K + 1), gamma(K + 2)
+    if fp32_products:
+        g1, g2 = g1 + U * (1 + g1), g2 + U * (1 + g2)
     if act == "gelu":
-        return gelu(z), GELU_LIP * gamma(K + 1) * S + gelu_fast_err(z)
+        return gelu(z), GELU_LIP * g1 * S + gelu_fast_err(z)
     if res is not None:
-        return z + res.double(), gamma(K + 2) * (S + res.double().abs())
-    return z, gamma(K + 1) * S
+        return z + res.double(), g2 * (S + res.double().abs())
+    return z, g1 * S
+
+
+def layernorm_of_bounded(x, Ex, g, b, eps):
+    """LayerNorm of an fp32 row x~ known only as |x~ - x| <= Ex per element: (ref, E) with ref = LN(x) in float64 and E = the
+    kernel's own error on x~ (layernorm_ref's bound evaluated at x and scaled by 1 + 2 e / sigma: between x and x~ it changes by second-order terms U e only)
+    plus the passage of Ex through the normalisation.  With e = max_c Ex of the row: the mean moves by <= e, every x - mu by
+    <= 2 e, sigma = sqrt(var + eps) by <= e (the RMS of delta - mean(delta) is at most that of delta, and sqrt(. + eps) is
+    1-Lipschitz in the RMS); so z = (x - mu) / sigma moves by |dn sigma - n dsigma| / (sigma (sigma + dsigma)) <= (2 + |z|) e / (sigma - e),
+    times |g|."""
+    ref, E = layernorm_ref(x, g, b, eps)
+    x = x.double()
+    e = Ex.double().amax(-1, keepdim=True)
+    mu = x.mean(-1, keepdim=True)
+    sigma = torch.sqrt((x - mu).pow(2).mean(-1, keepdim=True) + eps)
+    z = (x - mu) / sigma
+    assert bool((sigma > 2 * e).all())
+    return ref, E * (1 + 2 * e / sigma) + g.double().abs() * (2 + z.abs()) * e / (sigma - e)
 
 
 def conv_rows(x, k, stride, rows):
@@ -182,6 +206,39 @@ def layernorm_ref(x, g, b, eps, act=None):
     if act == "gelu":
         return gelu(y), GELU_LIP * E + gelu_fast_err(y)
     return y, E
+
+
+def ln_linear_ref(x, ln_g, ln_b, eps, w, b):
+    """LayerNorm + Linear on the exact-fp32 tap-GEMM when the LayerNorm's rows are not stored apart (the head; the feature
+    projection): ref = LN(x) W^T + b in float64.  The LayerNorm's own bound Ey (layernorm_ref) passes through the Linear as
+    sum |w| Ey, and the Linear's bound (linear_ref, fp32_products) is taken at the operand magnitude |y| + Ey.  ln_g None: the
+    Linear alone."""
+    if ln_g is None:
+        return linear_ref(x, w, b, round_w=False, fp32_products=True)
+    y, Ey = layernorm_ref(x, ln_g, ln_b, eps)
+    ref, _ = linear_ref(y, w, b, round_w=False, fp32_products=True)
+    _, bound = linear_ref(y.abs() + Ey, w.abs(), b.abs(), round_w=False, fp32_products=True)
+    return ref, bound + Ey @ w.double().abs().t()
+
+
+def pos_conv_weight(sd, prefix="base_model.encoder.pos_conv_embed.conv."):
+    """The packer's fold of the positional conv (Packer::folded with norm_dim = 2: weight-norm over every dim but the taps'): squares
+    summed in double, the root rounded to fp32 once, w = v * (g / norm) in fp32.  -> (H, H / groups, k) fp32."""
+    if prefix + "weight" in sd:
+        return sd[prefix + "weight"].float()
+    new = prefix + "parametrizations.weight.original0" in sd
+    g = sd[prefix + ("parametrizations.weight.original0" if new else "weight_g")].float()
+    v = sd[prefix + ("parametrizations.weight.original1" if new else "weight_v")].float()
+    nrm = v.double().pow(2).sum(dim=(0, 1), keepdim=True).sqrt().float()
+    return v * (g.reshape(nrm.shape) / nrm)
+
+
+def pos_conv_geom(k, groups):
+    """The positional conv's geometry as a float64 contraction for vocoder_ref.tapgemm_ref: a (T, H), w (H, H / groups, k) -> (T, H);
+    zero padding k / 2 per side, the extra last row of an even kernel dropped (the launch computes M = T rows)."""
+    def f(a, w):
+        return F.conv1d(a.t()[None], w, padding=k // 2, groups=groups)[0].t()[:a.shape[0]]
+    return f
 
 
 # ----------------------------------------------------------------------------------------------------------- conv0 + GroupNorm

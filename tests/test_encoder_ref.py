@@ -1,6 +1,8 @@
 """The float64 references of tests/encoder_ref.py pinned on the CPU: with unrounded operands each reproduces the oracle's own
 function (ref_cpu.hubert_attention with key_mask, ref_cpu.hubert_ffn, the conv stack of ref_cpu.hubert_feature_extractor,
-F.layer_norm) in float64 to 1e-12 relative, and each bound helper rejects the first value outside its bound."""
+ref_cpu.hubert_pos_conv, F.layer_norm) in float64 to 1e-12 relative, and each bound helper rejects the first value outside its
+bound; the exact-fp32 tap-GEMM's references (fp32_products, the grouped positional conv, LayerNorm + Linear) hold for an fp32
+evaluation on the CPU and reject a zeroed last row, a shifted tap and a masked column written wrongly."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -155,3 +157,96 @@ def test_each_bound_rejects_the_first_value_outside_it(case):
     assert float(v - r) <= float(limit - r) + float(step(v)), name                 # one step of the output type past it
     g[i] = v[0]
     assert check(g.view_as(got), ref, bound)["bad"] == 1, name
+
+
+# ------------------------------------------------------------------------------- the exact-fp32 tap-GEMM (fp32 encoder)
+def test_pos_conv_reference_reproduces_the_oracle_and_rejects_mistakes(tiny):
+    """tapgemm_ref with the grouped geometry, GELU and the residual is h + ref_cpu.hubert_pos_conv(h) in float64; in "f32" an fp32
+    evaluation lies inside the bound, a tap shifted by one row and a zeroed last row outside; through the encoder's LayerNorm
+    (layernorm_of_bounded) likewise."""
+    from tests import vocoder_ref as V
+    harch, sd = tiny
+    H, G, k = harch.hidden_size, harch.num_conv_pos_embedding_groups, harch.num_conv_pos_embeddings
+    p = "base_model.encoder.pos_conv_embed.conv."
+    geom = E.pos_conv_geom(k, G)
+    for T in (1, 37):
+        h = torch.randn(T, H)
+        want = h.double() + R.hubert_pos_conv(_sd64(sd), harch, "base_model.", h.double()[None])[0]
+        w64 = R._conv_weight(_sd64(sd), p[:-1], dim=2)
+        got = V.tapgemm_ref(h, w64, sd[p + "bias"], "f64", geom, k * H // G, act="gelu", res=h)
+        assert _rel(got.ref, want) <= 1e-12
+        w = E.pos_conv_weight(sd)
+        assert _rel(w.double(), w64) <= 1e-6
+        r = V.tapgemm_ref(h, w, sd[p + "bias"], "f32", geom, k * H // G, act="gelu", res=h)
+        assert bool((r.E > 0).all()) and float(r.E.max()) < 1e-2 * float(r.ref.abs().max())      # a bound, not a blanket
+
+        def fp32(hh):
+            y = F.conv1d(hh.t()[None], w, sd[p + "bias"], padding=k // 2, groups=G)[0].t()[:T]
+            return hh + F.gelu(y)
+
+        good = fp32(h)
+        assert V.check_f32(good, r.ref, r.E)["bad"] == 0
+        if T > 1:
+            shifted = h + (fp32(torch.cat([h[1:], torch.zeros(1, H)])) - torch.cat([h[1:], torch.zeros(1, H)]))
+            assert V.check_f32(shifted, r.ref, r.E)["bad"] > 0
+            z = good.clone()
+            z[T - 1] = 0
+            assert V.check_f32(z, r.ref, r.E)["bad"] > 0
+            g_, b_ = sd["base_model.encoder.layer_norm.weight"], sd["base_model.encoder.layer_norm.bias"]
+            ref, bound = E.layernorm_of_bounded(r.ref, r.E, g_, b_, 1e-5)
+            assert float(bound.max()) < 1e-2 * float(ref.abs().max())
+            ln = F.layer_norm(good, (H,), g_, b_, 1e-5)
+            assert E.check_f32(ln, ref, bound)["bad"] == 0
+            assert E.check_f32(F.layer_norm(shifted, (H,), g_, b_, 1e-5), ref, bound)["bad"] > 0
+            # the passage term is needed: the worst-case input inside the conv's bound leaves the LayerNorm's own bound
+            own = E.layernorm_ref(r.ref, g_, b_, 1e-5)[1]
+            moved = F.layer_norm(r.ref + r.E * torch.sign(torch.randn(T, H, dtype=torch.float64)), (H,), g_.double(), b_.double(), 1e-5)
+            assert E.check_f32(moved, ref, bound)["bad"] == 0 and E.check_f32(moved, ref, own)["bad"] > 0
+
+
+def test_ln_linear_reference_and_the_masked_columns():
+    """LayerNorm + Linear(-> 80): F.layer_norm + F.linear in float64 to 1e-12; an fp32 evaluation inside the bound; a last row zeroed, a
+    column of the partial tile (64 .. 79) left unwritten and a weight row taken from the padding (80: zeros, so the bias alone) outside."""
+    torch.manual_seed(3)
+    H, N, M = 256, 80, 129
+    x = torch.randn(M, H) * 2 + 0.3
+    g, b = torch.randn(H) * 0.1 + 1, torch.randn(H) * 0.1
+    w, bias = torch.randn(N, H) / 16, torch.randn(N) * 0.1
+    ref, bound = E.ln_linear_ref(x, g, b, 1e-5, w, bias)
+    want = F.linear(F.layer_norm(x.double(), (H,), g.double(), b.double(), 1e-5), w.double(), bias.double())
+    assert _rel(ref, want) <= 1e-12 and float(bound.max()) < 1e-2 * float(ref.abs().max())
+    good = F.linear(F.layer_norm(x, (H,), g, b, 1e-5), w, bias)
+    assert E.check_f32(good, ref, bound)["bad"] == 0
+    for mutate in (lambda t: t[M - 1].zero_(), lambda t: t[:, 79].zero_(), lambda t: t[:, 64].copy_(bias[64].expand(M))):
+        bad = good.clone()
+        mutate(bad)
+        assert E.check_f32(bad, ref, bound)["bad"] > 0
+    lin, lb = E.ln_linear_ref(x, None, None, 0.0, w, bias)
+    plain, pb = E.linear_ref(x, w, bias, round_w=False)
+    assert torch.equal(lin, plain) and bool((lb > pb).all()) and bool((lb <= pb * (1 + 2.0 ** -8)).all())   # one U per product on K + 1 >= 257 terms' gamma
+    assert E.check_f32(F.linear(x, w, bias), lin, lb)["bad"] == 0
+
+
+def test_pos_conv_bound_at_the_real_width_rejects_a_dropped_halo_row():
+    """HuBERT-base's positional conv (K = 128 x 48 = 6144 products: the worst-case bound is some per cent of the output) still separates
+    a correct fp32 evaluation (far inside) from a tile that reads the last row of the tile before it as zero (the first row of a
+    second 128-row tile, T = 129)."""
+    from tests import vocoder_ref as V
+    harch = HubertArch(num_hidden_layers=1)
+    sd = synth.synth_hubert_state(harch, 31)
+    H, G, k, T = harch.hidden_size, harch.num_conv_pos_embedding_groups, harch.num_conv_pos_embeddings, 129
+    w, bias = E.pos_conv_weight(sd), sd["base_model.encoder.pos_conv_embed.conv.bias"]
+    h = torch.randn(T, H, generator=torch.Generator().manual_seed(2)) * 0.5
+    r = V.tapgemm_ref(h, w, bias, "f32", E.pos_conv_geom(k, G), k * H // G, act="gelu", res=h)
+
+    def fp32(x):
+        return h + F.gelu(F.conv1d(x.t()[None], w, bias, padding=k // 2, groups=G)[0].t()[:T])
+
+    good = fp32(h)
+    assert float(V.check_f32(good, r.ref, r.E)["ratio"].max()) < 1e-2
+    h2 = h.clone()
+    h2[127] = 0
+    bad = good.clone()
+    bad[128] = fp32(h2)[128]
+    c = V.check_f32(bad, r.ref, r.E)
+    assert c["bad"] > 0 and float(c["ratio"].max()) > 3

@@ -237,3 +237,174 @@ def test_seam_distance_and_report():
     got[4, 1] = 3.0
     line, near, rest = V.report("op", "kern", 1, V.check_f16(got, ref, E), 10, 4, 0)
     assert "FAILED" in line and "row 4, channel 1, 0 rows from a tile seam, 4 from the clip edge, err/E 3.000" in line and near == 3.0 and rest == 0.0
+
+
+# ------------------------------------------------------------------------------- the tap-GEMM on an fp32 activation stream
+def _generator_by_tapgemm_ref(sd, arch, mel, math="f64"):
+    """The ResBlock1 generator of one clip composed from tapgemm_ref the way api.hip's forward launches it (conv_pre, the upsampler
+    as a transposed conv, conv 1, conv 2 with residual / alpha / accumulate): mel (80, Tm) -> {name: (L, C)}."""
+    sd64 = {k: _F64(v) for k, v in sd.items()}
+    f = (lambda n: R._conv_weight(sd64, n)) if math == "f64" else (lambda n: V.fold(sd, n, round16=False).float())      # noqa: E731
+    nk = len(arch.resblock_kernel_sizes)
+    alpha = 1.0 / nk if math == "f64" else V.alpha32(nk)
+    slope = 0.1 if math == "f64" else V.SLOPE32
+    cast = (lambda t: t) if math == "f64" else (lambda t: t.float())                                                    # noqa: E731
+    taps = {}
+    w = f("conv_pre")
+    x = cast(V.tapgemm_ref(mel.t(), w, sd["conv_pre.bias"], math, V.conv_geom(1), 7 * 80).ref)
+    taps["pre"] = x
+    for i, (u, k) in enumerate(zip(arch.upsample_rates, arch.upsample_kernel_sizes)):
+        w = f(f"ups.{i}")
+        x = cast(V.tapgemm_ref(x, w, sd[f"ups.{i}.bias"], math, V.tconv_geom(u), -(-k // u) * w.shape[0], slope=slope).ref)
+        taps[f"ups{i}"] = x
+        xs = None
+        for j, (rk, dil) in enumerate(zip(arch.resblock_kernel_sizes, arch.resblock_dilation_sizes)):
+            r = f"resblocks.{i * nk + j}."
+            y = x
+            for n, d in enumerate(dil):
+                last = n == len(dil) - 1
+                K = rk * y.shape[1]
+                t = cast(V.tapgemm_ref(y, f(f"{r}convs1.{n}"), sd[f"{r}convs1.{n}.bias"], math, V.conv_geom(d), K, slope=slope).ref)
+                y = cast(V.tapgemm_ref(t, f(f"{r}convs2.{n}"), sd[f"{r}convs2.{n}.bias"], math, V.conv_geom(1), K, slope=slope, res=y,
+                                       alpha=alpha if last else 1.0, prev=xs if (last and j > 0) else None).ref)
+            xs = y
+        x = xs
+        taps[f"stage{i}"] = x
+    return taps
+
+
+@pytest.mark.parametrize("name", ["v1", "u1"])
+def test_tapgemm_ref_reproduces_the_oracle_generator(name):
+    """math = "f64" (nothing rounded) is the oracle's generator to 1e-12; the three arithmetics stay within their modes' distance of it."""
+    arch = ARCHS[name]
+    sd = synth.synth_generator_state(arch)
+    mel = synth.synth_mel(2, 11, 80, 5)
+    want = {}
+    R.generator_forward({k: _F64(v) for k, v in sd.items()}, arch, _F64(mel), want)
+    for b in range(2):
+        taps = _generator_by_tapgemm_ref(sd, arch, mel[b])
+        for nm in want:
+            assert _rel(taps[nm], want[nm][b].t()) <= 1e-12, (name, nm)
+    for math, tol in (("f32", 1e-5), ("bf16x3", 1e-4), ("bf16", 5e-2)):
+        taps = _generator_by_tapgemm_ref(sd, arch, mel[0], math)
+        for nm in want:
+            assert _rel(taps[nm].double(), want[nm][0].t()) <= tol, (name, math, nm)
+
+
+def _h_f2bf(v):
+    """Packer's h_f2bf restated on the bit patterns: u += 0x7FFF + ((u >> 16) & 1); u >> 16 (finite inputs)."""
+    u = v.float().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    u = u + 0x7FFF + ((u >> 16) & 1)
+    return (u >> 16) << 16
+
+
+def test_bf16_split_is_the_packers_and_the_kernels():
+    """bf16r is h_f2bf (api.hip) on random values and on exact ties; split_bf16's lo plane is h_f2bf(v - bf2f(hi)); hi + lo leaves
+    |r| <= 2^-16 |v| and |lo| <= 2^-8 (1 + 2^-8) |v| (two roundings to 8 significant bits), the figures E_exact's closed form rests on."""
+    g = torch.Generator().manual_seed(3)
+    v = torch.cat([torch.randn(20000, generator=g) * 3, torch.randn(2000, generator=g) * 1e-4,
+                   torch.tensor([1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, -1.0 - 2.0 ** -8, 2.0 ** -20 * (1 + 2.0 ** -8), 0.0])])
+    bits = _h_f2bf(v)
+    want = (bits & 0xFFFFFFFF).to(torch.int64)
+    got = V.bf16r(v).view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    assert torch.equal(got, want)
+    assert V.bf16r(torch.tensor([1.0 + 2.0 ** -8])).item() == 1.0 and V.bf16r(torch.tensor([1.0 + 3 * 2.0 ** -8])).item() == 1.0 + 2.0 ** -6
+    hi, lo = V.split_bf16(v)
+    assert torch.equal(hi, V.bf16r(v).double())
+    rem32 = v - V.bf16r(v)
+    assert torch.equal(rem32.double(), v.double() - hi), "the fp32 subtraction v - hi is exact"
+    assert torch.equal((_h_f2bf(rem32) & 0xFFFFFFFF), lo.float().view(torch.int32).to(torch.int64) & 0xFFFFFFFF)
+    r = v.double() - hi - lo
+    assert bool((lo.abs() <= 2.0 ** -8 * (1 + 2.0 ** -8) * v.double().abs()).all()) and bool((r.abs() <= 2.0 ** -16 * v.double().abs()).all())
+
+
+def _tg_case(C, k, dil, L, seed, Cout=None):
+    g = torch.Generator().manual_seed(seed)
+    Cout = Cout or C
+    x = torch.randn(L, C, generator=g)
+    w = torch.randn(Cout, C, k, generator=g) / (C * k) ** 0.5
+    b = torch.randn(Cout, generator=g) * 0.05
+    res = torch.randn(L, Cout, generator=g)
+    prev = torch.randn(L, Cout, generator=g)
+    return x, w, b, res, prev
+
+
+def _emulate(x, w, b, math, contract, slope=1.0, res=None, alpha=1.0, prev=None, drop=(), slope_after=False):
+    """What a kernel would store, with its accumulation done in float32 on the CPU (a different order from any MFMA's, within the
+    same gamma): the operand planes as fp32 tensors, contracted in fp32, summed lo-terms first, the epilogue in fp32 in the kernel's
+    order.  drop / slope_after: the mistakes."""
+    v = V.lrelu32(x, slope)
+    wf = w.float()
+    if math == "f32":
+        planes = [("v*w", v, wf)]
+    elif math == "bf16":
+        a = V.bf16r(V.lrelu32(V.bf16r(x), slope)) if slope_after else V.bf16r(v)
+        planes = [("hi*hi", a, V.bf16r(wf))]
+    else:
+        vh, wh = V.bf16r(v), V.bf16r(wf)
+        planes = [("lo*hi", V.bf16r(v - vh), wh), ("hi*lo", vh, V.bf16r(wf - wh)), ("hi*hi", vh, wh)]
+    acc = None
+    for nm, a, ww in planes:
+        if nm in drop:
+            continue
+        t = contract(a, ww)
+        assert t.dtype == torch.float32
+        acc = t if acc is None else acc + t
+    out = acc + b.float()
+    if res is not None:
+        out = out + res.float()
+    out = out * torch.tensor(alpha, dtype=torch.float32)
+    if prev is not None:
+        out = out + prev.float()
+    return out
+
+
+MATHS = ("f32", "bf16x3", "bf16")
+
+
+@pytest.mark.parametrize("math", MATHS)
+@pytest.mark.parametrize("C,k,dil", [(32, 3, 1), (64, 7, 3), (32, 11, 5)])
+def test_tapgemm_bounds_hold_for_an_fp32_evaluation_and_reject_every_listed_mistake(math, C, k, dil):
+    """An honest fp32 evaluation of the same operation lies inside E (and, for bf16x3, inside E_exact of the fp32 product); each
+    mistake the bounds exist for lands outside on at least one element: a dropped bf16x3 cross term, a tap shifted by one row,
+    a dilation off by one, the slope applied after the bf16 rounding, alpha omitted, the last valid row of a 128-row tile zeroed."""
+    L = 150
+    x, w, b, res, prev = _tg_case(C, k, dil, L, 11 + C + k)
+    a3 = V.alpha32(3)
+    geom = V.conv_geom(dil)
+    kw = dict(slope=V.SLOPE32, res=res, alpha=a3, prev=prev)
+    r = V.tapgemm_ref(x, w, b, math, geom, k * C, **kw)
+    assert bool((r.E > 0).all()) and float(r.E.max()) < 1e-3 * float(r.ref.abs().max())            # a bound, not a blanket
+
+    def bad(got, exact=False):
+        return V.check_f32(got, r.exact if exact else r.ref, r.E_exact if exact else r.E)["bad"]
+
+    good = _emulate(x, w, b, math, geom, **kw)
+    assert bad(good) == 0
+    assert bad(r.ref.float()) == 0
+    if math != "bf16":
+        assert bad(good, exact=True) == 0
+    if math == "bf16x3":
+        # the split's distance to the fp32 product is inside its computed part of E_exact, and that part is small: <= 3.1 * 2^-16 S
+        S = V.conv_geom(dil)(V.lrelu32(x, V.SLOPE32).double().abs(), w.double().abs())
+        assert bool(((r.ref - r.exact).abs() <= r.E_exact - r.E + 1e-18).all())
+        assert bool((r.E_exact - r.E <= a3 * 3.1 * 2.0 ** -16 * S * (1 + 1e-6)).all())
+        for term in ("lo*hi", "hi*lo"):
+            assert bad(_emulate(x, w, b, math, geom, drop=(term,), **kw)) > 0, term
+            assert bad(V.tapgemm_ref(x, w, b, math, geom, k * C, drop=(term,), **kw).ref.float()) > 0, term
+    assert bad(_emulate(x, w, b, math, V.conv_geom(dil, shift=1), **kw)) > 0
+    assert bad(_emulate(x, w, b, math, V.conv_geom(dil + 1), **kw)) > 0
+    assert bad(_emulate(x, w, b, math, geom, slope=V.SLOPE32, res=res, alpha=1.0, prev=prev)) > 0
+    zeroed = good.clone()
+    zeroed[127] = 0.0
+    assert bad(zeroed) > 0
+    if math == "bf16":
+        assert bad(_emulate(x, w, b, math, geom, slope_after=True, **kw)) > 0
+    # the same layer as a transposed convolution (u = 2, k = 4; two taps per phase): honest inside, a shifted phase outside
+    g = torch.Generator().manual_seed(5)
+    wt = torch.randn(C, C // 2, 4, generator=g) / (2 * C) ** 0.5
+    bt = torch.randn(C // 2, generator=g) * 0.05
+    rt = V.tapgemm_ref(x, wt, bt, math, V.tconv_geom(2), 2 * C, slope=V.SLOPE32)
+    up = _emulate(x, wt, bt, math, V.tconv_geom(2), slope=V.SLOPE32)
+    assert up.shape == (2 * L, C // 2) and V.check_f32(up, rt.ref, rt.E)["bad"] == 0
+    assert V.check_f32(torch.roll(up, 1, 0), rt.ref, rt.E)["bad"] > 0

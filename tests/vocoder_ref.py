@@ -5,7 +5,8 @@ Every reference takes the kernel's OWN operands: the fp16 tensor the previous ke
 of include/si_hip.h), the weights folded as the packer folds them (`fold`: v * (g / norm) in fp32, torch._weight_norm's order)
 and rounded once to fp16 (`h16`), the biases in fp32.  It returns (ref, E): the exact result in float64 and a bound on
 |stored fp16 value - ref| per element, derived in the docstring from the kernel's arithmetic and fitted to no measurement.
-Tensors are channels-last, one clip at a time: (rows, channels).
+Tensors are channels-last, one clip at a time: (rows, channels).  The last section (`tapgemm_ref`) does the same for the tap-GEMM on an
+fp32 activation stream -- the fp32, bf16x3 and bf16 vocoders and the fp32 encoder's convolutions -- with fp32 outputs.
 
 The staged operand.  Every kernel of the stream applies its leaky-ReLU to the packed fp16 halves while staging, so the product
 with the slope ROUNDS TO fp16 and the slope is the fp16 constant (fp16(0.1) = 0.0999755859375, fp16(0.01) = 0.0100021362...):
@@ -28,6 +29,7 @@ rounds: either way the stored value is rne_f16(clamp(v, +-65504)) of the fp32 v.
 stored value must be exactly +-65504; where |ref| + E < 65504 the ordinary bound holds; in between either is accepted.  The
 ResBlock intermediate t saturates the same way; the references clamp it (a clamp is 1-Lipschitz: the bound on t is unchanged).
 """
+import collections
 import math
 
 import numpy as np
@@ -256,6 +258,136 @@ def conv_post_ref(x, w, b, mfma, round_w=True, slope=SLOPE_POST32):
     Es = _conv(da, wd.abs()) + gamma(K + 1) * S
     ref = torch.tanh(z)
     return ref[:, 0], (Es + TANH_ULPS * 2.0 ** -23 * ref.abs() + 2.0 ** -149)[:, 0]
+
+
+# ------------------------------------------------------------------------------- the tap-GEMM on an fp32 activation stream
+# (tapgemm.hip with fp32 inputs: the whole fp32 and bf16x3 vocoder, the bf16 vocoder without operand-ready activations, the
+# fp32 encoder's Linear layers and convolutions)
+FTZ = 2.0 ** -126                               # the smallest normal fp32: what one flushed product or partial sum can lose
+
+
+def bf16r(x: torch.Tensor) -> torch.Tensor:
+    """fp32 -> bf16 (round to nearest, ties to even: v_cvt_pk_bf16_f32 and the packer's h_f2bf) -> fp32."""
+    return x.float().to(torch.bfloat16).float()
+
+
+def lrelu32(x: torch.Tensor, slope: float) -> torch.Tensor:
+    """tapgemm.hip:215, bit-exact: v > 0 ? v : v * slope with the fp32 slope, one fp32 rounding of the product.  slope = 1: x."""
+    x = x.float()
+    return x if slope == 1.0 else torch.where(x > 0, x, x * torch.tensor(slope, dtype=torch.float32))
+
+
+def split_bf16(v: torch.Tensor):
+    """The bf16x3 split of an fp32 tensor, bit-exact: hi = bf16(v), lo = bf16(v - hi), the subtraction in fp32 (it is exact: hi
+    shares v's leading bits).  Activations: tapgemm.hip:225-229; weights: Packer::put in api.hip -- `hi = h_f2bf(v)` into the w
+    plane, `h_f2bf(v - h_bf2f(hi))` into the w_lo plane, h_f2bf being round to nearest, ties to even.  -> (hi, lo) as float64."""
+    v = v.float()
+    hi = bf16r(v)
+    lo = bf16r(v - hi)
+    return hi.double(), lo.double()
+
+
+TapRef = collections.namedtuple("TapRef", "ref E exact E_exact")
+
+
+def tapgemm_ref(x, w, b, math, contract, K, slope=1.0, act=None, res=None, alpha=1.0, prev=None, drop=()):
+    """One tap-GEMM launch with an fp32 output, on the kernel's own fp32 input:
+        out = ((act(sum_K pro(x) w + b) + res) * alpha) + prev,    pro(x) = lrelu32(x, slope) staged in the arithmetic `math`.
+    x: the fp32 tensor the kernel read; w: the fp32 (folded) weight the packer was given; b fp32 or None; contract(a, w) the
+    layer's geometry as a float64 function, linear in both arguments (`conv_geom`, `tconv_geom`, a matmul, a grouped conv), applied to
+    operand planes and to their magnitudes; K products per output; res / prev fp32 tensors of the output's shape (residual,
+    accumulate); alpha the fp32 scale.  -> TapRef(ref, E, exact, E_exact).
+
+    The operand planes the MFMAs multiply (everything before them is emulated bit-exactly, the bounds start behind it):
+      "f32"     v = lrelu32(x) and w themselves.  v_mfma_f32_32x32x2_f32 either rounds each product to fp32 before adding it
+                (relative U) or fuses it; the accumulation of K products and the bias add (epilogue: acc + bias, one rounding) are K + 1
+                fp32 additions in whatever order: |z~ - z| <= gamma(K + 1) S + U (1 + gamma(K + 1)) S, S = sum |v||w| + |b|.
+      "bf16"    bf16(v) (the slope applied in fp32 BEFORE the rounding, tapgemm.hip:215 then :225) and bf16(w), rounded once.
+                Products of two bf16 values are exact in fp32: |z~ - z| <= gamma(K + 1) S.
+      "bf16x3"  (v_hi, v_lo), (w_hi, w_lo) of `split_bf16`; the kernel sums v_lo w_hi + v_hi w_lo + v_hi w_hi per K step, each
+                product exact: ref is THAT sum in float64 and |z~ - z| <= gamma(3 K + 1) S, S = the sum of the three
+                magnitude contractions + |b|.  `exact` is the contraction of the fp32 v and w themselves; with v = v_hi + v_lo + r_v,
+                w = w_hi + w_lo + r_w:   v w - (three terms) = v_lo w_lo + r_v w + (v_hi + v_lo) r_w, so
+                E_exact = E + epilogue-scaled sum (|v_lo||w_lo| + |r_v||w| + |v_hi + v_lo||r_w|), all computed, nothing
+                estimated (bf16 keeps 8 significant bits: |v_lo| <= 2^-8 (1 + 2^-8) |v|, |r_v| <= 2^-16 |v|, likewise for w, so the sum is
+                <= 3.1 * 2^-16 sum |v||w| in the worst case of every rounding at half an ulp: what the "fp32-equivalent" claim amounts to).
+      "f64"     lrelu(x, slope) and w in float64, E = 0: the operation itself, for pinning the references to the oracle.
+    Each term may also lose FTZ to a flushed subnormal: + (terms + 1) FTZ.
+    Epilogue (tapgemm.hip:598-602, fp32 VALU, relative U each): act = "gelu": |GELU'| <= GELU_LIP carries the sum error and erff
+    adds gelu_fast_err; then with n of {+ res, * alpha (alpha != 1), + prev} present and A = alpha (|z| + Ez + |res|) + |prev|:
+    E = alpha Ez + gamma(n, U) A.  A fused multiply-add of the compiler's has fewer roundings.
+    drop: names of product planes left out ("lo*hi", "hi*lo", "hi*hi") -- the CPU self-tests' emulation of a kernel that forgets one."""
+    from tests.encoder_ref import GELU_LIP, gelu, gelu_fast_err
+    wf = w.float()
+    if math == "f64":
+        planes, coef, terms = [("v*w", lrelu(x.double(), slope), w.double())], 0.0, 0
+    else:
+        v = lrelu32(x, slope)
+        if math == "f32":
+            planes = [("v*w", v.double(), wf.double())]
+            coef, terms = gamma(K + 1) + U * (1 + gamma(K + 1)), K
+        elif math == "bf16":
+            planes = [("hi*hi", bf16r(v).double(), bf16r(wf).double())]
+            coef, terms = gamma(K + 1), K
+        elif math == "bf16x3":
+            (vh, vl), (wh, wl) = split_bf16(v), split_bf16(wf)
+            planes = [("lo*hi", vl, wh), ("hi*lo", vh, wl), ("hi*hi", vh, wh)]
+            coef, terms = gamma(3 * K + 1), 3 * K
+        else:
+            raise ValueError(math)
+    planes = [p for p in planes if p[0] not in drop]
+    z = sum(contract(a, ww) for _, a, ww in planes)
+    S = sum(contract(a.abs(), ww.abs()) for _, a, ww in planes)
+    if b is not None:
+        z = z + b.double()
+        S = S + b.double().abs()
+    Ez = coef * S + (terms + 1) * FTZ if math != "f64" else torch.zeros_like(z)
+    zx = Dx = None
+    if math == "bf16x3":
+        vd, wd = v.double(), wf.double()
+        zx = contract(vd, wd) + (b.double() if b is not None else 0.0)
+        Dx = contract(vl.abs(), wl.abs()) + contract((vd - vh - vl).abs(), wd.abs()) + contract((vh + vl).abs(), (wd - wh - wl).abs())
+
+    def epilogue(z, Ez):
+        if act == "gelu":
+            Ez = GELU_LIP * Ez + (gelu_fast_err(z) if math != "f64" else 0.0)
+            z = gelu(z)
+        elif act is not None:
+            raise ValueError(act)
+        n = (res is not None) + (alpha != 1.0) + (prev is not None)
+        A = z.abs() + Ez
+        if res is not None:
+            z = z + res.double()
+            A = A + res.double().abs()
+        z, A, Ez = z * alpha, A * abs(alpha), Ez * abs(alpha)
+        if prev is not None:
+            z = z + prev.double()
+            A = A + prev.double().abs()
+        return z, (Ez + gamma(n, U) * A if (n and math != "f64") else Ez)
+
+    ref, E = epilogue(z, Ez)
+    if zx is None:
+        return TapRef(ref, E, ref if math != "bf16" else None, E if math != "bf16" else None)
+    exact, Ex = epilogue(zx, Ez + Dx)
+    return TapRef(ref, E, exact, Ex)
+
+
+def conv_geom(dil=1, shift=0):
+    """The same-length convolution of `_conv` (zero padding dil (k - 1) / 2 per side) as a contract(a (L, Cin), w (Cout, Cin, k)).
+    shift: every tap reads `shift` rows further down (the self-tests' shifted-tap mistake; 0 is the layer)."""
+    def f(a, w):
+        if shift:
+            a = torch.cat([a[shift:], a.new_zeros(shift, a.shape[1])])
+        return _conv(a, w, dil)
+    return f
+
+
+def tconv_geom(u):
+    """ConvTranspose1d(k, stride u, padding (k - u) / 2) as a contract(a (Lin, Cin), w (Cin, Cout, k)) -> (u Lin, Cout): the sum the
+    kernel forms as u phases of a ceil(k / u)-tap convolution with dil = -1 (see `upsample_ref`); K = ceil(k / u) Cin."""
+    def f(a, w):
+        return F.conv_transpose1d(a.t()[None], w, stride=u, padding=(w.shape[2] - u) // 2)[0].t()
+    return f
 
 
 # ----------------------------------------------------------------------------------------------------------- checking
