@@ -18,7 +18,8 @@ against linear_ref(round_w=False, fp32_products=True); the grouped positional co
 48; N = 48 in Npad = 64) from "projected" to "encoder_in"; the head's LayerNorm + Linear(-> 80), two 64-column tiles of a weight padded to
 Npad = 128 whose second tile masks 48 columns, from "last_hidden" to what encode returns; uniform and ragged with a single-frame clip.
 
-(conv_pre's packed K is the mel width rounded up to 32 -- 96 channels, BK = 32 -- so BK = 16 is reached by the base positional conv only.)
+(conv_pre's packed K is the input width rounded up to 32 -- 96 channels for 80 mels, BK = 32 -- so in this file BK = 16 is reached by the base
+positional conv only; tests/test_gpu_unitvoc_ops.py runs a 16-channel stage, an ungrouped conv at BK = 16, through the same helpers.)
 
 What the bounds can see.  They are worst-case bounds of K fp32 additions, linear in K, while the error of a correct kernel grows like
 sqrt(K): measured on MI355X (RECORD; max err / E over rows within the taps' reach of a tile seam or clip edge | the rest) the kernels sit
@@ -59,7 +60,8 @@ RECORD = {
 
 def _config(math, N, M, ntaps, dil, Cin, stride=1):
     """launch_math (tapgemm.hip) for fp32 inputs (x16 == nullptr) -> (profile name, BM).  MaxA<256, 512> = 6 and MaxA<256> = 12 float4 per
-    thread: both caps are 3072 float4, i.e. 384 rows of 32 channels."""
+    thread: both caps are 3072 float4, i.e. 384 rows of 32 channels.  N = 16 (a 32-column tile, Npad = 32) and Cin = 16 (BK = 16: a quarter of
+    the float4 per row, so the 256-row tile's halo always fits) need no case of their own: tests/test_gpu_unitvoc_ops.py asserts these names there."""
     bk = 32 if Cin % 32 == 0 else 16
     bn = 128 if N >= 128 else 64 if N > 32 else 32
     rows256 = 255 * stride + (ntaps - 1) * abs(dil) + 1
@@ -69,6 +71,10 @@ def _config(math, N, M, ntaps, dil, Cin, stride=1):
         return (f"tapgemm_{math}_256x128w8", 256) if tall else (f"tapgemm_{math}_128x128", 128)
     tall = rows256 * (bk // 4) <= cap and M > 128
     return (f"tapgemm_{math}_256x{bn}", 256) if tall else (f"tapgemm_{math}_128x{bn}", 128)
+
+
+def _mel_ld(num_mels):
+    return -(-num_mels // 32) * 32
 
 
 _ENGINES = {}
@@ -156,8 +162,9 @@ def _one(tag, kernel, clip, got, r, stored, halo):
     _note(kernel, near, rest)
 
 
-def _verify(varch, mode, mel, lens, taps, prof, tag, clips=None):
-    """Every tap of every clip against its reference from the tapped input; -> the configurations the launches must have taken."""
+def _verify(varch, mode, mel, lens, taps, prof, tag, clips=None, wave=None):
+    """Every tap of every clip against its reference from the tapped input; -> the configurations the launches must have taken.
+    wave: the samples, to check conv_post_kernel (fp32 rows, the slope in fp32) against conv_post_ref(mfma=False) on the last stage's tap."""
     math = MODES[mode][1]
     sd = _state(varch)
     B, _, Tm = mel.shape
@@ -168,11 +175,12 @@ def _verify(varch, mode, mel, lens, taps, prof, tag, clips=None):
     for b in (range(B) if clips is None else clips):
         L = int(lens[b]) if lens is not None else Tm
         C0 = varch.upsample_initial_channel
-        kern, bm = _config(math, C0, Lmax, 7, 1, 96)
+        nm = varch.num_mels
+        kern, bm = _config(math, C0, Lmax, 7, 1, _mel_ld(nm))              # (conv_pre's packed K: the input width rounded up to 32, api.hip's mel_ld)
         want.add(kern)
-        r = V.tapgemm_ref(mel[b, :, :L].t(), _w(varch, "conv_pre"), sd["conv_pre.bias"], math, V.conv_geom(1), 7 * 80)
+        r = V.tapgemm_ref(mel[b, :, :L].t(), _w(varch, "conv_pre"), sd["conv_pre.bias"], math, V.conv_geom(1), 7 * nm)
         x = taps["pre"][b, :L]
-        _one(f"{tag} conv_pre 80->{C0}", kern, b, x, r, bm, 6)
+        _one(f"{tag} conv_pre {nm}->{C0}", kern, b, x, r, bm, 6)
         C, Lm = C0, Lmax
         for i, (u, k) in enumerate(zip(varch.upsample_rates, varch.upsample_kernel_sizes)):
             w = _w(varch, f"ups.{i}")
@@ -205,26 +213,34 @@ def _verify(varch, mode, mel, lens, taps, prof, tag, clips=None):
                 xs_prev = xin
             assert torch.equal(taps[f"stage{i}"][b, :L], xs_prev), f"{tag} stage{i} is not the last resblock's running sum"
             x = xs_prev
+        if wave is not None:
+            ref, Eb = V.conv_post_ref(x, _w(varch, "conv_post"), sd["conv_post.bias"], mfma=False)
+            c = V.check_f32(wave[b, :L], ref, Eb)
+            line, near, rest = V.report(f"{tag} conv_post C={C}", "conv_post", b, c, L, 256, 3)
+            print("   " + line)
+            assert "conv_post" in prof and c["finite"] and c["bad"] == 0, line
+            assert not bool(wave[b, L:].any()), f"{tag}: samples past clip {b}'s end are not silence"
+            _note(f"conv_post_kernel C={C}", near, rest)
     got = {n for n in prof if n.startswith("tapgemm_")}
     assert got == want, f"{tag}: the launches took {sorted(got)}, launch_math restated gives {sorted(want)}"
     return want
 
 
-def _uniform(varch, mode, L, seed, tag):
-    one = _mel(1, L, seed)
+def _uniform(varch, mode, L, seed, tag, post=False):
+    one = _mel(1, L, seed, varch.num_mels)
     mel = torch.cat([one, one]).contiguous()
     taps, wave, prof = _run(_engine(varch, mode), varch, mel)
-    cfgs = _verify(varch, mode, mel, None, taps, prof, f"{tag} L={L}", clips=[0])
+    cfgs = _verify(varch, mode, mel, None, taps, prof, f"{tag} L={L}", clips=[0], wave=wave if post else None)
     for k, t in taps.items():
         assert torch.equal(t[0], t[1]), f"{tag} L={L}: {k} differs between two copies of one clip"
     assert torch.equal(wave[0], wave[1])
     return cfgs, taps, wave
 
 
-def _reached(mode, C, L):
+def _reached(mode, C, L, num_mels=80):
     """The configurations of one (C, L) case, from `_config` alone (no GPU): conv_pre, the u = 1, k = 3 upsampler(s), the pairs."""
     math = MODES[mode][1]
-    out = {_config(math, 2 * C, L, 7, 1, 96)[0], _config(math, C, L + 1, 3, -1, 2 * C)[0], _config(math, C, L, 3, 1, C)[0]}
+    out = {_config(math, 2 * C, L, 7, 1, _mel_ld(num_mels))[0], _config(math, C, L + 1, 3, -1, 2 * C)[0], _config(math, C, L, 3, 1, C)[0]}
     if C == 256:
         out |= {_config(math, 128, L + 1, 3, -1, 256)[0], _config(math, 128, L, 3, 1, 128)[0]}
     return out

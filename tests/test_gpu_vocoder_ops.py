@@ -37,14 +37,20 @@ V1_BLOCKS = dict(resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 
 SUMMARY = {}                                          # kernel -> [max err / E near seams and edges, max elsewhere, checks]
 
 
-def _arch(C, u=1, k=3, **kw):
+def _arch(C, u=1, k=3, num_mels=80, **kw):
     """One stage of C channels behind an upsampler (u, k).  C = 256 gets a second u = 1 stage of 128 channels behind it: conv_post_kernel
-    keeps 262 rows of C + 4 floats in LDS and refuses 256 channels (no generator ends that wide)."""
+    keeps 262 rows of C + 4 floats in LDS and refuses 256 channels (no generator ends that wide).  num_mels: conv_pre's input width
+    (80 mel bins; the unit vocoder's 384 embedding channels)."""
     from speech_inpainting_amd.arch import VocoderArch
     blocks = dict(V1_BLOCKS)
     blocks.update(kw)
     us, ks = ((u, 1), (k, 3)) if C == 256 else ((u,), (k,))
-    return VocoderArch(upsample_rates=us, upsample_kernel_sizes=ks, upsample_initial_channel=2 * C, **blocks)
+    return VocoderArch(upsample_rates=us, upsample_kernel_sizes=ks, upsample_initial_channel=2 * C, num_mels=num_mels, **blocks)
+
+
+def _padded(C):
+    """The width the fp16 stream carries a stage of C channels at (api.hip, stage_channels: 4 <= C < 32 is padded to 32 with zero weights)."""
+    return 32 if 4 <= C < 32 else C
 
 
 _STATE = {}
@@ -90,15 +96,16 @@ def _engine(varch, env=None):
 
 
 def _shapes(varch, B, Tm):
-    """{tap name: (B, rows, channels)} of every tap the architecture can produce at Tm frames (stretch off)."""
+    """{tap name: (B, rows, channels)} of every tap the architecture can produce at Tm frames (stretch off); a stage's taps have the
+    width the stream carries it at (`_padded`)."""
     C, L = varch.upsample_initial_channel, Tm
     out = {"pre.f16": (B, L, C)}
     for i, u in enumerate(varch.upsample_rates):
         C, L = C // 2, L * u
-        out[f"ups{i}.f16"] = out[f"stage{i}.f16"] = (B, L, C)
+        out[f"ups{i}.f16"] = out[f"stage{i}.f16"] = (B, L, _padded(C))
         for j, dil in enumerate(varch.resblock_dilation_sizes):
             for n in range(len(dil)):
-                out[f"stage{i}.rb{j}.p{n}.f16"] = (B, L, C)
+                out[f"stage{i}.rb{j}.p{n}.f16"] = (B, L, _padded(C))
     return out
 
 
@@ -155,11 +162,17 @@ def _verify(varch, mel, lens, taps, wave, prof, tag, ops=("pre", "ups", "rb", "p
     two = str(varch.resblock) == "2"
     # stored activated: the producer of an upsampler that ran in gemmcu's TC kernels (include/si_hip.h); all candidates or none
     cand = [i for i, (u, k) in enumerate(zip(varch.upsample_rates, varch.upsample_kernel_sizes))
-            if k == 2 * u and (u * (varch.upsample_initial_channel >> (i + 1))) % 256 == 0 and (varch.upsample_initial_channel >> i) % 64 == 0]
+            if -(-k // u) == 2 and (u * (varch.upsample_initial_channel >> (i + 1))) % 256 == 0 and (varch.upsample_initial_channel >> i) % 64 == 0]
     n_tc = sum(v for k, v in prof.items() if k.startswith("gemmcu_f16_"))
     assert n_tc in (0, len(cand)), (n_tc, cand, prof)
     on_tc = set(cand) if n_tc else set()
     assert upsgemm or not on_tc
+    def real(name, b, L, C):
+        """Rows :L of clip b of a stage tap as the C real channels; the channels the stream pads the stage with must hold exact zeros."""
+        t = taps[name][b, :L]
+        assert t.shape[1] == _padded(C), (name, t.shape, C)
+        return V.real_channels(t, C, f"{tag} {name} clip {b}")
+
     for b in (range(B) if clips is None else clips):
         L = int(lens[b]) if lens is not None else Tm
         x = taps["pre.f16"][b, :L]
@@ -171,7 +184,8 @@ def _verify(varch, mel, lens, taps, wave, prof, tag, ops=("pre", "ups", "rb", "p
         for i, (u, k) in enumerate(zip(varch.upsample_rates, varch.upsample_kernel_sizes)):
             staged = x.double() if i in on_tc else V.lrelu16(x).double()
             Lo, C = L * u, C // 2
-            U16 = taps[f"ups{i}.f16"][b, :Lo]
+            U16 = real(f"ups{i}.f16", b, Lo, C)
+            Cp = _padded(C)                                        # the kernels' width: names and tile heights follow it, the references C
             if "ups" in ops:
                 ref, E = V.upsample_ref(staged, _w(varch, f"ups.{i}"), sd[f"ups.{i}.bias"], u)
                 if i in on_tc:
@@ -195,9 +209,9 @@ def _verify(varch, mel, lens, taps, wave, prof, tag, ops=("pre", "ups", "rb", "p
                     chained = name not in taps or (last and f"stage{i}.rb{j}.p0.f16" not in taps and last_n > 0)
                     if name not in taps:                               # inside a reschain.hip launch: x_n from the pairs run
                         assert x2_from is not None and not last, (name, sorted(taps))
-                        xin = x2_from[name][b, :L]
+                        xin = x2_from[name][b, :L, :C]
                         continue
-                    out = taps[name][b, :L]
+                    out = real(name, b, L, C)
                     if "rb" in ops:
                         alpha = V.alpha32(nk) if last else 1.0
                         prev = xs_prev.double() if (last and j > 0) else None
@@ -212,10 +226,10 @@ def _verify(varch, mel, lens, taps, wave, prof, tag, ops=("pre", "ups", "rb", "p
                             halo = (rk - 1) * (d + 1)
                             acc = "_acc" if (last and j > 0) else ""
                             if chained:
-                                kern, stored = f"reschain_f16_c{C}{acc}", 768 - (rk - 1) * (sum(dils) + 3)
-                                assert torch.equal(out, x2_from[name][b, :L]), f"{tag} {name}: the chain kernel and the pair kernels differ"
-                            elif f"respair_f16_c{C}{acc}" in prof:
-                                kern, stored = f"respair_f16_c{C}{acc}", R1[C] - (rk - 1)
+                                kern, stored = f"reschain_f16_c{Cp}{acc}", 768 - (rk - 1) * (sum(dils) + 3)
+                                assert torch.equal(taps[name][b, :L], x2_from[name][b, :L]), f"{tag} {name}: the chain kernel and the pair kernels differ"
+                            elif f"respair_f16_c{Cp}{acc}" in prof:
+                                kern, stored = f"respair_f16_c{Cp}{acc}", R1[Cp] - (rk - 1)
                             else:
                                 kern, stored = _kernel(prof, r"tapgemm_f16_.*"), None
                             assert kern.startswith("tapgemm") or kern in prof, (kern, sorted(prof))
@@ -223,17 +237,21 @@ def _verify(varch, mel, lens, taps, wave, prof, tag, ops=("pre", "ups", "rb", "p
                              kern, b, out, ref, E, stored, halo, hot)
                     xin = out
                 xs_prev = xin
-            assert torch.equal(taps[f"stage{i}.f16"][b, :L], xs_prev), f"{tag} stage{i}.f16 is not the last resblock's running sum"
+            assert torch.equal(real(f"stage{i}.f16", b, L, C), xs_prev), f"{tag} stage{i}.f16 is not the last resblock's running sum"
             x = xs_prev
         if "post" in ops:
-            ref, E = V.conv_post_ref(x, V.fold(sd, "conv_post", round16=False).float(), sd["conv_post.bias"], mfma=(C == 32))
-            _one(f"{tag} conv_post C={C}", _kernel(prof, "conv_post"), b, wave[b, :L], ref, E, 512 if C == 32 else 256, 3, True, f32=True)
+            ref, E = V.conv_post_ref(x, V.fold(sd, "conv_post", round16=False).float(), sd["conv_post.bias"], mfma=(_padded(C) == 32))
+            _one(f"{tag} conv_post C={C}", _kernel(prof, "conv_post"), b, wave[b, :L], ref, E, 512 if _padded(C) == 32 else 256, 3, True, f32=True)
             assert not bool(wave[b, L:].any()), f"{tag}: samples past clip {b}'s end are not silence"
 
 
-def _mel(B, Tm, seed):
+def _mel(B, Tm, seed, num_mels=80):
+    """The generator's input: a synthetic log-mel at 80 bins; at any other width (the unit vocoder's 384 channels of concatenated
+    embeddings) N(0, 0.5^2), as test_ida_style_generator_geometry_matches_oracle draws it."""
     from speech_inpainting_amd import synth
-    return synth.synth_mel(B, Tm, 80, seed)
+    if num_mels == 80:
+        return synth.synth_mel(B, Tm, 80, seed)
+    return torch.randn(B, num_mels, Tm, generator=torch.Generator().manual_seed(seed)) * 0.5
 
 
 def _ragged(eng, varch, lengths, seed, tag, **kw):
@@ -243,14 +261,14 @@ def _ragged(eng, varch, lengths, seed, tag, **kw):
         lengths = sorted(set(int(v) for v in lengths if v >= 1))
         lens = lengths[::2] + lengths[1::2][::-1]          # long and short clips interleaved: workgroups get different tile counts
     assert len(lens) <= 32
-    mel = _mel(len(lens), max(lens), seed)
+    mel = _mel(len(lens), max(lens), seed, varch.num_mels)
     taps, wave, prof = _run(eng, varch, mel, lens)
     _verify(varch, mel, lens, taps, wave, prof, f"{tag} ragged", **kw)
     return prof
 
 
 def _uniform(eng, varch, L, seed, tag, **kw):
-    one = _mel(1, L, seed)
+    one = _mel(1, L, seed, varch.num_mels)
     mel = torch.cat([one, one]).contiguous()
     taps, wave, prof = _run(eng, varch, mel)
     _verify(varch, mel, None, taps, wave, prof, f"{tag} uniform L={L}", clips=[0], **kw)

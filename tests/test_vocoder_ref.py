@@ -38,7 +38,17 @@ ARCHS = {
     "v1": dataclasses.replace(VocoderArch.v1(), upsample_initial_channel=128),     # V1's rates and blocks at an eighth of the width
     "v3": dataclasses.replace(VocoderArch.v3(), upsample_initial_channel=64),
     "u1": _one_stage(32),
+    # the I_da unit vocoder (hubert_lut.json) at its real widths: three taps per phase with empty slots (5, 11), k = 2 u at u = 4, 16 channels at the end
+    "unit": VocoderArch(upsample_rates=(5, 4, 4, 2, 2), upsample_kernel_sizes=(11, 8, 8, 4, 4), upsample_initial_channel=512, num_mels=384,
+                        sampling_rate=16000),
 }
+
+
+def _input(arch, B, Tm, seed):
+    """A synthetic log-mel for 80 bins; the unit vocoder's 384 embedding channels as N(0, 0.5^2)."""
+    if arch.num_mels == 80:
+        return synth.synth_mel(B, Tm, 80, seed)
+    return torch.randn(B, arch.num_mels, Tm, generator=torch.Generator().manual_seed(seed)) * 0.5
 
 
 def _plain(x):
@@ -46,7 +56,7 @@ def _plain(x):
 
 
 def _generator_by_refs(sd, arch, mel):
-    """The generator of one clip composed from the references, nothing rounded: mel (80, Tm) -> ({name: (L, C)}, wave (L,))."""
+    """The generator of one clip composed from the references, nothing rounded: mel (num_mels, Tm) -> ({name: (L, C)}, wave (L,))."""
     sd64 = {k: _F64(v) for k, v in sd.items()}
     f = lambda n: R._conv_weight(sd64, n)                                        # noqa: E731  (the fold itself in float64, as the oracle's run)
     taps = {}
@@ -81,8 +91,8 @@ def _generator_by_refs(sd, arch, mel):
 def test_references_reproduce_the_oracle_generator(name):
     arch = ARCHS[name]
     sd = synth.synth_generator_state(arch)
-    B, Tm = 2, 13
-    mel = synth.synth_mel(B, Tm, 80, 5)
+    B, Tm = 2, (3 if name == "unit" else 13)
+    mel = _input(arch, B, Tm, 5)
     want_taps = {}
     want = R.generator_forward({k: _F64(v) for k, v in sd.items()}, arch, _F64(mel), want_taps)
     assert want.dtype == torch.float64 and want.shape == (B, 1, Tm * arch.hop)
@@ -251,7 +261,7 @@ def _generator_by_tapgemm_ref(sd, arch, mel, math="f64"):
     cast = (lambda t: t) if math == "f64" else (lambda t: t.float())                                                    # noqa: E731
     taps = {}
     w = f("conv_pre")
-    x = cast(V.tapgemm_ref(mel.t(), w, sd["conv_pre.bias"], math, V.conv_geom(1), 7 * 80).ref)
+    x = cast(V.tapgemm_ref(mel.t(), w, sd["conv_pre.bias"], math, V.conv_geom(1), 7 * arch.num_mels).ref)
     taps["pre"] = x
     for i, (u, k) in enumerate(zip(arch.upsample_rates, arch.upsample_kernel_sizes)):
         w = f(f"ups.{i}")
@@ -273,12 +283,12 @@ def _generator_by_tapgemm_ref(sd, arch, mel, math="f64"):
     return taps
 
 
-@pytest.mark.parametrize("name", ["v1", "u1"])
+@pytest.mark.parametrize("name", ["v1", "u1", "unit"])
 def test_tapgemm_ref_reproduces_the_oracle_generator(name):
     """math = "f64" (nothing rounded) is the oracle's generator to 1e-12; the three arithmetics stay within their modes' distance of it."""
     arch = ARCHS[name]
     sd = synth.synth_generator_state(arch)
-    mel = synth.synth_mel(2, 11, 80, 5)
+    mel = _input(arch, 2, 3 if name == "unit" else 11, 5)
     want = {}
     R.generator_forward({k: _F64(v) for k, v in sd.items()}, arch, _F64(mel), want)
     for b in range(2):
@@ -408,3 +418,129 @@ def test_tapgemm_bounds_hold_for_an_fp32_evaluation_and_reject_every_listed_mist
     up = _emulate(x, wt, bt, math, V.tconv_geom(2), slope=V.SLOPE32)
     assert up.shape == (2 * L, C // 2) and V.check_f32(up, rt.ref, rt.E)["bad"] == 0
     assert V.check_f32(torch.roll(up, 1, 0), rt.ref, rt.E)["bad"] > 0
+
+
+# ------------------------------------------------------------------------------- the unit vocoder's geometry: (5, 11), (4, 8), 16 channels
+def _by_phases(a, w, b, u, swap=False, pad=None, crop=True, fill=False):
+    """ConvTranspose1d the way the kernels run it, in float32: tap j of the kernel is slot (tap q = j div u, phase p = j mod u); input row i
+    adds a[i] w[:, :, j] to row u (i + q) + p of the uncropped result (GEMM row m = i + q reads input rows m, m - 1, ...), slots j >= k hold
+    zero weights, and the first `pad` = (k - u) / 2 rows are cropped (ooff = -pad Cout) to leave u Lin rows.  a (Lin, Cin) and w (Cin, Cout, k)
+    float32.  The mistakes: swap -- phase and tap exchanged (j mod u for j div u); pad -- another crop; crop=False -- ooff = 0; fill -- an empty
+    (phase, tap) slot filled with the neighbouring tap's weight of the same phase."""
+    Lin, k = a.shape[0], w.shape[2]
+    ntaps = -(-k // u)
+    p0 = (k - u) // 2 if pad is None else pad
+    full = torch.zeros(u * (Lin + max(ntaps, u)) + u, w.shape[1], dtype=torch.float32)
+    for j in range(ntaps * u):
+        if j < k:
+            wj = w[:, :, j]
+        elif fill:
+            wj = w[:, :, j - u]
+        else:
+            continue
+        q, p = (j % u, j // u) if swap else (j // u, j % u)
+        rows = u * (torch.arange(Lin) + q) + p
+        full.index_add_(0, rows, a @ wj)
+    off = p0 if crop else 0
+    return full[off:off + u * Lin] + b.float()
+
+
+UPS_GEOM = [(5, 11, 64, 32), (4, 8, 64, 32), (5, 11, 32, 16)]
+
+
+@pytest.mark.parametrize("u,k,Cin,Cout", UPS_GEOM)
+def test_upsampler_bounds_at_the_unit_vocoders_geometry(u, k, Cin, Cout):
+    """(5, 11) and (4, 8): upsample_ref / tconv_geom are F.conv_transpose1d; a float32 evaluation by phases and taps (fp16 operands and an
+    fp16 store for the fp16 stream, fp32 operands for the tap-GEMM's exact path) stays inside the bound at Lin = 1, 2, 5, 7 and 40, and each
+    mistake of the phase / tap / crop bookkeeping lands outside it."""
+    g = torch.Generator().manual_seed(100 + u)
+    w32 = torch.randn(Cin, Cout, k, generator=g) / (Cin * k / u) ** 0.5
+    b = torch.randn(Cout, generator=g) * 0.05
+    pad = (k - u) // 2
+    for Lin in (1, 2, 5, 7, 40):
+        x16 = torch.randn(Lin, Cin, generator=g).to(torch.float16)
+        a = V.lrelu16(x16).double()
+        ref, E = V.upsample_ref(a, V.h16(w32), b, u)
+        assert ref.shape == (u * Lin, Cout)
+        want = torch.nn.functional.conv_transpose1d(a.t()[None], V.h16(w32), b.double(), stride=u, padding=pad)[0].t()
+        assert torch.equal(ref, want)
+        w16 = V.h16(w32).float()
+
+        def bad16(**kw):
+            return V.check_f16(_by_phases(a.float(), w16, b, u, **kw).to(torch.float16), ref, E)["bad"]
+
+        x32 = x16.float() * 1.37
+        r = V.tapgemm_ref(x32, w32, b, "f32", V.tconv_geom(u), -(-k // u) * Cin, slope=V.SLOPE32)
+
+        def bad32(**kw):
+            return V.check_f32(_by_phases(V.lrelu32(x32, V.SLOPE32), w32, b, u, **kw), r.ref, r.E)["bad"]
+
+        for bad in (bad16, bad32):
+            assert bad() == 0
+            assert bad(swap=True) > 0
+            assert bad(pad=pad - 1) > 0 and bad(pad=pad + 1) > 0
+            assert bad(crop=False) > 0
+            if k % u and Lin >= 2:               # (tap 2 of GEMM row m reads input row m - 2: with one input row an empty slot meets zeros only)
+                assert bad(fill=True) > 0
+
+
+def test_padded_stage_rejects_a_non_zero_value_in_channel_16():
+    """The fp16 stream's 16-channel stage at 32: real_channels hands back the 16 real channels and refuses any non-zero value in the padding,
+    down to the smallest subnormal; -0 is zero."""
+    t = torch.zeros(5, 32, dtype=torch.float16)
+    t[:, :16] = 1.5
+    t[3, 20] = -0.0
+    assert torch.equal(V.real_channels(t, 16), t[:, :16])
+    t[2, 16] = 2.0 ** -24
+    with pytest.raises(AssertionError, match="not exactly zero"):
+        V.real_channels(t, 16, "stage")
+    assert V.real_channels(t, 32) is not None
+
+
+def _compose16(arch, sd, mel):
+    """The fp16 stream of one clip composed from the references (the packer's fp16 weights, every stored tensor rounded to fp16 as the next
+    kernel reads it; hand-offs unactivated, which is the larger value): -> {tensor name: max |ref|} over every stored tensor."""
+    out = {}
+    nk = len(arch.resblock_kernel_sizes)
+
+    def keep(name, ref):
+        out[name] = float(ref.abs().max())
+        return V.rne_f16(ref.clamp(-V.F16_MAX, V.F16_MAX)).to(torch.float16)
+
+    x = keep("pre", V.tapconv_ref(V.h16(mel.t().clamp(-V.F16_MAX, V.F16_MAX)), V.fold(sd, "conv_pre"), sd["conv_pre.bias"])[0])
+    for i, u in enumerate(arch.upsample_rates):
+        x = keep(f"ups{i}", V.upsample_ref(V.lrelu16(x).double(), V.fold(sd, f"ups.{i}"), sd[f"ups.{i}.bias"], u)[0])
+        xs = None
+        for j, dils in enumerate(arch.resblock_dilation_sizes):
+            r = f"resblocks.{i * nk + j}."
+            y = x
+            for n, d in enumerate(dils):
+                last = n == len(dils) - 1
+                ref = V.pair_ref(V.lrelu16(y).double(), y.double(), V.fold(sd, f"{r}convs1.{n}"), sd[f"{r}convs1.{n}.bias"], V.fold(sd, f"{r}convs2.{n}"),
+                                 sd[f"{r}convs2.{n}.bias"], d, V.alpha32(nk) if last else 1.0, xs.double() if (last and xs is not None) else None)[0]
+                y = keep(f"stage{i}.rb{j}.p{n}", ref)
+            xs = y
+        x = xs
+    return out
+
+
+def test_every_fp16_input_of_the_unit_vocoder_tests_stays_far_from_saturation():
+    """tests/test_gpu_unitvoc_ops.py checks every element as an ordinary bound only where max |ref| < 65504 / 4 (`_one` asserts it on the
+    device): here the same inputs (architecture, seed, frames), composed on the CPU for the clips the GPU test checks, one clip per distinct
+    (architecture, seed, length)."""
+    from tests.test_gpu_unitvoc_ops import fp16_inputs
+    from tests.test_gpu_vocoder_ops import _mel, _state
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    seen, worst = set(), 0.0
+    for tag, arch, seed, lens, Tm, clips in fp16_inputs():
+        sd = _state(arch)
+        mel = _mel(1 if lens is None else len(lens), Tm if lens is None else max(lens), seed, arch.num_mels)
+        for b in ([0] if lens is None else (clips if clips is not None else range(len(lens)))):
+            L = Tm if lens is None else lens[b]
+            if (repr(arch), seed, b, L) in seen:
+                continue
+            seen.add((repr(arch), seed, b, L))
+            for name, m in _compose16(arch, sd, mel[b, :, :L]).items():
+                worst = max(worst, m)
+                assert m < V.F16_MAX / 4, (tag, b, L, name, m)
+    print(f"   largest |ref| over every tensor of {len(seen)} clips: {worst:.1f}")

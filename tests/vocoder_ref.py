@@ -391,6 +391,16 @@ def tconv_geom(u):
 
 
 # ----------------------------------------------------------------------------------------------------------- checking
+def real_channels(t, C, what="tensor"):
+    """A tensor of the fp16 stream as its C real channels (last dim).  A stage narrower than 32 channels is carried at 32 (api.hip,
+    stage_channels): the weights and biases of the extra channels are zero, so every stored value there is EXACTLY zero (a sum of
+    exact zero products, + 0 bias, + a zero residual), and the real channels see sixteen more zero products, which round nothing:
+    the references of the real width and their bounds apply unchanged.  Any non-zero bit pattern in the padding is a failure."""
+    assert t.shape[-1] >= C, (what, tuple(t.shape), C)
+    assert not bool((t[..., C:] != 0).any()), f"{what}: the padded channels {C}..{t.shape[-1] - 1} are not exactly zero"
+    return t[..., :C]
+
+
 def check_f16(got, ref, E):
     """A stored fp16 tensor against (ref, E) with the saturation rule of the module docstring, over ALL elements.
     -> dict(bad, ratio (err / E per element, 0 where the saturation rule decided), worst index)."""
