@@ -24,6 +24,8 @@
  *                           I_ea/predict.py:99-106 ; I_ea/dataset/mel_dump.py:40-98
  *   si_hifigan_forward   <- extend_mel + Generator.forward     I_ea/hifi_gan/inference_modified.py:16-19 ;
  *                           I_ea/hifi_gan/models.py:107-123 (called at I_ea/predict.py:189,203)
+ *   si_wave_peak / si_gather_windows / si_patch_compose  <- the whole-clip generator call and int16 write-out, for a recording
+ *                           that keeps its own samples outside the gaps      I_ea/predict.py:104,189,203-207
  *   si_load_weights      <- model.load_state_dict / generator.load_state_dict + remove_weight_norm + ApplyKmeans
  *                           I_ea/predict.py:117-122,149 ; I_ea/hifi_gan/models.py:125-132 ; I_ea/dataset/km_label.py:12-24
  *
@@ -405,6 +407,71 @@ int si_codebook_splice_labels_spans(si_ctx* ctx, const int64_t* labels, int B, c
 int si_codebook_metrics_spans(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_clip, const int32_t* frame_pos, int F,
                               const int64_t* target_labels, float* loss_terms, float* loss, int64_t* pred_labels, float* cos_pred_target,
                               si_stream_t stream);
+
+/* ---- Patch mode: generated audio spliced into the original recording -----------------------------------------------------------
+ * The reference's script writes the generator's waveform for the WHOLE clip (I_ea/predict.py:189,203-207: `generator(extend_mel(...))`,
+ * `audio * MAX_WAV_VALUE`, `.astype('int16')`), at the level `librosa.util.normalize(wave_22) * 0.95` gave its input (:104).  The calls
+ * below replace those lines for a caller who wants the recording back with only the gaps filled: the generator runs over windows of
+ * the stretched mel, and its samples are cross-faded into the caller's own 22.05 kHz samples at the caller's own level.
+ * Generator sample n IS 22.05 kHz input sample n (extend_mel centres stretched frame t at input sample (t + 0.5) * 256; 256 samples
+ * per stretched frame), so a window row that starts at stretched frame w0 starts at input sample w0 * 256. */
+
+/* The peak that si_mel_frontend(normalize != 0) divides by (I_ea/predict.py:104, `librosa.util.normalize`): peak_out[b] = max |x| over
+ * clip b with its spans zeroed (:99-102) -- the existing front-end pass, exposed.  gain = peak / 0.95 undoes `x / peak * 0.95`.
+ * spans: a 22.05 kHz si_span_table or NULL (no masking); sample_len: DEVICE int32 (B) or NULL (every clip holds N22 samples);
+ * peak_out device fp32 (B).  Needs no weights. */
+int si_wave_peak(si_ctx* ctx, const float* wave22, const si_span_table* spans, const int32_t* sample_len, int B, int N22, float* peak_out,
+                 si_stream_t stream);
+
+/* Windows of the stretched mel as the ragged generator batch (replaces the per-window slice copies in front of
+ * si_hifigan_forward_varlen(stretch = 0); the stretch itself is si_extend_mel, I_ea/hifi_gan/inference_modified.py:16-19).
+ * ext device fp32 (B, num_mels, Tout) channels-first; window w < W = stretched frames [w0[w], w1[w]) of clip clip[w], given twice as
+ * [clip (W) | w0 (W) | w1 (W)]: host_win (HOST int32, validated: 0 <= clip < B, 0 <= w0 < w1 <= Tout, w1 - w0 <= Wmax; a table that
+ * fails is never launched) and win (DEVICE int32, the same values, read by the kernel; keeping the two equal is the caller's duty, as
+ * for si_span_table).  out device fp32 (W, num_mels, Wmax): row (w, d) = ext[clip, d, w0:w1], zero past it. */
+int si_gather_windows(si_ctx* ctx, const float* ext, int B, int Tout, const int32_t* host_win, const int32_t* win, int W, int Wmax,
+                      float* out, si_stream_t stream);
+
+/* si_patch_table: where the generated samples of each span lie.  Window w < num_windows is one row of `gen`: it belongs to clip
+ * win_clip[w], its first sample is 22.05 kHz sample win_start[w] of that clip and it holds win_len[w] samples.  Span k of the span
+ * table (same order) takes its samples from window span_win[k].  lim[b] = min(clip b's samples, clip b's generated samples): nothing
+ * at or past it is replaced.  ramp: DEVICE fp32 (fade), the rising half of the cross-fade, w[i] = 0.5 (1 - cos(pi (i + 0.5) / fade))
+ * rounded once from float64 (speech_inpainting_amd/gaps.py::fade_ramp); the kernel reads it and evaluates no cosine.
+ * host_* (HOST) are validated, the DEVICE copies are read: the si_span_table rule. */
+typedef struct si_patch_table {
+    int32_t struct_size;            /* = sizeof(si_patch_table) */
+    int32_t num_clips;              /* B of the call */
+    int32_t num_windows;            /* W: rows of gen */
+    int32_t num_spans;              /* = the span table's num_spans */
+    int32_t fade;                   /* cross-fade length in samples, >= 0 (0 = hard splice) */
+    int32_t reserved;
+    const int32_t* host_win_clip;   /* HOST (num_windows) */
+    const int32_t* host_win_start;  /* HOST (num_windows) */
+    const int32_t* host_win_len;    /* HOST (num_windows) */
+    const int32_t* host_span_win;   /* HOST (num_spans) */
+    const int32_t* host_lim;        /* HOST (num_clips) */
+    const int32_t* win_start;       /* DEVICE copies of the last four */
+    const int32_t* win_len;
+    const int32_t* span_win;
+    const int32_t* lim;
+    const float* ramp;              /* DEVICE (fade), may be NULL when fade = 0 */
+} si_patch_table;
+
+/* The composition + B6 (replaces I_ea/predict.py:203-207 for a patched clip, and the host-side paste a caller of the whole-clip output
+ * would write).  Per clip b and span [s, e) of `spans` (22.05 kHz; spans of length 0 or starting at / past lim[b] are skipped) the
+ * blend region is [max(s - fade, 0), min(e + fade, lim[b])); the weight of sample m is ramp[m - (s - fade)] on the rise, 1 in [s, e),
+ * ramp[e + fade - 1 - m] on the fall, the MAXIMUM over the clip's spans, 0 elsewhere.  Output sample m:
+ *   weight 0:  orig's bits, unchanged (-0.0 and NaN payloads included);
+ *   weight 1:  exactly the fp32 product gain[b] * gen;
+ *   else:      fma(w, gain[b] * gen, (1 - w) * orig).
+ * orig device fp32 (B, N22); sample_len HOST int32 (B) or NULL: ragged batch, lim[b] <= sample_len[b] <= N22 is checked; gen device
+ * fp32 (num_windows, Lrow); gain device fp32 (B) or NULL (= 1); out_f32 device fp32 (B, N22) and / or out_pcm device int16 (B, N22) =
+ * si_pcm16's arithmetic on the same values (one of them may be NULL).  Rows are copied whole: samples past a ragged clip's end too.
+ * SI_EINVAL before any launch for: NULL / mis-sized structs; fade < 0; both outputs NULL; a window outside its clip (clip not in
+ * [0, B), start < 0, len < 0 or > Lrow, start + len > N22); a span whose window index is outside [0, num_windows) or names a window of
+ * another clip, or whose blend region leaves the window's row. */
+int si_patch_compose(si_ctx* ctx, const float* orig, const si_span_table* spans, const int32_t* sample_len, const si_patch_table* patch,
+                     const float* gen, int Lrow, const float* gain, int B, int N22, float* out_f32, int16_t* out_pcm, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

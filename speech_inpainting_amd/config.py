@@ -53,6 +53,8 @@ class PredictConfig:
     asr_model_name: Optional[str] = None
     raw: Optional[dict] = None
     masks: Optional[list] = None  # optional `masks:` list of (start_pos_in_sec, end_pos_in_sec): several gaps in the one file
+    patch_fade_ms: Optional[float] = None   # optional `patch:` mapping ({fade_ms: 5}): also write patched.wav (the recording with
+                                            # only the gaps filled); None without the key
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -74,6 +76,11 @@ class PredictConfig:
     @property
     def mask_pos(self) -> int:
         return self.start_sample // 320
+
+    @property
+    def patch_fade(self) -> Optional[int]:
+        """The cross-fade of patch mode in 22.05 kHz samples (fade_ms = 5 -> 110); None without a `patch:` key."""
+        return None if self.patch_fade_ms is None else int(round(self.patch_fade_ms * 22.05))
 
     @property
     def gaps(self):
@@ -105,6 +112,17 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             if not isinstance(masks, list) or not masks:
                 raise ValueError(f"{path}: `masks:` must be a non-empty list of {{start_pos_in_sec, end_pos_in_sec}} mappings")
             masks = sorted((float(m["start_pos_in_sec"]), float(m["end_pos_in_sec"])) for m in masks)
+        patch_fade_ms = None
+        if "patch" in data:
+            pm = data["patch"] if data["patch"] is not None else {}
+            if not isinstance(pm, dict):
+                raise ValueError(f"{path}: `patch:` must be a mapping (fade_ms: <milliseconds>, default 5)")
+            for key in pm:
+                if key != "fade_ms":
+                    raise ValueError(f"{path}: unknown key `{key}` in `patch:` (it takes fade_ms)")
+            patch_fade_ms = float(pm.get("fade_ms", 5))
+            if patch_fade_ms < 0:
+                raise ValueError(f"{path}: patch.fade_ms = {patch_fade_ms} is negative")
         return PredictConfig(
             dataset=ds,
             wave_path=data["wave"][ds]["wave_path"],
@@ -120,7 +138,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_type=str(data["hubert_model"]["type"]),
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
-            raw=data, masks=masks)
+            raw=data, masks=masks, patch_fade_ms=patch_fade_ms)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

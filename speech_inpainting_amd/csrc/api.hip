@@ -1937,6 +1937,84 @@ static int mel_run(si_ctx* ctx, const float* wave22, const int32_t* mask_start, 
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------------ patch mode
+extern "C" {
+
+int si_wave_peak(si_ctx* ctx, const float* wave22, const si_span_table* spans, const int32_t* sample_len, int B, int N22, float* peak_out,
+                 si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!wave22 || !peak_out || B <= 0 || N22 <= 0) return si_fail(ctx, SI_EINVAL, "si_wave_peak: NULL / empty argument");
+    SiSpans sp{};
+    if (spans) if (int rc = check_span_table(ctx, "si_wave_peak", spans, B, sp)) return rc;
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    return si_launch_wave_peak(ctx, wave22, nullptr, nullptr, B, N22, peak_out, static_cast<hipStream_t>(stream), sample_len, spans ? &sp : nullptr);
+}
+
+int si_gather_windows(si_ctx* ctx, const float* ext, int B, int Tout, const int32_t* host_win, const int32_t* win, int W, int Wmax,
+                      float* out, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!ext || !host_win || !win || !out || B <= 0 || Tout <= 0 || W <= 0 || Wmax <= 0)
+        return si_fail(ctx, SI_EINVAL, "si_gather_windows: NULL / empty argument");
+    for (int w = 0; w < W; ++w) {
+        const int clip = host_win[w], w0 = host_win[W + w], w1 = host_win[2 * W + w];
+        if (clip < 0 || clip >= B) return si_fail(ctx, SI_EINVAL, "si_gather_windows: window %d names clip %d of a batch of %d", w, clip, B);
+        if (w0 < 0 || w1 <= w0 || w1 > Tout)
+            return si_fail(ctx, SI_EINVAL, "si_gather_windows: window %d = frames [%d, %d) is outside its clip's %d stretched frames", w, w0, w1, Tout);
+        if (w1 - w0 > Wmax) return si_fail(ctx, SI_EINVAL, "si_gather_windows: window %d holds %d frames, rows hold %d", w, w1 - w0, Wmax);
+    }
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    return si_launch_gather_windows(ctx, ext, win, W, ctx->d.num_mels, Tout, Wmax, out, static_cast<hipStream_t>(stream));
+}
+
+int si_patch_compose(si_ctx* ctx, const float* orig, const si_span_table* spans, const int32_t* sample_len, const si_patch_table* patch,
+                     const float* gen, int Lrow, const float* gain, int B, int N22, float* out_f32, int16_t* out_pcm, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!orig || B <= 0 || N22 <= 0) return si_fail(ctx, SI_EINVAL, "si_patch_compose: NULL / empty argument");
+    if (!out_f32 && !out_pcm) return si_fail(ctx, SI_EINVAL, "si_patch_compose: both outputs are NULL");
+    SiSpans sp{};
+    if (int rc = check_span_table(ctx, "si_patch_compose", spans, B, sp)) return rc;
+    const si_patch_table* t = patch;
+    if (!t || t->struct_size != (int32_t)sizeof(si_patch_table)) return si_fail(ctx, SI_EINVAL, "si_patch_compose: si_patch_table size mismatch");
+    if (t->fade < 0 || (long)t->fade + N22 > 0x7fffffffL) return si_fail(ctx, SI_EINVAL, "si_patch_compose: fade of %d samples is negative or too long", t->fade);
+    if (t->num_clips != B || t->num_spans != spans->num_spans || t->num_windows < 0)
+        return si_fail(ctx, SI_EINVAL, "si_patch_compose: patch table for %d clips / %d spans / %d windows, call with %d clips / %d spans", t->num_clips,
+                       t->num_spans, t->num_windows, B, spans->num_spans);
+    const int W = t->num_windows;
+    if (!t->host_lim || !t->lim || (t->fade > 0 && !t->ramp)) return si_fail(ctx, SI_EINVAL, "si_patch_compose: patch table with NULL lim / ramp");
+    if (W > 0 && (!t->host_win_clip || !t->host_win_start || !t->host_win_len || !t->win_start || !t->win_len || !gen || Lrow <= 0))
+        return si_fail(ctx, SI_EINVAL, "si_patch_compose: %d windows but NULL window arrays / generator rows", W);
+    if (t->num_spans > 0 && (!t->host_span_win || !t->span_win)) return si_fail(ctx, SI_EINVAL, "si_patch_compose: patch table with NULL span_win");
+    for (int w = 0; w < W; ++w) {
+        const long c = t->host_win_clip[w], s = t->host_win_start[w], l = t->host_win_len[w];
+        if (c < 0 || c >= B || s < 0 || l < 0 || l > Lrow || s + l > N22)
+            return si_fail(ctx, SI_EINVAL, "si_patch_compose: window %d = clip %ld samples [%ld, +%ld) is outside its clip (%d clips of %d samples, rows of %d)",
+                           w, c, s, l, B, N22, Lrow);
+    }
+    for (int b = 0; b < B; ++b) {
+        const int n = sample_len ? sample_len[b] : N22, lim = t->host_lim[b];
+        if (n < 0 || n > N22 || lim < 0 || lim > n)
+            return si_fail(ctx, SI_EINVAL, "si_patch_compose: clip %d holds %d samples of its row of %d, lim %d", b, n, N22, lim);
+        for (int k = spans->host_off[b]; k < spans->host_off[b + 1]; ++k) {
+            const int s = spans->host_start[k], l = spans->host_len[k];
+            if (l <= 0 || s >= lim) continue;
+            const int w = t->host_span_win[k];
+            if (w < 0 || w >= W) return si_fail(ctx, SI_EINVAL, "si_patch_compose: clip %d span %d names window %d of %d", b, k - spans->host_off[b], w, W);
+            if (t->host_win_clip[w] != b)
+                return si_fail(ctx, SI_EINVAL, "si_patch_compose: clip %d span %d names window %d, which belongs to clip %d", b, k - spans->host_off[b], w, t->host_win_clip[w]);
+            const int e = std::min(s + l, lim);
+            const int ra = std::max(s - t->fade, 0), rb = std::min(e + t->fade, lim);
+            if (ra < t->host_win_start[w] || rb > t->host_win_start[w] + t->host_win_len[w])
+                return si_fail(ctx, SI_EINVAL, "si_patch_compose: clip %d span %d blends samples [%d, %d), its window's row holds [%d, %d)", b,
+                               k - spans->host_off[b], ra, rb, t->host_win_start[w], t->host_win_start[w] + t->host_win_len[w]);
+        }
+    }
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    const SiPatch pt{t->win_start, t->win_len, t->span_win, t->lim, t->ramp, t->fade};
+    return si_launch_patch_compose(ctx, orig, sp, pt, gen, Lrow, gain, B, N22, out_f32, out_pcm, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"
+
 extern "C" {
 
 int si_profile_start(si_ctx* ctx, int max_launches) {

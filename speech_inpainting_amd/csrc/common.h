@@ -320,6 +320,18 @@ int si_launch_resample_sinc(si_ctx* ctx, const float* x, const int32_t* n_len, i
 // `audio * 32768` + truncating int16 cast (I_ea/predict.py:204-206)
 int si_launch_pcm16(si_ctx* ctx, const float* wav, long n, int16_t* out, hipStream_t st);
 
+// ------------------------------------------------------------------------------------------------
+// patch mode (patch_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// The device half of si_patch_table: per window the first 22.05 kHz sample of its generator row and the row's length, per span the
+// window that holds it, per clip lim = min(its samples, its generated samples), and the rising cross-fade ramp (fade floats).
+struct SiPatch { const int32_t* win_start; const int32_t* win_len; const int32_t* span_win; const int32_t* lim; const float* ramp; int fade; };
+// ext (B, D, Tout) -> out (W, D, Wmax): row (w, d) = ext[clip_w, d, w0_w : w1_w], zero past it; win (device) = [clip (W) | w0 (W) | w1 (W)]
+int si_launch_gather_windows(si_ctx* ctx, const float* ext, const int32_t* win, int W, int D, int Tout, int Wmax, float* out, hipStream_t st);
+// out / pcm (B, N22; either may be null) = orig outside the blend regions of `sp`, (1 - w) orig + w gain[b] gen inside; gain null = 1
+int si_launch_patch_compose(si_ctx* ctx, const float* orig, const SiSpans& sp, const SiPatch& pt, const float* gen, int Lrow, const float* gain,
+                            int B, int N22, float* out, int16_t* pcm, hipStream_t st);
+
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16
 // rounding every consumer of these outputs applies; 15 VALU operations instead of libm erff's ~31 with two divergent branches.

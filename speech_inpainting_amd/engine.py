@@ -12,14 +12,14 @@ benchmark times.  Nothing here computes on the CPU: a missing library or a CPU d
 """
 from __future__ import annotations
 
-from typing import Dict, Mapping, Optional, Sequence
+from typing import Dict, Mapping, Optional, Sequence, Tuple
 
 import torch
 
 from .arch import HubertArch, VocoderArch
 from .checkpoint import flatten_checkpoint
 from . import gaps as G
-from .native import NativeContext, SpanTable, make_desc
+from .native import NativeContext, PatchTable, SpanTable, make_desc
 
 
 def mask_samples_from_frames(frame_pos: int, frame_len: int):
@@ -392,7 +392,8 @@ class InpaintingEngine:
                 "wave_len": [self.ctx.vocoder_samples(m, True) for m in mel_len]}
 
     # ---- several gaps per clip, one pass
-    def gap_tables(self, gaps, n16: Sequence[int], n_mel: Sequence[int], mel_frames: bool = False, spans22=None, staging=None) -> Dict[str, object]:
+    def gap_tables(self, gaps, n16: Sequence[int], n_mel: Sequence[int], mel_frames: bool = False, spans22=None, staging=None,
+                   patch_fade: Optional[int] = None) -> Dict[str, object]:
         """Validate `gaps` (per clip a list of (first frame, frame count)) against each clip's min(T, Tm) and build what one multi-gap
         pass needs: gaps (sorted), tab16 (SpanTable of the 16 kHz spans), tab22 (SpanTable of the 22.05 kHz spans: the gaps' by
         I_ea/predict.py:99-100, or `spans22[b]` = [start, end) sample pairs; None when n_mel counts mel frames), frame_clip /
@@ -400,7 +401,11 @@ class InpaintingEngine:
         n16: 16 kHz samples per clip; n_mel: 22.05 kHz samples per clip, or mel frames when mel_frames=True.
         staging = (pinned int32 tensor, device int32 tensor, stream): all tables are written into the pinned buffer and cross in ONE
         asynchronous copy on `stream` (the request front's host-to-device stream); the caller orders that stream before the compute
-        stream and keeps both buffers untouched until the pass is done.  Default: pageable copies on the current stream."""
+        stream and keeps both buffers untouched until the pass is done.  Default: pageable copies on the current stream.
+        patch_fade (22.05 kHz samples; raw clips only): also plan patch mode (`plan_patch`) -- entry "patch"; with `staging` its
+        tables ride in the same buffer and the same copy."""
+        if patch_fade is not None and mel_frames:
+            raise ValueError("gap_tables: patch mode needs the 22.05 kHz samples, not a mel")
         if not (len(gaps) == len(n16) == len(n_mel)):
             raise ValueError(f"gaps for {len(gaps)} clips, batch of {len(n16)}")
         lim = [min(self.ctx.num_frames(int(a)), int(m) if mel_frames else self.ctx.mel_frames(int(m))) for a, m in zip(n16, n_mel)]
@@ -409,13 +414,18 @@ class InpaintingEngine:
         s16 = G.spans16(g)
         s22 = None if mel_frames else (G.spans22(g, n_mel) if spans22 is None else G.clamp_spans22(spans22, n_mel))
         F = len(ci)
+        plan = None if patch_fade is None else self.plan_patch(s22, n_mel, patch_fade)
         if staging is None:
             tab = torch.tensor([ci, fp], dtype=torch.int32).to(self.device)
-            return {"gaps": g, "tab16": SpanTable(s16, self.device), "tab22": None if s22 is None else SpanTable(s22, self.device),
-                    "frame_clip": tab[0].contiguous(), "frame_pos": tab[1].contiguous(), "label_off": off}
+            tb = {"gaps": g, "tab16": SpanTable(s16, self.device), "tab22": None if s22 is None else SpanTable(s22, self.device),
+                  "frame_clip": tab[0].contiguous(), "frame_pos": tab[1].contiguous(), "label_off": off}
+            if plan is not None:
+                tb["patch"] = self._patch_tables(plan)
+            return tb
         pin, dbuf, stream = staging
         w16, w22 = SpanTable.words(s16), 0 if s22 is None else SpanTable.words(s22)
-        total = w16 + w22 + 2 * F
+        wp = 0 if plan is None else self.patch_words(plan)
+        total = w16 + w22 + 2 * F + wp
         if total > min(pin.numel(), dbuf.numel()):
             raise ValueError(f"gap_tables: the staging buffers hold {min(pin.numel(), dbuf.numel())} words, the tables need {total}")
         hp = pin.numpy()
@@ -424,9 +434,124 @@ class InpaintingEngine:
         o = w16 + w22
         hp[o:o + F] = ci
         hp[o + F:o + 2 * F] = fp
+        if plan is not None:
+            self._patch_tables(plan, staged=(hp[o + 2 * F:total], dbuf[o + 2 * F:total]))
         with torch.cuda.stream(stream):
             dbuf[:total].copy_(pin[:total], non_blocking=True)
-        return {"gaps": g, "tab16": tab16, "tab22": tab22, "frame_clip": dbuf[o:o + F], "frame_pos": dbuf[o + F:o + 2 * F], "label_off": off}
+        tb = {"gaps": g, "tab16": tab16, "tab22": tab22, "frame_clip": dbuf[o:o + F], "frame_pos": dbuf[o + F:o + 2 * F], "label_off": off}
+        if plan is not None:
+            tb["patch"] = plan
+        return tb
+
+    # ---- patch mode: the generated audio of the gaps spliced into the caller's own 22.05 kHz samples
+    def plan_patch(self, spans22: Sequence[Sequence[Sequence[int]]], n22: Sequence[int], fade: int) -> Dict[str, object]:
+        """Host planning of one patched batch: per clip the blend regions of its 22.05 kHz spans (start, len) and the generator
+        windows that hold them (gaps.blend_regions / gaps.plan_patch_windows with this generator's hop and receptive radius).
+        -> fade, hop, wins = (clip, w0, w1) of all windows, windows (per clip), span_win (flat, the span table's order), lim and
+        n22 (per clip)."""
+        hop = self.ctx.vocoder_samples(1, False)
+        if hop != 256:
+            # extend_mel centres stretched frame t at input sample (t + 0.5) * 256: generator sample n is input sample n only at hop 256
+            raise ValueError(f"patch mode needs a generator of hop 256 (the x441/256 stretch's identity time map), this one has hop {hop}")
+        rf = -(-self.receptive_radius() // hop)
+        wins, span_win, lim, per_clip = [], [], [], []
+        for b, (spans, n) in enumerate(zip(spans22, n22)):
+            n_out = self.ctx.vocoder_samples(self.ctx.mel_frames(int(n)), True)
+            w, which = G.plan_patch_windows(G.blend_regions(spans, int(n), n_out, fade), n_out // hop, hop, rf)
+            span_win += [len(wins) + k if k >= 0 else -1 for k in which]
+            wins += [(b, w0, w1) for w0, w1 in w]
+            per_clip.append(w)
+            lim.append(min(int(n), n_out))
+        return {"fade": int(fade), "hop": hop, "wins": wins, "windows": per_clip, "span_win": span_win, "lim": lim, "n22": [int(n) for n in n22]}
+
+    @staticmethod
+    def patch_words(plan: Dict[str, object]) -> int:
+        """int32 words the tables of a plan take in a staging buffer: the PatchTable, the window table of the gather, the lengths."""
+        W, B = len(plan["wins"]), len(plan["lim"])
+        return PatchTable.words(W, len(plan["span_win"]), B, plan["fade"]) + 3 * W + B
+
+    def _patch_tables(self, plan: Dict[str, object], staged=None) -> Dict[str, object]:
+        """Adds the device tables to a plan: table (PatchTable), gwin (the gather's window words, host + device) and len22 (device
+        int32 (B)).  staged = (host, dev) views of `patch_words(plan)` words that the CALLER copies."""
+        wins, hop, B = plan["wins"], plan["hop"], len(plan["lim"])
+        W = len(wins)
+        rows = [(b, w0 * hop, (w1 - w0) * hop) for b, w0, w1 in wins]
+        if staged is None:
+            plan["table"] = PatchTable(rows, plan["span_win"], plan["lim"], plan["fade"], self.device)
+            plan["gwin"] = None
+            plan["len22"] = torch.tensor(plan["n22"], dtype=torch.int32).to(self.device)
+            return plan
+        hp, dv = staged
+        wt = PatchTable.words(W, len(plan["span_win"]), B, plan["fade"])
+        plan["table"] = PatchTable(rows, plan["span_win"], plan["lim"], plan["fade"], self.device, staged=(hp[:wt], dv[:wt]))
+        hp[wt:wt + 3 * W] = self.ctx.window_words(wins)
+        hp[wt + 3 * W:wt + 3 * W + B] = plan["n22"]
+        plan["gwin"] = (hp[wt:wt + 3 * W], dv[wt:wt + 3 * W])
+        plan["len22"] = dv[wt + 3 * W:wt + 3 * W + B]
+        return plan
+
+    def _compose(self, wave22: torch.Tensor, tab22: SpanTable, table: PatchTable, gen: Optional[torch.Tensor], len22_host, len22_dev,
+                 pcm: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        # the front-end divided by this peak and multiplied by 0.95 (I_ea/predict.py:104): the generated audio goes back by peak / 0.95
+        gain = self.ctx.wave_peak(wave22, tab22, len22_dev) / 0.95
+        return self.ctx.patch_compose(wave22, tab22, table, gen, gain, sample_len=len22_host, f32=True, pcm=pcm)
+
+    def patch_multigap_batch(self, wave16: torch.Tensor, wave22: torch.Tensor, gaps, fade: int = 110, len16: Optional[Sequence[int]] = None,
+                             len22: Optional[Sequence[int]] = None, spans22: Optional[Sequence[Sequence[Sequence[int]]]] = None,
+                             tables: Optional[Dict[str, object]] = None, pcm: bool = False) -> Dict[str, object]:
+        """`predict_multigap_batch` on RAW 22.05 kHz clips whose output is the caller's own recording with only the gaps filled:
+        `patched` (B, N22) fp32 equals wave22 BIT FOR BIT outside a cross-fade of `fade` samples (22.05 kHz; 110 ~ 5 ms; 0 = hard
+        splice) around each gap, and inside the gaps it is the generator's audio at the recording's level (the front-end's peak
+        normalisation undone).  The generator runs only over the windows of the stretched mel those samples need
+        (gaps.plan_patch_windows), as one ragged stretch=False batch -- bit-identical there to a full pass.  A clip without gaps comes
+        back as an exact copy.  tables: `gap_tables(..., patch_fade=fade)`'s result.
+        -> predict_multigap_batch's dictionary WITHOUT `wave`, plus patched, patched_pcm (int16, with pcm=True), patch_windows
+        (per clip the (w0, w1) stretched-frame windows that were vocoded)."""
+        if wave22.dim() != 2:
+            raise ValueError("patch_multigap_batch: patch mode keeps the caller's samples, so it needs the raw (B, N22) 22.05 kHz clips")
+        B = wave16.shape[0]
+        ragged = len16 is not None
+        if ragged and len22 is None:
+            raise ValueError("patch_multigap_batch: a ragged batch needs len22")
+        n16 = [int(n) for n in len16] if ragged else [wave16.shape[1]] * B
+        n22 = [int(n) for n in len22] if len22 is not None else [wave22.shape[1]] * B
+        tb = tables if tables is not None else self.gap_tables(gaps, n16, n22, spans22=spans22, patch_fade=fade)
+        plan = tb.get("patch")
+        if plan is None or plan["fade"] != int(fade):
+            raise ValueError("patch_multigap_batch: `tables` were not built by gap_tables(..., patch_fade=fade) for this fade")
+        out = self.predict_multigap_batch(wave16, wave22, gaps, len16=len16, len22=len22 if ragged else None, tables=tb, vocode=False)
+        wins, gen = plan["wins"], None
+        if wins:
+            mel2 = out["mel"]
+            ext = self.ctx.extend_mel(mel2)
+            if ragged:
+                # the stretch of a shorter clip clamps at ITS last frame: its rows come from the clip stretched alone (as vocode_windows)
+                Tout = ext.shape[2]
+                for b, m in enumerate(out["mel_len"]):
+                    t_b = self.ctx.vocoder_samples(int(m), True) // plan["hop"]
+                    if t_b < Tout and plan["windows"][b]:
+                        ext[b, :, :t_b] = self.ctx.extend_mel(mel2[b:b + 1, :, :int(m)].contiguous())[0]
+            win = self.ctx.gather_windows(ext, wins, tab=plan["gwin"])
+            gen = self.vocode_ragged(win, [w1 - w0 for _, w0, w1 in wins], stretch=False)
+        patched, ppcm = self._compose(wave22, tb["tab22"], plan["table"], gen, n22 if ragged else None, plan["len22"] if ragged else None, pcm)
+        out.update(patched=patched, patch_windows=plan["windows"])
+        if pcm:
+            out["patched_pcm"] = ppcm
+        return out
+
+    def patch_from_wave(self, wave22: torch.Tensor, wave: torch.Tensor, tab22: SpanTable, fade: int = 110, len22: Optional[Sequence[int]] = None,
+                        wave_len: Optional[Sequence[int]] = None, pcm: bool = False):
+        """The same composition from a FULL generator pass `wave` (B, L) of the spliced mel (for callers who also want `wave`, and
+        the reference the windowed route is tested against): one window per clip, starting at sample 0.  tab22: the 22.05 kHz
+        SpanTable the mel front-end read; len22 / wave_len: per-clip samples of a ragged batch.  -> (patched, patched_pcm or None)."""
+        B, L = wave.shape
+        n22 = [int(n) for n in len22] if len22 is not None else [wave22.shape[1]] * B
+        wl = [int(n) for n in wave_len] if wave_len is not None else [L] * B
+        spans = tab22.spans()
+        rows = [(b, 0, min(wl[b], wave22.shape[1])) for b in range(B)]
+        table = PatchTable(rows, [b for b in range(B) for _ in spans[b]], [min(n, w) for n, w in zip(n22, wl)], fade, self.device)
+        l22 = None if len22 is None else torch.tensor(n22, dtype=torch.int32).to(self.device)
+        return self._compose(wave22.contiguous(), tab22, table, wave.contiguous(), n22 if len22 is not None else None, l22, pcm)
 
     def predict_multigap_batch(self, wave16: torch.Tensor, mel_or_wave22: torch.Tensor, gaps, len16: Optional[Sequence[int]] = None,
                                len22: Optional[Sequence[int]] = None, mel_len: Optional[Sequence[int]] = None,

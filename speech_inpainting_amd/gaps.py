@@ -136,3 +136,72 @@ def plan_windows(ranges: Sequence[Gap], t_out: int, rf: int) -> List[Tuple[int, 
 def kept_region(w0: int, w1: int, t_out: int, rf: int) -> Tuple[int, int]:
     """The frames of window [w0, w1) whose output is spliced back."""
     return w0 + (rf if w0 > 0 else 0), w1 - (rf if w1 < t_out else 0)
+
+
+# ---- patch mode: the generated audio of the gaps spliced into the caller's own 22.05 kHz samples (DESIGN.md 4.13)
+def fade_ramp(fade: int):
+    """The rising half of the cross-fade, fp32 (fade): w[i] = 0.5 * (1 - cos(pi * (i + 0.5) / fade)), computed in float64 and rounded
+    once.  The compose kernel READS this table (it evaluates no cosine), so host and device weights are the same floats.
+    fade = 0 gives an empty table: a hard splice."""
+    import numpy as np
+    fade = int(fade)
+    if fade < 0:
+        raise ValueError(f"fade = {fade} samples is negative")
+    i = np.arange(fade, dtype=np.float64)
+    return (0.5 * (1.0 - np.cos(np.pi * (i + 0.5) / max(fade, 1)))).astype(np.float32)
+
+
+def blend_regions(spans22_b: Sequence[Gap], n22_b: int, n_out_b: int, fade: int) -> List[Optional[Gap]]:
+    """Per (start, len) span of ONE clip (22.05 kHz samples) the half-open sample range [a, b) in which the patched output is not
+    the original: the span widened by `fade` on each side, clamped to [0, lim), lim = min(n22_b, n_out_b) (the generator emits
+    n_out_b <= n22_b samples; past them the original stays).  None for a span of length 0 and for one that starts at or past lim."""
+    lim = min(int(n22_b), int(n_out_b))
+    out: List[Optional[Gap]] = []
+    for s, l in spans22_b:
+        s, e = int(s), int(s) + int(l)
+        out.append(None if l <= 0 or s >= lim else (max(s - fade, 0), min(e + fade, lim)))
+    return out
+
+
+def blend_weights(spans22_b: Sequence[Gap], n22_b: int, n_out_b: int, fade: int, n: Optional[int] = None):
+    """The weight of the generated audio at every sample of one clip, fp32 (n or n22_b): per span ramp[m - (s - fade)] on the rise,
+    1 inside [s, e), ramp[e + fade - 1 - m] on the fall; the MAXIMUM over the clip's spans (ramps overlap when two gaps are closer
+    than 2 * fade); 0 elsewhere and for every m >= lim.  What patch_compose_kernel computes, as a host table for tests and tools."""
+    import numpy as np
+    ramp = fade_ramp(fade)
+    w = np.zeros(int(n22_b) if n is None else int(n), dtype=np.float32)
+    lim = min(int(n22_b), int(n_out_b), w.size)
+    for (s, l), reg in zip(spans22_b, blend_regions(spans22_b, n22_b, n_out_b, fade)):
+        if reg is None:
+            continue
+        s, e = int(s), int(s) + int(l)
+        one = np.zeros_like(w)
+        m = np.arange(reg[0], min(reg[1], lim))
+        one[m] = np.where(m < s, ramp[np.clip(m - (s - fade), 0, max(fade - 1, 0))] if fade else 0.0,
+                          np.where(m < e, 1.0, ramp[np.clip(e + fade - 1 - m, 0, max(fade - 1, 0))] if fade else 0.0))
+        w = np.maximum(w, one)
+    return w
+
+
+def plan_patch_windows(regions: Sequence[Optional[Gap]], t_out: int, hop: int, rf: int) -> Tuple[List[Tuple[int, int]], List[int]]:
+    """Generator windows [w0, w1) (stretched frames) for one clip's blend regions (`blend_regions`; None entries get no window).
+    A region [a, b) needs stretched frames [a // hop, ceil(b / hop)); the window is that range widened by rf on each side and
+    clamped to [0, t_out), so the needed frames lie in its kept region (`kept_region`).  Windows that overlap or touch are merged:
+    only the needed samples must be exact here, not everything a changed frame can reach, hence rf and not `plan_windows`' 2 * rf.
+    -> (windows sorted and disjoint, per region the index of its window or -1)."""
+    order = sorted((k for k, r in enumerate(regions) if r is not None), key=lambda k: regions[k])
+    wins: List[Tuple[int, int]] = []
+    which = [-1] * len(regions)
+    for k in order:
+        a, b = regions[k]
+        w0, w1 = max(a // hop - rf, 0), min(-(-b // hop) + rf, t_out)
+        if wins and w0 <= wins[-1][1]:
+            wins[-1] = (wins[-1][0], max(wins[-1][1], w1))
+        else:
+            wins.append((w0, w1))
+        which[k] = len(wins) - 1
+    for k in order:
+        a, b = regions[k]
+        k0, k1 = kept_region(*wins[which[k]], t_out, rf)
+        assert k0 * hop <= a and b <= k1 * hop, f"region [{a}, {b}) leaves the kept frames [{k0}, {k1}) of its window"
+    return wins, which

@@ -29,7 +29,7 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_vocoder_samples", "si_profile_start", "si_profile_filter", "si_profile_stop",
            "si_debug_capture", "si_debug_size",
            "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
-           "si_codebook_metrics_spans"]
+           "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose"]
 SI_MAX_SPANS = 16
 
 
@@ -94,10 +94,59 @@ class SpanTable:
                 raise ValueError(f"SpanTable: staged views of {self.host.size} / {self.dev.numel()} words, the table has {vals.size}")
             np.copyto(self.host, vals)
 
+    def spans(self):
+        """The table back as per-clip lists of (start, len), from the host copy."""
+        B, n, h = self.B, self.n, self.host
+        return [[(int(h[B + 1 + k]), int(h[B + 1 + n + k])) for k in range(int(h[b]), int(h[b + 1]))] for b in range(B)]
+
     def struct(self) -> SpanTableStruct:
         h, d, B, n = self.host.ctypes.data, self.dev.data_ptr(), self.B, self.n
         return SpanTableStruct(C.sizeof(SpanTableStruct), B, n, 0, h, h + 4 * (B + 1), h + 4 * (B + 1 + n),
                                d, d + 4 * (B + 1), d + 4 * (B + 1 + n))
+
+
+class PatchTableStruct(C.Structure):
+    """Mirror of si_patch_table."""
+    _fields_ = [("struct_size", C.c_int32), ("num_clips", C.c_int32), ("num_windows", C.c_int32), ("num_spans", C.c_int32),
+                ("fade", C.c_int32), ("reserved", C.c_int32),
+                ("host_win_clip", C.c_void_p), ("host_win_start", C.c_void_p), ("host_win_len", C.c_void_p), ("host_span_win", C.c_void_p),
+                ("host_lim", C.c_void_p),
+                ("win_start", C.c_void_p), ("win_len", C.c_void_p), ("span_win", C.c_void_p), ("lim", C.c_void_p), ("ramp", C.c_void_p)]
+
+
+class PatchTable:
+    """Where the generated samples of each span lie, as si_patch_table takes it (the companion of the 22.05 kHz SpanTable):
+    windows = (clip, first 22.05 kHz sample, samples) per generator row; span_win = per span of the SpanTable (flat, its order) the row
+    that holds it (-1 for a span that is skipped); lim = per clip min(its samples, its generated samples); fade in samples.
+    Like SpanTable it holds the host words the library validates and ONE device tensor
+    [win_clip | win_start | win_len | span_win | lim | ramp (fp32 bits)] the kernel reads -- one array, one copy.
+    staged = (host, dev) as SpanTable's: views of `words(...)` int32 elements of a caller-owned (pinned) buffer and of the device
+    tensor the caller copies it to."""
+
+    @staticmethod
+    def words(n_windows: int, n_spans: int, n_clips: int, fade: int) -> int:
+        return 3 * n_windows + n_spans + n_clips + fade + 1
+
+    def __init__(self, windows, span_win, lim, fade: int, device, staged=None):
+        from .gaps import fade_ramp
+        self.W, self.S, self.B, self.fade = len(windows), len(span_win), len(lim), int(fade)
+        cols = [[int(w[j]) for w in windows] for j in range(3)]
+        ints = np.array(cols[0] + cols[1] + cols[2] + [int(k) for k in span_win] + [int(n) for n in lim], dtype=np.int32)
+        vals = np.concatenate([ints, fade_ramp(self.fade).view(np.int32), np.zeros(1, np.int32)])    # (+ 1: never an empty array)
+        if staged is None:
+            self.host = np.ascontiguousarray(vals)
+            self.dev = torch.from_numpy(self.host).to(device, non_blocking=True)
+        else:
+            self.host, self.dev = staged
+            if self.host.size != vals.size or self.dev.numel() != vals.size:
+                raise ValueError(f"PatchTable: staged views of {self.host.size} / {self.dev.numel()} words, the table has {vals.size}")
+            np.copyto(self.host, vals)
+
+    def struct(self) -> PatchTableStruct:
+        h, d, W, S, B = self.host.ctypes.data, self.dev.data_ptr(), self.W, self.S, self.B
+        o = [0, 4 * W, 8 * W, 12 * W, 12 * W + 4 * S, 12 * W + 4 * S + 4 * B]
+        return PatchTableStruct(C.sizeof(PatchTableStruct), B, W, S, self.fade, 0, h + o[0], h + o[1], h + o[2], h + o[3], h + o[4],
+                                d + o[1], d + o[2], d + o[3], d + o[4], d + o[5])
 
 
 class ExtractDesc(C.Structure):
@@ -239,6 +288,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_codebook_splice_spans.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]
     lib.si_codebook_splice_labels_spans.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp]
     lib.si_codebook_metrics_spans.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.si_wave_peak.argtypes = [vp, vp, C.POINTER(SpanTableStruct), vp, i32, i32, vp, vp]
+    lib.si_gather_windows.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp]
+    lib.si_patch_compose.argtypes = [vp, vp, C.POINTER(SpanTableStruct), vp, C.POINTER(PatchTableStruct), vp, i32, vp, i32, i32, vp, vp, vp]
     lib.si_num_frames.argtypes = [vp, i32]
     lib.si_vocoder_samples.argtypes = [vp, i32, i32]
     lib.si_debug_capture.argtypes = [vp, C.c_char_p, vp, C.c_long]
@@ -478,6 +530,64 @@ class NativeContext:
                                                    int(normalize), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
                     "si_mel_frontend_spans")
         return out
+
+    # ---- patch mode
+    def wave_peak(self, wave22: torch.Tensor, spans: Optional["SpanTable"] = None, sample_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """max |x| per clip with the spans zeroed: the divisor of mel_frontend's normalisation (si_wave_peak).  sample_len: DEVICE int32 (B)."""
+        assert wave22.is_cuda and wave22.dtype == torch.float32 and wave22.dim() == 2 and wave22.is_contiguous()
+        B, N = wave22.shape
+        assert sample_len is None or (sample_len.is_cuda and sample_len.dtype == torch.int32 and sample_len.numel() == B and sample_len.is_contiguous())
+        out = torch.empty(B, dtype=torch.float32, device=self.device)
+        t = None if spans is None else spans.struct()
+        self._check(self.lib.si_wave_peak(self._h, _ptr(wave22), None if t is None else C.byref(t), _ptr(sample_len), B, N, _ptr(out), self._stream()),
+                    "si_wave_peak")
+        return out
+
+    @staticmethod
+    def window_words(wins) -> np.ndarray:
+        """(clip, w0, w1) triples -> the int32 words [clip (W) | w0 (W) | w1 (W)] si_gather_windows reads."""
+        return np.array([[int(w[j]) for w in wins] for j in range(3)], dtype=np.int32).reshape(-1)
+
+    def gather_windows(self, ext: torch.Tensor, wins, wmax: Optional[int] = None, tab=None) -> torch.Tensor:
+        """ext (B, D, Tout) + wins = (clip, w0, w1) triples -> (W, D, Wmax), zero past each window's own frames (si_gather_windows).
+        tab = (host int32 numpy view, device int32 tensor) holding `window_words(wins)` ALREADY (a caller that staged the table with
+        its other tables, one copy); default: built and copied here."""
+        assert ext.is_cuda and ext.dtype == torch.float32 and ext.dim() == 3 and ext.is_contiguous() and ext.shape[1] == self.desc.num_mels
+        B, D, Tout = ext.shape
+        W = len(wins)
+        if tab is None:
+            host = self.window_words(wins)
+            dev = torch.from_numpy(host).to(self.device, non_blocking=True)
+        else:
+            host, dev = tab
+            assert host.size == 3 * W and dev.numel() == 3 * W and dev.dtype == torch.int32
+        if wmax is None:
+            wmax = max(int(w1) - int(w0) for _, w0, w1 in wins)
+        out = torch.empty(W, D, int(wmax), dtype=torch.float32, device=self.device)
+        self._check(self.lib.si_gather_windows(self._h, _ptr(ext), B, Tout, host.ctypes.data_as(C.c_void_p), _ptr(dev), W, int(wmax), _ptr(out),
+                                               self._stream()), "si_gather_windows")
+        return out
+
+    def patch_compose(self, orig: torch.Tensor, spans: "SpanTable", patch: "PatchTable", gen: Optional[torch.Tensor], gain: Optional[torch.Tensor] = None,
+                      sample_len=None, f32: bool = True, pcm: bool = False, out: Optional[torch.Tensor] = None, out_pcm: Optional[torch.Tensor] = None):
+        """orig (B, N22) with the generated rows gen (W, Lrow) cross-faded in around every span (si_patch_compose) -> (fp32 or None,
+        int16 or None), each (B, N22).  gain (B,) fp32 on the device or None; sample_len: host ints of a ragged batch."""
+        assert orig.is_cuda and orig.dtype == torch.float32 and orig.dim() == 2 and orig.is_contiguous()
+        B, N = orig.shape
+        assert gen is None or (gen.is_cuda and gen.dtype == torch.float32 and gen.dim() == 2 and gen.is_contiguous() and gen.shape[0] == patch.W)
+        assert gain is None or (gain.is_cuda and gain.dtype == torch.float32 and gain.numel() == B and gain.is_contiguous())
+        lens = None if sample_len is None else self._host_lens(sample_len, B)
+        if f32 and out is None:
+            out = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        if pcm and out_pcm is None:
+            out_pcm = torch.empty(B, N, dtype=torch.int16, device=self.device)
+        for o, dt in ((out, torch.float32), (out_pcm, torch.int16)):
+            assert o is None or (o.is_cuda and o.dtype == dt and o.is_contiguous() and o.numel() == B * N)
+        ts, tp = spans.struct(), patch.struct()
+        self._check(self.lib.si_patch_compose(self._h, _ptr(orig), C.byref(ts), None if lens is None else lens.ctypes.data_as(C.c_void_p), C.byref(tp),
+                                              _ptr(gen), 0 if gen is None else gen.shape[1], _ptr(gain), B, N, _ptr(out), _ptr(out_pcm), self._stream()),
+                    "si_patch_compose")
+        return out, out_pcm
 
     def _frame_table(self, frame_clip: torch.Tensor, frame_pos: torch.Tensor) -> int:
         for m in (frame_clip, frame_pos):

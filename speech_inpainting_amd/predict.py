@@ -66,7 +66,7 @@ def _one_of(mask_pos, mask_frames, gaps, blind: bool) -> None:
 def predict_clips(engine: InpaintingEngine, waves16: Sequence[np.ndarray], waves22: Sequence[np.ndarray],
                   mask_pos: Optional[Sequence[int]] = None, mask_frames: Optional[int] = None, blind: bool = False,
                   mask22: Optional[Sequence[Tuple[int, int]]] = None, diagnostics: bool = False,
-                  target_labels: Optional[torch.Tensor] = None, gaps=None) -> Dict[str, torch.Tensor]:
+                  target_labels: Optional[torch.Tensor] = None, gaps=None, patch: bool = False, fade: int = 110) -> Dict[str, torch.Tensor]:
     """Batch form of I_ea/predict.py:97-207 for clips of EQUAL length.
     waves16 / waves22: the same clips at 16 kHz / 22.05 kHz (float32, un-normalised), mask_pos: first masked 20 ms frame.
     mask22: per-clip [start, end) of the span zeroed on the 22.05 kHz side (predict.py:99-102: the 16 kHz sample
@@ -77,7 +77,11 @@ def predict_clips(engine: InpaintingEngine, waves16: Sequence[np.ndarray], waves
     codeword metrics of predict.py:171-173 (`loss`, `cos_pred_target`).
     gaps: instead of mask_pos / mask_frames, per clip a list of (first frame, frame count) -- several gaps per clip, different per
     clip, in one pass (engine.predict_multigap_batch).  `labels` is then flat (F,) with `label_off` (B + 1), `target_labels` flat (F,)
-    in the same order, and mask22 per clip a list of [start, end) pairs, one per gap in sorted order."""
+    in the same order, and mask22 per clip a list of [start, end) pairs, one per gap in sorted order.
+    patch=True (not with blind): PATCH MODE -- adds `patched` (B, n22): the caller's own 22.05 kHz samples, bit for bit, outside a
+    cross-fade of `fade` samples around each gap, the generator's audio at the recording's level inside (engine.patch_multigap_batch;
+    the generator then runs only over the windows the gaps need and there is no `wave`, unless diagnostics=True asks for the full
+    passes anyway)."""
     dev = engine.device
     n16, n22 = len(waves16[0]), len(waves22[0])
     if any(len(w) != n16 for w in waves16) or any(len(w) != n22 for w in waves22):
@@ -85,15 +89,23 @@ def predict_clips(engine: InpaintingEngine, waves16: Sequence[np.ndarray], waves
                          "different lengths)")
     wave22 = torch.from_numpy(np.stack([np.asarray(w, dtype=np.float32) for w in waves22])).to(dev)
     wave = torch.from_numpy(np.stack([np.asarray(w, dtype=np.float32) for w in waves16])).to(dev)
-    return predict_resident(engine, wave, wave22, mask_pos, mask_frames, blind, mask22, diagnostics, target_labels, gaps)
+    return predict_resident(engine, wave, wave22, mask_pos, mask_frames, blind, mask22, diagnostics, target_labels, gaps, patch, fade)
 
 
 def _predict_gaps(engine: InpaintingEngine, wave: torch.Tensor, wave22: torch.Tensor, gaps, mask22, diagnostics: bool,
-                  target_labels: Optional[torch.Tensor], len16=None, len22=None) -> Dict[str, object]:
+                  target_labels: Optional[torch.Tensor], len16=None, len22=None, patch: bool = False, fade: int = 110) -> Dict[str, object]:
     """The multi-gap body of predict_resident / predict_clips_ragged.  diagnostics: ONE full generator pass over the masked mel
     (`hifi_masked`); `wave` and `expected_inpaint` come from windowed passes over the merged windows around the gaps
-    (engine.vocode_windows: bit-identical to full passes)."""
-    out = engine.predict_multigap_batch(wave, wave22, gaps, len16=len16, len22=len22, spans22=mask22, vocode=not diagnostics)
+    (engine.vocode_windows: bit-identical to full passes).  patch: `patched` by engine.patch_multigap_batch, or -- with diagnostics,
+    where the full `wave` exists anyway -- by engine.patch_from_wave."""
+    if patch and not diagnostics:
+        return engine.patch_multigap_batch(wave, wave22, gaps, fade=fade, len16=len16, len22=len22, spans22=mask22)
+    tables = None
+    if patch:
+        B = wave.shape[0]
+        tables = engine.gap_tables(gaps, len16 if len16 is not None else [wave.shape[1]] * B, len22 if len22 is not None else [wave22.shape[1]] * B,
+                                   spans22=mask22)
+    out = engine.predict_multigap_batch(wave, wave22, gaps, len16=len16, len22=len22, spans22=mask22, tables=tables, vocode=not diagnostics)
     if not diagnostics:
         return out
     mlen = out["mel_len"] if len16 is not None else None
@@ -108,17 +120,36 @@ def _predict_gaps(engine: InpaintingEngine, wave: torch.Tensor, wave22: torch.Te
         out["expected_inpaint"] = engine.vocode_windows(base, exp, out["gaps"], mlen)
         m = engine.codebook_metrics_spans(out["feats"], out["frame_clip"], out["frame_pos"], tgt)
         out["loss"], out["cos_pred_target"] = m["loss"], m["cos_pred_target"]
+    if patch:
+        out["patched"], _ = engine.patch_from_wave(wave22, out["wave"], tables["tab22"], fade, len22, out.get("wave_len"))
     return out
+
+
+def _patch_args(patch: bool, blind: bool, gaps, mask_pos, mask_frames):
+    """Patch mode's routing: it keeps what lies outside the gaps, so blind mode (every frame replaced) has nothing to keep; a single
+    mask_pos / mask_frames gap is one gap per clip on the multi-gap route."""
+    if not patch:
+        return gaps
+    if blind:
+        raise ValueError("patch=True with blind=True: blind mode replaces every frame, there is nothing of the recording to keep")
+    return gaps if gaps is not None else [[(int(p), int(mask_frames))] for p in mask_pos]
 
 
 def predict_resident(engine: InpaintingEngine, wave: torch.Tensor, wave22: torch.Tensor, mask_pos: Optional[Sequence[int]] = None,
                      mask_frames: Optional[int] = None, blind: bool = False, mask22: Optional[Sequence[Tuple[int, int]]] = None,
-                     diagnostics: bool = False, target_labels: Optional[torch.Tensor] = None, gaps=None) -> Dict[str, torch.Tensor]:
+                     diagnostics: bool = False, target_labels: Optional[torch.Tensor] = None, gaps=None, patch: bool = False,
+                     fade: int = 110) -> Dict[str, torch.Tensor]:
     """`predict_clips` on clips that are already on the GPU: wave (B, n16) / wave22 (B, n22) float32 device tensors (e.g. straight
     out of `engine.resample`); same outputs."""
     _one_of(mask_pos, mask_frames, gaps, blind)
+    if patch and gaps is None and not blind:
+        # one gap per clip on the multi-gap route: mask22 becomes one [start, end) pair per clip's only gap, target labels go flat
+        check_mask_span(engine, wave.shape[1], wave22.shape[1], mask_pos, mask_frames)
+        mask22 = None if mask22 is None else [[m] for m in mask22]
+        target_labels = None if target_labels is None else target_labels.reshape(-1)
+    gaps = _patch_args(patch, blind, gaps, mask_pos, mask_frames)
     if gaps is not None:
-        return _predict_gaps(engine, wave, wave22, gaps, mask22, diagnostics, target_labels)
+        return _predict_gaps(engine, wave, wave22, gaps, mask22, diagnostics, target_labels, patch=patch, fade=fade)
     dev = engine.device
     n16, n22 = wave.shape[1], wave22.shape[1]
     if not blind:
@@ -215,16 +246,23 @@ def pad_stack(waves: Sequence[np.ndarray]) -> Tuple[torch.Tensor, List[int]]:
 def predict_clips_ragged(engine: InpaintingEngine, waves16: Sequence[np.ndarray], waves22: Sequence[np.ndarray],
                          mask_pos: Optional[Sequence[int]] = None, mask_frames: Optional[int] = None, blind: bool = False,
                          mask22: Optional[Sequence[Tuple[int, int]]] = None, gaps=None, diagnostics: bool = False,
-                         target_labels: Optional[torch.Tensor] = None) -> Dict[str, object]:
+                         target_labels: Optional[torch.Tensor] = None, patch: bool = False, fade: int = 110) -> Dict[str, object]:
     """`predict_clips` for clips of DIFFERENT lengths in ONE set of launches (the library's ragged-batch entry points): every
     clip's outputs equal that clip's alone.  Tensors are (B, longest ...); `wave_len`, `frames`, `mel_len` give each clip's extent.
-    gaps (with diagnostics / target_labels): several gaps per clip, as predict_clips."""
+    gaps (with diagnostics / target_labels): several gaps per clip, as predict_clips.  patch / fade: patch mode, as predict_clips
+    (`patched` (B, longest n22); clip b's own samples are its first len(waves22[b]))."""
     dev = engine.device
     _one_of(mask_pos, mask_frames, gaps, blind)
+    if patch and gaps is None and not blind:
+        for i, (a, b) in enumerate(zip(waves16, waves22)):
+            check_mask_span(engine, len(a), len(b), [mask_pos[i]], mask_frames)
+        mask22 = None if mask22 is None else [[m] for m in mask22]
+        target_labels = None if target_labels is None else target_labels.reshape(-1)
+    gaps = _patch_args(patch, blind, gaps, mask_pos, mask_frames)
     if gaps is not None:
         w22, len22 = pad_stack(waves22)
         w16, len16 = pad_stack(waves16)
-        return _predict_gaps(engine, w16.to(dev), w22.to(dev), gaps, mask22, diagnostics, target_labels, len16, len22)
+        return _predict_gaps(engine, w16.to(dev), w22.to(dev), gaps, mask22, diagnostics, target_labels, len16, len22, patch, fade)
     if diagnostics or target_labels is not None:
         raise ValueError("predict_clips_ragged: diagnostics are served on the gaps= route")
     if not blind:
@@ -305,14 +343,19 @@ def main(argv=None) -> int:
     if os.path.exists(labels_path):                                                # predict.py:160-161
         all_labels = torch.load(labels_path, map_location="cpu").t().reshape(-1)
         labels = torch.cat([all_labels[pos:pos + lm] for pos, lm in gap_list]).long()
+    patch = cfg.patch_fade is not None                                             # optional `patch:` mapping: also write patched.wav
+    fade = cfg.patch_fade if patch else 110
     if multi:
-        out = predict_resident(engine, wave_16, wave_22, gaps=[gap_list], mask22=[cfg.spans22], diagnostics=True, target_labels=labels)
+        out = predict_resident(engine, wave_16, wave_22, gaps=[gap_list], mask22=[cfg.spans22], diagnostics=True, target_labels=labels,
+                               patch=patch, fade=fade)
         out["labels"] = out["labels"][None]
     else:
         pos, lm = gap_list[0]
         span22 = (cfg.start_sample * 22050 // 16000, cfg.end_sample * 22050 // 16000)   # predict.py:99-100
         out = predict_resident(engine, wave_16, wave_22, [pos], lm, mask22=[span22], diagnostics=True,
-                               target_labels=None if labels is None else labels[None])
+                               target_labels=None if labels is None else labels[None], patch=patch, fade=fade)
+        if patch:
+            out["labels"] = out["labels"][None]
     pcm = lambda w: engine.to_int16(w[0]).cpu().numpy()                            # predict.py:204-206 on the GPU (si_pcm16)
     # hifi_masked.wav: the vocoder on the masked mel alone (predict.py:123-128)
     audio.write_wav(os.path.join(save_dir, "hifi_masked.wav"), pcm(out["hifi_masked"]), 22050)
@@ -323,6 +366,8 @@ def main(argv=None) -> int:
         print("Target codewords: ", labels.tolist())
     print("Predicted codewords: ", out["labels"][0].tolist())
     audio.write_wav(os.path.join(save_dir, "inpainted.wav"), pcm(out["wave"]), 22050)
+    if patch:                                                                      # the recording itself, only the gaps filled
+        audio.write_wav(os.path.join(save_dir, "patched.wav"), pcm(out["patched"]), 22050)
     print("wrote", save_dir)
     return 0
 

@@ -34,11 +34,14 @@ class Request:
     tag: object = None
     gaps: Optional[Sequence[Sequence[Sequence[int]]]] = None   # per clip a list of (first frame, frame count): several gaps per clip,
                                                                # one pass (replaces mask_pos / mask_frames; not with blind)
+    patch: bool = False                     # patch mode: Result.pcm is the clip's OWN 22.05 kHz samples with only the gaps filled
+    fade: int = 110                         # (cross-fade of `fade` 22.05 kHz samples around each gap); not with blind
 
 
 @dataclass
 class Result:
-    pcm: List[np.ndarray]                   # int16 at 22.05 kHz, one array per clip, cut to the clip's own length
+    pcm: List[np.ndarray]                   # int16 at 22.05 kHz, one array per clip, cut to the clip's own length (the generator's
+                                            # wave_len; with Request.patch the INPUT's 22.05 kHz length len22)
     labels: torch.Tensor                    # (B, Lm) predicted codewords (host); with gaps: flat (F,), clip b = [label_off[b], label_off[b + 1])
     tag: object = None
     label_off: Optional[List[int]] = None
@@ -100,20 +103,32 @@ class RequestFront:
         frames = [eng.ctx.num_frames(n) for n in len16]
         if rq.gaps is not None and rq.blind:
             raise ValueError("Request: blind mode takes no gaps")
+        if rq.patch and rq.blind:
+            raise ValueError("Request: patch=True with blind=True: blind mode replaces every frame, there is nothing of the recording to keep")
+        rq_gaps = rq.gaps
+        if rq.patch and rq_gaps is None:                             # the single gap, as one gap per clip on the multi-gap route
+            rq_gaps = [[(int(p), int(rq.mask_frames))] for p in rq.mask_pos]
         lm = max(min(t, m) for t, m in zip(frames, mel_len)) if rq.blind else int(rq.mask_frames)
         n_tab = 0
         gaps = None
-        if rq.gaps is not None:
+        if rq_gaps is not None:
             # validated BEFORE any slot buffer is sized from them: a refused request (ValueError naming clip and gap) leaves the slot as it was
-            if len(rq.gaps) != B:
-                raise ValueError(f"Request: gaps for {len(rq.gaps)} clips, batch of {B}")
-            gaps = G.normalize_gaps(rq.gaps, [min(t, m) for t, m in zip(frames, mel_len)])
+            if len(rq_gaps) != B:
+                raise ValueError(f"Request: gaps for {len(rq_gaps)} clips, batch of {B}")
+            gaps = G.normalize_gaps(rq_gaps, [min(t, m) for t, m in zip(frames, mel_len)])
             # label buffer: all masked frames of the batch, flat; table buffer: two span tables (off (B + 1), start, len, one spare
             # word each) and the frame table (clip, frame per masked frame)
             F = sum(l for clip in gaps for _, l in clip)
             lm = -(-F // B)
-            n_tab = 2 * (B + 2 + 2 * sum(len(clip) for clip in gaps)) + 2 * F
-        n_wave = eng.ctx.vocoder_samples(max(mel_len), True)
+            S = sum(len(clip) for clip in gaps)
+            n_tab = 2 * (B + 2 + 2 * S) + 2 * F
+            if rq.patch:
+                # the patch tables ride in the same buffer: at most one window per span -- PatchTable (3 W + S + B + fade + 1 words),
+                # the gather's window table (3 W) and the clips' 22.05 kHz lengths (B)
+                if int(rq.fade) < 0:
+                    raise ValueError(f"Request: fade = {rq.fade} samples is negative")
+                n_tab += 7 * S + 2 * B + int(rq.fade) + 1
+        n_wave = max(len22) if rq.patch else eng.ctx.vocoder_samples(max(mel_len), True)
         self._ensure(s, B, n_in, n_wave, lm, n_tab)
         # host -> pinned (zero tail for shorter clips), pinned -> device on the copy stream
         # (numpy views of the pinned buffers: plain memcpy.  torch CPU ops here would each wake the intra-op thread pool, whose
@@ -129,20 +144,27 @@ class RequestFront:
         tables = None
         with torch.cuda.stream(self.h2d):
             raw.copy_(pin, non_blocking=True)
-        if rq.gaps is not None:
+        if rq_gaps is not None:
             # the span tables (16 kHz and 22.05 kHz) and the frame table are validated and built on the host, into the slot's pinned
             # buffer, and cross on the copy stream behind the clips: no copy of this request waits on the compute stream
-            tables = eng.gap_tables(gaps, len16, len22, staging=(s.pin_tab, s.dev_tab, self.h2d))
+            # (patch mode: its window and patch tables too, in the same copy)
+            tables = eng.gap_tables(gaps, len16, len22, staging=(s.pin_tab, s.dev_tab, self.h2d), patch_fade=int(rq.fade) if rq.patch else None)
         s.ev_h2d.record(self.h2d)
         compute.wait_event(s.ev_h2d)
         # librosa.load x 2 (I_ea/predict.py:79-80): the file's samples at 22.05 kHz and at 16 kHz
         w22 = raw if self.sr_in == 22050 else eng.resample(raw, self.sr_in, 22050, lens=lens if ragged else None)
         w16 = raw if self.sr_in == 16000 else eng.resample(raw, self.sr_in, 16000, lens=lens if ragged else None)
-        if rq.gaps is not None:
-            out = eng.predict_multigap_batch(w16, w22, gaps, len16=len16 if ragged else None, len22=len22 if ragged else None,
-                                             tables=tables)
-            wave_len = out["wave_len"] if ragged else [out["wave"].shape[1]] * B
-            pcm = eng.to_int16(out["wave"])
+        if rq_gaps is not None:
+            if rq.patch:
+                # orig = the clip at 22.05 kHz (resampled when the file's rate is another); the int16 conversion is fused into the compose
+                out = eng.patch_multigap_batch(w16, w22, gaps, fade=int(rq.fade), len16=len16 if ragged else None,
+                                               len22=len22 if ragged else None, tables=tables, pcm=True)
+                wave_len, pcm = len22, out["patched_pcm"]
+            else:
+                out = eng.predict_multigap_batch(w16, w22, gaps, len16=len16 if ragged else None, len22=len22 if ragged else None,
+                                                 tables=tables)
+                wave_len = out["wave_len"] if ragged else [out["wave"].shape[1]] * B
+                pcm = eng.to_int16(out["wave"])
             s.ev_done.record(compute)
             self.d2h.wait_event(s.ev_done)
             F = out["labels"].numel()
@@ -151,7 +173,7 @@ class RequestFront:
                 s.pin_lab[:F].copy_(out["labels"], non_blocking=True)
                 s.ev_d2h.record(self.d2h)
             s.keep = (w22, w16, out, pcm)
-            s.meta = dict(B=B, wave_len=wave_len, n_lab=F, n_wave=pcm.shape[1], tag=rq.tag, label_off=out["label_off"])
+            s.meta = dict(B=B, wave_len=wave_len, n_lab=F, n_wave=pcm.shape[1], tag=rq.tag, label_off=out["label_off"], tables=tables)
             return
         pos = torch.tensor([int(p) for p in rq.mask_pos], dtype=torch.int32).to(dev, non_blocking=True)
         if rq.blind:
