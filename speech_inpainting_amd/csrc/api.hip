@@ -1191,102 +1191,90 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     return si_launch_repack_rows(ctx, qkv, out_feats, B, T, d.codebook_dim, d_rowoff, true, st);
 }
 
+// What the seven si_codebook_* entry points require before they launch: a context whose weights are loaded and -- for a blob that was
+// received, not read -- verified; `args_ok`, the call's own NULL / empty check; for a call that writes a mel, centroids as wide as the
+// generator's input.  Selects the context's device.
+static int codebook_enter(si_ctx* ctx, const char* call, bool args_ok, bool writes_mel) {
+    if (!ctx) return SI_EINVAL;
+    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "%s before weights were loaded", call);
+    if (!ctx->weights_verified) if (int rcw = si_weights_check(ctx)) return rcw;
+    if (!args_ok) return si_fail(ctx, SI_EINVAL, "%s: NULL / empty argument", call);
+    if (writes_mel && ctx->d.codebook_dim != ctx->d.num_mels)
+        return si_fail(ctx, SI_EINVAL, "codebook_dim %d != generator input width %d: centroids are not frames of this generator's input",
+                       ctx->d.codebook_dim, ctx->d.num_mels);
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    return SI_OK;
+}
+
+static int codebook_splice(si_ctx* ctx, const float* feats, int B, int T, const si_cb_frames& fr, float* mel, int Tm, int64_t* labels,
+                           si_stream_t stream) {
+    const Layout& L = ctx->lay;
+    return si_launch_codebook_splice(ctx, feats, B, T, ctx->d.codebook_dim, fr, wf(ctx, L.cb_centered), wf(ctx, L.cb_raw), wf(ctx, L.cb_rnorm),
+                                     ctx->d.num_clusters, mel, Tm, labels, static_cast<hipStream_t>(stream));
+}
+
+static int codebook_gather(si_ctx* ctx, const int64_t* labels, int B, const si_cb_frames& fr, float* mel, int Tm, si_stream_t stream) {
+    return si_launch_codebook_gather(ctx, labels, B, ctx->d.codebook_dim, fr, wf(ctx, ctx->lay.cb_raw), ctx->d.num_clusters, mel, Tm,
+                                     static_cast<hipStream_t>(stream));
+}
+
+static int codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, const si_cb_frames& fr, const int64_t* target_labels,
+                            float* loss_terms, float* loss, int64_t* pred_labels, float* cos_pred_target, si_stream_t stream) {
+    const Layout& L = ctx->lay;
+    return si_launch_codebook_metrics(ctx, feats, B, T, ctx->d.codebook_dim, fr, wf(ctx, L.cb_centered), wf(ctx, L.cb_rnorm), ctx->d.num_clusters,
+                                      target_labels, loss_terms, loss, pred_labels, cos_pred_target, static_cast<hipStream_t>(stream));
+}
+
 extern "C" {
 
 int si_codebook_splice(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_pos, int Lm, float* mel, int Tm,
                        int64_t* labels, si_stream_t stream) {
-    if (!ctx) return SI_EINVAL;
-    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_splice before weights were loaded");
-    if (!ctx->weights_verified) if (int rcw = si_weights_check(ctx)) return rcw;
-    if (!feats || !frame_pos || !mel || B <= 0 || Lm < 0) return si_fail(ctx, SI_EINVAL, "si_codebook_splice: NULL / empty argument");
-    if (ctx->d.codebook_dim != ctx->d.num_mels)
-        return si_fail(ctx, SI_EINVAL, "codebook_dim %d != generator input width %d: centroids are not frames of this generator's input",
-                       ctx->d.codebook_dim, ctx->d.num_mels);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    const Layout& L = ctx->lay;
-    return si_launch_codebook_splice(ctx, feats, B, T, ctx->d.codebook_dim, frame_pos, Lm, wf(ctx, L.cb_centered), wf(ctx, L.cb_raw),
-                                     wf(ctx, L.cb_rnorm), ctx->d.num_clusters, mel, Tm, labels, static_cast<hipStream_t>(stream));
+    if (int rc = codebook_enter(ctx, "si_codebook_splice", feats && frame_pos && mel && B > 0 && Lm >= 0, true)) return rc;
+    return codebook_splice(ctx, feats, B, T, si_cb_frames::grid(frame_pos, Lm), mel, Tm, labels, stream);
 }
 
 int si_codebook_splice_varlen(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_pos, const int32_t* frame_cnt, int Lm,
                               float* mel, int Tm, int64_t* labels, si_stream_t stream) {
-    if (!ctx) return SI_EINVAL;
-    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_splice_varlen before weights were loaded");
-    if (!feats || !frame_pos || !frame_cnt || !mel || B <= 0 || Lm < 0) return si_fail(ctx, SI_EINVAL, "si_codebook_splice_varlen: NULL / empty argument");
-    if (ctx->d.codebook_dim != ctx->d.num_mels)
-        return si_fail(ctx, SI_EINVAL, "codebook_dim %d != generator input width %d", ctx->d.codebook_dim, ctx->d.num_mels);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    const Layout& L = ctx->lay;
-    return si_launch_codebook_splice(ctx, feats, B, T, ctx->d.codebook_dim, frame_pos, Lm, wf(ctx, L.cb_centered), wf(ctx, L.cb_raw),
-                                     wf(ctx, L.cb_rnorm), ctx->d.num_clusters, mel, Tm, labels, static_cast<hipStream_t>(stream), frame_cnt);
+    if (int rc = codebook_enter(ctx, "si_codebook_splice_varlen", feats && frame_pos && frame_cnt && mel && B > 0 && Lm >= 0, true)) return rc;
+    return codebook_splice(ctx, feats, B, T, si_cb_frames::grid(frame_pos, Lm, frame_cnt), mel, Tm, labels, stream);
+}
+
+int si_codebook_splice_spans(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                             float* mel, int Tm, int64_t* labels, si_stream_t stream) {
+    const bool args_ok = feats && mel && B > 0 && T > 0 && Tm > 0 && F >= 0 && (F == 0 || (frame_clip && frame_pos));
+    if (int rc = codebook_enter(ctx, "si_codebook_splice_spans", args_ok, true)) return rc;
+    return codebook_splice(ctx, feats, B, T, si_cb_frames::of_table(frame_clip, frame_pos, F), mel, Tm, labels, stream);
 }
 
 int si_codebook_splice_labels(si_ctx* ctx, const int64_t* labels, int B, const int32_t* frame_pos, int Lm, float* mel, int Tm,
                               si_stream_t stream) {
-    if (!ctx) return SI_EINVAL;
-    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_splice_labels before weights were loaded");
-    if (!labels || !frame_pos || !mel || B <= 0 || Lm < 0) return si_fail(ctx, SI_EINVAL, "si_codebook_splice_labels: NULL / empty argument");
-    if (ctx->d.codebook_dim != ctx->d.num_mels)
-        return si_fail(ctx, SI_EINVAL, "codebook_dim %d != generator input width %d", ctx->d.codebook_dim, ctx->d.num_mels);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    return si_launch_codebook_gather(ctx, labels, B, ctx->d.codebook_dim, frame_pos, Lm, wf(ctx, ctx->lay.cb_raw), ctx->d.num_clusters,
-                                     mel, Tm, static_cast<hipStream_t>(stream));
+    if (int rc = codebook_enter(ctx, "si_codebook_splice_labels", labels && frame_pos && mel && B > 0 && Lm >= 0, true)) return rc;
+    return codebook_gather(ctx, labels, B, si_cb_frames::grid(frame_pos, Lm), mel, Tm, stream);
+}
+
+int si_codebook_splice_labels_spans(si_ctx* ctx, const int64_t* labels, int B, const int32_t* frame_clip, const int32_t* frame_pos, int F,
+                                    float* mel, int Tm, si_stream_t stream) {
+    const bool args_ok = mel && B > 0 && Tm > 0 && F >= 0 && (F == 0 || (labels && frame_clip && frame_pos));
+    if (int rc = codebook_enter(ctx, "si_codebook_splice_labels_spans", args_ok, true)) return rc;
+    return codebook_gather(ctx, labels, B, si_cb_frames::of_table(frame_clip, frame_pos, F), mel, Tm, stream);
 }
 
 int si_codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_pos, int Lm,
                         const int64_t* target_labels, float* loss_terms, float* loss, int64_t* pred_labels, float* cos_pred_target,
                         si_stream_t stream) {
-    if (!ctx) return SI_EINVAL;
-    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_metrics before weights were loaded");
-    if (!feats || !frame_pos || !target_labels || !loss_terms || !loss || !cos_pred_target || B <= 0 || Lm <= 0)
-        return si_fail(ctx, SI_EINVAL, "si_codebook_metrics: NULL / empty argument");
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    const Layout& L = ctx->lay;
-    return si_launch_codebook_metrics(ctx, feats, B, T, ctx->d.codebook_dim, frame_pos, Lm, wf(ctx, L.cb_centered), wf(ctx, L.cb_rnorm),
-                                      ctx->d.num_clusters, target_labels, loss_terms, loss, pred_labels, cos_pred_target,
-                                      static_cast<hipStream_t>(stream));
-}
-
-int si_codebook_splice_spans(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_clip, const int32_t* frame_pos, int F,
-                             float* mel, int Tm, int64_t* labels, si_stream_t stream) {
-    if (!ctx) return SI_EINVAL;
-    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_splice_spans before weights were loaded");
-    if (!ctx->weights_verified) if (int rcw = si_weights_check(ctx)) return rcw;
-    if (!feats || !mel || B <= 0 || T <= 0 || Tm <= 0 || F < 0 || (F > 0 && (!frame_clip || !frame_pos)))
-        return si_fail(ctx, SI_EINVAL, "si_codebook_splice_spans: NULL / empty argument");
-    if (ctx->d.codebook_dim != ctx->d.num_mels)
-        return si_fail(ctx, SI_EINVAL, "codebook_dim %d != generator input width %d", ctx->d.codebook_dim, ctx->d.num_mels);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    const Layout& L = ctx->lay;
-    return si_launch_codebook_splice_spans(ctx, feats, B, T, ctx->d.codebook_dim, frame_clip, frame_pos, F, wf(ctx, L.cb_centered), wf(ctx, L.cb_raw),
-                                           wf(ctx, L.cb_rnorm), ctx->d.num_clusters, mel, Tm, labels, static_cast<hipStream_t>(stream));
-}
-
-int si_codebook_splice_labels_spans(si_ctx* ctx, const int64_t* labels, int B, const int32_t* frame_clip, const int32_t* frame_pos, int F,
-                                    float* mel, int Tm, si_stream_t stream) {
-    if (!ctx) return SI_EINVAL;
-    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_splice_labels_spans before weights were loaded");
-    if (!mel || B <= 0 || Tm <= 0 || F < 0 || (F > 0 && (!labels || !frame_clip || !frame_pos)))
-        return si_fail(ctx, SI_EINVAL, "si_codebook_splice_labels_spans: NULL / empty argument");
-    if (ctx->d.codebook_dim != ctx->d.num_mels)
-        return si_fail(ctx, SI_EINVAL, "codebook_dim %d != generator input width %d", ctx->d.codebook_dim, ctx->d.num_mels);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    return si_launch_codebook_gather_spans(ctx, labels, B, ctx->d.codebook_dim, frame_clip, frame_pos, F, wf(ctx, ctx->lay.cb_raw),
-                                           ctx->d.num_clusters, mel, Tm, static_cast<hipStream_t>(stream));
+    const bool args_ok = feats && frame_pos && target_labels && loss_terms && loss && cos_pred_target && B > 0 && Lm > 0;
+    if (int rc = codebook_enter(ctx, "si_codebook_metrics", args_ok, false)) return rc;
+    return codebook_metrics(ctx, feats, B, T, si_cb_frames::grid(frame_pos, Lm), target_labels, loss_terms, loss, pred_labels, cos_pred_target,
+                            stream);
 }
 
 int si_codebook_metrics_spans(si_ctx* ctx, const float* feats, int B, int T, const int32_t* frame_clip, const int32_t* frame_pos, int F,
                               const int64_t* target_labels, float* loss_terms, float* loss, int64_t* pred_labels, float* cos_pred_target,
                               si_stream_t stream) {
-    if (!ctx) return SI_EINVAL;
-    if (!ctx->weights_ready) return si_fail(ctx, SI_ESTATE, "si_codebook_metrics_spans before weights were loaded");
-    if (!feats || !frame_clip || !frame_pos || !target_labels || !loss_terms || !loss || !cos_pred_target || B <= 0 || T <= 0 || F <= 0)
-        return si_fail(ctx, SI_EINVAL, "si_codebook_metrics_spans: NULL / empty argument");
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    const Layout& L = ctx->lay;
-    return si_launch_codebook_metrics_spans(ctx, feats, B, T, ctx->d.codebook_dim, frame_clip, frame_pos, F, wf(ctx, L.cb_centered), wf(ctx, L.cb_rnorm),
-                                            ctx->d.num_clusters, target_labels, loss_terms, loss, pred_labels, cos_pred_target,
-                                            static_cast<hipStream_t>(stream));
+    const bool args_ok = feats && frame_clip && frame_pos && target_labels && loss_terms && loss && cos_pred_target && B > 0 && T > 0 && F > 0;
+    if (int rc = codebook_enter(ctx, "si_codebook_metrics_spans", args_ok, false)) return rc;
+    return codebook_metrics(ctx, feats, B, T, si_cb_frames::of_table(frame_clip, frame_pos, F), target_labels, loss_terms, loss, pred_labels,
+                            cos_pred_target, stream);
 }
 
 int si_kmeans_assign(si_ctx* ctx, const float* feats, int64_t rows, int D, const float* centroids, int K, int64_t* labels,

@@ -254,30 +254,32 @@ int si_launch_frame_lengths(si_ctx* ctx, const int32_t* valid_len, int B, int nc
 // x[b][t][:] = 0 for t >= valid_frames[b] (padded frames of the projected states, modeling_hubert.py:428-431)
 int si_launch_zero_padded_rows(si_ctx* ctx, float* x, int B, int T, int H, const int32_t* valid_frames, hipStream_t st);
 
+// Which frames a codebook call works on.  GRID form: frames frame_pos[b] + [0, n) of every clip, outputs (B, n); frame_cnt (B) or null:
+// frames replaced per clip (ragged batches), <= n.  TABLE form (multi-gap masks): n entries, entry f = frame frame_pos[f] of clip
+// frame_clip[f]; labels / target / terms / pred / cos_pt are flat (n), in table order.  All arrays are device int32.
+struct si_cb_frames {
+    bool table;
+    const int32_t* frame_clip;
+    const int32_t* frame_pos;
+    const int32_t* frame_cnt;
+    int n;
+    static si_cb_frames grid(const int32_t* frame_pos, int Lm, const int32_t* frame_cnt = nullptr) { return {false, nullptr, frame_pos, frame_cnt, Lm}; }
+    static si_cb_frames of_table(const int32_t* frame_clip, const int32_t* frame_pos, int F) { return {true, frame_clip, frame_pos, nullptr, F}; }
+    long frames(int B) const { return table ? (long)n : (long)B * n; }
+};
+
 // cosine arg-max against centred centroids + splice of the raw centroid into mel (A10..A13)
-int si_launch_codebook_splice(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_pos, int Lm,
-                              const float* cb_centered /*K x D*/, const float* cb_raw /*K x D*/,
-                              const float* cb_rnorm /*K*/, int K, float* mel, int Tm, int64_t* labels, hipStream_t st,
-                              const int32_t* frame_cnt = nullptr /* (B): frames replaced per clip (ragged batches), <= Lm */);
+int si_launch_codebook_splice(si_ctx* ctx, const float* feats, int B, int T, int D, const si_cb_frames& fr, const float* cb_centered /*K x D*/,
+                              const float* cb_raw /*K x D*/, const float* cb_rnorm /*K*/, int K, float* mel, int Tm, int64_t* labels,
+                              hipStream_t st);
 
 // out[b][t] = (t < first[b] || t >= last[b]) ? clean[b][t] : masked[b][t]  (I_da/scripts/inpainting.py:209-214)
 int si_launch_code_splice(si_ctx* ctx, const int64_t* clean, const int64_t* masked, const int32_t* first, const int32_t* last, int B, int T,
                           int64_t* out, hipStream_t st);
 
-// mel[b, :, pos_b + j] = cb_raw[labels[b, j]] (the expected_inpaint splice, I_ea/predict.py:177-189)
-int si_launch_codebook_gather(si_ctx* ctx, const int64_t* labels, int B, int D, const int32_t* frame_pos, int Lm,
-                              const float* cb_raw, int K, float* mel, int Tm, hipStream_t st);
-
-// The three codebook calls over a FRAME TABLE (multi-gap masks): entry f < F = frame frame_pos[f] of clip frame_clip[f] (device int32);
-// labels / target / terms / pred / cos_pt are flat (F), in table order
-int si_launch_codebook_splice_spans(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_clip, const int32_t* frame_pos,
-                                    int F, const float* cb_centered, const float* cb_raw, const float* cb_rnorm, int K, float* mel, int Tm,
-                                    int64_t* labels, hipStream_t st);
-int si_launch_codebook_gather_spans(si_ctx* ctx, const int64_t* labels, int B, int D, const int32_t* frame_clip, const int32_t* frame_pos, int F,
-                                    const float* cb_raw, int K, float* mel, int Tm, hipStream_t st);
-int si_launch_codebook_metrics_spans(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_clip, const int32_t* frame_pos,
-                                     int F, const float* cb_centered, const float* cb_rnorm, int K, const int64_t* target, float* terms,
-                                     float* loss, int64_t* pred, float* cos_pt, hipStream_t st);
+// mel[b, :, pos] = cb_raw[label] for every frame of `fr` (the expected_inpaint splice, I_ea/predict.py:177-189)
+int si_launch_codebook_gather(si_ctx* ctx, const int64_t* labels, int B, int D, const si_cb_frames& fr, const float* cb_raw, int K, float* mel,
+                              int Tm, hipStream_t st);
 
 // k-means unit assignment: labels[row] = argmin_k ||x_row - c_k||^2 (first minimum); dist (optional) = that squared distance
 // cnorm_scratch (K floats, device) or null: with it (and D % 32 == 0) the distance GEMM runs on the matrix pipe (exact-fp32 MFMA)
@@ -286,9 +288,9 @@ int si_launch_kmeans_assign(si_ctx* ctx, const float* x, long rows, int D, const
 
 // loss half of LossFunction.cos_sim + cos_sim_target_labels (f-4): per-frame terms 1 - cos(v, c_target), their
 // fixed-order sum, arg-max labels and cos(c_pred, c_target)
-int si_launch_codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_pos, int Lm,
-                               const float* cb_centered, const float* cb_rnorm, int K, const int64_t* target, float* terms,
-                               float* loss, int64_t* pred, float* cos_pt, hipStream_t st);
+int si_launch_codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, int D, const si_cb_frames& fr, const float* cb_centered,
+                               const float* cb_rnorm, int K, const int64_t* target, float* terms, float* loss, int64_t* pred, float* cos_pt,
+                               hipStream_t st);
 
 // mel-domain and waveform metrics (metrics_kernels.hip; I_ea/metrics.py:38-62,127-142)
 int si_launch_mel_metrics(si_ctx* ctx, const float* a, const float* b, int B, int D, int L, const float* center, float* out, hipStream_t st);

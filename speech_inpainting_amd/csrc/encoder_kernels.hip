@@ -1104,32 +1104,116 @@ __device__ __forceinline__ int codebook_argmax_128(const float* v, int D, const 
     return min(lab, K - 1);                                          // K >= 1: thread 0 always holds a real index
 }
 
-// One workgroup per (clip, masked frame).  D <= 128.
-// frame_cnt (B) or null: ragged batches -- clip b replaces frame_cnt[b] frames (blind mode: all of ITS frames); j past it is label -1
-__global__ __launch_bounds__(128) void codebook_splice_kernel(const float* __restrict__ feats, int T, int D,
-                                                              const int32_t* __restrict__ frame_pos, int Lm,
-                                                              const float* __restrict__ cc, const float* __restrict__ raw,
-                                                              const float* __restrict__ rnorm, int K, float* __restrict__ mel,
-                                                              int Tm, int64_t* __restrict__ labels, const int32_t* __restrict__ frame_cnt) {
+// Which frame a workgroup of the codebook kernels works on: frame `pos` of clip b, outputs at flat index o; !ok = no such frame.
+struct CbFrame { int b, pos; long o; bool ok; };
+// GRID form, grid (Lm, B): frame j of clip b is frame_pos[b] + j, outputs (B, Lm).  frame_cnt (B) or null: ragged batches -- clip b
+// replaces frame_cnt[b] frames (blind mode: all of ITS frames); j past it is no frame
+struct CbGridFrames {
+    const int32_t* frame_pos; const int32_t* frame_cnt; int Lm;
+    __device__ __forceinline__ CbFrame frame() const {
+        const int b = blockIdx.y, j = blockIdx.x;
+        return {b, frame_pos[b] + j, (long)b * Lm + j, !(frame_cnt && j >= frame_cnt[b])};
+    }
+};
+// TABLE form (multi-gap masks), grid (F): entry f = frame frame_pos[f] of clip frame_clip[f], flattened over all gaps of all clips;
+// outputs flat (F) in table order; an entry whose clip lies outside the batch is no frame
+struct CbTableFrames {
+    const int32_t* frame_clip; const int32_t* frame_pos; int B;
+    __device__ __forceinline__ CbFrame frame() const {
+        const int f = blockIdx.x, b = frame_clip[f];
+        return {b, frame_pos[f], f, b >= 0 && b < B};
+    }
+};
+// the launch of one codebook operation in the form `fr` asks for
+template <class GridKernel, class TableKernel, class... Args>
+static void codebook_launch(GridKernel grid_kernel, TableKernel table_kernel, const si_cb_frames& fr, int B, hipStream_t st, Args... args) {
+    if (fr.table) hipLaunchKernelGGL(table_kernel, dim3(fr.n), dim3(128), 0, st, CbTableFrames{fr.frame_clip, fr.frame_pos, B}, args...);
+    else hipLaunchKernelGGL(grid_kernel, dim3(fr.n, B), dim3(128), 0, st, CbGridFrames{fr.frame_pos, fr.frame_cnt, fr.n}, args...);
+}
+
+// One workgroup per masked frame.  D <= 128.  Both forms are this body, in this operation order: a frame's label and spliced column
+// have the same bits whichever form decided them.  labels (optional): -1 where there is no such encoder frame.
+template <class Frames>
+__device__ __forceinline__ void codebook_splice_frame(const Frames& frames, const float* __restrict__ feats, int T, int D,
+                                                      const float* __restrict__ cc, const float* __restrict__ raw,
+                                                      const float* __restrict__ rnorm, int K, float* __restrict__ mel, int Tm,
+                                                      int64_t* __restrict__ labels) {
     __shared__ float v[128];
     __shared__ float bs[2];
     __shared__ int bi[2];
-    const int b = blockIdx.y, j = blockIdx.x;
-    const int pos = frame_pos[b] + j;
-    if (pos < 0 || pos >= T || (frame_cnt && j >= frame_cnt[b])) {   // uniform per block: no such encoder frame
-        if (threadIdx.x == 0 && labels) labels[(long)b * Lm + j] = -1;
+    const CbFrame fr = frames.frame();
+    if (!fr.ok || fr.pos < 0 || fr.pos >= T) {                       // uniform per block
+        if (threadIdx.x == 0 && labels) labels[fr.o] = -1;
         return;
     }
-    const float* f = feats + ((long)b * T + pos) * D;
+    const float* f = feats + ((long)fr.b * T + fr.pos) * D;
     if ((int)threadIdx.x < D) v[threadIdx.x] = f[threadIdx.x];
     __syncthreads();
     const int lab = codebook_argmax_128(v, D, cc, rnorm, K, bs, bi);
-    if (threadIdx.x == 0 && labels) labels[(long)b * Lm + j] = lab;
-    if (pos < Tm && (int)threadIdx.x < D) mel[((long)b * D + threadIdx.x) * Tm + pos] = raw[(long)lab * D + threadIdx.x];
+    if (threadIdx.x == 0 && labels) labels[fr.o] = lab;
+    if (fr.pos < Tm && (int)threadIdx.x < D) mel[((long)fr.b * D + threadIdx.x) * Tm + fr.pos] = raw[(long)lab * D + threadIdx.x];
+}
+
+__global__ __launch_bounds__(128) void codebook_splice_kernel(CbGridFrames frames, const float* __restrict__ feats, int T, int D,
+                                                              const float* __restrict__ cc, const float* __restrict__ raw,
+                                                              const float* __restrict__ rnorm, int K, float* __restrict__ mel,
+                                                              int Tm, int64_t* __restrict__ labels) {
+    codebook_splice_frame(frames, feats, T, D, cc, raw, rnorm, K, mel, Tm, labels);
+}
+
+__global__ __launch_bounds__(128) void codebook_splice_spans_kernel(CbTableFrames frames, const float* __restrict__ feats, int T, int D,
+                                                                    const float* __restrict__ cc, const float* __restrict__ raw,
+                                                                    const float* __restrict__ rnorm, int K, float* __restrict__ mel,
+                                                                    int Tm, int64_t* __restrict__ labels) {
+    codebook_splice_frame(frames, feats, T, D, cc, raw, rnorm, K, mel, Tm, labels);
+}
+
+int si_launch_codebook_splice(si_ctx* ctx, const float* feats, int B, int T, int D, const si_cb_frames& fr, const float* cb_centered,
+                              const float* cb_raw, const float* cb_rnorm, int K, float* mel, int Tm, int64_t* labels, hipStream_t st) {
+    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
+    if (B <= 0 || fr.n <= 0) return SI_OK;
+    const double F = (double)fr.frames(B);
+    si_prof_begin(ctx, fr.table ? "codebook_splice_spans" : "codebook_splice", 2.0 * F * (double)K * D, 4.0 * F * 2.0 * D, st);
+    codebook_launch(codebook_splice_kernel, codebook_splice_spans_kernel, fr, B, st, feats, T, D, cb_centered, cb_raw, cb_rnorm, K, mel, Tm,
+                    labels);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+// expected_inpaint splice: given labels -> raw centroids into the mel (I_ea/predict.py:177-189)
+template <class Frames>
+__device__ __forceinline__ void codebook_gather_frame(const Frames& frames, const int64_t* __restrict__ labels, int D,
+                                                      const float* __restrict__ raw, int K, float* __restrict__ mel, int Tm) {
+    const CbFrame fr = frames.frame();
+    const long lab = labels[fr.o];
+    if (!fr.ok || fr.pos < 0 || fr.pos >= Tm || lab < 0 || lab >= K) return;
+    if ((int)threadIdx.x < D) mel[((long)fr.b * D + threadIdx.x) * Tm + fr.pos] = raw[lab * D + threadIdx.x];
+}
+
+__global__ __launch_bounds__(128) void codebook_gather_kernel(CbGridFrames frames, const int64_t* __restrict__ labels, int D,
+                                                              const float* __restrict__ raw, int K, float* __restrict__ mel, int Tm) {
+    codebook_gather_frame(frames, labels, D, raw, K, mel, Tm);
+}
+
+__global__ __launch_bounds__(128) void codebook_gather_spans_kernel(CbTableFrames frames, const int64_t* __restrict__ labels, int D,
+                                                                    const float* __restrict__ raw, int K, float* __restrict__ mel, int Tm) {
+    codebook_gather_frame(frames, labels, D, raw, K, mel, Tm);
+}
+
+int si_launch_codebook_gather(si_ctx* ctx, const int64_t* labels, int B, int D, const si_cb_frames& fr, const float* cb_raw, int K,
+                              float* mel, int Tm, hipStream_t st) {
+    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
+    if (B <= 0 || fr.n <= 0) return SI_OK;
+    si_prof_begin(ctx, fr.table ? "codebook_gather_spans" : "codebook_gather", 0.0, 8.0 * (double)fr.frames(B) * D, st);
+    codebook_launch(codebook_gather_kernel, codebook_gather_spans_kernel, fr, B, st, labels, D, cb_raw, K, mel, Tm);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
 }
 
 // Loss half of LossFunction.cos_sim + cos_sim_target_labels (I_ea/loss_fn.py:29-62).
-// One workgroup per (clip, masked frame): term = 1 - cos(v, c_target), pred = arg-max_k cos(v, c_k) (same rule as the
+// One workgroup per masked frame, in either form: term = 1 - cos(v, c_target), pred = arg-max_k cos(v, c_k) (same rule as the
 // splice kernel), cpt = cos(c_pred, c_target); all cosines as F.cosine_similarity computes them: both vectors divided
 // by max(norm, 1e-8) first, then the dot product.  A target label outside [0, K) yields NaN in both outputs.
 __device__ __forceinline__ float block_sum_128(float x, float* scratch) {
@@ -1141,8 +1225,8 @@ __device__ __forceinline__ float block_sum_128(float x, float* scratch) {
     return scratch[0] + scratch[1];
 }
 
-// one frame of it: frame `pos` of clip b, outputs at flat index o
-__device__ __forceinline__ void codebook_metrics_frame(const float* __restrict__ feats, int T, int D, int b, int pos, long o,
+template <class Frames>
+__device__ __forceinline__ void codebook_metrics_frame(const Frames& frames, const float* __restrict__ feats, int T, int D,
                                                        const float* __restrict__ cc, const float* __restrict__ rnorm, int K,
                                                        const int64_t* __restrict__ target, float* __restrict__ terms,
                                                        int64_t* __restrict__ pred, float* __restrict__ cos_pt) {
@@ -1150,14 +1234,16 @@ __device__ __forceinline__ void codebook_metrics_frame(const float* __restrict__
     __shared__ float red[2];
     __shared__ float bs[2];
     __shared__ int bi[2];
+    const CbFrame fr = frames.frame();
+    const long o = fr.o;
     const long y = target[o];
     const float nanv = __builtin_nanf("");
-    if (pos < 0 || pos >= T || y < 0 || y >= K) {                    // uniform per block
+    if (!fr.ok || fr.pos < 0 || fr.pos >= T || y < 0 || y >= K) {    // uniform per block
         if (threadIdx.x == 0) { terms[o] = nanv; cos_pt[o] = nanv; if (pred) pred[o] = -1; }
         return;
     }
     const int d = threadIdx.x;
-    const float* f = feats + ((long)b * T + pos) * D;
+    const float* f = feats + ((long)fr.b * T + fr.pos) * D;
     const float vd = d < D ? f[d] : 0.f;
     v[d] = vd;
     const float* ct = cc + y * D;
@@ -1177,26 +1263,19 @@ __device__ __forceinline__ void codebook_metrics_frame(const float* __restrict__
     }
 }
 
-
-__global__ __launch_bounds__(128) void codebook_metrics_kernel(const float* __restrict__ feats, int T, int D,
-                                                               const int32_t* __restrict__ frame_pos, int Lm,
+__global__ __launch_bounds__(128) void codebook_metrics_kernel(CbGridFrames frames, const float* __restrict__ feats, int T, int D,
                                                                const float* __restrict__ cc, const float* __restrict__ rnorm,
                                                                int K, const int64_t* __restrict__ target,
                                                                float* __restrict__ terms, int64_t* __restrict__ pred,
                                                                float* __restrict__ cos_pt) {
-    const int b = blockIdx.y, j = blockIdx.x;
-    codebook_metrics_frame(feats, T, D, b, frame_pos[b] + j, (long)b * Lm + j, cc, rnorm, K, target, terms, pred, cos_pt);
+    codebook_metrics_frame(frames, feats, T, D, cc, rnorm, K, target, terms, pred, cos_pt);
 }
 
-// The same per entry of a FRAME TABLE (multi-gap masks): entry f = frame frame_pos[f] of clip frame_clip[f]; outputs flat (F) in table order.
-__global__ __launch_bounds__(128) void codebook_metrics_spans_kernel(const float* __restrict__ feats, int B, int T, int D,
-                                                                     const int32_t* __restrict__ frame_clip, const int32_t* __restrict__ frame_pos,
+__global__ __launch_bounds__(128) void codebook_metrics_spans_kernel(CbTableFrames frames, const float* __restrict__ feats, int T, int D,
                                                                      const float* __restrict__ cc, const float* __restrict__ rnorm, int K,
                                                                      const int64_t* __restrict__ target, float* __restrict__ terms,
                                                                      int64_t* __restrict__ pred, float* __restrict__ cos_pt) {
-    const int f = blockIdx.x, b = frame_clip[f];
-    const bool clip_ok = b >= 0 && b < B;
-    codebook_metrics_frame(feats, T, D, clip_ok ? b : 0, clip_ok ? frame_pos[f] : -1, f, cc, rnorm, K, target, terms, pred, cos_pt);
+    codebook_metrics_frame(frames, feats, T, D, cc, rnorm, K, target, terms, pred, cos_pt);
 }
 
 // loss = sum of the per-frame terms, in a fixed order (deterministic): double partials, tree over 256 threads
@@ -1213,29 +1292,16 @@ __global__ __launch_bounds__(256) void sum_terms_kernel(const float* __restrict_
     if (threadIdx.x == 0) out[0] = (float)part[0];
 }
 
-int si_launch_codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_pos, int Lm,
-                               const float* cb_centered, const float* cb_rnorm, int K, const int64_t* target, float* terms,
-                               float* loss, int64_t* pred, float* cos_pt, hipStream_t st) {
+int si_launch_codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, int D, const si_cb_frames& fr, const float* cb_centered,
+                               const float* cb_rnorm, int K, const int64_t* target, float* terms, float* loss, int64_t* pred, float* cos_pt,
+                               hipStream_t st) {
     if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
-    if (B <= 0 || Lm <= 0) return SI_OK;
-    si_prof_begin(ctx, "codebook_metrics", 2.0 * B * Lm * (double)K * D, 4.0 * B * Lm * 2.0 * D, st);
-    hipLaunchKernelGGL(codebook_metrics_kernel, dim3(Lm, B), dim3(128), 0, st, feats, T, D, frame_pos, Lm, cb_centered, cb_rnorm, K,
-                       target, terms, pred, cos_pt);
-    hipLaunchKernelGGL(sum_terms_kernel, dim3(1), dim3(256), 0, st, terms, (long)B * Lm, loss);
-    si_prof_end(ctx, st);
-    SI_HIP_CHECK(hipGetLastError());
-    return SI_OK;
-}
-
-int si_launch_codebook_metrics_spans(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_clip, const int32_t* frame_pos,
-                                     int F, const float* cb_centered, const float* cb_rnorm, int K, const int64_t* target, float* terms,
-                                     float* loss, int64_t* pred, float* cos_pt, hipStream_t st) {
-    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
-    if (B <= 0 || F <= 0) return SI_OK;
-    si_prof_begin(ctx, "codebook_metrics_spans", 2.0 * F * (double)K * D, 4.0 * F * 2.0 * D, st);
-    hipLaunchKernelGGL(codebook_metrics_spans_kernel, dim3(F), dim3(128), 0, st, feats, B, T, D, frame_clip, frame_pos, cb_centered, cb_rnorm, K,
-                       target, terms, pred, cos_pt);
-    hipLaunchKernelGGL(sum_terms_kernel, dim3(1), dim3(256), 0, st, terms, (long)F, loss);
+    if (B <= 0 || fr.n <= 0) return SI_OK;
+    const double F = (double)fr.frames(B);
+    si_prof_begin(ctx, fr.table ? "codebook_metrics_spans" : "codebook_metrics", 2.0 * F * (double)K * D, 4.0 * F * 2.0 * D, st);
+    codebook_launch(codebook_metrics_kernel, codebook_metrics_spans_kernel, fr, B, st, feats, T, D, cb_centered, cb_rnorm, K, target, terms,
+                    pred, cos_pt);
+    hipLaunchKernelGGL(sum_terms_kernel, dim3(1), dim3(256), 0, st, terms, fr.frames(B), loss);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;
@@ -1413,96 +1479,3 @@ int si_launch_code_splice(si_ctx* ctx, const int64_t* clean, const int64_t* mask
     return SI_OK;
 }
 
-// expected_inpaint splice: given labels -> raw centroids into the mel (I_ea/predict.py:177-189)
-__global__ __launch_bounds__(128) void codebook_gather_kernel(const int64_t* __restrict__ labels, int D,
-                                                              const int32_t* __restrict__ frame_pos, int Lm,
-                                                              const float* __restrict__ raw, int K, float* __restrict__ mel, int Tm) {
-    const int b = blockIdx.y, j = blockIdx.x;
-    const int pos = frame_pos[b] + j;
-    const long lab = labels[(long)b * Lm + j];
-    if (pos < 0 || pos >= Tm || lab < 0 || lab >= K) return;
-    if ((int)threadIdx.x < D) mel[((long)b * D + threadIdx.x) * Tm + pos] = raw[lab * D + threadIdx.x];
-}
-
-// Multi-gap masks: the two splices per entry of a FRAME TABLE -- entry f = frame frame_pos[f] of clip frame_clip[f], flattened over all
-// gaps of all clips -- with a grid over the F entries.  The arg-max and the centroid write are codebook_splice_kernel's, in its operation
-// order: a frame's label and spliced column have its bits.  labels (F) in table order; an entry outside the batch or the clip is -1.
-__global__ __launch_bounds__(128) void codebook_splice_spans_kernel(const float* __restrict__ feats, int B, int T, int D,
-                                                                    const int32_t* __restrict__ frame_clip, const int32_t* __restrict__ frame_pos,
-                                                                    const float* __restrict__ cc, const float* __restrict__ raw,
-                                                                    const float* __restrict__ rnorm, int K, float* __restrict__ mel,
-                                                                    int Tm, int64_t* __restrict__ labels) {
-    __shared__ float v[128];
-    __shared__ float bs[2];
-    __shared__ int bi[2];
-    const int f = blockIdx.x;
-    const int b = frame_clip[f], pos = frame_pos[f];
-    if (b < 0 || b >= B || pos < 0 || pos >= T) {                    // uniform per block
-        if (threadIdx.x == 0 && labels) labels[f] = -1;
-        return;
-    }
-    const float* fr = feats + ((long)b * T + pos) * D;
-    if ((int)threadIdx.x < D) v[threadIdx.x] = fr[threadIdx.x];
-    __syncthreads();
-    const int lab = codebook_argmax_128(v, D, cc, rnorm, K, bs, bi);
-    if (threadIdx.x == 0 && labels) labels[f] = lab;
-    if (pos < Tm && (int)threadIdx.x < D) mel[((long)b * D + threadIdx.x) * Tm + pos] = raw[(long)lab * D + threadIdx.x];
-}
-
-__global__ __launch_bounds__(128) void codebook_gather_spans_kernel(const int64_t* __restrict__ labels, int B, int D,
-                                                                    const int32_t* __restrict__ frame_clip, const int32_t* __restrict__ frame_pos,
-                                                                    const float* __restrict__ raw, int K, float* __restrict__ mel, int Tm) {
-    const int f = blockIdx.x;
-    const int b = frame_clip[f], pos = frame_pos[f];
-    const long lab = labels[f];
-    if (b < 0 || b >= B || pos < 0 || pos >= Tm || lab < 0 || lab >= K) return;
-    if ((int)threadIdx.x < D) mel[((long)b * D + threadIdx.x) * Tm + pos] = raw[lab * D + threadIdx.x];
-}
-
-int si_launch_codebook_splice_spans(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_clip, const int32_t* frame_pos,
-                                    int F, const float* cb_centered, const float* cb_raw, const float* cb_rnorm, int K, float* mel, int Tm,
-                                    int64_t* labels, hipStream_t st) {
-    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
-    if (B <= 0 || F <= 0) return SI_OK;
-    si_prof_begin(ctx, "codebook_splice_spans", 2.0 * F * (double)K * D, 4.0 * F * 2.0 * D, st);
-    hipLaunchKernelGGL(codebook_splice_spans_kernel, dim3(F), dim3(128), 0, st, feats, B, T, D, frame_clip, frame_pos, cb_centered, cb_raw,
-                       cb_rnorm, K, mel, Tm, labels);
-    si_prof_end(ctx, st);
-    SI_HIP_CHECK(hipGetLastError());
-    return SI_OK;
-}
-
-int si_launch_codebook_gather_spans(si_ctx* ctx, const int64_t* labels, int B, int D, const int32_t* frame_clip, const int32_t* frame_pos, int F,
-                                    const float* cb_raw, int K, float* mel, int Tm, hipStream_t st) {
-    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
-    if (B <= 0 || F <= 0) return SI_OK;
-    si_prof_begin(ctx, "codebook_gather_spans", 0.0, 8.0 * F * D, st);
-    hipLaunchKernelGGL(codebook_gather_spans_kernel, dim3(F), dim3(128), 0, st, labels, B, D, frame_clip, frame_pos, cb_raw, K, mel, Tm);
-    si_prof_end(ctx, st);
-    SI_HIP_CHECK(hipGetLastError());
-    return SI_OK;
-}
-
-int si_launch_codebook_gather(si_ctx* ctx, const int64_t* labels, int B, int D, const int32_t* frame_pos, int Lm,
-                              const float* cb_raw, int K, float* mel, int Tm, hipStream_t st) {
-    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
-    if (B <= 0 || Lm <= 0) return SI_OK;
-    si_prof_begin(ctx, "codebook_gather", 0.0, 8.0 * B * Lm * D, st);
-    hipLaunchKernelGGL(codebook_gather_kernel, dim3(Lm, B), dim3(128), 0, st, labels, D, frame_pos, Lm, cb_raw, K, mel, Tm);
-    si_prof_end(ctx, st);
-    SI_HIP_CHECK(hipGetLastError());
-    return SI_OK;
-}
-
-int si_launch_codebook_splice(si_ctx* ctx, const float* feats, int B, int T, int D, const int32_t* frame_pos, int Lm,
-                              const float* cb_centered, const float* cb_raw, const float* cb_rnorm, int K, float* mel, int Tm,
-                              int64_t* labels, hipStream_t st, const int32_t* frame_cnt) {
-    if (D > 128) return si_fail(ctx, SI_EINVAL, "codebook dim %d > 128", D);
-    if (B <= 0 || Lm <= 0) return SI_OK;
-    si_prof_begin(ctx, "codebook_splice", 2.0 * B * Lm * (double)K * D, 4.0 * B * Lm * 2.0 * D, st);
-    hipLaunchKernelGGL(codebook_splice_kernel, dim3(Lm, B), dim3(128), 0, st, feats, T, D, frame_pos, Lm, cb_centered, cb_raw,
-                       cb_rnorm, K, mel, Tm, labels, frame_cnt);
-    si_prof_end(ctx, st);
-    SI_HIP_CHECK(hipGetLastError());
-    return SI_OK;
-}

@@ -224,59 +224,46 @@ class InpaintingEngine:
         [frame_pos[b], frame_pos[b] + lm): the generator runs on a window of the stretched frames around the change (as a ragged
         batch: a window clamped at a clip edge keeps that edge's real zero padding) and the samples the change can reach are spliced
         into a copy of `wave_base`.  Every output sample of the generator is the same fixed-order sum wherever its tile falls, so
-        the result is BIT-IDENTICAL to a full pass (asserted per vocoder mode in tests/test_gpu_configs.py)."""
-        import math
-        ext = self.ctx.extend_mel(mel_var.contiguous())
-        B, D, Tout = ext.shape
-        hop = wave_base.shape[1] // Tout
-        R = self.receptive_radius()
-        Rf = -(-R // hop)
-        r = 441.0 / 256.0
-        spans = []
+        the result is BIT-IDENTICAL to a full pass (asserted per vocoder mode in tests/test_gpu_configs.py).
+        This is `vocode_windows` with one range per clip: gaps.plan_windows on one range and gaps.kept_region give the window and
+        the kept samples."""
+        return self.vocode_windows(wave_base, mel_var, [[(int(p), int(lm))] for p in frame_pos])
+
+    def _stretch(self, mel: torch.Tensor, hop: int, mel_len: Optional[Sequence[int]] = None, windowed: Sequence = ()) -> Tuple[torch.Tensor, list]:
+        """The x441/256 stretched mel (B, D, Tout) the windows are cut from, and each clip's own stretched frames.  mel_len: per-clip
+        mel frames of a ragged batch -- the stretch of a shorter clip clamps at ITS last frame, so the rows of a shorter clip that
+        has windows (windowed[b] non-empty) come from the clip stretched alone."""
+        ext = self.ctx.extend_mel(mel.contiguous())
+        B, _, Tout = ext.shape
+        if mel_len is None:
+            return ext, [Tout] * B
+        touts = [self.ctx.vocoder_samples(int(m), True) // hop for m in mel_len]
         for b in range(B):
-            p = int(frame_pos[b])
-            c0 = max(int(math.floor((p - 0.5) * r - 0.5)) - 1, 0)      # stretched frames whose two source frames touch [p, p + lm)
-            c1 = min(int(math.ceil((p + lm + 0.5) * r - 0.5)) + 1, Tout)
-            spans.append((max(c0 - 2 * Rf, 0), min(c1 + 2 * Rf, Tout)))
-        W = max(w1 - w0 for w0, w1 in spans)
-        win = torch.zeros(B, D, W, dtype=torch.float32, device=self.device)
-        for b, (w0, w1) in enumerate(spans):
-            win[b, :, :w1 - w0] = ext[b, :, w0:w1]
-        out = self.vocode_ragged(win, [w1 - w0 for w0, w1 in spans], stretch=False)
-        wave = wave_base.clone()
-        for b, (w0, w1) in enumerate(spans):
-            s0 = w0 * hop + (Rf * hop if w0 > 0 else 0)               # a window edge that is not a clip edge: its first / last Rf frames
-            s1 = w1 * hop - (Rf * hop if w1 < Tout else 0)            # see missing neighbours and are dropped
-            wave[b, s0:s1] = out[b, s0 - w0 * hop:s1 - w0 * hop]
-        return wave
+            if touts[b] < Tout and windowed[b]:
+                ext[b, :, :touts[b]] = self.ctx.extend_mel(mel[b:b + 1, :, :int(mel_len[b])].contiguous())[0]
+        return ext, touts
+
+    def _vocode_gathered(self, ext: torch.Tensor, wins, tab=None) -> torch.Tensor:
+        """The windows `wins` = (clip, w0, w1) of the stretched mel -> their waveforms, one row per window: one gather launch and one
+        ragged stretch=False generator pass over all of them.  tab: the window table where the caller staged it (gather_windows)."""
+        return self.vocode_ragged(self.ctx.gather_windows(ext, wins, tab=tab), [w1 - w0 for _, w0, w1 in wins], stretch=False)
 
     def vocode_windows(self, wave_base: torch.Tensor, mel_var: torch.Tensor, ranges: Sequence[Sequence[Sequence[int]]],
                        mel_len: Optional[Sequence[int]] = None) -> torch.Tensor:
-        """The multi-window form of `vocode_window`: `mel_var` differs from the mel that produced `wave_base` only in the frame
-        ranges `ranges[b]` = (pos, len) pairs of clip b (none, one or several, any lengths).  gaps.plan_windows merges a clip's
+        """The waveform of `mel_var`, which differs from the mel that produced `wave_base` only in the frame ranges `ranges[b]` =
+        (pos, len) pairs of clip b (none, one or several, any lengths).  gaps.plan_windows merges a clip's
         windows where they overlap or touch; ALL windows of ALL clips go through the generator as one ragged stretch=False batch,
         and each window's kept region (its output without the rf frames at an edge that is not a clip edge) is spliced into a
         copy of `wave_base` -- the single-window rule, so the result is bit-identical to a full pass as well.
         mel_len: per-clip mel frames of a ragged batch (the stretch and the windows stop at the clip's own end)."""
-        ext = self.ctx.extend_mel(mel_var.contiguous())
-        B, D, Tout = ext.shape
-        hop = wave_base.shape[1] // Tout
+        B, hop = mel_var.shape[0], self.ctx.vocoder_samples(1, False)
         Rf = -(-self.receptive_radius() // hop)
-        touts = [Tout] * B if mel_len is None else [self.ctx.vocoder_samples(int(m), True) // hop for m in mel_len]
-        if mel_len is not None:
-            # the stretch of a shorter clip clamps at ITS last frame: its rows come from the clip stretched alone
-            for b in range(B):
-                if touts[b] < Tout and ranges[b]:
-                    ext[b, :, :touts[b]] = self.ctx.extend_mel(mel_var[b:b + 1, :, :int(mel_len[b])].contiguous())[0]
+        ext, touts = self._stretch(mel_var, hop, mel_len, ranges)
         wins = [(b, w0, w1) for b in range(B) for w0, w1 in G.plan_windows(ranges[b], touts[b], Rf)]
         wave = wave_base.clone()
         if not wins:
             return wave
-        W = max(w1 - w0 for _, w0, w1 in wins)
-        win = torch.zeros(len(wins), D, W, dtype=torch.float32, device=self.device)
-        for i, (b, w0, w1) in enumerate(wins):
-            win[i, :, :w1 - w0] = ext[b, :, w0:w1]
-        out = self.vocode_ragged(win, [w1 - w0 for _, w0, w1 in wins], stretch=False)
+        out = self._vocode_gathered(ext, wins)
         for i, (b, w0, w1) in enumerate(wins):
             k0, k1 = G.kept_region(w0, w1, touts[b], Rf)
             wave[b, k0 * hop:k1 * hop] = out[i, (k0 - w0) * hop:(k1 - w0) * hop]
@@ -522,17 +509,8 @@ class InpaintingEngine:
         out = self.predict_multigap_batch(wave16, wave22, gaps, len16=len16, len22=len22 if ragged else None, tables=tb, vocode=False)
         wins, gen = plan["wins"], None
         if wins:
-            mel2 = out["mel"]
-            ext = self.ctx.extend_mel(mel2)
-            if ragged:
-                # the stretch of a shorter clip clamps at ITS last frame: its rows come from the clip stretched alone (as vocode_windows)
-                Tout = ext.shape[2]
-                for b, m in enumerate(out["mel_len"]):
-                    t_b = self.ctx.vocoder_samples(int(m), True) // plan["hop"]
-                    if t_b < Tout and plan["windows"][b]:
-                        ext[b, :, :t_b] = self.ctx.extend_mel(mel2[b:b + 1, :, :int(m)].contiguous())[0]
-            win = self.ctx.gather_windows(ext, wins, tab=plan["gwin"])
-            gen = self.vocode_ragged(win, [w1 - w0 for _, w0, w1 in wins], stretch=False)
+            ext, _ = self._stretch(out["mel"], plan["hop"], out["mel_len"] if ragged else None, plan["windows"])
+            gen = self._vocode_gathered(ext, wins, plan["gwin"])
         patched, ppcm = self._compose(wave22, tb["tab22"], plan["table"], gen, n22 if ragged else None, plan["len22"] if ragged else None, pcm)
         out.update(patched=patched, patch_windows=plan["windows"])
         if pcm:

@@ -315,6 +315,24 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _dev(t: torch.Tensor, dtype: torch.dtype, dim: Optional[int] = None, n: Optional[int] = None) -> torch.Tensor:
+    """What every entry point asks of a tensor argument: on the GPU, this dtype, contiguous [, this rank] [, this many elements]."""
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and (dim is None or t.dim() == dim) and (n is None or t.numel() == n)
+    return t
+
+
+def _f32(t: torch.Tensor, dim: Optional[int] = None) -> torch.Tensor:
+    return _dev(t, torch.float32, dim)
+
+
+def _i32(t: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
+    return _dev(t, torch.int32, None, n)
+
+
+def _i64(t: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
+    return _dev(t, torch.int64, None, n)
+
+
 class NativeContext:
     """One si_ctx: a model pair bound to one GPU."""
 
@@ -408,22 +426,28 @@ class NativeContext:
         return self._ws
 
     # ---- forward calls (all enqueue on torch's current stream)
-    def hubert_forward(self, wav: torch.Tensor, mask_start: Optional[torch.Tensor], mask_len: Optional[torch.Tensor],
-                       normalize: bool = True, valid_len: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """valid_len (B,) int32 on the device: real samples of each RIGHT-PADDED clip (None: every clip fills its row)."""
-        assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
-        B, N = wav.shape
+    def _encoder_call(self, name: str, wav: torch.Tensor, width: int, masks, mid, head=(), sample_len=None) -> torch.Tensor:
+        """The encoder entry points: wav (B, N) -> (B, T, width) in the shared workspace.  They differ in the output width and in the
+        arguments between `wav` and `B` -- mid(lens) -> that tuple, lens = the HOST lengths `sample_len` of a ragged batch as a pointer
+        (None without) -- and `head`, what precedes `wav`.  masks: optional per-clip int32 (B) device tensors."""
+        B, N = _f32(wav, 2).shape
+        lens = None if sample_len is None else self._host_lens(sample_len, B)
         T = self.num_frames(N)
         if T < 1:
             raise ValueError(f"clip of {N} samples is too short")
-        for m in (mask_start, mask_len, valid_len):
-            assert m is None or (m.is_cuda and m.dtype == torch.int32 and m.numel() == B and m.is_contiguous())
-        out = torch.empty(B, T, self.desc.codebook_dim, dtype=torch.float32, device=self.device)
+        for m in masks:
+            assert m is None or _i32(m, B) is m
+        out = torch.empty(B, T, width, dtype=torch.float32, device=self.device)
         ws = self.workspace(B, N, 0)
-        self._check(self.lib.si_hubert_forward_padded(self._h, _ptr(wav), _ptr(mask_start), _ptr(mask_len), _ptr(valid_len),
-                                                      int(normalize), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
-                    "si_hubert_forward_padded")
+        self._check(getattr(self.lib, name)(self._h, *head, _ptr(wav), *mid(None if lens is None else lens.ctypes.data_as(C.c_void_p)), B, N,
+                                            _ptr(out), _ptr(ws), ws.numel(), self._stream()), name)
         return out
+
+    def hubert_forward(self, wav: torch.Tensor, mask_start: Optional[torch.Tensor], mask_len: Optional[torch.Tensor],
+                       normalize: bool = True, valid_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """valid_len (B,) int32 on the device: real samples of each RIGHT-PADDED clip (None: every clip fills its row)."""
+        return self._encoder_call("si_hubert_forward_padded", wav, self.desc.codebook_dim, (mask_start, mask_len, valid_len),
+                                  lambda _: (_ptr(mask_start), _ptr(mask_len), _ptr(valid_len), int(normalize)))
 
     @staticmethod
     def _host_lens(lens, B: int):
@@ -437,31 +461,14 @@ class NativeContext:
                               mask_len: Optional[torch.Tensor] = None, normalize: bool = True) -> torch.Tensor:
         """RAGGED batch: wav (B, Nmax), clip b = the first sample_len[b] samples of its row (host ints) -> (B, Tmax, D) with zero
         rows past each clip's own frames; every clip's rows equal that clip run alone (si_hubert_forward_varlen)."""
-        assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
-        B, N = wav.shape
-        lens = self._host_lens(sample_len, B)
-        T = self.num_frames(N)
-        if T < 1:
-            raise ValueError(f"clip of {N} samples is too short")
-        for m in (mask_start, mask_len):
-            assert m is None or (m.is_cuda and m.dtype == torch.int32 and m.numel() == B and m.is_contiguous())
-        out = torch.empty(B, T, self.desc.codebook_dim, dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, N, 0)
-        self._check(self.lib.si_hubert_forward_varlen(self._h, _ptr(wav), _ptr(mask_start), _ptr(mask_len), lens.ctypes.data_as(C.c_void_p),
-                                                      int(normalize), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
-                    "si_hubert_forward_varlen")
-        return out
+        return self._encoder_call("si_hubert_forward_varlen", wav, self.desc.codebook_dim, (mask_start, mask_len),
+                                  lambda lens: (_ptr(mask_start), _ptr(mask_len), lens, int(normalize)), sample_len=sample_len)
 
     def codebook_splice_varlen(self, feats: torch.Tensor, frame_pos: torch.Tensor, frame_cnt: torch.Tensor, lm: int, mel: torch.Tensor) -> torch.Tensor:
         """As codebook_splice with a per-clip frame count (B,) int32 on the device; labels past a clip's count are -1."""
-        assert feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous() and feats.dim() == 3
-        assert mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.dim() == 3
-        B, T, D = feats.shape
-        for m in (frame_pos, frame_cnt):
-            assert m.is_cuda and m.dtype == torch.int32 and m.is_contiguous() and m.numel() == B
-        assert mel.shape[0] == B and mel.shape[1] == D
+        B, T, Tm = self._feats_mel(feats, mel)
         labels = torch.empty(B, lm, dtype=torch.int64, device=self.device)
-        self._check(self.lib.si_codebook_splice_varlen(self._h, _ptr(feats), B, T, _ptr(frame_pos), _ptr(frame_cnt), lm, _ptr(mel), mel.shape[2],
+        self._check(self.lib.si_codebook_splice_varlen(self._h, _ptr(feats), B, T, _ptr(_i32(frame_pos, B)), _ptr(_i32(frame_cnt, B)), lm, _ptr(mel), Tm,
                                                        _ptr(labels), self._stream()), "si_codebook_splice_varlen")
         return labels
 
@@ -482,54 +489,20 @@ class NativeContext:
     def mel_frontend_varlen(self, wave22: torch.Tensor, sample_len, mask_start: Optional[torch.Tensor] = None,
                             mask_end: Optional[torch.Tensor] = None, normalize: bool = True) -> torch.Tensor:
         """RAGGED batch: wave22 (B, N22max), clip b = its first sample_len[b] samples -> (B, 80, Tm_max), zero frames past a clip's own."""
-        assert wave22.is_cuda and wave22.dtype == torch.float32 and wave22.dim() == 2 and wave22.is_contiguous()
-        B, N = wave22.shape
-        lens = self._host_lens(sample_len, B)
-        Tm = int(self.lib.si_mel_frames(N))
-        if Tm < 1:
-            raise ValueError(f"clip of {N} samples is too short for the mel front-end")
-        assert (mask_start is None) == (mask_end is None)
-        for m in (mask_start, mask_end):
-            assert m is None or (m.is_cuda and m.dtype == torch.int32 and m.numel() == B and m.is_contiguous())
-        ws = self._mel_workspace(B, N)
-        out = torch.empty(B, 80, Tm, dtype=torch.float32, device=self.device)
-        self._check(self.lib.si_mel_frontend_varlen(self._h, _ptr(wave22), _ptr(mask_start), _ptr(mask_end), lens.ctypes.data_as(C.c_void_p),
-                                                    int(normalize), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
-                    "si_mel_frontend_varlen")
-        return out
+        return self._mel_call("si_mel_frontend_varlen", wave22, (mask_start, mask_end),
+                              lambda lens: (_ptr(mask_start), _ptr(mask_end), lens, int(normalize)), sample_len)
 
     # ---- several gaps per clip (si_span_table / frame tables)
     def hubert_forward_spans(self, wav: torch.Tensor, spans: "SpanTable", normalize: bool = True, sample_len=None) -> torch.Tensor:
         """hubert_forward / hubert_forward_varlen (sample_len: host ints) with every span of `spans` (16 kHz samples) zeroed."""
-        assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
-        B, N = wav.shape
-        T = self.num_frames(N)
-        if T < 1:
-            raise ValueError(f"clip of {N} samples is too short")
-        lens = None if sample_len is None else self._host_lens(sample_len, B)
-        out = torch.empty(B, T, self.desc.codebook_dim, dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, N, 0)
         t = spans.struct()
-        self._check(self.lib.si_hubert_forward_spans(self._h, _ptr(wav), C.byref(t), None if lens is None else lens.ctypes.data_as(C.c_void_p),
-                                                     int(normalize), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
-                    "si_hubert_forward_spans")
-        return out
+        return self._encoder_call("si_hubert_forward_spans", wav, self.desc.codebook_dim, (), lambda lens: (C.byref(t), lens, int(normalize)),
+                                  sample_len=sample_len)
 
     def mel_frontend_spans(self, wave22: torch.Tensor, spans: "SpanTable", normalize: bool = True, sample_len=None) -> torch.Tensor:
         """mel_frontend / mel_frontend_varlen (sample_len: host ints) with every span of `spans` (22.05 kHz samples) zeroed."""
-        assert wave22.is_cuda and wave22.dtype == torch.float32 and wave22.dim() == 2 and wave22.is_contiguous()
-        B, N = wave22.shape
-        Tm = int(self.lib.si_mel_frames(N))
-        if Tm < 1:
-            raise ValueError(f"clip of {N} samples is too short for the mel front-end")
-        lens = None if sample_len is None else self._host_lens(sample_len, B)
-        ws = self._mel_workspace(B, N)
-        out = torch.empty(B, 80, Tm, dtype=torch.float32, device=self.device)
         t = spans.struct()
-        self._check(self.lib.si_mel_frontend_spans(self._h, _ptr(wave22), C.byref(t), None if lens is None else lens.ctypes.data_as(C.c_void_p),
-                                                   int(normalize), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
-                    "si_mel_frontend_spans")
-        return out
+        return self._mel_call("si_mel_frontend_spans", wave22, (), lambda lens: (C.byref(t), lens, int(normalize)), sample_len)
 
     # ---- patch mode (DESIGN.md 4.13)
     def wave_peak(self, wave22: torch.Tensor, spans: Optional["SpanTable"] = None, sample_len: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -589,44 +562,46 @@ class NativeContext:
                     "si_patch_compose")
         return out, out_pcm
 
-    def _frame_table(self, frame_clip: torch.Tensor, frame_pos: torch.Tensor) -> int:
-        for m in (frame_clip, frame_pos):
-            assert m.is_cuda and m.dtype == torch.int32 and m.is_contiguous() and m.dim() == 1
-        assert frame_clip.numel() == frame_pos.numel()
-        return frame_clip.numel()
+    @staticmethod
+    def _feats_mel(feats: torch.Tensor, mel: torch.Tensor):
+        """feats (B, T, D) and the mel (B, D, Tm) it is spliced into -> B, T, Tm."""
+        B, T, D = _f32(feats, 3).shape
+        assert _f32(mel, 3).shape[0] == B and mel.shape[1] == D
+        return B, T, mel.shape[2]
+
+    @staticmethod
+    def _frame_table(frame_clip: torch.Tensor, frame_pos: torch.Tensor) -> int:
+        F = frame_clip.numel()
+        assert _i32(frame_clip, F).dim() == 1 and _i32(frame_pos, F).dim() == 1
+        return F
+
+    def _metrics_out(self, *shape: int):
+        """loss (1,), loss_terms, pred_labels (int64) and cos_pred_target of a codebook_metrics call, the last three of `shape`."""
+        f32 = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=self.device)
+        return f32(1), f32(*shape), torch.empty(*shape, dtype=torch.int64, device=self.device), f32(*shape)
 
     def codebook_splice_spans(self, feats: torch.Tensor, frame_clip: torch.Tensor, frame_pos: torch.Tensor, mel: torch.Tensor) -> torch.Tensor:
         """In-place splice into `mel` (B, D, Tm) of the frames of a frame table (clip, frame: int32 (F) each); labels (F,) int64."""
-        assert feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous() and feats.dim() == 3
-        assert mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.dim() == 3
-        B, T, D = feats.shape
-        assert mel.shape[0] == B and mel.shape[1] == D
+        B, T, Tm = self._feats_mel(feats, mel)
         F = self._frame_table(frame_clip, frame_pos)
         labels = torch.empty(F, dtype=torch.int64, device=self.device)
-        self._check(self.lib.si_codebook_splice_spans(self._h, _ptr(feats), B, T, _ptr(frame_clip), _ptr(frame_pos), F, _ptr(mel), mel.shape[2],
+        self._check(self.lib.si_codebook_splice_spans(self._h, _ptr(feats), B, T, _ptr(frame_clip), _ptr(frame_pos), F, _ptr(mel), Tm,
                                                       _ptr(labels), self._stream()), "si_codebook_splice_spans")
         return labels
 
     def codebook_splice_labels_spans(self, labels: torch.Tensor, frame_clip: torch.Tensor, frame_pos: torch.Tensor, mel: torch.Tensor) -> None:
         """In-place splice of the raw centroids of GIVEN labels (F,) int64 at the frames of a frame table."""
-        assert mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.dim() == 3
         F = self._frame_table(frame_clip, frame_pos)
-        assert labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == F
-        self._check(self.lib.si_codebook_splice_labels_spans(self._h, _ptr(labels), mel.shape[0], _ptr(frame_clip), _ptr(frame_pos), F, _ptr(mel),
-                                                             mel.shape[2], self._stream()), "si_codebook_splice_labels_spans")
+        self._check(self.lib.si_codebook_splice_labels_spans(self._h, _ptr(_i64(labels, F)), _f32(mel, 3).shape[0], _ptr(frame_clip), _ptr(frame_pos), F,
+                                                             _ptr(mel), mel.shape[2], self._stream()), "si_codebook_splice_labels_spans")
 
     def codebook_metrics_spans(self, feats: torch.Tensor, frame_clip: torch.Tensor, frame_pos: torch.Tensor, target: torch.Tensor):
         """-> (loss (1,), loss_terms (F,), pred_labels (F,) int64, cos_pred_target (F,)) over the frames of a frame table."""
-        assert feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous() and feats.dim() == 3
-        B, T, D = feats.shape
+        B, T, D = _f32(feats, 3).shape
         F = self._frame_table(frame_clip, frame_pos)
-        assert target.is_cuda and target.dtype == torch.int64 and target.is_contiguous() and target.numel() == F
-        terms = torch.empty(F, dtype=torch.float32, device=self.device)
-        cpt = torch.empty(F, dtype=torch.float32, device=self.device)
-        pred = torch.empty(F, dtype=torch.int64, device=self.device)
-        loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        self._check(self.lib.si_codebook_metrics_spans(self._h, _ptr(feats), B, T, _ptr(frame_clip), _ptr(frame_pos), F, _ptr(target), _ptr(terms),
-                                                       _ptr(loss), _ptr(pred), _ptr(cpt), self._stream()), "si_codebook_metrics_spans")
+        loss, terms, pred, cpt = self._metrics_out(F)
+        self._check(self.lib.si_codebook_metrics_spans(self._h, _ptr(feats), B, T, _ptr(frame_clip), _ptr(frame_pos), F, _ptr(_i64(target, F)),
+                                                       _ptr(terms), _ptr(loss), _ptr(pred), _ptr(cpt), self._stream()), "si_codebook_metrics_spans")
         return loss, terms, pred, cpt
 
     def hubert_extract_features(self, wav: torch.Tensor, output_layer: int, normalize="layer_norm",
@@ -636,24 +611,12 @@ class NativeContext:
         `extract_features(output_layer=...)`, I_da/src/hubert_feature_reader.py:60-65).  normalize: "layer_norm" (I_da:
         F.layer_norm over the clip, eps 1e-5), "processor" (I_ea: eps 1e-7) or None.  mask_start / mask_len int32 (B) and
         pre_mask_add float64 (B): `(y + add) * mask` in front of it (I_da/scripts/inpainting.py:186-192)."""
-        assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
-        B, N = wav.shape
-        T = self.num_frames(N)
-        if T < 1:
-            raise ValueError(f"clip of {N} samples is too short")
-        for m in (mask_start, mask_len):
-            assert m is None or (m.is_cuda and m.dtype == torch.int32 and m.numel() == B and m.is_contiguous())
-        assert pre_mask_add is None or (pre_mask_add.is_cuda and pre_mask_add.dtype == torch.float64 and pre_mask_add.numel() == B
-                                        and pre_mask_add.is_contiguous())
+        assert pre_mask_add is None or _dev(pre_mask_add, torch.float64, None, wav.shape[0]) is pre_mask_add
         if normalize not in NORMALIZE_MODES:
             raise ValueError(f"normalize={normalize!r}: expected one of {list(NORMALIZE_MODES)}")
         x = ExtractDesc(C.sizeof(ExtractDesc), int(output_layer), NORMALIZE_MODES[normalize], 0)
-        out = torch.empty(B, T, self.desc.hidden_size, dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, N, 0)
-        self._check(self.lib.si_hubert_extract_features(self._h, C.byref(x), _ptr(wav), _ptr(mask_start), _ptr(mask_len),
-                                                        _ptr(pre_mask_add), B, N, _ptr(out), _ptr(ws), ws.numel(), self._stream()),
-                    "si_hubert_extract_features")
-        return out
+        return self._encoder_call("si_hubert_extract_features", wav, self.desc.hidden_size, (mask_start, mask_len),
+                                  lambda _: (_ptr(mask_start), _ptr(mask_len), _ptr(pre_mask_add)), head=(C.byref(x),))
 
     def code_splice(self, code_clean: torch.Tensor, code_masked: torch.Tensor, first: torch.Tensor, last: torch.Tensor) -> torch.Tensor:
         """(B, T) int64 unit series of the clean and the corrupted clip -> the corrupted clip's units inside frames
@@ -671,37 +634,26 @@ class NativeContext:
 
     def codebook_splice(self, feats: torch.Tensor, frame_pos: torch.Tensor, lm: int, mel: torch.Tensor) -> torch.Tensor:
         """In-place splice into `mel` (B, D, Tm); returns labels (B, Lm) int64."""
-        assert feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous() and feats.dim() == 3
-        assert mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.dim() == 3
-        assert frame_pos.is_cuda and frame_pos.dtype == torch.int32 and frame_pos.is_contiguous()
-        B, T, D = feats.shape
-        assert mel.shape[0] == B and mel.shape[1] == D and frame_pos.numel() == B
+        B, T, Tm = self._feats_mel(feats, mel)
         labels = torch.empty(B, lm, dtype=torch.int64, device=self.device)
-        self._check(self.lib.si_codebook_splice(self._h, _ptr(feats), B, T, _ptr(frame_pos), lm, _ptr(mel), mel.shape[2],
+        self._check(self.lib.si_codebook_splice(self._h, _ptr(feats), B, T, _ptr(_i32(frame_pos, B)), lm, _ptr(mel), Tm,
                                                 _ptr(labels), self._stream()), "si_codebook_splice")
         return labels
 
     def codebook_splice_labels(self, labels: torch.Tensor, frame_pos: torch.Tensor, mel: torch.Tensor) -> None:
         """In-place splice of the raw centroids of GIVEN labels (B, Lm) int64 into `mel` (B, D, Tm)."""
-        assert labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 2
-        assert mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.dim() == 3
-        assert frame_pos.is_cuda and frame_pos.dtype == torch.int32 and frame_pos.is_contiguous()
+        assert _i64(labels).dim() == 2
         B, lm = labels.shape
-        assert mel.shape[0] == B and frame_pos.numel() == B
-        self._check(self.lib.si_codebook_splice_labels(self._h, _ptr(labels), B, _ptr(frame_pos), lm, _ptr(mel), mel.shape[2],
+        assert _f32(mel, 3).shape[0] == B
+        self._check(self.lib.si_codebook_splice_labels(self._h, _ptr(labels), B, _ptr(_i32(frame_pos, B)), lm, _ptr(mel), mel.shape[2],
                                                        self._stream()), "si_codebook_splice_labels")
 
     def codebook_metrics(self, feats: torch.Tensor, frame_pos: torch.Tensor, lm: int, target: torch.Tensor):
         """-> (loss (1,), loss_terms (B, Lm), pred_labels (B, Lm) int64, cos_pred_target (B, Lm))."""
-        assert feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous() and feats.dim() == 3
-        assert frame_pos.is_cuda and frame_pos.dtype == torch.int32 and frame_pos.is_contiguous()
-        B, T, D = feats.shape
-        assert target.is_cuda and target.dtype == torch.int64 and target.is_contiguous() and tuple(target.shape) == (B, lm)
-        terms = torch.empty(B, lm, dtype=torch.float32, device=self.device)
-        cpt = torch.empty(B, lm, dtype=torch.float32, device=self.device)
-        pred = torch.empty(B, lm, dtype=torch.int64, device=self.device)
-        loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        self._check(self.lib.si_codebook_metrics(self._h, _ptr(feats), B, T, _ptr(frame_pos), lm, _ptr(target), _ptr(terms),
+        B, T, D = _f32(feats, 3).shape
+        assert tuple(_i64(target).shape) == (B, lm)
+        loss, terms, pred, cpt = self._metrics_out(B, lm)
+        self._check(self.lib.si_codebook_metrics(self._h, _ptr(feats), B, T, _ptr(_i32(frame_pos)), lm, _ptr(target), _ptr(terms),
                                                  _ptr(loss), _ptr(pred), _ptr(cpt), self._stream()), "si_codebook_metrics")
         return loss, terms, pred, cpt
 
@@ -843,22 +795,28 @@ class NativeContext:
             self._ws_mel = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         return self._ws_mel
 
-    def mel_frontend(self, wave22: torch.Tensor, mask_start: Optional[torch.Tensor] = None,
-                     mask_end: Optional[torch.Tensor] = None, normalize: bool = True) -> torch.Tensor:
-        """(B, N22) raw 22.05 kHz clips -> (B, 80, Tm) log-mel; the span [mask_start, mask_end) of each clip is zeroed first."""
-        assert wave22.is_cuda and wave22.dtype == torch.float32 and wave22.dim() == 2 and wave22.is_contiguous()
-        B, N = wave22.shape
+    def _mel_call(self, name: str, wave22: torch.Tensor, masks, mid, sample_len=None) -> torch.Tensor:
+        """The mel front-end entry points: wave22 (B, N22) -> (B, 80, Tm) in the front-end's own workspace.  mid(lens) -> the arguments
+        between `wave22` and `B`, lens = the HOST lengths `sample_len` of a ragged batch as a pointer (None without); masks: the
+        per-clip int32 (B) device tensors of the one span, both or neither."""
+        B, N = _f32(wave22, 2).shape
+        lens = None if sample_len is None else self._host_lens(sample_len, B)
         Tm = int(self.lib.si_mel_frames(N))
         if Tm < 1:
             raise ValueError(f"clip of {N} samples is too short for the mel front-end")
-        assert (mask_start is None) == (mask_end is None)
-        for m in (mask_start, mask_end):
-            assert m is None or (m.is_cuda and m.dtype == torch.int32 and m.numel() == B and m.is_contiguous())
+        assert len({m is None for m in masks}) <= 1
+        for m in masks:
+            assert m is None or _i32(m, B) is m
         ws = self._mel_workspace(B, N)
         out = torch.empty(B, 80, Tm, dtype=torch.float32, device=self.device)
-        self._check(self.lib.si_mel_frontend(self._h, _ptr(wave22), _ptr(mask_start), _ptr(mask_end), int(normalize), B, N,
-                                             _ptr(out), _ptr(ws), ws.numel(), self._stream()), "si_mel_frontend")
+        self._check(getattr(self.lib, name)(self._h, _ptr(wave22), *mid(None if lens is None else lens.ctypes.data_as(C.c_void_p)), B, N,
+                                            _ptr(out), _ptr(ws), ws.numel(), self._stream()), name)
         return out
+
+    def mel_frontend(self, wave22: torch.Tensor, mask_start: Optional[torch.Tensor] = None,
+                     mask_end: Optional[torch.Tensor] = None, normalize: bool = True) -> torch.Tensor:
+        """(B, N22) raw 22.05 kHz clips -> (B, 80, Tm) log-mel; the span [mask_start, mask_end) of each clip is zeroed first."""
+        return self._mel_call("si_mel_frontend", wave22, (mask_start, mask_end), lambda _: (_ptr(mask_start), _ptr(mask_end), int(normalize)))
 
     def capture(self, names, capacity=0):
         """Register capture buffers for the named intermediates (sizes come from the previous forward unless

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import audio
+from . import gaps as G
 from .arch import HubertArch, VocoderArch
 from .checkpoint import arch_for_type, load_codebook, load_generator_checkpoint, load_hubert_checkpoint
 from .config import PredictConfig, choose_device, load_predict_config
@@ -61,6 +62,16 @@ def _one_of(mask_pos, mask_frames, gaps, blind: bool) -> None:
         raise ValueError("give either mask_pos / mask_frames (one gap per clip) or gaps= (several), not both; blind mode takes no gaps")
     if gaps is None and (mask_pos is None or mask_frames is None):
         raise ValueError("mask_pos and mask_frames (or gaps=) are required")
+
+
+def _single_span22(mask_pos, mask_frames: int, mask22, n22: Sequence[int], dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[start, end) of the one span zeroed per clip on the 22.05 kHz side, int32 (B) each on the device: the frame span
+    (gaps.spans22, I_ea/predict.py:99-100) or the explicit `mask22` pairs, clamped to each clip's n22 samples."""
+    if mask22 is None:
+        pairs = [(s, s + l) for (s, l), in G.spans22([[(int(p), int(mask_frames))] for p in mask_pos], n22)]
+    else:
+        pairs = [(min(max(int(a), 0), n), min(max(int(b), 0), n)) for (a, b), n in zip(mask22, n22)]
+    return tuple(torch.tensor(col, dtype=torch.int32, device=dev) for col in zip(*pairs))
 
 
 def predict_clips(engine: InpaintingEngine, waves16: Sequence[np.ndarray], waves22: Sequence[np.ndarray],
@@ -157,10 +168,7 @@ def predict_resident(engine: InpaintingEngine, wave: torch.Tensor, wave22: torch
     if blind:
         mel = engine.mel(wave22)                                                    # nothing zeroed; predict.py:104-106
     else:
-        if mask22 is None:
-            mask22 = [(p * 320 * 22050 // 16000, (p + mask_frames) * 320 * 22050 // 16000) for p in mask_pos]
-        s22 = torch.tensor([min(max(int(a), 0), n22) for a, _ in mask22], dtype=torch.int32, device=dev)
-        e22 = torch.tensor([min(max(int(b), 0), n22) for _, b in mask22], dtype=torch.int32, device=dev)
+        s22, e22 = _single_span22(mask_pos, mask_frames, mask22, [n22] * len(mask_pos), dev)
         mel = engine.mel(wave22, s22, e22)                                          # predict.py:99-106 on the GPU
     pos = torch.tensor(list(mask_pos), dtype=torch.int32, device=dev)
     if diagnostics and not blind:
@@ -274,10 +282,7 @@ def predict_clips_ragged(engine: InpaintingEngine, waves16: Sequence[np.ndarray]
     if blind:
         mel = engine.mel_ragged(wave22, len22)
     else:
-        if mask22 is None:
-            mask22 = [(p * 320 * 22050 // 16000, (p + mask_frames) * 320 * 22050 // 16000) for p in mask_pos]
-        s22 = torch.tensor([min(max(int(a), 0), n) for (a, _), n in zip(mask22, len22)], dtype=torch.int32, device=dev)
-        e22 = torch.tensor([min(max(int(b), 0), n) for (_, b), n in zip(mask22, len22)], dtype=torch.int32, device=dev)
+        s22, e22 = _single_span22(mask_pos, mask_frames, mask22, len22, dev)
         mel = engine.mel_ragged(wave22, len22, s22, e22)
     mel_len = [engine.ctx.mel_frames(n) for n in len22]
     pos = torch.tensor(list(mask_pos), dtype=torch.int32, device=dev)

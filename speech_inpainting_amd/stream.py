@@ -165,22 +165,16 @@ class RequestFront:
                                                  tables=tables)
                 wave_len = out["wave_len"] if ragged else [out["wave"].shape[1]] * B
                 pcm = eng.to_int16(out["wave"])
-            s.ev_done.record(compute)
-            self.d2h.wait_event(s.ev_done)
-            F = out["labels"].numel()
-            with torch.cuda.stream(self.d2h):
-                s.pin_out[:pcm.numel()].view(pcm.shape).copy_(pcm, non_blocking=True)
-                s.pin_lab[:F].copy_(out["labels"], non_blocking=True)
-                s.ev_d2h.record(self.d2h)
-            s.keep = (w22, w16, out, pcm)
-            s.meta = dict(B=B, wave_len=wave_len, n_lab=F, n_wave=pcm.shape[1], tag=rq.tag, label_off=out["label_off"], tables=tables)
+            self._finish(s, compute, pcm, out["labels"], (w22, w16, out, pcm), B=B, wave_len=wave_len, n_lab=out["labels"].numel(), tag=rq.tag,
+                         label_off=out["label_off"], tables=tables)
             return
         pos = torch.tensor([int(p) for p in rq.mask_pos], dtype=torch.int32).to(dev, non_blocking=True)
         if rq.blind:
             s22 = e22 = None
         else:
-            s22 = torch.tensor([min(int(p) * 320 * 22050 // 16000, n) for p, n in zip(rq.mask_pos, len22)], dtype=torch.int32).to(dev)
-            e22 = torch.tensor([min((int(p) + lm) * 320 * 22050 // 16000, n) for p, n in zip(rq.mask_pos, len22)], dtype=torch.int32).to(dev)
+            sp = [clip[0] for clip in G.spans22([[(int(p), lm)] for p in rq.mask_pos], len22)]
+            s22 = torch.tensor([a for a, _ in sp], dtype=torch.int32).to(dev)
+            e22 = torch.tensor([a + l for a, l in sp], dtype=torch.int32).to(dev)
         if ragged:
             mel = eng.mel_ragged(w22, len22, s22, e22)
             out = eng.predict_ragged_batch(w16, len16, mel, mel_len, pos, lm, blind=rq.blind)
@@ -190,15 +184,20 @@ class RequestFront:
             out = eng.predict_batch(w16, mel, pos, lm, blind=rq.blind)
             wave_len = [out["wave"].shape[1]] * B
         pcm = eng.to_int16(out["wave"])                              # B6 on the device
+        self._finish(s, compute, pcm, out["labels"], (w22, w16, mel, out, pcm, pos, s22, e22), B=B, wave_len=wave_len,
+                     n_lab=out["labels"].shape[1], tag=rq.tag)
+
+    def _finish(self, s: _Slot, compute, pcm: torch.Tensor, labels: torch.Tensor, keep: tuple, **meta):
+        """The tail of a submitted batch: once the compute stream is done, PCM and labels (flat) go to the slot's pinned buffers on the
+        device-to-host stream; `keep` (the batch's device tensors) stays alive until those copies have run."""
         s.ev_done.record(compute)
         self.d2h.wait_event(s.ev_done)
-        n_lab = out["labels"].shape[1]
         with torch.cuda.stream(self.d2h):
             s.pin_out[:pcm.numel()].view(pcm.shape).copy_(pcm, non_blocking=True)
-            s.pin_lab[:B * n_lab].view(B, n_lab).copy_(out["labels"], non_blocking=True)
+            s.pin_lab[:labels.numel()].copy_(labels.reshape(-1), non_blocking=True)
             s.ev_d2h.record(self.d2h)
-        s.keep = (w22, w16, mel, out, pcm, pos, s22, e22)              # alive until the copies have run
-        s.meta = dict(B=B, wave_len=wave_len, n_lab=n_lab, n_wave=pcm.shape[1], tag=rq.tag)
+        s.keep = keep
+        s.meta = dict(n_wave=pcm.shape[1], **meta)
 
     def _collect(self, s: _Slot) -> Result:
         s.ev_d2h.synchronize()

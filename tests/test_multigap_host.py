@@ -64,6 +64,10 @@ def test_span_tables_against_the_oracles_single_mask():
     assert all(st[k] + ln[k] <= st[k + 1] for b in range(4) for k in range(off[b], off[b + 1] - 1))
     # the 22.05 kHz span of a gap at the end of a clip is clamped to the clip
     assert G.spans22([[(190, 9)]], [87000])[0][0] == (83790, 87000 - 83790)            # unclamped end: 87759
+    # a one-gap clip gives the single-gap route's clamp (min of each scaled end and the clip), for a gap that ends past the clip
+    p, lm, n = 190, 9, 87000
+    s, e = min(p * 320 * 22050 // 16000, n), min((p + lm) * 320 * 22050 // 16000, n)
+    assert e == n < (p + lm) * 320 * 22050 // 16000 and G.spans22([[(p, lm)]], [n]) == [[(s, e - s)]]
     ci, fp, loff = G.frame_table(gaps)
     assert loff == [0, 35, 45, 45, 83] and len(ci) == len(fp) == 83
     assert ci[:35] == [0] * 35 and fp[:5] == [20, 21, 22, 23, 24] and fp[5] == 90 and ci[45:] == [3] * 38 and fp[-1] == 184
