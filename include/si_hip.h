@@ -506,6 +506,11 @@ int si_profile_stop(si_ctx* ctx, si_profile_entry* out, int capacity, int* count
  *   conv0.ln / conv0.ln.bf16  layer flavour: LayerNorm + GELU behind conv0
  *   conv<i> / conv<i>.bf16    strided conv i (+ GELU in the group flavour), (B, L_{i+1}, C_i); ragged: rows past a clip are stale
  *   conv<i>.ln[.bf16]         layer flavour: LayerNorm + GELU behind conv i
+ *   features.ln[.bf16]        the feature projection's LayerNorm rows, (rows, C_last), directly behind it: fp32, or in bf16 mode with
+ *                             operand-ready activations the bf16 operand only (the form the projection GEMM reads); absent
+ *                             without feat_proj_layer_norm
+ *   pos_conv                  h + GELU(pos_conv(h) + b), (rows, H) fp32, directly behind the positional conv (posconv.hip or the
+ *                             tap-GEMM) and before the encoder LayerNorm; h is "projected" with the padded frames zeroed
  *   layer<l>.h                the fp32 hidden state entering layer l (out-proj's residual)
  *   layer<l>.h.bf16           the QKV GEMM's bf16 operand
  *   layer<l>.qkv[.bf16]       q | k | v, (rows, 3H)

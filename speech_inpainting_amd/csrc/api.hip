@@ -1071,6 +1071,9 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
         // (bf16 mode: the projection reads the bf16 operand only)
         if ((rc = si_launch_layernorm(ctx, feat, nullptr, wf(ctx, L.fp_ln_g), wf(ctx, L.fp_ln_b), lnf16 ? nullptr : lnf, BT, CF, d.layer_norm_eps, 0, st, lnf16))) return rc;
         proj_io.x16 = lnf16;
+        // (per-op tap: named and looked up only while some capture is registered)
+        if (!ctx->dbg_capture.empty() &&
+            (rc = lnf16 ? si_tap(ctx, st, {lnf16, BT * CF, 2}, "features.ln.bf16") : si_tap(ctx, st, {lnf, BT * CF}, "features.ln"))) return rc;
     }
     if ((rc = linear(ctx, L.proj, d.feat_proj_layer_norm ? lnf : feat, h, BT, SI_ACT_NONE, nullptr, st, proj_io))) return rc;
     if ((rc = si_tap(ctx, st, {h, BT * H}, "projected"))) return rc;
@@ -1094,6 +1097,7 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
         if (vl) p.seg_row_off = d_rowoff;                    // packed rows: the conv's zero padding begins at each clip's own last frame
         if ((rc = si_launch_tapgemm(ctx, L.pos.math, p, st))) return rc;
     }
+    if (!ctx->dbg_capture.empty() && (rc = si_tap(ctx, st, {h2, BT * H}, "pos_conv"))) return rc;   // (per-op tap, before the encoder LayerNorm)
     const float eps = d.layer_norm_eps;
     ResLn cur_ln;                                                      // ln_fuse: the LayerNorm whose (unwritten) output is the current hidden state
     // LayerNorm of the transformer rows: fp32 rows to y and / or their bf16 operand to y16; ln_fuse: (mean, rstd) per row for cur_ln

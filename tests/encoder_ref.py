@@ -280,6 +280,8 @@ def tap_capacities(harch, B, N, R):
     for i, C in enumerate(harch.conv_dim):
         for nm in (f"conv{i}", f"conv{i}.ln"):
             cap[nm] = cap[nm + ".bf16"] = B * Ls[i + 1] * C
+    cap["features.ln"] = cap["features.ln.bf16"] = R * harch.conv_dim[-1]
+    cap["pos_conv"] = R * H
     for l in range(harch.num_hidden_layers):
         for t, w in (("h", H), ("qkv", 3 * H), ("att", H), ("ln1", H), ("ffn", I), ("ln2", H)):
             cap[f"layer{l}.{t}"] = cap[f"layer{l}.{t}.bf16"] = R * w

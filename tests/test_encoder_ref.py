@@ -2,7 +2,14 @@
 function (ref_cpu.hubert_attention with key_mask, ref_cpu.hubert_ffn, the conv stack of ref_cpu.hubert_feature_extractor,
 ref_cpu.hubert_pos_conv, F.layer_norm) in float64 to 1e-12 relative, and each bound helper rejects the first value outside its
 bound; the exact-fp32 tap-GEMM's references (fp32_products, the grouped positional conv, LayerNorm + Linear) hold for an fp32
-evaluation on the CPU and reject a zeroed last row, a shifted tap and a masked column written wrongly."""
+evaluation on the CPU and reject a zeroed last row, a shifted tap and a masked column written wrongly.
+
+The bf16 positional conv (posconv.hip and the bf16 tap-GEMM; tests/test_gpu_encoder_ops.py holds them to tapgemm_ref's "bf16"
+bound): an fp32 emulation on bf16 operands at the real widths (Cg = 48 / 64) passes at T = 1, 65, 257, 513 and fails with each of
+four seeded mistakes -- a halo off by one row at the 256-row half seam, a dropped tap, a neighbouring clip's rows where the zero
+padding belongs, the even kernel's extra last row kept.  What that bound can see: it is the worst case of K = 6144 / 8192 fp32
+additions, linear in K, and a correct evaluation sits below 1e-3 of it; it catches a wrong row, tap, halo or clip, not a mistake
+of a few ulp."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -249,4 +256,110 @@ def test_pos_conv_bound_at_the_real_width_rejects_a_dropped_halo_row():
     bad = good.clone()
     bad[128] = fp32(h2)[128]
     c = V.check_f32(bad, r.ref, r.E)
+    assert c["bad"] > 0 and float(c["ratio"].max()) > 3
+
+
+# ------------------------------------------------------------------------------- the bf16 positional conv (posconv.hip, bf16 tap-GEMM)
+_PC = {}
+
+
+def _pc_setup(cg, T):
+    """(h, w, bias, k, G, reference) of the positional conv at the real width (Cg = 48: base, 64: large) on T rows of N(0, 0.5^2);
+    computed once per (Cg, T) and shared, never modified."""
+    from tests import vocoder_ref as V
+    if ("sd", cg) not in _PC:
+        import dataclasses
+        harch = HubertArch(num_hidden_layers=1) if cg == 48 else dataclasses.replace(HubertArch.large(), num_hidden_layers=1)
+        sd = synth.synth_hubert_state(harch, 31)
+        _PC[("sd", cg)] = (harch, E.pos_conv_weight(sd), sd["base_model.encoder.pos_conv_embed.conv.bias"])
+    harch, w, bias = _PC[("sd", cg)]
+    H, G, k = harch.hidden_size, harch.num_conv_pos_embedding_groups, harch.num_conv_pos_embeddings
+    if (cg, T) not in _PC:
+        h = torch.randn(T, H, generator=torch.Generator().manual_seed(100 + T)) * 0.5
+        _PC[(cg, T)] = (h, V.tapgemm_ref(h, w, bias, "bf16", E.pos_conv_geom(k, G), k * H // G, act="gelu", res=h))
+    h, r = _PC[(cg, T)]
+    return h, w, bias, k, G, r
+
+
+def _pc_emulate(h, w, bias, k, G, x=None, keep_last_row=False):
+    """What posconv.hip and the bf16 tap-GEMM compute, in fp32 on the CPU: operands rounded to bf16, an fp32 conv1d (zero padding k / 2,
+    the even kernel's extra last row dropped), erf-GELU, the fp32 residual h.  x: the rows the conv reads when they are not h's own
+    (the seeded mistakes); keep_last_row: the FIRST of the T + 1 rows dropped instead of the last."""
+    T = h.shape[0]
+    x = h if x is None else x
+    y = F.conv1d(x.to(torch.bfloat16).float().t()[None], w.to(torch.bfloat16).float(), bias, padding=k // 2, groups=G)[0].t()
+    return h + F.gelu(y[1:T + 1] if keep_last_row else y[:T])
+
+
+@pytest.mark.parametrize("cg", [48, 64])
+@pytest.mark.parametrize("T", [1, 65, 257, 513])
+def test_bf16_pos_conv_emulation_passes_the_bound(cg, T):
+    """The fp32 emulation of the bf16 positional conv lies inside tapgemm_ref's "bf16" bound at every element, and far inside: below
+    1e-3 of E (the bound is the worst case of K = 6144 / 8192 fp32 additions).  T = 1 (every tap but one reads padding), 65 (the first
+    and last taps reach a real row), 257 and 513 (one row past posconv.hip's 256-row half and 512-row block)."""
+    from tests import vocoder_ref as V
+    h, w, bias, k, G, r = _pc_setup(cg, T)
+    c = V.check_f32(_pc_emulate(h, w, bias, k, G), r.ref, r.E)
+    print(f"Cg={cg} T={T}: max err / E {float(c['ratio'].max()):.2e}")
+    assert c["finite"] and c["bad"] == 0
+    assert float(c["ratio"].max()) < 1e-3
+
+
+@pytest.mark.parametrize("cg", [48, 64])
+def test_bf16_pos_conv_bound_rejects_a_halo_off_by_one_at_the_half_seam(cg):
+    """Rows >= 256 (the second half of a posconv.hip tile) computed from an input shifted by one row: outside the bound.
+    Measured on the CPU: Cg = 48: 181 647 of 393 984 elements at T = 513, 723 of 197 376 at T = 257 (one wrong row);
+    Cg = 64: 232 277 of 525 312 and 949 of 263 168."""
+    from tests import vocoder_ref as V
+    for T in (257, 513):
+        h, w, bias, k, G, r = _pc_setup(cg, T)
+        bad = _pc_emulate(h, w, bias, k, G).clone()
+        shifted = torch.cat([h[1:], torch.zeros(1, h.shape[1])])
+        bad[256:] = _pc_emulate(h, w, bias, k, G, x=shifted)[256:]
+        c = V.check_f32(bad, r.ref, r.E)
+        print(f"Cg={cg} T={T}: {c['bad']} of {bad.numel()} outside")
+        assert c["bad"] > 0 and not bool((~c["ok"][:256]).any())
+        assert float(c["ratio"].max()) > 3
+
+
+@pytest.mark.parametrize("cg", [48, 64])
+def test_bf16_pos_conv_bound_rejects_a_dropped_tap(cg):
+    """One of the 128 taps left out (tap 0, which reads row t - 64: T >= 65 for it to read a real row at all; at T = 1 it reads
+    padding and nothing fails).  Measured on the CPU at T = 257: Cg = 48: 56 993 of 197 376 elements outside the bound; Cg = 64: 53 124 of
+    263 168."""
+    from tests import vocoder_ref as V
+    h, w, bias, k, G, r = _pc_setup(cg, 257)
+    w2 = w.clone()
+    w2[:, :, 0] = 0
+    c = V.check_f32(_pc_emulate(h, w2, bias, k, G), r.ref, r.E)
+    print(f"Cg={cg}: {c['bad']} of {h.numel()} outside")
+    assert c["bad"] > 0 and not bool((~c["ok"][:64]).any())            # rows < 64: tap 0 reads padding
+    h1, _, _, _, _, r1 = _pc_setup(cg, 1)
+    assert V.check_f32(_pc_emulate(h1, w2, bias, k, G), r1.ref, r1.E)["bad"] == 0
+
+
+@pytest.mark.parametrize("cg", [48, 64])
+def test_bf16_pos_conv_bound_rejects_a_neighbouring_clip_in_the_padding(cg):
+    """Two clips packed (65 and 257 rows): the conv of the first reads the second's rows where its zero padding belongs, and the
+    second's the first's.  Measured on the CPU: Cg = 48: 41 342 of 49 920 elements of the first clip and 38 108 of 197 376 of the second outside the bound; Cg = 64:
+    51 596 of 66 560 and 46 234 of 263 168."""
+    from tests import vocoder_ref as V
+    ha, w, bias, k, G, ra = _pc_setup(cg, 65)
+    hb, _, _, _, _, rb = _pc_setup(cg, 257)
+    both = torch.cat([ha, hb])
+    out = _pc_emulate(both, w, bias, k, G)
+    ca, cb = V.check_f32(out[:65], ra.ref, ra.E), V.check_f32(out[65:], rb.ref, rb.E)
+    print(f"Cg={cg}: {ca['bad']} of {ha.numel()} and {cb['bad']} of {hb.numel()} outside")
+    assert ca["bad"] > 0 and cb["bad"] > 0
+    assert not bool((~cb["ok"][64:]).any())                            # rows >= 64 of the second clip read none of the first
+
+
+@pytest.mark.parametrize("cg", [48, 64])
+def test_bf16_pos_conv_bound_rejects_the_even_kernels_extra_row_kept(cg):
+    """The even kernel gives T + 1 rows; keeping the last and dropping the first shifts the conv's output by one row.  Measured on
+    the CPU at T = 65: Cg = 48: 47 703 of 49 920 elements outside the bound; Cg = 64: 62 002 of 66 560."""
+    from tests import vocoder_ref as V
+    h, w, bias, k, G, r = _pc_setup(cg, 65)
+    c = V.check_f32(_pc_emulate(h, w, bias, k, G, keep_last_row=True), r.ref, r.E)
+    print(f"Cg={cg}: {c['bad']} of {h.numel()} outside")
     assert c["bad"] > 0 and float(c["ratio"].max()) > 3

@@ -3,7 +3,30 @@ the kernel itself read, captured through the encoder's per-op taps: the GEMMs (g
 three tile heights, the tap-GEMM's bf16 path) at M = BM - 1, BM, BM + 1 and on ragged per-clip segments; the attention kernels
 at the 32-key tile edges, across the whole-K/V / tiled switch (T = 256 / 257), on padded and ragged batches; LayerNorm at
 C = 512, 768, 1024 (its bf16 operand bit-equal to rne of its fp32 rows); conv0 + GroupNorm + GELU.  Real layer widths, one
-layer.  Every bound is an error bound derived in encoder_ref.py, not a tolerance fitted to these runs."""
+layer.  Every bound is an error bound derived in encoder_ref.py, not a tolerance fitted to these runs.
+
+The feature projection (`_check_projection`, in every run that checks a layer's GEMMs): its LayerNorm(512), stored as the GEMM's
+bf16 operand only ("features.ln.bf16"), and Linear(512 -> H), the encoder's only GEMM with K = 512, on that operand.
+
+The positional conv (`test_posconv_*`): posconv.hip and the SI_ENC_POSCONV=0 fallback (the grouped bf16 tap-GEMM, N = 48 in
+Npad = 64), Cg = 48 and 64, at the "pos_conv" tap against vocoder_ref.tapgemm_ref's "bf16" bound on the captured "projected" rows, every
+row and channel, at the smallest shapes that reach each seam of posconv.hip's tiling: two clips per workgroup (Tmax <= 256) | 512-row
+blocks of two 256-row halves, each staged with a 128-row halo; an odd batch, a half or a block holding one row, clips shorter than
+the 64-row padding, the clamped rows outside a clip, padded frames zeroed.  What that bound can see: it is the worst case of
+K = 6144 / 8192 fp32 additions, linear in K, while a correct kernel's error grows like sqrt(K) and sits far below it (the records
+below).  A wrong row, tap, halo or clip lands outside it (tests/test_encoder_ref.py fails it with four seeded mistakes on a CPU
+emulation: a halo off by one at the half seam, a dropped tap, a neighbouring clip in the padding, the even kernel's extra row kept);
+a mistake of a few ulp does not.  The bit-identity assertions (each ragged clip equal to the clip alone) see those.
+
+Measured on MI355X (records, not limits): max err / E over the rows within 64 of a 256-row seam or a clip edge | over the rest
+    posconv_bf16_c48        below 5e-4 | below 5e-4 (23 clips; the run printed 0.000)
+    posconv_bf16_c64        below 5e-4 | below 5e-4 (23 clips)
+    tapgemm_bf16_256x64     below 5e-4 | below 5e-4 (46 clips) (the fallback, both widths)
+the projection GEMM, max err / E over the rows of the last (partial) row tile | the rest
+    gemmcu_bf16_320x256, 256x256, 160x128, 224x128, 128x128, 208x256 (M = BM - 1, BM, BM + 1 each)     0.002 over all rows
+    lingemm_bf16_64x128 (M = 3984, 3700, 300 and the ragged base / large batches, M = 432)              0.002
+    tapgemm_bf16_128x128w8 (SI_ENC_LINGEMM=0, M = 300) 0.002;  tapgemm_bf16_128x128 (fp32 features, no LayerNorm, M = 257) 0.002
+and the share of "features.ln.bf16" outputs != rne(float64 LayerNorm): at most 0.0059 % over 24 runs (the "ln" guard: 0.064 %)."""
 import dataclasses
 import os
 
@@ -11,6 +34,7 @@ import pytest
 import torch
 
 from tests import encoder_ref as E
+from tests import vocoder_ref as V
 
 pytestmark = pytest.mark.gpu
 
@@ -19,9 +43,11 @@ GEMMCU_BM = {10: 320, 11: 256, 12: 160, 13: 224, 14: 128, 15: 208}
 GEMMCU_BN = {10: 256, 11: 256, 12: 128, 13: 128, 14: 128, 15: 256}
 # Fraction of a launch's bf16 outputs that differ from rne(float64 result), the bf16 value nearest to the exact one: twice the
 # worst measured over this file's runs on MI355X (GEMM / conv 0.395 %, conv0 + GroupNorm 0.051 %, LayerNorm + GELU 0.032 %,
-# attention_kernel with a bf16 output 0.0061 %).  The bf16-input attention kernels round P to bf16 before P V, so about one
-# output in five lands on the other neighbour of the exact value (measured up to 18.6 %, at T = 31); their limit is the same
-# twice-measured guard, the error bound above being the check on their arithmetic.
+# attention_kernel with a bf16 output 0.0061 %; the projection LayerNorm's C = 512 operand, "features.ln.bf16", measured at most
+# 0.0059 % against the float64 reference over 24 runs, so it is held to "ln" and has no key of its own).  The bf16-input
+# attention kernels round P to bf16 before P V, so about one output in five lands on the other neighbour of the exact value
+# (measured up to 18.6 %, at T = 31); their limit is the same twice-measured guard, the error bound above being the check on
+# their arithmetic.
 MISMATCH_LIMIT = {"gemm": 0.0079, "conv0": 0.00103, "ln": 0.00064, "attention": 0.00012, "attention_p16": 0.372}
 
 
@@ -40,7 +66,7 @@ _STATES = {}
 
 def _state(harch):
     from speech_inpainting_amd import synth
-    key = (harch.hidden_size, harch.feat_extract_norm, harch.do_stable_layer_norm)
+    key = (harch.hidden_size, harch.feat_extract_norm, harch.do_stable_layer_norm, harch.feat_proj_layer_norm)
     if key not in _STATES:
         _STATES[key] = synth.synth_hubert_state(harch, 31)
     return _STATES[key]
@@ -66,11 +92,12 @@ def _engine(harch, env=None):
 
 
 def _run(eng, harch, wave, lens=None, valid_len=None, profile=False):
-    """One encoder forward with every per-op tap registered -> (taps {name: cpu tensor} of the taps the path produced,
-    rows of the transformer, kernel names if profiled)."""
+    """One encoder forward with every per-op tap registered (and "features", "projected", the projection's two ends) -> (taps
+    {name: cpu tensor} of the taps the path produced, rows of the transformer, kernel names if profiled)."""
     B, N = wave.shape
     R = sum(harch.num_frames(n) for n in lens) if lens is not None else B * harch.num_frames(N)
     cap = E.tap_capacities(harch, B, N, R)
+    cap["features"], cap["projected"] = R * harch.conv_dim[-1], R * harch.hidden_size
     eng.ctx.clear_captures()
     caps = eng.ctx.capture(list(cap), capacity=cap)
     if profile:
@@ -152,6 +179,83 @@ def _check_layers(got, harch, R, tag, rows=None):
                *E.linear_ref(a2, sd[p + "feed_forward.output_dense.weight"], sd[p + "feed_forward.output_dense.bias"], res=res2))
 
 
+GEMMCU_CFGS = ((320, 256), (256, 256), (160, 128), (224, 128), (128, 128), (208, 256))     # gemmcu.hip, k_cfgs: (BM, BN) of instantiation c
+
+
+def _linear_kernel(M, N, K, env=None, x16=True):
+    """The profile name of one Linear of the bf16 encoder (one tap, one flat segment of M rows, N >= 128), restating the launchers'
+    rules: si_launch_tapgemm hands an operand-ready (bf16) input to si_launch_lingemm unless SI_ENC_LINGEMM=0; that tries
+    si_launch_gemmcu first (SI_ENC_GEMMCU: 0 never, 10 + c instantiation c wherever BN divides N, 1 the whole-rounds rule over the
+    device's CUs), then picks its own tile height by rounds x (BM + 24) over two workgroup slots per CU; everything else runs
+    launch_math's bf16 branch: eight light waves on a 128 x 128 tile for an operand-ready input of M > 256 rows ("w8"), else four."""
+    env = env or {}
+    assert N >= 128
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    opt = int(env.get("SI_ENC_GEMMCU", "1"))
+    if x16 and env.get("SI_ENC_LINGEMM", "1") != "0" and N % 128 == 0 and K % 64 == 0:
+        pick = -1
+        if opt >= 10:
+            pick = opt - 10 if N % GEMMCU_CFGS[opt - 10][1] == 0 else -1
+        elif opt > 0:
+            best, fills_256 = 1e30, False
+            for c, (bm, bn) in enumerate(GEMMCU_CFGS):
+                if N % bn:
+                    continue
+                rb = -(-M // bm)
+                tiles = rb * (N // bn)
+                rounds = -(-tiles // cus)
+                fill = tiles / (rounds * cus)
+                if c == 1:
+                    fills_256 = K >= 128 and fill * M / (rb * bm) >= 0.72
+                if opt == 1 and (fill < (0.6 if rounds == 1 else 0.75) or M < 0.75 * rb * bm):
+                    continue
+                if rounds * (bm + bn) < best:
+                    best, pick = rounds * (bm + bn), c
+            if pick < 0 and opt == 1 and fills_256:
+                pick = 1
+        if pick >= 0:
+            return "gemmcu_bf16_%dx%d" % GEMMCU_CFGS[pick]
+        best, height = 1e30, 128
+        for cand in (128, 96, 64):
+            tiles = -(-M // cand) * (N // 128)
+            cost = -(-tiles // (2 * cus)) * (cand + 24)
+            if cost < best * 0.97:
+                best, height = cost, cand
+        return f"lingemm_bf16_{height}x128"
+    return "tapgemm_bf16_128x128w8" if x16 and M > 256 else "tapgemm_bf16_128x128"
+
+
+def _check_projection(got, harch, R, tag, names, env=None, rows=None):
+    """The feature projection, op by op: its LayerNorm(512) from "features" to "features.ln.bf16" (the rows are stored as the GEMM's
+    bf16 operand only) against layernorm_ref, then Linear(512 -> H) -- the encoder's only GEMM with K = 512 -- from that operand to
+    "projected" against linear_ref.  Without the LayerNorm the GEMM's staging rounds the fp32 features.  `names`: the run's profile,
+    which must hold the kernel the launchers' rule gives this GEMM."""
+    sd = _state(harch)
+    p = "base_model.feature_projection."
+    CF, H = harch.conv_dim[-1], harch.hidden_size
+    rows = torch.arange(R) if rows is None else rows
+    feats = got["features"].view(R, CF)[rows]
+    if harch.feat_proj_layer_norm:
+        assert "features.ln.bf16" in got and "features.ln" not in got, sorted(got)
+        op = got["features.ln.bf16"].view(R, CF)[rows]
+        ref, bound = E.layernorm_ref(feats, sd[p + "layer_norm.weight"], sd[p + "layer_norm.bias"], harch.layer_norm_eps)
+        _check(f"{tag} projection LayerNorm (C = {CF}) bf16 operand", "bf16", op, ref, bound, "ln")
+        a = _f64(op)
+        kern = _linear_kernel(R, H, CF, env)
+    else:
+        assert "features.ln.bf16" not in got and "features.ln" not in got, sorted(got)
+        a = E.bf16(feats)                                              # fp32 operand, rounded by the GEMM's staging
+        kern = _linear_kernel(R, H, CF, env, x16=False)
+    ref, bound = E.linear_ref(a, sd[p + "projection.weight"], sd[p + "projection.bias"])
+    y = got["projected"].view(R, H)[rows]
+    _check(f"{tag} projection (K = {CF}) [{kern}]", "f32", y, ref, bound)
+    ratio = ((y.double() - ref).abs() / bound).amax(1)
+    bm = int(kern.split("_")[2].split("x")[0])                         # the kernel's tile height
+    last = rows >= (R - 1) // bm * bm                                  # rows of the last (partial) row tile | the rest
+    print(f"   [{kern}] max err/E last tile {float(ratio[last].max()):.2e}, the rest {float(ratio[~last].max()) if bool((~last).any()) else 0.0:.2e}")
+    assert kern in names, (kern, sorted(names))
+
+
 def _check_convs(got, harch, B, N, tag, clip_lens=None):
     """Strided convs 1..n-1 of every clip against linear_ref on their captured inputs (rows: _sel_rows of the clip's own length)."""
     sd = _state(harch)
@@ -207,6 +311,7 @@ def test_gemmcu_instantiation_against_float64(flag, dm):
     Ls = harch.feat_lengths(wave.shape[1])
     print(f"\nSI_ENC_GEMMCU={flag} ({bm} rows): M = {R} (M mod BM = {R % bm}); conv segments {Ls[2:]} mod BM {[L % bm for L in Ls[2:]]}")
     _check_layers(got, harch, R, f"gemmcu {bm}")
+    _check_projection(got, harch, R, f"gemmcu {bm}", names, {"SI_ENC_GEMMCU": str(flag)})
     _check_convs(got, harch, 1, wave.shape[1], f"gemmcu {bm}")
 
 
@@ -238,6 +343,7 @@ def test_lingemm_and_tapgemm_against_float64(B, T, env):
     assert not any(n.startswith("gemmcu_bf16") for n in names), names
     assert bool(lg) != ("SI_ENC_LINGEMM" in env), names
     _check_layers(got, harch, R, "lingemm" if lg else "tapgemm", rows=_sel_rows(R))
+    _check_projection(got, harch, R, "lingemm" if lg else "tapgemm", names, env, rows=_sel_rows(R))
     _check_convs(got, harch, B, wave.shape[1], "lingemm" if lg else "tapgemm")
 
 
@@ -265,7 +371,22 @@ def test_ragged_batch_gemms_against_float64(arch):
     got, R, names = _run(eng, harch, wave, lens=lens, profile=True)
     print(f"\nragged {arch}: clips {[harch.num_frames(n) for n in lens]} frames, packed M = {R}; {sorted(n for n in names if 'gemm' in n)}")
     _check_layers(got, harch, R, f"ragged {arch}")
+    _check_projection(got, harch, R, f"ragged {arch}", names)
     _check_convs(got, harch, len(lens), max(lens), f"ragged {arch}", clip_lens=lens)
+
+
+def test_projection_without_layernorm_against_float64():
+    """feat_proj_layer_norm=False: the projection reads the fp32 features themselves, so it runs on the tap-GEMM's bf16 path, whose
+    staging rounds them (M = 257: two 128-row tiles and a last tile of one row)."""
+    from speech_inpainting_amd import synth
+    from speech_inpainting_amd.arch import HubertArch
+    harch = HubertArch(feat_proj_layer_norm=False, num_hidden_layers=1)
+    eng = _engine(harch)
+    T = 257
+    got, R, names = _run(eng, harch, synth.synth_wave(1, 320 * (T - 1) + 400, 11).cuda(), profile=True)
+    assert R == T
+    _check_projection(got, harch, R, "no LayerNorm", names)
+    _check_layers(got, harch, R, "no LayerNorm")
 
 
 # ------------------------------------------------------------------------------------------------------------ attention
@@ -341,6 +462,172 @@ def test_ragged_batch_attention_against_float64(frames):
     got, R, _ = _run(eng, harch, wave, lens=lens)
     offs = [sum(frames[:b]) for b in range(len(frames))]
     _check_attention(got, harch, [(o, f, f) for o, f in zip(offs, frames)], "ragged", "bf16")
+
+
+def test_ragged_batch_attention_of_the_large_encoder_against_float64():
+    """The first frame list above on the large encoder: 16 heads (H = 1024; every other attention case here has 12)."""
+    from speech_inpainting_amd import synth
+    harch = _large()
+    assert harch.num_attention_heads == 16
+    frames = [256, 33, 1, 129, 200, 32]
+    lens = [320 * (f - 1) + 400 for f in frames]
+    wave = synth.synth_wave(len(lens), max(lens), 90).cuda()
+    got, R, _ = _run(_engine(harch), harch, wave, lens=lens)
+    offs = [sum(frames[:b]) for b in range(len(frames))]
+    _check_attention(got, harch, [(o, f, f) for o, f in zip(offs, frames)], "ragged large", "bf16")
+
+
+# ------------------------------------------------------------------------------------------------------- positional conv
+PC_HALF = 256                                          # posconv.hip, PC_HALF_ROWS: output rows per half of a workgroup's tile
+PC_UNIFORM = [(3, 256), (2, 257), (1, 513)]
+PC_RAGGED = [[256, 1, 255, 16, 17, 64, 65], [513, 1, 257, 512, 256, 511]]
+PC_PADDED = (300, [1, 32, 33, 299])
+PC_KERNELS = {"posconv": {}, "tapgemm": {"SI_ENC_POSCONV": "0"}}
+_PC_ENGINES = {}
+
+
+def _pc_arch(cg):
+    return _base() if cg == 48 else _large()
+
+
+def _pc_engine(cg, kernel):
+    """One engine per (width, kernel), kept for the file: SI_ENC_POSCONV is read when the context is created."""
+    if (cg, kernel) not in _PC_ENGINES:
+        _PC_ENGINES[(cg, kernel)] = _engine(_pc_arch(cg), PC_KERNELS[kernel])
+    return _PC_ENGINES[(cg, kernel)]
+
+
+def _pc_both(cg, wave, lens=None, valid_len=None):
+    """The same batch through posconv.hip and through the SI_ENC_POSCONV=0 fallback -> {kernel: (taps, profile name of the conv's
+    kernel)}.  The profile must name the one and none of the other; "projected", the conv's input, must be equal in both runs."""
+    from tests.test_gpu_tapgemm_ops import _config
+    harch = _pc_arch(cg)
+    runs = {}
+    for kernel in PC_KERNELS:
+        got, R, names = _run(_pc_engine(cg, kernel), harch, wave, lens=lens, valid_len=valid_len, profile=True)
+        ran = {n for n in names if n.startswith("posconv_")}
+        if kernel == "posconv":
+            name = f"posconv_bf16_c{cg}"
+            assert ran == {name}, names
+        else:                                                          # the grouped tap-GEMM on the fp32 rows: N = Cg in Npad = 64
+            name = _config("bf16", cg, harch.num_frames(wave.shape[1]), harch.num_conv_pos_embeddings, 1, cg)[0]
+            assert not ran and name in names and name.startswith("tapgemm_bf16_"), names
+        runs[kernel] = (got, name)
+    assert torch.equal(runs["posconv"][0]["projected"], runs["tapgemm"][0]["projected"])
+    return runs
+
+
+def _check_posconv(runs, cg, clips, tag, valid=None):
+    """Every row and channel of every clip at the "pos_conv" tap, of both kernels, against ONE float64 reference per clip on the
+    captured "projected" rows.  clips: [(first packed row, T)]; valid: the clips' valid frame counts in a padded batch ("projected"
+    is tapped before the padded frames are zeroed, so the reference zeroes them itself)."""
+    harch = _pc_arch(cg)
+    sd = _state(harch)
+    H, G, k = harch.hidden_size, harch.num_conv_pos_embedding_groups, harch.num_conv_pos_embeddings
+    assert H // G == cg
+    w, bias = E.pos_conv_weight(sd), sd["base_model.encoder.pos_conv_embed.conv.bias"]
+    geom = E.pos_conv_geom(k, G)
+    proj = runs["posconv"][0]["projected"]
+    R = proj.numel() // H
+    for i, (r0, T) in enumerate(clips):
+        h = proj.view(R, H)[r0:r0 + T]
+        if valid is not None:
+            h = h.clone()
+            h[valid[i]:] = 0
+        r = V.tapgemm_ref(h, w, bias, "bf16", geom, k * cg, act="gelu", res=h)
+        for kernel, (got, name) in runs.items():
+            c = V.check_f32(got["pos_conv"].view(R, H)[r0:r0 + T], r.ref, r.E)
+            line, near, rest = V.report(tag, name, i, c, T, PC_HALF, 64)
+            print(f"   {line} ({near:.2e} | {rest:.2e})")
+            assert c["finite"] and c["bad"] == 0, line
+
+
+@pytest.mark.parametrize("cg", [48, 64])
+@pytest.mark.parametrize("B,T", PC_UNIFORM)
+def test_posconv_uniform_batches_against_float64(B, T, cg):
+    """(3, 256): two clips per workgroup with an odd batch -- the last workgroup's second half has no clip; (2, 257): 512-row
+    blocks, the second half holding one row; (1, 513): two blocks per clip, the second holding one row.  Cg = 48: base (post-LN,
+    where only the "pos_conv" tap shows the conv's output), 64: large (pre-LN)."""
+    from speech_inpainting_amd import synth
+    wave = synth.synth_wave(B, 320 * (T - 1) + 400, 120 + T).cuda()
+    runs = _pc_both(cg, wave)
+    print(f"\nCg={cg} B={B} T={T}: {[n for _, n in runs.values()]}")
+    _check_posconv(runs, cg, [(b * T, T) for b in range(B)], f"uniform B={B}")
+
+
+@pytest.mark.parametrize("cg", [48, 64])
+@pytest.mark.parametrize("frames", PC_RAGGED)
+def test_posconv_ragged_batches_against_float64(frames, cg):
+    """encode_ragged, packed rows.  Tmax = 256: two clips per workgroup -- seven clips (the last workgroup has an empty half), clips
+    of different lengths sharing a workgroup, a single-frame clip, a clip shorter than the 64-row padding, T = 64 | 65 where the
+    first and last taps first reach a real row.  Tmax = 513: a two-block grid in which clips shorter than one half sit.  Every clip
+    against float64, and bit-identical to the same clip run alone (256 and 255 run alone two per workgroup, but share the second
+    batch's block grid): a clip's result does not depend on which other clip shares its workgroup."""
+    from speech_inpainting_amd import synth
+    harch = _pc_arch(cg)
+    H = harch.hidden_size
+    lens = [320 * (f - 1) + 400 for f in frames]
+    wave = synth.synth_wave(len(lens), max(lens), 130 + len(frames)).cuda()
+    runs = _pc_both(cg, wave, lens=lens)
+    offs = [sum(frames[:b]) for b in range(len(frames))]
+    print(f"\nCg={cg} ragged {frames}: {[n for _, n in runs.values()]}")
+    _check_posconv(runs, cg, list(zip(offs, frames)), f"ragged Tmax={max(frames)}")
+    R = sum(frames)
+    for b, f in enumerate(frames):
+        alone = wave[b:b + 1, :lens[b]].contiguous()
+        for kernel, (got, name) in runs.items():
+            one, R1, _ = _run(_pc_engine(cg, kernel), harch, alone, lens=[lens[b]])
+            assert R1 == f
+            assert torch.equal(one["pos_conv"].view(f, H), got["pos_conv"].view(R, H)[offs[b]:offs[b] + f]), \
+                f"{name}: clip {b} ({f} frames) in the batch differs from the clip alone"
+
+
+@pytest.mark.parametrize("cg", [48, 64])
+def test_posconv_padded_batch_against_float64(cg):
+    """encode(valid_len=...), T = 300, valid frames 1, 32, 33, 299: the conv reads "projected" with every frame >= the clip's valid
+    count zeroed -- which also holds frame_lengths_kernel and zero_padded_rows_kernel to their definitions -- and is defined on
+    all T rows."""
+    from speech_inpainting_amd import synth
+    harch = _pc_arch(cg)
+    T, frames = PC_PADDED
+    valid = torch.tensor([320 * (f - 1) + 400 for f in frames], dtype=torch.int32, device="cuda")
+    assert [harch.num_frames(int(v)) for v in valid] == frames
+    wave = synth.synth_wave(len(frames), 320 * (T - 1) + 400, 140).cuda()
+    runs = _pc_both(cg, wave, valid_len=valid)
+    print(f"\nCg={cg} padded T={T} valid {frames}: {[n for _, n in runs.values()]}")
+    _check_posconv(runs, cg, [(b * T, T) for b in range(len(frames))], "padded", valid=frames)
+
+
+def test_posconv_coverage_of_seams():
+    """The cases above through the launcher's rule alone (pair mode when Tmax <= 256, else ceil(Tmax / 512) blocks of two 256-row
+    halves per clip; 16-row MFMA tiles): together they reach pair mode, block mode with one and with two blocks per clip, a half
+    without a clip or without a row of its clip, and last row tiles of 1, 15 and 16 rows.  Runs nothing on the GPU."""
+    batches = [[T] * B for B, T in PC_UNIFORM] + PC_RAGGED + [[PC_PADDED[0]] * len(PC_PADDED[1])]
+    reached, last_tiles = set(), set()
+    for frames in batches:
+        Tmax, B = max(frames), len(frames)
+        pair = Tmax <= PC_HALF
+        blocks = -(-Tmax // (2 * PC_HALF))
+        reached.add("pair" if pair else f"blocks{blocks}")
+        halves = []                                                    # (clip or None, first row) of every half of every workgroup
+        if pair:
+            halves = [(c if c < B else None, 0) for c in range(2 * ((B + 1) // 2))]
+        else:
+            halves = [(c, (2 * j + h) * PC_HALF) for c in range(B) for j in range(blocks) for h in range(2)]
+        for c, r0 in halves:
+            if c is None or r0 >= frames[c]:
+                reached.add("empty half")
+            else:
+                last_tiles.add((min(frames[c] - r0, PC_HALF) - 1) % 16 + 1)
+        for T in frames:
+            if T < 64:
+                reached.add("clip shorter than the padding")
+        if pair and len(set(frames)) > 1:
+            reached.add("clips of different lengths in a workgroup")
+    print(sorted(reached), "last row tiles:", sorted(last_tiles))
+    assert {"pair", "blocks1", "blocks2", "empty half", "clip shorter than the padding", "clips of different lengths in a workgroup"} <= reached, reached
+    assert {1, 15, 16} <= last_tiles, last_tiles
+    assert any(len(f) % 2 for f in batches if max(f) <= PC_HALF)      # pair mode with an odd batch: a half without a clip
 
 
 # ------------------------------------------------------------------------------------------------------------ LayerNorm
