@@ -544,7 +544,15 @@ int si_profile_stop(si_ctx* ctx, si_profile_entry* out, int capacity, int* count
  *   stage<i>.rb<j>.t<n>          the intermediate of pair n of resblock j: conv 1's output before conv 2's leaky-ReLU, (B, Lo, C_i).
  *   stage<i>.rb<j>.t<n>.bf16     The operand-ready modes store it only as conv 2's 16-bit operand, type16(leaky_relu(t, 0.1)): the raw
  *   stage<i>.rb<j>.t<n>.f16      tensor, 2 bytes per element (bf16 mode / fp16 mode with SI_VOC_RES16=0).  ResBlock2 has no intermediate.
- *   stage<i>.rb<j>.p<n>          as its ".f16" namesake: the block's own stream for n < last, the running MRF sum for the last n */
+ *   stage<i>.rb<j>.p<n>          as its ".f16" namesake: the block's own stream for n < last, the running MRF sum for the last n
+ * Taps of the mel front-end (si_mel_frontend and its _varlen / _spans forms), under the same rule: fp32 copies behind the producing
+ * launch, changing no launch and no value.  "mel_frames" is sized on every call; the other two only while some capture is registered.
+ *   mel_peak                     max |x| of each clip with its spans zeroed, (B); only with normalize != 0
+ *   mel_frames                   the windowed frames as the DFT GEMMs read them, folded: (B, Tm, 1040) =
+ *                                [s_0 .. s_512 | 15 zeros | 0, d_1 .. d_511], s_k = w[k] + w[1024 - k], d_k = w[k] - w[1024 - k]
+ *                                (s_0 = w[0], s_512 = w[512]).  Ragged batches: frames past a clip's own are not written (stale).
+ *   mel_spec                     the DFT, (B, Tm, 1032) = [re(0..512) | 3 pad | im(0..512) | 3 pad]; the pad columns (513..515,
+ *                                1029..1031) hold whatever the workspace held, and so do the rows of frames past a ragged clip's own */
 int si_debug_capture(si_ctx* ctx, const char* name, float* dst, long capacity);
 long si_debug_size(si_ctx* ctx, const char* name);
 

@@ -1907,6 +1907,7 @@ static int mel_run(si_ctx* ctx, const float* wave22, const int32_t* mask_start, 
     if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: mel workspace carve exceeded its own estimate");
     const float* hann = reinterpret_cast<const float*>(ctx->fe_dev + ctx->fe_hann);
     if (normalize && (rc = si_launch_wave_peak(ctx, wave22, mask_start, mask_end, B, N22, peak, st, d_n, spans))) return rc;
+    if (normalize && !ctx->dbg_capture.empty() && (rc = si_tap(ctx, st, {peak, (long)B}, "mel_peak"))) return rc;   // (per-op tap)
     if ((rc = si_launch_mel_frames(ctx, wave22, mask_start, mask_end, peak, hann, B, N22, Tm, FE_HOP, FE_PAD, FE_NFFT, FE_KC, normalize, frames, st, d_n, d_tm, spans)))
         return rc;
     if ((rc = si_tap(ctx, st, {frames, (long)B * Tm * FE_FRAME}, "mel_frames"))) return rc;
@@ -1922,6 +1923,7 @@ static int mel_run(si_ctx* ctx, const float* wave22, const int32_t* mask_start, 
         p.pro_slope = 1.f; p.act = SI_ACT_NONE; p.alpha = 1.f; p.accumulate = 0;
         if ((rc = si_launch_tapgemm(ctx, SI_MATH_F32, p, st))) return rc;
     }
+    if (!ctx->dbg_capture.empty() && (rc = si_tap(ctx, st, {spec, (long)B * Tm * FE_LDSPEC}, "mel_spec"))) return rc;   // (per-op tap)
     return si_launch_mel_project(ctx, spec, FE_LDSPEC, FE_NBIN, FE_IMOFF, reinterpret_cast<const float*>(ctx->fe_dev + ctx->fe_basis),
                                  reinterpret_cast<const int32_t*>(ctx->fe_dev + ctx->fe_lo),
                                  reinterpret_cast<const int32_t*>(ctx->fe_dev + ctx->fe_hi), FE_NMEL, B, Tm, mel_out, st, d_tm);
