@@ -26,6 +26,9 @@
  *                           I_ea/hifi_gan/models.py:107-123 (called at I_ea/predict.py:189,203)
  *   si_wave_peak / si_gather_windows / si_patch_compose  <- the whole-clip generator call and int16 write-out, for a recording
  *                           that keeps its own samples outside the gaps      I_ea/predict.py:104,189,203-207
+ *   si_cut_clips / si_patch_regions  <- the same lines for a recording LONGER than one clip: the slices that turn one file into the
+ *                           clips the script takes one per run, and the write-out of many clips' gaps into the one long file
+ *                                                                             I_ea/predict.py:79-80,104,203-207
  *   si_load_weights      <- model.load_state_dict / generator.load_state_dict + remove_weight_norm + ApplyKmeans
  *                           I_ea/predict.py:117-122,149 ; I_ea/hifi_gan/models.py:125-132 ; I_ea/dataset/km_label.py:12-24
  *
@@ -472,6 +475,75 @@ typedef struct si_patch_table {
  * another clip, or whose blend region leaves the window's row. */
 int si_patch_compose(si_ctx* ctx, const float* orig, const si_span_table* spans, const int32_t* sample_len, const si_patch_table* patch,
                      const float* gen, int Lrow, const float* gain, int B, int N22, float* out_f32, int16_t* out_pcm, si_stream_t stream);
+
+/* ---- Long recordings: many context clips cut from, and patched back into, ONE recording -------------------------
+ * The reference's script handles one file of clip length per run (I_ea/predict.py:76-207).  A recording of any length is served as a
+ * set of context clips that start on the recording's 20 ms frame grid (frame f = 22.05 kHz sample 441 f = 16 kHz sample 320 f), each
+ * through the span-table calls above; the two calls below are the ends of that route. */
+
+/* The clips, cut on the device (stands for the script's per-file `librosa.load`, I_ea/predict.py:79-80, when the files are slices of
+ * one recording): out (C, L) row c = src[start[c] : start[c] + L].  src device fp32 (n_src), one channel, either sample rate.  start is
+ * given twice, the si_span_table rule: host_start (HOST int32 (C)) is validated -- any start < 0 or start + L > n_src refuses the call
+ * and nothing is launched -- and start (DEVICE int32 (C), the same values) is read.  n_src <= 2^31 - 1 - 2048.  Bits are copied
+ * unchanged (-0.0, NaN payloads). */
+int si_cut_clips(si_ctx* ctx, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L, float* out,
+                 si_stream_t stream);
+
+/* si_region_table: the blend regions of MANY context clips on the recording's own 22.05 kHz sample axis.  Span k < num_spans is
+ * samples [start[k], start[k] + len[k]) of the recording (len > 0; sorted by start, disjoint); its generated samples lie in row
+ * span_win[k] of `gen`; nothing at or past span_lim[k] -- the recording sample where the audio its context generated ends,
+ * start of the context + min(its samples, its generated samples), > start[k] -- is replaced.  Window w < num_windows is one row of
+ * `gen`: it belongs to context win_ctx[w] (the index into `gain`), its first sample is recording sample win_start[w] and it holds
+ * win_len[w] samples.  The kernel runs one workgroup per TOUCHED chunk of 2048 samples: entry q < num_chunks names chunk chunk[q]
+ * (strictly increasing, chunk * 2048 < N22) and the spans [k0[q], k1[q]) whose regions [max(start - fade, 0), min(start + len + fade,
+ * span_lim)) meet it (speech_inpainting_amd/gaps.py::region_chunks).  ramp as si_patch_table's.  host_* (HOST) are validated, the DEVICE
+ * copies are read: the si_span_table rule. */
+typedef struct si_region_table {
+    int32_t struct_size;            /* = sizeof(si_region_table) */
+    int32_t num_contexts;           /* C: entries of gain */
+    int32_t num_windows;            /* W: rows of gen */
+    int32_t num_spans;              /* K */
+    int32_t num_chunks;             /* Q: workgroups of the launch */
+    int32_t fade;                   /* cross-fade length in samples, >= 0 (0 = hard splice) */
+    const int32_t* host_start;      /* HOST (num_spans) */
+    const int32_t* host_len;        /* HOST (num_spans) */
+    const int32_t* host_span_win;   /* HOST (num_spans) */
+    const int32_t* host_span_lim;   /* HOST (num_spans) */
+    const int32_t* host_win_ctx;    /* HOST (num_windows) */
+    const int32_t* host_win_start;  /* HOST (num_windows) */
+    const int32_t* host_win_len;    /* HOST (num_windows) */
+    const int32_t* host_chunk;      /* HOST (num_chunks) */
+    const int32_t* host_k0;         /* HOST (num_chunks) */
+    const int32_t* host_k1;         /* HOST (num_chunks) */
+    const int32_t* start;           /* DEVICE copies of the ten */
+    const int32_t* len;
+    const int32_t* span_win;
+    const int32_t* span_lim;
+    const int32_t* win_ctx;
+    const int32_t* win_start;
+    const int32_t* win_len;
+    const int32_t* chunk;
+    const int32_t* k0;
+    const int32_t* k1;
+    const float* ramp;              /* DEVICE (fade), may be NULL when fade = 0 */
+} si_region_table;
+
+/* The write-out of the gaps of many context clips into the one recording (replaces I_ea/predict.py:203-207 per clip plus the host-side
+ * paste of each clip's gaps into the long file).  Per sample m of a listed chunk the weight is si_patch_compose's: the MAXIMUM over
+ * the chunk's spans of ramp[m - (s - fade)] on the rise, 1 in [s, s + len), ramp[s + len + fade - 1 - m] on the fall, 0 at and past the
+ * span's span_lim.  A sample of weight 0 is NOT WRITTEN: out_f32 / out_pcm keep what the caller put there (a copy of the recording).
+ * Otherwise g = gain[win_ctx[win]] * gen[win, m - win_start[win]] and the sample is g (weight 1) or fma(w, g, (1 - w) * orig[m]):
+ * si_patch_compose's roundings in its order, so every written sample equals what si_patch_compose writes for the context clip alone.
+ * orig device fp32 (N22), read only (never out_f32: a repeated call gives the same result); gen device fp32 (num_windows, Lrow); gain
+ * device fp32 (num_contexts) or NULL (= 1); out_f32 device fp32 (N22) and / or out_pcm device int16 (N22), si_pcm16's arithmetic on the
+ * same values (one of them may be NULL).  Sample indices are int32: N22 <= 2^31 - 1 - 2048.
+ * SI_EINVAL before any launch, naming the entry, for: NULL / mis-sized struct; fade < 0; both outputs NULL; N22 out of range; a span
+ * with len <= 0, start < 0, span_lim <= start or span_lim > N22, or not after its predecessor's end; a window index or context index
+ * out of range; a window with start < 0, len < 0 or > Lrow, start + len > N22; a span whose region leaves its window's row; chunks
+ * not strictly increasing or at / past N22; k0 / k1 outside 0 <= k0 <= k1 <= num_spans; a region that meets a chunk the list lacks, or
+ * whose span is outside that chunk's [k0, k1).  num_chunks = 0 launches nothing and succeeds. */
+int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_table* table, const float* gen, int Lrow, const float* gain,
+                     float* out_f32, int16_t* out_pcm, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

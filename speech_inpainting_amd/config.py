@@ -55,6 +55,8 @@ class PredictConfig:
     masks: Optional[list] = None  # optional `masks:` list of (start_pos_in_sec, end_pos_in_sec): several gaps in the one file
     patch_fade_ms: Optional[float] = None   # optional `patch:` mapping ({fade_ms: 5}): also write patched.wav (the recording with
                                             # only the gaps filled); None without the key
+    long: Optional[dict] = None   # optional `long:` mapping ({clip_s: 4.0, context_s: 1.0, batch: 32}): the file is a recording of any
+                                  # length, served as context clips (engine.patch_recording); None without the key
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -123,6 +125,20 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             patch_fade_ms = float(pm.get("fade_ms", 5))
             if patch_fade_ms < 0:
                 raise ValueError(f"{path}: patch.fade_ms = {patch_fade_ms} is negative")
+        long_cfg = None
+        if "long" in data:
+            lm = data["long"] if data["long"] is not None else {}
+            if not isinstance(lm, dict):
+                raise ValueError(f"{path}: `long:` must be a mapping (clip_s: <seconds>, context_s: <seconds>, batch: <contexts per pass>)")
+            long_cfg = {"clip_s": 4.0, "context_s": 1.0, "batch": 32}
+            for key, val in lm.items():
+                if key not in long_cfg:
+                    raise ValueError(f"{path}: unknown key `{key}` in `long:` (it takes clip_s, context_s, batch)")
+                long_cfg[key] = int(val) if key == "batch" else float(val)
+                if long_cfg[key] < 0:
+                    raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
+            if long_cfg["batch"] < 1 or long_cfg["clip_s"] <= 2 * long_cfg["context_s"]:
+                raise ValueError(f"{path}: `long:` needs batch >= 1 and clip_s > 2 * context_s, got {long_cfg}")
         return PredictConfig(
             dataset=ds,
             wave_path=data["wave"][ds]["wave_path"],
@@ -138,7 +154,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_type=str(data["hubert_model"]["type"]),
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
-            raw=data, masks=masks, patch_fade_ms=patch_fade_ms)
+            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

@@ -2007,6 +2007,90 @@ int si_patch_compose(si_ctx* ctx, const float* orig, const si_span_table* spans,
     return si_launch_patch_compose(ctx, orig, sp, pt, gen, Lrow, gain, B, N22, out_f32, out_pcm, static_cast<hipStream_t>(stream));
 }
 
+// ---- long recordings
+static const long SI_MAX_REC = 0x7fffffffL - 2048;      // int32 sample indices, one chunk of headroom for the chunk's end
+
+int si_cut_clips(si_ctx* ctx, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L, float* out,
+                 si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!src || !host_start || !start || !out || n_src <= 0 || C <= 0 || L <= 0) return si_fail(ctx, SI_EINVAL, "si_cut_clips: NULL / empty argument");
+    if ((long)n_src > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_cut_clips: a source of %d samples, at most %ld", n_src, SI_MAX_REC);
+    if (C > 65535) return si_fail(ctx, SI_EINVAL, "si_cut_clips: %d clips in one call, at most 65535 (the launch grid's second dimension)", C);
+    for (int c = 0; c < C; ++c) {
+        const long s = host_start[c];
+        if (s < 0 || s + L > n_src)
+            return si_fail(ctx, SI_EINVAL, "si_cut_clips: clip %d = samples [%ld, %ld) is outside the source's %d samples", c, s, s + L, n_src);
+    }
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    return si_launch_cut_clips(ctx, src, start, C, L, out, static_cast<hipStream_t>(stream));
+}
+
+int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_table* table, const float* gen, int Lrow, const float* gain,
+                     float* out_f32, int16_t* out_pcm, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!orig || N22 <= 0) return si_fail(ctx, SI_EINVAL, "si_patch_regions: NULL / empty argument");
+    if ((long)N22 > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_patch_regions: a recording of %d samples, at most %ld", N22, SI_MAX_REC);
+    if (!out_f32 && !out_pcm) return si_fail(ctx, SI_EINVAL, "si_patch_regions: both outputs are NULL");
+    const si_region_table* t = table;
+    if (!t || t->struct_size != (int32_t)sizeof(si_region_table)) return si_fail(ctx, SI_EINVAL, "si_patch_regions: si_region_table size mismatch");
+    if (t->fade < 0 || (long)t->fade + N22 > 0x7fffffffL) return si_fail(ctx, SI_EINVAL, "si_patch_regions: fade of %d samples is negative or too long", t->fade);
+    const int C = t->num_contexts, W = t->num_windows, K = t->num_spans, Q = t->num_chunks, fade = t->fade;
+    if (C < 0 || W < 0 || K < 0 || Q < 0)
+        return si_fail(ctx, SI_EINVAL, "si_patch_regions: region table with %d contexts / %d windows / %d spans / %d chunks", C, W, K, Q);
+    if (fade > 0 && K > 0 && !t->ramp) return si_fail(ctx, SI_EINVAL, "si_patch_regions: region table with NULL ramp");
+    if (W > 0 && (!t->host_win_ctx || !t->host_win_start || !t->host_win_len || !t->win_ctx || !t->win_start || !t->win_len || !gen || Lrow <= 0))
+        return si_fail(ctx, SI_EINVAL, "si_patch_regions: %d windows but NULL window arrays / generator rows", W);
+    if (K > 0 && (!t->host_start || !t->host_len || !t->host_span_win || !t->host_span_lim || !t->start || !t->len || !t->span_win || !t->span_lim))
+        return si_fail(ctx, SI_EINVAL, "si_patch_regions: %d spans but NULL span arrays", K);
+    if (Q > 0 && (!t->host_chunk || !t->host_k0 || !t->host_k1 || !t->chunk || !t->k0 || !t->k1))
+        return si_fail(ctx, SI_EINVAL, "si_patch_regions: %d chunks but NULL chunk arrays", Q);
+    for (int w = 0; w < W; ++w) {
+        const long c = t->host_win_ctx[w], s = t->host_win_start[w], l = t->host_win_len[w];
+        if (c < 0 || c >= C) return si_fail(ctx, SI_EINVAL, "si_patch_regions: window %d names context %ld of %d", w, c, C);
+        if (s < 0 || l < 0 || l > Lrow || s + l > N22)
+            return si_fail(ctx, SI_EINVAL, "si_patch_regions: window %d = samples [%ld, +%ld) is outside the recording (%d samples, rows of %d)", w, s, l,
+                           N22, Lrow);
+    }
+    for (int q = 0; q < Q; ++q) {
+        const long c = t->host_chunk[q];
+        if (c < 0 || c * 2048 >= N22) return si_fail(ctx, SI_EINVAL, "si_patch_regions: chunk entry %d names chunk %ld, at or past the recording's %d samples", q, c, N22);
+        if (q && c <= t->host_chunk[q - 1])
+            return si_fail(ctx, SI_EINVAL, "si_patch_regions: chunk entry %d names chunk %ld after chunk %d: not strictly increasing", q, c, t->host_chunk[q - 1]);
+        if (t->host_k0[q] < 0 || t->host_k0[q] > t->host_k1[q] || t->host_k1[q] > K)
+            return si_fail(ctx, SI_EINVAL, "si_patch_regions: chunk entry %d walks spans [%d, %d) of %d", q, t->host_k0[q], t->host_k1[q], K);
+    }
+    for (int k = 0; k < K; ++k) {
+        const long s = t->host_start[k], l = t->host_len[k], lim = t->host_span_lim[k];
+        if (s < 0 || l <= 0 || lim <= s || lim > N22)
+            return si_fail(ctx, SI_EINVAL, "si_patch_regions: span %d = samples [%ld, +%ld) with lim %ld does not lie in the recording's %d samples", k, s, l, lim, N22);
+        if (k && s < (long)t->host_start[k - 1] + t->host_len[k - 1])
+            return si_fail(ctx, SI_EINVAL, "si_patch_regions: span %d starts at %ld, before span %d ends: unsorted or overlapping", k, s, k - 1);
+    }
+    int q = 0;                                                     // the spans are sorted: the chunk list is walked (nearly) once
+    for (int k = 0; k < K; ++k) {
+        const long s = t->host_start[k], l = t->host_len[k], lim = t->host_span_lim[k];
+        const int w = t->host_span_win[k];
+        if (w < 0 || w >= W) return si_fail(ctx, SI_EINVAL, "si_patch_regions: span %d names window %d of %d", k, w, W);
+        const long ra = std::max(s - fade, 0L), rb = std::min(s + l + fade, lim);
+        if (ra < t->host_win_start[w] || rb > (long)t->host_win_start[w] + t->host_win_len[w])
+            return si_fail(ctx, SI_EINVAL, "si_patch_regions: span %d blends samples [%ld, %ld), its window's row holds [%d, %d)", k, ra, rb,
+                           t->host_win_start[w], t->host_win_start[w] + t->host_win_len[w]);
+        const long qa = ra / 2048, qb = (rb - 1) / 2048;
+        while (q > 0 && t->host_chunk[q - 1] >= qa) --q;            // a region may start in the chunk its predecessor ended in
+        for (long c = qa; c <= qb; ++c) {
+            while (q < Q && t->host_chunk[q] < c) ++q;
+            if (q >= Q || t->host_chunk[q] != c)
+                return si_fail(ctx, SI_EINVAL, "si_patch_regions: span %d blends samples [%ld, %ld), the chunk list lacks chunk %ld", k, ra, rb, c);
+            if (k < t->host_k0[q] || k >= t->host_k1[q])
+                return si_fail(ctx, SI_EINVAL, "si_patch_regions: chunk entry %d (chunk %ld) walks spans [%d, %d) and omits span %d, which blends samples [%ld, %ld)",
+                               q, c, t->host_k0[q], t->host_k1[q], k, ra, rb);
+        }
+    }
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    const SiRegions rt{t->start, t->len, t->span_win, t->span_lim, t->win_ctx, t->win_start, t->chunk, t->k0, t->k1, t->ramp, fade};
+    return si_launch_patch_regions(ctx, orig, rt, Q, gen, Lrow, gain, N22, out_f32, out_pcm, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"
 
 extern "C" {

@@ -333,6 +333,17 @@ int si_launch_gather_windows(si_ctx* ctx, const float* ext, const int32_t* win, 
 // out / pcm (B, N22; either may be null) = orig outside the blend regions of `sp`, (1 - w) orig + w gain[b] gen inside; gain null = 1
 int si_launch_patch_compose(si_ctx* ctx, const float* orig, const SiSpans& sp, const SiPatch& pt, const float* gen, int Lrow, const float* gain,
                             int B, int N22, float* out, int16_t* pcm, hipStream_t st);
+// long recordings.  out (C, L) row c = src[start[c] : start[c] + L]; start device int32 (C), validated by the caller
+int si_launch_cut_clips(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float* out, hipStream_t st);
+// the device half of si_region_table: per span, per window and per chunk arrays on the recording's own sample axis
+struct SiRegions {
+    const int32_t* start; const int32_t* len; const int32_t* span_win; const int32_t* span_lim;
+    const int32_t* win_ctx; const int32_t* win_start; const int32_t* chunk; const int32_t* k0; const int32_t* k1;
+    const float* ramp; int fade;
+};
+// one workgroup per listed chunk: the blended samples of its spans written into out / pcm (N22; either may be null), the rest untouched
+int si_launch_patch_regions(si_ctx* ctx, const float* orig, const SiRegions& rt, int Q, const float* gen, int Lrow, const float* gain,
+                            int N22, float* out, int16_t* pcm, hipStream_t st);
 
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16

@@ -5,6 +5,9 @@
 // The time map between the generator's samples and the input's is the identity (vocoder_kernels.hip, extend_mel: stretched frame t is
 // centred at input sample (t + 0.5) * 256 and the generator emits 256 samples per stretched frame), so sample m of a window row that
 // starts at stretched frame w0 is input sample w0 * hop + m: no resampling, no drift.
+// Recordings longer than one clip add the two ends of the route that serves them as context clips:
+//   cut_clips_kernel        rows src[start[c] : start[c] + L] of the 1-D recording -> the context clips (C, L), either sample rate
+//   patch_regions_kernel    the blended samples of many contexts' gaps written straight into the one long output, chunk by touched chunk
 #include "common.h"
 
 // ------------------------------------------------------------------------------------------------ window gather
@@ -131,6 +134,91 @@ int si_launch_patch_compose(si_ctx* ctx, const float* orig, const SiSpans& sp, c
     if (B <= 0 || N22 <= 0) return SI_OK;
     si_prof_begin(ctx, "patch_compose", 0.0, (double)B * N22 * (4.0 + (out ? 4.0 : 0.0) + (pcm ? 2.0 : 0.0)), st);
     patch_compose_kernel<<<dim3((N22 + PC_CHUNK - 1) / PC_CHUNK, B), 256, 0, st>>>(orig, sp, pt, gen, Lrow, gain, N22, out, pcm);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ long recordings
+// grid (ceil(L / PC_CHUNK), C), 256 threads: one workgroup copies samples [x0, x1) of context clip c from src + start[c].  start is
+// 441 f or 320 f, so the source row is generally off the 16-byte grid, and the destination row is when L % 4 != 0: alignment is decided
+// PER ROW and per side as in gather_windows_kernel (x0 is a multiple of PC_CHUNK, so a chunk has its row's alignment) -- 16-byte stores
+// into an aligned destination, fed by 16-byte loads when the source row is aligned too and by scalar loads otherwise; scalar accesses
+// into a destination that is not.  The C ABI checked 0 <= start and start + L <= n_src on the host copy.
+__global__ __launch_bounds__(256) void cut_clips_kernel(const float* __restrict__ src, const int32_t* __restrict__ start, int L, float* __restrict__ out) {
+    const int c = blockIdx.y;
+    const int x0 = blockIdx.x * PC_CHUNK, x1 = min(x0 + PC_CHUNK, L);
+    const float* s = src + (size_t)start[c];
+    float* d = out + (size_t)c * L;
+    const bool dvec = (reinterpret_cast<size_t>(d) & 15) == 0, svec = (reinterpret_cast<size_t>(s) & 15) == 0;
+#pragma unroll
+    for (int r = 0; r < PC_CHUNK / 1024; ++r) {
+        const int i = x0 + r * 1024 + threadIdx.x * 4;
+        if (dvec && i + 4 <= x1) {
+            float4 v;
+            if (svec) {
+                v = *reinterpret_cast<const float4*>(s + i);
+            } else {
+                v.x = s[i];
+                v.y = s[i + 1];
+                v.z = s[i + 2];
+                v.w = s[i + 3];
+            }
+            *reinterpret_cast<float4*>(d + i) = v;
+        } else {
+            for (int j = i; j < x1 && j < i + 4; ++j) d[j] = s[j];
+        }
+    }
+}
+
+int si_launch_cut_clips(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float* out, hipStream_t st) {
+    if (C <= 0 || L <= 0) return SI_OK;
+    si_prof_begin(ctx, "cut_clips", 0.0, 8.0 * C * L, st);
+    cut_clips_kernel<<<dim3((L + PC_CHUNK - 1) / PC_CHUNK, C), 256, 0, st>>>(src, start, L, out);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+// grid (Q), 256 threads: workgroup q owns samples [c0, c1) of chunk rt.chunk[q] of the RECORDING and walks spans [k0[q], k1[q]) per
+// sample -- patch_compose_kernel's blend path on the recording's own sample axis (q is workgroup-uniform: the table arrives through
+// scalar loads).  The spans of a chunk may belong to different contexts; each carries its own span_lim (where its context's generated
+// audio ends) and, through its window, its own gain.  A sample of weight 0 is NOT written: out / pcm hold the caller's copy of the
+// recording there, so the untouched chunks -- nearly all of a long recording -- cost nothing.  The written samples are
+// patch_compose_kernel's, rounding for rounding: gain * gen; then that product (w == 1) or fma(w, g, (1 - w) * orig).  orig is the
+// recording, never out.  The C ABI checked on the host copy that every region lies inside its window's row and inside [0, N22).
+__global__ __launch_bounds__(256) void patch_regions_kernel(const float* __restrict__ orig, SiRegions rt, const float* __restrict__ gen, int Lrow,
+                                                            const float* __restrict__ gain, int N22, float* __restrict__ out, int16_t* __restrict__ pcm) {
+    const int q = blockIdx.x;
+    const int c0 = rt.chunk[q] * PC_CHUNK, c1 = min(c0 + PC_CHUNK, N22);
+    const int k0 = rt.k0[q], k1 = rt.k1[q], fade = rt.fade;
+    for (int m = c0 + threadIdx.x; m < c1; m += 256) {
+        float w = 0.f;
+        int win = 0;
+        for (int k = k0; k < k1; ++k) {                              // uniform loop: s, l, span_lim, span_win come through scalar loads
+            if (m >= rt.span_lim[k]) continue;
+            const int s = rt.start[k], l = rt.len[k];
+            const int d = m - s;
+            float wk = 0.f;
+            if (d < 0) { if (d >= -fade) wk = rt.ramp[d + fade]; }
+            else if (d < l) wk = 1.f;
+            else if (d - l < fade) wk = rt.ramp[fade - 1 - (d - l)];
+            if (wk > w) { w = wk; win = rt.span_win[k]; }
+        }
+        if (w == 0.f) continue;
+        const float g0 = gain ? gain[rt.win_ctx[win]] : 1.f;
+        const float g = __fmul_rn(g0, gen[(size_t)win * Lrow + (m - rt.win_start[win])]);
+        const float v = w == 1.f ? g : __fmaf_rn(w, g, __fmul_rn(1.f - w, orig[m]));
+        if (out) out[m] = v;
+        if (pcm) pcm[m] = pc_pcm16(v);
+    }
+}
+
+int si_launch_patch_regions(si_ctx* ctx, const float* orig, const SiRegions& rt, int Q, const float* gen, int Lrow, const float* gain,
+                            int N22, float* out, int16_t* pcm, hipStream_t st) {
+    if (Q <= 0) return SI_OK;
+    si_prof_begin(ctx, "patch_regions", 0.0, (double)Q * PC_CHUNK * (8.0 + (out ? 4.0 : 0.0) + (pcm ? 2.0 : 0.0)), st);
+    patch_regions_kernel<<<dim3(Q), 256, 0, st>>>(orig, rt, gen, Lrow, gain, N22, out, pcm);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;

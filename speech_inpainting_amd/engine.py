@@ -19,7 +19,7 @@ import torch
 from .arch import HubertArch, VocoderArch
 from .checkpoint import flatten_checkpoint
 from . import gaps as G
-from .native import NativeContext, PatchTable, SpanTable, make_desc
+from .native import NativeContext, PatchTable, RegionTable, SpanTable, make_desc
 
 
 def mask_samples_from_frames(frame_pos: int, frame_len: int):
@@ -530,6 +530,90 @@ class InpaintingEngine:
         table = PatchTable(rows, [b for b in range(B) for _ in spans[b]], [min(n, w) for n, w in zip(n22, wl)], fade, self.device)
         l22 = None if len22 is None else torch.tensor(n22, dtype=torch.int32).to(self.device)
         return self._compose(wave22.contiguous(), tab22, table, wave.contiguous(), n22 if len22 is not None else None, l22, pcm)
+
+    # ---- recordings longer than one clip: context clips cut from, and patched back into, the one recording
+    def _region_table(self, ctxs: Sequence[dict], plan: Dict[str, object], spans22: Sequence[Sequence[Sequence[int]]]) -> RegionTable:
+        """One batch of contexts, their own 22.05 kHz spans (local samples) and the `plan_patch` of those spans -> the RegionTable on
+        the recording's sample axis: every local sample shifted by 441 * the context's first frame."""
+        hop, fade = plan["hop"], plan["fade"]
+        off = [441 * int(c["start"]) for c in ctxs]
+        spans, regions, k = [], [], 0
+        for b, clip in enumerate(spans22):
+            for (s, l), reg in zip(clip, G.blend_regions(clip, plan["n22"][b], plan["lim"][b], fade)):
+                if reg is not None:
+                    spans.append((off[b] + s, l, plan["span_win"][k], off[b] + plan["lim"][b]))
+                    regions.append((off[b] + reg[0], off[b] + reg[1]))
+                k += 1
+        wins = [(b, off[b] + w0 * hop, (w1 - w0) * hop) for b, w0, w1 in plan["wins"]]
+        return RegionTable(spans, wins, G.region_chunks(regions), len(ctxs), fade, self.device)
+
+    def patch_recording(self, wave22, gaps, wave16=None, fade: int = 110, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
+                        pcm: bool = False) -> Dict[str, object]:
+        """Patch mode for a recording of ANY length: wave22 (N22,) is the recording at 22.05 kHz (tensor or array, host or device),
+        gaps = (first frame, frame count) pairs on ITS 20 ms grid (frame p = samples [441 p, 441 (p + 1))).  gaps.plan_contexts groups
+        the gaps into context clips of clip_frames frames that start on the recording's frame grid; per batch of at most `batch`
+        contexts the clips are cut on the device (si_cut_clips; from wave16 (N16,), the same recording at 16 kHz, at 320 f when it is
+        given, else the cut 22.05 kHz clips are resampled), go through ONE multi-gap pass with every gap they hold masked (their own
+        and the neighbours' that fall into them), the generator runs over the windows of the OWN gaps only, and one si_patch_regions
+        launch writes the blended samples into `patched`, a copy of the recording.  Every written sample is the one
+        patch_multigap_batch gives for that context clip; every other sample is wave22's, bit for bit.
+        -> patched (N22,) fp32, patched_pcm (N22,) int16 with pcm=True, contexts (the plan), labels (flat, int64) / label_off
+        (gaps + 1): the predicted codewords per gap in sorted gap order, each from the context that owns the gap.
+        A recording without gaps comes back as an exact copy and no model kernel is launched."""
+        self._need(head=True, codebook=True, what="patch_recording")
+        as1d = lambda x: torch.as_tensor(x).to(self.device, torch.float32).reshape(-1).contiguous()
+        wave22 = as1d(wave22)
+        wave16 = None if wave16 is None else as1d(wave16)
+        N22, fade, clip_frames, batch = wave22.numel(), int(fade), int(clip_frames), int(batch)
+        if batch <= 0:
+            raise ValueError(f"patch_recording: batch = {batch}")
+        n_rec = N22 // 441
+        whole = n_rec <= clip_frames                                   # one context: the whole recording, with its true sample counts
+        L22 = N22 if whole else clip_frames * 441
+        if wave16 is not None:
+            L16 = wave16.numel() if whole else clip_frames * 320
+        else:
+            L16 = -(-L22 * 16000 // 22050)
+        patched = wave22.clone()
+        out: Dict[str, object] = {"patched": patched}
+        if pcm:
+            out["patched_pcm"] = self.to_int16(wave22)
+        lim = min(self.ctx.num_frames(L16), self.ctx.mel_frames(L22)) if L16 > 0 and L22 > 0 else 0
+        ctxs = G.plan_contexts(gaps, n_rec, clip_frames, min_context, lim_frames=lim, fade_frames=max(-(-fade // 441), 1))
+        n_gaps = sum(len(c["own"]) for c in ctxs)
+        out["contexts"] = ctxs
+        labels, counts = [], [0] * n_gaps
+        for i in range(0, len(ctxs), batch):
+            cb = ctxs[i:i + batch]
+            B = len(cb)
+            w22 = self.ctx.cut_clips(wave22, [441 * c["start"] for c in cb], L22)
+            w16 = self.resample(w22, 22050, 16000) if wave16 is None else self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16)
+            tb = self.gap_tables([c["own"] + c["foreign"] for c in cb], [L16] * B, [L22] * B)
+            res = self.predict_multigap_batch(w16, w22, None, tables=tb, vocode=False)
+            own22 = G.spans22([c["own"] for c in cb], [L22] * B)
+            plan = self.plan_patch(own22, [L22] * B, fade)
+            if plan["wins"]:
+                ext, _ = self._stretch(res["mel"], plan["hop"], None, plan["windows"])
+                gen = self._vocode_gathered(ext, plan["wins"])
+                # the front-end divided by this peak and multiplied by 0.95 (I_ea/predict.py:104), with ALL gaps of the context zeroed
+                gain = self.ctx.wave_peak(w22, tb["tab22"]) / 0.95
+                self.ctx.patch_regions(wave22, self._region_table(cb, plan, own22), gen, gain, patched, out.get("patched_pcm"))
+            # labels of the own gaps: clip b's gaps lie sorted in the flat label vector, gap by gap
+            idx = []
+            for b, c in enumerate(cb):
+                o = tb["label_off"][b]
+                for p, l in tb["gaps"][b]:
+                    if (p, l) in c["own"]:
+                        counts[c["own_index"][c["own"].index((p, l))]] = l
+                        idx += range(o, o + l)
+                    o += l
+            labels.append(res["labels"][torch.tensor(idx, dtype=torch.int64).to(self.device)])
+        out["labels"] = torch.cat(labels) if labels else torch.zeros(0, dtype=torch.int64, device=self.device)
+        off = [0]
+        for n in counts:
+            off.append(off[-1] + n)
+        out["label_off"] = off
+        return out
 
     def predict_multigap_batch(self, wave16: torch.Tensor, mel_or_wave22: torch.Tensor, gaps, len16: Optional[Sequence[int]] = None,
                                len22: Optional[Sequence[int]] = None, mel_len: Optional[Sequence[int]] = None,

@@ -205,3 +205,105 @@ def plan_patch_windows(regions: Sequence[Optional[Gap]], t_out: int, hop: int, r
         k0, k1 = kept_region(*wins[which[k]], t_out, rf)
         assert k0 * hop <= a and b <= k1 * hop, f"region [{a}, {b}) leaves the kept frames [{k0}, {k1}) of its window"
     return wins, which
+
+
+# ---- recordings longer than one clip: gaps on the recording's frame grid -> context clips
+PC_CHUNK = 2048         # samples per workgroup of patch_regions_kernel (patch_kernels.hip)
+
+
+def plan_contexts(gaps: Sequence[Sequence[int]], n_rec_frames: int, clip_frames: int = 200, min_context: int = 50,
+                  lim_frames: Optional[int] = None, fade_frames: int = 1) -> List[dict]:
+    """Gaps of a RECORDING, (first frame, frame count) pairs on its 20 ms grid of n_rec_frames frames, -> the context clips that serve
+    them.  The gaps are sorted and grouped greedily: a group starts with the first ungrouped gap and takes the next one while
+    (that gap's end - the group's first start) <= clip_frames - 2 * min_context, up to MAX_SPANS gaps.  A group's context is
+    min(clip_frames, n_rec_frames) frames long and starts at frame clamp((first start + last end) // 2 - clip_frames // 2, 0,
+    max(n_rec_frames - clip_frames, 0)): every own gap has at least min_context frames of the recording on each side unless the
+    recording ends there.  A recording of at most clip_frames frames is ONE context that owns every gap.
+    lim_frames: the frames of a context clip that exist on the encoder AND the mel side (`gap_tables`' min(T, Tm)); default = all.
+    -> per context a dict: start (frame), frames, own (the group's gaps, LOCAL frames), own_index (their places in the sorted gap
+    list), foreign (every other gap that meets the context's usable frames [0, lim), clipped to them, local frames: its samples are
+    unknown, so it is masked, predicted and spliced in the pass like an own gap, but never composed from this context).
+    Raises a ValueError naming the gap in RECORDING frames for: a non-pair entry, a frame count <= 0, a gap outside [0, n_rec_frames),
+    overlapping gaps, a gap longer than clip_frames - 2 * min_context, an own gap that does not fit [0, lim) of its context (a gap
+    in the recording's last frame: the encoder has one frame fewer than the mel), own + foreign gaps above MAX_SPANS, and two gaps of
+    DIFFERENT groups fewer than 2 * fade_frames frames apart (their cross-fades, fade_frames frames on each side, would overlap
+    across contexts -- it takes a cluster of gaps longer than clip_frames - 2 * min_context)."""
+    n_rec, clip, ctx_min, ff = int(n_rec_frames), int(clip_frames), int(min_context), int(fade_frames)
+    if clip <= 0 or ctx_min < 0 or clip - 2 * ctx_min <= 0 or ff < 0:
+        raise ValueError(f"plan_contexts: clip_frames = {clip}, min_context = {ctx_min}, fade_frames = {ff}: the clip must be longer than two contexts")
+    try:
+        g = sorted((int(p), int(l)) for p, l in gaps)
+    except (TypeError, ValueError):
+        bad = next((k for k, e in enumerate(gaps) if not _is_pair(e)), None)
+        raise ValueError(f"recording: gap {bad} = {gaps[bad] if bad is not None else gaps!r} is not a (first frame, frame count) pair") from None
+    budget = clip - 2 * ctx_min
+    for k, (p, l) in enumerate(g):
+        if l <= 0:
+            raise ValueError(f"recording: gap {k} = ({p}, {l}) has no frames")
+        if p < 0 or p + l > n_rec:
+            raise ValueError(f"recording: gap {k} = frames [{p}, {p + l}) does not fit the recording ({n_rec} frames)")
+        if k and p < g[k - 1][0] + g[k - 1][1]:
+            raise ValueError(f"recording: gap {k} = frames [{p}, {p + l}) overlaps gap {k - 1} = [{g[k - 1][0]}, {g[k - 1][0] + g[k - 1][1]})")
+    n_ctx = min(clip, n_rec)
+    lim = n_ctx if lim_frames is None else min(int(lim_frames), n_ctx)
+    groups: List[List[int]] = []
+    if n_rec <= clip:
+        if len(g) > MAX_SPANS:
+            raise ValueError(f"recording: {len(g)} gaps in one context of {n_rec} frames, more than the {MAX_SPANS} a clip may carry")
+        groups = [list(range(len(g)))] if g else []
+    else:
+        for k, (p, l) in enumerate(g):
+            if l > budget:
+                raise ValueError(f"recording: gap {k} = frames [{p}, {p + l}) is longer than the {budget} frames a context of {clip} frames "
+                                 f"leaves between two contexts of {ctx_min}")
+            if groups and len(groups[-1]) < MAX_SPANS and p + l - g[groups[-1][0]][0] <= budget:
+                groups[-1].append(k)
+            else:
+                groups.append([k])
+    group_of = {k: i for i, grp in enumerate(groups) for k in grp}
+    for k in range(1, len(g)):
+        if group_of[k] != group_of[k - 1] and g[k][0] - (g[k - 1][0] + g[k - 1][1]) < 2 * ff:
+            raise ValueError(f"recording: gap {k} = frames [{g[k][0]}, {g[k][0] + g[k][1]}) lies {g[k][0] - g[k - 1][0] - g[k - 1][1]} frames after gap "
+                             f"{k - 1}, which another context serves: their cross-fades ({ff} frames each side) would overlap across contexts")
+    out = []
+    for grp in groups:
+        first, last = g[grp[0]][0], g[grp[-1]][0] + g[grp[-1]][1]
+        f = min(max((first + last) // 2 - clip // 2, 0), max(n_rec - clip, 0))
+        own, foreign = [], []
+        for k, (p, l) in enumerate(g):
+            if k in grp:
+                if p - f < 0 or p + l - f > lim:
+                    raise ValueError(f"recording: gap {k} = frames [{p}, {p + l}) does not fit the usable frames [{f}, {f + lim}) of its context")
+                own.append((p - f, l))
+            else:
+                a, b = max(p, f), min(p + l, f + lim)
+                if a < b:
+                    foreign.append((a - f, b - a))
+        if len(own) + len(foreign) > MAX_SPANS:
+            k = grp[0]
+            raise ValueError(f"recording: the context of gap {k} = frames [{g[k][0]}, {g[k][0] + g[k][1]}) holds {len(own)} gaps of its own and "
+                             f"{len(foreign)} of other contexts, more than the {MAX_SPANS} a clip may carry")
+        out.append({"start": f, "frames": n_ctx, "own": own, "own_index": list(grp), "foreign": foreign})
+    return out
+
+
+def region_chunks(regions: Sequence[Gap], chunk: int = PC_CHUNK) -> List[Tuple[int, int, int]]:
+    """Blend regions [a, b) on the recording's sample axis, sorted by a with non-decreasing b (sorted disjoint spans widened by one
+    fade), -> the chunks of `chunk` samples they touch, strictly increasing, each as (chunk index, k0, k1): regions [k0, k1) are
+    the ones that meet it.  The chunk list of si_region_table: one workgroup per entry."""
+    out: List[Tuple[int, int, int]] = []
+    for k, (a, b) in enumerate(regions):
+        a, b = int(a), int(b)
+        if b <= a:
+            raise ValueError(f"region {k} = [{a}, {b}) is empty")
+        if k and (a < int(regions[k - 1][0]) or b < int(regions[k - 1][1])):
+            raise ValueError(f"region {k} = [{a}, {b}) is not sorted after region {k - 1}")
+        for c in range(a // chunk, (b - 1) // chunk + 1):
+            j = len(out) - 1
+            while j >= 0 and out[j][0] > c:
+                j -= 1
+            if j >= 0 and out[j][0] == c:
+                out[j] = (c, out[j][1], k + 1)
+            else:
+                out.append((c, k, k + 1))
+    return out

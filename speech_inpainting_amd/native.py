@@ -29,7 +29,8 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_vocoder_samples", "si_profile_start", "si_profile_filter", "si_profile_stop",
            "si_debug_capture", "si_debug_size",
            "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
-           "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose"]
+           "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
+           "si_cut_clips", "si_patch_regions"]
 SI_MAX_SPANS = 16
 
 
@@ -147,6 +148,36 @@ class PatchTable:
         o = [0, 4 * W, 8 * W, 12 * W, 12 * W + 4 * S, 12 * W + 4 * S + 4 * B]
         return PatchTableStruct(C.sizeof(PatchTableStruct), B, W, S, self.fade, 0, h + o[0], h + o[1], h + o[2], h + o[3], h + o[4],
                                 d + o[1], d + o[2], d + o[3], d + o[4], d + o[5])
+
+
+class RegionTableStruct(C.Structure):
+    """Mirror of si_region_table."""
+    _HOST = ("start", "len", "span_win", "span_lim", "win_ctx", "win_start", "win_len", "chunk", "k0", "k1")
+    _fields_ = ([(n, C.c_int32) for n in ("struct_size", "num_contexts", "num_windows", "num_spans", "num_chunks", "fade")] +
+                [("host_" + n, C.c_void_p) for n in _HOST] + [(n, C.c_void_p) for n in _HOST] + [("ramp", C.c_void_p)])
+
+
+class RegionTable:
+    """The blend regions of many context clips on the recording's own 22.05 kHz sample axis, as si_region_table takes them:
+    spans = (start, len, window, lim) per span, sorted and disjoint (lim: the recording sample where its context's generated audio
+    ends); windows = (context, first recording sample, samples) per generator row; chunks = (chunk, k0, k1) per touched chunk of 2048
+    samples (gaps.region_chunks); n_contexts = entries of the gain vector; fade in samples.  Like PatchTable: the host words the
+    library validates and ONE device tensor [start | len | span_win | span_lim | win_ctx | win_start | win_len | chunk | k0 | k1 |
+    ramp (fp32 bits)] the kernel reads -- one array, one copy."""
+
+    def __init__(self, spans, windows, chunks, n_contexts: int, fade: int, device):
+        from .gaps import fade_ramp
+        self.K, self.W, self.Q, self.C, self.fade = len(spans), len(windows), len(chunks), int(n_contexts), int(fade)
+        cols = [[int(r[j]) for r in rows] for rows, n in ((spans, 4), (windows, 3), (chunks, 3)) for j in range(n)]
+        ints = np.array([v for col in cols for v in col], dtype=np.int32)
+        self.host = np.ascontiguousarray(np.concatenate([ints, fade_ramp(self.fade).view(np.int32), np.zeros(1, np.int32)]))   # (+ 1: never empty)
+        self.dev = torch.from_numpy(self.host).to(device, non_blocking=True)
+
+    def struct(self) -> RegionTableStruct:
+        h, d, K, W, Q = self.host.ctypes.data, self.dev.data_ptr(), self.K, self.W, self.Q
+        o = [4 * x for x in (0, K, 2 * K, 3 * K, 4 * K, 4 * K + W, 4 * K + 2 * W, 4 * K + 3 * W, 4 * K + 3 * W + Q, 4 * K + 3 * W + 2 * Q,
+                             4 * K + 3 * W + 3 * Q)]
+        return RegionTableStruct(C.sizeof(RegionTableStruct), self.C, W, K, Q, self.fade, *[h + x for x in o[:10]], *[d + x for x in o[:10]], d + o[10])
 
 
 class ExtractDesc(C.Structure):
@@ -291,6 +322,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_wave_peak.argtypes = [vp, vp, C.POINTER(SpanTableStruct), vp, i32, i32, vp, vp]
     lib.si_gather_windows.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp]
     lib.si_patch_compose.argtypes = [vp, vp, C.POINTER(SpanTableStruct), vp, C.POINTER(PatchTableStruct), vp, i32, vp, i32, i32, vp, vp, vp]
+    lib.si_cut_clips.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
+    lib.si_patch_regions.argtypes = [vp, vp, i32, C.POINTER(RegionTableStruct), vp, i32, vp, vp, vp, vp]
     lib.si_num_frames.argtypes = [vp, i32]
     lib.si_vocoder_samples.argtypes = [vp, i32, i32]
     lib.si_debug_capture.argtypes = [vp, C.c_char_p, vp, C.c_long]
@@ -561,6 +594,35 @@ class NativeContext:
                                               _ptr(gen), 0 if gen is None else gen.shape[1], _ptr(gain), B, N, _ptr(out), _ptr(out_pcm), self._stream()),
                     "si_patch_compose")
         return out, out_pcm
+
+    # ---- long recordings
+    def cut_clips(self, src: torch.Tensor, starts, L: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """src (n,) fp32 + starts (host ints) -> (C, L): row c = src[starts[c] : starts[c] + L] (si_cut_clips).  A start table that
+        leaves the source is refused before the launch."""
+        assert src.is_cuda and src.dtype == torch.float32 and src.dim() == 1 and src.is_contiguous()
+        host = np.ascontiguousarray(np.asarray(list(starts), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        Cn, L = host.size, int(L)
+        dev = torch.from_numpy(host).to(self.device, non_blocking=True)
+        if out is None:
+            out = torch.empty(Cn, L, dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * L
+        self._check(self.lib.si_cut_clips(self._h, _ptr(src), min(src.numel(), 2 ** 31 - 1), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L, _ptr(out), self._stream()),
+                    "si_cut_clips")
+        return out
+
+    def patch_regions(self, orig: torch.Tensor, table: "RegionTable", gen: Optional[torch.Tensor], gain: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None, out_pcm: Optional[torch.Tensor] = None) -> None:
+        """The blended samples of `table`'s regions written IN PLACE into out (N22) fp32 and / or out_pcm (N22) int16, which hold the
+        caller's copy of the recording `orig` (N22) everywhere else (si_patch_regions).  gen (W, Lrow); gain (C,) fp32 or None."""
+        assert orig.is_cuda and orig.dtype == torch.float32 and orig.dim() == 1 and orig.is_contiguous()
+        N = orig.numel()
+        assert gen is None or (gen.is_cuda and gen.dtype == torch.float32 and gen.dim() == 2 and gen.is_contiguous() and gen.shape[0] == table.W)
+        assert gain is None or (gain.is_cuda and gain.dtype == torch.float32 and gain.numel() == table.C and gain.is_contiguous())
+        for o, dt in ((out, torch.float32), (out_pcm, torch.int16)):
+            assert o is None or (o.is_cuda and o.dtype == dt and o.is_contiguous() and o.numel() == N and o.data_ptr() != orig.data_ptr())
+        t = table.struct()
+        self._check(self.lib.si_patch_regions(self._h, _ptr(orig), min(N, 2 ** 31 - 1), C.byref(t), _ptr(gen), 0 if gen is None else gen.shape[1], _ptr(gain), _ptr(out),
+                                              _ptr(out_pcm), self._stream()), "si_patch_regions")
 
     @staticmethod
     def _feats_mel(feats: torch.Tensor, mel: torch.Tensor):

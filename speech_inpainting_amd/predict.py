@@ -9,6 +9,12 @@ It reads the reference's YAML schema, loads the same three artefacts (CustomMode
 `<save_pred>/<wave_name>/{orig,masked,hifi_masked,expected_inpaint,inpainted}.wav` (I_ea/predict.py:84,128,134,201,207;
 `expected_inpaint.wav` only when the ground-truth label file exists).  `predict_clips` is the importable batch form.
 
+With an optional `long:` mapping ({clip_s: 4.0, context_s: 1.0, batch: 32}) the file is a RECORDING of any length: the gaps of
+`mask:` / `masks:` are read on the file's own time axis, the recording is served as context clips (engine.patch_recording, DESIGN.md
+4.14; the cross-fade comes from `patch:`, 5 ms without it) and `orig.wav`, `masked.wav` and `patched.wav` are written at 22.05 kHz,
+all with the recording's own sample count.  The whole-clip diagnostics (`hifi_masked.wav`, `inpainted.wav`, `expected_inpaint.wav`)
+are NOT produced on this route: no generator pass over a whole recording exists there.
+
 Differences from the script, all outside the three replaced subsystems: no Whisper `Metrics` object is built (the
 script constructs it and never uses it, I_ea/predict.py:72-73), PNG plots are skipped, and the two `librosa.load` calls are one
 wav read plus the resampler librosa 0.9.1 itself uses (resampy `kaiser_best`) run on the GPU (si_resample_sinc; pinned against the
@@ -321,6 +327,27 @@ def predict_ragged(engine: InpaintingEngine, waves16: Sequence[np.ndarray], wave
     return results  # type: ignore[return-value]
 
 
+def _main_long(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> int:
+    """The `long:` route of `main`: the file as a recording of any length, its gaps on its own time axis."""
+    raw, sr_file = audio.read_wav(cfg.wave_path)
+    wave_22 = engine.resample(torch.from_numpy(raw)[None].to(engine.device), sr_file, 22050)[0].contiguous()
+    gap_list = sorted(cfg.gaps) if cfg.gaps is not None else [(cfg.mask_pos, cfg.mask_frames)]
+    audio.write_wav(os.path.join(save_dir, "orig.wav"), engine.to_int16(wave_22).cpu().numpy(), 22050)
+    masked = wave_22.clone()
+    for pos, lm in gap_list:
+        masked[pos * 441:(pos + lm) * 441] = 0                                     # gaps.spans22: frame p = samples [441 p, 441 (p + 1))
+    audio.write_wav(os.path.join(save_dir, "masked.wav"), engine.to_int16(masked).cpu().numpy(), 22050)
+    out = engine.patch_recording(wave_22, gap_list, fade=cfg.patch_fade if cfg.patch_fade is not None else 110,
+                                 clip_frames=int(round(cfg.long["clip_s"] * 50)), min_context=int(round(cfg.long["context_s"] * 50)),
+                                 batch=cfg.long["batch"], pcm=True)
+    labels, off = out["labels"].tolist(), out["label_off"]
+    for k, (pos, lm) in enumerate(gap_list):
+        print(f"Predicted codewords, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[k]:off[k + 1]])
+    audio.write_wav(os.path.join(save_dir, "patched.wav"), out["patched_pcm"].cpu().numpy(), 22050)
+    print("wrote", save_dir)
+    return 0
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     cfg = load_predict_config(argv[0] if argv else "predict.yaml")
@@ -330,6 +357,8 @@ def main(argv=None) -> int:
     wave_name = cfg.wave_path.split("/")[-1].split(".")[0]
     save_dir = os.path.join(cfg.save_pred, wave_name)
     os.makedirs(save_dir, exist_ok=True)
+    if cfg.long is not None:                                                       # optional `long:` mapping: a recording of any length
+        return _main_long(cfg, engine, save_dir)
     raw, sr_file = audio.read_wav(cfg.wave_path)                                   # predict.py:79-80 (librosa.load x 2): one read,
     raw_dev = torch.from_numpy(raw)[None].to(engine.device)                        # both rates on the GPU with librosa 0.9.1's own
     wave_22 = engine.resample(raw_dev, sr_file, 22050)                             # resampler (resampy kaiser_best); they STAY there
