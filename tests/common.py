@@ -41,6 +41,21 @@ def load_case(name):
     return case
 
 
+def case_engine(c, enc="fp32", voc="fp32", chunk=0):
+    """A fresh engine with a golden case's architectures and state."""
+    from tests.harness import build_engine
+    return build_engine(c["harch"], c["varch"], c["meta"]["K"], enc, voc, vocoder_chunk=chunk, state=(c["hsd"], c["gsd"], c["cb"]))
+
+
+def run_case(eng, c):
+    """predict_batch on a golden case's inputs -> its outputs on the CPU."""
+    m = c["meta"]
+    pos = torch.tensor(c["frame_pos"], dtype=torch.int32, device="cuda")
+    out = eng.predict_batch(c["wave"].cuda(), c["mel"].cuda(), pos, m["lm"], blind=m["blind"])
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in out.items()}
+
+
 def rms(a, b=None):
     a = torch.as_tensor(a).double()
     if b is not None:

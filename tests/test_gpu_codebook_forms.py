@@ -6,7 +6,7 @@ the library: the claim is that they are one body.  Correctness against the refer
 import pytest
 import torch
 
-from tests.common import load_case
+from tests.common import case_engine, load_case
 
 pytestmark = pytest.mark.gpu
 
@@ -16,10 +16,9 @@ FRAME_POS = [0, 4, -2]      # clip 1 crosses Tm at pos 6 (label, no column) and 
 
 @pytest.fixture(scope="module")
 def forms():
-    from speech_inpainting_amd.engine import InpaintingEngine
     c = load_case("tiny_group")
     K = c["meta"]["K"]
-    eng = InpaintingEngine(c["harch"], c["varch"], K, "cuda:0").load_state(c["hsd"], c["gsd"], c["cb"])
+    eng = case_engine(c)
     assert eng.harch.codebook_dim == D
     feats = torch.randn(B, T, D, generator=torch.Generator().manual_seed(5)).cuda()
     i32 = lambda v: torch.tensor(v, dtype=torch.int32, device="cuda")

@@ -5,15 +5,15 @@ import pytest
 import torch
 
 from tests.common import rms
+from tests.harness import build_engine, scoped_env
 
 pytestmark = pytest.mark.gpu
 
 
 def _mk(harch, varch, enc="fp32", voc="fp32", K=100):
     from speech_inpainting_amd import synth
-    from speech_inpainting_amd.engine import InpaintingEngine
-    hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(K)
-    return InpaintingEngine(harch, varch, K, "cuda:0", enc, voc).load_state(hsd, gsd, cb), (hsd, gsd, cb)
+    state = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(K)
+    return build_engine(harch, varch, K, enc, voc, state=state), state
 
 
 def test_config5_blind_10s_clip_matches_oracle():
@@ -306,7 +306,6 @@ def test_f0_vqvae_front_matches_oracle(B, T):
 def test_f0_encoder_single_launch_equals_the_layer_by_layer_form():
     """si_f0_encoder_forward as ONE persistent launch (activations in LDS) against its 37-launch form (SI_F0_FUSED=0, also the route
     of tracks too long for LDS): bit-identical, for the hubert_lut.json shape at 4 s / 10 s tracks and a 30 s track that does not fit."""
-    import os
     from speech_inpainting_amd import native, synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
     ctx = native.NativeContext(native.make_desc(HubertArch.tiny(), VocoderArch.tiny(), 10), torch.device("cuda:0"))
@@ -317,11 +316,8 @@ def test_f0_encoder_single_launch_equals_the_layer_by_layer_form():
     for B, T in ((16, 797), (3, 2000), (2, 6000)):
         f0 = torch.randn(B, 1, T, generator=g).cuda()
         a = ctx.f0_encoder(desc, w, f0)
-        os.environ["SI_F0_FUSED"] = "0"
-        try:
+        with scoped_env({"SI_F0_FUSED": "0"}):
             b = ctx.f0_encoder(desc, w, f0)
-        finally:
-            os.environ.pop("SI_F0_FUSED", None)
         torch.cuda.synchronize()
         assert torch.equal(a, b), (B, T, float((a - b).abs().max()))
     ctx.close()

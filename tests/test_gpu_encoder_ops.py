@@ -28,17 +28,18 @@ the projection GEMM, max err / E over the rows of the last (partial) row tile | 
     tapgemm_bf16_128x128w8 (SI_ENC_LINGEMM=0, M = 300) 0.002;  tapgemm_bf16_128x128 (fp32 features, no LayerNorm, M = 257) 0.002
 and the share of "features.ln.bf16" outputs != rne(float64 LayerNorm): at most 0.0059 % over 24 runs (the "ln" guard: 0.064 %)."""
 import dataclasses
-import os
 
 import pytest
 import torch
 
 from tests import encoder_ref as E
 from tests import vocoder_ref as V
+from tests.cases import _config, _pick_wave, _sel_rows
+from tests.cases import _enc_state as _state
+from tests.harness import build_engine, tapped_run
 
 pytestmark = pytest.mark.gpu
 
-torch.set_num_threads(16)
 GEMMCU_BM = {10: 320, 11: 256, 12: 160, 13: 224, 14: 128, 15: 208}
 GEMMCU_BN = {10: 256, 11: 256, 12: 128, 13: 128, 14: 128, 15: 256}
 # Fraction of a launch's bf16 outputs that differ from rne(float64 result), the bf16 value nearest to the exact one: twice the
@@ -61,34 +62,10 @@ def _large():
     return dataclasses.replace(HubertArch.large(), num_hidden_layers=1)
 
 
-_STATES = {}
-
-
-def _state(harch):
-    from speech_inpainting_amd import synth
-    key = (harch.hidden_size, harch.feat_extract_norm, harch.do_stable_layer_norm, harch.feat_proj_layer_norm)
-    if key not in _STATES:
-        _STATES[key] = synth.synth_hubert_state(harch, 31)
-    return _STATES[key]
-
-
-def _engine(harch, env=None):
+def _engine(harch, env=None, key=None):
     """bf16 encoder; `env` knobs are read when the context is created."""
-    from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
-    env = env or {}
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        eng = InpaintingEngine(harch, VocoderArch.tiny(), 50, "cuda:0", "bf16", "fp32")
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return eng.load_state(_state(harch), synth.synth_generator_state(VocoderArch.tiny()), synth.synth_codebook(50))
+    return build_engine(harch, VocoderArch.tiny(), 50, "bf16", "fp32", env=env, state=(_state(harch), None, None), key=key)
 
 
 def _run(eng, harch, wave, lens=None, valid_len=None, profile=False):
@@ -98,21 +75,10 @@ def _run(eng, harch, wave, lens=None, valid_len=None, profile=False):
     R = sum(harch.num_frames(n) for n in lens) if lens is not None else B * harch.num_frames(N)
     cap = E.tap_capacities(harch, B, N, R)
     cap["features"], cap["projected"] = R * harch.conv_dim[-1], R * harch.hidden_size
-    eng.ctx.clear_captures()
-    caps = eng.ctx.capture(list(cap), capacity=cap)
-    if profile:
-        eng.ctx.profile_start(4000)
-    if lens is not None:
-        out = eng.encode_ragged(wave, lens)
-    else:
-        out = eng.encode(wave, valid_len=valid_len, normalize=False)
-    names = {e["name"] for e in eng.ctx.profile_stop()} if profile else set()
-    torch.cuda.synchronize()
-    produced = {k: eng.ctx.lib.si_debug_size(eng.ctx._h, k.encode()) for k in cap}
-    got = {k: v.cpu() for k, v in caps.items() if produced[k] > 0 and produced[k] == cap[k]}
-    eng.ctx.clear_captures()
+    got, out, prof = tapped_run(eng.ctx, cap, lambda: eng.encode_ragged(wave, lens) if lens is not None
+                                else eng.encode(wave, valid_len=valid_len, normalize=False), profile=profile)
     assert bool(torch.isfinite(out).all())
-    return got, R, names
+    return got, R, set(prof)
 
 
 def _f64(t):
@@ -133,14 +99,6 @@ def _tap(got, name):
     if name + ".bf16" in got:
         return got[name + ".bf16"], "bf16"
     return got[name], "f32"
-
-
-def _sel_rows(M, k=96, seed=0):
-    """Rows to check of a long GEMM: the first 8, the last 336 (every last tile of every height, whole), k random ones."""
-    if M <= 512:
-        return torch.arange(M)
-    g = torch.Generator().manual_seed(seed)
-    return torch.unique(torch.cat([torch.arange(8), torch.arange(M - 336, M), torch.randint(0, M, (k,), generator=g)]))
 
 
 def _check_layers(got, harch, R, tag, rows=None):
@@ -276,21 +234,6 @@ def _check_convs(got, harch, B, N, tag, clip_lens=None):
             xb = _f64(xin[b]) if kin == "bf16" else E.bf16(xin[b])
             ref, bound = E.linear_ref(E.conv_rows(xb, k, s, rows), w, bias, act=None if layer else "gelu")
             _check(f"{tag} conv{i} clip {b} (L = {Lb})", ky, y[b][rows], ref, bound)
-
-
-def _pick_wave(harch, B, T, bm):
-    """A batch of B clips of exactly T frames whose sample count puts as many strided convs as possible at a last tile of 1 or
-    bm - 1 rows (every count 320 (T - 1) + 400 + d, d < 320, has T frames)."""
-    from speech_inpainting_amd import synth
-    best, bestd = -1, 0
-    for d in range(320):
-        Ls = harch.feat_lengths(320 * (T - 1) + 400 + d)
-        score = sum(L % bm in (1, bm - 1) for L in Ls[2:-1])
-        if score > best:
-            best, bestd = score, d
-    N = 320 * (T - 1) + 400 + bestd
-    assert harch.num_frames(N) == T
-    return synth.synth_wave(B, N, 7 + T).cuda()
 
 
 GEMM_CASES = [(c, d) for c in range(10, 16) for d in (-1, 0, 1)]
@@ -483,7 +426,6 @@ PC_UNIFORM = [(3, 256), (2, 257), (1, 513)]
 PC_RAGGED = [[256, 1, 255, 16, 17, 64, 65], [513, 1, 257, 512, 256, 511]]
 PC_PADDED = (300, [1, 32, 33, 299])
 PC_KERNELS = {"posconv": {}, "tapgemm": {"SI_ENC_POSCONV": "0"}}
-_PC_ENGINES = {}
 
 
 def _pc_arch(cg):
@@ -491,16 +433,13 @@ def _pc_arch(cg):
 
 
 def _pc_engine(cg, kernel):
-    """One engine per (width, kernel), kept for the file: SI_ENC_POSCONV is read when the context is created."""
-    if (cg, kernel) not in _PC_ENGINES:
-        _PC_ENGINES[(cg, kernel)] = _engine(_pc_arch(cg), PC_KERNELS[kernel])
-    return _PC_ENGINES[(cg, kernel)]
+    """One engine per (width, kernel), kept for the session: SI_ENC_POSCONV is read when the context is created."""
+    return _engine(_pc_arch(cg), PC_KERNELS[kernel], key=("posconv", cg, kernel))
 
 
 def _pc_both(cg, wave, lens=None, valid_len=None):
     """The same batch through posconv.hip and through the SI_ENC_POSCONV=0 fallback -> {kernel: (taps, profile name of the conv's
     kernel)}.  The profile must name the one and none of the other; "projected", the conv's input, must be equal in both runs."""
-    from tests.test_gpu_tapgemm_ops import _config
     harch = _pc_arch(cg)
     runs = {}
     for kernel in PC_KERNELS:

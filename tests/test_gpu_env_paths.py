@@ -18,8 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SNIPPET = r"""
 import json, sys, numpy as np, torch
 sys.path.insert(0, %r)
-from tests.common import load_case, rms
-from tests.test_gpu_parity import _engine, _run
+from tests.common import case_engine as _engine, load_case, rms, run_case as _run
 out = {}
 c = load_case("tiny_group")
 z = c["z"]

@@ -12,6 +12,7 @@ import torch
 from oracle import ref_cpu as R
 from speech_inpainting_amd import synth
 from speech_inpainting_amd.arch import HubertArch, VocoderArch, mel_frames
+from tests.harness import scoped_env
 
 pytestmark = pytest.mark.gpu
 
@@ -184,17 +185,13 @@ def test_kmeans_mfma_kernel_agrees_with_the_scalar_kernel_up_to_near_ties(ctx):
     workgroup scalar kernel (SI_KMEANS_MFMA=0) and the float64 distances: identical labels wherever the two best distances differ by
     more than 1e-4 relative, squared distances within 1e-4; shapes of the I_da call (6368 x 1024, K = 100), the F0 bottleneck
     (800 x 128, K = 20), K > 128 (two centroid blocks), and a ragged last row tile."""
-    import os
     g = torch.Generator().manual_seed(41)
     for rows, D, K in ((6368, 1024, 100), (800, 128, 20), (1001, 256, 300), (33, 64, 7)):
         cent = torch.randn(K, D, generator=g)
         x = cent[torch.randint(0, K, (rows,), generator=g)] + 0.7 * torch.randn(rows, D, generator=g)
         got, dist = ctx.kmeans_assign(x.cuda(), cent.cuda(), with_distance=True)
-        os.environ["SI_KMEANS_MFMA"] = "0"
-        try:
+        with scoped_env({"SI_KMEANS_MFMA": "0"}):
             old, dist_old = ctx.kmeans_assign(x.cuda(), cent.cuda(), with_distance=True)
-        finally:
-            os.environ.pop("SI_KMEANS_MFMA", None)
         d_all = torch.cdist(x.double(), cent.double()).pow(2)
         top2 = d_all.topk(2, dim=1, largest=False).values
         clear = (top2[:, 1] - top2[:, 0]) > 1e-4 * top2[:, 1]

@@ -11,10 +11,11 @@ import torch
 
 from speech_inpainting_amd.arch import HubertArch, VocoderArch
 from tests import frontend_ref as FR
+from tests.harness import RatioSummary, tapped_run
 
 pytestmark = pytest.mark.gpu
 
-SUMMARY = {}
+SUMMARY = RatioSummary()
 CASES = {c.name: c for c in FR.cases()}
 
 
@@ -44,29 +45,23 @@ def run(ctx, case, tapped=True, offset=0, entry=None):
     cap = {"mel_frames": B * Tm * FR.FRAME, "mel_spec": B * Tm * FR.LDSPEC}
     if case.normalize:
         cap["mel_peak"] = B
-    ctx.clear_captures()
-    caps = ctx.capture(list(cap), capacity=cap) if tapped else {}
     spans = case.spans if case.spans is not None else [[] for _ in range(B)]
     ms = me = None
     if case.spans is not None and entry != "spans":
         assert all(len(s) <= 1 for s in spans)
         ms = _i32(s[0][0] if s else 0 for s in spans)
         me = _i32(s[0][0] + s[0][1] if s else 0 for s in spans)
-    ctx.profile_start(64)
-    if entry == "spans":
-        mel = ctx.mel_frontend_spans(w, SpanTable(spans, torch.device("cuda:0")), normalize=case.normalize, sample_len=case.lens)
-    elif entry == "varlen":
-        mel = ctx.mel_frontend_varlen(w, case.lens, ms, me, normalize=case.normalize)
-    else:
+
+    def forward():
+        if entry == "spans":
+            return ctx.mel_frontend_spans(w, SpanTable(spans, torch.device("cuda:0")), normalize=case.normalize, sample_len=case.lens)
+        if entry == "varlen":
+            return ctx.mel_frontend_varlen(w, case.lens, ms, me, normalize=case.normalize)
         assert case.lens is None
-        mel = ctx.mel_frontend(w, ms, me, normalize=case.normalize)
-    prof = {e["name"]: e["launches"] for e in ctx.profile_stop()}
-    torch.cuda.synchronize()
-    taps = {}
-    for k, t in caps.items():
-        assert ctx.lib.si_debug_size(ctx._h, k.encode()) == t.numel(), (k, "was not produced")
-        taps[k] = t.cpu().numpy()
-    ctx.clear_captures()
+        return ctx.mel_frontend(w, ms, me, normalize=case.normalize)
+
+    taps, mel, prof = tapped_run(ctx, cap if tapped else {}, forward, require_all=True, max_launches=64)
+    taps = {k: t.numpy() for k, t in taps.items()}
     peak = taps.get("mel_peak")
     frames = taps["mel_frames"].reshape(B, Tm, FR.FRAME) if tapped else None
     spec = taps["mel_spec"].reshape(B, Tm, FR.LDSPEC) if tapped else None
@@ -109,8 +104,7 @@ def check(case, peak, frames, spec, mel, tag=None):
     res = FR.check_batch(case, peak, frames, spec, mel)
     for stage, r in res.items():
         print(f"{tag or case.name} {stage}: {r['bad']} over, max err/E edge frames {r['edge']:.6f}, interior {r['interior']:.6f}")
-        s = SUMMARY.setdefault(stage, [0.0, 0.0])
-        s[0], s[1] = max(s[0], r["edge"]), max(s[1], r["interior"])
+        SUMMARY.note(stage, r["edge"], r["interior"])
     assert np.isfinite(mel).all()
     assert all(r["bad"] == 0 for r in res.values()), {k: r["bad"] for k, r in res.items()}
 
@@ -211,6 +205,4 @@ def test_coverage_of_frame_and_span_situations():
 def test_zz_summary_of_ratios():
     """(last in the file) the largest err / E per stage over every check above: edge frames (reflecting, or with a span in reach) |
     interior frames.  The log-mel's figure is the distance from the middle of its interval in half-widths."""
-    for stage in ("frames", "spec", "logmel"):
-        if stage in SUMMARY:
-            print(f"front-end {stage}: max err/E edge frames {SUMMARY[stage][0]:.6f} | interior frames {SUMMARY[stage][1]:.6f}")
+    SUMMARY.report("front-end {key}: max err/E edge frames {near:.6f} | interior frames {rest:.6f}", keys=("frames", "spec", "logmel"))

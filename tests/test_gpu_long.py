@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_patch import CHUNK, FADES, HOP, N_OUT, _engine, _weights64
+from tests.cases import CHUNK, FADES, HOP, N_OUT, _weights64
+from tests.cases import _patch_engine as _engine
 
 pytestmark = pytest.mark.gpu
 

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 from oracle import ref_cpu as R
 from tests import encoder_ref as E
+from tests.common import case_engine as _engine
 from tests.common import load_case, rms
 
 pytestmark = pytest.mark.gpu
@@ -25,12 +26,6 @@ GAPS_B4 = [[(20, 5), (90, 10), (150, 20)], [(60, 10)], [], [(5, 3), (40, 8), (10
 GAPS_TINY = {"tiny_group": [[(1, 4), (12, 6)], [(3, 3), (15, 8)], [(0, 5), (18, 7)]],
              "tiny_layer": [[(2, 3), (10, 5)], [(0, 4), (12, 6)]]}
 MEL_ATOL = 2e-4          # tests/test_gpu_frontend.py: the HIP mel front-end against torch's FFT-based one
-
-
-def _engine(c, enc="fp32", voc="fp32"):
-    from speech_inpainting_amd.engine import InpaintingEngine
-    eng = InpaintingEngine(c["harch"], c["varch"], c["meta"]["K"], "cuda:0", enc, voc)
-    return eng.load_state(c["hsd"], c["gsd"], c["cb"])
 
 
 def zero_spans16(wave, gaps):

@@ -3,23 +3,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests.common import case_engine as _engine
 from tests.common import load_case, rms
+from tests.common import run_case as _run
 
 pytestmark = pytest.mark.gpu
-
-
-def _engine(c, enc="fp32", voc="fp32", chunk=0):
-    from speech_inpainting_amd.engine import InpaintingEngine
-    eng = InpaintingEngine(c["harch"], c["varch"], c["meta"]["K"], "cuda:0", enc, voc, chunk)
-    return eng.load_state(c["hsd"], c["gsd"], c["cb"])
-
-
-def _run(eng, c):
-    m = c["meta"]
-    pos = torch.tensor(c["frame_pos"], dtype=torch.int32, device="cuda")
-    out = eng.predict_batch(c["wave"].cuda(), c["mel"].cuda(), pos, m["lm"], blind=m["blind"])
-    torch.cuda.synchronize()
-    return {k: v.cpu() for k, v in out.items()}
 
 
 @pytest.mark.parametrize("name", ["tiny_group", "tiny_layer", "tiny_blind", "base_4s", "large_4s", "base_b4"])

@@ -11,52 +11,21 @@ import numpy as np
 import pytest
 import torch
 
-from tests.common import load_case
+from tests.cases import CHUNK, FADES, HOP, N_OUT, _weights64
+from tests.cases import _patch_engine as _engine
+from tests.common import case_engine, load_case
 
 pytestmark = pytest.mark.gpu
 
 GAPS = [[(20, 5)], [(0, 3), (60, 10)], [], [(30, 4), (35, 4)]]
 GAPS_B4 = [[(20, 5), (90, 10), (150, 20)], [(60, 10)], [], [(5, 3), (40, 8), (100, 12), (170, 15)]]      # tests/test_gpu_multigap.py
-N16, N22, N_OUT, T_OUT, HOP = 24000, 33075, 33024, 129, 256
-FADES = [0, 110, 300]
-CHUNK = 2048                                     # PC_CHUNK of patch_kernels.hip: samples per workgroup of the compose kernel
+N16, N22, T_OUT = 24000, 33075, 129              # (N_OUT, HOP, FADES and CHUNK: tests/cases.py, shared with test_gpu_long.py)
 U = 2.0 ** -24                                   # fp32 unit roundoff
-
-_ENG = {}
-
-
-def _engine(voc="fp32"):
-    """Tiny HuBERT + V1 generator, as test_windowed_passes_over_merged_windows_equal_full_passes builds them; one per vocoder mode."""
-    if voc not in _ENG:
-        from speech_inpainting_amd import synth
-        from speech_inpainting_amd.arch import HubertArch, VocoderArch
-        from speech_inpainting_amd.engine import InpaintingEngine
-        harch, varch = HubertArch.tiny(), VocoderArch.v1()
-        _ENG[voc] = InpaintingEngine(harch, varch, 100, "cuda:0", "fp32", voc).load_state(
-            synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(100))
-    return _ENG[voc]
 
 
 def _clips(B=4, seed=31):
     from speech_inpainting_amd import synth
     return synth.synth_wave(B, N16, seed).cuda(), synth.synth_wave(B, N22, seed + 1, sr=22050).cuda()
-
-
-def _weights64(spans, lim, fade, n):
-    """The weight of the generated audio per sample of one clip, float64, written out from the definition (not through gaps.blend_weights):
-    the maximum over the spans of {ramp on the rise, 1 inside, mirrored ramp on the fall}, 0 at and past lim; and the index of the span
-    that gives it (the first on ties)."""
-    from speech_inpainting_amd import gaps as G
-    ramp = G.fade_ramp(fade).astype(np.float64)
-    w, who = np.zeros(n), np.full(n, -1)
-    for k, (s, l) in enumerate(spans):
-        if l <= 0 or s >= lim:
-            continue
-        for m in range(max(s - fade, 0), min(s + l + fade, lim)):
-            wk = ramp[m - (s - fade)] if m < s else 1.0 if m < s + l else ramp[s + l + fade - 1 - m]
-            if wk > w[m]:
-                w[m], who[m] = wk, k
-    return w, who
 
 
 def _seam_spans(fade):
@@ -248,9 +217,8 @@ def test_headline_arithmetic_end_to_end():
     outside every blend region the output is wave22 bit for bit, inside the gaps it is gain x the full pass's wave."""
     from speech_inpainting_amd import gaps as G
     from speech_inpainting_amd import native, synth
-    from speech_inpainting_amd.engine import InpaintingEngine
     c = load_case("base_b4")
-    eng = InpaintingEngine(c["harch"], c["varch"], c["meta"]["K"], "cuda:0", "bf16", "fp16").load_state(c["hsd"], c["gsd"], c["cb"])
+    eng = case_engine(c, "bf16", "fp16")
     wave = c["wave"].cuda()
     B, n16 = wave.shape
     n22 = n16 * 441 // 320

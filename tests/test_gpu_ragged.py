@@ -9,15 +9,15 @@ import pytest
 import torch
 
 from tests.common import rms
+from tests.harness import build_engine
 
 pytestmark = pytest.mark.gpu
 
 
 def _mk(harch, varch, enc="fp32", voc="fp32", K=100):
     from speech_inpainting_amd import synth
-    from speech_inpainting_amd.engine import InpaintingEngine
-    hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(K)
-    return InpaintingEngine(harch, varch, K, "cuda:0", enc, voc).load_state(hsd, gsd, cb), (hsd, gsd, cb)
+    state = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(K)
+    return build_engine(harch, varch, K, enc, voc, state=state), state
 
 
 def _clips(secs, seed0=100):
@@ -164,26 +164,18 @@ def test_posconv_kernel_against_a_float64_convolution_of_the_same_bf16_operands(
     (the captured projection output, the folded weights): h + GELU(conv(h) + b) within fp32 accumulation error for both -- on 4 s
     clips (two clips per workgroup), 10 s clips (512-row blocks), 10.6 s clips (two blocks per clip); then a ragged batch (packed
     rows), where every clip must still be bit-identical to that clip alone."""
-    import os
     import torch.nn.functional as F
     from oracle import ref_cpu as R
     from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
     # pre-LN ("stable") flavour: the tap `encoder_in` is then the positional conv's output itself, h + gelu(conv(h) + b)
     harch = HubertArch.tiny(hidden_size=H, num_attention_heads=heads, num_hidden_layers=1, intermediate_size=512,
                             num_conv_pos_embeddings=128, num_conv_pos_embedding_groups=16, do_stable_layer_norm=True)
     varch = VocoderArch.tiny()
     hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(50)
 
-    def make():
-        return InpaintingEngine(harch, varch, 50, "cuda:0", "bf16", "fp16").load_state(hsd, gsd, cb)
-    new = make()
-    os.environ["SI_ENC_POSCONV"] = "0"
-    try:
-        old = make()
-    finally:
-        os.environ.pop("SI_ENC_POSCONV", None)
+    new = build_engine(harch, varch, 50, "bf16", "fp16", state=(hsd, gsd, cb))
+    old = build_engine(harch, varch, 50, "bf16", "fp16", state=(hsd, gsd, cb), env={"SI_ENC_POSCONV": "0"})
     w = R._conv_weight(hsd, "base_model.encoder.pos_conv_embed.conv", dim=2).to(torch.bfloat16).double()
     bias = hsd["base_model.encoder.pos_conv_embed.conv.bias"].double()
     torch.set_num_threads(16)

@@ -1,34 +1,25 @@
 """The fused ResBlock-pair kernels (respair.hip: C = 32 / 64; respair_wide.hip: C = 128 / 256) against the two-launch
 tap-GEMM form of the same arithmetic (SI_VOC_FUSE=0) and against the fp32 oracle, on the V1 generator (all four widths)
 at clip lengths that exercise interior tiles, ragged last tiles and clips shorter than one tile."""
-import os
-
 import pytest
 import torch
 
 from tests.common import rms
+from tests.harness import build_engine
 
 pytestmark = pytest.mark.gpu
 
 
-def _engine(varch, gsd, fuse, voc="fp16", chain=True):
-    from speech_inpainting_amd import synth
+def _engine(varch, gsd, fuse, voc="fp16", chain=True, **env):
     from speech_inpainting_amd.arch import HubertArch
-    from speech_inpainting_amd.engine import InpaintingEngine
-    harch = HubertArch.tiny()
     fuse = fuse if isinstance(fuse, str) else ("1" if fuse else "0")   # a string: SI_VOC_FUSE as a mask
-    want = {"SI_VOC_FUSE": fuse, "SI_VOC_CHAIN": "1" if chain else "0"}   # read when the context is created
-    old = {k: os.environ.get(k) for k in want}
-    os.environ.update(want)
-    try:
-        eng = InpaintingEngine(harch, varch, 20, "cuda:0", "fp32", voc)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return eng.load_state(synth.synth_hubert_state(harch), gsd, synth.synth_codebook(20))
+    env.update(SI_VOC_FUSE=fuse, SI_VOC_CHAIN="1" if chain else "0")   # read when the context is created
+    return build_engine(HubertArch.tiny(), varch, 20, "fp32", voc, env=env, state=(None, gsd, None))
+
+
+def _enc_engine(harch, varch, state, env=None):
+    """bf16 encoder, fp32 vocoder, K = 50, with `env` set while the context is created."""
+    return build_engine(harch, varch, 50, "bf16", "fp32", env=env, state=state)
 
 
 @pytest.mark.parametrize("B,Tm", [(3, 57), (2, 1), (1, 130), (5, 9)])
@@ -97,11 +88,7 @@ def test_early_upsamplers_on_gemmcu_match_the_tap_gemm_form_and_oracle(B, Tm):
     ref = R.generator_forward(gsd, varch, mel[:4])[:, 0, :]
 
     def run(flag, m):
-        os.environ["SI_VOC_UPSGEMM"] = flag
-        try:
-            eng = _engine(varch, gsd, True)
-        finally:
-            os.environ.pop("SI_VOC_UPSGEMM", None)
+        eng = _engine(varch, gsd, True, SI_VOC_UPSGEMM=flag)
         eng.ctx.profile_start(4000)
         w = eng.vocode(m.cuda(), stretch=False).cpu()
         names = {e["name"] for e in eng.ctx.profile_stop()}
@@ -121,11 +108,7 @@ def test_early_upsamplers_on_gemmcu_match_the_tap_gemm_form_and_oracle(B, Tm):
     a, c = run("1", hot), run("0", hot)
     assert bool(torch.isfinite(a).all()) and ((a > 0) == (c > 0)).float().mean().item() > 0.9
     if B > 1:                                                                         # a clip does not depend on its batch neighbours
-        os.environ["SI_VOC_UPSGEMM"] = "1"
-        try:
-            eng = _engine(varch, gsd, True)
-        finally:
-            os.environ.pop("SI_VOC_UPSGEMM", None)
+        eng = _engine(varch, gsd, True, SI_VOC_UPSGEMM="1")
         assert torch.equal(eng.vocode(mel[1:2].cuda(), stretch=False).cpu(), new[1:2])
 
 
@@ -186,23 +169,18 @@ def test_lingemm_matches_tapgemm_in_the_bf16_encoder(arch):
     (a bf16 activation copy that rounds the other way is a 2^-9 relative step), far inside the bf16 mode's own error."""
     from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
     harch = HubertArch.base() if arch == "base" else HubertArch.large()
     varch = VocoderArch.tiny()
     hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(50)
     wave = synth.synth_wave(3, 24000, 91).cuda()
     outs = {}
     for flag in ("1", "0"):
-        os.environ["SI_ENC_LINGEMM"] = flag
-        try:
-            eng = InpaintingEngine(harch, varch, 50, "cuda:0", "bf16", "fp32").load_state(hsd, gsd, cb)
-        finally:
-            os.environ.pop("SI_ENC_LINGEMM", None)
+        eng = _enc_engine(harch, varch, (hsd, gsd, cb), {"SI_ENC_LINGEMM": flag})
         eng.ctx.profile_start(4000)
         outs[flag] = eng.encode(wave).cpu()
         names = {e["name"] for e in eng.ctx.profile_stop()}
         assert any(n.startswith("lingemm_bf16_") for n in names) == (flag == "1"), names     # the kernel under test actually ran
-    ref = InpaintingEngine(harch, varch, 50, "cuda:0", "fp32", "fp32").load_state(hsd, gsd, cb).encode(wave).cpu()
+    ref = build_engine(harch, varch, 50, state=(hsd, gsd, cb)).encode(wave).cpu()
     d = rms(outs["1"], outs["0"]) / rms(outs["0"])
     e1, e0 = rms(outs["1"], ref) / rms(ref), rms(outs["0"], ref) / rms(ref)
     print(f"{arch}: lingemm vs tapgemm {d:.3e} relative; vs the fp32 encoder: lingemm {e1:.3e}, tapgemm {e0:.3e}")
@@ -220,18 +198,13 @@ def test_gemmcu_matches_lingemm_in_the_bf16_encoder(arch, B, N, flag):
     run as well (a race in the DMA ring would show as noise), and a clip must not depend on its batch neighbours."""
     from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
     harch = HubertArch.base() if arch == "base" else HubertArch.large()
     varch = VocoderArch.tiny()
     hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(50)
     wave = synth.synth_wave(B, N, 97).cuda()
     outs, engs = {}, {}
     for f in (flag, "0"):
-        os.environ["SI_ENC_GEMMCU"] = f
-        try:
-            eng = InpaintingEngine(harch, varch, 50, "cuda:0", "bf16", "fp32").load_state(hsd, gsd, cb)
-        finally:
-            os.environ.pop("SI_ENC_GEMMCU", None)
+        eng = _enc_engine(harch, varch, (hsd, gsd, cb), {"SI_ENC_GEMMCU": f})
         eng.ctx.profile_start(4000)
         outs[f] = eng.encode(wave).cpu()
         names = {e["name"] for e in eng.ctx.profile_stop()}
@@ -256,19 +229,12 @@ def test_layernorm_residual_fusion_changes_no_value(env):
     wherever they cover the shape; =2: gemmcu wherever an instantiation does), and with the launcher's own choice at B = 32."""
     from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
     harch, varch = HubertArch.base(), VocoderArch.tiny()
     hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(50)
     wave = synth.synth_wave(3 if env else 32, 30000 if env else 64000, 99).cuda()
     outs = {}
     for fuse in ("1", "0"):
-        os.environ.update(env)
-        os.environ["SI_ENC_LNFUSE"] = fuse
-        try:
-            eng = InpaintingEngine(harch, varch, 50, "cuda:0", "bf16", "fp32").load_state(hsd, gsd, cb)
-        finally:
-            for k in list(env) + ["SI_ENC_LNFUSE"]:
-                os.environ.pop(k, None)
+        eng = _enc_engine(harch, varch, (hsd, gsd, cb), dict(env, SI_ENC_LNFUSE=fuse))
         outs[fuse] = eng.encode(wave).cpu()
         if fuse == "1":
             assert torch.equal(eng.encode(wave).cpu(), outs["1"])                      # (the in-place update: run to run)
@@ -290,17 +256,12 @@ def test_ffn_row_padding_changes_no_value():
     6272 instead of 6144 bytes apart); a layout choice only -- the encoder output equals the dense layout's bit for bit."""
     from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
     harch, varch = HubertArch.base(), VocoderArch.tiny()
     hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(50)
     wave = synth.synth_wave(5, 40000, 98).cuda()
     outs = {}
     for pad in ("0", "64", "128"):
-        os.environ["SI_ENC_FFNPAD"] = pad
-        try:
-            eng = InpaintingEngine(harch, varch, 50, "cuda:0", "bf16", "fp32").load_state(hsd, gsd, cb)
-        finally:
-            os.environ.pop("SI_ENC_FFNPAD", None)
+        eng = _enc_engine(harch, varch, (hsd, gsd, cb), {"SI_ENC_FFNPAD": pad})
         outs[pad] = eng.encode(wave).cpu()
     assert torch.equal(outs["0"], outs["64"]) and torch.equal(outs["0"], outs["128"])
 
@@ -312,17 +273,12 @@ def test_gemmcu_rule_at_the_bench_shape():
     on 160 x 128) -- and none on the 128-row kernel; the features equal the run without the kernel bit for bit, twice."""
     from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
     harch, varch = HubertArch.base(), VocoderArch.tiny()
     hsd, gsd, cb = synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(50)
     wave = synth.synth_wave(32, 64000, 96).cuda()
     outs = {}
     for flag in ("1", "0"):
-        os.environ["SI_ENC_GEMMCU"] = flag
-        try:
-            eng = InpaintingEngine(harch, varch, 50, "cuda:0", "bf16", "fp32").load_state(hsd, gsd, cb)
-        finally:
-            os.environ.pop("SI_ENC_GEMMCU", None)
+        eng = _enc_engine(harch, varch, (hsd, gsd, cb), {"SI_ENC_GEMMCU": flag})
         eng.ctx.profile_start(4000)
         outs[flag] = eng.encode(wave).cpu()
         prof = {e["name"]: e["launches"] for e in eng.ctx.profile_stop()}

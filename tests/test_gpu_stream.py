@@ -4,16 +4,14 @@ import numpy as np
 import pytest
 import torch
 
+from tests.harness import build_engine
+
 pytestmark = pytest.mark.gpu
 
 
 def _engine(enc="fp32", voc="fp32"):
-    from speech_inpainting_amd import synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
-    harch, varch = HubertArch.tiny(), VocoderArch.tiny()
-    return InpaintingEngine(harch, varch, 50, "cuda:0", enc, voc).load_state(synth.synth_hubert_state(harch), synth.synth_generator_state(varch),
-                                                                             synth.synth_codebook(50))
+    return build_engine(HubertArch.tiny(), VocoderArch.tiny(), 50, enc, voc)
 
 
 @pytest.mark.parametrize("enc,voc", [("fp32", "fp32"), ("bf16", "fp16")])

@@ -28,22 +28,22 @@ row, tap, dilation, slope order, alpha, a dropped bf16x3 cross term or a masked 
 tests/test_encoder_ref.py emulate each on the CPU, the positional conv's dropped halo row at the real widths); a mistake of a few ulp does not.
 """
 import dataclasses
-import os
 
 import pytest
 import torch
 
 from tests import encoder_ref as E
+from tests import tapgemm_checks as TG
 from tests import vocoder_ref as V
-from tests.test_gpu_vocoder_ops import _arch, _mel, _state
+from tests.cases import _arch, _config, _enc_state, _mel, _pick_wave, _sel_rows
+from tests.harness import RatioSummary, build_engine, tapped_run
+from tests.tapgemm_checks import MODES, _engine, _reached, _run
 
 pytestmark = pytest.mark.gpu
 
-torch.set_num_threads(16)
-MODES = {"fp32": ("fp32", "f32", {}), "bf16x3": ("bf16x3", "bf16x3", {}), "bf16": ("bf16", "bf16", {"SI_VOC_OPREADY": "0"})}
+SUMMARY = RatioSummary()                              # this file's max err / E per kernel configuration
 TILES = ("128x32", "256x32", "128x64", "256x64", "128x128", "256x128w8")
 ROWS = (127, 128, 129, 255, 256, 257, 513)
-SUMMARY = {}                                          # kernel configuration -> [max err / E near seams and edges, elsewhere, checks]
 # max err / E per configuration as measured on MI355X by test_zz_summary_of_ratios (records, not limits): (seam + edge rows, the rest).
 # The encoder's Linear layers and strided convs are in the 128x128 / 128x64 fp32 lines (last tile | the rest); "groups": the positional conv.
 RECORD = {
@@ -58,192 +58,12 @@ RECORD = {
 }
 
 
-def _config(math, N, M, ntaps, dil, Cin, stride=1):
-    """launch_math (tapgemm.hip) for fp32 inputs (x16 == nullptr) -> (profile name, BM).  MaxA<256, 512> = 6 and MaxA<256> = 12 float4 per
-    thread: both caps are 3072 float4, i.e. 384 rows of 32 channels.  N = 16 (a 32-column tile, Npad = 32) and Cin = 16 (BK = 16: a quarter of
-    the float4 per row, so the 256-row tile's halo always fits) need no case of their own: tests/test_gpu_unitvoc_ops.py asserts these names there."""
-    bk = 32 if Cin % 32 == 0 else 16
-    bn = 128 if N >= 128 else 64 if N > 32 else 32
-    rows256 = 255 * stride + (ntaps - 1) * abs(dil) + 1
-    cap = (3 if ntaps == 1 else 6) * 512
-    if bn == 128:
-        tall = bk == 32 and M > 256 and rows256 * (bk // 4) <= cap
-        return (f"tapgemm_{math}_256x128w8", 256) if tall else (f"tapgemm_{math}_128x128", 128)
-    tall = rows256 * (bk // 4) <= cap and M > 128
-    return (f"tapgemm_{math}_256x{bn}", 256) if tall else (f"tapgemm_{math}_128x{bn}", 128)
+def _verify(*args, summary=SUMMARY, **kw):
+    return TG._verify(*args, summary=summary, **kw)
 
 
-def _mel_ld(num_mels):
-    return -(-num_mels // 32) * 32
-
-
-_ENGINES = {}
-_FOLDED = {}
-
-
-def _engine(varch, mode, opready=False):
-    """An engine per (architecture, arithmetic), kept for the file: the knobs are read when the context is created."""
-    from speech_inpainting_amd import synth
-    from speech_inpainting_amd.arch import HubertArch
-    from speech_inpainting_amd.engine import InpaintingEngine
-    key = (repr(varch), mode, opready)
-    if key not in _ENGINES:
-        voc, _, env = MODES[mode]
-        env = {} if opready else env
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
-            eng = InpaintingEngine(HubertArch.tiny(), varch, 20, "cuda:0", "fp32", voc)
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-        _ENGINES[key] = eng.load_state(synth.synth_hubert_state(HubertArch.tiny()), _state(varch), synth.synth_codebook(20))
-    return _ENGINES[key]
-
-
-def _w(varch, name):
-    """The packer's fp32 folded weight of a module (vocoder_ref.fold, unrounded)."""
-    key = (repr(varch), name)
-    if key not in _FOLDED:
-        _FOLDED[key] = V.fold(_state(varch), name, round16=False).float()
-    return _FOLDED[key]
-
-
-def _shapes(varch, B, Tm, t_suffix=""):
-    """{tap name: (B, rows, channels)} of every tap of the fp32 residual stream at Tm frames (stretch off)."""
-    C, L = varch.upsample_initial_channel, Tm
-    out = {"pre": (B, L, C)}
-    for i, u in enumerate(varch.upsample_rates):
-        C, L = C // 2, L * u
-        out[f"ups{i}"] = out[f"stage{i}"] = (B, L, C)
-        for j, dil in enumerate(varch.resblock_dilation_sizes):
-            for n in range(len(dil)):
-                out[f"stage{i}.rb{j}.p{n}"] = (B, L, C)
-                out[f"stage{i}.rb{j}.t{n}{t_suffix}"] = (B, L, C)
-    return out
-
-
-def _run(eng, varch, mel, lens=None, tapped=True, t_suffix=""):
-    """One generator pass -> (taps {name: (B, rows, C) cpu}, wave cpu, {kernel: launches})."""
-    B, _, Tm = mel.shape
-    shapes = _shapes(varch, B, Tm, t_suffix)
-    eng.ctx.clear_captures()
-    caps = eng.ctx.capture(list(shapes), capacity={k: s[0] * s[1] * s[2] for k, s in shapes.items()}) if tapped else {}
-    eng.ctx.profile_start(4000)
-    wave = eng.vocode_ragged(mel.cuda(), lens, stretch=False) if lens is not None else eng.vocode(mel.cuda(), stretch=False)
-    prof = {e["name"]: e["launches"] for e in eng.ctx.profile_stop()}
-    torch.cuda.synchronize()
-    taps = {}
-    for k, t in caps.items():
-        assert eng.ctx.lib.si_debug_size(eng.ctx._h, k.encode()) == t.numel(), (k, "was not produced")
-        taps[k] = t.cpu().view(shapes[k])
-    eng.ctx.clear_captures()
-    return taps, wave.cpu(), prof
-
-
-def _note(kernel, near, rest):
-    s = SUMMARY.setdefault(kernel, [0.0, 0.0, 0])
-    s[0], s[1], s[2] = max(s[0], near), max(s[1], rest), s[2] + 1
-
-
-def _one(tag, kernel, clip, got, r, stored, halo):
-    L = r.ref.shape[0]
-    c = V.check_f32(got.reshape(r.ref.shape), r.ref, r.E)
-    line, near, rest = V.report(tag, kernel, clip, c, L, stored, halo)
-    print("   " + line)
-    assert c["finite"] and c["bad"] == 0, line
-    if r.exact is not None and r.exact is not r.ref:           # bf16x3: also within the derived distance of the exact fp32 product
-        cx = V.check_f32(got.reshape(r.ref.shape), r.exact, r.E_exact)
-        linex, _, _ = V.report(tag + " vs the fp32 product", kernel, clip, cx, L, stored, halo)
-        assert cx["bad"] == 0, linex
-    _note(kernel, near, rest)
-
-
-def _verify(varch, mode, mel, lens, taps, prof, tag, clips=None, wave=None):
-    """Every tap of every clip against its reference from the tapped input; -> the configurations the launches must have taken.
-    wave: the samples, to check conv_post_kernel (fp32 rows, the slope in fp32) against conv_post_ref(mfma=False) on the last stage's tap."""
-    math = MODES[mode][1]
-    sd = _state(varch)
-    B, _, Tm = mel.shape
-    nk = len(varch.resblock_kernel_sizes)
-    a_last = V.alpha32(nk)
-    want = set()
-    Lmax = Tm
-    for b in (range(B) if clips is None else clips):
-        L = int(lens[b]) if lens is not None else Tm
-        C0 = varch.upsample_initial_channel
-        nm = varch.num_mels
-        kern, bm = _config(math, C0, Lmax, 7, 1, _mel_ld(nm))              # (conv_pre's packed K: the input width rounded up to 32, api.hip's mel_ld)
-        want.add(kern)
-        r = V.tapgemm_ref(mel[b, :, :L].t(), _w(varch, "conv_pre"), sd["conv_pre.bias"], math, V.conv_geom(1), 7 * nm)
-        x = taps["pre"][b, :L]
-        _one(f"{tag} conv_pre {nm}->{C0}", kern, b, x, r, bm, 6)
-        C, Lm = C0, Lmax
-        for i, (u, k) in enumerate(zip(varch.upsample_rates, varch.upsample_kernel_sizes)):
-            w = _w(varch, f"ups.{i}")
-            ntaps, pad = -(-k // u), (k - u) // 2
-            Lo, Lmo, Cin, C = L * u, Lm * u, C, C // 2
-            kern, bm = _config(math, u * C, (pad + Lmo - 1) // u + 1, ntaps, -1, Cin)
-            want.add(kern)
-            r = V.tapgemm_ref(x, w, sd[f"ups.{i}.bias"], math, V.tconv_geom(u), ntaps * Cin, slope=V.SLOPE32)
-            U = taps[f"ups{i}"][b, :Lo]
-            _one(f"{tag} ups{i} {Cin}->{C} u={u} k={k}", kern, b, U, r, bm * u, k)
-            L, Lm = Lo, Lmo
-            kern, bm = _config(math, C, Lm, 3, 1, C)               # (k and the dilation never change the tile here: 255 + 10 * 5 + 1 <= 384 rows)
-            want.add(kern)
-            xs_prev = None
-            for j, (rk, dils) in enumerate(zip(varch.resblock_kernel_sizes, varch.resblock_dilation_sizes)):
-                assert _config(math, C, Lm, rk, max(dils), C)[0] == kern
-                p = f"resblocks.{i * nk + j}."
-                xin = U
-                for n, d in enumerate(dils):
-                    last = n == len(dils) - 1
-                    t = taps[f"stage{i}.rb{j}.t{n}"][b, :L]
-                    r = V.tapgemm_ref(xin, _w(varch, f"{p}convs1.{n}"), sd[f"{p}convs1.{n}.bias"], math, V.conv_geom(d), rk * C, slope=V.SLOPE32)
-                    _one(f"{tag} stage{i}.rb{j}.t{n} k={rk} d={d}", kern, b, t, r, bm, (rk - 1) * d)
-                    prev = xs_prev if (last and j > 0) else None
-                    r = V.tapgemm_ref(t, _w(varch, f"{p}convs2.{n}"), sd[f"{p}convs2.{n}.bias"], math, V.conv_geom(1), rk * C, slope=V.SLOPE32,
-                                      res=xin, alpha=a_last if last else 1.0, prev=prev)
-                    out = taps[f"stage{i}.rb{j}.p{n}"][b, :L]
-                    _one(f"{tag} stage{i}.rb{j}.p{n} k={rk}" + (" alpha" if last else "") + (" acc" if prev is not None else ""), kern, b, out, r, bm, rk - 1)
-                    xin = out
-                xs_prev = xin
-            assert torch.equal(taps[f"stage{i}"][b, :L], xs_prev), f"{tag} stage{i} is not the last resblock's running sum"
-            x = xs_prev
-        if wave is not None:
-            ref, Eb = V.conv_post_ref(x, _w(varch, "conv_post"), sd["conv_post.bias"], mfma=False)
-            c = V.check_f32(wave[b, :L], ref, Eb)
-            line, near, rest = V.report(f"{tag} conv_post C={C}", "conv_post", b, c, L, 256, 3)
-            print("   " + line)
-            assert "conv_post" in prof and c["finite"] and c["bad"] == 0, line
-            assert not bool(wave[b, L:].any()), f"{tag}: samples past clip {b}'s end are not silence"
-            _note(f"conv_post_kernel C={C}", near, rest)
-    got = {n for n in prof if n.startswith("tapgemm_")}
-    assert got == want, f"{tag}: the launches took {sorted(got)}, launch_math restated gives {sorted(want)}"
-    return want
-
-
-def _uniform(varch, mode, L, seed, tag, post=False):
-    one = _mel(1, L, seed, varch.num_mels)
-    mel = torch.cat([one, one]).contiguous()
-    taps, wave, prof = _run(_engine(varch, mode), varch, mel)
-    cfgs = _verify(varch, mode, mel, None, taps, prof, f"{tag} L={L}", clips=[0], wave=wave if post else None)
-    for k, t in taps.items():
-        assert torch.equal(t[0], t[1]), f"{tag} L={L}: {k} differs between two copies of one clip"
-    assert torch.equal(wave[0], wave[1])
-    return cfgs, taps, wave
-
-
-def _reached(mode, C, L, num_mels=80):
-    """The configurations of one (C, L) case, from `_config` alone (no GPU): conv_pre, the u = 1, k = 3 upsampler(s), the pairs."""
-    math = MODES[mode][1]
-    out = {_config(math, 2 * C, L, 7, 1, _mel_ld(num_mels))[0], _config(math, C, L + 1, 3, -1, 2 * C)[0], _config(math, C, L, 3, 1, C)[0]}
-    if C == 256:
-        out |= {_config(math, 128, L + 1, 3, -1, 256)[0], _config(math, 128, L, 3, 1, 128)[0]}
-    return out
+def _uniform(*args, summary=SUMMARY, **kw):
+    return TG._uniform(*args, summary=summary, **kw)
 
 
 @pytest.mark.parametrize("L", ROWS)
@@ -341,21 +161,11 @@ def _harch(name):
     return HubertArch(num_hidden_layers=1) if name == "base" else dataclasses.replace(HubertArch.large(), num_hidden_layers=1)
 
 
-def _enc_state(harch):
-    from tests.test_gpu_encoder_ops import _state as enc_state
-    return enc_state(harch)
-
-
 def _enc_engine(name):
-    """fp32 encoder, one layer, real widths."""
-    from speech_inpainting_amd import synth
+    """fp32 encoder, one layer, real widths; one per width, kept for the session."""
     from speech_inpainting_amd.arch import VocoderArch
-    from speech_inpainting_amd.engine import InpaintingEngine
-    if ("enc", name) not in _ENGINES:
-        harch = _harch(name)
-        eng = InpaintingEngine(harch, VocoderArch.tiny(), 50, "cuda:0", "fp32", "fp32")
-        _ENGINES[("enc", name)] = eng.load_state(_enc_state(harch), synth.synth_generator_state(VocoderArch.tiny()), synth.synth_codebook(50))
-    return _ENGINES[("enc", name)]
+    harch = _harch(name)
+    return build_engine(harch, VocoderArch.tiny(), 50, "fp32", "fp32", state=(_enc_state(harch), None, None), key=("tapgemm-enc", name))
 
 
 def _enc_run(eng, harch, wave, lens=None):
@@ -366,15 +176,8 @@ def _enc_run(eng, harch, wave, lens=None):
     for nm in ("projected", "encoder_in", "last_hidden"):
         cap[nm] = R * harch.hidden_size
     cap["features"] = R * harch.conv_dim[-1]
-    eng.ctx.clear_captures()
-    caps = eng.ctx.capture(list(cap), capacity=cap)
-    eng.ctx.profile_start(4000)
-    out = eng.encode_ragged(wave, lens, normalize=False) if lens is not None else eng.encode(wave, normalize=False)
-    prof = {e["name"]: e["launches"] for e in eng.ctx.profile_stop()}
-    torch.cuda.synchronize()
-    produced = {k: eng.ctx.lib.si_debug_size(eng.ctx._h, k.encode()) for k in cap}
-    got = {k: v.cpu() for k, v in caps.items() if produced[k] > 0 and produced[k] == cap[k]}
-    eng.ctx.clear_captures()
+    got, out, prof = tapped_run(eng.ctx, cap, lambda: eng.encode_ragged(wave, lens, normalize=False) if lens is not None
+                                else eng.encode(wave, normalize=False))
     return got, R, prof, out.cpu()
 
 
@@ -387,7 +190,7 @@ def _enc_one(tag, kernel, got, ref, bound, stored=128):
     rest = float(ratio[:last0].max()) if last0 else 0.0
     print(f"   {E.fmt(tag, r)} [{kernel}] last tile {near:.3f}, rest {rest:.3f}")
     assert r["bad"] == 0, E.fmt(tag, r)
-    _note(kernel, near, rest)
+    SUMMARY.note(kernel, near, rest)
 
 
 def _check_layer32(got, harch, R, tag):
@@ -417,7 +220,6 @@ def _check_layer32(got, harch, R, tag):
 
 def _check_convs32(got, harch, B, N, tag, clip_lens=None):
     """Strided convs 1 .. n - 1 (stride 2: the 256-row tile's halo does not fit, 128 x 128 tiles) of every clip on their captured fp32 inputs."""
-    from tests.test_gpu_encoder_ops import _sel_rows
     sd = _enc_state(harch)
     Ls = harch.feat_lengths(N)
     layer = harch.feat_extract_norm == "layer"
@@ -438,7 +240,7 @@ def _check_convs32(got, harch, B, N, tag, clip_lens=None):
             r = E.check_f32(y[b][rows], ref, bound)
             print("   " + E.fmt(f"{tag} conv{i} clip {b} (L = {Lb}, last tile {Lb % 128} rows) [{kern}]", r))
             assert r["bad"] == 0, E.fmt(f"{tag} conv{i} clip {b}", r)
-            _note(kern, r["worst"], 0.0)
+            SUMMARY.note(kern, r["worst"], 0.0)
     return want
 
 
@@ -466,7 +268,7 @@ def _check_posconv32(got, harch, clips, Tmax, tag):
         line, near, rest = V.report(f"{tag} positional conv ({G} groups of {cg}, BK = {32 if cg % 32 == 0 else 16}) T={T}", kern, r0, c, T, bm, k // 2)
         print("   " + line)
         assert c["finite"] and c["bad"] == 0, line
-        _note(kern + f" groups BK={32 if cg % 32 == 0 else 16}", near, rest)
+        SUMMARY.note(kern + f" groups BK={32 if cg % 32 == 0 else 16}", near, rest)
     return {kern}
 
 
@@ -508,7 +310,6 @@ ENC_CASES = [(1, 127), (2, 128), (1, 129), (1, 255), (1, 257)]
 def test_fp32_encoder_tapgemm_launches(arch, B, T):
     """M = B T = 127, 256, 129, 255, 257 transformer rows (last tiles of 127, 128, 1, 127 and 1 rows; T = 127 / 128 | 129 on both sides of the
     positional conv's 256-row switch); the sample count puts strided convs at last tiles of 1 and 127 rows where it can."""
-    from tests.test_gpu_encoder_ops import _pick_wave
     harch = _harch(arch)
     eng = _enc_engine(arch)
     wave = _pick_wave(harch, B, T, 128)
@@ -554,7 +355,4 @@ def test_fp32_encoder_ragged_with_a_single_frame_clip(arch):
 
 def test_zz_summary_of_ratios():
     """(last in the file) the largest err / E per kernel configuration over every check above: near seams and clip edges | elsewhere."""
-    for k in sorted(SUMMARY):
-        s = SUMMARY[k]
-        print(f"   SUMMARY {k}: max err/E seam+edge rows {s[0]:.4f}, interior {s[1]:.4f} over {s[2]} checks")
-        assert s[0] <= 1.0 and s[1] <= 1.0
+    SUMMARY.report()

@@ -21,245 +21,28 @@ failure there.  Two are loose: conv_post's (fp32 output, worst-case growth of 22
 order, not a one-ulp mistake.  A packed leaky-ReLU computed in fp32 and rounded once instead (one ulp on some negative operands, a
 tenth of the activations' size) stays under the pair bound (0.72 against 0.71 at C = 64); the bit-equality of reschain.hip with the pair
 kernels is what notices it."""
-import os
 import re
 
 import pytest
 import torch
 
 from tests import vocoder_ref as V
+from tests.cases import R1, _arch, _interleave, _mel, _pair_lengths
+from tests.harness import RatioSummary
+from tests.vocoder_checks import _engine, _run
+from tests.vocoder_checks import _verify as _verify_into
 
 pytestmark = pytest.mark.gpu
 
-torch.set_num_threads(16)
-R1 = {32: 256, 64: 512, 128: 256, 256: 128}           # rows of a pair kernel's tile (see the module docstring)
-V1_BLOCKS = dict(resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3)
-SUMMARY = {}                                          # kernel -> [max err / E near seams and edges, max elsewhere, checks]
+SUMMARY = RatioSummary(digits=3)                      # this file's max err / E per kernel
 
 
-def _arch(C, u=1, k=3, num_mels=80, **kw):
-    """One stage of C channels behind an upsampler (u, k).  C = 256 gets a second u = 1 stage of 128 channels behind it: conv_post_kernel
-    keeps 262 rows of C + 4 floats in LDS and refuses 256 channels (no generator ends that wide).  num_mels: conv_pre's input width
-    (80 mel bins; the unit vocoder's 384 embedding channels)."""
-    from speech_inpainting_amd.arch import VocoderArch
-    blocks = dict(V1_BLOCKS)
-    blocks.update(kw)
-    us, ks = ((u, 1), (k, 3)) if C == 256 else ((u,), (k,))
-    return VocoderArch(upsample_rates=us, upsample_kernel_sizes=ks, upsample_initial_channel=2 * C, num_mels=num_mels, **blocks)
-
-
-def _padded(C):
-    """The width the fp16 stream carries a stage of C channels at (api.hip, stage_channels: 4 <= C < 32 is padded to 32 with zero weights)."""
-    return 32 if 4 <= C < 32 else C
-
-
-_STATE = {}
-_FOLDED = {}
-
-
-def _key(varch):
-    return repr(varch)
-
-
-def _state(varch):
-    from speech_inpainting_amd import synth
-    if _key(varch) not in _STATE:
-        _STATE[_key(varch)] = synth.synth_generator_state(varch, 47)
-    return _STATE[_key(varch)]
-
-
-def _w(varch, name):
-    """The kernel's fp16 weight of a module, as float64 (vocoder_ref.fold: the packer's fold, rounded once)."""
-    if (_key(varch), name) not in _FOLDED:
-        _FOLDED[(_key(varch), name)] = V.fold(_state(varch), name)
-    return _FOLDED[(_key(varch), name)]
-
-
-def _engine(varch, env=None):
-    """fp16 vocoder; `env` knobs (SI_VOC_FUSE, SI_VOC_CHAIN, SI_VOC_UPSGEMM) are read when the context is created."""
-    from speech_inpainting_amd import synth
-    from speech_inpainting_amd.arch import HubertArch
-    from speech_inpainting_amd.engine import InpaintingEngine
-    harch = HubertArch.tiny()
-    env = env or {}
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        eng = InpaintingEngine(harch, varch, 20, "cuda:0", "fp32", "fp16")
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return eng.load_state(synth.synth_hubert_state(harch), _state(varch), synth.synth_codebook(20))
-
-
-def _shapes(varch, B, Tm):
-    """{tap name: (B, rows, channels)} of every tap the architecture can produce at Tm frames (stretch off); a stage's taps have the
-    width the stream carries it at (`_padded`)."""
-    C, L = varch.upsample_initial_channel, Tm
-    out = {"pre.f16": (B, L, C)}
-    for i, u in enumerate(varch.upsample_rates):
-        C, L = C // 2, L * u
-        out[f"ups{i}.f16"] = out[f"stage{i}.f16"] = (B, L, _padded(C))
-        for j, dil in enumerate(varch.resblock_dilation_sizes):
-            for n in range(len(dil)):
-                out[f"stage{i}.rb{j}.p{n}.f16"] = (B, L, _padded(C))
-    return out
-
-
-def _run(eng, varch, mel, lens=None, tapped=True):
-    """One generator pass -> (taps {name: (B, rows, C) cpu fp16} of the taps the path produced, wave cpu, {kernel: launches})."""
-    B, _, Tm = mel.shape
-    shapes = _shapes(varch, B, Tm)
-    eng.ctx.clear_captures()
-    caps = eng.ctx.capture(list(shapes), capacity={k: s[0] * s[1] * s[2] for k, s in shapes.items()}) if tapped else {}
-    eng.ctx.profile_start(4000)
-    wave = eng.vocode_ragged(mel.cuda(), lens, stretch=False) if lens is not None else eng.vocode(mel.cuda(), stretch=False)
-    prof = {e["name"]: e["launches"] for e in eng.ctx.profile_stop()}
-    torch.cuda.synchronize()
-    taps = {}
-    for k, t in caps.items():
-        assert t.dtype == torch.float16
-        if eng.ctx.lib.si_debug_size(eng.ctx._h, k.encode()) == t.numel():
-            taps[k] = t.cpu().view(shapes[k])
-    eng.ctx.clear_captures()
-    return taps, wave.cpu(), prof
-
-
-def _kernel(prof, *patterns):
-    """The one profiled kernel family matching any of the patterns; asserts that it ran."""
-    hit = sorted(n for n in prof if any(re.fullmatch(p, n) for p in patterns))
-    assert hit, (patterns, sorted(prof))
-    return "+".join(hit)
-
-
-def _note(kernel, near, rest):
-    kernel = "tapgemm_f16_*" if kernel.startswith("tapgemm") else kernel          # (its tile shapes follow the layer: one line for the family)
-    s = SUMMARY.setdefault(kernel, [0.0, 0.0, 0])
-    s[0], s[1], s[2] = max(s[0], near), max(s[1], rest), s[2] + 1
-
-
-def _one(tag, kernel, clip, got, ref, E, stored, halo, hot, f32=False):
-    L = ref.shape[0]
-    if not hot:                                            # the case is built to stay far from saturation: only then is every element an ordinary check
-        assert float(ref.abs().max()) < V.F16_MAX / 4, (tag, float(ref.abs().max()))
-    r = (V.check_f32 if f32 else V.check_f16)(got.reshape(ref.shape), ref, E)
-    line, near, rest = V.report(tag, kernel, clip, r, L, stored, halo)
-    print("   " + line)
-    assert r["finite"] and r["bad"] == 0, line
-    _note(kernel, near, rest)
-    return r
-
-
-def _verify(varch, mel, lens, taps, wave, prof, tag, ops=("pre", "ups", "rb", "post"), clips=None, hot=False, x2_from=None, upsgemm=True):
-    """Every produced tap of every clip against its reference from the tapped input.  x2_from: the taps of a run of the SAME input with
-    the pairs one by one (SI_VOC_CHAIN=0), which supply the x_2 a reschain.hip launch keeps to itself."""
-    sd = _state(varch)
-    B, _, Tm = mel.shape
-    nk = len(varch.resblock_kernel_sizes)
-    two = str(varch.resblock) == "2"
-    # stored activated: the producer of an upsampler that ran in gemmcu's TC kernels (include/si_hip.h); all candidates or none
-    cand = [i for i, (u, k) in enumerate(zip(varch.upsample_rates, varch.upsample_kernel_sizes))
-            if -(-k // u) == 2 and (u * (varch.upsample_initial_channel >> (i + 1))) % 256 == 0 and (varch.upsample_initial_channel >> i) % 64 == 0]
-    n_tc = sum(v for k, v in prof.items() if k.startswith("gemmcu_f16_"))
-    assert n_tc in (0, len(cand)), (n_tc, cand, prof)
-    on_tc = set(cand) if n_tc else set()
-    assert upsgemm or not on_tc
-    def real(name, b, L, C):
-        """Rows :L of clip b of a stage tap as the C real channels; the channels the stream pads the stage with must hold exact zeros."""
-        t = taps[name][b, :L]
-        assert t.shape[1] == _padded(C), (name, t.shape, C)
-        return V.real_channels(t, C, f"{tag} {name} clip {b}")
-
-    for b in (range(B) if clips is None else clips):
-        L = int(lens[b]) if lens is not None else Tm
-        x = taps["pre.f16"][b, :L]
-        if "pre" in ops:
-            a = V.h16(mel[b, :, :L].t().clamp(-V.F16_MAX, V.F16_MAX))
-            ref, E = V.tapconv_ref(a, _w(varch, "conv_pre"), sd["conv_pre.bias"], out_slope=V.SLOPE32 if 0 in on_tc else 1.0)
-            _one(f"{tag} conv_pre", _kernel(prof, r"tapgemm_f16_.*"), b, x, ref, E, None, 3, hot)
-        C = varch.upsample_initial_channel
-        for i, (u, k) in enumerate(zip(varch.upsample_rates, varch.upsample_kernel_sizes)):
-            staged = x.double() if i in on_tc else V.lrelu16(x).double()
-            Lo, C = L * u, C // 2
-            U16 = real(f"ups{i}.f16", b, Lo, C)
-            Cp = _padded(C)                                        # the kernels' width: names and tile heights follow it, the references C
-            if "ups" in ops:
-                ref, E = V.upsample_ref(staged, _w(varch, f"ups.{i}"), sd[f"ups.{i}.bias"], u)
-                if i in on_tc:
-                    kern = _kernel(prof, r"gemmcu_f16_.*")
-                    rows = int(re.search(r"gemmcu_f16_(\d+)x", kern).group(1)) * u           # BM GEMM rows = BM u output rows per tile
-                elif u == 2 and k == 4 and 2 * C in (128, 64) and f"upsample_f16_c{2 * C}" in prof:
-                    kern, rows = f"upsample_f16_c{2 * C}", 256 * u
-                else:
-                    kern, rows = _kernel(prof, r"tapgemm_f16_.*"), None
-                _one(f"{tag} ups{i} {2 * C}->{C} u={u}", kern, b, U16, ref, E, rows, k, hot)
-            L = Lo
-            act_next = (i + 1) in on_tc
-            xs_prev = None
-            for j, (rk, dils) in enumerate(zip(varch.resblock_kernel_sizes, varch.resblock_dilation_sizes)):
-                r = f"resblocks.{i * nk + j}."
-                xin = U16
-                last_n = len(dils) - 1
-                for n, d in enumerate(dils):
-                    name = f"stage{i}.rb{j}.p{n}.f16"
-                    last = n == last_n
-                    chained = name not in taps or (last and f"stage{i}.rb{j}.p0.f16" not in taps and last_n > 0)
-                    if name not in taps:                               # inside a reschain.hip launch: x_n from the pairs run
-                        assert x2_from is not None and not last, (name, sorted(taps))
-                        xin = x2_from[name][b, :L, :C]
-                        continue
-                    out = real(name, b, L, C)
-                    if "rb" in ops:
-                        alpha = V.alpha32(nk) if last else 1.0
-                        prev = xs_prev.double() if (last and j > 0) else None
-                        os_ = V.SLOPE32 if (last and j == nk - 1 and act_next) else 1.0
-                        a = V.lrelu16(xin).double()
-                        if two:
-                            ref, E = V.rb2_ref(a, xin.double(), _w(varch, f"{r}convs.{n}"), sd[f"{r}convs.{n}.bias"], d, alpha, prev, os_)
-                            kern, stored, halo = _kernel(prof, r"tapgemm_f16_.*"), None, (rk - 1) * d
-                        else:
-                            ref, E = V.pair_ref(a, xin.double(), _w(varch, f"{r}convs1.{n}"), sd[f"{r}convs1.{n}.bias"],
-                                                _w(varch, f"{r}convs2.{n}"), sd[f"{r}convs2.{n}.bias"], d, alpha, prev, os_)
-                            halo = (rk - 1) * (d + 1)
-                            acc = "_acc" if (last and j > 0) else ""
-                            if chained:
-                                kern, stored = f"reschain_f16_c{Cp}{acc}", 768 - (rk - 1) * (sum(dils) + 3)
-                                assert torch.equal(taps[name][b, :L], x2_from[name][b, :L]), f"{tag} {name}: the chain kernel and the pair kernels differ"
-                            elif f"respair_f16_c{Cp}{acc}" in prof:
-                                kern, stored = f"respair_f16_c{Cp}{acc}", R1[Cp] - (rk - 1)
-                            else:
-                                kern, stored = _kernel(prof, r"tapgemm_f16_.*"), None
-                            assert kern.startswith("tapgemm") or kern in prof, (kern, sorted(prof))
-                        _one(f"{tag} {name} k={rk} d={d}" + (" acc" if prev is not None else "") + (" act" if os_ != 1.0 else ""),
-                             kern, b, out, ref, E, stored, halo, hot)
-                    xin = out
-                xs_prev = xin
-            assert torch.equal(real(f"stage{i}.f16", b, L, C), xs_prev), f"{tag} stage{i}.f16 is not the last resblock's running sum"
-            x = xs_prev
-        if "post" in ops:
-            ref, E = V.conv_post_ref(x, V.fold(sd, "conv_post", round16=False).float(), sd["conv_post.bias"], mfma=(_padded(C) == 32))
-            _one(f"{tag} conv_post C={C}", _kernel(prof, "conv_post"), b, wave[b, :L], ref, E, 512 if _padded(C) == 32 else 256, 3, True, f32=True)
-            assert not bool(wave[b, L:].any()), f"{tag}: samples past clip {b}'s end are not silence"
-
-
-def _mel(B, Tm, seed, num_mels=80):
-    """The generator's input: a synthetic log-mel at 80 bins; at any other width (the unit vocoder's 384 channels of concatenated
-    embeddings) N(0, 0.5^2), as test_ida_style_generator_geometry_matches_oracle draws it."""
-    from speech_inpainting_amd import synth
-    if num_mels == 80:
-        return synth.synth_mel(B, Tm, 80, seed)
-    return torch.randn(B, num_mels, Tm, generator=torch.Generator().manual_seed(seed)) * 0.5
+def _verify(*args, summary=SUMMARY, **kw):
+    return _verify_into(*args, summary=summary, **kw)
 
 
 def _ragged(eng, varch, lengths, seed, tag, **kw):
-    if isinstance(lengths, list):
-        lens = lengths                                     # (a list: the batch as given)
-    else:
-        lengths = sorted(set(int(v) for v in lengths if v >= 1))
-        lens = lengths[::2] + lengths[1::2][::-1]          # long and short clips interleaved: workgroups get different tile counts
+    lens = lengths if isinstance(lengths, list) else _interleave(lengths)          # (a list: the batch as given)
     assert len(lens) <= 32
     mel = _mel(len(lens), max(lens), seed, varch.num_mels)
     taps, wave, prof = _run(eng, varch, mel, lens)
@@ -276,14 +59,6 @@ def _uniform(eng, varch, L, seed, tag, **kw):
         assert torch.equal(t[0], t[1]), f"{tag} uniform L={L}: {k} differs between two copies of one clip"
     assert torch.equal(wave[0], wave[1])
     return prof
-
-
-def _pair_lengths(C, ks=(3, 7, 11), dils=(1, 3, 5)):
-    out = {1, 2, R1[C], R1[C] + 1}
-    for k in ks:
-        st = R1[C] - (k - 1)
-        out |= {k - 1, st - 1, st, st + 1, 2 * st + 1} | {(k - 1) * d for d in dils}
-    return out
 
 
 @pytest.mark.parametrize("C", [32, 64, 128, 256])
@@ -426,7 +201,4 @@ def test_hot_input_saturates_exactly_where_it_must():
 
 def test_zz_summary_of_ratios():
     """(last in the file) the largest err / E per kernel over every check above: near seams and clip edges | elsewhere."""
-    for k in sorted(SUMMARY):
-        s = SUMMARY[k]
-        print(f"   SUMMARY {k}: max err/E seam+edge rows {s[0]:.3f}, interior {s[1]:.3f} over {s[2]} checks")
-        assert s[0] <= 1.0 and s[1] <= 1.0
+    SUMMARY.report()

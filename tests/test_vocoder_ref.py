@@ -528,8 +528,7 @@ def test_every_fp16_input_of_the_unit_vocoder_tests_stays_far_from_saturation():
     """tests/test_gpu_unitvoc_ops.py checks every element as an ordinary bound only where max |ref| < 65504 / 4 (`_one` asserts it on the
     device): here the same inputs (architecture, seed, frames), composed on the CPU for the clips the GPU test checks, one clip per distinct
     (architecture, seed, length)."""
-    from tests.test_gpu_unitvoc_ops import fp16_inputs
-    from tests.test_gpu_vocoder_ops import _mel, _state
+    from tests.cases import _mel, _state, fp16_inputs
     torch.set_num_threads(min(16, torch.get_num_threads()))
     seen, worst = set(), 0.0
     for tag, arch, seed, lens, Tm, clips in fp16_inputs():
