@@ -29,6 +29,8 @@
  *   si_cut_clips / si_patch_regions  <- the same lines for a recording LONGER than one clip: the slices that turn one file into the
  *                           clips the script takes one per run, and the write-out of many clips' gaps into the one long file
  *                                                                             I_ea/predict.py:79-80,104,203-207
+ *   si_quiet_runs        <- nothing the reference computes: it has no detection.  The call supplies the `mask:` values
+ *                           (start_pos_in_sec, end_pos_in_sec) that a user of the script types by hand      I_ea/predict.py:85-90
  *   si_load_weights      <- model.load_state_dict / generator.load_state_dict + remove_weight_norm + ApplyKmeans
  *                           I_ea/predict.py:117-122,149 ; I_ea/hifi_gan/models.py:125-132 ; I_ea/dataset/km_label.py:12-24
  *
@@ -544,6 +546,22 @@ typedef struct si_region_table {
  * whose span is outside that chunk's [k0, k1).  num_chunks = 0 launches nothing and succeeds. */
 int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_table* table, const float* gen, int Lrow, const float* gain,
                      float* out_f32, int16_t* out_pcm, si_stream_t stream);
+
+/* ---- Dropout detection: where the gaps of a damaged recording are -------------------------------------------------
+ * The reference has no detection: the script's user types the one mask into predict.yaml (I_ea/predict.py:85-90).  This call finds
+ * what a digital dropout leaves behind -- runs of (near) digital silence from lost packets, underruns or muted samples -- on the
+ * device, where the recording already lies; gaps.runs_to_gaps turns the runs into gaps on the 20 ms grid.
+ * x device, n samples, one channel, any sample rate: fp32 (is_pcm16 = 0) or int16 PCM as it lies in a file (is_pcm16 != 0); the base
+ * needs only its element's alignment.  Sample i is QUIET iff |x[i]| <= threshold: NaN is loud, -0.0 is quiet, |-32768| is taken in
+ * int32, samples at and past n are loud.  The result is every MAXIMAL run of quiet samples of at least min_len samples, as int32
+ * (start, len) rows SORTED BY START: rows [0, min(total, max_runs)) of runs (device int32 (max_runs, 2)) are written, rows at and past
+ * that are not touched, and n_runs (device int32 (1)) receives the TOTAL number of such runs whether or not they all fit.  The same
+ * input gives the same bytes (no atomics; plain stores).  max_runs = 0 counts only (runs may be NULL).  Needs no weights.  Scratch
+ * (one bit per sample, five words per 2048 samples) is the context's own and is reused by the next call in stream order.
+ * SI_EINVAL before any launch, naming the argument, for: NULL x or n_runs; NULL runs with max_runs > 0; n < 1 or n > 2^31 - 1 - 2048;
+ * threshold negative or NaN; min_len < 1; max_runs < 0. */
+int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs,
+                  int32_t* n_runs, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

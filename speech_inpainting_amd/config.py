@@ -2,6 +2,7 @@
 
 Only the keys the predict script reads are interpreted (I_ea/predict.py:60-73,85-89,109,144-146,158-159); unknown keys
 are ignored, so both shipped files load.  An optional `bench:` / `batch:` block may be added by users of this package.
+Keys of this package's own: `masks:`, `patch:`, `long:` and `detect:` (see PredictConfig).
 """
 from __future__ import annotations
 
@@ -57,6 +58,8 @@ class PredictConfig:
                                             # only the gaps filled); None without the key
     long: Optional[dict] = None   # optional `long:` mapping ({clip_s: 4.0, context_s: 1.0, batch: 32}): the file is a recording of any
                                   # length, served as context clips (engine.patch_recording); None without the key
+    detect: Optional[dict] = None  # optional `detect:` mapping ({threshold: 0.0, min_ms: 5.0, max_ms: 400.0, pad_frames: 0}): the gaps are
+                                   # found in the file itself (engine.find_gaps) instead of given as `mask:` / `masks:`; needs `long:`
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -139,6 +142,23 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
             if long_cfg["batch"] < 1 or long_cfg["clip_s"] <= 2 * long_cfg["context_s"]:
                 raise ValueError(f"{path}: `long:` needs batch >= 1 and clip_s > 2 * context_s, got {long_cfg}")
+        detect_cfg = None
+        if "detect" in data:
+            dm = data["detect"] if data["detect"] is not None else {}
+            if not isinstance(dm, dict):
+                raise ValueError(f"{path}: `detect:` must be a mapping (threshold: <full scale>, min_ms: <milliseconds>, max_ms: <milliseconds>, "
+                                 f"pad_frames: <20 ms frames>)")
+            if long_cfg is None:
+                raise ValueError(f"{path}: `detect:` needs a `long:` mapping (the gaps it finds are served on the recording's own time axis)")
+            if "mask" in data or "masks" in data:
+                raise ValueError(f"{path}: give either `detect:` (the gaps are found) or `mask:` / `masks:` (the gaps are given), not both")
+            detect_cfg = {"threshold": 0.0, "min_ms": 5.0, "max_ms": 400.0, "pad_frames": 0}
+            for key, val in dm.items():
+                if key not in detect_cfg:
+                    raise ValueError(f"{path}: unknown key `{key}` in `detect:` (it takes threshold, min_ms, max_ms, pad_frames)")
+                detect_cfg[key] = int(val) if key == "pad_frames" else float(val)
+                if not detect_cfg[key] >= 0:
+                    raise ValueError(f"{path}: detect.{key} = {detect_cfg[key]} is negative")
         return PredictConfig(
             dataset=ds,
             wave_path=data["wave"][ds]["wave_path"],
@@ -154,7 +174,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_type=str(data["hubert_model"]["type"]),
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
-            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg)
+            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, detect=detect_cfg)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

@@ -103,6 +103,8 @@ struct si_ctx {
     int vl_next = 0;
     float* km_cnorm = nullptr;               // |c_k|^2 scratch of si_kmeans_assign (K floats; library-owned, stream-ordered reuse)
     int km_cnorm_cap = 0;
+    char* det_scratch = nullptr;             // bitmap + per-chunk words of si_quiet_runs (library-owned, stream-ordered reuse, grown on demand)
+    size_t det_scratch_cap = 0;
 };
 
 static char g_create_err[512] = "";
@@ -768,6 +770,7 @@ void si_destroy(si_ctx* ctx) {
     if (ctx->wdev) { (void)hipSetDevice(ctx->device); (void)hipFree(ctx->wdev); }
     if (ctx->fe_dev) { (void)hipSetDevice(ctx->device); (void)hipFree(ctx->fe_dev); }
     if (ctx->km_cnorm) { (void)hipSetDevice(ctx->device); (void)hipFree(ctx->km_cnorm); }
+    if (ctx->det_scratch) { (void)hipSetDevice(ctx->device); (void)hipFree(ctx->det_scratch); }
     for (hipEvent_t e : ctx->prof_pool) (void)hipEventDestroy(e);
     for (int i = 0; i < si_ctx::VL_SLOTS; ++i) {
         if (ctx->vl_ev[i]) { (void)hipEventSynchronize(ctx->vl_ev[i]); (void)hipEventDestroy(ctx->vl_ev[i]); }
@@ -2089,6 +2092,28 @@ int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_ta
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     const SiRegions rt{t->start, t->len, t->span_win, t->span_lim, t->win_ctx, t->win_start, t->chunk, t->k0, t->k1, t->ramp, fade};
     return si_launch_patch_regions(ctx, orig, rt, Q, gen, Lrow, gain, N22, out_f32, out_pcm, static_cast<hipStream_t>(stream));
+}
+
+// ---- dropout detection
+int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
+                  si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!x) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: x is NULL");
+    if (!n_runs) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: n_runs is NULL");
+    if (max_runs < 0) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: max_runs = %d is negative", max_runs);
+    if (!runs && max_runs > 0) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: runs is NULL with max_runs = %d", max_runs);
+    if (n < 1 || (long)n > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: n = %d samples, outside 1 .. %ld", n, SI_MAX_REC);
+    if (!(threshold >= 0.f)) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: threshold = %g is negative or NaN", (double)threshold);
+    if (min_len < 1) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: min_len = %d samples, at least 1", min_len);
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t need = si_detect_scratch_bytes(n);
+    if (need > ctx->det_scratch_cap) {                                 // (a context is single-threaded and its calls stream-ordered by contract)
+        if (ctx->det_scratch) { SI_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream))); SI_HIP_CHECK(hipFree(ctx->det_scratch)); ctx->det_scratch = nullptr; ctx->det_scratch_cap = 0; }
+        const size_t cap = std::max(need, (size_t)1 << 20);
+        SI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx->det_scratch), cap));
+        ctx->det_scratch_cap = cap;
+    }
+    return si_launch_quiet_runs(ctx, x, is_pcm16 != 0, n, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

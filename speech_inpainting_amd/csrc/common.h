@@ -345,6 +345,16 @@ struct SiRegions {
 int si_launch_patch_regions(si_ctx* ctx, const float* orig, const SiRegions& rt, int Q, const float* gen, int Lrow, const float* gain,
                             int N22, float* out, int16_t* pcm, hipStream_t st);
 
+// ------------------------------------------------------------------------------------------------
+// dropout detection (detect_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// bytes of scratch the passes need for n samples: one bit per sample and five words per chunk of 2048 samples
+size_t si_detect_scratch_bytes(int n);
+// x device fp32 or int16 (n) -> runs (max_runs, 2) = the maximal runs of |x| <= thr of at least min_len samples, sorted by start, and
+// *n_runs = how many there are (all of them, whether or not they fit); arguments validated by the caller, scratch 16-byte aligned
+int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
+                         char* scratch, hipStream_t st);
+
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16
 // rounding every consumer of these outputs applies; 15 VALU operations instead of libm erff's ~31 with two divergent branches.

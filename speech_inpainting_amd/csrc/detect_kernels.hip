@@ -1,0 +1,286 @@
+// detect_kernels.hip -- dropout detection, gfx950: every maximal run of quiet samples (|x| <= thr) of at least min_len
+// samples in a recording of up to 2^31 - 1 - 2048 samples, as (start, len) rows sorted by start.  One pass over the samples, the rest
+// over one bit per sample and a few words per chunk of DT_CHUNK samples:
+//   detect_bits_kernel     the quiet bits of a chunk (one byte per thread: 8 consecutive samples) + the chunk's summary {lead, trail}
+//   detect_carry_kernel    carry[c] = the length of the quiet run that ends exactly in front of chunk c (a segmented scan, one workgroup)
+//   detect_runs_kernel     <false>: the qualifying runs that END in each chunk, counted; <true>: written at offset[c] + rank
+//   detect_offsets_kernel  the exclusive scan of the counts (one workgroup) and the total, a plain store
+// A run belongs to the chunk its LAST sample lies in, chunks are numbered along the recording and the ranks inside a chunk follow the
+// samples, so the rows come out sorted by construction: no atomics, no sort, and the same input gives the same bytes.
+#include "common.h"
+
+constexpr int DT_CHUNK = 2048;      // samples per workgroup: 256 threads x 8 consecutive samples (patch_kernels.hip's PC_CHUNK)
+constexpr int DT_TILE = 1024;       // chunks per tile of the two single-workgroup scans: 256 threads x 4 consecutive chunks
+
+struct DtMax { __device__ int operator()(int a, int b) const { return a > b ? a : b; } };
+struct DtMin { __device__ int operator()(int a, int b) const { return a < b ? a : b; } };
+struct DtAdd { __device__ int operator()(int a, int b) const { return a + b; } };
+
+// The EXCLUSIVE prefix of v over the workgroup's 256 threads under `op` (identity `ident`), and the workgroup's total in `tot`: a 6-step
+// wave scan with shuffles, the four wave totals through LDS (sw: 4 ints).  Every thread of the workgroup calls it.
+template <class Op>
+__device__ __forceinline__ int dt_block_excl(int v, int ident, int* sw, int& tot, Op op) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(incl, o, 64);
+        if (lane >= o) incl = op(u, incl);
+    }
+    if (lane == 63) sw[wave] = incl;
+    __syncthreads();
+    int pre = ident, all = ident;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int s = sw[w];
+        if (w < wave) pre = op(pre, s);
+        all = op(all, s);
+    }
+    tot = all;
+    int ex = __shfl_up(incl, 1, 64);
+    if (lane == 0) ex = ident;
+    __syncthreads();                                                  // sw may be written again by the next call
+    return op(pre, ex);
+}
+
+// NaN compares false: loud.  -0.0 has magnitude 0: quiet.  |-32768| is taken in int32 and is exact in fp32.
+__device__ __forceinline__ bool dt_quiet(float v, float thr) { return __builtin_fabsf(v) <= thr; }
+__device__ __forceinline__ bool dt_quiet(int16_t v, float thr) { const int a = v; return (float)(a < 0 ? -a : a) <= thr; }
+
+// ------------------------------------------------------------------------------------------------ pass 1: bits + summary
+// grid (chunks), 256 threads.  Thread t owns samples [c0 + 8 t, c0 + 8 t + 8): 32 bytes of fp32 (two 16-byte loads) or 16 bytes of int16
+// (one).  Callers pass views, so the base is generally off the 16-byte grid; c0 * sizeof(T) is a multiple of 16, so the alignment is the
+// call's: an aligned call takes the 16-byte loads, any other stages the chunk through LDS with coalesced element loads and reads its
+// eight samples from there.  Samples at and past n are loud, so bit (c0 + i >= n) is 0 and a run never reaches past the input.
+//   lead  = quiet samples from the chunk's first sample forward (the chunk's length when all of it is quiet)
+//   trail = quiet samples from the chunk's last sample backward (likewise)
+template <typename T>
+__global__ __launch_bounds__(256) void detect_bits_kernel(const T* __restrict__ x, int n, float thr, uint8_t* __restrict__ bitmap,
+                                                          int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    __shared__ __attribute__((aligned(16))) T tile[DT_CHUNK];
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0), g = c0 + t * 8;
+    union { uint4 q[sizeof(T) / 2]; T e[8]; } u;
+    if ((reinterpret_cast<size_t>(x) & 15) == 0) {
+        if (g + 8 <= n) {
+#pragma unroll
+            for (int i = 0; i < (int)sizeof(T) / 2; ++i) u.q[i] = reinterpret_cast<const uint4*>(x + g)[i];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) u.e[j] = g + j < n ? x[g + j] : T(0);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = j * 256 + t;
+            tile[i] = i < len ? x[c0 + i] : T(0);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < (int)sizeof(T) / 2; ++i) u.q[i] = reinterpret_cast<const uint4*>(tile + t * 8)[i];
+    }
+    unsigned b = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b |= (t * 8 + j < len && dt_quiet(u.e[j], thr)) ? 1u << j : 0u;
+    bitmap[(size_t)c * 256 + t] = (uint8_t)b;
+    // bits at and past len are 0, so the first loud bit is at most len
+    const unsigned loud = ~b & 0xffu;
+    const int k = len - t * 8;
+    const unsigned inside = loud & (k >= 8 ? 0xffu : k <= 0 ? 0u : (1u << k) - 1u);
+    int first, last;
+    (void)dt_block_excl(loud ? t * 8 + __builtin_ctz(loud) : DT_CHUNK, DT_CHUNK, sw, first, DtMin());
+    (void)dt_block_excl(inside ? t * 8 + 31 - __builtin_clz(inside) : -1, -1, sw, last, DtMax());
+    if (t == 0) {
+        lead[c] = first;
+        trail[c] = len - 1 - last;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pass 2: carries
+// One workgroup.  Chunk c maps the quiet run that ends in front of it to the one that ends in front of chunk c + 1:
+//     f_c(v) = v + len_c  when the whole chunk is quiet (lead == len_c),    f_c(v) = trail_c  otherwise
+// a map (a, b): v -> a ? v + b : b, closed under composition ((a2, b2) after (a1, b1) = (a1 & a2, a2 ? b1 + b2 : b2)), so
+// carry[c] = (f_{c-1} o ... o f_0)(0) is a scan.  Per tile of DT_TILE chunks a thread composes its 4 consecutive chunks, the
+// workgroup scans the 256 maps (shuffles inside a wave, four wave totals through LDS), each thread applies its prefix to the tile's
+// incoming carry and steps through its chunks; the tile's total map carries the value on.  b <= n throughout: no overflow.
+struct DtMap { int a, b; };
+__device__ __forceinline__ DtMap dt_then(DtMap p, DtMap q) { return DtMap{p.a & q.a, q.a ? p.b + q.b : q.b}; }   // q after p
+__device__ __forceinline__ int dt_apply(DtMap m, int v) { return m.a ? v + m.b : m.b; }
+
+__global__ __launch_bounds__(256) void detect_carry_kernel(const int32_t* __restrict__ lead, const int32_t* __restrict__ trail, int nchunks, int n,
+                                                           int32_t* __restrict__ carry) {
+    __shared__ DtMap sw[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int v0 = 0;                                                       // the carry into the tile (uniform)
+    for (int base = 0; base < nchunks; base += DT_TILE) {
+        DtMap f[4], mine{1, 0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = base + t * 4 + k;
+            f[k] = DtMap{1, 0};
+            if (c < nchunks) {
+                const int len = min(DT_CHUNK, n - c * DT_CHUNK), ld = lead[c];
+                f[k] = ld == len ? DtMap{1, len} : DtMap{0, trail[c]};
+            }
+            mine = dt_then(mine, f[k]);
+        }
+        DtMap incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            DtMap p{__shfl_up(incl.a, o, 64), __shfl_up(incl.b, o, 64)};
+            if (lane >= o) incl = dt_then(p, incl);
+        }
+        if (lane == 63) sw[wave] = incl;
+        __syncthreads();
+        DtMap pre{1, 0}, all{1, 0};
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const DtMap s = sw[w];
+            if (w < wave) pre = dt_then(pre, s);
+            all = dt_then(all, s);
+        }
+        DtMap ex{__shfl_up(incl.a, 1, 64), __shfl_up(incl.b, 1, 64)};
+        if (lane == 0) ex = DtMap{1, 0};
+        int v = dt_apply(dt_then(pre, ex), v0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = base + t * 4 + k;
+            if (c < nchunks) carry[c] = v;
+            v = dt_apply(f[k], v);
+        }
+        v0 = dt_apply(all, v0);
+        __syncthreads();                                              // sw is written again by the next tile
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ passes 3 and 4: count, emit
+// grid (chunks), 256 threads.  Sample i ends a run when it is quiet and sample i + 1 is loud (the chunk's last sample looks at the next
+// chunk's first bit, lead[c + 1] > 0; past the last chunk everything is loud).  The run starts one past the last loud sample before i in
+// the chunk -- inside the thread's own byte, or else the workgroup max-scan of "last loud position" over the bytes before it -- and, when
+// the chunk has none, carry[c] samples before the chunk.  A thread's byte ends at most 4 runs; the exclusive sum of the qualifying ones
+// over the workgroup is the rank of its first.  EMIT = false stores the chunk's count; EMIT = true stores rows offset[c] + rank that
+// lie below max_runs, as plain stores.
+template <bool EMIT>
+__global__ __launch_bounds__(256) void detect_runs_kernel(const uint8_t* __restrict__ bitmap, const int32_t* __restrict__ lead,
+                                                          const int32_t* __restrict__ carry, int nchunks, int min_len, int32_t* __restrict__ count,
+                                                          const int32_t* __restrict__ offset, int32_t* __restrict__ runs, int max_runs) {
+    __shared__ uint8_t sb[256];
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const unsigned b = bitmap[(size_t)c * 256 + t];
+    sb[t] = (uint8_t)b;
+    __syncthreads();
+    const unsigned next = t < 255 ? sb[t + 1] & 1u : (c + 1 < nchunks && lead[c + 1] > 0) ? 1u : 0u;
+    const unsigned ends = b & ~((b | next << 8) >> 1) & 0xffu;
+    const unsigned loud = ~b & 0xffu;
+    int unused;
+    const int before = dt_block_excl(loud ? t * 8 + 31 - __builtin_clz(loud) : -1, -1, sw, unused, DtMax());
+    const int c0 = c * DT_CHUNK, cin = carry[c];
+    auto run_of = [&](int j, int& start) {                            // the run that ends at bit j of this thread's byte -> its length
+        const unsigned below = loud & ((1u << j) - 1u);
+        const int p = below ? t * 8 + 31 - __builtin_clz(below) : before;
+        start = p >= 0 ? c0 + p + 1 : c0 - cin;
+        return c0 + t * 8 + j - start + 1;
+    };
+    int m = 0;
+    for (unsigned e = ends; e; e &= e - 1) {
+        int start;
+        m += run_of(__builtin_ctz(e), start) >= min_len ? 1 : 0;
+    }
+    int total;
+    const int rank = dt_block_excl(m, 0, sw, total, DtAdd());
+    if (!EMIT) {
+        if (t == 0) count[c] = total;
+    } else {
+        int r = offset[c] + rank;
+        for (unsigned e = ends; e; e &= e - 1) {
+            int start;
+            const int l = run_of(__builtin_ctz(e), start);
+            if (l < min_len) continue;
+            if (r < max_runs) {
+                runs[2 * (size_t)r] = start;
+                runs[2 * (size_t)r + 1] = l;
+            }
+            ++r;
+        }
+    }
+}
+
+// One workgroup: offset[c] = the counts of the chunks before c, and their total into *n_runs.  At most 1024 runs end in a chunk, so the
+// total stays below 2^30 for every legal n.
+__global__ __launch_bounds__(256) void detect_offsets_kernel(const int32_t* __restrict__ count, int nchunks, int32_t* __restrict__ offset,
+                                                             int32_t* __restrict__ n_runs) {
+    __shared__ int sw[4];
+    const int t = threadIdx.x;
+    int v0 = 0;
+    for (int base = 0; base < nchunks; base += DT_TILE) {
+        int f[4], mine = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = base + t * 4 + k;
+            f[k] = c < nchunks ? count[c] : 0;
+            mine += f[k];
+        }
+        int total;
+        int v = v0 + dt_block_excl(mine, 0, sw, total, DtAdd());
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = base + t * 4 + k;
+            if (c < nchunks) offset[c] = v;
+            v += f[k];
+        }
+        v0 += total;
+    }
+    if (t == 0) *n_runs = v0;
+}
+
+// ------------------------------------------------------------------------------------------------ launcher
+size_t si_detect_scratch_bytes(int n) {
+    const size_t chunks = ((size_t)n + DT_CHUNK - 1) / DT_CHUNK;
+    return chunks * 256 + 5 * ((chunks * sizeof(int32_t) + 15) & ~(size_t)15);
+}
+
+// The caller (si_quiet_runs) checked every argument.  scratch: si_detect_scratch_bytes(n) bytes, 16-byte aligned.
+int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
+                         char* scratch, hipStream_t st) {
+    const int chunks = (int)(((long)n + DT_CHUNK - 1) / DT_CHUNK);
+    const size_t words = ((size_t)chunks * sizeof(int32_t) + 15) & ~(size_t)15;
+    uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch);
+    char* p = scratch + (size_t)chunks * 256;
+    int32_t* lead = reinterpret_cast<int32_t*>(p);
+    int32_t* trail = reinterpret_cast<int32_t*>(p + words);
+    int32_t* carry = reinterpret_cast<int32_t*>(p + 2 * words);
+    int32_t* count = reinterpret_cast<int32_t*>(p + 3 * words);
+    int32_t* offset = reinterpret_cast<int32_t*>(p + 4 * words);
+    const double bits = (double)chunks * 256.0, sums = (double)chunks * 4.0;
+
+    si_prof_begin(ctx, "detect_bits", 0.0, (double)n * (pcm16 ? 2.0 : 4.0) + bits + 2.0 * sums, st);
+    if (pcm16) detect_bits_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, thr, bitmap, lead, trail);
+    else detect_bits_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, thr, bitmap, lead, trail);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+
+    si_prof_begin(ctx, "detect_carry", 0.0, 3.0 * sums, st);
+    detect_carry_kernel<<<dim3(1), 256, 0, st>>>(lead, trail, chunks, n, carry);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+
+    si_prof_begin(ctx, "detect_count", 0.0, bits + 3.0 * sums, st);
+    detect_runs_kernel<false><<<dim3(chunks), 256, 0, st>>>(bitmap, lead, carry, chunks, min_len, count, nullptr, nullptr, 0);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+
+    si_prof_begin(ctx, "detect_offsets", 0.0, 2.0 * sums, st);
+    detect_offsets_kernel<<<dim3(1), 256, 0, st>>>(count, chunks, offset, n_runs);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+
+    if (max_runs > 0) {
+        si_prof_begin(ctx, "detect_emit", 0.0, bits + 3.0 * sums, st);
+        detect_runs_kernel<true><<<dim3(chunks), 256, 0, st>>>(bitmap, lead, carry, chunks, min_len, nullptr, offset, runs, max_runs);
+        si_prof_end(ctx, st);
+        SI_HIP_CHECK(hipGetLastError());
+    }
+    return SI_OK;
+}

@@ -615,6 +615,72 @@ class InpaintingEngine:
         out["label_off"] = off
         return out
 
+    # ---- dropout detection: where the gaps are, found on the device; then patch_recording as it is
+    def find_quiet_runs(self, x, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536) -> torch.Tensor:
+        """x (n,) fp32 or int16 (tensor or array, host or device; a device view may start anywhere) -> device int32 (R, 2): every
+        maximal run of samples with |x| <= threshold of at least min_len samples, as (start, len) rows sorted by start
+        (si_quiet_runs).  One D2H copy: the count.  A ValueError names both numbers when more than max_runs runs qualify."""
+        x = torch.as_tensor(x)
+        x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32).reshape(-1).contiguous()
+        runs, n_runs = self.ctx.quiet_runs(x, threshold, min_len, max_runs)
+        total = int(n_runs.item())
+        if total > int(max_runs):
+            raise ValueError(f"find_quiet_runs: {total} runs of at least {int(min_len)} quiet samples, more than max_runs = {int(max_runs)}")
+        return runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+
+    def recording_frames(self, n22: int, clip_frames: int = 200, n16: Optional[int] = None) -> Tuple[int, int]:
+        """(n_rec_frames, lim_frames) of a recording of n22 samples at 22.05 kHz as patch_recording serves it: its 20 ms frames and
+        the usable ones [0, lim) -- a context clip's min(T, Tm) (patch_recording's own arithmetic, n16 = the samples of a supplied
+        16 kHz recording), counted from frame n_rec - clip_frames, where the last context starts, when there is more than one clip."""
+        n22, clip_frames = int(n22), int(clip_frames)
+        n_rec = n22 // 441
+        whole = n_rec <= clip_frames
+        L22 = n22 if whole else clip_frames * 441
+        L16 = (int(n16) if whole else clip_frames * 320) if n16 is not None else -(-L22 * 16000 // 22050)
+        lim = min(self.ctx.num_frames(L16), self.ctx.mel_frames(L22)) if L16 > 0 and L22 > 0 else 0
+        return n_rec, max(lim, 0) + (0 if whole else n_rec - clip_frames)
+
+    def find_gaps(self, x, sr: int = 22050, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
+                  merge_frames: Optional[int] = None, fade: int = 110, n_rec_frames: Optional[int] = None,
+                  lim_frames: Optional[int] = None) -> Dict[str, object]:
+        """The dropouts of a recording x (n samples at `sr` Hz, fp32 in full-scale units or int16 PCM): runs of at least min_ms of
+        |x| <= threshold (find_quiet_runs), mapped by gaps.runs_to_gaps onto the 20 ms grid of the recording's n_rec_frames frames
+        (default n * 50 // sr) with the usable frames [0, lim_frames).  merge_frames None = 2 * the frames one cross-fade of `fade`
+        22.05 kHz samples reaches over; gaps of more than max_ms are skipped.
+        -> gaps ((first frame, frame count), sorted: what patch_recording takes), skipped ((first frame, frame count, reason)),
+        runs (device int32 (R, 2), samples at `sr`)."""
+        x = torch.as_tensor(x)
+        n, sr = x.numel(), int(sr)
+        if n < 1 or sr <= 0:
+            raise ValueError(f"find_gaps: {n} samples at {sr} Hz")
+        runs = self.find_quiet_runs(x, threshold, max(1, int(round(float(min_ms) * sr / 1000.0))))
+        n_rec = n * 50 // sr if n_rec_frames is None else int(n_rec_frames)
+        mf = 2 * max(-(-int(fade) // 441), 1) if merge_frames is None else int(merge_frames)
+        gaps, skipped = G.runs_to_gaps(runs.tolist(), n, sr, n_rec, lim_frames, pad_frames, mf, max(int(float(max_ms) // 20), 1))
+        return {"gaps": gaps, "skipped": skipped, "runs": runs}
+
+    def conceal_recording(self, wave22, wave16=None, detect_on=None, sr: int = 22050, threshold: float = 0.0, min_ms: float = 5.0,
+                          max_ms: float = 400.0, pad_frames: int = 0, merge_frames: Optional[int] = None, fade: int = 110,
+                          clip_frames: int = 200, min_context: int = 50, batch: int = 32, pcm: bool = False) -> Dict[str, object]:
+        """File in, repaired file out: find_gaps, then patch_recording unchanged with the gaps it found.  Detection runs on detect_on
+        when given -- the file's own samples at `sr` Hz, where a dropout is still exact zeros -- else on wave22 (sr is 22050 then).
+        The usable frames are patch_recording's own (its last context's min(T, Tm)), and a gap longer than the planner's budget
+        clip_frames - 2 * min_context counts as long whatever max_ms says.
+        -> patch_recording's dictionary + gaps + skipped.  With nothing found: an exact copy; only the detection kernels launched."""
+        as1d = lambda x: torch.as_tensor(x).to(self.device, torch.float32).reshape(-1).contiguous()
+        wave22 = as1d(wave22)
+        wave16 = None if wave16 is None else as1d(wave16)
+        clip_frames, min_context = int(clip_frames), int(min_context)
+        n_rec, lim = self.recording_frames(wave22.numel(), clip_frames, None if wave16 is None else wave16.numel())
+        if n_rec > clip_frames:
+            max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
+        found = self.find_gaps(wave22 if detect_on is None else detect_on, 22050 if detect_on is None else sr, threshold, min_ms, max_ms,
+                               pad_frames, merge_frames, fade, n_rec, lim)
+        out = self.patch_recording(wave22, found["gaps"], wave16=wave16, fade=fade, clip_frames=clip_frames, min_context=min_context,
+                                   batch=batch, pcm=pcm)
+        out["gaps"], out["skipped"] = found["gaps"], found["skipped"]
+        return out
+
     def predict_multigap_batch(self, wave16: torch.Tensor, mel_or_wave22: torch.Tensor, gaps, len16: Optional[Sequence[int]] = None,
                                len22: Optional[Sequence[int]] = None, mel_len: Optional[Sequence[int]] = None,
                                spans22: Optional[Sequence[Sequence[Sequence[int]]]] = None, tables: Optional[Dict[str, object]] = None,

@@ -307,3 +307,44 @@ def region_chunks(regions: Sequence[Gap], chunk: int = PC_CHUNK) -> List[Tuple[i
             else:
                 out.append((c, k, k + 1))
     return out
+
+
+# ---- dropout detection: runs of quiet samples at any file rate -> gaps on the recording's 20 ms grid
+def runs_to_gaps(runs: Sequence[Sequence[int]], n: int, sr: int, n_rec_frames: int, lim_frames: Optional[int] = None, pad_frames: int = 0,
+                 merge_frames: int = 2, max_frames: int = 20) -> Tuple[List[Gap], List[Tuple[int, int, str]]]:
+    """Runs of quiet samples, (start, len) pairs in samples of a recording of n samples at `sr` Hz (si_quiet_runs' rows), -> the gaps
+    to conceal, (first frame, frame count) pairs on the recording's 20 ms grid of n_rec_frames frames, sorted and disjoint: what
+    normalize_gaps and plan_contexts accept as they are.  Integer arithmetic only (sr = 11025 has 220.5 samples per frame).
+      cover   run [s, e) covers frames [s * 50 // sr - pad_frames, ceil(e * 50 / sr) + pad_frames), clamped to [0, n_rec_frames): every
+              frame the run touches.  At 22 050 Hz this inverts `spans22`: a zeroed [441 p, 441 (p + l)) gives (p, l) back.
+      edge    a run that touches sample 0 or sample n is leading or trailing padding, not a dropout, and a cover that does not fit the
+              usable frames [0, lim_frames) cannot be served (lim_frames None: [0, n_rec_frames - 1), the encoder's frame count):
+              skipped, reason "edge".
+      merge   covers that overlap, touch or lie fewer than merge_frames frames apart become one gap.
+      long    a merged gap of more than max_frames frames is skipped, reason "long".
+    -> (gaps, skipped); skipped = (first frame, frame count, reason) per skipped run or merged gap, in order."""
+    n, sr, n_rec, pad, mf, cap = int(n), int(sr), int(n_rec_frames), int(pad_frames), int(merge_frames), int(max_frames)
+    if n < 0 or sr <= 0 or n_rec < 0 or pad < 0 or mf < 0 or cap < 1:
+        raise ValueError(f"runs_to_gaps: n = {n}, sr = {sr}, n_rec_frames = {n_rec}, pad_frames = {pad}, merge_frames = {mf}, max_frames = {cap}")
+    lim = max(n_rec - 1, 0) if lim_frames is None else min(int(lim_frames), n_rec)
+    covers: List[Tuple[int, int]] = []
+    skipped: List[Tuple[int, int, str]] = []
+    for k, (s, l) in enumerate(sorted((int(s), int(l)) for s, l in runs)):
+        e = s + l
+        if l <= 0 or s < 0 or e > n:
+            raise ValueError(f"runs_to_gaps: run {k} = samples [{s}, {e}) is not a run of a recording of {n} samples")
+        a = min(max(s * 50 // sr - pad, 0), n_rec)
+        b = min(max(-(-e * 50 // sr) + pad, 0), n_rec)
+        if s == 0 or e == n or b > lim or b <= a:
+            skipped.append((a, max(b - a, 0), "edge"))
+        elif covers and a - covers[-1][1] < max(mf, 1):
+            covers[-1] = (covers[-1][0], max(covers[-1][1], b))
+        else:
+            covers.append((a, b))
+    gaps: List[Gap] = []
+    for a, b in covers:
+        if b - a > cap:
+            skipped.append((a, b - a, "long"))
+        else:
+            gaps.append((a, b - a))
+    return gaps, sorted(skipped)

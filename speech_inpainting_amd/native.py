@@ -30,7 +30,7 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_debug_capture", "si_debug_size",
            "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
            "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
-           "si_cut_clips", "si_patch_regions"]
+           "si_cut_clips", "si_patch_regions", "si_quiet_runs"]
 SI_MAX_SPANS = 16
 
 
@@ -324,6 +324,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_patch_compose.argtypes = [vp, vp, C.POINTER(SpanTableStruct), vp, C.POINTER(PatchTableStruct), vp, i32, vp, i32, i32, vp, vp, vp]
     lib.si_cut_clips.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
     lib.si_patch_regions.argtypes = [vp, vp, i32, C.POINTER(RegionTableStruct), vp, i32, vp, vp, vp, vp]
+    lib.si_quiet_runs.argtypes = [vp, vp, i32, i32, C.c_float, i32, vp, i32, vp, vp]
     lib.si_num_frames.argtypes = [vp, i32]
     lib.si_vocoder_samples.argtypes = [vp, i32, i32]
     lib.si_debug_capture.argtypes = [vp, C.c_char_p, vp, C.c_long]
@@ -623,6 +624,24 @@ class NativeContext:
         t = table.struct()
         self._check(self.lib.si_patch_regions(self._h, _ptr(orig), min(N, 2 ** 31 - 1), C.byref(t), _ptr(gen), 0 if gen is None else gen.shape[1], _ptr(gain), _ptr(out),
                                               _ptr(out_pcm), self._stream()), "si_patch_regions")
+
+    # ---- dropout detection
+    def quiet_runs(self, x: torch.Tensor, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536, runs: Optional[torch.Tensor] = None,
+                   n_runs: Optional[torch.Tensor] = None):
+        """x (n,) fp32 or int16 on the device (a view may start anywhere) -> (runs (max_runs, 2) int32, n_runs (1,) int32), both on
+        the device: the maximal runs of |x| <= threshold of at least min_len samples as (start, len) rows sorted by start, and how
+        many there are in all (si_quiet_runs).  Rows at and past min(n_runs, max_runs) are not written; max_runs = 0 counts only."""
+        assert x.is_cuda and x.dtype in (torch.float32, torch.int16) and x.dim() == 1 and x.is_contiguous()
+        max_runs = int(max_runs)
+        if runs is None and max_runs > 0:
+            runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
+        if n_runs is None:
+            n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
+        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
+        assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
+        self._check(self.lib.si_quiet_runs(self._h, _ptr(x), int(x.dtype == torch.int16), min(x.numel(), 2 ** 31 - 1), float(threshold), int(min_len),
+                                           _ptr(runs), max_runs, _ptr(n_runs), self._stream()), "si_quiet_runs")
+        return runs, n_runs
 
     @staticmethod
     def _feats_mel(feats: torch.Tensor, mel: torch.Tensor):

@@ -13,7 +13,10 @@ With an optional `long:` mapping ({clip_s: 4.0, context_s: 1.0, batch: 32}) the 
 `mask:` / `masks:` are read on the file's own time axis, the recording is served as context clips (engine.patch_recording, DESIGN.md
 4.14; the cross-fade comes from `patch:`, 5 ms without it) and `orig.wav`, `masked.wav` and `patched.wav` are written at 22.05 kHz,
 all with the recording's own sample count.  The whole-clip diagnostics (`hifi_masked.wav`, `inpainted.wav`, `expected_inpaint.wav`)
-are NOT produced on this route: no generator pass over a whole recording exists there.
+are NOT produced on this route: no generator pass over a whole recording exists there.  With a `detect:` mapping ({threshold: 0.0,
+min_ms: 5.0, max_ms: 400.0, pad_frames: 0}) beside `long:` and instead of `mask:` / `masks:` the gaps are FOUND: the runs of
+|x| <= threshold of at least min_ms in the file's own samples (engine.find_gaps); each gap and each skipped run is
+printed and `gaps.json` is written beside the three waves.
 
 Differences from the script, all outside the three replaced subsystems: no Whisper `Metrics` object is built (the
 script constructs it and never uses it, I_ea/predict.py:72-73), PNG plots are skipped, and the two `librosa.load` calls are one
@@ -22,6 +25,7 @@ reference-held LJ001-0001 22k / 16k pair), the clips staying on the device from 
 """
 from __future__ import annotations
 
+import json
 import os
 import sys
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -327,19 +331,45 @@ def predict_ragged(engine: InpaintingEngine, waves16: Sequence[np.ndarray], wave
     return results  # type: ignore[return-value]
 
 
+def _detect_gaps(cfg: PredictConfig, engine: InpaintingEngine, raw: np.ndarray, sr_file: int, n22: int, fade: int, clip_frames: int,
+                 min_context: int, save_dir: str) -> List[Tuple[int, int]]:
+    """The `detect:` key of the `long:` route: the gaps found in the file's OWN samples at the file's rate, where a dropout is still
+    exact zeros (the resampler's ringing fills it in at 22.05 kHz).  A mono int16 file is scanned as the int16 it holds, the threshold
+    scaled by 32768 (an exact scaling: the same samples are quiet).  Prints every gap and every skipped run, writes gaps.json."""
+    from scipy.io import wavfile
+    d = cfg.detect
+    x, thr = raw, d["threshold"]
+    pcm_file = wavfile.read(cfg.wave_path)[1]
+    if pcm_file.dtype == np.int16 and pcm_file.ndim == 1:
+        x, thr = pcm_file, d["threshold"] * 32768.0
+    n_rec, lim = engine.recording_frames(n22, clip_frames)
+    max_ms = d["max_ms"] if n_rec <= clip_frames else min(d["max_ms"], 20.0 * (clip_frames - 2 * min_context))
+    found = engine.find_gaps(x, sr_file, thr, d["min_ms"], max_ms, d["pad_frames"], None, fade, n_rec, lim)
+    for k, (pos, lm) in enumerate(found["gaps"]):
+        print(f"Detected gap {k} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s")
+    for pos, lm, why in found["skipped"]:
+        print(f"Skipped quiet run = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s: {why}")
+    with open(os.path.join(save_dir, "gaps.json"), "w") as f:
+        json.dump({"gaps": [list(g) for g in found["gaps"]], "skipped": [list(g) for g in found["skipped"]]}, f)
+    return found["gaps"]
+
+
 def _main_long(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> int:
     """The `long:` route of `main`: the file as a recording of any length, its gaps on its own time axis."""
     raw, sr_file = audio.read_wav(cfg.wave_path)
     wave_22 = engine.resample(torch.from_numpy(raw)[None].to(engine.device), sr_file, 22050)[0].contiguous()
-    gap_list = sorted(cfg.gaps) if cfg.gaps is not None else [(cfg.mask_pos, cfg.mask_frames)]
+    fade = cfg.patch_fade if cfg.patch_fade is not None else 110
+    clip_frames, min_context = int(round(cfg.long["clip_s"] * 50)), int(round(cfg.long["context_s"] * 50))
+    if cfg.detect is not None:                                                     # optional `detect:` mapping: the gaps are found
+        gap_list = _detect_gaps(cfg, engine, raw, sr_file, wave_22.numel(), fade, clip_frames, min_context, save_dir)
+    else:
+        gap_list = sorted(cfg.gaps) if cfg.gaps is not None else [(cfg.mask_pos, cfg.mask_frames)]
     audio.write_wav(os.path.join(save_dir, "orig.wav"), engine.to_int16(wave_22).cpu().numpy(), 22050)
     masked = wave_22.clone()
     for pos, lm in gap_list:
         masked[pos * 441:(pos + lm) * 441] = 0                                     # gaps.spans22: frame p = samples [441 p, 441 (p + 1))
     audio.write_wav(os.path.join(save_dir, "masked.wav"), engine.to_int16(masked).cpu().numpy(), 22050)
-    out = engine.patch_recording(wave_22, gap_list, fade=cfg.patch_fade if cfg.patch_fade is not None else 110,
-                                 clip_frames=int(round(cfg.long["clip_s"] * 50)), min_context=int(round(cfg.long["context_s"] * 50)),
-                                 batch=cfg.long["batch"], pcm=True)
+    out = engine.patch_recording(wave_22, gap_list, fade=fade, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"], pcm=True)
     labels, off = out["labels"].tolist(), out["label_off"]
     for k, (pos, lm) in enumerate(gap_list):
         print(f"Predicted codewords, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[k]:off[k + 1]])

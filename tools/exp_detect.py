@@ -1,0 +1,95 @@
+"""Experiment: what finding the dropouts costs.  The 10-minute synthetic recording of tools/exp_long.py with its 60
+gaps of 200 ms zeroed, HuBERT-base bf16 + HiFi-GAN V1 fp16 stream, in ONE process, the variants alternated inside each repeat after
+warm-up, device-synchronised wall clock per call:
+
+  (a) si_quiet_runs (five launches) + the one D2H copy of the count: engine.find_quiet_runs
+  (b) the torch formulation on the same device: q = x.abs() <= thr, diff of the zero-padded mask, nonzero of the rises and of the
+      falls, the length filter, stack -- the baseline a caller would write
+  (c) engine.conceal_recording(pcm=True): find the gaps, then patch_recording
+  (d) engine.patch_recording(pcm=True) with the known gaps
+
+Prints whether (a) equals (b) and (c) equals (d) bit for bit, one line per repeat, the medians, and -- from a separate, untimed run
+under the library's profiler -- the per-kernel times of the detect_* family and the effective bytes per second of the whole call
+(the recording's bytes / the family's summed time).
+usage: python tools/exp_detect.py [--repeats 7] [--minutes 10] [--gaps 60] [--pcm16]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--repeats", type=int, default=7)
+ap.add_argument("--minutes", type=float, default=10.0)
+ap.add_argument("--gaps", type=int, default=60)
+ap.add_argument("--fade", type=int, default=110)
+ap.add_argument("--batch", type=int, default=32)
+ap.add_argument("--pcm16", action="store_true", help="time (a) and (b) on the int16 PCM of the recording instead of its fp32 samples")
+a = ap.parse_args()
+WARMUP = 2
+CLIP, CTX, LM, MIN_LEN = 200, 50, 10, 110
+
+import torch
+
+from speech_inpainting_amd import synth
+from speech_inpainting_amd.arch import HubertArch, VocoderArch
+from speech_inpainting_amd.engine import InpaintingEngine
+
+dev = torch.device("cuda:0")
+harch, varch = HubertArch.base(), VocoderArch.v1()
+eng = InpaintingEngine(harch, varch, 100, dev, "bf16", "fp16").load_state(
+    synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(100))
+N22 = int(a.minutes * 60 * 22050) + 123
+n_rec = N22 // 441
+tile = synth.synth_wave(1, 30 * 22050, synth.DEFAULT_SEED + 6, sr=22050)[0]
+wave22 = tile.repeat(-(-N22 // tile.numel()))[:N22].contiguous().to(dev)
+every = n_rec // a.gaps
+gaps = [(k * every + every // 2, LM) for k in range(a.gaps)]
+for p, l in gaps:
+    wave22[441 * p:441 * (p + l)] = 0
+x = eng.to_int16(wave22) if a.pcm16 else wave22
+KW = dict(fade=a.fade, clip_frames=CLIP, min_context=CTX, batch=a.batch, pcm=True)
+
+
+def torch_runs():
+    q = (x.abs() <= 0).to(torch.int8) if not a.pcm16 else (x.to(torch.int32).abs() <= 0).to(torch.int8)
+    d = torch.diff(q, prepend=q.new_zeros(1), append=q.new_zeros(1))
+    start, end = torch.nonzero(d == 1).flatten(), torch.nonzero(d == -1).flatten()
+    keep = end - start >= MIN_LEN
+    return torch.stack([start[keep], (end - start)[keep]], dim=1).to(torch.int32)
+
+
+variants = {"a": lambda: eng.find_quiet_runs(x, 0.0, MIN_LEN), "b": torch_runs,
+            "c": lambda: eng.conceal_recording(wave22, **KW), "d": lambda: eng.patch_recording(wave22, gaps, **KW)}
+oa, ob, oc, od = (fn() for fn in variants.values())
+torch.cuda.synchronize()
+print(f"recording of {N22} samples ({N22 / 22050 / 60:.2f} min, {x.element_size()} bytes per sample), {len(gaps)} gaps of {LM} frames zeroed")
+print(f"(a) equals (b): {torch.equal(oa, ob)} ({oa.shape[0]} runs);  (c) found the gaps: {oc['gaps'] == gaps};  (c) equals (d) bit for bit: fp32",
+      torch.equal(oc["patched"].view(torch.int32), od["patched"].view(torch.int32)), " int16", torch.equal(oc["patched_pcm"], od["patched_pcm"]))
+del oa, ob, oc, od
+for fn in variants.values():
+    for _ in range(WARMUP):
+        fn()
+torch.cuda.synchronize()
+ms = {k: [] for k in variants}
+for r in range(a.repeats):
+    for k, fn in variants.items():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms[k].append((time.perf_counter() - t0) * 1e3)
+    print(f"repeat {r}: " + "  ".join(f"({k}) {ms[k][-1]:.3f} ms" for k in variants), flush=True)
+med = {k: statistics.median(v) for k, v in ms.items()}
+print("median ms/recording: " + "  ".join(f"({k}) {med[k]:.3f}" for k in variants))
+print(f"spread of (d) over {a.repeats} repeats: {max(ms['d']) - min(ms['d']):.3f} ms;  (c) - (d) {med['c'] - med['d']:+.3f} ms;  (a) / (b) {med['a'] / med['b']:.3f}")
+# per-kernel device times, from a run of their own under the library's event profiler (every launch bracketed: not a step time)
+eng.ctx.profile_start(1000)
+for _ in range(10):
+    eng.find_quiet_runs(x, 0.0, MIN_LEN)
+rows = {e["name"]: e for e in eng.ctx.profile_stop() if e["name"].startswith("detect_")}
+total = sum(e["ms"] for e in rows.values()) / 10
+print(f"si_quiet_runs under the profiler: {total * 1e3:.1f} us per call = {x.numel() * x.element_size() / (total * 1e-3) / 1e9:.1f} GB/s of the recording;  "
+      + "  ".join(f"{n} {e['ms'] / e['launches'] * 1e3:.1f} us" for n, e in rows.items()))
