@@ -31,6 +31,8 @@
  *                                                                             I_ea/predict.py:79-80,104,203-207
  *   si_quiet_runs        <- nothing the reference computes: it has no detection.  The call supplies the `mask:` values
  *                           (start_pos_in_sec, end_pos_in_sec) that a user of the script types by hand      I_ea/predict.py:85-90
+ *   si_patch_rate        <- the same write-out for a file at ANY sample rate, which the script resamples on the way in and never
+ *                           brings back                                       I_ea/predict.py:79-80,203-207
  *   si_load_weights      <- model.load_state_dict / generator.load_state_dict + remove_weight_norm + ApplyKmeans
  *                           I_ea/predict.py:117-122,149 ; I_ea/hifi_gan/models.py:125-132 ; I_ea/dataset/km_label.py:12-24
  *
@@ -562,6 +564,75 @@ int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_ta
  * threshold negative or NaN; min_len < 1; max_runs < 0. */
 int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs,
                   int32_t* n_runs, si_stream_t stream);
+
+/* ---- Repair at the file's own sample rate -----------------------------------------------------------------------------
+ * The reference's script resamples its input to 22.05 kHz and writes 22.05 kHz (I_ea/predict.py:79-80,203-207); si_patch_regions keeps
+ * the recording's own samples only when the file already is at that rate.  The call below replaces, for a file at ANY rate sr, the
+ * `engine.resample(patched, 22050, sr)` over the whole repaired recording that would otherwise bring it back (si_resample_sinc, row f-3)
+ * together with si_patch_regions' write-out: the recording stays at sr in its own sample type, and only the generated audio around each
+ * gap is carried from 22.05 kHz to sr -- by si_resample_sinc's band-limited interpolation at the EXACT rational time -- and blended in.
+ *
+ * si_rate_table: si_region_table with the spans on the FILE's sample axis.  With g = gcd(22050, sr), P = 22050 / g, Q = sr / g, file
+ * sample i sits at position i P / Q of the 22.05 kHz axis.  Span k < num_spans is FILE samples [start[k], start[k] + len[k]) (len > 0;
+ * sorted, disjoint); nothing at or past file sample span_lim[k] is written; its generated samples lie in row span_win[k] of `gen`.
+ * Window w < num_windows is one row of `gen` and stays on the 22.05 kHz axis: context win_ctx[w] (the index into `gain`), first sample =
+ * 22.05 kHz sample win_start[w] of the recording, win_len[w] samples, and win_lim[w] = the 22.05 kHz sample where its context's
+ * generated audio ends.  Chunks are chunks of 2048 FILE samples, listed as in si_region_table (gaps.region_chunks); fade and ramp are in
+ * file samples.  host_* (HOST) are validated, the DEVICE copies are read: the si_span_table rule. */
+typedef struct si_rate_table {
+    int32_t struct_size;            /* = sizeof(si_rate_table) */
+    int32_t num_contexts;           /* C: entries of gain */
+    int32_t num_windows;            /* W: rows of gen */
+    int32_t num_spans;              /* K */
+    int32_t num_chunks;             /* Q: workgroups of the launch */
+    int32_t fade;                   /* cross-fade length in FILE samples, >= 0 (0 = hard splice) */
+    const int32_t* host_start;      /* HOST (num_spans), file samples */
+    const int32_t* host_len;        /* HOST (num_spans), file samples */
+    const int32_t* host_span_win;   /* HOST (num_spans) */
+    const int32_t* host_span_lim;   /* HOST (num_spans), file samples */
+    const int32_t* host_win_ctx;    /* HOST (num_windows) */
+    const int32_t* host_win_start;  /* HOST (num_windows), 22.05 kHz samples */
+    const int32_t* host_win_len;    /* HOST (num_windows), 22.05 kHz samples */
+    const int32_t* host_win_lim;    /* HOST (num_windows), 22.05 kHz samples */
+    const int32_t* host_chunk;      /* HOST (num_chunks) */
+    const int32_t* host_k0;         /* HOST (num_chunks) */
+    const int32_t* host_k1;         /* HOST (num_chunks) */
+    const int32_t* start;           /* DEVICE copies of the eleven */
+    const int32_t* len;
+    const int32_t* span_win;
+    const int32_t* span_lim;
+    const int32_t* win_ctx;
+    const int32_t* win_start;
+    const int32_t* win_len;
+    const int32_t* win_lim;
+    const int32_t* chunk;
+    const int32_t* k0;
+    const int32_t* k1;
+    const float* ramp;              /* DEVICE (fade), may be NULL when fade = 0 */
+} si_rate_table;
+
+/* Per file sample i of a listed chunk the weight w is si_patch_regions' on the file axis: the MAXIMUM over the chunk's spans of
+ * ramp[i - (s - fade)] on the rise, 1 in [s, s + len), ramp[s + len + fade - 1 - i] on the fall, 0 at and past span_lim; the first span
+ * of the greatest weight supplies the window.  A sample of weight 0 is NOT WRITTEN: `out` keeps the caller's copy of the recording.
+ * The generated sample at file sample i: n, r = divmod(i P, Q) in 64-bit integers, frac = scale (r / Q), and with the tables of
+ * `filt` (audio.design_kaiser_best(22050, sr, .): win, dwin, nwin, num_table, step, scale; time_reg, n_time and ratio are NOT read)
+ *     left wing   off, eta = split(frac num_table):            taps k < min(n + 1, (nwin - off) / step) weigh x[n - k]
+ *     right wing  off', eta' = split((scale - frac) num_table): taps k < (nwin - off') / step            weigh x[n + 1 + k]
+ * by fma(eta, dwin[off + k step], win[off + k step]), accumulated by fma in float64 in that order (left ascending, then right ascending)
+ * and rounded once to fp32 -- si_resample_sinc's arithmetic at the exact time, so a sample has the same bits wherever its window row
+ * starts and however the chunks are listed.  x[j] is 22.05 kHz sample j of the recording's generated audio, read from the window's row;
+ * j < 0 and j >= win_lim read as zero.  Then g = gain[win_ctx] * y and the sample is g (w = 1) or fma(w, g, (1 - w) * orig[i]):
+ * si_patch_regions' roundings in its order.  orig / out: device, n_file samples of the SAME type, fp32 (is_pcm16 = 0) or int16 PCM
+ * (is_pcm16 != 0: orig = (float)v / 32768, the result stored by si_pcm16's arithmetic); a base needs only its element's alignment;
+ * orig is read only and must not be out.  gen device fp32 (num_windows, Lrow); gain device fp32 (num_contexts) or NULL (= 1).
+ * SI_EINVAL before any launch, naming the entry, for: everything si_patch_regions refuses, on the file axis; sr outside 4000 .. 192000
+ * or equal to 22050; n_file, or its 22.05 kHz length ceil(n_file P / Q), above 2^31 - 1 - 2048; a filter with nwin < 2, num_table < 1,
+ * step < 1, scale outside (0, 1] or NULL tables; a window outside that 22.05 kHz length or with win_lim outside (win_start, length];
+ * a span whose span_lim reaches a sample at or past its window's win_lim; a span whose region [max(s - fade, 0), min(s + len + fade,
+ * span_lim)), mapped to 22.05 kHz samples [floor(a P / Q) - H, floor((b - 1) P / Q) + 1 + H) with H = ceil(nwin / step), leaves its
+ * window's row other than before sample 0 or at or past win_lim.  num_chunks = 0 launches nothing and succeeds. */
+int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int sr, const si_rate_table* table, const float* gen, int Lrow,
+                  const float* gain, const si_sinc_filter* filt, void* out, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

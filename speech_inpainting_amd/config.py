@@ -58,6 +58,8 @@ class PredictConfig:
                                             # only the gaps filled); None without the key
     long: Optional[dict] = None   # optional `long:` mapping ({clip_s: 4.0, context_s: 1.0, batch: 32}): the file is a recording of any
                                   # length, served as context clips (engine.patch_recording); None without the key
+    long_rate: object = 22050     # `rate:` inside `long:`: 22050 (default: patched.wav is the recording resampled to 22.05 kHz) or "file"
+                                  # (patched.wav keeps the file's own rate and sample type: engine.patch_file)
     detect: Optional[dict] = None  # optional `detect:` mapping ({threshold: 0.0, min_ms: 5.0, max_ms: 400.0, pad_frames: 0}): the gaps are
                                    # found in the file itself (engine.find_gaps) instead of given as `mask:` / `masks:`; needs `long:`
 
@@ -128,15 +130,20 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             patch_fade_ms = float(pm.get("fade_ms", 5))
             if patch_fade_ms < 0:
                 raise ValueError(f"{path}: patch.fade_ms = {patch_fade_ms} is negative")
-        long_cfg = None
+        long_cfg, long_rate = None, 22050
         if "long" in data:
             lm = data["long"] if data["long"] is not None else {}
             if not isinstance(lm, dict):
                 raise ValueError(f"{path}: `long:` must be a mapping (clip_s: <seconds>, context_s: <seconds>, batch: <contexts per pass>)")
             long_cfg = {"clip_s": 4.0, "context_s": 1.0, "batch": 32}
+            lm = dict(lm)
+            if "rate" in lm:
+                long_rate = lm.pop("rate")
+                if long_rate not in (22050, "file"):
+                    raise ValueError(f"{path}: long.rate = {long_rate!r}: 22050 (the default) or file (the file's own rate and sample type)")
             for key, val in lm.items():
                 if key not in long_cfg:
-                    raise ValueError(f"{path}: unknown key `{key}` in `long:` (it takes clip_s, context_s, batch)")
+                    raise ValueError(f"{path}: unknown key `{key}` in `long:` (it takes clip_s, context_s, batch, rate)")
                 long_cfg[key] = int(val) if key == "batch" else float(val)
                 if long_cfg[key] < 0:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
@@ -174,7 +181,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_type=str(data["hubert_model"]["type"]),
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
-            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, detect=detect_cfg)
+            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, detect=detect_cfg)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

@@ -2094,6 +2094,97 @@ int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_ta
     return si_launch_patch_regions(ctx, orig, rt, Q, gen, Lrow, gain, N22, out_f32, out_pcm, static_cast<hipStream_t>(stream));
 }
 
+// ---- repair at the file's own sample rate
+int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int sr, const si_rate_table* table, const float* gen, int Lrow,
+                  const float* gain, const si_sinc_filter* filt, void* out, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!orig || !out || n_file <= 0) return si_fail(ctx, SI_EINVAL, "si_patch_rate: NULL / empty argument");
+    if (orig == out) return si_fail(ctx, SI_EINVAL, "si_patch_rate: out is orig (orig is read while out is written)");
+    if (sr < 4000 || sr > 192000) return si_fail(ctx, SI_EINVAL, "si_patch_rate: sr = %d Hz, outside 4000 .. 192000", sr);
+    if (sr == 22050) return si_fail(ctx, SI_EINVAL, "si_patch_rate: sr = 22050 Hz is the generator's own rate: that file is si_patch_regions'");
+    if ((long)n_file > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_patch_rate: a file of %d samples, at most %ld", n_file, SI_MAX_REC);
+    long ga = 22050, gb = sr;
+    while (gb) { const long r = ga % gb; ga = gb; gb = r; }
+    const long P = 22050 / ga, Qr = sr / ga;
+    const long N22 = ((long)n_file * P + Qr - 1) / Qr;              // the recording's samples on the 22.05 kHz axis, ceil(n_file P / Q)
+    if (N22 > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_patch_rate: %d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
+    const si_sinc_filter* f = filt;
+    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return si_fail(ctx, SI_EINVAL, "si_patch_rate: si_sinc_filter size mismatch");
+    if (!f->win || !f->dwin || f->nwin < 2 || f->num_table < 1 || f->step < 1 || !(f->scale > 0.0 && f->scale <= 1.0))
+        return si_fail(ctx, SI_EINVAL, "si_patch_rate: bad filter table (nwin %d, num_table %d, step %d, scale %g)", f->nwin, f->num_table, f->step, f->scale);
+    const long H = ((long)f->nwin + f->step - 1) / f->step;
+    const long row_cap = 2047 * P / Qr + 2 + 2 * H;
+    if (row_cap * (long)sizeof(float) > 65536)
+        return si_fail(ctx, SI_EINVAL, "si_patch_rate: bad filter table: %ld taps per wing at %d Hz need %ld staged samples per chunk, at most 16384", H, sr, row_cap);
+    const si_rate_table* t = table;
+    if (!t || t->struct_size != (int32_t)sizeof(si_rate_table)) return si_fail(ctx, SI_EINVAL, "si_patch_rate: si_rate_table size mismatch");
+    if (t->fade < 0 || (long)t->fade + n_file > 0x7fffffffL) return si_fail(ctx, SI_EINVAL, "si_patch_rate: fade of %d samples is negative or too long", t->fade);
+    const int C = t->num_contexts, W = t->num_windows, K = t->num_spans, Q = t->num_chunks, fade = t->fade;
+    if (C < 0 || W < 0 || K < 0 || Q < 0)
+        return si_fail(ctx, SI_EINVAL, "si_patch_rate: rate table with %d contexts / %d windows / %d spans / %d chunks", C, W, K, Q);
+    if (fade > 0 && K > 0 && !t->ramp) return si_fail(ctx, SI_EINVAL, "si_patch_rate: rate table with NULL ramp");
+    if (W > 0 && (!t->host_win_ctx || !t->host_win_start || !t->host_win_len || !t->host_win_lim || !t->win_ctx || !t->win_start || !t->win_len ||
+                  !t->win_lim || !gen || Lrow <= 0))
+        return si_fail(ctx, SI_EINVAL, "si_patch_rate: %d windows but NULL window arrays / generator rows", W);
+    if (K > 0 && (!t->host_start || !t->host_len || !t->host_span_win || !t->host_span_lim || !t->start || !t->len || !t->span_win || !t->span_lim))
+        return si_fail(ctx, SI_EINVAL, "si_patch_rate: %d spans but NULL span arrays", K);
+    if (Q > 0 && (!t->host_chunk || !t->host_k0 || !t->host_k1 || !t->chunk || !t->k0 || !t->k1))
+        return si_fail(ctx, SI_EINVAL, "si_patch_rate: %d chunks but NULL chunk arrays", Q);
+    for (int w = 0; w < W; ++w) {
+        const long c = t->host_win_ctx[w], s = t->host_win_start[w], l = t->host_win_len[w], lim = t->host_win_lim[w];
+        if (c < 0 || c >= C) return si_fail(ctx, SI_EINVAL, "si_patch_rate: window %d names context %ld of %d", w, c, C);
+        if (s < 0 || l < 0 || l > Lrow || s + l > N22)
+            return si_fail(ctx, SI_EINVAL, "si_patch_rate: window %d = 22.05 kHz samples [%ld, +%ld) is outside the recording (%ld samples, rows of %d)", w, s, l,
+                           N22, Lrow);
+        if (lim <= s || lim > N22)
+            return si_fail(ctx, SI_EINVAL, "si_patch_rate: window %d starts at 22.05 kHz sample %ld, its context's audio ends at %ld of %ld", w, s, lim, N22);
+    }
+    for (int q = 0; q < Q; ++q) {
+        const long c = t->host_chunk[q];
+        if (c < 0 || c * 2048 >= n_file) return si_fail(ctx, SI_EINVAL, "si_patch_rate: chunk entry %d names chunk %ld, at or past the file's %d samples", q, c, n_file);
+        if (q && c <= t->host_chunk[q - 1])
+            return si_fail(ctx, SI_EINVAL, "si_patch_rate: chunk entry %d names chunk %ld after chunk %d: not strictly increasing", q, c, t->host_chunk[q - 1]);
+        if (t->host_k0[q] < 0 || t->host_k0[q] > t->host_k1[q] || t->host_k1[q] > K)
+            return si_fail(ctx, SI_EINVAL, "si_patch_rate: chunk entry %d walks spans [%d, %d) of %d", q, t->host_k0[q], t->host_k1[q], K);
+    }
+    for (int k = 0; k < K; ++k) {
+        const long s = t->host_start[k], l = t->host_len[k], lim = t->host_span_lim[k];
+        if (s < 0 || l <= 0 || lim <= s || lim > n_file)
+            return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d = samples [%ld, +%ld) with lim %ld does not lie in the file's %d samples", k, s, l, lim, n_file);
+        if (k && s < (long)t->host_start[k - 1] + t->host_len[k - 1])
+            return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d starts at %ld, before span %d ends: unsorted or overlapping", k, s, k - 1);
+    }
+    int q = 0;                                                     // the spans are sorted: the chunk list is walked (nearly) once
+    for (int k = 0; k < K; ++k) {
+        const long s = t->host_start[k], l = t->host_len[k], lim = t->host_span_lim[k];
+        const int w = t->host_span_win[k];
+        if (w < 0 || w >= W) return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d names window %d of %d", k, w, W);
+        const long ws = t->host_win_start[w], we = ws + t->host_win_len[w], wlim = t->host_win_lim[w];
+        if ((lim - 1) * P >= wlim * Qr)
+            return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d writes up to file sample %ld = 22.05 kHz sample %ld, its context's audio ends at %ld", k, lim,
+                           (lim - 1) * P / Qr, wlim);
+        const long ra = std::max(s - fade, 0L), rb = std::min(s + l + fade, lim);
+        const long xa = std::max(ra * P / Qr - H, 0L), xb = std::min((rb - 1) * P / Qr + 1 + H, wlim);      // what the taps read inside [0, win_lim)
+        if (xa < ws || xb > we)
+            return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d blends file samples [%ld, %ld) and reads 22.05 kHz samples [%ld, %ld), its window's row holds [%ld, %ld)",
+                           k, ra, rb, xa, xb, ws, we);
+        const long qa = ra / 2048, qb = (rb - 1) / 2048;
+        while (q > 0 && t->host_chunk[q - 1] >= qa) --q;            // a region may start in the chunk its predecessor ended in
+        for (long c = qa; c <= qb; ++c) {
+            while (q < Q && t->host_chunk[q] < c) ++q;
+            if (q >= Q || t->host_chunk[q] != c)
+                return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d blends samples [%ld, %ld), the chunk list lacks chunk %ld", k, ra, rb, c);
+            if (k < t->host_k0[q] || k >= t->host_k1[q])
+                return si_fail(ctx, SI_EINVAL, "si_patch_rate: chunk entry %d (chunk %ld) walks spans [%d, %d) and omits span %d, which blends samples [%ld, %ld)",
+                               q, c, t->host_k0[q], t->host_k1[q], k, ra, rb);
+        }
+    }
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    const SiRate rt{t->start, t->len, t->span_win, t->span_lim, t->win_ctx, t->win_start, t->win_len, t->win_lim, t->chunk, t->k0, t->k1, t->ramp, fade,
+                    f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Qr, (int)H, (int)row_cap};
+    return si_launch_patch_rate(ctx, orig, is_pcm16 != 0, n_file, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
+}
+
 // ---- dropout detection
 int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
                   si_stream_t stream) {

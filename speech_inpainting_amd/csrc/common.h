@@ -355,6 +355,25 @@ size_t si_detect_scratch_bytes(int n);
 int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
                          char* scratch, hipStream_t st);
 
+// ------------------------------------------------------------------------------------------------
+// repair at the file's own sample rate (rate_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// si_rate_table's device arrays (spans, span_lim, chunks, fade and ramp in FILE samples; windows in 22.05 kHz samples), the kaiser_best
+// tables of 22 050 -> sr, P / Q = (22050, sr) / gcd, H = ceil(nwin / step) taps per wing, and row_cap = floor(2047 P / Q) + 2 + 2 H:
+// the 22.05 kHz samples one chunk's share of one span can read, the floats of dynamic LDS the launch asks for.
+struct SiRate {
+    const int32_t* start; const int32_t* len; const int32_t* span_win; const int32_t* span_lim;
+    const int32_t* win_ctx; const int32_t* win_start; const int32_t* win_len; const int32_t* win_lim;
+    const int32_t* chunk; const int32_t* k0; const int32_t* k1;
+    const float* ramp; int fade;
+    const double* win; const double* dwin; int nwin, num_table, step; double scale;
+    int P, Q, H, row_cap;
+};
+// one workgroup per listed chunk of 2048 file samples: the blended samples of its spans written into out (n_file, orig's type: fp32 or
+// int16 when pcm16), the rest untouched; arguments validated by the caller
+int si_launch_patch_rate(si_ctx* ctx, const void* orig, bool pcm16, int n_file, const SiRate& rt, int num_chunks, const float* gen, int Lrow,
+                         const float* gain, void* out, hipStream_t st);
+
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16
 // rounding every consumer of these outputs applies; 15 VALU operations instead of libm erff's ~31 with two divergent branches.

@@ -19,7 +19,7 @@ import torch
 from .arch import HubertArch, VocoderArch
 from .checkpoint import flatten_checkpoint
 from . import gaps as G
-from .native import NativeContext, PatchTable, RegionTable, SpanTable, make_desc
+from .native import NativeContext, PatchTable, RateTable, RegionTable, SpanTable, make_desc
 
 
 def mask_samples_from_frames(frame_pos: int, frame_len: int):
@@ -431,11 +431,12 @@ class InpaintingEngine:
         return tb
 
     # ---- patch mode: the generated audio of the gaps spliced into the caller's own 22.05 kHz samples
-    def plan_patch(self, spans22: Sequence[Sequence[Sequence[int]]], n22: Sequence[int], fade: int) -> Dict[str, object]:
+    def plan_patch(self, spans22: Sequence[Sequence[Sequence[int]]], n22: Sequence[int], fade: int, regions=None) -> Dict[str, object]:
         """Host planning of one patched batch: per clip the blend regions of its 22.05 kHz spans (start, len) and the generator
         windows that hold them (gaps.blend_regions / gaps.plan_patch_windows with this generator's hop and receptive radius).
         -> fade, hop, wins = (clip, w0, w1) of all windows, windows (per clip), span_win (flat, the span table's order), lim and
-        n22 (per clip)."""
+        n22 (per clip).  regions (per clip, per span a [a, b) sample range or None): the samples each span's window must KEEP, in
+        place of its blend region -- patch_file's regions widened by the interpolation's reach (gaps.reach_regions22)."""
         hop = self.ctx.vocoder_samples(1, False)
         if hop != 256:
             # extend_mel centres stretched frame t at input sample (t + 0.5) * 256: generator sample n is input sample n only at hop 256
@@ -444,7 +445,7 @@ class InpaintingEngine:
         wins, span_win, lim, per_clip = [], [], [], []
         for b, (spans, n) in enumerate(zip(spans22, n22)):
             n_out = self.ctx.vocoder_samples(self.ctx.mel_frames(int(n)), True)
-            w, which = G.plan_patch_windows(G.blend_regions(spans, int(n), n_out, fade), n_out // hop, hop, rf)
+            w, which = G.plan_patch_windows(G.blend_regions(spans, int(n), n_out, fade) if regions is None else regions[b], n_out // hop, hop, rf)
             span_win += [len(wins) + k if k >= 0 else -1 for k in which]
             wins += [(b, w0, w1) for w0, w1 in w]
             per_clip.append(w)
@@ -564,9 +565,35 @@ class InpaintingEngine:
         as1d = lambda x: torch.as_tensor(x).to(self.device, torch.float32).reshape(-1).contiguous()
         wave22 = as1d(wave22)
         wave16 = None if wave16 is None else as1d(wave16)
-        N22, fade, clip_frames, batch = wave22.numel(), int(fade), int(clip_frames), int(batch)
+        fade, batch = int(fade), int(batch)
         if batch <= 0:
             raise ValueError(f"patch_recording: batch = {batch}")
+        patched = wave22.clone()
+        out: Dict[str, object] = {"patched": patched}
+        if pcm:
+            out["patched_pcm"] = self.to_int16(wave22)
+
+        def write(cb, tb, res, w22, L22):
+            own22 = G.spans22([c["own"] for c in cb], [L22] * len(cb))
+            plan = self.plan_patch(own22, [L22] * len(cb), fade)
+            if plan["wins"]:
+                ext, _ = self._stretch(res["mel"], plan["hop"], None, plan["windows"])
+                gen = self._vocode_gathered(ext, plan["wins"])
+                # the front-end divided by this peak and multiplied by 0.95 (I_ea/predict.py:104), with ALL gaps of the context zeroed
+                gain = self.ctx.wave_peak(w22, tb["tab22"]) / 0.95
+                self.ctx.patch_regions(wave22, self._region_table(cb, plan, own22), gen, gain, patched, out.get("patched_pcm"))
+
+        out.update(self._recording_passes(wave22, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write))
+        return out
+
+    def _recording_passes(self, wave22: torch.Tensor, wave16: Optional[torch.Tensor], gaps, fade_frames: int, clip_frames: int,
+                          min_context: int, batch: int, write) -> Dict[str, object]:
+        """What patch_recording and patch_file share: the context plan of a recording wave22 (N22,) on the device and, per batch of
+        at most `batch` contexts, the cut, the one multi-gap pass with every gap the clips hold masked, and the labels of the own
+        gaps.  write(cb, tb, res, w22, L22) -- the contexts of the pass, their gap tables, the pass's result (vocode=False), the cut
+        22.05 kHz clips (B, L22) -- plans the generator windows of the own gaps, runs the generator over them and writes the blended
+        samples.  -> contexts, labels, label_off."""
+        N22, clip_frames, batch = wave22.numel(), int(clip_frames), int(batch)
         n_rec = N22 // 441
         whole = n_rec <= clip_frames                                   # one context: the whole recording, with its true sample counts
         L22 = N22 if whole else clip_frames * 441
@@ -574,12 +601,9 @@ class InpaintingEngine:
             L16 = wave16.numel() if whole else clip_frames * 320
         else:
             L16 = -(-L22 * 16000 // 22050)
-        patched = wave22.clone()
-        out: Dict[str, object] = {"patched": patched}
-        if pcm:
-            out["patched_pcm"] = self.to_int16(wave22)
+        out: Dict[str, object] = {}
         lim = min(self.ctx.num_frames(L16), self.ctx.mel_frames(L22)) if L16 > 0 and L22 > 0 else 0
-        ctxs = G.plan_contexts(gaps, n_rec, clip_frames, min_context, lim_frames=lim, fade_frames=max(-(-fade // 441), 1))
+        ctxs = G.plan_contexts(gaps, n_rec, clip_frames, min_context, lim_frames=lim, fade_frames=int(fade_frames))
         n_gaps = sum(len(c["own"]) for c in ctxs)
         out["contexts"] = ctxs
         labels, counts = [], [0] * n_gaps
@@ -590,14 +614,7 @@ class InpaintingEngine:
             w16 = self.resample(w22, 22050, 16000) if wave16 is None else self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16)
             tb = self.gap_tables([c["own"] + c["foreign"] for c in cb], [L16] * B, [L22] * B)
             res = self.predict_multigap_batch(w16, w22, None, tables=tb, vocode=False)
-            own22 = G.spans22([c["own"] for c in cb], [L22] * B)
-            plan = self.plan_patch(own22, [L22] * B, fade)
-            if plan["wins"]:
-                ext, _ = self._stretch(res["mel"], plan["hop"], None, plan["windows"])
-                gen = self._vocode_gathered(ext, plan["wins"])
-                # the front-end divided by this peak and multiplied by 0.95 (I_ea/predict.py:104), with ALL gaps of the context zeroed
-                gain = self.ctx.wave_peak(w22, tb["tab22"]) / 0.95
-                self.ctx.patch_regions(wave22, self._region_table(cb, plan, own22), gen, gain, patched, out.get("patched_pcm"))
+            write(cb, tb, res, w22, L22)
             # labels of the own gaps: clip b's gaps lie sorted in the flat label vector, gap by gap
             idx = []
             for b, c in enumerate(cb):
@@ -613,6 +630,138 @@ class InpaintingEngine:
         for n in counts:
             off.append(off[-1] + n)
         out["label_off"] = off
+        return out
+
+    # ---- repair at the file's own sample rate: the recording stays at `sr` in its own sample type
+    def _rate_filter(self, sr: int) -> Dict[str, object]:
+        """audio.design_kaiser_best(22050, sr, .) with win / dwin on the device (time_reg is not used) + reach = taps per wing."""
+        from . import audio
+        key = ("rate", int(sr))
+        if key not in self._resamplers:
+            f = audio.design_kaiser_best(22050, int(sr), 1)
+            f.pop("time_reg")
+            f["reach"] = G.rate_reach(f["win"].size, f["step"])
+            for k in ("win", "dwin"):
+                f[k] = torch.from_numpy(f[k]).to(self.device)
+            self._resamplers[key] = f
+        return self._resamplers[key]
+
+    def plan_rate(self, ctxs: Sequence[dict], L22: int, sr: int, n_file: int, fade_f: int, reach: int) -> Dict[str, object]:
+        """Host planning of one pass of patch_file: the own gaps of the contexts `ctxs` (clips of L22 samples at 22.05 kHz) as spans
+        and blend regions on the FILE's sample axis (gaps.file_spans / file_lim / file_regions), those regions mapped to the 22.05 kHz
+        samples their interpolation reads (gaps.reach_regions22, `reach` taps per wing), and the generator windows that keep them
+        (plan_patch).  -> plan_patch's dictionary + spans ((start, len, window, lim_f) rows), regions (file samples), rows ((context,
+        first 22.05 kHz sample, samples, lim22) per window): what RateTable takes.  A ValueError names a gap whose interpolation reaches
+        in front of its context (a gap within `reach` samples of a context's start that is not the recording's)."""
+        hop = self.ctx.vocoder_samples(1, False)
+        n_out = self.ctx.vocoder_samples(self.ctx.mel_frames(int(L22)), True)
+        lim_loc = min(int(L22), n_out)
+        spans, regions, local, lim22 = [], [], [], []
+        for b, c in enumerate(ctxs):
+            off = 441 * int(c["start"])
+            lim22.append(off + lim_loc)
+            lim_f = G.file_lim(off + lim_loc, sr, n_file)
+            sp = G.file_spans([(c["start"] + p, l) for p, l in c["own"]], sr)
+            regs = G.file_regions(sp, [lim_f] * len(sp), fade_f)
+            r22 = G.reach_regions22(regs, sr, reach, 0 if off == 0 else -2 ** 62, off + lim_loc)
+            for (p, l), r in zip(c["own"], r22):
+                if r is not None and r[0] < off:
+                    raise ValueError(f"patch_file: the interpolation of the gap at frames [{c['start'] + p}, {c['start'] + p + l}) reads 22.05 kHz sample {r[0]}, "
+                                     f"its context starts at {off} (reach {reach} samples): raise min_context")
+            local.append([None if r is None else (r[0] - off, r[1] - off) for r in r22])
+            spans.append([(s, l, lim_f) for s, l in sp])
+            regions.append(regs)
+        plan = self.plan_patch([[(0, 0)] * len(c["own"]) for c in ctxs], [int(L22)] * len(ctxs), int(fade_f), regions=local)
+        rows, flat_regions, k = [], [], 0
+        for b in range(len(ctxs)):
+            for (s, l, lim_f), reg in zip(spans[b], regions[b]):
+                if reg is not None:
+                    rows.append((s, l, plan["span_win"][k], lim_f))
+                    flat_regions.append(reg)
+                k += 1
+        plan["spans"], plan["regions"] = rows, flat_regions
+        plan["rows"] = [(b, 441 * int(ctxs[b]["start"]) + w0 * hop, (w1 - w0) * hop, lim22[b]) for b, w0, w1 in plan["wins"]]
+        return plan
+
+    def patch_file(self, x, sr: int, gaps, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
+                   return_windows: bool = False) -> Dict[str, object]:
+        """patch_recording for a file at ITS OWN sample rate and in its own sample type: x (n,) is the recording at `sr` Hz, fp32 in
+        full-scale units or int16 PCM (tensor or array, host or device), gaps = (first frame, frame count) pairs on its 20 ms grid.
+        The recording is resampled to 22.05 kHz here (`resample`) only to FEED the model; the contexts, the multi-gap passes and the
+        labels are patch_recording's (one shared body).  The generator runs over windows widened by the interpolation's reach, and one
+        si_patch_rate launch per pass carries its samples to `sr` by band-limited interpolation at the exact time i * 22050 / sr and
+        blends them into `patched`, a copy of x: every sample outside a cross-fade of fade_ms around a gap is x's, bit for bit.
+        sr = 22050 is patch_recording itself, bit for bit.
+        -> patched (n,) in x's dtype, contexts, labels, label_off as patch_recording; return_windows=True adds passes: per pass its
+        contexts, gen (W, Lrow), gain (C,), table (RateTable) and plan.  No gaps: an exact copy, no model kernel launched."""
+        self._need(head=True, codebook=True, what="patch_file")
+        sr, batch = int(sr), int(batch)
+        P, Q = G.rate_ratio(sr)
+        if batch <= 0:
+            raise ValueError(f"patch_file: batch = {batch}")
+        x = torch.as_tensor(x)
+        pcm = x.dtype == torch.int16
+        x = x.to(self.device, torch.int16 if pcm else torch.float32).reshape(-1).contiguous()
+        n_file = x.numel()
+        if n_file < 1 or n_file > 2 ** 31 - 1 - 2048:
+            raise ValueError(f"patch_file: a file of {n_file} samples")
+        xf = x.to(torch.float32) / 32768.0 if pcm else x               # exact: 16 bits x 2^-15
+        fade_f = G.file_fade(fade_ms, sr)
+        if sr == 22050:
+            out = self.patch_recording(xf, gaps, fade=fade_f, clip_frames=clip_frames, min_context=min_context, batch=batch, pcm=pcm)
+            if pcm:
+                out["patched"] = out.pop("patched_pcm")
+            return out
+        patched = x.clone()
+        out: Dict[str, object] = {"patched": patched}
+        passes = []
+        gaps = list(gaps)
+        if not gaps:                                                   # nothing to repair: not even the resampler runs
+            out.update(contexts=[], labels=torch.zeros(0, dtype=torch.int64, device=self.device), label_off=[0])
+            if return_windows:
+                out["passes"] = passes
+            return out
+        wave22 = self.resample(xf[None], sr, 22050)[0].contiguous()
+        filt = self._rate_filter(sr)
+
+        def write(cb, tb, res, w22, L22):
+            plan = self.plan_rate(cb, L22, sr, n_file, fade_f, filt["reach"])
+            if plan["wins"]:
+                ext, _ = self._stretch(res["mel"], plan["hop"], None, plan["windows"])
+                gen = self._vocode_gathered(ext, plan["wins"])
+                # the front-end divided by this peak and multiplied by 0.95 (I_ea/predict.py:104), with ALL gaps of the context zeroed
+                gain = self.ctx.wave_peak(w22, tb["tab22"]) / 0.95
+                table = RateTable(plan["spans"], plan["rows"], G.region_chunks(plan["regions"]), len(cb), fade_f, self.device)
+                self.ctx.patch_rate(x, sr, table, gen, filt, patched, gain)
+                if return_windows:
+                    passes.append({"contexts": cb, "gen": gen, "gain": gain, "table": table, "plan": plan})
+
+        fade_frames = max(-(-fade_f * 50 // sr), 1)
+        out.update(self._recording_passes(wave22, None, gaps, fade_frames, clip_frames, min_context, batch, write))
+        if return_windows:
+            out["passes"] = passes
+        return out
+
+    def conceal_file(self, x, sr: int, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
+                     merge_frames: Optional[int] = None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
+                     return_windows: bool = False) -> Dict[str, object]:
+        """File in, repaired file out, at the file's own rate and in its own sample type: find_gaps on x itself, where a dropout is
+        still exact zeros, then patch_file with the gaps it found.  The usable frames are those of the recording's 22.05 kHz length
+        ceil(n * 22050 / sr) (`recording_frames`), and a gap longer than the planner's budget counts as long, as in conceal_recording.
+        threshold is in x's own units, as find_gaps takes it: full scale for fp32, int16 steps for an int16 file.
+        -> patch_file's dictionary + gaps + skipped.  With nothing found: an exact copy; only the detection kernels launched."""
+        sr, clip_frames, min_context = int(sr), int(clip_frames), int(min_context)
+        P, Q = G.rate_ratio(sr)
+        x = torch.as_tensor(x)
+        x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32).reshape(-1).contiguous()
+        n_rec, lim = self.recording_frames(-(-x.numel() * P // Q), clip_frames)
+        if n_rec > clip_frames:
+            max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
+        fade22 = -(-G.file_fade(fade_ms, sr) * P // Q)
+        found = self.find_gaps(x, sr, threshold, min_ms, max_ms, pad_frames, merge_frames, fade22, n_rec, lim)
+        out = self.patch_file(x, sr, found["gaps"], fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch,
+                              return_windows=return_windows)
+        out["gaps"], out["skipped"] = found["gaps"], found["skipped"]
         return out
 
     # ---- dropout detection (DESIGN.md 4.15): where the gaps are, found on the device; then patch_recording as it is

@@ -348,3 +348,64 @@ def runs_to_gaps(runs: Sequence[Sequence[int]], n: int, sr: int, n_rec_frames: i
         else:
             gaps.append((a, b - a))
     return gaps, sorted(skipped)
+
+
+# ---- repair at the file's own sample rate: gaps -> spans, regions and limits on the FILE's sample axis
+RATE_MIN, RATE_MAX = 4000, 192000
+
+
+def rate_ratio(sr: int) -> Tuple[int, int]:
+    """(P, Q) = (22050, sr) / gcd: file sample i sits at position i * P / Q on the 22.05 kHz axis.  A ValueError for a rate outside
+    [RATE_MIN, RATE_MAX]."""
+    sr = int(sr)
+    if not RATE_MIN <= sr <= RATE_MAX:
+        raise ValueError(f"sample rate {sr} Hz is outside {RATE_MIN} .. {RATE_MAX}")
+    g = math.gcd(22050, sr)
+    return 22050 // g, sr // g
+
+
+def file_fade(fade_ms: float, sr: int) -> int:
+    """The cross-fade length in file samples: round(fade_ms * sr / 1000), Python's round (5 ms: 240 at 48 kHz, 220 at 44.1 kHz, 110 at
+    22.05 kHz as config.patch_fade gives)."""
+    return int(round(float(fade_ms) * int(sr) / 1000.0))
+
+
+def file_spans(gaps: Sequence[Gap], sr: int) -> List[Gap]:
+    """(start, len) in FILE samples per gap (first frame, frame count) of the 20 ms grid: samples [ceil(p * sr / 50),
+    ceil((p + l) * sr / 50)) -- exactly the file samples whose 22.05 kHz position lies in [441 p, 441 (p + l)).  Integers only."""
+    sr = int(sr)
+    return [(-(-int(p) * sr // 50), -(-(int(p) + int(l)) * sr // 50) - -(-int(p) * sr // 50)) for p, l in gaps]
+
+
+def file_lim(lim22: int, sr: int, n_file: Optional[int] = None) -> int:
+    """The first file sample whose 22.05 kHz position is at or past lim22: ceil(lim22 * Q / P), clamped to the file's n_file samples."""
+    P, Q = rate_ratio(sr)
+    lim = -(-int(lim22) * Q // P)
+    return lim if n_file is None else min(lim, int(n_file))
+
+
+def file_regions(spans_f: Sequence[Gap], lims_f: Sequence[int], fade_f: int) -> List[Optional[Gap]]:
+    """`blend_regions` on the file axis: per (start, len) span and its lim_f the half-open range [max(s - fade_f, 0),
+    min(s + l + fade_f, lim_f)) of file samples that are written; None for a span that starts at or past its lim_f."""
+    fade_f = int(fade_f)
+    return [None if l <= 0 or s >= lim else (max(s - fade_f, 0), min(s + l + fade_f, lim)) for (s, l), lim in zip(spans_f, lims_f)]
+
+
+def rate_reach(nwin: int, step: int) -> int:
+    """H: taps per wing of the band-limited interpolation, ceil(nwin / step) (audio.design_kaiser_best's table)."""
+    return -(-int(nwin) // int(step))
+
+
+def reach_regions22(regions_f: Sequence[Optional[Gap]], sr: int, reach: int, lo22: int, lim22: int) -> List[Optional[Gap]]:
+    """File-axis regions -> the 22.05 kHz samples their interpolation reads: [floor(a * P / Q) - reach, floor((b - 1) * P / Q) + 1 +
+    reach), clamped to [lo22, lim22) -- pass lo22 = 0 where the recording starts (taps before it read as zero) and lim22 = where the
+    context's generated audio ends (taps at and past it read as zero).  The regions the generator windows must keep."""
+    P, Q = rate_ratio(sr)
+    out: List[Optional[Gap]] = []
+    for reg in regions_f:
+        if reg is None:
+            out.append(None)
+            continue
+        a, b = int(reg[0]), int(reg[1])
+        out.append((max(a * P // Q - int(reach), int(lo22)), min((b - 1) * P // Q + 1 + int(reach), int(lim22))))
+    return out

@@ -30,7 +30,7 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_debug_capture", "si_debug_size",
            "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
            "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
-           "si_cut_clips", "si_patch_regions", "si_quiet_runs"]
+           "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate"]
 SI_MAX_SPANS = 16
 
 
@@ -180,6 +180,38 @@ class RegionTable:
         return RegionTableStruct(C.sizeof(RegionTableStruct), self.C, W, K, Q, self.fade, *[h + x for x in o[:10]], *[d + x for x in o[:10]], d + o[10])
 
 
+class RateTableStruct(C.Structure):
+    """Mirror of si_rate_table."""
+    _HOST = ("start", "len", "span_win", "span_lim", "win_ctx", "win_start", "win_len", "win_lim", "chunk", "k0", "k1")
+    _fields_ = ([(n, C.c_int32) for n in ("struct_size", "num_contexts", "num_windows", "num_spans", "num_chunks", "fade")] +
+                [("host_" + n, C.c_void_p) for n in _HOST] + [(n, C.c_void_p) for n in _HOST] + [("ramp", C.c_void_p)])
+
+
+class RateTable:
+    """RegionTable for a file at its own sample rate, as si_rate_table takes it: spans = (start, len, window, lim) per span in FILE
+    samples, sorted and disjoint; windows = (context, first sample, samples, lim) per generator row in 22.05 kHz samples of the
+    recording (lim: where its context's generated audio ends); chunks = (chunk, k0, k1) per touched chunk of 2048 FILE samples
+    (gaps.region_chunks); fade in file samples.  One array, one copy: [start | len | span_win | span_lim | win_ctx | win_start |
+    win_len | win_lim | chunk | k0 | k1 | ramp (fp32 bits)].  A value outside int32 is refused here (the library could not see it)."""
+
+    def __init__(self, spans, windows, chunks, n_contexts: int, fade: int, device):
+        from .gaps import fade_ramp
+        self.K, self.W, self.Q, self.C, self.fade = len(spans), len(windows), len(chunks), int(n_contexts), int(fade)
+        for what, rows, n in (("span", spans, 4), ("window", windows, 4), ("chunk", chunks, 3)):
+            for k, r in enumerate(rows):
+                if len(r) != n or any(not -2 ** 31 <= int(v) < 2 ** 31 for v in r):
+                    raise ValueError(f"RateTable: {what} {k} = {tuple(r)} is not {n} int32 values")
+        cols = [[int(r[j]) for r in rows] for rows, n in ((spans, 4), (windows, 4), (chunks, 3)) for j in range(n)]
+        ints = np.array([v for col in cols for v in col], dtype=np.int32)
+        self.host = np.ascontiguousarray(np.concatenate([ints, fade_ramp(self.fade).view(np.int32), np.zeros(1, np.int32)]))   # (+ 1: never empty)
+        self.dev = torch.from_numpy(self.host).to(device, non_blocking=True)
+
+    def struct(self) -> RateTableStruct:
+        h, d, K, W, Q = self.host.ctypes.data, self.dev.data_ptr(), self.K, self.W, self.Q
+        o = [4 * x for x in [j * K for j in range(4)] + [4 * K + j * W for j in range(4)] + [4 * K + 4 * W + j * Q for j in range(4)]]
+        return RateTableStruct(C.sizeof(RateTableStruct), self.C, W, K, Q, self.fade, *[h + x for x in o[:11]], *[d + x for x in o[:11]], d + o[11])
+
+
 class ExtractDesc(C.Structure):
     """Mirror of si_extract_desc."""
     _fields_ = [("struct_size", C.c_int32), ("output_layer", C.c_int32), ("normalize", C.c_int32), ("reserved", C.c_int32)]
@@ -325,6 +357,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_cut_clips.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
     lib.si_patch_regions.argtypes = [vp, vp, i32, C.POINTER(RegionTableStruct), vp, i32, vp, vp, vp, vp]
     lib.si_quiet_runs.argtypes = [vp, vp, i32, i32, C.c_float, i32, vp, i32, vp, vp]
+    lib.si_patch_rate.argtypes = [vp, vp, i32, i32, i32, C.POINTER(RateTableStruct), vp, i32, vp, C.POINTER(SincFilter), vp, vp]
     lib.si_num_frames.argtypes = [vp, i32]
     lib.si_vocoder_samples.argtypes = [vp, i32, i32]
     lib.si_debug_capture.argtypes = [vp, C.c_char_p, vp, C.c_long]
@@ -624,6 +657,26 @@ class NativeContext:
         t = table.struct()
         self._check(self.lib.si_patch_regions(self._h, _ptr(orig), min(N, 2 ** 31 - 1), C.byref(t), _ptr(gen), 0 if gen is None else gen.shape[1], _ptr(gain), _ptr(out),
                                               _ptr(out_pcm), self._stream()), "si_patch_regions")
+
+    # ---- repair at the file's own sample rate
+    def patch_rate(self, orig: torch.Tensor, sr: int, table: "RateTable", gen: Optional[torch.Tensor], filt: dict, out: torch.Tensor,
+                   gain: Optional[torch.Tensor] = None) -> None:
+        """The blended samples of `table`'s regions written IN PLACE into out (n_file,), which holds the caller's copy of the file
+        `orig` (n_file,) at `sr` Hz everywhere else (si_patch_rate).  orig / out: fp32 or int16, the same type, device views that may
+        start anywhere.  gen (W, Lrow) fp32 at 22.05 kHz; gain (C,) fp32 or None; filt: audio.design_kaiser_best(22050, sr, .) with win /
+        dwin as float64 device tensors."""
+        assert orig.is_cuda and orig.dtype in (torch.float32, torch.int16) and orig.dim() == 1 and orig.is_contiguous()
+        assert out.is_cuda and out.dtype == orig.dtype and out.dim() == 1 and out.is_contiguous() and out.numel() == orig.numel()
+        assert gen is None or (gen.is_cuda and gen.dtype == torch.float32 and gen.dim() == 2 and gen.is_contiguous() and gen.shape[0] == table.W)
+        assert gain is None or (gain.is_cuda and gain.dtype == torch.float32 and gain.numel() == table.C and gain.is_contiguous())
+        win, dwin = filt["win"], filt["dwin"]
+        assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
+        assert win.numel() == dwin.numel()
+        f = SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
+                       float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
+        t = table.struct()
+        self._check(self.lib.si_patch_rate(self._h, _ptr(orig), int(orig.dtype == torch.int16), min(orig.numel(), 2 ** 31 - 1), int(sr), C.byref(t), _ptr(gen),
+                                           0 if gen is None else gen.shape[1], _ptr(gain), C.byref(f), _ptr(out), self._stream()), "si_patch_rate")
 
     # ---- dropout detection (DESIGN.md 4.15)
     def quiet_runs(self, x: torch.Tensor, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536, runs: Optional[torch.Tensor] = None,

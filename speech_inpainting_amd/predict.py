@@ -9,14 +9,16 @@ It reads the reference's YAML schema, loads the same three artefacts (CustomMode
 `<save_pred>/<wave_name>/{orig,masked,hifi_masked,expected_inpaint,inpainted}.wav` (I_ea/predict.py:84,128,134,201,207;
 `expected_inpaint.wav` only when the ground-truth label file exists).  `predict_clips` is the importable batch form.
 
-With an optional `long:` mapping ({clip_s: 4.0, context_s: 1.0, batch: 32}) the file is a RECORDING of any length: the gaps of
+With an optional `long:` mapping ({clip_s: 4.0, context_s: 1.0, batch: 32, rate: 22050 | file}) the file is a RECORDING of any length: the gaps of
 `mask:` / `masks:` are read on the file's own time axis, the recording is served as context clips (engine.patch_recording, DESIGN.md
 4.14; the cross-fade comes from `patch:`, 5 ms without it) and `orig.wav`, `masked.wav` and `patched.wav` are written at 22.05 kHz,
 all with the recording's own sample count.  The whole-clip diagnostics (`hifi_masked.wav`, `inpainted.wav`, `expected_inpaint.wav`)
 are NOT produced on this route: no generator pass over a whole recording exists there.  With a `detect:` mapping ({threshold: 0.0,
 min_ms: 5.0, max_ms: 400.0, pad_frames: 0}) beside `long:` and instead of `mask:` / `masks:` the gaps are FOUND: the runs of
 |x| <= threshold of at least min_ms in the file's own samples (engine.find_gaps); each gap and each skipped run is
-printed and `gaps.json` is written beside the three waves.
+printed and `gaps.json` is written beside the three waves.  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
+on the way out: the three waves keep the file's own rate and sample type (an int16 file stays int16), and patched.wav holds the file's
+own samples, bit for bit, outside the cross-fades (engine.patch_file).  A multi-channel file is refused there.
 
 Differences from the script, all outside the three replaced subsystems: no Whisper `Metrics` object is built (the
 script constructs it and never uses it, I_ea/predict.py:72-73), PNG plots are skipped, and the two `librosa.load` calls are one
@@ -354,8 +356,43 @@ def _detect_gaps(cfg: PredictConfig, engine: InpaintingEngine, raw: np.ndarray, 
     return found["gaps"]
 
 
+def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> int:
+    """`long: {rate: file}`: the recording stays at the file's own rate and in its own sample type (engine.patch_file).  orig.wav,
+    masked.wav and patched.wav are written at that rate; an int16 file is written as int16, any other as the float32 it was read to."""
+    from scipy.io import wavfile
+    from . import gaps as G
+    sr_file, data = wavfile.read(cfg.wave_path)
+    if data.ndim != 1:
+        raise ValueError(f"{cfg.wave_path}: {data.shape[1]} channels -- `long: {{rate: file}}` gives the file's own samples back and serves one channel; "
+                         f"split the channels, or drop `rate: file` for the 22.05 kHz mix-down")
+    raw, sr_file = audio.read_wav(cfg.wave_path)
+    x = data if data.dtype == np.int16 else raw
+    P, Q = G.rate_ratio(sr_file)
+    fade_ms = cfg.patch_fade_ms if cfg.patch_fade_ms is not None else 5.0
+    clip_frames, min_context = int(round(cfg.long["clip_s"] * 50)), int(round(cfg.long["context_s"] * 50))
+    if cfg.detect is not None:
+        gap_list = _detect_gaps(cfg, engine, raw, sr_file, -(-len(x) * P // Q), -(-G.file_fade(fade_ms, sr_file) * P // Q), clip_frames, min_context,
+                                save_dir)
+    else:
+        gap_list = sorted(cfg.gaps) if cfg.gaps is not None else [(cfg.mask_pos, cfg.mask_frames)]
+    audio.write_wav(os.path.join(save_dir, "orig.wav"), x, sr_file)
+    masked = x.copy()
+    for s, l in G.file_spans(gap_list, sr_file):
+        masked[s:s + l] = 0                                                        # the file samples whose time lies in the gap's frames
+    audio.write_wav(os.path.join(save_dir, "masked.wav"), masked, sr_file)
+    out = engine.patch_file(x, sr_file, gap_list, fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"])
+    labels, off = out["labels"].tolist(), out["label_off"]
+    for k, (pos, lm) in enumerate(gap_list):
+        print(f"Predicted codewords, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[k]:off[k + 1]])
+    audio.write_wav(os.path.join(save_dir, "patched.wav"), out["patched"].cpu().numpy(), sr_file)
+    print("wrote", save_dir)
+    return 0
+
+
 def _main_long(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> int:
     """The `long:` route of `main`: the file as a recording of any length, its gaps on its own time axis."""
+    if cfg.long_rate == "file":
+        return _main_long_file(cfg, engine, save_dir)
     raw, sr_file = audio.read_wav(cfg.wave_path)
     wave_22 = engine.resample(torch.from_numpy(raw)[None].to(engine.device), sr_file, 22050)[0].contiguous()
     fade = cfg.patch_fade if cfg.patch_fade is not None else 110

@@ -1,0 +1,95 @@
+"""Experiment: what keeping the file's own rate costs.  A 10-minute synthetic 48 kHz int16 recording with 60 gaps of
+200 ms, HuBERT-base bf16 + HiFi-GAN V1 fp16 stream, in ONE process, the variants alternated inside each repeat after warm-up,
+device-synchronised wall clock per call:
+
+  (a) engine.patch_file(x, 48000, gaps): the recording stays 48 kHz int16, one si_patch_rate per pass
+  (b) the only way back there was: resample to 22.05 kHz, engine.patch_recording, engine.resample of the WHOLE result to 48 kHz,
+      to_int16 -- which returns none of the file's own samples
+
+Both resample the recording to 22.05 kHz on the way in (that is outside this change).  Prints one line per repeat, the medians, how
+many samples of the file each variant changed, and -- from a separate, untimed run under the library's profiler -- the time of the
+patch_rate family beside resample_sinc's.
+usage: python tools/exp_rate.py [--repeats 5] [--minutes 10] [--gaps 60] [--sr 48000]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--repeats", type=int, default=5)
+ap.add_argument("--minutes", type=float, default=10.0)
+ap.add_argument("--gaps", type=int, default=60)
+ap.add_argument("--sr", type=int, default=48000)
+ap.add_argument("--batch", type=int, default=32)
+a = ap.parse_args()
+WARMUP = 1
+CLIP, CTX, LM = 200, 50, 10
+
+import torch
+
+from speech_inpainting_amd import synth
+from speech_inpainting_amd.arch import HubertArch, VocoderArch
+from speech_inpainting_amd.engine import InpaintingEngine
+
+dev = torch.device("cuda:0")
+harch, varch = HubertArch.base(), VocoderArch.v1()
+eng = InpaintingEngine(harch, varch, 100, dev, "bf16", "fp16").load_state(
+    synth.synth_hubert_state(harch), synth.synth_generator_state(varch), synth.synth_codebook(100))
+sr = a.sr
+n = int(a.minutes * 60 * sr) + 77
+n_rec = n * 50 // sr
+tile = synth.synth_wave(1, 30 * sr, synth.DEFAULT_SEED + 6, sr=sr)[0]
+x = (tile.repeat(-(-n // tile.numel()))[:n] * 32767.0).to(torch.int16).contiguous().to(dev)
+every = n_rec // a.gaps
+gaps = [(k * every + every // 2, LM) for k in range(a.gaps)]
+KW = dict(clip_frames=CLIP, min_context=CTX, batch=a.batch)
+
+
+def keep_rate():
+    return eng.patch_file(x, sr, gaps, **KW)["patched"]
+
+
+def round_trip():
+    wave22 = eng.resample((x.to(torch.float32) / 32768.0)[None], sr, 22050)[0].contiguous()
+    patched = eng.patch_recording(wave22, gaps, fade=110, **KW)["patched"]
+    return eng.to_int16(eng.resample(patched[None], 22050, sr)[0][:n].contiguous())
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+times = {"patch_file": [], "round_trip": []}
+for r in range(WARMUP + a.repeats):
+    order = (("patch_file", keep_rate), ("round_trip", round_trip)) if r % 2 == 0 else (("round_trip", round_trip), ("patch_file", keep_rate))
+    row = {}
+    for name, fn in order:
+        row[name], out = timed(fn)
+        if r == WARMUP:
+            print(f"{name}: {int((out != x[:out.numel()]).sum())} of {n} samples differ from the file's")
+    if r >= WARMUP:
+        for k, v in row.items():
+            times[k].append(v)
+        print(f"repeat {r - WARMUP}: patch_file {row['patch_file']:.1f} ms, round trip {row['round_trip']:.1f} ms")
+for k, v in times.items():
+    print(f"median {k}: {statistics.median(v):.1f} ms over {len(v)} repeats")
+
+eng.ctx.profile_start(20000)
+keep_rate()
+prof = {e["name"]: e for e in eng.ctx.profile_stop()}
+for name in ("patch_rate", "resample_sinc"):
+    if name in prof:
+        print(f"profiled patch_file: {name} {prof[name]['launches']} launches, {prof[name]['ms']:.3f} ms")
+eng.ctx.profile_start(20000)
+round_trip()
+prof = {e["name"]: e for e in eng.ctx.profile_stop()}
+for name in ("patch_regions", "resample_sinc"):
+    if name in prof:
+        print(f"profiled round trip: {name} {prof[name]['launches']} launches, {prof[name]['ms']:.3f} ms")
