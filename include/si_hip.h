@@ -33,6 +33,8 @@
  *                           (start_pos_in_sec, end_pos_in_sec) that a user of the script types by hand      I_ea/predict.py:85-90
  *   si_patch_rate        <- the same write-out for a file at ANY sample rate, which the script resamples on the way in and never
  *                           brings back                                       I_ea/predict.py:79-80,203-207
+ *   si_cut_rate          <- that resampling on the way in, for the context clips alone instead of the whole file (with si_cut_clips'
+ *                           slicing)                                          I_ea/predict.py:79-80
  *   si_load_weights      <- model.load_state_dict / generator.load_state_dict + remove_weight_norm + ApplyKmeans
  *                           I_ea/predict.py:117-122,149 ; I_ea/hifi_gan/models.py:125-132 ; I_ea/dataset/km_label.py:12-24
  *
@@ -633,6 +635,37 @@ typedef struct si_rate_table {
  * window's row other than before sample 0 or at or past win_lim.  num_chunks = 0 launches nothing and succeeds. */
 int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int sr, const si_rate_table* table, const float* gen, int Lrow,
                   const float* gain, const si_sinc_filter* filt, void* out, si_stream_t stream);
+
+/* ---- Context clips cut at the file's own sample rate ------------------------------------------------------------------
+ * The reference's script resamples its whole input to 22.05 kHz before anything else (I_ea/predict.py:79-80).  For a long file with a
+ * few gaps that pass -- si_resample_sinc over every sample, an fp32 copy of an int16 file, a 22.05 kHz copy of the recording and a
+ * float64 time table of its length -- is the one cost that scales with the file instead of the damage.  The call below replaces it
+ * together with si_cut_clips: it computes ONLY the 22.05 kHz samples of the context clips, straight from the file's own samples.
+ *
+ * With g = gcd(22050, sr), P = 22050 / g, Q = sr / g, sample j of the recording's 22.05 kHz axis sits at file position j Q / P, and the
+ * recording has N22 = ceil(n_file P / Q) such samples (every j < N22 has its position inside the file).  out (C, L) fp32, row c =
+ * samples [start[c], start[c] + L) of that axis; the starts are arbitrary (not tied to any frame grid), clips may overlap and come in
+ * any order.  Sample j: n, r = divmod(j Q, P) in 64-bit integers, frac = scale (r / P), and with the tables of `filt`
+ * (audio.design_kaiser_best(sr, 22050, .): win -- scaled by the ratio when down-sampling --, dwin, nwin, num_table, step, scale;
+ * time_reg, n_time and ratio are NOT read)
+ *     left wing   off, eta = split(frac num_table):            taps k < min(n + 1, (nwin - off) / step)           weigh x[n - k]
+ *     right wing  off', eta' = split((scale - frac) num_table): taps k < min(n_file - n - 1, (nwin - off') / step) weigh x[n + 1 + k]
+ * by fma(eta, dwin[off + k step], win[off + k step]), accumulated by fma in float64 in that order (left ascending, then right ascending)
+ * and rounded once to fp32 -- si_resample_sinc's arithmetic at the EXACT time instead of 1 / ratio accumulated by repeated addition.  File
+ * samples before 0 and at or past n_file do not exist (the tap counts say so).  Two deliberate differences from si_resample_sinc over
+ * the whole file: (a) at exactly-integer times (j a multiple of P) frac is exactly 0, where the accumulated rounding picks the table
+ * phase; elsewhere a result moves by at most an fp32 rounding; (b) the last sample j = N22 - 1 is interpolated when n_file P / Q is no
+ * integer, where si_resample_sinc writes zero at and past int(n ratio).
+ * x: device, n_file samples, fp32 (is_pcm16 = 0) or int16 PCM (is_pcm16 != 0: a sample enters as (float)v / 32768, exact); the base
+ * needs only its element's alignment.  host_start (HOST, C) is validated, start (DEVICE, C) is read: the si_span_table rule.  One
+ * workgroup owns a tile of SI_CUT_RATE_TILE consecutive outputs of one clip.
+ * SI_EINVAL before any launch, naming the argument, for: NULL pointers; sr outside 4000 .. 192000 or equal to 22050; n_file < 1; n_file
+ * or N22 above 2^31 - 1 - 2048; a filter si_patch_rate would refuse (nwin < 2, num_table < 1, step < 1, scale outside (0, 1], NULL
+ * tables, or so many taps per wing that a tile's staged samples exceed 64 KB); C < 0 or above 65535; L < 1; any start < 0 or
+ * start + L > N22.  C = 0 launches nothing and succeeds. */
+#define SI_CUT_RATE_TILE 512
+int si_cut_rate(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_start, const int32_t* start, int C, int L,
+                const si_sinc_filter* filt, float* out, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

@@ -60,6 +60,8 @@ class PredictConfig:
                                   # length, served as context clips (engine.patch_recording); None without the key
     long_rate: object = 22050     # `rate:` inside `long:`: 22050 (default: patched.wav is the recording resampled to 22.05 kHz) or "file"
                                   # (patched.wav keeps the file's own rate and sample type: engine.patch_file)
+    long_feed: str = "recording"  # `feed:` inside `long:` (needs rate: file): "recording" (default: the whole file is resampled to 22.05 kHz
+                                  # to feed the model) or "contexts" (only the context clips are, straight from the file: DESIGN.md 4.17)
     detect: Optional[dict] = None  # optional `detect:` mapping ({threshold: 0.0, min_ms: 5.0, max_ms: 400.0, pad_frames: 0}): the gaps are
                                    # found in the file itself (engine.find_gaps) instead of given as `mask:` / `masks:`; needs `long:`
 
@@ -130,7 +132,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             patch_fade_ms = float(pm.get("fade_ms", 5))
             if patch_fade_ms < 0:
                 raise ValueError(f"{path}: patch.fade_ms = {patch_fade_ms} is negative")
-        long_cfg, long_rate = None, 22050
+        long_cfg, long_rate, long_feed = None, 22050, "recording"
         if "long" in data:
             lm = data["long"] if data["long"] is not None else {}
             if not isinstance(lm, dict):
@@ -141,9 +143,16 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                 long_rate = lm.pop("rate")
                 if long_rate not in (22050, "file"):
                     raise ValueError(f"{path}: long.rate = {long_rate!r}: 22050 (the default) or file (the file's own rate and sample type)")
+            if "feed" in lm:
+                long_feed = lm.pop("feed")
+                if long_feed not in ("recording", "contexts"):
+                    raise ValueError(f"{path}: long.feed = {long_feed!r}: recording (the default: the whole file is resampled to feed the model) or "
+                                     f"contexts (only the context clips are cut from the file, at its own rate)")
+                if long_feed == "contexts" and long_rate != "file":
+                    raise ValueError(f"{path}: long.feed = contexts needs `rate: file` (at rate: {long_rate} the recording is resampled as a whole)")
             for key, val in lm.items():
                 if key not in long_cfg:
-                    raise ValueError(f"{path}: unknown key `{key}` in `long:` (it takes clip_s, context_s, batch, rate)")
+                    raise ValueError(f"{path}: unknown key `{key}` in `long:` (it takes clip_s, context_s, batch, rate, feed)")
                 long_cfg[key] = int(val) if key == "batch" else float(val)
                 if long_cfg[key] < 0:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
@@ -181,7 +190,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_type=str(data["hubert_model"]["type"]),
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
-            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, detect=detect_cfg)
+            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, detect=detect_cfg)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

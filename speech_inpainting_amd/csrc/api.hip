@@ -2185,6 +2185,42 @@ int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int s
     return si_launch_patch_rate(ctx, orig, is_pcm16 != 0, n_file, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
 }
 
+// ---- context clips cut at the file's own sample rate
+int si_cut_rate(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_start, const int32_t* start, int C, int L,
+                const si_sinc_filter* filt, float* out, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (sr < 4000 || sr > 192000) return si_fail(ctx, SI_EINVAL, "si_cut_rate: sr = %d Hz, outside 4000 .. 192000", sr);
+    if (sr == 22050) return si_fail(ctx, SI_EINVAL, "si_cut_rate: sr = 22050 Hz is the model's own rate: that file is si_cut_clips'");
+    if (n_file < 1) return si_fail(ctx, SI_EINVAL, "si_cut_rate: n_file = %d", n_file);
+    if ((long)n_file > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_cut_rate: n_file = %d samples, at most %ld", n_file, SI_MAX_REC);
+    long ga = 22050, gb = sr;
+    while (gb) { const long r = ga % gb; ga = gb; gb = r; }
+    const long P = 22050 / ga, Qr = sr / ga;
+    const long N22 = ((long)n_file * P + Qr - 1) / Qr;              // the recording's samples on the 22.05 kHz axis, ceil(n_file P / Q)
+    if (N22 > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_cut_rate: n_file = %d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
+    const si_sinc_filter* f = filt;
+    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return si_fail(ctx, SI_EINVAL, "si_cut_rate: filt: si_sinc_filter size mismatch");
+    if (!f->win || !f->dwin || f->nwin < 2 || f->num_table < 1 || f->step < 1 || !(f->scale > 0.0 && f->scale <= 1.0))
+        return si_fail(ctx, SI_EINVAL, "si_cut_rate: filt: bad filter table (nwin %d, num_table %d, step %d, scale %g)", f->nwin, f->num_table, f->step, f->scale);
+    const long H = ((long)f->nwin + f->step - 1) / f->step;
+    const long cap = (RF_TILE - 1) * Qr / P + 2 + 2 * H;            // file samples one tile stages in LDS: 5 581 at 192 kHz with kaiser_best, of 160 KB
+    if (cap * (long)sizeof(float) > 65536)
+        return si_fail(ctx, SI_EINVAL, "si_cut_rate: filt: bad filter table: %ld taps per wing at %d Hz need %ld staged samples per tile, at most 16384", H, sr, cap);
+    if (C < 0 || C > 65535) return si_fail(ctx, SI_EINVAL, "si_cut_rate: C = %d clips in one call, 0 .. 65535 (the launch grid's second dimension)", C);
+    if (L < 1) return si_fail(ctx, SI_EINVAL, "si_cut_rate: L = %d", L);
+    if (C == 0) return SI_OK;                                       // nothing is read or written
+    if (!x || !out || !host_start || !start)
+        return si_fail(ctx, SI_EINVAL, "si_cut_rate: %s is NULL", !x ? "x" : !out ? "out" : !host_start ? "host_start" : "start");
+    for (int c = 0; c < C; ++c) {
+        const long s = host_start[c];
+        if (s < 0 || s + L > N22)
+            return si_fail(ctx, SI_EINVAL, "si_cut_rate: start[%d]: clip = 22.05 kHz samples [%ld, %ld) is outside the recording's %ld samples", c, s, s + L, N22);
+    }
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    const SiFeed fd{f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Qr, (int)H, (int)cap, (int)N22};
+    return si_launch_cut_rate(ctx, x, is_pcm16 != 0, n_file, start, C, L, fd, out, static_cast<hipStream_t>(stream));
+}
+
 // ---- dropout detection
 int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
                   si_stream_t stream) {

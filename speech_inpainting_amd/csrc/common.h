@@ -374,6 +374,21 @@ struct SiRate {
 int si_launch_patch_rate(si_ctx* ctx, const void* orig, bool pcm16, int n_file, const SiRate& rt, int num_chunks, const float* gen, int Lrow,
                          const float* gain, void* out, hipStream_t st);
 
+// ------------------------------------------------------------------------------------------------
+// context clips cut at the file's own rate (rate_feed_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+constexpr int RF_TILE = SI_CUT_RATE_TILE;       // consecutive outputs of one clip per workgroup (si_hip.h; native.CUT_RATE_TILE)
+// the kaiser_best tables of sr -> 22 050, P / Q = (22050, sr) / gcd, H = ceil(nwin / step) taps per wing, cap = floor((RF_TILE - 1) Q / P)
+// + 2 + 2 H: the file samples one tile can read, the floats of dynamic LDS the launch asks for, and N22 = ceil(n_file P / Q)
+struct SiFeed {
+    const double* win; const double* dwin; int nwin, num_table, step; double scale;
+    int P, Q, H, cap, N22;
+};
+// out (C, L) row c = 22.05 kHz samples [start[c], start[c] + L) of the file x (n_file; fp32, or int16 when pcm16), interpolated at the
+// exact time j Q / P; start device int32 (C); arguments validated by the caller
+int si_launch_cut_rate(si_ctx* ctx, const void* x, bool pcm16, int n_file, const int32_t* start, int C, int L, const SiFeed& fd, float* out,
+                       hipStream_t st);
+
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16
 // rounding every consumer of these outputs applies; 15 VALU operations instead of libm erff's ~31 with two divergent branches.

@@ -1,0 +1,95 @@
+// rate_feed_kernels.hip -- the model's 22.05 kHz context clips cut straight out of a file at its own rate, gfx950.
+//   cut_rate_kernel<float | int16_t>   per tile of 512 consecutive outputs of one clip: the file samples the tile's interpolation reads
+//                                      staged in LDS as fp32, then per output the two wings of the band-limited interpolation at the
+//                                      exact rational time j Q / P
+// It stands where `resample(file, sr, 22050)` over the whole recording + si_cut_clips would: that pass costs every 22.05 kHz sample of
+// the recording a 2 H-tap float64 sum, an fp32 copy of an int16 file, a 22.05 kHz copy of the recording and a float64 time table of its
+// length; this one computes the samples of the context clips and creates nothing of the recording's length.
+#include "common.h"
+
+__device__ __forceinline__ float rf_load(const float* p) { return *p; }
+__device__ __forceinline__ float rf_load(const int16_t* p) { return (float)*p * (1.0f / 32768.0f); }     // exact: 16 bits x 2^-15
+
+// grid (ceil(L / 512), C), 256 threads, fd.cap floats of dynamic LDS.  Workgroup (tile, c) owns outputs [tile 512, min(tile 512 + 512, L))
+// of clip c = 22.05 kHz samples j0 + [0, cnt) of the recording, j0 = start[c] + tile 512 (workgroup-uniform: scalar loads).
+//   stage   file samples [n0 - H, n1 + H], n0 = floor(j0 Q / P), n1 = floor((j0 + cnt - 1) Q / P): lane t loads element t, t + 256, ...
+//           (one element wide: coalesced whatever the file's alignment -- callers pass views), int16 converted on the way in, zero before
+//           file sample 0 and at / past n_file.  n1 - n0 <= floor(511 Q / P) + 1, so the range holds at most
+//           floor(511 Q / P) + 2 + 2 H = cap samples: 65 taps per wing when up-sampling, 140 at 48 kHz, 565 at 192 kHz (5 582 floats).
+//   sample  lane t owns outputs t and t + 256.  n, r = divmod(j Q, P) in int64; frac = scale (r / P); left wing off, eta =
+//           split(frac num_table), taps k < min(n + 1, (nwin - off) / step) on x[n - k]; right wing the same from scale - frac, taps
+//           k < min(n_file - n - 1, (nwin - off') / step) on x[n + 1 + k]; weights fma(eta, dwin, win), sum by fma in float64, left
+//           ascending then right ascending, rounded once to fp32: resample_sinc_kernel's arithmetic at the exact time.  Neighbouring
+//           lanes read neighbouring LDS words (stride Q / P); the tables stay in L2 as they do for resample_sinc_kernel.  Nothing in
+//           it depends on where the clip or the tile starts: a sample has the same bits in whichever clip it is cut.
+// Plain stores, no atomics; each output is written once.  The C ABI validated the host copy of `start`; an output whose j lies outside
+// [0, N22) -- a device table that differs from the validated one -- is written as zero, and the staging loop reads the file only inside
+// [0, n_file): wrong output, not a fault.
+template <typename T>
+__global__ __launch_bounds__(256) void cut_rate_kernel(const T* __restrict__ x, int n_file, const int32_t* __restrict__ start, int L, SiFeed fd,
+                                                       float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float rf_row[];
+    const int c = blockIdx.y, o0 = blockIdx.x * RF_TILE;
+    const int cnt = min(RF_TILE, L - o0);
+    const long j0 = (long)start[c] + o0;
+    const long P = fd.P, Q = fd.Q;
+    const int H = fd.H, nwin = fd.nwin, step = fd.step;
+    const double scale = fd.scale, ntab = (double)fd.num_table;
+    const bool live = j0 >= 0 && j0 + cnt <= (long)fd.N22;              // uniform
+    const long base = live ? j0 * Q / P - H : 0;
+    const int span = live ? min((int)((j0 + cnt - 1) * Q / P + H + 1 - base), fd.cap) : 0;
+    for (int p = threadIdx.x; p < span; p += 256) {
+        const long i = base + p;
+        rf_row[p] = (i >= 0 && i < (long)n_file) ? rf_load(x + i) : 0.f;
+    }
+    __syncthreads();
+    float* orow = out + (size_t)c * L + o0;
+    for (int m = threadIdx.x; m < cnt; m += 256) {
+        if (!live) { orow[m] = 0.f; continue; }
+        const long t = (j0 + m) * Q;
+        const long nl = t / P;
+        const int n = (int)nl;
+        const double frac = scale * ((double)(t - nl * P) / (double)P);
+        double acc = 0.0;
+        {
+            const double idx = frac * ntab;
+            const int off = (int)idx;
+            const double eta = idx - (double)off;
+            const int taps = min(n + 1, (nwin - off) / step);
+            const float* xs = rf_row + (nl - base);
+            for (int k = 0; k < taps; ++k) {
+                const int i = off + k * step;
+                acc = fma(fma(eta, fd.dwin[i], fd.win[i]), (double)xs[-k], acc);
+            }
+        }
+        {
+            const double idx = (scale - frac) * ntab;
+            const int off = (int)idx;
+            const double eta = idx - (double)off;
+            const int taps = min(n_file - n - 1, (nwin - off) / step);
+            const float* xs = rf_row + (nl + 1 - base);
+            for (int k = 0; k < taps; ++k) {
+                const int i = off + k * step;
+                acc = fma(fma(eta, fd.dwin[i], fd.win[i]), (double)xs[k], acc);
+            }
+        }
+        orow[m] = (float)acc;
+    }
+}
+
+// The caller (si_cut_rate) checked every argument, fd.cap * 4 <= 64 KB and C <= 65535 among them.
+int si_launch_cut_rate(si_ctx* ctx, const void* x, bool pcm16, int n_file, const int32_t* start, int C, int L, const SiFeed& fd, float* out,
+                       hipStream_t st) {
+    if (C <= 0 || L <= 0) return SI_OK;
+    const size_t lds = (size_t)fd.cap * sizeof(float);
+    const dim3 grid((L + RF_TILE - 1) / RF_TILE, C);
+    const double outs = (double)C * L;
+    si_prof_begin(ctx, "cut_rate", outs * 8.0 * fd.H, outs * 4.0 + (double)grid.x * C * fd.cap * (pcm16 ? 2.0 : 4.0), st);
+    if (pcm16)
+        cut_rate_kernel<int16_t><<<grid, 256, lds, st>>>(static_cast<const int16_t*>(x), n_file, start, L, fd, out);
+    else
+        cut_rate_kernel<float><<<grid, 256, lds, st>>>(static_cast<const float*>(x), n_file, start, L, fd, out);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}

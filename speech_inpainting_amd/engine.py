@@ -583,17 +583,19 @@ class InpaintingEngine:
                 gain = self.ctx.wave_peak(w22, tb["tab22"]) / 0.95
                 self.ctx.patch_regions(wave22, self._region_table(cb, plan, own22), gen, gain, patched, out.get("patched_pcm"))
 
-        out.update(self._recording_passes(wave22, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write))
+        cut = lambda starts, L: self.ctx.cut_clips(wave22, starts, L)
+        out.update(self._recording_passes(wave22.numel(), cut, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write))
         return out
 
-    def _recording_passes(self, wave22: torch.Tensor, wave16: Optional[torch.Tensor], gaps, fade_frames: int, clip_frames: int,
+    def _recording_passes(self, N22: int, cut, wave16: Optional[torch.Tensor], gaps, fade_frames: int, clip_frames: int,
                           min_context: int, batch: int, write) -> Dict[str, object]:
-        """What patch_recording and patch_file share: the context plan of a recording wave22 (N22,) on the device and, per batch of
-        at most `batch` contexts, the cut, the one multi-gap pass with every gap the clips hold masked, and the labels of the own
-        gaps.  write(cb, tb, res, w22, L22) -- the contexts of the pass, their gap tables, the pass's result (vocode=False), the cut
+        """What patch_recording and patch_file share: the context plan of a recording of N22 samples at 22.05 kHz and, per batch of
+        at most `batch` contexts, the cut -- cut(starts, L22) -> the (B, L22) clips that start at those 22.05 kHz samples, on the
+        device --, the one multi-gap pass with every gap the clips hold masked, and the labels of the own gaps.
+        write(cb, tb, res, w22, L22) -- the contexts of the pass, their gap tables, the pass's result (vocode=False), the cut
         22.05 kHz clips (B, L22) -- plans the generator windows of the own gaps, runs the generator over them and writes the blended
         samples.  -> contexts, labels, label_off."""
-        N22, clip_frames, batch = wave22.numel(), int(clip_frames), int(batch)
+        N22, clip_frames, batch = int(N22), int(clip_frames), int(batch)
         n_rec = N22 // 441
         whole = n_rec <= clip_frames                                   # one context: the whole recording, with its true sample counts
         L22 = N22 if whole else clip_frames * 441
@@ -610,7 +612,7 @@ class InpaintingEngine:
         for i in range(0, len(ctxs), batch):
             cb = ctxs[i:i + batch]
             B = len(cb)
-            w22 = self.ctx.cut_clips(wave22, [441 * c["start"] for c in cb], L22)
+            w22 = cut([441 * c["start"] for c in cb], L22)
             w16 = self.resample(w22, 22050, 16000) if wave16 is None else self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16)
             tb = self.gap_tables([c["own"] + c["foreign"] for c in cb], [L16] * B, [L22] * B)
             res = self.predict_multigap_batch(w16, w22, None, tables=tb, vocode=False)
@@ -683,8 +685,20 @@ class InpaintingEngine:
         plan["rows"] = [(b, 441 * int(ctxs[b]["start"]) + w0 * hop, (w1 - w0) * hop, lim22[b]) for b, w0, w1 in plan["wins"]]
         return plan
 
+    def _feed_filter(self, sr: int) -> Dict[str, object]:
+        """audio.design_kaiser_best(sr, 22050, .) with win / dwin on the device (time_reg is not used): what si_cut_rate takes."""
+        from . import audio
+        key = ("feed", int(sr))
+        if key not in self._resamplers:
+            f = audio.design_kaiser_best(int(sr), 22050, 1)
+            f.pop("time_reg")
+            for k in ("win", "dwin"):
+                f[k] = torch.from_numpy(f[k]).to(self.device)
+            self._resamplers[key] = f
+        return self._resamplers[key]
+
     def patch_file(self, x, sr: int, gaps, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
-                   return_windows: bool = False) -> Dict[str, object]:
+                   return_windows: bool = False, feed: str = "recording") -> Dict[str, object]:
         """patch_recording for a file at ITS OWN sample rate and in its own sample type: x (n,) is the recording at `sr` Hz, fp32 in
         full-scale units or int16 PCM (tensor or array, host or device), gaps = (first frame, frame count) pairs on its 20 ms grid.
         The recording is resampled to 22.05 kHz here (`resample`) only to FEED the model; the contexts, the multi-gap passes and the
@@ -692,9 +706,17 @@ class InpaintingEngine:
         si_patch_rate launch per pass carries its samples to `sr` by band-limited interpolation at the exact time i * 22050 / sr and
         blends them into `patched`, a copy of x: every sample outside a cross-fade of fade_ms around a gap is x's, bit for bit.
         sr = 22050 is patch_recording itself, bit for bit.
+        feed="contexts"  feeds the model without that whole-file resample: per pass one si_cut_rate launch cuts the
+        context clips straight from x at its own rate and in its own sample type (an int16 file is read as int16), interpolating at
+        the exact time j * sr / 22050 with the file's real neighbours at the clip edges; nothing of the recording's length is
+        created but `patched`.  The clips differ from the slices of the whole-file resample by at most an fp32 rounding, except at
+        exactly-integer times and in the recording's last sample (4.17 (a), (b)); everything after the cut is the same code.
         -> patched (n,) in x's dtype, contexts, labels, label_off as patch_recording; return_windows=True adds passes: per pass its
-        contexts, gen (W, Lrow), gain (C,), table (RateTable) and plan.  No gaps: an exact copy, no model kernel launched."""
+        contexts, gen (W, Lrow), gain (C,), table (RateTable), plan and clips22 (the cut 22.05 kHz clips).  No gaps: an exact copy,
+        no model kernel launched."""
         self._need(head=True, codebook=True, what="patch_file")
+        if feed not in ("recording", "contexts"):
+            raise ValueError(f"patch_file: feed = {feed!r}: 'recording' or 'contexts'")
         sr, batch = int(sr), int(batch)
         P, Q = G.rate_ratio(sr)
         if batch <= 0:
@@ -705,9 +727,9 @@ class InpaintingEngine:
         n_file = x.numel()
         if n_file < 1 or n_file > 2 ** 31 - 1 - 2048:
             raise ValueError(f"patch_file: a file of {n_file} samples")
-        xf = x.to(torch.float32) / 32768.0 if pcm else x               # exact: 16 bits x 2^-15
         fade_f = G.file_fade(fade_ms, sr)
         if sr == 22050:
+            xf = x.to(torch.float32) / 32768.0 if pcm else x           # exact: 16 bits x 2^-15
             out = self.patch_recording(xf, gaps, fade=fade_f, clip_frames=clip_frames, min_context=min_context, batch=batch, pcm=pcm)
             if pcm:
                 out["patched"] = out.pop("patched_pcm")
@@ -721,7 +743,15 @@ class InpaintingEngine:
             if return_windows:
                 out["passes"] = passes
             return out
-        wave22 = self.resample(xf[None], sr, 22050)[0].contiguous()
+        if feed == "contexts":                                         # the clips alone, cut from x itself
+            fin = self._feed_filter(sr)
+            N22 = -(-n_file * P // Q)
+            cut = lambda starts, L: self.ctx.cut_rate(x, sr, starts, L, fin)
+        else:
+            xf = x.to(torch.float32) / 32768.0 if pcm else x           # exact: 16 bits x 2^-15
+            wave22 = self.resample(xf[None], sr, 22050)[0].contiguous()
+            N22 = wave22.numel()
+            cut = lambda starts, L: self.ctx.cut_clips(wave22, starts, L)
         filt = self._rate_filter(sr)
 
         def write(cb, tb, res, w22, L22):
@@ -734,21 +764,22 @@ class InpaintingEngine:
                 table = RateTable(plan["spans"], plan["rows"], G.region_chunks(plan["regions"]), len(cb), fade_f, self.device)
                 self.ctx.patch_rate(x, sr, table, gen, filt, patched, gain)
                 if return_windows:
-                    passes.append({"contexts": cb, "gen": gen, "gain": gain, "table": table, "plan": plan})
+                    passes.append({"contexts": cb, "gen": gen, "gain": gain, "table": table, "plan": plan, "clips22": w22})
 
         fade_frames = max(-(-fade_f * 50 // sr), 1)
-        out.update(self._recording_passes(wave22, None, gaps, fade_frames, clip_frames, min_context, batch, write))
+        out.update(self._recording_passes(N22, cut, None, gaps, fade_frames, clip_frames, min_context, batch, write))
         if return_windows:
             out["passes"] = passes
         return out
 
     def conceal_file(self, x, sr: int, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
                      merge_frames: Optional[int] = None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
-                     return_windows: bool = False) -> Dict[str, object]:
+                     return_windows: bool = False, feed: str = "recording") -> Dict[str, object]:
         """File in, repaired file out, at the file's own rate and in its own sample type: find_gaps on x itself, where a dropout is
         still exact zeros, then patch_file with the gaps it found.  The usable frames are those of the recording's 22.05 kHz length
         ceil(n * 22050 / sr) (`recording_frames`), and a gap longer than the planner's budget counts as long, as in conceal_recording.
         threshold is in x's own units, as find_gaps takes it: full scale for fp32, int16 steps for an int16 file.
+        feed: patch_file's ("recording" or "contexts").
         -> patch_file's dictionary + gaps + skipped.  With nothing found: an exact copy; only the detection kernels launched."""
         sr, clip_frames, min_context = int(sr), int(clip_frames), int(min_context)
         P, Q = G.rate_ratio(sr)
@@ -760,7 +791,7 @@ class InpaintingEngine:
         fade22 = -(-G.file_fade(fade_ms, sr) * P // Q)
         found = self.find_gaps(x, sr, threshold, min_ms, max_ms, pad_frames, merge_frames, fade22, n_rec, lim)
         out = self.patch_file(x, sr, found["gaps"], fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch,
-                              return_windows=return_windows)
+                              return_windows=return_windows, feed=feed)
         out["gaps"], out["skipped"] = found["gaps"], found["skipped"]
         return out
 

@@ -30,8 +30,9 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_debug_capture", "si_debug_size",
            "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
            "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
-           "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate"]
+           "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate"]
 SI_MAX_SPANS = 16
+CUT_RATE_TILE = 512                        # SI_CUT_RATE_TILE: consecutive outputs of one clip per workgroup of si_cut_rate
 
 
 class _F0EncStruct(C.Structure):
@@ -358,6 +359,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_patch_regions.argtypes = [vp, vp, i32, C.POINTER(RegionTableStruct), vp, i32, vp, vp, vp, vp]
     lib.si_quiet_runs.argtypes = [vp, vp, i32, i32, C.c_float, i32, vp, i32, vp, vp]
     lib.si_patch_rate.argtypes = [vp, vp, i32, i32, i32, C.POINTER(RateTableStruct), vp, i32, vp, C.POINTER(SincFilter), vp, vp]
+    lib.si_cut_rate.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, C.POINTER(SincFilter), vp, vp]
     lib.si_num_frames.argtypes = [vp, i32]
     lib.si_vocoder_samples.argtypes = [vp, i32, i32]
     lib.si_debug_capture.argtypes = [vp, C.c_char_p, vp, C.c_long]
@@ -677,6 +679,29 @@ class NativeContext:
         t = table.struct()
         self._check(self.lib.si_patch_rate(self._h, _ptr(orig), int(orig.dtype == torch.int16), min(orig.numel(), 2 ** 31 - 1), int(sr), C.byref(t), _ptr(gen),
                                            0 if gen is None else gen.shape[1], _ptr(gain), C.byref(f), _ptr(out), self._stream()), "si_patch_rate")
+
+    # ---- context clips cut at the file's own sample rate
+    def cut_rate(self, x: torch.Tensor, sr: int, starts, L: int, filt: dict, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x (n_file,) at `sr` Hz, fp32 or int16, a device view that may start anywhere + starts (host ints, 22.05 kHz samples) ->
+        (C, L) fp32: row c = samples [starts[c], starts[c] + L) of the recording's 22.05 kHz axis, interpolated at the exact time
+        j * sr / 22050 straight from the file's samples (si_cut_rate).  filt: audio.design_kaiser_best(sr, 22050, .) with win / dwin as
+        float64 device tensors.  A start table that leaves the recording's ceil(n_file * 22050 / sr) samples is refused before the
+        launch."""
+        assert x.is_cuda and x.dtype in (torch.float32, torch.int16) and x.dim() == 1 and x.is_contiguous()
+        host = np.ascontiguousarray(np.asarray(list(starts), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        Cn, L = host.size, int(L)
+        dev = torch.from_numpy(host).to(self.device, non_blocking=True) if Cn else None
+        if out is None:
+            out = torch.empty(Cn, max(L, 0), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * max(L, 0)
+        win, dwin = filt["win"], filt["dwin"]
+        assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
+        assert win.numel() == dwin.numel()
+        f = SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
+                       float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
+        self._check(self.lib.si_cut_rate(self._h, _ptr(x), int(x.dtype == torch.int16), min(x.numel(), 2 ** 31 - 1), int(sr), host.ctypes.data_as(C.c_void_p),
+                                         _ptr(dev), Cn, L, C.byref(f), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate")
+        return out
 
     # ---- dropout detection (DESIGN.md 4.15)
     def quiet_runs(self, x: torch.Tensor, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536, runs: Optional[torch.Tensor] = None,

@@ -19,6 +19,8 @@ min_ms: 5.0, max_ms: 400.0, pad_frames: 0}) beside `long:` and instead of `mask:
 printed and `gaps.json` is written beside the three waves.  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
 on the way out: the three waves keep the file's own rate and sample type (an int16 file stays int16), and patched.wav holds the file's
 own samples, bit for bit, outside the cross-fades (engine.patch_file).  A multi-channel file is refused there.
+With `feed: contexts` beside `rate: file` the recording is not resampled as a whole on the way in either: only the context clips
+are cut from it, at its own rate and in its own sample type (si_cut_rate); `feed: recording` is the default.
 
 Differences from the script, all outside the three replaced subsystems: no Whisper `Metrics` object is built (the
 script constructs it and never uses it, I_ea/predict.py:72-73), PNG plots are skipped, and the two `librosa.load` calls are one
@@ -380,7 +382,8 @@ def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str)
     for s, l in G.file_spans(gap_list, sr_file):
         masked[s:s + l] = 0                                                        # the file samples whose time lies in the gap's frames
     audio.write_wav(os.path.join(save_dir, "masked.wav"), masked, sr_file)
-    out = engine.patch_file(x, sr_file, gap_list, fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"])
+    out = engine.patch_file(x, sr_file, gap_list, fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"],
+                            feed=cfg.long_feed)
     labels, off = out["labels"].tolist(), out["label_off"]
     for k, (pos, lm) in enumerate(gap_list):
         print(f"Predicted codewords, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[k]:off[k + 1]])

@@ -6,10 +6,15 @@ device-synchronised wall clock per call:
   (b) the only way back there was: resample to 22.05 kHz, engine.patch_recording, engine.resample of the WHOLE result to 48 kHz,
       to_int16 -- which returns none of the file's own samples
 
-Both resample the recording to 22.05 kHz on the way in (that is outside this change).  Prints one line per repeat, the medians, how
-many samples of the file each variant changed, and -- from a separate, untimed run under the library's profiler -- the time of the
-patch_rate family beside resample_sinc's.
-usage: python tools/exp_rate.py [--repeats 5] [--minutes 10] [--gaps 60] [--sr 48000]"""
+  (c) engine.patch_file(x, 48000, gaps, feed="contexts"): as (a), but the model is fed by context clips cut straight
+      from the int16 file (one si_cut_rate per pass)
+
+(a) and (b) resample the whole recording to 22.05 kHz on the way in; (c) does not.  Prints the first (warm-up) call of each variant
+on its own line -- it includes building and uploading the filter tables, for (a) and (b) a float64 time table of the recording's
+length --, one line per repeat, the medians, how many samples of the file each variant changed, how many predicted labels differ between
+(a) and (c), and -- from separate, untimed runs -- the profiler's time of the cut_rate, patch_rate and resample_sinc families and the
+peak device memory (torch.cuda.max_memory_allocated above what is allocated before the call) per variant.
+usage: python tools/exp_rate.py [--repeats 5] [--minutes 10] [--gaps 60] [--sr 48000]      (sparse case: --minutes 60 --gaps 6)"""
 import argparse
 import os
 import statistics
@@ -52,6 +57,10 @@ def keep_rate():
     return eng.patch_file(x, sr, gaps, **KW)["patched"]
 
 
+def feed_contexts():
+    return eng.patch_file(x, sr, gaps, feed="contexts", **KW)["patched"]
+
+
 def round_trip():
     wave22 = eng.resample((x.to(torch.float32) / 32768.0)[None], sr, 22050)[0].contiguous()
     patched = eng.patch_recording(wave22, gaps, fade=110, **KW)["patched"]
@@ -66,27 +75,44 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-times = {"patch_file": [], "round_trip": []}
+VARIANTS = (("patch_file", keep_rate), ("feed_contexts", feed_contexts), ("round_trip", round_trip))
+times = {name: [] for name, _ in VARIANTS}
 for r in range(WARMUP + a.repeats):
-    order = (("patch_file", keep_rate), ("round_trip", round_trip)) if r % 2 == 0 else (("round_trip", round_trip), ("patch_file", keep_rate))
+    order = VARIANTS[r % 3:] + VARIANTS[:r % 3]                        # alternated: each variant takes each place in turn
     row = {}
     for name, fn in order:
         row[name], out = timed(fn)
         if r == WARMUP:
             print(f"{name}: {int((out != x[:out.numel()]).sum())} of {n} samples differ from the file's")
+        del out
     if r >= WARMUP:
         for k, v in row.items():
             times[k].append(v)
-        print(f"repeat {r - WARMUP}: patch_file {row['patch_file']:.1f} ms, round trip {row['round_trip']:.1f} ms")
+        print(f"repeat {r - WARMUP}: " + ", ".join(f"{k} {row[k]:.1f} ms" for k, _ in VARIANTS))
+    else:
+        print("first call (tables built and uploaded): " + ", ".join(f"{k} {row[k]:.1f} ms" for k, _ in VARIANTS))
 for k, v in times.items():
     print(f"median {k}: {statistics.median(v):.1f} ms over {len(v)} repeats")
 
-eng.ctx.profile_start(20000)
-keep_rate()
-prof = {e["name"]: e for e in eng.ctx.profile_stop()}
-for name in ("patch_rate", "resample_sinc"):
-    if name in prof:
-        print(f"profiled patch_file: {name} {prof[name]['launches']} launches, {prof[name]['ms']:.3f} ms")
+ra = eng.patch_file(x, sr, gaps, **KW)
+rc = eng.patch_file(x, sr, gaps, feed="contexts", **KW)
+print(f"feed=recording | feed=contexts: {int((ra['labels'] != rc['labels']).sum())} of {ra['labels'].numel()} predicted labels differ, "
+      f"{int((ra['patched'] != rc['patched']).sum())} of {n} samples of patched differ")
+del ra, rc
+for name, fn in VARIANTS:
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    print(f"peak device memory {name}: {(torch.cuda.max_memory_allocated() - before) / 2 ** 20:.1f} MiB above the {before / 2 ** 20:.1f} MiB held before the call")
+for label, fn in (("patch_file", keep_rate), ("feed_contexts", feed_contexts)):
+    eng.ctx.profile_start(20000)
+    fn()
+    prof = {e["name"]: e for e in eng.ctx.profile_stop()}
+    for name in ("cut_rate", "cut_clips", "patch_rate", "resample_sinc"):
+        if name in prof and prof[name]["launches"]:
+            print(f"profiled {label}: {name} {prof[name]['launches']} launches, {prof[name]['ms']:.3f} ms")
 eng.ctx.profile_start(20000)
 round_trip()
 prof = {e["name"]: e for e in eng.ctx.profile_stop()}
