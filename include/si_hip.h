@@ -35,6 +35,8 @@
  *                           brings back                                       I_ea/predict.py:79-80,203-207
  *   si_cut_rate          <- that resampling on the way in, for the context clips alone instead of the whole file (with si_cut_clips'
  *                           slicing)                                          I_ea/predict.py:79-80
+ *   si_quiet_runs_ch / si_cut_rate_ch / si_patch_rate_ch  <- the three above on an interleaved multi-channel file, channel by channel,
+ *                           where the script mixes its input down to one channel on load      I_ea/predict.py:79
  *   si_load_weights      <- model.load_state_dict / generator.load_state_dict + remove_weight_norm + ApplyKmeans
  *                           I_ea/predict.py:117-122,149 ; I_ea/hifi_gan/models.py:125-132 ; I_ea/dataset/km_label.py:12-24
  *
@@ -666,6 +668,36 @@ int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int s
 #define SI_CUT_RATE_TILE 512
 int si_cut_rate(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_start, const int32_t* start, int C, int L,
                 const si_sinc_filter* filt, float* out, si_stream_t stream);
+
+/* ---- Interleaved multi-channel files ----------------------------------------------------------------------------------
+ * The reference's script mixes its input down to one channel on load (librosa.load, I_ea/predict.py:79).  The three calls below serve a
+ * file as a WAV stores it: x is (n, channels) INTERLEAVED, element i * channels + c is channel c at sample time i, 1 <= channels <=
+ * SI_MAX_CHANNELS.  n, n_file, runs, spans, chunks, fades and starts count SAMPLE TIMES and obey the mono limits (n <= 2^31 - 1 - 2048);
+ * n * channels may pass 2^31, every element offset is 64-bit.  Each channel is a mono recording: whatever a call computes for channel c
+ * is, byte for byte, what its mono sibling computes on the de-interleaved channel, and no de-interleaved copy is made.
+ *
+ * si_quiet_runs_ch: si_quiet_runs with sample time i quiet iff |x[i * channels + channel]| <= threshold (0 <= channel < channels), or,
+ * for channel = -1, iff EVERY channel's element is (a joint dropout).  NaN, -0.0, -32768 and "past n is loud" as si_quiet_runs; the same
+ * sorted (start, len) rows in sample times, the total in n_runs, max_runs = 0 counts only; the same input gives the same bytes.  With
+ * channels = 1 (channel 0 or -1) the output bytes are si_quiet_runs'.  SI_EINVAL before any launch, naming the argument, for everything
+ * si_quiet_runs refuses, channels outside 1 .. SI_MAX_CHANNELS, and channel outside [-1, channels).
+ *
+ * si_cut_rate_ch: si_cut_rate reading channel `channel` of the interleaved file x (n_file sample times).  A file sample time outside
+ * [0, n_file) does not exist: it is never the neighbouring channel's element.  SI_EINVAL before any launch, naming the argument, for
+ * everything si_cut_rate refuses, channels outside 1 .. SI_MAX_CHANNELS, and channel outside [0, channels).
+ *
+ * si_patch_rate_ch: si_patch_rate whose spans and chunks are sample times of channel `channel`; orig and out are interleaved, (n_file,
+ * channels) of the same type.  Only elements i * channels + channel of sample times i with non-zero weight are written: the other
+ * channels, and this channel outside its regions, keep what the caller put there.  The table may name windows and contexts that none of
+ * its spans use (another channel's rows of gen and entries of gain, when the channels share a pass).  SI_EINVAL before any launch,
+ * naming the entry, for everything si_patch_rate refuses, channels outside 1 .. SI_MAX_CHANNELS, and channel outside [0, channels). */
+#define SI_MAX_CHANNELS 8
+int si_quiet_runs_ch(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, float threshold, int min_len, int32_t* runs,
+                     int max_runs, int32_t* n_runs, si_stream_t stream);
+int si_cut_rate_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr, const int32_t* host_start,
+                   const int32_t* start, int C, int L, const si_sinc_filter* filt, float* out, si_stream_t stream);
+int si_patch_rate_ch(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int channels, int channel, int sr, const si_rate_table* table,
+                     const float* gen, int Lrow, const float* gain, const si_sinc_filter* filt, void* out, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

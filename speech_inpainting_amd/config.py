@@ -64,6 +64,9 @@ class PredictConfig:
                                   # to feed the model) or "contexts" (only the context clips are, straight from the file: DESIGN.md 4.17)
     detect: Optional[dict] = None  # optional `detect:` mapping ({threshold: 0.0, min_ms: 5.0, max_ms: 400.0, pad_frames: 0}): the gaps are
                                    # found in the file itself (engine.find_gaps) instead of given as `mask:` / `masks:`; needs `long:`
+    detect_channels: str = "each"  # `channels:` inside `detect:` (needs long: {rate: file}), for a multi-channel file: "each" (default:
+                                   # every channel is scanned and repaired on its own) or "joint" (a gap is where ALL channels are
+                                   # quiet, and is repaired in all of them: DESIGN.md 4.18)
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -158,7 +161,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
             if long_cfg["batch"] < 1 or long_cfg["clip_s"] <= 2 * long_cfg["context_s"]:
                 raise ValueError(f"{path}: `long:` needs batch >= 1 and clip_s > 2 * context_s, got {long_cfg}")
-        detect_cfg = None
+        detect_cfg, detect_channels = None, "each"
         if "detect" in data:
             dm = data["detect"] if data["detect"] is not None else {}
             if not isinstance(dm, dict):
@@ -169,9 +172,17 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             if "mask" in data or "masks" in data:
                 raise ValueError(f"{path}: give either `detect:` (the gaps are found) or `mask:` / `masks:` (the gaps are given), not both")
             detect_cfg = {"threshold": 0.0, "min_ms": 5.0, "max_ms": 400.0, "pad_frames": 0}
+            dm = dict(dm)
+            if "channels" in dm:
+                detect_channels = dm.pop("channels")
+                if detect_channels not in ("each", "joint"):
+                    raise ValueError(f"{path}: detect.channels = {detect_channels!r}: each (the default: every channel is scanned and repaired on its "
+                                     f"own) or joint (a gap is where all channels are quiet)")
+                if long_rate != "file":
+                    raise ValueError(f"{path}: detect.channels needs `long: {{rate: file}}` (at rate: {long_rate} the file is mixed down to one channel)")
             for key, val in dm.items():
                 if key not in detect_cfg:
-                    raise ValueError(f"{path}: unknown key `{key}` in `detect:` (it takes threshold, min_ms, max_ms, pad_frames)")
+                    raise ValueError(f"{path}: unknown key `{key}` in `detect:` (it takes threshold, min_ms, max_ms, pad_frames, channels)")
                 detect_cfg[key] = int(val) if key == "pad_frames" else float(val)
                 if not detect_cfg[key] >= 0:
                     raise ValueError(f"{path}: detect.{key} = {detect_cfg[key]} is negative")
@@ -190,7 +201,8 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_type=str(data["hubert_model"]["type"]),
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
-            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, detect=detect_cfg)
+            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, detect=detect_cfg,
+            detect_channels=detect_channels)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

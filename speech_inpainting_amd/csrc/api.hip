@@ -2095,143 +2095,180 @@ int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_ta
 }
 
 // ---- repair at the file's own sample rate
-int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int sr, const si_rate_table* table, const float* gen, int Lrow,
-                  const float* gain, const si_sinc_filter* filt, void* out, si_stream_t stream) {
+// The mono entry points and their interleaved siblings share one validation each: `fn` names the entry in the message;
+// inter = false is the mono call (its own kernel; channels and channel are not read), inter = true the interleaved one, with n / n_file
+// counting sample times.
+#define SI_FAIL_FN(fmt, ...) si_fail(ctx, SI_EINVAL, "%s: " fmt, fn, ##__VA_ARGS__)
+
+static int si_check_channels(si_ctx* ctx, const char* fn, int channels, int channel, int lowest) {
+    if (channels < 1 || channels > SI_MAX_CHANNELS) return SI_FAIL_FN("channels = %d, outside 1 .. SI_MAX_CHANNELS = %d", channels, SI_MAX_CHANNELS);
+    if (channel < lowest || channel >= channels) return SI_FAIL_FN("channel = %d, outside %d .. %d", channel, lowest, channels - 1);
+    return SI_OK;
+}
+
+static int patch_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* orig, int is_pcm16, int n_file, int channels, int channel, int sr,
+                           const si_rate_table* table, const float* gen, int Lrow, const float* gain, const si_sinc_filter* filt, void* out,
+                           si_stream_t stream) {
     if (!ctx) return SI_EINVAL;
-    if (!orig || !out || n_file <= 0) return si_fail(ctx, SI_EINVAL, "si_patch_rate: NULL / empty argument");
-    if (orig == out) return si_fail(ctx, SI_EINVAL, "si_patch_rate: out is orig (orig is read while out is written)");
-    if (sr < 4000 || sr > 192000) return si_fail(ctx, SI_EINVAL, "si_patch_rate: sr = %d Hz, outside 4000 .. 192000", sr);
-    if (sr == 22050) return si_fail(ctx, SI_EINVAL, "si_patch_rate: sr = 22050 Hz is the generator's own rate: that file is si_patch_regions'");
-    if ((long)n_file > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_patch_rate: a file of %d samples, at most %ld", n_file, SI_MAX_REC);
+    if (inter && si_check_channels(ctx, fn, channels, channel, 0) != SI_OK) return SI_EINVAL;
+    if (!orig || !out || n_file <= 0) return SI_FAIL_FN("NULL / empty argument");
+    if (orig == out) return SI_FAIL_FN("out is orig (orig is read while out is written)");
+    if (sr < 4000 || sr > 192000) return SI_FAIL_FN("sr = %d Hz, outside 4000 .. 192000", sr);
+    if (sr == 22050) return SI_FAIL_FN("sr = 22050 Hz is the generator's own rate: that file is si_patch_regions'");
+    if ((long)n_file > SI_MAX_REC) return SI_FAIL_FN("a file of %d samples, at most %ld", n_file, SI_MAX_REC);
     long ga = 22050, gb = sr;
     while (gb) { const long r = ga % gb; ga = gb; gb = r; }
     const long P = 22050 / ga, Qr = sr / ga;
     const long N22 = ((long)n_file * P + Qr - 1) / Qr;              // the recording's samples on the 22.05 kHz axis, ceil(n_file P / Q)
-    if (N22 > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_patch_rate: %d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
+    if (N22 > SI_MAX_REC) return SI_FAIL_FN("%d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
     const si_sinc_filter* f = filt;
-    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return si_fail(ctx, SI_EINVAL, "si_patch_rate: si_sinc_filter size mismatch");
+    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return SI_FAIL_FN("si_sinc_filter size mismatch");
     if (!f->win || !f->dwin || f->nwin < 2 || f->num_table < 1 || f->step < 1 || !(f->scale > 0.0 && f->scale <= 1.0))
-        return si_fail(ctx, SI_EINVAL, "si_patch_rate: bad filter table (nwin %d, num_table %d, step %d, scale %g)", f->nwin, f->num_table, f->step, f->scale);
+        return SI_FAIL_FN("bad filter table (nwin %d, num_table %d, step %d, scale %g)", f->nwin, f->num_table, f->step, f->scale);
     const long H = ((long)f->nwin + f->step - 1) / f->step;
     const long row_cap = 2047 * P / Qr + 2 + 2 * H;
     if (row_cap * (long)sizeof(float) > 65536)
-        return si_fail(ctx, SI_EINVAL, "si_patch_rate: bad filter table: %ld taps per wing at %d Hz need %ld staged samples per chunk, at most 16384", H, sr, row_cap);
+        return SI_FAIL_FN("bad filter table: %ld taps per wing at %d Hz need %ld staged samples per chunk, at most 16384", H, sr, row_cap);
     const si_rate_table* t = table;
-    if (!t || t->struct_size != (int32_t)sizeof(si_rate_table)) return si_fail(ctx, SI_EINVAL, "si_patch_rate: si_rate_table size mismatch");
-    if (t->fade < 0 || (long)t->fade + n_file > 0x7fffffffL) return si_fail(ctx, SI_EINVAL, "si_patch_rate: fade of %d samples is negative or too long", t->fade);
+    if (!t || t->struct_size != (int32_t)sizeof(si_rate_table)) return SI_FAIL_FN("si_rate_table size mismatch");
+    if (t->fade < 0 || (long)t->fade + n_file > 0x7fffffffL) return SI_FAIL_FN("fade of %d samples is negative or too long", t->fade);
     const int C = t->num_contexts, W = t->num_windows, K = t->num_spans, Q = t->num_chunks, fade = t->fade;
     if (C < 0 || W < 0 || K < 0 || Q < 0)
-        return si_fail(ctx, SI_EINVAL, "si_patch_rate: rate table with %d contexts / %d windows / %d spans / %d chunks", C, W, K, Q);
-    if (fade > 0 && K > 0 && !t->ramp) return si_fail(ctx, SI_EINVAL, "si_patch_rate: rate table with NULL ramp");
+        return SI_FAIL_FN("rate table with %d contexts / %d windows / %d spans / %d chunks", C, W, K, Q);
+    if (fade > 0 && K > 0 && !t->ramp) return SI_FAIL_FN("rate table with NULL ramp");
     if (W > 0 && (!t->host_win_ctx || !t->host_win_start || !t->host_win_len || !t->host_win_lim || !t->win_ctx || !t->win_start || !t->win_len ||
                   !t->win_lim || !gen || Lrow <= 0))
-        return si_fail(ctx, SI_EINVAL, "si_patch_rate: %d windows but NULL window arrays / generator rows", W);
+        return SI_FAIL_FN("%d windows but NULL window arrays / generator rows", W);
     if (K > 0 && (!t->host_start || !t->host_len || !t->host_span_win || !t->host_span_lim || !t->start || !t->len || !t->span_win || !t->span_lim))
-        return si_fail(ctx, SI_EINVAL, "si_patch_rate: %d spans but NULL span arrays", K);
+        return SI_FAIL_FN("%d spans but NULL span arrays", K);
     if (Q > 0 && (!t->host_chunk || !t->host_k0 || !t->host_k1 || !t->chunk || !t->k0 || !t->k1))
-        return si_fail(ctx, SI_EINVAL, "si_patch_rate: %d chunks but NULL chunk arrays", Q);
+        return SI_FAIL_FN("%d chunks but NULL chunk arrays", Q);
     for (int w = 0; w < W; ++w) {
         const long c = t->host_win_ctx[w], s = t->host_win_start[w], l = t->host_win_len[w], lim = t->host_win_lim[w];
-        if (c < 0 || c >= C) return si_fail(ctx, SI_EINVAL, "si_patch_rate: window %d names context %ld of %d", w, c, C);
+        if (c < 0 || c >= C) return SI_FAIL_FN("window %d names context %ld of %d", w, c, C);
         if (s < 0 || l < 0 || l > Lrow || s + l > N22)
-            return si_fail(ctx, SI_EINVAL, "si_patch_rate: window %d = 22.05 kHz samples [%ld, +%ld) is outside the recording (%ld samples, rows of %d)", w, s, l,
+            return SI_FAIL_FN("window %d = 22.05 kHz samples [%ld, +%ld) is outside the recording (%ld samples, rows of %d)", w, s, l,
                            N22, Lrow);
         if (lim <= s || lim > N22)
-            return si_fail(ctx, SI_EINVAL, "si_patch_rate: window %d starts at 22.05 kHz sample %ld, its context's audio ends at %ld of %ld", w, s, lim, N22);
+            return SI_FAIL_FN("window %d starts at 22.05 kHz sample %ld, its context's audio ends at %ld of %ld", w, s, lim, N22);
     }
     for (int q = 0; q < Q; ++q) {
         const long c = t->host_chunk[q];
-        if (c < 0 || c * 2048 >= n_file) return si_fail(ctx, SI_EINVAL, "si_patch_rate: chunk entry %d names chunk %ld, at or past the file's %d samples", q, c, n_file);
+        if (c < 0 || c * 2048 >= n_file) return SI_FAIL_FN("chunk entry %d names chunk %ld, at or past the file's %d samples", q, c, n_file);
         if (q && c <= t->host_chunk[q - 1])
-            return si_fail(ctx, SI_EINVAL, "si_patch_rate: chunk entry %d names chunk %ld after chunk %d: not strictly increasing", q, c, t->host_chunk[q - 1]);
+            return SI_FAIL_FN("chunk entry %d names chunk %ld after chunk %d: not strictly increasing", q, c, t->host_chunk[q - 1]);
         if (t->host_k0[q] < 0 || t->host_k0[q] > t->host_k1[q] || t->host_k1[q] > K)
-            return si_fail(ctx, SI_EINVAL, "si_patch_rate: chunk entry %d walks spans [%d, %d) of %d", q, t->host_k0[q], t->host_k1[q], K);
+            return SI_FAIL_FN("chunk entry %d walks spans [%d, %d) of %d", q, t->host_k0[q], t->host_k1[q], K);
     }
     for (int k = 0; k < K; ++k) {
         const long s = t->host_start[k], l = t->host_len[k], lim = t->host_span_lim[k];
         if (s < 0 || l <= 0 || lim <= s || lim > n_file)
-            return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d = samples [%ld, +%ld) with lim %ld does not lie in the file's %d samples", k, s, l, lim, n_file);
+            return SI_FAIL_FN("span %d = samples [%ld, +%ld) with lim %ld does not lie in the file's %d samples", k, s, l, lim, n_file);
         if (k && s < (long)t->host_start[k - 1] + t->host_len[k - 1])
-            return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d starts at %ld, before span %d ends: unsorted or overlapping", k, s, k - 1);
+            return SI_FAIL_FN("span %d starts at %ld, before span %d ends: unsorted or overlapping", k, s, k - 1);
     }
     int q = 0;                                                     // the spans are sorted: the chunk list is walked (nearly) once
     for (int k = 0; k < K; ++k) {
         const long s = t->host_start[k], l = t->host_len[k], lim = t->host_span_lim[k];
         const int w = t->host_span_win[k];
-        if (w < 0 || w >= W) return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d names window %d of %d", k, w, W);
+        if (w < 0 || w >= W) return SI_FAIL_FN("span %d names window %d of %d", k, w, W);
         const long ws = t->host_win_start[w], we = ws + t->host_win_len[w], wlim = t->host_win_lim[w];
         if ((lim - 1) * P >= wlim * Qr)
-            return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d writes up to file sample %ld = 22.05 kHz sample %ld, its context's audio ends at %ld", k, lim,
+            return SI_FAIL_FN("span %d writes up to file sample %ld = 22.05 kHz sample %ld, its context's audio ends at %ld", k, lim,
                            (lim - 1) * P / Qr, wlim);
         const long ra = std::max(s - fade, 0L), rb = std::min(s + l + fade, lim);
         const long xa = std::max(ra * P / Qr - H, 0L), xb = std::min((rb - 1) * P / Qr + 1 + H, wlim);      // what the taps read inside [0, win_lim)
         if (xa < ws || xb > we)
-            return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d blends file samples [%ld, %ld) and reads 22.05 kHz samples [%ld, %ld), its window's row holds [%ld, %ld)",
+            return SI_FAIL_FN("span %d blends file samples [%ld, %ld) and reads 22.05 kHz samples [%ld, %ld), its window's row holds [%ld, %ld)",
                            k, ra, rb, xa, xb, ws, we);
         const long qa = ra / 2048, qb = (rb - 1) / 2048;
         while (q > 0 && t->host_chunk[q - 1] >= qa) --q;            // a region may start in the chunk its predecessor ended in
         for (long c = qa; c <= qb; ++c) {
             while (q < Q && t->host_chunk[q] < c) ++q;
             if (q >= Q || t->host_chunk[q] != c)
-                return si_fail(ctx, SI_EINVAL, "si_patch_rate: span %d blends samples [%ld, %ld), the chunk list lacks chunk %ld", k, ra, rb, c);
+                return SI_FAIL_FN("span %d blends samples [%ld, %ld), the chunk list lacks chunk %ld", k, ra, rb, c);
             if (k < t->host_k0[q] || k >= t->host_k1[q])
-                return si_fail(ctx, SI_EINVAL, "si_patch_rate: chunk entry %d (chunk %ld) walks spans [%d, %d) and omits span %d, which blends samples [%ld, %ld)",
+                return SI_FAIL_FN("chunk entry %d (chunk %ld) walks spans [%d, %d) and omits span %d, which blends samples [%ld, %ld)",
                                q, c, t->host_k0[q], t->host_k1[q], k, ra, rb);
         }
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     const SiRate rt{t->start, t->len, t->span_win, t->span_lim, t->win_ctx, t->win_start, t->win_len, t->win_lim, t->chunk, t->k0, t->k1, t->ramp, fade,
                     f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Qr, (int)H, (int)row_cap};
+    if (inter) return si_launch_patch_rate_ch(ctx, orig, is_pcm16 != 0, n_file, channels, channel, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
     return si_launch_patch_rate(ctx, orig, is_pcm16 != 0, n_file, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
 }
 
+int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int sr, const si_rate_table* table, const float* gen, int Lrow,
+                  const float* gain, const si_sinc_filter* filt, void* out, si_stream_t stream) {
+    return patch_rate_call(ctx, "si_patch_rate", false, orig, is_pcm16, n_file, 0, 0, sr, table, gen, Lrow, gain, filt, out, stream);
+}
+
+int si_patch_rate_ch(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int channels, int channel, int sr, const si_rate_table* table,
+                     const float* gen, int Lrow, const float* gain, const si_sinc_filter* filt, void* out, si_stream_t stream) {
+    return patch_rate_call(ctx, "si_patch_rate_ch", true, orig, is_pcm16, n_file, channels, channel, sr, table, gen, Lrow, gain, filt, out, stream);
+}
+
 // ---- context clips cut at the file's own sample rate
-int si_cut_rate(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_start, const int32_t* start, int C, int L,
-                const si_sinc_filter* filt, float* out, si_stream_t stream) {
+static int cut_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr,
+                         const int32_t* host_start, const int32_t* start, int C, int L, const si_sinc_filter* filt, float* out, si_stream_t stream) {
     if (!ctx) return SI_EINVAL;
-    if (sr < 4000 || sr > 192000) return si_fail(ctx, SI_EINVAL, "si_cut_rate: sr = %d Hz, outside 4000 .. 192000", sr);
-    if (sr == 22050) return si_fail(ctx, SI_EINVAL, "si_cut_rate: sr = 22050 Hz is the model's own rate: that file is si_cut_clips'");
-    if (n_file < 1) return si_fail(ctx, SI_EINVAL, "si_cut_rate: n_file = %d", n_file);
-    if ((long)n_file > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_cut_rate: n_file = %d samples, at most %ld", n_file, SI_MAX_REC);
+    if (inter && si_check_channels(ctx, fn, channels, channel, 0) != SI_OK) return SI_EINVAL;
+    if (sr < 4000 || sr > 192000) return SI_FAIL_FN("sr = %d Hz, outside 4000 .. 192000", sr);
+    if (sr == 22050) return SI_FAIL_FN("sr = 22050 Hz is the model's own rate: that file is si_cut_clips'");
+    if (n_file < 1) return SI_FAIL_FN("n_file = %d", n_file);
+    if ((long)n_file > SI_MAX_REC) return SI_FAIL_FN("n_file = %d samples, at most %ld", n_file, SI_MAX_REC);
     long ga = 22050, gb = sr;
     while (gb) { const long r = ga % gb; ga = gb; gb = r; }
     const long P = 22050 / ga, Qr = sr / ga;
     const long N22 = ((long)n_file * P + Qr - 1) / Qr;              // the recording's samples on the 22.05 kHz axis, ceil(n_file P / Q)
-    if (N22 > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_cut_rate: n_file = %d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
+    if (N22 > SI_MAX_REC) return SI_FAIL_FN("n_file = %d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
     const si_sinc_filter* f = filt;
-    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return si_fail(ctx, SI_EINVAL, "si_cut_rate: filt: si_sinc_filter size mismatch");
+    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return SI_FAIL_FN("filt: si_sinc_filter size mismatch");
     if (!f->win || !f->dwin || f->nwin < 2 || f->num_table < 1 || f->step < 1 || !(f->scale > 0.0 && f->scale <= 1.0))
-        return si_fail(ctx, SI_EINVAL, "si_cut_rate: filt: bad filter table (nwin %d, num_table %d, step %d, scale %g)", f->nwin, f->num_table, f->step, f->scale);
+        return SI_FAIL_FN("filt: bad filter table (nwin %d, num_table %d, step %d, scale %g)", f->nwin, f->num_table, f->step, f->scale);
     const long H = ((long)f->nwin + f->step - 1) / f->step;
     const long cap = (RF_TILE - 1) * Qr / P + 2 + 2 * H;            // file samples one tile stages in LDS: 5 581 at 192 kHz with kaiser_best, of 160 KB
     if (cap * (long)sizeof(float) > 65536)
-        return si_fail(ctx, SI_EINVAL, "si_cut_rate: filt: bad filter table: %ld taps per wing at %d Hz need %ld staged samples per tile, at most 16384", H, sr, cap);
-    if (C < 0 || C > 65535) return si_fail(ctx, SI_EINVAL, "si_cut_rate: C = %d clips in one call, 0 .. 65535 (the launch grid's second dimension)", C);
-    if (L < 1) return si_fail(ctx, SI_EINVAL, "si_cut_rate: L = %d", L);
+        return SI_FAIL_FN("filt: bad filter table: %ld taps per wing at %d Hz need %ld staged samples per tile, at most 16384", H, sr, cap);
+    if (C < 0 || C > 65535) return SI_FAIL_FN("C = %d clips in one call, 0 .. 65535 (the launch grid's second dimension)", C);
+    if (L < 1) return SI_FAIL_FN("L = %d", L);
     if (C == 0) return SI_OK;                                       // nothing is read or written
     if (!x || !out || !host_start || !start)
-        return si_fail(ctx, SI_EINVAL, "si_cut_rate: %s is NULL", !x ? "x" : !out ? "out" : !host_start ? "host_start" : "start");
+        return SI_FAIL_FN("%s is NULL", !x ? "x" : !out ? "out" : !host_start ? "host_start" : "start");
     for (int c = 0; c < C; ++c) {
         const long s = host_start[c];
         if (s < 0 || s + L > N22)
-            return si_fail(ctx, SI_EINVAL, "si_cut_rate: start[%d]: clip = 22.05 kHz samples [%ld, %ld) is outside the recording's %ld samples", c, s, s + L, N22);
+            return SI_FAIL_FN("start[%d]: clip = 22.05 kHz samples [%ld, %ld) is outside the recording's %ld samples", c, s, s + L, N22);
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     const SiFeed fd{f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Qr, (int)H, (int)cap, (int)N22};
+    if (inter) return si_launch_cut_rate_ch(ctx, x, is_pcm16 != 0, n_file, channels, channel, start, C, L, fd, out, static_cast<hipStream_t>(stream));
     return si_launch_cut_rate(ctx, x, is_pcm16 != 0, n_file, start, C, L, fd, out, static_cast<hipStream_t>(stream));
 }
 
+int si_cut_rate(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_start, const int32_t* start, int C, int L,
+                const si_sinc_filter* filt, float* out, si_stream_t stream) {
+    return cut_rate_call(ctx, "si_cut_rate", false, x, is_pcm16, n_file, 0, 0, sr, host_start, start, C, L, filt, out, stream);
+}
+
+int si_cut_rate_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr, const int32_t* host_start,
+                   const int32_t* start, int C, int L, const si_sinc_filter* filt, float* out, si_stream_t stream) {
+    return cut_rate_call(ctx, "si_cut_rate_ch", true, x, is_pcm16, n_file, channels, channel, sr, host_start, start, C, L, filt, out, stream);
+}
+
 // ---- dropout detection
-int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
-                  si_stream_t stream) {
+static int quiet_runs_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n, int channels, int channel, float threshold, int min_len,
+                           int32_t* runs, int max_runs, int32_t* n_runs, si_stream_t stream) {
     if (!ctx) return SI_EINVAL;
-    if (!x) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: x is NULL");
-    if (!n_runs) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: n_runs is NULL");
-    if (max_runs < 0) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: max_runs = %d is negative", max_runs);
-    if (!runs && max_runs > 0) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: runs is NULL with max_runs = %d", max_runs);
-    if (n < 1 || (long)n > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: n = %d samples, outside 1 .. %ld", n, SI_MAX_REC);
-    if (!(threshold >= 0.f)) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: threshold = %g is negative or NaN", (double)threshold);
-    if (min_len < 1) return si_fail(ctx, SI_EINVAL, "si_quiet_runs: min_len = %d samples, at least 1", min_len);
+    if (inter && si_check_channels(ctx, fn, channels, channel, -1) != SI_OK) return SI_EINVAL;
+    if (!x) return SI_FAIL_FN("x is NULL");
+    if (!n_runs) return SI_FAIL_FN("n_runs is NULL");
+    if (max_runs < 0) return SI_FAIL_FN("max_runs = %d is negative", max_runs);
+    if (!runs && max_runs > 0) return SI_FAIL_FN("runs is NULL with max_runs = %d", max_runs);
+    if (n < 1 || (long)n > SI_MAX_REC) return SI_FAIL_FN("n = %d samples, outside 1 .. %ld", n, SI_MAX_REC);
+    if (!(threshold >= 0.f)) return SI_FAIL_FN("threshold = %g is negative or NaN", (double)threshold);
+    if (min_len < 1) return SI_FAIL_FN("min_len = %d samples, at least 1", min_len);
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t need = si_detect_scratch_bytes(n);
     if (need > ctx->det_scratch_cap) {                                 // (a context is single-threaded and its calls stream-ordered by contract)
@@ -2240,8 +2277,23 @@ int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float thresho
         SI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx->det_scratch), cap));
         ctx->det_scratch_cap = cap;
     }
+    if (inter)
+        return si_launch_quiet_runs_ch(ctx, x, is_pcm16 != 0, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch,
+                                       static_cast<hipStream_t>(stream));
     return si_launch_quiet_runs(ctx, x, is_pcm16 != 0, n, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch, static_cast<hipStream_t>(stream));
 }
+
+int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
+                  si_stream_t stream) {
+    return quiet_runs_call(ctx, "si_quiet_runs", false, x, is_pcm16, n, 0, 0, threshold, min_len, runs, max_runs, n_runs, stream);
+}
+
+int si_quiet_runs_ch(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, float threshold, int min_len, int32_t* runs,
+                     int max_runs, int32_t* n_runs, si_stream_t stream) {
+    return quiet_runs_call(ctx, "si_quiet_runs_ch", true, x, is_pcm16, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, stream);
+}
+
+#undef SI_FAIL_FN
 
 }  // extern "C"
 

@@ -354,6 +354,9 @@ size_t si_detect_scratch_bytes(int n);
 // *n_runs = how many there are (all of them, whether or not they fit); arguments validated by the caller, scratch 16-byte aligned
 int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
                          char* scratch, hipStream_t st);
+// the same for an interleaved x (n sample times of `channels` channels): channel c >= 0 alone, or all jointly (c < 0)
+int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
+                            int max_runs, int32_t* n_runs, char* scratch, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // repair at the file's own sample rate (rate_kernels.hip)
@@ -373,6 +376,9 @@ struct SiRate {
 // int16 when pcm16), the rest untouched; arguments validated by the caller
 int si_launch_patch_rate(si_ctx* ctx, const void* orig, bool pcm16, int n_file, const SiRate& rt, int num_chunks, const float* gen, int Lrow,
                          const float* gain, void* out, hipStream_t st);
+// the same into channel `channel` of an interleaved orig / out (n_file sample times of ch channels)
+int si_launch_patch_rate_ch(si_ctx* ctx, const void* orig, bool pcm16, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
+                            const float* gen, int Lrow, const float* gain, void* out, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // context clips cut at the file's own rate (rate_feed_kernels.hip)
@@ -388,6 +394,9 @@ struct SiFeed {
 // exact time j Q / P; start device int32 (C); arguments validated by the caller
 int si_launch_cut_rate(si_ctx* ctx, const void* x, bool pcm16, int n_file, const int32_t* start, int C, int L, const SiFeed& fd, float* out,
                        hipStream_t st);
+// the same from channel `channel` of an interleaved x (n_file sample times of ch channels)
+int si_launch_cut_rate_ch(si_ctx* ctx, const void* x, bool pcm16, int n_file, int ch, int channel, const int32_t* start, int C, int L,
+                          const SiFeed& fd, float* out, hipStream_t st);
 
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16

@@ -2,6 +2,7 @@
 // samples in a recording of up to 2^31 - 1 - 2048 samples, as (start, len) rows sorted by start.  One pass over the samples, the rest
 // over one bit per sample and a few words per chunk of DT_CHUNK samples:
 //   detect_bits_kernel     the quiet bits of a chunk (one byte per thread: 8 consecutive samples) + the chunk's summary {lead, trail}
+//   detect_bits_ch_kernel  the same pass 1 over an INTERLEAVED recording: one channel of it, or all of them jointly
 //   detect_carry_kernel    carry[c] = the length of the quiet run that ends exactly in front of chunk c (a segmented scan, one workgroup)
 //   detect_runs_kernel     <false>: the qualifying runs that END in each chunk, counted; <true>: written at offset[c] + rank
 //   detect_offsets_kernel  the exclusive scan of the counts (one workgroup) and the total, a plain store
@@ -47,6 +48,24 @@ __device__ __forceinline__ int dt_block_excl(int v, int ident, int* sw, int& tot
 __device__ __forceinline__ bool dt_quiet(float v, float thr) { return __builtin_fabsf(v) <= thr; }
 __device__ __forceinline__ bool dt_quiet(int16_t v, float thr) { const int a = v; return (float)(a < 0 ? -a : a) <= thr; }
 
+// What pass 1 leaves per chunk, from the quiet bits b of this thread's eight samples (bits at and past len are 0, so the first loud bit
+// is at most len): the bitmap byte, and through two workgroup scans the chunk's lead and trail.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void dt_store_chunk(unsigned b, int c, int len, uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead,
+                                               int32_t* __restrict__ trail, int* sw) {
+    const int t = threadIdx.x;
+    bitmap[(size_t)c * 256 + t] = (uint8_t)b;
+    const unsigned loud = ~b & 0xffu;
+    const int k = len - t * 8;
+    const unsigned inside = loud & (k >= 8 ? 0xffu : k <= 0 ? 0u : (1u << k) - 1u);
+    int first, last;
+    (void)dt_block_excl(loud ? t * 8 + __builtin_ctz(loud) : DT_CHUNK, DT_CHUNK, sw, first, DtMin());
+    (void)dt_block_excl(inside ? t * 8 + 31 - __builtin_clz(inside) : -1, -1, sw, last, DtMax());
+    if (t == 0) {
+        lead[c] = first;
+        trail[c] = len - 1 - last;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ pass 1: bits + summary
 // grid (chunks), 256 threads.  Thread t owns samples [c0 + 8 t, c0 + 8 t + 8): 32 bytes of fp32 (two 16-byte loads) or 16 bytes of int16
 // (one).  Callers pass views, so the base is generally off the 16-byte grid; c0 * sizeof(T) is a multiple of 16, so the alignment is the
@@ -83,18 +102,47 @@ __global__ __launch_bounds__(256) void detect_bits_kernel(const T* __restrict__ 
     unsigned b = 0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) b |= (t * 8 + j < len && dt_quiet(u.e[j], thr)) ? 1u << j : 0u;
-    bitmap[(size_t)c * 256 + t] = (uint8_t)b;
-    // bits at and past len are 0, so the first loud bit is at most len
-    const unsigned loud = ~b & 0xffu;
-    const int k = len - t * 8;
-    const unsigned inside = loud & (k >= 8 ? 0xffu : k <= 0 ? 0u : (1u << k) - 1u);
-    int first, last;
-    (void)dt_block_excl(loud ? t * 8 + __builtin_ctz(loud) : DT_CHUNK, DT_CHUNK, sw, first, DtMin());
-    (void)dt_block_excl(inside ? t * 8 + 31 - __builtin_clz(inside) : -1, -1, sw, last, DtMax());
-    if (t == 0) {
-        lead[c] = first;
-        trail[c] = len - 1 - last;
+    dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
+}
+
+// The same pass over an INTERLEAVED recording: n sample times of ch channels, element i ch + channel.  A chunk is
+// DT_CHUNK sample times = DT_CHUNK ch consecutive elements from element c0 ch on (a 64-bit offset; inside the chunk an int).
+//   channel >= 0   sample time i is quiet iff that channel's element is: lane t loads times t, t + 256, ... (a stride of ch elements,
+//                  which is what one channel of an interleaved file costs) and leaves one byte per time in LDS
+//   channel  < 0   JOINT: quiet iff EVERY channel's element is.  Lane t loads elements t, t + 256, ... of the chunk -- consecutive
+//                  lanes, consecutive elements, whatever ch is and wherever the base lies -- and leaves one byte per element in LDS;
+//                  the thread that owns eight sample times then ANDs their 8 ch bytes (16 KB of LDS at ch = 8)
+// Times at and past n are loud.  From the byte on this is detect_bits_kernel: the same bitmap, lead and trail (dt_store_chunk).
+template <typename T>
+__global__ __launch_bounds__(256) void detect_bits_ch_kernel(const T* __restrict__ x, int n, int ch, int channel, float thr,
+                                                             uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    __shared__ uint8_t sq[DT_CHUNK * SI_MAX_CHANNELS];
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    const T* __restrict__ xc = x + (size_t)c0 * ch;
+    unsigned b = 0;
+    if (channel < 0) {
+        const int cnt = len * ch;
+        for (int e = t; e < DT_CHUNK * ch; e += 256) sq[e] = (e < cnt && dt_quiet(xc[e], thr)) ? 1 : 0;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            unsigned q = 1;
+            for (int k = 0; k < ch; ++k) q &= sq[(t * 8 + j) * ch + k];
+            b |= q << j;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = j * 256 + t;
+            sq[i] = (i < len && dt_quiet(xc[(size_t)i * ch + channel], thr)) ? 1 : 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b |= (unsigned)sq[t * 8 + j] << j;
     }
+    dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
 }
 
 // ------------------------------------------------------------------------------------------------ pass 2: carries
@@ -241,9 +289,11 @@ size_t si_detect_scratch_bytes(int n) {
     return chunks * 256 + 5 * ((chunks * sizeof(int32_t) + 15) & ~(size_t)15);
 }
 
-// The caller (si_quiet_runs) checked every argument.  scratch: si_detect_scratch_bytes(n) bytes, 16-byte aligned.
-int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
-                         char* scratch, hipStream_t st) {
+// The caller (si_quiet_runs, si_quiet_runs_ch) checked every argument.  scratch: si_detect_scratch_bytes(n) bytes, 16-byte aligned.
+// channels = 0: x is one channel of n samples (detect_bits_kernel); channels >= 1: x is interleaved, n sample times of `channels`
+// channels, and `channel` picks one of them or, below 0, all of them jointly (detect_bits_ch_kernel).  Passes 2 - 5 are the same launches.
+static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
+                     int32_t* n_runs, char* scratch, hipStream_t st) {
     const int chunks = (int)(((long)n + DT_CHUNK - 1) / DT_CHUNK);
     const size_t words = ((size_t)chunks * sizeof(int32_t) + 15) & ~(size_t)15;
     uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch);
@@ -255,9 +305,16 @@ int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float th
     int32_t* offset = reinterpret_cast<int32_t*>(p + 4 * words);
     const double bits = (double)chunks * 256.0, sums = (double)chunks * 4.0;
 
-    si_prof_begin(ctx, "detect_bits", 0.0, (double)n * (pcm16 ? 2.0 : 4.0) + bits + 2.0 * sums, st);
-    if (pcm16) detect_bits_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, thr, bitmap, lead, trail);
-    else detect_bits_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, thr, bitmap, lead, trail);
+    if (channels == 0) {
+        si_prof_begin(ctx, "detect_bits", 0.0, (double)n * (pcm16 ? 2.0 : 4.0) + bits + 2.0 * sums, st);
+        if (pcm16) detect_bits_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, thr, bitmap, lead, trail);
+        else detect_bits_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, thr, bitmap, lead, trail);
+    } else {
+        // a single channel still moves the whole 32- or 64-byte sectors its elements lie in: counted as the chunk's elements either way
+        si_prof_begin(ctx, "detect_bits_ch", 0.0, (double)n * channels * (pcm16 ? 2.0 : 4.0) + bits + 2.0 * sums, st);
+        if (pcm16) detect_bits_ch_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, channels, channel, thr, bitmap, lead, trail);
+        else detect_bits_ch_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, channels, channel, thr, bitmap, lead, trail);
+    }
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
 
@@ -283,4 +340,14 @@ int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float th
         SI_HIP_CHECK(hipGetLastError());
     }
     return SI_OK;
+}
+
+int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
+                         char* scratch, hipStream_t st) {
+    return dt_launch(ctx, x, pcm16, n, 0, 0, thr, min_len, runs, max_runs, n_runs, scratch, st);
+}
+
+int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
+                            int max_runs, int32_t* n_runs, char* scratch, hipStream_t st) {
+    return dt_launch(ctx, x, pcm16, n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st);
 }

@@ -2,6 +2,7 @@
 //   cut_rate_kernel<float | int16_t>   per tile of 512 consecutive outputs of one clip: the file samples the tile's interpolation reads
 //                                      staged in LDS as fp32, then per output the two wings of the band-limited interpolation at the
 //                                      exact rational time j Q / P
+//   cut_rate_ch_kernel<float | int16_t>  the same tile read from one channel of an INTERLEAVED file: one shared body
 // It stands where `resample(file, sr, 22050)` over the whole recording + si_cut_clips would: that pass costs every 22.05 kHz sample of
 // the recording a 2 H-tap float64 sum, an fp32 copy of an int16 file, a 22.05 kHz copy of the recording and a float64 time table of its
 // length; this one computes the samples of the context clips and creates nothing of the recording's length.
@@ -25,9 +26,14 @@ __device__ __forceinline__ float rf_load(const int16_t* p) { return (float)*p * 
 // Plain stores, no atomics; each output is written once.  The C ABI validated the host copy of `start`; an output whose j lies outside
 // [0, N22) -- a device table that differs from the validated one -- is written as zero, and the staging loop reads the file only inside
 // [0, n_file): wrong output, not a fault.
+//
+// cut_rate_ch_kernel is the same workgroup reading channel `channel` of an INTERLEAVED file (n_file sample times of ch
+// channels, element i ch + channel): one body, rf_cut_tile, serves both, the mono kernel with ch = 1, channel = 0 folded in.  The staging
+// loop clamps on the sample TIME before it forms the 64-bit element offset, so a time outside [0, n_file) is zero, never the neighbouring
+// channel's element; everything after the staging is the mono arithmetic on the staged fp32 row.
 template <typename T>
-__global__ __launch_bounds__(256) void cut_rate_kernel(const T* __restrict__ x, int n_file, const int32_t* __restrict__ start, int L, SiFeed fd,
-                                                       float* __restrict__ out) {
+__device__ __forceinline__ void rf_cut_tile(const T* __restrict__ x, int n_file, int ch, int channel, const int32_t* __restrict__ start, int L,
+                                            const SiFeed& fd, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float rf_row[];
     const int c = blockIdx.y, o0 = blockIdx.x * RF_TILE;
     const int cnt = min(RF_TILE, L - o0);
@@ -40,7 +46,7 @@ __global__ __launch_bounds__(256) void cut_rate_kernel(const T* __restrict__ x, 
     const int span = live ? min((int)((j0 + cnt - 1) * Q / P + H + 1 - base), fd.cap) : 0;
     for (int p = threadIdx.x; p < span; p += 256) {
         const long i = base + p;
-        rf_row[p] = (i >= 0 && i < (long)n_file) ? rf_load(x + i) : 0.f;
+        rf_row[p] = (i >= 0 && i < (long)n_file) ? rf_load(x + ((size_t)i * ch + channel)) : 0.f;
     }
     __syncthreads();
     float* orow = out + (size_t)c * L + o0;
@@ -77,6 +83,18 @@ __global__ __launch_bounds__(256) void cut_rate_kernel(const T* __restrict__ x, 
     }
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void cut_rate_kernel(const T* __restrict__ x, int n_file, const int32_t* __restrict__ start, int L, SiFeed fd,
+                                                       float* __restrict__ out) {
+    rf_cut_tile(x, n_file, 1, 0, start, L, fd, out);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cut_rate_ch_kernel(const T* __restrict__ x, int n_file, int ch, int channel, const int32_t* __restrict__ start,
+                                                          int L, SiFeed fd, float* __restrict__ out) {
+    rf_cut_tile(x, n_file, ch, channel, start, L, fd, out);
+}
+
 // The caller (si_cut_rate) checked every argument, fd.cap * 4 <= 64 KB and C <= 65535 among them.
 int si_launch_cut_rate(si_ctx* ctx, const void* x, bool pcm16, int n_file, const int32_t* start, int C, int L, const SiFeed& fd, float* out,
                        hipStream_t st) {
@@ -89,6 +107,23 @@ int si_launch_cut_rate(si_ctx* ctx, const void* x, bool pcm16, int n_file, const
         cut_rate_kernel<int16_t><<<grid, 256, lds, st>>>(static_cast<const int16_t*>(x), n_file, start, L, fd, out);
     else
         cut_rate_kernel<float><<<grid, 256, lds, st>>>(static_cast<const float*>(x), n_file, start, L, fd, out);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+// The caller (si_cut_rate_ch) checked every argument, 1 <= ch <= SI_MAX_CHANNELS and 0 <= channel < ch among them.
+int si_launch_cut_rate_ch(si_ctx* ctx, const void* x, bool pcm16, int n_file, int ch, int channel, const int32_t* start, int C, int L,
+                          const SiFeed& fd, float* out, hipStream_t st) {
+    if (C <= 0 || L <= 0) return SI_OK;
+    const size_t lds = (size_t)fd.cap * sizeof(float);
+    const dim3 grid((L + RF_TILE - 1) / RF_TILE, C);
+    const double outs = (double)C * L;
+    si_prof_begin(ctx, "cut_rate_ch", outs * 8.0 * fd.H, outs * 4.0 + (double)grid.x * C * fd.cap * (pcm16 ? 2.0 : 4.0), st);
+    if (pcm16)
+        cut_rate_ch_kernel<int16_t><<<grid, 256, lds, st>>>(static_cast<const int16_t*>(x), n_file, ch, channel, start, L, fd, out);
+    else
+        cut_rate_ch_kernel<float><<<grid, 256, lds, st>>>(static_cast<const float*>(x), n_file, ch, channel, start, L, fd, out);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;

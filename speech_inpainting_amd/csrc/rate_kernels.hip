@@ -2,6 +2,7 @@
 // generator's 22.05 kHz axis to the FILE's rate and blended into the file's own samples, fp32 or int16 as they lie in the file.
 //   patch_rate_kernel<float | int16_t>   per touched chunk of 2048 file samples: band-limited interpolation of the window rows at the
 //                                        exact rational time i P / Q + patch_regions_kernel's blend, written into the caller's copy
+//   patch_rate_ch_kernel<float | int16_t> the same chunk written into one channel of an INTERLEAVED file: one shared body
 // It stands where `resample(patched, 22050, sr)` over the whole repaired recording would: that pass costs every sample of the file a
 // 2 x 65-tap float64 sum and returns none of the samples its owner recorded; this one computes the few hundred thousand samples the
 // cross-fades and gaps cover and leaves every other sample of `out` alone.
@@ -39,9 +40,14 @@ __device__ __forceinline__ void rk_store(int16_t* p, float v) { *p = rk_pcm16(v)
 // Every global access is one element wide, so orig / out / gen need only their element's alignment: callers pass views.  Plain stores, no
 // atomics.  The C ABI validated on the host copy that every staged sample inside [0, win_lim) lies in its window's row; the staging
 // loop still clamps to the row, so a device table that differs from the validated one gives wrong output, not a fault.
+//
+// patch_rate_ch_kernel is the same workgroup for channel `channel` of an INTERLEAVED file (n_file sample times of ch
+// channels): spans, chunks, fades and m are sample times of that channel, orig / out element m ch + channel (a 64-bit offset), and no
+// other element of out is touched.  One body, rk_patch_chunk, serves both, the mono kernel with ch = 1, channel = 0 folded in.  The table
+// may name windows (rows of gen) and contexts (entries of gain) that none of its spans use: another channel's share of the pass.
 template <typename T>
-__global__ __launch_bounds__(256) void patch_rate_kernel(const T* __restrict__ orig, SiRate rt, const float* __restrict__ gen, int Lrow,
-                                                         const float* __restrict__ gain, int n_file, T* __restrict__ out) {
+__device__ __forceinline__ void rk_patch_chunk(const T* __restrict__ orig, const SiRate& rt, const float* __restrict__ gen, int Lrow,
+                                               const float* __restrict__ gain, int n_file, int ch, int channel, T* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float rk_row[];
     const int q = blockIdx.x;
     const int c0 = rt.chunk[q] * RK_CHUNK, c1 = min(c0 + RK_CHUNK, n_file);
@@ -105,9 +111,22 @@ __global__ __launch_bounds__(256) void patch_rate_kernel(const T* __restrict__ o
                 }
             }
             const float g = __fmul_rn(g0, (float)acc);
-            rk_store(out + m, w == 1.f ? g : __fmaf_rn(w, g, __fmul_rn(1.f - w, rk_load(orig + m))));
+            const size_t e = (size_t)m * ch + channel;
+            rk_store(out + e, w == 1.f ? g : __fmaf_rn(w, g, __fmul_rn(1.f - w, rk_load(orig + e))));
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void patch_rate_kernel(const T* __restrict__ orig, SiRate rt, const float* __restrict__ gen, int Lrow,
+                                                         const float* __restrict__ gain, int n_file, T* __restrict__ out) {
+    rk_patch_chunk(orig, rt, gen, Lrow, gain, n_file, 1, 0, out);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void patch_rate_ch_kernel(const T* __restrict__ orig, SiRate rt, const float* __restrict__ gen, int Lrow,
+                                                            const float* __restrict__ gain, int n_file, int ch, int channel, T* __restrict__ out) {
+    rk_patch_chunk(orig, rt, gen, Lrow, gain, n_file, ch, channel, out);
 }
 
 // The caller (si_patch_rate) checked every argument, row_cap * 4 <= 64 KB among them.
@@ -121,6 +140,24 @@ int si_launch_patch_rate(si_ctx* ctx, const void* orig, bool pcm16, int n_file, 
         patch_rate_kernel<int16_t><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const int16_t*>(orig), rt, gen, Lrow, gain, n_file, static_cast<int16_t*>(out));
     else
         patch_rate_kernel<float><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const float*>(orig), rt, gen, Lrow, gain, n_file, static_cast<float*>(out));
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+// The caller (si_patch_rate_ch) checked every argument, 1 <= ch <= SI_MAX_CHANNELS and 0 <= channel < ch among them.
+int si_launch_patch_rate_ch(si_ctx* ctx, const void* orig, bool pcm16, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
+                            const float* gen, int Lrow, const float* gain, void* out, hipStream_t st) {
+    if (num_chunks <= 0) return SI_OK;
+    const size_t lds = (size_t)rt.row_cap * sizeof(float);
+    const double esz = pcm16 ? 2.0 : 4.0;
+    si_prof_begin(ctx, "patch_rate_ch", (double)num_chunks * RK_CHUNK * 8.0 * rt.H, (double)num_chunks * (RK_CHUNK * 2.0 * esz + 4.0 * rt.row_cap), st);
+    if (pcm16)
+        patch_rate_ch_kernel<int16_t><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const int16_t*>(orig), rt, gen, Lrow, gain, n_file, ch, channel,
+                                                                       static_cast<int16_t*>(out));
+    else
+        patch_rate_ch_kernel<float><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const float*>(orig), rt, gen, Lrow, gain, n_file, ch, channel,
+                                                                     static_cast<float*>(out));
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;

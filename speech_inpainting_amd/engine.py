@@ -583,18 +583,21 @@ class InpaintingEngine:
                 gain = self.ctx.wave_peak(w22, tb["tab22"]) / 0.95
                 self.ctx.patch_regions(wave22, self._region_table(cb, plan, own22), gen, gain, patched, out.get("patched_pcm"))
 
-        cut = lambda starts, L: self.ctx.cut_clips(wave22, starts, L)
+        cut = lambda cb, L: self.ctx.cut_clips(wave22, [441 * c["start"] for c in cb], L)
         out.update(self._recording_passes(wave22.numel(), cut, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write))
         return out
 
     def _recording_passes(self, N22: int, cut, wave16: Optional[torch.Tensor], gaps, fade_frames: int, clip_frames: int,
-                          min_context: int, batch: int, write) -> Dict[str, object]:
+                          min_context: int, batch: int, write, channel_gaps=None) -> Dict[str, object]:
         """What patch_recording and patch_file share: the context plan of a recording of N22 samples at 22.05 kHz and, per batch of
-        at most `batch` contexts, the cut -- cut(starts, L22) -> the (B, L22) clips that start at those 22.05 kHz samples, on the
-        device --, the one multi-gap pass with every gap the clips hold masked, and the labels of the own gaps.
+        at most `batch` contexts, the cut -- cut(cb, L22) -> the (B, L22) clips of the contexts cb, which start at 22.05 kHz samples
+        441 * start, on the device --, the one multi-gap pass with every gap the clips hold masked, and the labels of the own gaps.
         write(cb, tb, res, w22, L22) -- the contexts of the pass, their gap tables, the pass's result (vocode=False), the cut
         22.05 kHz clips (B, L22) -- plans the generator windows of the own gaps, runs the generator over them and writes the blended
-        samples.  -> contexts, labels, label_off."""
+        samples.  -> contexts, labels, label_off.
+        channel_gaps: one gap list per channel of an interleaved file in place of `gaps`.  Every channel is planned
+        as a recording of its own (gaps.plan_channel_contexts), the contexts follow in (channel, start) order with a "channel" key, the
+        batches fill across channels, and labels / label_off run over the gaps in (channel, gap) order; + channel_off."""
         N22, clip_frames, batch = int(N22), int(clip_frames), int(batch)
         n_rec = N22 // 441
         whole = n_rec <= clip_frames                                   # one context: the whole recording, with its true sample counts
@@ -605,14 +608,18 @@ class InpaintingEngine:
             L16 = -(-L22 * 16000 // 22050)
         out: Dict[str, object] = {}
         lim = min(self.ctx.num_frames(L16), self.ctx.mel_frames(L22)) if L16 > 0 and L22 > 0 else 0
-        ctxs = G.plan_contexts(gaps, n_rec, clip_frames, min_context, lim_frames=lim, fade_frames=int(fade_frames))
+        if channel_gaps is None:
+            ctxs = G.plan_contexts(gaps, n_rec, clip_frames, min_context, lim_frames=lim, fade_frames=int(fade_frames))
+        else:
+            ctxs, out["channel_off"] = G.plan_channel_contexts(channel_gaps, n_rec, clip_frames, min_context, lim_frames=lim,
+                                                               fade_frames=int(fade_frames))
         n_gaps = sum(len(c["own"]) for c in ctxs)
         out["contexts"] = ctxs
-        labels, counts = [], [0] * n_gaps
+        labels = []
         for i in range(0, len(ctxs), batch):
             cb = ctxs[i:i + batch]
             B = len(cb)
-            w22 = cut([441 * c["start"] for c in cb], L22)
+            w22 = cut(cb, L22)
             w16 = self.resample(w22, 22050, 16000) if wave16 is None else self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16)
             tb = self.gap_tables([c["own"] + c["foreign"] for c in cb], [L16] * B, [L22] * B)
             res = self.predict_multigap_batch(w16, w22, None, tables=tb, vocode=False)
@@ -623,15 +630,11 @@ class InpaintingEngine:
                 o = tb["label_off"][b]
                 for p, l in tb["gaps"][b]:
                     if (p, l) in c["own"]:
-                        counts[c["own_index"][c["own"].index((p, l))]] = l
                         idx += range(o, o + l)
                     o += l
             labels.append(res["labels"][torch.tensor(idx, dtype=torch.int64).to(self.device)])
         out["labels"] = torch.cat(labels) if labels else torch.zeros(0, dtype=torch.int64, device=self.device)
-        off = [0]
-        for n in counts:
-            off.append(off[-1] + n)
-        out["label_off"] = off
+        out["label_off"] = G.gap_label_off(ctxs, n_gaps)
         return out
 
     # ---- repair at the file's own sample rate: the recording stays at `sr` in its own sample type
@@ -653,7 +656,7 @@ class InpaintingEngine:
         and blend regions on the FILE's sample axis (gaps.file_spans / file_lim / file_regions), those regions mapped to the 22.05 kHz
         samples their interpolation reads (gaps.reach_regions22, `reach` taps per wing), and the generator windows that keep them
         (plan_patch).  -> plan_patch's dictionary + spans ((start, len, window, lim_f) rows), regions (file samples), rows ((context,
-        first 22.05 kHz sample, samples, lim22) per window): what RateTable takes.  A ValueError names a gap whose interpolation reaches
+        first 22.05 kHz sample, samples, lim22) per window): what RateTable takes; span_ctx: per row of spans the context it belongs to.  A ValueError names a gap whose interpolation reaches
         in front of its context (a gap within `reach` samples of a context's start that is not the recording's)."""
         hop = self.ctx.vocoder_samples(1, False)
         n_out = self.ctx.vocoder_samples(self.ctx.mel_frames(int(L22)), True)
@@ -674,14 +677,15 @@ class InpaintingEngine:
             spans.append([(s, l, lim_f) for s, l in sp])
             regions.append(regs)
         plan = self.plan_patch([[(0, 0)] * len(c["own"]) for c in ctxs], [int(L22)] * len(ctxs), int(fade_f), regions=local)
-        rows, flat_regions, k = [], [], 0
+        rows, flat_regions, span_ctx, k = [], [], [], 0
         for b in range(len(ctxs)):
             for (s, l, lim_f), reg in zip(spans[b], regions[b]):
                 if reg is not None:
                     rows.append((s, l, plan["span_win"][k], lim_f))
                     flat_regions.append(reg)
+                    span_ctx.append(b)
                 k += 1
-        plan["spans"], plan["regions"] = rows, flat_regions
+        plan["spans"], plan["regions"], plan["span_ctx"] = rows, flat_regions, span_ctx
         plan["rows"] = [(b, 441 * int(ctxs[b]["start"]) + w0 * hop, (w1 - w0) * hop, lim22[b]) for b, w0, w1 in plan["wins"]]
         return plan
 
@@ -697,8 +701,8 @@ class InpaintingEngine:
             self._resamplers[key] = f
         return self._resamplers[key]
 
-    def patch_file(self, x, sr: int, gaps, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
-                   return_windows: bool = False, feed: str = "recording") -> Dict[str, object]:
+    def patch_file(self, x, sr: int, gaps=None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
+                   return_windows: bool = False, feed: str = "recording", channel_gaps=None) -> Dict[str, object]:
         """patch_recording for a file at ITS OWN sample rate and in its own sample type: x (n,) is the recording at `sr` Hz, fp32 in
         full-scale units or int16 PCM (tensor or array, host or device), gaps = (first frame, frame count) pairs on its 20 ms grid.
         The recording is resampled to 22.05 kHz here (`resample`) only to FEED the model; the contexts, the multi-gap passes and the
@@ -713,7 +717,16 @@ class InpaintingEngine:
         exactly-integer times and in the recording's last sample (4.17 (a), (b)); everything after the cut is the same code.
         -> patched (n,) in x's dtype, contexts, labels, label_off as patch_recording; return_windows=True adds passes: per pass its
         contexts, gen (W, Lrow), gain (C,), table (RateTable), plan and clips22 (the cut 22.05 kHz clips).  No gaps: an exact copy,
-        no model kernel launched."""
+        no model kernel launched.
+        An INTERLEAVED file x (n, ch), 1 <= ch <= 8, as a WAV stores it: every channel is a mono recording to the
+        model, repaired exactly as patch_file repairs x[:, c] alone -- byte for byte -- and the contexts of all channels share the
+        passes.  `gaps` is one list for every channel; channel_gaps is one list per channel instead (an empty one: that channel comes
+        back as the file's).  x is never flattened, and with feed="contexts" never de-interleaved: si_cut_rate_ch and si_patch_rate_ch
+        read and write channel c in place, one launch each per channel present in a pass.  -> patched (n, ch), contexts with a
+        "channel" key in (channel, start) order, labels / label_off over the gaps in (channel, gap) order, channel_off (ch + 1): the
+        gaps of channel c are [channel_off[c], channel_off[c + 1]); with return_windows a pass holds tables ((channel, RateTable)
+        pairs) in place of table.  (n, 1) is the mono route with patched reshaped.  A file at sr = 22050 goes channel by channel
+        through patch_recording, as the mono file does: feed and return_windows are not read there and no `passes` come back."""
         self._need(head=True, codebook=True, what="patch_file")
         if feed not in ("recording", "contexts"):
             raise ValueError(f"patch_file: feed = {feed!r}: 'recording' or 'contexts'")
@@ -722,6 +735,18 @@ class InpaintingEngine:
         if batch <= 0:
             raise ValueError(f"patch_file: batch = {batch}")
         x = torch.as_tensor(x)
+        if gaps is not None and channel_gaps is not None:
+            raise ValueError("patch_file: both gaps and channel_gaps: one list for every channel, or one list per channel")
+        if x.dim() == 2:
+            per = G.channel_gap_lists(gaps, channel_gaps, x.shape[1])
+            kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed)
+            if x.shape[1] == 1:
+                out = self.patch_file(x.reshape(-1), sr, per[0], **kw)
+                out["patched"] = out["patched"].reshape(-1, 1)
+                return out
+            return self._patch_file_channels(x, sr, per, **kw)
+        if gaps is None:
+            raise ValueError("patch_file: a one-channel (n,) recording takes `gaps`; channel_gaps belongs to an (n, ch) file")
         pcm = x.dtype == torch.int16
         x = x.to(self.device, torch.int16 if pcm else torch.float32).reshape(-1).contiguous()
         n_file = x.numel()
@@ -746,12 +771,12 @@ class InpaintingEngine:
         if feed == "contexts":                                         # the clips alone, cut from x itself
             fin = self._feed_filter(sr)
             N22 = -(-n_file * P // Q)
-            cut = lambda starts, L: self.ctx.cut_rate(x, sr, starts, L, fin)
+            cut = lambda cb, L: self.ctx.cut_rate(x, sr, [441 * c["start"] for c in cb], L, fin)
         else:
             xf = x.to(torch.float32) / 32768.0 if pcm else x           # exact: 16 bits x 2^-15
             wave22 = self.resample(xf[None], sr, 22050)[0].contiguous()
             N22 = wave22.numel()
-            cut = lambda starts, L: self.ctx.cut_clips(wave22, starts, L)
+            cut = lambda cb, L: self.ctx.cut_clips(wave22, [441 * c["start"] for c in cb], L)
         filt = self._rate_filter(sr)
 
         def write(cb, tb, res, w22, L22):
@@ -772,37 +797,143 @@ class InpaintingEngine:
             out["passes"] = passes
         return out
 
+    def _patch_file_channels(self, x: torch.Tensor, sr: int, channel_gaps, fade_ms: float, clip_frames: int, min_context: int, batch: int,
+                             return_windows: bool, feed: str) -> Dict[str, object]:
+        """patch_file for an interleaved file x (n, ch >= 2) with one gap list per channel."""
+        n_file, ch = x.shape
+        if ch > G.MAX_CHANNELS:
+            raise ValueError(f"patch_file: a file of {ch} channels, at most {G.MAX_CHANNELS}")
+        pcm = x.dtype == torch.int16
+        x = x.to(self.device, torch.int16 if pcm else torch.float32).contiguous()
+        if n_file < 1 or n_file > 2 ** 31 - 1 - 2048:
+            raise ValueError(f"patch_file: a file of {n_file} samples")
+        P, Q = G.rate_ratio(sr)
+        fade_f = G.file_fade(fade_ms, sr)
+        if sr == 22050:                                                # patch_recording, channel by channel, as the mono file goes
+            outs = [self.patch_file(x[:, c].contiguous(), sr, channel_gaps[c], fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context,
+                                    batch=batch) for c in range(ch)]
+            off = [0]
+            for o in outs:
+                off.append(off[-1] + len(o["label_off"]) - 1)
+            ctxs = [dict(k, channel=c, own_index=[off[c] + i for i in k["own_index"]]) for c, o in enumerate(outs) for k in o["contexts"]]
+            label_off = [0]
+            for o in outs:
+                label_off += [label_off[-1] + v for v in o["label_off"][1:]]
+            return {"patched": torch.stack([o["patched"] for o in outs], dim=1), "contexts": ctxs, "labels": torch.cat([o["labels"] for o in outs]),
+                    "label_off": label_off, "channel_off": off}
+        patched = x.clone()
+        out: Dict[str, object] = {"patched": patched}
+        passes = []
+        if not any(channel_gaps):                                      # nothing to repair: not even the resampler runs
+            out.update(contexts=[], labels=torch.zeros(0, dtype=torch.int64, device=self.device), label_off=[0], channel_off=[0] * (ch + 1))
+            if return_windows:
+                out["passes"] = passes
+            return out
+        if feed == "contexts":                                         # the clips alone, cut from x itself, channel c in place
+            fin = self._feed_filter(sr)
+            N22 = -(-n_file * P // Q)
+            cut_rows = lambda c, starts, L, rows: self.ctx.cut_rate(x, sr, starts, L, fin, out=rows, channel=c)
+        else:                                                          # the whole-file resample per channel: it de-interleaves
+            wave22 = {}
+            for c in range(ch):
+                if channel_gaps[c]:
+                    xc = x[:, c].contiguous()
+                    xf = xc.to(torch.float32) / 32768.0 if pcm else xc   # exact: 16 bits x 2^-15
+                    wave22[c] = self.resample(xf[None], sr, 22050)[0].contiguous()   # row by row: the mono call's own launch
+            N22 = next(iter(wave22.values())).numel()
+            cut_rows = lambda c, starts, L, rows: self.ctx.cut_clips(wave22[c], starts, L, out=rows)
+        filt = self._rate_filter(sr)
+
+        def cut(cb, L):
+            w22 = torch.empty(len(cb), L, dtype=torch.float32, device=self.device)
+            for c, r0, r1 in G.pass_channels(cb):                      # a channel's clips are consecutive rows of the pass
+                cut_rows(c, [441 * k["start"] for k in cb[r0:r1]], L, w22[r0:r1])
+            return w22
+
+        def write(cb, tb, res, w22, L22):
+            plan = self.plan_rate(cb, L22, sr, n_file, fade_f, filt["reach"])
+            if plan["wins"]:
+                ext, _ = self._stretch(res["mel"], plan["hop"], None, plan["windows"])
+                gen = self._vocode_gathered(ext, plan["wins"])
+                # the front-end divided by this peak and multiplied by 0.95 (I_ea/predict.py:104), with ALL gaps of the context zeroed
+                gain = self.ctx.wave_peak(w22, tb["tab22"]) / 0.95
+                tables = []
+                for c, r0, r1 in G.pass_channels(cb):                  # the channel's spans and chunks, the pass's whole gen and gain
+                    ks = [k for k, b in enumerate(plan["span_ctx"]) if r0 <= b < r1]
+                    if not ks:
+                        continue
+                    table = RateTable([plan["spans"][k] for k in ks], plan["rows"], G.region_chunks([plan["regions"][k] for k in ks]), len(cb),
+                                      fade_f, self.device)
+                    self.ctx.patch_rate(x, sr, table, gen, filt, patched, gain, channel=c)
+                    tables.append((c, table))
+                if return_windows:
+                    passes.append({"contexts": cb, "gen": gen, "gain": gain, "tables": tables, "plan": plan, "clips22": w22})
+
+        fade_frames = max(-(-fade_f * 50 // sr), 1)
+        out.update(self._recording_passes(N22, cut, None, None, fade_frames, clip_frames, min_context, batch, write, channel_gaps=channel_gaps))
+        if return_windows:
+            out["passes"] = passes
+        return out
+
     def conceal_file(self, x, sr: int, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
                      merge_frames: Optional[int] = None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
-                     return_windows: bool = False, feed: str = "recording") -> Dict[str, object]:
+                     return_windows: bool = False, feed: str = "recording", detect: str = "each") -> Dict[str, object]:
         """File in, repaired file out, at the file's own rate and in its own sample type: find_gaps on x itself, where a dropout is
         still exact zeros, then patch_file with the gaps it found.  The usable frames are those of the recording's 22.05 kHz length
         ceil(n * 22050 / sr) (`recording_frames`), and a gap longer than the planner's budget counts as long, as in conceal_recording.
         threshold is in x's own units, as find_gaps takes it: full scale for fp32, int16 steps for an int16 file.
         feed: patch_file's ("recording" or "contexts").
-        -> patch_file's dictionary + gaps + skipped.  With nothing found: an exact copy; only the detection kernels launched."""
+        -> patch_file's dictionary + gaps + skipped.  With nothing found: an exact copy; only the detection kernels launched.
+        An interleaved file x (n, ch >= 2): detect="each" runs the detection once per channel and repairs a dropout
+        in the channel it is in (gaps, skipped: one list per channel); detect="joint" runs it once over the sample times at which
+        EVERY channel is quiet and repairs those gaps in every channel (gaps, skipped: one list).  A one-channel file ignores it."""
         sr, clip_frames, min_context = int(sr), int(clip_frames), int(min_context)
+        if detect not in ("each", "joint"):
+            raise ValueError(f"conceal_file: detect = {detect!r}: 'each' or 'joint'")
         P, Q = G.rate_ratio(sr)
         x = torch.as_tensor(x)
-        x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32).reshape(-1).contiguous()
-        n_rec, lim = self.recording_frames(-(-x.numel() * P // Q), clip_frames)
+        shape = x.shape
+        many = x.dim() == 2 and shape[1] >= 2                          # (n, 1) is the mono route, reshaped at the end
+        if many and shape[1] > G.MAX_CHANNELS:
+            raise ValueError(f"conceal_file: a file of {shape[1]} channels, at most {G.MAX_CHANNELS}")
+        x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32)
+        x = x.contiguous() if many else x.reshape(-1).contiguous()
+        n_rec, lim = self.recording_frames(-(-x.shape[0] * P // Q), clip_frames)
         if n_rec > clip_frames:
             max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
         fade22 = -(-G.file_fade(fade_ms, sr) * P // Q)
-        found = self.find_gaps(x, sr, threshold, min_ms, max_ms, pad_frames, merge_frames, fade22, n_rec, lim)
-        out = self.patch_file(x, sr, found["gaps"], fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch,
-                              return_windows=return_windows, feed=feed)
+        find = lambda c: self.find_gaps(x, sr, threshold, min_ms, max_ms, pad_frames, merge_frames, fade22, n_rec, lim, channel=c)
+        kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed)
+        if many and detect == "each":
+            found = [find(c) for c in range(shape[1])]
+            out = self.patch_file(x, sr, channel_gaps=[f["gaps"] for f in found], **kw)
+            out["gaps"], out["skipped"] = [f["gaps"] for f in found], [f["skipped"] for f in found]
+            return out
+        found = find(-1 if many else None)
+        out = self.patch_file(x, sr, found["gaps"], **kw)
         out["gaps"], out["skipped"] = found["gaps"], found["skipped"]
+        if not many and len(shape) == 2:
+            out["patched"] = out["patched"].reshape(-1, 1)
         return out
 
     # ---- dropout detection (DESIGN.md 4.15): where the gaps are, found on the device; then patch_recording as it is
-    def find_quiet_runs(self, x, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536) -> torch.Tensor:
+    def find_quiet_runs(self, x, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536, channel: Optional[int] = None) -> torch.Tensor:
         """x (n,) fp32 or int16 (tensor or array, host or device; a device view may start anywhere) -> device int32 (R, 2): every
         maximal run of samples with |x| <= threshold of at least min_len samples, as (start, len) rows sorted by start
-        (si_quiet_runs).  One D2H copy: the count.  A ValueError names both numbers when more than max_runs runs qualify."""
+        (si_quiet_runs).  One D2H copy: the count.  A ValueError names both numbers when more than max_runs runs qualify.
+        An interleaved x (n, ch >= 2) needs `channel`: an index for that channel's runs, -1 for the runs of sample
+        times at which every channel is quiet; rows are in sample times (si_quiet_runs_ch).  x is not flattened or de-interleaved."""
         x = torch.as_tensor(x)
-        x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32).reshape(-1).contiguous()
-        runs, n_runs = self.ctx.quiet_runs(x, threshold, min_len, max_runs)
+        if x.dim() == 2 and x.shape[1] >= 2:
+            if channel is None:
+                raise ValueError(f"find_quiet_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
+            x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32).contiguous()
+            runs, n_runs = self.ctx.quiet_runs(x, threshold, min_len, max_runs, channel=int(channel))
+        else:
+            if channel is not None and int(channel) not in (-1, 0):
+                raise ValueError(f"find_quiet_runs: channel = {channel} of a one-channel recording")
+            x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32).reshape(-1).contiguous()
+            runs, n_runs = self.ctx.quiet_runs(x, threshold, min_len, max_runs)
         total = int(n_runs.item())
         if total > int(max_runs):
             raise ValueError(f"find_quiet_runs: {total} runs of at least {int(min_len)} quiet samples, more than max_runs = {int(max_runs)}")
@@ -822,18 +953,19 @@ class InpaintingEngine:
 
     def find_gaps(self, x, sr: int = 22050, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
                   merge_frames: Optional[int] = None, fade: int = 110, n_rec_frames: Optional[int] = None,
-                  lim_frames: Optional[int] = None) -> Dict[str, object]:
+                  lim_frames: Optional[int] = None, channel: Optional[int] = None) -> Dict[str, object]:
         """The dropouts of a recording x (n samples at `sr` Hz, fp32 in full-scale units or int16 PCM): runs of at least min_ms of
         |x| <= threshold (find_quiet_runs), mapped by gaps.runs_to_gaps onto the 20 ms grid of the recording's n_rec_frames frames
         (default n * 50 // sr) with the usable frames [0, lim_frames).  merge_frames None = 2 * the frames one cross-fade of `fade`
         22.05 kHz samples reaches over; gaps of more than max_ms are skipped.
         -> gaps ((first frame, frame count), sorted: what patch_recording takes), skipped ((first frame, frame count, reason)),
-        runs (device int32 (R, 2), samples at `sr`)."""
+        runs (device int32 (R, 2), samples at `sr`).
+        An interleaved x (n, ch) takes find_quiet_runs' `channel`; n, the runs and the gaps then count sample times and frames."""
         x = torch.as_tensor(x)
-        n, sr = x.numel(), int(sr)
+        n, sr = (x.shape[0] if x.dim() == 2 else x.numel()), int(sr)
         if n < 1 or sr <= 0:
             raise ValueError(f"find_gaps: {n} samples at {sr} Hz")
-        runs = self.find_quiet_runs(x, threshold, max(1, int(round(float(min_ms) * sr / 1000.0))))
+        runs = self.find_quiet_runs(x, threshold, max(1, int(round(float(min_ms) * sr / 1000.0))), channel=channel)
         n_rec = n * 50 // sr if n_rec_frames is None else int(n_rec_frames)
         mf = 2 * max(-(-int(fade) // 441), 1) if merge_frames is None else int(merge_frames)
         gaps, skipped = G.runs_to_gaps(runs.tolist(), n, sr, n_rec, lim_frames, pad_frames, mf, max(int(float(max_ms) // 20), 1))

@@ -12,6 +12,7 @@ import math
 from typing import List, Optional, Sequence, Tuple
 
 MAX_SPANS = 16          # SI_MAX_SPANS of include/si_hip.h: spans per clip
+MAX_CHANNELS = 8        # SI_MAX_CHANNELS of include/si_hip.h: channels of an interleaved file
 
 Gap = Tuple[int, int]
 
@@ -209,6 +210,66 @@ def plan_patch_windows(regions: Sequence[Optional[Gap]], t_out: int, hop: int, r
 
 # ---- recordings longer than one clip: gaps on the recording's frame grid -> context clips
 PC_CHUNK = 2048         # samples per workgroup of patch_regions_kernel (patch_kernels.hip)
+
+
+def channel_gap_lists(gaps, channel_gaps, channels: int) -> List[list]:
+    """One gap list per channel of an interleaved file: `gaps` for every channel, or channel_gaps as it is (a sequence
+    of `channels` lists, any of them empty).  Both, neither, or a channel_gaps of another length raise a ValueError."""
+    if gaps is not None and channel_gaps is not None:
+        raise ValueError("both gaps and channel_gaps: one list for every channel, or one list per channel")
+    if channel_gaps is None:
+        if gaps is None:
+            raise ValueError("neither gaps nor channel_gaps")
+        return [list(gaps) for _ in range(int(channels))]
+    per = [list(g) for g in channel_gaps]
+    if len(per) != int(channels):
+        raise ValueError(f"channel_gaps holds {len(per)} lists for a file of {int(channels)} channels")
+    return per
+
+
+def plan_channel_contexts(channel_gaps: Sequence[Sequence[Sequence[int]]], n_rec_frames: int, clip_frames: int = 200, min_context: int = 50,
+                          lim_frames: Optional[int] = None, fade_frames: int = 1):
+    """The contexts of an interleaved file: plan_contexts as it stands on each channel's own gap list -- a channel is
+    a mono recording --, concatenated in (channel, start) order.  Each context carries "channel"; its own_index counts over ALL
+    channels' sorted gaps in (channel, gap) order.  -> (contexts, channel_off): channel_off has one entry per channel + 1, the gaps
+    of channel c are [channel_off[c], channel_off[c + 1]).  A ValueError of plan_contexts names the channel in front."""
+    ctxs, off = [], [0]
+    for c, g in enumerate(channel_gaps):
+        try:
+            own = plan_contexts(g, n_rec_frames, clip_frames, min_context, lim_frames=lim_frames, fade_frames=fade_frames)
+        except ValueError as e:
+            raise ValueError(f"channel {c}: {e}") from None
+        for k in own:
+            k["channel"] = c
+            k["own_index"] = [off[-1] + i for i in k["own_index"]]
+        ctxs += own
+        off.append(off[-1] + len(g))
+    return ctxs, off
+
+
+def pass_channels(ctxs: Sequence[dict]) -> List[Tuple[int, int, int]]:
+    """The contexts of ONE pass, in (channel, start) order, -> (channel, first row, end row) per channel present: its clips are
+    consecutive rows of the pass, one cut and one write-back launch each."""
+    out: List[Tuple[int, int, int]] = []
+    for r, k in enumerate(ctxs):
+        c = int(k["channel"])
+        if out and out[-1][0] == c:
+            out[-1] = (c, out[-1][1], r + 1)
+        else:
+            out.append((c, r, r + 1))
+    return out
+
+
+def gap_label_off(ctxs: Sequence[dict], n_gaps: int) -> List[int]:
+    """label_off of a plan: gap k (own_index) of n_gaps owns labels [label_off[k], label_off[k + 1]), one per frame of the gap."""
+    counts = [0] * int(n_gaps)
+    for k in ctxs:
+        for i, (_, l) in zip(k["own_index"], k["own"]):
+            counts[i] = int(l)
+    off = [0]
+    for n in counts:
+        off.append(off[-1] + n)
+    return off
 
 
 def plan_contexts(gaps: Sequence[Sequence[int]], n_rec_frames: int, clip_frames: int = 200, min_context: int = 50,

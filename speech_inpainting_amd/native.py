@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -30,8 +30,10 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_debug_capture", "si_debug_size",
            "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
            "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
-           "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate"]
+           "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate",
+           "si_quiet_runs_ch", "si_cut_rate_ch", "si_patch_rate_ch"]
 SI_MAX_SPANS = 16
+SI_MAX_CHANNELS = 8                        # channels of an interleaved file
 CUT_RATE_TILE = 512                        # SI_CUT_RATE_TILE: consecutive outputs of one clip per workgroup of si_cut_rate
 
 
@@ -360,6 +362,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_quiet_runs.argtypes = [vp, vp, i32, i32, C.c_float, i32, vp, i32, vp, vp]
     lib.si_patch_rate.argtypes = [vp, vp, i32, i32, i32, C.POINTER(RateTableStruct), vp, i32, vp, C.POINTER(SincFilter), vp, vp]
     lib.si_cut_rate.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, C.POINTER(SincFilter), vp, vp]
+    lib.si_quiet_runs_ch.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, i32, vp, vp]
+    lib.si_cut_rate_ch.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, C.POINTER(SincFilter), vp, vp]
+    lib.si_patch_rate_ch.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(RateTableStruct), vp, i32, vp, C.POINTER(SincFilter), vp, vp]
     lib.si_num_frames.argtypes = [vp, i32]
     lib.si_vocoder_samples.argtypes = [vp, i32, i32]
     lib.si_debug_capture.argtypes = [vp, C.c_char_p, vp, C.c_long]
@@ -661,14 +666,27 @@ class NativeContext:
                                               _ptr(out_pcm), self._stream()), "si_patch_regions")
 
     # ---- repair at the file's own sample rate
+    @staticmethod
+    def _interleaved(x: torch.Tensor, channel: Optional[int]) -> Tuple[int, int]:
+        """(sample times, channels) of x as a call with `channel` takes it: (n,) for channel None, else (n, ch) interleaved (DESIGN.md
+        4.18).  Channel counts and indices the C ABI would refuse are passed on, so that it is the one that refuses them."""
+        assert x.is_cuda and x.dtype in (torch.float32, torch.int16) and x.is_contiguous()
+        if channel is None:
+            assert x.dim() == 1
+            return min(x.numel(), 2 ** 31 - 1), 0
+        assert x.dim() == 2
+        return min(x.shape[0], 2 ** 31 - 1), x.shape[1]
+
     def patch_rate(self, orig: torch.Tensor, sr: int, table: "RateTable", gen: Optional[torch.Tensor], filt: dict, out: torch.Tensor,
-                   gain: Optional[torch.Tensor] = None) -> None:
+                   gain: Optional[torch.Tensor] = None, channel: Optional[int] = None) -> None:
         """The blended samples of `table`'s regions written IN PLACE into out (n_file,), which holds the caller's copy of the file
         `orig` (n_file,) at `sr` Hz everywhere else (si_patch_rate).  orig / out: fp32 or int16, the same type, device views that may
         start anywhere.  gen (W, Lrow) fp32 at 22.05 kHz; gain (C,) fp32 or None; filt: audio.design_kaiser_best(22050, sr, .) with win /
-        dwin as float64 device tensors."""
-        assert orig.is_cuda and orig.dtype in (torch.float32, torch.int16) and orig.dim() == 1 and orig.is_contiguous()
-        assert out.is_cuda and out.dtype == orig.dtype and out.dim() == 1 and out.is_contiguous() and out.numel() == orig.numel()
+        dwin as float64 device tensors.
+        channel = c: orig / out are (n_file, ch) interleaved and only channel c of out is written, the table's spans and chunks being
+        sample times of that channel (si_patch_rate_ch); the table may name windows and contexts of other channels."""
+        n_file, ch = self._interleaved(orig, channel)
+        assert out.is_cuda and out.dtype == orig.dtype and out.shape == orig.shape and out.is_contiguous()
         assert gen is None or (gen.is_cuda and gen.dtype == torch.float32 and gen.dim() == 2 and gen.is_contiguous() and gen.shape[0] == table.W)
         assert gain is None or (gain.is_cuda and gain.dtype == torch.float32 and gain.numel() == table.C and gain.is_contiguous())
         win, dwin = filt["win"], filt["dwin"]
@@ -677,17 +695,22 @@ class NativeContext:
         f = SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
                        float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
         t = table.struct()
-        self._check(self.lib.si_patch_rate(self._h, _ptr(orig), int(orig.dtype == torch.int16), min(orig.numel(), 2 ** 31 - 1), int(sr), C.byref(t), _ptr(gen),
+        if channel is not None:
+            self._check(self.lib.si_patch_rate_ch(self._h, _ptr(orig), int(orig.dtype == torch.int16), n_file, ch, int(channel), int(sr), C.byref(t), _ptr(gen),
+                                                  0 if gen is None else gen.shape[1], _ptr(gain), C.byref(f), _ptr(out), self._stream()), "si_patch_rate_ch")
+            return
+        self._check(self.lib.si_patch_rate(self._h, _ptr(orig), int(orig.dtype == torch.int16), n_file, int(sr), C.byref(t), _ptr(gen),
                                            0 if gen is None else gen.shape[1], _ptr(gain), C.byref(f), _ptr(out), self._stream()), "si_patch_rate")
 
     # ---- context clips cut at the file's own sample rate
-    def cut_rate(self, x: torch.Tensor, sr: int, starts, L: int, filt: dict, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def cut_rate(self, x: torch.Tensor, sr: int, starts, L: int, filt: dict, out: Optional[torch.Tensor] = None,
+                 channel: Optional[int] = None) -> torch.Tensor:
         """x (n_file,) at `sr` Hz, fp32 or int16, a device view that may start anywhere + starts (host ints, 22.05 kHz samples) ->
         (C, L) fp32: row c = samples [starts[c], starts[c] + L) of the recording's 22.05 kHz axis, interpolated at the exact time
         j * sr / 22050 straight from the file's samples (si_cut_rate).  filt: audio.design_kaiser_best(sr, 22050, .) with win / dwin as
         float64 device tensors.  A start table that leaves the recording's ceil(n_file * 22050 / sr) samples is refused before the
-        launch."""
-        assert x.is_cuda and x.dtype in (torch.float32, torch.int16) and x.dim() == 1 and x.is_contiguous()
+        launch.  channel = c: x is (n_file, ch) interleaved and the clips are cut from its channel c (si_cut_rate_ch)."""
+        n_file, ch = self._interleaved(x, channel)
         host = np.ascontiguousarray(np.asarray(list(starts), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
         Cn, L = host.size, int(L)
         dev = torch.from_numpy(host).to(self.device, non_blocking=True) if Cn else None
@@ -699,17 +722,23 @@ class NativeContext:
         assert win.numel() == dwin.numel()
         f = SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
                        float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
-        self._check(self.lib.si_cut_rate(self._h, _ptr(x), int(x.dtype == torch.int16), min(x.numel(), 2 ** 31 - 1), int(sr), host.ctypes.data_as(C.c_void_p),
+        if channel is not None:
+            self._check(self.lib.si_cut_rate_ch(self._h, _ptr(x), int(x.dtype == torch.int16), n_file, ch, int(channel), int(sr), host.ctypes.data_as(C.c_void_p),
+                                                _ptr(dev), Cn, L, C.byref(f), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate_ch")
+            return out
+        self._check(self.lib.si_cut_rate(self._h, _ptr(x), int(x.dtype == torch.int16), n_file, int(sr), host.ctypes.data_as(C.c_void_p),
                                          _ptr(dev), Cn, L, C.byref(f), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate")
         return out
 
     # ---- dropout detection
     def quiet_runs(self, x: torch.Tensor, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536, runs: Optional[torch.Tensor] = None,
-                   n_runs: Optional[torch.Tensor] = None):
+                   n_runs: Optional[torch.Tensor] = None, channel: Optional[int] = None):
         """x (n,) fp32 or int16 on the device (a view may start anywhere) -> (runs (max_runs, 2) int32, n_runs (1,) int32), both on
         the device: the maximal runs of |x| <= threshold of at least min_len samples as (start, len) rows sorted by start, and how
-        many there are in all (si_quiet_runs).  Rows at and past min(n_runs, max_runs) are not written; max_runs = 0 counts only."""
-        assert x.is_cuda and x.dtype in (torch.float32, torch.int16) and x.dim() == 1 and x.is_contiguous()
+        many there are in all (si_quiet_runs).  Rows at and past min(n_runs, max_runs) are not written; max_runs = 0 counts only.
+        channel = c: x is (n, ch) interleaved and the runs are channel c's, in sample times; channel = -1: the runs of sample times at
+        which EVERY channel is quiet (si_quiet_runs_ch)."""
+        n, ch = self._interleaved(x, channel)
         max_runs = int(max_runs)
         if runs is None and max_runs > 0:
             runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
@@ -717,7 +746,11 @@ class NativeContext:
             n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
         assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
         assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
-        self._check(self.lib.si_quiet_runs(self._h, _ptr(x), int(x.dtype == torch.int16), min(x.numel(), 2 ** 31 - 1), float(threshold), int(min_len),
+        if channel is not None:
+            self._check(self.lib.si_quiet_runs_ch(self._h, _ptr(x), int(x.dtype == torch.int16), n, ch, int(channel), float(threshold), int(min_len),
+                                                  _ptr(runs), max_runs, _ptr(n_runs), self._stream()), "si_quiet_runs_ch")
+            return runs, n_runs
+        self._check(self.lib.si_quiet_runs(self._h, _ptr(x), int(x.dtype == torch.int16), n, float(threshold), int(min_len),
                                            _ptr(runs), max_runs, _ptr(n_runs), self._stream()), "si_quiet_runs")
         return runs, n_runs
 

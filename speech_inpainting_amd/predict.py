@@ -18,9 +18,15 @@ min_ms: 5.0, max_ms: 400.0, pad_frames: 0}) beside `long:` and instead of `mask:
 |x| <= threshold of at least min_ms in the file's own samples (engine.find_gaps); each gap and each skipped run is
 printed and `gaps.json` is written beside the three waves.  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
 on the way out: the three waves keep the file's own rate and sample type (an int16 file stays int16), and patched.wav holds the file's
-own samples, bit for bit, outside the cross-fades (engine.patch_file).  A multi-channel file is refused there.
+own samples, bit for bit, outside the cross-fades (engine.patch_file).
 With `feed: contexts` beside `rate: file` the recording is not resampled as a whole on the way in either: only the context clips
 are cut from it, at its own rate and in its own sample type (si_cut_rate); `feed: recording` is the default.
+A multi-channel file of up to 8 channels is served with `rate: file, feed: contexts`: it stays interleaved, every
+channel is repaired as the mono recording it is to the model, and the three waves are written multi-channel; with `rate: file` and the
+default `feed: recording` it is refused, as it was (that feed would de-interleave it).  `mask:` / `masks:` apply to every
+channel; `detect:` takes `channels: each` (the default: every channel is scanned and repaired on its own, gaps.json holds one list
+per channel) or `channels: joint` (a gap is where ALL channels are quiet, repaired in all of them).  Without `rate: file` a
+multi-channel file is mixed down to one channel at 22.05 kHz, as before.
 
 Differences from the script, all outside the three replaced subsystems: no Whisper `Metrics` object is built (the
 script constructs it and never uses it, I_ea/predict.py:72-73), PNG plots are skipped, and the two `librosa.load` calls are one
@@ -360,13 +366,19 @@ def _detect_gaps(cfg: PredictConfig, engine: InpaintingEngine, raw: np.ndarray, 
 
 def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> int:
     """`long: {rate: file}`: the recording stays at the file's own rate and in its own sample type (engine.patch_file).  orig.wav,
-    masked.wav and patched.wav are written at that rate; an int16 file is written as int16, any other as the float32 it was read to."""
+    masked.wav and patched.wav are written at that rate; an int16 file is written as int16, any other as the float32 it was read to.
+    With `feed: contexts` a multi-channel file (up to 8 channels) stays interleaved and is repaired channel by channel (DESIGN.md
+    4.18): `mask:` / `masks:` apply to every channel, `detect: {channels: each | joint}` finds the gaps per channel or where all
+    channels are quiet.  With the default `feed: recording` it is refused, as it was."""
     from scipy.io import wavfile
     from . import gaps as G
     sr_file, data = wavfile.read(cfg.wave_path)
     if data.ndim != 1:
-        raise ValueError(f"{cfg.wave_path}: {data.shape[1]} channels -- `long: {{rate: file}}` gives the file's own samples back and serves one channel; "
-                         f"split the channels, or drop `rate: file` for the 22.05 kHz mix-down")
+        if cfg.long_feed != "contexts":                                            # the refusal of before, for the feed of before
+            raise ValueError(f"{cfg.wave_path}: {data.shape[1]} channels -- `long: {{rate: file}}` with the default `feed: recording` resamples the "
+                             f"whole file to feed the model and serves one channel; add `feed: contexts` to repair the channels in place, split "
+                             f"the channels, or drop `rate: file` for the 22.05 kHz mix-down")
+        return _main_long_file_channels(cfg, engine, save_dir, sr_file, data)
     raw, sr_file = audio.read_wav(cfg.wave_path)
     x = data if data.dtype == np.int16 else raw
     P, Q = G.rate_ratio(sr_file)
@@ -387,6 +399,64 @@ def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str)
     labels, off = out["labels"].tolist(), out["label_off"]
     for k, (pos, lm) in enumerate(gap_list):
         print(f"Predicted codewords, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[k]:off[k + 1]])
+    audio.write_wav(os.path.join(save_dir, "patched.wav"), out["patched"].cpu().numpy(), sr_file)
+    print("wrote", save_dir)
+    return 0
+
+
+def _wav_samples(data: np.ndarray) -> np.ndarray:
+    """A WAV file's samples as patch_file takes them: int16 as it is, any other type as audio.read_wav's float32, channels kept."""
+    if data.dtype == np.int16:
+        return data
+    if data.dtype == np.int32:
+        return data.astype(np.float32) / 2147483648.0
+    if data.dtype == np.uint8:
+        return (data.astype(np.float32) - 128.0) / 128.0
+    return data.astype(np.float32)
+
+
+def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str, sr_file: int, data: np.ndarray) -> int:
+    """`long: {rate: file}` on a multi-channel file (n, ch): the three files are written multi-channel, at the file's rate and in its
+    sample type; gaps.json holds one list per channel for `detect: {channels: each}`.  The file is uploaded once; with `detect:` the
+    route is engine.conceal_file itself, otherwise engine.patch_file with the given gaps for every channel."""
+    from . import gaps as G
+    ch = data.shape[1]
+    if ch > G.MAX_CHANNELS:
+        raise ValueError(f"{cfg.wave_path}: {ch} channels -- `long: {{rate: file}}` serves at most {G.MAX_CHANNELS}")
+    x = np.ascontiguousarray(_wav_samples(data))
+    fade_ms = cfg.patch_fade_ms if cfg.patch_fade_ms is not None else 5.0
+    clip_frames, min_context = int(round(cfg.long["clip_s"] * 50)), int(round(cfg.long["context_s"] * 50))
+    dev = torch.from_numpy(x).to(engine.device)                                    # the one upload: detection and repair read it
+    kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"], feed=cfg.long_feed)
+    if cfg.detect is not None:                                                     # conceal_file: its own budget for a gap, its own fade
+        d = cfg.detect
+        thr = d["threshold"] * 32768.0 if x.dtype == np.int16 else d["threshold"]   # an int16 file is scanned as the int16 it holds
+        joint = cfg.detect_channels == "joint"
+        out = engine.conceal_file(dev, sr_file, thr, d["min_ms"], d["max_ms"], d["pad_frames"], detect=cfg.detect_channels, **kw)
+        found = [(out["gaps"], out["skipped"])] if joint else list(zip(out["gaps"], out["skipped"]))
+        for c, (gaps_c, skipped_c) in enumerate(found):
+            who = "all channels" if joint else f"channel {c}"
+            for k, (pos, lm) in enumerate(gaps_c):
+                print(f"Detected gap {k} of {who} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s")
+            for pos, lm, why in skipped_c:
+                print(f"Skipped quiet run of {who} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s: {why}")
+        lists = lambda v: [list(g) for g in v] if joint else [[list(g) for g in one] for one in v]
+        with open(os.path.join(save_dir, "gaps.json"), "w") as f:
+            json.dump({"gaps": lists(out["gaps"]), "skipped": lists(out["skipped"])}, f)
+        per = [out["gaps"]] * ch if joint else out["gaps"]
+    else:
+        per = [sorted(cfg.gaps) if cfg.gaps is not None else [(cfg.mask_pos, cfg.mask_frames)]] * ch
+        out = engine.patch_file(dev, sr_file, channel_gaps=per, **kw)
+    audio.write_wav(os.path.join(save_dir, "orig.wav"), x, sr_file)
+    masked = x.copy()
+    for c in range(ch):
+        for s, l in G.file_spans(per[c], sr_file):
+            masked[s:s + l, c] = 0                                                 # the file samples whose time lies in the gap's frames
+    audio.write_wav(os.path.join(save_dir, "masked.wav"), masked, sr_file)
+    labels, off, coff = out["labels"].tolist(), out["label_off"], out["channel_off"]
+    for c in range(ch):
+        for k, (pos, lm) in enumerate(sorted(per[c])):
+            print(f"Predicted codewords, channel {c}, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[coff[c] + k]:off[coff[c] + k + 1]])
     audio.write_wav(os.path.join(save_dir, "patched.wav"), out["patched"].cpu().numpy(), sr_file)
     print("wrote", save_dir)
     return 0
