@@ -245,7 +245,12 @@ int si_codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, const int
  * ties -- what `kmeans_model.predict(feats)` returns at I_da/scripts/inpainting.py:204-205 (sklearn minimises
  * ||c||^2 - 2 x.c) and `ApplyKmeans.__call__` at I_ea/dataset/km_label.py:20-24.  feats device fp32 (rows, D),
  * centroids device fp32 (K, D) (caller-owned: I_da's unit codebook lives in HuBERT feature space, not in the context),
- * labels device int64 (rows), sq_dist optional device fp32 (rows).  Needs no weights. */
+ * labels device int64 (rows), sq_dist optional device fp32 (rows).  Needs no weights.
+ * The arg-min follows torch.argmin's rules (as `dist.argmin` / `np.argmin` do in the two scripts): a NaN score is the minimum, and
+ * among equal scores, and among NaNs, the lowest index wins.  A stored label is therefore always in [0, K): a row that holds a NaN
+ * gets label 0, as does a row whose scores are all NaN through inf - inf; a centroid that holds a NaN wins every row at the lowest
+ * such index; a row whose scores all overflow to +inf gets label 0.  sq_dist of such a row is NaN or +-inf.  Finite rows of the same
+ * call are not affected. */
 int si_kmeans_assign(si_ctx* ctx, const float* feats, int64_t rows, int D, const float* centroids, int K, int64_t* labels,
                      float* sq_dist, si_stream_t stream);
 

@@ -1307,6 +1307,16 @@ int si_launch_codebook_metrics(si_ctx* ctx, const float* feats, int B, int T, in
     return SI_OK;
 }
 
+// arg-min with torch.argmin's rules, the mirror image of argmax_better: a NaN is the minimum, ties (and several NaNs) go to the
+// lowest index.  Both kernels seed a thread's running best with its first candidate unconditionally; a thread without one carries
+// (+inf, INT_MAX) and loses to any real index, so a stored label is always in [0, K) -- also for a row that holds a NaN or whose
+// scores all overflow.  For finite scores the comparisons are those of `s < best` / `(ob == best && oi < besti)`.
+__device__ __forceinline__ bool argmin_better(float a, int ai, float b, int bi) {
+    const bool an = a != a, bn = b != b;
+    if (an != bn) return an;
+    if (!an && a != b) return a < b;
+    return ai < bi;
+}
 // k-means unit assignment: label = argmin_k ||x - c_k||^2 = argmin_k (||c_k||^2 - 2 x.c_k), the
 // quantity sklearn's KMeans.predict minimises (I_da/scripts/inpainting.py:204-205 calls it on HuBERT features; same
 // distance as I_ea/dataset/km_label.py:20-24).  One workgroup per row; thread k walks centroid k (L2-resident table).
@@ -1327,13 +1337,13 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restr
         float dot = 0.f, cc = 0.f;
         for (int d = 0; d < D; ++d) { const float cv = c[d]; dot = fmaf(xs[d], cv, dot); cc = fmaf(cv, cv, cc); }
         const float s = cc - 2.f * dot;
-        if (s < best) { best = s; besti = k; }                      // ascending k per thread: first minimum wins
+        if (besti == 0x7fffffff || argmin_better(s, k, best, besti)) { best = s; besti = k; }   // ascending k per thread: first minimum wins
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ob = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(besti, o, 64);
-        if (ob < best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        if (argmin_better(ob, oi, best, besti)) { best = ob; besti = oi; }
         xx += __shfl_xor(xx, o, 64);
     }
     __shared__ float xparts[4];
@@ -1341,7 +1351,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restr
     __syncthreads();
     if (threadIdx.x == 0) {
         float b = bs[0]; int i = bi[0];
-        for (int w = 1; w < 4; ++w) if (bs[w] < b || (bs[w] == b && bi[w] < i)) { b = bs[w]; i = bi[w]; }
+        for (int w = 1; w < 4; ++w) if (argmin_better(bs[w], bi[w], b, i)) { b = bs[w]; i = bi[w]; }
         labels[row] = i;
         if (dist) dist[row] = b + (xparts[0] + xparts[1] + xparts[2] + xparts[3]);   // squared distance to the winner
     }
@@ -1419,7 +1429,7 @@ __global__ __launch_bounds__(256) void kmeans_mfma_kernel(const float* __restric
             if (k < K) {
                 const float dot = (dots[0][r][c] + dots[1][r][c]) + (dots[2][r][c] + dots[3][r][c]);
                 const float sv = cnorm[k] - 2.f * dot;
-                if (sv < best) { best = sv; besti = k; }                // ascending k per thread: first minimum wins
+                if (besti == 0x7fffffff || argmin_better(sv, k, best, besti)) { best = sv; besti = k; }   // ascending k per thread: first minimum wins
             }
         }
     }
@@ -1427,7 +1437,7 @@ __global__ __launch_bounds__(256) void kmeans_mfma_kernel(const float* __restric
     for (int o = 1; o < 8; o <<= 1) {                                   // the 8 threads of a row are 8 consecutive lanes
         const float ob = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(besti, o, 64);
-        if (ob < best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        if (argmin_better(ob, oi, best, besti)) { best = ob; besti = oi; }
     }
     const long row = row0 + (tid >> 3);
     if ((tid & 7) == 0 && row < rows) {

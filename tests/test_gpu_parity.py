@@ -437,5 +437,9 @@ def test_mel_and_waveform_metrics_match_oracle():
         want, got = R.sisdr(est, ref), met.sisdr(est, ref)
         print(f"sisdr noise {noise}: oracle {want:.4f} dB, GPU {got:.4f} dB")
         assert abs(got - want) <= (1e-3 if noise > 0 else 3.0)         # the noiseless case is eps / rounding residue in both
-    batch = eng.ctx.mel_metrics(torch.stack([synth.synth_mel(1, 40, 80, 7)[0]] * 2).cuda(), torch.stack([synth.synth_mel(1, 40, 80, 8)[0]] * 2).cuda())
-    assert batch.shape == (2, 3) and torch.equal(batch[0], batch[1])
+    # a batch of two DIFFERENT clips: each row is that clip's single-clip result, bit for bit (a kernel that read clip 0 twice would not be)
+    a, b = torch.cat([synth.synth_mel(1, 40, 80, 7), synth.synth_mel(1, 40, 80, 9)]).cuda(), torch.cat([synth.synth_mel(1, 40, 80, 8), synth.synth_mel(1, 40, 80, 10)]).cuda()
+    batch = eng.ctx.mel_metrics(a, b)
+    assert batch.shape == (2, 3) and not torch.equal(batch[0], batch[1])
+    for i in range(2):
+        assert torch.equal(batch[i], eng.ctx.mel_metrics(a[i:i + 1].contiguous(), b[i:i + 1].contiguous())[0])
