@@ -31,6 +31,8 @@
  *                                                                             I_ea/predict.py:79-80,104,203-207
  *   si_quiet_runs        <- nothing the reference computes: it has no detection.  The call supplies the `mask:` values
  *                           (start_pos_in_sec, end_pos_in_sec) that a user of the script types by hand      I_ea/predict.py:85-90
+ *   si_dead_runs         <- nothing the reference computes either: si_quiet_runs for dropouts that are not digital silence -- held
+ *                           samples, mutes relative to the file's peak.  It has no detection                I_ea/predict.py:85-90
  *   si_patch_rate        <- the same write-out for a file at ANY sample rate, which the script resamples on the way in and never
  *                           brings back                                       I_ea/predict.py:79-80,203-207
  *   si_cut_rate          <- that resampling on the way in, for the context clips alone instead of the whole file (with si_cut_clips'
@@ -568,7 +570,7 @@ int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_ta
  * (start, len) rows SORTED BY START: rows [0, min(total, max_runs)) of runs (device int32 (max_runs, 2)) are written, rows at and past
  * that are not touched, and n_runs (device int32 (1)) receives the TOTAL number of such runs whether or not they all fit.  The same
  * input gives the same bytes (no atomics; plain stores).  max_runs = 0 counts only (runs may be NULL).  Needs no weights.  Scratch
- * (one bit per sample, five words per 2048 samples) is the context's own and is reused by the next call in stream order.
+ * (one bit per sample, six words per 2048 samples) is the context's own and is reused by the next call in stream order.
  * SI_EINVAL before any launch, naming the argument, for: NULL x or n_runs; NULL runs with max_runs > 0; n < 1 or n > 2^31 - 1 - 2048;
  * threshold negative or NaN; min_len < 1; max_runs < 0. */
 int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs,
@@ -703,6 +705,36 @@ int si_cut_rate_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int cha
                    const int32_t* start, int C, int L, const si_sinc_filter* filt, float* out, si_stream_t stream);
 int si_patch_rate_ch(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int channels, int channel, int sr, const si_rate_table* table,
                      const float* gen, int Lrow, const float* gain, const si_sinc_filter* filt, void* out, si_stream_t stream);
+
+/* ---- Held-sample and peak-relative dropouts ---------------------------------------------------------------------------
+ * The reference has no detection: the script's user types the one mask into predict.yaml (I_ea/predict.py:85-90).  si_quiet_runs finds
+ * digital silence against a fixed number; this call finds the other two things an underrun leaves behind -- a sample that is HELD (the
+ * last one repeated, a DC level) and a mute that is not exact zeros (dither, a noise floor), judged against the file's own peak -- with
+ * si_quiet_runs' output and limits.  x is si_quiet_runs_ch's: (n, channels) interleaved, fp32 or int16; channels = 1 is a mono file
+ * (channel 0 or -1) and gives the bytes of the mono layout.  For one channel x[0 .. n) (elements i * channels + c):
+ *   peak      the largest |x[i]| over the FINITE samples (NaN and +-inf are skipped; int16 magnitudes are taken in int32, |-32768| =
+ *             32768, exact in fp32); 0 when none qualifies.  Samples at and past n, and in front of the base, do not exist.
+ *   T         max(threshold, fl32(rel_threshold * peak)), the product ONE fp32 multiply.  With rel_threshold == 0 the peak is not
+ *             computed and T = threshold.
+ *   quiet(i)  |x[i]| <= T, as si_quiet_runs: NaN is loud, -0.0 is quiet.
+ *   link(i)   for 1 <= i < n: |x[i] - x[i - 1]| <= held_tol.  fp32: the subtraction in fp32, one rounding; a NaN neighbour and
+ *             inf - inf give false.  int16: the subtraction in int32, the magnitude compared as a float (32767 - (-32768) = 65535, no
+ *             wrap).  There is no link at i = 0 and none to x[n].
+ *   held(i)   link(i) or link(i + 1): the sample equals a neighbour to within held_tol.
+ *   dead(i)   (kind & SI_DEAD_QUIET and quiet(i)) or (kind & SI_DEAD_HELD and held(i)).
+ * channel >= 0 scans that channel: its neighbours are elements (i +- 1) * channels + channel, never the adjacent elements, and the peak
+ * is taken over that channel's elements.  channel = -1 is JOINT: a sample time is dead when EVERY channel's element is dead, each by
+ * its own links, and the peak is one value over all elements of the file.
+ * The result is every maximal run of dead samples of at least min_len samples: int32 (start, len) rows sorted by start, rows [0,
+ * min(total, max_runs)) written and the rows past them untouched, the total in n_runs (device int32 (1)); the same input gives the same
+ * bytes (no atomics; plain stores).  threshold_out, when not NULL, is a device fp32 word that receives T.  Scratch is si_quiet_runs'
+ * (one more word per 2048 samples, and two).
+ * SI_EINVAL before any launch, naming the argument, for: everything si_quiet_runs_ch refuses; kind outside 1 .. 3; rel_threshold NaN or
+ * outside [0, 1]; held_tol negative or NaN (checked whether or not kind has SI_DEAD_HELD). */
+#define SI_DEAD_QUIET 1
+#define SI_DEAD_HELD 2
+int si_dead_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int kind, float threshold, float rel_threshold,
+                 float held_tol, int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

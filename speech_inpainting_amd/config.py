@@ -67,6 +67,9 @@ class PredictConfig:
     detect_channels: str = "each"  # `channels:` inside `detect:` (needs long: {rate: file}), for a multi-channel file: "each" (default:
                                    # every channel is scanned and repaired on its own) or "joint" (a gap is where ALL channels are
                                    # quiet, and is repaired in all of them: DESIGN.md 4.18)
+    detect_dead: Optional[dict] = None  # `kind:`, `rel_threshold:` and `held_tol:` inside `detect:`: kind "quiet" (default),
+                                        # "held" (a sample repeated, a DC level) or "any"; rel_threshold a fraction of the file's peak in
+                                        # [0, 1]; held_tol in full-scale units like threshold.  {quiet, 0.0, 0.0} is the detection of 4.15
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -161,7 +164,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
             if long_cfg["batch"] < 1 or long_cfg["clip_s"] <= 2 * long_cfg["context_s"]:
                 raise ValueError(f"{path}: `long:` needs batch >= 1 and clip_s > 2 * context_s, got {long_cfg}")
-        detect_cfg, detect_channels = None, "each"
+        detect_cfg, detect_channels, detect_dead = None, "each", None
         if "detect" in data:
             dm = data["detect"] if data["detect"] is not None else {}
             if not isinstance(dm, dict):
@@ -173,6 +176,19 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                 raise ValueError(f"{path}: give either `detect:` (the gaps are found) or `mask:` / `masks:` (the gaps are given), not both")
             detect_cfg = {"threshold": 0.0, "min_ms": 5.0, "max_ms": 400.0, "pad_frames": 0}
             dm = dict(dm)
+            detect_dead = {"kind": "quiet", "rel_threshold": 0.0, "held_tol": 0.0}
+            if "kind" in dm:
+                detect_dead["kind"] = dm.pop("kind")
+                if detect_dead["kind"] not in ("quiet", "held", "any"):
+                    raise ValueError(f"{path}: detect.kind = {detect_dead['kind']!r}: quiet (the default: |x| <= the threshold), held (a sample "
+                                     f"repeated, a DC level) or any")
+            for key in ("rel_threshold", "held_tol"):
+                if key in dm:
+                    detect_dead[key] = float(dm.pop(key))
+                    if not detect_dead[key] >= 0:
+                        raise ValueError(f"{path}: detect.{key} = {detect_dead[key]} is negative")
+            if detect_dead["rel_threshold"] > 1:
+                raise ValueError(f"{path}: detect.rel_threshold = {detect_dead['rel_threshold']} is a fraction of the file's peak, at most 1")
             if "channels" in dm:
                 detect_channels = dm.pop("channels")
                 if detect_channels not in ("each", "joint"):
@@ -182,7 +198,8 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                     raise ValueError(f"{path}: detect.channels needs `long: {{rate: file}}` (at rate: {long_rate} the file is mixed down to one channel)")
             for key, val in dm.items():
                 if key not in detect_cfg:
-                    raise ValueError(f"{path}: unknown key `{key}` in `detect:` (it takes threshold, min_ms, max_ms, pad_frames, channels)")
+                    raise ValueError(f"{path}: unknown key `{key}` in `detect:` (it takes threshold, min_ms, max_ms, pad_frames, channels, kind, rel_threshold, "
+                                     f"held_tol)")
                 detect_cfg[key] = int(val) if key == "pad_frames" else float(val)
                 if not detect_cfg[key] >= 0:
                     raise ValueError(f"{path}: detect.{key} = {detect_cfg[key]} is negative")
@@ -202,7 +219,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
             raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, detect=detect_cfg,
-            detect_channels=detect_channels)
+            detect_channels=detect_channels, detect_dead=detect_dead)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

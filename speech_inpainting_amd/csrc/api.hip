@@ -2258,9 +2258,21 @@ int si_cut_rate_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int cha
 }
 
 // ---- dropout detection
-static int quiet_runs_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n, int channels, int channel, float threshold, int min_len,
-                           int32_t* runs, int max_runs, int32_t* n_runs, si_stream_t stream) {
-    if (!ctx) return SI_EINVAL;
+// The detector's scratch for n samples: the context's own, grown on demand (a context is single-threaded and its calls stream-ordered by contract).
+static int det_scratch_reserve(si_ctx* ctx, int n, si_stream_t stream) {
+    const size_t need = si_detect_scratch_bytes(n);
+    if (need > ctx->det_scratch_cap) {
+        if (ctx->det_scratch) { SI_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream))); SI_HIP_CHECK(hipFree(ctx->det_scratch)); ctx->det_scratch = nullptr; ctx->det_scratch_cap = 0; }
+        const size_t cap = std::max(need, (size_t)1 << 20);
+        SI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx->det_scratch), cap));
+        ctx->det_scratch_cap = cap;
+    }
+    return SI_OK;
+}
+
+// What si_quiet_runs and its siblings refuse, in one order.
+static int quiet_runs_check(si_ctx* ctx, const char* fn, bool inter, const void* x, int n, int channels, int channel, float threshold, int min_len,
+                            const int32_t* runs, int max_runs, const int32_t* n_runs) {
     if (inter && si_check_channels(ctx, fn, channels, channel, -1) != SI_OK) return SI_EINVAL;
     if (!x) return SI_FAIL_FN("x is NULL");
     if (!n_runs) return SI_FAIL_FN("n_runs is NULL");
@@ -2269,14 +2281,15 @@ static int quiet_runs_call(si_ctx* ctx, const char* fn, bool inter, const void* 
     if (n < 1 || (long)n > SI_MAX_REC) return SI_FAIL_FN("n = %d samples, outside 1 .. %ld", n, SI_MAX_REC);
     if (!(threshold >= 0.f)) return SI_FAIL_FN("threshold = %g is negative or NaN", (double)threshold);
     if (min_len < 1) return SI_FAIL_FN("min_len = %d samples, at least 1", min_len);
+    return SI_OK;
+}
+
+static int quiet_runs_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n, int channels, int channel, float threshold, int min_len,
+                           int32_t* runs, int max_runs, int32_t* n_runs, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (quiet_runs_check(ctx, fn, inter, x, n, channels, channel, threshold, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
     SI_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t need = si_detect_scratch_bytes(n);
-    if (need > ctx->det_scratch_cap) {                                 // (a context is single-threaded and its calls stream-ordered by contract)
-        if (ctx->det_scratch) { SI_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream))); SI_HIP_CHECK(hipFree(ctx->det_scratch)); ctx->det_scratch = nullptr; ctx->det_scratch_cap = 0; }
-        const size_t cap = std::max(need, (size_t)1 << 20);
-        SI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx->det_scratch), cap));
-        ctx->det_scratch_cap = cap;
-    }
+    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
     if (inter)
         return si_launch_quiet_runs_ch(ctx, x, is_pcm16 != 0, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch,
                                        static_cast<hipStream_t>(stream));
@@ -2291,6 +2304,21 @@ int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float thresho
 int si_quiet_runs_ch(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, float threshold, int min_len, int32_t* runs,
                      int max_runs, int32_t* n_runs, si_stream_t stream) {
     return quiet_runs_call(ctx, "si_quiet_runs_ch", true, x, is_pcm16, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, stream);
+}
+
+// ---- held-sample and peak-relative dropouts
+int si_dead_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int kind, float threshold, float rel_threshold,
+                 float held_tol, int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream) {
+    const char* fn = "si_dead_runs";
+    if (!ctx) return SI_EINVAL;
+    if (quiet_runs_check(ctx, fn, true, x, n, channels, channel, threshold, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
+    if (kind < 1 || kind > 3) return SI_FAIL_FN("kind = %d, outside 1 .. 3 (SI_DEAD_QUIET | SI_DEAD_HELD)", kind);
+    if (!(rel_threshold >= 0.f && rel_threshold <= 1.f)) return SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 1]", (double)rel_threshold);
+    if (!(held_tol >= 0.f)) return SI_FAIL_FN("held_tol = %g is negative or NaN", (double)held_tol);
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
+    return si_launch_dead_runs(ctx, x, is_pcm16 != 0, n, channels, channel, kind, threshold, rel_threshold, held_tol, min_len, runs, max_runs, n_runs,
+                               threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
 }
 
 #undef SI_FAIL_FN

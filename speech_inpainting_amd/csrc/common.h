@@ -348,7 +348,7 @@ int si_launch_patch_regions(si_ctx* ctx, const float* orig, const SiRegions& rt,
 // ------------------------------------------------------------------------------------------------
 // dropout detection (detect_kernels.hip)
 // ------------------------------------------------------------------------------------------------
-// bytes of scratch the passes need for n samples: one bit per sample and five words per chunk of 2048 samples
+// bytes of scratch the passes need for n samples: one bit per sample, six words per chunk of 2048 samples and two more
 size_t si_detect_scratch_bytes(int n);
 // x device fp32 or int16 (n) -> runs (max_runs, 2) = the maximal runs of |x| <= thr of at least min_len samples, sorted by start, and
 // *n_runs = how many there are (all of them, whether or not they fit); arguments validated by the caller, scratch 16-byte aligned
@@ -357,6 +357,10 @@ int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float th
 // the same for an interleaved x (n sample times of `channels` channels): channel c >= 0 alone, or all jointly (c < 0)
 int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
                             int max_runs, int32_t* n_runs, char* scratch, hipStream_t st);
+// the maximal runs of DEAD samples: quiet against max(thr, rel * peak) (kind & 1), held = within tol of a neighbour of
+// the same channel (kind & 2); channels = 1 is a one-channel file; *thr_out (device, may be null) receives the effective threshold
+int si_launch_dead_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, int kind, float thr, float rel, float tol,
+                        int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // repair at the file's own sample rate (rate_kernels.hip)

@@ -3,6 +3,8 @@
 // over one bit per sample and a few words per chunk of DT_CHUNK samples:
 //   detect_bits_kernel     the quiet bits of a chunk (one byte per thread: 8 consecutive samples) + the chunk's summary {lead, trail}
 //   detect_bits_ch_kernel  the same pass 1 over an INTERLEAVED recording: one channel of it, or all of them jointly
+//   detect_peak*_kernel, detect_dead*_kernel  pass 0 and another pass 1: the bit means DEAD -- quiet against a threshold
+//                          that follows the recording's peak, or held (equal to a neighbour) -- and the passes below do not care
 //   detect_carry_kernel    carry[c] = the length of the quiet run that ends exactly in front of chunk c (a segmented scan, one workgroup)
 //   detect_runs_kernel     <false>: the qualifying runs that END in each chunk, counted; <true>: written at offset[c] + rank
 //   detect_offsets_kernel  the exclusive scan of the counts (one workgroup) and the total, a plain store
@@ -283,17 +285,204 @@ __global__ __launch_bounds__(256) void detect_offsets_kernel(const int32_t* __re
     if (t == 0) *n_runs = v0;
 }
 
+// ------------------------------------------------------------------------------------------------ dead samples
+// A richer pass 1 in front of the same passes 2 - 5: sample i is DEAD when it is quiet against a threshold that may follow the
+// recording's peak, T = max(thr, rel * peak), or HELD -- equal to a neighbour of its own channel to within tol.
+//   detect_peak_kernel / _ch   pass 0 (rel > 0 only): the largest finite magnitude of a chunk, one word per chunk
+//   detect_peak_final_kernel   one workgroup: the largest of those words -> {peak, T} in two device words
+//   detect_dead_kernel / _ch   pass 1: the dead bits of a chunk and its summary (dt_store_chunk)
+
+// The magnitude of a sample as the bits of a non-negative finite float, which order as ints; NaN and +-inf count as 0 (skipped).
+__device__ __forceinline__ int dt_mag_bits(float v) { const int b = __float_as_int(v) & 0x7fffffff; return b < 0x7f800000 ? b : 0; }
+__device__ __forceinline__ int dt_mag_bits(int16_t v) { const int a = v; return __float_as_int((float)(a < 0 ? -a : a)); }
+
+// |a - b| <= tol.  fp32: one fp32 subtraction; a NaN neighbour and inf - inf compare false.  int16: the difference in int32 (65535 at most).
+__device__ __forceinline__ bool dt_link(float a, float b, float tol) { return __builtin_fabsf(a - b) <= tol; }
+__device__ __forceinline__ bool dt_link(int16_t a, int16_t b, float tol) { const int d = (int)a - (int)b; return (float)(d < 0 ? -d : d) <= tol; }
+
+__device__ __forceinline__ float dt_shfl_up1(float v) { return __shfl_up(v, 1, 64); }
+__device__ __forceinline__ int16_t dt_shfl_up1(int16_t v) { return (int16_t)__shfl_up((int)v, 1, 64); }
+__device__ __forceinline__ float dt_shfl_down1(float v) { return __shfl_down(v, 1, 64); }
+__device__ __forceinline__ int16_t dt_shfl_down1(int16_t v) { return (int16_t)__shfl_down((int)v, 1, 64); }
+
+// This thread's eight consecutive samples of a one-channel chunk, as detect_bits_kernel reads them: two / one 16-byte loads from an
+// aligned base, else the chunk staged through LDS (tile: DT_CHUNK elements) with coalesced element loads.  Samples at and past n read 0.
+// Every thread of the workgroup calls it.
+template <typename T>
+union DtEight { uint4 q[sizeof(T) / 2]; T e[8]; };
+
+template <typename T>
+__device__ __forceinline__ void dt_load_eight(const T* __restrict__ x, int n, int c0, int len, T* tile, DtEight<T>& u) {
+    const int t = threadIdx.x, g = c0 + t * 8;
+    if ((reinterpret_cast<size_t>(x) & 15) == 0) {
+        if (g + 8 <= n) {
+#pragma unroll
+            for (int i = 0; i < (int)sizeof(T) / 2; ++i) u.q[i] = reinterpret_cast<const uint4*>(x + g)[i];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) u.e[j] = g + j < n ? x[g + j] : T(0);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = j * 256 + t;
+            tile[i] = i < len ? x[c0 + i] : T(0);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < (int)sizeof(T) / 2; ++i) u.q[i] = reinterpret_cast<const uint4*>(tile + t * 8)[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pass 0: the peak
+// grid (chunks), 256 threads.  cpeak[c] = the largest dt_mag_bits over the chunk's samples below n (0 when none is finite).
+template <typename T>
+__global__ __launch_bounds__(256) void detect_peak_kernel(const T* __restrict__ x, int n, int32_t* __restrict__ cpeak) {
+    __shared__ __attribute__((aligned(16))) T tile[DT_CHUNK];
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    DtEight<T> u;
+    dt_load_eight(x, n, c0, len, tile, u);
+    int m = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m = max(m, t * 8 + j < len ? dt_mag_bits(u.e[j]) : 0);
+    int top;
+    (void)dt_block_excl(m, 0, sw, top, DtMax());
+    if (t == 0) cpeak[c] = top;
+}
+
+// The same over an interleaved recording: a chunk is DT_CHUNK sample times.  channel >= 0: that channel's elements (a stride of ch);
+// channel < 0: every element of the chunk, consecutive lanes on consecutive elements.
+template <typename T>
+__global__ __launch_bounds__(256) void detect_peak_ch_kernel(const T* __restrict__ x, int n, int ch, int channel, int32_t* __restrict__ cpeak) {
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    const T* __restrict__ xc = x + (size_t)c0 * ch;
+    int m = 0;
+    if (channel < 0) {
+        for (int e = t; e < len * ch; e += 256) m = max(m, dt_mag_bits(xc[e]));
+    } else {
+        for (int i = t; i < len; i += 256) m = max(m, dt_mag_bits(xc[(size_t)i * ch + channel]));
+    }
+    int top;
+    (void)dt_block_excl(m, 0, sw, top, DtMax());
+    if (t == 0) cpeak[c] = top;
+}
+
+// One workgroup: the largest per-chunk word, walked in tiles of DT_TILE chunks -> pk[0] = peak, pk[1] = T = max(thr, fl32(rel * peak)).
+__global__ __launch_bounds__(256) void detect_peak_final_kernel(const int32_t* __restrict__ cpeak, int nchunks, float thr, float rel,
+                                                                float* __restrict__ pk) {
+    __shared__ int sw[4];
+    const int t = threadIdx.x;
+    int m = 0;
+    for (int base = 0; base < nchunks; base += DT_TILE) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = base + t * 4 + k;
+            if (c < nchunks) m = max(m, cpeak[c]);
+        }
+    }
+    int top;
+    (void)dt_block_excl(m, 0, sw, top, DtMax());
+    if (t == 0) {
+        const float peak = __int_as_float(top), prod = __fmul_rn(rel, peak);
+        pk[0] = peak;
+        pk[1] = thr > prod ? thr : prod;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pass 1: dead bits + summary
+// grid (chunks), 256 threads, one channel.  Thread t owns samples [g, g + 8), g = c0 + 8 t, loaded as detect_bits_kernel loads them; it
+// needs x[g - 1] and x[g + 8] as well: the neighbour lane's edge sample through a wave shuffle, and on lanes 0 and 63 of a wave (the
+// wave's and the chunk's edges) one extra load each -- only when that sample exists, 0 <= index < n.  link(i) = |x[i] - x[i - 1]| <= tol
+// exists for 1 <= i < n alone, so sample 0 has no left link, sample n - 1 no right one, and whatever lies in front of the base or
+// behind the input is never read.  thr_dev, when given, holds T (pass 0); else T = thr.  Block 0 leaves T in *thr_out when asked.
+template <typename T>
+__global__ __launch_bounds__(256) void detect_dead_kernel(const T* __restrict__ x, int n, int kind, float thr, const float* __restrict__ thr_dev,
+                                                          float tol, float* __restrict__ thr_out, uint8_t* __restrict__ bitmap,
+                                                          int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    __shared__ __attribute__((aligned(16))) T tile[DT_CHUNK];
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x, lane = t & 63;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0), g = c0 + t * 8;
+    const float Tq = thr_dev ? *thr_dev : thr;
+    if (thr_out && c == 0 && t == 0) *thr_out = Tq;
+    DtEight<T> u;
+    dt_load_eight(x, n, c0, len, tile, u);
+    T prev = dt_shfl_up1(u.e[7]), next = dt_shfl_down1(u.e[0]);
+    if (lane == 0) prev = (g >= 1 && g - 1 < n) ? x[g - 1] : T(0);
+    if (lane == 63) next = g + 8 < n ? x[g + 8] : T(0);
+    unsigned lk = 0;                                                  // bit j: link(g + j), j = 0 .. 8
+#pragma unroll
+    for (int j = 0; j <= 8; ++j) {
+        const T a = j == 0 ? prev : u.e[j - 1], b = j == 8 ? next : u.e[j];
+        lk |= (g + j >= 1 && g + j < n && dt_link(b, a, tol)) ? 1u << j : 0u;
+    }
+    unsigned q = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) q |= (t * 8 + j < len && dt_quiet(u.e[j], Tq)) ? 1u << j : 0u;
+    const unsigned held = (lk | lk >> 1) & 0xffu;                     // link(i) needs i < n, so no bit at or past len is set
+    const unsigned b = ((kind & SI_DEAD_QUIET) ? q : 0u) | ((kind & SI_DEAD_HELD) ? held : 0u);
+    dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
+}
+
+// The same pass over an INTERLEAVED recording, through an image of the chunk in dynamic LDS with a one-sample-time halo on both sides:
+// sample times c0 - 1 .. c0 + DT_CHUNK, (DT_CHUNK + 2) m elements, m = ch for the joint mode (every element of those times, consecutive
+// lanes on consecutive elements) and 1 for one channel (that channel's elements).  A time outside [0, n) does not exist: it is not
+// loaded, and a link to it is false.  Channel k's neighbours in the image are m elements away: elements (i +- 1) ch + k of the file,
+// never the adjacent ones.  Joint: a time is dead when every channel's element is, each by its own links.
+template <typename T>
+__global__ __launch_bounds__(256) void detect_dead_ch_kernel(const T* __restrict__ x, int n, int ch, int channel, int kind, float thr,
+                                                             const float* __restrict__ thr_dev, float tol, float* __restrict__ thr_out,
+                                                             uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    extern __shared__ __attribute__((aligned(16))) char dt_img[];
+    __shared__ int sw[4];
+    T* img = reinterpret_cast<T*>(dt_img);
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    const int m = channel < 0 ? ch : 1;
+    const float Tq = thr_dev ? *thr_dev : thr;
+    if (thr_out && c == 0 && t == 0) *thr_out = Tq;
+    for (int e = t; e < (DT_CHUNK + 2) * m; e += 256) {
+        const long time = (long)c0 - 1 + e / m;
+        const bool exists = time >= 0 && time < n;
+        img[e] = exists ? x[(size_t)time * ch + (channel < 0 ? e % m : channel)] : T(0);
+    }
+    __syncthreads();
+    unsigned b = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int p = t * 8 + j, i = c0 + p;                          // image position p + 1
+        const bool left = i >= 1 && i < n, right = i + 1 < n;         // link(i), link(i + 1) exist
+        bool dead = p < len;
+        for (int k = 0; k < m; ++k) {
+            const T v = img[(p + 1) * m + k];
+            const bool qt = (kind & SI_DEAD_QUIET) && dt_quiet(v, Tq);
+            const bool hd = (kind & SI_DEAD_HELD) && ((left && dt_link(v, img[p * m + k], tol)) || (right && dt_link(img[(p + 2) * m + k], v, tol)));
+            dead = dead && (qt || hd);
+        }
+        b |= dead ? 1u << j : 0u;
+    }
+    dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
+}
+
 // ------------------------------------------------------------------------------------------------ launcher
 size_t si_detect_scratch_bytes(int n) {
     const size_t chunks = ((size_t)n + DT_CHUNK - 1) / DT_CHUNK;
-    return chunks * 256 + 5 * ((chunks * sizeof(int32_t) + 15) & ~(size_t)15);
+    return chunks * 256 + 6 * ((chunks * sizeof(int32_t) + 15) & ~(size_t)15) + 16;     // + the peak's word per chunk and {peak, T}
 }
+
+// What si_dead_runs adds to a detection call; the quiet routes pass none.
+struct DtDead { int kind; float rel, tol; float* thr_out; };
 
 // The caller (si_quiet_runs, si_quiet_runs_ch) checked every argument.  scratch: si_detect_scratch_bytes(n) bytes, 16-byte aligned.
 // channels = 0: x is one channel of n samples (detect_bits_kernel); channels >= 1: x is interleaved, n sample times of `channels`
 // channels, and `channel` picks one of them or, below 0, all of them jointly (detect_bits_ch_kernel).  Passes 2 - 5 are the same launches.
+// dead != nullptr: pass 1 is detect_dead(_ch)_kernel, behind pass 0 when dead->rel > 0; nullptr: the launches above.
 static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
-                     int32_t* n_runs, char* scratch, hipStream_t st) {
+                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr) {
     const int chunks = (int)(((long)n + DT_CHUNK - 1) / DT_CHUNK);
     const size_t words = ((size_t)chunks * sizeof(int32_t) + 15) & ~(size_t)15;
     uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch);
@@ -303,9 +492,43 @@ static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels
     int32_t* carry = reinterpret_cast<int32_t*>(p + 2 * words);
     int32_t* count = reinterpret_cast<int32_t*>(p + 3 * words);
     int32_t* offset = reinterpret_cast<int32_t*>(p + 4 * words);
+    int32_t* cpeak = reinterpret_cast<int32_t*>(p + 5 * words);
+    float* pk = reinterpret_cast<float*>(p + 6 * words);              // {peak, T}
     const double bits = (double)chunks * 256.0, sums = (double)chunks * 4.0;
+    const double samples = (double)n * (channels ? channels : 1) * (pcm16 ? 2.0 : 4.0);
 
-    if (channels == 0) {
+    if (dead) {
+        const float* thr_dev = nullptr;
+        if (dead->rel > 0.f) {
+            si_prof_begin(ctx, "detect_peak", 0.0, samples + sums, st);
+            if (channels == 0) {
+                if (pcm16) detect_peak_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, cpeak);
+                else detect_peak_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, cpeak);
+            } else {
+                if (pcm16) detect_peak_ch_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, channels, channel, cpeak);
+                else detect_peak_ch_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, channels, channel, cpeak);
+            }
+            si_prof_end(ctx, st);
+            SI_HIP_CHECK(hipGetLastError());
+            si_prof_begin(ctx, "detect_peak_final", 0.0, sums + 8.0, st);
+            detect_peak_final_kernel<<<dim3(1), 256, 0, st>>>(cpeak, chunks, thr, dead->rel, pk);
+            si_prof_end(ctx, st);
+            SI_HIP_CHECK(hipGetLastError());
+            thr_dev = pk + 1;
+        }
+        if (channels == 0) {
+            si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
+            if (pcm16) detect_dead_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
+            else detect_dead_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
+        } else {
+            const size_t lds = (size_t)(DT_CHUNK + 2) * (channel < 0 ? channels : 1) * (pcm16 ? sizeof(int16_t) : sizeof(float));   // 65 600 bytes at 8 fp32 channels
+            const void* kern = pcm16 ? reinterpret_cast<const void*>(&detect_dead_ch_kernel<int16_t>) : reinterpret_cast<const void*>(&detect_dead_ch_kernel<float>);
+            if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
+            si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
+            if (pcm16) detect_dead_ch_kernel<int16_t><<<dim3(chunks), 256, lds, st>>>(static_cast<const int16_t*>(x), n, channels, channel, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
+            else detect_dead_ch_kernel<float><<<dim3(chunks), 256, lds, st>>>(static_cast<const float*>(x), n, channels, channel, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
+        }
+    } else if (channels == 0) {
         si_prof_begin(ctx, "detect_bits", 0.0, (double)n * (pcm16 ? 2.0 : 4.0) + bits + 2.0 * sums, st);
         if (pcm16) detect_bits_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, thr, bitmap, lead, trail);
         else detect_bits_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, thr, bitmap, lead, trail);
@@ -350,4 +573,11 @@ int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float th
 int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
                             int max_runs, int32_t* n_runs, char* scratch, hipStream_t st) {
     return dt_launch(ctx, x, pcm16, n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st);
+}
+
+// channels = 1 is a one-channel file: its elements are the mono call's, and so are its kernels.
+int si_launch_dead_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, int kind, float thr, float rel, float tol,
+                        int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st) {
+    const DtDead dead{kind, rel, tol, thr_out};
+    return dt_launch(ctx, x, pcm16, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, &dead);
 }

@@ -16,7 +16,10 @@ all with the recording's own sample count.  The whole-clip diagnostics (`hifi_ma
 are NOT produced on this route: no generator pass over a whole recording exists there.  With a `detect:` mapping ({threshold: 0.0,
 min_ms: 5.0, max_ms: 400.0, pad_frames: 0}) beside `long:` and instead of `mask:` / `masks:` the gaps are FOUND: the runs of
 |x| <= threshold of at least min_ms in the file's own samples (engine.find_gaps); each gap and each skipped run is
-printed and `gaps.json` is written beside the three waves.  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
+printed and `gaps.json` is written beside the three waves.  `detect:` also takes `kind:` (quiet, the default; held: samples that
+repeat a neighbour, as an underrun or a DC level leaves them; any), `rel_threshold:` (a fraction of the file's own peak: the
+threshold is max(threshold, rel_threshold * peak)) and `held_tol:` (full scale, like threshold); off their defaults the effective
+threshold is printed and gaps.json records `kind` and `T` (engine.find_dead_runs).  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
 on the way out: the three waves keep the file's own rate and sample type (an int16 file stays int16), and patched.wav holds the file's
 own samples, bit for bit, outside the cross-fades (engine.patch_file).
 With `feed: contexts` beside `rate: file` the recording is not resampled as a whole on the way in either: only the context clips
@@ -345,23 +348,45 @@ def _detect_gaps(cfg: PredictConfig, engine: InpaintingEngine, raw: np.ndarray, 
                  min_context: int, save_dir: str) -> List[Tuple[int, int]]:
     """The `detect:` key of the `long:` route: the gaps found in the file's OWN samples at the file's rate, where a dropout is still
     exact zeros (the resampler's ringing fills it in at 22.05 kHz).  A mono int16 file is scanned as the int16 it holds, the threshold
-    scaled by 32768 (an exact scaling: the same samples are quiet).  Prints every gap and every skipped run, writes gaps.json."""
+    scaled by 32768 (an exact scaling: the same samples are quiet).  Prints every gap and every skipped run, writes gaps.json.
+    With `kind:`, `rel_threshold:` or `held_tol:` off their defaults it also prints the effective threshold and records
+    `kind` and `T` in gaps.json."""
     from scipy.io import wavfile
     d = cfg.detect
-    x, thr = raw, d["threshold"]
+    x, scale = raw, 1.0
     pcm_file = wavfile.read(cfg.wave_path)[1]
     if pcm_file.dtype == np.int16 and pcm_file.ndim == 1:
-        x, thr = pcm_file, d["threshold"] * 32768.0
+        x, scale = pcm_file, 32768.0
     n_rec, lim = engine.recording_frames(n22, clip_frames)
     max_ms = d["max_ms"] if n_rec <= clip_frames else min(d["max_ms"], 20.0 * (clip_frames - 2 * min_context))
-    found = engine.find_gaps(x, sr_file, thr, d["min_ms"], max_ms, d["pad_frames"], None, fade, n_rec, lim)
+    found = engine.find_gaps(x, sr_file, d["threshold"] * scale, d["min_ms"], max_ms, d["pad_frames"], None, fade, n_rec, lim,
+                             **dead_keywords(cfg.detect_dead, scale))
+    report = _dead_report(cfg, found, scale)
     for k, (pos, lm) in enumerate(found["gaps"]):
         print(f"Detected gap {k} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s")
     for pos, lm, why in found["skipped"]:
         print(f"Skipped quiet run = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s: {why}")
     with open(os.path.join(save_dir, "gaps.json"), "w") as f:
-        json.dump({"gaps": [list(g) for g in found["gaps"]], "skipped": [list(g) for g in found["skipped"]]}, f)
+        json.dump({"gaps": [list(g) for g in found["gaps"]], "skipped": [list(g) for g in found["skipped"]], **report}, f)
     return found["gaps"]
+
+
+def dead_keywords(dead: Optional[dict], scale: float) -> dict:
+    """`detect:`'s kind / rel_threshold / held_tol as find_gaps and conceal_file take them, for a file whose samples are `scale` times
+    full-scale units (32768 for an int16 file, scanned as the int16 it holds): held_tol is scaled as the threshold is -- exact, a power
+    of two -- and rel_threshold, a fraction of the file's own peak, is not."""
+    dead = dead if dead is not None else {"kind": "quiet", "rel_threshold": 0.0, "held_tol": 0.0}
+    return {"kind": dead["kind"], "rel_threshold": dead["rel_threshold"], "held_tol": dead["held_tol"] * scale}
+
+
+def _dead_report(cfg: PredictConfig, found: dict, scale: float) -> dict:
+    """What gaps.json gains when the detection went through find_dead_runs: `kind`, and `T`, the effective threshold in the units the
+    file was scanned in (one per channel for `channels: each`).  Printed too.  Empty at the defaults: gaps.json is then what it was."""
+    if "threshold" not in found:
+        return {}
+    T, unit = found["threshold"], "int16 steps" if scale != 1.0 else "full scale"
+    print(f"Detection kind = {cfg.detect_dead['kind']}, effective threshold T = {T} ({unit})")
+    return {"kind": cfg.detect_dead["kind"], "T": T}
 
 
 def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> int:
@@ -430,9 +455,11 @@ def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_
     kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"], feed=cfg.long_feed)
     if cfg.detect is not None:                                                     # conceal_file: its own budget for a gap, its own fade
         d = cfg.detect
-        thr = d["threshold"] * 32768.0 if x.dtype == np.int16 else d["threshold"]   # an int16 file is scanned as the int16 it holds
+        scale = 32768.0 if x.dtype == np.int16 else 1.0                             # an int16 file is scanned as the int16 it holds
         joint = cfg.detect_channels == "joint"
-        out = engine.conceal_file(dev, sr_file, thr, d["min_ms"], d["max_ms"], d["pad_frames"], detect=cfg.detect_channels, **kw)
+        out = engine.conceal_file(dev, sr_file, d["threshold"] * scale, d["min_ms"], d["max_ms"], d["pad_frames"], detect=cfg.detect_channels,
+                                  **dead_keywords(cfg.detect_dead, scale), **kw)
+        report = _dead_report(cfg, out, scale)
         found = [(out["gaps"], out["skipped"])] if joint else list(zip(out["gaps"], out["skipped"]))
         for c, (gaps_c, skipped_c) in enumerate(found):
             who = "all channels" if joint else f"channel {c}"
@@ -442,7 +469,7 @@ def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_
                 print(f"Skipped quiet run of {who} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s: {why}")
         lists = lambda v: [list(g) for g in v] if joint else [[list(g) for g in one] for one in v]
         with open(os.path.join(save_dir, "gaps.json"), "w") as f:
-            json.dump({"gaps": lists(out["gaps"]), "skipped": lists(out["skipped"])}, f)
+            json.dump({"gaps": lists(out["gaps"]), "skipped": lists(out["skipped"]), **report}, f)
         per = [out["gaps"]] * ch if joint else out["gaps"]
     else:
         per = [sorted(cfg.gaps) if cfg.gaps is not None else [(cfg.mask_pos, cfg.mask_frames)]] * ch

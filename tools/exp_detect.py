@@ -7,8 +7,13 @@ warm-up, device-synchronised wall clock per call:
       falls, the length filter, stack -- the baseline a caller would write
   (c) engine.conceal_recording(pcm=True): find the gaps, then patch_recording
   (d) engine.patch_recording(pcm=True) with the known gaps
+  (e) engine.find_dead_runs(kind="held") on the same recording with its gaps filled by the HELD last sample instead of zeros
+      (si_dead_runs: pass 1 with the links, the four scan passes), and (f) its torch formulation: the links
+      |x[i] - x[i-1]| <= 0, held = link(i) | link(i+1), then (b)'s run extraction
+  (g) engine.find_dead_runs(kind="any", rel_threshold=1e-3) on that file (pass 0 reads the samples once more for the peak), and (h)
+      its torch formulation: the peak over the finite samples, T = fp32(1e-3) * peak, (abs() <= T) | held
 
-Prints whether (a) equals (b) and (c) equals (d) bit for bit, one line per repeat, the medians, and -- from a separate, untimed run
+Prints whether (a) equals (b), (e) equals (f), (g) equals (h) and (c) equals (d) bit for bit, one line per repeat, the medians, and -- from a separate, untimed run
 under the library's profiler -- the per-kernel times of the detect_* family and the effective bytes per second of the whole call
 (the recording's bytes / the family's summed time).
 usage: python tools/exp_detect.py [--repeats 7] [--minutes 10] [--gaps 60] [--pcm16]"""
@@ -61,14 +66,41 @@ def torch_runs():
     return torch.stack([start[keep], (end - start)[keep]], dim=1).to(torch.int32)
 
 
+# the same recording with every gap filled by the last sample before it (x[s - 1] is a sample of the tile, not a zero)
+held22 = wave22.clone()
+for p, l in gaps:
+    held22[441 * p:441 * (p + l)] = held22[441 * p - 1]
+xh = eng.to_int16(held22) if a.pcm16 else held22
+
+
+def torch_dead(rel):
+    v = xh.to(torch.int32) if a.pcm16 else xh
+    link = (v[1:] - v[:-1]).abs() <= 0
+    no = link.new_zeros(1)
+    dead = torch.cat([no, link]) | torch.cat([link, no])
+    if rel > 0:
+        mag = v.abs().to(torch.float32)
+        peak = mag[torch.isfinite(mag)].max()
+        dead = dead | (mag <= torch.tensor(rel, dtype=torch.float32, device=dev) * peak)
+    q = dead.to(torch.int8)
+    d = torch.diff(q, prepend=q.new_zeros(1), append=q.new_zeros(1))
+    start, end = torch.nonzero(d == 1).flatten(), torch.nonzero(d == -1).flatten()
+    keep = end - start >= MIN_LEN
+    return torch.stack([start[keep], (end - start)[keep]], dim=1).to(torch.int32)
+
+
 variants = {"a": lambda: eng.find_quiet_runs(x, 0.0, MIN_LEN), "b": torch_runs,
-            "c": lambda: eng.conceal_recording(wave22, **KW), "d": lambda: eng.patch_recording(wave22, gaps, **KW)}
-oa, ob, oc, od = (fn() for fn in variants.values())
+            "c": lambda: eng.conceal_recording(wave22, **KW), "d": lambda: eng.patch_recording(wave22, gaps, **KW),
+            "e": lambda: eng.find_dead_runs(xh, "held", min_len=MIN_LEN), "f": lambda: torch_dead(0.0),
+            "g": lambda: eng.find_dead_runs(xh, "any", rel_threshold=1e-3, min_len=MIN_LEN), "h": lambda: torch_dead(1e-3)}
+oa, ob, oc, od, oe, of, og, oh = (fn() for fn in variants.values())
 torch.cuda.synchronize()
 print(f"recording of {N22} samples ({N22 / 22050 / 60:.2f} min, {x.element_size()} bytes per sample), {len(gaps)} gaps of {LM} frames zeroed")
 print(f"(a) equals (b): {torch.equal(oa, ob)} ({oa.shape[0]} runs);  (c) found the gaps: {oc['gaps'] == gaps};  (c) equals (d) bit for bit: fp32",
       torch.equal(oc["patched"].view(torch.int32), od["patched"].view(torch.int32)), " int16", torch.equal(oc["patched_pcm"], od["patched_pcm"]))
-del oa, ob, oc, od
+print(f"(e) equals (f): {torch.equal(oe, of)} ({oe.shape[0]} runs, {int((oe[:, 1] == 441 * LM + 1).sum())} of them a gap and the sample it holds);  "
+      f"(g) equals (h): {torch.equal(og, oh)} ({og.shape[0]} runs)")
+del oa, ob, oc, od, oe, of, og, oh
 for fn in variants.values():
     for _ in range(WARMUP):
         fn()
@@ -84,7 +116,8 @@ for r in range(a.repeats):
     print(f"repeat {r}: " + "  ".join(f"({k}) {ms[k][-1]:.3f} ms" for k in variants), flush=True)
 med = {k: statistics.median(v) for k, v in ms.items()}
 print("median ms/recording: " + "  ".join(f"({k}) {med[k]:.3f}" for k in variants))
-print(f"spread of (d) over {a.repeats} repeats: {max(ms['d']) - min(ms['d']):.3f} ms;  (c) - (d) {med['c'] - med['d']:+.3f} ms;  (a) / (b) {med['a'] / med['b']:.3f}")
+print(f"spread of (d) over {a.repeats} repeats: {max(ms['d']) - min(ms['d']):.3f} ms;  (c) - (d) {med['c'] - med['d']:+.3f} ms;  (a) / (b) {med['a'] / med['b']:.3f};  "
+      f"(e) / (f) {med['e'] / med['f']:.3f};  (g) / (h) {med['g'] / med['h']:.3f};  (e) / (a) {med['e'] / med['a']:.3f};  (g) / (a) {med['g'] / med['a']:.3f}")
 # per-kernel device times, from a run of their own under the library's event profiler (every launch bracketed: not a step time)
 eng.ctx.profile_start(1000)
 for _ in range(10):
@@ -93,3 +126,12 @@ rows = {e["name"]: e for e in eng.ctx.profile_stop() if e["name"].startswith("de
 total = sum(e["ms"] for e in rows.values()) / 10
 print(f"si_quiet_runs under the profiler: {total * 1e3:.1f} us per call = {x.numel() * x.element_size() / (total * 1e-3) / 1e9:.1f} GB/s of the recording;  "
       + "  ".join(f"{n} {e['ms'] / e['launches'] * 1e3:.1f} us" for n, e in rows.items()))
+for what, call in (("kind=held", lambda: eng.find_dead_runs(xh, "held", min_len=MIN_LEN)),
+                   ("kind=any, rel_threshold=1e-3", lambda: eng.find_dead_runs(xh, "any", rel_threshold=1e-3, min_len=MIN_LEN))):
+    eng.ctx.profile_start(1000)
+    for _ in range(10):
+        call()
+    rows = {e["name"]: e for e in eng.ctx.profile_stop() if e["name"].startswith("detect_")}
+    total = sum(e["ms"] for e in rows.values()) / 10
+    print(f"si_dead_runs ({what}) under the profiler: {total * 1e3:.1f} us per call = {xh.numel() * xh.element_size() / (total * 1e-3) / 1e9:.1f} GB/s of the "
+          f"recording;  " + "  ".join(f"{n} {e['ms'] / e['launches'] * 1e3:.1f} us" for n, e in rows.items()))
