@@ -305,7 +305,9 @@ def test_f0_vqvae_front_matches_oracle(B, T):
 
 def test_f0_encoder_single_launch_equals_the_layer_by_layer_form():
     """si_f0_encoder_forward as ONE persistent launch (activations in LDS) against its 37-launch form (SI_F0_FUSED=0, also the route
-    of tracks too long for LDS): bit-identical, for the hubert_lut.json shape at 4 s / 10 s tracks and a 30 s track that does not fit."""
+    of tracks too long for LDS): bit-identical, for the hubert_lut.json shape.  The single launch fits LDS up to T = 877 frames (4.4 s
+    of 5 ms frames): the 4 s track and the longest one that fits run fused -- the profile must say so -- while the 10 s and the 30 s
+    track take the 37 launches either way (tests/test_gpu_io_ops.py pins the boundary itself)."""
     from speech_inpainting_amd import native, synth
     from speech_inpainting_amd.arch import HubertArch, VocoderArch
     ctx = native.NativeContext(native.make_desc(HubertArch.tiny(), VocoderArch.tiny(), 10), torch.device("cuda:0"))
@@ -313,9 +315,14 @@ def test_f0_encoder_single_launch_equals_the_layer_by_layer_form():
     from speech_inpainting_amd.engine import pack_f0_encoder
     w = pack_f0_encoder(synth.synth_f0_vqvae_state(desc, 20, seed=5), desc).cuda()
     g = torch.Generator().manual_seed(9)
-    for B, T in ((16, 797), (3, 2000), (2, 6000)):
+    for B, T, fused in ((16, 797, True), (3, 877, True), (3, 2000, False), (2, 6000, False)):
         f0 = torch.randn(B, 1, T, generator=g).cuda()
-        a = ctx.f0_encoder(desc, w, f0)
+        ctx.profile_start(4000)
+        try:
+            a = ctx.f0_encoder(desc, w, f0)
+        finally:
+            route = {e["name"]: e["launches"] for e in ctx.profile_stop()}
+        assert route == ({"f0enc_fused": 1} if fused else {"f0enc_conv1d": 37}), (B, T, route)
         with scoped_env({"SI_F0_FUSED": "0"}):
             b = ctx.f0_encoder(desc, w, f0)
         torch.cuda.synchronize()
