@@ -176,7 +176,8 @@ int si_hubert_forward_padded(si_ctx* ctx, const float* wav, const int32_t* mask_
  * of DIFFERENT lengths in one call, each clip's result EQUAL to that clip run alone -- the reference's script handles one file of
  * any length per invocation (I_ea/predict.py:76-207) -- and not the padded semantics of si_hubert_forward_padded (whose GroupNorm
  * sees the padding, as HuggingFace's does).  wav (B, N): clip b occupies the first sample_len[b] samples of its row, the rest is
- * ignored.  sample_len: HOST int32 (B) (launch grids depend on it).  mask_start / mask_len as si_hubert_forward.
+ * ignored (held for every ragged entry point, with NaN and 1e30 there: tests/test_gpu_scratch.py).
+ * sample_len: HOST int32 (B) (launch grids depend on it).  mask_start / mask_len as si_hubert_forward.
  * Per clip: the processor's statistics over its own samples, conv0's GroupNorm statistics over its own conv rows, every strided
  * convolution stops at its own length (modeling_hubert.py:664-677), the transformer runs on the packed rows of all clips (the
  * positional conv's zero padding begins at the clip's own last frame, attention sees its own frames only).

@@ -838,7 +838,7 @@ __global__ __launch_bounds__(256) void attention_bf16in_kernel(const unsigned sh
         __syncthreads();
         *reinterpret_cast<u32x4_t*>(Ks + kr * ATB_LDK + 8 * kj) = kv;
         {   // V transposed: four packed 32-bit words (key pair) per thread
-            const bool in0 = k0 + 2 * vrp < T, in1 = k0 + 2 * vrp + 1 < T;     // zero, not a clamped copy: P * V must not see NaN payloads of stale rows
+            const bool in0 = k0 + 2 * vrp < T, in1 = k0 + 2 * vrp + 1 < T;     // zero past the clip (the clamped copy is the clip's own row T - 1 and P = 0 there: the same sums either way)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const unsigned lo = in0 ? (w0[e >> 1] >> (16 * (e & 1))) & 0xffffu : 0u, hi = in1 ? (w1[e >> 1] >> (16 * (e & 1))) & 0xffffu : 0u;
