@@ -149,6 +149,22 @@ int si_weights_device_ptr(si_ctx* ctx, void** ptr, size_t* nbytes);
  * run it once before the first use of a blob that came from si_alloc_weights. */
 int si_weights_check(si_ctx* ctx);
 
+/* The plan and the packer WITHOUT a device (csrc/weights_host.cpp: plain host code; both calls work with zero visible devices and
+ * read the SI_VOC_OPREADY / SI_VOC_RES16 options from the environment exactly as si_create does).
+ * si_plan_weights: the descriptor check of si_create (SI_EINVAL with a message that names the field, through si_last_error(NULL);
+ * the bounds are listed in csrc/weights_host.h) and the byte size of the packed blob.
+ * si_pack_weights_host: the bytes si_load_weights copies to the device -- it calls the same function -- header included, into
+ * out[0 .. *needed).  *needed (may be NULL) is set as soon as the desc is accepted.  Order of the checks: desc (SI_EINVAL), capacity
+ * (SI_ENOMEM when out is NULL or capacity < *needed), index and tensors (SI_EWEIGHTS, naming the tensor or the index line), host
+ * memory for the image (SI_ENOMEM).  Every required tensor is looked up and its shape compared BEFORE the image is allocated.
+ * Refused with SI_EWEIGHTS besides missing / mis-shaped tensors: an empty or malformed index, a name listed twice, dims that
+ * overflow, an offset that is negative, misaligned or past the blob, a weight-norm row of zero norm, a non-finite value in anything
+ * that is packed (a FINITE weight beyond +-65504 is clamped silently in the fp16 mode).  On failure nothing is written to `out`;
+ * the message goes to err[0 .. errcap) (may be NULL).  No C++ exception leaves either call. */
+int si_plan_weights(const si_model_desc* desc, size_t* total_bytes);
+int si_pack_weights_host(const si_model_desc* desc, const void* host_blob, size_t nbytes, const char* index, void* out, size_t capacity,
+                         size_t* needed, char* err, size_t errcap);
+
 /* Workspace (device scratch) needed for a batch of B clips of N samples and Tm mel frames. */
 int si_workspace_bytes(si_ctx* ctx, int B, int N, int Tm, size_t* out);
 

@@ -1,15 +1,9 @@
 // api.hip -- C ABI of libsi_hip.so (include/si_hip.h): context, checkpoint packing, forward orchestration.
 //
-// Host-side work done here, once per checkpoint load:
-//   * weight-norm folding, w = g * v / ||v||  (generator convs: norm over all dims but 0,
-//     I_ea/hifi_gan/models.py:125-132; positional conv: over all dims but 2, modeling_hubert.py:78)
-//   * re-layout of every Conv1d / ConvTranspose1d / Linear weight into the tap-GEMM form
-//     W[group][tap][n][ci] (ci contiguous), q/k/v fused into one (3H, H) matrix, ConvTranspose1d split into
-//     its `stride` output phases (n = phase*Cout + co, taps q = 0..k/stride-1 read input row u-q)
-//   * conversion to the arithmetic of the model desc (fp32 / bf16 / bf16 hi+lo)
-//   * codebook tables: centred centroids, 1/||centred||, raw centroids (I_ea/loss_fn.py:10-14)
-// The result is ONE packed device blob whose layout depends only on the model desc, so ranks that did not
-// read the checkpoint can receive it by a single RCCL broadcast (si_alloc_weights + si_weights_device_ptr).
+// The checkpoint packing itself (weight-norm folding, re-layout into the tap-GEMM form, the casts, the codebook tables), the
+// descriptor check and the layout plan are plain host code in weights_host.cpp; this file keeps the context and the device.
+// The result is ONE packed device blob whose layout depends only on the model desc and two environment options, so ranks that
+// did not read the checkpoint can receive it by a single RCCL broadcast (si_alloc_weights + si_weights_device_ptr).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -22,41 +16,7 @@
 
 #include "common.h"
 
-namespace {
-
-struct HostTensor {
-    const float* data = nullptr;
-    std::vector<long> shape;
-    long numel() const { long n = 1; for (long d : shape) n *= d; return n; }
-};
-
-struct GemmW {              // one tap-GEMM weight inside the packed blob
-    size_t w = 0, w_lo = 0, bias = 0;   // byte offsets (bias: 0 = none)
-    int Cin = 0, N = 0, Npad = 0, ntaps = 0, groups = 1, math = 0;
-    bool has_bias = false;
-};
-
-struct LayerW { GemmW qkv, out, ffn1, ffn2; size_t ln1_g, ln1_b, ln2_g, ln2_b; };
-struct ConvW { GemmW g; size_t ln_g = 0, ln_b = 0; };
-struct ResW { GemmW c1[SI_MAX_DIL], c2[SI_MAX_DIL]; };
-
-struct Layout {
-    size_t total = 0;
-    // encoder
-    size_t conv0_w, conv0_bias, conv0_g, conv0_b;
-    std::vector<ConvW> convs;            // conv layers 1..n-1
-    size_t fp_ln_g, fp_ln_b; GemmW proj;
-    GemmW pos; size_t enc_ln_g, enc_ln_b;
-    std::vector<LayerW> layers;
-    size_t head_ln_g, head_ln_b; GemmW head;
-    size_t cb_centered, cb_raw, cb_rnorm;
-    // vocoder
-    GemmW pre; std::vector<GemmW> ups; std::vector<ResW> rbs;   // rbs[stage*num_rb + j]
-    size_t post_w, post_b; int post_C = 0;
-    int mel_ld = 0;                      // padded mel channel count (conv_pre Cin)
-};
-
-}  // namespace
+using namespace siw;   // GemmW / Layout, the plan and the packer: weights_host.h
 
 struct si_ctx {
     int device = 0;
@@ -80,7 +40,8 @@ struct si_ctx {
     int num_cus = 0;
     std::map<const void*, size_t> dyn_lds;   // per kernel: dynamic-LDS limit already raised on this context's device
     // arithmetic-path options, read from the environment when the context is created (all default to 1)
-    bool opt_voc_opready = true, opt_voc_res16 = true, opt_enc_opready = true, opt_att_bf16 = true, opt_enc_lingemm = true;
+    PackOpts popt;                           // SI_VOC_OPREADY / SI_VOC_RES16: the two options that move bytes of the packed image
+    bool opt_enc_opready = true, opt_att_bf16 = true, opt_enc_lingemm = true;
     bool opt_enc_posconv = true;             // the positional conv on posconv.hip in the bf16 encoder mode (SI_ENC_POSCONV=0: the generic tap-GEMM)
     int opt_ln_fuse = 1;                     // post-LN layers, bf16 mode: LayerNorm outputs read as residuals are recomputed in the GEMM epilogues (SI_ENC_LNFUSE=0: written)
     int opt_voc_upsgemm = 1;                 // the generator's early upsamplers on gemmcu.hip's TC instantiations (SI_VOC_UPSGEMM=0: the tap-GEMM)
@@ -106,8 +67,6 @@ struct si_ctx {
     char* det_scratch = nullptr;             // bitmap + per-chunk words of si_quiet_runs (library-owned, stream-ordered reuse, grown on demand)
     size_t det_scratch_cap = 0;
 };
-
-static char g_create_err[512] = "";
 
 int si_fail(si_ctx* ctx, int code, const char* fmt, ...) {
     char* dst = ctx ? ctx->err : g_create_err;
@@ -210,388 +169,11 @@ void si_prof_end(si_ctx* ctx, hipStream_t st) {
     ctx->prof_open = -1;
 }
 
-// ------------------------------------------------------------------------------------------------ layout
 namespace {
 
-size_t elem_bytes(int math) { return math == SI_MATH_F32 ? 4 : 2; }
-
-struct Planner {
-    size_t cur = 0;
-    size_t take(size_t bytes) { size_t o = cur; cur += (bytes + 255) / 256 * 256; return o; }
-    size_t floats(size_t n) { return take(n * 4); }
-    GemmW gemm(int math, int groups, int ntaps, int N, int Cin, bool bias) {
-        GemmW g;
-        g.math = math; g.groups = groups; g.ntaps = ntaps; g.N = N; g.Cin = Cin; g.has_bias = bias;
-        g.Npad = si_round_up(N, si_pick_bn(N));
-        const size_t n = (size_t)groups * ntaps * g.Npad * Cin;
-        g.w = take(n * elem_bytes(math));
-        if (math == SI_MATH_BF16X3) g.w_lo = take(n * 2);
-        if (bias) g.bias = floats((size_t)groups * N);
-        return g;
-    }
-};
-
-// Channel count of upsampling stage i as the kernels see it.  On the fp16 activation stream a stage narrower than 32 channels
-// (I_da's unit vocoder ends on 16) is carried PADDED to 32: its weights, biases and therefore activations are zero in the extra
-// channels, and the stage runs on the 32-channel chain kernel (three launches per stage) instead of 18 tap-GEMM launches that
-// move the stream at a tenth of the HBM rate; `conv_post` reads the padded rows with zero weights.  Other modes keep the real width
-// (their per-stage taps are compared against the reference's tensors).
-int stage_channels(const si_ctx* ctx, int i) {
-    const int real = ctx->d.up_initial_channel >> (i + 1);
-    const bool r16 = ctx->opt_voc_opready && ctx->opt_voc_res16 && ctx->d.vocoder_math == SI_MATH_F16;
-    return (r16 && real < 32 && real >= 4) ? 32 : real;
-}
-
-int plan_layout(si_ctx* ctx) {
-    const si_model_desc& d = ctx->d;
-    Layout& L = ctx->lay;
-    Planner P;
-    P.take(256);                                           // offset 0 is reserved to mean "absent"
-    const int em = d.encoder_math, vm = d.vocoder_math;
-    const int H = d.hidden_size;
-    // encoder
-    L.conv0_w = P.floats((size_t)d.conv_dim[0] * d.conv_kernel[0]);
-    L.conv0_bias = d.conv_bias ? P.floats(d.conv_dim[0]) : 0;
-    L.conv0_g = P.floats(d.conv_dim[0]);
-    L.conv0_b = P.floats(d.conv_dim[0]);
-    L.convs.clear();
-    for (int i = 1; i < d.num_conv; ++i) {
-        ConvW c;
-        c.g = P.gemm(em, 1, d.conv_kernel[i], d.conv_dim[i], d.conv_dim[i - 1], d.conv_bias != 0);
-        if (d.feat_norm_layer) { c.ln_g = P.floats(d.conv_dim[i]); c.ln_b = P.floats(d.conv_dim[i]); }
-        L.convs.push_back(c);
-    }
-    const int CF = d.conv_dim[d.num_conv - 1];
-    L.fp_ln_g = P.floats(CF); L.fp_ln_b = P.floats(CF);
-    L.proj = P.gemm(em, 1, 1, H, CF, true);
-    L.pos = P.gemm(em, d.pos_conv_groups, d.pos_conv_kernel, H / d.pos_conv_groups, H / d.pos_conv_groups, true);
-    L.enc_ln_g = P.floats(H); L.enc_ln_b = P.floats(H);
-    L.layers.clear();
-    for (int l = 0; l < d.num_layers; ++l) {
-        LayerW w;
-        w.qkv = P.gemm(em, 1, 1, 3 * H, H, true);
-        w.out = P.gemm(em, 1, 1, H, H, true);
-        w.ln1_g = P.floats(H); w.ln1_b = P.floats(H);
-        w.ffn1 = P.gemm(em, 1, 1, d.intermediate_size, H, true);
-        w.ffn2 = P.gemm(em, 1, 1, H, d.intermediate_size, true);
-        w.ln2_g = P.floats(H); w.ln2_b = P.floats(H);
-        L.layers.push_back(w);
-    }
-    L.head_ln_g = P.floats(H); L.head_ln_b = P.floats(H);
-    L.head = P.gemm(SI_MATH_F32, 1, 1, d.codebook_dim, H, true);       // the arg-max input stays fp32
-    L.cb_centered = P.floats((size_t)d.num_clusters * d.codebook_dim);
-    L.cb_raw = P.floats((size_t)d.num_clusters * d.codebook_dim);
-    L.cb_rnorm = P.floats(d.num_clusters);
-    // vocoder
-    L.mel_ld = si_round_up(d.num_mels, 32);
-    const int C0 = d.up_initial_channel;
-    L.pre = P.gemm(vm, 1, 7, C0, L.mel_ld, true);
-    L.ups.clear(); L.rbs.clear();
-    int c = C0;
-    for (int i = 0; i < d.num_ups; ++i) {
-        const int u = d.up_rates[i], k = d.up_kernels[i], cout = stage_channels(ctx, i);
-        L.ups.push_back(P.gemm(vm, 1, (k + u - 1) / u, u * cout, c, true));   // taps q = j div u; absent (phase, tap) pairs stay zero
-        c = cout;
-        for (int j = 0; j < d.num_rb; ++j) {
-            ResW r;
-            for (int n = 0; n < d.num_dil; ++n) {
-                r.c1[n] = P.gemm(vm, 1, d.rb_kernels[j], c, c, true);
-                if (d.resblock_type != 2) r.c2[n] = P.gemm(vm, 1, d.rb_kernels[j], c, c, true);   // ResBlock2 has one conv per dilation
-            }
-            L.rbs.push_back(r);
-        }
-    }
-    L.post_C = c;
-    L.post_w = P.floats((size_t)7 * c);
-    L.post_b = P.floats(1);
-    L.total = P.cur;
-    return SI_OK;
-}
-
-// The packed blob's layout is a function of the model desc AND of the context's arithmetic-path options (stage_channels: the
-// padded widths of the fp16 stream).  A rank that receives the blob by broadcast must have planned the SAME layout as the rank
-// that packed it; the first 32 bytes of the blob (offset 0 is reserved) carry a fingerprint of the plan so that a mismatch is an
-// error instead of silently mis-read weights.
-struct BlobHeader { uint32_t magic, version; uint64_t fingerprint, total; uint64_t reserved; };
-constexpr uint32_t BLOB_MAGIC = 0x42574953u;   // "SIWB"
-uint64_t layout_fingerprint(const si_ctx* ctx) {
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const void* p, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(p); for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } };
-    mix(&ctx->d, sizeof(ctx->d));
-    const Layout& L = ctx->lay;
-    const uint64_t total = L.total; mix(&total, 8);
-    for (int i = 0; i < ctx->d.num_ups; ++i) { const int c = stage_channels(ctx, i); mix(&c, 4); mix(&L.ups[i].w, sizeof(size_t)); }
-    mix(&L.post_w, sizeof(size_t)); mix(&L.post_C, 4); mix(&L.cb_raw, sizeof(size_t)); mix(&L.head.w, sizeof(size_t));
-    return h;
-}
-BlobHeader blob_header(const si_ctx* ctx) { return BlobHeader{BLOB_MAGIC, (uint32_t)SI_ABI_VERSION, layout_fingerprint(ctx), (uint64_t)ctx->lay.total, 0}; }
-
-int check_desc(si_ctx* ctx, const si_model_desc* d) {
-    if (!d || d->struct_size != (int32_t)sizeof(si_model_desc))
-        return si_fail(ctx, SI_EINVAL, "si_model_desc size mismatch (got %d, library expects %zu)", d ? d->struct_size : -1,
-                       sizeof(si_model_desc));
-    if (d->num_conv < 2 || d->num_conv > SI_MAX_CONV) return si_fail(ctx, SI_EINVAL, "num_conv=%d out of range", d->num_conv);
-    if (d->num_ups < 1 || d->num_ups > SI_MAX_UPS) return si_fail(ctx, SI_EINVAL, "num_ups=%d out of range", d->num_ups);
-    if (d->num_rb < 1 || d->num_rb > SI_MAX_RB || d->num_dil < 1 || d->num_dil > SI_MAX_DIL)
-        return si_fail(ctx, SI_EINVAL, "resblock shape %dx%d out of range", d->num_rb, d->num_dil);
-    if (d->hidden_size <= 0 || d->num_heads <= 0 || d->hidden_size != d->num_heads * 64)
-        return si_fail(ctx, SI_EINVAL, "hidden_size=%d / heads=%d: the attention kernel needs head_dim 64", d->hidden_size, d->num_heads);
-    if (d->pos_conv_groups <= 0 || d->hidden_size % d->pos_conv_groups || (d->hidden_size / d->pos_conv_groups) % 16)
-        return si_fail(ctx, SI_EINVAL, "positional conv: hidden/groups must be a multiple of 16");
-    for (int i = 0; i < d->num_conv; ++i)
-        if (d->conv_dim[i] % 16 || d->conv_kernel[i] <= 0 || d->conv_stride[i] <= 0)
-            return si_fail(ctx, SI_EINVAL, "conv layer %d: dim %d must be a multiple of 16", i, d->conv_dim[i]);
-    if (d->hidden_size % 16 || d->intermediate_size % 16) return si_fail(ctx, SI_EINVAL, "hidden / intermediate sizes must be multiples of 16");
-    if (d->codebook_dim <= 0 || d->codebook_dim > 128 || d->num_clusters <= 0) return si_fail(ctx, SI_EINVAL, "codebook %dx%d unsupported", d->num_clusters, d->codebook_dim);
-    int c = d->up_initial_channel;
-    for (int i = 0; i < d->num_ups; ++i) {
-        // output length rate * L needs padding (k - u) / 2 exact; k need not be a multiple of u (I_da's 11 / 5)
-        if (d->up_kernels[i] < d->up_rates[i] || (d->up_kernels[i] - d->up_rates[i]) % 2)
-            return si_fail(ctx, SI_EINVAL, "upsample %d: kernel %d must be >= rate %d with an even difference", i, d->up_kernels[i], d->up_rates[i]);
-        if (c % 32) return si_fail(ctx, SI_EINVAL, "upsample %d: %d input channels must be a multiple of 32", i, c);
-        c /= 2;
-    }
-    if (c % 4) return si_fail(ctx, SI_EINVAL, "final generator width %d must be a multiple of 4", c);
-    for (int j = 0; j < d->num_rb; ++j)
-        if (d->rb_kernels[j] % 2 == 0) return si_fail(ctx, SI_EINVAL, "resblock kernel %d must be odd", d->rb_kernels[j]);
-    if (d->resblock_type < 0 || d->resblock_type > 2) return si_fail(ctx, SI_EINVAL, "resblock_type %d: 1 (ResBlock1) or 2 (ResBlock2)", d->resblock_type);
-    for (int m : {d->encoder_math, d->vocoder_math})
-        if (m < SI_MATH_F32 || m > SI_MATH_F16) return si_fail(ctx, SI_EINVAL, "unknown math mode %d", m);
-    return SI_OK;
-}
-
-// ---- host packing helpers ------------------------------------------------------------------------
-unsigned short h_f2bf(float f) {
-    unsigned u; memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-// fp32 -> fp16, round to nearest even, saturating at +-65504 (NaN stays NaN)
-unsigned short h_f2h(float f) {
-    if (f != f) return 0x7e00;
-    const float c = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
-    const _Float16 h = (_Float16)c;
-    unsigned short u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-float h_bf2f(unsigned short h) { unsigned u = ((unsigned)h) << 16; float f; memcpy(&f, &u, 4); return f; }
-
-struct Packer {
-    si_ctx* ctx;
-    std::map<std::string, HostTensor> t;
-    std::vector<char> out;
-    int rc = SI_OK;
-
-    const HostTensor* get(const std::string& name, std::initializer_list<long> shape) {
-        auto it = t.find(name);
-        if (it == t.end()) { if (!rc) rc = si_fail(ctx, SI_EWEIGHTS, "checkpoint is missing tensor '%s'", name.c_str()); return nullptr; }
-        std::vector<long> want(shape);
-        if (it->second.shape != want) {
-            std::ostringstream a, b;
-            for (long v : it->second.shape) a << v << ' ';
-            for (long v : want) b << v << ' ';
-            if (!rc) rc = si_fail(ctx, SI_EWEIGHTS, "tensor '%s' has shape [%s] but the model needs [%s]", name.c_str(), a.str().c_str(), b.str().c_str());
-            return nullptr;
-        }
-        return &it->second;
-    }
-    bool has(const std::string& n) const { return t.count(n) != 0; }
-    float* fptr(size_t off) { return reinterpret_cast<float*>(out.data() + off); }
-    void copy_floats(size_t off, const std::string& name, long n) {
-        const HostTensor* h = get(name, {n});
-        if (h) memcpy(out.data() + off, h->data, (size_t)n * 4);
-    }
-    // Folded weight of a conv-like module (shape `shape`); norm_dim = the dim weight_norm keeps.
-    bool folded(const std::string& prefix, std::initializer_list<long> shape, int norm_dim, std::vector<float>& w) {
-        std::vector<long> sh(shape);
-        long n = 1; for (long v : sh) n *= v;
-        if (has(prefix + ".weight")) {
-            const HostTensor* h = get(prefix + ".weight", shape);
-            if (!h) return false;
-            w.assign(h->data, h->data + n);
-            return true;
-        }
-        std::string gn = prefix + ".weight_g", vn = prefix + ".weight_v";
-        if (!has(gn)) { gn = prefix + ".parametrizations.weight.original0"; vn = prefix + ".parametrizations.weight.original1"; }
-        if (!has(gn)) { if (!rc) rc = si_fail(ctx, SI_EWEIGHTS, "checkpoint has neither '%s.weight' nor a weight-norm pair", prefix.c_str()); return false; }
-        const HostTensor* v = get(vn, shape);
-        if (!v) return false;
-        auto git = t.find(gn);
-        const long keep = sh[norm_dim];
-        if (git->second.numel() != keep) { if (!rc) rc = si_fail(ctx, SI_EWEIGHTS, "'%s' must hold %ld magnitudes", gn.c_str(), keep); return false; }
-        long inner = 1; for (size_t i = norm_dim + 1; i < sh.size(); ++i) inner *= sh[i];
-        std::vector<double> ss(keep, 0.0);
-        for (long i = 0; i < n; ++i) { const long kidx = (i / inner) % keep; ss[kidx] += (double)v->data[i] * v->data[i]; }
-        w.resize(n);
-        for (long i = 0; i < n; ++i) {
-            const long kidx = (i / inner) % keep;
-            // same operation order as torch._weight_norm: v * (g / norm), all in fp32
-            const float nrm = (float)std::sqrt(ss[kidx]);
-            w[i] = v->data[i] * (git->second.data[kidx] / nrm);
-        }
-        return true;
-    }
-    // store element (g, tap, n, ci) of a tap-GEMM weight
-    void put(const GemmW& G, int g, int tap, int n, int ci, float v) {
-        const size_t idx = (((size_t)g * G.ntaps + tap) * G.Npad + n) * G.Cin + ci;
-        if (G.math == SI_MATH_F32) { fptr(G.w)[idx] = v; return; }
-        if (G.math == SI_MATH_F16) { reinterpret_cast<unsigned short*>(out.data() + G.w)[idx] = h_f2h(v); return; }
-        const unsigned short hi = h_f2bf(v);
-        reinterpret_cast<unsigned short*>(out.data() + G.w)[idx] = hi;
-        if (G.math == SI_MATH_BF16X3) reinterpret_cast<unsigned short*>(out.data() + G.w_lo)[idx] = h_f2bf(v - h_bf2f(hi));
-    }
-    // Conv1d weight (Cout, Cin/groups, k) -> W[g][tap][n][ci]; cin_valid < G.Cin leaves zero padding
-    void conv(const GemmW& G, const std::vector<float>& w, int cout_total, int cin_g, int k) {
-        const int npg = cout_total / G.groups;
-        for (int co = 0; co < cout_total; ++co)
-            for (int ci = 0; ci < cin_g; ++ci)
-                for (int tp = 0; tp < k; ++tp)
-                    put(G, co / npg, tp, co % npg, ci, w[((size_t)co * cin_g + ci) * k + tp]);
-    }
-    void bias(const GemmW& G, const std::string& name, long n) { if (G.has_bias) copy_floats(G.bias, name, n); }
-};
-
-int parse_index(si_ctx* ctx, const char* index, const void* blob, size_t nbytes, std::map<std::string, HostTensor>& out) {
-    std::istringstream in(index ? index : "");
-    std::string line;
-    int lineno = 0;
-    while (std::getline(in, line)) {
-        ++lineno;
-        if (line.empty()) continue;
-        std::istringstream ls(line);
-        std::string name; long long off; int nd;
-        if (!(ls >> name >> off >> nd) || nd < 0 || nd > 8) return si_fail(ctx, SI_EWEIGHTS, "index line %d is malformed: '%s'", lineno, line.c_str());
-        HostTensor t;
-        for (int i = 0; i < nd; ++i) { long v; if (!(ls >> v) || v < 0) return si_fail(ctx, SI_EWEIGHTS, "index line %d: bad dims", lineno); t.shape.push_back(v); }
-        if (off < 0 || off % 4 || (size_t)off + (size_t)t.numel() * 4 > nbytes)
-            return si_fail(ctx, SI_EWEIGHTS, "tensor '%s' (offset %lld, %ld floats) does not fit the %zu-byte blob", name.c_str(), off, t.numel(), nbytes);
-        t.data = reinterpret_cast<const float*>(static_cast<const char*>(blob) + off);
-        out[name] = t;
-    }
-    if (out.empty()) return si_fail(ctx, SI_EWEIGHTS, "checkpoint index is empty");
-    return SI_OK;
-}
-
-int pack_weights(si_ctx* ctx, Packer& P) {
-    const si_model_desc& d = ctx->d;
-    const Layout& L = ctx->lay;
-    P.out.assign(L.total, 0);
-    const std::string B = "base_model.";
-    const int H = d.hidden_size;
-    std::vector<float> w;
-    // ---- feature extractor
-    {
-        const std::string p0 = B + "feature_extractor.conv_layers.0.";
-        const HostTensor* h = P.get(p0 + "conv.weight", {d.conv_dim[0], 1, d.conv_kernel[0]});
-        if (h) memcpy(P.out.data() + L.conv0_w, h->data, (size_t)h->numel() * 4);
-        if (d.conv_bias) P.copy_floats(L.conv0_bias, p0 + "conv.bias", d.conv_dim[0]);
-        P.copy_floats(L.conv0_g, p0 + "layer_norm.weight", d.conv_dim[0]);
-        P.copy_floats(L.conv0_b, p0 + "layer_norm.bias", d.conv_dim[0]);
-    }
-    for (int i = 1; i < d.num_conv; ++i) {
-        const std::string p = B + "feature_extractor.conv_layers." + std::to_string(i) + ".";
-        const ConvW& c = L.convs[i - 1];
-        const HostTensor* h = P.get(p + "conv.weight", {d.conv_dim[i], d.conv_dim[i - 1], d.conv_kernel[i]});
-        if (h) { w.assign(h->data, h->data + h->numel()); P.conv(c.g, w, d.conv_dim[i], d.conv_dim[i - 1], d.conv_kernel[i]); }
-        P.bias(c.g, p + "conv.bias", d.conv_dim[i]);
-        if (d.feat_norm_layer) { P.copy_floats(c.ln_g, p + "layer_norm.weight", d.conv_dim[i]); P.copy_floats(c.ln_b, p + "layer_norm.bias", d.conv_dim[i]); }
-    }
-    const int CF = d.conv_dim[d.num_conv - 1];
-    if (d.feat_proj_layer_norm) {
-        P.copy_floats(L.fp_ln_g, B + "feature_projection.layer_norm.weight", CF);
-        P.copy_floats(L.fp_ln_b, B + "feature_projection.layer_norm.bias", CF);
-    }
-    auto linear = [&](const GemmW& G, const std::string& name, int nout, int nin, int row0 = 0) {
-        const HostTensor* h = P.get(name + ".weight", {nout, nin});
-        if (h) for (int o = 0; o < nout; ++o) for (int i = 0; i < nin; ++i) P.put(G, 0, 0, row0 + o, i, h->data[(size_t)o * nin + i]);
-        const HostTensor* b = P.get(name + ".bias", {nout});
-        if (b) memcpy(P.fptr(G.bias) + row0, b->data, (size_t)nout * 4);
-    };
-    linear(L.proj, B + "feature_projection.projection", H, CF);
-    {
-        const int cg = H / d.pos_conv_groups;
-        if (P.folded(B + "encoder.pos_conv_embed.conv", {H, cg, d.pos_conv_kernel}, 2, w)) P.conv(L.pos, w, H, cg, d.pos_conv_kernel);
-        P.bias(L.pos, B + "encoder.pos_conv_embed.conv.bias", H);
-    }
-    P.copy_floats(L.enc_ln_g, B + "encoder.layer_norm.weight", H);
-    P.copy_floats(L.enc_ln_b, B + "encoder.layer_norm.bias", H);
-    for (int l = 0; l < d.num_layers; ++l) {
-        const std::string p = B + "encoder.layers." + std::to_string(l) + ".";
-        const LayerW& W = L.layers[l];
-        linear(W.qkv, p + "attention.q_proj", H, H, 0);
-        linear(W.qkv, p + "attention.k_proj", H, H, H);
-        linear(W.qkv, p + "attention.v_proj", H, H, 2 * H);
-        linear(W.out, p + "attention.out_proj", H, H);
-        P.copy_floats(W.ln1_g, p + "layer_norm.weight", H); P.copy_floats(W.ln1_b, p + "layer_norm.bias", H);
-        linear(W.ffn1, p + "feed_forward.intermediate_dense", d.intermediate_size, H);
-        linear(W.ffn2, p + "feed_forward.output_dense", H, d.intermediate_size);
-        P.copy_floats(W.ln2_g, p + "final_layer_norm.weight", H); P.copy_floats(W.ln2_b, p + "final_layer_norm.bias", H);
-    }
-    P.copy_floats(L.head_ln_g, "final_layers.0.weight", H);
-    P.copy_floats(L.head_ln_b, "final_layers.0.bias", H);
-    linear(L.head, "final_layers.1", d.codebook_dim, H);
-    // ---- codebook tables (I_ea/loss_fn.py:10-14): centre = mean over K; centred; 1/max(||centred||, 1e-8)
-    {
-        const int K = d.num_clusters, D = d.codebook_dim;
-        const HostTensor* c = P.get("codebook", {K, D});
-        if (c) {
-            std::vector<float> center(D, 0.f);
-            for (int j = 0; j < D; ++j) { float s = 0.f; for (int k = 0; k < K; ++k) s += c->data[(size_t)k * D + j]; center[j] = s / K; }
-            float* cc = P.fptr(L.cb_centered); float* raw = P.fptr(L.cb_raw); float* rn = P.fptr(L.cb_rnorm);
-            for (int k = 0; k < K; ++k) {
-                double ss = 0;
-                for (int j = 0; j < D; ++j) {
-                    const float v = c->data[(size_t)k * D + j] - center[j];
-                    cc[(size_t)k * D + j] = v;
-                    raw[(size_t)k * D + j] = v + center[j];        // predict.py:184: all_embeds_t_c + center_
-                    ss += (double)v * v;
-                }
-                rn[k] = 1.0f / fmaxf((float)std::sqrt(ss), 1e-8f);
-            }
-        }
-    }
-    // ---- generator
-    const std::string G = "generator.";
-    const int C0 = d.up_initial_channel;
-    if (P.folded(G + "conv_pre", {C0, d.num_mels, 7}, 0, w)) P.conv(L.pre, w, C0, d.num_mels, 7);
-    P.bias(L.pre, G + "conv_pre.bias", C0);
-    int c = C0;                                            // REAL channel counts here; the packed matrices have the padded strides
-    for (int i = 0; i < d.num_ups; ++i) {
-        const int u = d.up_rates[i], k = d.up_kernels[i], cout = c / 2, coutp = stage_channels(ctx, i);
-        const GemmW& U = L.ups[i];
-        // ConvTranspose1d weight (Cin, Cout, k), weight-norm over dim 0 (= Cin).  Phase p = j mod u, tap q = j / u.
-        if (P.folded(G + "ups." + std::to_string(i), {c, cout, k}, 0, w))
-            for (int ci = 0; ci < c; ++ci)
-                for (int co = 0; co < cout; ++co)
-                    for (int j = 0; j < k; ++j) P.put(U, 0, j / u, (j % u) * coutp + co, ci, w[((size_t)ci * cout + co) * k + j]);
-        const HostTensor* b = P.get(G + "ups." + std::to_string(i) + ".bias", {cout});
-        if (b) for (int ph = 0; ph < u; ++ph) memcpy(P.fptr(U.bias) + (size_t)ph * coutp, b->data, (size_t)cout * 4);
-        c = cout;
-        for (int j = 0; j < d.num_rb; ++j) {
-            const ResW& R = L.rbs[(size_t)i * d.num_rb + j];
-            const std::string rp = G + "resblocks." + std::to_string(i * d.num_rb + j) + ".";
-            for (int n = 0; n < d.num_dil; ++n) {
-                if (d.resblock_type == 2) {                       // ResBlock2: `convs.<n>` (I_ea/hifi_gan/models.py:56-61)
-                    const std::string a = rp + "convs." + std::to_string(n);
-                    if (P.folded(a, {c, c, d.rb_kernels[j]}, 0, w)) P.conv(R.c1[n], w, c, c, d.rb_kernels[j]);
-                    P.bias(R.c1[n], a + ".bias", c);
-                    continue;
-                }
-                const std::string a = rp + "convs1." + std::to_string(n), bb = rp + "convs2." + std::to_string(n);
-                if (P.folded(a, {c, c, d.rb_kernels[j]}, 0, w)) P.conv(R.c1[n], w, c, c, d.rb_kernels[j]);
-                P.bias(R.c1[n], a + ".bias", c);
-                if (P.folded(bb, {c, c, d.rb_kernels[j]}, 0, w)) P.conv(R.c2[n], w, c, c, d.rb_kernels[j]);
-                P.bias(R.c2[n], bb + ".bias", c);
-            }
-        }
-    }
-    if (P.folded(G + "conv_post", {1, c, 7}, 0, w))
-        for (int ci = 0; ci < c; ++ci) for (int k = 0; k < 7; ++k) P.fptr(L.post_w)[(size_t)k * L.post_C + ci] = w[(size_t)ci * 7 + k];
-    P.copy_floats(L.post_b, G + "conv_post.bias", 1);
-    return P.rc;
-}
+int stage_channels(const si_ctx* ctx, int i) { return siw::stage_channels(ctx->d, ctx->popt, i); }
+BlobHeader blob_header(const si_ctx* ctx) { return siw::blob_header(ctx->d, ctx->popt, ctx->lay); }
+Err ctx_err(si_ctx* ctx) { return ctx ? Err{ctx->err, sizeof(ctx->err)} : Err{g_create_err, sizeof(g_create_err)}; }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -739,7 +321,7 @@ const char* si_last_error(const si_ctx* ctx) { return ctx ? ctx->err : g_create_
 int si_create(si_ctx** out, int device_id, const si_model_desc* desc) {
     if (!out) return si_fail(nullptr, SI_EINVAL, "si_create: out is NULL");
     *out = nullptr;
-    int rc = check_desc(nullptr, desc);
+    int rc = check_desc(desc, ctx_err(nullptr));
     if (rc) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev)
@@ -747,9 +329,7 @@ int si_create(si_ctx** out, int device_id, const si_model_desc* desc) {
     si_ctx* ctx = new si_ctx();
     ctx->device = device_id;
     ctx->d = *desc;
-    auto env_flag = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) != 0 : true; };
-    ctx->opt_voc_opready = env_flag("SI_VOC_OPREADY");
-    ctx->opt_voc_res16 = env_flag("SI_VOC_RES16");
+    ctx->popt = pack_opts_from_env();        // the same reading as si_plan_weights / si_pack_weights_host
     ctx->opt_voc_fuse = getenv("SI_VOC_FUSE") ? atoi(getenv("SI_VOC_FUSE")) : 1;
     ctx->opt_voc_chain = getenv("SI_VOC_CHAIN") ? atoi(getenv("SI_VOC_CHAIN")) : 1;
     ctx->opt_enc_opready = env_flag("SI_ENC_OPREADY");
@@ -760,7 +340,7 @@ int si_create(si_ctx** out, int device_id, const si_model_desc* desc) {
     ctx->opt_ln_fuse = getenv("SI_ENC_LNFUSE") ? atoi(getenv("SI_ENC_LNFUSE")) : 1;
     ctx->opt_voc_upsgemm = getenv("SI_VOC_UPSGEMM") ? atoi(getenv("SI_VOC_UPSGEMM")) : 1;
     ctx->opt_ffn_pad = getenv("SI_ENC_FFNPAD") ? std::min(128, std::max(0, atoi(getenv("SI_ENC_FFNPAD")) / 8 * 8)) : 64;
-    plan_layout(ctx);
+    plan_layout(ctx->d, ctx->popt, ctx->lay);
     *out = ctx;
     return SI_OK;
 }
@@ -790,17 +370,12 @@ int si_alloc_weights(si_ctx* ctx) {
 
 int si_load_weights(si_ctx* ctx, const void* host_blob, size_t nbytes, const char* index) {
     if (!ctx || !host_blob || !index) return si_fail(ctx, SI_EINVAL, "si_load_weights: NULL argument");
-    Packer P;
-    P.ctx = ctx;
-    int rc = parse_index(ctx, index, host_blob, nbytes, P.t);
-    if (rc) return rc;
-    rc = pack_weights(ctx, P);
-    if (rc) return rc;
+    std::vector<char> image;                 // the same bytes si_pack_weights_host returns, header included
+    int rc = pack_image(ctx->d, ctx->popt, ctx->lay, host_blob, nbytes, index, image, ctx_err(ctx));
+    if (rc) return rc;                       // a refused checkpoint leaves the device blob and the context's state as they were
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     if (!ctx->wdev) SI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx->wdev), ctx->lay.total));
-    const BlobHeader hd = blob_header(ctx);
-    memcpy(P.out.data(), &hd, sizeof(hd));
-    SI_HIP_CHECK(hipMemcpy(ctx->wdev, P.out.data(), ctx->lay.total, hipMemcpyHostToDevice));
+    SI_HIP_CHECK(hipMemcpy(ctx->wdev, image.data(), ctx->lay.total, hipMemcpyHostToDevice));
     ctx->weights_ready = true;
     ctx->weights_verified = true;
     return SI_OK;
@@ -1535,13 +1110,13 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
     // what the next convolution would compute while staging -- so consumers copy 2-byte operands instead of loading
     // fp32 and converting; the ResBlock intermediate exists only in that form.  Same arithmetic, bit-identical output;
     // 20-40 % less HBM / L2 traffic on the convolution inputs.  SI_VOC_OPREADY=0 restores the fp32-input path.
-    const bool opr = ctx->opt_voc_opready && (d.vocoder_math == SI_MATH_BF16 || d.vocoder_math == SI_MATH_F16);
+    const bool opr = ctx->popt.voc_opready && (d.vocoder_math == SI_MATH_BF16 || d.vocoder_math == SI_MATH_F16);
     // fp16 activation stream (fp16 mode): activations live ONLY as raw fp16 -- the residual stream too -- and the
     // consumer applies its leaky-ReLU to the packed halves while staging: 10 instead of 16 bytes of HBM traffic per
     // element and conv pair (these stages run on the memory side in fp16).  The rounding it adds (fp16 after every
     // residual add) is small next to the operand rounding the mode already has: waveform RMS error 1.35e-4 vs 1.10e-4
     // (gate 1e-3).  SI_VOC_RES16=0 keeps the fp32 residual stream.
-    const bool r16 = opr && ctx->opt_voc_res16 && d.vocoder_math == SI_MATH_F16;
+    const bool r16 = opr && ctx->popt.voc_res16 && d.vocoder_math == SI_MATH_F16;
     const int fuse_mask = ctx->opt_voc_fuse == 1 ? ~0 : ctx->opt_voc_fuse;
     if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: vocoder workspace carve exceeded its own estimate");
     const int nk = d.num_rb;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/si_hip.h"
+#include "weights_host.h"
 
 #define SI_HIP_CHECK(expr)                                                                      \
     do {                                                                                        \
@@ -126,8 +127,7 @@ struct TapGemmParams {
 };
 
 // N-tile width the launcher uses for a given N; the packer pads W rows to a multiple of it.
-static inline int si_pick_bn(int N) { return N >= 128 ? 128 : (N > 32 ? 64 : 32); }
-static inline int si_round_up(int a, int b) { return (a + b - 1) / b * b; }
+// si_pick_bn / si_round_up: weights_host.h (the layout plan pads N with them on the host)
 
 int si_launch_tapgemm(si_ctx* ctx, int math, const TapGemmParams& p, hipStream_t st);
 

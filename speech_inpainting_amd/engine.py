@@ -78,10 +78,17 @@ class InpaintingEngine:
             codebook = torch.zeros(self.ctx.desc.num_clusters, self.harch.codebook_dim)
         blob, index = flatten_checkpoint(hubert_sd, gen_sd, codebook)
         self.ctx.load_weights(blob, index)
+        # what this checkpoint held travels WITH the blob, in the header's reserved word (the library writes 0 there and never reads
+        # it): a rank that receives the bytes by broadcast learns it in weights_check(), without a collective of its own
+        word = self._FLAGS_VALID | (self._FLAG_HEAD if self._has_head else 0) | (self._FLAG_CODEBOOK if self._has_codebook else 0)
+        self.ctx.weights_tensor()[24:32].copy_(torch.tensor(list(word.to_bytes(8, "little")), dtype=torch.uint8))
         return self
 
+    _FLAGS_VALID, _FLAG_HEAD, _FLAG_CODEBOOK = 1, 2, 4             # bits of the blob header's reserved word (bytes 24..31)
+
     def alloc_weights(self, has_head: bool = True, has_codebook: bool = True):
-        """Receiving rank of the weight broadcast: the flags say what the SOURCE rank's checkpoint held."""
+        """Receiving rank of the weight broadcast: the flags say what the SOURCE rank's checkpoint held.  They only stand until
+        weights_check(), which replaces them by what the received blob itself records."""
         self.ctx.alloc_weights()
         self._has_head, self._has_codebook = bool(has_head), bool(has_codebook)
         return self
@@ -97,8 +104,13 @@ class InpaintingEngine:
         return self.ctx.weights_tensor()
 
     def weights_check(self) -> None:
-        """After the weight broadcast: the blob in this context carries the fingerprint of THIS context's layout (raises otherwise)."""
+        """After the weight broadcast: the blob in this context carries the fingerprint of THIS context's layout (raises otherwise),
+        and this engine serves what the source rank's checkpoint held -- no trained head or no codebook there means `_need` raises
+        here too, instead of serving the placeholder head or the zero codebook."""
         self.ctx.weights_check()
+        word = int.from_bytes(bytes(self.ctx.weights_tensor()[24:32].cpu().tolist()), "little")
+        if word & self._FLAGS_VALID:
+            self._has_head, self._has_codebook = bool(word & self._FLAG_HEAD), bool(word & self._FLAG_CODEBOOK)
 
     # ---- the three stages
     def encode(self, wave16: torch.Tensor, mask_start: Optional[torch.Tensor] = None, mask_len: Optional[torch.Tensor] = None,

@@ -31,7 +31,8 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
            "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
            "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate",
-           "si_quiet_runs_ch", "si_cut_rate_ch", "si_patch_rate_ch", "si_dead_runs"]
+           "si_quiet_runs_ch", "si_cut_rate_ch", "si_patch_rate_ch", "si_dead_runs",
+           "si_plan_weights", "si_pack_weights_host"]
 SI_MAX_SPANS = 16
 SI_MAX_CHANNELS = 8                        # channels of an interleaved file
 DEAD_QUIET, DEAD_HELD = 1, 2               # SI_DEAD_QUIET, SI_DEAD_HELD: the `kind` bits of si_dead_runs
@@ -367,6 +368,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_cut_rate_ch.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, C.POINTER(SincFilter), vp, vp]
     lib.si_patch_rate_ch.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(RateTableStruct), vp, i32, vp, C.POINTER(SincFilter), vp, vp]
     lib.si_dead_runs.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp]
+    lib.si_plan_weights.argtypes = [C.POINTER(ModelDesc), C.POINTER(sz)]
+    lib.si_pack_weights_host.argtypes = [C.POINTER(ModelDesc), vp, sz, C.c_char_p, vp, sz, C.POINTER(sz), C.c_char_p, sz]
     lib.si_num_frames.argtypes = [vp, i32]
     lib.si_vocoder_samples.argtypes = [vp, i32, i32]
     lib.si_debug_capture.argtypes = [vp, C.c_char_p, vp, C.c_long]
@@ -385,6 +388,30 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 
 class NativeError(RuntimeError):
     pass
+
+
+def plan_weights(desc: ModelDesc):
+    """(return code, byte size of the packed blob, message) of si_plan_weights: the descriptor check and the plan, no device needed."""
+    lib = load_library()
+    n = C.c_size_t(0)
+    rc = lib.si_plan_weights(C.byref(desc), C.byref(n))
+    return rc, int(n.value), lib.si_last_error(None).decode()
+
+
+def pack_weights_host(desc: ModelDesc, blob: np.ndarray, index: str, capacity: Optional[int] = None, slack: int = 0):
+    """si_pack_weights_host on the (blob, index) pair of checkpoint.flatten_checkpoint, no device needed -> (return code, image as a
+    uint8 array of capacity + slack bytes pre-filled with 0xA5, needed, message).  capacity None: what si_plan_weights reports."""
+    lib = load_library()
+    blob = np.ascontiguousarray(blob)
+    if capacity is None:
+        rc, capacity, msg = plan_weights(desc)
+        if rc != 0:
+            return rc, np.zeros(0, np.uint8), 0, msg
+    out = np.full(int(capacity) + int(slack), 0xA5, dtype=np.uint8)
+    need, err = C.c_size_t(0), C.create_string_buffer(512)
+    rc = lib.si_pack_weights_host(C.byref(desc), blob.ctypes.data_as(C.c_void_p), blob.nbytes, index.encode(), out.ctypes.data_as(C.c_void_p),
+                                  int(capacity), C.byref(need), err, 512)
+    return rc, out, int(need.value), err.value.decode()
 
 
 def _ptr(t: Optional[torch.Tensor]):

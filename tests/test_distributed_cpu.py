@@ -26,10 +26,13 @@ class _FakeEngine:
 
     def load_state(self, hsd, gsd, cb):
         self.blob = torch.arange(1000, dtype=torch.uint8) * 3
+        self.has_head, self.has_codebook = hsd is not None, cb is not None
+        self.blob[24] = 1 | (2 if self.has_head else 0) | (4 if self.has_codebook else 0)      # InpaintingEngine's flag word in the blob header
         return self
 
     def alloc_weights(self):
         self.blob = torch.zeros(1000, dtype=torch.uint8)
+        self.has_head = self.has_codebook = True                   # the defaults of a receiving rank, until the blob says otherwise
         return self
 
     def weights_tensor(self):
@@ -37,6 +40,8 @@ class _FakeEngine:
 
     def weights_check(self):
         self.checked = True
+        if int(self.blob[24]) & 1:                                 # the matching read: the flags travel with the broadcast bytes
+            self.has_head, self.has_codebook = bool(int(self.blob[24]) & 2), bool(int(self.blob[24]) & 4)
 
 
 def _worker(rank, world, port, q):
@@ -52,7 +57,10 @@ def _worker(rank, world, port, q):
     loads = []
     eng = parallel.setup_engine(_FakeEngine, lambda: (loads.append(1), None, None), rank)
     assert len(loads) == (1 if rank == 0 else 0)              # only the source rank reads the checkpoint
-    assert torch.equal(eng.weights_tensor(), torch.arange(1000, dtype=torch.uint8) * 3)
+    want = torch.arange(1000, dtype=torch.uint8) * 3
+    want[24] = 1                                                  # the fake checkpoint holds neither a head nor a codebook ...
+    assert torch.equal(eng.weights_tensor(), want)
+    assert (eng.has_head, eng.has_codebook) == (False, False)     # ... and the receiving rank knows it after the one broadcast
     assert eng.checked                                            # the layout check runs on every rank after the broadcast
     # shard a global list of 5 utterances; each rank runs its slice; outputs must equal the 1-process run
     harch, varch = HubertArch.tiny(), VocoderArch.tiny()

@@ -241,6 +241,30 @@ def test_receiving_rank_weight_path_on_one_gpu():
         assert torch.equal(oa["labels"], ob["labels"]) and torch.equal(oa["wave"], ob["wave"]) and torch.equal(oa["feats"], ob["feats"])
         del wa, wb
         A.ctx.close(); B.ctx.close()
+    # What the source checkpoint lacked travels with the blob (its header's reserved word): after weights_check() the receiving
+    # engine refuses exactly what the source refuses, instead of serving the placeholder head or the zero codebook.
+    enc_only = {k: v for k, v in c["hsd"].items() if not k.startswith("final_layers.")}
+    wave = c["wave"].cuda()
+    for hsd, cb, head, book in ((enc_only, c["cb"], False, True), (c["hsd"], None, True, False), (enc_only, None, False, False)):
+        A = InpaintingEngine(c["harch"], c["varch"], m["K"], "cuda:0").load_state(hsd, c["gsd"], cb)
+        B = InpaintingEngine(c["harch"], c["varch"], m["K"], "cuda:0").alloc_weights()
+        assert (B._has_head, B._has_codebook) == (True, True)
+        B.weights_tensor().copy_(A.weights_tensor())
+        B.weights_check()
+        assert (B._has_head, B._has_codebook) == (A._has_head, A._has_codebook) == (head, book)
+        errs = []
+        for E in (A, B):
+            with pytest.raises(RuntimeError) as ei:
+                _run(E, c)
+            errs.append(str(ei.value))
+            if not head:
+                with pytest.raises(RuntimeError, match="final_layers"):
+                    E.encode(wave)
+        assert errs[0] == errs[1] and ("final_layers" in errs[0] or "codebook" in errs[0])
+        fa, fb = A.extract_features(wave, 1), B.extract_features(wave, 1)          # what needs neither is served by both, same bits
+        torch.cuda.synchronize()
+        assert torch.equal(fa, fb)
+        A.ctx.close(); B.ctx.close()
 
 
 def test_expected_inpaint_and_hifi_masked_batch_outputs():
