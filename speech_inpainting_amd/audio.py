@@ -57,6 +57,16 @@ def design_resampler(sr_in: int, sr_out: int, n_in: int):
 KAISER_BEST = dict(num_zeros=64, precision=9, rolloff=0.9475937167399596, beta=KAISER_BETA)
 
 
+def resampled_len(n: int, sr_in: int, sr_out: int) -> int:
+    """Samples of `librosa.load(path, sr=sr_out)` for a file of n samples at sr_in: librosa 0.9.1's `ceil(n * ratio)` with the ratio
+    rounded to float64 FIRST (librosa/core/audio.py resample: ratio = float(target_sr) / orig_sr).  THE length rule of the resampler
+    (design_kaiser_best) and of the request front; `ceil(n * float(sr_out) / sr_in)` -- the product first -- rounds differently
+    (DESIGN.md 4.24).  The file-rate routes count with exact integers by their own definition."""
+    if int(sr_in) == int(sr_out):
+        return int(n)
+    return int(math.ceil(n * (float(sr_out) / float(sr_in))))
+
+
 def design_kaiser_best(sr_in: int, sr_out: int, n_in: int):
     """Tables of resampy's `kaiser_best` band-limited interpolation -- the resampler behind `librosa.load(path, sr=...)` in the
     reference's pinned librosa==0.9.1 (I_ea/predict.py:79-80; requirements.txt:3) -- for the GPU kernel (si_resample_sinc):
@@ -76,12 +86,19 @@ def design_kaiser_best(sr_in: int, sr_out: int, n_in: int):
     dwin = np.zeros_like(win)
     dwin[:-1] = np.diff(win)
     scale = min(1.0, ratio)
-    n_out = int(math.ceil(n_in * ratio))
-    inc = 1.0 / ratio
+    n_out = resampled_len(n_in, sr_in, sr_out)
+    return dict(win=np.ascontiguousarray(win), dwin=dwin, time_reg=time_registers(sr_in, sr_out, n_out), num_table=nb, step=int(scale * nb),
+                scale=scale, ratio=ratio, n_out=n_out)
+
+
+def time_registers(sr_in: int, sr_out: int, n_out: int) -> np.ndarray:
+    """design_kaiser_best's time_reg alone: entry t is the running float64 sum of t + 1 increments 1 / ratio (a sequential
+    accumulation) less one increment, whatever n_out is -- the table for a shorter clip is, bit for bit, a prefix of the table for a
+    longer one (what lets the engine keep one per rate pair)."""
+    inc = 1.0 / (float(sr_out) / float(sr_in))
     tr = np.cumsum(np.full(max(n_out, 1), inc)) - inc
     tr[0] = 0.0
-    return dict(win=np.ascontiguousarray(win), dwin=dwin, time_reg=tr[:n_out].copy(), num_table=nb, step=int(scale * nb), scale=scale,
-                ratio=ratio, n_out=n_out)
+    return tr[:n_out].copy()
 
 
 def resample(x: np.ndarray, sr_in: int, sr_out: int) -> np.ndarray:

@@ -292,33 +292,49 @@ class InpaintingEngine:
         return self.ctx.mel_frontend(wave22, mask_start, mask_end, normalize)
 
     def resample(self, x: torch.Tensor, sr_in: int, sr_out: int, kind: str = "kaiser_best", lens=None) -> torch.Tensor:
-        """(B, n) fp32 clips at sr_in -> (B, ceil(n * sr_out / sr_in)) at sr_out on the GPU: `librosa.load(..., sr=...)`'s resampling
-        (I_ea/predict.py:79-80).  kind="kaiser_best" (default): resampy's band-limited interpolation, what librosa 0.9.1 runs --
+        """(B, n) fp32 clips at sr_in -> (B, audio.resampled_len(n, sr_in, sr_out)) at sr_out on the GPU: the resampling of
+        `librosa.load(..., sr=...)` (I_ea/predict.py:79-80).  kind="kaiser_best" (default): resampy's band-limited interpolation, what librosa 0.9.1 runs --
         pinned bit for bit by the reference-held LJ001-0001 22k / 16k pair (si_resample_sinc).  kind="poly": the polyphase Kaiser
         FIR with scipy.signal.resample_poly's arithmetic (si_resample_poly; a different filter).  lens: per-clip sample counts of a
         ragged batch (kaiser_best only): clip b's output is zero past int(lens[b] * ratio)."""
         from . import audio
         if sr_in == sr_out:
             return x.clone()
-        key = (kind, int(sr_in), int(sr_out), int(x.shape[1]))
         if kind == "kaiser_best":
-            if key not in self._resamplers:
-                f = audio.design_kaiser_best(sr_in, sr_out, x.shape[1])
-                for k in ("win", "dwin", "time_reg"):
-                    f[k] = torch.from_numpy(f[k]).to(self.device)
-                self._resamplers[key] = f
-            f = self._resamplers[key]
+            # one entry per rate pair, whatever lengths pass through (DESIGN.md 4.24): win / dwin once, and ONE time-register table
+            # as long as the longest output seen -- time_reg[t] does not depend on the clip's length (repeated addition from 0), and
+            # the kernel reads it for t < n_out only, so a longer table serves every shorter clip with the same bits
+            f = self._sinc_tables(sr_in, sr_out)
+            n_out = audio.resampled_len(int(x.shape[1]), sr_in, sr_out)
+            if f["time_reg"] is None or f["time_reg"].numel() < n_out:
+                f["time_reg"] = torch.from_numpy(audio.time_registers(sr_in, sr_out, n_out)).to(self.device)
             n_len = None if lens is None else torch.as_tensor(list(lens), dtype=torch.int32).to(self.device)
-            return self.ctx.resample_sinc(x.contiguous(), f, f["n_out"], n_len)
+            return self.ctx.resample_sinc(x.contiguous(), f, n_out, n_len)
         if kind != "poly":
             raise ValueError(f"resample kind {kind!r}: 'kaiser_best' or 'poly'")
         if lens is not None:
             raise ValueError("ragged batches are resampled with kind='kaiser_best'")
+        key = (kind, int(sr_in), int(sr_out), int(x.shape[1]))
         if key not in self._resamplers:
             taps, up, down, pre, n_out = audio.design_resampler(sr_in, sr_out, x.shape[1])
             self._resamplers[key] = (torch.from_numpy(taps).to(self.device), up, down, pre, n_out)
         taps, up, down, pre, n_out = self._resamplers[key]
         return self.ctx.resample_poly(x.contiguous(), taps, up, down, pre, n_out)
+
+    def _sinc_tables(self, sr_in: int, sr_out: int) -> Dict[str, object]:
+        """audio.design_kaiser_best(sr_in, sr_out, .) once per rate pair: win / dwin on the device and the scalars; time_reg (None until
+        resample needs it) grows to the longest output seen.  resample, _rate_filter and _feed_filter share these device tables."""
+        from . import audio
+        key = ("kaiser_best", int(sr_in), int(sr_out))
+        if key not in self._resamplers:
+            f = audio.design_kaiser_best(int(sr_in), int(sr_out), 1)
+            f.pop("n_out")
+            f["time_reg"] = None
+            f["reach"] = G.rate_reach(f["win"].size, f["step"])                      # taps per wing
+            for k in ("win", "dwin"):
+                f[k] = torch.from_numpy(f[k]).to(self.device)
+            self._resamplers[key] = f
+        return self._resamplers[key]
 
     def to_int16(self, wave: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """B6 on the GPU (I_ea/predict.py:204-206): fp32 waveform -> int16 PCM, `* 32768` truncated toward zero (si_pcm16)."""
@@ -651,17 +667,9 @@ class InpaintingEngine:
 
     # ---- repair at the file's own sample rate: the recording stays at `sr` in its own sample type
     def _rate_filter(self, sr: int) -> Dict[str, object]:
-        """audio.design_kaiser_best(22050, sr, .) with win / dwin on the device (time_reg is not used) + reach = taps per wing."""
-        from . import audio
-        key = ("rate", int(sr))
-        if key not in self._resamplers:
-            f = audio.design_kaiser_best(22050, int(sr), 1)
-            f.pop("time_reg")
-            f["reach"] = G.rate_reach(f["win"].size, f["step"])
-            for k in ("win", "dwin"):
-                f[k] = torch.from_numpy(f[k]).to(self.device)
-            self._resamplers[key] = f
-        return self._resamplers[key]
+        """audio.design_kaiser_best(22050, sr, .) with win / dwin on the device (time_reg is not used) + reach = taps per wing: the
+        tables resample(., 22050, sr) runs on, held once."""
+        return self._sinc_tables(22050, sr)
 
     def plan_rate(self, ctxs: Sequence[dict], L22: int, sr: int, n_file: int, fade_f: int, reach: int) -> Dict[str, object]:
         """Host planning of one pass of patch_file: the own gaps of the contexts `ctxs` (clips of L22 samples at 22.05 kHz) as spans
@@ -702,16 +710,9 @@ class InpaintingEngine:
         return plan
 
     def _feed_filter(self, sr: int) -> Dict[str, object]:
-        """audio.design_kaiser_best(sr, 22050, .) with win / dwin on the device (time_reg is not used): what si_cut_rate takes."""
-        from . import audio
-        key = ("feed", int(sr))
-        if key not in self._resamplers:
-            f = audio.design_kaiser_best(int(sr), 22050, 1)
-            f.pop("time_reg")
-            for k in ("win", "dwin"):
-                f[k] = torch.from_numpy(f[k]).to(self.device)
-            self._resamplers[key] = f
-        return self._resamplers[key]
+        """audio.design_kaiser_best(sr, 22050, .) with win / dwin on the device (time_reg is not used): what si_cut_rate takes -- the
+        tables resample(., sr, 22050) runs on, held once."""
+        return self._sinc_tables(sr, 22050)
 
     def patch_file(self, x, sr: int, gaps=None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
                    return_windows: bool = False, feed: str = "recording", channel_gaps=None) -> Dict[str, object]:

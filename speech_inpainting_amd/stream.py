@@ -13,13 +13,13 @@ PyTorch owns the streams, events and pinned buffers; all arithmetic is the HIP l
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass, field
 from typing import Iterable, Iterator, List, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import audio
 from . import gaps as G
 from .engine import InpaintingEngine
 
@@ -73,16 +73,22 @@ class RequestFront:
         self.d2h = torch.cuda.Stream(self.dev)
         self.slots = [_Slot() for _ in range(self.depth)]
 
-    # ---- sizes of librosa.load's outputs (librosa.resample: ceil(n * ratio) after fix_length)
+    # ---- sizes of librosa.load's outputs (librosa.resample: ceil(n * ratio) after fix_length): the resampler's own rule, so that
+    # a clip is as long for the front as for engine.resample and for the unpipelined path
     def _len_at(self, n: int, sr: int) -> int:
-        return n if sr == self.sr_in else int(math.ceil(n * float(sr) / self.sr_in))
+        return audio.resampled_len(n, self.sr_in, sr)
 
     def _ensure(self, s: _Slot, B: int, n_in: int, n_out: int, lm: int, n_tab: int = 0):
-        # flat, persistent buffers per slot: the device side of the H2D copy must never be a block the caching allocator could
-        # hand out while kernels of the compute stream still use it (the copy stream is not ordered with that stream's frees)
+        # flat, persistent buffers per slot.  The copy stream is not ordered with the compute stream's frees: a block the caching
+        # allocator hands out here may be one that temporaries of the batch in flight gave back on the host while kernels still queued
+        # on the compute stream read it.  So after an allocation -- and only then -- the copy stream waits ONCE for what the compute
+        # stream holds at this moment, before the first copy into the new block.  From then on the block is the slot's own: a request
+        # that grows nothing makes the copy stream wait for nothing, and batch i + 1's upload overlaps batch i's compute.
+        grown = False
         if s.pin_in is None or s.pin_in.numel() < B * n_in:
             s.pin_in = torch.empty(B * n_in, dtype=torch.float32).pin_memory()
             s.dev_in = torch.empty(B * n_in, dtype=torch.float32, device=self.dev)
+            grown = True
         if s.pin_out is None or s.pin_out.numel() < B * n_out:
             s.pin_out = torch.empty(B * n_out, dtype=torch.int16).pin_memory()
         if s.pin_lab is None or s.pin_lab.numel() < B * max(lm, 1):
@@ -90,6 +96,9 @@ class RequestFront:
         if n_tab and (s.pin_tab is None or s.pin_tab.numel() < n_tab):
             s.pin_tab = torch.empty(n_tab, dtype=torch.int32).pin_memory()
             s.dev_tab = torch.empty(n_tab, dtype=torch.int32, device=self.dev)
+            grown = True
+        if grown:
+            self.h2d.wait_stream(torch.cuda.current_stream(self.dev))
 
     def _submit(self, s: _Slot, rq: Request):
         eng, dev = self.engine, self.dev
@@ -211,17 +220,39 @@ class RequestFront:
         s.keep, s.meta = (), None
         return Result(pcm, lab, m["tag"], m.get("label_off"))
 
+    def _drain(self, streams: bool = False):
+        """Every slot synchronised and empty: the copies of a batch still in flight have run, its device tensors are released and its
+        result is dropped.  streams: also wait for the copy streams and the compute stream (a request that raised part-way)."""
+        for s in self.slots:
+            if s.meta is not None:
+                s.ev_d2h.synchronize()
+            s.keep, s.meta = (), None
+        if streams:
+            self.h2d.synchronize()
+            torch.cuda.current_stream(self.dev).synchronize()
+            self.d2h.synchronize()
+
     def run(self, requests: Iterable[Request]) -> Iterator[Result]:
+        """One Result per Request, in order.  However the run ends -- exhausted, the generator closed or dropped early, a request
+        refused by `_submit` (its exception leaves `run` unchanged) -- every slot ends synchronised with `meta = None` and `keep = ()`,
+        and the same front serves the next `run`, which also starts from clean slots.  Results of batches in flight when a run ends
+        early are DROPPED, not yielded: their copies are waited for and their buffers released."""
+        self._drain()
         inflight: List[_Slot] = []
-        for i, rq in enumerate(requests):
-            s = self.slots[i % self.depth]
-            if s.meta is not None:                                   # the slot's previous batch: its PCM must be out before reuse
-                inflight.remove(s)
-                yield self._collect(s)
-            self._submit(s, rq)
-            inflight.append(s)
-        for s in inflight:
-            yield self._collect(s)
+        done = False
+        try:
+            for i, rq in enumerate(requests):
+                s = self.slots[i % self.depth]
+                if s.meta is not None:                               # the slot's previous batch: its PCM must be out before reuse
+                    inflight.remove(s)
+                    yield self._collect(s)
+                self._submit(s, rq)
+                inflight.append(s)
+            while inflight:
+                yield self._collect(inflight.pop(0))
+            done = True
+        finally:
+            self._drain(streams=not done)
 
 
 def predict_stream(engine: InpaintingEngine, requests: Iterable[Request], sr_in: int = 22050, depth: int = 2) -> Iterator[Result]:

@@ -51,7 +51,7 @@ def test_stream_front_with_gaps_equals_the_unpipelined_path(enc, voc):
             raw[i, :lens[i]] = torch.from_numpy(c)
         ragged = min(lens) != max(lens)
         w16 = eng.resample(raw.cuda(), 22050, 16000, lens=lens if ragged else None).cpu().numpy()
-        n16 = [int(np.ceil(n * 16000 / 22050)) for n in lens]
+        n16 = [audio.resampled_len(n, 22050, 16000) for n in lens]
         a16 = [w16[i, :n16[i]] for i in range(len(lens))]
         kw = dict(gaps=rq.gaps) if rq.gaps is not None else dict(mask_pos=rq.mask_pos, mask_frames=rq.mask_frames)
         if ragged:

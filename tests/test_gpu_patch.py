@@ -268,7 +268,7 @@ def test_ragged_batch_of_two_equals_each_clip_alone():
 def test_stream_request_with_patch_equals_the_resident_route():
     """stream.Request(patch=True) through the request front (its patch tables staged with the gap tables) against the resident route:
     the PCM is equal and as long as each clip's own 22.05 kHz input."""
-    from speech_inpainting_amd import synth
+    from speech_inpainting_amd import audio, synth
     from speech_inpainting_amd.stream import Request, predict_stream
     eng = _engine()
     secs = [[1.5, 1.5, 1.5], [1.5, 1.1], [1.2, 1.2]]
@@ -287,7 +287,7 @@ def test_stream_request_with_patch_equals_the_resident_route():
             raw[i, :lens[i]] = torch.from_numpy(c)
         raw = raw.cuda()
         w16 = eng.resample(raw, 22050, 16000, lens=lens if ragged else None)
-        n16 = [int(np.ceil(n * 16000 / 22050)) for n in lens]
+        n16 = [audio.resampled_len(n, 22050, 16000) for n in lens]
         g = rq.gaps if rq.gaps is not None else [[(int(p), rq.mask_frames)] for p in rq.mask_pos]
         ref = eng.patch_multigap_batch(w16, raw, g, fade=rq.fade, len16=n16 if ragged else None, len22=lens if ragged else None, pcm=True)
         torch.cuda.synchronize()

@@ -35,7 +35,7 @@ def test_stream_front_equals_the_unpipelined_path(enc, voc):
             raw[i, :lens[i]] = torch.from_numpy(c)
         ragged = min(lens) != max(lens)
         w16 = eng.resample(raw.cuda(), 22050, 16000, lens=lens if ragged else None).cpu().numpy()
-        n16 = [int(np.ceil(n * 16000 / 22050)) for n in lens]
+        n16 = [audio.resampled_len(n, 22050, 16000) for n in lens]
         a16 = [w16[i, :n16[i]] for i in range(len(lens))]
         if ragged:
             ref = predict_clips_ragged(eng, a16, list(rq.clips), rq.mask_pos, rq.mask_frames, blind=rq.blind)
