@@ -33,6 +33,8 @@
  *                           (start_pos_in_sec, end_pos_in_sec) that a user of the script types by hand      I_ea/predict.py:85-90
  *   si_dead_runs         <- nothing the reference computes either: si_quiet_runs for dropouts that are not digital silence -- held
  *                           samples, mutes relative to the file's peak.  It has no detection                I_ea/predict.py:85-90
+ *   si_level_runs        <- nothing the reference computes either: si_dead_runs for a dropout that is a NOISE FLOOR (dither, a
+ *                           concealer's comfort noise), found by windowed RMS level.  It has no detection     I_ea/predict.py:85-90
  *   si_patch_rate        <- the same write-out for a file at ANY sample rate, which the script resamples on the way in and never
  *                           brings back                                       I_ea/predict.py:79-80,203-207
  *   si_cut_rate          <- that resampling on the way in, for the context clips alone instead of the whole file (with si_cut_clips'
@@ -752,6 +754,42 @@ int si_patch_rate_ch(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, in
 #define SI_DEAD_HELD 2
 int si_dead_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int kind, float threshold, float rel_threshold,
                  float held_tol, int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream);
+
+/* ---- Dropouts by windowed RMS level ------------------------------------------------------------------------------------
+ * The reference has no detection: the script's user types the one mask into predict.yaml (I_ea/predict.py:85-90).  si_quiet_runs and
+ * si_dead_runs judge a dropout sample by sample; a dropout that is a NOISE FLOOR -- dither, comfort noise from a codec's concealer, a
+ * file re-encoded after the damage -- has peaks of about five sigma, where speech's own soft passages live, and one outlier splits
+ * the run.  This call judges the RMS level of a window of 2 * half + 1 samples instead, with si_dead_runs' input, output and limits:
+ * x is (n, channels) interleaved, fp32 or int16; channels = 1 is a mono file (channel 0 or -1) and gives the mono bytes.  For one
+ * channel x[0 .. n) (elements k * channels + c), with h = half:
+ *   peak, T   si_dead_runs': T = max(threshold, fl32(rel_threshold * peak)), the peak over the FINITE samples; with rel_threshold == 0
+ *             the peak is not computed and T = threshold.
+ *   sq(k)     (double)x[k] * (double)x[k], exact for every finite fp32 and every int16 (-32768 included).  bad(k): x[k] is NaN or +-inf.
+ *   W(i)      [max(0, i - h), min(n - 1, i + h)], cnt(i) = |W(i)|: samples in front of the base and at or past n do not exist and are
+ *             never read; a window at either end of the file is truncated, and so is its count.
+ *   E(i)      the sum of sq(k) over k in W(i), in float64, BY ADDITIONS ONLY: no window is a difference of running sums (behind one
+ *             3e38 sample such a difference is garbage, and one NaN would poison every window after it).  The order of the additions
+ *             is the implementation's: E lies within cnt * 2^-52 * E of the exact sum, and is exact whenever every partial sum is
+ *             representable -- always for int16 (E < 2^42), and for fp32 samples on a 2^-20 grid with |x| <= 1.
+ *   low(i)    no bad sample lies in W(i), and E(i) <= lim(i) = fl64(((double)T * (double)T) * cnt(i)): the square exact, the product
+ *             one rounding.  That is RMS(W(i)) <= T without a division or a root.
+ *   dead(j)   low(i) for some i with |i - j| <= h and 0 <= i < n: the UNION of the low windows.  An exact-zero dropout [s, e) of at
+ *             least 2 h + 1 samples in loud audio therefore comes back as exactly [s, e), not shrunk by h on each side.
+ * channel >= 0 scans that channel: its window is elements k * channels + channel, never the adjacent elements, and the peak is taken
+ * over that channel's elements.  channel = -1 is JOINT: a sample time is dead when EVERY channel's dead_c holds, each by its own
+ * windows, against one T from the peak over all elements of the file.
+ * Two consequences: with half = 0, low(i) <=> |x[i]| <= T exactly (both squares are exact) and the bytes are those of si_dead_runs(kind =
+ * SI_DEAD_QUIET); a huge finite sample, 3e38 at position p, followed by zeros starts a run at exactly p + 1.
+ * The result is si_quiet_runs': every maximal run of dead samples of at least min_len samples as int32 (start, len) rows sorted by
+ * start, rows [0, min(total, max_runs)) written and the rows past them untouched, the total in n_runs (device int32 (1)); the same
+ * input gives the same bytes (no atomics; plain stores).  threshold_out, when not NULL, is a device fp32 word that receives T.
+ * Scratch is si_dead_runs'.  One workgroup stages 2048 + 4 * half squares in LDS (139 264 bytes at SI_LEVEL_MAX_HALF).
+ * SI_EINVAL before any launch, naming the argument, for: everything si_dead_runs refuses for the arguments they share (x, n, channels,
+ * channel, threshold negative or NaN, rel_threshold NaN or outside [0, 1], min_len, runs, max_runs, n_runs); half outside 0 ..
+ * SI_LEVEL_MAX_HALF; a threshold that is not finite. */
+#define SI_LEVEL_MAX_HALF 1024
+int si_level_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int half, float threshold, float rel_threshold,
+                  int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

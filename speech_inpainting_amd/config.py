@@ -69,7 +69,10 @@ class PredictConfig:
                                    # quiet, and is repaired in all of them: DESIGN.md 4.18)
     detect_dead: Optional[dict] = None  # `kind:`, `rel_threshold:` and `held_tol:` inside `detect:`: kind "quiet" (default),
                                         # "held" (a sample repeated, a DC level) or "any"; rel_threshold a fraction of the file's peak in
-                                        # [0, 1]; held_tol in full-scale units like threshold.  {quiet, 0.0, 0.0} is the detection of 4.15
+                                        # [0, 1]; held_tol in full-scale units like threshold.  {quiet, 0.0, 0.0} is the detection of 4.15.
+                                        # kind "level" (DESIGN.md 4.25): the RMS level of a window of `win_ms:` against the threshold
+    detect_level: Optional[dict] = None  # `win_ms:` inside `detect:` ({win_ms: 2.0}): the window of kind "level" in
+                                         # milliseconds, read at no other kind; None without `detect:`
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -164,7 +167,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
             if long_cfg["batch"] < 1 or long_cfg["clip_s"] <= 2 * long_cfg["context_s"]:
                 raise ValueError(f"{path}: `long:` needs batch >= 1 and clip_s > 2 * context_s, got {long_cfg}")
-        detect_cfg, detect_channels, detect_dead = None, "each", None
+        detect_cfg, detect_channels, detect_dead, detect_level = None, "each", None, None
         if "detect" in data:
             dm = data["detect"] if data["detect"] is not None else {}
             if not isinstance(dm, dict):
@@ -179,9 +182,9 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             detect_dead = {"kind": "quiet", "rel_threshold": 0.0, "held_tol": 0.0}
             if "kind" in dm:
                 detect_dead["kind"] = dm.pop("kind")
-                if detect_dead["kind"] not in ("quiet", "held", "any"):
+                if detect_dead["kind"] not in ("quiet", "held", "any", "level"):
                     raise ValueError(f"{path}: detect.kind = {detect_dead['kind']!r}: quiet (the default: |x| <= the threshold), held (a sample "
-                                     f"repeated, a DC level) or any")
+                                     f"repeated, a DC level) or any, or level (the RMS level of a window of win_ms milliseconds <= the threshold)")
             for key in ("rel_threshold", "held_tol"):
                 if key in dm:
                     detect_dead[key] = float(dm.pop(key))
@@ -189,6 +192,15 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                         raise ValueError(f"{path}: detect.{key} = {detect_dead[key]} is negative")
             if detect_dead["rel_threshold"] > 1:
                 raise ValueError(f"{path}: detect.rel_threshold = {detect_dead['rel_threshold']} is a fraction of the file's peak, at most 1")
+            detect_level = {"win_ms": 2.0}
+            if "win_ms" in dm:
+                detect_level["win_ms"] = float(dm.pop("win_ms"))
+                if detect_dead["kind"] != "level":
+                    raise ValueError(f"{path}: detect.win_ms needs `kind: level` (kind: {detect_dead['kind']} judges sample by sample and has no window)")
+                if not 0 <= detect_level["win_ms"] < float("inf"):
+                    raise ValueError(f"{path}: detect.win_ms = {detect_level['win_ms']} is negative or not finite")
+            if detect_dead["kind"] == "level" and detect_dead["held_tol"] != 0:
+                raise ValueError(f"{path}: detect.held_tol = {detect_dead['held_tol']} with `kind: level` (held samples are kind: held or any)")
             if "channels" in dm:
                 detect_channels = dm.pop("channels")
                 if detect_channels not in ("each", "joint"):
@@ -199,7 +211,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             for key, val in dm.items():
                 if key not in detect_cfg:
                     raise ValueError(f"{path}: unknown key `{key}` in `detect:` (it takes threshold, min_ms, max_ms, pad_frames, channels, kind, rel_threshold, "
-                                     f"held_tol)")
+                                     f"held_tol) and, with kind: level, win_ms")
                 detect_cfg[key] = int(val) if key == "pad_frames" else float(val)
                 if not detect_cfg[key] >= 0:
                     raise ValueError(f"{path}: detect.{key} = {detect_cfg[key]} is negative")
@@ -219,7 +231,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
             raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, detect=detect_cfg,
-            detect_channels=detect_channels, detect_dead=detect_dead)
+            detect_channels=detect_channels, detect_dead=detect_dead, detect_level=detect_level)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

@@ -361,6 +361,10 @@ int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, bool pcm16, int n, int c
 // the same channel (kind & 2); channels = 1 is a one-channel file; *thr_out (device, may be null) receives the effective threshold
 int si_launch_dead_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, int kind, float thr, float rel, float tol,
                         int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
+// the maximal runs of samples under a window of low RMS level: the windows of 2 half + 1 samples whose energy is at
+// most T^2 times their sample count, T = max(thr, rel * peak), dilated by half; channels and *thr_out as above
+int si_launch_level_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, int half, float thr, float rel, int min_len,
+                         int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // repair at the file's own sample rate (rate_kernels.hip)

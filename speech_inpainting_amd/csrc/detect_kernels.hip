@@ -5,6 +5,7 @@
 //   detect_bits_ch_kernel  the same pass 1 over an INTERLEAVED recording: one channel of it, or all of them jointly
 //   detect_peak*_kernel, detect_dead*_kernel  pass 0 and another pass 1: the bit means DEAD -- quiet against a threshold
 //                          that follows the recording's peak, or held (equal to a neighbour) -- and the passes below do not care
+//   detect_level_kernel    a third pass 1: the bit means that a window of low RMS level reaches over the sample
 //   detect_carry_kernel    carry[c] = the length of the quiet run that ends exactly in front of chunk c (a segmented scan, one workgroup)
 //   detect_runs_kernel     <false>: the qualifying runs that END in each chunk, counted; <true>: written at offset[c] + rank
 //   detect_offsets_kernel  the exclusive scan of the counts (one workgroup) and the total, a plain store
@@ -468,6 +469,150 @@ __global__ __launch_bounds__(256) void detect_dead_ch_kernel(const T* __restrict
     dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
 }
 
+// ------------------------------------------------------------------------------------------------ windowed RMS level
+// A third pass 1 in front of the same passes 2 - 5: sample j is DEAD when a window of low level reaches over it.  With h = half,
+//   E(i)    = the sum of x[k]^2 over k in [max(0, i - h), min(n - 1, i + h)], float64, each square exact
+//   low(i)  = no NaN or +-inf in that window, and E(i) <= fl64((T T) cnt(i)), cnt(i) the window's samples (truncated at both ends)
+//   dead(j) = low(i) for some i in [j - h, j + h] inside [0, n): the union of the low windows
+// A chunk needs low on [c0 - h, c0 + DT_CHUNK + h) and therefore samples on [c0 - 2 h, c0 + DT_CHUNK + 2 h): N = DT_CHUNK + 4 h squares,
+// staged as float64 in dynamic LDS, lane t on element t.  A time outside [0, n) does not exist: it is not loaded, its square is 0
+// (adding +0.0 to a sum of non-negative doubles changes nothing) and it is no `bad` sample; only cnt knows the truncation.
+// NO WINDOW IS A DIFFERENCE OF RUNNING SUMS: behind one 3e38 sample a float64 prefix difference is garbage, and one NaN would poison
+// every window after it.  The image is cut into segments of 2 h + 1 squares; P[p] sums its segment up to p, S[p] from p to the
+// segment's end (two segmented scans, additions only), and the window [q, q + 2 h] is S[q] + P[q + 2 h] -- or the whole segment S[q]
+// when it starts on one (van Herk's decomposition).  `bad` samples are counted with integers, whose prefix differences are exact; the
+// dilation is an integer prefix count of low as well.
+// LDS (cdna_hip_programming.md section 2): the staging and the window loops run lane t on element t + 256 k; the scans give a thread `per`
+// consecutive elements with `per` ODD, so the 32 lanes of a ds_read_b64 group fall on 32 different bank pairs.
+struct LvSeg { int f; double v; };   // a span of a segmented sum: v = the sum since the last segment head in it (all of it when f = 0)
+__device__ __forceinline__ LvSeg lv_then(LvSeg p, LvSeg q) { return LvSeg{p.f | q.f, q.f ? q.v : p.v + q.v}; }   // q after p
+
+__device__ __forceinline__ void lv_square(float v, double& s, int& bad) {
+    const bool finite = (__float_as_int(v) & 0x7fffffff) < 0x7f800000;
+    const double d = finite ? (double)v : 0.0;
+    s = d * d;                                                        // 24 x 24 bits: exact
+    bad = finite ? 0 : 1;
+}
+__device__ __forceinline__ void lv_square(int16_t v, double& s, int& bad) { const int a = v; s = (double)(a * a); bad = 0; }   // at most 2^30
+
+// dst[p] = the sum of src over p's segment up to p (REV = false: from the segment's first element; true: from p to its last).  Segments
+// are [k L, (k + 1) L) cut at N.  Thread t walks `per` consecutive elements in scan order, the 256 partial sums are scanned with
+// shuffles and four wave totals (sw), then it walks them again with its carry.  src == dst is fine.  Every thread calls it.
+template <bool REV>
+__device__ __forceinline__ void lv_seg_scan(const double* src, double* dst, int N, int per, int L, LvSeg* sw) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int u0 = min(t * per, N), u1 = min(u0 + per, N);
+    LvSeg mine{0, 0.0};
+    for (int u = u0; u < u1; ++u) {
+        const int p = REV ? N - 1 - u : u;
+        const bool head = REV ? p % L == L - 1 : p % L == 0;
+        const double a = src[p];
+        mine = head ? LvSeg{1, a} : LvSeg{mine.f, mine.v + a};
+    }
+    LvSeg incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const LvSeg p{__shfl_up(incl.f, o, 64), __shfl_up(incl.v, o, 64)};
+        if (lane >= o) incl = lv_then(p, incl);
+    }
+    if (lane == 63) sw[wave] = incl;
+    __syncthreads();
+    LvSeg pre{0, 0.0};
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+        if (w < wave) pre = lv_then(pre, sw[w]);
+    LvSeg ex{__shfl_up(incl.f, 1, 64), __shfl_up(incl.v, 1, 64)};
+    if (lane == 0) ex = LvSeg{0, 0.0};
+    double run = lv_then(pre, ex).v;
+    for (int u = u0; u < u1; ++u) {
+        const int p = REV ? N - 1 - u : u;
+        const bool head = REV ? p % L == L - 1 : p % L == 0;
+        const double a = src[p];
+        run = head ? a : run + a;
+        dst[p] = run;
+    }
+    __syncthreads();                                                  // dst is read, and sw written again, after this
+}
+
+// a[p] = a[0] + ... + a[p], in place, integers.  Every thread calls it.
+__device__ __forceinline__ void lv_count_scan(int* a, int N, int per, int* sw) {
+    const int t = threadIdx.x;
+    const int u0 = min(t * per, N), u1 = min(u0 + per, N);
+    int mine = 0;
+    for (int u = u0; u < u1; ++u) mine += a[u];
+    int unused;
+    int run = dt_block_excl(mine, 0, sw, unused, DtAdd());
+    for (int u = u0; u < u1; ++u) {
+        run += a[u];
+        a[u] = run;
+    }
+    __syncthreads();
+}
+
+// grid (chunks), 256 threads, dynamic LDS 20 N + 4 M bytes (N = DT_CHUNK + 4 h squares, M = DT_CHUNK + 2 h windows; 139 264 at h = 1024).
+// x is (n, ch) interleaved (ch = 1: one channel); channel >= 0 scans that channel, channel < 0 walks the channels one after another
+// through the same image and ANDs their bits.  Element offsets are 64-bit.  thr_dev, when given, holds T (pass 0); else T = thr.
+template <typename T>
+__global__ __launch_bounds__(256) void detect_level_kernel(const T* __restrict__ x, int n, int ch, int channel, int h, float thr,
+                                                           const float* __restrict__ thr_dev, float* __restrict__ thr_out,
+                                                           uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    extern __shared__ __attribute__((aligned(16))) char lv_img[];
+    __shared__ int sw[4];
+    __shared__ LvSeg ssw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    const int N = DT_CHUNK + 4 * h, M = DT_CHUNK + 2 * h, L = 2 * h + 1;
+    const int per = ((N + 255) / 256) | 1, perm = ((M + 255) / 256) | 1;
+    double* P = reinterpret_cast<double*>(lv_img);                    // the squares, then their segment prefixes
+    double* S = P + N;                                                // their segment suffixes
+    int* bad = reinterpret_cast<int*>(S + N);                         // 1 at NaN / +-inf, then its prefix count
+    int* low = bad + N;                                               // low(c0 - h + q), then its prefix count
+    const float Tq = thr_dev ? *thr_dev : thr;
+    if (thr_out && c == 0 && t == 0) *thr_out = Tq;
+    const double T2 = (double)Tq * (double)Tq;                        // exact
+    const int m = channel < 0 ? ch : 1;
+    unsigned b = 0xffu;
+    for (int k = 0; k < m; ++k) {
+        const int col = channel < 0 ? k : channel;
+        for (int p = t; p < N; p += 256) {
+            const long time = (long)c0 - 2 * h + p;
+            double s = 0.0;
+            int bd = 0;
+            if (time >= 0 && time < n) lv_square(x[(size_t)time * ch + col], s, bd);
+            P[p] = s;
+            bad[p] = bd;
+        }
+        __syncthreads();
+        lv_seg_scan<true>(P, S, N, per, L, ssw);
+        lv_seg_scan<false>(P, P, N, per, L, ssw);
+        lv_count_scan(bad, N, per, sw);
+        for (int q = t; q < M; q += 256) {
+            const long i = (long)c0 - h + q;                          // the window's centre; its squares are image positions [q, q + 2 h]
+            int lo = 0;
+            if (i >= 0 && i < n) {
+                const double E = q % L == 0 ? S[q] : S[q] + P[q + 2 * h];
+                const int nb = bad[q + 2 * h] - (q > 0 ? bad[q - 1] : 0);
+                const long a = i - h > 0 ? i - h : 0, z = i + h < n - 1 ? i + h : n - 1;
+                const double lim = __dmul_rn(T2, (double)(z - a + 1));
+                lo = (nb == 0 && E <= lim) ? 1 : 0;
+            }
+            low[q] = lo;
+        }
+        __syncthreads();
+        lv_count_scan(low, M, perm, sw);
+        unsigned bk = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int r = t * 8 + j;                                  // low on times [c0 + r - h, c0 + r + h] = positions [r, r + 2 h]
+            const int cnt = low[r + 2 * h] - (r > 0 ? low[r - 1] : 0);
+            bk |= (r < len && cnt > 0) ? 1u << j : 0u;
+        }
+        b &= bk;
+        __syncthreads();                                              // the next channel stages over the image
+    }
+    dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
+}
+
 // ------------------------------------------------------------------------------------------------ launcher
 size_t si_detect_scratch_bytes(int n) {
     const size_t chunks = ((size_t)n + DT_CHUNK - 1) / DT_CHUNK;
@@ -476,13 +621,16 @@ size_t si_detect_scratch_bytes(int n) {
 
 // What si_dead_runs adds to a detection call; the quiet routes pass none.
 struct DtDead { int kind; float rel, tol; float* thr_out; };
+// What si_level_runs adds instead.
+struct DtLevel { int half; float rel; float* thr_out; };
 
 // The caller (si_quiet_runs, si_quiet_runs_ch) checked every argument.  scratch: si_detect_scratch_bytes(n) bytes, 16-byte aligned.
 // channels = 0: x is one channel of n samples (detect_bits_kernel); channels >= 1: x is interleaved, n sample times of `channels`
 // channels, and `channel` picks one of them or, below 0, all of them jointly (detect_bits_ch_kernel).  Passes 2 - 5 are the same launches.
 // dead != nullptr: pass 1 is detect_dead(_ch)_kernel, behind pass 0 when dead->rel > 0; nullptr: the launches above.
+// level != nullptr (dead is nullptr then): pass 1 is detect_level_kernel, behind the same pass 0 when level->rel > 0.
 static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
-                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr) {
+                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr, const DtLevel* level = nullptr) {
     const int chunks = (int)(((long)n + DT_CHUNK - 1) / DT_CHUNK);
     const size_t words = ((size_t)chunks * sizeof(int32_t) + 15) & ~(size_t)15;
     uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch);
@@ -497,9 +645,10 @@ static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels
     const double bits = (double)chunks * 256.0, sums = (double)chunks * 4.0;
     const double samples = (double)n * (channels ? channels : 1) * (pcm16 ? 2.0 : 4.0);
 
-    if (dead) {
+    if (dead || level) {
         const float* thr_dev = nullptr;
-        if (dead->rel > 0.f) {
+        const float rel = dead ? dead->rel : level->rel;
+        if (rel > 0.f) {
             si_prof_begin(ctx, "detect_peak", 0.0, samples + sums, st);
             if (channels == 0) {
                 if (pcm16) detect_peak_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, cpeak);
@@ -511,12 +660,21 @@ static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels
             si_prof_end(ctx, st);
             SI_HIP_CHECK(hipGetLastError());
             si_prof_begin(ctx, "detect_peak_final", 0.0, sums + 8.0, st);
-            detect_peak_final_kernel<<<dim3(1), 256, 0, st>>>(cpeak, chunks, thr, dead->rel, pk);
+            detect_peak_final_kernel<<<dim3(1), 256, 0, st>>>(cpeak, chunks, thr, rel, pk);
             si_prof_end(ctx, st);
             SI_HIP_CHECK(hipGetLastError());
             thr_dev = pk + 1;
         }
-        if (channels == 0) {
+        if (level) {
+            const int h = level->half, ch = channels ? channels : 1;
+            const size_t lds = 20 * (size_t)(DT_CHUNK + 4 * h) + 4 * (size_t)(DT_CHUNK + 2 * h);   // 139 264 bytes at h = SI_LEVEL_MAX_HALF
+            const void* kern = pcm16 ? reinterpret_cast<const void*>(&detect_level_kernel<int16_t>) : reinterpret_cast<const void*>(&detect_level_kernel<float>);
+            if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
+            // profiled in the family of the descriptor routes' pass 1, as both detect_dead kernels are: the lists of families are closed
+            si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
+            if (pcm16) detect_level_kernel<int16_t><<<dim3(chunks), 256, lds, st>>>(static_cast<const int16_t*>(x), n, ch, channels ? channel : 0, h, thr, thr_dev, level->thr_out, bitmap, lead, trail);
+            else detect_level_kernel<float><<<dim3(chunks), 256, lds, st>>>(static_cast<const float*>(x), n, ch, channels ? channel : 0, h, thr, thr_dev, level->thr_out, bitmap, lead, trail);
+        } else if (channels == 0) {
             si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
             if (pcm16) detect_dead_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
             else detect_dead_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
@@ -580,4 +738,12 @@ int si_launch_dead_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int chann
                         int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st) {
     const DtDead dead{kind, rel, tol, thr_out};
     return dt_launch(ctx, x, pcm16, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, &dead);
+}
+
+// The windowed RMS level; channels = 1 is a one-channel file, as for si_launch_dead_runs.
+int si_launch_level_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, int half, float thr, float rel, int min_len,
+                         int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st) {
+    const DtLevel level{half, rel, thr_out};
+    return dt_launch(ctx, x, pcm16, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
+                     &level);
 }

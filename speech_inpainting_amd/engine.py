@@ -891,7 +891,7 @@ class InpaintingEngine:
     def conceal_file(self, x, sr: int, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
                      merge_frames: Optional[int] = None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
                      return_windows: bool = False, feed: str = "recording", detect: str = "each", kind: str = "quiet",
-                     rel_threshold: float = 0.0, held_tol: float = 0.0) -> Dict[str, object]:
+                     rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = 2.0) -> Dict[str, object]:
         """File in, repaired file out, at the file's own rate and in its own sample type: find_gaps on x itself, where a dropout is
         still exact zeros, then patch_file with the gaps it found.  The usable frames are those of the recording's 22.05 kHz length
         ceil(n * 22050 / sr) (`recording_frames`), and a gap longer than the planner's budget counts as long, as in conceal_recording.
@@ -902,7 +902,8 @@ class InpaintingEngine:
         in the channel it is in (gaps, skipped: one list per channel); detect="joint" runs it once over the sample times at which
         EVERY channel is quiet and repairs those gaps in every channel (gaps, skipped: one list).  A one-channel file ignores it.
         kind, rel_threshold, held_tol: find_gaps' (DESIGN.md 4.20); held_tol in x's own units, like threshold.  Off their defaults the
-        dictionary gains `threshold`, the effective one (one per channel for detect="each" on an interleaved file)."""
+        dictionary gains `threshold`, the effective one (one per channel for detect="each" on an interleaved file).
+        kind "level" with win_ms: find_gaps' (DESIGN.md 4.25), in the file's own samples like everything else here."""
         sr, clip_frames, min_context = int(sr), int(clip_frames), int(min_context)
         if detect not in ("each", "joint"):
             raise ValueError(f"conceal_file: detect = {detect!r}: 'each' or 'joint'")
@@ -919,7 +920,7 @@ class InpaintingEngine:
             max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
         fade22 = -(-G.file_fade(fade_ms, sr) * P // Q)
         find = lambda c: self.find_gaps(x, sr, threshold, min_ms, max_ms, pad_frames, merge_frames, fade22, n_rec, lim, channel=c, kind=kind,
-                                        rel_threshold=rel_threshold, held_tol=held_tol)
+                                        rel_threshold=rel_threshold, held_tol=held_tol, **({"win_ms": win_ms} if kind == "level" else {}))
         kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed)
         if many and detect == "each":
             found = [find(c) for c in range(shape[1])]
@@ -989,6 +990,39 @@ class InpaintingEngine:
         runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
         return (runs, T) if return_threshold else runs
 
+    def find_level_runs(self, x, win: Optional[int] = None, half: Optional[int] = None, threshold: float = 0.0, rel_threshold: float = 0.0,
+                        min_len: int = 1, max_runs: int = 65536, channel: Optional[int] = None, return_threshold: bool = False):
+        """find_dead_runs for a dropout that is a noise floor (si_level_runs): a sample is dead when a window of
+        2 * half + 1 samples of its channel that reaches over it has an RMS level of at most T = max(threshold, rel_threshold * the
+        peak of x), and no NaN or inf.  Give the window as `half`, or as `win` = its odd length in samples; half = 0 is the sample-wise
+        "quiet".  x, channel, min_len, max_runs, threshold, rel_threshold and the rows are find_dead_runs'.
+        One D2H copy: the count, which with return_threshold=True also carries T; -> runs, or (runs, T)."""
+        if (win is None) == (half is None):
+            raise ValueError("find_level_runs: give the window as win = its odd length in samples, or as half = (win - 1) / 2, not both")
+        if win is not None:
+            if int(win) != win or int(win) < 1 or int(win) % 2 == 0:
+                raise ValueError(f"find_level_runs: win = {win}: an odd number of samples, 2 * half + 1")
+            half = (int(win) - 1) // 2
+        if int(half) != half or not 0 <= int(half) <= G.LEVEL_MAX_HALF:
+            raise ValueError(f"find_level_runs: half = {half} samples, outside 0 .. {G.LEVEL_MAX_HALF}")
+        x = torch.as_tensor(x)
+        many = x.dim() == 2 and x.shape[1] >= 2
+        if many and channel is None:
+            raise ValueError(f"find_level_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
+        if not many and channel is not None and int(channel) not in (-1, 0):
+            raise ValueError(f"find_level_runs: channel = {channel} of a one-channel recording")
+        x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32)
+        x = x.contiguous() if many else x.reshape(-1).contiguous()
+        words = torch.zeros(2, dtype=torch.int32, device=self.device)      # {the count, T's bits}: one copy brings both
+        runs, _ = self.ctx.level_runs(x, int(half), threshold, rel_threshold, min_len, max_runs, n_runs=words[:1],
+                                      channel=int(channel) if many else None, threshold_out=words[1:].view(torch.float32))
+        host = words.cpu()
+        total, T = int(host[0]), float(host[1:].view(torch.float32)[0])
+        if total > int(max_runs):
+            raise ValueError(f"find_level_runs: {total} runs of at least {int(min_len)} dead samples, more than max_runs = {int(max_runs)}")
+        runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+        return (runs, T) if return_threshold else runs
+
     def recording_frames(self, n22: int, clip_frames: int = 200, n16: Optional[int] = None) -> Tuple[int, int]:
         """(n_rec_frames, lim_frames) of a recording of n22 samples at 22.05 kHz as patch_recording serves it: its 20 ms frames and
         the usable ones [0, lim) -- a context clip's min(T, Tm) (patch_recording's own arithmetic, n16 = the samples of a supplied
@@ -1004,7 +1038,7 @@ class InpaintingEngine:
     def find_gaps(self, x, sr: int = 22050, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
                   merge_frames: Optional[int] = None, fade: int = 110, n_rec_frames: Optional[int] = None,
                   lim_frames: Optional[int] = None, channel: Optional[int] = None, kind: str = "quiet", rel_threshold: float = 0.0,
-                  held_tol: float = 0.0) -> Dict[str, object]:
+                  held_tol: float = 0.0, win_ms: float = 2.0) -> Dict[str, object]:
         """The dropouts of a recording x (n samples at `sr` Hz, fp32 in full-scale units or int16 PCM): runs of at least min_ms of
         |x| <= threshold (find_quiet_runs), mapped by gaps.runs_to_gaps onto the 20 ms grid of the recording's n_rec_frames frames
         (default n * 50 // sr) with the usable frames [0, lim_frames).  merge_frames None = 2 * the frames one cross-fade of `fade`
@@ -1013,13 +1047,21 @@ class InpaintingEngine:
         runs (device int32 (R, 2), samples at `sr`).
         An interleaved x (n, ch) takes find_quiet_runs' `channel`; n, the runs and the gaps then count sample times and frames.
         kind, rel_threshold, held_tol: find_dead_runs' (DESIGN.md 4.20).  At their defaults the runs are find_quiet_runs', the same
-        launches; anything else goes to find_dead_runs, and the dictionary gains `threshold`: the effective one, T."""
+        launches; anything else goes to find_dead_runs, and the dictionary gains `threshold`: the effective one, T.
+        kind "level" (DESIGN.md 4.25): the runs are find_level_runs' -- the RMS level of a window of win_ms milliseconds, half =
+        round(win_ms * sr / 2000) samples on each side, against the threshold -- and the dictionary carries `threshold` as well.
+        held_tol has no meaning there and must be 0; win_ms is read at no other kind."""
         x = torch.as_tensor(x)
         n, sr = (x.shape[0] if x.dim() == 2 else x.numel()), int(sr)
         if n < 1 or sr <= 0:
             raise ValueError(f"find_gaps: {n} samples at {sr} Hz")
         min_len, T = max(1, int(round(float(min_ms) * sr / 1000.0))), None
-        if kind == "quiet" and float(rel_threshold) == 0.0 and float(held_tol) == 0.0:
+        if kind == "level":
+            if float(held_tol) != 0.0:
+                raise ValueError(f"find_gaps: held_tol = {held_tol} with kind = 'level' (held samples are kind 'held' or 'any')")
+            runs, T = self.find_level_runs(x, half=G.level_half(win_ms, sr), threshold=threshold, rel_threshold=rel_threshold, min_len=min_len,
+                                           channel=channel, return_threshold=True)
+        elif kind == "quiet" and float(rel_threshold) == 0.0 and float(held_tol) == 0.0:
             runs = self.find_quiet_runs(x, threshold, min_len, channel=channel)
         else:
             runs, T = self.find_dead_runs(x, kind, threshold, rel_threshold, held_tol, min_len, channel=channel, return_threshold=True)
@@ -1031,12 +1073,13 @@ class InpaintingEngine:
     def conceal_recording(self, wave22, wave16=None, detect_on=None, sr: int = 22050, threshold: float = 0.0, min_ms: float = 5.0,
                           max_ms: float = 400.0, pad_frames: int = 0, merge_frames: Optional[int] = None, fade: int = 110,
                           clip_frames: int = 200, min_context: int = 50, batch: int = 32, pcm: bool = False, kind: str = "quiet",
-                          rel_threshold: float = 0.0, held_tol: float = 0.0) -> Dict[str, object]:
+                          rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = 2.0) -> Dict[str, object]:
         """File in, repaired file out: find_gaps, then patch_recording unchanged with the gaps it found.  Detection runs on detect_on
         when given -- the file's own samples at `sr` Hz, where a dropout is still exact zeros -- else on wave22 (sr is 22050 then).
         The usable frames are patch_recording's own (its last context's min(T, Tm)), and a gap longer than the planner's budget
         clip_frames - 2 * min_context counts as long whatever max_ms says.
         kind, rel_threshold, held_tol: find_gaps' (held samples, a threshold relative to the peak).
+        kind "level" with win_ms: find_gaps' too (a noise-floor dropout, by windowed RMS level).
         -> patch_recording's dictionary + gaps + skipped [+ threshold].  With nothing found: an exact copy; only the detection kernels launched."""
         as1d = lambda x: torch.as_tensor(x).to(self.device, torch.float32).reshape(-1).contiguous()
         wave22 = as1d(wave22)
@@ -1046,7 +1089,8 @@ class InpaintingEngine:
         if n_rec > clip_frames:
             max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
         found = self.find_gaps(wave22 if detect_on is None else detect_on, 22050 if detect_on is None else sr, threshold, min_ms, max_ms,
-                               pad_frames, merge_frames, fade, n_rec, lim, kind=kind, rel_threshold=rel_threshold, held_tol=held_tol)
+                               pad_frames, merge_frames, fade, n_rec, lim, kind=kind, rel_threshold=rel_threshold, held_tol=held_tol,
+                               **({"win_ms": win_ms} if kind == "level" else {}))
         out = self.patch_recording(wave22, found["gaps"], wave16=wave16, fade=fade, clip_frames=clip_frames, min_context=min_context,
                                    batch=batch, pcm=pcm)
         out["gaps"], out["skipped"] = found["gaps"], found["skipped"]

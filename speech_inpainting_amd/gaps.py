@@ -431,6 +431,23 @@ def file_fade(fade_ms: float, sr: int) -> int:
     return int(round(float(fade_ms) * int(sr) / 1000.0))
 
 
+LEVEL_MAX_HALF = 1024   # SI_LEVEL_MAX_HALF of include/si_hip.h: the largest half window of the level detector
+
+
+def level_half(win_ms: float, sr: int) -> int:
+    """The level detector's half window in file samples: round(win_ms * sr / 2000), Python's round -- a window of 2 * half + 1 samples
+    is win_ms long to within a sample (2 ms: 8 at 8 kHz, 22 at 22.05 kHz, 48 at 48 kHz, 192 at 192 kHz).  A ValueError that names the
+    longest window this rate allows when half would pass LEVEL_MAX_HALF, and for a negative or NaN win_ms."""
+    win_ms, sr = float(win_ms), int(sr)
+    if not win_ms >= 0 or sr <= 0:
+        raise ValueError(f"win_ms = {win_ms} at {sr} Hz: a window length in milliseconds, not negative")
+    half = int(round(win_ms * sr / 2000.0)) if math.isfinite(win_ms) else LEVEL_MAX_HALF + 1
+    if half > LEVEL_MAX_HALF:
+        most = math.floor(2000.0 * LEVEL_MAX_HALF / sr * 1000.0) / 1000.0
+        raise ValueError(f"win_ms = {win_ms} at {sr} Hz is a half window of more than {LEVEL_MAX_HALF} samples: at most win_ms = {most} at this rate")
+    return half
+
+
 def file_spans(gaps: Sequence[Gap], sr: int) -> List[Gap]:
     """(start, len) in FILE samples per gap (first frame, frame count) of the 20 ms grid: samples [ceil(p * sr / 50),
     ceil((p + l) * sr / 50)) -- exactly the file samples whose 22.05 kHz position lies in [441 p, 441 (p + l)).  Integers only."""

@@ -19,7 +19,9 @@ min_ms: 5.0, max_ms: 400.0, pad_frames: 0}) beside `long:` and instead of `mask:
 printed and `gaps.json` is written beside the three waves.  `detect:` also takes `kind:` (quiet, the default; held: samples that
 repeat a neighbour, as an underrun or a DC level leaves them; any), `rel_threshold:` (a fraction of the file's own peak: the
 threshold is max(threshold, rel_threshold * peak)) and `held_tol:` (full scale, like threshold); off their defaults the effective
-threshold is printed and gaps.json records `kind` and `T` (engine.find_dead_runs).  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
+threshold is printed and gaps.json records `kind` and `T` (engine.find_dead_runs).  `kind: level` with `win_ms:` (2 by
+default) finds a dropout that is a noise floor -- dither, a concealer's comfort noise -- by the RMS level of a window of win_ms
+milliseconds against the threshold, and gaps.json records `kind`, `T` and `win_ms` (engine.find_level_runs).  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
 on the way out: the three waves keep the file's own rate and sample type (an int16 file stays int16), and patched.wav holds the file's
 own samples, bit for bit, outside the cross-fades (engine.patch_file).
 With `feed: contexts` beside `rate: file` the recording is not resampled as a whole on the way in either: only the context clips
@@ -360,7 +362,7 @@ def _detect_gaps(cfg: PredictConfig, engine: InpaintingEngine, raw: np.ndarray, 
     n_rec, lim = engine.recording_frames(n22, clip_frames)
     max_ms = d["max_ms"] if n_rec <= clip_frames else min(d["max_ms"], 20.0 * (clip_frames - 2 * min_context))
     found = engine.find_gaps(x, sr_file, d["threshold"] * scale, d["min_ms"], max_ms, d["pad_frames"], None, fade, n_rec, lim,
-                             **dead_keywords(cfg.detect_dead, scale))
+                             **dead_keywords(cfg.detect_dead, scale), **level_keywords(cfg))
     report = _dead_report(cfg, found, scale)
     for k, (pos, lm) in enumerate(found["gaps"]):
         print(f"Detected gap {k} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s")
@@ -379,14 +381,25 @@ def dead_keywords(dead: Optional[dict], scale: float) -> dict:
     return {"kind": dead["kind"], "rel_threshold": dead["rel_threshold"], "held_tol": dead["held_tol"] * scale}
 
 
+def level_keywords(cfg) -> dict:
+    """`detect:`'s win_ms as find_gaps and conceal_file take it: given with `kind: level` alone, so that every other
+    kind is called as it was.  win_ms is a time and, like rel_threshold, is not scaled for an int16 file."""
+    dead, level = getattr(cfg, "detect_dead", None), getattr(cfg, "detect_level", None)
+    if dead is None or dead["kind"] != "level":
+        return {}
+    return {"win_ms": level["win_ms"] if level is not None else 2.0}
+
+
 def _dead_report(cfg: PredictConfig, found: dict, scale: float) -> dict:
     """What gaps.json gains when the detection went through find_dead_runs: `kind`, and `T`, the effective threshold in the units the
     file was scanned in (one per channel for `channels: each`).  Printed too.  Empty at the defaults: gaps.json is then what it was."""
     if "threshold" not in found:
         return {}
     T, unit = found["threshold"], "int16 steps" if scale != 1.0 else "full scale"
-    print(f"Detection kind = {cfg.detect_dead['kind']}, effective threshold T = {T} ({unit})")
-    return {"kind": cfg.detect_dead["kind"], "T": T}
+    level = level_keywords(cfg)                                                    # kind level: the window is printed and recorded too
+    window = f", window win_ms = {level['win_ms']}" if level else ""
+    print(f"Detection kind = {cfg.detect_dead['kind']}, effective threshold T = {T} ({unit}){window}")
+    return {"kind": cfg.detect_dead["kind"], "T": T, **level}
 
 
 def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> int:
@@ -458,7 +471,7 @@ def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_
         scale = 32768.0 if x.dtype == np.int16 else 1.0                             # an int16 file is scanned as the int16 it holds
         joint = cfg.detect_channels == "joint"
         out = engine.conceal_file(dev, sr_file, d["threshold"] * scale, d["min_ms"], d["max_ms"], d["pad_frames"], detect=cfg.detect_channels,
-                                  **dead_keywords(cfg.detect_dead, scale), **kw)
+                                  **dead_keywords(cfg.detect_dead, scale), **level_keywords(cfg), **kw)
         report = _dead_report(cfg, out, scale)
         found = [(out["gaps"], out["skipped"])] if joint else list(zip(out["gaps"], out["skipped"]))
         for c, (gaps_c, skipped_c) in enumerate(found):

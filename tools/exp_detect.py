@@ -12,8 +12,12 @@ warm-up, device-synchronised wall clock per call:
       |x[i] - x[i-1]| <= 0, held = link(i) | link(i+1), then (b)'s run extraction
   (g) engine.find_dead_runs(kind="any", rel_threshold=1e-3) on that file (pass 0 reads the samples once more for the peak), and (h)
       its torch formulation: the peak over the finite samples, T = fp32(1e-3) * peak, (abs() <= T) | held
+  (i) engine.find_level_runs(half=22, threshold=16 int16 steps) on the same recording with its gaps filled by seeded NOISE of sigma =
+      12 int16 steps (si_level_runs: pass 1 with the windowed energy, the four scan passes), and (j) its torch
+      formulation: avg_pool1d of the float64 squares (count_include_pad=False: the truncated count) against T^2, max_pool1d of the
+      mask, then (b)'s run extraction
 
-Prints whether (a) equals (b), (e) equals (f), (g) equals (h) and (c) equals (d) bit for bit, one line per repeat, the medians, and -- from a separate, untimed run
+Prints whether (a) equals (b), (e) equals (f), (g) equals (h), (i) equals (j) and (c) equals (d) bit for bit, one line per repeat, the medians, and -- from a separate, untimed run
 under the library's profiler -- the per-kernel times of the detect_* family and the effective bytes per second of the whole call
 (the recording's bytes / the family's summed time).
 usage: python tools/exp_detect.py [--repeats 7] [--minutes 10] [--gaps 60] [--pcm16]"""
@@ -89,18 +93,42 @@ def torch_dead(rel):
     return torch.stack([start[keep], (end - start)[keep]], dim=1).to(torch.int32)
 
 
+# the same recording with every gap filled by a noise floor: rint(N(0, 12)) int16 steps, seeded (values on the 2^-15 grid in fp32)
+LEVEL_HALF, LEVEL_T = 22, 16.0
+noise22 = wave22.clone()
+gen = torch.Generator(device="cpu").manual_seed(7)
+for p, l in gaps:
+    noise22[441 * p:441 * (p + l)] = (torch.randn(441 * l, generator=gen) * 12.0).round().to(dev) / 32768.0
+xn = eng.to_int16(noise22) if a.pcm16 else noise22
+level_thr = LEVEL_T if a.pcm16 else LEVEL_T / 32768.0
+
+
+def torch_level():
+    sq = xn.to(torch.float64).square()[None, None]
+    mean = torch.nn.functional.avg_pool1d(sq, 2 * LEVEL_HALF + 1, 1, LEVEL_HALF, count_include_pad=False)
+    low = (mean <= level_thr * level_thr).to(torch.float32)
+    q = (torch.nn.functional.max_pool1d(low, 2 * LEVEL_HALF + 1, 1, LEVEL_HALF)[0, 0] > 0).to(torch.int8)
+    d = torch.diff(q, prepend=q.new_zeros(1), append=q.new_zeros(1))
+    start, end = torch.nonzero(d == 1).flatten(), torch.nonzero(d == -1).flatten()
+    keep = end - start >= MIN_LEN
+    return torch.stack([start[keep], (end - start)[keep]], dim=1).to(torch.int32)
+
+
 variants = {"a": lambda: eng.find_quiet_runs(x, 0.0, MIN_LEN), "b": torch_runs,
             "c": lambda: eng.conceal_recording(wave22, **KW), "d": lambda: eng.patch_recording(wave22, gaps, **KW),
             "e": lambda: eng.find_dead_runs(xh, "held", min_len=MIN_LEN), "f": lambda: torch_dead(0.0),
-            "g": lambda: eng.find_dead_runs(xh, "any", rel_threshold=1e-3, min_len=MIN_LEN), "h": lambda: torch_dead(1e-3)}
-oa, ob, oc, od, oe, of, og, oh = (fn() for fn in variants.values())
+            "g": lambda: eng.find_dead_runs(xh, "any", rel_threshold=1e-3, min_len=MIN_LEN), "h": lambda: torch_dead(1e-3),
+            "i": lambda: eng.find_level_runs(xn, half=LEVEL_HALF, threshold=level_thr, min_len=MIN_LEN), "j": torch_level}
+oa, ob, oc, od, oe, of, og, oh, oi, oj = (fn() for fn in variants.values())
 torch.cuda.synchronize()
 print(f"recording of {N22} samples ({N22 / 22050 / 60:.2f} min, {x.element_size()} bytes per sample), {len(gaps)} gaps of {LM} frames zeroed")
 print(f"(a) equals (b): {torch.equal(oa, ob)} ({oa.shape[0]} runs);  (c) found the gaps: {oc['gaps'] == gaps};  (c) equals (d) bit for bit: fp32",
       torch.equal(oc["patched"].view(torch.int32), od["patched"].view(torch.int32)), " int16", torch.equal(oc["patched_pcm"], od["patched_pcm"]))
 print(f"(e) equals (f): {torch.equal(oe, of)} ({oe.shape[0]} runs, {int((oe[:, 1] == 441 * LM + 1).sum())} of them a gap and the sample it holds);  "
       f"(g) equals (h): {torch.equal(og, oh)} ({og.shape[0]} runs)")
-del oa, ob, oc, od, oe, of, og, oh
+print(f"(i) equals (j): {torch.equal(oi, oj)} ({oi.shape[0]} runs, {sum(1 for r in oi.tolist() if r in [[441 * p, 441 * l] for p, l in gaps])} of them exactly a gap;  "
+      f"the sample-wise detector at the same threshold finds {eng.find_quiet_runs(xn, level_thr, MIN_LEN).shape[0]} runs)")
+del oa, ob, oc, od, oe, of, og, oh, oi, oj
 for fn in variants.values():
     for _ in range(WARMUP):
         fn()
@@ -117,7 +145,7 @@ for r in range(a.repeats):
 med = {k: statistics.median(v) for k, v in ms.items()}
 print("median ms/recording: " + "  ".join(f"({k}) {med[k]:.3f}" for k in variants))
 print(f"spread of (d) over {a.repeats} repeats: {max(ms['d']) - min(ms['d']):.3f} ms;  (c) - (d) {med['c'] - med['d']:+.3f} ms;  (a) / (b) {med['a'] / med['b']:.3f};  "
-      f"(e) / (f) {med['e'] / med['f']:.3f};  (g) / (h) {med['g'] / med['h']:.3f};  (e) / (a) {med['e'] / med['a']:.3f};  (g) / (a) {med['g'] / med['a']:.3f}")
+      f"(e) / (f) {med['e'] / med['f']:.3f};  (g) / (h) {med['g'] / med['h']:.3f};  (e) / (a) {med['e'] / med['a']:.3f};  (g) / (a) {med['g'] / med['a']:.3f};  (i) / (j) {med['i'] / med['j']:.3f};  (i) / (a) {med['i'] / med['a']:.3f}")
 # per-kernel device times, from a run of their own under the library's event profiler (every launch bracketed: not a step time)
 eng.ctx.profile_start(1000)
 for _ in range(10):
@@ -135,3 +163,16 @@ for what, call in (("kind=held", lambda: eng.find_dead_runs(xh, "held", min_len=
     total = sum(e["ms"] for e in rows.values()) / 10
     print(f"si_dead_runs ({what}) under the profiler: {total * 1e3:.1f} us per call = {xh.numel() * xh.element_size() / (total * 1e-3) / 1e9:.1f} GB/s of the "
           f"recording;  " + "  ".join(f"{n} {e['ms'] / e['launches'] * 1e3:.1f} us" for n, e in rows.items()))
+eng.ctx.profile_start(1000)
+for _ in range(10):
+    eng.find_level_runs(xn, half=LEVEL_HALF, threshold=level_thr, min_len=MIN_LEN)
+rows = {e["name"]: e for e in eng.ctx.profile_stop() if e["name"].startswith("detect_")}
+total = sum(e["ms"] for e in rows.values()) / 10
+print(f"si_level_runs (half={LEVEL_HALF}) under the profiler: {total * 1e3:.1f} us per call = {xn.numel() * xn.element_size() / (total * 1e-3) / 1e9:.1f} GB/s of the "
+      f"recording;  " + "  ".join(f"{n} {e['ms'] / e['launches'] * 1e3:.1f} us" for n, e in rows.items()))
+for half in (0, 110, 1024):
+    eng.ctx.profile_start(1000)
+    for _ in range(10):
+        eng.find_level_runs(xn, half=half, threshold=level_thr, min_len=MIN_LEN)
+    e = {e["name"]: e for e in eng.ctx.profile_stop()}["detect_dead"]             # the level kernel is profiled in pass 1's family
+    print(f"detect_level_kernel at half={half}: {e['ms'] / e['launches'] * 1e3:.1f} us")
