@@ -41,6 +41,8 @@
  *                           slicing)                                          I_ea/predict.py:79-80
  *   si_quiet_runs_ch / si_cut_rate_ch / si_patch_rate_ch  <- the three above on an interleaved multi-channel file, channel by channel,
  *                           where the script mixes its input down to one channel on load      I_ea/predict.py:79
+ *   si_cut_pair / si_cut_pair_ch  <- the script's TWO loads of the one file, at 22.05 kHz for the mel and at 16 kHz for HuBERT, each
+ *                           straight from the file's samples, for the context clips alone and in one launch    I_ea/predict.py:79-80
  *   si_load_weights      <- model.load_state_dict / generator.load_state_dict + remove_weight_norm + ApplyKmeans
  *                           I_ea/predict.py:117-122,149 ; I_ea/hifi_gan/models.py:125-132 ; I_ea/dataset/km_label.py:12-24
  *
@@ -724,6 +726,37 @@ int si_cut_rate_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int cha
                    const int32_t* start, int C, int L, const si_sinc_filter* filt, float* out, si_stream_t stream);
 int si_patch_rate_ch(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int channels, int channel, int sr, const si_rate_table* table,
                      const float* gen, int Lrow, const float* gain, const si_sinc_filter* filt, void* out, si_stream_t stream);
+
+/* ---- Both clip sets of a pass cut straight from the file, in one launch ------------------------------------------------
+ * The reference loads its input twice, each time from the file's own samples: librosa.load(path, sr=22050) for the mel and
+ * librosa.load(path, sr=16000) for HuBERT (I_ea/predict.py:79-80).  si_cut_rate serves the first; the calls below serve both, so that
+ * the encoder's 16 kHz clips are not a second resampling of the 22.05 kHz clips (with nothing before or after each clip) but the file's
+ * samples at the exact 16 kHz times -- and, for a 16 kHz file, the file's samples themselves, as librosa resamples nothing at equal rates.
+ *
+ * A clip starts on the 20 ms frame grid, the only grid the two rates share (gcd(22050, 16000) = 50): frame f is 22.05 kHz sample 441 f
+ * and 16 kHz sample 320 f.  out22 (C, L22) row c = 22.05 kHz samples 441 frame[c] + [0, L22), by si_cut_rate's definition with filt22
+ * (audio.design_kaiser_best(sr, 22050, .)): the bytes are si_cut_rate's.  out16 (C, L16) row c = 16 kHz samples j = 320 frame[c] +
+ * [0, L16): with (P16, Q16) = (16000, sr) / gcd, sample j sits at file position j Q16 / P16, n, r = divmod(j Q16, P16) in 64-bit
+ * integers, frac = scale (r / P16), and the two wings, their tap counts, the fma order and the single rounding to fp32 are si_cut_rate's
+ * on the tables of filt16 (audio.design_kaiser_best(sr, 16000, .); time_reg, n_time and ratio are NOT read).  The recording has
+ * N16 = ceil(n_file P16 / Q16) samples at 16 kHz; an output with j >= N16 lies at or past the file's end and is +0.0.
+ * sr = 16000: the 16 kHz row is the file's own samples, x[j] (fp32) or (float)v / 32768 (int16); no filter is applied and filt16 must be
+ * NULL, as it must be non-NULL at every other rate.  An int16 sample enters as (float)v / 32768; file samples outside [0, n_file) do not
+ * exist; a sample has the same bits in whichever clip, tile or batch it is cut.
+ * x as si_cut_rate's (si_cut_pair_ch: as si_cut_rate_ch's, channel `channel` of an interleaved file, never the neighbouring channel's
+ * element).  host_frame (HOST, C) is validated, frame (DEVICE, C) is read: the si_span_table rule; a device table that differs gives
+ * zeros, never a read outside the file.  One workgroup owns SI_CUT_PAIR_FRAMES consecutive frames of one clip (441 + 320 outputs each)
+ * and stages the file samples both rates read for them once, ceil(SI_CUT_PAIR_FRAMES sr / 50) + 2 + 2 max(H22, H16) floats of LDS.
+ * SI_EINVAL before any launch, naming the argument, for everything si_cut_rate[_ch] refuses (L is L22, start is 441 frame, filt is
+ * filt22), and: L16 < 1; a frame with 441 f + L22 > N22 or 320 f + L16 > ceil(N22 320 / 441) (which exceeds N16 by at most 1); filt16
+ * NULL when sr != 16000 or non-NULL when sr = 16000; a filt16 that fails filt22's checks; a staged tile above 64 KB.  C = 0 launches
+ * nothing and succeeds. */
+#define SI_CUT_PAIR_FRAMES 1
+int si_cut_pair(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_frame, const int32_t* frame, int C, int L22,
+                int L16, const si_sinc_filter* filt22, const si_sinc_filter* filt16, float* out22, float* out16, si_stream_t stream);
+int si_cut_pair_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr, const int32_t* host_frame,
+                   const int32_t* frame, int C, int L22, int L16, const si_sinc_filter* filt22, const si_sinc_filter* filt16, float* out22,
+                   float* out16, si_stream_t stream);
 
 /* ---- Held-sample and peak-relative dropouts ---------------------------------------------------------------------------
  * The reference has no detection: the script's user types the one mask into predict.yaml (I_ea/predict.py:85-90).  si_quiet_runs finds

@@ -62,6 +62,8 @@ class PredictConfig:
                                   # (patched.wav keeps the file's own rate and sample type: engine.patch_file)
     long_feed: str = "recording"  # `feed:` inside `long:` (needs rate: file): "recording" (default: the whole file is resampled to 22.05 kHz
                                   # to feed the model) or "contexts" (only the context clips are, straight from the file: DESIGN.md 4.17)
+    long_clips16: str = "resampled"   # `clips16:` inside `long:` (needs feed: contexts): "resampled" (default: the encoder's 16 kHz clips are
+                                      # the cut 22.05 kHz clips resampled) or "file" (they too are cut straight from the file: DESIGN.md 4.26)
     detect: Optional[dict] = None  # optional `detect:` mapping ({threshold: 0.0, min_ms: 5.0, max_ms: 400.0, pad_frames: 0}): the gaps are
                                    # found in the file itself (engine.find_gaps) instead of given as `mask:` / `masks:`; needs `long:`
     detect_channels: str = "each"  # `channels:` inside `detect:` (needs long: {rate: file}), for a multi-channel file: "each" (default:
@@ -141,7 +143,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             patch_fade_ms = float(pm.get("fade_ms", 5))
             if patch_fade_ms < 0:
                 raise ValueError(f"{path}: patch.fade_ms = {patch_fade_ms} is negative")
-        long_cfg, long_rate, long_feed = None, 22050, "recording"
+        long_cfg, long_rate, long_feed, long_clips16 = None, 22050, "recording", "resampled"
         if "long" in data:
             lm = data["long"] if data["long"] is not None else {}
             if not isinstance(lm, dict):
@@ -159,9 +161,18 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                                      f"contexts (only the context clips are cut from the file, at its own rate)")
                 if long_feed == "contexts" and long_rate != "file":
                     raise ValueError(f"{path}: long.feed = contexts needs `rate: file` (at rate: {long_rate} the recording is resampled as a whole)")
+            if "clips16" in lm:
+                long_clips16 = lm.pop("clips16")
+                if long_clips16 not in ("resampled", "file"):
+                    raise ValueError(f"{path}: long.clips16 = {long_clips16!r}: resampled (the default: the 16 kHz clips are the cut 22.05 kHz clips "
+                                     f"resampled) or file (they are cut straight from the file as well)")
+                if long_clips16 == "file" and long_feed != "contexts":
+                    raise ValueError(f"{path}: long.clips16 = file needs `feed: contexts` (with feed: {long_feed} the clips are slices of the "
+                                     f"resampled recording)")
             for key, val in lm.items():
                 if key not in long_cfg:
-                    raise ValueError(f"{path}: unknown key `{key}` in `long:` (it takes clip_s, context_s, batch, rate, feed)")
+                    raise ValueError(f"{path}: unknown key `{key}` in `long:` (it takes clip_s, context_s, batch, rate, feed) and, with feed: "
+                                     f"contexts, clips16")
                 long_cfg[key] = int(val) if key == "batch" else float(val)
                 if long_cfg[key] < 0:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
@@ -230,7 +241,8 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_type=str(data["hubert_model"]["type"]),
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
-            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, detect=detect_cfg,
+            raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, long_clips16=long_clips16,
+            detect=detect_cfg,
             detect_channels=detect_channels, detect_dead=detect_dead, detect_level=detect_level)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None

@@ -1832,6 +1832,83 @@ int si_cut_rate_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int cha
     return cut_rate_call(ctx, "si_cut_rate_ch", true, x, is_pcm16, n_file, channels, channel, sr, host_start, start, C, L, filt, out, stream);
 }
 
+// ---- both clip sets of a pass cut straight from the file
+// One rate's tables of a pair call: the checks cut_rate_call puts to its filter, under the argument's own name.
+static int pair_filter(si_ctx* ctx, const char* fn, const char* arg, const si_sinc_filter* f, int target, int sr, SiPairRate* r) {
+    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return SI_FAIL_FN("%s: si_sinc_filter size mismatch", arg);
+    if (!f->win || !f->dwin || f->nwin < 2 || f->num_table < 1 || f->step < 1 || !(f->scale > 0.0 && f->scale <= 1.0))
+        return SI_FAIL_FN("%s: bad filter table (nwin %d, num_table %d, step %d, scale %g)", arg, f->nwin, f->num_table, f->step, f->scale);
+    long ga = target, gb = sr;
+    while (gb) { const long t = ga % gb; ga = gb; gb = t; }
+    const long H = ((long)f->nwin + f->step - 1) / f->step;
+    if (H > 16384) return SI_FAIL_FN("%s: bad filter table: %ld taps per wing at %d Hz, no tile's staged samples fit 64 KB", arg, H, sr);
+    *r = SiPairRate{f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)(target / ga), (int)(sr / ga), (int)H};
+    return SI_OK;
+}
+
+static int cut_pair_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr,
+                         const int32_t* host_frame, const int32_t* frame, int C, int L22, int L16, const si_sinc_filter* filt22,
+                         const si_sinc_filter* filt16, float* out22, float* out16, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (inter && si_check_channels(ctx, fn, channels, channel, 0) != SI_OK) return SI_EINVAL;
+    if (sr < 4000 || sr > 192000) return SI_FAIL_FN("sr = %d Hz, outside 4000 .. 192000", sr);
+    if (sr == 22050) return SI_FAIL_FN("sr = 22050 Hz is the model's own rate: that file is si_cut_clips'");
+    if (n_file < 1) return SI_FAIL_FN("n_file = %d", n_file);
+    if ((long)n_file > SI_MAX_REC) return SI_FAIL_FN("n_file = %d samples, at most %ld", n_file, SI_MAX_REC);
+    SiPair pr{};
+    if (pair_filter(ctx, fn, "filt22", filt22, 22050, sr, &pr.r22) != SI_OK) return SI_EINVAL;
+    const long P = pr.r22.P, Qr = pr.r22.Q;
+    const long N22 = ((long)n_file * P + Qr - 1) / Qr;              // the recording's samples on the 22.05 kHz axis, ceil(n_file P / Q)
+    if (N22 > SI_MAX_REC) return SI_FAIL_FN("n_file = %d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
+    if (sr == 16000) {
+        if (filt16) return SI_FAIL_FN("filt16 is not NULL at sr = 16000 Hz: the 16 kHz clips are the file's own samples, no filter is applied");
+        pr.r16 = SiPairRate{nullptr, nullptr, 0, 1, 1, 1.0, 1, 1, 0};
+        pr.direct16 = 1;
+    } else {
+        if (!filt16) return SI_FAIL_FN("filt16 is NULL at sr = %d Hz: only a 16000 Hz file goes without the 16 kHz filter", sr);
+        if (pair_filter(ctx, fn, "filt16", filt16, 16000, sr, &pr.r16) != SI_OK) return SI_EINVAL;
+    }
+    const long N16 = ((long)n_file * pr.r16.P + pr.r16.Q - 1) / pr.r16.Q;      // ceil(n_file P16 / Q16) <= lim16 <= N16 + 1
+    const long lim16 = (N22 * 320 + 440) / 441;
+    const long H = std::max(pr.r22.H, pr.r16.H);
+    const long cap = ((long)RF_PAIR_FRAMES * sr + 49) / 50 + 2 + 2 * H;         // file samples one tile stages in LDS: 5 404 at 192 kHz with kaiser_best
+    if (cap * (long)sizeof(float) > 65536)
+        return SI_FAIL_FN("%s: bad filter table: %ld taps per wing at %d Hz need %ld staged samples per tile, at most 16384",
+                          pr.r22.H >= pr.r16.H ? "filt22" : "filt16", H, sr, cap);
+    if (C < 0 || C > 65535) return SI_FAIL_FN("C = %d clips in one call, 0 .. 65535 (the launch grid's second dimension)", C);
+    if (L22 < 1) return SI_FAIL_FN("L22 = %d", L22);
+    if (L16 < 1) return SI_FAIL_FN("L16 = %d", L16);
+    if (C == 0) return SI_OK;                                       // nothing is read or written
+    if (!x || !out22 || !out16 || !host_frame || !frame)
+        return SI_FAIL_FN("%s is NULL", !x ? "x" : !out22 ? "out22" : !out16 ? "out16" : !host_frame ? "host_frame" : "frame");
+    for (int c = 0; c < C; ++c) {
+        const long f = host_frame[c];
+        if (f < 0 || 441 * f + L22 > N22)
+            return SI_FAIL_FN("frame[%d] = %ld: clip = 22.05 kHz samples [%ld, %ld) is outside the recording's %ld samples", c, f, 441 * f,
+                              441 * f + L22, N22);
+        if (320 * f + L16 > lim16)
+            return SI_FAIL_FN("frame[%d] = %ld: clip = 16 kHz samples [%ld, %ld) ends past ceil(N22 320 / 441) = %ld (N22 = %ld)", c, f, 320 * f,
+                              320 * f + L16, lim16, N22);
+    }
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    pr.cap = (int)cap, pr.N22 = (int)N22, pr.N16 = (int)N16, pr.lim16 = (int)lim16;
+    return si_launch_cut_pair(ctx, x, is_pcm16 != 0, n_file, inter ? channels : 0, inter ? channel : 0, frame, C, L22, L16, pr, out22, out16,
+                              static_cast<hipStream_t>(stream));
+}
+
+int si_cut_pair(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_frame, const int32_t* frame, int C, int L22,
+                int L16, const si_sinc_filter* filt22, const si_sinc_filter* filt16, float* out22, float* out16, si_stream_t stream) {
+    return cut_pair_call(ctx, "si_cut_pair", false, x, is_pcm16, n_file, 0, 0, sr, host_frame, frame, C, L22, L16, filt22, filt16, out22, out16,
+                         stream);
+}
+
+int si_cut_pair_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr, const int32_t* host_frame,
+                   const int32_t* frame, int C, int L22, int L16, const si_sinc_filter* filt22, const si_sinc_filter* filt16, float* out22,
+                   float* out16, si_stream_t stream) {
+    return cut_pair_call(ctx, "si_cut_pair_ch", true, x, is_pcm16, n_file, channels, channel, sr, host_frame, frame, C, L22, L16, filt22, filt16,
+                         out22, out16, stream);
+}
+
 // ---- dropout detection
 // The detector's scratch for n samples: the context's own, grown on demand (a context is single-threaded and its calls stream-ordered by contract).
 static int det_scratch_reserve(si_ctx* ctx, int n, si_stream_t stream) {

@@ -406,6 +406,24 @@ int si_launch_cut_rate(si_ctx* ctx, const void* x, bool pcm16, int n_file, const
 int si_launch_cut_rate_ch(si_ctx* ctx, const void* x, bool pcm16, int n_file, int ch, int channel, const int32_t* start, int C, int L,
                           const SiFeed& fd, float* out, hipStream_t st);
 
+// both clip sets of a pass from one staged tile (rate_feed_kernels.hip)
+constexpr int RF_PAIR_FRAMES = SI_CUT_PAIR_FRAMES;      // consecutive 20 ms frames of one clip per workgroup (si_hip.h; native.CUT_PAIR_FRAMES)
+// one rate's kaiser_best tables, sr -> 22 050 or sr -> 16 000: P / Q = (target, sr) / gcd, H = ceil(nwin / step) taps per wing
+struct SiPairRate {
+    const double* win; const double* dwin; int nwin, num_table, step; double scale;
+    int P, Q, H;
+};
+// cap = ceil(RF_PAIR_FRAMES sr / 50) + 2 + 2 max(H22, H16): the floats of dynamic LDS; N22 = ceil(n_file P22 / Q22), N16 = ceil(n_file
+// P16 / Q16), lim16 = ceil(N22 320 / 441): where a clip's 16 kHz row may end; direct16: sr = 16000, r16 holds no tables (H = 0, P = Q = 1)
+struct SiPair {
+    SiPairRate r22, r16;
+    int cap, N22, N16, lim16, direct16;
+};
+// out22 (C, L22) row c = 22.05 kHz samples 441 frame[c] + [0, L22), out16 (C, L16) row c = 16 kHz samples 320 frame[c] + [0, L16) of the
+// file x; ch = 0: a mono file (the mono kernel), else channel `channel` of ch interleaved; arguments validated by the caller
+int si_launch_cut_pair(si_ctx* ctx, const void* x, bool pcm16, int n_file, int ch, int channel, const int32_t* frame, int C, int L22, int L16,
+                       const SiPair& pr, float* out22, float* out16, hipStream_t st);
+
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16
 // rounding every consumer of these outputs applies; 15 VALU operations instead of libm erff's ~31 with two divergent branches.

@@ -3,6 +3,8 @@
 //                                      staged in LDS as fp32, then per output the two wings of the band-limited interpolation at the
 //                                      exact rational time j Q / P
 //   cut_rate_ch_kernel<float | int16_t>  the same tile read from one channel of an INTERLEAVED file: one shared body
+//   cut_pair_kernel, cut_pair_ch_kernel  per 20 ms frame of one clip, its 22.05 kHz AND its 16 kHz samples from one staged range (DESIGN.md
+//                                      4.26; further down, with its own description)
 // It stands where `resample(file, sr, 22050)` over the whole recording + si_cut_clips would: that pass costs every 22.05 kHz sample of
 // the recording a 2 H-tap float64 sum, an fp32 copy of an int16 file, a 22.05 kHz copy of the recording and a float64 time table of its
 // length; this one computes the samples of the context clips and creates nothing of the recording's length.
@@ -93,6 +95,139 @@ template <typename T>
 __global__ __launch_bounds__(256) void cut_rate_ch_kernel(const T* __restrict__ x, int n_file, int ch, int channel, const int32_t* __restrict__ start,
                                                           int L, SiFeed fd, float* __restrict__ out) {
     rf_cut_tile(x, n_file, ch, channel, start, L, fd, out);
+}
+
+// ---- both clip sets of a pass from one staged tile
+//   cut_pair_kernel<float | int16_t>     per RF_PAIR_FRAMES consecutive 20 ms frames of one clip: the file samples that BOTH rates read for
+//                                        them staged once in LDS as fp32, then the frames' 441 F outputs at 22.05 kHz and 320 F at 16 kHz
+//   cut_pair_ch_kernel<float | int16_t>  the same tile read from one channel of an INTERLEAVED file: one shared body, rf_pair_tile
+// grid (max(ceil(L22 / 441 F), ceil(L16 / 320 F)), C), 256 threads, pr.cap floats of dynamic LDS.  Workgroup (tile, c) owns frames
+// f0 + [0, F), f0 = frame[c] + tile F (workgroup-uniform): 22.05 kHz samples 441 f0 + [0, cnt22) and 16 kHz samples 320 f0 + [0, cnt16).
+//   stage   both rows start at the SAME file position f0 sr / 50 (441 f0 Q22 / P22 = 320 f0 Q16 / P16), so n0 = floor of it is shared;
+//           n1 = the larger last integer part of the two; file samples [n0 - H, n1 + H], H = max(H22, H16), by cut_rate's staging loop
+//           (lane t on element t, one element wide, int16 converted on the way in, zero outside [0, n_file), the sample TIME clamped
+//           before the 64-bit element offset of an interleaved file is formed).  Every output's time lies in [f0, f0 + F) / 50 s, so
+//           n1 - n0 <= ceil(F sr / 50) and the range holds at most ceil(F sr / 50) + 1 + 2 H <= cap samples.
+//   sample  one index space over the tile's cnt22 + cnt16 outputs, lane t on t, t + 256, ...: rf_wings is rf_cut_tile's per-output
+//           arithmetic, statement for statement, on the tables of the output's rate -- a 22.05 kHz output has si_cut_rate's bits.  A
+//           16 kHz output with j >= N16 (at or past the file's end: at most the one the L16 rule allows) is +0.0; at sr = 16000 the
+//           output is the staged sample itself, n = j, no table read.  Neighbouring lanes read LDS words Q / P apart, as in cut_rate:
+//           an even integer stride (32 kHz: 2, 192 kHz: 12) costs ds_read_b32 a 2- or 4-way bank conflict, under two float64 fma and
+//           two float64 table loads per tap.
+// Plain stores, no atomics; each output is written once.  A device frame table that differs from the validated host copy: a tile whose
+// outputs leave [0, N22) / [0, lim16) is written as zero, and the staging loop reads the file only inside [0, n_file).
+__device__ __forceinline__ float rf_wings(const float* __restrict__ row, long base, long j, int n_file, const SiPairRate& r) {
+    const long P = r.P, Q = r.Q;
+    const int nwin = r.nwin, step = r.step;
+    const double scale = r.scale, ntab = (double)r.num_table;
+    const long t = j * Q;
+    const long nl = t / P;
+    const int n = (int)nl;
+    const double frac = scale * ((double)(t - nl * P) / (double)P);
+    double acc = 0.0;
+    {
+        const double idx = frac * ntab;
+        const int off = (int)idx;
+        const double eta = idx - (double)off;
+        const int taps = min(n + 1, (nwin - off) / step);
+        const float* xs = row + (nl - base);
+        for (int k = 0; k < taps; ++k) {
+            const int i = off + k * step;
+            acc = fma(fma(eta, r.dwin[i], r.win[i]), (double)xs[-k], acc);
+        }
+    }
+    {
+        const double idx = (scale - frac) * ntab;
+        const int off = (int)idx;
+        const double eta = idx - (double)off;
+        const int taps = min(n_file - n - 1, (nwin - off) / step);
+        const float* xs = row + (nl + 1 - base);
+        for (int k = 0; k < taps; ++k) {
+            const int i = off + k * step;
+            acc = fma(fma(eta, r.dwin[i], r.win[i]), (double)xs[k], acc);
+        }
+    }
+    return (float)acc;
+}
+
+template <typename T>
+__device__ __forceinline__ void rf_pair_tile(const T* __restrict__ x, int n_file, int ch, int channel, const int32_t* __restrict__ frame, int L22,
+                                             int L16, const SiPair& pr, float* __restrict__ out22, float* __restrict__ out16) {
+    extern __shared__ __attribute__((aligned(16))) float rf_pair_row[];
+    constexpr int T22 = 441 * RF_PAIR_FRAMES, T16 = 320 * RF_PAIR_FRAMES;
+    const int c = blockIdx.y, o22 = blockIdx.x * T22, o16 = blockIdx.x * T16;
+    const int cnt22 = max(0, min(T22, L22 - o22)), cnt16 = max(0, min(T16, L16 - o16));
+    const long fc = frame[c];
+    const long f0 = fc + (long)blockIdx.x * RF_PAIR_FRAMES;
+    const long j22 = 441 * f0, j16 = 320 * f0;
+    const bool live22 = fc >= 0 && cnt22 > 0 && j22 + cnt22 <= (long)pr.N22;        // uniform
+    const bool live16 = fc >= 0 && cnt16 > 0 && j16 + cnt16 <= (long)pr.lim16;      // uniform
+    const int H = max(pr.r22.H, pr.r16.H);
+    const long n0 = j22 * pr.r22.Q / pr.r22.P;                                      // = floor(j16 Q16 / P16): the frame's own file position
+    long n1 = n0;
+    if (live22) n1 = max(n1, (j22 + cnt22 - 1) * pr.r22.Q / pr.r22.P);
+    if (live16) n1 = max(n1, (j16 + cnt16 - 1) * pr.r16.Q / pr.r16.P);
+    const long base = (live22 || live16) ? n0 - H : 0;
+    const int span = (live22 || live16) ? (int)min(n1 + H + 1 - base, (long)pr.cap) : 0;
+    for (int p = threadIdx.x; p < span; p += 256) {
+        const long i = base + p;
+        rf_pair_row[p] = (i >= 0 && i < (long)n_file) ? rf_load(x + ((size_t)i * ch + channel)) : 0.f;
+    }
+    __syncthreads();
+    float* row22 = out22 + (size_t)c * L22 + o22;
+    float* row16 = out16 + (size_t)c * L16 + o16;
+    for (int m = threadIdx.x; m < cnt22 + cnt16; m += 256) {
+        if (m < cnt22) {
+            row22[m] = live22 ? rf_wings(rf_pair_row, base, j22 + m, n_file, pr.r22) : 0.f;
+            continue;
+        }
+        const int m16 = m - cnt22;
+        const long j = j16 + m16;
+        float y = 0.f;
+        if (live16 && j < (long)pr.N16) y = pr.direct16 ? rf_pair_row[j - base] : rf_wings(rf_pair_row, base, j, n_file, pr.r16);
+        row16[m16] = y;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cut_pair_kernel(const T* __restrict__ x, int n_file, const int32_t* __restrict__ frame, int L22, int L16,
+                                                       SiPair pr, float* __restrict__ out22, float* __restrict__ out16) {
+    rf_pair_tile(x, n_file, 1, 0, frame, L22, L16, pr, out22, out16);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cut_pair_ch_kernel(const T* __restrict__ x, int n_file, int ch, int channel, const int32_t* __restrict__ frame,
+                                                          int L22, int L16, SiPair pr, float* __restrict__ out22, float* __restrict__ out16) {
+    rf_pair_tile(x, n_file, ch, channel, frame, L22, L16, pr, out22, out16);
+}
+
+// The caller (si_cut_pair[_ch]) checked every argument, pr.cap * 4 <= 64 KB and C <= 65535 among them.  ch = 0: the mono kernel.  The
+// launches are profiled under cut_rate's names: the same family, and like it they hold no scratch of the context's.
+int si_launch_cut_pair(si_ctx* ctx, const void* x, bool pcm16, int n_file, int ch, int channel, const int32_t* frame, int C, int L22, int L16,
+                       const SiPair& pr, float* out22, float* out16, hipStream_t st) {
+    if (C <= 0 || L22 <= 0 || L16 <= 0) return SI_OK;
+    constexpr int T22 = 441 * RF_PAIR_FRAMES, T16 = 320 * RF_PAIR_FRAMES;
+    const size_t lds = (size_t)pr.cap * sizeof(float);
+    const dim3 grid(std::max((L22 + T22 - 1) / T22, (L16 + T16 - 1) / T16), C);
+    const double o22 = (double)C * L22, o16 = (double)C * L16;
+    const double flops = o22 * 8.0 * pr.r22.H + o16 * 8.0 * pr.r16.H;
+    const double bytes = (o22 + o16) * 4.0 + (double)grid.x * C * pr.cap * (pcm16 ? 2.0 : 4.0);
+    if (ch > 0) {
+        si_prof_begin(ctx, "cut_rate_ch", flops, bytes, st);
+        if (pcm16)
+            cut_pair_ch_kernel<int16_t><<<grid, 256, lds, st>>>(static_cast<const int16_t*>(x), n_file, ch, channel, frame, L22, L16, pr, out22, out16);
+        else
+            cut_pair_ch_kernel<float><<<grid, 256, lds, st>>>(static_cast<const float*>(x), n_file, ch, channel, frame, L22, L16, pr, out22, out16);
+    } else {
+        si_prof_begin(ctx, "cut_rate", flops, bytes, st);
+        if (pcm16)
+            cut_pair_kernel<int16_t><<<grid, 256, lds, st>>>(static_cast<const int16_t*>(x), n_file, frame, L22, L16, pr, out22, out16);
+        else
+            cut_pair_kernel<float><<<grid, 256, lds, st>>>(static_cast<const float*>(x), n_file, frame, L22, L16, pr, out22, out16);
+    }
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
 }
 
 // The caller (si_cut_rate) checked every argument, fd.cap * 4 <= 64 KB and C <= 65535 among them.

@@ -616,7 +616,7 @@ class InpaintingEngine:
         return out
 
     def _recording_passes(self, N22: int, cut, wave16: Optional[torch.Tensor], gaps, fade_frames: int, clip_frames: int,
-                          min_context: int, batch: int, write, channel_gaps=None) -> Dict[str, object]:
+                          min_context: int, batch: int, write, channel_gaps=None, cut16=None) -> Dict[str, object]:
         """What patch_recording and patch_file share: the context plan of a recording of N22 samples at 22.05 kHz and, per batch of
         at most `batch` contexts, the cut -- cut(cb, L22) -> the (B, L22) clips of the contexts cb, which start at 22.05 kHz samples
         441 * start, on the device --, the one multi-gap pass with every gap the clips hold masked, and the labels of the own gaps.
@@ -625,7 +625,9 @@ class InpaintingEngine:
         samples.  -> contexts, labels, label_off.
         channel_gaps: one gap list per channel of an interleaved file in place of `gaps`.  Every channel is planned
         as a recording of its own (gaps.plan_channel_contexts), the contexts follow in (channel, start) order with a "channel" key, the
-        batches fill across channels, and labels / label_off run over the gaps in (channel, gap) order; + channel_off."""
+        batches fill across channels, and labels / label_off run over the gaps in (channel, gap) order; + channel_off.
+        cut16: cut16(cb, L22, L16) -> (the (B, L22) clips, the (B, L16) clips at 16 kHz, which start at samples 320 *
+        start), both from the cutter, in place of `cut` and of the resampling of its clips; wave16 is None then."""
         N22, clip_frames, batch = int(N22), int(clip_frames), int(batch)
         n_rec = N22 // 441
         whole = n_rec <= clip_frames                                   # one context: the whole recording, with its true sample counts
@@ -647,8 +649,11 @@ class InpaintingEngine:
         for i in range(0, len(ctxs), batch):
             cb = ctxs[i:i + batch]
             B = len(cb)
-            w22 = cut(cb, L22)
-            w16 = self.resample(w22, 22050, 16000) if wave16 is None else self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16)
+            if cut16 is not None:
+                w22, w16 = cut16(cb, L22, L16)
+            else:
+                w22 = cut(cb, L22)
+                w16 = self.resample(w22, 22050, 16000) if wave16 is None else self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16)
             tb = self.gap_tables([c["own"] + c["foreign"] for c in cb], [L16] * B, [L22] * B)
             res = self.predict_multigap_batch(w16, w22, None, tables=tb, vocode=False)
             write(cb, tb, res, w22, L22)
@@ -709,13 +714,18 @@ class InpaintingEngine:
         plan["rows"] = [(b, 441 * int(ctxs[b]["start"]) + w0 * hop, (w1 - w0) * hop, lim22[b]) for b, w0, w1 in plan["wins"]]
         return plan
 
+    def _feed_filter16(self, sr: int) -> Optional[Dict[str, object]]:
+        """audio.design_kaiser_best(sr, 16000, .) with win / dwin on the device: what si_cut_pair takes for its 16 kHz rows (DESIGN.md
+        4.26) -- the tables resample(., sr, 16000) runs on, from the same cache.  None for a 16 kHz file: its samples are the rows."""
+        return None if int(sr) == 16000 else self._sinc_tables(sr, 16000)
+
     def _feed_filter(self, sr: int) -> Dict[str, object]:
         """audio.design_kaiser_best(sr, 22050, .) with win / dwin on the device (time_reg is not used): what si_cut_rate takes -- the
         tables resample(., sr, 22050) runs on, held once."""
         return self._sinc_tables(sr, 22050)
 
     def patch_file(self, x, sr: int, gaps=None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
-                   return_windows: bool = False, feed: str = "recording", channel_gaps=None) -> Dict[str, object]:
+                   return_windows: bool = False, feed: str = "recording", channel_gaps=None, clips16: str = "resampled") -> Dict[str, object]:
         """patch_recording for a file at ITS OWN sample rate and in its own sample type: x (n,) is the recording at `sr` Hz, fp32 in
         full-scale units or int16 PCM (tensor or array, host or device), gaps = (first frame, frame count) pairs on its 20 ms grid.
         The recording is resampled to 22.05 kHz here (`resample`) only to FEED the model; the contexts, the multi-gap passes and the
@@ -739,10 +749,18 @@ class InpaintingEngine:
         "channel" key in (channel, start) order, labels / label_off over the gaps in (channel, gap) order, channel_off (ch + 1): the
         gaps of channel c are [channel_off[c], channel_off[c + 1]); with return_windows a pass holds tables ((channel, RateTable)
         pairs) in place of table.  (n, 1) is the mono route with patched reshaped.  A file at sr = 22050 goes channel by channel
-        through patch_recording, as the mono file does: feed and return_windows are not read there and no `passes` come back."""
+        through patch_recording, as the mono file does: feed and return_windows are not read there and no `passes` come back.
+        clips16: "resampled" (the default) makes the encoder's 16 kHz clips from the cut 22.05 kHz clips, each clip
+        resampled as a file of its own; "file" (needs feed="contexts") cuts them straight from x as well, at the exact 16 kHz times with
+        the file's real neighbours at the clip edges, as the reference's second load of the file does (I_ea/predict.py:80): one
+        si_cut_pair launch per pass -- si_cut_pair_ch per channel present in a pass -- yields both clip sets, the 22.05 kHz ones with
+        si_cut_rate's bytes, and no resample_sinc runs.  A 16 kHz file's own samples reach the encoder.  return_windows then adds clips16
+        per pass.  At sr = 22050 it is not read, as feed is not."""
         self._need(head=True, codebook=True, what="patch_file")
         if feed not in ("recording", "contexts"):
             raise ValueError(f"patch_file: feed = {feed!r}: 'recording' or 'contexts'")
+        if clips16 not in ("resampled", "file"):
+            raise ValueError(f"patch_file: clips16 = {clips16!r}: 'resampled' or 'file'")
         sr, batch = int(sr), int(batch)
         P, Q = G.rate_ratio(sr)
         if batch <= 0:
@@ -752,7 +770,8 @@ class InpaintingEngine:
             raise ValueError("patch_file: both gaps and channel_gaps: one list for every channel, or one list per channel")
         if x.dim() == 2:
             per = G.channel_gap_lists(gaps, channel_gaps, x.shape[1])
-            kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed)
+            kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed,
+                      clips16=clips16)
             if x.shape[1] == 1:
                 out = self.patch_file(x.reshape(-1), sr, per[0], **kw)
                 out["patched"] = out["patched"].reshape(-1, 1)
@@ -772,6 +791,8 @@ class InpaintingEngine:
             if pcm:
                 out["patched"] = out.pop("patched_pcm")
             return out
+        if clips16 == "file" and feed != "contexts":
+            raise ValueError(f"patch_file: clips16 = 'file' needs feed = 'contexts' (with feed = {feed!r} the clips are slices of the resampled recording)")
         patched = x.clone()
         out: Dict[str, object] = {"patched": patched}
         passes = []
@@ -790,6 +811,13 @@ class InpaintingEngine:
             wave22 = self.resample(xf[None], sr, 22050)[0].contiguous()
             N22 = wave22.numel()
             cut = lambda cb, L: self.ctx.cut_clips(wave22, [441 * c["start"] for c in cb], L)
+        cut16, last16 = None, {}
+        if clips16 == "file":                                          # both clip sets of a pass from x itself, in one launch
+            fin16 = self._feed_filter16(sr)
+
+            def cut16(cb, L22, L16):
+                w22, last16["w16"] = self.ctx.cut_pair(x, sr, [c["start"] for c in cb], L22, L16, fin, fin16)
+                return w22, last16["w16"]
         filt = self._rate_filter(sr)
 
         def write(cb, tb, res, w22, L22):
@@ -802,16 +830,16 @@ class InpaintingEngine:
                 table = RateTable(plan["spans"], plan["rows"], G.region_chunks(plan["regions"]), len(cb), fade_f, self.device)
                 self.ctx.patch_rate(x, sr, table, gen, filt, patched, gain)
                 if return_windows:
-                    passes.append({"contexts": cb, "gen": gen, "gain": gain, "table": table, "plan": plan, "clips22": w22})
+                    passes.append({"contexts": cb, "gen": gen, "gain": gain, "table": table, "plan": plan, "clips22": w22, **({"clips16": last16["w16"]} if last16 else {})})
 
         fade_frames = max(-(-fade_f * 50 // sr), 1)
-        out.update(self._recording_passes(N22, cut, None, gaps, fade_frames, clip_frames, min_context, batch, write))
+        out.update(self._recording_passes(N22, cut, None, gaps, fade_frames, clip_frames, min_context, batch, write, cut16=cut16))
         if return_windows:
             out["passes"] = passes
         return out
 
     def _patch_file_channels(self, x: torch.Tensor, sr: int, channel_gaps, fade_ms: float, clip_frames: int, min_context: int, batch: int,
-                             return_windows: bool, feed: str) -> Dict[str, object]:
+                             return_windows: bool, feed: str, clips16: str = "resampled") -> Dict[str, object]:
         """patch_file for an interleaved file x (n, ch >= 2) with one gap list per channel."""
         n_file, ch = x.shape
         if ch > G.MAX_CHANNELS:
@@ -834,6 +862,8 @@ class InpaintingEngine:
                 label_off += [label_off[-1] + v for v in o["label_off"][1:]]
             return {"patched": torch.stack([o["patched"] for o in outs], dim=1), "contexts": ctxs, "labels": torch.cat([o["labels"] for o in outs]),
                     "label_off": label_off, "channel_off": off}
+        if clips16 == "file" and feed != "contexts":
+            raise ValueError(f"patch_file: clips16 = 'file' needs feed = 'contexts' (with feed = {feed!r} the clips are slices of the resampled recording)")
         patched = x.clone()
         out: Dict[str, object] = {"patched": patched}
         passes = []
@@ -855,6 +885,16 @@ class InpaintingEngine:
                     wave22[c] = self.resample(xf[None], sr, 22050)[0].contiguous()   # row by row: the mono call's own launch
             N22 = next(iter(wave22.values())).numel()
             cut_rows = lambda c, starts, L, rows: self.ctx.cut_clips(wave22[c], starts, L, out=rows)
+        cut16, last16 = None, {}
+        if clips16 == "file":                                          # both clip sets of a pass, channel c in place: one launch per channel
+            fin16 = self._feed_filter16(sr)
+
+            def cut16(cb, L22, L16):
+                w22 = torch.empty(len(cb), L22, dtype=torch.float32, device=self.device)
+                last16["w16"] = w16 = torch.empty(len(cb), L16, dtype=torch.float32, device=self.device)
+                for c, r0, r1 in G.pass_channels(cb):
+                    self.ctx.cut_pair(x, sr, [k["start"] for k in cb[r0:r1]], L22, L16, fin, fin16, out22=w22[r0:r1], out16=w16[r0:r1], channel=c)
+                return w22, w16
         filt = self._rate_filter(sr)
 
         def cut(cb, L):
@@ -880,10 +920,11 @@ class InpaintingEngine:
                     self.ctx.patch_rate(x, sr, table, gen, filt, patched, gain, channel=c)
                     tables.append((c, table))
                 if return_windows:
-                    passes.append({"contexts": cb, "gen": gen, "gain": gain, "tables": tables, "plan": plan, "clips22": w22})
+                    passes.append({"contexts": cb, "gen": gen, "gain": gain, "tables": tables, "plan": plan, "clips22": w22, **({"clips16": last16["w16"]} if last16 else {})})
 
         fade_frames = max(-(-fade_f * 50 // sr), 1)
-        out.update(self._recording_passes(N22, cut, None, None, fade_frames, clip_frames, min_context, batch, write, channel_gaps=channel_gaps))
+        out.update(self._recording_passes(N22, cut, None, None, fade_frames, clip_frames, min_context, batch, write, channel_gaps=channel_gaps,
+                                          cut16=cut16))
         if return_windows:
             out["passes"] = passes
         return out
@@ -891,12 +932,13 @@ class InpaintingEngine:
     def conceal_file(self, x, sr: int, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
                      merge_frames: Optional[int] = None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
                      return_windows: bool = False, feed: str = "recording", detect: str = "each", kind: str = "quiet",
-                     rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = 2.0) -> Dict[str, object]:
+                     rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = 2.0, clips16: str = "resampled") -> Dict[str, object]:
         """File in, repaired file out, at the file's own rate and in its own sample type: find_gaps on x itself, where a dropout is
         still exact zeros, then patch_file with the gaps it found.  The usable frames are those of the recording's 22.05 kHz length
         ceil(n * 22050 / sr) (`recording_frames`), and a gap longer than the planner's budget counts as long, as in conceal_recording.
         threshold is in x's own units, as find_gaps takes it: full scale for fp32, int16 steps for an int16 file.
-        feed: patch_file's ("recording" or "contexts").
+        feed: patch_file's ("recording" or "contexts").  clips16: patch_file's ("resampled" or "file"), passed on when
+        it is off its default.
         -> patch_file's dictionary + gaps + skipped.  With nothing found: an exact copy; only the detection kernels launched.
         An interleaved file x (n, ch >= 2): detect="each" runs the detection once per channel and repairs a dropout
         in the channel it is in (gaps, skipped: one list per channel); detect="joint" runs it once over the sample times at which
@@ -922,6 +964,8 @@ class InpaintingEngine:
         find = lambda c: self.find_gaps(x, sr, threshold, min_ms, max_ms, pad_frames, merge_frames, fade22, n_rec, lim, channel=c, kind=kind,
                                         rel_threshold=rel_threshold, held_tol=held_tol, **({"win_ms": win_ms} if kind == "level" else {}))
         kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed)
+        if clips16 != "resampled":                                     # the default: patch_file is called as it was
+            kw["clips16"] = clips16
         if many and detect == "each":
             found = [find(c) for c in range(shape[1])]
             out = self.patch_file(x, sr, channel_gaps=[f["gaps"] for f in found], **kw)

@@ -425,6 +425,15 @@ def rate_ratio(sr: int) -> Tuple[int, int]:
     return 22050 // g, sr // g
 
 
+def rate_ratio16(sr: int) -> Tuple[int, int]:
+    """(P16, Q16) = (16000, sr) / gcd: sample j of the recording's 16 kHz axis sits at file position j * Q16 / P16, and
+    a file of n samples has ceil(n * P16 / Q16) samples on that axis.  (1, 1) for a 16 kHz file.  rate_ratio's ValueError."""
+    sr = int(sr)
+    rate_ratio(sr)
+    g = math.gcd(16000, sr)
+    return 16000 // g, sr // g
+
+
 def file_fade(fade_ms: float, sr: int) -> int:
     """The cross-fade length in file samples: round(fade_ms * sr / 1000), Python's round (5 ms: 240 at 48 kHz, 220 at 44.1 kHz, 110 at
     22.05 kHz as config.patch_fade gives)."""

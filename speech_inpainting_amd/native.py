@@ -31,13 +31,20 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
            "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
            "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate",
-           "si_quiet_runs_ch", "si_cut_rate_ch", "si_patch_rate_ch", "si_dead_runs", "si_level_runs",
+           "si_quiet_runs_ch", "si_cut_rate_ch", "si_patch_rate_ch", "si_dead_runs", "si_level_runs", "si_cut_pair", "si_cut_pair_ch",
            "si_plan_weights", "si_pack_weights_host"]
 SI_MAX_SPANS = 16
 SI_MAX_CHANNELS = 8                        # channels of an interleaved file
 DEAD_QUIET, DEAD_HELD = 1, 2               # SI_DEAD_QUIET, SI_DEAD_HELD: the `kind` bits of si_dead_runs
 LEVEL_MAX_HALF = 1024                      # SI_LEVEL_MAX_HALF: the largest half window of si_level_runs
 CUT_RATE_TILE = 512                        # SI_CUT_RATE_TILE: consecutive outputs of one clip per workgroup of si_cut_rate
+CUT_PAIR_FRAMES = 1                        # SI_CUT_PAIR_FRAMES: consecutive 20 ms frames of one clip per workgroup of si_cut_pair
+
+
+def cut_pair_lds_floats(sr: int, reach22: int, reach16: int) -> int:
+    """The floats of LDS one workgroup of si_cut_pair stages at `sr` Hz: ceil(CUT_PAIR_FRAMES sr / 50) + 2 + 2 max(H22, H16), H = taps per
+    wing of the two filters (H16 = 0 at 16 kHz, which has none).  The call refuses above 16384 (64 KB)."""
+    return -(-CUT_PAIR_FRAMES * int(sr) // 50) + 2 + 2 * max(int(reach22), int(reach16))
 
 
 class _F0EncStruct(C.Structure):
@@ -370,6 +377,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_patch_rate_ch.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(RateTableStruct), vp, i32, vp, C.POINTER(SincFilter), vp, vp]
     lib.si_dead_runs.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp]
     lib.si_level_runs.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp]
+    lib.si_cut_pair.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(SincFilter), C.POINTER(SincFilter), vp, vp, vp]
+    lib.si_cut_pair_ch.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(SincFilter), C.POINTER(SincFilter), vp, vp, vp]
     lib.si_plan_weights.argtypes = [C.POINTER(ModelDesc), C.POINTER(sz)]
     lib.si_pack_weights_host.argtypes = [C.POINTER(ModelDesc), vp, sz, C.c_char_p, vp, sz, C.POINTER(sz), C.c_char_p, sz]
     lib.si_num_frames.argtypes = [vp, i32]
@@ -760,6 +769,43 @@ class NativeContext:
         self._check(self.lib.si_cut_rate(self._h, _ptr(x), int(x.dtype == torch.int16), n_file, int(sr), host.ctypes.data_as(C.c_void_p),
                                          _ptr(dev), Cn, L, C.byref(f), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate")
         return out
+
+    # ---- both clip sets of a pass cut straight from the file, in one launch
+    def cut_pair(self, x: torch.Tensor, sr: int, frames, L22: int, L16: int, filt22: dict, filt16: Optional[dict],
+                 out22: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None, channel: Optional[int] = None):
+        """x (n_file,) at `sr` Hz, fp32 or int16, a device view that may start anywhere + frames (host ints, 20 ms frames) ->
+        (out22 (C, L22), out16 (C, L16)) fp32: row c = 22.05 kHz samples 441 frames[c] + [0, L22) -- si_cut_rate's bytes -- and 16 kHz
+        samples 320 frames[c] + [0, L16), interpolated at the exact time j * sr / 16000 straight from the file's samples, zero at and past
+        the recording's ceil(n_file * 16000 / sr) samples (si_cut_pair: one launch for both).  filt22 / filt16:
+        audio.design_kaiser_best(sr, 22050 / 16000, .) with win / dwin as float64 device tensors; at sr = 16000 filt16 is None and the
+        16 kHz rows are the file's own samples.  channel = c: x is (n_file, ch) interleaved (si_cut_pair_ch)."""
+        n_file, ch = self._interleaved(x, channel)
+        host = np.ascontiguousarray(np.asarray(list(frames), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        Cn, L22, L16 = host.size, int(L22), int(L16)
+        dev = torch.from_numpy(host).to(self.device, non_blocking=True) if Cn else None
+        outs = []
+        for out, L in ((out22, L22), (out16, L16)):
+            if out is None:
+                out = torch.empty(Cn, max(L, 0), dtype=torch.float32, device=self.device)
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * max(L, 0)
+            outs.append(out)
+        fs = []
+        for filt in (filt22, filt16):
+            if filt is None:
+                fs.append(None)
+                continue
+            win, dwin = filt["win"], filt["dwin"]
+            assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
+            assert win.numel() == dwin.numel()
+            fs.append(C.byref(SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
+                                         float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)))
+        tail = (host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L22, L16, fs[0], fs[1], C.c_void_p(outs[0].data_ptr()), C.c_void_p(outs[1].data_ptr()),
+                self._stream())
+        if channel is not None:
+            self._check(self.lib.si_cut_pair_ch(self._h, _ptr(x), int(x.dtype == torch.int16), n_file, ch, int(channel), int(sr), *tail), "si_cut_pair_ch")
+        else:
+            self._check(self.lib.si_cut_pair(self._h, _ptr(x), int(x.dtype == torch.int16), n_file, int(sr), *tail), "si_cut_pair")
+        return outs[0], outs[1]
 
     # ---- dropout detection (DESIGN.md 4.15)
     def quiet_runs(self, x: torch.Tensor, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536, runs: Optional[torch.Tensor] = None,

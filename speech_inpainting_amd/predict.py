@@ -26,6 +26,9 @@ on the way out: the three waves keep the file's own rate and sample type (an int
 own samples, bit for bit, outside the cross-fades (engine.patch_file).
 With `feed: contexts` beside `rate: file` the recording is not resampled as a whole on the way in either: only the context clips
 are cut from it, at its own rate and in its own sample type (si_cut_rate); `feed: recording` is the default.
+With `clips16: file` beside `feed: contexts` the encoder's 16 kHz clips are cut straight from the file too, in the same launch, instead
+of being resampled from the 22.05 kHz clips (si_cut_pair): a 16 kHz file's own samples reach the encoder; the key is
+printed, and recorded in gaps.json when `detect:` writes one.  `clips16: resampled` is the default.
 A multi-channel file of up to 8 channels is served with `rate: file, feed: contexts`: it stays interleaved, every
 channel is repaired as the mono recording it is to the model, and the three waves are written multi-channel; with `rate: file` and the
 default `feed: recording` it is refused, as it was (that feed would de-interleave it).  `mask:` / `masks:` apply to every
@@ -369,7 +372,7 @@ def _detect_gaps(cfg: PredictConfig, engine: InpaintingEngine, raw: np.ndarray, 
     for pos, lm, why in found["skipped"]:
         print(f"Skipped quiet run = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s: {why}")
     with open(os.path.join(save_dir, "gaps.json"), "w") as f:
-        json.dump({"gaps": [list(g) for g in found["gaps"]], "skipped": [list(g) for g in found["skipped"]], **report}, f)
+        json.dump({"gaps": [list(g) for g in found["gaps"]], "skipped": [list(g) for g in found["skipped"]], **report, **clips16_keywords(cfg)}, f)
     return found["gaps"]
 
 
@@ -400,6 +403,13 @@ def _dead_report(cfg: PredictConfig, found: dict, scale: float) -> dict:
     window = f", window win_ms = {level['win_ms']}" if level else ""
     print(f"Detection kind = {cfg.detect_dead['kind']}, effective threshold T = {T} ({unit}){window}")
     return {"kind": cfg.detect_dead["kind"], "T": T, **level}
+
+
+def clips16_keywords(cfg) -> dict:
+    """`long:`'s clips16 as patch_file and conceal_file take it: given off its default alone, so that every other run
+    calls them, and writes gaps.json, as before."""
+    clips16 = getattr(cfg, "long_clips16", "resampled")
+    return {} if clips16 == "resampled" else {"clips16": clips16}
 
 
 def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> int:
@@ -433,7 +443,9 @@ def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str)
         masked[s:s + l] = 0                                                        # the file samples whose time lies in the gap's frames
     audio.write_wav(os.path.join(save_dir, "masked.wav"), masked, sr_file)
     out = engine.patch_file(x, sr_file, gap_list, fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"],
-                            feed=cfg.long_feed)
+                            feed=cfg.long_feed, **clips16_keywords(cfg))
+    if clips16_keywords(cfg):
+        print(f"16 kHz clips: clips16 = {cfg.long_clips16} (cut straight from the file, with the 22.05 kHz clips)")
     labels, off = out["labels"].tolist(), out["label_off"]
     for k, (pos, lm) in enumerate(gap_list):
         print(f"Predicted codewords, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[k]:off[k + 1]])
@@ -465,7 +477,9 @@ def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_
     fade_ms = cfg.patch_fade_ms if cfg.patch_fade_ms is not None else 5.0
     clip_frames, min_context = int(round(cfg.long["clip_s"] * 50)), int(round(cfg.long["context_s"] * 50))
     dev = torch.from_numpy(x).to(engine.device)                                    # the one upload: detection and repair read it
-    kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"], feed=cfg.long_feed)
+    kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"], feed=cfg.long_feed, **clips16_keywords(cfg))
+    if clips16_keywords(cfg):
+        print(f"16 kHz clips: clips16 = {cfg.long_clips16} (cut straight from the file, with the 22.05 kHz clips)")
     if cfg.detect is not None:                                                     # conceal_file: its own budget for a gap, its own fade
         d = cfg.detect
         scale = 32768.0 if x.dtype == np.int16 else 1.0                             # an int16 file is scanned as the int16 it holds
@@ -482,7 +496,7 @@ def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_
                 print(f"Skipped quiet run of {who} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s: {why}")
         lists = lambda v: [list(g) for g in v] if joint else [[list(g) for g in one] for one in v]
         with open(os.path.join(save_dir, "gaps.json"), "w") as f:
-            json.dump({"gaps": lists(out["gaps"]), "skipped": lists(out["skipped"]), **report}, f)
+            json.dump({"gaps": lists(out["gaps"]), "skipped": lists(out["skipped"]), **report, **clips16_keywords(cfg)}, f)
         per = [out["gaps"]] * ch if joint else out["gaps"]
     else:
         per = [sorted(cfg.gaps) if cfg.gaps is not None else [(cfg.mask_pos, cfg.mask_frames)]] * ch

@@ -14,7 +14,11 @@ on its own line -- it includes building and uploading the filter tables, for (a)
 length --, one line per repeat, the medians, how many samples of the file each variant changed, how many predicted labels differ between
 (a) and (c), and -- from separate, untimed runs -- the profiler's time of the cut_rate, patch_rate and resample_sinc families and the
 peak device memory (torch.cuda.max_memory_allocated above what is allocated before the call) per variant.
-usage: python tools/exp_rate.py [--repeats 5] [--minutes 10] [--gaps 60] [--sr 48000]      (sparse case: --minutes 60 --gaps 6)"""
+usage: python tools/exp_rate.py [--repeats 5] [--minutes 10] [--gaps 60] [--sr 48000]      (sparse case: --minutes 60 --gaps 6)
+
+--clips16 runs another pair instead, by the same protocol: feed="contexts" with clips16="file" (one si_cut_pair per pass
+yields both clip sets) against clips16="resampled" (si_cut_rate, then the clips resampled to 16 kHz), on the recording and on a 16 kHz
+int16 copy of it; wall clock, the profiler's rows of the way in, and the labels and samples that differ between the two."""
 import argparse
 import os
 import statistics
@@ -29,6 +33,7 @@ ap.add_argument("--minutes", type=float, default=10.0)
 ap.add_argument("--gaps", type=int, default=60)
 ap.add_argument("--sr", type=int, default=48000)
 ap.add_argument("--batch", type=int, default=32)
+ap.add_argument("--clips16", action="store_true")
 a = ap.parse_args()
 WARMUP = 1
 CLIP, CTX, LM = 200, 50, 10
@@ -73,6 +78,37 @@ def timed(fn):
     out = fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, out
+
+
+def clips16_pair(xf, srf, label):
+    """clips16="file" against "resampled" on the file xf at srf Hz: alternated wall clock, profiled rows, what differs."""
+    run = {m: (lambda m=m: eng.patch_file(xf, srf, gaps, feed="contexts", clips16=m, **KW)) for m in ("resampled", "file")}
+    t = {m: [] for m in run}
+    for r in range(WARMUP + a.repeats):
+        for m in (("resampled", "file") if r % 2 == 0 else ("file", "resampled")):
+            ms, out = timed(run[m])
+            del out
+            if r >= WARMUP:
+                t[m].append(ms)
+    for m in run:
+        print(f"{label}: median clips16={m}: {statistics.median(t[m]):.1f} ms over {len(t[m])} repeats (min {min(t[m]):.1f}, max {max(t[m]):.1f})")
+    res = {}
+    for m in run:
+        eng.ctx.profile_start(20000)
+        res[m] = run[m]()
+        prof = {e["name"]: e for e in eng.ctx.profile_stop()}
+        for name in ("cut_rate", "resample_sinc", "patch_rate"):
+            if name in prof and prof[name]["launches"]:
+                print(f"{label}: profiled clips16={m}: {name} {prof[name]['launches']} launches, {prof[name]['ms']:.3f} ms")
+    print(f"{label}: clips16 file | resampled: {int((res['file']['labels'] != res['resampled']['labels']).sum())} of {res['file']['labels'].numel()} "
+          f"predicted labels differ, {int((res['file']['patched'] != res['resampled']['patched']).sum())} of {xf.numel()} samples of patched differ")
+
+
+if a.clips16:
+    clips16_pair(x, sr, f"{sr} Hz int16")
+    x16k = eng.to_int16(eng.resample((x.to(torch.float32) / 32768.0)[None], sr, 16000)[0].contiguous())
+    clips16_pair(x16k, 16000, "16000 Hz int16 copy")
+    sys.exit(0)
 
 
 VARIANTS = (("patch_file", keep_rate), ("feed_contexts", feed_contexts), ("round_trip", round_trip))
