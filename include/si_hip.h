@@ -581,12 +581,35 @@ typedef struct si_region_table {
 int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_table* table, const float* gen, int Lrow, const float* gain,
                      float* out_f32, int16_t* out_pcm, si_stream_t stream);
 
+/* ---- The sample types of the file-typed calls -------------------------------------------------------------------------
+ * The eleven calls that take a file as it lies on disk -- si_quiet_runs[_ch], si_dead_runs, si_level_runs, si_cut_rate[_ch],
+ * si_cut_pair[_ch], si_patch_rate[_ch] -- name its sample type in their `is_pcm16` argument.  Pass one of:
+ *   SI_SAMPLE_F32 = 0   fp32
+ *   SI_SAMPLE_S16 = 1   int16 PCM; a sample enters the cutters and the patch as (float)v / 32768, exact
+ *   SI_SAMPLE_S24 = 2   packed little-endian signed 24-bit PCM, three bytes per sample, (n, ch) interleaved as a WAV data chunk holds
+ *                       it (blockAlign = 3 ch).  A sample v in [-2^23, 2^23 - 1] enters every kernel as v * 2^-23, exact in fp32.
+ *                       x / orig / out point at the first byte and may start at ANY byte; no byte before the base or at / after
+ *                       3 n ch is read.  `threshold` and `held_tol` count 24-bit steps, as they count int16 steps for int16
+ *                       (rel_threshold, half, min_len are not scaled): |v| and the held difference (2^24 - 1 at most) are taken in
+ *                       int32 and are exact in fp32, si_level_runs' squares (2^46 at most) in int64 and are exact in float64, and
+ *                       threshold_out receives T in 24-bit steps.  si_patch_rate[_ch] store a blend w as trunc(w * 8388608) clamped to
+ *                       [-8388608, 8388607], NaN -> 0 (si_pcm16's statement at 24 bits), with stores of exactly the sample's three
+ *                       bytes: no byte of a neighbouring sample or channel is written or rewritten.
+ * Any other non-zero value means what it meant before 2 was given a meaning, int16; no caller should pass one.  n, n_file and channels
+ * obey the same limits for every type; byte offsets ((i ch + channel) * 3) are 64-bit.  Every result for an s24 file V equals the
+ * call's result on its fp32 image V * 2^-23 with threshold and held_tol times 2^-23: the runs row for row, the clips byte for byte, and
+ * a patched sample is the store rule above applied to the fp32 the call writes for the image. */
+#define SI_SAMPLE_F32 0
+#define SI_SAMPLE_S16 1
+#define SI_SAMPLE_S24 2
+
 /* ---- Dropout detection: where the gaps of a damaged recording are -------------------------------------------------
  * The reference has no detection: the script's user types the one mask into predict.yaml (I_ea/predict.py:85-90).  This call finds
  * what a digital dropout leaves behind -- runs of (near) digital silence from lost packets, underruns or muted samples -- on the
  * device, where the recording already lies; gaps.runs_to_gaps turns the runs into gaps on the 20 ms grid.
- * x device, n samples, one channel, any sample rate: fp32 (is_pcm16 = 0) or int16 PCM as it lies in a file (is_pcm16 != 0); the base
- * needs only its element's alignment.  Sample i is QUIET iff |x[i]| <= threshold: NaN is loud, -0.0 is quiet, |-32768| is taken in
+ * x device, n samples, one channel, any sample rate: fp32 (is_pcm16 = SI_SAMPLE_F32), int16 PCM as it lies in a file (SI_SAMPLE_S16)
+ * or packed 24-bit PCM (SI_SAMPLE_S24: threshold in 24-bit steps; see above); the base needs only its element's alignment, any
+ * byte for s24.  Sample i is QUIET iff |x[i]| <= threshold: NaN is loud, -0.0 is quiet, |-32768| is taken in
  * int32, samples at and past n are loud.  The result is every MAXIMAL run of quiet samples of at least min_len samples, as int32
  * (start, len) rows SORTED BY START: rows [0, min(total, max_runs)) of runs (device int32 (max_runs, 2)) are written, rows at and past
  * that are not touched, and n_runs (device int32 (1)) receives the TOTAL number of such runs whether or not they all fit.  The same
@@ -654,8 +677,9 @@ typedef struct si_rate_table {
  * and rounded once to fp32 -- si_resample_sinc's arithmetic at the exact time, so a sample has the same bits wherever its window row
  * starts and however the chunks are listed.  x[j] is 22.05 kHz sample j of the recording's generated audio, read from the window's row;
  * j < 0 and j >= win_lim read as zero.  Then g = gain[win_ctx] * y and the sample is g (w = 1) or fma(w, g, (1 - w) * orig[i]):
- * si_patch_regions' roundings in its order.  orig / out: device, n_file samples of the SAME type, fp32 (is_pcm16 = 0) or int16 PCM
- * (is_pcm16 != 0: orig = (float)v / 32768, the result stored by si_pcm16's arithmetic); a base needs only its element's alignment;
+ * si_patch_regions' roundings in its order.  orig / out: device, n_file samples of the SAME type, fp32 (is_pcm16 = SI_SAMPLE_F32), int16
+ * PCM (SI_SAMPLE_S16: orig = (float)v / 32768, the result stored by si_pcm16's arithmetic) or packed 24-bit PCM (SI_SAMPLE_S24: orig =
+ * v * 2^-23, the result stored by the 24-bit store rule above, three bytes per written sample); a base needs only its element's alignment;
  * orig is read only and must not be out.  gen device fp32 (num_windows, Lrow); gain device fp32 (num_contexts) or NULL (= 1).
  * SI_EINVAL before any launch, naming the entry, for: everything si_patch_regions refuses, on the file axis; sr outside 4000 .. 192000
  * or equal to 22050; n_file, or its 22.05 kHz length ceil(n_file P / Q), above 2^31 - 1 - 2048; a filter with nwin < 2, num_table < 1,
@@ -686,7 +710,8 @@ int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int s
  * the whole file: (a) at exactly-integer times (j a multiple of P) frac is exactly 0, where the accumulated rounding picks the table
  * phase; elsewhere a result moves by at most an fp32 rounding; (b) the last sample j = N22 - 1 is interpolated when n_file P / Q is no
  * integer, where si_resample_sinc writes zero at and past int(n ratio).
- * x: device, n_file samples, fp32 (is_pcm16 = 0) or int16 PCM (is_pcm16 != 0: a sample enters as (float)v / 32768, exact); the base
+ * x: device, n_file samples, fp32 (is_pcm16 = SI_SAMPLE_F32), int16 PCM (SI_SAMPLE_S16: a sample enters as (float)v / 32768, exact) or
+ * packed 24-bit PCM (SI_SAMPLE_S24: v * 2^-23, exact; si_cut_pair takes the same three); the base
  * needs only its element's alignment.  host_start (HOST, C) is validated, start (DEVICE, C) is read: the si_span_table rule.  One
  * workgroup owns a tile of SI_CUT_RATE_TILE consecutive outputs of one clip.
  * SI_EINVAL before any launch, naming the argument, for: NULL pointers; sr outside 4000 .. 192000 or equal to 22050; n_file < 1; n_file

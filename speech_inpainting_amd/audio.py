@@ -134,3 +134,79 @@ def to_int16_pcm(audio: torch.Tensor, clip: bool = False) -> np.ndarray:
 def write_wav(path: str, pcm_or_float: np.ndarray, sr: int):
     from scipy.io import wavfile
     wavfile.write(path, sr, pcm_or_float)
+
+
+# ---- packed 24-bit PCM: the bytes of a WAV data chunk, kept as they are
+def pack_s24(v: np.ndarray) -> np.ndarray:
+    """int32 values in [-2^23, 2^23 - 1], any shape -> uint8 (..., 3): little-endian packed signed 24-bit PCM, as a WAV data chunk
+    holds it.  A value outside the range raises a ValueError."""
+    v = np.asarray(v)
+    if v.dtype.kind not in "iu":
+        raise ValueError(f"pack_s24: {v.dtype} values, integers wanted")
+    v = v.astype(np.int64)
+    if v.size and (v.min() < -(1 << 23) or v.max() > (1 << 23) - 1):
+        raise ValueError(f"pack_s24: values in [{v.min()}, {v.max()}], outside [-8388608, 8388607]")
+    u = (v & 0xFFFFFF).astype(np.uint32)
+    return np.stack([u & 0xFF, (u >> 8) & 0xFF, u >> 16], axis=-1).astype(np.uint8)
+
+
+def unpack_s24(b: np.ndarray) -> np.ndarray:
+    """uint8 (..., 3) packed little-endian signed 24-bit PCM -> int32 (...): byte 0 is the low one, the sign is bit 7 of byte 2."""
+    b = np.asarray(b)
+    if b.dtype != np.uint8 or b.ndim < 1 or b.shape[-1] != 3:
+        raise ValueError(f"unpack_s24: {b.dtype} {b.shape}, uint8 (..., 3) wanted")
+    w = b[..., 0].astype(np.uint32) << 8 | b[..., 1].astype(np.uint32) << 16 | b[..., 2].astype(np.uint32) << 24
+    return w.view(np.int32) >> 8 if w.ndim else np.int32(np.uint32(w).view(np.int32) >> 8)
+
+
+_PCM_SUBFORMAT = bytes.fromhex("0100000000001000800000aa00389b71")      # KSDATAFORMAT_SUBTYPE_PCM, the GUID of WAVE_FORMAT_EXTENSIBLE
+
+
+def read_wav_pcm(path: str):
+    """A small RIFF reader for the one case the file-typed routes keep packed: -> (data, sample_rate, channels).  A 24-bit PCM file
+    (format tag 1, or 0xFFFE with the PCM sub-format; 3 ch bytes per block) comes back as its data chunk's own bytes, uint8
+    (n, ch, 3), a trailing partial block dropped.  Everything else is left to the existing reader: data is what scipy returns for
+    the file, (n,) or (n, ch) in its own dtype.  Chunks other than `fmt ` and `data` are skipped, pad bytes honoured."""
+    import struct
+    with open(path, "rb") as f:
+        blob = f.read()
+    fmt = data = None
+    if len(blob) >= 12 and blob[:4] == b"RIFF" and blob[8:12] == b"WAVE":
+        pos = 12
+        while pos + 8 <= len(blob):
+            cid, size = blob[pos:pos + 4], struct.unpack_from("<I", blob, pos + 4)[0]
+            body = blob[pos + 8:pos + 8 + size]
+            if cid == b"fmt " and fmt is None:
+                fmt = body
+            elif cid == b"data" and data is None:
+                data = body
+            pos += 8 + size + (size & 1)
+    if fmt is not None and data is not None and len(fmt) >= 16:
+        tag, ch, sr, _, align, bits = struct.unpack_from("<HHIIHH", fmt, 0)
+        if tag == 0xFFFE and len(fmt) >= 40 and fmt[24:40] == _PCM_SUBFORMAT:
+            tag = 1
+        if tag == 1 and bits == 24 and ch >= 1 and align == 3 * ch:
+            n = len(data) // align
+            return np.frombuffer(data, np.uint8, n * align).reshape(n, ch, 3).copy(), int(sr), int(ch)
+    from scipy.io import wavfile
+    sr, arr = wavfile.read(path)
+    return arr, int(sr), (arr.shape[1] if arr.ndim == 2 else 1)
+
+
+def write_wav_s24(path: str, data: np.ndarray, sr: int):
+    """uint8 (n, 3) mono or (n, ch, 3) interleaved packed 24-bit PCM -> a 24-bit WAV file at `sr` Hz: a plain 16-byte PCM `fmt `
+    chunk (format tag 1, blockAlign 3 ch), the bytes as the data chunk, and the RIFF pad byte when 3 n ch is odd."""
+    import struct
+    data = np.ascontiguousarray(data)
+    if data.dtype != np.uint8 or data.ndim not in (2, 3) or data.shape[-1] != 3:
+        raise ValueError(f"write_wav_s24: {data.dtype} {data.shape}, uint8 (n, 3) or (n, ch, 3) wanted")
+    ch = data.shape[1] if data.ndim == 3 else 1
+    if not 1 <= ch <= 65535:
+        raise ValueError(f"write_wav_s24: {ch} channels")
+    raw = data.tobytes()
+    pad = len(raw) & 1
+    fmt = struct.pack("<HHIIHH", 1, ch, int(sr), int(sr) * 3 * ch, 3 * ch, 24)
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", 4 + 8 + len(fmt) + 8 + len(raw) + pad) + b"WAVE")
+        f.write(b"fmt " + struct.pack("<I", len(fmt)) + fmt)
+        f.write(b"data" + struct.pack("<I", len(raw)) + raw + b"\0" * pad)

@@ -64,6 +64,9 @@ class PredictConfig:
                                   # to feed the model) or "contexts" (only the context clips are, straight from the file: DESIGN.md 4.17)
     long_clips16: str = "resampled"   # `clips16:` inside `long:` (needs feed: contexts): "resampled" (default: the encoder's 16 kHz clips are
                                       # the cut 22.05 kHz clips resampled) or "file" (they too are cut straight from the file: DESIGN.md 4.26)
+    long_pcm24: str = "float32"   # `pcm24:` inside `long:` (needs rate: file and feed: contexts): "float32" (default: a 24-bit PCM file is read
+                                  # to float32 and written as float32, as before the key existed) or "keep" (its packed bytes go to the engine
+                                  # and the three files are written 24-bit: DESIGN.md 4.27); a file that is not 24-bit PCM ignores it
     detect: Optional[dict] = None  # optional `detect:` mapping ({threshold: 0.0, min_ms: 5.0, max_ms: 400.0, pad_frames: 0}): the gaps are
                                    # found in the file itself (engine.find_gaps) instead of given as `mask:` / `masks:`; needs `long:`
     detect_channels: str = "each"  # `channels:` inside `detect:` (needs long: {rate: file}), for a multi-channel file: "each" (default:
@@ -143,7 +146,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             patch_fade_ms = float(pm.get("fade_ms", 5))
             if patch_fade_ms < 0:
                 raise ValueError(f"{path}: patch.fade_ms = {patch_fade_ms} is negative")
-        long_cfg, long_rate, long_feed, long_clips16 = None, 22050, "recording", "resampled"
+        long_cfg, long_rate, long_feed, long_clips16, long_pcm24 = None, 22050, "recording", "resampled", "float32"
         if "long" in data:
             lm = data["long"] if data["long"] is not None else {}
             if not isinstance(lm, dict):
@@ -169,10 +172,18 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                 if long_clips16 == "file" and long_feed != "contexts":
                     raise ValueError(f"{path}: long.clips16 = file needs `feed: contexts` (with feed: {long_feed} the clips are slices of the "
                                      f"resampled recording)")
+            if "pcm24" in lm:
+                long_pcm24 = lm.pop("pcm24")
+                if long_pcm24 not in ("float32", "keep"):
+                    raise ValueError(f"{path}: long.pcm24 = {long_pcm24!r}: float32 (the default: a 24-bit file is read and written as float32) or "
+                                     f"keep (its packed samples are repaired in place and written 24-bit)")
+                if long_pcm24 == "keep" and (long_rate != "file" or long_feed != "contexts"):
+                    raise ValueError(f"{path}: long.pcm24 = keep needs `rate: file` and `feed: contexts` (with rate: {long_rate}, feed: {long_feed} "
+                                     f"the recording is resampled as a whole, from a float32 copy)")
             for key, val in lm.items():
                 if key not in long_cfg:
                     raise ValueError(f"{path}: unknown key `{key}` in `long:` (it takes clip_s, context_s, batch, rate, feed) and, with feed: "
-                                     f"contexts, clips16")
+                                     f"contexts, clips16 and pcm24")
                 long_cfg[key] = int(val) if key == "batch" else float(val)
                 if long_cfg[key] < 0:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
@@ -242,7 +253,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             hubert_checkpoint=data["hubert_model"][ds]["model_checkpoint"],
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
             raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, long_clips16=long_clips16,
-            detect=detect_cfg,
+            long_pcm24=long_pcm24, detect=detect_cfg,
             detect_channels=detect_channels, detect_dead=detect_dead, detect_level=detect_level)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None

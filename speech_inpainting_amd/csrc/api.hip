@@ -1770,8 +1770,8 @@ static int patch_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* 
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     const SiRate rt{t->start, t->len, t->span_win, t->span_lim, t->win_ctx, t->win_start, t->win_len, t->win_lim, t->chunk, t->k0, t->k1, t->ramp, fade,
                     f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Qr, (int)H, (int)row_cap};
-    if (inter) return si_launch_patch_rate_ch(ctx, orig, is_pcm16 != 0, n_file, channels, channel, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
-    return si_launch_patch_rate(ctx, orig, is_pcm16 != 0, n_file, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
+    if (inter) return si_launch_patch_rate_ch(ctx, orig, si_sample_format(is_pcm16), n_file, channels, channel, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
+    return si_launch_patch_rate(ctx, orig, si_sample_format(is_pcm16), n_file, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
 }
 
 int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int sr, const si_rate_table* table, const float* gen, int Lrow,
@@ -1818,8 +1818,8 @@ static int cut_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* x,
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     const SiFeed fd{f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Qr, (int)H, (int)cap, (int)N22};
-    if (inter) return si_launch_cut_rate_ch(ctx, x, is_pcm16 != 0, n_file, channels, channel, start, C, L, fd, out, static_cast<hipStream_t>(stream));
-    return si_launch_cut_rate(ctx, x, is_pcm16 != 0, n_file, start, C, L, fd, out, static_cast<hipStream_t>(stream));
+    if (inter) return si_launch_cut_rate_ch(ctx, x, si_sample_format(is_pcm16), n_file, channels, channel, start, C, L, fd, out, static_cast<hipStream_t>(stream));
+    return si_launch_cut_rate(ctx, x, si_sample_format(is_pcm16), n_file, start, C, L, fd, out, static_cast<hipStream_t>(stream));
 }
 
 int si_cut_rate(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_start, const int32_t* start, int C, int L,
@@ -1892,7 +1892,7 @@ static int cut_pair_call(si_ctx* ctx, const char* fn, bool inter, const void* x,
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     pr.cap = (int)cap, pr.N22 = (int)N22, pr.N16 = (int)N16, pr.lim16 = (int)lim16;
-    return si_launch_cut_pair(ctx, x, is_pcm16 != 0, n_file, inter ? channels : 0, inter ? channel : 0, frame, C, L22, L16, pr, out22, out16,
+    return si_launch_cut_pair(ctx, x, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, frame, C, L22, L16, pr, out22, out16,
                               static_cast<hipStream_t>(stream));
 }
 
@@ -1943,9 +1943,9 @@ static int quiet_runs_call(si_ctx* ctx, const char* fn, bool inter, const void* 
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
     if (inter)
-        return si_launch_quiet_runs_ch(ctx, x, is_pcm16 != 0, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch,
+        return si_launch_quiet_runs_ch(ctx, x, si_sample_format(is_pcm16), n, channels, channel, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch,
                                        static_cast<hipStream_t>(stream));
-    return si_launch_quiet_runs(ctx, x, is_pcm16 != 0, n, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch, static_cast<hipStream_t>(stream));
+    return si_launch_quiet_runs(ctx, x, si_sample_format(is_pcm16), n, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch, static_cast<hipStream_t>(stream));
 }
 
 int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
@@ -1969,7 +1969,7 @@ int si_dead_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, 
     if (!(held_tol >= 0.f)) return SI_FAIL_FN("held_tol = %g is negative or NaN", (double)held_tol);
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
-    return si_launch_dead_runs(ctx, x, is_pcm16 != 0, n, channels, channel, kind, threshold, rel_threshold, held_tol, min_len, runs, max_runs, n_runs,
+    return si_launch_dead_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, kind, threshold, rel_threshold, held_tol, min_len, runs, max_runs, n_runs,
                                threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
 }
 
@@ -1984,7 +1984,7 @@ int si_level_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels,
     if (!(rel_threshold >= 0.f && rel_threshold <= 1.f)) return SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 1]", (double)rel_threshold);
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
-    return si_launch_level_runs(ctx, x, is_pcm16 != 0, n, channels, channel, half, threshold, rel_threshold, min_len, runs, max_runs, n_runs,
+    return si_launch_level_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, half, threshold, rel_threshold, min_len, runs, max_runs, n_runs,
                                 threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
 }
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/si_hip.h"
 #include "weights_host.h"
 
@@ -27,6 +29,30 @@ int si_ensure_dyn_lds(si_ctx* ctx, const void* kern, size_t bytes);
 int si_num_cus(si_ctx* ctx);   // compute units of the context's device (persistent-kernel grids)
 
 typedef unsigned short bf16_t;   // raw bf16 bits
+
+// ------------------------------------------------------------------------------------------------
+// The sample types of the file-typed calls.  SiS24 is one packed little-endian signed 24-bit PCM sample as a WAV
+// data chunk holds it: three bytes of alignment 1, so `const SiS24* x` indexes samples, x[i] touches exactly bytes [3 i, 3 i + 3) and a
+// view may start at any byte.  value() is exact in fp32, and so is value() * 2^-23.
+// ------------------------------------------------------------------------------------------------
+struct SiS24 {
+    uint8_t b[3];
+    SiS24() = default;
+    __host__ __device__ explicit SiS24(int v) : b{(uint8_t)v, (uint8_t)(v >> 8), (uint8_t)(v >> 16)} {}
+    __host__ __device__ int value() const { return (int)((unsigned)b[0] << 8 | (unsigned)b[1] << 16 | (unsigned)b[2] << 24) >> 8; }
+};
+static_assert(sizeof(SiS24) == 3 && alignof(SiS24) == 1, "SiS24 is three packed bytes");
+
+// The C ABI's is_pcm16 argument as one of SI_SAMPLE_F32 / _S16 / _S24: 2 is s24, every other non-zero value int16 as it always was.
+inline int si_sample_format(int is_pcm16) { return is_pcm16 == SI_SAMPLE_S24 ? SI_SAMPLE_S24 : is_pcm16 != 0 ? SI_SAMPLE_S16 : SI_SAMPLE_F32; }
+inline double si_sample_bytes(int fmt) { return fmt == SI_SAMPLE_S24 ? 3.0 : fmt == SI_SAMPLE_S16 ? 2.0 : 4.0; }
+// f(null pointer of the sample type fmt names): the launchers pick their instantiation through its type.
+template <class F>
+inline void si_with_sample(int fmt, F&& f) {
+    if (fmt == SI_SAMPLE_S24) f(static_cast<const SiS24*>(nullptr));
+    else if (fmt == SI_SAMPLE_S16) f(static_cast<const int16_t*>(nullptr));
+    else f(static_cast<const float*>(nullptr));
+}
 
 // ------------------------------------------------------------------------------------------------
 // Ragged batches (BASELINE configs[4]: clips of different lengths in ONE launch, each clip's result equal to that clip run
@@ -352,18 +378,18 @@ int si_launch_patch_regions(si_ctx* ctx, const float* orig, const SiRegions& rt,
 size_t si_detect_scratch_bytes(int n);
 // x device fp32 or int16 (n) -> runs (max_runs, 2) = the maximal runs of |x| <= thr of at least min_len samples, sorted by start, and
 // *n_runs = how many there are (all of them, whether or not they fit); arguments validated by the caller, scratch 16-byte aligned
-int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
+int si_launch_quiet_runs(si_ctx* ctx, const void* x, int fmt, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
                          char* scratch, hipStream_t st);
 // the same for an interleaved x (n sample times of `channels` channels): channel c >= 0 alone, or all jointly (c < 0)
-int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
+int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
                             int max_runs, int32_t* n_runs, char* scratch, hipStream_t st);
 // the maximal runs of DEAD samples: quiet against max(thr, rel * peak) (kind & 1), held = within tol of a neighbour of
 // the same channel (kind & 2); channels = 1 is a one-channel file; *thr_out (device, may be null) receives the effective threshold
-int si_launch_dead_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, int kind, float thr, float rel, float tol,
+int si_launch_dead_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int kind, float thr, float rel, float tol,
                         int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
 // the maximal runs of samples under a window of low RMS level: the windows of 2 half + 1 samples whose energy is at
 // most T^2 times their sample count, T = max(thr, rel * peak), dilated by half; channels and *thr_out as above
-int si_launch_level_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, int half, float thr, float rel, int min_len,
+int si_launch_level_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
                          int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
@@ -381,11 +407,11 @@ struct SiRate {
     int P, Q, H, row_cap;
 };
 // one workgroup per listed chunk of 2048 file samples: the blended samples of its spans written into out (n_file, orig's type: fp32 or
-// int16 when pcm16), the rest untouched; arguments validated by the caller
-int si_launch_patch_rate(si_ctx* ctx, const void* orig, bool pcm16, int n_file, const SiRate& rt, int num_chunks, const float* gen, int Lrow,
+// int16 / packed 24-bit by fmt), the rest untouched; arguments validated by the caller
+int si_launch_patch_rate(si_ctx* ctx, const void* orig, int fmt, int n_file, const SiRate& rt, int num_chunks, const float* gen, int Lrow,
                          const float* gain, void* out, hipStream_t st);
 // the same into channel `channel` of an interleaved orig / out (n_file sample times of ch channels)
-int si_launch_patch_rate_ch(si_ctx* ctx, const void* orig, bool pcm16, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
+int si_launch_patch_rate_ch(si_ctx* ctx, const void* orig, int fmt, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
                             const float* gen, int Lrow, const float* gain, void* out, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
@@ -398,12 +424,12 @@ struct SiFeed {
     const double* win; const double* dwin; int nwin, num_table, step; double scale;
     int P, Q, H, cap, N22;
 };
-// out (C, L) row c = 22.05 kHz samples [start[c], start[c] + L) of the file x (n_file; fp32, or int16 when pcm16), interpolated at the
+// out (C, L) row c = 22.05 kHz samples [start[c], start[c] + L) of the file x (n_file; fp32, int16 or packed 24-bit by fmt), interpolated at the
 // exact time j Q / P; start device int32 (C); arguments validated by the caller
-int si_launch_cut_rate(si_ctx* ctx, const void* x, bool pcm16, int n_file, const int32_t* start, int C, int L, const SiFeed& fd, float* out,
+int si_launch_cut_rate(si_ctx* ctx, const void* x, int fmt, int n_file, const int32_t* start, int C, int L, const SiFeed& fd, float* out,
                        hipStream_t st);
 // the same from channel `channel` of an interleaved x (n_file sample times of ch channels)
-int si_launch_cut_rate_ch(si_ctx* ctx, const void* x, bool pcm16, int n_file, int ch, int channel, const int32_t* start, int C, int L,
+int si_launch_cut_rate_ch(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* start, int C, int L,
                           const SiFeed& fd, float* out, hipStream_t st);
 
 // both clip sets of a pass from one staged tile (rate_feed_kernels.hip)
@@ -421,7 +447,7 @@ struct SiPair {
 };
 // out22 (C, L22) row c = 22.05 kHz samples 441 frame[c] + [0, L22), out16 (C, L16) row c = 16 kHz samples 320 frame[c] + [0, L16) of the
 // file x; ch = 0: a mono file (the mono kernel), else channel `channel` of ch interleaved; arguments validated by the caller
-int si_launch_cut_pair(si_ctx* ctx, const void* x, bool pcm16, int n_file, int ch, int channel, const int32_t* frame, int C, int L22, int L16,
+int si_launch_cut_pair(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* frame, int C, int L22, int L16,
                        const SiPair& pr, float* out22, float* out16, hipStream_t st);
 
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).

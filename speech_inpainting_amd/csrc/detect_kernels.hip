@@ -50,6 +50,8 @@ __device__ __forceinline__ int dt_block_excl(int v, int ident, int* sw, int& tot
 // NaN compares false: loud.  -0.0 has magnitude 0: quiet.  |-32768| is taken in int32 and is exact in fp32.
 __device__ __forceinline__ bool dt_quiet(float v, float thr) { return __builtin_fabsf(v) <= thr; }
 __device__ __forceinline__ bool dt_quiet(int16_t v, float thr) { const int a = v; return (float)(a < 0 ? -a : a) <= thr; }
+// Packed 24-bit: thr counts 24-bit steps; |-2^23| is taken in int32 and is exact in fp32.
+__device__ __forceinline__ bool dt_quiet(SiS24 v, float thr) { const int a = v.value(); return (float)(a < 0 ? -a : a) <= thr; }
 
 // What pass 1 leaves per chunk, from the quiet bits b of this thread's eight samples (bits at and past len are 0, so the first loud bit
 // is at most len): the bitmap byte, and through two workgroup scans the chunk's lead and trail.  Every thread of the workgroup calls it.
@@ -69,21 +71,15 @@ __device__ __forceinline__ void dt_store_chunk(unsigned b, int c, int len, uint8
     }
 }
 
-// ------------------------------------------------------------------------------------------------ pass 1: bits + summary
-// grid (chunks), 256 threads.  Thread t owns samples [c0 + 8 t, c0 + 8 t + 8): 32 bytes of fp32 (two 16-byte loads) or 16 bytes of int16
-// (one).  Callers pass views, so the base is generally off the 16-byte grid; c0 * sizeof(T) is a multiple of 16, so the alignment is the
-// call's: an aligned call takes the 16-byte loads, any other stages the chunk through LDS with coalesced element loads and reads its
-// eight samples from there.  Samples at and past n are loud, so bit (c0 + i >= n) is 0 and a run never reaches past the input.
-//   lead  = quiet samples from the chunk's first sample forward (the chunk's length when all of it is quiet)
-//   trail = quiet samples from the chunk's last sample backward (likewise)
+// This thread's eight consecutive samples of a one-channel chunk, for every pass 1 and pass 0: two / one 16-byte loads from an
+// aligned base, else the chunk staged through LDS (tile: DT_CHUNK elements) with coalesced element loads.  Samples at and past n read 0.
+// Every thread of the workgroup calls it.
 template <typename T>
-__global__ __launch_bounds__(256) void detect_bits_kernel(const T* __restrict__ x, int n, float thr, uint8_t* __restrict__ bitmap,
-                                                          int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
-    __shared__ __attribute__((aligned(16))) T tile[DT_CHUNK];
-    __shared__ int sw[4];
-    const int c = blockIdx.x, t = threadIdx.x;
-    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0), g = c0 + t * 8;
-    union { uint4 q[sizeof(T) / 2]; T e[8]; } u;
+union DtEight { uint4 q[sizeof(T) / 2]; T e[8]; };
+
+template <typename T>
+__device__ __forceinline__ void dt_load_eight(const T* __restrict__ x, int n, int c0, int len, T* tile, DtEight<T>& u) {
+    const int t = threadIdx.x, g = c0 + t * 8;
     if ((reinterpret_cast<size_t>(x) & 15) == 0) {
         if (g + 8 <= n) {
 #pragma unroll
@@ -102,6 +98,69 @@ __global__ __launch_bounds__(256) void detect_bits_kernel(const T* __restrict__ 
 #pragma unroll
         for (int i = 0; i < (int)sizeof(T) / 2; ++i) u.q[i] = reinterpret_cast<const uint4*>(tile + t * 8)[i];
     }
+}
+
+// The same for packed 24-bit samples.  The thread's eight samples are 24 bytes from byte 3 c0 + 24 t of the view, and
+// 3 c0 is a multiple of 6144, so the alignment is again the call's: a base on the 8-byte grid takes three 8-byte loads; any other base
+// stages the chunk through LDS, lane t on element t, t + 256, ... -- three byte loads each, which touch the sample's own bytes alone --
+// and reads its 24 bytes from there (8-byte aligned in LDS: the tile is 16-byte aligned).  Samples at and past n read 0, and no byte
+// at or past 3 n is loaded on either route.
+// The eight samples leave the six loaded words by constant shifts (sample j = bytes [3 j, 3 j + 3) of the 24), so they stay in
+// registers: a union with the words would be indexed by bytes and land in scratch or LDS.
+template <>
+union DtEight<SiS24> { SiS24 e[8]; };
+
+__device__ __forceinline__ void dt_unpack_eight(const uint2 (&d)[3], DtEight<SiS24>& u) {
+    const unsigned w[6] = {d[0].x, d[0].y, d[1].x, d[1].y, d[2].x, d[2].y};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int k = (3 * j) >> 2, sh = ((3 * j) & 3) * 8;           // sh = 0, 24, 16, 8: only 24 and 16 reach into the next word
+        const unsigned v = sh > 8 ? w[k] >> sh | w[k + 1] << (32 - sh) : w[k] >> sh;
+        u.e[j] = SiS24((int)v);                                       // keeps the low 24 bits
+    }
+}
+
+__device__ __forceinline__ void dt_load_eight(const SiS24* __restrict__ x, int n, int c0, int len, SiS24* tile, DtEight<SiS24>& u) {
+    const int t = threadIdx.x, g = c0 + t * 8;
+    uint2 d[3];
+    if ((reinterpret_cast<size_t>(x) & 7) == 0) {
+        if (g + 8 <= n) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) d[i] = reinterpret_cast<const uint2*>(x + g)[i];
+            dt_unpack_eight(d, u);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) u.e[j] = g + j < n ? x[g + j] : SiS24(0);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = j * 256 + t;
+            tile[i] = i < len ? x[c0 + i] : SiS24(0);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 3; ++i) d[i] = reinterpret_cast<const uint2*>(tile + t * 8)[i];
+        dt_unpack_eight(d, u);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pass 1: bits + summary
+// grid (chunks), 256 threads.  Thread t owns samples [c0 + 8 t, c0 + 8 t + 8): 32 bytes of fp32 (two 16-byte loads), 16 bytes of int16
+// (one) or 24 bytes of packed 24-bit (three 8-byte loads; dt_load_eight above).  Callers pass views, so the base is generally off the 16-byte grid; c0 * sizeof(T) is a multiple of 16, so the alignment is the
+// call's: an aligned call takes the 16-byte loads, any other stages the chunk through LDS with coalesced element loads and reads its
+// eight samples from there.  Samples at and past n are loud, so bit (c0 + i >= n) is 0 and a run never reaches past the input.
+//   lead  = quiet samples from the chunk's first sample forward (the chunk's length when all of it is quiet)
+//   trail = quiet samples from the chunk's last sample backward (likewise)
+template <typename T>
+__global__ __launch_bounds__(256) void detect_bits_kernel(const T* __restrict__ x, int n, float thr, uint8_t* __restrict__ bitmap,
+                                                          int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    __shared__ __attribute__((aligned(16))) T tile[DT_CHUNK];
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    DtEight<T> u;
+    dt_load_eight(x, n, c0, len, tile, u);
     unsigned b = 0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) b |= (t * 8 + j < len && dt_quiet(u.e[j], thr)) ? 1u << j : 0u;
@@ -296,44 +355,20 @@ __global__ __launch_bounds__(256) void detect_offsets_kernel(const int32_t* __re
 // The magnitude of a sample as the bits of a non-negative finite float, which order as ints; NaN and +-inf count as 0 (skipped).
 __device__ __forceinline__ int dt_mag_bits(float v) { const int b = __float_as_int(v) & 0x7fffffff; return b < 0x7f800000 ? b : 0; }
 __device__ __forceinline__ int dt_mag_bits(int16_t v) { const int a = v; return __float_as_int((float)(a < 0 ? -a : a)); }
+__device__ __forceinline__ int dt_mag_bits(SiS24 v) { const int a = v.value(); return __float_as_int((float)(a < 0 ? -a : a)); }      // 24-bit steps
 
 // |a - b| <= tol.  fp32: one fp32 subtraction; a NaN neighbour and inf - inf compare false.  int16: the difference in int32 (65535 at most).
 __device__ __forceinline__ bool dt_link(float a, float b, float tol) { return __builtin_fabsf(a - b) <= tol; }
 __device__ __forceinline__ bool dt_link(int16_t a, int16_t b, float tol) { const int d = (int)a - (int)b; return (float)(d < 0 ? -d : d) <= tol; }
+// packed 24-bit: the difference in int32, 2^24 - 1 at most and therefore exact in fp32; tol counts 24-bit steps
+__device__ __forceinline__ bool dt_link(SiS24 a, SiS24 b, float tol) { const int d = a.value() - b.value(); return (float)(d < 0 ? -d : d) <= tol; }
 
 __device__ __forceinline__ float dt_shfl_up1(float v) { return __shfl_up(v, 1, 64); }
 __device__ __forceinline__ int16_t dt_shfl_up1(int16_t v) { return (int16_t)__shfl_up((int)v, 1, 64); }
+__device__ __forceinline__ SiS24 dt_shfl_up1(SiS24 v) { return SiS24(__shfl_up(v.value(), 1, 64)); }
 __device__ __forceinline__ float dt_shfl_down1(float v) { return __shfl_down(v, 1, 64); }
+__device__ __forceinline__ SiS24 dt_shfl_down1(SiS24 v) { return SiS24(__shfl_down(v.value(), 1, 64)); }
 __device__ __forceinline__ int16_t dt_shfl_down1(int16_t v) { return (int16_t)__shfl_down((int)v, 1, 64); }
-
-// This thread's eight consecutive samples of a one-channel chunk, as detect_bits_kernel reads them: two / one 16-byte loads from an
-// aligned base, else the chunk staged through LDS (tile: DT_CHUNK elements) with coalesced element loads.  Samples at and past n read 0.
-// Every thread of the workgroup calls it.
-template <typename T>
-union DtEight { uint4 q[sizeof(T) / 2]; T e[8]; };
-
-template <typename T>
-__device__ __forceinline__ void dt_load_eight(const T* __restrict__ x, int n, int c0, int len, T* tile, DtEight<T>& u) {
-    const int t = threadIdx.x, g = c0 + t * 8;
-    if ((reinterpret_cast<size_t>(x) & 15) == 0) {
-        if (g + 8 <= n) {
-#pragma unroll
-            for (int i = 0; i < (int)sizeof(T) / 2; ++i) u.q[i] = reinterpret_cast<const uint4*>(x + g)[i];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) u.e[j] = g + j < n ? x[g + j] : T(0);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = j * 256 + t;
-            tile[i] = i < len ? x[c0 + i] : T(0);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < (int)sizeof(T) / 2; ++i) u.q[i] = reinterpret_cast<const uint4*>(tile + t * 8)[i];
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ pass 0: the peak
 // grid (chunks), 256 threads.  cpeak[c] = the largest dt_mag_bits over the chunk's samples below n (0 when none is finite).
@@ -494,6 +529,7 @@ __device__ __forceinline__ void lv_square(float v, double& s, int& bad) {
     bad = finite ? 0 : 1;
 }
 __device__ __forceinline__ void lv_square(int16_t v, double& s, int& bad) { const int a = v; s = (double)(a * a); bad = 0; }   // at most 2^30
+__device__ __forceinline__ void lv_square(SiS24 v, double& s, int& bad) { const long a = v.value(); s = (double)(a * a); bad = 0; }    // at most 2^46: int64, exact in float64
 
 // dst[p] = the sum of src over p's segment up to p (REV = false: from the segment's first element; true: from p to its last).  Segments
 // are [k L, (k + 1) L) cut at N.  Thread t walks `per` consecutive elements in scan order, the 256 partial sums are scanned with
@@ -629,8 +665,9 @@ struct DtLevel { int half; float rel; float* thr_out; };
 // channels, and `channel` picks one of them or, below 0, all of them jointly (detect_bits_ch_kernel).  Passes 2 - 5 are the same launches.
 // dead != nullptr: pass 1 is detect_dead(_ch)_kernel, behind pass 0 when dead->rel > 0; nullptr: the launches above.
 // level != nullptr (dead is nullptr then): pass 1 is detect_level_kernel, behind the same pass 0 when level->rel > 0.
-static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
-                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr, const DtLevel* level = nullptr) {
+template <typename T>
+static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
+                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead, const DtLevel* level) {
     const int chunks = (int)(((long)n + DT_CHUNK - 1) / DT_CHUNK);
     const size_t words = ((size_t)chunks * sizeof(int32_t) + 15) & ~(size_t)15;
     uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch);
@@ -643,7 +680,7 @@ static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels
     int32_t* cpeak = reinterpret_cast<int32_t*>(p + 5 * words);
     float* pk = reinterpret_cast<float*>(p + 6 * words);              // {peak, T}
     const double bits = (double)chunks * 256.0, sums = (double)chunks * 4.0;
-    const double samples = (double)n * (channels ? channels : 1) * (pcm16 ? 2.0 : 4.0);
+    const double samples = (double)n * (channels ? channels : 1) * (double)sizeof(T);
 
     if (dead || level) {
         const float* thr_dev = nullptr;
@@ -651,11 +688,9 @@ static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels
         if (rel > 0.f) {
             si_prof_begin(ctx, "detect_peak", 0.0, samples + sums, st);
             if (channels == 0) {
-                if (pcm16) detect_peak_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, cpeak);
-                else detect_peak_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, cpeak);
+                detect_peak_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, cpeak);
             } else {
-                if (pcm16) detect_peak_ch_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, channels, channel, cpeak);
-                else detect_peak_ch_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, channels, channel, cpeak);
+                detect_peak_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, cpeak);
             }
             si_prof_end(ctx, st);
             SI_HIP_CHECK(hipGetLastError());
@@ -668,33 +703,28 @@ static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels
         if (level) {
             const int h = level->half, ch = channels ? channels : 1;
             const size_t lds = 20 * (size_t)(DT_CHUNK + 4 * h) + 4 * (size_t)(DT_CHUNK + 2 * h);   // 139 264 bytes at h = SI_LEVEL_MAX_HALF
-            const void* kern = pcm16 ? reinterpret_cast<const void*>(&detect_level_kernel<int16_t>) : reinterpret_cast<const void*>(&detect_level_kernel<float>);
+            const void* kern = reinterpret_cast<const void*>(&detect_level_kernel<T>);
             if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
             // profiled in the family of the descriptor routes' pass 1, as both detect_dead kernels are: the lists of families are closed
             si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
-            if (pcm16) detect_level_kernel<int16_t><<<dim3(chunks), 256, lds, st>>>(static_cast<const int16_t*>(x), n, ch, channels ? channel : 0, h, thr, thr_dev, level->thr_out, bitmap, lead, trail);
-            else detect_level_kernel<float><<<dim3(chunks), 256, lds, st>>>(static_cast<const float*>(x), n, ch, channels ? channel : 0, h, thr, thr_dev, level->thr_out, bitmap, lead, trail);
+            detect_level_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, channels ? channel : 0, h, thr, thr_dev, level->thr_out, bitmap, lead, trail);
         } else if (channels == 0) {
             si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
-            if (pcm16) detect_dead_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
-            else detect_dead_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
+            detect_dead_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
         } else {
-            const size_t lds = (size_t)(DT_CHUNK + 2) * (channel < 0 ? channels : 1) * (pcm16 ? sizeof(int16_t) : sizeof(float));   // 65 600 bytes at 8 fp32 channels
-            const void* kern = pcm16 ? reinterpret_cast<const void*>(&detect_dead_ch_kernel<int16_t>) : reinterpret_cast<const void*>(&detect_dead_ch_kernel<float>);
+            const size_t lds = (size_t)(DT_CHUNK + 2) * (channel < 0 ? channels : 1) * sizeof(T);   // 65 600 bytes at 8 fp32 channels
+            const void* kern = reinterpret_cast<const void*>(&detect_dead_ch_kernel<T>);
             if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
             si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
-            if (pcm16) detect_dead_ch_kernel<int16_t><<<dim3(chunks), 256, lds, st>>>(static_cast<const int16_t*>(x), n, channels, channel, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
-            else detect_dead_ch_kernel<float><<<dim3(chunks), 256, lds, st>>>(static_cast<const float*>(x), n, channels, channel, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
+            detect_dead_ch_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, channels, channel, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
         }
     } else if (channels == 0) {
-        si_prof_begin(ctx, "detect_bits", 0.0, (double)n * (pcm16 ? 2.0 : 4.0) + bits + 2.0 * sums, st);
-        if (pcm16) detect_bits_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, thr, bitmap, lead, trail);
-        else detect_bits_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, thr, bitmap, lead, trail);
+        si_prof_begin(ctx, "detect_bits", 0.0, (double)n * (double)sizeof(T) + bits + 2.0 * sums, st);
+        detect_bits_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, thr, bitmap, lead, trail);
     } else {
         // a single channel still moves the whole 32- or 64-byte sectors its elements lie in: counted as the chunk's elements either way
-        si_prof_begin(ctx, "detect_bits_ch", 0.0, (double)n * channels * (pcm16 ? 2.0 : 4.0) + bits + 2.0 * sums, st);
-        if (pcm16) detect_bits_ch_kernel<int16_t><<<dim3(chunks), 256, 0, st>>>(static_cast<const int16_t*>(x), n, channels, channel, thr, bitmap, lead, trail);
-        else detect_bits_ch_kernel<float><<<dim3(chunks), 256, 0, st>>>(static_cast<const float*>(x), n, channels, channel, thr, bitmap, lead, trail);
+        si_prof_begin(ctx, "detect_bits_ch", 0.0, (double)n * channels * (double)sizeof(T) + bits + 2.0 * sums, st);
+        detect_bits_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, thr, bitmap, lead, trail);
     }
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
@@ -723,27 +753,36 @@ static int dt_launch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels
     return SI_OK;
 }
 
-int si_launch_quiet_runs(si_ctx* ctx, const void* x, bool pcm16, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
-                         char* scratch, hipStream_t st) {
-    return dt_launch(ctx, x, pcm16, n, 0, 0, thr, min_len, runs, max_runs, n_runs, scratch, st);
+static int dt_launch(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
+                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr, const DtLevel* level = nullptr) {
+    int rc = SI_OK;
+    si_with_sample(fmt, [&](auto tag) {
+        rc = dt_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st, dead, level);
+    });
+    return rc;
 }
 
-int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
+int si_launch_quiet_runs(si_ctx* ctx, const void* x, int fmt, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
+                         char* scratch, hipStream_t st) {
+    return dt_launch(ctx, x, fmt, n, 0, 0, thr, min_len, runs, max_runs, n_runs, scratch, st);
+}
+
+int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
                             int max_runs, int32_t* n_runs, char* scratch, hipStream_t st) {
-    return dt_launch(ctx, x, pcm16, n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st);
+    return dt_launch(ctx, x, fmt, n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st);
 }
 
 // channels = 1 is a one-channel file: its elements are the mono call's, and so are its kernels.
-int si_launch_dead_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, int kind, float thr, float rel, float tol,
+int si_launch_dead_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int kind, float thr, float rel, float tol,
                         int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st) {
     const DtDead dead{kind, rel, tol, thr_out};
-    return dt_launch(ctx, x, pcm16, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, &dead);
+    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, &dead);
 }
 
 // The windowed RMS level; channels = 1 is a one-channel file, as for si_launch_dead_runs.
-int si_launch_level_runs(si_ctx* ctx, const void* x, bool pcm16, int n, int channels, int channel, int half, float thr, float rel, int min_len,
+int si_launch_level_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
                          int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st) {
     const DtLevel level{half, rel, thr_out};
-    return dt_launch(ctx, x, pcm16, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
+    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
                      &level);
 }

@@ -1,5 +1,5 @@
 // rate_feed_kernels.hip -- the model's 22.05 kHz context clips cut straight out of a file at its own rate, gfx950.
-//   cut_rate_kernel<float | int16_t>   per tile of 512 consecutive outputs of one clip: the file samples the tile's interpolation reads
+//   cut_rate_kernel<float | int16_t | SiS24>   per tile of 512 consecutive outputs of one clip: the file samples the tile's interpolation reads
 //                                      staged in LDS as fp32, then per output the two wings of the band-limited interpolation at the
 //                                      exact rational time j Q / P
 //   cut_rate_ch_kernel<float | int16_t>  the same tile read from one channel of an INTERLEAVED file: one shared body
@@ -12,6 +12,7 @@
 
 __device__ __forceinline__ float rf_load(const float* p) { return *p; }
 __device__ __forceinline__ float rf_load(const int16_t* p) { return (float)*p * (1.0f / 32768.0f); }     // exact: 16 bits x 2^-15
+__device__ __forceinline__ float rf_load(const SiS24* p) { return (float)p->value() * (1.0f / 8388608.0f); }  // exact: 24 bits x 2^-23
 
 // grid (ceil(L / 512), C), 256 threads, fd.cap floats of dynamic LDS.  Workgroup (tile, c) owns outputs [tile 512, min(tile 512 + 512, L))
 // of clip c = 22.05 kHz samples j0 + [0, cnt) of the recording, j0 = start[c] + tile 512 (workgroup-uniform: scalar loads).
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(256) void cut_pair_ch_kernel(const T* __restrict__ 
 
 // The caller (si_cut_pair[_ch]) checked every argument, pr.cap * 4 <= 64 KB and C <= 65535 among them.  ch = 0: the mono kernel.  The
 // launches are profiled under cut_rate's names: the same family, and like it they hold no scratch of the context's.
-int si_launch_cut_pair(si_ctx* ctx, const void* x, bool pcm16, int n_file, int ch, int channel, const int32_t* frame, int C, int L22, int L16,
+int si_launch_cut_pair(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* frame, int C, int L22, int L16,
                        const SiPair& pr, float* out22, float* out16, hipStream_t st) {
     if (C <= 0 || L22 <= 0 || L16 <= 0) return SI_OK;
     constexpr int T22 = 441 * RF_PAIR_FRAMES, T16 = 320 * RF_PAIR_FRAMES;
@@ -211,19 +212,19 @@ int si_launch_cut_pair(si_ctx* ctx, const void* x, bool pcm16, int n_file, int c
     const dim3 grid(std::max((L22 + T22 - 1) / T22, (L16 + T16 - 1) / T16), C);
     const double o22 = (double)C * L22, o16 = (double)C * L16;
     const double flops = o22 * 8.0 * pr.r22.H + o16 * 8.0 * pr.r16.H;
-    const double bytes = (o22 + o16) * 4.0 + (double)grid.x * C * pr.cap * (pcm16 ? 2.0 : 4.0);
+    const double bytes = (o22 + o16) * 4.0 + (double)grid.x * C * pr.cap * si_sample_bytes(fmt);
     if (ch > 0) {
         si_prof_begin(ctx, "cut_rate_ch", flops, bytes, st);
-        if (pcm16)
-            cut_pair_ch_kernel<int16_t><<<grid, 256, lds, st>>>(static_cast<const int16_t*>(x), n_file, ch, channel, frame, L22, L16, pr, out22, out16);
-        else
-            cut_pair_ch_kernel<float><<<grid, 256, lds, st>>>(static_cast<const float*>(x), n_file, ch, channel, frame, L22, L16, pr, out22, out16);
+        si_with_sample(fmt, [&](auto tag) {
+            using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
+            cut_pair_ch_kernel<T><<<grid, 256, lds, st>>>(static_cast<const T*>(x), n_file, ch, channel, frame, L22, L16, pr, out22, out16);
+        });
     } else {
         si_prof_begin(ctx, "cut_rate", flops, bytes, st);
-        if (pcm16)
-            cut_pair_kernel<int16_t><<<grid, 256, lds, st>>>(static_cast<const int16_t*>(x), n_file, frame, L22, L16, pr, out22, out16);
-        else
-            cut_pair_kernel<float><<<grid, 256, lds, st>>>(static_cast<const float*>(x), n_file, frame, L22, L16, pr, out22, out16);
+        si_with_sample(fmt, [&](auto tag) {
+            using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
+            cut_pair_kernel<T><<<grid, 256, lds, st>>>(static_cast<const T*>(x), n_file, frame, L22, L16, pr, out22, out16);
+        });
     }
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
@@ -231,34 +232,34 @@ int si_launch_cut_pair(si_ctx* ctx, const void* x, bool pcm16, int n_file, int c
 }
 
 // The caller (si_cut_rate) checked every argument, fd.cap * 4 <= 64 KB and C <= 65535 among them.
-int si_launch_cut_rate(si_ctx* ctx, const void* x, bool pcm16, int n_file, const int32_t* start, int C, int L, const SiFeed& fd, float* out,
+int si_launch_cut_rate(si_ctx* ctx, const void* x, int fmt, int n_file, const int32_t* start, int C, int L, const SiFeed& fd, float* out,
                        hipStream_t st) {
     if (C <= 0 || L <= 0) return SI_OK;
     const size_t lds = (size_t)fd.cap * sizeof(float);
     const dim3 grid((L + RF_TILE - 1) / RF_TILE, C);
     const double outs = (double)C * L;
-    si_prof_begin(ctx, "cut_rate", outs * 8.0 * fd.H, outs * 4.0 + (double)grid.x * C * fd.cap * (pcm16 ? 2.0 : 4.0), st);
-    if (pcm16)
-        cut_rate_kernel<int16_t><<<grid, 256, lds, st>>>(static_cast<const int16_t*>(x), n_file, start, L, fd, out);
-    else
-        cut_rate_kernel<float><<<grid, 256, lds, st>>>(static_cast<const float*>(x), n_file, start, L, fd, out);
+    si_prof_begin(ctx, "cut_rate", outs * 8.0 * fd.H, outs * 4.0 + (double)grid.x * C * fd.cap * si_sample_bytes(fmt), st);
+    si_with_sample(fmt, [&](auto tag) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
+        cut_rate_kernel<T><<<grid, 256, lds, st>>>(static_cast<const T*>(x), n_file, start, L, fd, out);
+    });
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;
 }
 
 // The caller (si_cut_rate_ch) checked every argument, 1 <= ch <= SI_MAX_CHANNELS and 0 <= channel < ch among them.
-int si_launch_cut_rate_ch(si_ctx* ctx, const void* x, bool pcm16, int n_file, int ch, int channel, const int32_t* start, int C, int L,
+int si_launch_cut_rate_ch(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* start, int C, int L,
                           const SiFeed& fd, float* out, hipStream_t st) {
     if (C <= 0 || L <= 0) return SI_OK;
     const size_t lds = (size_t)fd.cap * sizeof(float);
     const dim3 grid((L + RF_TILE - 1) / RF_TILE, C);
     const double outs = (double)C * L;
-    si_prof_begin(ctx, "cut_rate_ch", outs * 8.0 * fd.H, outs * 4.0 + (double)grid.x * C * fd.cap * (pcm16 ? 2.0 : 4.0), st);
-    if (pcm16)
-        cut_rate_ch_kernel<int16_t><<<grid, 256, lds, st>>>(static_cast<const int16_t*>(x), n_file, ch, channel, start, L, fd, out);
-    else
-        cut_rate_ch_kernel<float><<<grid, 256, lds, st>>>(static_cast<const float*>(x), n_file, ch, channel, start, L, fd, out);
+    si_prof_begin(ctx, "cut_rate_ch", outs * 8.0 * fd.H, outs * 4.0 + (double)grid.x * C * fd.cap * si_sample_bytes(fmt), st);
+    si_with_sample(fmt, [&](auto tag) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
+        cut_rate_ch_kernel<T><<<grid, 256, lds, st>>>(static_cast<const T*>(x), n_file, ch, channel, start, L, fd, out);
+    });
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;

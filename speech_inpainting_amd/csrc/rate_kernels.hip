@@ -1,6 +1,6 @@
 // rate_kernels.hip -- repair at the file's own sample rate, gfx950: the generated audio of the gaps carried from the
-// generator's 22.05 kHz axis to the FILE's rate and blended into the file's own samples, fp32 or int16 as they lie in the file.
-//   patch_rate_kernel<float | int16_t>   per touched chunk of 2048 file samples: band-limited interpolation of the window rows at the
+// generator's 22.05 kHz axis to the FILE's rate and blended into the file's own samples, fp32, int16 or packed 24-bit as they lie in the file.
+//   patch_rate_kernel<float | int16_t | SiS24>   per touched chunk of 2048 file samples: band-limited interpolation of the window rows at the
 //                                        exact rational time i P / Q + patch_regions_kernel's blend, written into the caller's copy
 //   patch_rate_ch_kernel<float | int16_t> the same chunk written into one channel of an INTERLEAVED file: one shared body
 // It stands where `resample(patched, 22050, sr)` over the whole repaired recording would: that pass costs every sample of the file a
@@ -19,6 +19,19 @@ __device__ __forceinline__ float rk_load(const float* p) { return *p; }
 __device__ __forceinline__ float rk_load(const int16_t* p) { return (float)*p * (1.0f / 32768.0f); }     // exact: 16 bits x 2^-15
 __device__ __forceinline__ void rk_store(float* p, float v) { *p = v; }
 __device__ __forceinline__ void rk_store(int16_t* p, float v) { *p = rk_pcm16(v); }
+// Packed 24-bit PCM: rk_pcm16's statement at 24 bits -- `* 8388608`, truncated toward zero, 8388608.0 -> 8388607, NaN -> 0.
+// The load is exact (24 bits x 2^-23); the store writes the sample's own three bytes, one byte each: no word a neighbour owns is touched.
+__device__ __forceinline__ int rk_pcm24(float v) {
+    const float p = v * 8388608.0f;
+    return (int)fminf(fmaxf(truncf(p == p ? p : 0.f), -8388608.f), 8388607.f);
+}
+__device__ __forceinline__ float rk_load(const SiS24* p) { return (float)p->value() * (1.0f / 8388608.0f); }
+__device__ __forceinline__ void rk_store(SiS24* p, float v) {
+    const int q = rk_pcm24(v);
+    p->b[0] = (uint8_t)q;
+    p->b[1] = (uint8_t)(q >> 8);
+    p->b[2] = (uint8_t)(q >> 16);
+}
 
 // grid (Q), 256 threads, rt.row_cap floats of dynamic LDS.  Workgroup q owns file samples [c0, c1) of chunk rt.chunk[q] and walks spans
 // [k0[q], k1[q]) -- q is workgroup-uniform, so the whole table arrives through scalar loads and the span loop is uniform.  Per span ks
@@ -130,34 +143,32 @@ __global__ __launch_bounds__(256) void patch_rate_ch_kernel(const T* __restrict_
 }
 
 // The caller (si_patch_rate) checked every argument, row_cap * 4 <= 64 KB among them.
-int si_launch_patch_rate(si_ctx* ctx, const void* orig, bool pcm16, int n_file, const SiRate& rt, int num_chunks, const float* gen, int Lrow,
+int si_launch_patch_rate(si_ctx* ctx, const void* orig, int fmt, int n_file, const SiRate& rt, int num_chunks, const float* gen, int Lrow,
                          const float* gain, void* out, hipStream_t st) {
     if (num_chunks <= 0) return SI_OK;
     const size_t lds = (size_t)rt.row_cap * sizeof(float);
-    const double esz = pcm16 ? 2.0 : 4.0;
+    const double esz = si_sample_bytes(fmt);
     si_prof_begin(ctx, "patch_rate", (double)num_chunks * RK_CHUNK * 8.0 * rt.H, (double)num_chunks * (RK_CHUNK * 2.0 * esz + 4.0 * rt.row_cap), st);
-    if (pcm16)
-        patch_rate_kernel<int16_t><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const int16_t*>(orig), rt, gen, Lrow, gain, n_file, static_cast<int16_t*>(out));
-    else
-        patch_rate_kernel<float><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const float*>(orig), rt, gen, Lrow, gain, n_file, static_cast<float*>(out));
+    si_with_sample(fmt, [&](auto tag) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
+        patch_rate_kernel<T><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const T*>(orig), rt, gen, Lrow, gain, n_file, static_cast<T*>(out));
+    });
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;
 }
 
 // The caller (si_patch_rate_ch) checked every argument, 1 <= ch <= SI_MAX_CHANNELS and 0 <= channel < ch among them.
-int si_launch_patch_rate_ch(si_ctx* ctx, const void* orig, bool pcm16, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
+int si_launch_patch_rate_ch(si_ctx* ctx, const void* orig, int fmt, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
                             const float* gen, int Lrow, const float* gain, void* out, hipStream_t st) {
     if (num_chunks <= 0) return SI_OK;
     const size_t lds = (size_t)rt.row_cap * sizeof(float);
-    const double esz = pcm16 ? 2.0 : 4.0;
+    const double esz = si_sample_bytes(fmt);
     si_prof_begin(ctx, "patch_rate_ch", (double)num_chunks * RK_CHUNK * 8.0 * rt.H, (double)num_chunks * (RK_CHUNK * 2.0 * esz + 4.0 * rt.row_cap), st);
-    if (pcm16)
-        patch_rate_ch_kernel<int16_t><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const int16_t*>(orig), rt, gen, Lrow, gain, n_file, ch, channel,
-                                                                       static_cast<int16_t*>(out));
-    else
-        patch_rate_ch_kernel<float><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const float*>(orig), rt, gen, Lrow, gain, n_file, ch, channel,
-                                                                     static_cast<float*>(out));
+    si_with_sample(fmt, [&](auto tag) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
+        patch_rate_ch_kernel<T><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const T*>(orig), rt, gen, Lrow, gain, n_file, ch, channel, static_cast<T*>(out));
+    });
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;

@@ -724,6 +724,22 @@ class InpaintingEngine:
         tables resample(., sr, 22050) runs on, held once."""
         return self._sinc_tables(sr, 22050)
 
+    @staticmethod
+    def _file_samples(x: torch.Tensor, fn: str) -> Tuple[bool, int]:
+        """(s24, sample dimensions) of a file x: packed 24-bit PCM is a uint8 tensor whose last dimension is the
+        sample's 3 bytes, (n, 3) mono or (n, ch, 3) interleaved -- np.frombuffer(data, np.uint8).reshape(n, ch, 3) of a WAV data chunk;
+        the sample dimensions are those in front of it.  Any other uint8 shape is refused here, before any launch."""
+        if x.dtype != torch.uint8:
+            return False, x.dim()
+        if x.dim() not in (2, 3) or x.shape[-1] != 3:
+            raise ValueError(f"{fn}: a uint8 input is packed 24-bit PCM, (n, 3) mono or (n, ch, 3) interleaved, not {tuple(x.shape)}")
+        return True, x.dim() - 1
+
+    @staticmethod
+    def _file_on_device(x: torch.Tensor, device) -> torch.Tensor:
+        """x on `device` in the sample type it is read in: int16 and packed 24-bit bytes as they are, anything else as fp32."""
+        return x.to(device, x.dtype if x.dtype in (torch.int16, torch.uint8) else torch.float32)
+
     def patch_file(self, x, sr: int, gaps=None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
                    return_windows: bool = False, feed: str = "recording", channel_gaps=None, clips16: str = "resampled") -> Dict[str, object]:
         """patch_recording for a file at ITS OWN sample rate and in its own sample type: x (n,) is the recording at `sr` Hz, fp32 in
@@ -755,7 +771,11 @@ class InpaintingEngine:
         the file's real neighbours at the clip edges, as the reference's second load of the file does (I_ea/predict.py:80): one
         si_cut_pair launch per pass -- si_cut_pair_ch per channel present in a pass -- yields both clip sets, the 22.05 kHz ones with
         si_cut_rate's bytes, and no resample_sinc runs.  A 16 kHz file's own samples reach the encoder.  return_windows then adds clips16
-        per pass.  At sr = 22050 it is not read, as feed is not."""
+        per pass.  At sr = 22050 it is not read, as feed is not.
+        PACKED 24-BIT PCM: x uint8, (n, 3) mono or (n, ch, 3) interleaved, the bytes of a WAV data chunk.  It needs
+        feed="contexts": the clips are cut from the bytes (a sample enters as v * 2^-23, exact) and si_patch_rate writes the three
+        bytes of each blended sample -- trunc(w * 2^23), clamped -- into `patched`, a uint8 copy of x's shape; no fp32 image of the
+        file exists.  Everything else above holds as for int16.  A 22.05 kHz s24 file is refused."""
         self._need(head=True, codebook=True, what="patch_file")
         if feed not in ("recording", "contexts"):
             raise ValueError(f"patch_file: feed = {feed!r}: 'recording' or 'contexts'")
@@ -766,22 +786,27 @@ class InpaintingEngine:
         if batch <= 0:
             raise ValueError(f"patch_file: batch = {batch}")
         x = torch.as_tensor(x)
+        s24, sdim = InpaintingEngine._file_samples(x, "patch_file")
+        if s24 and feed != "contexts":
+            raise ValueError(f"patch_file: packed 24-bit PCM needs feed = 'contexts' (feed = {feed!r} resamples an fp32 image of the whole file)")
+        if s24 and sr == 22050:
+            raise ValueError("patch_file: packed 24-bit PCM at 22050 Hz is not served: that file goes through patch_recording as fp32")
         if gaps is not None and channel_gaps is not None:
             raise ValueError("patch_file: both gaps and channel_gaps: one list for every channel, or one list per channel")
-        if x.dim() == 2:
+        if sdim == 2:
             per = G.channel_gap_lists(gaps, channel_gaps, x.shape[1])
             kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed,
                       clips16=clips16)
             if x.shape[1] == 1:
-                out = self.patch_file(x.reshape(-1), sr, per[0], **kw)
-                out["patched"] = out["patched"].reshape(-1, 1)
+                out = self.patch_file(x.reshape(-1, 3) if s24 else x.reshape(-1), sr, per[0], **kw)
+                out["patched"] = out["patched"].reshape(x.shape)
                 return out
             return self._patch_file_channels(x, sr, per, **kw)
         if gaps is None:
             raise ValueError("patch_file: a one-channel (n,) recording takes `gaps`; channel_gaps belongs to an (n, ch) file")
         pcm = x.dtype == torch.int16
-        x = x.to(self.device, torch.int16 if pcm else torch.float32).reshape(-1).contiguous()
-        n_file = x.numel()
+        x = InpaintingEngine._file_on_device(x, self.device).contiguous() if s24 else x.to(self.device, torch.int16 if pcm else torch.float32).reshape(-1).contiguous()
+        n_file = x.shape[0]
         if n_file < 1 or n_file > 2 ** 31 - 1 - 2048:
             raise ValueError(f"patch_file: a file of {n_file} samples")
         fade_f = G.file_fade(fade_ms, sr)
@@ -841,11 +866,11 @@ class InpaintingEngine:
     def _patch_file_channels(self, x: torch.Tensor, sr: int, channel_gaps, fade_ms: float, clip_frames: int, min_context: int, batch: int,
                              return_windows: bool, feed: str, clips16: str = "resampled") -> Dict[str, object]:
         """patch_file for an interleaved file x (n, ch >= 2) with one gap list per channel."""
-        n_file, ch = x.shape
+        n_file, ch = x.shape[:2]                                       # packed 24-bit (DESIGN.md 4.27): (n, ch, 3) bytes, feed = "contexts"
         if ch > G.MAX_CHANNELS:
             raise ValueError(f"patch_file: a file of {ch} channels, at most {G.MAX_CHANNELS}")
         pcm = x.dtype == torch.int16
-        x = x.to(self.device, torch.int16 if pcm else torch.float32).contiguous()
+        x = InpaintingEngine._file_on_device(x, self.device).contiguous()
         if n_file < 1 or n_file > 2 ** 31 - 1 - 2048:
             raise ValueError(f"patch_file: a file of {n_file} samples")
         P, Q = G.rate_ratio(sr)
@@ -936,7 +961,8 @@ class InpaintingEngine:
         """File in, repaired file out, at the file's own rate and in its own sample type: find_gaps on x itself, where a dropout is
         still exact zeros, then patch_file with the gaps it found.  The usable frames are those of the recording's 22.05 kHz length
         ceil(n * 22050 / sr) (`recording_frames`), and a gap longer than the planner's budget counts as long, as in conceal_recording.
-        threshold is in x's own units, as find_gaps takes it: full scale for fp32, int16 steps for an int16 file.
+        threshold is in x's own units, as find_gaps takes it: full scale for fp32, int16 steps for an int16 file, 24-bit steps for
+        packed 24-bit PCM (uint8 (n, 3) or (n, ch, 3), DESIGN.md 4.27: it needs feed="contexts" and comes back as uint8).
         feed: patch_file's ("recording" or "contexts").  clips16: patch_file's ("resampled" or "file"), passed on when
         it is off its default.
         -> patch_file's dictionary + gaps + skipped.  With nothing found: an exact copy; only the detection kernels launched.
@@ -951,12 +977,17 @@ class InpaintingEngine:
             raise ValueError(f"conceal_file: detect = {detect!r}: 'each' or 'joint'")
         P, Q = G.rate_ratio(sr)
         x = torch.as_tensor(x)
+        s24, sdim = InpaintingEngine._file_samples(x, "conceal_file")
+        if s24 and feed != "contexts":
+            raise ValueError(f"conceal_file: packed 24-bit PCM needs feed = 'contexts' (feed = {feed!r} resamples an fp32 image of the whole file)")
+        if s24 and sr == 22050:
+            raise ValueError("conceal_file: packed 24-bit PCM at 22050 Hz is not served: that file goes through conceal_recording as fp32")
         shape = x.shape
-        many = x.dim() == 2 and shape[1] >= 2                          # (n, 1) is the mono route, reshaped at the end
+        many = sdim == 2 and shape[1] >= 2                             # (n, 1) is the mono route, reshaped at the end
         if many and shape[1] > G.MAX_CHANNELS:
             raise ValueError(f"conceal_file: a file of {shape[1]} channels, at most {G.MAX_CHANNELS}")
-        x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32)
-        x = x.contiguous() if many else x.reshape(-1).contiguous()
+        x = InpaintingEngine._file_on_device(x, self.device)
+        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
         n_rec, lim = self.recording_frames(-(-x.shape[0] * P // Q), clip_frames)
         if n_rec > clip_frames:
             max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
@@ -978,8 +1009,8 @@ class InpaintingEngine:
         out["gaps"], out["skipped"] = found["gaps"], found["skipped"]
         if "threshold" in found:
             out["threshold"] = found["threshold"]
-        if not many and len(shape) == 2:
-            out["patched"] = out["patched"].reshape(-1, 1)
+        if not many and sdim == 2:
+            out["patched"] = out["patched"].reshape(shape)
         return out
 
     # ---- dropout detection: where the gaps are, found on the device; then patch_recording as it is
@@ -988,17 +1019,20 @@ class InpaintingEngine:
         maximal run of samples with |x| <= threshold of at least min_len samples, as (start, len) rows sorted by start
         (si_quiet_runs).  One D2H copy: the count.  A ValueError names both numbers when more than max_runs runs qualify.
         An interleaved x (n, ch >= 2) needs `channel`: an index for that channel's runs, -1 for the runs of sample
-        times at which every channel is quiet; rows are in sample times (si_quiet_runs_ch).  x is not flattened or de-interleaved."""
+        times at which every channel is quiet; rows are in sample times (si_quiet_runs_ch).  x is not flattened or de-interleaved.
+        Packed 24-bit PCM: x uint8, (n, 3) or (n, ch, 3); threshold in 24-bit steps."""
         x = torch.as_tensor(x)
-        if x.dim() == 2 and x.shape[1] >= 2:
+        s24, sdim = InpaintingEngine._file_samples(x, "find_quiet_runs")
+        if sdim == 2 and x.shape[1] >= 2:
             if channel is None:
                 raise ValueError(f"find_quiet_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
-            x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32).contiguous()
+            x = InpaintingEngine._file_on_device(x, self.device).contiguous()
             runs, n_runs = self.ctx.quiet_runs(x, threshold, min_len, max_runs, channel=int(channel))
         else:
             if channel is not None and int(channel) not in (-1, 0):
                 raise ValueError(f"find_quiet_runs: channel = {channel} of a one-channel recording")
-            x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32).reshape(-1).contiguous()
+            x = InpaintingEngine._file_on_device(x, self.device)
+            x = (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
             runs, n_runs = self.ctx.quiet_runs(x, threshold, min_len, max_runs)
         total = int(n_runs.item())
         if total > int(max_runs):
@@ -1017,13 +1051,14 @@ class InpaintingEngine:
         if kind not in self.DEAD_KINDS:
             raise ValueError(f"find_dead_runs: kind = {kind!r}: 'quiet', 'held' or 'any'")
         x = torch.as_tensor(x)
-        many = x.dim() == 2 and x.shape[1] >= 2
+        s24, sdim = InpaintingEngine._file_samples(x, "find_dead_runs")                      # packed 24-bit PCM: uint8 (n, 3) or (n, ch, 3), 24-bit steps
+        many = sdim == 2 and x.shape[1] >= 2
         if many and channel is None:
             raise ValueError(f"find_dead_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
         if not many and channel is not None and int(channel) not in (-1, 0):
             raise ValueError(f"find_dead_runs: channel = {channel} of a one-channel recording")
-        x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32)
-        x = x.contiguous() if many else x.reshape(-1).contiguous()
+        x = InpaintingEngine._file_on_device(x, self.device)
+        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
         words = torch.zeros(2, dtype=torch.int32, device=self.device)      # {the count, T's bits}: one copy brings both
         runs, _ = self.ctx.dead_runs(x, self.DEAD_KINDS[kind], threshold, rel_threshold, held_tol, min_len, max_runs, n_runs=words[:1],
                                      channel=int(channel) if many else None, threshold_out=words[1:].view(torch.float32))
@@ -1050,13 +1085,14 @@ class InpaintingEngine:
         if int(half) != half or not 0 <= int(half) <= G.LEVEL_MAX_HALF:
             raise ValueError(f"find_level_runs: half = {half} samples, outside 0 .. {G.LEVEL_MAX_HALF}")
         x = torch.as_tensor(x)
-        many = x.dim() == 2 and x.shape[1] >= 2
+        s24, sdim = InpaintingEngine._file_samples(x, "find_level_runs")                      # packed 24-bit PCM: uint8 (n, 3) or (n, ch, 3), 24-bit steps
+        many = sdim == 2 and x.shape[1] >= 2
         if many and channel is None:
             raise ValueError(f"find_level_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
         if not many and channel is not None and int(channel) not in (-1, 0):
             raise ValueError(f"find_level_runs: channel = {channel} of a one-channel recording")
-        x = x.to(self.device, x.dtype if x.dtype == torch.int16 else torch.float32)
-        x = x.contiguous() if many else x.reshape(-1).contiguous()
+        x = InpaintingEngine._file_on_device(x, self.device)
+        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
         words = torch.zeros(2, dtype=torch.int32, device=self.device)      # {the count, T's bits}: one copy brings both
         runs, _ = self.ctx.level_runs(x, int(half), threshold, rel_threshold, min_len, max_runs, n_runs=words[:1],
                                       channel=int(channel) if many else None, threshold_out=words[1:].view(torch.float32))
@@ -1083,7 +1119,7 @@ class InpaintingEngine:
                   merge_frames: Optional[int] = None, fade: int = 110, n_rec_frames: Optional[int] = None,
                   lim_frames: Optional[int] = None, channel: Optional[int] = None, kind: str = "quiet", rel_threshold: float = 0.0,
                   held_tol: float = 0.0, win_ms: float = 2.0) -> Dict[str, object]:
-        """The dropouts of a recording x (n samples at `sr` Hz, fp32 in full-scale units or int16 PCM): runs of at least min_ms of
+        """The dropouts of a recording x (n samples at `sr` Hz, fp32 in full-scale units, int16 PCM or packed 24-bit PCM): runs of at least min_ms of
         |x| <= threshold (find_quiet_runs), mapped by gaps.runs_to_gaps onto the 20 ms grid of the recording's n_rec_frames frames
         (default n * 50 // sr) with the usable frames [0, lim_frames).  merge_frames None = 2 * the frames one cross-fade of `fade`
         22.05 kHz samples reaches over; gaps of more than max_ms are skipped.
@@ -1096,7 +1132,8 @@ class InpaintingEngine:
         round(win_ms * sr / 2000) samples on each side, against the threshold -- and the dictionary carries `threshold` as well.
         held_tol has no meaning there and must be 0; win_ms is read at no other kind."""
         x = torch.as_tensor(x)
-        n, sr = (x.shape[0] if x.dim() == 2 else x.numel()), int(sr)
+        s24, sdim = InpaintingEngine._file_samples(x, "find_gaps")                 # packed 24-bit PCM (DESIGN.md 4.27): thresholds in 24-bit steps
+        n, sr = (x.shape[0] if sdim == 2 or s24 else x.numel()), int(sr)
         if n < 1 or sr <= 0:
             raise ValueError(f"find_gaps: {n} samples at {sr} Hz")
         min_len, T = max(1, int(round(float(min_ms) * sr / 1000.0))), None

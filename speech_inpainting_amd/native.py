@@ -35,6 +35,7 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_plan_weights", "si_pack_weights_host"]
 SI_MAX_SPANS = 16
 SI_MAX_CHANNELS = 8                        # channels of an interleaved file
+SAMPLE_F32, SAMPLE_S16, SAMPLE_S24 = 0, 1, 2   # SI_SAMPLE_*: the file-typed calls' sample types; s24 = uint8 (..., 3)
 DEAD_QUIET, DEAD_HELD = 1, 2               # SI_DEAD_QUIET, SI_DEAD_HELD: the `kind` bits of si_dead_runs
 LEVEL_MAX_HALF = 1024                      # SI_LEVEL_MAX_HALF: the largest half window of si_level_runs
 CUT_RATE_TILE = 512                        # SI_CUT_RATE_TILE: consecutive outputs of one clip per workgroup of si_cut_rate
@@ -710,12 +711,19 @@ class NativeContext:
     def _interleaved(x: torch.Tensor, channel: Optional[int]) -> Tuple[int, int]:
         """(sample times, channels) of x as a call with `channel` takes it: (n,) for channel None, else (n, ch) interleaved (DESIGN.md
         4.18).  Channel counts and indices the C ABI would refuse are passed on, so that it is the one that refuses them."""
-        assert x.is_cuda and x.dtype in (torch.float32, torch.int16) and x.is_contiguous()
+        assert x.is_cuda and x.dtype in (torch.float32, torch.int16, torch.uint8) and x.is_contiguous()
+        byte = int(x.dtype == torch.uint8)                             # packed 24-bit (DESIGN.md 4.27): a trailing dimension of the 3 bytes
+        assert not byte or x.shape[-1] == 3
         if channel is None:
-            assert x.dim() == 1
-            return min(x.numel(), 2 ** 31 - 1), 0
-        assert x.dim() == 2
+            assert x.dim() == 1 + byte
+            return min(x.shape[0], 2 ** 31 - 1), 0
+        assert x.dim() == 2 + byte
         return min(x.shape[0], 2 ** 31 - 1), x.shape[1]
+
+    @staticmethod
+    def _sample_format(x: torch.Tensor) -> int:
+        """The file-typed calls' is_pcm16 argument for x: SI_SAMPLE_F32 / _S16 / _S24."""
+        return SAMPLE_S24 if x.dtype == torch.uint8 else SAMPLE_S16 if x.dtype == torch.int16 else SAMPLE_F32
 
     def patch_rate(self, orig: torch.Tensor, sr: int, table: "RateTable", gen: Optional[torch.Tensor], filt: dict, out: torch.Tensor,
                    gain: Optional[torch.Tensor] = None, channel: Optional[int] = None) -> None:
@@ -736,10 +744,10 @@ class NativeContext:
                        float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
         t = table.struct()
         if channel is not None:
-            self._check(self.lib.si_patch_rate_ch(self._h, _ptr(orig), int(orig.dtype == torch.int16), n_file, ch, int(channel), int(sr), C.byref(t), _ptr(gen),
+            self._check(self.lib.si_patch_rate_ch(self._h, _ptr(orig), self._sample_format(orig), n_file, ch, int(channel), int(sr), C.byref(t), _ptr(gen),
                                                   0 if gen is None else gen.shape[1], _ptr(gain), C.byref(f), _ptr(out), self._stream()), "si_patch_rate_ch")
             return
-        self._check(self.lib.si_patch_rate(self._h, _ptr(orig), int(orig.dtype == torch.int16), n_file, int(sr), C.byref(t), _ptr(gen),
+        self._check(self.lib.si_patch_rate(self._h, _ptr(orig), self._sample_format(orig), n_file, int(sr), C.byref(t), _ptr(gen),
                                            0 if gen is None else gen.shape[1], _ptr(gain), C.byref(f), _ptr(out), self._stream()), "si_patch_rate")
 
     # ---- context clips cut at the file's own sample rate
@@ -763,10 +771,10 @@ class NativeContext:
         f = SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
                        float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
         if channel is not None:
-            self._check(self.lib.si_cut_rate_ch(self._h, _ptr(x), int(x.dtype == torch.int16), n_file, ch, int(channel), int(sr), host.ctypes.data_as(C.c_void_p),
+            self._check(self.lib.si_cut_rate_ch(self._h, _ptr(x), self._sample_format(x), n_file, ch, int(channel), int(sr), host.ctypes.data_as(C.c_void_p),
                                                 _ptr(dev), Cn, L, C.byref(f), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate_ch")
             return out
-        self._check(self.lib.si_cut_rate(self._h, _ptr(x), int(x.dtype == torch.int16), n_file, int(sr), host.ctypes.data_as(C.c_void_p),
+        self._check(self.lib.si_cut_rate(self._h, _ptr(x), self._sample_format(x), n_file, int(sr), host.ctypes.data_as(C.c_void_p),
                                          _ptr(dev), Cn, L, C.byref(f), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate")
         return out
 
@@ -802,9 +810,9 @@ class NativeContext:
         tail = (host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L22, L16, fs[0], fs[1], C.c_void_p(outs[0].data_ptr()), C.c_void_p(outs[1].data_ptr()),
                 self._stream())
         if channel is not None:
-            self._check(self.lib.si_cut_pair_ch(self._h, _ptr(x), int(x.dtype == torch.int16), n_file, ch, int(channel), int(sr), *tail), "si_cut_pair_ch")
+            self._check(self.lib.si_cut_pair_ch(self._h, _ptr(x), self._sample_format(x), n_file, ch, int(channel), int(sr), *tail), "si_cut_pair_ch")
         else:
-            self._check(self.lib.si_cut_pair(self._h, _ptr(x), int(x.dtype == torch.int16), n_file, int(sr), *tail), "si_cut_pair")
+            self._check(self.lib.si_cut_pair(self._h, _ptr(x), self._sample_format(x), n_file, int(sr), *tail), "si_cut_pair")
         return outs[0], outs[1]
 
     # ---- dropout detection
@@ -824,10 +832,10 @@ class NativeContext:
         assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
         assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
         if channel is not None:
-            self._check(self.lib.si_quiet_runs_ch(self._h, _ptr(x), int(x.dtype == torch.int16), n, ch, int(channel), float(threshold), int(min_len),
+            self._check(self.lib.si_quiet_runs_ch(self._h, _ptr(x), self._sample_format(x), n, ch, int(channel), float(threshold), int(min_len),
                                                   _ptr(runs), max_runs, _ptr(n_runs), self._stream()), "si_quiet_runs_ch")
             return runs, n_runs
-        self._check(self.lib.si_quiet_runs(self._h, _ptr(x), int(x.dtype == torch.int16), n, float(threshold), int(min_len),
+        self._check(self.lib.si_quiet_runs(self._h, _ptr(x), self._sample_format(x), n, float(threshold), int(min_len),
                                            _ptr(runs), max_runs, _ptr(n_runs), self._stream()), "si_quiet_runs")
         return runs, n_runs
 
@@ -848,7 +856,7 @@ class NativeContext:
         assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
         assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
         assert threshold_out is None or (threshold_out.is_cuda and threshold_out.dtype == torch.float32 and threshold_out.numel() == 1)
-        self._check(self.lib.si_dead_runs(self._h, _ptr(x), int(x.dtype == torch.int16), n, ch if channel is not None else 1,
+        self._check(self.lib.si_dead_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
                                           int(channel) if channel is not None else 0, int(kind), float(threshold), float(rel_threshold),
                                           float(held_tol), int(min_len), _ptr(runs), max_runs, _ptr(n_runs), _ptr(threshold_out), self._stream()),
                     "si_dead_runs")
@@ -870,7 +878,7 @@ class NativeContext:
         assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
         assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
         assert threshold_out is None or (threshold_out.is_cuda and threshold_out.dtype == torch.float32 and threshold_out.numel() == 1)
-        self._check(self.lib.si_level_runs(self._h, _ptr(x), int(x.dtype == torch.int16), n, ch if channel is not None else 1,
+        self._check(self.lib.si_level_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
                                            int(channel) if channel is not None else 0, int(half), float(threshold), float(rel_threshold),
                                            int(min_len), _ptr(runs), max_runs, _ptr(n_runs), _ptr(threshold_out), self._stream()),
                     "si_level_runs")

@@ -350,18 +350,22 @@ def predict_ragged(engine: InpaintingEngine, waves16: Sequence[np.ndarray], wave
 
 
 def _detect_gaps(cfg: PredictConfig, engine: InpaintingEngine, raw: np.ndarray, sr_file: int, n22: int, fade: int, clip_frames: int,
-                 min_context: int, save_dir: str) -> List[Tuple[int, int]]:
+                 min_context: int, save_dir: str, x24: Optional[np.ndarray] = None) -> List[Tuple[int, int]]:
     """The `detect:` key of the `long:` route: the gaps found in the file's OWN samples at the file's rate, where a dropout is still
     exact zeros (the resampler's ringing fills it in at 22.05 kHz).  A mono int16 file is scanned as the int16 it holds, the threshold
     scaled by 32768 (an exact scaling: the same samples are quiet).  Prints every gap and every skipped run, writes gaps.json.
     With `kind:`, `rel_threshold:` or `held_tol:` off their defaults it also prints the effective threshold and records
-    `kind` and `T` in gaps.json."""
+    `kind` and `T` in gaps.json.  x24: the packed bytes (n, 3) of a 24-bit file under `pcm24: keep`, scanned as they
+    are with the threshold scaled by 2^23."""
     from scipy.io import wavfile
     d = cfg.detect
     x, scale = raw, 1.0
-    pcm_file = wavfile.read(cfg.wave_path)[1]
-    if pcm_file.dtype == np.int16 and pcm_file.ndim == 1:
-        x, scale = pcm_file, 32768.0
+    if x24 is not None:
+        x, scale = x24, 8388608.0
+    else:
+        pcm_file = wavfile.read(cfg.wave_path)[1]
+        if pcm_file.dtype == np.int16 and pcm_file.ndim == 1:
+            x, scale = pcm_file, 32768.0
     n_rec, lim = engine.recording_frames(n22, clip_frames)
     max_ms = d["max_ms"] if n_rec <= clip_frames else min(d["max_ms"], 20.0 * (clip_frames - 2 * min_context))
     found = engine.find_gaps(x, sr_file, d["threshold"] * scale, d["min_ms"], max_ms, d["pad_frames"], None, fade, n_rec, lim,
@@ -398,11 +402,11 @@ def _dead_report(cfg: PredictConfig, found: dict, scale: float) -> dict:
     file was scanned in (one per channel for `channels: each`).  Printed too.  Empty at the defaults: gaps.json is then what it was."""
     if "threshold" not in found:
         return {}
-    T, unit = found["threshold"], "int16 steps" if scale != 1.0 else "full scale"
+    T, unit = found["threshold"], {1.0: "full scale", 8388608.0: "24-bit steps"}.get(scale, "int16 steps")
     level = level_keywords(cfg)                                                    # kind level: the window is printed and recorded too
     window = f", window win_ms = {level['win_ms']}" if level else ""
     print(f"Detection kind = {cfg.detect_dead['kind']}, effective threshold T = {T} ({unit}){window}")
-    return {"kind": cfg.detect_dead["kind"], "T": T, **level}
+    return {"kind": cfg.detect_dead["kind"], "T": T, **({"unit": unit} if scale == 8388608.0 else {}), **level}
 
 
 def clips16_keywords(cfg) -> dict:
@@ -417,31 +421,43 @@ def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str)
     masked.wav and patched.wav are written at that rate; an int16 file is written as int16, any other as the float32 it was read to.
     With `feed: contexts` a multi-channel file (up to 8 channels) stays interleaved and is repaired channel by channel (DESIGN.md
     4.18): `mask:` / `masks:` apply to every channel, `detect: {channels: each | joint}` finds the gaps per channel or where all
-    channels are quiet.  With the default `feed: recording` it is refused, as it was."""
+    channels are quiet.  With the default `feed: recording` it is refused, as it was.
+    `pcm24: keep` (DESIGN.md 4.27): a 24-bit PCM file goes to the engine as its packed bytes and the three files are written 24-bit;
+    `detect:` thresholds are scaled by 2^23 and gaps.json names the unit "24-bit steps".  Any other file ignores the key."""
     from scipy.io import wavfile
     from . import gaps as G
-    sr_file, data = wavfile.read(cfg.wave_path)
-    if data.ndim != 1:
+    x24 = None
+    if getattr(cfg, "long_pcm24", "float32") == "keep":
+        packed, sr24, ch24 = audio.read_wav_pcm(cfg.wave_path)
+        if packed.dtype == np.uint8 and packed.ndim == 3:                          # a 24-bit PCM file: (n, ch, 3) bytes
+            if ch24 > 1:
+                return _main_long_file_channels(cfg, engine, save_dir, sr24, packed)
+            x24 = np.ascontiguousarray(packed[:, 0])
+    sr_file, data = (sr24, x24) if x24 is not None else wavfile.read(cfg.wave_path)
+    write = audio.write_wav_s24 if x24 is not None else audio.write_wav
+    if x24 is None and data.ndim != 1:
         if cfg.long_feed != "contexts":                                            # the refusal of before, for the feed of before
             raise ValueError(f"{cfg.wave_path}: {data.shape[1]} channels -- `long: {{rate: file}}` with the default `feed: recording` resamples the "
                              f"whole file to feed the model and serves one channel; add `feed: contexts` to repair the channels in place, split "
                              f"the channels, or drop `rate: file` for the 22.05 kHz mix-down")
         return _main_long_file_channels(cfg, engine, save_dir, sr_file, data)
-    raw, sr_file = audio.read_wav(cfg.wave_path)
-    x = data if data.dtype == np.int16 else raw
+    raw = None
+    if x24 is None:
+        raw, sr_file = audio.read_wav(cfg.wave_path)
+    x = data if x24 is not None or data.dtype == np.int16 else raw
     P, Q = G.rate_ratio(sr_file)
     fade_ms = cfg.patch_fade_ms if cfg.patch_fade_ms is not None else 5.0
     clip_frames, min_context = int(round(cfg.long["clip_s"] * 50)), int(round(cfg.long["context_s"] * 50))
     if cfg.detect is not None:
         gap_list = _detect_gaps(cfg, engine, raw, sr_file, -(-len(x) * P // Q), -(-G.file_fade(fade_ms, sr_file) * P // Q), clip_frames, min_context,
-                                save_dir)
+                                save_dir, x24)
     else:
         gap_list = sorted(cfg.gaps) if cfg.gaps is not None else [(cfg.mask_pos, cfg.mask_frames)]
-    audio.write_wav(os.path.join(save_dir, "orig.wav"), x, sr_file)
+    write(os.path.join(save_dir, "orig.wav"), x, sr_file)
     masked = x.copy()
     for s, l in G.file_spans(gap_list, sr_file):
         masked[s:s + l] = 0                                                        # the file samples whose time lies in the gap's frames
-    audio.write_wav(os.path.join(save_dir, "masked.wav"), masked, sr_file)
+    write(os.path.join(save_dir, "masked.wav"), masked, sr_file)
     out = engine.patch_file(x, sr_file, gap_list, fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"],
                             feed=cfg.long_feed, **clips16_keywords(cfg))
     if clips16_keywords(cfg):
@@ -449,7 +465,7 @@ def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str)
     labels, off = out["labels"].tolist(), out["label_off"]
     for k, (pos, lm) in enumerate(gap_list):
         print(f"Predicted codewords, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[k]:off[k + 1]])
-    audio.write_wav(os.path.join(save_dir, "patched.wav"), out["patched"].cpu().numpy(), sr_file)
+    write(os.path.join(save_dir, "patched.wav"), out["patched"].cpu().numpy(), sr_file)
     print("wrote", save_dir)
     return 0
 
@@ -468,12 +484,15 @@ def _wav_samples(data: np.ndarray) -> np.ndarray:
 def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str, sr_file: int, data: np.ndarray) -> int:
     """`long: {rate: file}` on a multi-channel file (n, ch): the three files are written multi-channel, at the file's rate and in its
     sample type; gaps.json holds one list per channel for `detect: {channels: each}`.  The file is uploaded once; with `detect:` the
-    route is engine.conceal_file itself, otherwise engine.patch_file with the given gaps for every channel."""
+    route is engine.conceal_file itself, otherwise engine.patch_file with the given gaps for every channel.  data uint8 (n, ch, 3): the
+    packed bytes of a 24-bit file under `pcm24: keep`, kept as they are and written 24-bit."""
     from . import gaps as G
     ch = data.shape[1]
+    s24 = data.dtype == np.uint8 and data.ndim == 3
+    write = audio.write_wav_s24 if s24 else audio.write_wav
     if ch > G.MAX_CHANNELS:
         raise ValueError(f"{cfg.wave_path}: {ch} channels -- `long: {{rate: file}}` serves at most {G.MAX_CHANNELS}")
-    x = np.ascontiguousarray(_wav_samples(data))
+    x = np.ascontiguousarray(data if s24 else _wav_samples(data))
     fade_ms = cfg.patch_fade_ms if cfg.patch_fade_ms is not None else 5.0
     clip_frames, min_context = int(round(cfg.long["clip_s"] * 50)), int(round(cfg.long["context_s"] * 50))
     dev = torch.from_numpy(x).to(engine.device)                                    # the one upload: detection and repair read it
@@ -482,7 +501,7 @@ def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_
         print(f"16 kHz clips: clips16 = {cfg.long_clips16} (cut straight from the file, with the 22.05 kHz clips)")
     if cfg.detect is not None:                                                     # conceal_file: its own budget for a gap, its own fade
         d = cfg.detect
-        scale = 32768.0 if x.dtype == np.int16 else 1.0                             # an int16 file is scanned as the int16 it holds
+        scale = 8388608.0 if s24 else 32768.0 if x.dtype == np.int16 else 1.0       # an int16 / 24-bit file is scanned as the integers it holds
         joint = cfg.detect_channels == "joint"
         out = engine.conceal_file(dev, sr_file, d["threshold"] * scale, d["min_ms"], d["max_ms"], d["pad_frames"], detect=cfg.detect_channels,
                                   **dead_keywords(cfg.detect_dead, scale), **level_keywords(cfg), **kw)
@@ -501,17 +520,17 @@ def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_
     else:
         per = [sorted(cfg.gaps) if cfg.gaps is not None else [(cfg.mask_pos, cfg.mask_frames)]] * ch
         out = engine.patch_file(dev, sr_file, channel_gaps=per, **kw)
-    audio.write_wav(os.path.join(save_dir, "orig.wav"), x, sr_file)
+    write(os.path.join(save_dir, "orig.wav"), x, sr_file)
     masked = x.copy()
     for c in range(ch):
         for s, l in G.file_spans(per[c], sr_file):
             masked[s:s + l, c] = 0                                                 # the file samples whose time lies in the gap's frames
-    audio.write_wav(os.path.join(save_dir, "masked.wav"), masked, sr_file)
+    write(os.path.join(save_dir, "masked.wav"), masked, sr_file)
     labels, off, coff = out["labels"].tolist(), out["label_off"], out["channel_off"]
     for c in range(ch):
         for k, (pos, lm) in enumerate(sorted(per[c])):
             print(f"Predicted codewords, channel {c}, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[coff[c] + k]:off[coff[c] + k + 1]])
-    audio.write_wav(os.path.join(save_dir, "patched.wav"), out["patched"].cpu().numpy(), sr_file)
+    write(os.path.join(save_dir, "patched.wav"), out["patched"].cpu().numpy(), sr_file)
     print("wrote", save_dir)
     return 0
 
