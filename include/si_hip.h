@@ -35,6 +35,9 @@
  *                           samples, mutes relative to the file's peak.  It has no detection                I_ea/predict.py:85-90
  *   si_level_runs        <- nothing the reference computes either: si_dead_runs for a dropout that is a NOISE FLOOR (dither, a
  *                           concealer's comfort noise), found by windowed RMS level.  It has no detection     I_ea/predict.py:85-90
+ *   si_burst_runs        <- nothing the reference computes either: the detector for damage that is LOUDER than the speech -- a block
+ *                           of corrupted PCM (random data, swapped or misaligned bytes), found by the windowed level of the second
+ *                           difference.  It has no detection                                          I_ea/predict.py:85-90
  *   si_patch_rate        <- the same write-out for a file at ANY sample rate, which the script resamples on the way in and never
  *                           brings back                                       I_ea/predict.py:79-80,203-207
  *   si_cut_rate          <- that resampling on the way in, for the context clips alone instead of the whole file (with si_cut_clips'
@@ -582,7 +585,7 @@ int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_ta
                      float* out_f32, int16_t* out_pcm, si_stream_t stream);
 
 /* ---- The sample types of the file-typed calls -------------------------------------------------------------------------
- * The eleven calls that take a file as it lies on disk -- si_quiet_runs[_ch], si_dead_runs, si_level_runs, si_cut_rate[_ch],
+ * The twelve calls that take a file as it lies on disk -- si_quiet_runs[_ch], si_dead_runs, si_level_runs, si_burst_runs, si_cut_rate[_ch],
  * si_cut_pair[_ch], si_patch_rate[_ch] -- name its sample type in their `is_pcm16` argument.  Pass one of:
  *   SI_SAMPLE_F32 = 0   fp32
  *   SI_SAMPLE_S16 = 1   int16 PCM; a sample enters the cutters and the patch as (float)v / 32768, exact
@@ -591,7 +594,8 @@ int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_ta
  *                       x / orig / out point at the first byte and may start at ANY byte; no byte before the base or at / after
  *                       3 n ch is read.  `threshold` and `held_tol` count 24-bit steps, as they count int16 steps for int16
  *                       (rel_threshold, half, min_len are not scaled): |v| and the held difference (2^24 - 1 at most) are taken in
- *                       int32 and are exact in fp32, si_level_runs' squares (2^46 at most) in int64 and are exact in float64, and
+ *                       int32 and are exact in fp32, si_level_runs' squares (2^46 at most) in int64 and are exact in float64, si_burst_runs'
+ *                       second difference (below 2^26) in int32 and its square as a product of two doubles (below 2^52, exact), and
  *                       threshold_out receives T in 24-bit steps.  si_patch_rate[_ch] store a blend w as trunc(w * 8388608) clamped to
  *                       [-8388608, 8388607], NaN -> 0 (si_pcm16's statement at 24 bits), with stores of exactly the sample's three
  *                       bytes: no byte of a neighbouring sample or channel is written or rewritten.
@@ -847,6 +851,37 @@ int si_dead_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, 
  * SI_LEVEL_MAX_HALF; a threshold that is not finite. */
 #define SI_LEVEL_MAX_HALF 1024
 int si_level_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int half, float threshold, float rel_threshold,
+                  int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream);
+
+/* ---- Corrupted blocks by second-difference level ---------------------------------------------------------------------
+ * The reference has no detection (I_ea/predict.py:85-90).  si_quiet_runs, si_dead_runs and si_level_runs find damage that is QUIETER
+ * than the speech around it.  A block of corrupted PCM -- a sector of random data, byte-swapped or byte-misaligned samples, a burst of
+ * bit errors in the high bytes -- is louder: white noise at full scale.  This call judges the level of the SECOND DIFFERENCE over a
+ * window of 2 * half + 1 centres, a high-pass under which such a block has an RMS of sqrt(2) of full scale and speech stays below
+ * full scale.  Arguments, input layout, output rows, scratch and limits are si_level_runs'.  For one channel x[0 .. n) (elements
+ * k * channels + c), with h = half:
+ *   peak, T   si_dead_runs': T = max(threshold, fl32(rel_threshold * peak)); with rel_threshold == 0 the peak is not computed.
+ *   d(k)      for 1 <= k <= n - 2 ONLY: nothing in front of the base or at or past n is read.
+ *             int16, packed 24-bit: d = x[k - 1] - 2 x[k] + x[k + 1] in int32 from the integer sample values (|d| <= 131 070 for int16,
+ *             < 2^26 for 24-bit: no wrap), sq(k) = (double)d * (double)d, exact (below 2^34 / 2^52).  24-bit thresholds count 24-bit steps.
+ *             fp32: D = fl64(fl64((double)x[k - 1] + (double)x[k + 1]) - 2 * (double)x[k]), sq(k) = fl64(D * D): two roundings and one,
+ *             in this order, and NO contraction into a fused multiply-add anywhere in it.
+ *   bad(k)    any of x[k - 1], x[k], x[k + 1] is NaN or +-inf; its square counts as 0.  Counted with integers.
+ *   W(i)      [max(1, i - h), min(n - 2, i + h)], cnt(i) = |W(i)|, which may be 0 (i = 0 or n - 1 with h = 0; every i when n < 3).
+ *   E(i)      the sum of sq(k) over k in W(i), in float64, BY ADDITIONS ONLY (si_level_runs' rule and bound: within cnt * 2^-52 * E of
+ *             the exact sum).  Exact for int16 (E < 2^46), and for fp32 samples on a 2^-20 grid with |x| <= 1.
+ *   hot(i)    cnt(i) >= 1, no bad centre lies in W(i), and E(i) >= lim(i) = fl64(((double)T * (double)T) * cnt(i)).
+ *   dead(j)   hot(i) for some i with |i - j| <= h and 0 <= i < n: the union of the hot windows.
+ * channel >= 0 scans that channel: its neighbours are elements (k +- 1) * channels + channel, never the adjacent elements.  channel = -1
+ * is JOINT: a sample time is dead when every channel's dead_c holds, against one T.
+ * Consequences: with half = 0, hot(i) <=> |d(i)| >= T for 1 <= i <= n - 2; n < 3 gives zero runs; a window that holds a non-finite
+ * sample is never hot (a float file whose damage IS non-finite samples is not this call's).  With threshold = 0 and rel_threshold = 0
+ * every window with a centre is hot.
+ * The result is si_quiet_runs': sorted int32 (start, len) rows, rows [0, min(total, max_runs)) written, the total in n_runs, T in
+ * threshold_out when not NULL; the same input gives the same bytes (no atomics; plain stores).
+ * SI_EINVAL before any launch, naming the argument, for everything si_level_runs refuses, except that rel_threshold must lie in
+ * [0, 4] (|d| <= 4 * peak) and not be NaN. */
+int si_burst_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int half, float threshold, float rel_threshold,
                   int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */

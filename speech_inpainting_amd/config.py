@@ -76,8 +76,11 @@ class PredictConfig:
                                         # "held" (a sample repeated, a DC level) or "any"; rel_threshold a fraction of the file's peak in
                                         # [0, 1]; held_tol in full-scale units like threshold.  {quiet, 0.0, 0.0} is the detection of 4.15.
                                         # kind "level" (DESIGN.md 4.25): the RMS level of a window of `win_ms:` against the threshold
+                                        # kind "burst" (DESIGN.md 4.28): the second difference's RMS level over `win_ms:` AT OR ABOVE the
+                                        # threshold -- a block of corrupted PCM; rel_threshold in [0, 4] there; start from threshold: 1.15
     detect_level: Optional[dict] = None  # `win_ms:` inside `detect:` ({win_ms: 2.0}): the window of kind "level" in
-                                         # milliseconds, read at no other kind; None without `detect:`
+                                         # milliseconds, and of kind "burst" ({win_ms: 4.0} there), read at no other
+                                         # kind; None without `detect:`
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -204,25 +207,28 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             detect_dead = {"kind": "quiet", "rel_threshold": 0.0, "held_tol": 0.0}
             if "kind" in dm:
                 detect_dead["kind"] = dm.pop("kind")
-                if detect_dead["kind"] not in ("quiet", "held", "any", "level"):
+                if detect_dead["kind"] not in ("quiet", "held", "any", "level", "burst"):
                     raise ValueError(f"{path}: detect.kind = {detect_dead['kind']!r}: quiet (the default: |x| <= the threshold), held (a sample "
-                                     f"repeated, a DC level) or any, or level (the RMS level of a window of win_ms milliseconds <= the threshold)")
+                                     f"repeated, a DC level) or any, or level (the RMS level of a window of win_ms milliseconds <= the threshold), "
+                                     f"or burst (the RMS level of the second difference over a window of win_ms milliseconds >= the threshold)")
             for key in ("rel_threshold", "held_tol"):
                 if key in dm:
                     detect_dead[key] = float(dm.pop(key))
                     if not detect_dead[key] >= 0:
                         raise ValueError(f"{path}: detect.{key} = {detect_dead[key]} is negative")
-            if detect_dead["rel_threshold"] > 1:
-                raise ValueError(f"{path}: detect.rel_threshold = {detect_dead['rel_threshold']} is a fraction of the file's peak, at most 1")
-            detect_level = {"win_ms": 2.0}
+            burst = detect_dead["kind"] == "burst"                   # a second difference reaches 4 * the peak
+            if detect_dead["rel_threshold"] > (4 if burst else 1):
+                raise ValueError(f"{path}: detect.rel_threshold = {detect_dead['rel_threshold']} is a fraction of the file's peak, at most "
+                                 f"{'4 with `kind: burst`' if burst else 1}")
+            detect_level = {"win_ms": 4.0 if burst else 2.0}
             if "win_ms" in dm:
                 detect_level["win_ms"] = float(dm.pop("win_ms"))
-                if detect_dead["kind"] != "level":
+                if detect_dead["kind"] not in ("level", "burst"):
                     raise ValueError(f"{path}: detect.win_ms needs `kind: level` (kind: {detect_dead['kind']} judges sample by sample and has no window)")
                 if not 0 <= detect_level["win_ms"] < float("inf"):
                     raise ValueError(f"{path}: detect.win_ms = {detect_level['win_ms']} is negative or not finite")
-            if detect_dead["kind"] == "level" and detect_dead["held_tol"] != 0:
-                raise ValueError(f"{path}: detect.held_tol = {detect_dead['held_tol']} with `kind: level` (held samples are kind: held or any)")
+            if detect_dead["kind"] in ("level", "burst") and detect_dead["held_tol"] != 0:
+                raise ValueError(f"{path}: detect.held_tol = {detect_dead['held_tol']} with `kind: {detect_dead['kind']}` (held samples are kind: held or any)")
             if "channels" in dm:
                 detect_channels = dm.pop("channels")
                 if detect_channels not in ("each", "joint"):
@@ -233,7 +239,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             for key, val in dm.items():
                 if key not in detect_cfg:
                     raise ValueError(f"{path}: unknown key `{key}` in `detect:` (it takes threshold, min_ms, max_ms, pad_frames, channels, kind, rel_threshold, "
-                                     f"held_tol) and, with kind: level, win_ms")
+                                     f"held_tol) and, with kind: level, win_ms (kind: burst takes it too)")
                 detect_cfg[key] = int(val) if key == "pad_frames" else float(val)
                 if not detect_cfg[key] >= 0:
                     raise ValueError(f"{path}: detect.{key} = {detect_cfg[key]} is negative")

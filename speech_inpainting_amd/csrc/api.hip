@@ -1988,6 +1988,21 @@ int si_level_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels,
                                 threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
 }
 
+// ---- corrupted blocks by second-difference level
+int si_burst_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int half, float threshold, float rel_threshold,
+                  int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream) {
+    const char* fn = "si_burst_runs";
+    if (!ctx) return SI_EINVAL;
+    if (quiet_runs_check(ctx, fn, true, x, n, channels, channel, threshold, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
+    if (half < 0 || half > SI_LEVEL_MAX_HALF) return SI_FAIL_FN("half = %d samples, outside 0 .. SI_LEVEL_MAX_HALF = %d", half, SI_LEVEL_MAX_HALF);
+    if (__builtin_isinf(threshold)) return SI_FAIL_FN("threshold = %g is not finite", (double)threshold);
+    if (!(rel_threshold >= 0.f && rel_threshold <= 4.f)) return SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 4]", (double)rel_threshold);
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
+    return si_launch_burst_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, half, threshold, rel_threshold, min_len, runs, max_runs, n_runs,
+                                threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
+}
+
 #undef SI_FAIL_FN
 
 }  // extern "C"

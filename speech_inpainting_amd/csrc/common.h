@@ -391,6 +391,10 @@ int si_launch_dead_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels
 // most T^2 times their sample count, T = max(thr, rel * peak), dilated by half; channels and *thr_out as above
 int si_launch_level_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
                          int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
+// the maximal runs of samples under a window of LOUD second difference: the windows of 2 half + 1 centres, cut to
+// [1, n - 2], whose summed squares of x[k - 1] - 2 x[k] + x[k + 1] are at least T^2 times their centre count, dilated by half
+int si_launch_burst_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
+                         int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // repair at the file's own sample rate (rate_kernels.hip)

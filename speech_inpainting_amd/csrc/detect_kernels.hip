@@ -6,15 +6,14 @@
 //   detect_peak*_kernel, detect_dead*_kernel  pass 0 and another pass 1: the bit means DEAD -- quiet against a threshold
 //                          that follows the recording's peak, or held (equal to a neighbour) -- and the passes below do not care
 //   detect_level_kernel    a third pass 1: the bit means that a window of low RMS level reaches over the sample
+//   detect_burst_kernel    a fourth pass 1: the bit means that a window of LOUD second difference reaches over it
 //   detect_carry_kernel    carry[c] = the length of the quiet run that ends exactly in front of chunk c (a segmented scan, one workgroup)
 //   detect_runs_kernel     <false>: the qualifying runs that END in each chunk, counted; <true>: written at offset[c] + rank
 //   detect_offsets_kernel  the exclusive scan of the counts (one workgroup) and the total, a plain store
 // A run belongs to the chunk its LAST sample lies in, chunks are numbered along the recording and the ranks inside a chunk follow the
 // samples, so the rows come out sorted by construction: no atomics, no sort, and the same input gives the same bytes.
 #include "common.h"
-
-constexpr int DT_CHUNK = 2048;      // samples per workgroup: 256 threads x 8 consecutive samples (patch_kernels.hip's PC_CHUNK)
-constexpr int DT_TILE = 1024;       // chunks per tile of the two single-workgroup scans: 256 threads x 4 consecutive chunks
+#include "detect_sizes.h"           // DT_CHUNK, DT_TILE and the launcher's host arithmetic: chunks, the scratch layout, the LDS request
 
 struct DtMax { __device__ int operator()(int a, int b) const { return a > b ? a : b; } };
 struct DtMin { __device__ int operator()(int a, int b) const { return a < b ? a : b; } };
@@ -531,6 +530,32 @@ __device__ __forceinline__ void lv_square(float v, double& s, int& bad) {
 __device__ __forceinline__ void lv_square(int16_t v, double& s, int& bad) { const int a = v; s = (double)(a * a); bad = 0; }   // at most 2^30
 __device__ __forceinline__ void lv_square(SiS24 v, double& s, int& bad) { const long a = v.value(); s = (double)(a * a); bad = 0; }    // at most 2^46: int64, exact in float64
 
+// The square of the second difference d = a - 2 b + c of three consecutive samples of one channel, and whether any
+// of the three is NaN or +-inf (the square is then staged as 0).
+//   fp32: D = fl64(fl64((double)a + (double)c) - 2 (double)b), sq = fl64(D D): two roundings and one, in this order.  2 b is exact, so
+//         a fused multiply-subtract for the second step would round the same value once; contraction is switched off all the same, and
+//         the square goes to LDS before anything is added to it.
+//   PCM:  d in int32 (|d| <= 131 070 for int16, < 2^26 for 24-bit), the square of two exact doubles: below 2^34 / 2^52, exact.
+__device__ __forceinline__ void bu_square(float a, float b, float c, double& s, int& bad) {
+#pragma clang fp contract(off)
+    const bool finite = (__float_as_int(a) & 0x7fffffff) < 0x7f800000 && (__float_as_int(b) & 0x7fffffff) < 0x7f800000 &&
+                        (__float_as_int(c) & 0x7fffffff) < 0x7f800000;
+    const double sum = __dadd_rn((double)a, (double)c);
+    const double D = __dsub_rn(sum, 2.0 * (double)b);
+    s = finite ? __dmul_rn(D, D) : 0.0;
+    bad = finite ? 0 : 1;
+}
+__device__ __forceinline__ void bu_square(int16_t a, int16_t b, int16_t c, double& s, int& bad) {
+    const int d = (int)a - 2 * (int)b + (int)c;
+    s = (double)d * (double)d;
+    bad = 0;
+}
+__device__ __forceinline__ void bu_square(SiS24 a, SiS24 b, SiS24 c, double& s, int& bad) {
+    const int d = a.value() - 2 * b.value() + c.value();
+    s = (double)d * (double)d;
+    bad = 0;
+}
+
 // dst[p] = the sum of src over p's segment up to p (REV = false: from the segment's first element; true: from p to its last).  Segments
 // are [k L, (k + 1) L) cut at N.  Thread t walks `per` consecutive elements in scan order, the 256 partial sums are scanned with
 // shuffles and four wave totals (sw), then it walks them again with its carry.  src == dst is fine.  Every thread calls it.
@@ -588,10 +613,14 @@ __device__ __forceinline__ void lv_count_scan(int* a, int N, int per, int* sw) {
 // grid (chunks), 256 threads, dynamic LDS 20 N + 4 M bytes (N = DT_CHUNK + 4 h squares, M = DT_CHUNK + 2 h windows; 139 264 at h = 1024).
 // x is (n, ch) interleaved (ch = 1: one channel); channel >= 0 scans that channel, channel < 0 walks the channels one after another
 // through the same image and ANDs their bits.  Element offsets are 64-bit.  thr_dev, when given, holds T (pass 0); else T = thr.
-template <typename T>
-__global__ __launch_bounds__(256) void detect_level_kernel(const T* __restrict__ x, int n, int ch, int channel, int h, float thr,
-                                                           const float* __restrict__ thr_dev, float* __restrict__ thr_out,
-                                                           uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+// BURST = false is the level detector above.  BURST = true stages the square of the second difference instead --
+// centre k exists for 1 <= k <= n - 2 alone, its three samples x[k - 1], x[k], x[k + 1] come from global memory (neighbouring lanes,
+// neighbouring elements: the second and third are cache hits, and the image has no room for a copy of the samples at h = 1024), a
+// centre with a NaN or +-inf among the three is `bad` -- truncates the window to [1, n - 2], asks for cnt >= 1 and compares E >= lim.
+template <typename T, bool BURST>
+__device__ __forceinline__ void lv_window_body(const T* __restrict__ x, int n, int ch, int channel, int h, float thr,
+                                               const float* __restrict__ thr_dev, float* __restrict__ thr_out,
+                                               uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
     extern __shared__ __attribute__((aligned(16))) char lv_img[];
     __shared__ int sw[4];
     __shared__ LvSeg ssw[4];
@@ -614,7 +643,14 @@ __global__ __launch_bounds__(256) void detect_level_kernel(const T* __restrict__
             const long time = (long)c0 - 2 * h + p;
             double s = 0.0;
             int bd = 0;
-            if (time >= 0 && time < n) lv_square(x[(size_t)time * ch + col], s, bd);
+            if constexpr (BURST) {
+                if (time >= 1 && time + 1 < n) {
+                    const T* __restrict__ xk = x + (size_t)time * ch + col;
+                    bu_square(*(xk - ch), *xk, *(xk + ch), s, bd);
+                }
+            } else {
+                if (time >= 0 && time < n) lv_square(x[(size_t)time * ch + col], s, bd);
+            }
             P[p] = s;
             bad[p] = bd;
         }
@@ -628,9 +664,15 @@ __global__ __launch_bounds__(256) void detect_level_kernel(const T* __restrict__
             if (i >= 0 && i < n) {
                 const double E = q % L == 0 ? S[q] : S[q] + P[q + 2 * h];
                 const int nb = bad[q + 2 * h] - (q > 0 ? bad[q - 1] : 0);
-                const long a = i - h > 0 ? i - h : 0, z = i + h < n - 1 ? i + h : n - 1;
-                const double lim = __dmul_rn(T2, (double)(z - a + 1));
-                lo = (nb == 0 && E <= lim) ? 1 : 0;
+                if constexpr (BURST) {
+                    const long a = i - h > 1 ? i - h : 1, z = i + h < n - 2 ? i + h : n - 2;      // z - a + 1 <= 0: no centre in the window
+                    const double lim = __dmul_rn(T2, (double)(z - a + 1));
+                    lo = (nb == 0 && z >= a && E >= lim) ? 1 : 0;
+                } else {
+                    const long a = i - h > 0 ? i - h : 0, z = i + h < n - 1 ? i + h : n - 1;
+                    const double lim = __dmul_rn(T2, (double)(z - a + 1));
+                    lo = (nb == 0 && E <= lim) ? 1 : 0;
+                }
             }
             low[q] = lo;
         }
@@ -649,42 +691,63 @@ __global__ __launch_bounds__(256) void detect_level_kernel(const T* __restrict__
     dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
 }
 
-// ------------------------------------------------------------------------------------------------ launcher
-size_t si_detect_scratch_bytes(int n) {
-    const size_t chunks = ((size_t)n + DT_CHUNK - 1) / DT_CHUNK;
-    return chunks * 256 + 6 * ((chunks * sizeof(int32_t) + 15) & ~(size_t)15) + 16;     // + the peak's word per chunk and {peak, T}
+template <typename T>
+__global__ __launch_bounds__(256) void detect_level_kernel(const T* __restrict__ x, int n, int ch, int channel, int h, float thr,
+                                                           const float* __restrict__ thr_dev, float* __restrict__ thr_out,
+                                                           uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    lv_window_body<T, false>(x, n, ch, channel, h, thr, thr_dev, thr_out, bitmap, lead, trail);
 }
+
+// ------------------------------------------------------------------------------------------------ second-difference level
+// A fourth pass 1: sample j is DEAD when a window whose second difference d(k) = x[k - 1] - 2 x[k] + x[k + 1] is LOUD reaches over it --
+// a block of corrupted PCM (random data, swapped or misaligned bytes) is white at full scale, speech is not.  With h = half,
+//   E(i)    = the sum of d(k)^2 over k in W(i) = [max(1, i - h), min(n - 2, i + h)], float64, additions only; cnt(i) = |W(i)|, maybe 0
+//   hot(i)  = cnt(i) >= 1, no NaN or +-inf among the samples of W(i)'s differences, and E(i) >= fl64((T T) cnt(i))
+//   dead(j) = hot(i) for some i in [j - h, j + h] inside [0, n)
+// The image, the scans and the dilation are detect_level_kernel's (lv_window_body); a chunk reads samples [c0 - 2 h - 1, c0 + DT_CHUNK +
+// 2 h + 1) cut to [0, n).  Grid, threads and dynamic LDS are detect_level_kernel's too.
+template <typename T>
+__global__ __launch_bounds__(256) void detect_burst_kernel(const T* __restrict__ x, int n, int ch, int channel, int h, float thr,
+                                                           const float* __restrict__ thr_dev, float* __restrict__ thr_out,
+                                                           uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    lv_window_body<T, true>(x, n, ch, channel, h, thr, thr_dev, thr_out, bitmap, lead, trail);
+}
+
+// ------------------------------------------------------------------------------------------------ launcher
+size_t si_detect_scratch_bytes(int n) { return dt_scratch(n).bytes; }     // the bitmap, six words per chunk and {peak, T} (detect_sizes.h)
 
 // What si_dead_runs adds to a detection call; the quiet routes pass none.
 struct DtDead { int kind; float rel, tol; float* thr_out; };
 // What si_level_runs adds instead.
 struct DtLevel { int half; float rel; float* thr_out; };
+// What si_burst_runs adds instead: the same three, for detect_burst_kernel.
+struct DtBurst { int half; float rel; float* thr_out; };
 
 // The caller (si_quiet_runs, si_quiet_runs_ch) checked every argument.  scratch: si_detect_scratch_bytes(n) bytes, 16-byte aligned.
 // channels = 0: x is one channel of n samples (detect_bits_kernel); channels >= 1: x is interleaved, n sample times of `channels`
 // channels, and `channel` picks one of them or, below 0, all of them jointly (detect_bits_ch_kernel).  Passes 2 - 5 are the same launches.
 // dead != nullptr: pass 1 is detect_dead(_ch)_kernel, behind pass 0 when dead->rel > 0; nullptr: the launches above.
 // level != nullptr (dead is nullptr then): pass 1 is detect_level_kernel, behind the same pass 0 when level->rel > 0.
+// burst != nullptr (dead and level are nullptr then): pass 1 is detect_burst_kernel, behind the same pass 0 when burst->rel > 0.
 template <typename T>
 static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
-                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead, const DtLevel* level) {
-    const int chunks = (int)(((long)n + DT_CHUNK - 1) / DT_CHUNK);
-    const size_t words = ((size_t)chunks * sizeof(int32_t) + 15) & ~(size_t)15;
-    uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch);
-    char* p = scratch + (size_t)chunks * 256;
-    int32_t* lead = reinterpret_cast<int32_t*>(p);
-    int32_t* trail = reinterpret_cast<int32_t*>(p + words);
-    int32_t* carry = reinterpret_cast<int32_t*>(p + 2 * words);
-    int32_t* count = reinterpret_cast<int32_t*>(p + 3 * words);
-    int32_t* offset = reinterpret_cast<int32_t*>(p + 4 * words);
-    int32_t* cpeak = reinterpret_cast<int32_t*>(p + 5 * words);
-    float* pk = reinterpret_cast<float*>(p + 6 * words);              // {peak, T}
+                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead, const DtLevel* level, const DtBurst* burst) {
+    const int chunks = dt_chunks(n);
+    const DtScratch at = dt_scratch(n);
+    uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch + at.bitmap);
+    int32_t* lead = reinterpret_cast<int32_t*>(scratch + at.lead);
+    int32_t* trail = reinterpret_cast<int32_t*>(scratch + at.trail);
+    int32_t* carry = reinterpret_cast<int32_t*>(scratch + at.carry);
+    int32_t* count = reinterpret_cast<int32_t*>(scratch + at.count);
+    int32_t* offset = reinterpret_cast<int32_t*>(scratch + at.offset);
+    int32_t* cpeak = reinterpret_cast<int32_t*>(scratch + at.cpeak);
+    float* pk = reinterpret_cast<float*>(scratch + at.pk);            // {peak, T}
     const double bits = (double)chunks * 256.0, sums = (double)chunks * 4.0;
     const double samples = (double)n * (channels ? channels : 1) * (double)sizeof(T);
 
-    if (dead || level) {
+    if (dead || level || burst) {
         const float* thr_dev = nullptr;
-        const float rel = dead ? dead->rel : level->rel;
+        const float rel = dead ? dead->rel : level ? level->rel : burst->rel;
         if (rel > 0.f) {
             si_prof_begin(ctx, "detect_peak", 0.0, samples + sums, st);
             if (channels == 0) {
@@ -702,12 +765,20 @@ static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel
         }
         if (level) {
             const int h = level->half, ch = channels ? channels : 1;
-            const size_t lds = 20 * (size_t)(DT_CHUNK + 4 * h) + 4 * (size_t)(DT_CHUNK + 2 * h);   // 139 264 bytes at h = SI_LEVEL_MAX_HALF
+            const size_t lds = dt_window_lds(h);                      // 139 264 bytes at h = SI_LEVEL_MAX_HALF
             const void* kern = reinterpret_cast<const void*>(&detect_level_kernel<T>);
             if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
             // profiled in the family of the descriptor routes' pass 1, as both detect_dead kernels are: the lists of families are closed
             si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
             detect_level_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, channels ? channel : 0, h, thr, thr_dev, level->thr_out, bitmap, lead, trail);
+        } else if (burst) {
+            const int h = burst->half, ch = channels ? channels : 1;
+            const size_t lds = dt_window_lds(h);                      // detect_level_kernel's image
+            const void* kern = reinterpret_cast<const void*>(&detect_burst_kernel<T>);
+            if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
+            // the same family again: the lists of families are closed
+            si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
+            detect_burst_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, channels ? channel : 0, h, thr, thr_dev, burst->thr_out, bitmap, lead, trail);
         } else if (channels == 0) {
             si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
             detect_dead_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
@@ -754,10 +825,11 @@ static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel
 }
 
 static int dt_launch(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
-                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr, const DtLevel* level = nullptr) {
+                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr, const DtLevel* level = nullptr,
+                     const DtBurst* burst = nullptr) {
     int rc = SI_OK;
     si_with_sample(fmt, [&](auto tag) {
-        rc = dt_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st, dead, level);
+        rc = dt_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st, dead, level, burst);
     });
     return rc;
 }
@@ -785,4 +857,12 @@ int si_launch_level_runs(si_ctx* ctx, const void* x, int fmt, int n, int channel
     const DtLevel level{half, rel, thr_out};
     return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
                      &level);
+}
+
+// The second-difference level; channels = 1 is a one-channel file, as for si_launch_dead_runs.
+int si_launch_burst_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
+                         int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st) {
+    const DtBurst burst{half, rel, thr_out};
+    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
+                     nullptr, &burst);
 }

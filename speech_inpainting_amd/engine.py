@@ -971,7 +971,8 @@ class InpaintingEngine:
         EVERY channel is quiet and repairs those gaps in every channel (gaps, skipped: one list).  A one-channel file ignores it.
         kind, rel_threshold, held_tol: find_gaps' (DESIGN.md 4.20); held_tol in x's own units, like threshold.  Off their defaults the
         dictionary gains `threshold`, the effective one (one per channel for detect="each" on an interleaved file).
-        kind "level" with win_ms: find_gaps' (DESIGN.md 4.25), in the file's own samples like everything else here."""
+        kind "level" with win_ms: find_gaps' (DESIGN.md 4.25), in the file's own samples like everything else here.
+        kind "burst" with win_ms: find_gaps' (DESIGN.md 4.28), likewise: threshold = 1.15 of full scale and win_ms = 4.0 to start from."""
         sr, clip_frames, min_context = int(sr), int(clip_frames), int(min_context)
         if detect not in ("each", "joint"):
             raise ValueError(f"conceal_file: detect = {detect!r}: 'each' or 'joint'")
@@ -993,7 +994,7 @@ class InpaintingEngine:
             max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
         fade22 = -(-G.file_fade(fade_ms, sr) * P // Q)
         find = lambda c: self.find_gaps(x, sr, threshold, min_ms, max_ms, pad_frames, merge_frames, fade22, n_rec, lim, channel=c, kind=kind,
-                                        rel_threshold=rel_threshold, held_tol=held_tol, **({"win_ms": win_ms} if kind == "level" else {}))
+                                        rel_threshold=rel_threshold, held_tol=held_tol, **({"win_ms": win_ms} if kind in ("level", "burst") else {}))
         kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed)
         if clips16 != "resampled":                                     # the default: patch_file is called as it was
             kw["clips16"] = clips16
@@ -1103,6 +1104,43 @@ class InpaintingEngine:
         runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
         return (runs, T) if return_threshold else runs
 
+    def find_burst_runs(self, x, win: Optional[int] = None, half: Optional[int] = None, threshold: float = 0.0, rel_threshold: float = 0.0,
+                        min_len: int = 1, max_runs: int = 65536, channel: Optional[int] = None, return_threshold: bool = False):
+        """find_level_runs for damage that is LOUDER than the speech (si_burst_runs): a block of corrupted PCM --
+        random data, swapped or misaligned bytes.  A sample is dead when a window of 2 * half + 1 second differences x[k - 1] -
+        2 x[k] + x[k + 1] of its channel that reaches over it has an RMS level of at least T = max(threshold, rel_threshold * the peak
+        of x), and no NaN or inf under it.  The window, x, channel, min_len, max_runs, threshold and the rows are find_level_runs';
+        rel_threshold lies in [0, 4] (|d| <= 4 * peak).  T = 0 makes every window hot and is the caller's to refuse (find_gaps does).
+        One D2H copy: the count, which with return_threshold=True also carries T; -> runs, or (runs, T)."""
+        if (win is None) == (half is None):
+            raise ValueError("find_burst_runs: give the window as win = its odd length in samples, or as half = (win - 1) / 2, not both")
+        if win is not None:
+            if int(win) != win or int(win) < 1 or int(win) % 2 == 0:
+                raise ValueError(f"find_burst_runs: win = {win}: an odd number of samples, 2 * half + 1")
+            half = (int(win) - 1) // 2
+        if int(half) != half or not 0 <= int(half) <= G.LEVEL_MAX_HALF:
+            raise ValueError(f"find_burst_runs: half = {half} samples, outside 0 .. {G.LEVEL_MAX_HALF}")
+        if not 0.0 <= float(rel_threshold) <= 4.0:
+            raise ValueError(f"find_burst_runs: rel_threshold = {rel_threshold} is NaN or outside [0, 4] (a second difference is at most 4 * the peak)")
+        x = torch.as_tensor(x)
+        s24, sdim = InpaintingEngine._file_samples(x, "find_burst_runs")                      # packed 24-bit PCM: uint8 (n, 3) or (n, ch, 3), 24-bit steps
+        many = sdim == 2 and x.shape[1] >= 2
+        if many and channel is None:
+            raise ValueError(f"find_burst_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
+        if not many and channel is not None and int(channel) not in (-1, 0):
+            raise ValueError(f"find_burst_runs: channel = {channel} of a one-channel recording")
+        x = InpaintingEngine._file_on_device(x, self.device)
+        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
+        words = torch.zeros(2, dtype=torch.int32, device=self.device)      # {the count, T's bits}: one copy brings both
+        runs, _ = self.ctx.burst_runs(x, int(half), threshold, rel_threshold, min_len, max_runs, n_runs=words[:1],
+                                      channel=int(channel) if many else None, threshold_out=words[1:].view(torch.float32))
+        host = words.cpu()
+        total, T = int(host[0]), float(host[1:].view(torch.float32)[0])
+        if total > int(max_runs):
+            raise ValueError(f"find_burst_runs: {total} runs of at least {int(min_len)} dead samples, more than max_runs = {int(max_runs)}")
+        runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+        return (runs, T) if return_threshold else runs
+
     def recording_frames(self, n22: int, clip_frames: int = 200, n16: Optional[int] = None) -> Tuple[int, int]:
         """(n_rec_frames, lim_frames) of a recording of n22 samples at 22.05 kHz as patch_recording serves it: its 20 ms frames and
         the usable ones [0, lim) -- a context clip's min(T, Tm) (patch_recording's own arithmetic, n16 = the samples of a supplied
@@ -1130,7 +1168,11 @@ class InpaintingEngine:
         launches; anything else goes to find_dead_runs, and the dictionary gains `threshold`: the effective one, T.
         kind "level" (DESIGN.md 4.25): the runs are find_level_runs' -- the RMS level of a window of win_ms milliseconds, half =
         round(win_ms * sr / 2000) samples on each side, against the threshold -- and the dictionary carries `threshold` as well.
-        held_tol has no meaning there and must be 0; win_ms is read at no other kind."""
+        held_tol has no meaning there and must be 0.
+        kind "burst" (DESIGN.md 4.28): the runs are find_burst_runs' -- a block of corrupted PCM, LOUDER than the speech: the RMS level of
+        the second difference over a window of win_ms milliseconds at or above the threshold.  rel_threshold may reach 4 there, held_tol
+        must be 0, and T = 0 (both thresholds 0) is refused: start from 1.15 of full scale with win_ms = 4.0.  `threshold` is carried
+        as well.  win_ms is read at no other kind."""
         x = torch.as_tensor(x)
         s24, sdim = InpaintingEngine._file_samples(x, "find_gaps")                 # packed 24-bit PCM (DESIGN.md 4.27): thresholds in 24-bit steps
         n, sr = (x.shape[0] if sdim == 2 or s24 else x.numel()), int(sr)
@@ -1141,6 +1183,17 @@ class InpaintingEngine:
             if float(held_tol) != 0.0:
                 raise ValueError(f"find_gaps: held_tol = {held_tol} with kind = 'level' (held samples are kind 'held' or 'any')")
             runs, T = self.find_level_runs(x, half=G.level_half(win_ms, sr), threshold=threshold, rel_threshold=rel_threshold, min_len=min_len,
+                                           channel=channel, return_threshold=True)
+        elif kind == "burst":
+            if float(held_tol) != 0.0:
+                raise ValueError(f"find_gaps: held_tol = {held_tol} with kind = 'burst' (held samples are kind 'held' or 'any')")
+            if not 0.0 <= float(rel_threshold) <= 4.0:
+                raise ValueError(f"find_gaps: rel_threshold = {rel_threshold} with kind = 'burst' is NaN or outside [0, 4] (a second difference "
+                                 f"is at most 4 * the peak)")
+            if float(threshold) == 0.0 and float(rel_threshold) == 0.0:
+                raise ValueError("find_gaps: kind = 'burst' with threshold = 0 and rel_threshold = 0 is T = 0: every window would be hot.  "
+                                 "Start from threshold = 1.15 of full scale (1.15 * 32768 for int16, 1.15 * 2^23 for 24-bit) with win_ms = 4.0")
+            runs, T = self.find_burst_runs(x, half=G.level_half(win_ms, sr), threshold=threshold, rel_threshold=rel_threshold, min_len=min_len,
                                            channel=channel, return_threshold=True)
         elif kind == "quiet" and float(rel_threshold) == 0.0 and float(held_tol) == 0.0:
             runs = self.find_quiet_runs(x, threshold, min_len, channel=channel)
@@ -1161,6 +1214,7 @@ class InpaintingEngine:
         clip_frames - 2 * min_context counts as long whatever max_ms says.
         kind, rel_threshold, held_tol: find_gaps' (held samples, a threshold relative to the peak).
         kind "level" with win_ms: find_gaps' too (a noise-floor dropout, by windowed RMS level).
+        kind "burst" with win_ms: find_gaps' too (a block of corrupted PCM, by second-difference level).
         -> patch_recording's dictionary + gaps + skipped [+ threshold].  With nothing found: an exact copy; only the detection kernels launched."""
         as1d = lambda x: torch.as_tensor(x).to(self.device, torch.float32).reshape(-1).contiguous()
         wave22 = as1d(wave22)
@@ -1171,7 +1225,7 @@ class InpaintingEngine:
             max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
         found = self.find_gaps(wave22 if detect_on is None else detect_on, 22050 if detect_on is None else sr, threshold, min_ms, max_ms,
                                pad_frames, merge_frames, fade, n_rec, lim, kind=kind, rel_threshold=rel_threshold, held_tol=held_tol,
-                               **({"win_ms": win_ms} if kind == "level" else {}))
+                               **({"win_ms": win_ms} if kind in ("level", "burst") else {}))
         out = self.patch_recording(wave22, found["gaps"], wave16=wave16, fade=fade, clip_frames=clip_frames, min_context=min_context,
                                    batch=batch, pcm=pcm)
         out["gaps"], out["skipped"] = found["gaps"], found["skipped"]

@@ -32,7 +32,7 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
            "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate",
            "si_quiet_runs_ch", "si_cut_rate_ch", "si_patch_rate_ch", "si_dead_runs", "si_level_runs", "si_cut_pair", "si_cut_pair_ch",
-           "si_plan_weights", "si_pack_weights_host"]
+           "si_plan_weights", "si_pack_weights_host", "si_burst_runs"]
 SI_MAX_SPANS = 16
 SI_MAX_CHANNELS = 8                        # channels of an interleaved file
 SAMPLE_F32, SAMPLE_S16, SAMPLE_S24 = 0, 1, 2   # SI_SAMPLE_*: the file-typed calls' sample types; s24 = uint8 (..., 3)
@@ -378,6 +378,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_patch_rate_ch.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(RateTableStruct), vp, i32, vp, C.POINTER(SincFilter), vp, vp]
     lib.si_dead_runs.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp]
     lib.si_level_runs.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp]
+    lib.si_burst_runs.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp]
     lib.si_cut_pair.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(SincFilter), C.POINTER(SincFilter), vp, vp, vp]
     lib.si_cut_pair_ch.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(SincFilter), C.POINTER(SincFilter), vp, vp, vp]
     lib.si_plan_weights.argtypes = [C.POINTER(ModelDesc), C.POINTER(sz)]
@@ -882,6 +883,28 @@ class NativeContext:
                                            int(channel) if channel is not None else 0, int(half), float(threshold), float(rel_threshold),
                                            int(min_len), _ptr(runs), max_runs, _ptr(n_runs), _ptr(threshold_out), self._stream()),
                     "si_level_runs")
+        return runs, n_runs
+
+    # ---- corrupted blocks by second-difference level
+    def burst_runs(self, x: torch.Tensor, half: int = 0, threshold: float = 0.0, rel_threshold: float = 0.0, min_len: int = 1,
+                   max_runs: int = 65536, runs: Optional[torch.Tensor] = None, n_runs: Optional[torch.Tensor] = None,
+                   channel: Optional[int] = None, threshold_out: Optional[torch.Tensor] = None):
+        """level_runs with si_burst_runs' predicate: a sample is dead when a window of 2 * half + 1 second differences x[k - 1] -
+        2 x[k] + x[k + 1] of its channel within half samples of it has an RMS level of AT LEAST T = max(threshold, rel_threshold *
+        peak) and no NaN or inf under it.  x, channel, runs, n_runs and threshold_out are dead_runs'; -> (runs, n_runs)."""
+        n, ch = self._interleaved(x, channel)
+        max_runs = int(max_runs)
+        if runs is None and max_runs > 0:
+            runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
+        if n_runs is None:
+            n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
+        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
+        assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
+        assert threshold_out is None or (threshold_out.is_cuda and threshold_out.dtype == torch.float32 and threshold_out.numel() == 1)
+        self._check(self.lib.si_burst_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
+                                           int(channel) if channel is not None else 0, int(half), float(threshold), float(rel_threshold),
+                                           int(min_len), _ptr(runs), max_runs, _ptr(n_runs), _ptr(threshold_out), self._stream()),
+                    "si_burst_runs")
         return runs, n_runs
 
     @staticmethod

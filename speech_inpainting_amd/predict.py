@@ -21,7 +21,10 @@ repeat a neighbour, as an underrun or a DC level leaves them; any), `rel_thresho
 threshold is max(threshold, rel_threshold * peak)) and `held_tol:` (full scale, like threshold); off their defaults the effective
 threshold is printed and gaps.json records `kind` and `T` (engine.find_dead_runs).  `kind: level` with `win_ms:` (2 by
 default) finds a dropout that is a noise floor -- dither, a concealer's comfort noise -- by the RMS level of a window of win_ms
-milliseconds against the threshold, and gaps.json records `kind`, `T` and `win_ms` (engine.find_level_runs).  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
+milliseconds against the threshold, and gaps.json records `kind`, `T` and `win_ms` (engine.find_level_runs).  `kind: burst`
+finds damage that is LOUDER than the speech -- a block of corrupted PCM: random data, swapped or misaligned bytes -- by the RMS level of the
+second difference over a window of `win_ms:` (4 by default at this kind) at or above `threshold:`; start from `threshold: 1.15` of full
+scale, and a threshold of 0 is refused (engine.find_burst_runs).  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
 on the way out: the three waves keep the file's own rate and sample type (an int16 file stays int16), and patched.wav holds the file's
 own samples, bit for bit, outside the cross-fades (engine.patch_file).
 With `feed: contexts` beside `rate: file` the recording is not resampled as a whole on the way in either: only the context clips
@@ -392,7 +395,7 @@ def level_keywords(cfg) -> dict:
     """`detect:`'s win_ms as find_gaps and conceal_file take it: given with `kind: level` alone, so that every other
     kind is called as it was.  win_ms is a time and, like rel_threshold, is not scaled for an int16 file."""
     dead, level = getattr(cfg, "detect_dead", None), getattr(cfg, "detect_level", None)
-    if dead is None or dead["kind"] != "level":
+    if dead is None or dead["kind"] not in ("level", "burst"):                     # kind burst (DESIGN.md 4.28) has level's window key
         return {}
     return {"win_ms": level["win_ms"] if level is not None else 2.0}
 

@@ -16,8 +16,13 @@ warm-up, device-synchronised wall clock per call:
       12 int16 steps (si_level_runs: pass 1 with the windowed energy, the four scan passes), and (j) its torch
       formulation: avg_pool1d of the float64 squares (count_include_pad=False: the truncated count) against T^2, max_pool1d of the
       mask, then (b)'s run extraction
+  (k) engine.find_burst_runs(half=44, threshold=1.15 of full scale) on the same recording with its gaps filled by seeded full-scale
+      GARBAGE, uniformly random int16 (si_burst_runs: pass 1 with the windowed energy of the second difference, the four
+      scan passes), and (l) its torch formulation: the float64 squares of x[k-1] - 2 x[k] + x[k+1] for 1 <= k <= n - 2, avg_pool1d of
+      them and of the centres' indicator (times the window: the sum and the truncated count) against T^2, max_pool1d of the mask, then
+      (b)'s run extraction
 
-Prints whether (a) equals (b), (e) equals (f), (g) equals (h), (i) equals (j) and (c) equals (d) bit for bit, one line per repeat, the medians, and -- from a separate, untimed run
+Prints whether (a) equals (b), (e) equals (f), (g) equals (h), (i) equals (j), (k) equals (l) and (c) equals (d) bit for bit, one line per repeat, the medians, and -- from a separate, untimed run
 under the library's profiler -- the per-kernel times of the detect_* family and the effective bytes per second of the whole call
 (the recording's bytes / the family's summed time).
 usage: python tools/exp_detect.py [--repeats 7] [--minutes 10] [--gaps 60] [--pcm16]"""
@@ -114,12 +119,39 @@ def torch_level():
     return torch.stack([start[keep], (end - start)[keep]], dim=1).to(torch.int32)
 
 
+# the same recording with every gap filled by full-scale garbage: uniformly random int16, seeded (values on the 2^-15 grid in fp32)
+BURST_HALF, BURST_T = 44, 1.15
+garb22 = wave22.clone()
+for p, l in gaps:
+    garb22[441 * p:441 * (p + l)] = torch.randint(-32768, 32768, (441 * l,), generator=gen).to(dev) / 32768.0
+xb = eng.to_int16(garb22) if a.pcm16 else garb22
+burst_thr = BURST_T * 32768.0 if a.pcm16 else BURST_T
+
+
+def torch_burst():
+    v = xb.to(torch.float64)
+    n, L = v.numel(), 2 * BURST_HALF + 1
+    sq, centre = v.new_zeros(n), v.new_zeros(n)
+    sq[1:n - 1] = (v[:-2] - 2 * v[1:-1] + v[2:]).square()
+    centre[1:n - 1] = 1
+    pool = lambda t: torch.nn.functional.avg_pool1d(t[None, None], L, 1, BURST_HALF, count_include_pad=True) * L
+    T = float(torch.tensor(burst_thr, dtype=torch.float32))
+    E, cnt = pool(sq), pool(centre).round()
+    hot = ((cnt >= 1) & (E >= T * T * cnt)).to(torch.float32)
+    q = (torch.nn.functional.max_pool1d(hot, L, 1, BURST_HALF)[0, 0] > 0).to(torch.int8)
+    d = torch.diff(q, prepend=q.new_zeros(1), append=q.new_zeros(1))
+    start, end = torch.nonzero(d == 1).flatten(), torch.nonzero(d == -1).flatten()
+    keep = end - start >= MIN_LEN
+    return torch.stack([start[keep], (end - start)[keep]], dim=1).to(torch.int32)
+
+
 variants = {"a": lambda: eng.find_quiet_runs(x, 0.0, MIN_LEN), "b": torch_runs,
             "c": lambda: eng.conceal_recording(wave22, **KW), "d": lambda: eng.patch_recording(wave22, gaps, **KW),
             "e": lambda: eng.find_dead_runs(xh, "held", min_len=MIN_LEN), "f": lambda: torch_dead(0.0),
             "g": lambda: eng.find_dead_runs(xh, "any", rel_threshold=1e-3, min_len=MIN_LEN), "h": lambda: torch_dead(1e-3),
-            "i": lambda: eng.find_level_runs(xn, half=LEVEL_HALF, threshold=level_thr, min_len=MIN_LEN), "j": torch_level}
-oa, ob, oc, od, oe, of, og, oh, oi, oj = (fn() for fn in variants.values())
+            "i": lambda: eng.find_level_runs(xn, half=LEVEL_HALF, threshold=level_thr, min_len=MIN_LEN), "j": torch_level,
+            "k": lambda: eng.find_burst_runs(xb, half=BURST_HALF, threshold=burst_thr, min_len=MIN_LEN), "l": torch_burst}
+oa, ob, oc, od, oe, of, og, oh, oi, oj, ok, ol = (fn() for fn in variants.values())
 torch.cuda.synchronize()
 print(f"recording of {N22} samples ({N22 / 22050 / 60:.2f} min, {x.element_size()} bytes per sample), {len(gaps)} gaps of {LM} frames zeroed")
 print(f"(a) equals (b): {torch.equal(oa, ob)} ({oa.shape[0]} runs);  (c) found the gaps: {oc['gaps'] == gaps};  (c) equals (d) bit for bit: fp32",
@@ -128,7 +160,11 @@ print(f"(e) equals (f): {torch.equal(oe, of)} ({oe.shape[0]} runs, {int((oe[:, 1
       f"(g) equals (h): {torch.equal(og, oh)} ({og.shape[0]} runs)")
 print(f"(i) equals (j): {torch.equal(oi, oj)} ({oi.shape[0]} runs, {sum(1 for r in oi.tolist() if r in [[441 * p, 441 * l] for p, l in gaps])} of them exactly a gap;  "
       f"the sample-wise detector at the same threshold finds {eng.find_quiet_runs(xn, level_thr, MIN_LEN).shape[0]} runs)")
-del oa, ob, oc, od, oe, of, og, oh, oi, oj
+covered = sum(1 for p, l in gaps if any(r[0] <= 441 * p and r[0] + r[1] >= 441 * (p + l) for r in ok.tolist()))
+print(f"(k) equals (l): {torch.equal(ok, ol)} ({ok.shape[0]} runs, {covered} of {len(gaps)} gaps inside one of them;  quiet, held and level detection on that "
+      f"file find {eng.find_quiet_runs(xb, 0.0, MIN_LEN).shape[0]}, {eng.find_dead_runs(xb, 'held', min_len=MIN_LEN).shape[0]} and "
+      f"{eng.find_level_runs(xb, half=LEVEL_HALF, threshold=level_thr, min_len=MIN_LEN).shape[0]} runs)")
+del oa, ob, oc, od, oe, of, og, oh, oi, oj, ok, ol
 for fn in variants.values():
     for _ in range(WARMUP):
         fn()
@@ -145,7 +181,7 @@ for r in range(a.repeats):
 med = {k: statistics.median(v) for k, v in ms.items()}
 print("median ms/recording: " + "  ".join(f"({k}) {med[k]:.3f}" for k in variants))
 print(f"spread of (d) over {a.repeats} repeats: {max(ms['d']) - min(ms['d']):.3f} ms;  (c) - (d) {med['c'] - med['d']:+.3f} ms;  (a) / (b) {med['a'] / med['b']:.3f};  "
-      f"(e) / (f) {med['e'] / med['f']:.3f};  (g) / (h) {med['g'] / med['h']:.3f};  (e) / (a) {med['e'] / med['a']:.3f};  (g) / (a) {med['g'] / med['a']:.3f};  (i) / (j) {med['i'] / med['j']:.3f};  (i) / (a) {med['i'] / med['a']:.3f}")
+      f"(e) / (f) {med['e'] / med['f']:.3f};  (g) / (h) {med['g'] / med['h']:.3f};  (e) / (a) {med['e'] / med['a']:.3f};  (g) / (a) {med['g'] / med['a']:.3f};  (i) / (j) {med['i'] / med['j']:.3f};  (i) / (a) {med['i'] / med['a']:.3f};  (k) / (l) {med['k'] / med['l']:.3f};  (k) / (i) {med['k'] / med['i']:.3f}")
 # per-kernel device times, from a run of their own under the library's event profiler (every launch bracketed: not a step time)
 eng.ctx.profile_start(1000)
 for _ in range(10):
@@ -176,3 +212,9 @@ for half in (0, 110, 1024):
         eng.find_level_runs(xn, half=half, threshold=level_thr, min_len=MIN_LEN)
     e = {e["name"]: e for e in eng.ctx.profile_stop()}["detect_dead"]             # the level kernel is profiled in pass 1's family
     print(f"detect_level_kernel at half={half}: {e['ms'] / e['launches'] * 1e3:.1f} us")
+for half in (0, 44, 1024):
+    eng.ctx.profile_start(1000)
+    for _ in range(10):
+        eng.find_burst_runs(xb, half=half, threshold=burst_thr, min_len=MIN_LEN)
+    e = {e["name"]: e for e in eng.ctx.profile_stop()}["detect_dead"]             # the burst kernel is profiled in pass 1's family too
+    print(f"detect_burst_kernel at half={half}: {e['ms'] / e['launches'] * 1e3:.1f} us")
