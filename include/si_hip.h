@@ -967,6 +967,27 @@ int si_profile_stop(si_ctx* ctx, si_profile_entry* out, int capacity, int* count
 int si_debug_capture(si_ctx* ctx, const char* name, float* dst, long capacity);
 long si_debug_size(si_ctx* ctx, const char* name);
 
+/* Test hook: where a pass writes.  The encoder, the generator and the mel front-end carve their caller-owned workspace into named
+ * regions, in order, at 256-aligned offsets.  si_debug_ws_regions returns the regions of that pass's most recent call on this context
+ * (`which`: SI_WS_ENCODER, SI_WS_VOCODER, SI_WS_MEL): name, offset from the workspace pointer of that call, and the bytes the pass
+ * asked for -- the only bytes of the workspace it may write.  *count receives the number of regions (at most SI_WS_MAX_REGIONS; 0
+ * before the first call), of which the first min(count, capacity) are stored.  Host bookkeeping only: no allocation, no device work.
+ * SI_WS_REDZONE=<bytes> in the environment of si_create (a test switch; rounded down to a multiple of 256, at most 1 MiB, default 0)
+ * makes the carve leave that many bytes in front of the first region and behind every region, the last included; the library never
+ * writes them, and si_workspace_bytes / si_mel_workspace_bytes grow by that size times a fixed count per pass.  Unset, every offset
+ * and every size is what it is without the switch.  A test fills the workspace, runs the pass and finds every byte outside
+ * [offset, offset + bytes) of the regions as it left it. */
+#define SI_WS_ENCODER 0
+#define SI_WS_VOCODER 1
+#define SI_WS_MEL 2
+#define SI_WS_MAX_REGIONS 32
+typedef struct si_ws_region {
+    char name[24];
+    uint64_t offset;
+    uint64_t bytes;
+} si_ws_region;
+int si_debug_ws_regions(si_ctx* ctx, int which, si_ws_region* out, int capacity, int* count);
+
 #ifdef __cplusplus
 }
 #endif

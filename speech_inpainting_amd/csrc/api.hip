@@ -66,6 +66,12 @@ struct si_ctx {
     int km_cnorm_cap = 0;
     char* det_scratch = nullptr;             // bitmap + per-chunk words of si_quiet_runs (library-owned, stream-ordered reuse, grown on demand)
     size_t det_scratch_cap = 0;
+    // test switch SI_WS_REDZONE: bytes the carve leaves untouched around every region, and the regions of each
+    // pass's most recent carve (si_debug_ws_regions); fixed arrays, written on the host at carve time
+    size_t ws_zone = 0;
+    struct WsRegion { const char* name; size_t offset, bytes; };      // (the name is the carve call's literal)
+    struct WsLog { int n = 0; WsRegion r[SI_WS_MAX_REGIONS]; };
+    WsLog ws_log[3];                         // SI_WS_ENCODER, SI_WS_VOCODER, SI_WS_MEL
 };
 
 int si_fail(si_ctx* ctx, int code, const char* fmt, ...) {
@@ -177,15 +183,27 @@ Err ctx_err(si_ctx* ctx) { return ctx ? Err{ctx->err, sizeof(ctx->err)} : Err{g_
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The regions of one pass, carved in order from the caller's workspace at 256-aligned offsets.  zone > 0 (SI_WS_REDZONE): `zone` bytes
+// that nothing is handed out of lie in front of the first region and behind every region, the last one included.  Every region is
+// recorded by name in the pass's log; one more than the log holds fails the carve like one past the estimate.
 struct Carver {
-    char* base; size_t cap; size_t cur = 0; bool ok = true;
-    float* floats(size_t n) { return reinterpret_cast<float*>(bytes(n * 4)); }
-    char* bytes(size_t n) {
-        size_t o = cur; cur = align_up(cur + n, 256);
-        if (cur > cap) { ok = false; return base; }
+    char* base; size_t cap; size_t zone; si_ctx::WsLog* log; size_t cur; bool ok = true;
+    const char* failed = "";                 // the first region that did not fit (for the refusal's message)
+    float* floats(size_t n, const char* name) { return reinterpret_cast<float*>(bytes(n * 4, name)); }
+    char* bytes(size_t n, const char* name) {
+        size_t o = cur; cur = align_up(cur + n, 256) + zone;
+        if (cur > cap || log->n >= SI_WS_MAX_REGIONS) { if (ok) failed = name; ok = false; return base; }
+        log->r[log->n++] = {name, o, n};
         return base + o;
     }
 };
+Carver carver(si_ctx* ctx, int which, void* workspace, size_t workspace_bytes) {
+    ctx->ws_log[which].n = 0;
+    return Carver{static_cast<char*>(workspace), workspace_bytes, ctx->ws_zone, &ctx->ws_log[which], ctx->ws_zone};
+}
+// zones the estimates pay for: one in front, one behind each region a pass can carve (encoder: the length table or the frame
+// counts, never both; generator: table, mel, 6 + 6 buffers; mel: 3 + table)
+constexpr int ENC_WS_ZONES = 18, VOC_WS_ZONES = 15, MEL_WS_ZONES = 5;
 
 // Ragged batches: the per-clip length table of the call in progress.  `fill` writes its `ints` zeroed entries on the host and returns
 // an error code for a length it refuses; the table is then carved from the `what` workspace and uploaded in stream order.
@@ -194,8 +212,8 @@ template <class Fill>
 int vl_table(si_ctx* ctx, Carver& W, size_t ints, hipStream_t st, const char* what, VlTable& t, Fill fill) {
     ctx->vl_host.assign(ints, 0);
     if (int rc = fill(ctx->vl_host.data())) return rc;
-    t.dev = reinterpret_cast<int32_t*>(W.bytes(ints * 4));
-    if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: %s workspace carve exceeded its own estimate", what);
+    t.dev = reinterpret_cast<int32_t*>(W.bytes(ints * 4, "lengths"));
+    if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: %s workspace carve exceeded its own estimate at region '%s'", what, W.failed);
     if (int rc = vl_upload(ctx, t.dev, st)) return rc;
     t.host = ctx->vl_host.data();
     return SI_OK;
@@ -210,7 +228,8 @@ EncDims enc_dims(const si_model_desc& d, int N) {
     return e;
 }
 
-size_t encoder_ws_bytes(const si_model_desc& d, int B, int N) {
+size_t encoder_ws_bytes(const si_ctx* ctx, int B, int N) {
+    const si_model_desc& d = ctx->d;
     EncDims e = enc_dims(d, N);
     size_t cmax = 0;
     for (int i = 0; i < d.num_conv; ++i) cmax = std::max(cmax, (size_t)e.L[i + 1] * d.conv_dim[i]);
@@ -220,7 +239,8 @@ size_t encoder_ws_bytes(const si_model_desc& d, int B, int N) {
     // bf16 operand-ready copies (encoder in bf16 mode): LN(features), hidden, attention output, FFN intermediate
     const size_t h16 = (BT * d.conv_dim[d.num_conv - 1] + 2 * BT * d.hidden_size + BT * (d.intermediate_size + 128)) * 2;   // (+ the row padding of the FFN intermediate)
     return f * 4 + h16 + (size_t)B * 16 + (size_t)B * 4 + si_conv0_partials_bytes(B, N) + 41 * 256 +
-           align_up((size_t)(SI_MAX_CONV + 3) * (B + 1) * 4, 256);    // ragged batches: per-layer length table + row offsets
+           align_up((size_t)(SI_MAX_CONV + 3) * (B + 1) * 4, 256) +   // ragged batches: per-layer length table + row offsets
+           ENC_WS_ZONES * ctx->ws_zone;
 }
 
 // Clips per vocoder pass.  Measured on MI355X (B = 32, fp32): 4 -> 109 ms/step, 8 -> 93, 16 -> 89, 32 -> 88: small
@@ -239,7 +259,8 @@ size_t vocoder_ws_bytes(const si_ctx* ctx, int B, int Tm, int stretch) {
     for (int i = 0; i < d.num_ups; ++i) { L *= d.up_rates[i]; c = stage_channels(ctx, i); lc_max = std::max(lc_max, (size_t)L * c); }
     // 6 fp32 activation buffers + 6 half-size buffers for the operand-ready 16-bit copies (bf16 / fp16 modes)
     const size_t f = (size_t)Bc * Tout * ctx->lay.mel_ld + 9 * (size_t)Bc * lc_max;
-    return f * 4 + 32 * 256 + align_up((size_t)(2 * SI_MAX_UPS + 3) * B * 4, 256);   // ragged batches: per-stage length table
+    return f * 4 + 32 * 256 + align_up((size_t)(2 * SI_MAX_UPS + 3) * B * 4, 256) +   // ragged batches: per-stage length table
+           VOC_WS_ZONES * ctx->ws_zone;
 }
 
 TapGemmParams gemm_params(const si_ctx* ctx, const GemmW& G) {
@@ -340,6 +361,7 @@ int si_create(si_ctx** out, int device_id, const si_model_desc* desc) {
     ctx->opt_ln_fuse = getenv("SI_ENC_LNFUSE") ? atoi(getenv("SI_ENC_LNFUSE")) : 1;
     ctx->opt_voc_upsgemm = getenv("SI_VOC_UPSGEMM") ? atoi(getenv("SI_VOC_UPSGEMM")) : 1;
     ctx->opt_ffn_pad = getenv("SI_ENC_FFNPAD") ? std::min(128, std::max(0, atoi(getenv("SI_ENC_FFNPAD")) / 8 * 8)) : 64;
+    ctx->ws_zone = getenv("SI_WS_REDZONE") ? (size_t)std::min(1L << 20, std::max(0L, atol(getenv("SI_WS_REDZONE")))) / 256 * 256 : 0;
     plan_layout(ctx->d, ctx->popt, ctx->lay);
     *out = ctx;
     return SI_OK;
@@ -415,7 +437,7 @@ int si_vocoder_samples(const si_ctx* ctx, int Tm, int stretch) {
 
 int si_workspace_bytes(si_ctx* ctx, int B, int N, int Tm, size_t* out) {
     if (!ctx || !out || B <= 0) return si_fail(ctx, SI_EINVAL, "si_workspace_bytes: bad argument");
-    size_t a = N > 0 ? encoder_ws_bytes(ctx->d, B, N) : 0;
+    size_t a = N > 0 ? encoder_ws_bytes(ctx, B, N) : 0;
     size_t b = Tm > 0 ? vocoder_ws_bytes(ctx, B, Tm, 1) : 0;
     *out = std::max(a, b);
     return SI_OK;
@@ -491,14 +513,14 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const EncDims e = enc_dims(d, N);
     if (e.T < 1) return si_fail(ctx, SI_EINVAL, "clip of %d samples is shorter than the conv stack's receptive field", N);
-    if (workspace_bytes < encoder_ws_bytes(d, B, N))
-        return si_fail(ctx, SI_ENOMEM, "workspace of %zu bytes < %zu needed for B=%d N=%d", workspace_bytes, encoder_ws_bytes(d, B, N), B, N);
+    if (workspace_bytes < encoder_ws_bytes(ctx, B, N))
+        return si_fail(ctx, SI_ENOMEM, "workspace of %zu bytes < %zu needed for B=%d N=%d", workspace_bytes, encoder_ws_bytes(ctx, B, N), B, N);
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     const int T = e.T, H = d.hidden_size, I = d.intermediate_size, CF = d.conv_dim[d.num_conv - 1];
     size_t cmax = 0;
     for (int i = 0; i < d.num_conv; ++i) cmax = std::max(cmax, (size_t)e.L[i + 1] * d.conv_dim[i]);
 
-    Carver W{static_cast<char*>(workspace), workspace_bytes};
+    Carver W = carver(ctx, SI_WS_ENCODER, workspace, workspace_bytes);
     // ---- ragged batch: the table [samples | L_1 .. L_nconv | row offsets (B + 1)] on the host and on the device
     const bool vl = host_len != nullptr;
     VlTable tab;
@@ -527,27 +549,27 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     auto hL = [&](int i) { return tab.host + (size_t)i * B; };
     const int32_t* d_rowoff = vl ? dL(d.num_conv + 1) : nullptr;
     const long BT = vl ? rows_packed : (long)B * T;          // transformer rows
-    double* stats = reinterpret_cast<double*>(W.bytes((size_t)B * 16));
-    int32_t* vframes = (valid_len && !vl) ? reinterpret_cast<int32_t*>(W.bytes((size_t)B * 4)) : nullptr;
-    double* partials = reinterpret_cast<double*>(W.bytes(si_conv0_partials_bytes(B, N)));
-    float* affine = W.floats((size_t)B * d.conv_dim[0] * 2);
-    float* cbuf[2] = {W.floats((size_t)B * cmax), W.floats((size_t)B * cmax)};
+    double* stats = reinterpret_cast<double*>(W.bytes((size_t)B * 16, "stats"));
+    int32_t* vframes = (valid_len && !vl) ? reinterpret_cast<int32_t*>(W.bytes((size_t)B * 4, "vframes")) : nullptr;
+    double* partials = reinterpret_cast<double*>(W.bytes(si_conv0_partials_bytes(B, N), "partials"));
+    float* affine = W.floats((size_t)B * d.conv_dim[0] * 2, "affine");
+    float* cbuf[2] = {W.floats((size_t)B * cmax, "cbuf0"), W.floats((size_t)B * cmax, "cbuf1")};
     const bool c16 = ctx->opt_enc_opready && d.encoder_math == SI_MATH_BF16 && !d.feat_norm_layer && d.num_conv >= 2;
     unsigned short* cb16[2] = {reinterpret_cast<unsigned short*>(cbuf[0]), reinterpret_cast<unsigned short*>(cbuf[1])};   // same storage, bf16 view
-    float* lnf = W.floats(BT * CF);
-    float* h = W.floats(BT * H);
-    float* h2 = W.floats(BT * H);
-    float* att = W.floats(BT * H);
-    float* qkv = W.floats(BT * 3 * H);
-    float* ffn = W.floats(BT * I);
+    float* lnf = W.floats(BT * CF, "lnf");
+    float* h = W.floats(BT * H, "h");
+    float* h2 = W.floats(BT * H, "h2");
+    float* att = W.floats(BT * H, "att");
+    float* qkv = W.floats(BT * 3 * H, "qkv");
+    float* ffn = W.floats(BT * I, "ffn");
     // Operand-ready bf16 activations for the encoder GEMMs (bf16 mode): LayerNorm, attention and the FFN's first GEMM
     // also / only write bf16(x) -- the rounding the consuming GEMM would apply while staging -- so the four GEMMs of a
     // layer load 2-byte operands (their dominant traffic: M = B*T rows re-read by every N-tile) and skip the
     // conversion.  Bit-identical to converting in the consumer.  SI_ENC_OPREADY=0 restores fp32 inputs.
     const bool e16 = ctx->opt_enc_opready && d.encoder_math == SI_MATH_BF16;
-    unsigned short* lnf16 = e16 ? reinterpret_cast<unsigned short*>(W.bytes((size_t)BT * CF * 2)) : nullptr;
-    unsigned short* h16 = e16 ? reinterpret_cast<unsigned short*>(W.bytes((size_t)BT * H * 2)) : nullptr;
-    unsigned short* att16 = e16 ? reinterpret_cast<unsigned short*>(W.bytes((size_t)BT * H * 2)) : nullptr;
+    unsigned short* lnf16 = e16 ? reinterpret_cast<unsigned short*>(W.bytes((size_t)BT * CF * 2, "lnf16")) : nullptr;
+    unsigned short* h16 = e16 ? reinterpret_cast<unsigned short*>(W.bytes((size_t)BT * H * 2, "h16")) : nullptr;
+    unsigned short* att16 = e16 ? reinterpret_cast<unsigned short*>(W.bytes((size_t)BT * H * 2, "att16")) : nullptr;
     // Post-LN layers in bf16 mode: a LayerNorm's output is read as a bf16 GEMM operand and as the fp32 residual of the second GEMM
     // behind it.  The fp32 copy (19.5 MB per launch at the bench shape, 4.7 of the LayerNorm's 14.4 us) is not written: the
     // LayerNorm stores (mean, rstd) per row and the residual-adding epilogue recomputes the element from the row it was
@@ -556,10 +578,10 @@ static int hubert_run(si_ctx* ctx, const float* wav, const int32_t* mask_start, 
     // SI_ENC_LNFUSE=0, debug captures, fp32 mode or a width the bf16 GEMM kernels do not cover: every LayerNorm writes its rows.
     const bool ln_fuse = e16 && ctx->opt_ln_fuse && ctx->opt_enc_lingemm && !d.stable_layer_norm && ctx->dbg_capture.empty() && H % 128 == 0 && I % 64 == 0 &&
                          (double)(BT + 128) * (I + 128) * 2.0 < 2.0e9;
-    float* ln_stats = ln_fuse ? W.floats(BT * 2) : nullptr;
+    float* ln_stats = ln_fuse ? W.floats(BT * 2, "ln_stats") : nullptr;
     const int ffn_ld = e16 ? I + ctx->opt_ffn_pad : I;                 // row stride of the bf16 FFN intermediate (SI_ENC_FFNPAD)
-    unsigned short* ffn16 = e16 ? reinterpret_cast<unsigned short*>(W.bytes((size_t)BT * ffn_ld * 2)) : nullptr;
-    if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: encoder workspace carve exceeded its own estimate");
+    unsigned short* ffn16 = e16 ? reinterpret_cast<unsigned short*>(W.bytes((size_t)BT * ffn_ld * 2, "ffn16")) : nullptr;
+    if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: encoder workspace carve exceeded its own estimate at region '%s'", W.failed);
     // bf16 mode with the bf16-MFMA attention: the QKV GEMM writes q | k | v as bf16 only (the rounding the attention
     // kernel's staging would apply), into the storage of the fp32 matrix
     const bool qkv_bf16 = e16 && ctx->opt_att_bf16;
@@ -1078,7 +1100,7 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
         for (int i = 0; i < d.num_ups; ++i) { L *= d.up_rates[i]; c = stage_channels(ctx, i); lc_max = std::max(lc_max, (size_t)L * c); }
     }
     const long Lwav = si_vocoder_samples(ctx, Tm, stretch);
-    Carver W{static_cast<char*>(workspace), workspace_bytes};
+    Carver W = carver(ctx, SI_WS_VOCODER, workspace, workspace_bytes);
     // ---- ragged batch: the table [mel frames | rows of stage 0 (stretched frames) .. stage num_ups | GEMM rows of upsampler 1 .. num_ups]
     const bool vl = host_len != nullptr;
     VlTable tab;
@@ -1101,11 +1123,13 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
         })) return trc;
         SI_HIP_CHECK(hipMemsetAsync(wav_out, 0, (size_t)B * Lwav * sizeof(float), st));   // samples past a clip's own end read as silence
     }
-    float* ext_ws = W.floats((size_t)Bc_max * Tout * Ly.mel_ld);
-    float* buf_ws[6];
+    float* ext_ws = W.floats((size_t)Bc_max * Tout * Ly.mel_ld, "ext");
+    const size_t nbuf = (size_t)Bc_max * lc_max;
+    float* buf_ws[6] = {W.floats(nbuf, "buf0"), W.floats(nbuf, "buf1"), W.floats(nbuf, "buf2"), W.floats(nbuf, "buf3"), W.floats(nbuf, "buf4"), W.floats(nbuf, "buf5")};
+    char* const h16_raw[6] = {W.bytes(nbuf * 2, "h16_0"), W.bytes(nbuf * 2, "h16_1"), W.bytes(nbuf * 2, "h16_2"),
+                              W.bytes(nbuf * 2, "h16_3"), W.bytes(nbuf * 2, "h16_4"), W.bytes(nbuf * 2, "h16_5")};
     unsigned short* h16_ws[6];
-    for (auto& b : buf_ws) b = W.floats((size_t)Bc_max * lc_max);
-    for (auto& b : h16_ws) b = reinterpret_cast<unsigned short*>(W.bytes((size_t)Bc_max * lc_max * 2));
+    for (int i = 0; i < 6; ++i) h16_ws[i] = reinterpret_cast<unsigned short*>(h16_raw[i]);
     // Operand-ready activations (bf16 / fp16 vocoder): every producer also writes type16(leaky_relu(x, 0.1)) -- exactly
     // what the next convolution would compute while staging -- so consumers copy 2-byte operands instead of loading
     // fp32 and converting; the ResBlock intermediate exists only in that form.  Same arithmetic, bit-identical output;
@@ -1118,7 +1142,7 @@ static int hifigan_run(si_ctx* ctx, const float* mel, int B, int Tm, int stretch
     // (gate 1e-3).  SI_VOC_RES16=0 keeps the fp32 residual stream.
     const bool r16 = opr && ctx->popt.voc_res16 && d.vocoder_math == SI_MATH_F16;
     const int fuse_mask = ctx->opt_voc_fuse == 1 ? ~0 : ctx->opt_voc_fuse;
-    if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: vocoder workspace carve exceeded its own estimate");
+    if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: vocoder workspace carve exceeded its own estimate at region '%s'", W.failed);
     const int nk = d.num_rb;
     static const char* upn[] = {"ups0", "ups1", "ups2", "ups3", "ups4", "ups5", "ups6", "ups7"};
     static const char* stn[] = {"stage0", "stage1", "stage2", "stage3", "stage4", "stage5", "stage6", "stage7"};
@@ -1404,11 +1428,12 @@ int ensure_frontend(si_ctx* ctx) {
     return SI_OK;
 }
 
-size_t mel_ws_bytes(int B, int N22) {
+size_t mel_ws_bytes(const si_ctx* ctx, int B, int N22) {
     const long Tm = (N22 + 2 * FE_PAD - FE_NFFT) / FE_HOP + 1;
     if (Tm < 1) return 0;
     return fe_round((size_t)B * 4) + fe_round((size_t)B * Tm * FE_FRAME * 4) + fe_round((size_t)B * Tm * FE_LDSPEC * 4) + 256 +
-           fe_round((size_t)2 * B * 4);                               // ragged batches: the length table
+           fe_round((size_t)2 * B * 4) +                             // ragged batches: the length table
+           MEL_WS_ZONES * ctx->ws_zone;
 }
 
 }  // namespace
@@ -1419,7 +1444,7 @@ int si_mel_frames(int n22) { return n22 + 2 * FE_PAD < FE_NFFT ? 0 : (n22 + 2 * 
 
 int si_mel_workspace_bytes(si_ctx* ctx, int B, int N22, size_t* out) {
     if (!ctx || !out || B <= 0 || si_mel_frames(N22) < 1) return si_fail(ctx, SI_EINVAL, "si_mel_workspace_bytes: bad argument");
-    *out = mel_ws_bytes(B, N22);
+    *out = mel_ws_bytes(ctx, B, N22);
     return SI_OK;
 }
 
@@ -1458,16 +1483,16 @@ static int mel_run(si_ctx* ctx, const float* wave22, const int32_t* mask_start, 
         return si_fail(ctx, SI_EINVAL, "si_mel_frontend: mask_start and mask_end must both be given or both be NULL");
     const int Tm = si_mel_frames(N22);
     if (Tm < 1 || N22 <= FE_PAD) return si_fail(ctx, SI_EINVAL, "clip of %d samples is too short for the %d-sample reflect pad / %d-point STFT", N22, FE_PAD, FE_NFFT);
-    if (workspace_bytes < mel_ws_bytes(B, N22))
-        return si_fail(ctx, SI_ENOMEM, "workspace of %zu bytes < %zu needed for B=%d N22=%d", workspace_bytes, mel_ws_bytes(B, N22), B, N22);
+    if (workspace_bytes < mel_ws_bytes(ctx, B, N22))
+        return si_fail(ctx, SI_ENOMEM, "workspace of %zu bytes < %zu needed for B=%d N22=%d", workspace_bytes, mel_ws_bytes(ctx, B, N22), B, N22);
     int rc = ensure_frontend(ctx);
     if (rc) return rc;
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    Carver W{static_cast<char*>(workspace), workspace_bytes};
-    float* peak = W.floats((size_t)B);
-    float* frames = W.floats((size_t)B * Tm * FE_FRAME);
-    float* spec = W.floats((size_t)B * Tm * FE_LDSPEC);
+    Carver W = carver(ctx, SI_WS_MEL, workspace, workspace_bytes);
+    float* peak = W.floats((size_t)B, "peak");
+    float* frames = W.floats((size_t)B * Tm * FE_FRAME, "frames");
+    float* spec = W.floats((size_t)B * Tm * FE_LDSPEC, "spec");
     const int32_t *d_n = nullptr, *d_tm = nullptr;
     if (host_len) {                                                    // table [samples | frames] per clip
         VlTable tab;
@@ -1482,7 +1507,7 @@ static int mel_run(si_ctx* ctx, const float* wave22, const int32_t* mask_start, 
         }))) return rc;
         d_n = tab.dev; d_tm = tab.dev + B;
     }
-    if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: mel workspace carve exceeded its own estimate");
+    if (!W.ok) return si_fail(ctx, SI_ENOMEM, "internal: mel workspace carve exceeded its own estimate at region '%s'", W.failed);
     const float* hann = reinterpret_cast<const float*>(ctx->fe_dev + ctx->fe_hann);
     if (normalize && (rc = si_launch_wave_peak(ctx, wave22, mask_start, mask_end, B, N22, peak, st, d_n, spans))) return rc;
     if (normalize && !ctx->dbg_capture.empty() && (rc = si_tap(ctx, st, {peak, (long)B}, "mel_peak"))) return rc;   // (per-op tap)
@@ -2065,6 +2090,18 @@ long si_debug_size(si_ctx* ctx, const char* name) {
     auto it = ctx->dbg_size.find(name);
     if (it == ctx->dbg_size.end()) return si_fail(ctx, SI_EINVAL, "no intermediate named '%s' in the last forward", name);
     return it->second;
+}
+
+int si_debug_ws_regions(si_ctx* ctx, int which, si_ws_region* out, int capacity, int* count) {
+    if (!ctx || !count || capacity < 0 || (capacity > 0 && !out)) return si_fail(ctx, SI_EINVAL, "si_debug_ws_regions: NULL / bad argument");
+    if (which < SI_WS_ENCODER || which > SI_WS_MEL) return si_fail(ctx, SI_EINVAL, "si_debug_ws_regions: pass %d unknown (0 encoder, 1 generator, 2 mel)", which);
+    const si_ctx::WsLog& log = ctx->ws_log[which];
+    *count = log.n;
+    for (int i = 0; i < log.n && i < capacity; ++i) {
+        snprintf(out[i].name, sizeof(out[i].name), "%s", log.r[i].name);
+        out[i].offset = log.r[i].offset; out[i].bytes = log.r[i].bytes;
+    }
+    return SI_OK;
 }
 
 }  // extern "C"

@@ -27,7 +27,7 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_f0_encoder_weight_floats", "si_f0_encoder_frames", "si_f0_encoder_workspace_bytes", "si_f0_encoder_forward",
            "si_resample_poly", "si_resample_sinc", "si_pcm16", "si_extend_mel", "si_hifigan_forward", "si_mel_frames", "si_mel_workspace_bytes", "si_mel_frontend", "si_num_frames",
            "si_vocoder_samples", "si_profile_start", "si_profile_filter", "si_profile_stop",
-           "si_debug_capture", "si_debug_size",
+           "si_debug_capture", "si_debug_size", "si_debug_ws_regions",
            "si_hubert_forward_spans", "si_mel_frontend_spans", "si_codebook_splice_spans", "si_codebook_splice_labels_spans",
            "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
            "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate",
@@ -240,6 +240,11 @@ class ProfileEntry(C.Structure):
                 ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class WsRegion(C.Structure):
+    """Mirror of si_ws_region."""
+    _fields_ = [("name", C.c_char * 24), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
 class ModelDesc(C.Structure):
     """Mirror of si_model_desc (include/si_hip.h)."""
     _fields_ = [
@@ -388,6 +393,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_debug_capture.argtypes = [vp, C.c_char_p, vp, C.c_long]
     lib.si_debug_size.argtypes = [vp, C.c_char_p]
     lib.si_debug_size.restype = C.c_long
+    lib.si_debug_ws_regions.argtypes = [vp, i32, C.POINTER(WsRegion), i32, C.POINTER(i32)]
     lib.si_profile_start.argtypes = [vp, i32]
     lib.si_profile_filter.argtypes = [vp, C.c_char_p]
     lib.si_profile_stop.argtypes = [vp, C.POINTER(ProfileEntry), i32, C.POINTER(i32)]
@@ -1179,6 +1185,14 @@ class NativeContext:
             out[nm] = t
         self._captures = out
         return out
+
+    def ws_regions(self, which: str):
+        """[(name, offset, bytes)] of the most recent carve of the "encoder", "vocoder" or "mel" pass on this context, offsets from
+        the workspace pointer of that call (si_debug_ws_regions; a test hook)."""
+        arr = (WsRegion * 32)()
+        n = C.c_int(0)
+        self._check(self.lib.si_debug_ws_regions(self._h, ("encoder", "vocoder", "mel").index(which), arr, 32, C.byref(n)), "si_debug_ws_regions")
+        return [(arr[i].name.decode(), int(arr[i].offset), int(arr[i].bytes)) for i in range(n.value)]
 
     def clear_captures(self):
         for nm in list(getattr(self, "_captures", {})):
