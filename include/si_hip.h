@@ -38,6 +38,12 @@
  *   si_burst_runs        <- nothing the reference computes either: the detector for damage that is LOUDER than the speech -- a block
  *                           of corrupted PCM (random data, swapped or misaligned bytes), found by the windowed level of the second
  *                           difference.  It has no detection                                          I_ea/predict.py:85-90
+ *   si_invalid_runs      <- nothing the reference computes either: the detector for a FLOAT file whose damage is the sample values
+ *                           themselves -- NaN, +-inf, absurd magnitudes -- which no other detector sees.  It has no detection
+ *                                                                             I_ea/predict.py:85-90
+ *   si_cut_rate_valid / si_cut_pair_valid / si_cut_clips_valid  <- nothing the reference computes: si_cut_rate[_ch], si_cut_pair[_ch] and
+ *                           si_cut_clips with such a sample entering as +0.0, so that one NaN costs its gap and not its whole context.
+ *                           The script's loads (I_ea/predict.py:79-80) pass every value on; its mask is typed by hand (:85-90)
  *   si_patch_rate        <- the same write-out for a file at ANY sample rate, which the script resamples on the way in and never
  *                           brings back                                       I_ea/predict.py:79-80,203-207
  *   si_cut_rate          <- that resampling on the way in, for the context clips alone instead of the whole file (with si_cut_clips'
@@ -585,8 +591,8 @@ int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_ta
                      float* out_f32, int16_t* out_pcm, si_stream_t stream);
 
 /* ---- The sample types of the file-typed calls -------------------------------------------------------------------------
- * The twelve calls that take a file as it lies on disk -- si_quiet_runs[_ch], si_dead_runs, si_level_runs, si_burst_runs, si_cut_rate[_ch],
- * si_cut_pair[_ch], si_patch_rate[_ch] -- name its sample type in their `is_pcm16` argument.  Pass one of:
+ * The sixteen calls that take a file as it lies on disk -- si_quiet_runs[_ch], si_dead_runs, si_level_runs, si_burst_runs, si_invalid_runs,
+ * si_cut_rate[_ch], si_cut_pair[_ch], si_cut_rate_valid, si_cut_pair_valid, si_patch_rate[_ch] (si_cut_clips_valid takes fp32 alone) -- name its sample type in their `is_pcm16` argument.  Pass one of:
  *   SI_SAMPLE_F32 = 0   fp32
  *   SI_SAMPLE_S16 = 1   int16 PCM; a sample enters the cutters and the patch as (float)v / 32768, exact
  *   SI_SAMPLE_S24 = 2   packed little-endian signed 24-bit PCM, three bytes per sample, (n, ch) interleaved as a WAV data chunk holds
@@ -883,6 +889,43 @@ int si_level_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels,
  * [0, 4] (|d| <= 4 * peak) and not be NaN. */
 int si_burst_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int half, float threshold, float rel_threshold,
                   int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream);
+
+/* ---- NaN, inf and out-of-range samples: found, and kept out of the interpolation -----------------------------------------
+ * The reference has no detection (I_ea/predict.py:85-90) and its loads pass every sample value on (:79-80).  A float file whose damage is
+ * the sample VALUES -- NaN, +-inf, 3e38 left by a division by zero, a decoder that ran off its buffer, a damaged sector -- is seen by
+ * none of the detectors above (NaN is loud, never held, and a window that holds one is neither low nor hot), and one such sample inside
+ * a hand-typed gap still poisons its whole context: the interpolating cutters run FIRs over the file, so NaN leaves the masked span.
+ *
+ * invalid(v, c), for a ceiling c > 0 (+inf allowed) -- ONE definition (csrc/common.h, si_invalid) shared by the four calls below:
+ *   fp32            !(|v| <= min(c, FLT_MAX)): NaN of any payload and sign, +-inf, and |v| > c.  With c = +inf exactly "not finite".
+ *                   -0.0 and subnormals are valid.
+ *   int16           !((float)|v| <= c), the magnitude taken in int32 (|-32768| = 32768, exact); c counts the file's own steps.
+ *   packed 24-bit   the same with 24-bit steps (|-2^23| exact).  A PCM sample is invalid only under a finite ceiling: c = 32766 marks
+ *                   clipped int16 samples.
+ *
+ * si_invalid_runs: every maximal run of invalid samples of at least min_len samples.  Input layout, channels / channel (channels = 1 is
+ * a mono file and gives the mono bytes; channel = -1 is JOINT: a time is dead when EVERY channel's element is invalid), output rows,
+ * scratch, limits and refusals are si_dead_runs' for the arguments they share.  There is no pass 0: no peak, no threshold_out.  A sample
+ * at or past n, or in front of the base, is never read as dead.  Plain stores, no atomics: the same input gives the same bytes.
+ * SI_EINVAL before any launch, naming the argument, for everything si_dead_runs refuses for the shared arguments, and a ceiling that is
+ * <= 0 or NaN.
+ *
+ * si_cut_rate_valid / si_cut_pair_valid / si_cut_clips_valid: the contract of si_cut_rate[_ch] / si_cut_pair[_ch] / si_cut_clips, with
+ * one more sentence: A FILE SAMPLE THAT IS invalid(., ceiling) IS STAGED AS +0.0 (judged in the file's own units, before the conversion
+ * to full scale).  Wings, tap counts, fma order, the single rounding and the unfiltered 16 kHz row of a 16 kHz file are untouched, so
+ * the outputs equal, byte for byte, the plain call's on the file with its invalid samples replaced by +0.0 -- without that copy of the
+ * file.  channels = 1 is the mono file; channels >= 2 reads channel `channel` of the interleaved file (si_dead_runs' convention: one
+ * call, not two).  si_cut_clips_valid is fp32, the 22.05 kHz route.  SI_EINVAL before any launch for everything the mirrored call
+ * refuses, channels outside 1 .. SI_MAX_CHANNELS, channel outside [0, channels), and a ceiling that is <= 0 or NaN. */
+int si_invalid_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, float ceiling, int min_len, int32_t* runs,
+                    int max_runs, int32_t* n_runs, si_stream_t stream);
+int si_cut_rate_valid(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr, const int32_t* host_start,
+                      const int32_t* start, int C, int L, const si_sinc_filter* filt, float ceiling, float* out, si_stream_t stream);
+int si_cut_pair_valid(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr, const int32_t* host_frame,
+                      const int32_t* frame, int C, int L22, int L16, const si_sinc_filter* filt22, const si_sinc_filter* filt16, float ceiling,
+                      float* out22, float* out16, si_stream_t stream);
+int si_cut_clips_valid(si_ctx* ctx, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L, float ceiling,
+                       float* out, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

@@ -78,6 +78,8 @@ class PredictConfig:
                                         # kind "level" (DESIGN.md 4.25): the RMS level of a window of `win_ms:` against the threshold
                                         # kind "burst" (DESIGN.md 4.28): the second difference's RMS level over `win_ms:` AT OR ABOVE the
                                         # threshold -- a block of corrupted PCM; rel_threshold in [0, 4] there; start from threshold: 1.15
+                                        # kind "invalid" (DESIGN.md 4.30): NaN, inf and |x| > threshold, the CEILING in full-scale units
+                                        # (0 or absent: none); min_ms defaults to 0 there; rel_threshold, held_tol, win_ms are refused
     detect_level: Optional[dict] = None  # `win_ms:` inside `detect:` ({win_ms: 2.0}): the window of kind "level" in
                                          # milliseconds, and of kind "burst" ({win_ms: 4.0} there), read at no other
                                          # kind; None without `detect:`
@@ -207,16 +209,24 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             detect_dead = {"kind": "quiet", "rel_threshold": 0.0, "held_tol": 0.0}
             if "kind" in dm:
                 detect_dead["kind"] = dm.pop("kind")
-                if detect_dead["kind"] not in ("quiet", "held", "any", "level", "burst"):
+                if detect_dead["kind"] not in ("quiet", "held", "any", "level", "burst", "invalid"):
                     raise ValueError(f"{path}: detect.kind = {detect_dead['kind']!r}: quiet (the default: |x| <= the threshold), held (a sample "
                                      f"repeated, a DC level) or any, or level (the RMS level of a window of win_ms milliseconds <= the threshold), "
-                                     f"or burst (the RMS level of the second difference over a window of win_ms milliseconds >= the threshold)")
+                                     f"or burst (the RMS level of the second difference over a window of win_ms milliseconds >= the threshold), "
+                                     f"or invalid (NaN, inf and |x| > the threshold, the ceiling; 0 = no ceiling)")
             for key in ("rel_threshold", "held_tol"):
                 if key in dm:
                     detect_dead[key] = float(dm.pop(key))
                     if not detect_dead[key] >= 0:
                         raise ValueError(f"{path}: detect.{key} = {detect_dead[key]} is negative")
             burst = detect_dead["kind"] == "burst"                   # a second difference reaches 4 * the peak
+            invalid = detect_dead["kind"] == "invalid"               # the sample's value is the damage; threshold = the ceiling
+            if invalid:
+                detect_cfg["min_ms"] = 0.0                           # a single NaN is a run of one sample: the default at this kind only
+                for key in ("rel_threshold", "held_tol"):
+                    if detect_dead[key] != 0:
+                        raise ValueError(f"{path}: detect.{key} = {detect_dead[key]} with `kind: invalid` (the ceiling is `threshold:`, in full-scale "
+                                         f"units; nothing at this kind follows the peak or a neighbour)")
             if detect_dead["rel_threshold"] > (4 if burst else 1):
                 raise ValueError(f"{path}: detect.rel_threshold = {detect_dead['rel_threshold']} is a fraction of the file's peak, at most "
                                  f"{'4 with `kind: burst`' if burst else 1}")
@@ -224,7 +234,8 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             if "win_ms" in dm:
                 detect_level["win_ms"] = float(dm.pop("win_ms"))
                 if detect_dead["kind"] not in ("level", "burst"):
-                    raise ValueError(f"{path}: detect.win_ms needs `kind: level` (kind: {detect_dead['kind']} judges sample by sample and has no window)")
+                    raise ValueError(f"{path}: detect.win_ms needs `kind: level` (kind: {detect_dead['kind']} judges sample by sample and has no window)"
+                                     + (": `kind: invalid` takes threshold, min_ms, max_ms, pad_frames and channels" if invalid else ""))
                 if not 0 <= detect_level["win_ms"] < float("inf"):
                     raise ValueError(f"{path}: detect.win_ms = {detect_level['win_ms']} is negative or not finite")
             if detect_dead["kind"] in ("level", "burst") and detect_dead["held_tol"] != 0:

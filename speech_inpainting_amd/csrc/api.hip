@@ -1628,6 +1628,23 @@ int si_cut_clips(si_ctx* ctx, const float* src, int n_src, const int32_t* host_s
     return si_launch_cut_clips(ctx, src, start, C, L, out, static_cast<hipStream_t>(stream));
 }
 
+// si_cut_clips with an invalid sample copied as +0.0: its refusals under this entry's name, plus the ceiling.
+int si_cut_clips_valid(si_ctx* ctx, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L, float ceiling,
+                       float* out, si_stream_t stream) {
+    if (!ctx) return SI_EINVAL;
+    if (!src || !host_start || !start || !out || n_src <= 0 || C <= 0 || L <= 0) return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: NULL / empty argument");
+    if ((long)n_src > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: a source of %d samples, at most %ld", n_src, SI_MAX_REC);
+    if (C > 65535) return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: %d clips in one call, at most 65535 (the launch grid's second dimension)", C);
+    if (!(ceiling > 0.f)) return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: ceiling = %g is not above 0, or is NaN", (double)ceiling);
+    for (int c = 0; c < C; ++c) {
+        const long s = host_start[c];
+        if (s < 0 || s + L > n_src)
+            return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: clip %d = samples [%ld, %ld) is outside the source's %d samples", c, s, s + L, n_src);
+    }
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    return si_launch_cut_clips_valid(ctx, src, start, C, L, ceiling, out, static_cast<hipStream_t>(stream));
+}
+
 int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_table* table, const float* gen, int Lrow, const float* gain,
                      float* out_f32, int16_t* out_pcm, si_stream_t stream) {
     if (!ctx) return SI_EINVAL;
@@ -1810,10 +1827,13 @@ int si_patch_rate_ch(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, in
 }
 
 // ---- context clips cut at the file's own sample rate
+// ceiling != nullptr is si_cut_rate_valid: the same checks, one more, and the launch that stages invalid samples as +0.0.
 static int cut_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr,
-                         const int32_t* host_start, const int32_t* start, int C, int L, const si_sinc_filter* filt, float* out, si_stream_t stream) {
+                         const int32_t* host_start, const int32_t* start, int C, int L, const si_sinc_filter* filt, float* out, si_stream_t stream,
+                         const float* ceiling = nullptr) {
     if (!ctx) return SI_EINVAL;
-    if (inter && si_check_channels(ctx, fn, channels, channel, 0) != SI_OK) return SI_EINVAL;
+    if ((inter || ceiling) && si_check_channels(ctx, fn, channels, channel, 0) != SI_OK) return SI_EINVAL;
+    if (ceiling && !(*ceiling > 0.f)) return SI_FAIL_FN("ceiling = %g is not above 0, or is NaN", (double)*ceiling);
     if (sr < 4000 || sr > 192000) return SI_FAIL_FN("sr = %d Hz, outside 4000 .. 192000", sr);
     if (sr == 22050) return SI_FAIL_FN("sr = 22050 Hz is the model's own rate: that file is si_cut_clips'");
     if (n_file < 1) return SI_FAIL_FN("n_file = %d", n_file);
@@ -1843,6 +1863,9 @@ static int cut_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* x,
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     const SiFeed fd{f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Qr, (int)H, (int)cap, (int)N22};
+    if (ceiling)
+        return si_launch_cut_rate_valid(ctx, x, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, start, C, L, fd, *ceiling, out,
+                                        static_cast<hipStream_t>(stream));
     if (inter) return si_launch_cut_rate_ch(ctx, x, si_sample_format(is_pcm16), n_file, channels, channel, start, C, L, fd, out, static_cast<hipStream_t>(stream));
     return si_launch_cut_rate(ctx, x, si_sample_format(is_pcm16), n_file, start, C, L, fd, out, static_cast<hipStream_t>(stream));
 }
@@ -1855,6 +1878,13 @@ int si_cut_rate(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, co
 int si_cut_rate_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr, const int32_t* host_start,
                    const int32_t* start, int C, int L, const si_sinc_filter* filt, float* out, si_stream_t stream) {
     return cut_rate_call(ctx, "si_cut_rate_ch", true, x, is_pcm16, n_file, channels, channel, sr, host_start, start, C, L, filt, out, stream);
+}
+
+// channels = 1 is the mono file (the mono kernel); channels >= 2 reads channel `channel` of the interleaved file: si_dead_runs' convention.
+int si_cut_rate_valid(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr, const int32_t* host_start,
+                      const int32_t* start, int C, int L, const si_sinc_filter* filt, float ceiling, float* out, si_stream_t stream) {
+    return cut_rate_call(ctx, "si_cut_rate_valid", channels >= 2, x, is_pcm16, n_file, channels, channel, sr, host_start, start, C, L, filt, out, stream,
+                         &ceiling);
 }
 
 // ---- both clip sets of a pass cut straight from the file
@@ -1873,9 +1903,10 @@ static int pair_filter(si_ctx* ctx, const char* fn, const char* arg, const si_si
 
 static int cut_pair_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr,
                          const int32_t* host_frame, const int32_t* frame, int C, int L22, int L16, const si_sinc_filter* filt22,
-                         const si_sinc_filter* filt16, float* out22, float* out16, si_stream_t stream) {
+                         const si_sinc_filter* filt16, float* out22, float* out16, si_stream_t stream, const float* ceiling = nullptr) {
     if (!ctx) return SI_EINVAL;
-    if (inter && si_check_channels(ctx, fn, channels, channel, 0) != SI_OK) return SI_EINVAL;
+    if ((inter || ceiling) && si_check_channels(ctx, fn, channels, channel, 0) != SI_OK) return SI_EINVAL;
+    if (ceiling && !(*ceiling > 0.f)) return SI_FAIL_FN("ceiling = %g is not above 0, or is NaN", (double)*ceiling);   // si_cut_pair_valid
     if (sr < 4000 || sr > 192000) return SI_FAIL_FN("sr = %d Hz, outside 4000 .. 192000", sr);
     if (sr == 22050) return SI_FAIL_FN("sr = 22050 Hz is the model's own rate: that file is si_cut_clips'");
     if (n_file < 1) return SI_FAIL_FN("n_file = %d", n_file);
@@ -1917,6 +1948,9 @@ static int cut_pair_call(si_ctx* ctx, const char* fn, bool inter, const void* x,
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     pr.cap = (int)cap, pr.N22 = (int)N22, pr.N16 = (int)N16, pr.lim16 = (int)lim16;
+    if (ceiling)
+        return si_launch_cut_pair_valid(ctx, x, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, frame, C, L22, L16, pr,
+                                        *ceiling, out22, out16, static_cast<hipStream_t>(stream));
     return si_launch_cut_pair(ctx, x, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, frame, C, L22, L16, pr, out22, out16,
                               static_cast<hipStream_t>(stream));
 }
@@ -1932,6 +1966,13 @@ int si_cut_pair_ch(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int cha
                    float* out16, si_stream_t stream) {
     return cut_pair_call(ctx, "si_cut_pair_ch", true, x, is_pcm16, n_file, channels, channel, sr, host_frame, frame, C, L22, L16, filt22, filt16,
                          out22, out16, stream);
+}
+
+int si_cut_pair_valid(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr, const int32_t* host_frame,
+                      const int32_t* frame, int C, int L22, int L16, const si_sinc_filter* filt22, const si_sinc_filter* filt16, float ceiling,
+                      float* out22, float* out16, si_stream_t stream) {
+    return cut_pair_call(ctx, "si_cut_pair_valid", channels >= 2, x, is_pcm16, n_file, channels, channel, sr, host_frame, frame, C, L22, L16, filt22,
+                         filt16, out22, out16, stream, &ceiling);
 }
 
 // ---- dropout detection
@@ -2026,6 +2067,19 @@ int si_burst_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels,
     if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
     return si_launch_burst_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, half, threshold, rel_threshold, min_len, runs, max_runs, n_runs,
                                 threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
+}
+
+// ---- NaN, inf and out-of-range samples
+int si_invalid_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, float ceiling, int min_len, int32_t* runs,
+                    int max_runs, int32_t* n_runs, si_stream_t stream) {
+    const char* fn = "si_invalid_runs";
+    if (!ctx) return SI_EINVAL;
+    if (quiet_runs_check(ctx, fn, true, x, n, channels, channel, 0.f, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
+    if (!(ceiling > 0.f)) return SI_FAIL_FN("ceiling = %g is not above 0, or is NaN", (double)ceiling);
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
+    return si_launch_invalid_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, ceiling, min_len, runs, max_runs, n_runs, ctx->det_scratch,
+                                  static_cast<hipStream_t>(stream));
 }
 
 #undef SI_FAIL_FN

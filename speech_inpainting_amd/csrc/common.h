@@ -54,6 +54,14 @@ inline void si_with_sample(int fmt, F&& f) {
     else f(static_cast<const float*>(nullptr));
 }
 
+// invalid(v, c) for a ceiling c > 0 (+inf allowed): the ONE definition that si_invalid_runs and the three _valid feeds
+// share.  fp32: NaN of any payload and sign, +-inf and |v| > c; with c = +inf exactly "not finite"; -0.0 and subnormals are valid.
+// PCM: |v| > c with the magnitude taken in int32 (32768 / 2^23 exact in fp32) and c counting the file's own steps, so a PCM sample is
+// invalid only under a finite ceiling.
+__device__ __forceinline__ bool si_invalid(float v, float c) { return !(__builtin_fabsf(v) <= __builtin_fminf(c, __FLT_MAX__)); }
+__device__ __forceinline__ bool si_invalid(int16_t v, float c) { const int a = v; return !((float)(a < 0 ? -a : a) <= c); }
+__device__ __forceinline__ bool si_invalid(SiS24 v, float c) { const int a = v.value(); return !((float)(a < 0 ? -a : a) <= c); }
+
 // ------------------------------------------------------------------------------------------------
 // Ragged batches (BASELINE configs[4]: clips of different lengths in ONE launch, each clip's result equal to that clip run
 // alone -- the reference's one-file-per-run script, I_ea/predict.py:76-207).  Storage keeps a fixed stride per clip (the
@@ -395,6 +403,10 @@ int si_launch_level_runs(si_ctx* ctx, const void* x, int fmt, int n, int channel
 // [1, n - 2], whose summed squares of x[k - 1] - 2 x[k] + x[k + 1] are at least T^2 times their centre count, dilated by half
 int si_launch_burst_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
                          int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
+// the maximal runs of INVALID samples: si_invalid(x, ceiling) -- NaN, +-inf, |x| > ceiling; no pass 0, no threshold out;
+// channels as above (joint: every channel's element invalid)
+int si_launch_invalid_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float ceiling, int min_len, int32_t* runs,
+                           int max_runs, int32_t* n_runs, char* scratch, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // repair at the file's own sample rate (rate_kernels.hip)
@@ -453,6 +465,15 @@ struct SiPair {
 // file x; ch = 0: a mono file (the mono kernel), else channel `channel` of ch interleaved; arguments validated by the caller
 int si_launch_cut_pair(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* frame, int C, int L22, int L16,
                        const SiPair& pr, float* out22, float* out16, hipStream_t st);
+
+// the feeds that stage an invalid file sample as +0.0: the launches above with one more sentence -- a file sample that
+// is si_invalid(., ceiling), judged in the file's own units before any conversion, enters the interpolation (the copy) as +0.0.  ch = 0:
+// a mono file (the mono kernel), else channel `channel` of ch interleaved; arguments validated by the caller
+int si_launch_cut_rate_valid(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* start, int C, int L,
+                             const SiFeed& fd, float ceiling, float* out, hipStream_t st);
+int si_launch_cut_pair_valid(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* frame, int C, int L22,
+                             int L16, const SiPair& pr, float ceiling, float* out22, float* out16, hipStream_t st);
+int si_launch_cut_clips_valid(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float ceiling, float* out, hipStream_t st);
 
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16

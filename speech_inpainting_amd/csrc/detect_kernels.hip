@@ -7,6 +7,7 @@
 //                          that follows the recording's peak, or held (equal to a neighbour) -- and the passes below do not care
 //   detect_level_kernel    a third pass 1: the bit means that a window of low RMS level reaches over the sample
 //   detect_burst_kernel    a fourth pass 1: the bit means that a window of LOUD second difference reaches over it
+//   detect_invalid_kernel, detect_invalid_ch_kernel  a fifth pass 1: the bit means that the sample's VALUE is invalid
 //   detect_carry_kernel    carry[c] = the length of the quiet run that ends exactly in front of chunk c (a segmented scan, one workgroup)
 //   detect_runs_kernel     <false>: the qualifying runs that END in each chunk, counted; <true>: written at offset[c] + rank
 //   detect_offsets_kernel  the exclusive scan of the counts (one workgroup) and the total, a plain store
@@ -713,6 +714,60 @@ __global__ __launch_bounds__(256) void detect_burst_kernel(const T* __restrict__
     lv_window_body<T, true>(x, n, ch, channel, h, thr, thr_dev, thr_out, bitmap, lead, trail);
 }
 
+// ------------------------------------------------------------------------------------------------ invalid samples
+// A fifth pass 1: sample i is DEAD when its VALUE is the damage -- si_invalid(x[i], ceiling) (common.h): NaN of any payload, +-inf,
+// |x| > ceiling; a PCM sample only under a finite ceiling, in the file's own steps.  Nothing looks at a neighbour, so the pass is
+// detect_bits_kernel's with the other predicate: grid (chunks), 256 threads, dt_load_eight on either alignment route (the 24-bit routes
+// included), the bits masked by t 8 + j < len -- a sample at or past n is never dead, whatever lies there -- then dt_store_chunk.
+template <typename T>
+__global__ __launch_bounds__(256) void detect_invalid_kernel(const T* __restrict__ x, int n, float ceiling, uint8_t* __restrict__ bitmap,
+                                                             int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    __shared__ __attribute__((aligned(16))) T tile[DT_CHUNK];
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    DtEight<T> u;
+    dt_load_eight(x, n, c0, len, tile, u);
+    unsigned b = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b |= (t * 8 + j < len && si_invalid(u.e[j], ceiling)) ? 1u << j : 0u;
+    dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
+}
+
+// The same pass over an INTERLEAVED recording, shaped like detect_bits_ch_kernel and without a halo: channel >= 0 judges that channel's
+// element of a sample time (never the adjacent one), channel < 0 is JOINT -- a time is dead when EVERY channel's element is invalid.
+template <typename T>
+__global__ __launch_bounds__(256) void detect_invalid_ch_kernel(const T* __restrict__ x, int n, int ch, int channel, float ceiling,
+                                                                uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+    __shared__ uint8_t sq[DT_CHUNK * SI_MAX_CHANNELS];
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    const T* __restrict__ xc = x + (size_t)c0 * ch;
+    unsigned b = 0;
+    if (channel < 0) {
+        const int cnt = len * ch;
+        for (int e = t; e < DT_CHUNK * ch; e += 256) sq[e] = (e < cnt && si_invalid(xc[e], ceiling)) ? 1 : 0;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            unsigned q = 1;
+            for (int k = 0; k < ch; ++k) q &= sq[(t * 8 + j) * ch + k];
+            b |= q << j;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = j * 256 + t;
+            sq[i] = (i < len && si_invalid(xc[(size_t)i * ch + channel], ceiling)) ? 1 : 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b |= (unsigned)sq[t * 8 + j] << j;
+    }
+    dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
+}
+
 // ------------------------------------------------------------------------------------------------ launcher
 size_t si_detect_scratch_bytes(int n) { return dt_scratch(n).bytes; }     // the bitmap, six words per chunk and {peak, T} (detect_sizes.h)
 
@@ -722,6 +777,8 @@ struct DtDead { int kind; float rel, tol; float* thr_out; };
 struct DtLevel { int half; float rel; float* thr_out; };
 // What si_burst_runs adds instead: the same three, for detect_burst_kernel.
 struct DtBurst { int half; float rel; float* thr_out; };
+// What si_invalid_runs adds instead: the ceiling of detect_invalid(_ch)_kernel.  No pass 0 and no threshold out.
+struct DtInvalid { float ceiling; };
 
 // The caller (si_quiet_runs, si_quiet_runs_ch) checked every argument.  scratch: si_detect_scratch_bytes(n) bytes, 16-byte aligned.
 // channels = 0: x is one channel of n samples (detect_bits_kernel); channels >= 1: x is interleaved, n sample times of `channels`
@@ -729,9 +786,11 @@ struct DtBurst { int half; float rel; float* thr_out; };
 // dead != nullptr: pass 1 is detect_dead(_ch)_kernel, behind pass 0 when dead->rel > 0; nullptr: the launches above.
 // level != nullptr (dead is nullptr then): pass 1 is detect_level_kernel, behind the same pass 0 when level->rel > 0.
 // burst != nullptr (dead and level are nullptr then): pass 1 is detect_burst_kernel, behind the same pass 0 when burst->rel > 0.
+// invalid != nullptr (the other three are nullptr then): pass 1 is detect_invalid(_ch)_kernel, never behind a pass 0; thr is not read.
 template <typename T>
 static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
-                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead, const DtLevel* level, const DtBurst* burst) {
+                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead, const DtLevel* level, const DtBurst* burst,
+                     const DtInvalid* invalid) {
     const int chunks = dt_chunks(n);
     const DtScratch at = dt_scratch(n);
     uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch + at.bitmap);
@@ -745,7 +804,16 @@ static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel
     const double bits = (double)chunks * 256.0, sums = (double)chunks * 4.0;
     const double samples = (double)n * (channels ? channels : 1) * (double)sizeof(T);
 
-    if (dead || level || burst) {
+    if (invalid) {
+        // profiled in the families of the quiet routes' pass 1, whose shape these kernels have: the lists of families are closed
+        if (channels == 0) {
+            si_prof_begin(ctx, "detect_bits", 0.0, samples + bits + 2.0 * sums, st);
+            detect_invalid_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, invalid->ceiling, bitmap, lead, trail);
+        } else {
+            si_prof_begin(ctx, "detect_bits_ch", 0.0, samples + bits + 2.0 * sums, st);
+            detect_invalid_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, invalid->ceiling, bitmap, lead, trail);
+        }
+    } else if (dead || level || burst) {
         const float* thr_dev = nullptr;
         const float rel = dead ? dead->rel : level ? level->rel : burst->rel;
         if (rel > 0.f) {
@@ -826,10 +894,10 @@ static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel
 
 static int dt_launch(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
                      int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr, const DtLevel* level = nullptr,
-                     const DtBurst* burst = nullptr) {
+                     const DtBurst* burst = nullptr, const DtInvalid* invalid = nullptr) {
     int rc = SI_OK;
     si_with_sample(fmt, [&](auto tag) {
-        rc = dt_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st, dead, level, burst);
+        rc = dt_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st, dead, level, burst, invalid);
     });
     return rc;
 }
@@ -865,4 +933,12 @@ int si_launch_burst_runs(si_ctx* ctx, const void* x, int fmt, int n, int channel
     const DtBurst burst{half, rel, thr_out};
     return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
                      nullptr, &burst);
+}
+
+// The invalid samples; channels = 1 is a one-channel file, as for si_launch_dead_runs.
+int si_launch_invalid_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float ceiling, int min_len, int32_t* runs,
+                           int max_runs, int32_t* n_runs, char* scratch, hipStream_t st) {
+    const DtInvalid invalid{ceiling};
+    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, 0.f, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
+                     nullptr, nullptr, &invalid);
 }

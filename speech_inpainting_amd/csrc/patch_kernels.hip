@@ -145,7 +145,17 @@ int si_launch_patch_compose(si_ctx* ctx, const float* orig, const SiSpans& sp, c
 // PER ROW and per side as in gather_windows_kernel (x0 is a multiple of PC_CHUNK, so a chunk has its row's alignment) -- 16-byte stores
 // into an aligned destination, fed by 16-byte loads when the source row is aligned too and by scalar loads otherwise; scalar accesses
 // into a destination that is not.  The C ABI checked 0 <= start and start + L <= n_src on the host copy.
-__global__ __launch_bounds__(256) void cut_clips_kernel(const float* __restrict__ src, const int32_t* __restrict__ start, int L, float* __restrict__ out) {
+// CLEAN = true (si_cut_clips_valid) copies a sample that is si_invalid(., ceiling) as +0.0; CLEAN = false is the copy as
+// it always was, bits unchanged.
+template <bool CLEAN>
+__device__ __forceinline__ float pc_feed(float v, float ceiling) {
+    if constexpr (CLEAN) return si_invalid(v, ceiling) ? 0.f : v;
+    else return v;
+}
+
+template <bool CLEAN>
+__device__ __forceinline__ void pc_cut_clips(const float* __restrict__ src, const int32_t* __restrict__ start, int L, float ceiling,
+                                             float* __restrict__ out) {
     const int c = blockIdx.y;
     const int x0 = blockIdx.x * PC_CHUNK, x1 = min(x0 + PC_CHUNK, L);
     const float* s = src + (size_t)start[c];
@@ -158,23 +168,46 @@ __global__ __launch_bounds__(256) void cut_clips_kernel(const float* __restrict_
             float4 v;
             if (svec) {
                 v = *reinterpret_cast<const float4*>(s + i);
+                v.x = pc_feed<CLEAN>(v.x, ceiling);
+                v.y = pc_feed<CLEAN>(v.y, ceiling);
+                v.z = pc_feed<CLEAN>(v.z, ceiling);
+                v.w = pc_feed<CLEAN>(v.w, ceiling);
             } else {
-                v.x = s[i];
-                v.y = s[i + 1];
-                v.z = s[i + 2];
-                v.w = s[i + 3];
+                v.x = pc_feed<CLEAN>(s[i], ceiling);
+                v.y = pc_feed<CLEAN>(s[i + 1], ceiling);
+                v.z = pc_feed<CLEAN>(s[i + 2], ceiling);
+                v.w = pc_feed<CLEAN>(s[i + 3], ceiling);
             }
             *reinterpret_cast<float4*>(d + i) = v;
         } else {
-            for (int j = i; j < x1 && j < i + 4; ++j) d[j] = s[j];
+            for (int j = i; j < x1 && j < i + 4; ++j) d[j] = pc_feed<CLEAN>(s[j], ceiling);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void cut_clips_kernel(const float* __restrict__ src, const int32_t* __restrict__ start, int L, float* __restrict__ out) {
+    pc_cut_clips<false>(src, start, L, 0.f, out);
+}
+
+__global__ __launch_bounds__(256) void cut_clips_valid_kernel(const float* __restrict__ src, const int32_t* __restrict__ start, int L, float ceiling,
+                                                              float* __restrict__ out) {
+    pc_cut_clips<true>(src, start, L, ceiling, out);
 }
 
 int si_launch_cut_clips(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float* out, hipStream_t st) {
     if (C <= 0 || L <= 0) return SI_OK;
     si_prof_begin(ctx, "cut_clips", 0.0, 8.0 * C * L, st);
     cut_clips_kernel<<<dim3((L + PC_CHUNK - 1) / PC_CHUNK, C), 256, 0, st>>>(src, start, L, out);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+// The caller (si_cut_clips_valid) checked every argument, the ceiling among them.  The same grid and the same profile name.
+int si_launch_cut_clips_valid(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float ceiling, float* out, hipStream_t st) {
+    if (C <= 0 || L <= 0) return SI_OK;
+    si_prof_begin(ctx, "cut_clips", 0.0, 8.0 * C * L, st);
+    cut_clips_valid_kernel<<<dim3((L + PC_CHUNK - 1) / PC_CHUNK, C), 256, 0, st>>>(src, start, L, ceiling, out);
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;

@@ -3,6 +3,8 @@
 //                                      staged in LDS as fp32, then per output the two wings of the band-limited interpolation at the
 //                                      exact rational time j Q / P
 //   cut_rate_ch_kernel<float | int16_t>  the same tile read from one channel of an INTERLEAVED file: one shared body
+//   cut_rate_valid_kernel, cut_rate_valid_ch_kernel, cut_pair_valid_kernel, cut_pair_valid_ch_kernel
+//                                      the same bodies with an INVALID file sample (NaN, +-inf, |x| > ceiling) staged as +0.0
 //   cut_pair_kernel, cut_pair_ch_kernel  per 20 ms frame of one clip, its 22.05 kHz AND its 16 kHz samples from one staged range (DESIGN.md
 //                                      4.26; further down, with its own description)
 // It stands where `resample(file, sr, 22050)` over the whole recording + si_cut_clips would: that pass costs every 22.05 kHz sample of
@@ -13,6 +15,19 @@
 __device__ __forceinline__ float rf_load(const float* p) { return *p; }
 __device__ __forceinline__ float rf_load(const int16_t* p) { return (float)*p * (1.0f / 32768.0f); }     // exact: 16 bits x 2^-15
 __device__ __forceinline__ float rf_load(const SiS24* p) { return (float)p->value() * (1.0f / 8388608.0f); }  // exact: 24 bits x 2^-23
+
+// What the staging statement of both tile bodies reads for one existing file sample.  CLEAN = false: rf_load, the text it always was.
+// CLEAN = true (the _valid entry points): a sample that is si_invalid(., ceiling) -- judged in the file's own units,
+// before the conversion -- enters as +0.0; every other sample as rf_load gives it.  Nothing behind the staging loop knows the policy.
+template <bool CLEAN, typename T>
+__device__ __forceinline__ float rf_feed(const T* p, float ceiling) {
+    if constexpr (CLEAN) {
+        const T v = *p;
+        return si_invalid(v, ceiling) ? 0.f : rf_load(&v);
+    } else {
+        return rf_load(p);
+    }
+}
 
 // grid (ceil(L / 512), C), 256 threads, fd.cap floats of dynamic LDS.  Workgroup (tile, c) owns outputs [tile 512, min(tile 512 + 512, L))
 // of clip c = 22.05 kHz samples j0 + [0, cnt) of the recording, j0 = start[c] + tile 512 (workgroup-uniform: scalar loads).
@@ -34,9 +49,9 @@ __device__ __forceinline__ float rf_load(const SiS24* p) { return (float)p->valu
 // channels, element i ch + channel): one body, rf_cut_tile, serves both, the mono kernel with ch = 1, channel = 0 folded in.  The staging
 // loop clamps on the sample TIME before it forms the 64-bit element offset, so a time outside [0, n_file) is zero, never the neighbouring
 // channel's element; everything after the staging is the mono arithmetic on the staged fp32 row.
-template <typename T>
+template <typename T, bool CLEAN>
 __device__ __forceinline__ void rf_cut_tile(const T* __restrict__ x, int n_file, int ch, int channel, const int32_t* __restrict__ start, int L,
-                                            const SiFeed& fd, float* __restrict__ out) {
+                                            const SiFeed& fd, float ceiling, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float rf_row[];
     const int c = blockIdx.y, o0 = blockIdx.x * RF_TILE;
     const int cnt = min(RF_TILE, L - o0);
@@ -49,7 +64,7 @@ __device__ __forceinline__ void rf_cut_tile(const T* __restrict__ x, int n_file,
     const int span = live ? min((int)((j0 + cnt - 1) * Q / P + H + 1 - base), fd.cap) : 0;
     for (int p = threadIdx.x; p < span; p += 256) {
         const long i = base + p;
-        rf_row[p] = (i >= 0 && i < (long)n_file) ? rf_load(x + ((size_t)i * ch + channel)) : 0.f;
+        rf_row[p] = (i >= 0 && i < (long)n_file) ? rf_feed<CLEAN>(x + ((size_t)i * ch + channel), ceiling) : 0.f;
     }
     __syncthreads();
     float* orow = out + (size_t)c * L + o0;
@@ -89,13 +104,27 @@ __device__ __forceinline__ void rf_cut_tile(const T* __restrict__ x, int n_file,
 template <typename T>
 __global__ __launch_bounds__(256) void cut_rate_kernel(const T* __restrict__ x, int n_file, const int32_t* __restrict__ start, int L, SiFeed fd,
                                                        float* __restrict__ out) {
-    rf_cut_tile(x, n_file, 1, 0, start, L, fd, out);
+    rf_cut_tile<T, false>(x, n_file, 1, 0, start, L, fd, 0.f, out);
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void cut_rate_ch_kernel(const T* __restrict__ x, int n_file, int ch, int channel, const int32_t* __restrict__ start,
                                                           int L, SiFeed fd, float* __restrict__ out) {
-    rf_cut_tile(x, n_file, ch, channel, start, L, fd, out);
+    rf_cut_tile<T, false>(x, n_file, ch, channel, start, L, fd, 0.f, out);
+}
+
+// The same two kernels with an invalid file sample staged as +0.0: rf_cut_tile<T, true>.
+template <typename T>
+__global__ __launch_bounds__(256) void cut_rate_valid_kernel(const T* __restrict__ x, int n_file, const int32_t* __restrict__ start, int L, SiFeed fd,
+                                                             float ceiling, float* __restrict__ out) {
+    rf_cut_tile<T, true>(x, n_file, 1, 0, start, L, fd, ceiling, out);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cut_rate_valid_ch_kernel(const T* __restrict__ x, int n_file, int ch, int channel,
+                                                                const int32_t* __restrict__ start, int L, SiFeed fd, float ceiling,
+                                                                float* __restrict__ out) {
+    rf_cut_tile<T, true>(x, n_file, ch, channel, start, L, fd, ceiling, out);
 }
 
 // ---- both clip sets of a pass from one staged tile
@@ -151,9 +180,9 @@ __device__ __forceinline__ float rf_wings(const float* __restrict__ row, long ba
     return (float)acc;
 }
 
-template <typename T>
+template <typename T, bool CLEAN>
 __device__ __forceinline__ void rf_pair_tile(const T* __restrict__ x, int n_file, int ch, int channel, const int32_t* __restrict__ frame, int L22,
-                                             int L16, const SiPair& pr, float* __restrict__ out22, float* __restrict__ out16) {
+                                             int L16, const SiPair& pr, float ceiling, float* __restrict__ out22, float* __restrict__ out16) {
     extern __shared__ __attribute__((aligned(16))) float rf_pair_row[];
     constexpr int T22 = 441 * RF_PAIR_FRAMES, T16 = 320 * RF_PAIR_FRAMES;
     const int c = blockIdx.y, o22 = blockIdx.x * T22, o16 = blockIdx.x * T16;
@@ -172,7 +201,7 @@ __device__ __forceinline__ void rf_pair_tile(const T* __restrict__ x, int n_file
     const int span = (live22 || live16) ? (int)min(n1 + H + 1 - base, (long)pr.cap) : 0;
     for (int p = threadIdx.x; p < span; p += 256) {
         const long i = base + p;
-        rf_pair_row[p] = (i >= 0 && i < (long)n_file) ? rf_load(x + ((size_t)i * ch + channel)) : 0.f;
+        rf_pair_row[p] = (i >= 0 && i < (long)n_file) ? rf_feed<CLEAN>(x + ((size_t)i * ch + channel), ceiling) : 0.f;
     }
     __syncthreads();
     float* row22 = out22 + (size_t)c * L22 + o22;
@@ -193,13 +222,28 @@ __device__ __forceinline__ void rf_pair_tile(const T* __restrict__ x, int n_file
 template <typename T>
 __global__ __launch_bounds__(256) void cut_pair_kernel(const T* __restrict__ x, int n_file, const int32_t* __restrict__ frame, int L22, int L16,
                                                        SiPair pr, float* __restrict__ out22, float* __restrict__ out16) {
-    rf_pair_tile(x, n_file, 1, 0, frame, L22, L16, pr, out22, out16);
+    rf_pair_tile<T, false>(x, n_file, 1, 0, frame, L22, L16, pr, 0.f, out22, out16);
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void cut_pair_ch_kernel(const T* __restrict__ x, int n_file, int ch, int channel, const int32_t* __restrict__ frame,
                                                           int L22, int L16, SiPair pr, float* __restrict__ out22, float* __restrict__ out16) {
-    rf_pair_tile(x, n_file, ch, channel, frame, L22, L16, pr, out22, out16);
+    rf_pair_tile<T, false>(x, n_file, ch, channel, frame, L22, L16, pr, 0.f, out22, out16);
+}
+
+// The same two kernels with an invalid file sample staged as +0.0: rf_pair_tile<T, true>.  At sr = 16000 the unfiltered
+// 16 kHz row is the STAGED sample, so it is +0.0 there too.
+template <typename T>
+__global__ __launch_bounds__(256) void cut_pair_valid_kernel(const T* __restrict__ x, int n_file, const int32_t* __restrict__ frame, int L22, int L16,
+                                                             SiPair pr, float ceiling, float* __restrict__ out22, float* __restrict__ out16) {
+    rf_pair_tile<T, true>(x, n_file, 1, 0, frame, L22, L16, pr, ceiling, out22, out16);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cut_pair_valid_ch_kernel(const T* __restrict__ x, int n_file, int ch, int channel,
+                                                                const int32_t* __restrict__ frame, int L22, int L16, SiPair pr, float ceiling,
+                                                                float* __restrict__ out22, float* __restrict__ out16) {
+    rf_pair_tile<T, true>(x, n_file, ch, channel, frame, L22, L16, pr, ceiling, out22, out16);
 }
 
 // The caller (si_cut_pair[_ch]) checked every argument, pr.cap * 4 <= 64 KB and C <= 65535 among them.  ch = 0: the mono kernel.  The
@@ -259,6 +303,49 @@ int si_launch_cut_rate_ch(si_ctx* ctx, const void* x, int fmt, int n_file, int c
     si_with_sample(fmt, [&](auto tag) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
         cut_rate_ch_kernel<T><<<grid, 256, lds, st>>>(static_cast<const T*>(x), n_file, ch, channel, start, L, fd, out);
+    });
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+// ---- the feeds that stage an invalid file sample as +0.0
+// si_launch_cut_rate[_ch] and si_launch_cut_pair with the CLEAN instantiations: the same grids, the same LDS, the same profile names
+// (ch = 0: the mono kernel under "cut_rate"; else "cut_rate_ch").  The callers (si_cut_rate_valid, si_cut_pair_valid) checked every
+// argument, the ceiling among them.
+int si_launch_cut_rate_valid(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* start, int C, int L,
+                             const SiFeed& fd, float ceiling, float* out, hipStream_t st) {
+    if (C <= 0 || L <= 0) return SI_OK;
+    const size_t lds = (size_t)fd.cap * sizeof(float);
+    const dim3 grid((L + RF_TILE - 1) / RF_TILE, C);
+    const double outs = (double)C * L;
+    si_prof_begin(ctx, ch > 0 ? "cut_rate_ch" : "cut_rate", outs * 8.0 * fd.H, outs * 4.0 + (double)grid.x * C * fd.cap * si_sample_bytes(fmt), st);
+    si_with_sample(fmt, [&](auto tag) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
+        if (ch > 0) cut_rate_valid_ch_kernel<T><<<grid, 256, lds, st>>>(static_cast<const T*>(x), n_file, ch, channel, start, L, fd, ceiling, out);
+        else cut_rate_valid_kernel<T><<<grid, 256, lds, st>>>(static_cast<const T*>(x), n_file, start, L, fd, ceiling, out);
+    });
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+int si_launch_cut_pair_valid(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* frame, int C, int L22,
+                             int L16, const SiPair& pr, float ceiling, float* out22, float* out16, hipStream_t st) {
+    if (C <= 0 || L22 <= 0 || L16 <= 0) return SI_OK;
+    constexpr int T22 = 441 * RF_PAIR_FRAMES, T16 = 320 * RF_PAIR_FRAMES;
+    const size_t lds = (size_t)pr.cap * sizeof(float);
+    const dim3 grid(std::max((L22 + T22 - 1) / T22, (L16 + T16 - 1) / T16), C);
+    const double o22 = (double)C * L22, o16 = (double)C * L16;
+    const double flops = o22 * 8.0 * pr.r22.H + o16 * 8.0 * pr.r16.H;
+    const double bytes = (o22 + o16) * 4.0 + (double)grid.x * C * pr.cap * si_sample_bytes(fmt);
+    si_prof_begin(ctx, ch > 0 ? "cut_rate_ch" : "cut_rate", flops, bytes, st);
+    si_with_sample(fmt, [&](auto tag) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
+        if (ch > 0)
+            cut_pair_valid_ch_kernel<T><<<grid, 256, lds, st>>>(static_cast<const T*>(x), n_file, ch, channel, frame, L22, L16, pr, ceiling, out22, out16);
+        else
+            cut_pair_valid_kernel<T><<<grid, 256, lds, st>>>(static_cast<const T*>(x), n_file, frame, L22, L16, pr, ceiling, out22, out16);
     });
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());

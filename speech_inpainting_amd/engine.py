@@ -577,7 +577,7 @@ class InpaintingEngine:
         return RegionTable(spans, wins, G.region_chunks(regions), len(ctxs), fade, self.device)
 
     def patch_recording(self, wave22, gaps, wave16=None, fade: int = 110, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
-                        pcm: bool = False) -> Dict[str, object]:
+                        pcm: bool = False, ceiling: Optional[float] = None) -> Dict[str, object]:
         """Patch mode for a recording of ANY length: wave22 (N22,) is the recording at 22.05 kHz (tensor or array, host or device),
         gaps = (first frame, frame count) pairs on ITS 20 ms grid (frame p = samples [441 p, 441 (p + 1))).  gaps.plan_contexts groups
         the gaps into context clips of clip_frames frames that start on the recording's frame grid; per batch of at most `batch`
@@ -588,8 +588,14 @@ class InpaintingEngine:
         patch_multigap_batch gives for that context clip; every other sample is wave22's, bit for bit.
         -> patched (N22,) fp32, patched_pcm (N22,) int16 with pcm=True, contexts (the plan), labels (flat, int64) / label_off
         (gaps + 1): the predicted codewords per gap in sorted gap order, each from the context that owns the gap.
-        A recording without gaps comes back as an exact copy and no model kernel is launched."""
+        A recording without gaps comes back as an exact copy and no model kernel is launched.
+        ceiling: None is the calls above.  A float > 0, +inf included, cuts every clip through si_cut_clips_valid -- the
+        clips of wave16 too, under the same number: both are fp32 in full-scale units -- so that a sample that is NaN, +-inf or above
+        the ceiling reaches the model as +0.0 and stays inside its gap.  `patched` still starts as a copy of wave22 and is blended
+        against wave22: a sample of weight 0 keeps its bits, NaN payload included; only the clips are cleaned, and no copy of the
+        recording's length is made for it."""
         self._need(head=True, codebook=True, what="patch_recording")
+        ceiling = InpaintingEngine._ceiling(ceiling, "patch_recording")
         as1d = lambda x: torch.as_tensor(x).to(self.device, torch.float32).reshape(-1).contiguous()
         wave22 = as1d(wave22)
         wave16 = None if wave16 is None else as1d(wave16)
@@ -611,12 +617,27 @@ class InpaintingEngine:
                 gain = self.ctx.wave_peak(w22, tb["tab22"]) / 0.95
                 self.ctx.patch_regions(wave22, self._region_table(cb, plan, own22), gen, gain, patched, out.get("patched_pcm"))
 
-        cut = lambda cb, L: self.ctx.cut_clips(wave22, [441 * c["start"] for c in cb], L)
-        out.update(self._recording_passes(wave22.numel(), cut, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write))
+        if ceiling is None:
+            cut = lambda cb, L: self.ctx.cut_clips(wave22, [441 * c["start"] for c in cb], L)
+            out.update(self._recording_passes(wave22.numel(), cut, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write))
+        else:
+            cut = lambda cb, L: self.ctx.cut_clips_valid(wave22, [441 * c["start"] for c in cb], L, ceiling)
+            out.update(self._recording_passes(wave22.numel(), cut, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write,
+                                              ceiling=ceiling))
         return out
 
+    @staticmethod
+    def _ceiling(ceiling, fn: str) -> Optional[float]:
+        """The `ceiling` argument of the patch calls: None, or a float > 0 (+inf allowed) that is not NaN."""
+        if ceiling is None:
+            return None
+        c = float(ceiling)
+        if not c > 0.0:
+            raise ValueError(f"{fn}: ceiling = {ceiling} is not above 0, or is NaN (+inf, the samples that are not finite, is allowed)")
+        return c
+
     def _recording_passes(self, N22: int, cut, wave16: Optional[torch.Tensor], gaps, fade_frames: int, clip_frames: int,
-                          min_context: int, batch: int, write, channel_gaps=None, cut16=None) -> Dict[str, object]:
+                          min_context: int, batch: int, write, channel_gaps=None, cut16=None, ceiling: Optional[float] = None) -> Dict[str, object]:
         """What patch_recording and patch_file share: the context plan of a recording of N22 samples at 22.05 kHz and, per batch of
         at most `batch` contexts, the cut -- cut(cb, L22) -> the (B, L22) clips of the contexts cb, which start at 22.05 kHz samples
         441 * start, on the device --, the one multi-gap pass with every gap the clips hold masked, and the labels of the own gaps.
@@ -627,7 +648,8 @@ class InpaintingEngine:
         as a recording of its own (gaps.plan_channel_contexts), the contexts follow in (channel, start) order with a "channel" key, the
         batches fill across channels, and labels / label_off run over the gaps in (channel, gap) order; + channel_off.
         cut16: cut16(cb, L22, L16) -> (the (B, L22) clips, the (B, L16) clips at 16 kHz, which start at samples 320 *
-        start), both from the cutter, in place of `cut` and of the resampling of its clips; wave16 is None then."""
+        start), both from the cutter, in place of `cut` and of the resampling of its clips; wave16 is None then.
+        ceiling: cuts the clips of a supplied wave16 through si_cut_clips_valid; `cut` / `cut16` clean their own."""
         N22, clip_frames, batch = int(N22), int(clip_frames), int(batch)
         n_rec = N22 // 441
         whole = n_rec <= clip_frames                                   # one context: the whole recording, with its true sample counts
@@ -653,7 +675,12 @@ class InpaintingEngine:
                 w22, w16 = cut16(cb, L22, L16)
             else:
                 w22 = cut(cb, L22)
-                w16 = self.resample(w22, 22050, 16000) if wave16 is None else self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16)
+                if wave16 is None:
+                    w16 = self.resample(w22, 22050, 16000)
+                elif ceiling is None:
+                    w16 = self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16)
+                else:
+                    w16 = self.ctx.cut_clips_valid(wave16, [320 * c["start"] for c in cb], L16, ceiling)
             tb = self.gap_tables([c["own"] + c["foreign"] for c in cb], [L16] * B, [L22] * B)
             res = self.predict_multigap_batch(w16, w22, None, tables=tb, vocode=False)
             write(cb, tb, res, w22, L22)
@@ -741,7 +768,8 @@ class InpaintingEngine:
         return x.to(device, x.dtype if x.dtype in (torch.int16, torch.uint8) else torch.float32)
 
     def patch_file(self, x, sr: int, gaps=None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
-                   return_windows: bool = False, feed: str = "recording", channel_gaps=None, clips16: str = "resampled") -> Dict[str, object]:
+                   return_windows: bool = False, feed: str = "recording", channel_gaps=None, clips16: str = "resampled",
+                   ceiling: Optional[float] = None) -> Dict[str, object]:
         """patch_recording for a file at ITS OWN sample rate and in its own sample type: x (n,) is the recording at `sr` Hz, fp32 in
         full-scale units or int16 PCM (tensor or array, host or device), gaps = (first frame, frame count) pairs on its 20 ms grid.
         The recording is resampled to 22.05 kHz here (`resample`) only to FEED the model; the contexts, the multi-gap passes and the
@@ -775,8 +803,16 @@ class InpaintingEngine:
         PACKED 24-BIT PCM: x uint8, (n, 3) mono or (n, ch, 3) interleaved, the bytes of a WAV data chunk.  It needs
         feed="contexts": the clips are cut from the bytes (a sample enters as v * 2^-23, exact) and si_patch_rate writes the three
         bytes of each blended sample -- trunc(w * 2^23), clamped -- into `patched`, a uint8 copy of x's shape; no fp32 image of the
-        file exists.  Everything else above holds as for int16.  A 22.05 kHz s24 file is refused."""
+        file exists.  Everything else above holds as for int16.  A 22.05 kHz s24 file is refused.
+        ceiling: None is everything above, call for call.  A float > 0 in x's own units (full scale for fp32, the
+        file's steps for PCM; +inf = the samples that are not finite) cuts every clip of every pass through si_cut_rate_valid or
+        si_cut_pair_valid, which stage a sample that is NaN, +-inf or above the ceiling as +0.0: it no longer leaves its gap through the
+        interpolation's taps.  It needs feed="contexts" at sr != 22050 -- the whole-file resample would smear the damage before anything
+        could clean it -- and at sr = 22050 it is patch_recording's.  `patched` still starts as a copy of x and is blended against x;
+        no copy of the file's length is made for the cleaning.  A non-finite sample under a cross-fade weight 0 < w < 1 stays non-finite:
+        type the gap so that it covers the run (find_gaps(kind="invalid") does)."""
         self._need(head=True, codebook=True, what="patch_file")
+        ceiling = InpaintingEngine._ceiling(ceiling, "patch_file")
         if feed not in ("recording", "contexts"):
             raise ValueError(f"patch_file: feed = {feed!r}: 'recording' or 'contexts'")
         if clips16 not in ("resampled", "file"):
@@ -785,6 +821,9 @@ class InpaintingEngine:
         P, Q = G.rate_ratio(sr)
         if batch <= 0:
             raise ValueError(f"patch_file: batch = {batch}")
+        if ceiling is not None and sr != 22050 and feed != "contexts":
+            raise ValueError(f"patch_file: ceiling = {ceiling} needs feed=\"contexts\" at {sr} Hz (feed = {feed!r} resamples the whole file, which "
+                             f"smears an invalid sample over every output within the filter's reach before anything could clean it)")
         x = torch.as_tensor(x)
         s24, sdim = InpaintingEngine._file_samples(x, "patch_file")
         if s24 and feed != "contexts":
@@ -797,6 +836,8 @@ class InpaintingEngine:
             per = G.channel_gap_lists(gaps, channel_gaps, x.shape[1])
             kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed,
                       clips16=clips16)
+            if ceiling is not None:
+                kw["ceiling"] = ceiling
             if x.shape[1] == 1:
                 out = self.patch_file(x.reshape(-1, 3) if s24 else x.reshape(-1), sr, per[0], **kw)
                 out["patched"] = out["patched"].reshape(x.shape)
@@ -812,7 +853,9 @@ class InpaintingEngine:
         fade_f = G.file_fade(fade_ms, sr)
         if sr == 22050:
             xf = x.to(torch.float32) / 32768.0 if pcm else x           # exact: 16 bits x 2^-15
-            out = self.patch_recording(xf, gaps, fade=fade_f, clip_frames=clip_frames, min_context=min_context, batch=batch, pcm=pcm)
+            # the ceiling of the fp32 image of an int16 file: |v| <= c <=> |v| / 32768 <= c / 32768, a power of two
+            kc = {} if ceiling is None else {"ceiling": ceiling / 32768.0 if pcm else ceiling}
+            out = self.patch_recording(xf, gaps, fade=fade_f, clip_frames=clip_frames, min_context=min_context, batch=batch, pcm=pcm, **kc)
             if pcm:
                 out["patched"] = out.pop("patched_pcm")
             return out
@@ -830,7 +873,10 @@ class InpaintingEngine:
         if feed == "contexts":                                         # the clips alone, cut from x itself
             fin = self._feed_filter(sr)
             N22 = -(-n_file * P // Q)
-            cut = lambda cb, L: self.ctx.cut_rate(x, sr, [441 * c["start"] for c in cb], L, fin)
+            if ceiling is None:
+                cut = lambda cb, L: self.ctx.cut_rate(x, sr, [441 * c["start"] for c in cb], L, fin)
+            else:
+                cut = lambda cb, L: self.ctx.cut_rate_valid(x, sr, [441 * c["start"] for c in cb], L, fin, ceiling)
         else:
             xf = x.to(torch.float32) / 32768.0 if pcm else x           # exact: 16 bits x 2^-15
             wave22 = self.resample(xf[None], sr, 22050)[0].contiguous()
@@ -841,7 +887,10 @@ class InpaintingEngine:
             fin16 = self._feed_filter16(sr)
 
             def cut16(cb, L22, L16):
-                w22, last16["w16"] = self.ctx.cut_pair(x, sr, [c["start"] for c in cb], L22, L16, fin, fin16)
+                if ceiling is None:
+                    w22, last16["w16"] = self.ctx.cut_pair(x, sr, [c["start"] for c in cb], L22, L16, fin, fin16)
+                else:
+                    w22, last16["w16"] = self.ctx.cut_pair_valid(x, sr, [c["start"] for c in cb], L22, L16, fin, fin16, ceiling)
                 return w22, last16["w16"]
         filt = self._rate_filter(sr)
 
@@ -864,8 +913,9 @@ class InpaintingEngine:
         return out
 
     def _patch_file_channels(self, x: torch.Tensor, sr: int, channel_gaps, fade_ms: float, clip_frames: int, min_context: int, batch: int,
-                             return_windows: bool, feed: str, clips16: str = "resampled") -> Dict[str, object]:
-        """patch_file for an interleaved file x (n, ch >= 2) with one gap list per channel."""
+                             return_windows: bool, feed: str, clips16: str = "resampled", ceiling: Optional[float] = None) -> Dict[str, object]:
+        """patch_file for an interleaved file x (n, ch >= 2) with one gap list per channel.  ceiling: patch_file's
+        (the caller refused it with feed="recording" at this rate)."""
         n_file, ch = x.shape[:2]                                       # packed 24-bit (DESIGN.md 4.27): (n, ch, 3) bytes, feed = "contexts"
         if ch > G.MAX_CHANNELS:
             raise ValueError(f"patch_file: a file of {ch} channels, at most {G.MAX_CHANNELS}")
@@ -876,8 +926,9 @@ class InpaintingEngine:
         P, Q = G.rate_ratio(sr)
         fade_f = G.file_fade(fade_ms, sr)
         if sr == 22050:                                                # patch_recording, channel by channel, as the mono file goes
+            kc = {} if ceiling is None else {"ceiling": ceiling}
             outs = [self.patch_file(x[:, c].contiguous(), sr, channel_gaps[c], fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context,
-                                    batch=batch) for c in range(ch)]
+                                    batch=batch, **kc) for c in range(ch)]
             off = [0]
             for o in outs:
                 off.append(off[-1] + len(o["label_off"]) - 1)
@@ -900,7 +951,10 @@ class InpaintingEngine:
         if feed == "contexts":                                         # the clips alone, cut from x itself, channel c in place
             fin = self._feed_filter(sr)
             N22 = -(-n_file * P // Q)
-            cut_rows = lambda c, starts, L, rows: self.ctx.cut_rate(x, sr, starts, L, fin, out=rows, channel=c)
+            if ceiling is None:
+                cut_rows = lambda c, starts, L, rows: self.ctx.cut_rate(x, sr, starts, L, fin, out=rows, channel=c)
+            else:
+                cut_rows = lambda c, starts, L, rows: self.ctx.cut_rate_valid(x, sr, starts, L, fin, ceiling, out=rows, channel=c)
         else:                                                          # the whole-file resample per channel: it de-interleaves
             wave22 = {}
             for c in range(ch):
@@ -918,7 +972,11 @@ class InpaintingEngine:
                 w22 = torch.empty(len(cb), L22, dtype=torch.float32, device=self.device)
                 last16["w16"] = w16 = torch.empty(len(cb), L16, dtype=torch.float32, device=self.device)
                 for c, r0, r1 in G.pass_channels(cb):
-                    self.ctx.cut_pair(x, sr, [k["start"] for k in cb[r0:r1]], L22, L16, fin, fin16, out22=w22[r0:r1], out16=w16[r0:r1], channel=c)
+                    if ceiling is None:
+                        self.ctx.cut_pair(x, sr, [k["start"] for k in cb[r0:r1]], L22, L16, fin, fin16, out22=w22[r0:r1], out16=w16[r0:r1], channel=c)
+                    else:
+                        self.ctx.cut_pair_valid(x, sr, [k["start"] for k in cb[r0:r1]], L22, L16, fin, fin16, ceiling, out22=w22[r0:r1],
+                                                out16=w16[r0:r1], channel=c)
                 return w22, w16
         filt = self._rate_filter(sr)
 
@@ -972,7 +1030,12 @@ class InpaintingEngine:
         kind, rel_threshold, held_tol: find_gaps' (DESIGN.md 4.20); held_tol in x's own units, like threshold.  Off their defaults the
         dictionary gains `threshold`, the effective one (one per channel for detect="each" on an interleaved file).
         kind "level" with win_ms: find_gaps' (DESIGN.md 4.25), in the file's own samples like everything else here.
-        kind "burst" with win_ms: find_gaps' (DESIGN.md 4.28), likewise: threshold = 1.15 of full scale and win_ms = 4.0 to start from."""
+        kind "burst" with win_ms: find_gaps' (DESIGN.md 4.28), likewise: threshold = 1.15 of full scale and win_ms = 4.0 to start from.
+        kind "invalid" (DESIGN.md 4.30): find_gaps' -- the samples whose VALUE is the damage: NaN, +-inf, and |x| > threshold when
+        threshold != 0 (a ceiling in x's own units; 0, the default, is +inf: the non-finite samples only).  Pass min_ms=0: a single NaN
+        is a run of one sample.  The same ceiling goes on to patch_file(ceiling=...), so the samples that were judged are the ones
+        kept out of the clips; it needs feed="contexts" at sr != 22050.  An edge run (touching sample 0 or n) and a cover longer than
+        the planner's budget are skipped by the existing rules and those samples stay in `patched`, listed in `skipped`."""
         sr, clip_frames, min_context = int(sr), int(clip_frames), int(min_context)
         if detect not in ("each", "joint"):
             raise ValueError(f"conceal_file: detect = {detect!r}: 'each' or 'joint'")
@@ -998,6 +1061,8 @@ class InpaintingEngine:
         kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed)
         if clips16 != "resampled":                                     # the default: patch_file is called as it was
             kw["clips16"] = clips16
+        if kind == "invalid":                                          # no other kind hands patch_file a new keyword
+            kw["ceiling"] = G.invalid_ceiling(threshold)
         if many and detect == "each":
             found = [find(c) for c in range(shape[1])]
             out = self.patch_file(x, sr, channel_gaps=[f["gaps"] for f in found], **kw)
@@ -1141,6 +1206,32 @@ class InpaintingEngine:
         runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
         return (runs, T) if return_threshold else runs
 
+    def find_invalid_runs(self, x, ceiling: float = float("inf"), min_len: int = 1, max_runs: int = 65536,
+                          channel: Optional[int] = None) -> torch.Tensor:
+        """find_quiet_runs for a file whose damage is the sample VALUES (si_invalid_runs): every maximal run of at least
+        min_len samples that are NaN (any payload, either sign), +-inf or of a magnitude above `ceiling`, as device int32 (R, 2) (start,
+        len) rows sorted by start.  ceiling > 0 in x's own units, +inf (the default) = the non-finite samples; an int16 or packed
+        24-bit sample is invalid only under a finite ceiling (32766 marks clipped int16 samples).  x, channel (an index, or -1: the
+        times at which EVERY channel is invalid), min_len, max_runs, the one D2H copy (the count) and the ValueError on overflow are
+        find_quiet_runs'."""
+        c = float(ceiling)
+        if not c > 0.0:
+            raise ValueError(f"find_invalid_runs: ceiling = {ceiling} is not above 0, or is NaN (+inf, the samples that are not finite, is allowed)")
+        x = torch.as_tensor(x)
+        s24, sdim = InpaintingEngine._file_samples(x, "find_invalid_runs")
+        many = sdim == 2 and x.shape[1] >= 2
+        if many and channel is None:
+            raise ValueError(f"find_invalid_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
+        if not many and channel is not None and int(channel) not in (-1, 0):
+            raise ValueError(f"find_invalid_runs: channel = {channel} of a one-channel recording")
+        x = InpaintingEngine._file_on_device(x, self.device)
+        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
+        runs, n_runs = self.ctx.invalid_runs(x, c, min_len, max_runs, channel=int(channel) if many else None)
+        total = int(n_runs.item())
+        if total > int(max_runs):
+            raise ValueError(f"find_invalid_runs: {total} runs of at least {int(min_len)} invalid samples, more than max_runs = {int(max_runs)}")
+        return runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+
     def recording_frames(self, n22: int, clip_frames: int = 200, n16: Optional[int] = None) -> Tuple[int, int]:
         """(n_rec_frames, lim_frames) of a recording of n22 samples at 22.05 kHz as patch_recording serves it: its 20 ms frames and
         the usable ones [0, lim) -- a context clip's min(T, Tm) (patch_recording's own arithmetic, n16 = the samples of a supplied
@@ -1172,7 +1263,11 @@ class InpaintingEngine:
         kind "burst" (DESIGN.md 4.28): the runs are find_burst_runs' -- a block of corrupted PCM, LOUDER than the speech: the RMS level of
         the second difference over a window of win_ms milliseconds at or above the threshold.  rel_threshold may reach 4 there, held_tol
         must be 0, and T = 0 (both thresholds 0) is refused: start from 1.15 of full scale with win_ms = 4.0.  `threshold` is carried
-        as well.  win_ms is read at no other kind."""
+        as well.  win_ms is read at no other kind.
+        kind "invalid" (DESIGN.md 4.30): the runs are find_invalid_runs' -- samples that are NaN, +-inf or, with threshold != 0, of a
+        magnitude above `threshold`, the CEILING in x's own units (threshold = 0, the default, is +inf: the non-finite samples only).
+        rel_threshold and held_tol must be 0; win_ms is not read.  min_ms keeps its meaning and its default: pass min_ms=0 for this
+        kind, a single NaN is a run of one sample.  `threshold` carries the ceiling."""
         x = torch.as_tensor(x)
         s24, sdim = InpaintingEngine._file_samples(x, "find_gaps")                 # packed 24-bit PCM (DESIGN.md 4.27): thresholds in 24-bit steps
         n, sr = (x.shape[0] if sdim == 2 or s24 else x.numel()), int(sr)
@@ -1195,6 +1290,14 @@ class InpaintingEngine:
                                  "Start from threshold = 1.15 of full scale (1.15 * 32768 for int16, 1.15 * 2^23 for 24-bit) with win_ms = 4.0")
             runs, T = self.find_burst_runs(x, half=G.level_half(win_ms, sr), threshold=threshold, rel_threshold=rel_threshold, min_len=min_len,
                                            channel=channel, return_threshold=True)
+        elif kind == "invalid":
+            if float(rel_threshold) != 0.0:
+                raise ValueError(f"find_gaps: rel_threshold = {rel_threshold} with kind = 'invalid' (the ceiling is `threshold`, in the file's own units; "
+                                 f"nothing here follows the peak)")
+            if float(held_tol) != 0.0:
+                raise ValueError(f"find_gaps: held_tol = {held_tol} with kind = 'invalid' (held samples are kind 'held' or 'any')")
+            T = G.invalid_ceiling(threshold)
+            runs = self.find_invalid_runs(x, ceiling=T, min_len=min_len, channel=channel)
         elif kind == "quiet" and float(rel_threshold) == 0.0 and float(held_tol) == 0.0:
             runs = self.find_quiet_runs(x, threshold, min_len, channel=channel)
         else:
@@ -1215,7 +1318,12 @@ class InpaintingEngine:
         kind, rel_threshold, held_tol: find_gaps' (held samples, a threshold relative to the peak).
         kind "level" with win_ms: find_gaps' too (a noise-floor dropout, by windowed RMS level).
         kind "burst" with win_ms: find_gaps' too (a block of corrupted PCM, by second-difference level).
+        kind "invalid": find_gaps' too (NaN, +-inf, |x| > threshold when threshold != 0) -- pass min_ms=0.  The ceiling
+        goes on to patch_recording(ceiling=...); detect_on is refused, because the samples that are fed must be the ones that were judged.
         -> patch_recording's dictionary + gaps + skipped [+ threshold].  With nothing found: an exact copy; only the detection kernels launched."""
+        if kind == "invalid" and detect_on is not None:
+            raise ValueError("conceal_recording: kind = 'invalid' with detect_on: the samples that are fed to the model (wave22) must be the ones "
+                             "that were judged; for a file at its own rate use conceal_file(kind='invalid', feed='contexts')")
         as1d = lambda x: torch.as_tensor(x).to(self.device, torch.float32).reshape(-1).contiguous()
         wave22 = as1d(wave22)
         wave16 = None if wave16 is None else as1d(wave16)
@@ -1226,8 +1334,9 @@ class InpaintingEngine:
         found = self.find_gaps(wave22 if detect_on is None else detect_on, 22050 if detect_on is None else sr, threshold, min_ms, max_ms,
                                pad_frames, merge_frames, fade, n_rec, lim, kind=kind, rel_threshold=rel_threshold, held_tol=held_tol,
                                **({"win_ms": win_ms} if kind in ("level", "burst") else {}))
+        kc = {"ceiling": G.invalid_ceiling(threshold)} if kind == "invalid" else {}      # no other kind hands patch_recording a new keyword
         out = self.patch_recording(wave22, found["gaps"], wave16=wave16, fade=fade, clip_frames=clip_frames, min_context=min_context,
-                                   batch=batch, pcm=pcm)
+                                   batch=batch, pcm=pcm, **kc)
         out["gaps"], out["skipped"] = found["gaps"], found["skipped"]
         if "threshold" in found:
             out["threshold"] = found["threshold"]

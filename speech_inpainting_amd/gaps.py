@@ -440,6 +440,15 @@ def file_fade(fade_ms: float, sr: int) -> int:
     return int(round(float(fade_ms) * int(sr) / 1000.0))
 
 
+def invalid_ceiling(threshold: float) -> float:
+    """The ceiling of kind "invalid"  from the `threshold` of find_gaps / conceal_*: 0, their default, is +inf (the
+    samples that are not finite); anything else is the ceiling itself, in the file's own units.  A ValueError for a negative or NaN one."""
+    t = float(threshold)
+    if not t >= 0.0:
+        raise ValueError(f"threshold = {threshold} with kind = 'invalid' is negative or NaN: the ceiling in the file's own units, or 0 for none")
+    return math.inf if t == 0.0 else t
+
+
 LEVEL_MAX_HALF = 1024   # SI_LEVEL_MAX_HALF of include/si_hip.h: the largest half window of the level detector (DESIGN.md 4.25)
 
 

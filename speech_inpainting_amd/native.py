@@ -32,7 +32,8 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_codebook_metrics_spans", "si_wave_peak", "si_gather_windows", "si_patch_compose",
            "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate",
            "si_quiet_runs_ch", "si_cut_rate_ch", "si_patch_rate_ch", "si_dead_runs", "si_level_runs", "si_cut_pair", "si_cut_pair_ch",
-           "si_plan_weights", "si_pack_weights_host", "si_burst_runs"]
+           "si_plan_weights", "si_pack_weights_host", "si_burst_runs",
+           "si_invalid_runs", "si_cut_rate_valid", "si_cut_pair_valid", "si_cut_clips_valid"]
 SI_MAX_SPANS = 16
 SI_MAX_CHANNELS = 8                        # channels of an interleaved file
 SAMPLE_F32, SAMPLE_S16, SAMPLE_S24 = 0, 1, 2   # SI_SAMPLE_*: the file-typed calls' sample types; s24 = uint8 (..., 3)
@@ -386,6 +387,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_burst_runs.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp]
     lib.si_cut_pair.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(SincFilter), C.POINTER(SincFilter), vp, vp, vp]
     lib.si_cut_pair_ch.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(SincFilter), C.POINTER(SincFilter), vp, vp, vp]
+    lib.si_invalid_runs.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, i32, vp, vp]
+    lib.si_cut_rate_valid.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, C.POINTER(SincFilter), C.c_float, vp, vp]
+    lib.si_cut_pair_valid.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(SincFilter), C.POINTER(SincFilter), C.c_float,
+                                      vp, vp, vp]
+    lib.si_cut_clips_valid.argtypes = [vp, vp, i32, vp, vp, i32, i32, C.c_float, vp, vp]
     lib.si_plan_weights.argtypes = [C.POINTER(ModelDesc), C.POINTER(sz)]
     lib.si_pack_weights_host.argtypes = [C.POINTER(ModelDesc), vp, sz, C.c_char_p, vp, sz, C.POINTER(sz), C.c_char_p, sz]
     lib.si_num_frames.argtypes = [vp, i32]
@@ -912,6 +918,91 @@ class NativeContext:
                                            int(min_len), _ptr(runs), max_runs, _ptr(n_runs), _ptr(threshold_out), self._stream()),
                     "si_burst_runs")
         return runs, n_runs
+
+    # ---- NaN, inf and out-of-range samples
+    def invalid_runs(self, x: torch.Tensor, ceiling: float = float("inf"), min_len: int = 1, max_runs: int = 65536,
+                     runs: Optional[torch.Tensor] = None, n_runs: Optional[torch.Tensor] = None, channel: Optional[int] = None):
+        """dead_runs with si_invalid_runs' predicate: a sample is dead when its VALUE is invalid -- NaN, +-inf or |x| > ceiling (fp32);
+        |x| > ceiling in the file's own steps for int16 / packed 24-bit PCM, so only under a finite ceiling.  ceiling > 0, +inf (the
+        default) = "not finite".  x, channel (-1: every channel invalid), runs and n_runs are dead_runs'; no threshold comes back.
+        -> (runs, n_runs)."""
+        n, ch = self._interleaved(x, channel)
+        max_runs = int(max_runs)
+        if runs is None and max_runs > 0:
+            runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
+        if n_runs is None:
+            n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
+        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
+        assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
+        self._check(self.lib.si_invalid_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
+                                             int(channel) if channel is not None else 0, float(ceiling), int(min_len), _ptr(runs), max_runs,
+                                             _ptr(n_runs), self._stream()), "si_invalid_runs")
+        return runs, n_runs
+
+    def cut_rate_valid(self, x: torch.Tensor, sr: int, starts, L: int, filt: dict, ceiling: float, out: Optional[torch.Tensor] = None,
+                       channel: Optional[int] = None) -> torch.Tensor:
+        """cut_rate with a file sample that is invalid(., ceiling) -- NaN, +-inf, |x| > ceiling in the file's own units -- staged as +0.0
+        (si_cut_rate_valid): byte for byte cut_rate on the file with those samples replaced by +0.0, without that copy.  channel = c:
+        x is (n_file, ch) interleaved; None: the mono file (channels = 1 of the one C entry)."""
+        n_file, ch = self._interleaved(x, channel)
+        host = np.ascontiguousarray(np.asarray(list(starts), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        Cn, L = host.size, int(L)
+        dev = torch.from_numpy(host).to(self.device, non_blocking=True) if Cn else None
+        if out is None:
+            out = torch.empty(Cn, max(L, 0), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * max(L, 0)
+        win, dwin = filt["win"], filt["dwin"]
+        assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
+        assert win.numel() == dwin.numel()
+        f = SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
+                       float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
+        self._check(self.lib.si_cut_rate_valid(self._h, _ptr(x), self._sample_format(x), n_file, ch if channel is not None else 1,
+                                               int(channel) if channel is not None else 0, int(sr), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L,
+                                               C.byref(f), float(ceiling), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate_valid")
+        return out
+
+    def cut_pair_valid(self, x: torch.Tensor, sr: int, frames, L22: int, L16: int, filt22: dict, filt16: Optional[dict], ceiling: float,
+                       out22: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None, channel: Optional[int] = None):
+        """cut_pair with a file sample that is invalid(., ceiling) staged as +0.0 (si_cut_pair_valid): both outputs are cut_pair's on the
+        file with those samples replaced by +0.0, the unfiltered 16 kHz row of a 16 kHz file included.  channel as cut_rate_valid's."""
+        n_file, ch = self._interleaved(x, channel)
+        host = np.ascontiguousarray(np.asarray(list(frames), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        Cn, L22, L16 = host.size, int(L22), int(L16)
+        dev = torch.from_numpy(host).to(self.device, non_blocking=True) if Cn else None
+        outs = []
+        for out, L in ((out22, L22), (out16, L16)):
+            if out is None:
+                out = torch.empty(Cn, max(L, 0), dtype=torch.float32, device=self.device)
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * max(L, 0)
+            outs.append(out)
+        fs = []
+        for filt in (filt22, filt16):
+            if filt is None:
+                fs.append(None)
+                continue
+            win, dwin = filt["win"], filt["dwin"]
+            assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
+            assert win.numel() == dwin.numel()
+            fs.append(C.byref(SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
+                                         float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)))
+        self._check(self.lib.si_cut_pair_valid(self._h, _ptr(x), self._sample_format(x), n_file, ch if channel is not None else 1,
+                                               int(channel) if channel is not None else 0, int(sr), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L22,
+                                               L16, fs[0], fs[1], float(ceiling), C.c_void_p(outs[0].data_ptr()), C.c_void_p(outs[1].data_ptr()),
+                                               self._stream()), "si_cut_pair_valid")
+        return outs[0], outs[1]
+
+    def cut_clips_valid(self, src: torch.Tensor, starts, L: int, ceiling: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """cut_clips with a sample that is invalid(., ceiling) copied as +0.0 (si_cut_clips_valid); every other sample keeps its bits."""
+        assert src.is_cuda and src.dtype == torch.float32 and src.dim() == 1 and src.is_contiguous()
+        host = np.ascontiguousarray(np.asarray(list(starts), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        Cn, L = host.size, int(L)
+        dev = torch.from_numpy(host).to(self.device, non_blocking=True)
+        if out is None:
+            out = torch.empty(Cn, L, dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * L
+        self._check(self.lib.si_cut_clips_valid(self._h, _ptr(src), min(src.numel(), 2 ** 31 - 1), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L,
+                                                float(ceiling), _ptr(out), self._stream()), "si_cut_clips_valid")
+        return out
 
     @staticmethod
     def _feats_mel(feats: torch.Tensor, mel: torch.Tensor):

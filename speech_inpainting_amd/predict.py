@@ -24,7 +24,10 @@ default) finds a dropout that is a noise floor -- dither, a concealer's comfort 
 milliseconds against the threshold, and gaps.json records `kind`, `T` and `win_ms` (engine.find_level_runs).  `kind: burst`
 finds damage that is LOUDER than the speech -- a block of corrupted PCM: random data, swapped or misaligned bytes -- by the RMS level of the
 second difference over a window of `win_ms:` (4 by default at this kind) at or above `threshold:`; start from `threshold: 1.15` of full
-scale, and a threshold of 0 is refused (engine.find_burst_runs).  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
+scale, and a threshold of 0 is refused (engine.find_burst_runs).  `kind: invalid` finds a float file's samples whose
+VALUE is the damage -- NaN, inf and, with `threshold:` (the ceiling, in full-scale units; 0 or absent: none), |x| above it; `min_ms:`
+defaults to 0 at this kind, gaps.json records `kind` and `ceiling`, and the same ceiling keeps those samples out of the clips the model
+is fed; it needs `long: {rate: file, feed: contexts}` unless the file is at 22.05 kHz (engine.find_invalid_runs).  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
 on the way out: the three waves keep the file's own rate and sample type (an int16 file stays int16), and patched.wav holds the file's
 own samples, bit for bit, outside the cross-fades (engine.patch_file).
 With `feed: contexts` beside `rate: file` the recording is not resampled as a whole on the way in either: only the context clips
@@ -400,12 +403,27 @@ def level_keywords(cfg) -> dict:
     return {"win_ms": level["win_ms"] if level is not None else 2.0}
 
 
+def ceiling_keywords(cfg, scale: float) -> dict:
+    """`detect: {kind: invalid}`'s ceiling as patch_file and patch_recording take it: the threshold in the units the
+    file is read in, 0 or absent = +inf; given at that kind alone, so that every other run calls them as before."""
+    dead = getattr(cfg, "detect_dead", None)
+    if cfg.detect is None or dead is None or dead["kind"] != "invalid":
+        return {}
+    from . import gaps as G
+    return {"ceiling": G.invalid_ceiling(cfg.detect["threshold"] * scale)}
+
+
 def _dead_report(cfg: PredictConfig, found: dict, scale: float) -> dict:
     """What gaps.json gains when the detection went through find_dead_runs: `kind`, and `T`, the effective threshold in the units the
     file was scanned in (one per channel for `channels: each`).  Printed too.  Empty at the defaults: gaps.json is then what it was."""
     if "threshold" not in found:
         return {}
     T, unit = found["threshold"], {1.0: "full scale", 8388608.0: "24-bit steps"}.get(scale, "int16 steps")
+    if cfg.detect_dead["kind"] == "invalid":                                       # DESIGN.md 4.30: the ceiling; null = none (non-finite samples only)
+        many = isinstance(T, (list, tuple))
+        c = T[0] if many else T
+        print(f"Detection kind = invalid, ceiling = {'none' if c == float('inf') else c} ({unit})")
+        return {"kind": "invalid", "ceiling": None if c == float("inf") else c, **({"unit": unit} if scale == 8388608.0 else {})}
     level = level_keywords(cfg)                                                    # kind level: the window is printed and recorded too
     window = f", window win_ms = {level['win_ms']}" if level else ""
     print(f"Detection kind = {cfg.detect_dead['kind']}, effective threshold T = {T} ({unit}){window}")
@@ -461,8 +479,9 @@ def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str)
     for s, l in G.file_spans(gap_list, sr_file):
         masked[s:s + l] = 0                                                        # the file samples whose time lies in the gap's frames
     write(os.path.join(save_dir, "masked.wav"), masked, sr_file)
+    scale = 8388608.0 if x24 is not None else 32768.0 if x.dtype == np.int16 else 1.0   # the units patch_file reads x in: the ceiling's
     out = engine.patch_file(x, sr_file, gap_list, fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"],
-                            feed=cfg.long_feed, **clips16_keywords(cfg))
+                            feed=cfg.long_feed, **clips16_keywords(cfg), **ceiling_keywords(cfg, scale))
     if clips16_keywords(cfg):
         print(f"16 kHz clips: clips16 = {cfg.long_clips16} (cut straight from the file, with the 22.05 kHz clips)")
     labels, off = out["labels"].tolist(), out["label_off"]
@@ -543,6 +562,9 @@ def _main_long(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> i
     if cfg.long_rate == "file":
         return _main_long_file(cfg, engine, save_dir)
     raw, sr_file = audio.read_wav(cfg.wave_path)
+    if ceiling_keywords(cfg, 1.0) and sr_file != 22050:                            # the resample below would smear the damage
+        raise ValueError(f"{cfg.wave_path}: `detect: {{kind: invalid}}` on a {sr_file} Hz file needs `long: {{rate: file, feed: contexts}}` (the "
+                         f"22.05 kHz route resamples the whole file, which spreads an invalid sample over every output within the filter's reach)")
     wave_22 = engine.resample(torch.from_numpy(raw)[None].to(engine.device), sr_file, 22050)[0].contiguous()
     fade = cfg.patch_fade if cfg.patch_fade is not None else 110
     clip_frames, min_context = int(round(cfg.long["clip_s"] * 50)), int(round(cfg.long["context_s"] * 50))
@@ -555,7 +577,8 @@ def _main_long(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> i
     for pos, lm in gap_list:
         masked[pos * 441:(pos + lm) * 441] = 0                                     # gaps.spans22: frame p = samples [441 p, 441 (p + 1))
     audio.write_wav(os.path.join(save_dir, "masked.wav"), engine.to_int16(masked).cpu().numpy(), 22050)
-    out = engine.patch_recording(wave_22, gap_list, fade=fade, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"], pcm=True)
+    out = engine.patch_recording(wave_22, gap_list, fade=fade, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"], pcm=True,
+                                 **ceiling_keywords(cfg, 1.0))
     labels, off = out["labels"].tolist(), out["label_off"]
     for k, (pos, lm) in enumerate(gap_list):
         print(f"Predicted codewords, gap {k} = frames [{pos}, {pos + lm}): ", labels[off[k]:off[k + 1]])

@@ -21,6 +21,11 @@ warm-up, device-synchronised wall clock per call:
       scan passes), and (l) its torch formulation: the float64 squares of x[k-1] - 2 x[k] + x[k+1] for 1 <= k <= n - 2, avg_pool1d of
       them and of the centres' indicator (times the window: the sum and the truncated count) against T^2, max_pool1d of the mask, then
       (b)'s run extraction
+  (m) engine.find_invalid_runs(ceiling=4.0) on the same recording with its gaps filled by seeded NaN, +-inf and 3e38 (DESIGN.md 4.30;
+      si_invalid_runs: pass 1 with the value predicate, the four scan passes), and (n) its torch formulation: ~(x.abs() <= c), then
+      (b)'s run extraction; (o) engine.conceal_file(kind="invalid", threshold=4.0, feed="contexts", min_ms=0) on the 48 kHz copy of
+      the recording with the same damage in its gaps' file samples, beside (p) engine.patch_file(feed="contexts") with the known gaps
+      on the zero-filled 48 kHz copy.  fp32 only: skipped with --pcm16.  A timed block of its own behind the others.
 
 Prints whether (a) equals (b), (e) equals (f), (g) equals (h), (i) equals (j), (k) equals (l) and (c) equals (d) bit for bit, one line per repeat, the medians, and -- from a separate, untimed run
 under the library's profiler -- the per-kernel times of the detect_* family and the effective bytes per second of the whole call
@@ -218,3 +223,65 @@ for half in (0, 44, 1024):
         eng.find_burst_runs(xb, half=half, threshold=burst_thr, min_len=MIN_LEN)
     e = {e["name"]: e for e in eng.ctx.profile_stop()}["detect_dead"]             # the burst kernel is profiled in pass 1's family too
     print(f"detect_burst_kernel at half={half}: {e['ms'] / e['launches'] * 1e3:.1f} us")
+
+# ---- (m) .. (p): the sample values themselves are the damage.  fp32 only
+if not a.pcm16:
+    from speech_inpainting_amd import gaps as G
+    CEIL = 4.0
+    bad = torch.tensor([float("nan"), float("inf"), float("-inf"), 3e38, -3e38], dtype=torch.float32)
+    pick = lambda n: bad[torch.randint(0, bad.numel(), (n,), generator=gen)].to(dev)
+    inv22 = wave22.clone()
+    for p, l in gaps:
+        inv22[441 * p:441 * (p + l)] = pick(441 * l)
+    SR = 48000
+    wave48 = eng.resample(wave22[None], 22050, SR)[0].contiguous()              # the zero-filled copy at 48 kHz
+    zero48, inv48 = wave48.clone(), wave48.clone()
+    for s, l in G.file_spans(gaps, SR):
+        zero48[s:s + l] = 0
+        inv48[s:s + l] = pick(l)
+    FKW = dict(clip_frames=CLIP, min_context=CTX, batch=a.batch, feed="contexts")
+
+    def torch_invalid():
+        q = (~(inv22.abs() <= CEIL)).to(torch.int8)
+        d = torch.diff(q, prepend=q.new_zeros(1), append=q.new_zeros(1))
+        start, end = torch.nonzero(d == 1).flatten(), torch.nonzero(d == -1).flatten()
+        keep = end - start >= MIN_LEN
+        return torch.stack([start[keep], (end - start)[keep]], dim=1).to(torch.int32)
+
+    legs = {"m": lambda: eng.find_invalid_runs(inv22, CEIL, MIN_LEN), "n": torch_invalid,
+            "o": lambda: eng.conceal_file(inv48, SR, CEIL, min_ms=0, kind="invalid", **FKW), "p": lambda: eng.patch_file(zero48, SR, gaps, **FKW)}
+    om, on, oo, op = (fn() for fn in legs.values())
+    torch.cuda.synchronize()
+    inside = torch.zeros(zero48.numel(), dtype=torch.bool, device=dev)
+    for s, l in G.file_spans(oo["gaps"], SR):
+        inside[s:s + l] = True
+    print(f"(m) equals (n): {torch.equal(om, on)} ({om.shape[0]} runs, {sum(1 for r in om.tolist() if r in [[441 * p, 441 * l] for p, l in gaps])} of them exactly "
+          f"a gap);  (o) found the gaps: {oo['gaps'] == gaps}, skipped {len(oo['skipped'])};  (o) is finite: {bool(torch.isfinite(oo['patched']).all())};  "
+          f"(o) equals (p) inside the gaps bit for bit: {torch.equal(oo['patched'][inside].view(torch.int32), op['patched'][inside].view(torch.int32))}, labels "
+          f"{torch.equal(oo['labels'], op['labels'])};  quiet, held, level and burst detection on that file find "
+          f"{eng.find_quiet_runs(inv22, 0.0, MIN_LEN).shape[0]}, {eng.find_dead_runs(inv22, 'held', min_len=MIN_LEN).shape[0]}, "
+          f"{eng.find_level_runs(inv22, half=LEVEL_HALF, threshold=level_thr, min_len=MIN_LEN).shape[0]} and "
+          f"{eng.find_burst_runs(inv22, half=BURST_HALF, threshold=burst_thr, min_len=MIN_LEN).shape[0]} runs")
+    del om, on, oo, op
+    for fn in legs.values():
+        for _ in range(WARMUP):
+            fn()
+    torch.cuda.synchronize()
+    ms2 = {k: [] for k in legs}
+    for r in range(a.repeats):
+        for k, fn in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms2[k].append((time.perf_counter() - t0) * 1e3)
+        print(f"repeat {r}: " + "  ".join(f"({k}) {ms2[k][-1]:.3f} ms" for k in legs), flush=True)
+    med2 = {k: statistics.median(v) for k, v in ms2.items()}
+    print("median ms/recording: " + "  ".join(f"({k}) {med2[k]:.3f}" for k in legs)
+          + f";  (m) / (n) {med2['m'] / med2['n']:.3f};  (m) / (a) {med2['m'] / med['a']:.3f};  (o) - (p) {med2['o'] - med2['p']:+.3f} ms, spread of (p) "
+          f"{max(ms2['p']) - min(ms2['p']):.3f} ms")
+    eng.ctx.profile_start(1000)
+    for _ in range(10):
+        eng.find_invalid_runs(inv22, CEIL, MIN_LEN)
+    e = {e["name"]: e for e in eng.ctx.profile_stop()}["detect_bits"]            # the invalid kernel is profiled in the quiet pass 1's family
+    print(f"detect_invalid_kernel: {e['ms'] / e['launches'] * 1e3:.1f} us")
