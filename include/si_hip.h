@@ -44,6 +44,9 @@
  *   si_cut_rate_valid / si_cut_pair_valid / si_cut_clips_valid  <- nothing the reference computes: si_cut_rate[_ch], si_cut_pair[_ch] and
  *                           si_cut_clips with such a sample entering as +0.0, so that one NaN costs its gap and not its whole context.
  *                           The script's loads (I_ea/predict.py:79-80) pass every value on; its mask is typed by hand (:85-90)
+ *   si_mend_runs         <- nothing the reference computes: runs of at most 64 samples filled in place from their own neighbourhood
+ *                           by least-squares AR interpolation, instead of a generated 20 ms frame each.  It has no detection
+ *                                                                             I_ea/predict.py:85-90
  *   si_patch_rate        <- the same write-out for a file at ANY sample rate, which the script resamples on the way in and never
  *                           brings back                                       I_ea/predict.py:79-80,203-207
  *   si_cut_rate          <- that resampling on the way in, for the context clips alone instead of the whole file (with si_cut_clips'
@@ -926,6 +929,51 @@ int si_cut_pair_valid(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int 
                       float* out22, float* out16, si_stream_t stream);
 int si_cut_clips_valid(si_ctx* ctx, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L, float ceiling,
                        float* out, si_stream_t stream);
+
+/* ---- Short damaged runs mended in place by least-squares AR interpolation ------------------------------------------
+ * The detectors find a single NaN or a 3-sample underrun exactly; regenerating a 20 ms frame for it replaces good speech.  si_mend_runs
+ * fills the runs of at most max_len samples from their own neighbourhood instead (Janssen; Godsill & Rayner): an AR model of order p
+ * fitted to K intact samples on either side, then the missing samples that minimise its prediction error.  Nothing the reference
+ * computes: it has no detection and no repair but the model                                             I_ea/predict.py:85-90
+ *
+ * x: the caller's copy of the file on the device, repaired IN PLACE: n sample times of fp32, int16 or packed 24-bit PCM by is_pcm16
+ * (SI_SAMPLE_*; an s24 view may start at any byte), one channel (channels = 1) or channel `channel` of `channels` interleaved (element
+ * offsets are 64-bit).  runs: device int32 (n_runs, 2) rows (start, len), sorted and disjoint, as the five detectors emit them.
+ * status: device int32 (n_runs), one word per row -- the first of these that applies, with p = order, K = context, s = start, m = len,
+ * e = s + m:
+ *   SI_MEND_BADROW 6     s < 0, m < 1 or e > n: no sample read, none written
+ *   SI_MEND_LONG 0       m > max_len: left for the inpainter
+ *   SI_MEND_EDGE 3       s - K < 0 or e + K > n
+ *   SI_MEND_NEAR 4       another row meets [s - K, e + K): row i - 1 ends past s - K, or row i + 1 starts before e + K
+ *   SI_MEND_NONFINITE 5  a non-finite sample among the 2 K context samples, or a non-finite result
+ *   SI_MEND_AR 1         filled by the model
+ *   SI_MEND_LINE 2       model degenerate: u_i = x[s - 1] + (i + 1) / (m + 1) * (x[e] - x[s - 1]) in float64
+ * The model, in float64 on the file's own values (the fp32 value, the PCM integer), w = x[s - K .. e + K), W = 2 K + m:
+ *   r[k] = sum w[t] w[t + k] over the pairs that lie on ONE side of the gap (k = 0 .. p), then r[0] *= 1 + 1e-9; r[0] == 0: LINE
+ *   Levinson-Durbin for a_0 = 1, a_1 .. a_p with E <- E (1 - kappa^2); E <= 0 or not finite at any step: LINE
+ *   b[k] = sum_j a_j a_{j + k};  B_ij = b[|i - j|] (0 past p);  d_i = -sum over the KNOWN t within p of K + i of b[|t - K - i|] w[t]
+ *   B u = d by Cholesky; a pivot <= 0: LINE.  u minimises sum_{t = K}^{K + m - 1 + p} (sum_j a_j w[t - j])^2.
+ * fp32 stores (float) u; int16 and s24 store rint(u), ties to even, clamped to the type's range, as the sample's own 2 or 3 bytes.
+ * Only AR and LINE write, only [s, e) of that channel, and nothing before the whole solve has succeeded; NEAR keeps every row's reads
+ * clear of every other row's writes, so a row alone gives the bytes of the same row inside a table.  No atomics, fixed summation
+ * orders: the same input gives the same bits.  One workgroup per row, no scratch; profiled in the family "patch_rate".
+ * SI_EINVAL before any launch, naming the argument: channels outside 1 .. SI_MAX_CHANNELS, channel outside [0, channels), NULL x, n
+ * outside 1 .. 2^31 - 2049, n_runs outside 0 .. SI_MEND_MAX_RUNS, NULL runs or status with n_runs > 0, max_len outside
+ * 1 .. SI_MEND_MAX_LEN, order outside 2 .. SI_MEND_MAX_ORDER, context outside 4 * order .. SI_MEND_MAX_CONTEXT.  n_runs = 0 launches
+ * nothing. */
+#define SI_MEND_MAX_LEN 64
+#define SI_MEND_MAX_ORDER 32
+#define SI_MEND_MAX_CONTEXT 1024
+#define SI_MEND_MAX_RUNS 65536
+#define SI_MEND_LONG 0
+#define SI_MEND_AR 1
+#define SI_MEND_LINE 2
+#define SI_MEND_EDGE 3
+#define SI_MEND_NEAR 4
+#define SI_MEND_NONFINITE 5
+#define SI_MEND_BADROW 6
+int si_mend_runs(si_ctx* ctx, void* x, int is_pcm16, int n, int channels, int channel, const int32_t* runs, int n_runs, int max_len,
+                 int order, int context, int32_t* status, si_stream_t stream);
 
 /* Shape helpers (host arithmetic only). */
 int si_num_frames(const si_ctx* ctx, int N);            /* encoder frames T for N samples, <0 on error */

@@ -83,6 +83,10 @@ class PredictConfig:
     detect_level: Optional[dict] = None  # `win_ms:` inside `detect:` ({win_ms: 2.0}): the window of kind "level" in
                                          # milliseconds, and of kind "burst" ({win_ms: 4.0} there), read at no other
                                          # kind; None without `detect:`
+    detect_mend: Optional[dict] = None   # `mend_ms:`, `mend_order:` and `mend_context:` inside `detect:` (needs long: {rate: file}; DESIGN.md
+                                         # 4.31): runs of at most mend_ms milliseconds (at most 64 samples) are filled from their own
+                                         # neighbourhood by least-squares AR interpolation instead of a generated frame; {mend_ms, mend_order:
+                                         # 32, mend_context: 512}; None when `mend_ms:` is absent or 0: the run is what it was
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -194,7 +198,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
             if long_cfg["batch"] < 1 or long_cfg["clip_s"] <= 2 * long_cfg["context_s"]:
                 raise ValueError(f"{path}: `long:` needs batch >= 1 and clip_s > 2 * context_s, got {long_cfg}")
-        detect_cfg, detect_channels, detect_dead, detect_level = None, "each", None, None
+        detect_cfg, detect_channels, detect_dead, detect_level, detect_mend = None, "each", None, None, None
         if "detect" in data:
             dm = data["detect"] if data["detect"] is not None else {}
             if not isinstance(dm, dict):
@@ -247,6 +251,25 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                                      f"own) or joint (a gap is where all channels are quiet)")
                 if long_rate != "file":
                     raise ValueError(f"{path}: detect.channels needs `long: {{rate: file}}` (at rate: {long_rate} the file is mixed down to one channel)")
+            given = [key for key in ("mend_ms", "mend_order", "mend_context") if key in dm]
+            if given:                                                # short runs mended in place, the rest inpainted
+                if long_rate != "file":
+                    raise ValueError(f"{path}: detect.{given[0]} needs `long: {{rate: file}}` (short runs are mended in the file's own samples; at "
+                                     f"rate: {long_rate} the file is resampled first)")
+                if "mend_ms" not in dm:
+                    raise ValueError(f"{path}: detect.{given[0]} without detect.mend_ms (mend_ms: <milliseconds> switches the mending on)")
+                mend = {"mend_ms": float(dm.pop("mend_ms")), "mend_order": int(dm.pop("mend_order", 32)), "mend_context": int(dm.pop("mend_context", 512))}
+                if not 0 <= mend["mend_ms"] < float("inf"):
+                    raise ValueError(f"{path}: detect.mend_ms = {mend['mend_ms']} is negative or not finite")
+                if not 2 <= mend["mend_order"] <= 32:
+                    raise ValueError(f"{path}: detect.mend_order = {mend['mend_order']}, outside 2 .. 32")
+                if not 4 * mend["mend_order"] <= mend["mend_context"] <= 1024:
+                    raise ValueError(f"{path}: detect.mend_context = {mend['mend_context']} samples, outside 4 * mend_order = {4 * mend['mend_order']} .. 1024")
+                min_ms = float(dm.get("min_ms", detect_cfg["min_ms"]))
+                if mend["mend_ms"] > 0 and min_ms >= mend["mend_ms"]:
+                    raise ValueError(f"{path}: detect.min_ms = {min_ms} is not under detect.mend_ms = {mend['mend_ms']}: no run short enough to mend "
+                                     f"would be reported; lower min_ms (0 reports a single sample)")
+                detect_mend = mend if mend["mend_ms"] > 0 else None
             for key, val in dm.items():
                 if key not in detect_cfg:
                     raise ValueError(f"{path}: unknown key `{key}` in `detect:` (it takes threshold, min_ms, max_ms, pad_frames, channels, kind, rel_threshold, "
@@ -271,7 +294,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
             raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, long_clips16=long_clips16,
             long_pcm24=long_pcm24, detect=detect_cfg,
-            detect_channels=detect_channels, detect_dead=detect_dead, detect_level=detect_level)
+            detect_channels=detect_channels, detect_dead=detect_dead, detect_level=detect_level, detect_mend=detect_mend)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

@@ -2082,6 +2082,27 @@ int si_invalid_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channel
                                   static_cast<hipStream_t>(stream));
 }
 
+// ---- short runs mended in place by least-squares AR interpolation
+int si_mend_runs(si_ctx* ctx, void* x, int is_pcm16, int n, int channels, int channel, const int32_t* runs, int n_runs, int max_len,
+                 int order, int context, int32_t* status, si_stream_t stream) {
+    const char* fn = "si_mend_runs";
+    if (!ctx) return SI_EINVAL;
+    if (si_check_channels(ctx, fn, channels, channel, 0) != SI_OK) return SI_EINVAL;
+    if (!x) return SI_FAIL_FN("x is NULL");
+    if (n < 1 || (long)n > SI_MAX_REC) return SI_FAIL_FN("n = %d samples, outside 1 .. %ld", n, SI_MAX_REC);
+    if (n_runs < 0 || n_runs > SI_MEND_MAX_RUNS) return SI_FAIL_FN("n_runs = %d rows, outside 0 .. SI_MEND_MAX_RUNS = %d", n_runs, SI_MEND_MAX_RUNS);
+    if (!runs && n_runs > 0) return SI_FAIL_FN("runs is NULL with n_runs = %d", n_runs);
+    if (!status && n_runs > 0) return SI_FAIL_FN("status is NULL with n_runs = %d", n_runs);
+    if (max_len < 1 || max_len > SI_MEND_MAX_LEN) return SI_FAIL_FN("max_len = %d samples, outside 1 .. SI_MEND_MAX_LEN = %d", max_len, SI_MEND_MAX_LEN);
+    if (order < 2 || order > SI_MEND_MAX_ORDER) return SI_FAIL_FN("order = %d, outside 2 .. SI_MEND_MAX_ORDER = %d", order, SI_MEND_MAX_ORDER);
+    if (context < 4 * order || context > SI_MEND_MAX_CONTEXT)
+        return SI_FAIL_FN("context = %d samples, outside 4 * order = %d .. SI_MEND_MAX_CONTEXT = %d", context, 4 * order, SI_MEND_MAX_CONTEXT);
+    if (n_runs == 0) return SI_OK;
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    return si_launch_mend_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, runs, n_runs, max_len, order, context, status,
+                               static_cast<hipStream_t>(stream));
+}
+
 #undef SI_FAIL_FN
 
 }  // extern "C"

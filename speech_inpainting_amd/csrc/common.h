@@ -475,6 +475,14 @@ int si_launch_cut_pair_valid(si_ctx* ctx, const void* x, int fmt, int n_file, in
                              int L16, const SiPair& pr, float ceiling, float* out22, float* out16, hipStream_t st);
 int si_launch_cut_clips_valid(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float ceiling, float* out, hipStream_t st);
 
+// ------------------------------------------------------------------------------------------------
+// short runs mended in place by least-squares AR interpolation (mend_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// one workgroup per row of runs (n_runs, 2): status[row] = SI_MEND_*, and for AR / LINE the samples [start, start + len) of channel
+// `channel` of x (n sample times of ch >= 1 interleaved channels, the type fmt names) rewritten; arguments validated by the caller
+int si_launch_mend_runs(si_ctx* ctx, void* x, int fmt, int n, int ch, int channel, const int32_t* runs, int n_runs, int max_len, int order,
+                        int context, int32_t* status, hipStream_t st);
+
 // erf-GELU of the bf16 encoder's GEMM epilogues (lingemm.hip, gemmcu.hip: the SAME function, their results are bit-identical).
 // erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below one fp32 ulp of the result for |x| >= 1 and far below the bf16
 // rounding every consumer of these outputs applies; 15 VALU operations instead of libm erff's ~31 with two divergent branches.

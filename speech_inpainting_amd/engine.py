@@ -19,6 +19,7 @@ import torch
 from .arch import HubertArch, VocoderArch
 from .checkpoint import flatten_checkpoint
 from . import gaps as G
+from . import native
 from .native import NativeContext, PatchTable, RateTable, RegionTable, SpanTable, make_desc
 
 
@@ -1015,7 +1016,8 @@ class InpaintingEngine:
     def conceal_file(self, x, sr: int, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
                      merge_frames: Optional[int] = None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
                      return_windows: bool = False, feed: str = "recording", detect: str = "each", kind: str = "quiet",
-                     rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = 2.0, clips16: str = "resampled") -> Dict[str, object]:
+                     rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = 2.0, clips16: str = "resampled",
+                     mend_ms: float = 0.0, mend_order: int = 32, mend_context: int = 512) -> Dict[str, object]:
         """File in, repaired file out, at the file's own rate and in its own sample type: find_gaps on x itself, where a dropout is
         still exact zeros, then patch_file with the gaps it found.  The usable frames are those of the recording's 22.05 kHz length
         ceil(n * 22050 / sr) (`recording_frames`), and a gap longer than the planner's budget counts as long, as in conceal_recording.
@@ -1035,10 +1037,32 @@ class InpaintingEngine:
         threshold != 0 (a ceiling in x's own units; 0, the default, is +inf: the non-finite samples only).  Pass min_ms=0: a single NaN
         is a run of one sample.  The same ceiling goes on to patch_file(ceiling=...), so the samples that were judged are the ones
         kept out of the clips; it needs feed="contexts" at sr != 22050.  An edge run (touching sample 0 or n) and a cover longer than
-        the planner's budget are skipped by the existing rules and those samples stay in `patched`, listed in `skipped`."""
+        the planner's budget are skipped by the existing rules and those samples stay in `patched`, listed in `skipped`.
+        mend_ms: 0, the default, is everything above, call for call and launch for launch.  Above 0, the runs of at most
+        max_len = round(mend_ms * sr / 1000) samples (at most 64) are first filled from their own neighbourhood by mend_runs(order =
+        mend_order, context = mend_context) on a copy of the file; the rows it filled (status AR or LINE) leave the run list, the rest
+        goes through gaps.runs_to_gaps and patch_file as before, and both feeds read the mended copy.  min_ms must lie under mend_ms.
+        detect="each" mends every channel's own runs; detect="joint" mends the joint runs in every channel and a run leaves the gap
+        list only if every channel filled it.  The dictionary gains `mended`: host rows (start, len, status) of every run of at most
+        max_len samples, one list per channel where `gaps` is one (joint: one list; a row's status is AR or LINE when every channel
+        filled it -- LINE if any did by the line -- else the first channel's status that is no fill).  An edge run stays `skipped`."""
         sr, clip_frames, min_context = int(sr), int(clip_frames), int(min_context)
         if detect not in ("each", "joint"):
             raise ValueError(f"conceal_file: detect = {detect!r}: 'each' or 'joint'")
+        if not float(mend_ms) >= 0.0:
+            raise ValueError(f"conceal_file: mend_ms = {mend_ms} is negative or NaN (0 mends nothing)")
+        mend = float(mend_ms) > 0.0
+        if mend:
+            mend_len = int(round(float(mend_ms) * sr / 1000.0))
+            if mend_len > native.MEND_MAX_LEN:
+                raise ValueError(f"conceal_file: mend_ms = {mend_ms} at {sr} Hz is max_len = {mend_len} samples, at most {native.MEND_MAX_LEN}: lower mend_ms "
+                                 f"to {1000.0 * native.MEND_MAX_LEN / sr:.3f} or less; longer runs stay with the inpainter")
+            if mend_len < 1:
+                raise ValueError(f"conceal_file: mend_ms = {mend_ms} at {sr} Hz is less than one sample: raise it to {1000.0 / sr:.3f} or more, or pass 0")
+            if float(min_ms) >= float(mend_ms):
+                raise ValueError(f"conceal_file: min_ms = {min_ms} is not under mend_ms = {mend_ms}: no run short enough to mend would be reported; "
+                                 f"lower min_ms (0 reports a single sample)")
+            mend_len, mend_order, mend_context = self._mend_limits("conceal_file", mend_len, mend_order, mend_context)
         P, Q = G.rate_ratio(sr)
         x = torch.as_tensor(x)
         s24, sdim = InpaintingEngine._file_samples(x, "conceal_file")
@@ -1063,6 +1087,9 @@ class InpaintingEngine:
             kw["clips16"] = clips16
         if kind == "invalid":                                          # no other kind hands patch_file a new keyword
             kw["ceiling"] = G.invalid_ceiling(threshold)
+        if mend:
+            return self._conceal_mended(x, sr, find, kw, many, detect == "each", shape, sdim, (mend_len, mend_order, mend_context),
+                                        (n_rec, lim, pad_frames, merge_frames, fade22, max_ms))
         if many and detect == "each":
             found = [find(c) for c in range(shape[1])]
             out = self.patch_file(x, sr, channel_gaps=[f["gaps"] for f in found], **kw)
@@ -1073,6 +1100,48 @@ class InpaintingEngine:
         found = find(-1 if many else None)
         out = self.patch_file(x, sr, found["gaps"], **kw)
         out["gaps"], out["skipped"] = found["gaps"], found["skipped"]
+        if "threshold" in found:
+            out["threshold"] = found["threshold"]
+        if not many and sdim == 2:
+            out["patched"] = out["patched"].reshape(shape)
+        return out
+
+    def _conceal_mended(self, x: torch.Tensor, sr: int, find, kw, many: bool, each: bool, shape, sdim: int, limits, rules) -> Dict[str, object]:
+        """conceal_file with mend_ms > 0: detect on x, mend the short runs in a copy y, map the runs that are left onto
+        the 20 ms grid with find_gaps' own arithmetic, and patch y."""
+        max_len, order, context = limits
+        n_rec, lim, pad_frames, merge_frames, fade22, max_ms = rules
+        mf = 2 * max(-(-int(fade22) // 441), 1) if merge_frames is None else int(merge_frames)
+        to_gaps = lambda rows: G.runs_to_gaps(rows, x.shape[0], sr, n_rec, lim, pad_frames, mf, max(int(float(max_ms) // 20), 1))
+        filled = (native.MEND_AR, native.MEND_LINE)
+        y = x.clone()
+
+        def mend_rows(runs, channels):
+            """-> (the rows of at most max_len samples with their status, the rows that stay runs)."""
+            rows = [(int(s), int(l)) for s, l in runs.tolist()]
+            per = [self.mend_runs(y, runs, max_len, order, context, channel=c, inplace=True)[1].tolist() for c in channels] if rows else []
+            status = []
+            for i in range(len(rows)):
+                col = [st[i] for st in per]
+                bad = [v for v in col if v not in filled]
+                status.append(bad[0] if bad else native.MEND_LINE if native.MEND_LINE in col else native.MEND_AR)
+            mended = [(s, l, st) for (s, l), st in zip(rows, status) if l <= max_len]
+            return mended, [r for r, st in zip(rows, status) if st not in filled]
+
+        if many and each:
+            found = [find(c) for c in range(shape[1])]
+            done = [mend_rows(f["runs"], [c]) for c, f in enumerate(found)]
+            mapped = [to_gaps(left) for _, left in done]
+            out = self.patch_file(y, sr, channel_gaps=[g for g, _ in mapped], **kw)
+            out["gaps"], out["skipped"], out["mended"] = [g for g, _ in mapped], [k for _, k in mapped], [m for m, _ in done]
+            if "threshold" in found[0]:
+                out["threshold"] = [f["threshold"] for f in found]
+            return out
+        found = find(-1 if many else None)
+        mended, left = mend_rows(found["runs"], list(range(shape[1])) if many else [None])
+        gaps, skipped = to_gaps(left)
+        out = self.patch_file(y, sr, gaps, **kw)
+        out["gaps"], out["skipped"], out["mended"] = gaps, skipped, mended
         if "threshold" in found:
             out["threshold"] = found["threshold"]
         if not many and sdim == 2:
@@ -1231,6 +1300,71 @@ class InpaintingEngine:
         if total > int(max_runs):
             raise ValueError(f"find_invalid_runs: {total} runs of at least {int(min_len)} invalid samples, more than max_runs = {int(max_runs)}")
         return runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+
+    # ---- short runs mended in place by least-squares AR interpolation
+    @staticmethod
+    def _mend_limits(fn: str, max_len, order, context) -> Tuple[int, int, int]:
+        """(max_len, order, context) as integers inside si_mend_runs' limits, or a ValueError that names the fix."""
+        max_len, order, context = int(max_len), int(order), int(context)
+        if max_len > native.MEND_MAX_LEN:
+            raise ValueError(f"{fn}: max_len = {max_len} samples, at most {native.MEND_MAX_LEN}: least-squares AR interpolation is no better than a "
+                             f"straight line beyond that; leave longer runs to the inpainter (lower max_len / mend_ms)")
+        if max_len < 1:
+            raise ValueError(f"{fn}: max_len = {max_len} samples, at least 1")
+        if not 2 <= order <= native.MEND_MAX_ORDER:
+            raise ValueError(f"{fn}: order = {order}, outside 2 .. {native.MEND_MAX_ORDER}")
+        if not 4 * order <= context <= native.MEND_MAX_CONTEXT:
+            raise ValueError(f"{fn}: context = {context} samples, outside 4 * order = {4 * order} .. {native.MEND_MAX_CONTEXT}: "
+                             f"raise context or lower order")
+        return max_len, order, context
+
+    def mend_runs(self, x, runs, max_len: int = 64, order: int = 32, context: int = 512, channel: Optional[int] = None,
+                  inplace: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The runs of at most max_len samples among `runs` filled from their own neighbourhood by least-squares AR interpolation
+        (si_mend_runs): an AR model of order `order` fitted to `context` intact samples on either side of a run, then the
+        samples that minimise its prediction error -- for a stray NaN, a 3-sample underrun or a clipped peak, which a generated 20 ms
+        frame would repair at the cost of good speech.  x takes find_quiet_runs' rules: host or device, fp32 / int16 / packed 24-bit
+        (uint8 (n, 3) or (n, ch, 3)), and an interleaved (n, ch >= 2) file needs `channel` (an index: the one channel that is read and
+        written).  runs: the device tensor a find_*_runs call returned, or a host list of (start, len) rows, which is checked here to be
+        sorted, disjoint and inside the file (a ValueError names the row).
+        -> (y, status): y is a device copy of x with the mended samples (x itself with inplace=True, which needs a device tensor in
+        the sample type it is read in); status is device int32 (R,), native.MEND_* per row.  Only MEND_AR and MEND_LINE rows were
+        written, and only their own samples: everything else holds x's bits."""
+        max_len, order, context = self._mend_limits("mend_runs", max_len, order, context)
+        x = torch.as_tensor(x)
+        s24, sdim = InpaintingEngine._file_samples(x, "mend_runs")
+        many = sdim == 2 and x.shape[1] >= 2
+        if many and (channel is None or int(channel) < 0):
+            raise ValueError(f"mend_runs: an (n, {x.shape[1]}) recording needs channel = an index (one channel is mended per call)")
+        if not many and channel is not None and int(channel) != 0:
+            raise ValueError(f"mend_runs: channel = {channel} of a one-channel recording")
+        n = x.shape[0] if (sdim == 2 or s24) else x.numel()
+        if inplace:
+            if not x.is_cuda or x.dtype not in (torch.float32, torch.int16, torch.uint8) or not x.is_contiguous():
+                raise ValueError("mend_runs: inplace = True needs a contiguous device tensor of fp32, int16 or packed 24-bit samples (a host input or "
+                                 "another dtype is copied: pass inplace = False and use the returned y)")
+            y = x
+        else:
+            y = InpaintingEngine._file_on_device(x, self.device)
+            y = y.clone() if y.data_ptr() == x.data_ptr() else y
+        shape = y.shape
+        flat = y.contiguous() if many else (y.reshape(-1, 3) if s24 else y.reshape(-1)).contiguous()
+        assert not inplace or flat.data_ptr() == y.data_ptr()
+        if not torch.is_tensor(runs):
+            rows = [(int(r[0]), int(r[1])) for r in runs]
+            end = 0
+            for i, (s, m) in enumerate(rows):
+                if m < 1 or s < 0 or s + m > n:
+                    raise ValueError(f"mend_runs: row {i} = (start {s}, len {m}) is empty or outside the file's {n} samples")
+                if s < end:
+                    raise ValueError(f"mend_runs: row {i} = (start {s}, len {m}) starts before row {i - 1} ends at {end}: rows are sorted and disjoint")
+                end = s + m
+            runs = torch.tensor(rows, dtype=torch.int32).reshape(-1, 2).to(self.device)
+        runs = runs.to(self.device, torch.int32).reshape(-1, 2).contiguous()
+        if runs.shape[0] > native.MEND_MAX_RUNS:
+            raise ValueError(f"mend_runs: {runs.shape[0]} rows, at most {native.MEND_MAX_RUNS} in one call")
+        status = self.ctx.mend_runs(flat, runs, max_len, order, context, channel=int(channel) if many else None)
+        return flat.reshape(shape), status
 
     def recording_frames(self, n22: int, clip_frames: int = 200, n16: Optional[int] = None) -> Tuple[int, int]:
         """(n_rec_frames, lim_frames) of a recording of n22 samples at 22.05 kHz as patch_recording serves it: its 20 ms frames and

@@ -33,12 +33,15 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate",
            "si_quiet_runs_ch", "si_cut_rate_ch", "si_patch_rate_ch", "si_dead_runs", "si_level_runs", "si_cut_pair", "si_cut_pair_ch",
            "si_plan_weights", "si_pack_weights_host", "si_burst_runs",
-           "si_invalid_runs", "si_cut_rate_valid", "si_cut_pair_valid", "si_cut_clips_valid"]
+           "si_invalid_runs", "si_cut_rate_valid", "si_cut_pair_valid", "si_cut_clips_valid", "si_mend_runs"]
 SI_MAX_SPANS = 16
 SI_MAX_CHANNELS = 8                        # channels of an interleaved file
 SAMPLE_F32, SAMPLE_S16, SAMPLE_S24 = 0, 1, 2   # SI_SAMPLE_*: the file-typed calls' sample types; s24 = uint8 (..., 3)
 DEAD_QUIET, DEAD_HELD = 1, 2               # SI_DEAD_QUIET, SI_DEAD_HELD: the `kind` bits of si_dead_runs
 LEVEL_MAX_HALF = 1024                      # SI_LEVEL_MAX_HALF: the largest half window of si_level_runs
+MEND_MAX_LEN, MEND_MAX_ORDER, MEND_MAX_CONTEXT, MEND_MAX_RUNS = 64, 32, 1024, 65536   # SI_MEND_MAX_*: the limits of si_mend_runs
+MEND_LONG, MEND_AR, MEND_LINE, MEND_EDGE, MEND_NEAR, MEND_NONFINITE, MEND_BADROW = 0, 1, 2, 3, 4, 5, 6   # SI_MEND_*: a row's status
+MEND_STATUS = ("LONG", "AR", "LINE", "EDGE", "NEAR", "NONFINITE", "BADROW")                         # their names, by code
 CUT_RATE_TILE = 512                        # SI_CUT_RATE_TILE: consecutive outputs of one clip per workgroup of si_cut_rate
 CUT_PAIR_FRAMES = 1                        # SI_CUT_PAIR_FRAMES: consecutive 20 ms frames of one clip per workgroup of si_cut_pair
 
@@ -392,6 +395,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.si_cut_pair_valid.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(SincFilter), C.POINTER(SincFilter), C.c_float,
                                       vp, vp, vp]
     lib.si_cut_clips_valid.argtypes = [vp, vp, i32, vp, vp, i32, i32, C.c_float, vp, vp]
+    lib.si_mend_runs.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp]
     lib.si_plan_weights.argtypes = [C.POINTER(ModelDesc), C.POINTER(sz)]
     lib.si_pack_weights_host.argtypes = [C.POINTER(ModelDesc), vp, sz, C.c_char_p, vp, sz, C.POINTER(sz), C.c_char_p, sz]
     lib.si_num_frames.argtypes = [vp, i32]
@@ -938,6 +942,25 @@ class NativeContext:
                                              int(channel) if channel is not None else 0, float(ceiling), int(min_len), _ptr(runs), max_runs,
                                              _ptr(n_runs), self._stream()), "si_invalid_runs")
         return runs, n_runs
+
+    # ---- short runs mended in place by least-squares AR interpolation
+    def mend_runs(self, x: torch.Tensor, runs: Optional[torch.Tensor], max_len: int = 64, order: int = 32, context: int = 512,
+                  status: Optional[torch.Tensor] = None, channel: Optional[int] = None, n_runs: Optional[int] = None) -> torch.Tensor:
+        """The rows (start, len) of `runs` -- device int32 (R, 2), sorted and disjoint, as the detectors return them -- of at most max_len
+        samples filled IN PLACE in x by least-squares AR interpolation of order `order` over `context` intact samples on either side
+        (si_mend_runs).  x (n,) fp32 / int16, (n, 3) packed 24-bit, or with channel = c >= 0 the interleaved (n, ch[, 3]) file of which
+        only channel c is read and written; a device view may start anywhere.  -> status, device int32 (R,): MEND_* per row; only
+        MEND_AR and MEND_LINE rows were written, and only their own samples.  No rows: nothing is launched."""
+        n, ch = self._interleaved(x, channel)
+        R = (0 if runs is None else runs.shape[0]) if n_runs is None else int(n_runs)
+        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * R)
+        if status is None:
+            status = torch.empty(max(R, 0), dtype=torch.int32, device=self.device)
+        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() >= R
+        self._check(self.lib.si_mend_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
+                                          int(channel) if channel is not None else 0, _ptr(runs), R, int(max_len), int(order), int(context),
+                                          _ptr(status), self._stream()), "si_mend_runs")
+        return status
 
     def cut_rate_valid(self, x: torch.Tensor, sr: int, starts, L: int, filt: dict, ceiling: float, out: Optional[torch.Tensor] = None,
                        channel: Optional[int] = None) -> torch.Tensor:

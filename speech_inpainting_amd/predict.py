@@ -27,7 +27,10 @@ second difference over a window of `win_ms:` (4 by default at this kind) at or a
 scale, and a threshold of 0 is refused (engine.find_burst_runs).  `kind: invalid` finds a float file's samples whose
 VALUE is the damage -- NaN, inf and, with `threshold:` (the ceiling, in full-scale units; 0 or absent: none), |x| above it; `min_ms:`
 defaults to 0 at this kind, gaps.json records `kind` and `ceiling`, and the same ceiling keeps those samples out of the clips the model
-is fed; it needs `long: {rate: file, feed: contexts}` unless the file is at 22.05 kHz (engine.find_invalid_runs).  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
+is fed; it needs `long: {rate: file, feed: contexts}` unless the file is at 22.05 kHz (engine.find_invalid_runs).  With `mend_ms:` (and optionally
+`mend_order:`, `mend_context:`) inside `detect:`, on the `rate: file` routes only, the runs of at most mend_ms milliseconds (at most 64
+samples) are filled from their own neighbourhood by least-squares AR interpolation instead of a generated frame, only the rest is
+inpainted, and gaps.json records `mended`, a count by status (engine.mend_runs).  With `rate: file` inside `long:` the recording is NOT brought to 22.05 kHz
 on the way out: the three waves keep the file's own rate and sample type (an int16 file stays int16), and patched.wav holds the file's
 own samples, bit for bit, outside the cross-fades (engine.patch_file).
 With `feed: contexts` beside `rate: file` the recording is not resampled as a whole on the way in either: only the context clips
@@ -437,6 +440,22 @@ def clips16_keywords(cfg) -> dict:
     return {} if clips16 == "resampled" else {"clips16": clips16}
 
 
+def mend_keywords(cfg) -> dict:
+    """`detect:`'s mend_ms / mend_order / mend_context as conceal_file takes them: given when `mend_ms:` is above 0
+    alone, so that every other run calls what it called and writes the gaps.json it wrote."""
+    mend = getattr(cfg, "detect_mend", None)
+    return {} if cfg.detect is None or not mend else {"mend_ms": mend["mend_ms"], "mend_order": mend["mend_order"], "mend_context": mend["mend_context"]}
+
+
+def mended_report(rows) -> dict:
+    """conceal_file's `mended` rows (start, len, status) as gaps.json records them: how many there are by status name."""
+    from .native import MEND_STATUS
+    count: Dict[str, int] = {}
+    for _, _, st in rows:
+        count[MEND_STATUS[st]] = count.get(MEND_STATUS[st], 0) + 1
+    return count
+
+
 def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str) -> int:
     """`long: {rate: file}`: the recording stays at the file's own rate and in its own sample type (engine.patch_file).  orig.wav,
     masked.wav and patched.wav are written at that rate; an int16 file is written as int16, any other as the float32 it was read to.
@@ -469,7 +488,23 @@ def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str)
     P, Q = G.rate_ratio(sr_file)
     fade_ms = cfg.patch_fade_ms if cfg.patch_fade_ms is not None else 5.0
     clip_frames, min_context = int(round(cfg.long["clip_s"] * 50)), int(round(cfg.long["context_s"] * 50))
-    if cfg.detect is not None:
+    scale = 8388608.0 if x24 is not None else 32768.0 if x.dtype == np.int16 else 1.0   # the units patch_file reads x in: the ceiling's
+    out = None
+    if cfg.detect is not None and mend_keywords(cfg):                              # detection, mending and repair are conceal_file's
+        d = cfg.detect
+        out = engine.conceal_file(x, sr_file, d["threshold"] * scale, d["min_ms"], d["max_ms"], d["pad_frames"], fade_ms=fade_ms, clip_frames=clip_frames,
+                                  min_context=min_context, batch=cfg.long["batch"], feed=cfg.long_feed, **dead_keywords(cfg.detect_dead, scale),
+                                  **level_keywords(cfg), **clips16_keywords(cfg), **mend_keywords(cfg))
+        gap_list, report = out["gaps"], _dead_report(cfg, out, scale)
+        for k, (pos, lm) in enumerate(gap_list):
+            print(f"Detected gap {k} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s")
+        for pos, lm, why in out["skipped"]:
+            print(f"Skipped quiet run = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s: {why}")
+        print(f"Mended runs of at most {cfg.detect_mend['mend_ms']} ms, by status: {mended_report(out['mended'])}")
+        with open(os.path.join(save_dir, "gaps.json"), "w") as f:
+            json.dump({"gaps": [list(g) for g in gap_list], "skipped": [list(g) for g in out["skipped"]], **report, **clips16_keywords(cfg),
+                       "mended": mended_report(out["mended"])}, f)
+    elif cfg.detect is not None:
         gap_list = _detect_gaps(cfg, engine, raw, sr_file, -(-len(x) * P // Q), -(-G.file_fade(fade_ms, sr_file) * P // Q), clip_frames, min_context,
                                 save_dir, x24)
     else:
@@ -479,9 +514,9 @@ def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str)
     for s, l in G.file_spans(gap_list, sr_file):
         masked[s:s + l] = 0                                                        # the file samples whose time lies in the gap's frames
     write(os.path.join(save_dir, "masked.wav"), masked, sr_file)
-    scale = 8388608.0 if x24 is not None else 32768.0 if x.dtype == np.int16 else 1.0   # the units patch_file reads x in: the ceiling's
-    out = engine.patch_file(x, sr_file, gap_list, fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"],
-                            feed=cfg.long_feed, **clips16_keywords(cfg), **ceiling_keywords(cfg, scale))
+    if out is None:
+        out = engine.patch_file(x, sr_file, gap_list, fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=cfg.long["batch"],
+                                feed=cfg.long_feed, **clips16_keywords(cfg), **ceiling_keywords(cfg, scale))
     if clips16_keywords(cfg):
         print(f"16 kHz clips: clips16 = {cfg.long_clips16} (cut straight from the file, with the 22.05 kHz clips)")
     labels, off = out["labels"].tolist(), out["label_off"]
@@ -526,8 +561,11 @@ def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_
         scale = 8388608.0 if s24 else 32768.0 if x.dtype == np.int16 else 1.0       # an int16 / 24-bit file is scanned as the integers it holds
         joint = cfg.detect_channels == "joint"
         out = engine.conceal_file(dev, sr_file, d["threshold"] * scale, d["min_ms"], d["max_ms"], d["pad_frames"], detect=cfg.detect_channels,
-                                  **dead_keywords(cfg.detect_dead, scale), **level_keywords(cfg), **kw)
+                                  **dead_keywords(cfg.detect_dead, scale), **level_keywords(cfg), **mend_keywords(cfg), **kw)
         report = _dead_report(cfg, out, scale)
+        if mend_keywords(cfg):                                                     # gaps.json gains the count by status
+            report["mended"] = mended_report(out["mended"]) if joint else [mended_report(one) for one in out["mended"]]
+            print(f"Mended runs of at most {cfg.detect_mend['mend_ms']} ms, by status: {report['mended']}")
         found = [(out["gaps"], out["skipped"])] if joint else list(zip(out["gaps"], out["skipped"]))
         for c, (gaps_c, skipped_c) in enumerate(found):
             who = "all channels" if joint else f"channel {c}"
