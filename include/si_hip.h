@@ -41,6 +41,9 @@
  *   si_invalid_runs      <- nothing the reference computes either: the detector for a FLOAT file whose damage is the sample values
  *                           themselves -- NaN, +-inf, absurd magnitudes -- which no other detector sees.  It has no detection
  *                                                                             I_ea/predict.py:85-90
+ *   si_impulse_runs, si_impulse_residual  <- nothing the reference computes either: the detector for clicks and pops of one to a few
+ *                           IN-RANGE samples, by a short-time AR prediction error against that of its own neighbourhood, and that
+ *                           prediction error itself.  It has no detection                              I_ea/predict.py:85-90
  *   si_cut_rate_valid / si_cut_pair_valid / si_cut_clips_valid  <- nothing the reference computes: si_cut_rate[_ch], si_cut_pair[_ch] and
  *                           si_cut_clips with such a sample entering as +0.0, so that one NaN costs its gap and not its whole context.
  *                           The script's loads (I_ea/predict.py:79-80) pass every value on; its mask is typed by hand (:85-90)
@@ -595,7 +598,7 @@ int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_ta
 
 /* ---- The sample types of the file-typed calls -------------------------------------------------------------------------
  * The sixteen calls that take a file as it lies on disk -- si_quiet_runs[_ch], si_dead_runs, si_level_runs, si_burst_runs, si_invalid_runs,
- * si_cut_rate[_ch], si_cut_pair[_ch], si_cut_rate_valid, si_cut_pair_valid, si_patch_rate[_ch] (si_cut_clips_valid takes fp32 alone) -- name its sample type in their `is_pcm16` argument.  Pass one of:
+ * si_cut_rate[_ch], si_cut_pair[_ch], si_cut_rate_valid, si_cut_pair_valid, si_patch_rate[_ch] (si_cut_clips_valid takes fp32 alone) -- and, since DESIGN.md 4.33, si_impulse_runs and si_impulse_residual name its sample type in their `is_pcm16` argument.  Pass one of:
  *   SI_SAMPLE_F32 = 0   fp32
  *   SI_SAMPLE_S16 = 1   int16 PCM; a sample enters the cutters and the patch as (float)v / 32768, exact
  *   SI_SAMPLE_S24 = 2   packed little-endian signed 24-bit PCM, three bytes per sample, (n, ch) interleaved as a WAV data chunk holds
@@ -929,6 +932,54 @@ int si_cut_pair_valid(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int 
                       float* out22, float* out16, si_stream_t stream);
 int si_cut_clips_valid(si_ctx* ctx, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L, float ceiling,
                        float* out, si_stream_t stream);
+
+/* ---- Clicks and pops by locally scaled AR prediction error -----------------------------------------------------------
+ * The reference has no detection (I_ea/predict.py:85-90).  The five detectors above find damage that is quieter than the speech, blocks
+ * that are louder, and bad values; a click of one to a few IN-RANGE samples -- a bit error in a high byte, a dropped or repeated sample
+ * at a buffer seam, a contact click -- is seen by none of them.  si_impulse_runs whitens the signal with a short-time AR model (speech
+ * onsets, sibilants and glottal pulses are largely predictable; a click is not) and compares each sample's squared prediction error
+ * with the mean squared prediction error of its own neighbourhood (Vaseghi & Rayner; Godsill & Rayner ch. 5).  Input layout, sample
+ * types, channels / channel, output rows, scratch and limits are si_level_runs'.  For one channel x[0 .. n) (elements k * channels + c),
+ * values taken as the file's own numbers in float64 (the fp32 value, the PCM integer in its type's steps), with p = order, h = half,
+ * g = guard, B = 512:
+ *   peak, T   si_dead_runs': T = max(threshold, fl32(rel_threshold * peak)); with rel_threshold == 0 the peak is not computed.  T = 0
+ *             is allowed: the ratio test remains.
+ *   blocks    block b is [b B, min(n, (b + 1) B)); its fit window F_b = [max(0, b B - 256), min(n, (b + 1) B + 256)).
+ *   model     r[k] = the sum of w[t] * w[t + k] over t, t + k in F_b, k = 0 .. p, IN THIS ORDER: eight partial sums, partial q over
+ *             t = q, q + 8, q + 16, ... counted from F_b's first sample, each in index order starting from +0.0, then ((q0 + q1) + q2)
+ *             + ... + q7.  r[0] <- r[0] * (1 + 1e-9).  Levinson-Durbin, i = 1 .. p: a_0 = 1, E = r[0], kappa = -(r[i] + sum_{j=1}^{i-1}
+ *             a_j r[i - j]) / E (the sum in the order j = 1, 2, ...), a_j <- a_j + kappa * a_{i-j}, a_i = kappa, E <- E * (1 - kappa^2).
+ *             The model is a = (1, 0, ..., 0) when |F_b| <= p, r[0] == 0, or E <= 0 or non-finite at any step.
+ *   bad       badblk(b): a NaN or +-inf lies in F_b (counted with integers); then every t of the block is bad.
+ *   e(t)      for p <= t < n: a_0 * x[t] + a_1 * x[t - 1] + ... + a_p * x[t - p] with block(t)'s model, added in this order, float64, every
+ *             product and sum rounded on its own (no fused multiply-add).  x[t - j] in front of the block are the file's samples.
+ *             sq(t) = fl64(e * e).  t < p has no residual: it is never hot and lies in no window.
+ *   L(t), R(t)  [max(p, t - h), t - g - 1] and [t + g + 1, min(n - 1, t + h)], either may be empty; cnt(t) = |L| + |R|;
+ *             S(t) = the sum of sq over both, in float64 BY ADDITIONS ONLY (si_level_runs' rule; within cnt * 2^-52 * S of the exact sum).
+ *   hot(t)    t >= p; cnt(t) >= h - g; no bad sample is t or lies in L(t) or R(t); sq(t) > fl64((double)T * (double)T);
+ *             fl64(sq(t) * cnt(t)) > fl64(fl64((double)ratio * (double)ratio) * S(t)).  There is no division: a non-zero residual over an
+ *             all-zero neighbourhood (a click in digital silence) is hot, a zero residual never is.
+ *   dead(j)   hot(t) for some t with |t - j| <= pad and 0 <= t < n.
+ * channel >= 0 scans that channel (elements k * channels + channel, never the adjacent ones); channel = -1 is JOINT: a sample time is
+ * dead when EVERY channel's dead_c holds, against one T from the peak over all elements.  n <= p gives zero runs.
+ * The result is si_quiet_runs': sorted int32 (start, len) rows, rows [0, min(total, max_runs)) written, the total in n_runs, T in
+ * threshold_out when not NULL; plain stores, no atomics: the same input gives the same bytes.  Scratch is si_dead_runs'.  One workgroup
+ * holds its samples, residuals and window sums as float64 in LDS (135 168 bytes at half + pad = SI_IMPULSE_MAX_HALF).
+ * SI_EINVAL before any launch, naming the argument, for: everything si_level_runs refuses for the arguments they share; order outside
+ * 2 .. SI_IMPULSE_MAX_ORDER; guard outside 0 .. SI_IMPULSE_MAX_GUARD; half outside guard + 1 .. SI_IMPULSE_MAX_HALF; pad outside
+ * 0 .. SI_IMPULSE_MAX_PAD; half + pad above SI_IMPULSE_MAX_HALF; ratio NaN or outside [1, 1e6]; rel_threshold NaN or outside [0, 4].
+ *
+ * si_impulse_residual: e(t) itself, the whitened signal of ONE channel (0 <= channel < channels; channels = 1 is a mono file), through
+ * the same device functions as the detector: e[t] for t in [0, n) as device float64 -- 0.0 for t < p, NaN for a bad sample.  No
+ * scratch.  SI_EINVAL for channels / channel out of range, NULL x or e, n outside 1 .. 2^31 - 2049, order outside 2 .. 32. */
+#define SI_IMPULSE_MAX_ORDER 32
+#define SI_IMPULSE_MAX_HALF 1024
+#define SI_IMPULSE_MAX_GUARD 64
+#define SI_IMPULSE_MAX_PAD 16
+int si_impulse_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int order, int half, int guard, int pad,
+                    float ratio, float threshold, float rel_threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
+                    float* threshold_out, si_stream_t stream);
+int si_impulse_residual(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int order, double* e, si_stream_t stream);
 
 /* ---- Short damaged runs mended in place by least-squares AR interpolation ------------------------------------------
  * The detectors find a single NaN or a 3-sample underrun exactly; regenerating a 20 ms frame for it replaces good speech.  si_mend_runs

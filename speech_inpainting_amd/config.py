@@ -14,6 +14,8 @@ from typing import Optional, Union
 import torch
 import yaml
 
+from . import gaps as G
+
 
 class AttrDict(dict):
     """dict with attribute access (I_ea/hifi_gan/env.py:5-11)."""
@@ -87,6 +89,9 @@ class PredictConfig:
                                          # 4.31): runs of at most mend_ms milliseconds (at most 64 samples) are filled from their own
                                          # neighbourhood by least-squares AR interpolation instead of a generated frame; {mend_ms, mend_order:
                                          # 32, mend_context: 512}; None when `mend_ms:` is absent or 0: the run is what it was
+    detect_impulse: Optional[dict] = None  # `ratio:`, `order:`, `guard:` and `pad:` inside `detect:` with `kind: impulse`: clicks
+                                           # and pops by AR prediction error against its own neighbourhood's over `win_ms:` ({win_ms: 23.0}
+                                           # there); {ratio: 10.0, order: 16, guard: 4, pad: 2}; None at every other kind
 
     # derived exactly as the script does (I_ea/predict.py:85-90)
     @property
@@ -198,7 +203,7 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                     raise ValueError(f"{path}: long.{key} = {long_cfg[key]} is negative")
             if long_cfg["batch"] < 1 or long_cfg["clip_s"] <= 2 * long_cfg["context_s"]:
                 raise ValueError(f"{path}: `long:` needs batch >= 1 and clip_s > 2 * context_s, got {long_cfg}")
-        detect_cfg, detect_channels, detect_dead, detect_level, detect_mend = None, "each", None, None, None
+        detect_cfg, detect_channels, detect_dead, detect_level, detect_mend, detect_impulse = None, "each", None, None, None, None
         if "detect" in data:
             dm = data["detect"] if data["detect"] is not None else {}
             if not isinstance(dm, dict):
@@ -213,11 +218,12 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             detect_dead = {"kind": "quiet", "rel_threshold": 0.0, "held_tol": 0.0}
             if "kind" in dm:
                 detect_dead["kind"] = dm.pop("kind")
-                if detect_dead["kind"] not in ("quiet", "held", "any", "level", "burst", "invalid"):
+                if detect_dead["kind"] not in ("quiet", "held", "any", "level", "burst", "invalid", "impulse"):
                     raise ValueError(f"{path}: detect.kind = {detect_dead['kind']!r}: quiet (the default: |x| <= the threshold), held (a sample "
                                      f"repeated, a DC level) or any, or level (the RMS level of a window of win_ms milliseconds <= the threshold), "
                                      f"or burst (the RMS level of the second difference over a window of win_ms milliseconds >= the threshold), "
-                                     f"or invalid (NaN, inf and |x| > the threshold, the ceiling; 0 = no ceiling)")
+                                     f"or invalid (NaN, inf and |x| > the threshold, the ceiling; 0 = no ceiling), "
+                                     f"or impulse (clicks and pops: a sample's AR prediction error `ratio` times over that of its neighbourhood of win_ms milliseconds)")
             for key in ("rel_threshold", "held_tol"):
                 if key in dm:
                     detect_dead[key] = float(dm.pop(key))
@@ -231,18 +237,37 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
                     if detect_dead[key] != 0:
                         raise ValueError(f"{path}: detect.{key} = {detect_dead[key]} with `kind: invalid` (the ceiling is `threshold:`, in full-scale "
                                          f"units; nothing at this kind follows the peak or a neighbour)")
-            if detect_dead["rel_threshold"] > (4 if burst else 1):
+            impulse = detect_dead["kind"] == "impulse"               # a prediction error; the floor may reach 4 * the peak as well
+            if detect_dead["rel_threshold"] > (4 if burst or impulse else 1):
                 raise ValueError(f"{path}: detect.rel_threshold = {detect_dead['rel_threshold']} is a fraction of the file's peak, at most "
-                                 f"{'4 with `kind: burst`' if burst else 1}")
-            detect_level = {"win_ms": 4.0 if burst else 2.0}
+                                 f"{'4 with `kind: burst`' if burst else '4 with `kind: impulse`' if impulse else 1}")
+            detect_level = {"win_ms": G.IMPULSE_DEFAULTS["win_ms"] if impulse else 4.0 if burst else 2.0}
+            given = [key for key in ("ratio", "order", "guard", "pad") if key in dm]
+            if given and not impulse:
+                raise ValueError(f"{path}: detect.{given[0]} needs `kind: impulse` (kind: {detect_dead['kind']} has no prediction-error test)")
+            if impulse:
+                detect_impulse = {"ratio": float(dm.pop("ratio", G.IMPULSE_DEFAULTS["ratio"]))}
+                for key in ("order", "guard", "pad"):
+                    val = dm.pop(key, G.IMPULSE_DEFAULTS[key])
+                    if isinstance(val, bool) or int(val) != val:
+                        raise ValueError(f"{path}: detect.{key} = {val!r}: a whole number")
+                    detect_impulse[key] = int(val)
+                if not 1 <= detect_impulse["ratio"] <= 1e6:
+                    raise ValueError(f"{path}: detect.ratio = {detect_impulse['ratio']} is NaN or outside [1, 1e6] (10 is the default)")
+                if not 2 <= detect_impulse["order"] <= G.IMPULSE_MAX_ORDER:
+                    raise ValueError(f"{path}: detect.order = {detect_impulse['order']}, outside 2 .. {G.IMPULSE_MAX_ORDER} (16 is the default)")
+                if not 0 <= detect_impulse["guard"] <= G.IMPULSE_MAX_GUARD:
+                    raise ValueError(f"{path}: detect.guard = {detect_impulse['guard']} samples, outside 0 .. {G.IMPULSE_MAX_GUARD} (4 is the default)")
+                if not 0 <= detect_impulse["pad"] <= G.IMPULSE_MAX_PAD:
+                    raise ValueError(f"{path}: detect.pad = {detect_impulse['pad']} samples, outside 0 .. {G.IMPULSE_MAX_PAD} (2 is the default)")
             if "win_ms" in dm:
                 detect_level["win_ms"] = float(dm.pop("win_ms"))
-                if detect_dead["kind"] not in ("level", "burst"):
+                if detect_dead["kind"] not in ("level", "burst", "impulse"):
                     raise ValueError(f"{path}: detect.win_ms needs `kind: level` (kind: {detect_dead['kind']} judges sample by sample and has no window)"
                                      + (": `kind: invalid` takes threshold, min_ms, max_ms, pad_frames and channels" if invalid else ""))
                 if not 0 <= detect_level["win_ms"] < float("inf"):
                     raise ValueError(f"{path}: detect.win_ms = {detect_level['win_ms']} is negative or not finite")
-            if detect_dead["kind"] in ("level", "burst") and detect_dead["held_tol"] != 0:
+            if detect_dead["kind"] in ("level", "burst", "impulse") and detect_dead["held_tol"] != 0:
                 raise ValueError(f"{path}: detect.held_tol = {detect_dead['held_tol']} with `kind: {detect_dead['kind']}` (held samples are kind: held or any)")
             if "channels" in dm:
                 detect_channels = dm.pop("channels")
@@ -294,7 +319,8 @@ def load_predict_config(path: str = "predict.yaml") -> PredictConfig:
             asr_model_name=data.get("ASR_model", {}).get("model_name"),
             raw=data, masks=masks, patch_fade_ms=patch_fade_ms, long=long_cfg, long_rate=long_rate, long_feed=long_feed, long_clips16=long_clips16,
             long_pcm24=long_pcm24, detect=detect_cfg,
-            detect_channels=detect_channels, detect_dead=detect_dead, detect_level=detect_level, detect_mend=detect_mend)
+            detect_channels=detect_channels, detect_dead=detect_dead, detect_level=detect_level, detect_mend=detect_mend,
+            detect_impulse=detect_impulse)
     except KeyError as e:
         raise KeyError(f"{path}: missing key {e} (schema: I_ea/predict.yaml)") from None
 

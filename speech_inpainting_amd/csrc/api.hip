@@ -2082,6 +2082,40 @@ int si_invalid_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channel
                                   static_cast<hipStream_t>(stream));
 }
 
+// ---- clicks and pops by locally scaled AR prediction error
+int si_impulse_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int order, int half, int guard, int pad,
+                    float ratio, float threshold, float rel_threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
+                    float* threshold_out, si_stream_t stream) {
+    const char* fn = "si_impulse_runs";
+    if (!ctx) return SI_EINVAL;
+    if (quiet_runs_check(ctx, fn, true, x, n, channels, channel, threshold, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
+    if (order < 2 || order > SI_IMPULSE_MAX_ORDER) return SI_FAIL_FN("order = %d, outside 2 .. SI_IMPULSE_MAX_ORDER = %d", order, SI_IMPULSE_MAX_ORDER);
+    if (guard < 0 || guard > SI_IMPULSE_MAX_GUARD) return SI_FAIL_FN("guard = %d samples, outside 0 .. SI_IMPULSE_MAX_GUARD = %d", guard, SI_IMPULSE_MAX_GUARD);
+    if (half < guard + 1 || half > SI_IMPULSE_MAX_HALF)
+        return SI_FAIL_FN("half = %d samples, outside guard + 1 = %d .. SI_IMPULSE_MAX_HALF = %d", half, guard + 1, SI_IMPULSE_MAX_HALF);
+    if (pad < 0 || pad > SI_IMPULSE_MAX_PAD) return SI_FAIL_FN("pad = %d samples, outside 0 .. SI_IMPULSE_MAX_PAD = %d", pad, SI_IMPULSE_MAX_PAD);
+    if (half + pad > SI_IMPULSE_MAX_HALF) return SI_FAIL_FN("half + pad = %d samples, above SI_IMPULSE_MAX_HALF = %d", half + pad, SI_IMPULSE_MAX_HALF);
+    if (!(ratio >= 1.f && ratio <= 1e6f)) return SI_FAIL_FN("ratio = %g is NaN or outside [1, 1e6]", (double)ratio);
+    if (__builtin_isinf(threshold)) return SI_FAIL_FN("threshold = %g is not finite", (double)threshold);
+    if (!(rel_threshold >= 0.f && rel_threshold <= 4.f)) return SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 4]", (double)rel_threshold);
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
+    return si_launch_impulse_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, order, half, guard, pad, ratio, threshold, rel_threshold,
+                                  min_len, runs, max_runs, n_runs, threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
+}
+
+int si_impulse_residual(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int order, double* e, si_stream_t stream) {
+    const char* fn = "si_impulse_residual";
+    if (!ctx) return SI_EINVAL;
+    if (si_check_channels(ctx, fn, channels, channel, 0) != SI_OK) return SI_EINVAL;
+    if (!x) return SI_FAIL_FN("x is NULL");
+    if (!e) return SI_FAIL_FN("e is NULL");
+    if (n < 1 || (long)n > SI_MAX_REC) return SI_FAIL_FN("n = %d samples, outside 1 .. %ld", n, SI_MAX_REC);
+    if (order < 2 || order > SI_IMPULSE_MAX_ORDER) return SI_FAIL_FN("order = %d, outside 2 .. SI_IMPULSE_MAX_ORDER = %d", order, SI_IMPULSE_MAX_ORDER);
+    SI_HIP_CHECK(hipSetDevice(ctx->device));
+    return si_launch_impulse_residual(ctx, x, si_sample_format(is_pcm16), n, channels, channel, order, e, static_cast<hipStream_t>(stream));
+}
+
 // ---- short runs mended in place by least-squares AR interpolation
 int si_mend_runs(si_ctx* ctx, void* x, int is_pcm16, int n, int channels, int channel, const int32_t* runs, int n_runs, int max_len,
                  int order, int context, int32_t* status, si_stream_t stream) {

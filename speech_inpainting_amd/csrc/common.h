@@ -407,6 +407,13 @@ int si_launch_burst_runs(si_ctx* ctx, const void* x, int fmt, int n, int channel
 // channels as above (joint: every channel's element invalid)
 int si_launch_invalid_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float ceiling, int min_len, int32_t* runs,
                            int max_runs, int32_t* n_runs, char* scratch, hipStream_t st);
+// the maximal runs of samples within `pad` of an IMPULSE: a sample whose squared AR(order) prediction error is above
+// T^2 and above ratio^2 times the mean squared prediction error of the samples within `half` of it, `guard` on either side left out
+int si_launch_impulse_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int order, int half, int guard, int pad,
+                           float ratio, float thr, float rel, int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out,
+                           char* scratch, hipStream_t st);
+// that prediction error itself, one channel of the file -> e (n) device float64: 0.0 below `order`, NaN at a sample of a bad block
+int si_launch_impulse_residual(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int order, double* e, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // repair at the file's own sample rate (rate_kernels.hip)

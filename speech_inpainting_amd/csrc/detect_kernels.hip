@@ -8,6 +8,8 @@
 //   detect_level_kernel    a third pass 1: the bit means that a window of low RMS level reaches over the sample
 //   detect_burst_kernel    a fourth pass 1: the bit means that a window of LOUD second difference reaches over it
 //   detect_invalid_kernel, detect_invalid_ch_kernel  a fifth pass 1: the bit means that the sample's VALUE is invalid
+//   detect_impulse_kernel  a sixth pass 1: the bit means that a sample within `pad` of it has an AR prediction error far
+//                          above that of its own neighbourhood; detect_impulse_residual_kernel writes that prediction error itself
 //   detect_carry_kernel    carry[c] = the length of the quiet run that ends exactly in front of chunk c (a segmented scan, one workgroup)
 //   detect_runs_kernel     <false>: the qualifying runs that END in each chunk, counted; <true>: written at offset[c] + rank
 //   detect_offsets_kernel  the exclusive scan of the counts (one workgroup) and the total, a plain store
@@ -768,6 +770,222 @@ __global__ __launch_bounds__(256) void detect_invalid_ch_kernel(const T* __restr
     dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
 }
 
+// ------------------------------------------------------------------------------------------------ impulses
+// A sixth pass 1: sample j is DEAD when a sample within `pad` of it is HOT -- its squared AR prediction error stands `ratio`^2 over the
+// mean squared prediction error of its own neighbourhood.  For one channel, p = order, h = half, g = guard, blocks of IM_BLOCK = 512:
+//   model of block b   fitted to F_b = [max(0, 512 b - 256), min(n, 512 (b + 1) + 256)): r[k] = sum of w[t] w[t + k] over F_b, k = 0 .. p, AS
+//                      IM_PARTS = 8 INTERLEAVED PARTIAL SUMS (partial q takes t = q, q + 8, ... counted from F_b's first sample, in index
+//                      order, from +0.0) ADDED IN ORDER q = 0 .. 7; r[0] *= 1 + 1e-9; Levinson-Durbin as mend_kernels.hip runs it; the model
+//                      is (1, 0, ..., 0) when |F_b| <= p, r[0] == 0, or E <= 0 / non-finite at any step
+//   badblk(b)          a NaN or +-inf lies in F_b (an integer count): every sample of the block is `bad`
+//   e(t), p <= t < n   a_0 x[t] + a_1 x[t - 1] + ... + a_p x[t - p], added in this order, float64, nothing contracted; sq = fl64(e e)
+//   L(t), R(t)         [max(p, t - h), t - g - 1] and [t + g + 1, min(n - 1, t + h)]; cnt = |L| + |R|; S = the sum of sq over both, BY
+//                      ADDITIONS ONLY (two segmented scans with segments of h - g squares: a window is a suffix plus a prefix)
+//   hot(t)             t >= p, cnt >= h - g, no bad sample at t or in L or R, sq > T T, fl64(sq cnt) > fl64(fl64(ratio ratio) S)
+// The workgroup of chunk c fits the chunk's four blocks and `halo` = ceil((h + pad) / 512) blocks on either side (blocks outside the file
+// do not exist), so every residual its windows and its dilation reach comes from the model of the residual's own block, whichever
+// chunk computes it: the halo fits are redundant, not approximate.  Dynamic LDS: detect_sizes.h, dt_impulse_lds (135 168 bytes at halo 2).
+// LDS reads of 8 bytes (cdna_hip_programming.md section 2): the staging, the residual and the window loops run lane t on element
+// t + 256 k; the lag sums give eight consecutive lanes eight consecutive elements and the same second operand to each lag's eight; the
+// scans are lv_seg_scan / lv_count_scan with an odd `per`.
+struct ImBlock { int lo, hi, state; };                               // a block's fit window as image positions [lo, hi), and IM_*
+constexpr int IM_FIT = 0, IM_NONE = 1, IM_BAD = 2;
+
+__device__ __forceinline__ void im_stage(float v, double& d, int& nf) {
+    const bool finite = (__float_as_int(v) & 0x7fffffff) < 0x7f800000;
+    d = finite ? (double)v : 0.0;
+    nf = finite ? 0 : 1;
+}
+__device__ __forceinline__ void im_stage(int16_t v, double& d, int& nf) { d = (double)v; nf = 0; }
+__device__ __forceinline__ void im_stage(SiS24 v, double& d, int& nf) { d = (double)v.value(); nf = 0; }
+
+// The residuals of chunk c's blocks and of `halo` blocks on either side, for column `col` of the (n, ch) file: E[i] = e(q0 + i) for
+// image position i in [0, NQ), q0 = c0 - 512 halo, and 0.0 where there is none (a time outside [p, n), a bad block); bad[i] = 1 where
+// p <= time < n lies in a bad block.  X (NX doubles), E (NQ), part (NQ) and ints (2 NQ words; bad = ints) are the regions of
+// dt_impulse_lds.  Every thread of the workgroup calls it; it ends behind a barrier.
+template <typename T>
+__device__ __forceinline__ void im_residual_body(const T* __restrict__ x, int n, int ch, int col, int c0, int halo, int p, double* X, double* E,
+                                                 double* part, int* ints, int* sw) {
+#pragma clang fp contract(off)
+    __shared__ double a[IM_MAX_BLOCKS][IM_MAX_ORDER + 1], r[IM_MAX_BLOCKS][IM_MAX_ORDER + 1];
+    __shared__ ImBlock blk[IM_MAX_BLOCKS];
+    const int t = threadIdx.x;
+    const int NB = DT_CHUNK / IM_BLOCK + 2 * halo, NQ = dt_impulse_nq(halo), NX = dt_impulse_nx(halo);
+    const long q0 = (long)c0 - (long)IM_BLOCK * halo, x0 = q0 - IM_WING;          // the times of E[0] and X[0]
+    int* nf = ints;
+    // ---- the samples as float64, a non-finite one as 0.0 and counted; a time outside [0, n) does not exist and is not loaded
+    for (int i = t; i < NX; i += 256) {
+        const long time = x0 + i;
+        double v = 0.0;
+        int f = 0;
+        if (time >= 0 && time < n) im_stage(x[(size_t)time * ch + col], v, f);
+        X[i] = v;
+        nf[i] = f;
+    }
+    __syncthreads();
+    lv_count_scan(nf, NX, ((NX + 255) / 256) | 1, sw);
+    if (t < NB) {
+        const long b0 = q0 + (long)IM_BLOCK * t;                      // the block's first time; its fit window starts at image position 512 t
+        ImBlock k{0, 0, IM_NONE};
+        if (b0 >= 0 && b0 < n) {
+            k.lo = IM_BLOCK * t + (b0 < IM_WING ? IM_WING - (int)b0 : 0);
+            k.hi = IM_BLOCK * t + 2 * IM_WING + IM_BLOCK - (b0 + IM_BLOCK + IM_WING > n ? (int)(b0 + IM_BLOCK + IM_WING - n) : 0);
+            k.state = nf[k.hi - 1] - (k.lo > 0 ? nf[k.lo - 1] : 0) > 0 ? IM_BAD : IM_FIT;
+        }
+        blk[t] = k;
+    }
+    __syncthreads();
+    // ---- r[k] of every block that is fitted: IM_PARTS interleaved partial sums per lag, each by one thread in index order
+    for (int task = t; task < NB * (p + 1) * IM_PARTS; task += 256) {
+        const int sub = task % IM_PARTS, k = task / IM_PARTS % (p + 1), b = task / (IM_PARTS * (p + 1));
+        const ImBlock f = blk[b];
+        double acc = 0.0;
+        if (f.state == IM_FIT)
+            for (int i = f.lo + sub; i + k < f.hi; i += IM_PARTS) acc = acc + X[i] * X[i + k];
+        part[task] = acc;
+    }
+    __syncthreads();
+    // ---- Levinson-Durbin, one thread per block
+    if (t < NB && blk[t].state == IM_FIT) {
+        double* rr = r[t];
+        double* aa = a[t];
+        const double* pt = part + (size_t)t * (p + 1) * IM_PARTS;
+        for (int k = 0; k <= p; ++k) {
+            double acc = pt[k * IM_PARTS];
+            for (int q = 1; q < IM_PARTS; ++q) acc = acc + pt[k * IM_PARTS + q];
+            rr[k] = acc;
+            aa[k] = 0.0;
+        }
+        rr[0] = rr[0] * (1.0 + 1e-9);
+        aa[0] = 1.0;
+        bool delta = blk[t].hi - blk[t].lo <= p || rr[0] == 0.0;
+        if (!delta) {
+            double Ev = rr[0];
+            for (int i = 1; i <= p; ++i) {
+                double acc = rr[i];
+                for (int j = 1; j < i; ++j) acc = acc + aa[j] * rr[i - j];
+                const double kap = -acc / Ev;
+                for (int j = 1; 2 * j <= i; ++j) {
+                    const double lo = aa[j] + kap * aa[i - j], hi = aa[i - j] + kap * aa[j];
+                    aa[j] = lo;
+                    aa[i - j] = hi;
+                }
+                aa[i] = kap;
+                Ev = Ev * (1.0 - kap * kap);
+                if (!(Ev > 0.0) || !(Ev <= __DBL_MAX__)) { delta = true; break; }
+            }
+        }
+        if (delta) {
+            aa[0] = 1.0;
+            for (int k = 1; k <= p; ++k) aa[k] = 0.0;
+        }
+    }
+    __syncthreads();
+    // ---- the residuals: x[t - j] in front of the block are the file's samples, staged with the rest (j <= p <= IM_WING)
+    int* bad = ints;
+    for (int i = t; i < NQ; i += 256) {
+        const long time = q0 + i;
+        const int b = i / IM_BLOCK;
+        double e = 0.0;
+        int bd = 0;
+        if (time >= p && time < n) {
+            if (blk[b].state == IM_BAD) bd = 1;
+            else {
+                const double* aa = a[b];
+                const double* xt = X + i + IM_WING;
+                double acc = aa[0] * xt[0];
+                for (int j = 1; j <= p; ++j) acc = acc + aa[j] * xt[-j];
+                e = acc;
+            }
+        }
+        E[i] = e;
+        bad[i] = bd;
+    }
+    __syncthreads();
+}
+
+// grid (chunks), 256 threads, dynamic LDS dt_impulse_lds(halo).bytes, halo = dt_impulse_halo(h, pad).  x is (n, ch) interleaved (ch = 1: one
+// channel); channel >= 0 scans that channel, channel < 0 walks the channels one after another through the same image and ANDs their
+// bits.  Element offsets are 64-bit.  thr_dev, when given, holds T (pass 0); else T = thr.  Block 0 leaves T in *thr_out when asked.
+template <typename T>
+__global__ __launch_bounds__(256) void detect_impulse_kernel(const T* __restrict__ x, int n, int ch, int channel, int p, int h, int g, int pad,
+                                                             float ratio, float thr, const float* __restrict__ thr_dev, float* __restrict__ thr_out,
+                                                             uint8_t* __restrict__ bitmap, int32_t* __restrict__ lead, int32_t* __restrict__ trail) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) char im_img[];
+    __shared__ int sw[4];
+    __shared__ LvSeg ssw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    const int halo = dt_impulse_halo(h, pad), NQ = dt_impulse_nq(halo), base = IM_BLOCK * halo, wlen = h - g;
+    const int per = ((NQ + 255) / 256) | 1;
+    const DtImpulseLds at = dt_impulse_lds(halo);
+    double* X = reinterpret_cast<double*>(im_img + at.x);             // the samples, then S: the segment suffixes of the squares
+    double* E = reinterpret_cast<double*>(im_img + at.e);             // the residuals, then their squares
+    double* P = reinterpret_cast<double*>(im_img + at.p);             // the lag partial sums, then the segment prefixes of the squares
+    int* bad = reinterpret_cast<int*>(im_img + at.ints);              // 1 at a bad sample, then its prefix count
+    int* hot = bad + NQ;                                              // hot(q0 + i), then its prefix count
+    double* S = X;
+    const float Tq = thr_dev ? *thr_dev : thr;
+    if (thr_out && c == 0 && t == 0) *thr_out = Tq;
+    const double T2 = (double)Tq * (double)Tq, R2 = (double)ratio * (double)ratio;    // both exact
+    const long q0 = (long)c0 - base;
+    const int m = channel < 0 ? ch : 1;
+    unsigned b = 0xffu;
+    for (int k = 0; k < m; ++k) {
+        im_residual_body(x, n, ch, channel < 0 ? k : channel, c0, halo, p, X, E, P, bad, sw);
+        for (int i = t; i < NQ; i += 256) E[i] = E[i] * E[i];
+        __syncthreads();
+        lv_seg_scan<true>(E, S, NQ, per, wlen, ssw);
+        lv_seg_scan<false>(E, P, NQ, per, wlen, ssw);
+        lv_count_scan(bad, NQ, per, sw);
+        for (int i = t; i < NQ; i += 256) {
+            const long time = q0 + i;
+            int ht = 0;
+            if (i >= base - pad && i < base + DT_CHUNK + pad && time >= p && time < n) {
+                const int ql = i - h, qr = i + g + 1;                 // the two windows are positions [ql, i - g - 1] and [qr, i + h]
+                const double sl = ql % wlen == 0 ? S[ql] : S[ql] + P[ql + wlen - 1];
+                const double sr = qr % wlen == 0 ? S[qr] : S[qr] + P[qr + wlen - 1];
+                const double sum = sl + sr;
+                const long la = time - h > p ? time - h : p, rz = time + h < (long)n - 1 ? time + h : (long)n - 1;
+                const long cl = time - g - la > 0 ? time - g - la : 0, cr = rz - time - g > 0 ? rz - time - g : 0;
+                const int nb = (bad[i] - bad[i - 1]) + (bad[i - g - 1] - (ql > 0 ? bad[ql - 1] : 0)) + (bad[i + h] - bad[i + g]);
+                const double sq = E[i], cnt = (double)(cl + cr);
+                ht = (cl + cr >= wlen && nb == 0 && sq > T2 && sq * cnt > R2 * sum) ? 1 : 0;
+            }
+            hot[i] = ht;
+        }
+        __syncthreads();
+        lv_count_scan(hot, NQ, per, sw);
+        unsigned bk = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = base + t * 8 + j;                           // hot on times within pad = positions [i - pad, i + pad]
+            const int cnt = hot[i + pad] - hot[i - pad - 1];
+            bk |= (t * 8 + j < len && cnt > 0) ? 1u << j : 0u;
+        }
+        b &= bk;
+        __syncthreads();                                              // the next channel stages over the image
+    }
+    dt_store_chunk(b, c, len, bitmap, lead, trail, sw);
+}
+
+// The whitened signal itself (si_impulse_residual): the same body with no halo, then e[c0 + i] = the residual of the chunk's sample i --
+// 0.0 for a time below p, NaN for a bad sample.  grid (chunks), 256 threads, dynamic LDS dt_impulse_lds(0).bytes.
+template <typename T>
+__global__ __launch_bounds__(256) void detect_impulse_residual_kernel(const T* __restrict__ x, int n, int ch, int channel, int p,
+                                                                      double* __restrict__ e) {
+    extern __shared__ __attribute__((aligned(16))) char im_img[];
+    __shared__ int sw[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int c0 = c * DT_CHUNK, len = min(DT_CHUNK, n - c0);
+    const DtImpulseLds at = dt_impulse_lds(0);
+    double* E = reinterpret_cast<double*>(im_img + at.e);
+    int* bad = reinterpret_cast<int*>(im_img + at.ints);
+    im_residual_body(x, n, ch, channel, c0, 0, p, reinterpret_cast<double*>(im_img + at.x), E, reinterpret_cast<double*>(im_img + at.p), bad, sw);
+    for (int i = t; i < len; i += 256) e[(size_t)c0 + i] = bad[i] ? __builtin_nan("") : E[i];
+}
+
 // ------------------------------------------------------------------------------------------------ launcher
 size_t si_detect_scratch_bytes(int n) { return dt_scratch(n).bytes; }     // the bitmap, six words per chunk and {peak, T} (detect_sizes.h)
 
@@ -779,6 +997,8 @@ struct DtLevel { int half; float rel; float* thr_out; };
 struct DtBurst { int half; float rel; float* thr_out; };
 // What si_invalid_runs adds instead: the ceiling of detect_invalid(_ch)_kernel.  No pass 0 and no threshold out.
 struct DtInvalid { float ceiling; };
+// What si_impulse_runs adds instead: the model order, the window, and the ratio, for detect_impulse_kernel.
+struct DtImpulse { int order, half, guard, pad; float ratio, rel; float* thr_out; };
 
 // The caller (si_quiet_runs, si_quiet_runs_ch) checked every argument.  scratch: si_detect_scratch_bytes(n) bytes, 16-byte aligned.
 // channels = 0: x is one channel of n samples (detect_bits_kernel); channels >= 1: x is interleaved, n sample times of `channels`
@@ -787,10 +1007,11 @@ struct DtInvalid { float ceiling; };
 // level != nullptr (dead is nullptr then): pass 1 is detect_level_kernel, behind the same pass 0 when level->rel > 0.
 // burst != nullptr (dead and level are nullptr then): pass 1 is detect_burst_kernel, behind the same pass 0 when burst->rel > 0.
 // invalid != nullptr (the other three are nullptr then): pass 1 is detect_invalid(_ch)_kernel, never behind a pass 0; thr is not read.
+// impulse != nullptr (the other four are nullptr then): pass 1 is detect_impulse_kernel, behind the same pass 0 when impulse->rel > 0.
 template <typename T>
 static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
                      int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead, const DtLevel* level, const DtBurst* burst,
-                     const DtInvalid* invalid) {
+                     const DtInvalid* invalid, const DtImpulse* impulse) {
     const int chunks = dt_chunks(n);
     const DtScratch at = dt_scratch(n);
     uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch + at.bitmap);
@@ -804,7 +1025,32 @@ static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel
     const double bits = (double)chunks * 256.0, sums = (double)chunks * 4.0;
     const double samples = (double)n * (channels ? channels : 1) * (double)sizeof(T);
 
-    if (invalid) {
+    if (impulse) {
+        // pass 0 as the descriptor routes below run it, then the impulse pass; profiled in their pass 1's family: the lists of families are closed
+        const float* thr_dev = nullptr;
+        if (impulse->rel > 0.f) {
+            si_prof_begin(ctx, "detect_peak", 0.0, samples + sums, st);
+            if (channels == 0) {
+                detect_peak_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, cpeak);
+            } else {
+                detect_peak_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, cpeak);
+            }
+            si_prof_end(ctx, st);
+            SI_HIP_CHECK(hipGetLastError());
+            si_prof_begin(ctx, "detect_peak_final", 0.0, sums + 8.0, st);
+            detect_peak_final_kernel<<<dim3(1), 256, 0, st>>>(cpeak, chunks, thr, impulse->rel, pk);
+            si_prof_end(ctx, st);
+            SI_HIP_CHECK(hipGetLastError());
+            thr_dev = pk + 1;
+        }
+        const int ch = channels ? channels : 1;
+        const size_t lds = dt_impulse_lds(dt_impulse_halo(impulse->half, impulse->pad)).bytes;    // 135 168 bytes at half + pad = 1024
+        const void* kern = reinterpret_cast<const void*>(&detect_impulse_kernel<T>);
+        if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
+        si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
+        detect_impulse_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, channels ? channel : 0, impulse->order, impulse->half, impulse->guard,
+                                                                impulse->pad, impulse->ratio, thr, thr_dev, impulse->thr_out, bitmap, lead, trail);
+    } else if (invalid) {
         // profiled in the families of the quiet routes' pass 1, whose shape these kernels have: the lists of families are closed
         if (channels == 0) {
             si_prof_begin(ctx, "detect_bits", 0.0, samples + bits + 2.0 * sums, st);
@@ -894,10 +1140,10 @@ static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel
 
 static int dt_launch(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
                      int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr, const DtLevel* level = nullptr,
-                     const DtBurst* burst = nullptr, const DtInvalid* invalid = nullptr) {
+                     const DtBurst* burst = nullptr, const DtInvalid* invalid = nullptr, const DtImpulse* impulse = nullptr) {
     int rc = SI_OK;
     si_with_sample(fmt, [&](auto tag) {
-        rc = dt_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st, dead, level, burst, invalid);
+        rc = dt_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st, dead, level, burst, invalid, impulse);
     });
     return rc;
 }
@@ -941,4 +1187,32 @@ int si_launch_invalid_runs(si_ctx* ctx, const void* x, int fmt, int n, int chann
     const DtInvalid invalid{ceiling};
     return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, 0.f, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
                      nullptr, nullptr, &invalid);
+}
+
+// The impulses; channels = 1 is a one-channel file, as for si_launch_dead_runs.
+int si_launch_impulse_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int order, int half, int guard, int pad,
+                           float ratio, float thr, float rel, int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out,
+                           char* scratch, hipStream_t st) {
+    const DtImpulse impulse{order, half, guard, pad, ratio, rel, thr_out};
+    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
+                     nullptr, nullptr, nullptr, &impulse);
+}
+
+// The residual of one channel (si_impulse_residual): one launch, no scratch.  channels = 1 is a one-channel file.
+template <typename T>
+static int im_residual_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel, int order, double* e, hipStream_t st) {
+    const size_t lds = dt_impulse_lds(0).bytes;                       // 69 632 bytes
+    const void* kern = reinterpret_cast<const void*>(&detect_impulse_residual_kernel<T>);
+    if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
+    si_prof_begin(ctx, "detect_dead", 0.0, (double)n * channels * (double)sizeof(T) + (double)n * 8.0, st);
+    detect_impulse_residual_kernel<T><<<dim3(dt_chunks(n)), 256, lds, st>>>(x, n, channels, channel, order, e);
+    si_prof_end(ctx, st);
+    SI_HIP_CHECK(hipGetLastError());
+    return SI_OK;
+}
+
+int si_launch_impulse_residual(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int order, double* e, hipStream_t st) {
+    int rc = SI_OK;
+    si_with_sample(fmt, [&](auto tag) { rc = im_residual_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, order, e, st); });
+    return rc;
 }

@@ -50,6 +50,13 @@ def ida_match_lengths(n_audio: int, n_code: int, n_f0: int, code_hop: int = 320,
     return a, c, ci, f
 
 
+class _Unset(float):
+    """A keyword's default that can be told from the same number passed in: it compares and prints as the float."""
+
+
+_WIN_MS = _Unset(2.0)                      # win_ms "not given": 2 ms at kinds level and burst as ever, 23 ms at kind impulse (DESIGN.md 4.33)
+
+
 class InpaintingEngine:
     """One model pair (HuBERT + head, codebook, HiFi-GAN generator) resident on one GPU."""
 
@@ -1016,7 +1023,8 @@ class InpaintingEngine:
     def conceal_file(self, x, sr: int, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
                      merge_frames: Optional[int] = None, fade_ms: float = 5.0, clip_frames: int = 200, min_context: int = 50, batch: int = 32,
                      return_windows: bool = False, feed: str = "recording", detect: str = "each", kind: str = "quiet",
-                     rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = 2.0, clips16: str = "resampled",
+                     rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = _WIN_MS, clips16: str = "resampled",
+                     impulse_order: int = 16, impulse_guard: int = 4, impulse_pad: int = 2, impulse_ratio: float = 10.0,
                      mend_ms: float = 0.0, mend_order: int = 32, mend_context: int = 512) -> Dict[str, object]:
         """File in, repaired file out, at the file's own rate and in its own sample type: find_gaps on x itself, where a dropout is
         still exact zeros, then patch_file with the gaps it found.  The usable frames are those of the recording's 22.05 kHz length
@@ -1045,7 +1053,11 @@ class InpaintingEngine:
         detect="each" mends every channel's own runs; detect="joint" mends the joint runs in every channel and a run leaves the gap
         list only if every channel filled it.  The dictionary gains `mended`: host rows (start, len, status) of every run of at most
         max_len samples, one list per channel where `gaps` is one (joint: one list; a row's status is AR or LINE when every channel
-        filled it -- LINE if any did by the line -- else the first channel's status that is no fill).  An edge run stays `skipped`."""
+        filled it -- LINE if any did by the line -- else the first channel's status that is no fill).  An edge run stays `skipped`.
+        kind "impulse" with win_ms and impulse_order / _guard / _pad / _ratio: find_gaps' -- clicks and pops of one to a
+        few in-range samples.  Pass min_ms=0 (a click is a run of a few samples; the 5 ms default drops nearly all of them) and
+        mend_ms=1.0: conceal_file(kind="impulse", min_ms=0, mend_ms=1.0) detects, mends in place, and hands what comes back NEAR, EDGE
+        or LONG to the inpainter.  mend_ms=0 stays legal and costs a generated 20 ms frame per click."""
         sr, clip_frames, min_context = int(sr), int(clip_frames), int(min_context)
         if detect not in ("each", "joint"):
             raise ValueError(f"conceal_file: detect = {detect!r}: 'each' or 'joint'")
@@ -1081,7 +1093,8 @@ class InpaintingEngine:
             max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
         fade22 = -(-G.file_fade(fade_ms, sr) * P // Q)
         find = lambda c: self.find_gaps(x, sr, threshold, min_ms, max_ms, pad_frames, merge_frames, fade22, n_rec, lim, channel=c, kind=kind,
-                                        rel_threshold=rel_threshold, held_tol=held_tol, **({"win_ms": win_ms} if kind in ("level", "burst") else {}))
+                                        rel_threshold=rel_threshold, held_tol=held_tol, **({"win_ms": win_ms} if kind in ("level", "burst") else {}),
+                                        **(self._impulse_keywords(win_ms, impulse_order, impulse_guard, impulse_pad, impulse_ratio) if kind == "impulse" else {}))
         kw = dict(fade_ms=fade_ms, clip_frames=clip_frames, min_context=min_context, batch=batch, return_windows=return_windows, feed=feed)
         if clips16 != "resampled":                                     # the default: patch_file is called as it was
             kw["clips16"] = clips16
@@ -1275,6 +1288,67 @@ class InpaintingEngine:
         runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
         return (runs, T) if return_threshold else runs
 
+    def find_impulse_runs(self, x, win: Optional[int] = None, half: Optional[int] = None, order: int = 16, guard: int = 4, pad: int = 2,
+                          ratio: float = 10.0, threshold: float = 0.0, rel_threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536,
+                          channel: Optional[int] = None, return_threshold: bool = False):
+        """find_burst_runs for clicks and pops of one to a few IN-RANGE samples (si_impulse_runs).  The signal is whitened
+        by an AR model of order `order` fitted per block of 512 samples (to the block and 256 samples on either side); a sample is HOT
+        when its squared prediction error is above T^2, T = max(threshold, rel_threshold * the peak of x), and above ratio^2 times the
+        mean squared prediction error of the samples within `half` of it, `guard` samples on either side left out; a sample is dead
+        when a hot one lies within `pad` of it.  win = 2 * half + 1.  T = 0 (the default) is allowed: the ratio test remains.  x,
+        channel, min_len, max_runs and the rows are find_level_runs'; rel_threshold lies in [0, 4].
+        One D2H copy: the count, which with return_threshold=True also carries T; -> runs, or (runs, T)."""
+        if (win is None) == (half is None):
+            raise ValueError("find_impulse_runs: give the window as win = its odd length in samples, or as half = (win - 1) / 2, not both")
+        if win is not None:
+            if int(win) != win or int(win) < 1 or int(win) % 2 == 0:
+                raise ValueError(f"find_impulse_runs: win = {win}: an odd number of samples, 2 * half + 1")
+            half = (int(win) - 1) // 2
+        G.check_impulse("find_impulse_runs", order, half, guard, pad, ratio, rel_threshold)
+        x = torch.as_tensor(x)
+        s24, sdim = InpaintingEngine._file_samples(x, "find_impulse_runs")                    # packed 24-bit PCM: uint8 (n, 3) or (n, ch, 3), 24-bit steps
+        many = sdim == 2 and x.shape[1] >= 2
+        if many and channel is None:
+            raise ValueError(f"find_impulse_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
+        if not many and channel is not None and int(channel) not in (-1, 0):
+            raise ValueError(f"find_impulse_runs: channel = {channel} of a one-channel recording")
+        x = InpaintingEngine._file_on_device(x, self.device)
+        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
+        words = torch.zeros(2, dtype=torch.int32, device=self.device)      # {the count, T's bits}: one copy brings both
+        runs, _ = self.ctx.impulse_runs(x, int(order), int(half), int(guard), int(pad), ratio, threshold, rel_threshold, min_len, max_runs,
+                                        n_runs=words[:1], channel=int(channel) if many else None, threshold_out=words[1:].view(torch.float32))
+        host = words.cpu()
+        total, T = int(host[0]), float(host[1:].view(torch.float32)[0])
+        if total > int(max_runs):
+            raise ValueError(f"find_impulse_runs: {total} runs of at least {int(min_len)} dead samples, more than max_runs = {int(max_runs)}")
+        runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+        return (runs, T) if return_threshold else runs
+
+    def impulse_residual(self, x, order: int = 16, channel: Optional[int] = None) -> torch.Tensor:
+        """The whitened signal find_impulse_runs judges (si_impulse_residual): e(t) = sum_j a_j x[t - j] under the AR
+        model of t's block, as a device float64 tensor (n,) -- 0.0 for t < order, NaN in a block whose fit window holds a NaN or an
+        inf.  x is find_impulse_runs'; an (n, ch >= 2) file needs channel = an index."""
+        if int(order) != order or not 2 <= int(order) <= native.IMPULSE_MAX_ORDER:
+            raise ValueError(f"impulse_residual: order = {order}, outside 2 .. {native.IMPULSE_MAX_ORDER}")
+        x = torch.as_tensor(x)
+        s24, sdim = InpaintingEngine._file_samples(x, "impulse_residual")
+        many = sdim == 2 and x.shape[1] >= 2
+        if many and (channel is None or not 0 <= int(channel) < x.shape[1]):
+            raise ValueError(f"impulse_residual: an (n, {x.shape[1]}) recording needs channel = an index in 0 .. {x.shape[1] - 1}")
+        if not many and channel is not None and int(channel) != 0:
+            raise ValueError(f"impulse_residual: channel = {channel} of a one-channel recording")
+        x = InpaintingEngine._file_on_device(x, self.device)
+        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
+        return self.ctx.impulse_residual(x, int(order), channel=int(channel) if many else None)
+
+    @staticmethod
+    def _impulse_keywords(win_ms, order, guard, pad, ratio) -> Dict[str, object]:
+        """What conceal_* hand find_gaps at kind "impulse" and at no other: the four impulse_* keywords, and win_ms when it was given."""
+        kw = {"impulse_order": order, "impulse_guard": guard, "impulse_pad": pad, "impulse_ratio": ratio}
+        if win_ms is not _WIN_MS:
+            kw["win_ms"] = win_ms
+        return kw
+
     def find_invalid_runs(self, x, ceiling: float = float("inf"), min_len: int = 1, max_runs: int = 65536,
                           channel: Optional[int] = None) -> torch.Tensor:
         """find_quiet_runs for a file whose damage is the sample VALUES (si_invalid_runs): every maximal run of at least
@@ -1381,7 +1455,8 @@ class InpaintingEngine:
     def find_gaps(self, x, sr: int = 22050, threshold: float = 0.0, min_ms: float = 5.0, max_ms: float = 400.0, pad_frames: int = 0,
                   merge_frames: Optional[int] = None, fade: int = 110, n_rec_frames: Optional[int] = None,
                   lim_frames: Optional[int] = None, channel: Optional[int] = None, kind: str = "quiet", rel_threshold: float = 0.0,
-                  held_tol: float = 0.0, win_ms: float = 2.0) -> Dict[str, object]:
+                  held_tol: float = 0.0, win_ms: float = _WIN_MS, impulse_order: int = 16, impulse_guard: int = 4, impulse_pad: int = 2,
+                  impulse_ratio: float = 10.0) -> Dict[str, object]:
         """The dropouts of a recording x (n samples at `sr` Hz, fp32 in full-scale units, int16 PCM or packed 24-bit PCM): runs of at least min_ms of
         |x| <= threshold (find_quiet_runs), mapped by gaps.runs_to_gaps onto the 20 ms grid of the recording's n_rec_frames frames
         (default n * 50 // sr) with the usable frames [0, lim_frames).  merge_frames None = 2 * the frames one cross-fade of `fade`
@@ -1401,7 +1476,17 @@ class InpaintingEngine:
         kind "invalid" (DESIGN.md 4.30): the runs are find_invalid_runs' -- samples that are NaN, +-inf or, with threshold != 0, of a
         magnitude above `threshold`, the CEILING in x's own units (threshold = 0, the default, is +inf: the non-finite samples only).
         rel_threshold and held_tol must be 0; win_ms is not read.  min_ms keeps its meaning and its default: pass min_ms=0 for this
-        kind, a single NaN is a run of one sample.  `threshold` carries the ceiling."""
+        kind, a single NaN is a run of one sample.  `threshold` carries the ceiling.
+        kind "impulse" (DESIGN.md 4.33): the runs are find_impulse_runs' -- clicks and pops of one to a few IN-RANGE samples: a sample
+        whose squared AR(impulse_order) prediction error stands impulse_ratio^2 over the mean squared prediction error of the samples
+        within win_ms / 2 of it (23 ms when win_ms is not given, half = round(win_ms * sr / 2000)), impulse_guard samples on either side
+        left out, widened by impulse_pad samples.  threshold / rel_threshold set a floor T under the prediction error (0: none);
+        held_tol must be 0.  min_ms keeps its meaning and its default: pass min_ms=0 for this kind, or nearly every click is dropped.
+        The impulse_* keywords are read at no other kind.  `threshold` carries T.  The defaults were chosen on 22.05 kHz int16 speech;
+        other rates, fp32 material and music are unmeasured."""
+        impulse = kind == "impulse"
+        if win_ms is _WIN_MS:                                          # not given: 2 ms, as ever; 23 ms at kind "impulse"
+            win_ms = G.IMPULSE_DEFAULTS["win_ms"] if impulse else 2.0
         x = torch.as_tensor(x)
         s24, sdim = InpaintingEngine._file_samples(x, "find_gaps")                 # packed 24-bit PCM (DESIGN.md 4.27): thresholds in 24-bit steps
         n, sr = (x.shape[0] if sdim == 2 or s24 else x.numel()), int(sr)
@@ -1424,6 +1509,14 @@ class InpaintingEngine:
                                  "Start from threshold = 1.15 of full scale (1.15 * 32768 for int16, 1.15 * 2^23 for 24-bit) with win_ms = 4.0")
             runs, T = self.find_burst_runs(x, half=G.level_half(win_ms, sr), threshold=threshold, rel_threshold=rel_threshold, min_len=min_len,
                                            channel=channel, return_threshold=True)
+        elif impulse:
+            if float(held_tol) != 0.0:
+                raise ValueError(f"find_gaps: held_tol = {held_tol} with kind = 'impulse' (held samples are kind 'held' or 'any')")
+            half = G.level_half(win_ms, sr)
+            G.check_impulse("find_gaps", impulse_order, half, impulse_guard, impulse_pad, impulse_ratio, rel_threshold, win_ms=win_ms, sr=sr)
+            runs, T = self.find_impulse_runs(x, half=half, order=impulse_order, guard=impulse_guard, pad=impulse_pad, ratio=impulse_ratio,
+                                             threshold=threshold, rel_threshold=rel_threshold, min_len=min_len, channel=channel,
+                                             return_threshold=True)
         elif kind == "invalid":
             if float(rel_threshold) != 0.0:
                 raise ValueError(f"find_gaps: rel_threshold = {rel_threshold} with kind = 'invalid' (the ceiling is `threshold`, in the file's own units; "
@@ -1444,7 +1537,8 @@ class InpaintingEngine:
     def conceal_recording(self, wave22, wave16=None, detect_on=None, sr: int = 22050, threshold: float = 0.0, min_ms: float = 5.0,
                           max_ms: float = 400.0, pad_frames: int = 0, merge_frames: Optional[int] = None, fade: int = 110,
                           clip_frames: int = 200, min_context: int = 50, batch: int = 32, pcm: bool = False, kind: str = "quiet",
-                          rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = 2.0) -> Dict[str, object]:
+                          rel_threshold: float = 0.0, held_tol: float = 0.0, win_ms: float = _WIN_MS, impulse_order: int = 16,
+                          impulse_guard: int = 4, impulse_pad: int = 2, impulse_ratio: float = 10.0) -> Dict[str, object]:
         """File in, repaired file out: find_gaps, then patch_recording unchanged with the gaps it found.  Detection runs on detect_on
         when given -- the file's own samples at `sr` Hz, where a dropout is still exact zeros -- else on wave22 (sr is 22050 then).
         The usable frames are patch_recording's own (its last context's min(T, Tm)), and a gap longer than the planner's budget
@@ -1454,6 +1548,8 @@ class InpaintingEngine:
         kind "burst" with win_ms: find_gaps' too (a block of corrupted PCM, by second-difference level).
         kind "invalid": find_gaps' too (NaN, +-inf, |x| > threshold when threshold != 0) -- pass min_ms=0.  The ceiling
         goes on to patch_recording(ceiling=...); detect_on is refused, because the samples that are fed must be the ones that were judged.
+        kind "impulse" with win_ms and impulse_*: find_gaps' too (clicks and pops) -- pass min_ms=0.  Nothing is mended
+        here: every click costs a generated frame (conceal_file has mend_ms).
         -> patch_recording's dictionary + gaps + skipped [+ threshold].  With nothing found: an exact copy; only the detection kernels launched."""
         if kind == "invalid" and detect_on is not None:
             raise ValueError("conceal_recording: kind = 'invalid' with detect_on: the samples that are fed to the model (wave22) must be the ones "
@@ -1467,7 +1563,8 @@ class InpaintingEngine:
             max_ms = min(float(max_ms), 20.0 * (clip_frames - 2 * min_context))
         found = self.find_gaps(wave22 if detect_on is None else detect_on, 22050 if detect_on is None else sr, threshold, min_ms, max_ms,
                                pad_frames, merge_frames, fade, n_rec, lim, kind=kind, rel_threshold=rel_threshold, held_tol=held_tol,
-                               **({"win_ms": win_ms} if kind in ("level", "burst") else {}))
+                               **({"win_ms": win_ms} if kind in ("level", "burst") else {}),
+                               **(self._impulse_keywords(win_ms, impulse_order, impulse_guard, impulse_pad, impulse_ratio) if kind == "impulse" else {}))
         kc = {"ceiling": G.invalid_ceiling(threshold)} if kind == "invalid" else {}      # no other kind hands patch_recording a new keyword
         out = self.patch_recording(wave22, found["gaps"], wave16=wave16, fade=fade, clip_frames=clip_frames, min_context=min_context,
                                    batch=batch, pcm=pcm, **kc)

@@ -466,6 +466,41 @@ def level_half(win_ms: float, sr: int) -> int:
     return half
 
 
+# kind "impulse" (DESIGN.md 4.33): what find_gaps, conceal_* and `detect: {kind: impulse}` use when a key is not given.  Chosen on
+# 22.05 kHz int16 speech; other rates, fp32 material and music are unmeasured.
+IMPULSE_DEFAULTS = dict(order=16, win_ms=23.0, guard=4, pad=2, ratio=10.0)
+IMPULSE_MAX_ORDER, IMPULSE_MAX_HALF, IMPULSE_MAX_GUARD, IMPULSE_MAX_PAD = 32, 1024, 64, 16   # SI_IMPULSE_MAX_* of include/si_hip.h
+
+
+def check_impulse(who: str, order, half, guard, pad, ratio, rel_threshold=0.0, win_ms: Optional[float] = None, sr: Optional[int] = None) -> None:
+    """What si_impulse_runs would refuse about its own arguments, as a ValueError that names the fix.  `half` is in samples; with win_ms
+    and sr the message speaks of the window in milliseconds as well."""
+    ints = {"order": order, "half": half, "guard": guard, "pad": pad}
+    for k, v in ints.items():
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{who}: {k} = {v!r}: a whole number of samples" if k != "order" else f"{who}: order = {v!r}: a whole number")
+    order, half, guard, pad = int(order), int(half), int(guard), int(pad)
+    if not 2 <= order <= IMPULSE_MAX_ORDER:
+        raise ValueError(f"{who}: order = {order}, outside 2 .. {IMPULSE_MAX_ORDER}: 16 is the default")
+    if not 0 <= guard <= IMPULSE_MAX_GUARD:
+        raise ValueError(f"{who}: guard = {guard} samples, outside 0 .. {IMPULSE_MAX_GUARD}: 4 is the default")
+    if not 0 <= pad <= IMPULSE_MAX_PAD:
+        raise ValueError(f"{who}: pad = {pad} samples, outside 0 .. {IMPULSE_MAX_PAD}: 2 is the default")
+    at = f" (win_ms = {win_ms} at {sr} Hz)" if win_ms is not None and sr is not None else ""
+    if half < guard + 1:
+        need = f": raise win_ms to {2000.0 * (guard + 1) / sr:.3f} or more, or lower guard" if at else ": widen the window or lower guard"
+        raise ValueError(f"{who}: half = {half} samples{at} is under guard + 1 = {guard + 1}: no sample would be left to compare with{need}")
+    if half + pad > IMPULSE_MAX_HALF:
+        need = f": lower win_ms to {math.floor(2000.0 * (IMPULSE_MAX_HALF - pad) / sr * 1000.0) / 1000.0} or less" if at else ""
+        raise ValueError(f"{who}: half + pad = {half + pad} samples{at}, above {IMPULSE_MAX_HALF}{need}")
+    if not 1.0 <= float(ratio) <= 1e6:
+        raise ValueError(f"{who}: ratio = {ratio} is NaN or outside [1, 1e6]: how many times its neighbourhood's RMS prediction error a sample's "
+                         f"must stand above; 10 is the default")
+    if not 0.0 <= float(rel_threshold) <= 4.0:
+        raise ValueError(f"{who}: rel_threshold = {rel_threshold} is NaN or outside [0, 4]: the floor under the prediction error as a fraction of the peak, "
+                         f"0 for none")
+
+
 def file_spans(gaps: Sequence[Gap], sr: int) -> List[Gap]:
     """(start, len) in FILE samples per gap (first frame, frame count) of the 20 ms grid: samples [ceil(p * sr / 50),
     ceil((p + l) * sr / 50)) -- exactly the file samples whose 22.05 kHz position lies in [441 p, 441 (p + l)).  Integers only."""

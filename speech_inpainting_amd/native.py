@@ -33,12 +33,14 @@ EXPORTS = ["si_version", "si_create", "si_destroy", "si_last_error", "si_load_we
            "si_cut_clips", "si_patch_regions", "si_quiet_runs", "si_patch_rate", "si_cut_rate",
            "si_quiet_runs_ch", "si_cut_rate_ch", "si_patch_rate_ch", "si_dead_runs", "si_level_runs", "si_cut_pair", "si_cut_pair_ch",
            "si_plan_weights", "si_pack_weights_host", "si_burst_runs",
-           "si_invalid_runs", "si_cut_rate_valid", "si_cut_pair_valid", "si_cut_clips_valid", "si_mend_runs"]
+           "si_invalid_runs", "si_cut_rate_valid", "si_cut_pair_valid", "si_cut_clips_valid", "si_mend_runs",
+           "si_impulse_runs", "si_impulse_residual"]
 SI_MAX_SPANS = 16
 SI_MAX_CHANNELS = 8                        # channels of an interleaved file
 SAMPLE_F32, SAMPLE_S16, SAMPLE_S24 = 0, 1, 2   # SI_SAMPLE_*: the file-typed calls' sample types; s24 = uint8 (..., 3)
 DEAD_QUIET, DEAD_HELD = 1, 2               # SI_DEAD_QUIET, SI_DEAD_HELD: the `kind` bits of si_dead_runs
 LEVEL_MAX_HALF = 1024                      # SI_LEVEL_MAX_HALF: the largest half window of si_level_runs
+IMPULSE_MAX_ORDER, IMPULSE_MAX_HALF, IMPULSE_MAX_GUARD, IMPULSE_MAX_PAD = 32, 1024, 64, 16   # SI_IMPULSE_MAX_*: the limits of si_impulse_runs
 MEND_MAX_LEN, MEND_MAX_ORDER, MEND_MAX_CONTEXT, MEND_MAX_RUNS = 64, 32, 1024, 65536   # SI_MEND_MAX_*: the limits of si_mend_runs
 MEND_LONG, MEND_AR, MEND_LINE, MEND_EDGE, MEND_NEAR, MEND_NONFINITE, MEND_BADROW = 0, 1, 2, 3, 4, 5, 6   # SI_MEND_*: a row's status
 MEND_STATUS = ("LONG", "AR", "LINE", "EDGE", "NEAR", "NONFINITE", "BADROW")                         # their names, by code
@@ -396,6 +398,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                       vp, vp, vp]
     lib.si_cut_clips_valid.argtypes = [vp, vp, i32, vp, vp, i32, i32, C.c_float, vp, vp]
     lib.si_mend_runs.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp]
+    lib.si_impulse_runs.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp]
+    lib.si_impulse_residual.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
     lib.si_plan_weights.argtypes = [C.POINTER(ModelDesc), C.POINTER(sz)]
     lib.si_pack_weights_host.argtypes = [C.POINTER(ModelDesc), vp, sz, C.c_char_p, vp, sz, C.POINTER(sz), C.c_char_p, sz]
     lib.si_num_frames.argtypes = [vp, i32]
@@ -942,6 +946,43 @@ class NativeContext:
                                              int(channel) if channel is not None else 0, float(ceiling), int(min_len), _ptr(runs), max_runs,
                                              _ptr(n_runs), self._stream()), "si_invalid_runs")
         return runs, n_runs
+
+    # ---- clicks and pops by locally scaled AR prediction error
+    def impulse_runs(self, x: torch.Tensor, order: int = 16, half: int = 256, guard: int = 4, pad: int = 2, ratio: float = 10.0,
+                     threshold: float = 0.0, rel_threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536,
+                     runs: Optional[torch.Tensor] = None, n_runs: Optional[torch.Tensor] = None, channel: Optional[int] = None,
+                     threshold_out: Optional[torch.Tensor] = None):
+        """level_runs with si_impulse_runs' predicate: a sample is dead when a sample within `pad` of it is HOT -- its squared prediction
+        error under an AR model of order `order`, fitted per block of 512 samples, is above T^2, T = max(threshold, rel_threshold *
+        peak), and above ratio^2 times the mean squared prediction error of the samples within `half` of it, `guard` samples on either
+        side left out.  x, channel, runs, n_runs and threshold_out are dead_runs'; -> (runs, n_runs)."""
+        n, ch = self._interleaved(x, channel)
+        max_runs = int(max_runs)
+        if runs is None and max_runs > 0:
+            runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
+        if n_runs is None:
+            n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
+        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
+        assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
+        assert threshold_out is None or (threshold_out.is_cuda and threshold_out.dtype == torch.float32 and threshold_out.numel() == 1)
+        self._check(self.lib.si_impulse_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
+                                             int(channel) if channel is not None else 0, int(order), int(half), int(guard), int(pad),
+                                             float(ratio), float(threshold), float(rel_threshold), int(min_len), _ptr(runs), max_runs,
+                                             _ptr(n_runs), _ptr(threshold_out), self._stream()), "si_impulse_runs")
+        return runs, n_runs
+
+    def impulse_residual(self, x: torch.Tensor, order: int = 16, channel: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The prediction error si_impulse_runs judges, sample by sample (si_impulse_residual): x (n,) or, with channel = c >= 0, channel c
+        of the interleaved (n, ch) file -> e (n,) device float64, 0.0 below `order` and NaN at a sample of a block whose fit window
+        holds a NaN or an inf."""
+        n, ch = self._interleaved(x, channel)
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n
+        self._check(self.lib.si_impulse_residual(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
+                                                 int(channel) if channel is not None else 0, int(order), _ptr(out), self._stream()),
+                    "si_impulse_residual")
+        return out
 
     # ---- short runs mended in place by least-squares AR interpolation (DESIGN.md 4.31)
     def mend_runs(self, x: torch.Tensor, runs: Optional[torch.Tensor], max_len: int = 64, order: int = 32, context: int = 512,

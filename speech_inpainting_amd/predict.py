@@ -24,7 +24,9 @@ default) finds a dropout that is a noise floor -- dither, a concealer's comfort 
 milliseconds against the threshold, and gaps.json records `kind`, `T` and `win_ms` (engine.find_level_runs).  `kind: burst`
 finds damage that is LOUDER than the speech -- a block of corrupted PCM: random data, swapped or misaligned bytes -- by the RMS level of the
 second difference over a window of `win_ms:` (4 by default at this kind) at or above `threshold:`; start from `threshold: 1.15` of full
-scale, and a threshold of 0 is refused (engine.find_burst_runs).  `kind: invalid` finds a float file's samples whose
+scale, and a threshold of 0 is refused (engine.find_burst_runs).  `kind: impulse` finds clicks and pops of one to a few
+in-range samples by their AR prediction error against that of their own neighbourhood (`ratio:` 10, `order:` 16, `guard:` 4, `pad:` 2,
+`win_ms:` 23; give `min_ms: 0`, and `mend_ms: 1` to mend them in place; engine.find_impulse_runs).  `kind: invalid` finds a float file's samples whose
 VALUE is the damage -- NaN, inf and, with `threshold:` (the ceiling, in full-scale units; 0 or absent: none), |x| above it; `min_ms:`
 defaults to 0 at this kind, gaps.json records `kind` and `ceiling`, and the same ceiling keeps those samples out of the clips the model
 is fed; it needs `long: {rate: file, feed: contexts}` unless the file is at 22.05 kHz (engine.find_invalid_runs).  With `mend_ms:` (and optionally
@@ -378,7 +380,7 @@ def _detect_gaps(cfg: PredictConfig, engine: InpaintingEngine, raw: np.ndarray, 
     n_rec, lim = engine.recording_frames(n22, clip_frames)
     max_ms = d["max_ms"] if n_rec <= clip_frames else min(d["max_ms"], 20.0 * (clip_frames - 2 * min_context))
     found = engine.find_gaps(x, sr_file, d["threshold"] * scale, d["min_ms"], max_ms, d["pad_frames"], None, fade, n_rec, lim,
-                             **dead_keywords(cfg.detect_dead, scale), **level_keywords(cfg))
+                             **dead_keywords(cfg.detect_dead, scale), **level_keywords(cfg), **impulse_keywords(cfg))
     report = _dead_report(cfg, found, scale)
     for k, (pos, lm) in enumerate(found["gaps"]):
         print(f"Detected gap {k} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s")
@@ -401,9 +403,18 @@ def level_keywords(cfg) -> dict:
     """`detect:`'s win_ms as find_gaps and conceal_file take it: given with `kind: level` alone, so that every other
     kind is called as it was.  win_ms is a time and, like rel_threshold, is not scaled for an int16 file."""
     dead, level = getattr(cfg, "detect_dead", None), getattr(cfg, "detect_level", None)
-    if dead is None or dead["kind"] not in ("level", "burst"):                     # kind burst (DESIGN.md 4.28) has level's window key
+    if dead is None or dead["kind"] not in ("level", "burst", "impulse"):          # kinds burst (DESIGN.md 4.28) and impulse (4.33) have level's window key
         return {}
     return {"win_ms": level["win_ms"] if level is not None else 2.0}
+
+
+def impulse_keywords(cfg) -> dict:
+    """`detect: {kind: impulse}`'s order / guard / pad / ratio as find_gaps and conceal_file take them: given at that kind
+    alone, so that every other kind is called as it was.  None of them is scaled for a PCM file: the ratio test has no unit."""
+    dead, imp = getattr(cfg, "detect_dead", None), getattr(cfg, "detect_impulse", None)
+    if dead is None or dead["kind"] != "impulse" or imp is None:
+        return {}
+    return {"impulse_order": imp["order"], "impulse_guard": imp["guard"], "impulse_pad": imp["pad"], "impulse_ratio": imp["ratio"]}
 
 
 def ceiling_keywords(cfg, scale: float) -> dict:
@@ -429,6 +440,10 @@ def _dead_report(cfg: PredictConfig, found: dict, scale: float) -> dict:
         return {"kind": "invalid", "ceiling": None if c == float("inf") else c, **({"unit": unit} if scale == 8388608.0 else {})}
     level = level_keywords(cfg)                                                    # kind level: the window is printed and recorded too
     window = f", window win_ms = {level['win_ms']}" if level else ""
+    if cfg.detect_dead["kind"] == "impulse":                                       # the ratio test's settings are recorded as well
+        imp = cfg.detect_impulse
+        level = {**level, "ratio": imp["ratio"], "order": imp["order"], "guard": imp["guard"], "pad": imp["pad"]}
+        window += f", ratio = {imp['ratio']}, order = {imp['order']}, guard = {imp['guard']}, pad = {imp['pad']}"
     print(f"Detection kind = {cfg.detect_dead['kind']}, effective threshold T = {T} ({unit}){window}")
     return {"kind": cfg.detect_dead["kind"], "T": T, **({"unit": unit} if scale == 8388608.0 else {}), **level}
 
@@ -494,7 +509,7 @@ def _main_long_file(cfg: PredictConfig, engine: InpaintingEngine, save_dir: str)
         d = cfg.detect
         out = engine.conceal_file(x, sr_file, d["threshold"] * scale, d["min_ms"], d["max_ms"], d["pad_frames"], fade_ms=fade_ms, clip_frames=clip_frames,
                                   min_context=min_context, batch=cfg.long["batch"], feed=cfg.long_feed, **dead_keywords(cfg.detect_dead, scale),
-                                  **level_keywords(cfg), **clips16_keywords(cfg), **mend_keywords(cfg))
+                                  **level_keywords(cfg), **impulse_keywords(cfg), **clips16_keywords(cfg), **mend_keywords(cfg))
         gap_list, report = out["gaps"], _dead_report(cfg, out, scale)
         for k, (pos, lm) in enumerate(gap_list):
             print(f"Detected gap {k} = frames [{pos}, {pos + lm}) = {pos * 0.02:.2f} s .. {(pos + lm) * 0.02:.2f} s")
@@ -561,7 +576,7 @@ def _main_long_file_channels(cfg: PredictConfig, engine: InpaintingEngine, save_
         scale = 8388608.0 if s24 else 32768.0 if x.dtype == np.int16 else 1.0       # an int16 / 24-bit file is scanned as the integers it holds
         joint = cfg.detect_channels == "joint"
         out = engine.conceal_file(dev, sr_file, d["threshold"] * scale, d["min_ms"], d["max_ms"], d["pad_frames"], detect=cfg.detect_channels,
-                                  **dead_keywords(cfg.detect_dead, scale), **level_keywords(cfg), **mend_keywords(cfg), **kw)
+                                  **dead_keywords(cfg.detect_dead, scale), **level_keywords(cfg), **impulse_keywords(cfg), **mend_keywords(cfg), **kw)
         report = _dead_report(cfg, out, scale)
         if mend_keywords(cfg):                                                     # gaps.json gains the count by status
             report["mended"] = mended_report(out["mended"]) if joint else [mended_report(one) for one in out["mended"]]

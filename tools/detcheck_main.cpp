@@ -49,6 +49,39 @@ static void check_layout(int n, bool walk) {
     memcpy(s + at.pk, pk, 8);
 }
 
+// The dynamic LDS of the impulse pass at half window h, dilation pad, order p and guard g, WALKED: a buffer of exactly
+// dt_impulse_lds(halo).bytes, and the first and last element every loop of detect_impulse_kernel touches in each of its arrays.
+static void check_impulse(int h, int pad, int p, int g) {
+    const int halo = dt_impulse_halo(h, pad), NQ = dt_impulse_nq(halo), NX = dt_impulse_nx(halo), NB = DT_CHUNK / IM_BLOCK + 2 * halo;
+    const DtImpulseLds at = dt_impulse_lds(halo);
+    const int base = IM_BLOCK * halo, wlen = h - g;
+    EXPECT(halo >= 0 && halo <= IM_MAX_HALO && NB <= IM_MAX_BLOCKS && base >= h + pad && wlen >= 1, "h = %d, pad = %d: halo %d", h, pad, halo);
+    EXPECT(at.x == 0 && at.e == 8 * (size_t)NX && at.p == at.e + 8 * (size_t)NQ && at.ints == at.p + 8 * (size_t)NQ && at.bytes == at.ints + 8 * (size_t)NQ,
+           "h = %d, pad = %d: the regions", h, pad);
+    EXPECT(at.bytes == 32 * (size_t)NQ + 4096 && at.bytes + 8192 <= CU_LDS && at.ints % 8 == 0, "h = %d, pad = %d: %zu bytes", h, pad, at.bytes);
+    EXPECT(NQ <= NX && NX <= 2 * NQ && NB * (p + 1) * IM_PARTS <= NQ, "h = %d, pad = %d, p = %d: S in X, nf in the words, the partial sums in P", h, pad, p);
+    std::vector<unsigned char> buf(at.bytes);
+    unsigned char* s = buf.data();
+    const double d = 1.0;
+    const int32_t w = 1;
+    auto f64 = [&](size_t region, long i) { EXPECT(i >= 0, "index %ld", i); memcpy(s + region + 8 * (size_t)i, &d, 8); };
+    auto i32 = [&](long i) { EXPECT(i >= 0, "index %ld", i); memcpy(s + at.ints + 4 * (size_t)i, &w, 4); };
+    f64(at.x, 0), f64(at.x, NX - 1), i32(0), i32(NX - 1);                                  // the staged samples and their non-finite count
+    f64(at.x, IM_BLOCK * (NB - 1) + 2 * IM_WING + IM_BLOCK - 1);                           // the last block's fit window ends with the image
+    f64(at.p, 0), f64(at.p, (long)NB * (p + 1) * IM_PARTS - 1);                            // the lag partial sums
+    f64(at.x, 0 + IM_WING - p), f64(at.x, NQ - 1 + IM_WING);                               // the residual's oldest and newest sample
+    f64(at.e, 0), f64(at.e, NQ - 1), i32(NQ - 1);                                          // e / sq and bad
+    for (long i : {(long)base - pad, (long)base + DT_CHUNK + pad - 1}) {                   // the first and last candidate of hot
+        const long ql = i - h, qr = i + g + 1;
+        f64(at.x, ql), f64(at.p, ql + wlen - 1), f64(at.x, qr), f64(at.p, qr + wlen - 1);  // S[ql], P[..], S[qr], P[..]; S lies over X
+        EXPECT(qr + wlen - 1 == i + h && i + h <= NQ - 1 && ql >= 0, "h = %d, pad = %d: windows of position %ld", h, pad, i);
+        i32(i - 1), i32(i - g - 1), i32(ql > 0 ? ql - 1 : 0), i32(i + h), i32(i + g);      // the prefix counts of bad
+    }
+    i32(NQ + 0), i32(NQ + NQ - 1);                                                         // hot
+    i32(NQ + base - pad - 1), i32(NQ + base + DT_CHUNK - 1 + pad);                         // the dilation's first and last read
+    EXPECT(base - pad - 1 >= 0 && base + DT_CHUNK - 1 + pad <= NQ - 1, "h = %d, pad = %d: the dilation", h, pad);
+}
+
 int main() {
     // the scratch layout: every n around the chunk and 16-byte-rounding seams, walked; the largest legal n, arithmetic only
     for (int n : {1, 2, 3, 7, 2047, 2048, 2049, 4095, 4096, 4097, 3 * 2048, 4 * 2048, 4 * 2048 + 1, 5 * 2048 + 1, 1024 * 2048, 1024 * 2048 + 1,
@@ -91,6 +124,18 @@ int main() {
                 EXPECT(hi < n && (hi < 0 || lo >= 0), "n = %d, h = %d, chunk %d: reads [%ld, %ld]", n, h, c, lo, hi);
             }
         }
+    // the impulse pass: every (half, pad, order, guard) at the limits, and every half in between at the extreme pads
+    for (int p : {2, 16, SI_IMPULSE_MAX_ORDER})
+        for (int g : {0, 4, SI_IMPULSE_MAX_GUARD})
+            for (int pad : {0, 2, SI_IMPULSE_MAX_PAD})
+                for (int h = g + 1; h + pad <= SI_IMPULSE_MAX_HALF; h += (h < 16 || h + pad > SI_IMPULSE_MAX_HALF - 16 || h % 512 > 500 || h % 512 < 12) ? 1 : 37)
+                    check_impulse(h, pad, p, g);
+    EXPECT(IM_MAX_ORDER == SI_IMPULSE_MAX_ORDER && IM_MAX_HALF == SI_IMPULSE_MAX_HALF && IM_MAX_GUARD == SI_IMPULSE_MAX_GUARD && IM_MAX_PAD == SI_IMPULSE_MAX_PAD,
+           "detect_sizes.h against si_hip.h");
+    EXPECT(dt_impulse_lds(0).bytes == 69632 && dt_impulse_lds(1).bytes == 102400 && dt_impulse_lds(2).bytes == 135168, "%zu", dt_impulse_lds(2).bytes);
+    EXPECT(dt_impulse_halo(1, 0) == 1 && dt_impulse_halo(512, 0) == 1 && dt_impulse_halo(511, 2) == 2 && dt_impulse_halo(1008, 16) == 2 && IM_MAX_HALO == 2, "halo");
+    // 135 168 bytes dynamic + 4 400 static (the models, the lag sums' r, the block table, the scan words) stay under the CU's LDS
+    EXPECT(dt_impulse_lds(IM_MAX_HALO).bytes + 4400 <= CU_LDS, "%zu", dt_impulse_lds(IM_MAX_HALO).bytes + 4400);
     printf("detcheck: %d cases, %d answered as expected, %d not\n", g_cases, g_cases - g_bad, g_bad);
     return g_bad ? 1 : 0;
 }
