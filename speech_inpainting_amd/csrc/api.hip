@@ -2002,106 +2002,109 @@ static int quiet_runs_check(si_ctx* ctx, const char* fn, bool inter, const void*
     return SI_OK;
 }
 
-static int quiet_runs_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n, int channels, int channel, float threshold, int min_len,
-                           int32_t* runs, int max_runs, int32_t* n_runs, si_stream_t stream) {
+// The two range checks that more than one route makes, each with its one text.
+static int check_finite_threshold(si_ctx* ctx, const char* fn, float threshold) {
+    return __builtin_isinf(threshold) ? SI_FAIL_FN("threshold = %g is not finite", (double)threshold) : SI_OK;
+}
+static int check_rel_threshold(si_ctx* ctx, const char* fn, float rel_threshold, float top) {       // top: 1 (a fraction of the peak) or 4 (|d| <= 4 * peak)
+    if (rel_threshold >= 0.f && rel_threshold <= top) return SI_OK;
+    return top == 1.f ? SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 1]", (double)rel_threshold)
+                      : SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 4]", (double)rel_threshold);
+}
+
+// What route d.route alone refuses, in that route's order.  A new detector adds its case here.
+static int detect_route_check(si_ctx* ctx, const char* fn, const SiDetect& d, float threshold) {
+    switch (d.route) {
+    case SI_DET_DEAD:
+        if (d.kind < 1 || d.kind > 3) return SI_FAIL_FN("kind = %d, outside 1 .. 3 (SI_DEAD_QUIET | SI_DEAD_HELD)", d.kind);
+        if (check_rel_threshold(ctx, fn, d.rel, 1.f) != SI_OK) return SI_EINVAL;
+        if (!(d.tol >= 0.f)) return SI_FAIL_FN("held_tol = %g is negative or NaN", (double)d.tol);
+        return SI_OK;
+    case SI_DET_LEVEL:
+    case SI_DET_BURST:                                                 // the same window; a second difference reaches 4 * the peak
+        if (d.half < 0 || d.half > SI_LEVEL_MAX_HALF) return SI_FAIL_FN("half = %d samples, outside 0 .. SI_LEVEL_MAX_HALF = %d", d.half, SI_LEVEL_MAX_HALF);
+        if (check_finite_threshold(ctx, fn, threshold) != SI_OK) return SI_EINVAL;
+        return check_rel_threshold(ctx, fn, d.rel, d.route == SI_DET_LEVEL ? 1.f : 4.f);
+    case SI_DET_INVALID:
+        if (!(d.ceiling > 0.f)) return SI_FAIL_FN("ceiling = %g is not above 0, or is NaN", (double)d.ceiling);
+        return SI_OK;
+    case SI_DET_IMPULSE:
+        if (d.order < 2 || d.order > SI_IMPULSE_MAX_ORDER) return SI_FAIL_FN("order = %d, outside 2 .. SI_IMPULSE_MAX_ORDER = %d", d.order, SI_IMPULSE_MAX_ORDER);
+        if (d.guard < 0 || d.guard > SI_IMPULSE_MAX_GUARD) return SI_FAIL_FN("guard = %d samples, outside 0 .. SI_IMPULSE_MAX_GUARD = %d", d.guard, SI_IMPULSE_MAX_GUARD);
+        if (d.half < d.guard + 1 || d.half > SI_IMPULSE_MAX_HALF)
+            return SI_FAIL_FN("half = %d samples, outside guard + 1 = %d .. SI_IMPULSE_MAX_HALF = %d", d.half, d.guard + 1, SI_IMPULSE_MAX_HALF);
+        if (d.pad < 0 || d.pad > SI_IMPULSE_MAX_PAD) return SI_FAIL_FN("pad = %d samples, outside 0 .. SI_IMPULSE_MAX_PAD = %d", d.pad, SI_IMPULSE_MAX_PAD);
+        if (d.half + d.pad > SI_IMPULSE_MAX_HALF) return SI_FAIL_FN("half + pad = %d samples, above SI_IMPULSE_MAX_HALF = %d", d.half + d.pad, SI_IMPULSE_MAX_HALF);
+        if (!(d.ratio >= 1.f && d.ratio <= 1e6f)) return SI_FAIL_FN("ratio = %g is NaN or outside [1, 1e6]", (double)d.ratio);
+        if (check_finite_threshold(ctx, fn, threshold) != SI_OK) return SI_EINVAL;
+        return check_rel_threshold(ctx, fn, d.rel, 4.f);
+    default:
+        return SI_OK;                                                  // SI_DET_QUIET: nothing of its own
+    }
+}
+
+// One detection call: what every detector refuses, then what the route alone refuses, and only then the device: the
+// scratch and the route's launches.  inter = false is si_quiet_runs, the one entry point with no channels.
+static int detect_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n, int channels, int channel, float threshold, int min_len,
+                       int32_t* runs, int max_runs, int32_t* n_runs, si_stream_t stream, const SiDetect& d) {
     if (!ctx) return SI_EINVAL;
     if (quiet_runs_check(ctx, fn, inter, x, n, channels, channel, threshold, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
+    if (detect_route_check(ctx, fn, d, threshold) != SI_OK) return SI_EINVAL;
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
-    if (inter)
-        return si_launch_quiet_runs_ch(ctx, x, si_sample_format(is_pcm16), n, channels, channel, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch,
-                                       static_cast<hipStream_t>(stream));
-    return si_launch_quiet_runs(ctx, x, si_sample_format(is_pcm16), n, threshold, min_len, runs, max_runs, n_runs, ctx->det_scratch, static_cast<hipStream_t>(stream));
+    return si_launch_detect(ctx, x, si_sample_format(is_pcm16), n, inter ? channels : 0, inter ? channel : 0, threshold, min_len, runs, max_runs, n_runs,
+                            ctx->det_scratch, static_cast<hipStream_t>(stream), d);
 }
 
 int si_quiet_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, float threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
                   si_stream_t stream) {
-    return quiet_runs_call(ctx, "si_quiet_runs", false, x, is_pcm16, n, 0, 0, threshold, min_len, runs, max_runs, n_runs, stream);
+    const SiDetect d{SI_DET_QUIET};
+    return detect_call(ctx, "si_quiet_runs", false, x, is_pcm16, n, 0, 0, threshold, min_len, runs, max_runs, n_runs, stream, d);
 }
 
 int si_quiet_runs_ch(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, float threshold, int min_len, int32_t* runs,
                      int max_runs, int32_t* n_runs, si_stream_t stream) {
-    return quiet_runs_call(ctx, "si_quiet_runs_ch", true, x, is_pcm16, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, stream);
+    const SiDetect d{SI_DET_QUIET};
+    return detect_call(ctx, "si_quiet_runs_ch", true, x, is_pcm16, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, stream, d);
 }
 
 // ---- held-sample and peak-relative dropouts
 int si_dead_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int kind, float threshold, float rel_threshold,
                  float held_tol, int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream) {
-    const char* fn = "si_dead_runs";
-    if (!ctx) return SI_EINVAL;
-    if (quiet_runs_check(ctx, fn, true, x, n, channels, channel, threshold, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
-    if (kind < 1 || kind > 3) return SI_FAIL_FN("kind = %d, outside 1 .. 3 (SI_DEAD_QUIET | SI_DEAD_HELD)", kind);
-    if (!(rel_threshold >= 0.f && rel_threshold <= 1.f)) return SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 1]", (double)rel_threshold);
-    if (!(held_tol >= 0.f)) return SI_FAIL_FN("held_tol = %g is negative or NaN", (double)held_tol);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
-    return si_launch_dead_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, kind, threshold, rel_threshold, held_tol, min_len, runs, max_runs, n_runs,
-                               threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
+    SiDetect d{SI_DET_DEAD};
+    d.kind = kind, d.rel = rel_threshold, d.tol = held_tol, d.thr_out = threshold_out;
+    return detect_call(ctx, "si_dead_runs", true, x, is_pcm16, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, stream, d);
 }
 
 // ---- dropouts by windowed RMS level
 int si_level_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int half, float threshold, float rel_threshold,
                   int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream) {
-    const char* fn = "si_level_runs";
-    if (!ctx) return SI_EINVAL;
-    if (quiet_runs_check(ctx, fn, true, x, n, channels, channel, threshold, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
-    if (half < 0 || half > SI_LEVEL_MAX_HALF) return SI_FAIL_FN("half = %d samples, outside 0 .. SI_LEVEL_MAX_HALF = %d", half, SI_LEVEL_MAX_HALF);
-    if (__builtin_isinf(threshold)) return SI_FAIL_FN("threshold = %g is not finite", (double)threshold);
-    if (!(rel_threshold >= 0.f && rel_threshold <= 1.f)) return SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 1]", (double)rel_threshold);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
-    return si_launch_level_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, half, threshold, rel_threshold, min_len, runs, max_runs, n_runs,
-                                threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
+    const SiDetect d{SI_DET_LEVEL, rel_threshold, threshold_out, half};
+    return detect_call(ctx, "si_level_runs", true, x, is_pcm16, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, stream, d);
 }
 
 // ---- corrupted blocks by second-difference level
 int si_burst_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int half, float threshold, float rel_threshold,
                   int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* threshold_out, si_stream_t stream) {
-    const char* fn = "si_burst_runs";
-    if (!ctx) return SI_EINVAL;
-    if (quiet_runs_check(ctx, fn, true, x, n, channels, channel, threshold, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
-    if (half < 0 || half > SI_LEVEL_MAX_HALF) return SI_FAIL_FN("half = %d samples, outside 0 .. SI_LEVEL_MAX_HALF = %d", half, SI_LEVEL_MAX_HALF);
-    if (__builtin_isinf(threshold)) return SI_FAIL_FN("threshold = %g is not finite", (double)threshold);
-    if (!(rel_threshold >= 0.f && rel_threshold <= 4.f)) return SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 4]", (double)rel_threshold);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
-    return si_launch_burst_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, half, threshold, rel_threshold, min_len, runs, max_runs, n_runs,
-                                threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
+    const SiDetect d{SI_DET_BURST, rel_threshold, threshold_out, half};
+    return detect_call(ctx, "si_burst_runs", true, x, is_pcm16, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, stream, d);
 }
 
-// ---- NaN, inf and out-of-range samples
+// ---- NaN, inf and out-of-range samples: no threshold, so none is checked and none reaches a kernel
 int si_invalid_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, float ceiling, int min_len, int32_t* runs,
                     int max_runs, int32_t* n_runs, si_stream_t stream) {
-    const char* fn = "si_invalid_runs";
-    if (!ctx) return SI_EINVAL;
-    if (quiet_runs_check(ctx, fn, true, x, n, channels, channel, 0.f, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
-    if (!(ceiling > 0.f)) return SI_FAIL_FN("ceiling = %g is not above 0, or is NaN", (double)ceiling);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
-    return si_launch_invalid_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, ceiling, min_len, runs, max_runs, n_runs, ctx->det_scratch,
-                                  static_cast<hipStream_t>(stream));
+    SiDetect d{SI_DET_INVALID};
+    d.ceiling = ceiling;
+    return detect_call(ctx, "si_invalid_runs", true, x, is_pcm16, n, channels, channel, 0.f, min_len, runs, max_runs, n_runs, stream, d);
 }
 
 // ---- clicks and pops by locally scaled AR prediction error
 int si_impulse_runs(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int order, int half, int guard, int pad,
                     float ratio, float threshold, float rel_threshold, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
                     float* threshold_out, si_stream_t stream) {
-    const char* fn = "si_impulse_runs";
-    if (!ctx) return SI_EINVAL;
-    if (quiet_runs_check(ctx, fn, true, x, n, channels, channel, threshold, min_len, runs, max_runs, n_runs) != SI_OK) return SI_EINVAL;
-    if (order < 2 || order > SI_IMPULSE_MAX_ORDER) return SI_FAIL_FN("order = %d, outside 2 .. SI_IMPULSE_MAX_ORDER = %d", order, SI_IMPULSE_MAX_ORDER);
-    if (guard < 0 || guard > SI_IMPULSE_MAX_GUARD) return SI_FAIL_FN("guard = %d samples, outside 0 .. SI_IMPULSE_MAX_GUARD = %d", guard, SI_IMPULSE_MAX_GUARD);
-    if (half < guard + 1 || half > SI_IMPULSE_MAX_HALF)
-        return SI_FAIL_FN("half = %d samples, outside guard + 1 = %d .. SI_IMPULSE_MAX_HALF = %d", half, guard + 1, SI_IMPULSE_MAX_HALF);
-    if (pad < 0 || pad > SI_IMPULSE_MAX_PAD) return SI_FAIL_FN("pad = %d samples, outside 0 .. SI_IMPULSE_MAX_PAD = %d", pad, SI_IMPULSE_MAX_PAD);
-    if (half + pad > SI_IMPULSE_MAX_HALF) return SI_FAIL_FN("half + pad = %d samples, above SI_IMPULSE_MAX_HALF = %d", half + pad, SI_IMPULSE_MAX_HALF);
-    if (!(ratio >= 1.f && ratio <= 1e6f)) return SI_FAIL_FN("ratio = %g is NaN or outside [1, 1e6]", (double)ratio);
-    if (__builtin_isinf(threshold)) return SI_FAIL_FN("threshold = %g is not finite", (double)threshold);
-    if (!(rel_threshold >= 0.f && rel_threshold <= 4.f)) return SI_FAIL_FN("rel_threshold = %g is NaN or outside [0, 4]", (double)rel_threshold);
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    if (int rc = det_scratch_reserve(ctx, n, stream)) return rc;
-    return si_launch_impulse_runs(ctx, x, si_sample_format(is_pcm16), n, channels, channel, order, half, guard, pad, ratio, threshold, rel_threshold,
-                                  min_len, runs, max_runs, n_runs, threshold_out, ctx->det_scratch, static_cast<hipStream_t>(stream));
+    SiDetect d{SI_DET_IMPULSE};
+    d.order = order, d.half = half, d.guard = guard, d.pad = pad, d.ratio = ratio, d.rel = rel_threshold, d.thr_out = threshold_out;
+    return detect_call(ctx, "si_impulse_runs", true, x, is_pcm16, n, channels, channel, threshold, min_len, runs, max_runs, n_runs, stream, d);
 }
 
 int si_impulse_residual(si_ctx* ctx, const void* x, int is_pcm16, int n, int channels, int channel, int order, double* e, si_stream_t stream) {

@@ -384,34 +384,35 @@ int si_launch_patch_regions(si_ctx* ctx, const float* orig, const SiRegions& rt,
 // ------------------------------------------------------------------------------------------------
 // bytes of scratch the passes need for n samples: one bit per sample, six words per chunk of 2048 samples and two more
 size_t si_detect_scratch_bytes(int n);
-// x device fp32 or int16 (n) -> runs (max_runs, 2) = the maximal runs of |x| <= thr of at least min_len samples, sorted by start, and
-// *n_runs = how many there are (all of them, whether or not they fit); arguments validated by the caller, scratch 16-byte aligned
-int si_launch_quiet_runs(si_ctx* ctx, const void* x, int fmt, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
-                         char* scratch, hipStream_t st);
-// the same for an interleaved x (n sample times of `channels` channels): channel c >= 0 alone, or all jointly (c < 0)
-int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
-                            int max_runs, int32_t* n_runs, char* scratch, hipStream_t st);
-// the maximal runs of DEAD samples: quiet against max(thr, rel * peak) (kind & 1), held = within tol of a neighbour of
-// the same channel (kind & 2); channels = 1 is a one-channel file; *thr_out (device, may be null) receives the effective threshold
-int si_launch_dead_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int kind, float thr, float rel, float tol,
-                        int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
-// the maximal runs of samples under a window of low RMS level: the windows of 2 half + 1 samples whose energy is at
-// most T^2 times their sample count, T = max(thr, rel * peak), dilated by half; channels and *thr_out as above
-int si_launch_level_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
-                         int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
-// the maximal runs of samples under a window of LOUD second difference: the windows of 2 half + 1 centres, cut to
-// [1, n - 2], whose summed squares of x[k - 1] - 2 x[k] + x[k + 1] are at least T^2 times their centre count, dilated by half
-int si_launch_burst_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
-                         int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st);
-// the maximal runs of INVALID samples: si_invalid(x, ceiling) -- NaN, +-inf, |x| > ceiling; no pass 0, no threshold out;
-// channels as above (joint: every channel's element invalid)
-int si_launch_invalid_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float ceiling, int min_len, int32_t* runs,
-                           int max_runs, int32_t* n_runs, char* scratch, hipStream_t st);
-// the maximal runs of samples within `pad` of an IMPULSE: a sample whose squared AR(order) prediction error is above
-// T^2 and above ratio^2 times the mean squared prediction error of the samples within `half` of it, `guard` on either side left out
-int si_launch_impulse_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int order, int half, int guard, int pad,
-                           float ratio, float thr, float rel, int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out,
-                           char* scratch, hipStream_t st);
+// One detection call: x device fp32, int16 or packed 24-bit -> runs (max_runs, 2) = the maximal runs of DEAD samples of
+// at least min_len samples, sorted by start, and *n_runs = how many there are (all of them, whether or not they fit).  What "dead" means
+// is the route's, and SiDetect carries its parameters; a field a route does not name is not read.  Arguments validated by the caller,
+// scratch 16-byte aligned.
+enum SiDetRoute {
+    SI_DET_QUIET,       // |x| <= thr (interleaved 4.18)
+    SI_DET_DEAD,        // quiet against T = max(thr, rel * peak) (kind & 1), held = within tol of a neighbour of the same channel (kind & 2) (4.20)
+    SI_DET_LEVEL,       // under a window of 2 half + 1 samples whose energy is at most T^2 times their count, dilated by half (4.25)
+    SI_DET_BURST,       // under a window of 2 half + 1 centres, cut to [1, n - 2], whose summed squares of x[k - 1] - 2 x[k] + x[k + 1] are at
+                        // least T^2 times their count, dilated by half (4.28)
+    SI_DET_INVALID,     // si_invalid(x, ceiling): NaN, +-inf, |x| > ceiling; no pass 0, no threshold out, thr not read (4.30)
+    SI_DET_IMPULSE,     // within `pad` of a sample whose squared AR(order) prediction error is above T^2 and above ratio^2 times the mean
+                        // squared prediction error of the samples within `half` of it, `guard` on either side left out (4.33)
+};
+struct SiDetect {
+    int route;          // SiDetRoute
+    float rel;          // dead, level, burst, impulse: T = max(thr, rel * peak), the peak taken by a pass 0 when rel > 0; 0 in the other routes
+    float* thr_out;     // the same four: device, may be null; receives T
+    int half;           // level, burst, impulse
+    int kind;           // dead
+    float tol;          // dead
+    float ceiling;      // invalid
+    int order, guard, pad;      // impulse
+    float ratio;        // impulse
+};
+// channels = 0: x is one channel of n samples.  channels >= 1: x is interleaved (n sample times of `channels` channels),
+// channel c >= 0 alone or all jointly (c < 0).  Every route but SI_DET_QUIET takes channels = 1 as the one-channel file.
+int si_launch_detect(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
+                     int32_t* n_runs, char* scratch, hipStream_t st, SiDetect d);
 // that prediction error itself, one channel of the file -> e (n) device float64: 0.0 below `order`, NaN at a sample of a bad block
 int si_launch_impulse_residual(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int order, double* e, hipStream_t st);
 

@@ -989,29 +989,15 @@ __global__ __launch_bounds__(256) void detect_impulse_residual_kernel(const T* _
 // ------------------------------------------------------------------------------------------------ launcher
 size_t si_detect_scratch_bytes(int n) { return dt_scratch(n).bytes; }     // the bitmap, six words per chunk and {peak, T} (detect_sizes.h)
 
-// What si_dead_runs adds to a detection call; the quiet routes pass none.
-struct DtDead { int kind; float rel, tol; float* thr_out; };
-// What si_level_runs adds instead.
-struct DtLevel { int half; float rel; float* thr_out; };
-// What si_burst_runs adds instead: the same three, for detect_burst_kernel.
-struct DtBurst { int half; float rel; float* thr_out; };
-// What si_invalid_runs adds instead: the ceiling of detect_invalid(_ch)_kernel.  No pass 0 and no threshold out.
-struct DtInvalid { float ceiling; };
-// What si_impulse_runs adds instead: the model order, the window, and the ratio, for detect_impulse_kernel.
-struct DtImpulse { int order, half, guard, pad; float ratio, rel; float* thr_out; };
-
-// The caller (si_quiet_runs, si_quiet_runs_ch) checked every argument.  scratch: si_detect_scratch_bytes(n) bytes, 16-byte aligned.
-// channels = 0: x is one channel of n samples (detect_bits_kernel); channels >= 1: x is interleaved, n sample times of `channels`
-// channels, and `channel` picks one of them or, below 0, all of them jointly (detect_bits_ch_kernel).  Passes 2 - 5 are the same launches.
-// dead != nullptr: pass 1 is detect_dead(_ch)_kernel, behind pass 0 when dead->rel > 0; nullptr: the launches above.
-// level != nullptr (dead is nullptr then): pass 1 is detect_level_kernel, behind the same pass 0 when level->rel > 0.
-// burst != nullptr (dead and level are nullptr then): pass 1 is detect_burst_kernel, behind the same pass 0 when burst->rel > 0.
-// invalid != nullptr (the other three are nullptr then): pass 1 is detect_invalid(_ch)_kernel, never behind a pass 0; thr is not read.
-// impulse != nullptr (the other four are nullptr then): pass 1 is detect_impulse_kernel, behind the same pass 0 when impulse->rel > 0.
+// The six routes of a detection call.  The caller checked every argument.  scratch: si_detect_scratch_bytes(n) bytes,
+// 16-byte aligned.  channels = 0: x is one channel of n samples; channels >= 1: x is interleaved, n sample times of `channels` channels,
+// and `channel` picks one of them or, below 0, all of them jointly.  d.route names pass 1 and d carries its parameters (common.h).
+//   pass 0   the peak and {peak, T}, only when d.rel > 0: the routes with no peak-relative threshold leave rel at 0
+//   pass 1   the route's own kernel -> the bitmap and each chunk's lead / trail words: the one switch below
+//   2 - 5    carry, count, offsets and, when max_runs > 0, emit: the same launches for every route
 template <typename T>
 static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
-                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead, const DtLevel* level, const DtBurst* burst,
-                     const DtInvalid* invalid, const DtImpulse* impulse) {
+                       int32_t* n_runs, char* scratch, hipStream_t st, SiDetect d) {
     const int chunks = dt_chunks(n);
     const DtScratch at = dt_scratch(n);
     uint8_t* bitmap = reinterpret_cast<uint8_t*>(scratch + at.bitmap);
@@ -1023,93 +1009,83 @@ static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel
     int32_t* cpeak = reinterpret_cast<int32_t*>(scratch + at.cpeak);
     float* pk = reinterpret_cast<float*>(scratch + at.pk);            // {peak, T}
     const double bits = (double)chunks * 256.0, sums = (double)chunks * 4.0;
+    // a single channel still moves the whole 32- or 64-byte sectors its elements lie in: counted as the chunk's elements either way
     const double samples = (double)n * (channels ? channels : 1) * (double)sizeof(T);
 
-    if (impulse) {
-        // pass 0 as the descriptor routes below run it, then the impulse pass; profiled in their pass 1's family: the lists of families are closed
-        const float* thr_dev = nullptr;
-        if (impulse->rel > 0.f) {
-            si_prof_begin(ctx, "detect_peak", 0.0, samples + sums, st);
-            if (channels == 0) {
-                detect_peak_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, cpeak);
-            } else {
-                detect_peak_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, cpeak);
-            }
-            si_prof_end(ctx, st);
-            SI_HIP_CHECK(hipGetLastError());
-            si_prof_begin(ctx, "detect_peak_final", 0.0, sums + 8.0, st);
-            detect_peak_final_kernel<<<dim3(1), 256, 0, st>>>(cpeak, chunks, thr, impulse->rel, pk);
-            si_prof_end(ctx, st);
-            SI_HIP_CHECK(hipGetLastError());
-            thr_dev = pk + 1;
+    const float* thr_dev = nullptr;                                   // T on the device, for the passes behind a pass 0
+    if (d.rel > 0.f) {
+        si_prof_begin(ctx, "detect_peak", 0.0, samples + sums, st);
+        if (channels == 0) {
+            detect_peak_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, cpeak);
+        } else {
+            detect_peak_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, cpeak);
         }
-        const int ch = channels ? channels : 1;
-        const size_t lds = dt_impulse_lds(dt_impulse_halo(impulse->half, impulse->pad)).bytes;    // 135 168 bytes at half + pad = 1024
-        const void* kern = reinterpret_cast<const void*>(&detect_impulse_kernel<T>);
-        if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
-        si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
-        detect_impulse_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, channels ? channel : 0, impulse->order, impulse->half, impulse->guard,
-                                                                impulse->pad, impulse->ratio, thr, thr_dev, impulse->thr_out, bitmap, lead, trail);
-    } else if (invalid) {
-        // profiled in the families of the quiet routes' pass 1, whose shape these kernels have: the lists of families are closed
+        si_prof_end(ctx, st);
+        SI_HIP_CHECK(hipGetLastError());
+        si_prof_begin(ctx, "detect_peak_final", 0.0, sums + 8.0, st);
+        detect_peak_final_kernel<<<dim3(1), 256, 0, st>>>(cpeak, chunks, thr, d.rel, pk);
+        si_prof_end(ctx, st);
+        SI_HIP_CHECK(hipGetLastError());
+        thr_dev = pk + 1;
+    }
+
+    // Pass 1.  The families are those of the first two routes: the lists of families are closed.  The windowed kernels
+    // have no one-channel twin: they take the one-channel file as ch = 1, c = 0.
+    const int ch = channels ? channels : 1, c = channels ? channel : 0;
+    switch (d.route) {
+    case SI_DET_QUIET:
         if (channels == 0) {
             si_prof_begin(ctx, "detect_bits", 0.0, samples + bits + 2.0 * sums, st);
-            detect_invalid_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, invalid->ceiling, bitmap, lead, trail);
+            detect_bits_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, thr, bitmap, lead, trail);
         } else {
             si_prof_begin(ctx, "detect_bits_ch", 0.0, samples + bits + 2.0 * sums, st);
-            detect_invalid_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, invalid->ceiling, bitmap, lead, trail);
+            detect_bits_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, thr, bitmap, lead, trail);
         }
-    } else if (dead || level || burst) {
-        const float* thr_dev = nullptr;
-        const float rel = dead ? dead->rel : level ? level->rel : burst->rel;
-        if (rel > 0.f) {
-            si_prof_begin(ctx, "detect_peak", 0.0, samples + sums, st);
-            if (channels == 0) {
-                detect_peak_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, cpeak);
-            } else {
-                detect_peak_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, cpeak);
-            }
-            si_prof_end(ctx, st);
-            SI_HIP_CHECK(hipGetLastError());
-            si_prof_begin(ctx, "detect_peak_final", 0.0, sums + 8.0, st);
-            detect_peak_final_kernel<<<dim3(1), 256, 0, st>>>(cpeak, chunks, thr, rel, pk);
-            si_prof_end(ctx, st);
-            SI_HIP_CHECK(hipGetLastError());
-            thr_dev = pk + 1;
-        }
-        if (level) {
-            const int h = level->half, ch = channels ? channels : 1;
-            const size_t lds = dt_window_lds(h);                      // 139 264 bytes at h = SI_LEVEL_MAX_HALF
-            const void* kern = reinterpret_cast<const void*>(&detect_level_kernel<T>);
-            if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
-            // profiled in the family of the descriptor routes' pass 1, as both detect_dead kernels are: the lists of families are closed
+        break;
+    case SI_DET_DEAD:
+        if (channels == 0) {
             si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
-            detect_level_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, channels ? channel : 0, h, thr, thr_dev, level->thr_out, bitmap, lead, trail);
-        } else if (burst) {
-            const int h = burst->half, ch = channels ? channels : 1;
-            const size_t lds = dt_window_lds(h);                      // detect_level_kernel's image
-            const void* kern = reinterpret_cast<const void*>(&detect_burst_kernel<T>);
-            if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
-            // the same family again: the lists of families are closed
-            si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
-            detect_burst_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, channels ? channel : 0, h, thr, thr_dev, burst->thr_out, bitmap, lead, trail);
-        } else if (channels == 0) {
-            si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
-            detect_dead_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
+            detect_dead_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, d.kind, thr, thr_dev, d.tol, d.thr_out, bitmap, lead, trail);
         } else {
-            const size_t lds = (size_t)(DT_CHUNK + 2) * (channel < 0 ? channels : 1) * sizeof(T);   // 65 600 bytes at 8 fp32 channels
-            const void* kern = reinterpret_cast<const void*>(&detect_dead_ch_kernel<T>);
-            if (int rc = si_ensure_dyn_lds(ctx, kern, lds)) return rc;
+            const size_t lds = dt_dead_ch_lds(channel < 0 ? channels : 1, sizeof(T));      // 65 600 bytes at 8 fp32 channels
+            if (int rc = si_ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&detect_dead_ch_kernel<T>), lds)) return rc;
             si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
-            detect_dead_ch_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, channels, channel, dead->kind, thr, thr_dev, dead->tol, dead->thr_out, bitmap, lead, trail);
+            detect_dead_ch_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, channels, channel, d.kind, thr, thr_dev, d.tol, d.thr_out, bitmap, lead, trail);
         }
-    } else if (channels == 0) {
-        si_prof_begin(ctx, "detect_bits", 0.0, (double)n * (double)sizeof(T) + bits + 2.0 * sums, st);
-        detect_bits_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, thr, bitmap, lead, trail);
-    } else {
-        // a single channel still moves the whole 32- or 64-byte sectors its elements lie in: counted as the chunk's elements either way
-        si_prof_begin(ctx, "detect_bits_ch", 0.0, (double)n * channels * (double)sizeof(T) + bits + 2.0 * sums, st);
-        detect_bits_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, thr, bitmap, lead, trail);
+        break;
+    case SI_DET_LEVEL: {
+        const size_t lds = dt_window_lds(d.half);                     // 139 264 bytes at half = SI_LEVEL_MAX_HALF
+        if (int rc = si_ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&detect_level_kernel<T>), lds)) return rc;
+        si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
+        detect_level_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, c, d.half, thr, thr_dev, d.thr_out, bitmap, lead, trail);
+        break;
+    }
+    case SI_DET_BURST: {
+        const size_t lds = dt_window_lds(d.half);                     // detect_level_kernel's image
+        if (int rc = si_ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&detect_burst_kernel<T>), lds)) return rc;
+        si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
+        detect_burst_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, c, d.half, thr, thr_dev, d.thr_out, bitmap, lead, trail);
+        break;
+    }
+    case SI_DET_INVALID:                                              // never behind a pass 0; thr is not read
+        if (channels == 0) {
+            si_prof_begin(ctx, "detect_bits", 0.0, samples + bits + 2.0 * sums, st);
+            detect_invalid_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, d.ceiling, bitmap, lead, trail);
+        } else {
+            si_prof_begin(ctx, "detect_bits_ch", 0.0, samples + bits + 2.0 * sums, st);
+            detect_invalid_ch_kernel<T><<<dim3(chunks), 256, 0, st>>>(x, n, channels, channel, d.ceiling, bitmap, lead, trail);
+        }
+        break;
+    case SI_DET_IMPULSE: {
+        const size_t lds = dt_impulse_lds(dt_impulse_halo(d.half, d.pad)).bytes;           // 135 168 bytes at half + pad = 1024
+        if (int rc = si_ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&detect_impulse_kernel<T>), lds)) return rc;
+        si_prof_begin(ctx, "detect_dead", 0.0, samples + bits + 2.0 * sums, st);
+        detect_impulse_kernel<T><<<dim3(chunks), 256, lds, st>>>(x, n, ch, c, d.order, d.half, d.guard, d.pad, d.ratio, thr, thr_dev, d.thr_out, bitmap,
+                                                                lead, trail);
+        break;
+    }
+    default:
+        return SI_EINVAL;                                             // no such route: nothing was launched
     }
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
@@ -1138,64 +1114,16 @@ static int dt_launch_t(si_ctx* ctx, const T* x, int n, int channels, int channel
     return SI_OK;
 }
 
-static int dt_launch(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
-                     int32_t* n_runs, char* scratch, hipStream_t st, const DtDead* dead = nullptr, const DtLevel* level = nullptr,
-                     const DtBurst* burst = nullptr, const DtInvalid* invalid = nullptr, const DtImpulse* impulse = nullptr) {
+// channels = 1 is a one-channel file for every route but SI_DET_QUIET: its elements are the mono call's, and so are its kernels.
+// si_quiet_runs_ch reaches detect_bits_ch_kernel at channels = 1, as it always did; si_quiet_runs passes channels = 0.
+int si_launch_detect(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs, int max_runs,
+                     int32_t* n_runs, char* scratch, hipStream_t st, SiDetect d) {
+    if (d.route != SI_DET_QUIET && channels < 2) channels = channel = 0;
     int rc = SI_OK;
     si_with_sample(fmt, [&](auto tag) {
-        rc = dt_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st, dead, level, burst, invalid, impulse);
+        rc = dt_launch_t(ctx, static_cast<decltype(tag)>(x), n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st, d);
     });
     return rc;
-}
-
-int si_launch_quiet_runs(si_ctx* ctx, const void* x, int fmt, int n, float thr, int min_len, int32_t* runs, int max_runs, int32_t* n_runs,
-                         char* scratch, hipStream_t st) {
-    return dt_launch(ctx, x, fmt, n, 0, 0, thr, min_len, runs, max_runs, n_runs, scratch, st);
-}
-
-int si_launch_quiet_runs_ch(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float thr, int min_len, int32_t* runs,
-                            int max_runs, int32_t* n_runs, char* scratch, hipStream_t st) {
-    return dt_launch(ctx, x, fmt, n, channels, channel, thr, min_len, runs, max_runs, n_runs, scratch, st);
-}
-
-// channels = 1 is a one-channel file: its elements are the mono call's, and so are its kernels.
-int si_launch_dead_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int kind, float thr, float rel, float tol,
-                        int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st) {
-    const DtDead dead{kind, rel, tol, thr_out};
-    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, &dead);
-}
-
-// The windowed RMS level; channels = 1 is a one-channel file, as for si_launch_dead_runs.
-int si_launch_level_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
-                         int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st) {
-    const DtLevel level{half, rel, thr_out};
-    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
-                     &level);
-}
-
-// The second-difference level; channels = 1 is a one-channel file, as for si_launch_dead_runs.
-int si_launch_burst_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int half, float thr, float rel, int min_len,
-                         int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out, char* scratch, hipStream_t st) {
-    const DtBurst burst{half, rel, thr_out};
-    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
-                     nullptr, &burst);
-}
-
-// The invalid samples; channels = 1 is a one-channel file, as for si_launch_dead_runs.
-int si_launch_invalid_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, float ceiling, int min_len, int32_t* runs,
-                           int max_runs, int32_t* n_runs, char* scratch, hipStream_t st) {
-    const DtInvalid invalid{ceiling};
-    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, 0.f, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
-                     nullptr, nullptr, &invalid);
-}
-
-// The impulses; channels = 1 is a one-channel file, as for si_launch_dead_runs.
-int si_launch_impulse_runs(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int order, int half, int guard, int pad,
-                           float ratio, float thr, float rel, int min_len, int32_t* runs, int max_runs, int32_t* n_runs, float* thr_out,
-                           char* scratch, hipStream_t st) {
-    const DtImpulse impulse{order, half, guard, pad, ratio, rel, thr_out};
-    return dt_launch(ctx, x, fmt, n, channels >= 2 ? channels : 0, channels >= 2 ? channel : 0, thr, min_len, runs, max_runs, n_runs, scratch, st, nullptr,
-                     nullptr, nullptr, nullptr, &impulse);
 }
 
 // The residual of one channel (si_impulse_residual): one launch, no scratch.  channels = 1 is a one-channel file.

@@ -25,6 +25,10 @@ inline DtScratch dt_scratch(int n) {
 // DT_CHUNK + 4 h elements, an int32 array of M = DT_CHUNK + 2 h.  139 264 bytes at h = 1024 (SI_LEVEL_MAX_HALF).
 inline size_t dt_window_lds(int h) { return 20 * (size_t)(DT_CHUNK + 4 * h) + 4 * (size_t)(DT_CHUNK + 2 * h); }
 
+// The dynamic LDS of detect_dead_ch_kernel: the chunk's samples and one neighbour on either side, for each of the m channels it judges
+// (all of them jointly, or one), in the file's own sample type of `elem` bytes.  65 600 bytes at 8 fp32 channels.
+inline size_t dt_dead_ch_lds(int m, size_t elem) { return (size_t)(DT_CHUNK + 2) * (size_t)m * elem; }
+
 // The impulse pass (detect_impulse_kernel, detect_impulse_residual_kernel).  A chunk is four model blocks of IM_BLOCK
 // samples; a block's fit window reaches IM_WING samples past it on either side; the detector also fits `halo` blocks on either side of
 // the chunk, enough for the widest window (half) and the dilation (pad) of the chunk's edge samples.  The residual tap has halo = 0.

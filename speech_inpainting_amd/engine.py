@@ -1162,6 +1162,47 @@ class InpaintingEngine:
         return out
 
     # ---- dropout detection: where the gaps are, found on the device; then patch_recording as it is
+    # The six find_*_runs are one shape: their own argument checks, the file view, the call, the read-back.  The three
+    # helpers are called through the class, as _file_samples is: a find_*_runs also serves a stand-in that has only what the call touches.
+    def _file_view(self, x, fn: str, channel: Optional[int]):
+        """x as a detection call takes it -> (the device tensor, many, the channel to pass).  An interleaved (n, ch >= 2) file stays as it
+        is (many) and needs `channel`, an index or -1 for joint detection; anything else is the one-channel file, flattened to (n,) --
+        (n, 3) packed 24-bit -- and passed without a channel, of which only 0 and -1 exist.  A ValueError names the caller `fn`."""
+        x = torch.as_tensor(x)
+        s24, sdim = InpaintingEngine._file_samples(x, fn)                  # packed 24-bit PCM: uint8 (n, 3) or (n, ch, 3), 24-bit steps
+        many = sdim == 2 and x.shape[1] >= 2
+        if many and channel is None:
+            raise ValueError(f"{fn}: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
+        if not many and channel is not None and int(channel) not in (-1, 0):
+            raise ValueError(f"{fn}: channel = {channel} of a one-channel recording")
+        x = InpaintingEngine._file_on_device(x, self.device)               # only now: the refusals above need no device
+        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
+        return x, many, int(channel) if many else None
+
+    @staticmethod
+    def _window_half(fn: str, win, half, max_half: Optional[int] = None):
+        """The window of a windowed detector, given as `half` or as `win` = 2 * half + 1 -> half; held to 0 .. max_half when that is given."""
+        if (win is None) == (half is None):
+            raise ValueError(f"{fn}: give the window as win = its odd length in samples, or as half = (win - 1) / 2, not both")
+        if win is not None:
+            if int(win) != win or int(win) < 1 or int(win) % 2 == 0:
+                raise ValueError(f"{fn}: win = {win}: an odd number of samples, 2 * half + 1")
+            half = (int(win) - 1) // 2
+        if max_half is not None and (int(half) != half or not 0 <= int(half) <= max_half):
+            raise ValueError(f"{fn}: half = {half} samples, outside 0 .. {max_half}")
+        return half
+
+    @staticmethod
+    def _runs_found(fn: str, noun: str, runs, words: torch.Tensor, min_len, max_runs):
+        """The one D2H copy of a detection call: `words` is the device count, or {the count, T's bits} -> (the rows that were found, T or
+        None).  A ValueError names both numbers when more than max_runs runs of `noun` samples qualify."""
+        host = words.cpu()
+        total = int(host[0])
+        T = float(host[1:].view(torch.float32)[0]) if host.numel() == 2 else None
+        if total > int(max_runs):
+            raise ValueError(f"{fn}: {total} runs of at least {int(min_len)} {noun} samples, more than max_runs = {int(max_runs)}")
+        return (runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=words.device)), T
+
     def find_quiet_runs(self, x, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536, channel: Optional[int] = None) -> torch.Tensor:
         """x (n,) fp32 or int16 (tensor or array, host or device; a device view may start anywhere) -> device int32 (R, 2): every
         maximal run of samples with |x| <= threshold of at least min_len samples, as (start, len) rows sorted by start
@@ -1169,23 +1210,9 @@ class InpaintingEngine:
         An interleaved x (n, ch >= 2) needs `channel`: an index for that channel's runs, -1 for the runs of sample
         times at which every channel is quiet; rows are in sample times (si_quiet_runs_ch).  x is not flattened or de-interleaved.
         Packed 24-bit PCM: x uint8, (n, 3) or (n, ch, 3); threshold in 24-bit steps."""
-        x = torch.as_tensor(x)
-        s24, sdim = InpaintingEngine._file_samples(x, "find_quiet_runs")
-        if sdim == 2 and x.shape[1] >= 2:
-            if channel is None:
-                raise ValueError(f"find_quiet_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
-            x = InpaintingEngine._file_on_device(x, self.device).contiguous()
-            runs, n_runs = self.ctx.quiet_runs(x, threshold, min_len, max_runs, channel=int(channel))
-        else:
-            if channel is not None and int(channel) not in (-1, 0):
-                raise ValueError(f"find_quiet_runs: channel = {channel} of a one-channel recording")
-            x = InpaintingEngine._file_on_device(x, self.device)
-            x = (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
-            runs, n_runs = self.ctx.quiet_runs(x, threshold, min_len, max_runs)
-        total = int(n_runs.item())
-        if total > int(max_runs):
-            raise ValueError(f"find_quiet_runs: {total} runs of at least {int(min_len)} quiet samples, more than max_runs = {int(max_runs)}")
-        return runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+        x, _, channel = InpaintingEngine._file_view(self, x, "find_quiet_runs", channel)
+        runs, n_runs = self.ctx.quiet_runs(x, threshold, min_len, max_runs, channel=channel)
+        return InpaintingEngine._runs_found("find_quiet_runs", "quiet", runs, n_runs, min_len, max_runs)[0]
 
     DEAD_KINDS = {"quiet": 1, "held": 2, "any": 3}                    # SI_DEAD_QUIET, SI_DEAD_HELD and both
 
@@ -1198,23 +1225,11 @@ class InpaintingEngine:
         One D2H copy: the count, which with return_threshold=True also carries T; -> runs, or (runs, T)."""
         if kind not in self.DEAD_KINDS:
             raise ValueError(f"find_dead_runs: kind = {kind!r}: 'quiet', 'held' or 'any'")
-        x = torch.as_tensor(x)
-        s24, sdim = InpaintingEngine._file_samples(x, "find_dead_runs")                      # packed 24-bit PCM: uint8 (n, 3) or (n, ch, 3), 24-bit steps
-        many = sdim == 2 and x.shape[1] >= 2
-        if many and channel is None:
-            raise ValueError(f"find_dead_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
-        if not many and channel is not None and int(channel) not in (-1, 0):
-            raise ValueError(f"find_dead_runs: channel = {channel} of a one-channel recording")
-        x = InpaintingEngine._file_on_device(x, self.device)
-        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
+        x, _, channel = InpaintingEngine._file_view(self, x, "find_dead_runs", channel)
         words = torch.zeros(2, dtype=torch.int32, device=self.device)      # {the count, T's bits}: one copy brings both
         runs, _ = self.ctx.dead_runs(x, self.DEAD_KINDS[kind], threshold, rel_threshold, held_tol, min_len, max_runs, n_runs=words[:1],
-                                     channel=int(channel) if many else None, threshold_out=words[1:].view(torch.float32))
-        host = words.cpu()
-        total, T = int(host[0]), float(host[1:].view(torch.float32)[0])
-        if total > int(max_runs):
-            raise ValueError(f"find_dead_runs: {total} runs of at least {int(min_len)} dead samples, more than max_runs = {int(max_runs)}")
-        runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+                                     channel=channel, threshold_out=words[1:].view(torch.float32))
+        runs, T = InpaintingEngine._runs_found("find_dead_runs", "dead", runs, words, min_len, max_runs)
         return (runs, T) if return_threshold else runs
 
     def find_level_runs(self, x, win: Optional[int] = None, half: Optional[int] = None, threshold: float = 0.0, rel_threshold: float = 0.0,
@@ -1224,31 +1239,12 @@ class InpaintingEngine:
         peak of x), and no NaN or inf.  Give the window as `half`, or as `win` = its odd length in samples; half = 0 is the sample-wise
         "quiet".  x, channel, min_len, max_runs, threshold, rel_threshold and the rows are find_dead_runs'.
         One D2H copy: the count, which with return_threshold=True also carries T; -> runs, or (runs, T)."""
-        if (win is None) == (half is None):
-            raise ValueError("find_level_runs: give the window as win = its odd length in samples, or as half = (win - 1) / 2, not both")
-        if win is not None:
-            if int(win) != win or int(win) < 1 or int(win) % 2 == 0:
-                raise ValueError(f"find_level_runs: win = {win}: an odd number of samples, 2 * half + 1")
-            half = (int(win) - 1) // 2
-        if int(half) != half or not 0 <= int(half) <= G.LEVEL_MAX_HALF:
-            raise ValueError(f"find_level_runs: half = {half} samples, outside 0 .. {G.LEVEL_MAX_HALF}")
-        x = torch.as_tensor(x)
-        s24, sdim = InpaintingEngine._file_samples(x, "find_level_runs")                      # packed 24-bit PCM: uint8 (n, 3) or (n, ch, 3), 24-bit steps
-        many = sdim == 2 and x.shape[1] >= 2
-        if many and channel is None:
-            raise ValueError(f"find_level_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
-        if not many and channel is not None and int(channel) not in (-1, 0):
-            raise ValueError(f"find_level_runs: channel = {channel} of a one-channel recording")
-        x = InpaintingEngine._file_on_device(x, self.device)
-        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
+        half = InpaintingEngine._window_half("find_level_runs", win, half, G.LEVEL_MAX_HALF)
+        x, _, channel = InpaintingEngine._file_view(self, x, "find_level_runs", channel)
         words = torch.zeros(2, dtype=torch.int32, device=self.device)      # {the count, T's bits}: one copy brings both
         runs, _ = self.ctx.level_runs(x, int(half), threshold, rel_threshold, min_len, max_runs, n_runs=words[:1],
-                                      channel=int(channel) if many else None, threshold_out=words[1:].view(torch.float32))
-        host = words.cpu()
-        total, T = int(host[0]), float(host[1:].view(torch.float32)[0])
-        if total > int(max_runs):
-            raise ValueError(f"find_level_runs: {total} runs of at least {int(min_len)} dead samples, more than max_runs = {int(max_runs)}")
-        runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+                                      channel=channel, threshold_out=words[1:].view(torch.float32))
+        runs, T = InpaintingEngine._runs_found("find_level_runs", "dead", runs, words, min_len, max_runs)
         return (runs, T) if return_threshold else runs
 
     def find_burst_runs(self, x, win: Optional[int] = None, half: Optional[int] = None, threshold: float = 0.0, rel_threshold: float = 0.0,
@@ -1259,33 +1255,14 @@ class InpaintingEngine:
         of x), and no NaN or inf under it.  The window, x, channel, min_len, max_runs, threshold and the rows are find_level_runs';
         rel_threshold lies in [0, 4] (|d| <= 4 * peak).  T = 0 makes every window hot and is the caller's to refuse (find_gaps does).
         One D2H copy: the count, which with return_threshold=True also carries T; -> runs, or (runs, T)."""
-        if (win is None) == (half is None):
-            raise ValueError("find_burst_runs: give the window as win = its odd length in samples, or as half = (win - 1) / 2, not both")
-        if win is not None:
-            if int(win) != win or int(win) < 1 or int(win) % 2 == 0:
-                raise ValueError(f"find_burst_runs: win = {win}: an odd number of samples, 2 * half + 1")
-            half = (int(win) - 1) // 2
-        if int(half) != half or not 0 <= int(half) <= G.LEVEL_MAX_HALF:
-            raise ValueError(f"find_burst_runs: half = {half} samples, outside 0 .. {G.LEVEL_MAX_HALF}")
+        half = InpaintingEngine._window_half("find_burst_runs", win, half, G.LEVEL_MAX_HALF)
         if not 0.0 <= float(rel_threshold) <= 4.0:
             raise ValueError(f"find_burst_runs: rel_threshold = {rel_threshold} is NaN or outside [0, 4] (a second difference is at most 4 * the peak)")
-        x = torch.as_tensor(x)
-        s24, sdim = InpaintingEngine._file_samples(x, "find_burst_runs")                      # packed 24-bit PCM: uint8 (n, 3) or (n, ch, 3), 24-bit steps
-        many = sdim == 2 and x.shape[1] >= 2
-        if many and channel is None:
-            raise ValueError(f"find_burst_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
-        if not many and channel is not None and int(channel) not in (-1, 0):
-            raise ValueError(f"find_burst_runs: channel = {channel} of a one-channel recording")
-        x = InpaintingEngine._file_on_device(x, self.device)
-        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
+        x, _, channel = InpaintingEngine._file_view(self, x, "find_burst_runs", channel)
         words = torch.zeros(2, dtype=torch.int32, device=self.device)      # {the count, T's bits}: one copy brings both
         runs, _ = self.ctx.burst_runs(x, int(half), threshold, rel_threshold, min_len, max_runs, n_runs=words[:1],
-                                      channel=int(channel) if many else None, threshold_out=words[1:].view(torch.float32))
-        host = words.cpu()
-        total, T = int(host[0]), float(host[1:].view(torch.float32)[0])
-        if total > int(max_runs):
-            raise ValueError(f"find_burst_runs: {total} runs of at least {int(min_len)} dead samples, more than max_runs = {int(max_runs)}")
-        runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+                                      channel=channel, threshold_out=words[1:].view(torch.float32))
+        runs, T = InpaintingEngine._runs_found("find_burst_runs", "dead", runs, words, min_len, max_runs)
         return (runs, T) if return_threshold else runs
 
     def find_impulse_runs(self, x, win: Optional[int] = None, half: Optional[int] = None, order: int = 16, guard: int = 4, pad: int = 2,
@@ -1298,30 +1275,13 @@ class InpaintingEngine:
         when a hot one lies within `pad` of it.  win = 2 * half + 1.  T = 0 (the default) is allowed: the ratio test remains.  x,
         channel, min_len, max_runs and the rows are find_level_runs'; rel_threshold lies in [0, 4].
         One D2H copy: the count, which with return_threshold=True also carries T; -> runs, or (runs, T)."""
-        if (win is None) == (half is None):
-            raise ValueError("find_impulse_runs: give the window as win = its odd length in samples, or as half = (win - 1) / 2, not both")
-        if win is not None:
-            if int(win) != win or int(win) < 1 or int(win) % 2 == 0:
-                raise ValueError(f"find_impulse_runs: win = {win}: an odd number of samples, 2 * half + 1")
-            half = (int(win) - 1) // 2
+        half = InpaintingEngine._window_half("find_impulse_runs", win, half)
         G.check_impulse("find_impulse_runs", order, half, guard, pad, ratio, rel_threshold)
-        x = torch.as_tensor(x)
-        s24, sdim = InpaintingEngine._file_samples(x, "find_impulse_runs")                    # packed 24-bit PCM: uint8 (n, 3) or (n, ch, 3), 24-bit steps
-        many = sdim == 2 and x.shape[1] >= 2
-        if many and channel is None:
-            raise ValueError(f"find_impulse_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
-        if not many and channel is not None and int(channel) not in (-1, 0):
-            raise ValueError(f"find_impulse_runs: channel = {channel} of a one-channel recording")
-        x = InpaintingEngine._file_on_device(x, self.device)
-        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
+        x, _, channel = InpaintingEngine._file_view(self, x, "find_impulse_runs", channel)
         words = torch.zeros(2, dtype=torch.int32, device=self.device)      # {the count, T's bits}: one copy brings both
         runs, _ = self.ctx.impulse_runs(x, int(order), int(half), int(guard), int(pad), ratio, threshold, rel_threshold, min_len, max_runs,
-                                        n_runs=words[:1], channel=int(channel) if many else None, threshold_out=words[1:].view(torch.float32))
-        host = words.cpu()
-        total, T = int(host[0]), float(host[1:].view(torch.float32)[0])
-        if total > int(max_runs):
-            raise ValueError(f"find_impulse_runs: {total} runs of at least {int(min_len)} dead samples, more than max_runs = {int(max_runs)}")
-        runs = runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+                                        n_runs=words[:1], channel=channel, threshold_out=words[1:].view(torch.float32))
+        runs, T = InpaintingEngine._runs_found("find_impulse_runs", "dead", runs, words, min_len, max_runs)
         return (runs, T) if return_threshold else runs
 
     def impulse_residual(self, x, order: int = 16, channel: Optional[int] = None) -> torch.Tensor:
@@ -1360,20 +1320,9 @@ class InpaintingEngine:
         c = float(ceiling)
         if not c > 0.0:
             raise ValueError(f"find_invalid_runs: ceiling = {ceiling} is not above 0, or is NaN (+inf, the samples that are not finite, is allowed)")
-        x = torch.as_tensor(x)
-        s24, sdim = InpaintingEngine._file_samples(x, "find_invalid_runs")
-        many = sdim == 2 and x.shape[1] >= 2
-        if many and channel is None:
-            raise ValueError(f"find_invalid_runs: an (n, {x.shape[1]}) recording needs channel = an index, or -1 for joint detection")
-        if not many and channel is not None and int(channel) not in (-1, 0):
-            raise ValueError(f"find_invalid_runs: channel = {channel} of a one-channel recording")
-        x = InpaintingEngine._file_on_device(x, self.device)
-        x = x.contiguous() if many else (x.reshape(-1, 3) if s24 else x.reshape(-1)).contiguous()
-        runs, n_runs = self.ctx.invalid_runs(x, c, min_len, max_runs, channel=int(channel) if many else None)
-        total = int(n_runs.item())
-        if total > int(max_runs):
-            raise ValueError(f"find_invalid_runs: {total} runs of at least {int(min_len)} invalid samples, more than max_runs = {int(max_runs)}")
-        return runs[:total] if runs is not None else torch.zeros(0, 2, dtype=torch.int32, device=self.device)
+        x, _, channel = InpaintingEngine._file_view(self, x, "find_invalid_runs", channel)
+        runs, n_runs = self.ctx.invalid_runs(x, c, min_len, max_runs, channel=channel)
+        return InpaintingEngine._runs_found("find_invalid_runs", "invalid", runs, n_runs, min_len, max_runs)[0]
 
     # ---- short runs mended in place by least-squares AR interpolation
     @staticmethod

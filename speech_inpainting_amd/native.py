@@ -836,14 +836,12 @@ class NativeContext:
             self._check(self.lib.si_cut_pair(self._h, _ptr(x), self._sample_format(x), n_file, int(sr), *tail), "si_cut_pair")
         return outs[0], outs[1]
 
-    # ---- dropout detection
-    def quiet_runs(self, x: torch.Tensor, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536, runs: Optional[torch.Tensor] = None,
-                   n_runs: Optional[torch.Tensor] = None, channel: Optional[int] = None):
-        """x (n,) fp32 or int16 on the device (a view may start anywhere) -> (runs (max_runs, 2) int32, n_runs (1,) int32), both on
-        the device: the maximal runs of |x| <= threshold of at least min_len samples as (start, len) rows sorted by start, and how
-        many there are in all (si_quiet_runs).  Rows at and past min(n_runs, max_runs) are not written; max_runs = 0 counts only.
-        channel = c: x is (n, ch) interleaved and the runs are channel c's, in sample times; channel = -1: the runs of sample times at
-        which EVERY channel is quiet (si_quiet_runs_ch)."""
+    # ---- dropout detection; one call shape for every detector (4.34)
+    def _runs_call(self, name: str, x: torch.Tensor, args, min_len, max_runs, runs, n_runs, channel, threshold_out=None, takes_channels: bool = True,
+                   takes_threshold_out: bool = True):
+        """The run-list entry point `name`: (ctx, x, format, n, [channels, channel,] *args, min_len, runs, max_runs, n_runs, [threshold_out,]
+        stream).  `args` are the detector's own, already int / float.  Allocates runs (max_runs, 2) and n_runs (1,) when they are not given;
+        an x without `channel` is the one-channel file, channels = 1.  -> (runs, n_runs)."""
         n, ch = self._interleaved(x, channel)
         max_runs = int(max_runs)
         if runs is None and max_runs > 0:
@@ -852,13 +850,23 @@ class NativeContext:
             n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
         assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
         assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
-        if channel is not None:
-            self._check(self.lib.si_quiet_runs_ch(self._h, _ptr(x), self._sample_format(x), n, ch, int(channel), float(threshold), int(min_len),
-                                                  _ptr(runs), max_runs, _ptr(n_runs), self._stream()), "si_quiet_runs_ch")
-            return runs, n_runs
-        self._check(self.lib.si_quiet_runs(self._h, _ptr(x), self._sample_format(x), n, float(threshold), int(min_len),
-                                           _ptr(runs), max_runs, _ptr(n_runs), self._stream()), "si_quiet_runs")
+        assert threshold_out is None or (threshold_out.is_cuda and threshold_out.dtype == torch.float32 and threshold_out.numel() == 1)
+        file = (ch if channel is not None else 1, int(channel) if channel is not None else 0) if takes_channels else ()
+        out = (_ptr(threshold_out),) if takes_threshold_out else ()
+        self._check(getattr(self.lib, name)(self._h, _ptr(x), self._sample_format(x), n, *file, *args, int(min_len), _ptr(runs), max_runs, _ptr(n_runs),
+                                            *out, self._stream()), name)
         return runs, n_runs
+
+    def quiet_runs(self, x: torch.Tensor, threshold: float = 0.0, min_len: int = 1, max_runs: int = 65536, runs: Optional[torch.Tensor] = None,
+                   n_runs: Optional[torch.Tensor] = None, channel: Optional[int] = None):
+        """x (n,) fp32 or int16 on the device (a view may start anywhere) -> (runs (max_runs, 2) int32, n_runs (1,) int32), both on
+        the device: the maximal runs of |x| <= threshold of at least min_len samples as (start, len) rows sorted by start, and how
+        many there are in all (si_quiet_runs).  Rows at and past min(n_runs, max_runs) are not written; max_runs = 0 counts only.
+        channel = c: x is (n, ch) interleaved and the runs are channel c's, in sample times; channel = -1: the runs of sample times at
+        which EVERY channel is quiet (si_quiet_runs_ch)."""
+        name = "si_quiet_runs_ch" if channel is not None else "si_quiet_runs"          # the mono entry point has no channels
+        return self._runs_call(name, x, (float(threshold),), min_len, max_runs, runs, n_runs, channel, takes_channels=channel is not None,
+                               takes_threshold_out=False)
 
     # ---- held-sample and peak-relative dropouts (DESIGN.md 4.20)
     def dead_runs(self, x: torch.Tensor, kind: int = DEAD_QUIET | DEAD_HELD, threshold: float = 0.0, rel_threshold: float = 0.0,
@@ -868,20 +876,8 @@ class NativeContext:
         DEAD_QUIET) or when it is within held_tol of a neighbour of its own channel (kind & DEAD_HELD).  x (n,) or, with `channel`,
         (n, ch) interleaved; -> (runs, n_runs) as quiet_runs returns them.  threshold_out: a device fp32 word that receives T.
         n_runs may be one word of a longer int32 tensor (the engine reads count and T in one copy)."""
-        n, ch = self._interleaved(x, channel)
-        max_runs = int(max_runs)
-        if runs is None and max_runs > 0:
-            runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
-        if n_runs is None:
-            n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
-        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
-        assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
-        assert threshold_out is None or (threshold_out.is_cuda and threshold_out.dtype == torch.float32 and threshold_out.numel() == 1)
-        self._check(self.lib.si_dead_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
-                                          int(channel) if channel is not None else 0, int(kind), float(threshold), float(rel_threshold),
-                                          float(held_tol), int(min_len), _ptr(runs), max_runs, _ptr(n_runs), _ptr(threshold_out), self._stream()),
-                    "si_dead_runs")
-        return runs, n_runs
+        return self._runs_call("si_dead_runs", x, (int(kind), float(threshold), float(rel_threshold), float(held_tol)), min_len, max_runs, runs, n_runs,
+                               channel, threshold_out)
 
     # ---- dropouts by windowed RMS level (DESIGN.md 4.25)
     def level_runs(self, x: torch.Tensor, half: int = 0, threshold: float = 0.0, rel_threshold: float = 0.0, min_len: int = 1,
@@ -890,20 +886,8 @@ class NativeContext:
         """dead_runs with si_level_runs' predicate: a sample is dead when a window of 2 * half + 1 samples of its channel within half
         samples of it has an RMS level of at most T = max(threshold, rel_threshold * peak) and no NaN or inf in it.  x, channel, runs,
         n_runs and threshold_out are dead_runs'; -> (runs, n_runs)."""
-        n, ch = self._interleaved(x, channel)
-        max_runs = int(max_runs)
-        if runs is None and max_runs > 0:
-            runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
-        if n_runs is None:
-            n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
-        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
-        assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
-        assert threshold_out is None or (threshold_out.is_cuda and threshold_out.dtype == torch.float32 and threshold_out.numel() == 1)
-        self._check(self.lib.si_level_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
-                                           int(channel) if channel is not None else 0, int(half), float(threshold), float(rel_threshold),
-                                           int(min_len), _ptr(runs), max_runs, _ptr(n_runs), _ptr(threshold_out), self._stream()),
-                    "si_level_runs")
-        return runs, n_runs
+        return self._runs_call("si_level_runs", x, (int(half), float(threshold), float(rel_threshold)), min_len, max_runs, runs, n_runs, channel,
+                               threshold_out)
 
     # ---- corrupted blocks by second-difference level (DESIGN.md 4.28)
     def burst_runs(self, x: torch.Tensor, half: int = 0, threshold: float = 0.0, rel_threshold: float = 0.0, min_len: int = 1,
@@ -912,20 +896,8 @@ class NativeContext:
         """level_runs with si_burst_runs' predicate: a sample is dead when a window of 2 * half + 1 second differences x[k - 1] -
         2 x[k] + x[k + 1] of its channel within half samples of it has an RMS level of AT LEAST T = max(threshold, rel_threshold *
         peak) and no NaN or inf under it.  x, channel, runs, n_runs and threshold_out are dead_runs'; -> (runs, n_runs)."""
-        n, ch = self._interleaved(x, channel)
-        max_runs = int(max_runs)
-        if runs is None and max_runs > 0:
-            runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
-        if n_runs is None:
-            n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
-        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
-        assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
-        assert threshold_out is None or (threshold_out.is_cuda and threshold_out.dtype == torch.float32 and threshold_out.numel() == 1)
-        self._check(self.lib.si_burst_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
-                                           int(channel) if channel is not None else 0, int(half), float(threshold), float(rel_threshold),
-                                           int(min_len), _ptr(runs), max_runs, _ptr(n_runs), _ptr(threshold_out), self._stream()),
-                    "si_burst_runs")
-        return runs, n_runs
+        return self._runs_call("si_burst_runs", x, (int(half), float(threshold), float(rel_threshold)), min_len, max_runs, runs, n_runs, channel,
+                               threshold_out)
 
     # ---- NaN, inf and out-of-range samples (DESIGN.md 4.30)
     def invalid_runs(self, x: torch.Tensor, ceiling: float = float("inf"), min_len: int = 1, max_runs: int = 65536,
@@ -934,18 +906,7 @@ class NativeContext:
         |x| > ceiling in the file's own steps for int16 / packed 24-bit PCM, so only under a finite ceiling.  ceiling > 0, +inf (the
         default) = "not finite".  x, channel (-1: every channel invalid), runs and n_runs are dead_runs'; no threshold comes back.
         -> (runs, n_runs)."""
-        n, ch = self._interleaved(x, channel)
-        max_runs = int(max_runs)
-        if runs is None and max_runs > 0:
-            runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
-        if n_runs is None:
-            n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
-        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
-        assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
-        self._check(self.lib.si_invalid_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
-                                             int(channel) if channel is not None else 0, float(ceiling), int(min_len), _ptr(runs), max_runs,
-                                             _ptr(n_runs), self._stream()), "si_invalid_runs")
-        return runs, n_runs
+        return self._runs_call("si_invalid_runs", x, (float(ceiling),), min_len, max_runs, runs, n_runs, channel, takes_threshold_out=False)
 
     # ---- clicks and pops by locally scaled AR prediction error (DESIGN.md 4.33)
     def impulse_runs(self, x: torch.Tensor, order: int = 16, half: int = 256, guard: int = 4, pad: int = 2, ratio: float = 10.0,
@@ -956,20 +917,8 @@ class NativeContext:
         error under an AR model of order `order`, fitted per block of 512 samples, is above T^2, T = max(threshold, rel_threshold *
         peak), and above ratio^2 times the mean squared prediction error of the samples within `half` of it, `guard` samples on either
         side left out.  x, channel, runs, n_runs and threshold_out are dead_runs'; -> (runs, n_runs)."""
-        n, ch = self._interleaved(x, channel)
-        max_runs = int(max_runs)
-        if runs is None and max_runs > 0:
-            runs = torch.empty(max_runs, 2, dtype=torch.int32, device=self.device)
-        if n_runs is None:
-            n_runs = torch.empty(1, dtype=torch.int32, device=self.device)
-        assert runs is None or (runs.is_cuda and runs.dtype == torch.int32 and runs.is_contiguous() and runs.numel() >= 2 * max_runs)
-        assert n_runs.is_cuda and n_runs.dtype == torch.int32 and n_runs.numel() == 1
-        assert threshold_out is None or (threshold_out.is_cuda and threshold_out.dtype == torch.float32 and threshold_out.numel() == 1)
-        self._check(self.lib.si_impulse_runs(self._h, _ptr(x), self._sample_format(x), n, ch if channel is not None else 1,
-                                             int(channel) if channel is not None else 0, int(order), int(half), int(guard), int(pad),
-                                             float(ratio), float(threshold), float(rel_threshold), int(min_len), _ptr(runs), max_runs,
-                                             _ptr(n_runs), _ptr(threshold_out), self._stream()), "si_impulse_runs")
-        return runs, n_runs
+        return self._runs_call("si_impulse_runs", x, (int(order), int(half), int(guard), int(pad), float(ratio), float(threshold), float(rel_threshold)),
+                               min_len, max_runs, runs, n_runs, channel, threshold_out)
 
     def impulse_residual(self, x: torch.Tensor, order: int = 16, channel: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The prediction error si_impulse_runs judges, sample by sample (si_impulse_residual): x (n,) or, with channel = c >= 0, channel c

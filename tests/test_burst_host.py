@@ -43,7 +43,8 @@ def test_the_entry_point_is_declared_and_bound():
     api = open(os.path.join(ROOT, "speech_inpainting_amd", "csrc", "api.hip")).read()
     assert re.search(r"^int si_burst_runs\(", api, re.M)
     kern = open(os.path.join(ROOT, "speech_inpainting_amd", "csrc", "detect_kernels.hip")).read()
-    assert "detect_burst_kernel" in kern and "struct DtBurst" in kern
+    route = kern[kern.index("    case SI_DET_BURST: {"):kern.index("    case SI_DET_INVALID:")]      # the route's pass 1 in the launcher's one switch
+    assert "detect_burst_kernel" in kern and "detect_burst_kernel<T><<<" in route and re.findall(r'"(\w+)"', route) == ["detect_dead"]
     assert '"detect_burst"' not in kern                                 # profiled as "detect_dead": tests/poison.py's family lists are closed
     body = kern[kern.index("void bu_square(float"):kern.index("void bu_square(int16_t")]
     assert "#pragma clang fp contract(off)" in body and "fma" not in body.lower().replace("fused multiply", "")

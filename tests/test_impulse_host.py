@@ -58,12 +58,14 @@ def test_the_entry_points_are_declared_and_bound():
 
 def test_one_body_two_wrappers_and_a_profile_name_of_the_closed_lists():
     kern = open(os.path.join(ROOT, "speech_inpainting_amd", "csrc", "detect_kernels.hip")).read()
-    assert "struct DtImpulse" in kern and kern.count("im_residual_body(x, n, ch,") == 2          # the detector and the tap call the same body
+    assert "case SI_DET_IMPULSE:" in kern and kern.count("im_residual_body(x, n, ch,") == 2      # the detector and the tap call the same body
     for name in ("detect_impulse_kernel", "detect_impulse_residual_kernel"):
         assert re.search(rf"__global__ __launch_bounds__\(256\) void {name}\(", kern)
     assert '"detect_impulse"' not in kern and "detect_dead" in poison.SCRATCH_FAMILIES
     families = set(poison.SCRATCH_FAMILIES) | set(poison.NO_SCRATCH_FAMILIES)
-    launcher = kern[kern.index("    if (impulse) {"):kern.index("    } else if (invalid) {")]
+    # the launcher's pass 0, written once in front of its one switch, and the route's own case
+    launcher = kern[kern.index("    if (d.rel > 0.f) {"):kern.index("    switch (d.route) {")] + kern[kern.index("    case SI_DET_IMPULSE: {"):kern.index("    default:")]
+    assert "detect_impulse_kernel<T><<<" in launcher
     assert re.findall(r'si_prof_begin\(ctx, "(\w+)"', launcher) == ["detect_peak", "detect_peak_final", "detect_dead"]
     tap = kern[kern.index("static int im_residual_launch_t("):]
     assert re.findall(r'si_prof_begin\(ctx, "(\w+)"', tap) == ["detect_dead"] and {"detect_peak", "detect_peak_final", "detect_dead"} <= families

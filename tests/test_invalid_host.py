@@ -64,7 +64,7 @@ def test_the_entry_points_are_declared_and_bound():
     assert common.count("bool si_invalid(") == 3 and "__builtin_fminf(c, __FLT_MAX__)" in common
     src = {f: open(os.path.join(ROOT, "speech_inpainting_amd", "csrc", f)).read() for f in ("detect_kernels.hip", "rate_feed_kernels.hip", "patch_kernels.hip")}
     assert all("si_invalid(" in s and "bool si_invalid" not in s for s in src.values())
-    assert "struct DtInvalid" in src["detect_kernels.hip"] and "rf_cut_tile<T, true>" in src["rate_feed_kernels.hip"] and "rf_pair_tile<T, false>" in src["rate_feed_kernels.hip"]
+    assert "case SI_DET_INVALID:" in src["detect_kernels.hip"] and "rf_cut_tile<T, true>" in src["rate_feed_kernels.hip"] and "rf_pair_tile<T, false>" in src["rate_feed_kernels.hip"]
     if os.path.exists(native.LIB_PATH):
         lib = native.load_library()
         assert lib.si_version() == 3
@@ -87,7 +87,8 @@ def test_the_new_launchers_use_profile_names_of_the_closed_lists():
                 assert lit in families, (f, lit)
     assert {"detect_bits", "detect_bits_ch", "cut_rate", "cut_rate_ch", "cut_clips"} <= found
     kern = open(os.path.join(ROOT, "speech_inpainting_amd", "csrc", "detect_kernels.hip")).read()
-    body = kern[kern.index("if (invalid) {"):kern.index("} else if (dead || level || burst)")]
+    body = kern[kern.index("    case SI_DET_INVALID:"):kern.index("    case SI_DET_IMPULSE: {")]     # the route's case of the launcher's one switch
+    assert "detect_invalid_kernel<T><<<" in body and "detect_invalid_ch_kernel<T><<<" in body
     assert re.findall(r'"(\w+)"', body) == ["detect_bits", "detect_bits_ch"] and "detect_invalid" not in "".join(re.findall(r'"(\w+)"', kern))
     assert "detect_bits" in poison.SCRATCH_FAMILIES and "cut_rate" in poison.NO_SCRATCH_FAMILIES and "cut_clips" in poison.NO_SCRATCH_FAMILIES
 

@@ -124,6 +124,18 @@ int main() {
                 EXPECT(hi < n && (hi < 0 || lo >= 0), "n = %d, h = %d, chunk %d: reads [%ld, %ld]", n, h, c, lo, hi);
             }
         }
+    // the image of detect_dead_ch_kernel: every channel count the ABI accepts, joint (m = channels) or one channel (m = 1), in each sample
+    // type, WALKED: the first element staged and the last one read, img[(p + 2) m + k] at p = DT_CHUNK - 1, k = m - 1
+    for (size_t elem : {(size_t)4, (size_t)2, (size_t)3})
+        for (int m = 1; m <= SI_MAX_CHANNELS; ++m) {
+            const size_t lds = dt_dead_ch_lds(m, elem);
+            EXPECT(lds == (size_t)(DT_CHUNK + 2) * m * elem && lds + 16 <= CU_LDS, "m = %d, %zu-byte samples: %zu bytes", m, elem, lds);
+            std::vector<unsigned char> img(lds);
+            const size_t last = (size_t)(DT_CHUNK - 1 + 2) * m + (m - 1);
+            memset(img.data(), 1, elem), memset(img.data() + last * elem, 1, elem);
+            EXPECT((last + 1) * elem == lds, "m = %d: the last element ends at byte %zu of %zu", m, (last + 1) * elem, lds);
+        }
+    EXPECT(dt_dead_ch_lds(8, 4) == 65600, "%zu", dt_dead_ch_lds(8, 4));
     // the impulse pass: every (half, pad, order, guard) at the limits, and every half in between at the extreme pads
     for (int p : {2, 16, SI_IMPULSE_MAX_ORDER})
         for (int g : {0, 4, SI_IMPULSE_MAX_GUARD})
