@@ -1032,7 +1032,8 @@ class InpaintingEngine:
         threshold is in x's own units, as find_gaps takes it: full scale for fp32, int16 steps for an int16 file, 24-bit steps for
         packed 24-bit PCM (uint8 (n, 3) or (n, ch, 3), DESIGN.md 4.27: it needs feed="contexts" and comes back as uint8).
         feed: patch_file's ("recording" or "contexts").  clips16: patch_file's ("resampled" or "file"), passed on when
-        it is off its default.
+        it is off its default.  What patch_file refuses about feed="recording" at sr != 22050 -- clips16="file", and the ceiling of kind
+        "invalid" -- is refused here in its words, before the detection has launched anything.
         -> patch_file's dictionary + gaps + skipped.  With nothing found: an exact copy; only the detection kernels launched.
         An interleaved file x (n, ch >= 2): detect="each" runs the detection once per channel and repairs a dropout
         in the channel it is in (gaps, skipped: one list per channel); detect="joint" runs it once over the sample times at which
@@ -1082,6 +1083,14 @@ class InpaintingEngine:
             raise ValueError(f"conceal_file: packed 24-bit PCM needs feed = 'contexts' (feed = {feed!r} resamples an fp32 image of the whole file)")
         if s24 and sr == 22050:
             raise ValueError("conceal_file: packed 24-bit PCM at 22050 Hz is not served: that file goes through conceal_recording as fp32")
+        # patch_file's two rules on feed="recording", in its words, before the detection (and the mending) has launched anything for a call
+        # that patch_file would refuse afterwards
+        if feed == "recording" and sr != 22050:
+            if kind == "invalid":
+                raise ValueError(f"patch_file: ceiling = {G.invalid_ceiling(threshold)} needs feed=\"contexts\" at {sr} Hz (feed = {feed!r} resamples the whole "
+                                 f"file, which smears an invalid sample over every output within the filter's reach before anything could clean it)")
+            if clips16 == "file":
+                raise ValueError(f"patch_file: clips16 = 'file' needs feed = 'contexts' (with feed = {feed!r} the clips are slices of the resampled recording)")
         shape = x.shape
         many = sdim == 2 and shape[1] >= 2                             # (n, 1) is the mono route, reshaped at the end
         if many and shape[1] > G.MAX_CHANNELS:
