@@ -1613,36 +1613,32 @@ int si_patch_compose(si_ctx* ctx, const float* orig, const si_span_table* spans,
 // ---- long recordings
 static const long SI_MAX_REC = 0x7fffffffL - 2048;      // int32 sample indices, one chunk of headroom for the chunk's end
 
-int si_cut_clips(si_ctx* ctx, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L, float* out,
-                 si_stream_t stream) {
+// ceiling != nullptr is si_cut_clips_valid: an invalid sample copied as +0.0 -- the same refusals under that entry's name, plus
+// the ceiling's.
+static int cut_clips_call(si_ctx* ctx, const char* fn, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L,
+                          float* out, si_stream_t stream, const float* ceiling) {
     if (!ctx) return SI_EINVAL;
-    if (!src || !host_start || !start || !out || n_src <= 0 || C <= 0 || L <= 0) return si_fail(ctx, SI_EINVAL, "si_cut_clips: NULL / empty argument");
-    if ((long)n_src > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_cut_clips: a source of %d samples, at most %ld", n_src, SI_MAX_REC);
-    if (C > 65535) return si_fail(ctx, SI_EINVAL, "si_cut_clips: %d clips in one call, at most 65535 (the launch grid's second dimension)", C);
+    if (!src || !host_start || !start || !out || n_src <= 0 || C <= 0 || L <= 0) return si_fail(ctx, SI_EINVAL, "%s: NULL / empty argument", fn);
+    if ((long)n_src > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "%s: a source of %d samples, at most %ld", fn, n_src, SI_MAX_REC);
+    if (C > 65535) return si_fail(ctx, SI_EINVAL, "%s: %d clips in one call, at most 65535 (the launch grid's second dimension)", fn, C);
+    if (ceiling && !(*ceiling > 0.f)) return si_fail(ctx, SI_EINVAL, "%s: ceiling = %g is not above 0, or is NaN", fn, (double)*ceiling);
     for (int c = 0; c < C; ++c) {
         const long s = host_start[c];
         if (s < 0 || s + L > n_src)
-            return si_fail(ctx, SI_EINVAL, "si_cut_clips: clip %d = samples [%ld, %ld) is outside the source's %d samples", c, s, s + L, n_src);
+            return si_fail(ctx, SI_EINVAL, "%s: clip %d = samples [%ld, %ld) is outside the source's %d samples", fn, c, s, s + L, n_src);
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
-    return si_launch_cut_clips(ctx, src, start, C, L, out, static_cast<hipStream_t>(stream));
+    return si_launch_cut_clips(ctx, src, start, C, L, ceiling, out, static_cast<hipStream_t>(stream));
 }
 
-// si_cut_clips with an invalid sample copied as +0.0: its refusals under this entry's name, plus the ceiling.
+int si_cut_clips(si_ctx* ctx, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L, float* out,
+                 si_stream_t stream) {
+    return cut_clips_call(ctx, "si_cut_clips", src, n_src, host_start, start, C, L, out, stream, nullptr);
+}
+
 int si_cut_clips_valid(si_ctx* ctx, const float* src, int n_src, const int32_t* host_start, const int32_t* start, int C, int L, float ceiling,
                        float* out, si_stream_t stream) {
-    if (!ctx) return SI_EINVAL;
-    if (!src || !host_start || !start || !out || n_src <= 0 || C <= 0 || L <= 0) return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: NULL / empty argument");
-    if ((long)n_src > SI_MAX_REC) return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: a source of %d samples, at most %ld", n_src, SI_MAX_REC);
-    if (C > 65535) return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: %d clips in one call, at most 65535 (the launch grid's second dimension)", C);
-    if (!(ceiling > 0.f)) return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: ceiling = %g is not above 0, or is NaN", (double)ceiling);
-    for (int c = 0; c < C; ++c) {
-        const long s = host_start[c];
-        if (s < 0 || s + L > n_src)
-            return si_fail(ctx, SI_EINVAL, "si_cut_clips_valid: clip %d = samples [%ld, %ld) is outside the source's %d samples", c, s, s + L, n_src);
-    }
-    SI_HIP_CHECK(hipSetDevice(ctx->device));
-    return si_launch_cut_clips_valid(ctx, src, start, C, L, ceiling, out, static_cast<hipStream_t>(stream));
+    return cut_clips_call(ctx, "si_cut_clips_valid", src, n_src, host_start, start, C, L, out, stream, &ceiling);
 }
 
 int si_patch_regions(si_ctx* ctx, const float* orig, int N22, const si_region_table* table, const float* gen, int Lrow, const float* gain,
@@ -1723,6 +1719,13 @@ static int si_check_channels(si_ctx* ctx, const char* fn, int channels, int chan
     return SI_OK;
 }
 
+// (P, Q) = (target, sr) / gcd: sample j of the target rate's axis sits at position j Q / P of the axis at sr
+static void si_rate_ratio(long target, long sr, long* P, long* Q) {
+    long ga = target, gb = sr;
+    while (gb) { const long r = ga % gb; ga = gb; gb = r; }
+    *P = target / ga, *Q = sr / ga;
+}
+
 static int patch_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* orig, int is_pcm16, int n_file, int channels, int channel, int sr,
                            const si_rate_table* table, const float* gen, int Lrow, const float* gain, const si_sinc_filter* filt, void* out,
                            si_stream_t stream) {
@@ -1733,9 +1736,8 @@ static int patch_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* 
     if (sr < 4000 || sr > 192000) return SI_FAIL_FN("sr = %d Hz, outside 4000 .. 192000", sr);
     if (sr == 22050) return SI_FAIL_FN("sr = 22050 Hz is the generator's own rate: that file is si_patch_regions'");
     if ((long)n_file > SI_MAX_REC) return SI_FAIL_FN("a file of %d samples, at most %ld", n_file, SI_MAX_REC);
-    long ga = 22050, gb = sr;
-    while (gb) { const long r = ga % gb; ga = gb; gb = r; }
-    const long P = 22050 / ga, Qr = sr / ga;
+    long P, Qr;
+    si_rate_ratio(22050, sr, &P, &Qr);
     const long N22 = ((long)n_file * P + Qr - 1) / Qr;              // the recording's samples on the 22.05 kHz axis, ceil(n_file P / Q)
     if (N22 > SI_MAX_REC) return SI_FAIL_FN("%d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
     const si_sinc_filter* f = filt;
@@ -1810,10 +1812,11 @@ static int patch_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* 
         }
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
+    // the tables run 22 050 -> sr: the file is the target axis, so its ratio is (Qr, P)
     const SiRate rt{t->start, t->len, t->span_win, t->span_lim, t->win_ctx, t->win_start, t->win_len, t->win_lim, t->chunk, t->k0, t->k1, t->ramp, fade,
-                    f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Qr, (int)H, (int)row_cap};
-    if (inter) return si_launch_patch_rate_ch(ctx, orig, si_sample_format(is_pcm16), n_file, channels, channel, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
-    return si_launch_patch_rate(ctx, orig, si_sample_format(is_pcm16), n_file, rt, Q, gen, Lrow, gain, out, static_cast<hipStream_t>(stream));
+                    SiTaps{f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)Qr, (int)P, (int)H}, (int)row_cap};
+    return si_launch_patch_rate(ctx, orig, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, rt, Q, gen, Lrow, gain, out,
+                                static_cast<hipStream_t>(stream));
 }
 
 int si_patch_rate(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, int sr, const si_rate_table* table, const float* gen, int Lrow,
@@ -1827,6 +1830,16 @@ int si_patch_rate_ch(si_ctx* ctx, const void* orig, int is_pcm16, int n_file, in
 }
 
 // ---- context clips cut at the file's own sample rate
+// One rate's tables of a feed call, sr -> the rate whose ratio to sr is P / Q: the checks every feed puts to a filter, under the
+// argument's own name.
+static int feed_taps(si_ctx* ctx, const char* fn, const char* arg, const si_sinc_filter* f, long P, long Q, SiTaps* r) {
+    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return SI_FAIL_FN("%s: si_sinc_filter size mismatch", arg);
+    if (!f->win || !f->dwin || f->nwin < 2 || f->num_table < 1 || f->step < 1 || !(f->scale > 0.0 && f->scale <= 1.0))
+        return SI_FAIL_FN("%s: bad filter table (nwin %d, num_table %d, step %d, scale %g)", arg, f->nwin, f->num_table, f->step, f->scale);
+    *r = SiTaps{f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Q, (int)(((long)f->nwin + f->step - 1) / f->step)};
+    return SI_OK;
+}
+
 // ceiling != nullptr is si_cut_rate_valid: the same checks, one more, and the launch that stages invalid samples as +0.0.
 static int cut_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* x, int is_pcm16, int n_file, int channels, int channel, int sr,
                          const int32_t* host_start, const int32_t* start, int C, int L, const si_sinc_filter* filt, float* out, si_stream_t stream,
@@ -1838,16 +1851,13 @@ static int cut_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* x,
     if (sr == 22050) return SI_FAIL_FN("sr = 22050 Hz is the model's own rate: that file is si_cut_clips'");
     if (n_file < 1) return SI_FAIL_FN("n_file = %d", n_file);
     if ((long)n_file > SI_MAX_REC) return SI_FAIL_FN("n_file = %d samples, at most %ld", n_file, SI_MAX_REC);
-    long ga = 22050, gb = sr;
-    while (gb) { const long r = ga % gb; ga = gb; gb = r; }
-    const long P = 22050 / ga, Qr = sr / ga;
+    long P, Qr;
+    si_rate_ratio(22050, sr, &P, &Qr);
     const long N22 = ((long)n_file * P + Qr - 1) / Qr;              // the recording's samples on the 22.05 kHz axis, ceil(n_file P / Q)
     if (N22 > SI_MAX_REC) return SI_FAIL_FN("n_file = %d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
-    const si_sinc_filter* f = filt;
-    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return SI_FAIL_FN("filt: si_sinc_filter size mismatch");
-    if (!f->win || !f->dwin || f->nwin < 2 || f->num_table < 1 || f->step < 1 || !(f->scale > 0.0 && f->scale <= 1.0))
-        return SI_FAIL_FN("filt: bad filter table (nwin %d, num_table %d, step %d, scale %g)", f->nwin, f->num_table, f->step, f->scale);
-    const long H = ((long)f->nwin + f->step - 1) / f->step;
+    SiFeed fd{};
+    if (feed_taps(ctx, fn, "filt", filt, P, Qr, &fd.r) != SI_OK) return SI_EINVAL;
+    const long H = fd.r.H;
     const long cap = (RF_TILE - 1) * Qr / P + 2 + 2 * H;            // file samples one tile stages in LDS: 5 581 at 192 kHz with kaiser_best, of 160 KB
     if (cap * (long)sizeof(float) > 65536)
         return SI_FAIL_FN("filt: bad filter table: %ld taps per wing at %d Hz need %ld staged samples per tile, at most 16384", H, sr, cap);
@@ -1862,12 +1872,9 @@ static int cut_rate_call(si_ctx* ctx, const char* fn, bool inter, const void* x,
             return SI_FAIL_FN("start[%d]: clip = 22.05 kHz samples [%ld, %ld) is outside the recording's %ld samples", c, s, s + L, N22);
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
-    const SiFeed fd{f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)P, (int)Qr, (int)H, (int)cap, (int)N22};
-    if (ceiling)
-        return si_launch_cut_rate_valid(ctx, x, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, start, C, L, fd, *ceiling, out,
-                                        static_cast<hipStream_t>(stream));
-    if (inter) return si_launch_cut_rate_ch(ctx, x, si_sample_format(is_pcm16), n_file, channels, channel, start, C, L, fd, out, static_cast<hipStream_t>(stream));
-    return si_launch_cut_rate(ctx, x, si_sample_format(is_pcm16), n_file, start, C, L, fd, out, static_cast<hipStream_t>(stream));
+    fd.cap = (int)cap, fd.N22 = (int)N22;
+    return si_launch_cut_rate(ctx, x, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, start, C, L, fd, ceiling, out,
+                              static_cast<hipStream_t>(stream));
 }
 
 int si_cut_rate(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_start, const int32_t* start, int C, int L,
@@ -1888,16 +1895,12 @@ int si_cut_rate_valid(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int 
 }
 
 // ---- both clip sets of a pass cut straight from the file
-// One rate's tables of a pair call: the checks cut_rate_call puts to its filter, under the argument's own name.
-static int pair_filter(si_ctx* ctx, const char* fn, const char* arg, const si_sinc_filter* f, int target, int sr, SiPairRate* r) {
-    if (!f || f->struct_size != (int32_t)sizeof(si_sinc_filter)) return SI_FAIL_FN("%s: si_sinc_filter size mismatch", arg);
-    if (!f->win || !f->dwin || f->nwin < 2 || f->num_table < 1 || f->step < 1 || !(f->scale > 0.0 && f->scale <= 1.0))
-        return SI_FAIL_FN("%s: bad filter table (nwin %d, num_table %d, step %d, scale %g)", arg, f->nwin, f->num_table, f->step, f->scale);
-    long ga = target, gb = sr;
-    while (gb) { const long t = ga % gb; ga = gb; gb = t; }
-    const long H = ((long)f->nwin + f->step - 1) / f->step;
-    if (H > 16384) return SI_FAIL_FN("%s: bad filter table: %ld taps per wing at %d Hz, no tile's staged samples fit 64 KB", arg, H, sr);
-    *r = SiPairRate{f->win, f->dwin, f->nwin, f->num_table, f->step, f->scale, (int)(target / ga), (int)(sr / ga), (int)H};
+// One rate's tables of a pair call: feed_taps, and the bound that lets cut_pair_call form the tile's staged samples.
+static int pair_filter(si_ctx* ctx, const char* fn, const char* arg, const si_sinc_filter* f, int target, int sr, SiTaps* r) {
+    long P, Q;
+    si_rate_ratio(target, sr, &P, &Q);
+    if (feed_taps(ctx, fn, arg, f, P, Q, r) != SI_OK) return SI_EINVAL;
+    if (r->H > 16384) return SI_FAIL_FN("%s: bad filter table: %ld taps per wing at %d Hz, no tile's staged samples fit 64 KB", arg, (long)r->H, sr);
     return SI_OK;
 }
 
@@ -1918,7 +1921,7 @@ static int cut_pair_call(si_ctx* ctx, const char* fn, bool inter, const void* x,
     if (N22 > SI_MAX_REC) return SI_FAIL_FN("n_file = %d samples at %d Hz are %ld samples at 22050 Hz, at most %ld", n_file, sr, N22, SI_MAX_REC);
     if (sr == 16000) {
         if (filt16) return SI_FAIL_FN("filt16 is not NULL at sr = 16000 Hz: the 16 kHz clips are the file's own samples, no filter is applied");
-        pr.r16 = SiPairRate{nullptr, nullptr, 0, 1, 1, 1.0, 1, 1, 0};
+        pr.r16 = SiTaps{nullptr, nullptr, 0, 1, 1, 1.0, 1, 1, 0};
         pr.direct16 = 1;
     } else {
         if (!filt16) return SI_FAIL_FN("filt16 is NULL at sr = %d Hz: only a 16000 Hz file goes without the 16 kHz filter", sr);
@@ -1948,11 +1951,8 @@ static int cut_pair_call(si_ctx* ctx, const char* fn, bool inter, const void* x,
     }
     SI_HIP_CHECK(hipSetDevice(ctx->device));
     pr.cap = (int)cap, pr.N22 = (int)N22, pr.N16 = (int)N16, pr.lim16 = (int)lim16;
-    if (ceiling)
-        return si_launch_cut_pair_valid(ctx, x, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, frame, C, L22, L16, pr,
-                                        *ceiling, out22, out16, static_cast<hipStream_t>(stream));
-    return si_launch_cut_pair(ctx, x, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, frame, C, L22, L16, pr, out22, out16,
-                              static_cast<hipStream_t>(stream));
+    return si_launch_cut_pair(ctx, x, si_sample_format(is_pcm16), n_file, inter ? channels : 0, inter ? channel : 0, frame, C, L22, L16, pr, ceiling, out22,
+                              out16, static_cast<hipStream_t>(stream));
 }
 
 int si_cut_pair(si_ctx* ctx, const void* x, int is_pcm16, int n_file, int sr, const int32_t* host_frame, const int32_t* frame, int C, int L22,

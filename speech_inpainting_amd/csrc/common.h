@@ -53,6 +53,12 @@ inline void si_with_sample(int fmt, F&& f) {
     else if (fmt == SI_SAMPLE_S16) f(static_cast<const int16_t*>(nullptr));
     else f(static_cast<const float*>(nullptr));
 }
+// f(std::true_type or std::false_type): the same for a kernel's compile-time switch, read as decltype(flag)::value.
+template <class F>
+inline void si_with_flag(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // invalid(v, c) for a ceiling c > 0 (+inf allowed): the ONE definition that si_invalid_runs and the three _valid feeds
 // share.  fp32: NaN of any payload and sign, +-inf and |v| > c; with c = +inf exactly "not finite"; -0.0 and subnormals are valid.
@@ -367,8 +373,9 @@ int si_launch_gather_windows(si_ctx* ctx, const float* ext, const int32_t* win, 
 // out / pcm (B, N22; either may be null) = orig outside the blend regions of `sp`, (1 - w) orig + w gain[b] gen inside; gain null = 1
 int si_launch_patch_compose(si_ctx* ctx, const float* orig, const SiSpans& sp, const SiPatch& pt, const float* gen, int Lrow, const float* gain,
                             int B, int N22, float* out, int16_t* pcm, hipStream_t st);
-// long recordings.  out (C, L) row c = src[start[c] : start[c] + L]; start device int32 (C), validated by the caller
-int si_launch_cut_clips(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float* out, hipStream_t st);
+// long recordings.  out (C, L) row c = src[start[c] : start[c] + L]; start device int32 (C), validated by the caller.
+// ceiling != nullptr: a sample that is si_invalid(., *ceiling) is copied as +0.0
+int si_launch_cut_clips(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, const float* ceiling, float* out, hipStream_t st);
 // the device half of si_region_table: per span, per window and per chunk arrays on the recording's own sample axis
 struct SiRegions {
     const int32_t* start; const int32_t* len; const int32_t* span_win; const int32_t* span_lim;
@@ -417,71 +424,104 @@ int si_launch_detect(si_ctx* ctx, const void* x, int fmt, int n, int channels, i
 int si_launch_impulse_residual(si_ctx* ctx, const void* x, int fmt, int n, int channels, int channel, int order, double* e, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
+// band-limited interpolation between two sample rates at the exact rational time: the one set of tables
+// and the one per-output sum of rate_kernels.hip and rate_feed_kernels.hip
+// ------------------------------------------------------------------------------------------------
+// The kaiser_best tables of source rate -> target rate: P / Q = (target, source) / gcd, so output j of the target axis sits at source
+// position j Q / P; H = ceil(nwin / step) taps per wing.
+struct SiTaps {
+    const double* win; const double* dwin; int nwin, num_table, step; double scale;
+    int P, Q, H;
+};
+// Output j from `row`, which holds the source samples from `base` on as fp32 (zero where the source has none).  n, r = divmod(j Q, P)
+// in int64; frac = scale (r / P); left wing off, eta = split(frac num_table), taps k < min(n + 1, (nwin - off) / step) on x[n - k];
+// right wing the same from scale - frac, taps k < min(cap - n - 1, (nwin - off') / step) on x[n + 1 + k] -- cap: the source's length,
+// or a value no n reaches where the row's zeros already end it; weights fma(eta, dwin, win), sum by fma in float64, left ascending
+// then right ascending, rounded once to fp32: resample_sinc_kernel's arithmetic at the exact time.  Nothing in it depends on where the
+// row starts.  The statements keep this order: a * b - c contracts across them, and the bits depend on it.
+template <typename Cap>
+__device__ __forceinline__ float si_wings(const float* __restrict__ row, long base, long j, Cap cap, const SiTaps& r) {
+    const long P = r.P, Q = r.Q;
+    const int nwin = r.nwin, step = r.step;
+    const double scale = r.scale, ntab = (double)r.num_table;
+    const long t = j * Q;
+    const long nl = t / P;
+    const int n = (int)nl;
+    const double frac = scale * ((double)(t - nl * P) / (double)P);
+    double acc = 0.0;
+    {
+        const double idx = frac * ntab;
+        const int off = (int)idx;
+        const double eta = idx - (double)off;
+        const int taps = min(n + 1, (nwin - off) / step);
+        const float* xs = row + (nl - base);
+        for (int k = 0; k < taps; ++k) {
+            const int i = off + k * step;
+            acc = fma(fma(eta, r.dwin[i], r.win[i]), (double)xs[-k], acc);
+        }
+    }
+    {
+        const double idx = (scale - frac) * ntab;
+        const int off = (int)idx;
+        const double eta = idx - (double)off;
+        const int taps = (int)min(cap - n - 1, (Cap)((nwin - off) / step));
+        const float* xs = row + (nl + 1 - base);
+        for (int k = 0; k < taps; ++k) {
+            const int i = off + k * step;
+            acc = fma(fma(eta, r.dwin[i], r.win[i]), (double)xs[k], acc);
+        }
+    }
+    return (float)acc;
+}
+
+// ------------------------------------------------------------------------------------------------
 // repair at the file's own sample rate (rate_kernels.hip)
 // ------------------------------------------------------------------------------------------------
-// si_rate_table's device arrays (spans, span_lim, chunks, fade and ramp in FILE samples; windows in 22.05 kHz samples), the kaiser_best
-// tables of 22 050 -> sr, P / Q = (22050, sr) / gcd, H = ceil(nwin / step) taps per wing, and row_cap = floor(2047 P / Q) + 2 + 2 H:
-// the 22.05 kHz samples one chunk's share of one span can read, the floats of dynamic LDS the launch asks for.
+// si_rate_table's device arrays (spans, span_lim, chunks, fade and ramp in FILE samples; windows in 22.05 kHz samples), the tables of
+// 22 050 -> sr, and row_cap = floor(2047 Q / P) + 2 + 2 H: the 22.05 kHz samples one chunk's share of one span can read, the floats of
+// dynamic LDS the launch asks for.
 struct SiRate {
     const int32_t* start; const int32_t* len; const int32_t* span_win; const int32_t* span_lim;
     const int32_t* win_ctx; const int32_t* win_start; const int32_t* win_len; const int32_t* win_lim;
     const int32_t* chunk; const int32_t* k0; const int32_t* k1;
     const float* ramp; int fade;
-    const double* win; const double* dwin; int nwin, num_table, step; double scale;
-    int P, Q, H, row_cap;
+    SiTaps r;           // 22 050 -> sr: P / Q = (sr, 22050) / gcd, file sample i sits at 22.05 kHz position i Q / P
+    int row_cap;
 };
 // one workgroup per listed chunk of 2048 file samples: the blended samples of its spans written into out (n_file, orig's type: fp32 or
-// int16 / packed 24-bit by fmt), the rest untouched; arguments validated by the caller
-int si_launch_patch_rate(si_ctx* ctx, const void* orig, int fmt, int n_file, const SiRate& rt, int num_chunks, const float* gen, int Lrow,
-                         const float* gain, void* out, hipStream_t st);
-// the same into channel `channel` of an interleaved orig / out (n_file sample times of ch channels)
-int si_launch_patch_rate_ch(si_ctx* ctx, const void* orig, int fmt, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
-                            const float* gen, int Lrow, const float* gain, void* out, hipStream_t st);
+// int16 / packed 24-bit by fmt), the rest untouched.  ch = 0: a mono file (the mono kernel, profiled as patch_rate); else channel
+// `channel` of ch interleaved (patch_rate_ch).  Arguments validated by the caller.
+int si_launch_patch_rate(si_ctx* ctx, const void* orig, int fmt, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
+                         const float* gen, int Lrow, const float* gain, void* out, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
-// context clips cut at the file's own rate (rate_feed_kernels.hip; DESIGN.md 4.17)
+// context clips cut at the file's own rate (rate_feed_kernels.hip; DESIGN.md 4.17, 4.26, 4.30, 4.36)
 // ------------------------------------------------------------------------------------------------
-constexpr int RF_TILE = SI_CUT_RATE_TILE;       // consecutive outputs of one clip per workgroup (si_hip.h; native.CUT_RATE_TILE)
-// the kaiser_best tables of sr -> 22 050, P / Q = (22050, sr) / gcd, H = ceil(nwin / step) taps per wing, cap = floor((RF_TILE - 1) Q / P)
-// + 2 + 2 H: the file samples one tile can read, the floats of dynamic LDS the launch asks for, and N22 = ceil(n_file P / Q)
+constexpr int RF_TILE = SI_CUT_RATE_TILE;               // consecutive outputs of one clip per workgroup of cut_rate (si_hip.h; native.CUT_RATE_TILE)
+constexpr int RF_PAIR_FRAMES = SI_CUT_PAIR_FRAMES;      // consecutive 20 ms frames of one clip per workgroup of cut_pair (si_hip.h; native.CUT_PAIR_FRAMES)
+// si_cut_rate: the tables of sr -> 22 050; cap = floor((RF_TILE - 1) Q / P) + 2 + 2 H: the file samples one tile can read, the floats of
+// dynamic LDS the launch asks for, and N22 = ceil(n_file P / Q)
 struct SiFeed {
-    const double* win; const double* dwin; int nwin, num_table, step; double scale;
-    int P, Q, H, cap, N22;
+    SiTaps r;
+    int cap, N22;
 };
-// out (C, L) row c = 22.05 kHz samples [start[c], start[c] + L) of the file x (n_file; fp32, int16 or packed 24-bit by fmt), interpolated at the
-// exact time j Q / P; start device int32 (C); arguments validated by the caller
-int si_launch_cut_rate(si_ctx* ctx, const void* x, int fmt, int n_file, const int32_t* start, int C, int L, const SiFeed& fd, float* out,
-                       hipStream_t st);
-// the same from channel `channel` of an interleaved x (n_file sample times of ch channels)
-int si_launch_cut_rate_ch(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* start, int C, int L,
-                          const SiFeed& fd, float* out, hipStream_t st);
-
-// both clip sets of a pass from one staged tile (rate_feed_kernels.hip)
-constexpr int RF_PAIR_FRAMES = SI_CUT_PAIR_FRAMES;      // consecutive 20 ms frames of one clip per workgroup (si_hip.h; native.CUT_PAIR_FRAMES)
-// one rate's kaiser_best tables, sr -> 22 050 or sr -> 16 000: P / Q = (target, sr) / gcd, H = ceil(nwin / step) taps per wing
-struct SiPairRate {
-    const double* win; const double* dwin; int nwin, num_table, step; double scale;
-    int P, Q, H;
-};
-// cap = ceil(RF_PAIR_FRAMES sr / 50) + 2 + 2 max(H22, H16): the floats of dynamic LDS; N22 = ceil(n_file P22 / Q22), N16 = ceil(n_file
-// P16 / Q16), lim16 = ceil(N22 320 / 441): where a clip's 16 kHz row may end; direct16: sr = 16000, r16 holds no tables (H = 0, P = Q = 1)
+// si_cut_pair: the tables of sr -> 22 050 and sr -> 16 000; cap = ceil(RF_PAIR_FRAMES sr / 50) + 2 + 2 max(H22, H16): the floats of
+// dynamic LDS; N22 = ceil(n_file P22 / Q22), N16 = ceil(n_file P16 / Q16), lim16 = ceil(N22 320 / 441): where a clip's 16 kHz row may
+// end; direct16: sr = 16000, r16 holds no tables (H = 0, P = Q = 1)
 struct SiPair {
-    SiPairRate r22, r16;
+    SiTaps r22, r16;
     int cap, N22, N16, lim16, direct16;
 };
-// out22 (C, L22) row c = 22.05 kHz samples 441 frame[c] + [0, L22), out16 (C, L16) row c = 16 kHz samples 320 frame[c] + [0, L16) of the
-// file x; ch = 0: a mono file (the mono kernel), else channel `channel` of ch interleaved; arguments validated by the caller
+// One launcher per kernel family.  The file x (n_file sample times; fp32, int16 or packed 24-bit by fmt): ch = 0 a mono file (the mono
+// kernel, profiled as cut_rate), else channel `channel` of ch interleaved (cut_rate_ch).  ceiling = nullptr: the file
+// as it is; else a file sample that is si_invalid(., *ceiling), judged in the file's own units before any conversion,
+// enters the interpolation (the copy) as +0.0 -- the same grid, LDS and profile family.  Arguments validated by the caller.
+// out (C, L) row c = 22.05 kHz samples [start[c], start[c] + L) of x, interpolated at the exact time j Q / P; start device int32 (C)
+int si_launch_cut_rate(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* start, int C, int L, const SiFeed& fd,
+                       const float* ceiling, float* out, hipStream_t st);
+// out22 (C, L22) row c = 22.05 kHz samples 441 frame[c] + [0, L22), out16 (C, L16) row c = 16 kHz samples 320 frame[c] + [0, L16) of x
 int si_launch_cut_pair(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* frame, int C, int L22, int L16,
-                       const SiPair& pr, float* out22, float* out16, hipStream_t st);
-
-// the feeds that stage an invalid file sample as +0.0: the launches above with one more sentence -- a file sample that
-// is si_invalid(., ceiling), judged in the file's own units before any conversion, enters the interpolation (the copy) as +0.0.  ch = 0:
-// a mono file (the mono kernel), else channel `channel` of ch interleaved; arguments validated by the caller
-int si_launch_cut_rate_valid(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* start, int C, int L,
-                             const SiFeed& fd, float ceiling, float* out, hipStream_t st);
-int si_launch_cut_pair_valid(si_ctx* ctx, const void* x, int fmt, int n_file, int ch, int channel, const int32_t* frame, int C, int L22,
-                             int L16, const SiPair& pr, float ceiling, float* out22, float* out16, hipStream_t st);
-int si_launch_cut_clips_valid(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float ceiling, float* out, hipStream_t st);
+                       const SiPair& pr, const float* ceiling, float* out22, float* out16, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // short runs mended in place by least-squares AR interpolation (mend_kernels.hip)

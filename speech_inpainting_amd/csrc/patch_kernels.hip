@@ -185,29 +185,19 @@ __device__ __forceinline__ void pc_cut_clips(const float* __restrict__ src, cons
     }
 }
 
-__global__ __launch_bounds__(256) void cut_clips_kernel(const float* __restrict__ src, const int32_t* __restrict__ start, int L, float* __restrict__ out) {
-    pc_cut_clips<false>(src, start, L, 0.f, out);
+template <bool CLEAN>
+__global__ __launch_bounds__(256) void cut_clips_kernel(const float* __restrict__ src, const int32_t* __restrict__ start, int L, float ceiling,
+                                                        float* __restrict__ out) {
+    pc_cut_clips<CLEAN>(src, start, L, ceiling, out);
 }
 
-__global__ __launch_bounds__(256) void cut_clips_valid_kernel(const float* __restrict__ src, const int32_t* __restrict__ start, int L, float ceiling,
-                                                              float* __restrict__ out) {
-    pc_cut_clips<true>(src, start, L, ceiling, out);
-}
-
-int si_launch_cut_clips(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float* out, hipStream_t st) {
+// ceiling = nullptr: the copy as it always was; else (si_cut_clips_valid, which checked it) the CLEAN one: the same grid and profile name.
+int si_launch_cut_clips(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, const float* ceiling, float* out, hipStream_t st) {
     if (C <= 0 || L <= 0) return SI_OK;
     si_prof_begin(ctx, "cut_clips", 0.0, 8.0 * C * L, st);
-    cut_clips_kernel<<<dim3((L + PC_CHUNK - 1) / PC_CHUNK, C), 256, 0, st>>>(src, start, L, out);
-    si_prof_end(ctx, st);
-    SI_HIP_CHECK(hipGetLastError());
-    return SI_OK;
-}
-
-// The caller (si_cut_clips_valid) checked every argument, the ceiling among them.  The same grid and the same profile name.
-int si_launch_cut_clips_valid(si_ctx* ctx, const float* src, const int32_t* start, int C, int L, float ceiling, float* out, hipStream_t st) {
-    if (C <= 0 || L <= 0) return SI_OK;
-    si_prof_begin(ctx, "cut_clips", 0.0, 8.0 * C * L, st);
-    cut_clips_valid_kernel<<<dim3((L + PC_CHUNK - 1) / PC_CHUNK, C), 256, 0, st>>>(src, start, L, ceiling, out);
+    si_with_flag(ceiling != nullptr, [&](auto clean) {
+        cut_clips_kernel<decltype(clean)::value><<<dim3((L + PC_CHUNK - 1) / PC_CHUNK, C), 256, 0, st>>>(src, start, L, ceiling ? *ceiling : 0.f, out);
+    });
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());
     return SI_OK;

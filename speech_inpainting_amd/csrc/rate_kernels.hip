@@ -1,8 +1,9 @@
 // rate_kernels.hip -- repair at the file's own sample rate, gfx950: the generated audio of the gaps carried from the
 // generator's 22.05 kHz axis to the FILE's rate and blended into the file's own samples, fp32, int16 or packed 24-bit as they lie in the file.
-//   patch_rate_kernel<float | int16_t | SiS24>   per touched chunk of 2048 file samples: band-limited interpolation of the window rows at the
-//                                        exact rational time i P / Q + patch_regions_kernel's blend, written into the caller's copy
-//   patch_rate_ch_kernel<float | int16_t> the same chunk written into one channel of an INTERLEAVED file: one shared body
+//   patch_rate_kernel<T, INTER>   per touched chunk of 2048 file samples: band-limited interpolation of the window rows at the exact
+//                                 rational time i Q / P (si_wings, common.h) + patch_regions_kernel's blend, written into the caller's copy
+// T = float | int16_t | SiS24: the file's sample type.  INTER: the chunk is written into one channel of an INTERLEAVED file (DESIGN.md
+// 4.18); the mono instantiation folds ch = 1, channel = 0 in.  One body, one __global__ template, one launcher.
 // It stands where `resample(patched, 22050, sr)` over the whole repaired recording would: that pass costs every sample of the file a
 // 2 x 65-tap float64 sum and returns none of the samples its owner recorded; this one computes the few hundred thousand samples the
 // cross-fades and gaps cover and leaves every other sample of `out` alone.
@@ -36,27 +37,26 @@ __device__ __forceinline__ void rk_store(SiS24* p, float v) {
 // grid (Q), 256 threads, rt.row_cap floats of dynamic LDS.  Workgroup q owns file samples [c0, c1) of chunk rt.chunk[q] and walks spans
 // [k0[q], k1[q]) -- q is workgroup-uniform, so the whole table arrives through scalar loads and the span loop is uniform.  Per span ks
 // that meets the chunk in [ia, ib):
-//   stage   the 22.05 kHz samples its interpolation reads, [floor(ia P / Q) - H, floor((ib - 1) P / Q) + H], from the span's window row
+//   stage   the 22.05 kHz samples its interpolation reads, [floor(ia Q / P) - H, floor((ib - 1) Q / P) + H], from the span's window row
 //           into LDS: lane t loads element t, t + 256, ... (coalesced whatever the row's alignment -- rows start at arbitrary samples);
 //           samples before recording sample 0 and at / past the window's win_lim become zeros here, as the resampler treats a clip's ends.
-//           ib - ia <= 2048, so the range holds at most floor(2047 P / Q) + 2 + 2 H = row_cap samples.
+//           ib - ia <= 2048, so the range holds at most floor(2047 Q / P) + 2 + 2 H = row_cap samples (P / Q = (sr, 22050) / gcd).
 //   weight  per sample m of [ia, ib): patch_regions_kernel's walk over ALL the chunk's spans -- the maximum of rise / 1 / mirrored fall,
 //           0 at and past each span's span_lim.  The sample is computed here only when ks is the FIRST span of that greatest weight
 //           (strict >, as patch_regions_kernel picks its window), so every written sample is written once, by one span's pass.
-//   sample  n, r = divmod(m P, Q) in int64; frac = scale (r / Q); left wing off, eta = split(frac num_table), taps k < min(n + 1,
-//           (nwin - off) / step) on x[n - k]; right wing the same from scale - frac on x[n + 1 + k]; weights fma(eta, dwin, win), sum by
-//           fma in float64, left ascending then right ascending, rounded once to fp32: resample_sinc_kernel's arithmetic with the exact
-//           time in place of the accumulated one.  Neighbouring lanes read neighbouring LDS words (stride P / Q); the tables stay in L2
-//           as they do for resample_sinc_kernel.  Nothing in it depends on where the row or the chunk starts: same bits either way.
+//   sample  si_wings of the staged row at file sample m: resample_sinc_kernel's arithmetic with the exact time in place of the
+//           accumulated one.  The right wing's cap never binds (LONG_MAX): the row's zeros at and past win_lim end it.  Neighbouring
+//           lanes read neighbouring LDS words (stride Q / P); the tables stay in L2 as they do for resample_sinc_kernel.  Nothing in it
+//           depends on where the row or the chunk starts: same bits either way.
 //   blend   g = gain * y; w == 1: g; else fma(w, g, (1 - w) * orig) -- patch_regions_kernel's roundings in its order; int16 files
 //           read (float)v / 32768 and store through pc_pcm16's arithmetic.
 // Every global access is one element wide, so orig / out / gen need only their element's alignment: callers pass views.  Plain stores, no
 // atomics.  The C ABI validated on the host copy that every staged sample inside [0, win_lim) lies in its window's row; the staging
 // loop still clamps to the row, so a device table that differs from the validated one gives wrong output, not a fault.
 //
-// patch_rate_ch_kernel is the same workgroup for channel `channel` of an INTERLEAVED file (n_file sample times of ch
-// channels): spans, chunks, fades and m are sample times of that channel, orig / out element m ch + channel (a 64-bit offset), and no
-// other element of out is touched.  One body, rk_patch_chunk, serves both, the mono kernel with ch = 1, channel = 0 folded in.  The table
+// INTER is the same workgroup for channel `channel` of an INTERLEAVED file (n_file sample times of ch channels):
+// spans, chunks, fades and m are sample times of that channel, orig / out element m ch + channel (a 64-bit offset), and no other
+// element of out is touched.  The table
 // may name windows (rows of gen) and contexts (entries of gain) that none of its spans use: another channel's share of the pass.
 template <typename T>
 __device__ __forceinline__ void rk_patch_chunk(const T* __restrict__ orig, const SiRate& rt, const float* __restrict__ gen, int Lrow,
@@ -65,17 +65,16 @@ __device__ __forceinline__ void rk_patch_chunk(const T* __restrict__ orig, const
     const int q = blockIdx.x;
     const int c0 = rt.chunk[q] * RK_CHUNK, c1 = min(c0 + RK_CHUNK, n_file);
     const int k0 = rt.k0[q], k1 = rt.k1[q], fade = rt.fade;
-    const long P = rt.P, Q = rt.Q;
-    const int H = rt.H, nwin = rt.nwin, step = rt.step;
-    const double scale = rt.scale, ntab = (double)rt.num_table;
-    for (int ks = k0; ks < k1; ++ks) {                                // uniform
+    const long P = rt.r.P, Q = rt.r.Q;                                 // file sample i sits at 22.05 kHz position i Q / P
+    const int H = rt.r.H;
+    for (int ks = k0; ks < k1; ++ks) {                              // uniform
         const int s = rt.start[ks], l = rt.len[ks];
         const int ia = max(max(s - fade, 0), c0), ib = min(min(s + l + fade, rt.span_lim[ks]), c1);
         if (ia >= ib) continue;
         const int win = rt.span_win[ks];
         const int ws = rt.win_start[win], wl = rt.win_len[win], wlim = rt.win_lim[win];
-        const int base = (int)((long)ia * P / Q) - H;
-        const int cnt = min((int)((long)(ib - 1) * P / Q) + H + 1 - base, rt.row_cap);
+        const int base = (int)((long)ia * Q / P) - H;
+        const int cnt = min((int)((long)(ib - 1) * Q / P) + H + 1 - base, rt.row_cap);
         const float* __restrict__ grow = gen + (size_t)win * Lrow;
         __syncthreads();                                              // the previous span's readers are done with the row
         for (int p = threadIdx.x; p < cnt; p += 256) {
@@ -97,77 +96,34 @@ __device__ __forceinline__ void rk_patch_chunk(const T* __restrict__ orig, const
                 if (wk > w) { w = wk; kw = k; }
             }
             if (kw != ks) continue;                                   // weight 0, or another span's pass writes it
-            const long t = (long)m * P;
-            const int n = (int)(t / Q);
-            const double frac = scale * ((double)(t - (long)n * Q) / (double)Q);
-            double acc = 0.0;
-            {
-                const double idx = frac * ntab;
-                const int off = (int)idx;
-                const double eta = idx - (double)off;
-                const int taps = min(n + 1, (nwin - off) / step);
-                const float* x = rk_row + (n - base);
-                for (int k = 0; k < taps; ++k) {
-                    const int i = off + k * step;
-                    acc = fma(fma(eta, rt.dwin[i], rt.win[i]), (double)x[-k], acc);
-                }
-            }
-            {
-                const double idx = (scale - frac) * ntab;
-                const int off = (int)idx;
-                const double eta = idx - (double)off;
-                const int taps = (nwin - off) / step;
-                const float* x = rk_row + (n + 1 - base);
-                for (int k = 0; k < taps; ++k) {
-                    const int i = off + k * step;
-                    acc = fma(fma(eta, rt.dwin[i], rt.win[i]), (double)x[k], acc);
-                }
-            }
-            const float g = __fmul_rn(g0, (float)acc);
+            const float g = __fmul_rn(g0, si_wings(rk_row, (long)base, (long)m, LONG_MAX, rt.r));
             const size_t e = (size_t)m * ch + channel;
             rk_store(out + e, w == 1.f ? g : __fmaf_rn(w, g, __fmul_rn(1.f - w, rk_load(orig + e))));
         }
     }
 }
 
-template <typename T>
+template <typename T, bool INTER>
 __global__ __launch_bounds__(256) void patch_rate_kernel(const T* __restrict__ orig, SiRate rt, const float* __restrict__ gen, int Lrow,
-                                                         const float* __restrict__ gain, int n_file, T* __restrict__ out) {
-    rk_patch_chunk(orig, rt, gen, Lrow, gain, n_file, 1, 0, out);
+                                                         const float* __restrict__ gain, int n_file, int ch, int channel, T* __restrict__ out) {
+    rk_patch_chunk(orig, rt, gen, Lrow, gain, n_file, INTER ? ch : 1, INTER ? channel : 0, out);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void patch_rate_ch_kernel(const T* __restrict__ orig, SiRate rt, const float* __restrict__ gen, int Lrow,
-                                                            const float* __restrict__ gain, int n_file, int ch, int channel, T* __restrict__ out) {
-    rk_patch_chunk(orig, rt, gen, Lrow, gain, n_file, ch, channel, out);
-}
-
-// The caller (si_patch_rate) checked every argument, row_cap * 4 <= 64 KB among them.
-int si_launch_patch_rate(si_ctx* ctx, const void* orig, int fmt, int n_file, const SiRate& rt, int num_chunks, const float* gen, int Lrow,
-                         const float* gain, void* out, hipStream_t st) {
+// ch = 0: the mono kernel under "patch_rate"; else the interleaved one under "patch_rate_ch".  The caller (si_patch_rate[_ch]) checked
+// every argument, row_cap * 4 <= 64 KB, 1 <= ch <= SI_MAX_CHANNELS and 0 <= channel < ch among them.
+int si_launch_patch_rate(si_ctx* ctx, const void* orig, int fmt, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
+                         const float* gen, int Lrow, const float* gain, void* out, hipStream_t st) {
     if (num_chunks <= 0) return SI_OK;
     const size_t lds = (size_t)rt.row_cap * sizeof(float);
     const double esz = si_sample_bytes(fmt);
-    si_prof_begin(ctx, "patch_rate", (double)num_chunks * RK_CHUNK * 8.0 * rt.H, (double)num_chunks * (RK_CHUNK * 2.0 * esz + 4.0 * rt.row_cap), st);
+    si_prof_begin(ctx, ch > 0 ? "patch_rate_ch" : "patch_rate", (double)num_chunks * RK_CHUNK * 8.0 * rt.r.H,
+                  (double)num_chunks * (RK_CHUNK * 2.0 * esz + 4.0 * rt.row_cap), st);
     si_with_sample(fmt, [&](auto tag) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
-        patch_rate_kernel<T><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const T*>(orig), rt, gen, Lrow, gain, n_file, static_cast<T*>(out));
-    });
-    si_prof_end(ctx, st);
-    SI_HIP_CHECK(hipGetLastError());
-    return SI_OK;
-}
-
-// The caller (si_patch_rate_ch) checked every argument, 1 <= ch <= SI_MAX_CHANNELS and 0 <= channel < ch among them.
-int si_launch_patch_rate_ch(si_ctx* ctx, const void* orig, int fmt, int n_file, int ch, int channel, const SiRate& rt, int num_chunks,
-                            const float* gen, int Lrow, const float* gain, void* out, hipStream_t st) {
-    if (num_chunks <= 0) return SI_OK;
-    const size_t lds = (size_t)rt.row_cap * sizeof(float);
-    const double esz = si_sample_bytes(fmt);
-    si_prof_begin(ctx, "patch_rate_ch", (double)num_chunks * RK_CHUNK * 8.0 * rt.H, (double)num_chunks * (RK_CHUNK * 2.0 * esz + 4.0 * rt.row_cap), st);
-    si_with_sample(fmt, [&](auto tag) {
-        using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
-        patch_rate_ch_kernel<T><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const T*>(orig), rt, gen, Lrow, gain, n_file, ch, channel, static_cast<T*>(out));
+        si_with_flag(ch > 0, [&](auto inter) {
+            patch_rate_kernel<T, decltype(inter)::value><<<dim3(num_chunks), 256, lds, st>>>(static_cast<const T*>(orig), rt, gen, Lrow, gain, n_file, ch,
+                                                                                             channel, static_cast<T*>(out));
+        });
     });
     si_prof_end(ctx, st);
     SI_HIP_CHECK(hipGetLastError());

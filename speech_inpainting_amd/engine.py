@@ -625,13 +625,9 @@ class InpaintingEngine:
                 gain = self.ctx.wave_peak(w22, tb["tab22"]) / 0.95
                 self.ctx.patch_regions(wave22, self._region_table(cb, plan, own22), gen, gain, patched, out.get("patched_pcm"))
 
-        if ceiling is None:
-            cut = lambda cb, L: self.ctx.cut_clips(wave22, [441 * c["start"] for c in cb], L)
-            out.update(self._recording_passes(wave22.numel(), cut, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write))
-        else:
-            cut = lambda cb, L: self.ctx.cut_clips_valid(wave22, [441 * c["start"] for c in cb], L, ceiling)
-            out.update(self._recording_passes(wave22.numel(), cut, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write,
-                                              ceiling=ceiling))
+        cut = lambda cb, L: self.ctx.cut_clips(wave22, [441 * c["start"] for c in cb], L, ceiling=ceiling)
+        out.update(self._recording_passes(wave22.numel(), cut, wave16, gaps, max(-(-fade // 441), 1), clip_frames, min_context, batch, write,
+                                          ceiling=ceiling))
         return out
 
     @staticmethod
@@ -685,10 +681,8 @@ class InpaintingEngine:
                 w22 = cut(cb, L22)
                 if wave16 is None:
                     w16 = self.resample(w22, 22050, 16000)
-                elif ceiling is None:
-                    w16 = self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16)
                 else:
-                    w16 = self.ctx.cut_clips_valid(wave16, [320 * c["start"] for c in cb], L16, ceiling)
+                    w16 = self.ctx.cut_clips(wave16, [320 * c["start"] for c in cb], L16, ceiling=ceiling)
             tb = self.gap_tables([c["own"] + c["foreign"] for c in cb], [L16] * B, [L22] * B)
             res = self.predict_multigap_batch(w16, w22, None, tables=tb, vocode=False)
             write(cb, tb, res, w22, L22)
@@ -881,10 +875,7 @@ class InpaintingEngine:
         if feed == "contexts":                                         # the clips alone, cut from x itself
             fin = self._feed_filter(sr)
             N22 = -(-n_file * P // Q)
-            if ceiling is None:
-                cut = lambda cb, L: self.ctx.cut_rate(x, sr, [441 * c["start"] for c in cb], L, fin)
-            else:
-                cut = lambda cb, L: self.ctx.cut_rate_valid(x, sr, [441 * c["start"] for c in cb], L, fin, ceiling)
+            cut = lambda cb, L: self.ctx.cut_rate(x, sr, [441 * c["start"] for c in cb], L, fin, ceiling=ceiling)
         else:
             xf = x.to(torch.float32) / 32768.0 if pcm else x           # exact: 16 bits x 2^-15
             wave22 = self.resample(xf[None], sr, 22050)[0].contiguous()
@@ -895,10 +886,7 @@ class InpaintingEngine:
             fin16 = self._feed_filter16(sr)
 
             def cut16(cb, L22, L16):
-                if ceiling is None:
-                    w22, last16["w16"] = self.ctx.cut_pair(x, sr, [c["start"] for c in cb], L22, L16, fin, fin16)
-                else:
-                    w22, last16["w16"] = self.ctx.cut_pair_valid(x, sr, [c["start"] for c in cb], L22, L16, fin, fin16, ceiling)
+                w22, last16["w16"] = self.ctx.cut_pair(x, sr, [c["start"] for c in cb], L22, L16, fin, fin16, ceiling=ceiling)
                 return w22, last16["w16"]
         filt = self._rate_filter(sr)
 
@@ -959,10 +947,7 @@ class InpaintingEngine:
         if feed == "contexts":                                         # the clips alone, cut from x itself, channel c in place
             fin = self._feed_filter(sr)
             N22 = -(-n_file * P // Q)
-            if ceiling is None:
-                cut_rows = lambda c, starts, L, rows: self.ctx.cut_rate(x, sr, starts, L, fin, out=rows, channel=c)
-            else:
-                cut_rows = lambda c, starts, L, rows: self.ctx.cut_rate_valid(x, sr, starts, L, fin, ceiling, out=rows, channel=c)
+            cut_rows = lambda c, starts, L, rows: self.ctx.cut_rate(x, sr, starts, L, fin, out=rows, channel=c, ceiling=ceiling)
         else:                                                          # the whole-file resample per channel: it de-interleaves
             wave22 = {}
             for c in range(ch):
@@ -980,11 +965,8 @@ class InpaintingEngine:
                 w22 = torch.empty(len(cb), L22, dtype=torch.float32, device=self.device)
                 last16["w16"] = w16 = torch.empty(len(cb), L16, dtype=torch.float32, device=self.device)
                 for c, r0, r1 in G.pass_channels(cb):
-                    if ceiling is None:
-                        self.ctx.cut_pair(x, sr, [k["start"] for k in cb[r0:r1]], L22, L16, fin, fin16, out22=w22[r0:r1], out16=w16[r0:r1], channel=c)
-                    else:
-                        self.ctx.cut_pair_valid(x, sr, [k["start"] for k in cb[r0:r1]], L22, L16, fin, fin16, ceiling, out22=w22[r0:r1],
-                                                out16=w16[r0:r1], channel=c)
+                    self.ctx.cut_pair(x, sr, [k["start"] for k in cb[r0:r1]], L22, L16, fin, fin16, out22=w22[r0:r1], out16=w16[r0:r1], channel=c,
+                                      ceiling=ceiling)
                 return w22, w16
         filt = self._rate_filter(sr)
 

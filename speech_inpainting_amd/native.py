@@ -469,6 +469,16 @@ def _i64(t: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
     return _dev(t, torch.int64, None, n)
 
 
+def _sinc_filter(filt: dict):
+    """audio.design_kaiser_best's scalars with win / dwin as float64 device tensors -> the si_sinc_filter of the calls that interpolate at
+    exact times (si_patch_rate, si_cut_rate, si_cut_pair: time_reg is not read), by reference."""
+    win, dwin = filt["win"], filt["dwin"]
+    assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
+    assert win.numel() == dwin.numel()
+    return C.byref(SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
+                              float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None))
+
+
 class NativeContext:
     """One si_ctx: a model pair bound to one GPU."""
 
@@ -699,18 +709,30 @@ class NativeContext:
         return out, out_pcm
 
     # ---- long recordings
-    def cut_clips(self, src: torch.Tensor, starts, L: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """src (n,) fp32 + starts (host ints) -> (C, L): row c = src[starts[c] : starts[c] + L] (si_cut_clips).  A start table that
-        leaves the source is refused before the launch."""
-        assert src.is_cuda and src.dtype == torch.float32 and src.dim() == 1 and src.is_contiguous()
+    def _start_table(self, starts, empty: bool = False):
+        """starts (host ints) -> (host int32, device int32): what a feed validates and what its kernel reads; a value outside int32 is
+        clipped to its ends, which every feed refuses.  No device copy of an empty table unless `empty`."""
         host = np.ascontiguousarray(np.asarray(list(starts), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
-        Cn, L = host.size, int(L)
-        dev = torch.from_numpy(host).to(self.device, non_blocking=True)
+        return host, torch.from_numpy(host).to(self.device, non_blocking=True) if host.size or empty else None
+
+    def _clip_rows(self, out: Optional[torch.Tensor], Cn: int, L: int) -> torch.Tensor:
+        """out, or a new tensor: (Cn, max(L, 0)) fp32 on the device."""
         if out is None:
-            out = torch.empty(Cn, L, dtype=torch.float32, device=self.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * L
-        self._check(self.lib.si_cut_clips(self._h, _ptr(src), min(src.numel(), 2 ** 31 - 1), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L, _ptr(out), self._stream()),
-                    "si_cut_clips")
+            out = torch.empty(Cn, max(L, 0), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * max(L, 0)
+        return out
+
+    def cut_clips(self, src: torch.Tensor, starts, L: int, out: Optional[torch.Tensor] = None, ceiling: Optional[float] = None) -> torch.Tensor:
+        """src (n,) fp32 + starts (host ints) -> (C, L): row c = src[starts[c] : starts[c] + L] (si_cut_clips).  A start table that
+        leaves the source is refused before the launch.  ceiling: a sample that is invalid(., ceiling) is copied as +0.0
+        (si_cut_clips_valid)."""
+        assert src.is_cuda and src.dtype == torch.float32 and src.dim() == 1 and src.is_contiguous()
+        host, dev = self._start_table(starts, empty=True)
+        Cn, L = host.size, int(L)
+        out = self._clip_rows(out, Cn, L)
+        entry = "si_cut_clips" if ceiling is None else "si_cut_clips_valid"
+        self._check(getattr(self.lib, entry)(self._h, _ptr(src), min(src.numel(), 2 ** 31 - 1), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L,
+                                             *(() if ceiling is None else (float(ceiling),)), _ptr(out), self._stream()), entry)
         return out
 
     def patch_regions(self, orig: torch.Tensor, table: "RegionTable", gen: Optional[torch.Tensor], gain: Optional[torch.Tensor] = None,
@@ -758,83 +780,58 @@ class NativeContext:
         assert out.is_cuda and out.dtype == orig.dtype and out.shape == orig.shape and out.is_contiguous()
         assert gen is None or (gen.is_cuda and gen.dtype == torch.float32 and gen.dim() == 2 and gen.is_contiguous() and gen.shape[0] == table.W)
         assert gain is None or (gain.is_cuda and gain.dtype == torch.float32 and gain.numel() == table.C and gain.is_contiguous())
-        win, dwin = filt["win"], filt["dwin"]
-        assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
-        assert win.numel() == dwin.numel()
-        f = SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
-                       float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
         t = table.struct()
-        if channel is not None:
-            self._check(self.lib.si_patch_rate_ch(self._h, _ptr(orig), self._sample_format(orig), n_file, ch, int(channel), int(sr), C.byref(t), _ptr(gen),
-                                                  0 if gen is None else gen.shape[1], _ptr(gain), C.byref(f), _ptr(out), self._stream()), "si_patch_rate_ch")
-            return
-        self._check(self.lib.si_patch_rate(self._h, _ptr(orig), self._sample_format(orig), n_file, int(sr), C.byref(t), _ptr(gen),
-                                           0 if gen is None else gen.shape[1], _ptr(gain), C.byref(f), _ptr(out), self._stream()), "si_patch_rate")
+        entry, file = self._file_entry("si_patch_rate", orig, n_file, ch, channel)
+        self._check(getattr(self.lib, entry)(*file, int(sr), C.byref(t), _ptr(gen), 0 if gen is None else gen.shape[1], _ptr(gain), _sinc_filter(filt),
+                                             _ptr(out), self._stream()), entry)
+
+    def _file_entry(self, name: str, x: torch.Tensor, n_file: int, ch: int, channel: Optional[int], ceiling: Optional[float] = None):
+        """(the C entry point, its leading arguments) of a file-typed call on x as _interleaved read it: `name` for a file without
+        `channel`, `name`_ch with one; under a ceiling the one entry `name`_valid, which takes the file without `channel` as channels = 1,
+        channel = 0."""
+        file = (self._h, _ptr(x), self._sample_format(x), n_file)
+        if ceiling is not None:
+            return name + "_valid", file + ((ch, int(channel)) if channel is not None else (1, 0))
+        return (name + "_ch", file + (ch, int(channel))) if channel is not None else (name, file)
 
     # ---- context clips cut at the file's own sample rate (DESIGN.md 4.17)
     def cut_rate(self, x: torch.Tensor, sr: int, starts, L: int, filt: dict, out: Optional[torch.Tensor] = None,
-                 channel: Optional[int] = None) -> torch.Tensor:
+                 channel: Optional[int] = None, ceiling: Optional[float] = None) -> torch.Tensor:
         """x (n_file,) at `sr` Hz, fp32 or int16, a device view that may start anywhere + starts (host ints, 22.05 kHz samples) ->
         (C, L) fp32: row c = samples [starts[c], starts[c] + L) of the recording's 22.05 kHz axis, interpolated at the exact time
         j * sr / 22050 straight from the file's samples (si_cut_rate).  filt: audio.design_kaiser_best(sr, 22050, .) with win / dwin as
         float64 device tensors.  A start table that leaves the recording's ceil(n_file * 22050 / sr) samples is refused before the
-        launch.  channel = c: x is (n_file, ch) interleaved and the clips are cut from its channel c (si_cut_rate_ch)."""
+        launch.  channel = c: x is (n_file, ch) interleaved and the clips are cut from its channel c (si_cut_rate_ch).  ceiling: see
+        cut_rate_valid (si_cut_rate_valid)."""
         n_file, ch = self._interleaved(x, channel)
-        host = np.ascontiguousarray(np.asarray(list(starts), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        host, dev = self._start_table(starts)
         Cn, L = host.size, int(L)
-        dev = torch.from_numpy(host).to(self.device, non_blocking=True) if Cn else None
-        if out is None:
-            out = torch.empty(Cn, max(L, 0), dtype=torch.float32, device=self.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * max(L, 0)
-        win, dwin = filt["win"], filt["dwin"]
-        assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
-        assert win.numel() == dwin.numel()
-        f = SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
-                       float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
-        if channel is not None:
-            self._check(self.lib.si_cut_rate_ch(self._h, _ptr(x), self._sample_format(x), n_file, ch, int(channel), int(sr), host.ctypes.data_as(C.c_void_p),
-                                                _ptr(dev), Cn, L, C.byref(f), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate_ch")
-            return out
-        self._check(self.lib.si_cut_rate(self._h, _ptr(x), self._sample_format(x), n_file, int(sr), host.ctypes.data_as(C.c_void_p),
-                                         _ptr(dev), Cn, L, C.byref(f), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate")
+        out = self._clip_rows(out, Cn, L)
+        entry, file = self._file_entry("si_cut_rate", x, n_file, ch, channel, ceiling)
+        self._check(getattr(self.lib, entry)(*file, int(sr), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L, _sinc_filter(filt),
+                                             *(() if ceiling is None else (float(ceiling),)), C.c_void_p(out.data_ptr()), self._stream()), entry)
         return out
 
     # ---- both clip sets of a pass cut straight from the file, in one launch (DESIGN.md 4.26)
     def cut_pair(self, x: torch.Tensor, sr: int, frames, L22: int, L16: int, filt22: dict, filt16: Optional[dict],
-                 out22: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None, channel: Optional[int] = None):
+                 out22: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None, channel: Optional[int] = None,
+                 ceiling: Optional[float] = None):
         """x (n_file,) at `sr` Hz, fp32 or int16, a device view that may start anywhere + frames (host ints, 20 ms frames) ->
         (out22 (C, L22), out16 (C, L16)) fp32: row c = 22.05 kHz samples 441 frames[c] + [0, L22) -- si_cut_rate's bytes -- and 16 kHz
         samples 320 frames[c] + [0, L16), interpolated at the exact time j * sr / 16000 straight from the file's samples, zero at and past
         the recording's ceil(n_file * 16000 / sr) samples (si_cut_pair: one launch for both).  filt22 / filt16:
         audio.design_kaiser_best(sr, 22050 / 16000, .) with win / dwin as float64 device tensors; at sr = 16000 filt16 is None and the
-        16 kHz rows are the file's own samples.  channel = c: x is (n_file, ch) interleaved (si_cut_pair_ch)."""
+        16 kHz rows are the file's own samples.  channel = c: x is (n_file, ch) interleaved (si_cut_pair_ch).  ceiling: see
+        cut_pair_valid (si_cut_pair_valid)."""
         n_file, ch = self._interleaved(x, channel)
-        host = np.ascontiguousarray(np.asarray(list(frames), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        host, dev = self._start_table(frames)
         Cn, L22, L16 = host.size, int(L22), int(L16)
-        dev = torch.from_numpy(host).to(self.device, non_blocking=True) if Cn else None
-        outs = []
-        for out, L in ((out22, L22), (out16, L16)):
-            if out is None:
-                out = torch.empty(Cn, max(L, 0), dtype=torch.float32, device=self.device)
-            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * max(L, 0)
-            outs.append(out)
-        fs = []
-        for filt in (filt22, filt16):
-            if filt is None:
-                fs.append(None)
-                continue
-            win, dwin = filt["win"], filt["dwin"]
-            assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
-            assert win.numel() == dwin.numel()
-            fs.append(C.byref(SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
-                                         float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)))
-        tail = (host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L22, L16, fs[0], fs[1], C.c_void_p(outs[0].data_ptr()), C.c_void_p(outs[1].data_ptr()),
-                self._stream())
-        if channel is not None:
-            self._check(self.lib.si_cut_pair_ch(self._h, _ptr(x), self._sample_format(x), n_file, ch, int(channel), int(sr), *tail), "si_cut_pair_ch")
-        else:
-            self._check(self.lib.si_cut_pair(self._h, _ptr(x), self._sample_format(x), n_file, int(sr), *tail), "si_cut_pair")
-        return outs[0], outs[1]
+        out22, out16 = self._clip_rows(out22, Cn, L22), self._clip_rows(out16, Cn, L16)
+        entry, file = self._file_entry("si_cut_pair", x, n_file, ch, channel, ceiling)
+        self._check(getattr(self.lib, entry)(*file, int(sr), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L22, L16, _sinc_filter(filt22),
+                                             None if filt16 is None else _sinc_filter(filt16), *(() if ceiling is None else (float(ceiling),)),
+                                             C.c_void_p(out22.data_ptr()), C.c_void_p(out16.data_ptr()), self._stream()), entry)
+        return out22, out16
 
     # ---- dropout detection (DESIGN.md 4.15); one call shape for every detector (4.34)
     def _runs_call(self, name: str, x: torch.Tensor, args, min_len, max_runs, runs, n_runs, channel, threshold_out=None, takes_channels: bool = True,
@@ -957,65 +954,17 @@ class NativeContext:
         """cut_rate with a file sample that is invalid(., ceiling) -- NaN, +-inf, |x| > ceiling in the file's own units -- staged as +0.0
         (si_cut_rate_valid): byte for byte cut_rate on the file with those samples replaced by +0.0, without that copy.  channel = c:
         x is (n_file, ch) interleaved; None: the mono file (channels = 1 of the one C entry)."""
-        n_file, ch = self._interleaved(x, channel)
-        host = np.ascontiguousarray(np.asarray(list(starts), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
-        Cn, L = host.size, int(L)
-        dev = torch.from_numpy(host).to(self.device, non_blocking=True) if Cn else None
-        if out is None:
-            out = torch.empty(Cn, max(L, 0), dtype=torch.float32, device=self.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * max(L, 0)
-        win, dwin = filt["win"], filt["dwin"]
-        assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
-        assert win.numel() == dwin.numel()
-        f = SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
-                       float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)
-        self._check(self.lib.si_cut_rate_valid(self._h, _ptr(x), self._sample_format(x), n_file, ch if channel is not None else 1,
-                                               int(channel) if channel is not None else 0, int(sr), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L,
-                                               C.byref(f), float(ceiling), C.c_void_p(out.data_ptr()), self._stream()), "si_cut_rate_valid")
-        return out
+        return self.cut_rate(x, sr, starts, L, filt, out=out, channel=channel, ceiling=float(ceiling))
 
     def cut_pair_valid(self, x: torch.Tensor, sr: int, frames, L22: int, L16: int, filt22: dict, filt16: Optional[dict], ceiling: float,
                        out22: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None, channel: Optional[int] = None):
         """cut_pair with a file sample that is invalid(., ceiling) staged as +0.0 (si_cut_pair_valid): both outputs are cut_pair's on the
         file with those samples replaced by +0.0, the unfiltered 16 kHz row of a 16 kHz file included.  channel as cut_rate_valid's."""
-        n_file, ch = self._interleaved(x, channel)
-        host = np.ascontiguousarray(np.asarray(list(frames), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
-        Cn, L22, L16 = host.size, int(L22), int(L16)
-        dev = torch.from_numpy(host).to(self.device, non_blocking=True) if Cn else None
-        outs = []
-        for out, L in ((out22, L22), (out16, L16)):
-            if out is None:
-                out = torch.empty(Cn, max(L, 0), dtype=torch.float32, device=self.device)
-            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * max(L, 0)
-            outs.append(out)
-        fs = []
-        for filt in (filt22, filt16):
-            if filt is None:
-                fs.append(None)
-                continue
-            win, dwin = filt["win"], filt["dwin"]
-            assert win.is_cuda and dwin.is_cuda and win.dtype == dwin.dtype == torch.float64 and win.is_contiguous() and dwin.is_contiguous()
-            assert win.numel() == dwin.numel()
-            fs.append(C.byref(SincFilter(C.sizeof(SincFilter), win.numel(), int(filt["num_table"]), int(filt["step"]), 0, 0, float(filt["scale"]),
-                                         float(filt.get("ratio", 0.0)), win.data_ptr(), dwin.data_ptr(), None)))
-        self._check(self.lib.si_cut_pair_valid(self._h, _ptr(x), self._sample_format(x), n_file, ch if channel is not None else 1,
-                                               int(channel) if channel is not None else 0, int(sr), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L22,
-                                               L16, fs[0], fs[1], float(ceiling), C.c_void_p(outs[0].data_ptr()), C.c_void_p(outs[1].data_ptr()),
-                                               self._stream()), "si_cut_pair_valid")
-        return outs[0], outs[1]
+        return self.cut_pair(x, sr, frames, L22, L16, filt22, filt16, out22=out22, out16=out16, channel=channel, ceiling=float(ceiling))
 
     def cut_clips_valid(self, src: torch.Tensor, starts, L: int, ceiling: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """cut_clips with a sample that is invalid(., ceiling) copied as +0.0 (si_cut_clips_valid); every other sample keeps its bits."""
-        assert src.is_cuda and src.dtype == torch.float32 and src.dim() == 1 and src.is_contiguous()
-        host = np.ascontiguousarray(np.asarray(list(starts), dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
-        Cn, L = host.size, int(L)
-        dev = torch.from_numpy(host).to(self.device, non_blocking=True)
-        if out is None:
-            out = torch.empty(Cn, L, dtype=torch.float32, device=self.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Cn * L
-        self._check(self.lib.si_cut_clips_valid(self._h, _ptr(src), min(src.numel(), 2 ** 31 - 1), host.ctypes.data_as(C.c_void_p), _ptr(dev), Cn, L,
-                                                float(ceiling), _ptr(out), self._stream()), "si_cut_clips_valid")
-        return out
+        return self.cut_clips(src, starts, L, out=out, ceiling=float(ceiling))
 
     @staticmethod
     def _feats_mel(feats: torch.Tensor, mel: torch.Tensor):

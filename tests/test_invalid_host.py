@@ -64,7 +64,8 @@ def test_the_entry_points_are_declared_and_bound():
     assert common.count("bool si_invalid(") == 3 and "__builtin_fminf(c, __FLT_MAX__)" in common
     src = {f: open(os.path.join(ROOT, "speech_inpainting_amd", "csrc", f)).read() for f in ("detect_kernels.hip", "rate_feed_kernels.hip", "patch_kernels.hip")}
     assert all("si_invalid(" in s and "bool si_invalid" not in s for s in src.values())
-    assert "case SI_DET_INVALID:" in src["detect_kernels.hip"] and "rf_cut_tile<T, true>" in src["rate_feed_kernels.hip"] and "rf_pair_tile<T, false>" in src["rate_feed_kernels.hip"]
+    assert "case SI_DET_INVALID:" in src["detect_kernels.hip"] and "rf_cut_tile<T, CLEAN>" in src["rate_feed_kernels.hip"] and "rf_pair_tile<T, CLEAN>" in src["rate_feed_kernels.hip"]
+    assert src["rate_feed_kernels.hip"].count("si_with_flag(ceiling != nullptr, [&](auto clean)") == 2 and "cut_clips_kernel<decltype(clean)::value>" in src["patch_kernels.hip"]
     if os.path.exists(native.LIB_PATH):
         lib = native.load_library()
         assert lib.si_version() == 3

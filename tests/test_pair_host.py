@@ -87,7 +87,7 @@ def test_header_declares_the_entries_the_mirror_calls():
     block = hdr[hdr.index("DESIGN.md 4.26"):hdr.index("int si_cut_pair(")]
     assert "I_ea/predict.py:79-80" in block and "SI_EINVAL before any launch" in block
     src = open(os.path.join(ROOT, "speech_inpainting_amd", "csrc", "rate_feed_kernels.hip")).read()
-    assert "cut_pair_kernel" in src and "cut_pair_ch_kernel" in src and "RF_PAIR_FRAMES" in src
+    assert "cut_pair_kernel<T, decltype(inter)::value, decltype(clean)::value>" in src and "si_with_flag(ch > 0, [&](auto inter)" in src and "RF_PAIR_FRAMES" in src
 
 
 # ------------------------------------------------------------------------------------------------------------ predict.yaml
