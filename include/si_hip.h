@@ -63,8 +63,17 @@
  *
  * Conventions: plain C types only; every function returns 0 on success and a negative SI_E* code on
  * failure (message via si_last_error); no exceptions cross the boundary.  A context is bound to one device,
- * is not thread-safe, enqueues all work on the caller's HIP stream and never synchronises it.  All data
- * pointers are DEVICE pointers owned by the caller unless the parameter says "host".
+ * is not thread-safe and enqueues all work on the caller's HIP stream: every kernel, memset and copy of a call that takes a
+ * si_stream_t is ordered on that stream and on no other (a context is driven from one stream at a time).  A call does not wait
+ * for the stream, with three exceptions (tests/test_gpu_side_stream.py holds every entry point to this behind a delayed stream):
+ *   - growth of library-owned scratch: the call of si_kmeans_assign or of a detector (si_quiet_runs .. si_impulse_runs) whose K or
+ *     n no longer fits the scratch the context holds synchronises the stream before it frees the old block; the next call of
+ *     that size does not;
+ *   - reuse of a pinned slot: the ragged passes (sample_len / mel_len as a HOST array) upload their length table through 4 pinned
+ *     slots in turn; the fifth such call waits until the copy that the first one queued has left its slot;
+ *   - calls documented to wait or to return host values: si_profile_stop, si_weights_check, si_load_weights, si_destroy, and the
+ *     first mel front-end call of a context, which uploads its tables.
+ * All data pointers are DEVICE pointers owned by the caller unless the parameter says "host".
  * Activations are fp32.  Layouts are the reference's: wave (B, N); feats (B, T, D); mel (B, D, Tm)
  * channels-first; waveform (B, Tm' * hop).
  */

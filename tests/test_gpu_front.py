@@ -11,6 +11,7 @@ import torch
 
 from tests.front_ref import assert_same, reference_result
 from tests.harness import build_engine
+from tests.side_stream import _delay_cycles
 
 pytestmark = pytest.mark.gpu
 
@@ -128,26 +129,6 @@ def test_front_while_every_slot_buffer_grows(depth):
 
 
 # ------------------------------------------------------------------------------------------------------------ 3: stream order
-def _delay_cycles(target_ms=100.0):
-    """Cycle count for torch.cuda._sleep that lasts about `target_ms`, from probes timed with two events (the counter's rate is the device's own)."""
-    def timed(c):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        torch.cuda._sleep(int(c))
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b)
-    timed(1000)                                                                     # the first launch loads the kernel
-    c, ms = 250000, 0.0
-    while ms < 5.0 and c < 10 ** 10:                                                # a probe of 5 .. 20 ms: long enough to time
-        c *= 4
-        ms = timed(c)
-        assert ms < 250.0, (c, ms)
-    assert ms >= 5.0, (c, ms)
-    return int(c * target_ms / ms)
-
-
 def _probe(front, rq, numel, dtype, which):
     """A tensor of the compute stream (`numel` of `dtype`: exactly what the slot's device buffer `which` will take) is filled, a
     bounded delay and a copy of it are queued behind, and it is freed ON THE HOST while both are still queued; then the request is
