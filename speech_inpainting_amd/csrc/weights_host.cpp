@@ -71,6 +71,18 @@ int check_desc(const si_model_desc* d, Err e) {
         if (!in_range(d->conv_kernel[i], 1, 1024)) return fail(e, SI_EINVAL, "conv_kernel[%d]=%d out of range 1..1024", i, d->conv_kernel[i]);
         if (!in_range(d->conv_stride[i], 1, 1024)) return fail(e, SI_EINVAL, "conv_stride[%d]=%d out of range 1..1024", i, d->conv_stride[i]);
     }
+    // Widths that pass the ranges above and that a kernel of the first forward refuses (the launchers keep their own checks):
+    // the waveform conv is written for HuBERT's 10 taps and 4 * 2^j channels (conv0_check), a LayerNorm row lives in 8 registers
+    // of 256 lanes (si_launch_layernorm).
+    if (d->conv_kernel[0] != 10) return fail(e, SI_EINVAL, "conv_kernel[0]=%d: the waveform conv kernel is written for 10 taps", d->conv_kernel[0]);
+    if (d->conv_dim[0] > 1024 || (d->conv_dim[0] & (d->conv_dim[0] - 1)))
+        return fail(e, SI_EINVAL, "conv_dim[0]=%d: the waveform conv kernel needs 4 * 2^j channels, at most 1024", d->conv_dim[0]);
+    if (d->hidden_size > SI_LN_MAX_WIDTH) return fail(e, SI_EINVAL, "hidden_size=%d: a LayerNorm row is at most %d wide", d->hidden_size, SI_LN_MAX_WIDTH);
+    for (int i = 0; i < d->num_conv; ++i) {
+        const bool normed = d->feat_norm_layer || (i == d->num_conv - 1 && d->feat_proj_layer_norm);
+        if (normed && d->conv_dim[i] > SI_LN_MAX_WIDTH)
+            return fail(e, SI_EINVAL, "conv_dim[%d]=%d: a LayerNorm row is at most %d wide", i, d->conv_dim[i], SI_LN_MAX_WIDTH);
+    }
     if (!(std::isfinite(d->layer_norm_eps) && d->layer_norm_eps > 0.f))
         return fail(e, SI_EINVAL, "layer_norm_eps=%g must be finite and > 0", (double)d->layer_norm_eps);
     if (!in_range(d->codebook_dim, 1, 128)) return fail(e, SI_EINVAL, "codebook_dim=%d out of range 1..128 (codebook unsupported)", d->codebook_dim);
@@ -90,6 +102,9 @@ int check_desc(const si_model_desc* d, Err e) {
         if (hop > 65536) return fail(e, SI_EINVAL, "up_rates[%d]=%d: the product of the rates up to here is %ld, above 65536", i, d->up_rates[i], hop);
     }
     if (c % 4) return fail(e, SI_EINVAL, "up_initial_channel=%d: final generator width %d must be a multiple of 4", d->up_initial_channel, c);
+    // conv_post_kernel keeps 256 + 6 rows of c + 4 floats and its 7 taps of c weights in LDS (si_launch_conv_post)
+    if (((size_t)(256 + 6) * (c + 4) + (size_t)7 * c) * 4 > SI_POST_MAX_LDS)
+        return fail(e, SI_EINVAL, "up_initial_channel=%d: final generator width %d is more than conv_post holds in LDS (at most 148 channels)", d->up_initial_channel, c);
     for (int j = 0; j < d->num_rb; ++j) {
         if (!in_range(d->rb_kernels[j], 1, 255) || d->rb_kernels[j] % 2 == 0)
             return fail(e, SI_EINVAL, "rb_kernels[%d]=%d: resblock kernel must be odd in 1..255", j, d->rb_kernels[j]);

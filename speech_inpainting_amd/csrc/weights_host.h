@@ -20,8 +20,17 @@
 // The largest plan inside these bounds is below 2^37 bytes; every product that forms it is taken in size_t.
 // The flags (conv_bias, feat_norm_layer, stable_layer_norm, feat_proj_layer_norm) are read as booleans and vocoder_chunk <= 0
 // means the library default, so every value of those is legal.  Only the USED elements of the arrays are looked at.
+// Inside those ranges check_desc also refuses the widths a dedicated kernel of the first forward would refuse (what is left to the
+// first forward: a tap-GEMM tile past its prefetch registers or LDS -- strides, kernels or (k - 1) * dilation in the hundreds):
+//   conv_kernel[0]     10 (the waveform conv)                    conv_dim[0]       a power of two, <= 1024 (4 * 2^j)
+//   hidden_size, every LayerNormed conv_dim[i] (all of them in the layer flavour, the last one under feat_proj_layer_norm)  <= SI_LN_MAX_WIDTH
+//   up_initial_channel >> num_ups (conv_post's input width)      <= 148: 262 rows of width + 4 floats and 7 width weights in SI_POST_MAX_LDS
+// (num_mels needs no such rule: conv_pre's input rows are padded to a multiple of 32 channels, mel_ld.)
 #ifndef SI_WEIGHTS_HOST_H
 #define SI_WEIGHTS_HOST_H
+
+#define SI_LN_MAX_WIDTH 2048            /* si_launch_layernorm: 8 registers x 256 lanes */
+#define SI_POST_MAX_LDS (160 * 1024)    /* si_launch_conv_post: bytes of LDS a workgroup may have */
 
 #include <stddef.h>
 #include <stdint.h>

@@ -89,7 +89,7 @@ _ENC_STATES = {}
 
 def _enc_state(harch):
     from speech_inpainting_amd import synth
-    key = (harch.hidden_size, harch.feat_extract_norm, harch.do_stable_layer_norm, harch.feat_proj_layer_norm)
+    key = repr(harch)                                  # the whole architecture: two of one width may differ in any other shape
     if key not in _ENC_STATES:
         _ENC_STATES[key] = synth.synth_hubert_state(harch, 31)
     return _ENC_STATES[key]

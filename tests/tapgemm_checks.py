@@ -100,19 +100,21 @@ def _verify(varch, mode, mel, lens, taps, prof, tag, summary, clips=None, wave=N
             U = taps[f"ups{i}"][b, :Lo]
             _one(summary, f"{tag} ups{i} {Cin}->{C} u={u} k={k}", kern, b, U, r, bm * u, k)
             L, Lm = Lo, Lmo
-            kern, bm = _config(math, C, Lm, 3, 1, C)               # (k and the dilation never change the tile here: 255 + 10 * 5 + 1 <= 384 rows)
-            want.add(kern)
             xs_prev = None
             for j, (rk, dils) in enumerate(zip(varch.resblock_kernel_sizes, varch.resblock_dilation_sizes)):
-                assert _config(math, C, Lm, rk, max(dils), C)[0] == kern
                 p = f"resblocks.{i * nk + j}."
                 xin = U
                 for n, d in enumerate(dils):
                     last = n == len(dils) - 1
+                    # (the dilated conv's halo decides its tile: up to V1's 255 + 10 * 5 + 1 <= 384 rows it never changes it)
+                    kern, bm = _config(math, C, Lm, rk, d, C)
+                    want.add(kern)
                     t = taps[f"stage{i}.rb{j}.t{n}"][b, :L]
                     r = V.tapgemm_ref(xin, _w(varch, f"{p}convs1.{n}"), sd[f"{p}convs1.{n}.bias"], math, V.conv_geom(d), rk * C, slope=V.SLOPE32)
                     _one(summary, f"{tag} stage{i}.rb{j}.t{n} k={rk} d={d}", kern, b, t, r, bm, (rk - 1) * d)
                     prev = xs_prev if (last and j > 0) else None
+                    kern, bm = _config(math, C, Lm, rk, 1, C)
+                    want.add(kern)
                     r = V.tapgemm_ref(t, _w(varch, f"{p}convs2.{n}"), sd[f"{p}convs2.{n}.bias"], math, V.conv_geom(1), rk * C, slope=V.SLOPE32,
                                       res=xin, alpha=a_last if last else 1.0, prev=prev)
                     out = taps[f"stage{i}.rb{j}.p{n}"][b, :L]

@@ -27,9 +27,11 @@ import pytest
 import torch
 
 from tests import vocoder_ref as V
-from tests.cases import R1, _arch, _interleave, _mel, _pair_lengths
+from tests.cases import R1, _arch, _mel, _pair_lengths
 from tests.harness import RatioSummary
 from tests.vocoder_checks import _engine, _run
+from tests.vocoder_checks import _ragged as _ragged_into
+from tests.vocoder_checks import _uniform as _uniform_into
 from tests.vocoder_checks import _verify as _verify_into
 
 pytestmark = pytest.mark.gpu
@@ -41,24 +43,12 @@ def _verify(*args, summary=SUMMARY, **kw):
     return _verify_into(*args, summary=summary, **kw)
 
 
-def _ragged(eng, varch, lengths, seed, tag, **kw):
-    lens = lengths if isinstance(lengths, list) else _interleave(lengths)          # (a list: the batch as given)
-    assert len(lens) <= 32
-    mel = _mel(len(lens), max(lens), seed, varch.num_mels)
-    taps, wave, prof = _run(eng, varch, mel, lens)
-    _verify(varch, mel, lens, taps, wave, prof, f"{tag} ragged", **kw)
-    return prof
+def _ragged(*args, summary=SUMMARY, **kw):
+    return _ragged_into(*args, summary=summary, **kw)
 
 
-def _uniform(eng, varch, L, seed, tag, **kw):
-    one = _mel(1, L, seed, varch.num_mels)
-    mel = torch.cat([one, one]).contiguous()
-    taps, wave, prof = _run(eng, varch, mel)
-    _verify(varch, mel, None, taps, wave, prof, f"{tag} uniform L={L}", clips=[0], **kw)
-    for k, t in taps.items():
-        assert torch.equal(t[0], t[1]), f"{tag} uniform L={L}: {k} differs between two copies of one clip"
-    assert torch.equal(wave[0], wave[1])
-    return prof
+def _uniform(*args, summary=SUMMARY, **kw):
+    return _uniform_into(*args, summary=summary, **kw)
 
 
 @pytest.mark.parametrize("C", [32, 64, 128, 256])

@@ -276,13 +276,46 @@ def test_the_probed_descriptors_are_refused():
         _refused(d, field)
 
 
+def test_widths_a_kernel_of_the_first_forward_refuses_are_refused_at_load():
+    """Descriptors inside every range that conv0_check, si_launch_layernorm or si_launch_conv_post would refuse in the first pass: each
+    names its field; the neighbour on the accepted side of each rule plans."""
+    def enc(**kw):
+        return native.make_desc(HubertArch.tiny(**kw), VocoderArch.tiny(), 100, "fp32", "fp32")
+
+    def gen(**kw):
+        return native.make_desc(HubertArch.tiny(), VocoderArch(**kw), 100, "fp32", "fp16")
+    k7 = (10, 3, 3, 3, 3, 2, 2)
+    wide = dict(hidden_size=2112, num_attention_heads=33)
+    one = dict(upsample_rates=(1,), upsample_kernel_sizes=(3,))
+    refused = [("conv_kernel[0]", enc(conv_kernel=(8,) + k7[1:])), ("conv_kernel[0]", enc(conv_kernel=(11,) + k7[1:])),
+               ("conv_dim[0]", enc(conv_dim=(48,) + (32,) * 6)), ("conv_dim[0]", enc(conv_dim=(2048,) + (32,) * 6)),
+               ("conv_dim[0]", enc(conv_dim=(1040,) + (32,) * 6, feat_extract_norm="layer")),
+               ("hidden_size", enc(**wide)), ("hidden_size", enc(do_stable_layer_norm=True, **wide)),
+               ("conv_dim[3]", enc(conv_dim=(32, 32, 32, 2064, 32, 32, 32), feat_extract_norm="layer")),
+               ("conv_dim[6]", enc(conv_dim=(32,) * 6 + (2064,))),
+               ("final generator width 256", gen(upsample_initial_channel=512, **one)),
+               ("final generator width 160", gen(upsample_initial_channel=320, **one))]
+    for field, d in refused:
+        _refused(d, field)
+    accepted = [enc(conv_dim=(1024,) + (32,) * 6), enc(conv_dim=(16,) + (32,) * 6), enc(hidden_size=2048, num_attention_heads=32),
+                enc(conv_dim=(32, 32, 32, 2048, 32, 32, 32), feat_extract_norm="layer"),
+                enc(conv_dim=(32, 32, 32, 2064, 32, 32, 32)),                       # group flavour: only the last width is LayerNormed
+                enc(conv_dim=(32,) * 6 + (2064,), feat_proj_layer_norm=False), enc(conv_dim=(32,) * 6 + (2048,)),
+                gen(upsample_initial_channel=288, **one),                           # 144 wide at the end: the widest multiple of 16 under 148
+                gen(num_mels=1, upsample_initial_channel=64, **one), gen(num_mels=81, upsample_initial_channel=64, **one)]                  # conv_pre's rows are padded to 32 / 96 channels
+    for d in accepted:
+        rc, total, msg = native.plan_weights(d)
+        assert rc == 0 and total > 0, msg
+
+
 def test_bounds_leave_the_real_models_a_wide_margin():
     for harch, varch, K in ((HubertArch.base(), VocoderArch.v1(), 100), (HubertArch.large(), VocoderArch.v1(), 500), (HubertArch.base(), VocoderArch.v3(), 100),
                             (HubertArch.large(), unit_arch(), 500)):
         d = native.make_desc(harch, varch, K, "bf16", "fp16")
         rc, total, msg = native.plan_weights(d)
         assert rc == 0 and 0 < total < 2 ** 32, msg
-        for field, factor in (("hidden_size", 4), ("intermediate_size", 4), ("num_layers", 2), ("num_clusters", 100), ("up_initial_channel", 4), ("num_mels", 8)):
+        # (hidden_size: twice HuBERT-large is the widest LayerNorm row, SI_LN_MAX_WIDTH; beyond it the first forward used to fail)
+        for field, factor in (("hidden_size", 2), ("intermediate_size", 4), ("num_layers", 2), ("num_clusters", 100), ("up_initial_channel", 4), ("num_mels", 8)):
             d = native.make_desc(harch, varch, K, "bf16", "fp16")
             setattr(d, field, getattr(d, field) * factor)
             if field == "hidden_size":
